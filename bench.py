@@ -4,6 +4,7 @@
 of 50 brokers), at 1/2/4/8 GPUs.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's results as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -97,6 +98,46 @@ def emit(out):
     assert len(line) < FINAL_LINE_LIMIT, len(line)
     sys.stdout.flush()
     print(line, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, keys, results, world):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float64/float32 .npy files under d --
+    the packed best key of every topic, decoded (violation, objective, restart[, rank]; keys None: none), and rank 0's
+    per-topic results (objective, certificate, violation counts, assignment).  Assignments of all topics are concatenated
+    (row-major, partition x slot; 65535 = empty slot); past DUMP_LIMIT_BYTES a fixed, seeded sample of them is written."""
+    import numpy as np
+    from kafka_assignment_optimizer_amd import multigpu
+
+    os.makedirs(d, exist_ok=True)
+    arrays = {}
+    if keys is not None:
+        keys = keys.cpu().numpy() if hasattr(keys, "cpu") else np.asarray(keys)
+        if world > 1:
+            fields = np.array([multigpu.unpack_allreduced(k) for k in keys.astype(np.int64)], dtype=np.float64).reshape(-1, 4)
+            names = ("best_violation", "best_objective", "best_restart", "best_rank")
+        else:
+            k = keys.astype(np.uint64)
+            fields = np.stack([k >> np.uint64(44), np.uint64(0xFFFFFF) - ((k >> np.uint64(20)) & np.uint64(0xFFFFFF)),
+                               k & np.uint64(0xFFFFF)], axis=1).astype(np.float64)
+            names = ("best_violation", "best_objective", "best_restart")
+        arrays.update((n, fields[:, i]) for i, n in enumerate(names))
+    arrays["objective"] = np.array([r.objective for r in results], dtype=np.float64)
+    arrays["upper_bound"] = np.array([r.upper_bound for r in results], dtype=np.float64)
+    arrays["violations"] = np.stack([np.asarray(r.violations, dtype=np.float64) for r in results])
+    arrays["assignment_shape"] = np.array([r.assignment.shape for r in results], dtype=np.float64)
+    assign = np.concatenate([r.assignment.reshape(-1) for r in results]).astype(np.float32)
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())
+    if assign.nbytes > room:   # a sampled slot costs 4 B of value + 8 B of index
+        idx = np.sort(np.random.default_rng(0).choice(assign.size, size=room // 12, replace=False))
+        arrays["assignment_sample_index"] = idx.astype(np.float64)
+        assign = assign[idx]
+    arrays["assignment"] = assign
+    for n, a in arrays.items():
+        np.save(os.path.join(d, n + ".npy"), a)
+    return sorted(arrays)
 
 
 def host_cores() -> int:
@@ -297,7 +338,11 @@ def main():
                     help="ONE process, --gpus devices, through kao_solve_multi (what kao-cli --gpus N ships: topics dealt LPT, RCCL only "
                          "when topics < devices) instead of one process per GPU; not the driver's launch mode")
     ap.add_argument("--devices", type=str, default="", help="--in-library: device list (csv; repeats = logical shards on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -354,6 +399,8 @@ def main():
                 done.append((sum(r.status == "OPTIMAL_PROVEN" for r in rs), tm["delta_candidates"], tm["launches"], tm["elite_exchanges"]))
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, None, rs, 1)
         cand = sum(d[1] for d in done)
         print(json.dumps({"metric": "candidate assignments/sec (+ time_to_optimal_s), 10k-partition reassign", "value": cand / dt,
                           "unit": "candidates/s", "n_gpus": len(devices), "steps": args.steps, "warmup": args.warmup,
@@ -405,7 +452,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.warmup, n_batches):
-        one_step(sessions[i])
+        last_keys = one_step(sessions[i])
     barrier()
     dt = time.perf_counter() - t0
     timed = sessions[args.warmup:]
@@ -437,6 +484,8 @@ def main():
         n_res += len(res)
         feasible += sum(1 for r in res if r.violations[0] == 0 and r.objective >= 0)
         obj_after_step.append(sum(int(r.objective) for r in res))
+    if args.dump_outputs and rank == 0:   # before the steady-state launches below search the last batch further
+        dump_outputs(args.dump_outputs, last_keys, res, world)
 
     out_extra = {}
     if not args.no_extras:
