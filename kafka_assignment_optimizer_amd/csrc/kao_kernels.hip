@@ -226,10 +226,13 @@ __device__ __forceinline__ uint32_t band_fields(const TopicRegs &T, uint32_t c) 
     return band_entry((int)(c & 0xFFFFu), T.rep_lo, T.rep_hi) | (band_entry((int)(c >> 16), T.lead_lo, T.lead_hi) << 6);
 }
 constexpr uint32_t kWNoCand = 0x8000u;
+// Bit 14: no candidate for the SECOND slot of a fused two-slot REPLACE scan (search_body), which marks the brokers of its two partitions
+// at once, each slot with its own bit.  Padding indices carry both bits.
+constexpr uint32_t kWNoCand2 = 0x4000u;
 // W[x] for every index of the topic (XR: rack of x, `inv` = padding)
 // (`lane`, `stride`: a wavefront strides by 64; the wavefronts of a team stride together by the workgroup size)
 template <int NW> __device__ __forceinline__ void rebuild_band_state(const TopicRegs &T, const WaveLds<NW> &L, const uint8_t *XR, uint32_t inv, int lane, int stride = 64) {
-    for (int x = lane; x < ((T.Bx + 63) & ~63); x += stride) L.W[x] = (uint16_t)(XR[x] == inv ? kWNoCand : band_fields(T, L.C[x]));
+    for (int x = lane; x < ((T.Bx + 63) & ~63); x += stride) L.W[x] = (uint16_t)(XR[x] == inv ? (kWNoCand | kWNoCand2) : band_fields(T, L.C[x]));
 }
 
 // rebuild C and K from A (lanes stride partitions; LDS atomics)
@@ -551,6 +554,13 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
         n_iters = __builtin_amdgcn_readfirstlane(v2); it_base = __builtin_amdgcn_readfirstlane(v3);
         scan_two = __builtin_amdgcn_readfirstlane(v4);
     }
+    // Fused two-slot REPLACE scan (LDS-resident, unpriced, one chunk of at most 256 rounds): slot 2's draw of round rd is the generator
+    // state n_rd steps after slot 1's, s' = A_n s + C_n (mod 2^24) -- the jump-ahead of lcg24 over n_rd = rounds of the topic's scan
+    constexpr bool kFuse = !kGlobalA && !kTeam && !kPriced;
+    const bool fuse_ok = kFuse && T.Bx <= 16384;
+    uint32_t jmp_a = 1u, jmp_c = 0u;
+    if (fuse_ok)
+        for (int n = (T.Bx + 63) >> 6; n > 0; --n) { jmp_a = (jmp_a * 0x6D2B79u) & 0xFFFFFFu; jmp_c = (jmp_c * 0x6D2B79u + 0x3C6EF3u) & 0xFFFFFFu; }
     for (uint32_t i = 0; i < n_iters; ++i) {
         const uint32_t it = it_base + i;
         const int type = (int)((0x1210u >> ((it & 7u) * 2u)) & 3u);  // pattern R R X R L R X R
@@ -782,6 +792,110 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 const uint32_t k2 = wave_umin(lane == wA1 ? kKeyNull : keyA);
                 wA2 = k2 == kKeyNull ? -1 : (int)(k2 & 63u);   // (no other lane takes part: one slot)
             }
+            if (kFuse && type == 0 && wA2 >= 0 && fuse_ok) {
+                // ---- phase B (REPLACE), both tournament slots in ONE pass over the brokers (round 7).  The two slots score the same
+                //      brokers from the same W / XR words: each round loads them once and forms both slots' keys, two running minima.
+                //      Per slot everything is as in the one-slot scan below: its own RT half (the rack part of the delta, packed in the
+                //      two 16-bit halves of RT), its own no-candidate bit in W (slot 1: bit 15, slot 2: bit 14), its own weighted rounds
+                //      (the union of both slots' rounds is scored with weights: a slot's weights are zero on brokers outside its
+                //      current replicas), its own draw sequence (slot 2's round rd: jump-ahead of slot 1's draw by n_rd steps).  The
+                //      move is that of the slot with the strictly lower wave minimum (ties: slot 1), recomputed once.
+                int ps[2], ks[2], gs[2], dvos[2];
+                uint32_t us[2];
+                int v_rk[2];
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const int wA = s2 == 0 ? wA1 : wA2;
+                    ps[s2] = __builtin_amdgcn_readlane(pl_, wA);
+                    ks[s2] = __builtin_amdgcn_readlane(kl_, wA);
+                    us[s2] = (uint32_t)__builtin_amdgcn_readlane((int)oldw_l, wA);
+                    gs[s2] = __builtin_amdgcn_readlane(g_old_l, wA);
+                    dvos[s2] = __builtin_amdgcn_readlane(dvo_l, wA);
+                    v_rk[s2] = __builtin_amdgcn_readlane(dvr_l, wA);
+                }
+                const Part<NW> a1 = L.A[ps[0]], c1 = CUR[ps[0]], a2 = L.A[ps[1]], c2 = CUR[ps[1]];
+                const uint32_t ro1 = us[0] >> 16, ro2 = us[1] >> 16;
+                for (int r = lane; r < T.R; r += 64) {
+                    const int dk = dinc(L.K[r], T.rack_lo, T.rack_hi);
+                    const int v1 = ((uint32_t)r != ro1) ? v_rk[0] + dk + dinc(cnt4(a1, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
+                    const int v2 = ((uint32_t)r != ro2) ? v_rk[1] + dk + dinc(cnt4(a2, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
+                    L.RT[r] = (int)(((uint32_t)v1 & 0xFFFFu) | ((uint32_t)v2 << 16));
+                }
+                // lanes 0..NW-1 look after slot 1's partition, lanes NW..2NW-1 after slot 2's: their brokers are marked (a broker in
+                // both partitions gets both bits from both lanes: same value, same restore), their displaced current replicas listed
+                const int li = lane & (NW - 1);
+                const bool l2 = lane >= NW;
+                const uint32_t ai = l2 ? sel4(a2, li) : sel4(a1, li), ci = l2 ? sel4(c2, li) : sel4(c1, li);
+                const bool holds = (lane < 2 * NW) & (ai != kNoneW);
+                uint32_t w_keep = 0;
+                if (holds) w_keep = L.W[ai & 0xFFFFu];
+                if (holds) L.W[ai & 0xFFFFu] = (uint16_t)(w_keep | (in4(a1, ai) ? kWNoCand : 0u) | (in4(a2, ai) ? kWNoCand2 : 0u));
+                const bool hm_l = (lane < 2 * NW) & (ci != kNoneW) & !(l2 ? in4(a2, ci) : in4(a1, ci));
+                const int mr_l = hm_l ? (int)((ci & 0xFFFFu) >> 6) : -1;
+                int mr[2 * NW];
+#pragma unroll
+                for (int i2 = 0; i2 < 2 * NW; ++i2) mr[i2] = __builtin_amdgcn_readlane(mr_l, i2);
+                const bool lead1 = ks[0] == 0, lead2 = ks[1] == 0;
+                const uint32_t lw1 = lead1 ? 2u : 0u, lw2 = lead2 ? 2u : 0u;
+                const int wl1 = lead1 ? T.w00 : T.w01, wf1 = lead1 ? T.w10 : T.w11, wl2 = lead2 ? T.w00 : T.w01, wf2 = lead2 ? T.w10 : T.w11;
+                const int K01 = __mul24(S, gs[0]) + kDBias + __mul24(lam, dvos[0]);
+                const int K02 = __mul24(S, gs[1]) + kDBias + __mul24(lam, dvos[1]);
+                uint32_t jc = jmp_c;
+                asm volatile("" : "+v"(jc));
+                uint32_t best1 = kKeyNull, best2 = kKeyNull;   // (cost + bias) << 16 | tie << 8 | round, per slot
+                auto scan_round2 = [&](auto with_w, int base, int rd) {
+                    const uint32_t st1 = lcg24(rng);
+                    uint32_t st2;
+                    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(st2) : "v"(st1), "s"(jmp_a), "v"(jc));
+                    const int w = (int)(short)L.W[base + lane];   // sign-extended: bit 15 fills the upper half
+                    const int rt = L.RT[XR[base + lane]];
+                    const int inc = wfld(w, kWIncR);
+                    int d1 = __mul24(lam, inc + wfldw(w, kWIncL, lw1) + wfldw(rt, 0, 16u)) + K01;
+                    int d2 = __mul24(lam, inc + wfldw(w, kWIncL, lw2) + (rt >> 16)) + K02;
+                    if (decltype(with_w)::value) {
+                        const uint32_t x = (uint32_t)(base + lane);
+                        const uint32_t xw = x | ((uint32_t)XR[x] << 16);
+                        d1 -= __mul24(S, role_w2(c1, xw, wl1, wf1));
+                        d2 -= __mul24(S, role_w2(c2, xw, wl2, wf2));
+                    }
+                    d1 = min(max(d1, 0), 2 * kDBias - 2);
+                    d2 = min(max(d2, 0), 2 * kDBias - 2);
+                    best1 = min(best1, ((uint32_t)d1 << 16) | (st1 & 0xFF00u) | (uint32_t)rd | ((uint32_t)w & 0xFFFF0000u));
+                    best2 = min(best2, ((uint32_t)d2 << 16) | (st2 & 0xFF00u) | (uint32_t)rd | ((uint32_t)wflag(w, 14) & 0xFFFF0000u));
+                };
+                const int n_rd = (T.Bx + 63) >> 6;
+                int rd = 0, base = 0;
+                while (rd < n_rd) {
+                    int nxt = n_rd;   // the next round with a displaced current replica of either slot
+#pragma unroll
+                    for (int i2 = 0; i2 < 2 * NW; ++i2)
+                        if (mr[i2] >= rd) nxt = min(nxt, mr[i2]);
+                    for (; rd < nxt; ++rd, base += 64) scan_round2(std::false_type{}, base, rd);
+                    if (rd < n_rd) { scan_round2(std::true_type{}, base, rd); ++rd; base += 64; }
+                }
+                asm("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(rng) : "s"(jmp_a), "v"(jc));   // state after both slots' 2 n_rd draws
+                if (holds) L.W[ai & 0xFFFFu] = (uint16_t)w_keep;
+                const uint32_t key1 = best1 >> 8, key2 = best2 >> 8;
+                const uint32_t kmin1 = wave_umin(key1), kmin2 = wave_umin(key2);
+                const bool two = kmin2 < kmin1;   // wave-uniform; ties stay with slot 1
+                kmin = two ? kmin2 : kmin1;
+                win = __ffsll((long long)__ballot((two ? key2 : key1) == kmin)) - 1;   // ties inside the wave go to the lowest lane
+                p = two ? ps[1] : ps[0]; k = two ? ks[1] : ks[0]; uw = two ? us[1] : us[0];
+                if ((int)(kmin >> 8) - kDBias <= 0) {   // will be accepted: the winner's move, wave-uniform
+                    const bool lead = k == 0;
+                    const uint32_t bw_ = (uint32_t)__builtin_amdgcn_readlane((int)(two ? best2 : best1), win);
+                    const uint32_t xs = ((bw_ & 255u) << 6) + (uint32_t)win;
+                    const uint32_t rs = XR[xs];
+                    const uint32_t ws = L.W[xs];
+                    const int rts = L.RT[rs];
+                    vw = xs | (rs << 16);
+                    dV = wfld(ws, kWIncR) + wfldw(ws, kWIncL, lead ? 2u : 0u) + (two ? dvos[1] : dvos[0]) + (two ? (rts >> 16) : wfldw(rts, 0, 16u));
+                    bool has_missing = false;
+#pragma unroll
+                    for (int i2 = 0; i2 < NW; ++i2) has_missing |= (two ? mr[NW + i2] : mr[i2]) >= 0;
+                    dObj = -(two ? gs[1] : gs[0]) + (has_missing ? (two ? role_w2(c2, vw, wl2, wf2) : role_w2(c1, vw, wl1, wf1)) : 0);
+                }
+            } else {
             uint32_t b_kmin = kKeyNull, b_uw = 0, b_vw = 0;
             int b_win = 0, b_p = 0, b_k = 0, b_dV = 0, b_dObj = 0;
 #pragma nounroll
@@ -1029,6 +1143,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
             }
             }   // (the two scan slots)
             if (type == 0) { kmin = b_kmin; win = b_win; p = b_p; k = b_k; uw = b_uw; vw = b_vw; dV = b_dV; dObj = b_dObj; }
+            }   // (one slot at a time)
         }
         if (!kTeam) {
             if (kmin == kKeyNull) continue;

@@ -117,5 +117,11 @@ int main() {
     run<0>("v_add_u32, 1 wave per SIMD", d_out, 256, 256);
     run<8>("CONTROL v_fma_f32, 2 waves per SIMD", d_out, 512, 256);
     run<0>("v_add_u32, 2 waves per SIMD", d_out, 512, 256);
+    // the occupancies k_search runs at (4 and 6 waves per SIMD): is the 4-cycle figure a property of the instruction or of the wave count?
+    run<0>("v_add_u32, 4 waves per SIMD", d_out, 1024, 256);
+    run<0>("v_add_u32, 6 waves per SIMD", d_out, 1536, 256);
+    run<2>("v_mad_u32_u24, 1 wave per SIMD", d_out, 256, 256);
+    run<2>("v_mad_u32_u24, 4 waves per SIMD", d_out, 1024, 256);
+    run<2>("v_mad_u32_u24, 6 waves per SIMD", d_out, 1536, 256);
     return 0;
 }
