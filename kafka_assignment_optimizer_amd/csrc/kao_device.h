@@ -8,20 +8,20 @@ namespace kao {
 
 // Wavefront min (all 64 lanes active): butterfly inside each row of 16 with four fused v_min_u32_dpp
 // (quad_perm xor1, xor2, row_half_mirror, row_mirror; hipcc emits mov_dpp + min pairs for the builtin form),
-// then the four row minima are read with v_readlane and combined on the scalar unit.  Result is wave-uniform.
+// then the row minima are carried across rows: row_bcast:15 folds lane 15 / 47 into rows 1 / 3, row_bcast:31 folds
+// lane 31 into rows 2 / 3, so lane 63 holds the minimum of the wavefront and one v_readlane makes it wave-uniform
+// (reading the four row minima took four v_readlane and a vector min3 on top).
 // s_nop 1 = the 2 wait states a DPP read needs after the VALU write of its source.
 __device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
     asm("s_nop 1\n\tv_min_u32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
         "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
         "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
         "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\tv_min_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
         "s_nop 1"
         : "+v"(v));
-    uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-    uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-    uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
-    uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-    return min(min(a, b), min(c, d));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 // Wavefront sum, same structure with fused v_add_u32_dpp.
 __device__ __forceinline__ int wave_sum(int v) {

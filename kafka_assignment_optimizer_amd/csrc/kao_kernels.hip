@@ -821,16 +821,29 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int v2 = ((uint32_t)r != ro2) ? v_rk[1] + dk + dinc(cnt4(a2, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
                     L.RT[r] = (int)(((uint32_t)v1 & 0xFFFFu) | ((uint32_t)v2 << 16));
                 }
-                // lanes 0..NW-1 look after slot 1's partition, lanes NW..2NW-1 after slot 2's: their brokers are marked (a broker in
-                // both partitions gets both bits from both lanes: same value, same restore), their displaced current replicas listed
-                const int li = lane & (NW - 1);
-                const bool l2 = lane >= NW;
-                const uint32_t ai = l2 ? sel4(a2, li) : sel4(a1, li), ci = l2 ? sel4(c2, li) : sel4(c1, li);
-                const bool holds = (lane < 2 * NW) & (ai != kNoneW);
+                // lanes 0..NW-1 look after slot 1's partition, lanes NW..2NW-1 after slot 2's: their brokers are marked, their
+                // displaced current replicas listed.  (Each lane reads its own word.  The lane number goes through an empty asm: the
+                // lane masks derived from it are then one compare each here; hoisted out of the iteration loop they were spilled
+                // scalar pairs, two v_readlane restores per use.)
+                int lane_v = lane;
+                asm volatile("" : "+v"(lane_v));
+                const int li = lane_v & (NW - 1);
+                const bool l2 = lane_v >= NW;
+                const int p_l = l2 ? ps[1] : ps[0];
+                const uint32_t ai = reinterpret_cast<const uint32_t *>(&L.A[p_l])[li], ci = reinterpret_cast<const uint32_t *>(&CUR[p_l])[li];
+                const bool holds = (lane_v < 2 * NW) & (ai != kNoneW);
+                // (slot 1's lanes mark first, then slot 2's lanes read the word again and add their bit: a broker in both partitions
+                //  carries both bits without comparing every broker against the other partition's words; the restore writes the
+                //  word read before either mark, the same value from both lanes.  A current replica is in its slot's partition
+                //  exactly when the marks gave it that slot's bit.)
                 uint32_t w_keep = 0;
                 if (holds) w_keep = L.W[ai & 0xFFFFu];
-                if (holds) L.W[ai & 0xFFFFu] = (uint16_t)(w_keep | (in4(a1, ai) ? kWNoCand : 0u) | (in4(a2, ai) ? kWNoCand2 : 0u));
-                const bool hm_l = (lane < 2 * NW) & (ci != kNoneW) & !(l2 ? in4(a2, ci) : in4(a1, ci));
+                if (holds & !l2) L.W[ai & 0xFFFFu] = (uint16_t)(w_keep | kWNoCand);
+                if (holds & l2) L.W[ai & 0xFFFFu] = (uint16_t)(L.W[ai & 0xFFFFu] | kWNoCand2);
+                const bool hc = (lane_v < 2 * NW) & (ci != kNoneW);
+                uint32_t w_ci = 0;
+                if (hc) w_ci = L.W[ci & 0xFFFFu];
+                const bool hm_l = hc & ((w_ci & (l2 ? kWNoCand2 : kWNoCand)) == 0u);
                 const int mr_l = hm_l ? (int)((ci & 0xFFFFu) >> 6) : -1;
                 int mr[2 * NW];
 #pragma unroll
@@ -875,11 +888,12 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 }
                 asm("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(rng) : "s"(jmp_a), "v"(jc));   // state after both slots' 2 n_rd draws
                 if (holds) L.W[ai & 0xFFFFu] = (uint16_t)w_keep;
-                const uint32_t key1 = best1 >> 8, key2 = best2 >> 8;
-                const uint32_t kmin1 = wave_umin(key1), kmin2 = wave_umin(key2);
-                const bool two = kmin2 < kmin1;   // wave-uniform; ties stay with slot 1
-                kmin = two ? kmin2 : kmin1;
-                win = __ffsll((long long)__ballot((two ? key2 : key1) == kmin)) - 1;   // ties inside the wave go to the lowest lane
+                // one reduction picks slot and lane: key (24 bits: (cost + bias) << 8 | tie) << 7 | slot << 6 | lane.  Its minimum is the
+                // lowest key; ties go to slot 1, then to the lowest lane -- the rule of two minima, a compare and a ballot.
+                const uint32_t kw = wave_umin(min(((best1 >> 1) & ~127u) | (uint32_t)lane, ((best2 >> 1) & ~127u) | 64u | (uint32_t)lane));
+                const bool two = (kw & 64u) != 0u;   // wave-uniform
+                kmin = kw >> 7;
+                win = (int)(kw & 63u);
                 p = two ? ps[1] : ps[0]; k = two ? ks[1] : ks[0]; uw = two ? us[1] : us[0];
                 if ((int)(kmin >> 8) - kDBias <= 0) {   // will be accepted: the winner's move, wave-uniform
                     const bool lead = k == 0;
@@ -890,9 +904,10 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int rts = L.RT[rs];
                     vw = xs | (rs << 16);
                     dV = wfld(ws, kWIncR) + wfldw(ws, kWIncL, lead ? 2u : 0u) + (two ? dvos[1] : dvos[0]) + (two ? (rts >> 16) : wfldw(rts, 0, 16u));
-                    bool has_missing = false;
+                    int mx1 = -1, mx2 = -1;   // (each slot's own maximum, then a select: `two ? mr[NW + i2] : mr[i2]` became a dynamically indexed scratch array)
 #pragma unroll
-                    for (int i2 = 0; i2 < NW; ++i2) has_missing |= (two ? mr[NW + i2] : mr[i2]) >= 0;
+                    for (int i2 = 0; i2 < NW; ++i2) { mx1 = max(mx1, mr[i2]); mx2 = max(mx2, mr[NW + i2]); }
+                    const bool has_missing = (two ? mx2 : mx1) >= 0;
                     dObj = -(two ? gs[1] : gs[0]) + (has_missing ? (two ? role_w2(c2, vw, wl2, wf2) : role_w2(c1, vw, wl1, wf1)) : 0);
                 }
             } else {
