@@ -397,6 +397,24 @@ int kao_cycle_seeds(const kao_topic *t, const uint16_t *assignment, int32_t *tab
  * [2] edges, [3] pairs with no net replica effect and a positive gain.  Not used by kao_solve yet. */
 int kao_cycle_pair_edges(const kao_topic *t, const uint16_t *assignment, int32_t gmin, int32_t *cost, int64_t stats[4]);
 
+/* ---- Waves: a reassignment plan split for execution ---------------------------------------------
+ * Splits the partitions a plan changes into the fewest waves it finds such that no broker takes part in more than
+ * `max_per_broker` partition movements in one wave (Cruise Control's "concurrent partition movements per broker").  Rows of
+ * `width` (1..KAO_MAX_RF) broker indices per partition, padded with KAO_NONE, over ONE broker index covering the target brokers
+ * AND every broker of `current` (a decommissioned broker is still a copy source); partitions of all topics concatenated (the
+ * caps are cluster-wide).  Partition p is unchanged when current[p] == target[p] slot for slot: wave[p] = -1.  A changed p
+ * that adds no broker (leader order only, replicas removed) moves no data: wave 0, counted against no cap.  Otherwise its
+ * participants are the added brokers plus the copy source current[p][0] when that is not KAO_NONE (new followers fetch from
+ * the leader; the plan only names the preferred leader), and each wave holds at most max_per_broker partitions of any one
+ * participant.  Waves are numbered from 0; *n_waves = 0 when nothing changed.  *lower_bound = max over brokers of
+ * ceil(deg(b) / max_per_broker), deg(b) = moving partitions b takes part in (1 when only leader changes, 0 when nothing
+ * changed); *n_waves == *lower_bound proves the split optimal.  Balance bands are not enforced on the states between waves.
+ * The waves are the best of several first-fit orders run on the GPU; deterministic in (input, seed).  KAO_ERR_INVALID:
+ * max_per_broker < 1, width outside 1..KAO_MAX_RF, n_brokers outside 1..65534, a broker index >= n_brokers (other than
+ * KAO_NONE), a broker twice in one row, a target row without a broker. */
+int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
+                   int32_t max_per_broker, uint64_t seed, int32_t *wave /* [n_partitions] */, int32_t *n_waves, int32_t *lower_bound);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

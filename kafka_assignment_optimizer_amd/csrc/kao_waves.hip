@@ -1,0 +1,318 @@
+// kao_waves.hip -- kao_plan_waves: a reassignment plan split into waves with at most k partition movements per broker per wave
+// (DESIGN.md section 4g).  Kernels and the C entry point.
+//
+// A partition p that changed and adds brokers (add(p) = target \ current) moves data: its participants S(p) are add(p) plus the
+// copy source current[p][0] (new followers fetch from the leader).  The waves are a first fit: partitions in a priority order,
+// each into the first wave where every participant has fewer than k movements.  The GPU runs that sequential first fit EXACTLY,
+// for kWaveOrders priority orders at once, in rounds:
+//   - minkey[o][b] = lowest key among the still unplaced partitions of order o at broker b (one 64-bit atomicMin per participant);
+//   - an unplaced p whose key is minkey[o][b] at EVERY participant b has no unplaced partition ahead of it at any of its brokers,
+//     so the loads it sees are exactly the ones the sequential first fit would see: it is placed now.  Two partitions placed in
+//     one round share no broker (each broker has one minimum), so the load updates need no atomics;
+//   - every other unplaced p bids into the next round's minkey.
+// The round's lowest key is always placed, so the rounds end; a broker places at most one partition per round, so the round
+// count is at least the largest participant degree.  Keys are unique within an order ((~maxdeg) << 32 | a bijection of p), so
+// the result depends on (input, seed) only.  Order 0 is degree-descending, ties by partition index; orders 1.. break the ties by
+// a seeded bijective hash.  The order with the fewest waves wins (ties: the lowest order).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "kao_host.h"
+
+namespace {
+
+constexpr int kWaveOrders = 64;              // priority orders per launch (each its own slice of loads / minkeys)
+constexpr int kWavePart = KAO_MAX_RF + 1;    // participants per partition: up to KAO_MAX_RF added brokers + the source
+constexpr int kWaveThreads = 256;
+constexpr int kWaveBatch = 32;               // rounds enqueued between two checks of the "anything left" flag
+constexpr size_t kWaveBudget = size_t(1) << 30;  // device bytes the per-order state may take; fewer orders when it would not fit
+enum { CTL_NMV = 0, CTL_CHANGED = 1, CTL_LB = 2, CTL_WCAP = 3, CTL_ERR = 4, CTL_N = 8 };
+
+__host__ __device__ inline uint32_t wave_mix32(uint32_t x) {  // murmur3 finaliser: a bijection of 32-bit words
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+
+__host__ __device__ inline uint32_t wave_salt(uint64_t seed, uint32_t o) {  // splitmix64 of (seed, order), low word
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(o + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return (uint32_t)(z ^ (z >> 31));
+}
+
+// priority key of partition p in order o: smaller = earlier.  Unique within an order for p < 2^32.
+__device__ inline uint64_t wave_key(uint32_t o, uint32_t p, int32_t maxdeg, uint32_t salt) {
+    const uint32_t tie = o == 0 ? p : wave_mix32(p ^ salt);
+    return (uint64_t)(0xFFFFFFFFu - (uint32_t)maxdeg) << 32 | tie;
+}
+
+// wavefront-aggregated atomics on the few global control words (one atomic per wavefront, all 64 lanes must be active)
+__device__ inline int wave_reserve(bool take, int32_t *counter) {
+    const unsigned long long m = __ballot(take);
+    if (m == 0ull) return -1;
+    const int lane = __lane_id(), leader = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(counter, __popcll(m));
+    base = __shfl(base, leader);
+    return take ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+}
+
+__device__ inline void wave_max_to(int32_t v, int32_t *dst) {
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+    if (__lane_id() == 0 && v > 0) atomicMax(dst, v);
+}
+
+// One thread per partition: unchanged -> wave -1; changed without an added broker -> wave 0 (moves no data); otherwise the
+// partition joins the list of moving ones (slot order depends on timing; everything downstream is keyed by p, not by slot).
+__global__ void k_wave_classify(int32_t P, int32_t W, const uint16_t *__restrict__ cur, const uint16_t *__restrict__ tgt,
+                                int32_t *__restrict__ wave, uint16_t *__restrict__ part, uint8_t *__restrict__ npart,
+                                int32_t *__restrict__ mv_idx, int32_t *__restrict__ deg, int32_t *__restrict__ ctl) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint16_t c[KAO_MAX_RF], n[KAO_MAX_RF], s[kWavePart];
+    bool changed = false;
+    int ns = 0;
+    if (p < P) {
+        for (int i = 0; i < W; ++i) {
+            c[i] = cur[p * W + i];
+            n[i] = tgt[p * W + i];
+            changed |= c[i] != n[i];
+        }
+        if (changed) {
+            for (int i = 0; i < W; ++i) {
+                if (n[i] == KAO_NONE) continue;
+                bool held = false;
+                for (int j = 0; j < W; ++j) held |= c[j] == n[i];
+                if (!held) s[ns++] = n[i];
+            }
+            if (ns > 0 && c[0] != KAO_NONE) s[ns++] = c[0];
+        }
+        if (!changed) wave[p] = -1;
+        else if (ns == 0) wave[p] = 0;
+    }
+    const int slot = wave_reserve(ns > 0, &ctl[CTL_NMV]);
+    wave_max_to(changed ? 1 : 0, &ctl[CTL_CHANGED]);
+    if (slot < 0) return;
+    mv_idx[slot] = (int32_t)p;
+    npart[slot] = (uint8_t)ns;
+    for (int j = 0; j < ns; ++j) {
+        part[(size_t)slot * kWavePart + j] = s[j];
+        atomicAdd(&deg[s[j]], 1);
+    }
+}
+
+// One thread per moving partition: its largest participant degree (the first key), the lower bound max_b ceil(deg(b) / k) and
+// the wave cap: p's first fit is at most sum_b floor((deg(b) - 1) / k), since every wave before it is full at some participant.
+__global__ void k_wave_bound(int32_t n_mv, int32_t k, const uint16_t *__restrict__ part, const uint8_t *__restrict__ npart,
+                             const int32_t *__restrict__ deg, int32_t *__restrict__ maxdeg, int32_t *__restrict__ ctl) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t md = 0, cap = 0;
+    if (i < n_mv) {
+        for (int j = 0; j < npart[i]; ++j) {
+            const int32_t d = deg[part[(size_t)i * kWavePart + j]];
+            md = max(md, d);
+            cap += (d - 1) / k;
+        }
+        maxdeg[i] = md;
+        cap += 1;
+    }
+    wave_max_to((md + k - 1) / k, &ctl[CTL_LB]);
+    wave_max_to(cap, &ctl[CTL_WCAP]);
+}
+
+// Round -1: every moving partition bids into the first round's minkeys.  grid = (slots, orders).
+__global__ void k_wave_seed(int32_t n_mv, int32_t B, uint64_t seed, const uint16_t *__restrict__ part, const uint8_t *__restrict__ npart,
+                            const int32_t *__restrict__ mv_idx, const int32_t *__restrict__ maxdeg, unsigned long long *__restrict__ mk0) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t o = blockIdx.y;
+    if (i >= n_mv) return;
+    const unsigned long long key = wave_key(o, (uint32_t)mv_idx[i], maxdeg[i], wave_salt(seed, o));
+    unsigned long long *mk = mk0 + (size_t)o * B;
+    for (int j = 0; j < npart[i]; ++j) atomicMin(&mk[part[(size_t)i * kWavePart + j]], key);
+}
+
+// Round r: reads minkey buffer r % 3, bids into (r + 1) % 3, clears (r + 2) % 3 (read by round r - 1, written by round r + 1).
+// flags[(r + 1) % 3] = 1 when a partition is still unplaced after this round.  loads[o][b][w], waveo[o][slot] (-1 = unplaced).
+__global__ void k_wave_round(int32_t r, int32_t n_ord, int32_t n_mv, int32_t B, int32_t wcap, int32_t k, uint64_t seed,
+                             const uint16_t *__restrict__ part, const uint8_t *__restrict__ npart, const int32_t *__restrict__ mv_idx,
+                             const int32_t *__restrict__ maxdeg, unsigned long long *__restrict__ mk, int32_t *__restrict__ loads,
+                             int32_t *__restrict__ waveo, int32_t *__restrict__ nw, int32_t *__restrict__ flags, int32_t *__restrict__ ctl) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t o = blockIdx.y;
+    const size_t per = (size_t)n_ord * B;
+    {   // clear the buffer of round r + 2
+        const size_t nthreads = (size_t)gridDim.x * blockDim.x * gridDim.y;
+        const size_t tid = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+        unsigned long long *clr = mk + (size_t)((r + 2) % 3) * per;
+        for (size_t e = tid; e < per; e += nthreads) clr[e] = ~0ull;
+        if (tid == 0) flags[(r + 2) % 3] = 0;
+    }
+    bool pending = false;
+    if (i < n_mv && waveo[(size_t)o * n_mv + i] < 0) {
+        const uint32_t p = (uint32_t)mv_idx[i];
+        const unsigned long long key = wave_key(o, p, maxdeg[i], wave_salt(seed, o));
+        const int np = npart[i];
+        uint16_t b[kWavePart];
+        for (int j = 0; j < np; ++j) b[j] = part[(size_t)i * kWavePart + j];
+        const unsigned long long *mine = mk + (size_t)(r % 3) * per + (size_t)o * B;
+        bool ready = true;
+        for (int j = 0; j < np; ++j) ready &= mine[b[j]] == key;
+        if (ready) {
+            int32_t *L = loads + (size_t)o * B * wcap;
+            int32_t w = 0;
+            for (; w < wcap; ++w) {
+                bool fit = true;
+                for (int j = 0; j < np; ++j) fit &= L[(size_t)b[j] * wcap + w] < k;
+                if (fit) break;
+            }
+            if (w < wcap) {
+                for (int j = 0; j < np; ++j) L[(size_t)b[j] * wcap + w] += 1;
+                waveo[(size_t)o * n_mv + i] = w;
+                atomicMax(&nw[o], w + 1);
+            } else {
+                atomicOr(&ctl[CTL_ERR], 1);  // cannot happen (wcap bounds every first fit); the host stops on it
+            }
+        } else {
+            unsigned long long *next = mk + (size_t)((r + 1) % 3) * per + (size_t)o * B;
+            for (int j = 0; j < np; ++j) atomicMin(&next[b[j]], key);
+            pending = true;
+        }
+    }
+    wave_max_to(pending ? 1 : 0, &flags[(r + 1) % 3]);
+}
+
+__global__ void k_wave_scatter(int32_t n_mv, const int32_t *__restrict__ waveo, const int32_t *__restrict__ mv_idx, int32_t *__restrict__ wave) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_mv) wave[mv_idx[i]] = waveo[i];
+}
+
+// device buffers of one call, released on every return path
+struct WaveBufs {
+    std::vector<void *> ptrs;
+    hipStream_t stream = nullptr;
+    template <typename T>
+    int alloc(T **p, size_t n) {
+        *p = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), std::max<size_t>(n, 1) * sizeof(T)));
+        ptrs.push_back(*p);
+        return KAO_OK;
+    }
+    ~WaveBufs() {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+};
+
+int validate_waves(int32_t B, int32_t P, int32_t W, const uint16_t *cur, const uint16_t *tgt, int32_t k, const int32_t *wave,
+                   const int32_t *n_waves, const int32_t *lower_bound) {
+    if (!cur || !tgt || !wave || !n_waves || !lower_bound) return fail(KAO_ERR_INVALID, "kao_plan_waves: null pointer");
+    if (k < 1) return fail(KAO_ERR_INVALID, "kao_plan_waves: max_per_broker must be >= 1");
+    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, "kao_plan_waves: width must be 1.." + std::to_string(KAO_MAX_RF));
+    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, "kao_plan_waves: n_brokers must be 1..65534");
+    if (P < 0) return fail(KAO_ERR_INVALID, "kao_plan_waves: n_partitions < 0");
+    for (int64_t p = 0; p < P; ++p) {
+        for (int side = 0; side < 2; ++side) {
+            const uint16_t *row = (side ? tgt : cur) + p * W;
+            int filled = 0;
+            for (int i = 0; i < W; ++i) {
+                if (row[i] == KAO_NONE) continue;
+                if (row[i] >= B)
+                    return fail(KAO_ERR_INVALID, "kao_plan_waves: partition " + std::to_string(p) + ": broker index " + std::to_string(row[i]) + " >= n_brokers");
+                for (int j = 0; j < i; ++j)
+                    if (row[j] == row[i]) return fail(KAO_ERR_INVALID, "kao_plan_waves: partition " + std::to_string(p) + ": broker repeated in a row");
+                ++filled;
+            }
+            if (side == 1 && filled == 0) return fail(KAO_ERR_INVALID, "kao_plan_waves: partition " + std::to_string(p) + ": target row has no broker");
+        }
+    }
+    return KAO_OK;
+}
+
+}  // namespace
+
+extern "C" int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
+                              int32_t max_per_broker, uint64_t seed, int32_t *wave, int32_t *n_waves, int32_t *lower_bound) {
+    const int32_t B = n_brokers, P = n_partitions, W = width, k = max_per_broker;
+    int rc = validate_waves(B, P, W, current, target, k, wave, n_waves, lower_bound);
+    if (rc) return rc;
+    if ((rc = require_init())) return rc;
+    *n_waves = 0;
+    *lower_bound = 0;
+    if (P == 0) return KAO_OK;
+
+    WaveBufs m;
+    HIP_TRY(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
+    hipStream_t st = m.stream;
+    uint16_t *d_cur, *d_tgt, *d_part;
+    uint8_t *d_npart;
+    int32_t *d_wave, *d_mv, *d_deg, *d_maxdeg, *d_ctl;
+    const size_t PW = (size_t)P * W;
+    if ((rc = m.alloc(&d_cur, PW)) || (rc = m.alloc(&d_tgt, PW)) || (rc = m.alloc(&d_part, (size_t)P * kWavePart)) ||
+        (rc = m.alloc(&d_npart, (size_t)P)) || (rc = m.alloc(&d_wave, (size_t)P)) || (rc = m.alloc(&d_mv, (size_t)P)) ||
+        (rc = m.alloc(&d_deg, (size_t)B)) || (rc = m.alloc(&d_maxdeg, (size_t)P)) || (rc = m.alloc(&d_ctl, CTL_N)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_cur, current, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_tgt, target, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_deg, 0, (size_t)B * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(d_ctl, 0, CTL_N * sizeof(int32_t), st));
+    const unsigned pblocks = (unsigned)(((size_t)P + kWaveThreads - 1) / kWaveThreads);
+    k_wave_classify<<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_wave, d_part, d_npart, d_mv, d_deg, d_ctl);
+    HIP_TRY(hipGetLastError());
+    int32_t ctl[CTL_N];
+    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int32_t n_mv = ctl[CTL_NMV];
+    int32_t best_waves = ctl[CTL_CHANGED] ? 1 : 0;  // metadata-only partitions share wave 0
+    if (n_mv > 0) {
+        const unsigned mblocks = (unsigned)((n_mv + kWaveThreads - 1) / kWaveThreads);
+        k_wave_bound<<<mblocks, kWaveThreads, 0, st>>>(n_mv, k, d_part, d_npart, d_deg, d_maxdeg, d_ctl);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const int32_t wcap = ctl[CTL_WCAP];
+        // per-order state: loads[B][wcap], waveo[n_mv], three minkey rows [B]
+        const size_t per_order = (size_t)B * wcap * 4 + (size_t)n_mv * 4 + (size_t)3 * B * 8;
+        const int n_ord = (int)std::max<size_t>(1, std::min<size_t>(kWaveOrders, kWaveBudget / per_order));
+        int32_t *d_loads, *d_waveo, *d_nw, *d_flags;
+        unsigned long long *d_mk;
+        if ((rc = m.alloc(&d_loads, (size_t)n_ord * B * wcap)) || (rc = m.alloc(&d_waveo, (size_t)n_ord * n_mv)) ||
+            (rc = m.alloc(&d_mk, (size_t)3 * n_ord * B)) || (rc = m.alloc(&d_nw, (size_t)n_ord)) || (rc = m.alloc(&d_flags, 3)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(d_loads, 0, (size_t)n_ord * B * wcap * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(d_waveo, 0xFF, (size_t)n_ord * n_mv * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(d_mk, 0xFF, (size_t)2 * n_ord * B * sizeof(unsigned long long), st));  // rows of rounds 0 and 1
+        HIP_TRY(hipMemsetAsync(d_nw, 0, (size_t)n_ord * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(d_flags, 0, 3 * sizeof(int32_t), st));
+        const dim3 grid(mblocks, (unsigned)n_ord);
+        k_wave_seed<<<grid, kWaveThreads, 0, st>>>(n_mv, B, seed, d_part, d_npart, d_mv, d_maxdeg, d_mk);
+        HIP_TRY(hipGetLastError());
+        // every round places at least the lowest key of each order: n_mv rounds always suffice
+        int32_t r = 0, left = 1;
+        while (left) {
+            if (r > n_mv) return fail(KAO_ERR_HIP, "kao_plan_waves: rounds did not finish");
+            for (int i = 0; i < kWaveBatch; ++i, ++r)
+                k_wave_round<<<grid, kWaveThreads, 0, st>>>(r, n_ord, n_mv, B, wcap, k, seed, d_part, d_npart, d_mv, d_maxdeg, d_mk, d_loads,
+                                                            d_waveo, d_nw, d_flags, d_ctl);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&left, d_flags + r % 3, sizeof left, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (ctl[CTL_ERR]) return fail(KAO_ERR_HIP, "kao_plan_waves: a partition found no wave below the cap");
+        }
+        std::vector<int32_t> nw((size_t)n_ord);
+        HIP_TRY(hipMemcpyAsync(nw.data(), d_nw, nw.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const int best = (int)(std::min_element(nw.begin(), nw.end()) - nw.begin());  // first minimum: the lowest order
+        best_waves = nw[(size_t)best];
+        k_wave_scatter<<<mblocks, kWaveThreads, 0, st>>>(n_mv, d_waveo + (size_t)best * n_mv, d_mv, d_wave);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(wave, d_wave, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_waves = best_waves;
+    *lower_bound = n_mv > 0 ? ctl[CTL_LB] : best_waves;
+    return KAO_OK;
+}
