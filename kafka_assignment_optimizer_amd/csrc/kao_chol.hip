@@ -606,7 +606,7 @@ extern "C" int kao_dense_spd_test(const double *A, int32_t n, const double *rhs,
         SPD_TRY(hipStreamSynchronize(st));
         SPD_TRY(hipGetLastError());
     }
-    if (std::getenv("KAO_CHOL_DEBUG")) {     // clock ticks (s_memtime) of the diagonal tile's phases, to stderr
+    if (env_int("KAO_CHOL_DEBUG", 0) != 0) {     // clock ticks (s_memtime) of the diagonal tile's phases, to stderr
         long long *dbgd = nullptr, hd[32] = {0};
         SPD_TRY(hipMalloc(&dbgd, sizeof hd));
         SPD_TRY(hipMemset(dbgd, 0, sizeof hd));

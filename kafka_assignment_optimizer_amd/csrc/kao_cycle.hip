@@ -28,8 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/kao.h"
-#include "kao_internal.h"
+#include "kao_host.h"
 
 namespace kao {
 namespace {
@@ -629,11 +628,10 @@ struct Cx {
     }
 
     // edges, closures (device); diagonals to the host
-    // one min-plus squaring; small matrices are split over the midpoints so that the launch fills the chip (KAO_CX_SPLITK=0: never)
+    // one min-plus squaring; small matrices are split over the midpoints so that the launch fills the chip
     int square(const int32_t *Din, int32_t *Dout, uint16_t *Mout) {
         const int nt = q.np / 64, tiles = nt * nt;
-        static const bool split_on = [] { const char *e = std::getenv("KAO_CX_SPLITK"); return !(e && e[0] == '0'); }();
-        int ks = split_on && tiles < 200 ? std::min(8, std::max(2, (512 + tiles - 1) / tiles)) : 1;
+        int ks = tiles < 200 ? std::min(8, std::max(2, (512 + tiles - 1) / tiles)) : 1;
         const int kchunk = ((q.np + ks - 1) / ks + 15) / 16 * 16;
         ks = (q.np + kchunk - 1) / kchunk;
         if (ks <= 1) { hipLaunchKernelGGL(k_cx_square, dim3(nt, nt), dim3(256), 0, stream, q.np, Din, Dout, Mout); return KAO_OK; }
@@ -895,13 +893,11 @@ struct CxCand { int total, a, b, c; };   // seed: (total, p, cfg, y); cycle: (ga
 // a negative KAO_ERR_* code on failure
 int cx_round(Cx &cx, uint16_t *assign, int32_t base, int32_t *new_obj, int32_t stats[8]) {
     const CxParams &q = cx.q;
-    static const bool trace = std::getenv("KAO_CX_TRACE") != nullptr;
+    static const bool trace = env_int("KAO_CX_TRACE", 0) != 0;
     const double tt0 = api_now_s();
-    const char *bulk_env = std::getenv("KAO_CX_BULK_SLOTS");   // test hook (read every round: tests switch it)
-    const int64_t bulk_slots = bulk_env && *bulk_env ? (int64_t)std::atoll(bulk_env) : kCxBulkSlots;
+    const int64_t bulk_slots = env_int("KAO_CX_BULK_SLOTS", kCxBulkSlots);   // test hook (read every round: tests switch it)
     const bool bulk_topic = (int64_t)q.P * q.RF > bulk_slots;
-    static const bool lazy_on = [] { const char *e = std::getenv("KAO_CX_LAZY"); return !(e && e[0] == '0'); }();   // KAO_CX_LAZY=0: every level in every build
-    int rc = cx.build(assign, lazy_on && !bulk_topic);
+    int rc = cx.build(assign, !bulk_topic);
     if (rc) return rc;
     const double tt1 = api_now_s();
     // ---- candidates ----
@@ -1262,8 +1258,7 @@ int cycle_run(CycleCtx *c, uint16_t *assign, int32_t max_rounds, double deadline
         ++stats[0];
         if (got < 0) return got;   // a KAO_ERR_* code (negative) from cx_round
         if (got == 0) {            // a fixpoint of the plain layers: the compound-edge layer (test hook KAO_CX_PAIRS=1, see cx_pairs_round)
-            const char *pe = std::getenv("KAO_CX_PAIRS");   // read at every fixpoint: the tests switch it inside one process
-            if (!(pairs && pe && pe[0] == '1')) break;
+            if (!(pairs && env_int("KAO_CX_PAIRS", 0) != 0)) break;   // (read at every fixpoint: the tests switch it inside one process)
             got = cx_pairs_round(cx, assign, cur, &next, stats);
             if (got < 0) return got;
             if (got == 0) break;

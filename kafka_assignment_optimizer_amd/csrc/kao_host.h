@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -36,6 +37,11 @@ extern thread_local int t_device; // per-thread override: kao_solve_multi drives
 extern thread_local double g_timing[16];
 extern thread_local double g_lp[8];       // KAO-LP in the last kao_solve (kao_last_solve_lp)
 extern thread_local double g_profile[8];  // K-search as the last profiled kao_solve ran it (kao_last_solve_profile)   // wall-clock breakdown of the last solve (kao_last_solve_timing)
+// The KAO_* environment hooks (tests, measurements, diagnostics): an unset or empty variable gives `dflt`.
+// Every host-side read goes through these, except launch_init's own clamp of KAO_INIT_WAVES (kao_kernels.hip).
+inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e && *e ? e : nullptr; }
+inline int64_t env_int(const char *name, int64_t dflt) { const char *e = env_str(name); return e ? (int64_t)std::atoll(e) : dflt; }
+inline double env_real(const char *name, double dflt) { const char *e = env_str(name); return e ? std::atof(e) : dflt; }
 
 // ---- the model on the host (kao_model.cpp) ----
 int validate(const kao_topic *t);

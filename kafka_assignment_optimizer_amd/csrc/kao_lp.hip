@@ -250,7 +250,7 @@ constexpr int kLpSigmaExp = 10;
 // the unbounded ones (new-replica masses per rack, inflows) mostly far below 1; from 0.1 the perturbed solve of eight drift seeds takes 476
 // iterations instead of 527 (0.3: 487, 0.03: 538; profiles/r06_c32_start_floor.txt).
 constexpr double kLpXFloor = 0.1;
-static double lp_xfloor() { const char *e = std::getenv("KAO_LP_XFLOOR"); const double f = e ? std::atof(e) : kLpXFloor; return f > 0.0 && f <= 10.0 ? f : kLpXFloor; }   // (measurement hook)
+static double lp_xfloor() { const double f = env_real("KAO_LP_XFLOOR", kLpXFloor); return f > 0.0 && f <= 10.0 ? f : kLpXFloor; }   // (measurement hook)
 // Topics of more than kLpSigmaHugeSlots replica slots (the ones kao_solve gives their LP alone) take kLpSigmaExpHuge: with the starting point's floor at
 // 0.1 the iteration count keeps falling up to ~24 there (13 drifted 100,000-partition topics: 761 iterations at 10, 663 at 14, 554 at 20, 508 at 24,
 // 503-525 at 32-64; profiles/r06_c36_sigma_exponent_huge.txt) -- but on the small goldens 24 leaves 11 rounded iterates outside a band row instead of 4,
@@ -259,10 +259,10 @@ constexpr int kLpSigmaExpHuge = 24;
 constexpr long long kLpSigmaHugeSlots = 131072;
 static double lp_sigexp(long long slots) {
     const int dflt = slots > kLpSigmaHugeSlots ? kLpSigmaExpHuge : kLpSigmaExp;
-    const char *e = std::getenv("KAO_LP_SIGEXP"); const int k = e ? std::atoi(e) : dflt;      // (measurement hook)
+    const int k = (int)env_int("KAO_LP_SIGEXP", dflt);      // (measurement hook)
     return k >= 1 && k <= 64 ? k : dflt;
 }
-static double lp_gamma() { const char *e = std::getenv("KAO_LP_GAMMA"); const double g = e ? std::atof(e) : 0.0; return g > 0.5 && g < 1.0 ? g : 0.0; }
+static double lp_gamma() { const double g = env_real("KAO_LP_GAMMA", 0.0); return g > 0.5 && g < 1.0 ? g : 0.0; }
 __device__ __forceinline__ double lp_step_fraction(double a, double fixed) { return fixed > 0.0 ? fixed : (a > kLpGammaMax ? kLpGammaMax : (a < kLpGamma ? kLpGamma : a)); }
 __global__ void k_lp_sc_final(double *sc) {
     if (sc[SC_STOP] != 0.0) return;
@@ -1293,10 +1293,8 @@ struct LpCtx {
     double *rec = nullptr, *redA = nullptr, *redB = nullptr, *redC = nullptr, *part = nullptr, *ylast = nullptr, *trace = nullptr;
     int32_t *d_mult = nullptr, *d_zq = nullptr;
     VarVec dc{}; RowVec wc{}; int mcc = 2;   // centrality correctors per iteration (KAO_LP_MCC; 0: none) and their direction / row vector
-    bool rack_mfma = true;         // the rack x rack block of the Schur complement on the matrix cores (2R <= 128; KAO_LP_RACK=old: the LDS-tiled kernel)
     double *qd = nullptr, *wr = nullptr; int *qc = nullptr; int ncp = 0;   // the partitions' coupling columns / replica rows for k_lp_schur_broker (k_lp_factor_local); ncp = columns per partition, padded (0: more than 128, not kept)
     double *rack_part = nullptr;   // [2 R][kRackChunks] slice sums of the rack rows
-    int broker_u = 4;          // incidences in flight per wavefront in k_lp_schur_broker (KAO_LP_BROKER_U: 4 / 8 / 16)
     double *xz = nullptr;      // exchange vectors of the triangular solves (kao_chol.hip)
     LpFan *fan = nullptr;      // shard 0 of a fan (kao_internal.h): the lp_* entry points forward to it
     double *tri = nullptr;     // a shard's packed lower triangle of S for the all-reduce
@@ -1382,23 +1380,22 @@ void lp_factor(LpCtx &c) {
     hipLaunchKernelGGL(k_lp_factor_local, dim3(c.nblk_p), dim3(256), 0, c.st, D, c.th.z, c.fj, c.fr, c.ti, c.qd, c.qc, c.wr, c.ncp);
     const size_t lds_b = (size_t)c.broker_waves * 2 * D.mc * sizeof(double);
     const dim3 bg((D.B + c.broker_waves - 1) / c.broker_waves), bb(64 * c.broker_waves);
+    // 4 incidences in flight per wavefront (round 6, 100,000 partitions: 4.10 / 4.29 / 4.41 ms an iteration with 4 / 8 / 16)
     if (2 * D.NJ + 2 * D.R > 64) hipLaunchKernelGGL((k_lp_schur_broker<4, 2>), bg, bb, lds_b, c.st, D, c.th.z, c.th.zg, c.fj, c.fr, c.ti, c.qd, c.qc, c.wr, c.S);
-    else if (c.broker_u >= 16) hipLaunchKernelGGL(k_lp_schur_broker<16>, bg, bb, lds_b, c.st, D, c.th.z, c.th.zg, c.fj, c.fr, c.ti, c.qd, c.qc, c.wr, c.S);
-    else if (c.broker_u >= 8) hipLaunchKernelGGL(k_lp_schur_broker<8>, bg, bb, lds_b, c.st, D, c.th.z, c.th.zg, c.fj, c.fr, c.ti, c.qd, c.qc, c.wr, c.S);
     else hipLaunchKernelGGL(k_lp_schur_broker<4>, bg, bb, lds_b, c.st, D, c.th.z, c.th.zg, c.fj, c.fr, c.ti, c.qd, c.qc, c.wr, c.S);
     const int n2 = 2 * D.R, per = 6 * n2 + D.R, t16 = (n2 + 15) / 16;
     const dim3 sg((n2 * n2 + 255) / 256), sb(256), sg2((n2 * n2 + 15) / 16);
 #define KAO_RACK_MFMA(T) do { hipLaunchKernelGGL(k_lp_schur_rack_mfma<T>, dim3(kRackMfmaBlocks, rack_mfma_shares(T)), dim3(256), 0, c.st, D, c.th.z, c.fr, c.ti, c.part); \
                               hipLaunchKernelGGL(k_lp_schur_rack_sum2<T>, sg2, sb, 0, c.st, D, c.part, kRackMfmaBlocks, c.th.zg, c.S); } while (0)
-    if (c.rack_mfma && t16 == 1) KAO_RACK_MFMA(1);
-    else if (c.rack_mfma && t16 == 2) KAO_RACK_MFMA(2);
-    else if (c.rack_mfma && t16 == 3) KAO_RACK_MFMA(3);
-    else if (c.rack_mfma && t16 == 4) KAO_RACK_MFMA(4);
-    else if (c.rack_mfma && t16 == 5) KAO_RACK_MFMA(5);
-    else if (c.rack_mfma && t16 == 6) KAO_RACK_MFMA(6);
-    else if (c.rack_mfma && t16 == 7) KAO_RACK_MFMA(7);
-    else if (c.rack_mfma && t16 == 8) KAO_RACK_MFMA(8);
-    else {
+    if (t16 == 1) KAO_RACK_MFMA(1);
+    else if (t16 == 2) KAO_RACK_MFMA(2);
+    else if (t16 == 3) KAO_RACK_MFMA(3);
+    else if (t16 == 4) KAO_RACK_MFMA(4);
+    else if (t16 == 5) KAO_RACK_MFMA(5);
+    else if (t16 == 6) KAO_RACK_MFMA(6);
+    else if (t16 == 7) KAO_RACK_MFMA(7);
+    else if (t16 == 8) KAO_RACK_MFMA(8);
+    else {   // more than 64 racks: the LDS-tiled kernel
         hipLaunchKernelGGL(k_lp_schur_rack, dim3(c.rack_blocks), dim3(256), (size_t)c.rack_tile * per * sizeof(double), c.st, D, c.th.z, c.fj, c.fr, c.ti, c.rack_chunk, c.rack_tile, c.part);
         hipLaunchKernelGGL(k_lp_schur_rack_sum, sg, sb, 0, c.st, D, c.part, c.rack_blocks, c.th.zg, c.S);
     }
@@ -1551,7 +1548,7 @@ int lp_open(const kao_topic *t, LpCtx **out, const LpShard *shard) {
     for (RowVec *rv : {&c->y, &c->rp, &c->w1, &c->w2, &c->wc})
         if ((rc = c->row_vec(*rv))) return bail(rc);
     if ((rc = c->var_vec(c->dc))) return bail(rc);
-    { const char *e = std::getenv("KAO_LP_MCC"); c->mcc = e ? std::max(0, std::min(4, std::atoi(e))) : 2; }
+    c->mcc = (int)std::max<int64_t>(0, std::min<int64_t>(4, env_int("KAO_LP_MCC", 2)));
     const size_t nvtot = (size_t)D.NV * P + D.GV;
     c->nblk_var = (int)std::min<size_t>((nvtot + kRedBlock - 1) / kRedBlock, (size_t)kVarBlocks);
     c->nblk_p = (P + 255) / 256;
@@ -1572,11 +1569,7 @@ int lp_open(const kao_topic *t, LpCtx **out, const LpShard *shard) {
         return bail(rc);
     // dynamic LDS beyond 64 KiB has to be enabled per kernel
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_lp_schur_broker<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_lp_schur_broker<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_lp_schur_broker<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_lp_schur_broker<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    { const char *e = std::getenv("KAO_LP_RACK"); c->rack_mfma = !(e && e[0] == 'o'); }
-    { const char *e = std::getenv("KAO_LP_BROKER_U"); c->broker_u = e ? std::atoi(e) : 4; }   // (round 6, measured at 100,000 partitions: 4.10 / 4.29 / 4.41 ms an iteration with 4 / 8 / 16)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_lp_schur_rack), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
     for (const VarVec *vv : {&c->x, &c->s, &c->v, &c->th, &c->rd, &c->h, &c->g, &c->d1, &c->d2, &c->dsa, &c->dva, &c->ds, &c->dv, &c->dc})
         HIP_TRY(hipMemsetAsync(vv->z, 0, nvtot * sizeof(double), c->st));
@@ -1696,8 +1689,7 @@ int lp_enqueue(LpCtx *cp, int k) {
     HIP_TRY(hipSetDevice(c.device));
     if (!c.graph_tried) {   // capture one iteration (KAO_LP_GRAPH=0: plain launches)
         c.graph_tried = true;
-        const char *e = std::getenv("KAO_LP_GRAPH");
-        if (!(e && e[0] == '0') && !c.coll && hipStreamBeginCapture(c.st, hipStreamCaptureModeThreadLocal) == hipSuccess) {   // (a shard's iteration holds collectives: plain launches)
+        if (env_int("KAO_LP_GRAPH", 1) != 0 && !c.coll && hipStreamBeginCapture(c.st, hipStreamCaptureModeThreadLocal) == hipSuccess) {   // (a shard's iteration holds collectives: plain launches)
             lp_enqueue_one(c);
             hipGraph_t g = nullptr;
             if (hipStreamEndCapture(c.st, &g) == hipSuccess && g) {

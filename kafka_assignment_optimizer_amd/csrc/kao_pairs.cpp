@@ -253,7 +253,7 @@ int pair_edges(const kao_topic *t, const uint16_t *assignment, int gmin, std::un
       }
     }
     if (stats) { stats[0] = (int64_t)halves.size(); stats[1] = n_pairs; stats[2] = (int64_t)edges.size(); stats[3] = n_closed; }
-    if (std::getenv("KAO_CX_TRACE"))
+    if (env_int("KAO_CX_TRACE", 0) != 0)
         std::fprintf(stderr, "[kao-cx] pairs: %zu half-moves in %.1f ms, %lld pairs -> %zu compound edges in %.1f ms\n", halves.size(),
                      (t_halves - t_begin) * 1e3, (long long)n_pairs, edges.size(), (now_s() - t_halves) * 1e3);
     return KAO_OK;

@@ -581,12 +581,11 @@ int kao_session_create(const kao_topic *topics, int32_t n_topics, const kao_opts
         // both assignments in LDS when they fit (one wavefront per workgroup at least); else the working one alone, the current one read
         // from global memory / L2 (round 5: ~4,900 .. 9,800 partitions; KAO_CUR_GLOBAL=0: the HBM path as before); else everything in HBM
         const bool both_fit = search_lds_bytes(d.P, d.Bx, 1, false, true, d.nw, s->any_bw, d.R) <= 160 * 1024;
-        const bool curg_on = [] { const char *e = std::getenv("KAO_CUR_GLOBAL"); return !(e && e[0] == '0'); }();   // (read per session: a test hook)
+        const bool curg_on = env_int("KAO_CUR_GLOBAL", 1) != 0;   // (read per session: a test hook)
         // (one workgroup of ONE wavefront per restart and compute unit: with more restarts than compute units the workgroups run in rounds
         // and the HBM path, four wavefronts per workgroup, is the faster one -- 500 x 5000: 3.1 against 3.9 ms a launch at 256 restarts,
         // 12.4 against 4.2 at 1,024; teams (kao_opts.team) are a global-memory mode)
-        static const bool team_env = [] { const char *e = std::getenv("KAO_TEAM"); return e && std::atoi(e) > 1; }();
-        const bool curg = !both_fit && curg_on && o.team <= 1 && !team_env && o.restarts <= std::max(num_cu(s->device), 1) &&
+        const bool curg = !both_fit && curg_on && o.team <= 1 && o.restarts <= std::max(num_cu(s->device), 1) &&
                           search_lds_bytes(d.P, d.Bx, 1, false, true, d.nw, s->any_bw, d.R, 0, true) <= 160 * 1024;
         const bool global_a = !both_fit && !curg;
         s->topic_global[(size_t)t] = global_a;
@@ -672,16 +671,14 @@ int kao_session_create(const kao_topic *topics, int32_t n_topics, const kao_opts
         g.nw = s->pts[(size_t)mem[0]].d.nw;
         g.eval_coop = n_cand <= fill && g.maxP >= 1024;
         if (g.eval_coop) cpb = 1;
-        if (g.global_a) if (const char *e = std::getenv("KAO_GLOBAL_WAVES")) g.waves = std::min(kWaves, std::max(1, std::atoi(e)));  // measurement hook
         // Topics that live in global memory: a restart is latency-bound (dependent loads of 16-byte assignment words), so ONE
         // wavefront per restart leaves the restart shallow.  Round 4 tried a TEAM of wavefronts per restart (k_team): W proposals
         // per iteration against the same state, the disjoint ones applied.  Measured (gpurun_out/r04_c2_*): same iterations per
         // second per restart at team 2 / 4, fewer at 8, and the 3-s incumbents of 1000 x 30000 / 1000 x 100000 within noise of
-        // one wavefront per restart -- so teams are opt-in (kao_opts.team = n, or KAO_TEAM=n), the default is k_search.
+        // one wavefront per restart -- so teams are opt-in (kao_opts.team = n), the default is k_search.
         if (g.global_a) {
             const int tmax = g.nw > kRFP ? kTeamMax / 2 : kTeamMax;   // (8 replica words per partition: 256 threads keep the kernel out of scratch)
-            int want = o.team == 0 ? 1 : o.team;
-            if (const char *e = std::getenv("KAO_TEAM")) want = std::max(0, std::atoi(e));
+            const int want = o.team == 0 ? 1 : o.team;
             g.team = want <= 1 ? 0 : std::min(want, tmax);
             if (g.team > 0) g.waves = 1;   // the block map holds one workgroup per restart
         }
@@ -825,7 +822,6 @@ int kao_session_step(kao_session *s) {
     const int eper = s->opts.elite_period;
     prm.bw = s->any_bw ? 1 : 0;
     prm.scan2_max = kScanTwoSlots;
-    if (const char *e = std::getenv("KAO_X_SCAN2_MAX")) prm.scan2_max = std::atoi(e);   // experiment knob (the replay tests assume the default)
     prm.elite = (eper > 0 && s->launch > 0 && s->launch % (uint32_t)eper == 0) ? 1 : 0;
     sp.price_pool = s->d_price + (size_t)s->price_read * s->price_half_i32;
     sp.int_pool = s->d_int; sp.elite_assign = s->d_win_assign; sp.elite_key = s->d_keys; sp.bw_pool = s->d_bw;
@@ -839,8 +835,7 @@ int kao_session_step(kao_session *s) {
         prm.maxP = g.maxP; prm.maxBx = g.maxBx; prm.maxR = g.maxR; prm.wide = g.wide ? 1 : 0; prm.cur_global = g.cur_global ? 1 : 0;
         SearchParams gp = prm;
         if (gp.init && g.global_a) {   // topics in global memory: the holes are filled by a workgroup per restart (K-init), not by one wavefront
-            const char *e = std::getenv("KAO_INIT_WAVES");
-            if (!(e && e[0] == '0') && launch_init(sp, gp, g.smap_n, g.team > 0 ? 1 : g.waves, s->priced, g.nw, s->stream)) gp.init = 2;
+            if (env_int("KAO_INIT_WAVES", 1) != 0 && launch_init(sp, gp, g.smap_n, g.team > 0 ? 1 : g.waves, s->priced, g.nw, s->stream)) gp.init = 2;
             HIP_TRY(hipGetLastError());
         }
         launch_search(sp, gp, g.smap_n, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team);
@@ -1023,7 +1018,6 @@ static int bound_step_impl(kao_session *s, const int64_t *target, int32_t iters,
                                s->price_half_i32 * 4, hipMemcpyDeviceToDevice, s->stream_bound));
     bp.price_pool = s->d_price + (size_t)wh * s->price_half_i32;
     bp.export_prices = 1;
-    if (const char *e = std::getenv("KAO_X_PRICE_SRC")) bp.export_prices = std::atoi(e);  // experiment knob
     s->price_write_last = wh;
     HIP_TRY(hipEventRecord(s->ev_bound0, s->stream_bound));
     s->h_wide_map.clear();
@@ -1047,10 +1041,9 @@ static int bound_step_impl(kao_session *s, const int64_t *target, int32_t iters,
         // Round 3: the sliced topics run on the PERSISTENT multi-workgroup driver (k_bound_multi) -- and so do topics from 1,024
         // partitions up, in slices of 512 (a 2,000-partition topic: 52 us per iteration in k_bound's one workgroup).  Its workgroups
         // wait for each other, so a launch is kept to 96 of them (larger slices otherwise).  KAO_BOUND_MULTI=0: the round-2 drivers.
-        const char *multi_env = std::getenv("KAO_BOUND_MULTI");
-        const bool multi = !(multi_env && multi_env[0] == '0') && !s->multi_off;
+        const bool multi = env_int("KAO_BOUND_MULTI", 1) != 0 && !s->multi_off;
         if (multi && chunk == 0 && maxP >= 1024) chunk = 512;
-        if (const char *e = std::getenv("KAO_BOUND_CHUNK")) { chunk = std::max(0, std::atoi(e)) / 64 * 64; }
+        chunk = (int)std::max<int64_t>(0, env_int("KAO_BOUND_CHUNK", chunk)) / 64 * 64;
         if (multi && chunk > 0) {   // workgroups that wait for others (topics of more than one slice): at most 96 per launch
             auto waiting_at = [&](int c) {
                 int64_t nb = 0;
@@ -1075,9 +1068,7 @@ static int bound_step_impl(kao_session *s, const int64_t *target, int32_t iters,
                                    hipMemcpyHostToDevice, s->stream_bound));
             // 16 wavefronts whatever the slice: the O(B) phases every workgroup repeats (pools, totals, band terms, step) are what
             // an iteration waits for (measured: slices of 256 with 4 wavefronts 32 us, slices of 512 with 8 wavefronts 19 us at 500 x 5,000)
-            int multi_waves = 16;
-            if (const char *e = std::getenv("KAO_BOUND_WAVES")) multi_waves = std::min(16, std::max(1, std::atoi(e)));
-            if (!(multi && !force_step && launch_bound_multi(bp, wd, n_class[cls], (int)(s->h_wide_map.size() - map0), multi_waves, s->stream_bound)))
+            if (!(multi && !force_step && launch_bound_multi(bp, wd, n_class[cls], (int)(s->h_wide_map.size() - map0), 16, s->stream_bound)))
                 launch_bound_wide(bp, wd, n_class[cls], (int)(s->h_wide_map.size() - map0), 16, s->stream_bound);
         } else
             launch_bound(bp, n_class[cls], waves, s->stream_bound);
@@ -1320,8 +1311,8 @@ int kao_lp_trace(const kao_topic *t, double tol, int32_t max_iters, double *trac
     if (rc) return rc;
     LpCtx *lp = nullptr;
     if ((rc = lp_open(t, &lp))) return rc;
-    double pert = 0.0;       // experiment hook KAO_LP_TRACE_PERT=<eps> (-1: the solve's own default): the trace of the PERTURBED solve
-    if (const char *e = std::getenv("KAO_LP_TRACE_PERT")) { pert = std::atof(e); if (pert < 0) pert = std::min(1e-4, 1.5 / ((double)t->n_partitions * t->rf)); }
+    double pert = env_real("KAO_LP_TRACE_PERT", 0.0);   // experiment hook KAO_LP_TRACE_PERT=<eps> (-1: the solve's own default): the trace of the PERTURBED solve
+    if (pert < 0) pert = std::min(1e-4, 1.5 / ((double)t->n_partitions * t->rf));
     rc = lp_solve(lp, tol > 0 ? tol : 1e-7, max_iters > 0 ? max_iters : 80, multipliers, stats, trace, pert, 0);
     lp_close(lp);
     return rc;

@@ -20,11 +20,10 @@
 namespace {
 
 // The counts of the deterministic schedule (kao_opts.schedule == 0) for a session whose largest topic has `slots` replica
-// slots and `maxB` brokers.  Every value is a pure function of the instance and the options -- nothing measured at run time.
+// slots.  Every value is a pure function of the instance and the options -- nothing measured at run time.
 struct DetPlan { int bound_iters; int64_t cx_stall_iters, cx_due_iters; int cx_rounds; };
-DetPlan det_plan(int64_t slots, int maxB, int n_topics, int iters_per_launch) {
+DetPlan det_plan(int64_t slots, int iters_per_launch) {
     DetPlan d;
-    (void)maxB; (void)n_topics;
     // K-bound iterations per launch = about one K-search launch's worth of time, so that neither stream waits for the other
     // (measured on one MI355X, wall-clock schedule with KAO_SOLVE_TRACE=1, profiles/r03_schedule_trace.txt: drifted single
     // topics of 1,000 / 2,000 / 5,000 / 10,000 / 30,000 partitions: K-search launch 1.6 / 4.0 / 4.4 / 7.3 / 8.4 ms with prices, K-bound
@@ -55,7 +54,6 @@ DetPlan det_plan(int64_t slots, int maxB, int n_topics, int iters_per_launch) {
     // topics beyond 30,000 slots, where a round costs as much as several launches).  Test hooks KAO_DET_CX_STALL_L / _DUE_L
     // give both in launches.
     const int64_t it = std::max(iters_per_launch, 1);
-    auto env_l = [](const char *name, int64_t dflt) { const char *e = std::getenv(name); return e && *e ? (int64_t)std::atoll(e) : dflt; };
     // Beyond a few thousand partitions a launch takes 5-15 ms and KAO-CX is what carries the incumbent (1000 x 30000, 3 s:
     // 231,529 with a call every 6 / 36 launches, 231,159 with 24 / 144), so the counts shrink with the topic.
     // Round 4, beyond 131,072 slots: of a 3-s solve of the drifted 1000 x 100,000 topic KAO-CX's 97 rounds (0.93 s) brought ALL of
@@ -68,9 +66,9 @@ DetPlan det_plan(int64_t slots, int maxB, int n_topics, int iters_per_launch) {
     // 68 of 72 proven in 41 s of wall time with 8 / 48 against 66 of 72 in 58 s with 24 / 144 (GPU call 24; 16 / 96 and 12 / 72
     // on the hard half: 37 and 36 of 42 against 36 and 38).
     const int64_t stall_l = slots <= 16384 ? 8 : (slots <= 32768 ? 12 : (huge ? 1 : 6));
-    d.cx_stall_iters = it * env_l("KAO_DET_CX_STALL_L", stall_l);
-    d.cx_due_iters = it * env_l("KAO_DET_CX_DUE_L", huge ? 1 : 6 * stall_l);
-    d.cx_rounds = (int)env_l("KAO_DET_CX_ROUNDS", slots <= 32768 ? 12 : (huge ? 48 : 6));
+    d.cx_stall_iters = it * env_int("KAO_DET_CX_STALL_L", stall_l);
+    d.cx_due_iters = it * env_int("KAO_DET_CX_DUE_L", huge ? 1 : 6 * stall_l);
+    d.cx_rounds = (int)env_int("KAO_DET_CX_ROUNDS", slots <= 32768 ? 12 : (huge ? 48 : 6));
     return d;
 }
 
@@ -176,9 +174,7 @@ struct SolveRun {
     // vertex, which rounds to an assignment (lp_round_assignment).  One solve gives the certificate and, nearly always, the optimum.
     bool lp_round_on = true;      // KAO_LP_ROUND=0: certificate only (the unperturbed LP, as in the first half of round 5)
     double lp_pert_env = -1.0;    // KAO_LP_PERT=<eps>: the perturbation (default min(1e-4, 1.5 / slots))
-    double lp_first_s = 0.0;      // (KAO_LP_FIRST_S=<s>: fixed rule) huge topics: when the LP fits behind the ~0.2 s to the first feasible incumbent it runs straight after it,
     double lp_solo_s = 1.0; int64_t lp_solo_slots = 32768;
-    double lp_alone_s = 0.0;      // (KAO_LP_ALONE_S=<s>: fixed rule) when the LP's predicted time fits the limit it runs before any K-search launch (its rounded iterate needs no incumbent; K-search takes over if it fails)
     int lp_rounded = 0, lp_round_adopted = 0, lp_round_fractional = 0;
     std::vector<int> lp_fan_devs; // kao_solve_multi, KAO_MULTI_LP=shard: the devices ONE sharded LP of a large replicated topic runs on (lp_open_fan); empty: this device alone
     const bool *ext_pause = nullptr;   // ... and the other devices' runs: no K-search launches while the shards of that LP have the GPUs
@@ -197,9 +193,8 @@ struct SolveRun {
         if (lp_pert_env >= 0) return lp_pert_env;
         return std::min(1e-4, 1.5 / ((double)topics[i].n_partitions * topics[i].rf));
     }
-    bool lp_huge_first = false;   // experiment hook KAO_LP_HUGE_FIRST=1: huge topics get their LP before anything else (the search waits for its prices)
     bool lp_possible(int i) const { return lp_on && !has_target && dual_iters > 0 && s->dual_ok[(size_t)i] && lp_state[(size_t)i] < 2; }
-    // the LP alone on the GPU, before any K-search launch: huge topics when the limit leaves room for ~1.3 s of it, topics from
+    // the LP alone on the GPU, before any K-search launch: huge topics when the limit leaves room for it (lp_fits), topics from
     // lp_solo_slots replica slots (1000 x 30000: 0.56 s alone, 1.0 s two iterations per K-search launch) when it is at least a second
     // (a limit is an input, not the clock: the schedule stays count-keyed)
     bool solo(int i) const { return !huge(i) && (int64_t)topics[i].n_partitions * topics[i].rf >= lp_solo_slots; }
@@ -230,16 +225,15 @@ struct SolveRun {
     bool lp_fits(int i, double extra_s = 0.0) const { return lp_est_s(i) + extra_s <= lp_fit * (deadline - t0); }
     bool lp_alone(int i) const {
         if (!lp_round_on) return false;
-        const bool huge_ok = lp_alone_s > 0 ? deadline - t0 >= lp_alone_s : lp_fits(i);      // (KAO_LP_ALONE_S=<s>: the fixed rule, for experiments)
-        return (huge(i) && huge_ok) || (solo(i) && deadline - t0 >= lp_solo_s && only_open(i));
+        return (huge(i) && lp_fits(i)) || (solo(i) && deadline - t0 >= lp_solo_s && only_open(i));
     }
     // a huge topic between its first feasible incumbent and the end of its LP -- from the start when the limit leaves room for the LP alone
-    bool pause_wanted(int i) const { return lp_possible(i) && ((huge(i) && (feasible(i) || (lp_huge_first && launches >= 1))) || lp_alone(i)); }
+    bool pause_wanted(int i) const { return lp_possible(i) && ((huge(i) && feasible(i)) || lp_alone(i)); }
     static constexpr int kFirstShortIters = 32;
     int iters_last = 0;           // iterations of the launch just enqueued
     bool first_launch_short() const {
         if (s->opts.max_launches > 0 || !lp_on || has_target || dual_iters <= 0) return false;
-        { const char *e = std::getenv("KAO_FIRST_SHORT"); if (e && e[0] == '0') return false; }   // measurement hook
+        // (this does run: at turn 0 every key is still 0, which feasible() reads as feasible at objective kObjCap >= ub, so topic_done holds and search_paused() is false)
         for (int i = 0; i < n; ++i)
             if (!(huge(i) && lp_alone(i) && s->dual_ok[(size_t)i] && !s->topic_infeasible[(size_t)i])) return false;
         return n > 0;
@@ -318,32 +312,27 @@ struct SolveRun {
         if (tgt) { target.resize((size_t)n); for (int i = 0; i < n; ++i) target[(size_t)i] = tgt[origin[(size_t)i]]; }
         keys.assign((size_t)n, 0); prev.assign((size_t)n, ~0ull); t_best.assign((size_t)n, 0.0); dual_target.assign((size_t)n, -1);
         ub_seen.assign((size_t)n, INT64_MAX); bound_quiet.assign((size_t)n, 0); bound_turn.assign((size_t)n, 0); bound_ran.assign((size_t)n, 0);
-        { const char *e = std::getenv("KAO_X_BOUND_REST"); if (e && *e) bound_rest_slots = std::atoll(e); }   // experiment knob: slots beyond which K-bound rests (huge = never)
         dkeys.assign((size_t)n, ~0ull); gprev.assign((size_t)n, ~0ull); inc_key.assign((size_t)n, ~0ull); inc_assign.assign((size_t)n, {});
         this->topics = topics;
         t_improved.assign((size_t)n, 0.0); t_cx.assign((size_t)n, 0.0); cx_seen.assign((size_t)n, ~0ull);
         cx_started.assign((size_t)n, {});
         lp_ctx.assign((size_t)n, nullptr); lp_marks.assign((size_t)n, 0); lp_read.assign((size_t)n, 0); lp_all.assign((size_t)n, 0); lp_state.assign((size_t)n, 0); lp_try.assign((size_t)n, 0); lp_certified.assign((size_t)n, 0); bound_merges.assign((size_t)n, 0); lp_tgt.assign((size_t)n, -1);
         {   // test / experiment hooks: KAO_LP=0 switches KAO-LP off, KAO_LP_AFTER / KAO_LP_PER_LAUNCH / KAO_LP_MIN_SLOTS override the counts
-            auto env_i = [](const char *name, int64_t dflt) { const char *e = std::getenv(name); return e && *e ? (int64_t)std::atoll(e) : dflt; };
-            lp_on = (int)env_i("KAO_LP", 1);
-            lp_after_small = (int)env_i("KAO_LP_AFTER", lp_after_small);
-            lp_per_launch = (int)std::max<int64_t>(1, env_i("KAO_LP_PER_LAUNCH", lp_per_launch));
-            lp_min_slots = env_i("KAO_LP_MIN_SLOTS", lp_min_slots);
-            lp_huge_first = env_i("KAO_LP_HUGE_FIRST", 0) != 0;
-            lp_round_on = env_i("KAO_LP_ROUND", 1) != 0;
-            lp_max_tries = env_i("KAO_LP_TRIES", 3);
-            lp_max_running = (int)std::max<int64_t>(1, env_i("KAO_LP_MAX_RUNNING", lp_max_running));
-            if (const char *e = std::getenv("KAO_LP_TOL")) lp_tol = std::atof(e);
-            lp_retry_test = env_i("KAO_LP_RETRY_TEST", 0) != 0;
-            if (const char *e = std::getenv("KAO_LP_PERT")) lp_pert_env = std::atof(e);
-            if (const char *e = std::getenv("KAO_LP_FIRST_S")) lp_first_s = std::atof(e);
-            if (const char *e = std::getenv("KAO_LP_ALONE_S")) lp_alone_s = std::atof(e);
-            if (const char *e = std::getenv("KAO_LP_SOLO_S")) lp_solo_s = std::atof(e);
-            lp_solo_slots = env_i("KAO_LP_SOLO_SLOTS", 32768);
+            lp_on = (int)env_int("KAO_LP", 1);
+            lp_after_small = (int)env_int("KAO_LP_AFTER", lp_after_small);
+            lp_per_launch = (int)std::max<int64_t>(1, env_int("KAO_LP_PER_LAUNCH", lp_per_launch));
+            lp_min_slots = env_int("KAO_LP_MIN_SLOTS", lp_min_slots);
+            lp_round_on = env_int("KAO_LP_ROUND", 1) != 0;
+            lp_max_tries = env_int("KAO_LP_TRIES", 3);
+            lp_max_running = (int)std::max<int64_t>(1, env_int("KAO_LP_MAX_RUNNING", lp_max_running));
+            lp_tol = env_real("KAO_LP_TOL", lp_tol);
+            lp_retry_test = env_int("KAO_LP_RETRY_TEST", 0) != 0;
+            lp_pert_env = env_real("KAO_LP_PERT", lp_pert_env);
+            lp_solo_s = env_real("KAO_LP_SOLO_S", lp_solo_s);
+            lp_solo_slots = env_int("KAO_LP_SOLO_SLOTS", 32768);
         }
         cx_on = so.use_cycles >= 0;
-        { const char *e = std::getenv("KAO_CX_EAGER"); cx_eager = e && e[0] == '1'; }
+        cx_eager = env_int("KAO_CX_EAGER", 0) != 0;
         cx_ctx.assign((size_t)n, nullptr);
         cx_slice = std::max(0.1, 0.1 * (so.time_limit_s > 0 ? so.time_limit_s : 10.0));
         deadline = t_start + (so.time_limit_s > 0 ? so.time_limit_s : 10.0);
@@ -356,35 +345,30 @@ struct SolveRun {
         {   // the counts of the deterministic schedule, from the size of the largest topic (constants measured on one MI355X so
             // that a K-bound launch takes about as long as a K-search launch and KAO-CX gets about the share of the wall clock
             // the time slices of the wall-clock schedule gave it).  Test / tuning hooks: KAO_DET_*.
-            int64_t slots = 1; int maxB = 1;
-            for (int i = 0; i < n; ++i) {
-                slots = std::max<int64_t>(slots, (int64_t)topics[i].n_partitions * std::max(topics[i].rf, 1));
-                maxB = std::max(maxB, topics[i].n_brokers);
-            }
-            const DetPlan dp = det_plan(slots, maxB, n, o.iters_per_launch);
+            int64_t slots = 1;
+            for (int i = 0; i < n; ++i) slots = std::max<int64_t>(slots, (int64_t)topics[i].n_partitions * std::max(topics[i].rf, 1));
+            const DetPlan dp = det_plan(slots, o.iters_per_launch);
             if (det && o.dual_iters == 0) dual_now = dual_iters = dp.bound_iters;
             cx_stall_iters = dp.cx_stall_iters; cx_due_iters = dp.cx_due_iters; cx_rounds = dp.cx_rounds;
-            auto env_i = [](const char *name, int64_t dflt) { const char *e = std::getenv(name); return e && *e ? (int64_t)std::atoll(e) : dflt; };
-            if (det) { dual_now = dual_iters = dual_iters > 0 ? (int)env_i("KAO_DET_BOUND_ITERS", dual_iters) : 0; }
-            cx_stall_iters = env_i("KAO_DET_CX_STALL", cx_stall_iters); cx_due_iters = env_i("KAO_DET_CX_DUE", cx_due_iters);
-            cx_rounds = (int)env_i("KAO_DET_CX_ROUNDS", cx_rounds);
+            if (det) { dual_now = dual_iters = dual_iters > 0 ? (int)env_int("KAO_DET_BOUND_ITERS", dual_iters) : 0; }
+            cx_stall_iters = env_int("KAO_DET_CX_STALL", cx_stall_iters); cx_due_iters = env_int("KAO_DET_CX_DUE", cx_due_iters);
+            cx_rounds = (int)env_int("KAO_DET_CX_ROUNDS", cx_rounds);
             // further KAO-CX starting points per call (further_starts): where a round is cheap (closures of (B + 1)^2 entries, <= 512
             // realisations of P rows) eight more descents cost about as much as the launches between two calls
-            cx_starts = (int)env_i("KAO_DET_CX_STARTS", slots <= 16384 ? 8 : 0);
-            cx_starts_first = (int)env_i("KAO_DET_CX_STARTS_FIRST", 2 * cx_starts);
-            cx_start_rounds = (int)env_i("KAO_DET_CX_START_ROUNDS", 16);
+            cx_starts = (int)env_int("KAO_DET_CX_STARTS", slots <= 16384 ? 8 : 0);
+            cx_starts_first = (int)env_int("KAO_DET_CX_STARTS_FIRST", 2 * cx_starts);
+            cx_start_rounds = (int)env_int("KAO_DET_CX_START_ROUNDS", 16);
             start_budget.assign((size_t)n, cx_starts_first); start_near.assign((size_t)n, 0);
         }
         gens_on = allow_gens && det && cx_on && !has_target;
-        { const char *e = std::getenv("KAO_DET_GEN"); if (e && e[0] == '0') gens_on = false; }
+        if (env_int("KAO_DET_GEN", 1) == 0) gens_on = false;
         {   // a new population needs time in proportion to the topic to catch up with the one it replaces (1000 x 30000, 3 s: a
             // restart after 32 quiet launches cost 100 units): the patience grows with the largest topic's replica slots
             int64_t slots = 1;
             for (int i = 0; i < n; ++i) slots = std::max<int64_t>(slots, (int64_t)topics[i].n_partitions * std::max(topics[i].rf, 1));
-            gen_stall_iters = 32 * std::max<int64_t>(1, slots / 8192) * (int64_t)std::max(o.iters_per_launch, 1);
+            gen_stall_iters = env_int("KAO_DET_GEN_STALL_L", 32 * std::max<int64_t>(1, slots / 8192)) * (int64_t)std::max(o.iters_per_launch, 1);
         }
-        { const char *e = std::getenv("KAO_DET_GEN_STALL_L"); if (e && *e) gen_stall_iters = std::atoll(e) * (int64_t)std::max(o.iters_per_launch, 1); }
-        { const char *e = std::getenv("KAO_SOLVE_TRACE"); trace = e && e[0] == '1'; }
+        trace = env_int("KAO_SOLVE_TRACE", 0) != 0;
         t_prev = t_start;
         use_prices = so.use_prices >= 0;
         return KAO_OK;
@@ -511,11 +495,11 @@ struct SolveRun {
             int best = -1; int64_t best_slots = 0;
             for (int i = 0; i < n; ++i) {
                 if (lp_state[(size_t)i] != 0 || !s->dual_ok[(size_t)i] || s->topic_infeasible[(size_t)i] || (feasible(i) && objective(i) >= s->ub[(size_t)i])) continue;
-                if (huge(i) && !lp_huge_first) {   // ... once KAO-CX has run the incumbent to a fixpoint (or cannot run) -- or, when the time
+                if (huge(i)) {   // ... once KAO-CX has run the incumbent to a fixpoint (or cannot run) -- or, when the time
                     // limit leaves room for it (a limit is an input, not the clock), straight after the first feasible incumbent: its
                     // primal side makes the fixpoint unnecessary
                     const bool cx_can = cx_on && cycle_supported(&topics[i]);
-                    const bool lp_now = lp_round_on && (lp_first_s > 0 ? deadline - t0 >= lp_first_s : lp_fits(i, 0.2));
+                    const bool lp_now = lp_round_on && lp_fits(i, 0.2);
                     if (!lp_alone(i) && (!feasible(i) || (!lp_now && cx_can && (dkeys[(size_t)i] >> 20) != (cx_seen[(size_t)i] >> 20)))) continue;
                 }
                 const int64_t slots = (int64_t)topics[i].n_partitions * topics[i].rf;
@@ -751,8 +735,7 @@ struct SolveRun {
         int32_t st[8];
         // the clock only ends a deterministic call at the solve's own deadline (the stop condition)
         const double slice_end = det ? deadline : std::min(deadline, now_s() + cx_slice);
-        static const bool pairs_all = [] { const char *e = std::getenv("KAO_CX_PAIRS_ALL"); return e && e[0] == '1'; }();   // experiment hook
-        int rc = cycle_run(cx_ctx[(size_t)i], cx_buf.data(), rounds, slice_end, &obj, st, &SolveRun::poll_bound, this, is_elite || pairs_all);
+        int rc = cycle_run(cx_ctx[(size_t)i], cx_buf.data(), rounds, slice_end, &obj, st, &SolveRun::poll_bound, this, is_elite);
         ++cx_calls;
         if (rc) return rc;
         if (reached) *reached = obj;
@@ -1097,7 +1080,7 @@ struct LoopTable : Rccl {
         GroupStart = &loop_GroupStart; GroupEnd = &loop_GroupEnd; AllReduce = &loop_AllReduce; Broadcast = &loop_Broadcast;
     }
 } g_loop;
-bool loopback_wanted() { const char *e = std::getenv("KAO_RCCL_LOOPBACK"); return e && e[0] == '1'; }
+bool loopback_wanted() { return env_int("KAO_RCCL_LOOPBACK", 0) != 0; }
 
 struct CommSet { std::vector<int> devices; const Rccl *api; std::vector<ncclComm_t> comms; };
 std::vector<CommSet> g_comms;   // communicators per (device list, function table) (creation costs ~100 ms with RCCL; kept until kao_shutdown)
@@ -1210,7 +1193,7 @@ int kao_solve_multi(const kao_topic *topics, int32_t n_topics, const int32_t *de
     // devices (driven by device 0's solve loop through lp_open_fan; the other devices' loops launch no K-search while it has the GPUs).
     // Exercised on logical shards only (tests/test_gpu_parity.py); the race stays the default until a multi-GPU node has timed both.
     bool shard_lp = false, lp_pause = false;
-    { const char *e = std::getenv("KAO_MULTI_LP"); shard_lp = race && e && e[0] == 's' && (distinct || loopback_wanted()); }
+    { const char *e = env_str("KAO_MULTI_LP"); shard_lp = race && e && e[0] == 's' && (distinct || loopback_wanted()); }
     // ---- shards: LPT by brokers x partitions (independent sub-problems, README.md:146-184) ----
     std::vector<std::vector<int>> shard((size_t)n_dev);
     if (replicated) for (auto &sh : shard) for (int i = 0; i < n_topics; ++i) sh.push_back(i);
@@ -1625,7 +1608,7 @@ extern "C" {
 // units, which is where the exact joint optimum's prices often lie), half and whole units different plans -- which granularity finds
 // the best cap-respecting plan varies by instance (medium golden: plan 9169 / 9175 / 9169 with F = 4 / 2 / 1, the 12-topic case 4095 /
 // 4093 / 4097).  The runs share the time limit; the best plan and the smallest bound of all runs are returned, and the portfolio ends as
-// soon as they meet.  KAO_CAP_F=<n> (test hook): one run at that granularity.
+// soon as they meet.
 int kao_solve_capped(const kao_topic *topics, int32_t n_topics, const int32_t *replica_cap, const int32_t *devices, int32_t n_dev,
                      const kao_opts *opts, int32_t max_rounds, kao_result *results, int64_t *lagrangian_bound) {
     const double t0 = now_s();
@@ -1633,8 +1616,7 @@ int kao_solve_capped(const kao_topic *topics, int32_t n_topics, const int32_t *r
     int wmax = 1;
     for (int i = 0; i < n_topics; ++i) for (int a = 0; a < 2; ++a) for (int b = 0; b < 2; ++b) wmax = std::max(wmax, topics[i].w[a][b]);
     std::vector<int> fs;
-    if (const char *e = std::getenv("KAO_CAP_F")) fs.push_back(std::max(1, std::min(8, std::atoi(e))));
-    else for (int f : {4, 2, 1}) if (f == 1 || wmax * f <= 255) fs.push_back(f);   // F = 1 always runs (weights up to 1023 are valid; only the scaled runs need room)
+    for (int f : {4, 2, 1}) if (f == 1 || wmax * f <= 255) fs.push_back(f);   // F = 1 always runs (weights up to 1023 are valid; only the scaled runs need room)
     kao_opts o{};
     if (opts) o = *opts;
     const double limit = o.time_limit_s > 0 ? o.time_limit_s : 10.0;

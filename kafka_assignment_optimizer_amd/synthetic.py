@@ -154,7 +154,7 @@ def north_star_topic(which: str) -> Topic:
     raise ValueError("north_star_topic: drift30k | drift5k | drift100k | cfg5one")
 
 
-def north_star_steps(kao, which: str, launches: int = 6, iters: int = 512, restarts: int = 0) -> dict:
+def north_star_steps(kao, which: str, launches: int = 6, iters: int = 512, restarts: int = 0, team: int = 0) -> dict:
     """`launches` K-search + K-eval steps of a session on north_star_topic(which) after the init launch: per-launch HIP-event
     times and SURVEY.md 8(d)'s algorithmic bytes (`kao` = the package, initialised)."""
     import time
@@ -162,6 +162,8 @@ def north_star_steps(kao, which: str, launches: int = 6, iters: int = 512, resta
     opts = dict(seed=3, iters_per_launch=iters, profile=1)
     if restarts:
         opts["restarts"] = restarts
+    if team:
+        opts["team"] = team
     with kao.Session([t], **opts) as s:
         s.step(1)                      # launch 0: best-insertion init + the first iterations (not timed)
         s.sync()

@@ -339,3 +339,26 @@ def test_bench_result_line_is_short_and_strict_json():
     for k in ("value", "unit", "cores", "kind"):
         assert k in back["cpu_baseline"], k
     assert all(not isinstance(v, str) or len(v) <= 200 for d in back.values() if isinstance(d, dict) for v in d.values())
+
+
+def test_environment_table_names_exactly_the_switches_the_library_reads():
+    """INTEGRATION.md section 9 lists one row per KAO_* variable, and those are exactly the names csrc/ reads through env_int /
+    env_real / env_str (kao_host.h).  The only other read is launch_init's own clamp of KAO_INIT_WAVES in kao_kernels.hip."""
+    csrc = os.path.join(ROOT, "kafka_assignment_optimizer_amd", "csrc")
+    read, raw = set(), set()
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".cpp", ".hip", ".h")):
+            continue
+        src = open(os.path.join(csrc, name)).read()
+        read |= set(re.findall(r'\benv_(?:int|real|str)\(\s*"(KAO_[A-Z0-9_]+)"', src))
+        if name != "kao_host.h":
+            raw |= {(name, v) for v in re.findall(r'getenv\(\s*"?([A-Za-z0-9_]*)', src)}
+    assert raw <= {("kao_kernels.hip", "KAO_INIT_WAVES")}, raw
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 9. Environment hooks"):]
+    section = section[:section.find("\n## ")] if "\n## " in section else section
+    rows = [line.split("|")[1] for line in section.splitlines() if line.startswith("| `KAO_")]
+    listed = [n for cell in rows for n in re.findall(r"KAO_[A-Z0-9_]+", cell)]
+    assert len(listed) == len(set(listed)), sorted(n for n in listed if listed.count(n) > 1)
+    assert len(rows) == len(listed), "one variable per row"
+    assert set(listed) == read, (sorted(set(listed) - read), sorted(read - set(listed)))

@@ -1,7 +1,7 @@
 """GPU (round 6): KAO-LP's dense kernels (kao_chol.hip) through the kao_dense_spd_test hook against numpy: factor, diagonal-tile
-inverses, solution; then the interior point on drifted topics with the rack block / broker rows switched between their variants
-(KAO_LP_RACK, KAO_LP_BROKER_U).  (Until commit "remove round 5's dense kernels" the "old" mode also ran round 5's Cholesky and
-triangular solves, KAO_LP_DENSE=old: profiles/r06_c01 / r06_c02 hold those A/B runs.)"""
+inverses, solution; then the interior point on drifted topics: iterations, time per iteration, and two lp_bound calls that must agree
+bit for bit.  (profiles/r06_c01 / r06_c02 hold the A/B runs of round 5's dense kernels and of the rack / broker-row variants that
+this probe used to switch.)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,30 +37,10 @@ print("dependent row 70: L[70,70] =", d["factor"][70, 70], " x[70] =", d["x"][70
 
 def run(pt, tag):
     kao.lp_trace(pt, max_iters=1)
-    out = {}
-    for mode in ("old", "new"):
-        os.environ["KAO_LP_DENSE"] = mode; os.environ["KAO_LP_RACK"] = mode; os.environ["KAO_LP_BROKER_U"] = "4" if mode == "old" else "8"
-        t0 = time.perf_counter(); d = kao.lp_trace(pt, max_iters=200); dt = time.perf_counter() - t0
-        out[mode] = d
-        print(f"{tag} dense={mode}: status {d['status']} it {d['iterations']} primal {d['primal']:.6f} dual {d['dual']:.6f} ipm {d['ms']:.1f} ms = {d['ms']/max(1,d['iterations']):.3f} ms/it (call {dt*1e3:.0f} ms)", flush=True)
-    a, b = out["old"]["trace"], out["new"]["trace"]
-    m = min(len(a), len(b)); worst = 0.0
-    for i in range(m):
-        if a[i][0] > 1e-6:
-            worst = max(worst, abs(a[i][0] - b[i][0]) / a[i][0], abs(a[i][1] - b[i][1]) / max(1, abs(a[i][1])), abs(a[i][2] - b[i][2]) / max(1, abs(a[i][2])))
-    print(f"   worst relative trace deviation new vs old while mu > 1e-6: {worst:.2e}; multipliers max diff {np.abs(out['old']['a'].astype(np.int64) - out['new']['a']).max()}", flush=True)
-    os.environ["KAO_LP_DENSE"] = "new"
-    if pt.n_partitions >= 30000:
-        for u in ("4", "16"):
-            os.environ["KAO_LP_BROKER_U"] = u
-            d = kao.lp_trace(pt, max_iters=200)
-            print(f"   broker U={u}: it {d['iterations']} ipm {d['ms']:.1f} ms = {d['ms']/max(1,d['iterations']):.3f} ms/it", flush=True)
-        os.environ["KAO_LP_BROKER_U"] = "8"; os.environ["KAO_LP_RACK"] = "old"
-        d = kao.lp_trace(pt, max_iters=200)
-        print(f"   rack block by the LDS-tiled kernel: it {d['iterations']} ipm {d['ms']:.1f} ms = {d['ms']/max(1,d['iterations']):.3f} ms/it", flush=True)
-        os.environ["KAO_LP_RACK"] = "new"
+    t0 = time.perf_counter(); d = kao.lp_trace(pt, max_iters=200); dt = time.perf_counter() - t0
+    print(f"{tag}: status {d['status']} it {d['iterations']} primal {d['primal']:.6f} dual {d['dual']:.6f} ipm {d['ms']:.1f} ms = {d['ms']/max(1,d['iterations']):.3f} ms/it (call {dt*1e3:.0f} ms)", flush=True)
     b1 = kao.lp_bound(pt); b2 = kao.lp_bound(pt)
-    print(f"   lp_bound x2 (new): certificate {b1['bound']} / {b2['bound']}, same bits: {np.array_equal(b1['a'], b2['a']) and b1['best_dual'] == b2['best_dual']}", flush=True)
+    print(f"   lp_bound x2: certificate {b1['bound']} / {b2['bound']}, same bits: {np.array_equal(b1['a'], b2['a']) and b1['best_dual'] == b2['best_dual']}", flush=True)
 
 for (B, R, P) in ((100, 5, 1000), (130, 5, 1000), (500, 10, 5000)):
     run(sy.drift(sy.make_cluster(B, R, 1, P, 3, [], []), 0.2, 1)[0], f"{B}x{P}")
