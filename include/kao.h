@@ -156,7 +156,8 @@ typedef struct kao_stats {
     int32_t drift;              /* restarts whose incrementally tracked (V, objective) disagreed with the
                                    from-scratch recount at the end of a launch; must be 0 */
     int32_t launch_groups;      /* topics are bucketed by LDS footprint; one K-search + K-eval launch per group */
-    int32_t reserved;
+    int32_t search_rf3_launches;/* K-search launches (one per launch group and step) that ran the RF-3 instantiation: every topic of
+                                   the group has RF 3 and at most 3 current replicas, LDS-resident, unpriced.  Was `reserved`. */
 } kao_stats;
 
 typedef struct kao_session kao_session;

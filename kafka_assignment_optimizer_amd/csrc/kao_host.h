@@ -114,6 +114,7 @@ struct kao_session {
         int waves = kWaves;  // restarts per K-search workgroup: 4, 2 or 1 -- the largest whose LDS carve fits 160 KiB
         int nw = kRFP;       // replica words per partition of the group's topics: 4 or 8 (template instantiation)
         int rf_uniform = -1; // the RF all topics of the group share (0: mixed; -1: no topic yet)
+        bool rf3 = true;     // every topic has RF 3 and at most 3 current replicas per partition: K-search may run its RF-3 instantiation
         bool global_a = false;   // topic too large for LDS: assignment + current words stay in global memory
         bool cur_global = false; // (round 5) only the current-assignment words stay in global memory / L2, the working words are in LDS (~4,900 .. 9,800 partitions)
         int team = 0;            // > 0 (global_a only): every restart is searched by a TEAM of that many wavefronts (k_team), one workgroup per restart
@@ -186,6 +187,7 @@ struct kao_session {
     double ms_search = 0, ms_eval = 0;
     uint64_t eval_bytes_per_launch = 0;
     uint64_t delta_total = 0, search_bytes_total = 0;
+    uint64_t search_rf3_launches = 0;   // K-search launches that ran the RF-3 instantiation (kao_stats)
 };
 
 namespace kao {

@@ -155,7 +155,10 @@ constexpr int search_rack_tab(int maxR) { return ((maxR < 1 ? 1 : maxR) + 1 + 63
 // cur_global: only the working assignment in LDS, the current assignment read from global memory (k_search_curg, round 5)
 size_t search_lds_bytes(int maxP, int maxBx, int waves, bool global_a, bool priced = false, int nw = 4, bool bw = false, int maxR = kRackTab - 1, int team = 0, bool cur_global = false);
 size_t eval_lds_bytes(int maxP, int maxB, bool cur_in_lds, int ne = 4);
-void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team = 0);
+// rft = 3: every topic of the group has RF 3 and at most 3 current replicas per partition -- the launch runs the RF-3 instantiation of
+// k_search when search_rf3_eligible (LDS-resident, unpriced, four words per partition, no team); else, and for rft = 0, the generic one
+bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, int team);
+void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team = 0, int rft = 0);
 bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, void *stream);   // K-init (topics in global memory)
 void launch_eval(const EvalPools &pools, int n_blocks, int ne, void *stream);
 // copy every topic's winning snapshot (restart id in its packed key) and violation row into contiguous

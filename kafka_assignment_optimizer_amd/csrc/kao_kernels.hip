@@ -105,18 +105,29 @@ __device__ __forceinline__ int bw_of(uint32_t bw, bool lead) { return (int)(bw &
 // fixed point (kDualScale) -> key units (obj_scale per objective unit), rounded half up, clamped to 16 bits
 __device__ __forceinline__ int price_units(int v, int S) { return min(max((S * v + kDualScale / 2) >> kDualLog2, -32767), 32767); }
 
-template <int NW> __device__ __forceinline__ bool in4(const Part<NW> &a, uint32_t w) {
+// NS > 0 (the RF-3 instantiation of k_search): only words 0..NS-1 are compared.  The words beyond hold kNoneW, which equals no
+// broker word and whose rack field 0xFFFF equals no rack, so leaving them out changes no result.
+template <int NS = 0, int NW> __device__ __forceinline__ bool in4(const Part<NW> &a, uint32_t w) {
     bool r = false;
 #pragma unroll
-    for (int i = 0; i < NW; ++i) r |= a.w[i] == w;
+    for (int i = 0; i < (NS ? NS : NW); ++i) r |= a.w[i] == w;
     return r;
 }
 // replicas of the partition that sit in rack r (empty slots carry rack 0xFFFF and never match)
-template <int NW> __device__ __forceinline__ int cnt4(const Part<NW> &a, uint32_t r) {
+template <int NS = 0, int NW> __device__ __forceinline__ int cnt4(const Part<NW> &a, uint32_t r) {
     int n = 0;
 #pragma unroll
-    for (int i = 0; i < NW; ++i) n += (int)((a.w[i] >> 16) == r);
+    for (int i = 0; i < (NS ? NS : NW); ++i) n += (int)((a.w[i] >> 16) == r);
     return n;
+}
+// slot k < NS of a partition: three slots take two selects (the words pass through an empty asm first: selects between words of
+// the struct were turned into a dynamically indexed copy of it in scratch)
+template <int NS, int NW> __device__ __forceinline__ uint32_t sel_slot(const Part<NW> &a, int k) {
+    if constexpr (NS == 3 && NW == 4) {
+        uint32_t w0 = a.w[0], w1 = a.w[1], w2 = a.w[2];
+        asm("" : "+v"(w0), "+v"(w1), "+v"(w2));
+        return (k & 2) ? w2 : ((k & 1) ? w1 : w0);
+    } else return sel4(a, k);
 }
 
 __device__ __forceinline__ uint32_t make_key_tie(int lam, int S, int dV, int dObj, uint32_t tie) {
@@ -133,14 +144,15 @@ struct TopicRegs {  // wave-uniform copy of the fields the inner loop needs
 };
 
 // objective weight of broker word w on a partition whose current replicas are c, in new role nr
-template <int NW> __device__ __forceinline__ int role_w2(const Part<NW> &c, uint32_t w, int wl, int wf) {
+// (NS as in in4: words 0..NS-1 only)
+template <int NS = 0, int NW> __device__ __forceinline__ int role_w2(const Part<NW> &c, uint32_t w, int wl, int wf) {
     bool fol = false;
 #pragma unroll
-    for (int i = 1; i < NW; ++i) fol |= c.w[i] == w;
+    for (int i = 1; i < (NS ? NS : NW); ++i) fol |= c.w[i] == w;
     return (c.w[0] == w) ? wl : (fol ? wf : 0);
 }
-template <int NW> __device__ __forceinline__ int role_w(const TopicRegs &T, const Part<NW> &c, uint32_t w, int nr) {
-    return role_w2(c, w, nr ? T.w01 : T.w00, nr ? T.w11 : T.w10);
+template <int NS = 0, int NW> __device__ __forceinline__ int role_w(const TopicRegs &T, const Part<NW> &c, uint32_t w, int nr) {
+    return role_w2<NS>(c, w, nr ? T.w01 : T.w00, nr ? T.w11 : T.w10);
 }
 // internal index -> LDS word (x | rack << 16); 0xFFFF -> empty
 __device__ __forceinline__ uint32_t to_word(const TopicRegs &T, uint32_t x) {
@@ -319,10 +331,16 @@ template <int NW> __device__ __forceinline__ void snapshot(const TopicRegs &T, c
 //                   moves commute, so violation and objective deltas add up.  A 30,000-partition topic gets W moves per
 //                   latency-bound iteration instead of one (the depth large topics lack), deterministically (specification:
 //                   oracle/kao_port.c::ls_run with team > 1, replayed bit for bit).
-template <bool kGlobalA, bool kPriced, int NW, bool kWide, bool kTeam, bool kCurG = false>
+// RFT = 3        : (LDS-resident, NW = 4) every topic of the launch has RF 3 and at most 3 current replicas per partition, so word 3 of
+//                   both the working and the current words is always kNoneW (no move writes a slot k >= RF).  The move arithmetic
+//                   visits words 0..2 only and the slot loops run 2 / 3 times without `k >= RF` guards; memory layout and results
+//                   are those of RFT = 0 (RF read per topic).
+template <bool kGlobalA, bool kPriced, int NW, bool kWide, bool kTeam, bool kCurG = false, int RFT = 0>
 __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPools &pl, const SearchParams &prm) {
     static_assert(!kTeam || kGlobalA, "teams run topics that live in global memory");
     static_assert(!kCurG || !kGlobalA, "kCurG: the working assignment is in LDS");
+    static_assert(RFT == 0 || (RFT == 3 && NW == 4 && !kGlobalA && !kTeam), "RFT = 3: LDS-resident topics of four words per partition");
+    constexpr int NS = RFT ? RFT : NW;   // words of a partition the move arithmetic visits
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n_waves = kTeam ? __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6)) : 1;   // team size W
@@ -331,7 +349,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     const TopicDev *TD = pl.topics + bm.x;
 
     TopicRegs T;
-    T.P = TD->P; T.RF = TD->RF; T.R = TD->R; T.m = TD->m; T.Bx = TD->Bx; T.magic = TD->magic;
+    T.P = TD->P; T.RF = RFT ? RFT : TD->RF; T.R = TD->R; T.m = TD->m; T.Bx = TD->Bx; T.magic = TD->magic;
     T.rep_lo = TD->rep_lo; T.rep_hi = TD->rep_hi; T.lead_lo = TD->lead_lo; T.lead_hi = TD->lead_hi;
     T.rack_lo = TD->rack_lo; T.rack_hi = TD->rack_hi; T.prack_lo = TD->prack_lo; T.prack_hi = TD->prack_hi;
     T.w00 = TD->w00; T.w01 = TD->w01; T.w10 = TD->w10; T.w11 = TD->w11;
@@ -587,15 +605,15 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
             const Part<NW> c = CUR[p];
             if (type == 0) {  // REPLACE (p,k) <- x_g: 2 candidates of any rack, 2 of the old broker's rack
                 k = (int)rnd24(rng, RF8);
-                uw = sel4(a, k);
+                uw = sel_slot<NS>(a, k);
                 const uint32_t ro = uw >> 16;
                 const bool lead = k == 0;
                 const uint32_t lw = lead ? 2u : 0u;   // width of a leader field: a zero-width extract yields 0 for follower slots
                 const int wl = lead ? T.w00 : T.w01, wf = lead ? T.w10 : T.w11;
-                const int g_old = role_w2(c, uw, wl, wf) + (hbw ? bw_of(BW[uw & 0xFFFFu], lead) : 0);
+                const int g_old = role_w2<NS>(c, uw, wl, wf) + (hbw ? bw_of(BW[uw & 0xFFFFu], lead) : 0);
                 const uint32_t wo = L.W[uw & 0xFFFFu];
                 const int dV_old = wfld(wo, kWDecR) + wfldw(wo, kWDecL, lw);
-                const int dV_rack_old = ddec(L.K[ro], T.rack_lo, T.rack_hi) + ddec(cnt4(a, ro), T.prack_lo, T.prack_hi);
+                const int dV_rack_old = ddec(L.K[ro], T.rack_lo, T.rack_hi) + ddec(cnt4<NS>(a, ro), T.prack_lo, T.prack_hi);
                 const int rsz_ro = RSZ[ro];
                 int dP_old = 0, dP_rack_old = 0;
                 if (kPriced) {
@@ -619,14 +637,14 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     }
                     const uint32_t x = __umul24(r, (uint32_t)T.m) + jj;
                     const uint32_t xw = x | (r << 16);
-                    okg = okg && !in4(a, xw);
+                    okg = okg && !in4<NS>(a, xw);
                     const uint32_t wn = L.W[x];
                     int dVg = dV_old + wfld(wn, kWIncR) + wfldw(wn, kWIncL, lw);
                     if (g < 2) {
                         if (r != ro)
-                            dVg += dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + dinc(cnt4(a, r), T.prack_lo, T.prack_hi);
+                            dVg += dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + dinc(cnt4<NS>(a, r), T.prack_lo, T.prack_hi);
                     }
-                    const int dObjg = role_w2(c, xw, wl, wf) + (hbw ? bw_of(BW[x], lead) : 0) - g_old;
+                    const int dObjg = role_w2<NS>(c, xw, wl, wf) + (hbw ? bw_of(BW[x], lead) : 0) - g_old;
                     uint32_t keyg;
                     if (kPriced) {
                         const uint32_t prx = PR[x];
@@ -640,15 +658,15 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 }
             } else {  // LEADER SWAP inside p: slot 0 <-> slot k, every k = 1..RF-1 is a candidate
                 uw = a.w[0];
-                const int u_lead = role_w2(c, uw, T.w00, T.w10), u_fol = role_w2(c, uw, T.w01, T.w11);
+                const int u_lead = role_w2<NS>(c, uw, T.w00, T.w10), u_fol = role_w2<NS>(c, uw, T.w01, T.w11);
                 const uint32_t wu = L.W[uw & 0xFFFFu];
                 const int dV_u = wfld(wu, kWDecL);
                 const int dP_u = kPriced ? -(wflag(wu, kWPoutL) & price_lead(PR[uw & 0xFFFFu])) : 0;
 #pragma unroll
-                for (int kk = 1; kk < NW; ++kk) {
-                    if (kk >= T.RF) break;
+                for (int kk = 1; kk < NS; ++kk) {
+                    if (!RFT && kk >= T.RF) break;
                     const uint32_t xw = a.w[kk];
-                    const int dObjg = role_w2(c, xw, T.w00, T.w10) + u_fol - u_lead - role_w2(c, xw, T.w01, T.w11) +
+                    const int dObjg = role_w2<NS>(c, xw, T.w00, T.w10) + u_fol - u_lead - role_w2<NS>(c, xw, T.w01, T.w11) +
                                       (hbw ? (int)(BW[xw & 0xFFFFu] >> 16) - (int)(BW[uw & 0xFFFFu] >> 16) : 0);
                     const uint32_t wx = L.W[xw & 0xFFFFu];
                     const int dVg = dV_u + wfld(wx, kWIncL);
@@ -675,13 +693,13 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
             //  cyclically -- on topics that live in HBM the slots of a lane then share two cache lines instead of touching 16)
             auto score_words = [&](auto ty, uint32_t &key_o, const Part<NW> &al, const Part<NW> &cl, int k_o, uint32_t &oldw_o, int &g_o, int &dvo_o, int &dvr_o) {
                 constexpr int TY = decltype(ty)::value;
-                oldw_o = sel4(al, k_o);
+                oldw_o = sel_slot<NS>(al, k_o);
                 const uint32_t rol = oldw_o >> 16;
                 const bool leadl = k_o == 0;
-                g_o = role_w2(cl, oldw_o, leadl ? T.w00 : T.w01, leadl ? T.w10 : T.w11);
+                g_o = role_w2<NS>(cl, oldw_o, leadl ? T.w00 : T.w01, leadl ? T.w10 : T.w11);
                 if (hbw && TY == 0) g_o += bw_of(BW[oldw_o & 0xFFFFu], leadl);   // a REPLACE also gives up the broker's own weight
                 const uint32_t wo = L.W[oldw_o & 0xFFFFu];
-                const int dv7 = ddec(cnt4(al, rol), T.prack_lo, T.prack_hi);
+                const int dv7 = ddec(cnt4<NS>(al, rol), T.prack_lo, T.prack_hi);
                 int sc;
                 if (TY == 0) {
                     dvo_o = wfld(wo, kWDecR) + wfldw(wo, kWDecL, leadl ? 2u : 0u);
@@ -817,8 +835,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 const uint32_t ro1 = us[0] >> 16, ro2 = us[1] >> 16;
                 for (int r = lane; r < T.R; r += 64) {
                     const int dk = dinc(L.K[r], T.rack_lo, T.rack_hi);
-                    const int v1 = ((uint32_t)r != ro1) ? v_rk[0] + dk + dinc(cnt4(a1, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
-                    const int v2 = ((uint32_t)r != ro2) ? v_rk[1] + dk + dinc(cnt4(a2, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
+                    const int v1 = ((uint32_t)r != ro1) ? v_rk[0] + dk + dinc(cnt4<NS>(a1, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
+                    const int v2 = ((uint32_t)r != ro2) ? v_rk[1] + dk + dinc(cnt4<NS>(a2, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
                     L.RT[r] = (int)(((uint32_t)v1 & 0xFFFFu) | ((uint32_t)v2 << 16));
                 }
                 // lanes 0..NW-1 look after slot 1's partition, lanes NW..2NW-1 after slot 2's: their brokers are marked, their
@@ -847,7 +865,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 const int mr_l = hm_l ? (int)((ci & 0xFFFFu) >> 6) : -1;
                 int mr[2 * NW];
 #pragma unroll
-                for (int i2 = 0; i2 < 2 * NW; ++i2) mr[i2] = __builtin_amdgcn_readlane(mr_l, i2);
+                for (int i2 = 0; i2 < 2 * NW; ++i2) mr[i2] = (i2 & (NW - 1)) < NS ? __builtin_amdgcn_readlane(mr_l, i2) : -1;   // (RFT: lanes 3 / 7 hold none)
                 const bool lead1 = ks[0] == 0, lead2 = ks[1] == 0;
                 const uint32_t lw1 = lead1 ? 2u : 0u, lw2 = lead2 ? 2u : 0u;
                 const int wl1 = lead1 ? T.w00 : T.w01, wf1 = lead1 ? T.w10 : T.w11, wl2 = lead2 ? T.w00 : T.w01, wf2 = lead2 ? T.w10 : T.w11;
@@ -868,8 +886,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     if (decltype(with_w)::value) {
                         const uint32_t x = (uint32_t)(base + lane);
                         const uint32_t xw = x | ((uint32_t)XR[x] << 16);
-                        d1 -= __mul24(S, role_w2(c1, xw, wl1, wf1));
-                        d2 -= __mul24(S, role_w2(c2, xw, wl2, wf2));
+                        d1 -= __mul24(S, role_w2<NS>(c1, xw, wl1, wf1));
+                        d2 -= __mul24(S, role_w2<NS>(c2, xw, wl2, wf2));
                     }
                     d1 = min(max(d1, 0), 2 * kDBias - 2);
                     d2 = min(max(d2, 0), 2 * kDBias - 2);
@@ -908,7 +926,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
 #pragma unroll
                     for (int i2 = 0; i2 < NW; ++i2) { mx1 = max(mx1, mr[i2]); mx2 = max(mx2, mr[NW + i2]); }
                     const bool has_missing = (two ? mx2 : mx1) >= 0;
-                    dObj = -(two ? gs[1] : gs[0]) + (has_missing ? (two ? role_w2(c2, vw, wl2, wf2) : role_w2(c1, vw, wl1, wf1)) : 0);
+                    dObj = -(two ? gs[1] : gs[0]) + (has_missing ? (two ? role_w2<NS>(c2, vw, wl2, wf2) : role_w2<NS>(c1, vw, wl1, wf1)) : 0);
                 }
             } else {
             uint32_t b_kmin = kKeyNull, b_uw = 0, b_vw = 0;
@@ -941,7 +959,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 {   // rack-dependent part of the delta, racks strided over the lanes
                     const int dP_rack_old = kPriced ? p_out(L.K[ro], T.rack_lo, T.rack_hi, PG[ro]) : 0;
                     for (int r = lane; r < T.R; r += 64) {
-                        int v = ((uint32_t)r != ro) ? dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + dinc(cnt4(a, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
+                        int v = ((uint32_t)r != ro) ? dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + dinc(cnt4<NS>(a, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
                         if (kPriced)  // rack part of the price delta rides in the upper 24 bits (the violation delta is within -8..8)
                             v = (v & 0xFF) | ((((uint32_t)r != ro) ? dP_rack_old + p_in(L.K[r], T.rack_lo, T.rack_hi, PG[r]) : 0) * 256);
                         L.RT[r] = v;
@@ -952,29 +970,29 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 // duration of the scan its W entry points at the reserved RT entry; (2) current replica i, when displaced (in c,
                 // not in a), is the only broker with a non-zero objective weight here: the round it falls into is scored with weights
                 const int li = lane & (NW - 1);
-                const uint32_t ai = sel4(a, li), ci = sel4(c, li);
+                const uint32_t ai = sel_slot<NS>(a, li), ci = sel_slot<NS>(c, li);
                 // (a team shares W: nothing may be marked there -- the rounds that hold a broker of the partition take the slow
                 //  path below, like the rounds with a displaced current replica, and drop it by comparison)
-                const bool holds = (lane < NW) & (ai != kNoneW);
+                const bool holds = (lane < NS) & (ai != kNoneW);
                 uint32_t w_keep = 0;
                 if (!kTeam && holds) {
                     w_keep = L.W[ai & 0xFFFFu];
                     L.W[ai & 0xFFFFu] = (uint16_t)(w_keep | kWNoCand);
                 }
-                int ar[NW];
+                int ar[NS];
                 {
                     const int ar_l = (kTeam && holds) ? (int)((ai & 0xFFFFu) >> 6) : -1;
 #pragma unroll
-                    for (int i2 = 0; i2 < NW; ++i2) ar[i2] = __builtin_amdgcn_readlane(ar_l, i2);
+                    for (int i2 = 0; i2 < NS; ++i2) ar[i2] = __builtin_amdgcn_readlane(ar_l, i2);
                 }
-                const bool hm_l = (lane < NW) & (ci != kNoneW) & !in4(a, ci);
+                const bool hm_l = (lane < NS) & (ci != kNoneW) & !in4<NS>(a, ci);
                 const int mr_l = hm_l ? (int)((ci & 0xFFFFu) >> 6) : -1;
-                int mr[NW];
+                int mr[NS];
 #pragma unroll
-                for (int i2 = 0; i2 < NW; ++i2) mr[i2] = __builtin_amdgcn_readlane(mr_l, i2);
+                for (int i2 = 0; i2 < NS; ++i2) mr[i2] = __builtin_amdgcn_readlane(mr_l, i2);
                 bool has_missing = false;
 #pragma unroll
-                for (int i2 = 0; i2 < NW; ++i2) has_missing |= mr[i2] >= 0;
+                for (int i2 = 0; i2 < NS; ++i2) has_missing |= mr[i2] >= 0;
                 // cost + bias of a candidate = lam * (its own delta + dV_old) + S * g_old (+ prices) (- S * weight of a displaced
                 // current replica): everything that does not depend on the candidate is one wave-uniform constant
                 int K0 = __mul24(S, g_old) + kDBias + __mul24(lam, dV_old);
@@ -1007,8 +1025,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     if (decltype(with_w)::value) {
                         const uint32_t x = (uint32_t)(base + lane);
                         const uint32_t xw = x | ((uint32_t)XR[x] << 16);
-                        dsc -= __mul24(S, role_w2(c, xw, wl, wf));
-                        if (kTeam && in4(a, xw)) member = 0xFFFF0000u;   // row C5: already in the partition
+                        dsc -= __mul24(S, role_w2<NS>(c, xw, wl, wf));
+                        if (kTeam && in4<NS>(a, xw)) member = 0xFFFF0000u;   // row C5: already in the partition
                     }
                     dsc = min(max(dsc, 0), 2 * kDBias - 2);
                     // a "no candidate" index gets a cost field of 0xFFFF: above every real cost (<= 2 * kDBias - 2) and never accepted
@@ -1017,7 +1035,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 auto is_weighted = [&](int rdg) {   // wave-uniform
                     bool wgt = false;
 #pragma unroll
-                    for (int i2 = 0; i2 < NW; ++i2) wgt |= (mr[i2] == rdg) | (kTeam && ar[i2] == rdg);
+                    for (int i2 = 0; i2 < NS; ++i2) wgt |= (mr[i2] == rdg) | (kTeam && ar[i2] == rdg);
                     return wgt;
                 };
                 for (int cb = 0; cb < T.Bx; cb += 16384) {
@@ -1049,7 +1067,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         while (rd < n_rd) {
                             int nxt = n_rd;   // the next weighted round of this chunk at or after rd
 #pragma unroll
-                            for (int i2 = 0; i2 < NW; ++i2) {
+                            for (int i2 = 0; i2 < NS; ++i2) {
                                 const int m = mr[i2] - rd0;
                                 if (m >= rd) nxt = min(nxt, m);
                             }
@@ -1077,13 +1095,13 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int rts = L.RT[rs];
                     vw = xs | (rs << 16);
                     dV = wfld(ws, kWIncR) + wfldw(ws, kWIncL, lw) + dV_old + (kPriced ? (int)(signed char)(rts & 0xFF) : rts);
-                    dObj = -g_old + (has_missing ? role_w2(c, vw, wl, wf) : 0) + (hbw ? bw_of(BW[xs], lead) : 0);
+                    dObj = -g_old + (has_missing ? role_w2<NS>(c, vw, wl, wf) : 0) + (hbw ? bw_of(BW[xs], lead) : 0);
                 }
                 if (si == 0 || kmin < b_kmin) { b_kmin = kmin; b_win = win; b_p = p; b_k = k; b_uw = uw; b_vw = vw; b_dV = dV; b_dObj = dObj; }
             } else {
                 // ---- phase B (EXCHANGE): every partner slot (q,j) for slot (p,k), 64 partitions per round ----
                 const int nrp = lead ? 0 : 1;
-                const int cnt_a_ru = cnt4(a, ro);
+                const int cnt_a_ru = cnt4<NS>(a, ro);
                 const uint32_t wu = L.W[uw & 0xFFFFu];
                 const int pl_u = kPriced ? price_lead(PR[uw & 0xFFFFu]) : 0;
                 const int bwl_u = hbw ? (int)(BW[uw & 0xFFFFu] >> 16) : 0;
@@ -1099,17 +1117,17 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     int qq; bool okq;
                     x_partner(rd, qq, okq);
                     okq = okq & (qq != p);
-                    const bool u_in_b = in4(b, uw);
+                    const bool u_in_b = in4<NS>(b, uw);
                     // independent of the partner slot j: what u would be worth in q, and q's replicas in u's rack
-                    const int u_in_q_lead = role_w2(cb, uw, T.w00, T.w10), u_in_q_fol = role_w2(cb, uw, T.w01, T.w11);
-                    const int cnt_b_ro = cnt4(b, ro);
+                    const int u_in_q_lead = role_w2<NS>(cb, uw, T.w00, T.w10), u_in_q_fol = role_w2<NS>(cb, uw, T.w01, T.w11);
+                    const int cnt_b_ro = cnt4<NS>(b, ro);
 #pragma unroll
-                    for (int jj = 0; jj < NW; ++jj) {
-                        if (jj >= T.RF) break;
+                    for (int jj = 0; jj < NS; ++jj) {
+                        if (!RFT && jj >= T.RF) break;
                         const uint32_t v = b.w[jj];
-                        const bool ok = okq & (v != uw) & !in4(a, v) & !u_in_b;
+                        const bool ok = okq & (v != uw) & !in4<NS>(a, v) & !u_in_b;
                         const int nrq = jj != 0;
-                        int dObjx = role_w(T, c, v, nrp) + (jj == 0 ? u_in_q_lead : u_in_q_fol) - g_old - role_w(T, cb, v, nrq);
+                        int dObjx = role_w<NS>(T, c, v, nrp) + (jj == 0 ? u_in_q_lead : u_in_q_fol) - g_old - role_w<NS>(T, cb, v, nrq);
                         int dVx = 0, dPx = 0;
                         if (lead != (jj == 0)) {  // wave-uniform: exactly one of the two slots is a leader slot
                             const uint32_t wv = L.W[v & 0xFFFFu];
@@ -1123,8 +1141,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         }
                         const uint32_t rv = v >> 16;
                         if (rv != ro)
-                            dVx += ddec(cnt_a_ru, T.prack_lo, T.prack_hi) + dinc(cnt4(a, rv), T.prack_lo, T.prack_hi) +
-                                   ddec(cnt4(b, rv), T.prack_lo, T.prack_hi) + dinc(cnt_b_ro, T.prack_lo, T.prack_hi);
+                            dVx += ddec(cnt_a_ru, T.prack_lo, T.prack_hi) + dinc(cnt4<NS>(a, rv), T.prack_lo, T.prack_hi) +
+                                   ddec(cnt4<NS>(b, rv), T.prack_lo, T.prack_hi) + dinc(cnt_b_ro, T.prack_lo, T.prack_hi);
                         uint32_t keyx;
                         if (kPriced) keyx = ok ? make_key_tie_p(lam, S, dVx, dObjx, dPx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
                         else keyx = ok ? make_key_tie(lam, S, dVx, dObjx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
@@ -1268,10 +1286,10 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
 #define KAO_WPE_WIDE 6
 #endif
 template <bool kGlobalA, bool kPriced, int NW, bool kWide> constexpr int search_min_waves() { return kGlobalA ? 1 : (kWide ? KAO_WPE_WIDE : KAO_WPE_SMALL); }
-template <bool kGlobalA, bool kPriced, int NW, bool kWide>
+template <bool kGlobalA, bool kPriced, int NW, bool kWide, int RFT = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(search_min_waves<kGlobalA, kPriced, NW, kWide>(), 8))) void k_search(SearchPools pl, SearchParams prm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    search_body<kGlobalA, kPriced, NW, kWide, false>(smem, pl, prm);
+    search_body<kGlobalA, kPriced, NW, kWide, false, false, RFT>(smem, pl, prm);
 }
 // working assignment in LDS, current assignment from global memory / L2 (kCurG; ~4,900 .. 9,800 partitions: always wide)
 template <bool kPriced, int NW>
@@ -1851,10 +1869,10 @@ size_t eval_lds_bytes(int maxP, int maxB, bool cur_in_lds, int ne) {
 // largest dynamic-LDS size each kernel has been enabled for, per device (function attributes are per device)
 static int g_attr_eval_dev[kAttrDevices] = {0};
 
-template <bool kGlobalA, bool kPriced, int NW, bool kWide>
+template <bool kGlobalA, bool kPriced, int NW, bool kWide, int RFT = 0>
 static void launch_search_t(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, size_t lds, int &attr, hipStream_t st) {
-    if ((int)lds > attr) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_search<kGlobalA, kPriced, NW, kWide>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_search<kGlobalA, kPriced, NW, kWide>), dim3(n_blocks), dim3(64 * waves), lds, st, pools, prm);
+    if ((int)lds > attr) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_search<kGlobalA, kPriced, NW, kWide, RFT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((k_search<kGlobalA, kPriced, NW, kWide, RFT>), dim3(n_blocks), dim3(64 * waves), lds, st, pools, prm);
 }
 template <bool kGlobalA, bool kPriced, int NW>
 static void launch_search_w(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, size_t lds, int &attr, bool wide, hipStream_t st) {
@@ -1868,11 +1886,13 @@ static void launch_team_t(const SearchPools &pools, const SearchParams &prm, int
     hipLaunchKernelGGL((k_team<kPriced, NW>), dim3(n_blocks), dim3(64 * team), lds, st, pools, prm);
 }
 
-void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team) {
+bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, int team) { return !global_a && !cur_global && !priced && nw == 4 && team == 0; }
+
+void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team, int rft) {
     const bool curg = prm.cur_global != 0 && !global_a;
     const size_t lds = search_lds_bytes(prm.maxP, prm.maxBx, waves, global_a, priced, nw, prm.bw != 0, prm.maxR, team, curg);
     // largest dynamic-LDS size each of the instantiations has been enabled for, per device
-    static int attr[kAttrDevices][24] = {{0}};
+    static int attr[kAttrDevices][26] = {{0}};
     const bool wide = prm.wide != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (curg) {   // working assignment in LDS, current assignment from L2
@@ -1889,6 +1909,13 @@ void launch_search(const SearchPools &pools, const SearchParams &prm, int n_bloc
         if (nw == 8) { if (priced) launch_team_t<true, 8>(pools, prm, n_blocks, team, lds, ta, st); else launch_team_t<false, 8>(pools, prm, n_blocks, team, lds, ta, st); }
         else { if (priced) launch_team_t<true, 4>(pools, prm, n_blocks, team, lds, ta, st); else launch_team_t<false, 4>(pools, prm, n_blocks, team, lds, ta, st); }
         if ((int)lds > ta) ta = (int)lds;
+        return;
+    }
+    if (rft == 3 && search_rf3_eligible(global_a, curg, priced, nw, team)) {   // every topic RF 3, at most 3 current replicas (kao_session.cpp)
+        int &ra = attr[attr_slot()][24 + (wide ? 1 : 0)];
+        if (wide) launch_search_t<false, false, 4, true, 3>(pools, prm, n_blocks, waves, lds, ra, st);
+        else launch_search_t<false, false, 4, false, 3>(pools, prm, n_blocks, waves, lds, ra, st);
+        if ((int)lds > ra) ra = (int)lds;
         return;
     }
     int &a = attr[attr_slot()][(wide || global_a ? 8 : 0) + (global_a ? 4 : 0) + (priced ? 2 : 0) + (nw == 8 ? 1 : 0)];

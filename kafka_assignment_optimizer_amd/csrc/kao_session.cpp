@@ -626,6 +626,7 @@ int kao_session_create(const kao_topic *topics, int32_t n_topics, const kao_opts
     }
     s->total_restarts = restart_base;
     // ---- launch groups: topics sorted by single-wave LDS need, a new group whenever the need doubles (<= 8 groups) ----
+    const bool rft_on = env_int("KAO_SEARCH_RFT", 1) != 0;   // (read per session: a test hook; 0 = the generic K-search kernel throughout)
     std::vector<int> order((size_t)n_topics);
     for (int t = 0; t < n_topics; ++t) order[(size_t)t] = t;
     auto need1 = [&](int t) {  // topics kept in global memory sort last (their LDS need is tiny but they form their own groups)
@@ -664,8 +665,10 @@ int kao_session_create(const kao_topic *topics, int32_t n_topics, const kao_opts
         for (int t : mem) {
             const TopicDev &d = s->pts[(size_t)t].d;
             g.rf_uniform = g.rf_uniform < 0 ? d.RF : (g.rf_uniform == d.RF ? d.RF : 0);
+            g.rf3 = g.rf3 && d.RF == 3 && d.rf_cur <= 3;   // (RF 3 with four current replicas: word 3 of CUR is a real replica)
             g.maxP = std::max(g.maxP, d.P); g.maxBx = std::max(g.maxBx, d.Bx); g.maxB = std::max(g.maxB, d.B); g.maxR = std::max(g.maxR, d.R); g.wide = g.wide || (int64_t)d.P * d.RF >= 512;
         }
+        g.rf3 = g.rf3 && rft_on;
         g.global_a = s->topic_global[(size_t)mem[0]] != 0;
         g.cur_global = s->topic_curg[(size_t)mem[0]] != 0;
         g.nw = s->pts[(size_t)mem[0]].d.nw;
@@ -838,7 +841,9 @@ int kao_session_step(kao_session *s) {
             if (env_int("KAO_INIT_WAVES", 1) != 0 && launch_init(sp, gp, g.smap_n, g.team > 0 ? 1 : g.waves, s->priced, g.nw, s->stream)) gp.init = 2;
             HIP_TRY(hipGetLastError());
         }
-        launch_search(sp, gp, g.smap_n, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team);
+        const int rft = g.rf3 ? 3 : 0;
+        launch_search(sp, gp, g.smap_n, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team, rft);
+        if (rft && search_rf3_eligible(g.global_a, g.cur_global, s->priced, g.nw, g.team)) s->search_rf3_launches++;
         HIP_TRY(hipGetLastError());
     }
     if (prof) HIP_TRY(hipEventRecord(e[1], s->stream));
@@ -945,6 +950,7 @@ int kao_session_stats(kao_session *s, kao_stats *out) {
         out->lds_bytes_search = std::max(out->lds_bytes_search, (int32_t)search_lds_bytes(g.maxP, g.maxBx, g.waves, g.global_a, s->priced, g.nw, s->any_bw, g.maxR, g.team, g.cur_global));
     out->launch_groups = (int32_t)s->groups.size();
     out->blocks_search = s->blocks_search;
+    out->search_rf3_launches = (int32_t)std::min<uint64_t>(s->search_rf3_launches, (uint64_t)INT32_MAX);
     HIP_TRY(hipMemcpy(&out->drift, s->d_drift, 4, hipMemcpyDeviceToHost));
     return KAO_OK;
 }
