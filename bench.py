@@ -5,8 +5,15 @@ of 50 brokers), at 1/2/4/8 GPUs.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
   python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's results as DIR/<name>.npy
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + every figure that takes runs of its own (below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line: the headline figures
+and the K-search roofline of the timed launches (HIP events of the steps against the committed counter constants).
+--full adds what takes runs or checks of its own, after the timed steps: the quality of every timed batch, steady state,
+time-to-optimal and the cold CLI, the exactness / KAO-LP / north-star probes, the big-topic rooflines, the capped
+cluster, the K-eval stream and the CPU baseline (`value_non_null` needs the latter).
 
 One step = one pass of the hot path over ONE FRESH BATCH of synthetic input: the config-4 cluster after a 20 % drift
 (synthetic.drift, a different drift seed for every step), i.e. 200 reassignment problems nobody has solved yet, all
@@ -14,7 +21,7 @@ resident in HBM before the timed region.  A step runs, for this rank's topics, o
 iters_per_launch local-search iterations for every restart of every topic) + one K-eval launch (full evaluation of every
 restart's best snapshot, wavefront/workgroup min-reduce into one packed key per topic) + the host read-back of those keys
 [+ for N > 1 the min-allreduce of the global best over RCCL].  (Round 1 timed 20 launches on ONE batch, i.e. mostly on
-topics that were already solved; that figure is still reported, as `steady_state`.)
+topics that were already solved; --full still reports that figure, as `steady_state`.)
 Topics shard across ranks (independent sub-problems, README.md:146-184) and every rank fills its own GPU with
 restarts, so per-GPU work is fixed as N grows: "scaling": "weak".
 
@@ -331,9 +338,10 @@ def main():
     ap.add_argument("--iters", type=int, default=512, help="local-search iterations per K-search launch")
     ap.add_argument("--restarts", type=int, default=0,
                     help="restarts per topic (0 = four full rounds of resident wavefronts: 256 CUs x 32 x 4 / topics)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="timed steps only (what tools/profile.sh wraps in rocprofv3)")
-    ap.add_argument("--eval-bench", type=int, default=1, help="also time K-eval alone on a resident batch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also every figure and check that takes runs of its own (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--eval-bench", type=int, default=1, help="--full: also time K-eval alone on a resident batch")
     ap.add_argument("--in-library", action="store_true",
                     help="ONE process, --gpus devices, through kao_solve_multi (what kao-cli --gpus N ships: topics dealt LPT, RCCL only "
                          "when topics < devices) instead of one process per GPU; not the driver's launch mode")
@@ -476,19 +484,21 @@ def main():
         agg[0] = tmax[0]
     dt_max, tot_delta, tot_full = (float(x) for x in agg.cpu())
 
-    # ---- what the timed steps achieved: every batch's topics after its ONE step ------------------
-    feasible = n_res = 0
-    obj_after_step = []
-    for s in timed:
-        res = s.best()
-        n_res += len(res)
-        feasible += sum(1 for r in res if r.violations[0] == 0 and r.objective >= 0)
-        obj_after_step.append(sum(int(r.objective) for r in res))
     if args.dump_outputs and rank == 0:   # before the steady-state launches below search the last batch further
-        dump_outputs(args.dump_outputs, last_keys, res, world)
+        dump_outputs(args.dump_outputs, last_keys, timed[-1].best(), world)
 
     out_extra = {}
-    if not args.no_extras:
+    if args.full:
+        # ---- what the timed steps achieved: every batch's topics after its ONE step ------------------
+        feasible = n_res = 0
+        obj_after_step = []
+        for s in timed:
+            res = s.best()
+            n_res += len(res)
+            feasible += sum(1 for r in res if r.violations[0] == 0 and r.objective >= 0)
+            obj_after_step.append(sum(int(r.objective) for r in res))
+        out_extra["quality_after_one_step"] = {"batches": len(timed), "topics_rank0": n_res, "feasible": feasible, "drift": drift_ctr,
+                                               "objective_sum_per_batch_rank0": obj_after_step}
         # ---- steady state (round 1's figure): more launches on a batch that is already solved ----
         ss = timed[-1]
         sa = ss.stats()
@@ -507,7 +517,7 @@ def main():
         s.close()
 
     tto = {}
-    if not args.no_extras:
+    if args.full:
         # ---- time-to-optimal: fresh whole jobs (create + H2D + launches until every topic is PROVEN optimal + D2H),
         #      wall clock from kao_solve entry.  (a) the drifted batch of the first timed step: the closed-form bound has a
         #      gap on every topic, optimality is proven by K-bound beside K-search; (b) the balanced config as generated.
@@ -558,8 +568,6 @@ def main():
                    "parallelism": f"topic-sharded x{world}" if world > 1 else "single GPU"},
         "delta_candidates_per_s": tot_delta / dt_max,
         "full_candidates_per_s": tot_full / dt_max,
-        "quality_after_one_step": {"batches": len(timed), "topics_rank0": n_res, "feasible": feasible, "drift": drift_ctr,
-                                   "objective_sum_per_batch_rank0": obj_after_step},
     }
     out.update(out_extra)
     if tto:
@@ -581,7 +589,7 @@ def main():
                                    "rank 0's topics"}
 
     # ---- exactness at scale: single drifted topics of >= 1000 partitions, rank 0 only ----
-    if not args.no_extras and rank == 0:
+    if args.full and rank == 0:
         probes = []
         # (brokers, racks, partitions, budget, HiGHS MILP optimum or None, HiGHS LP relaxation value or None)
         for (B_, R_, P_, budget, known, lp) in ((100, 5, 1000, 3.0, 7430, 7430.0), (300, 6, 2000, 3.0, 14826, 14826.0),
@@ -634,7 +642,7 @@ def main():
                                  "reference": "HiGHS on the full model needed 2,876 s (450 x 3500, LP 26330) and 10,008 s (500 x 5000, LP 37558): tests/golden/drift_scale.json"}
 
     # ---- the north-star solve under the north-star's own budget, and the roofline of what decides it: a KAO-LP iteration ----
-    if not args.no_extras and rank == 0:
+    if args.full and rank == 0:
         tp = synthetic.north_star_topic("drift100k")
         kao.solve([tp], seed=1, max_launches=1)               # arenas / code objects
         t0 = time.perf_counter()
@@ -670,7 +678,7 @@ def main():
 
     # ---- the north-star regime (BASELINE config 5): one LARGE topic, assignment words in HBM/L2 -- the kernel variants that
     #      run there (k_search<true, ...>, the cooperative k_eval) against the HBM peak; traffic from profiles/ (rocprofv3 --pmc) ----
-    if not args.no_extras and rank == 0:
+    if args.full and rank == 0:
         big = []
         for which in ("drift30k", "drift100k", "cfg5one"):
             st = synthetic.north_star_steps(kao, which, launches=4)     # automatic restart count: 4 per compute unit (round 4)
@@ -723,7 +731,7 @@ def main():
 
     # ---- cluster-wide per-broker caps (BASELINE config 5 wording; kao_solve_capped) on the medium golden: wall time, plan
     #      against the exact joint optimum (HiGHS, tests/golden/capped_medium.json: numbers only, nothing of oracle/ runs here) ----
-    if not args.no_extras and rank == 0:
+    if args.full and rank == 0:
         try:
             with open(os.path.join(ROOT, "tests", "golden", "capped_medium.json")) as f:
                 cases = json.load(f)["cases"]
@@ -789,7 +797,7 @@ def main():
                                     "algorithmic_bytes_per_launch": eb // max(1, launches)}
 
     # ---- K-eval alone on a large resident batch: the genuinely HBM-streaming kernel ----------------
-    if args.eval_bench and not args.no_extras:
+    if args.full and args.eval_bench:
         t = topics[0]
         n = 1 << 18
         per = t.n_partitions * t.rf
@@ -814,7 +822,7 @@ def main():
                                        "frac": bytes_e / (ms_e * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                        "full_candidates_per_s": n / (ms_e * 1e-3)}
 
-    if world == 1 and not args.no_cpu_baseline and not args.no_extras:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         rpt = restarts_total // max(1, len(topics))
         cb = cpu_baseline(batches[args.warmup], rpt, args.iters)
         out["cpu_baseline"] = cb

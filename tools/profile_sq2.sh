@@ -4,7 +4,7 @@ set -u
 TAG=${1:-r01}
 REPO=$(pwd); OUT=$REPO/gpurun_out/prof_$TAG; mkdir -p "$OUT"
 export TMPDIR=/tmp; cd /tmp
-BENCH="python $REPO/bench.py --steps 4 --warmup 1 --no-cpu-baseline --eval-bench 0"
+BENCH="python $REPO/bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --eval-bench 0"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS -d "$OUT/pmc_sq2" -o bench -- $BENCH > /dev/null 2> "$OUT/sq2.err"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE -d "$OUT/pmc_sq3" -o bench -- $BENCH > /dev/null 2> "$OUT/sq3.err"
 cd "$REPO"
