@@ -435,14 +435,24 @@ bool dual_supported(const kao_topic *t, bool session_bw) {
     // topic is 300,000 slots).  What the integers need: a subgradient entry |s| <= n and a direction |d| <= 64 n in 32 bits
     // (n <= 2^20); |d|^2 summed over 2 B + R multipliers in 63 bits (4096 n^2 (2 B + R) < 2^62); the level gap in dual fixed
     // point below 2^42 (bound_step_length: n * weight * 65536, checked with the weights below).
-    // Round 6 (1000 x 500,000 = 1.5 M slots had no certificate and no LP): the 63-bit test above priced |d|^2 as (64 n)^2 per multiplier.  A
-    // family's subgradient has |s|_inf <= max(n, 65535) and |s|_1 <= n + 65535 * (entries) (counts add up to n, band ends are 16-bit), the
-    // deflected direction is 64 x a convex combination of such vectors, and sum d^2 <= |d|_inf |d|_1: three families stay below 2^62 up to
-    // 2^21 slots with 8,000 brokers.  |s| and 64 |s| in 32 bits need n < 2^25; the level gap n * weight * 65536 < 2^42 is the last line.
+    // Round 6 (1000 x 500,000 = 1.5 M slots had no certificate and no LP): the 63-bit test above priced |d|^2 as (64 n)^2 per multiplier.
+    // An entry of a family's subgradient is (band end) - (count): the counts are non-negative and add up to C (n replicas, P leaders, n
+    // rack slots), the band ends are non-negative, so |s|_inf <= max(C, end) and |s|_1 <= C + entries * end, with `end` the family's larger
+    // band end (derive_bounds, overrides included).  The deflected direction is 64 x a convex combination of such vectors and
+    // sum d^2 <= |d|_inf |d|_1, summed over the three families, must stay below 2^62: with the floor / ceil bands that is at most about
+    // 4096 * 6 n^2 (RF 1), inside up to n = 2^21 whatever the number of brokers.  |s| and 64 |s| in 32 bits need n < 2^25; the level gap
+    // n * weight * 65536 < 2^42 is the last line.
     if (n > ((int64_t)1 << 21)) return false;
     {
-        const double sinf = (double)std::max<int64_t>(n, 65535), s1 = (double)n + 65535.0 * (double)std::max(t->n_brokers, t->n_racks);
-        if (3.0 * 64.0 * sinf * 64.0 * s1 >= 4.0e18) return false;
+        int32_t bd[8];
+        derive_bounds(t, bd);
+        auto family = [](double count, double entries, int32_t lo, int32_t hi) {   // |s|_inf * |s|_1 of one family
+            const double end = (double)std::max(lo, hi);
+            return std::max(count, end) * (count + entries * end);
+        };
+        const double d2 = 64.0 * 64.0 * (family((double)n, t->n_brokers, bd[0], bd[1]) + family(t->n_partitions, t->n_brokers, bd[2], bd[3]) +
+                                         family((double)n, t->n_racks, bd[4], bd[5]));
+        if (d2 >= 4.0e18) return false;
     }
     int wmax = 0, bwmax = 0;
     for (int i = 0; i < 2; ++i)

@@ -227,6 +227,11 @@ struct SolveRun {
         if (!lp_round_on) return false;
         return (huge(i) && lp_fits(i)) || (solo(i) && deadline - t0 >= lp_solo_s && only_open(i));
     }
+    // a huge topic whose limit leaves no room for its LP beside the incumbent: the first LP starts once KAO-CX has run the incumbent to a
+    // fixpoint, so KAO-CX must not wait for that LP (both would wait while the search is paused, until the deadline)
+    bool lp_waits_for_cx(int i) const {
+        return huge(i) && !lp_alone(i) && !(lp_round_on && lp_fits(i, 0.2)) && cx_on && cycle_supported(&topics[i]);
+    }
     // a huge topic between its first feasible incumbent and the end of its LP -- from the start when the limit leaves room for the LP alone
     bool pause_wanted(int i) const { return lp_possible(i) && ((huge(i) && feasible(i)) || lp_alone(i)); }
     static constexpr int kFirstShortIters = 32;
@@ -498,9 +503,7 @@ struct SolveRun {
                 if (huge(i)) {   // ... once KAO-CX has run the incumbent to a fixpoint (or cannot run) -- or, when the time
                     // limit leaves room for it (a limit is an input, not the clock), straight after the first feasible incumbent: its
                     // primal side makes the fixpoint unnecessary
-                    const bool cx_can = cx_on && cycle_supported(&topics[i]);
-                    const bool lp_now = lp_round_on && lp_fits(i, 0.2);
-                    if (!lp_alone(i) && (!feasible(i) || (!lp_now && cx_can && (dkeys[(size_t)i] >> 20) != (cx_seen[(size_t)i] >> 20)))) continue;
+                    if (!lp_alone(i) && (!feasible(i) || (lp_waits_for_cx(i) && (dkeys[(size_t)i] >> 20) != (cx_seen[(size_t)i] >> 20)))) continue;
                 }
                 const int64_t slots = (int64_t)topics[i].n_partitions * topics[i].rf;
                 if (slots < lp_min_slots && !lp_try[(size_t)i] && (!feasible(i) || bound_merges[(size_t)i] < lp_after_small)) continue;
@@ -694,7 +697,8 @@ struct SolveRun {
             if (s->topic_infeasible[(size_t)i] || !gfeasible(i) || (feasible(i) && objective(i) >= s->ub[(size_t)i])) continue;
             if (!cycle_supported(&topics[i])) continue;
             if (lp_state[(size_t)i] == 1 && lp_all[(size_t)i]) continue;   // a huge topic's LP has the GPU to itself (beside it a round takes 20 ms instead of 8)
-            if (lp_round_on && lp_possible(i) && !lp_try[(size_t)i] && (int64_t)topics[i].n_partitions * topics[i].rf >= lp_mid_slots) continue;   // (round 6) its first LP is waiting or running: the rounded iterate comes first
+            if (lp_round_on && lp_possible(i) && !lp_try[(size_t)i] && (int64_t)topics[i].n_partitions * topics[i].rf >= lp_mid_slots &&
+                !lp_waits_for_cx(i)) continue;   // (round 6) its first LP is waiting or running: the rounded iterate comes first
             const bool elite_fresh = (dkeys[(size_t)i] >> 20) != (cx_seen[(size_t)i] >> 20);   // not the incumbent of the last fixpoint
             const bool more = det && cx_starts > 0;
             if (!elite_fresh && !more) continue;

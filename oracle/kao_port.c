@@ -951,8 +951,9 @@ static inline int32_t db_move(int32_t m, int64_t step, int sh, int k, int32_t d,
 }
 
 /* Runs up to `iters` dual iterations from the state (a[B], l[B], g[R] multipliers; da[B], dl[B], dg[R] previous
- * direction; lv[4] level-control state and step counter, zeros to start; *best_L), all in/out (zeros and INT64_MAX to start).  Needs P*RF <= 2^20, 4096 (P*RF)^2 (2B+R) < 2^62 and
- * P*RF*max(w) <= 2^25 (round 4; rounds 1-3: P*RF <= 2^17 -- the arithmetic below never needed that).  flags: 1 = closed (best_L < (target+1)*DB_SCALE), 2 = zero subgradient (dual optimum reached),
+ * direction; lv[4] level-control state and step counter, zeros to start; *best_L), all in/out (zeros and INT64_MAX to start).  Needs P*RF <= 2^21, 4096 sum over the three
+ * families of |s|_inf |s|_1 < 2^62 (|s|_1 <= count + entries * band end: kao_model.cpp dual_supported) and P*RF*max(w) <= 2^25
+ * (round 6; round 4: P*RF <= 2^20; rounds 1-3: P*RF <= 2^17 -- the arithmetic below never needed that).  flags: 1 = closed (best_L < (target+1)*DB_SCALE), 2 = zero subgradient (dual optimum reached),
  * 4 = a partition subproblem is infeasible (no bound).  Returns the number of iterations performed. */
 int kao_port_dual_bound_rec(const port_topic *t, int64_t target, int32_t iters, int32_t *a, int32_t *l, int32_t *g,
                             int32_t *da, int32_t *dl, int32_t *dg, int64_t *lv, int64_t *best_L, int32_t *flags,
