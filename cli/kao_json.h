@@ -18,6 +18,7 @@ struct JValue {
     double num = 0;
     bool b = false;
     std::string str;
+    std::string raw;   // a number's source text
     std::vector<JValue> arr;
     std::vector<std::pair<std::string, JValue>> obj;
     const JValue *get(const std::string &k) const {
@@ -74,7 +75,7 @@ struct JParser {
         if (c == '-' || std::isdigit((unsigned char)c)) {
             size_t j = i; if (s[j] == '-') ++j;
             while (j < s.size() && (std::isdigit((unsigned char)s[j]) || s[j] == '.' || s[j] == 'e' || s[j] == 'E' || s[j] == '+' || s[j] == '-')) ++j;
-            v.kind = JValue::Num; v.num = std::strtod(s.substr(i, j - i).c_str(), nullptr); i = j; return v;
+            v.kind = JValue::Num; v.raw = s.substr(i, j - i); v.num = std::strtod(v.raw.c_str(), nullptr); i = j; return v;
         }
         if (s.compare(i, 4, "true") == 0) { v.kind = JValue::Bool; v.b = true; i += 4; return v; }
         if (s.compare(i, 5, "false") == 0) { v.kind = JValue::Bool; i += 5; return v; }

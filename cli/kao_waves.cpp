@@ -4,12 +4,21 @@
 //   kao-cli --current current.json ... --out plan.json
 //   kao-waves --current current.json --plan plan.json --max-per-broker K --out-prefix wave [--seed S] [--device D] [--report]
 //
+// With --sizes FILE (the output of `kafka-log-dirs --describe`, or {"partitions":[{"topic":..,"partition":..,"size":..}]}) and
+// --max-bytes-per-broker N (bytes; K/M/G/T suffixes are powers of 1024), each wave also moves at most N bytes per broker
+// (kao_plan_waves_sized): an added broker receives size[p], the source sends size[p] once per added broker.  --max-per-broker
+// is then optional (0 = no count cap); --default-size N sizes the moving partitions --sizes does not list.
+//
 // which writes wave1.json .. waveN.json, each a reassignment document `kafka-reassign-partitions --execute` takes on its own; run
 // them in order, each after the previous one has finished.  A partition of current.json that plan.json leaves out is unchanged;
 // a partition of plan.json that current.json does not list is an error.  All computation happens in libkao.so on the GPU.
 // Exit status: 0 = waves written, 1 = error, 2 = usage.
 #include <algorithm>
+#include <cerrno>
+#include <climits>
+#include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <set>
 #include <string>
@@ -26,6 +35,8 @@ namespace {
     std::fprintf(stderr,
         "usage: kao-waves --current <reassignment.json> --plan <reassignment.json> --max-per-broker K --out-prefix PREFIX\n"
         "                 [--seed S] [--device D] [--report]\n"
+        "       sized: --sizes <kafka-log-dirs output | sizes.json> --max-bytes-per-broker N[K|M|G|T] [--default-size N]\n"
+        "              (--max-per-broker optional; 0 = no count cap)\n"
         "writes PREFIX1.json .. PREFIXn.json; exit status: 0 = ok, 1 = error, 2 = usage\n");
     std::exit(2);
 }
@@ -52,6 +63,105 @@ std::vector<std::pair<Key, std::vector<int>>> entries(const std::string &path, c
     return out;
 }
 
+constexpr uint64_t kMaxSize = uint64_t(1) << 53;   // JSON numbers are doubles here: exact up to 2^53, larger sizes are rejected
+
+// N, or N with a K / M / G / T suffix (powers of 1024), below 2^64; false when it is not one
+bool parse_bytes(const std::string &text, uint64_t &out) {
+    std::string t = text;
+    uint64_t mult = 1;
+    if (!t.empty()) {
+        const char c = (char)std::toupper((unsigned char)t.back());
+        const char *units = "KMGT", *u = std::strchr(units, c);
+        if (c && u) {
+            for (int i = 0; i <= u - units; ++i) mult *= 1024;
+            t.pop_back();
+        }
+    }
+    if (t.empty() || t.size() > 20 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+    errno = 0;
+    const unsigned long long v = std::strtoull(t.c_str(), nullptr, 10);
+    if (errno == ERANGE || (mult > 1 && v > UINT64_MAX / mult)) return false;
+    out = (uint64_t)v * mult;
+    return true;
+}
+
+uint64_t size_value(const JValue *v, const std::string &what) {
+    uint64_t x = 0;
+    if (!v || v->kind != JValue::Num || v->raw.empty() || v->raw.size() > 16 || v->raw.find_first_not_of("0123456789") != std::string::npos ||
+        (x = std::strtoull(v->raw.c_str(), nullptr, 10)) > kMaxSize)
+        throw std::runtime_error("sizes: " + what + ": size must be an integer 0..2^53");
+    return x;
+}
+
+// partition sizes, from `kafka-log-dirs --describe` output (the largest non-future replica; names split at the last '-') or from a
+// {"partitions":[{"topic","partition","size"}]} document
+std::map<Key, uint64_t> load_sizes(const std::string &path) {
+    const std::string txt = slurp(path);
+    JValue doc;
+    try {
+        doc = JParser(txt).parse();
+    } catch (const std::runtime_error &) {   // kafka-log-dirs prints status lines before its JSON line
+        std::istringstream in(txt);
+        std::string line;
+        bool found = false;
+        while (!found && std::getline(in, line)) {
+            const size_t b = line.find_first_not_of(" \t\r");
+            if (b != std::string::npos && line[b] == '{') { doc = JParser(line).parse(); found = true; }
+        }
+        if (!found) throw std::runtime_error("sizes: no JSON document found");
+    }
+    std::map<Key, uint64_t> out;
+    if (const JValue *brokers = doc.get("brokers")) {
+        for (auto &br : brokers->arr) {
+            const JValue *dirs = br.get("logDirs");
+            if (!dirs) continue;
+            for (auto &d : dirs->arr) {
+                const JValue *parts = d.get("partitions");
+                if (!parts) continue;
+                for (auto &e : parts->arr) {
+                    const JValue *fut = e.get("isFuture"), *name = e.get("partition");
+                    if (fut && fut->kind == JValue::Bool && fut->b) continue;
+                    if (!name || name->kind != JValue::Str) throw std::runtime_error("sizes: log-dir entry without a partition name");
+                    const size_t dash = name->str.rfind('-');
+                    const std::string idx = dash == std::string::npos ? "" : name->str.substr(dash + 1);
+                    if (dash == std::string::npos || dash == 0 || idx.empty() || idx.size() > 9 || idx.find_first_not_of("0123456789") != std::string::npos)
+                        throw std::runtime_error("sizes: partition name '" + name->str + "' is not <topic>-<partition>");
+                    const Key k{name->str.substr(0, dash), std::atoi(idx.c_str())};
+                    const uint64_t v = size_value(e.get("size"), name->str);
+                    auto it = out.find(k);
+                    if (it == out.end()) out[k] = v;
+                    else it->second = std::max(it->second, v);
+                }
+            }
+        }
+    } else if (const JValue *parts = doc.get("partitions")) {
+        for (auto &e : parts->arr) {
+            const JValue *t = e.get("topic"), *p = e.get("partition");
+            if (!t || !p) throw std::runtime_error("sizes: partition entry needs topic/partition/size");
+            const Key k{t->str, (int)p->num};
+            const std::string what = k.first + "-" + std::to_string(k.second);
+            if (out.count(k)) throw std::runtime_error("sizes: partition " + what + " listed twice");
+            out[k] = size_value(e.get("size"), what);
+        }
+    } else {
+        throw std::runtime_error("sizes: expected a \"brokers\" (kafka-log-dirs) or \"partitions\" document");
+    }
+    return out;
+}
+
+// participants of one partition and their copies of it: 1 at each added broker, n_added at the source; empty when it moves no data
+std::vector<std::pair<int, uint64_t>> traffic(const uint16_t *c, const uint16_t *t, size_t W) {
+    std::vector<std::pair<int, uint64_t>> out;
+    for (size_t i = 0; i < W; ++i) {
+        if (t[i] == KAO_NONE) continue;
+        bool held = false;
+        for (size_t j = 0; j < W; ++j) held |= c[j] == t[i];
+        if (!held) out.emplace_back(t[i], 1);
+    }
+    if (!out.empty() && c[0] != KAO_NONE) out.emplace_back(c[0], (uint64_t)out.size());
+    return out;
+}
+
 std::string quoted(const std::string &s) {
     std::string o = "\"";
     for (char c : s) {
@@ -64,16 +174,25 @@ std::string quoted(const std::string &s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string cur_path, plan_path, prefix;
+    std::string cur_path, plan_path, prefix, sizes_path;
     int k = 0, device = 0;
     unsigned long long seed = 1;
-    bool report = false;
+    bool report = false, have_k = false, sized = false, have_default = false;
+    uint64_t cap_bytes = 0, default_size = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
         if (a == "--current") cur_path = need("--current");
         else if (a == "--plan") plan_path = need("--plan");
-        else if (a == "--max-per-broker") k = std::atoi(need("--max-per-broker").c_str());
+        else if (a == "--max-per-broker") { k = std::atoi(need("--max-per-broker").c_str()); have_k = true; }
+        else if (a == "--sizes") { sizes_path = need("--sizes"); sized = true; }
+        else if (a == "--max-bytes-per-broker") {
+            if (!parse_bytes(need("--max-bytes-per-broker"), cap_bytes)) usage("--max-bytes-per-broker needs a byte count (N, or N with K/M/G/T)");
+            sized = true;
+        } else if (a == "--default-size") {
+            if (!parse_bytes(need("--default-size"), default_size) || default_size > kMaxSize) usage("--default-size needs a byte count up to 2^53");
+            sized = have_default = true;
+        }
         else if (a == "--out-prefix") prefix = need("--out-prefix");
         else if (a == "--seed") seed = std::strtoull(need("--seed").c_str(), nullptr, 0);
         else if (a == "--device") device = std::atoi(need("--device").c_str());
@@ -82,7 +201,10 @@ int main(int argc, char **argv) {
         else usage(("unknown flag " + a).c_str());
     }
     if (cur_path.empty() || plan_path.empty() || prefix.empty()) usage("--current, --plan and --out-prefix are required");
-    if (k < 1) usage("--max-per-broker needs a value >= 1");
+    if (!sized && k < 1) usage("--max-per-broker needs a value >= 1");
+    if (sized && (k < 0 || (k == 0 && cap_bytes == 0)))
+        usage(have_k ? "--max-per-broker must be >= 0, and a cap must be set (--max-per-broker >= 1 or --max-bytes-per-broker >= 1)"
+                     : "give --max-per-broker K >= 1 or --max-bytes-per-broker N >= 1");
     try {
         const auto cur = entries(cur_path, "current");
         const auto plan = entries(plan_path, "plan");
@@ -113,12 +235,37 @@ int main(int argc, char **argv) {
             for (size_t j = 0; j < cur[i].second.size(); ++j) c[i * W + j] = (uint16_t)dense[cur[i].second[j]];
             for (size_t j = 0; j < tgt[i]->size(); ++j) t[i * W + j] = (uint16_t)dense[(*tgt[i])[j]];
         }
+        std::vector<uint64_t> size;
+        if (sized) {   // bytes per partition; every partition that moves data needs one
+            const std::map<Key, uint64_t> known = sizes_path.empty() ? std::map<Key, uint64_t>() : load_sizes(sizes_path);
+            size.assign(std::max<size_t>(P, 1), 0);
+            std::vector<std::string> missing;
+            for (size_t i = 0; i < P; ++i) {
+                auto it = known.find(cur[i].first);
+                if (it != known.end()) size[i] = it->second;
+                else if (!traffic(&c[i * W], &t[i * W], W).empty()) {
+                    if (have_default) size[i] = default_size;
+                    else missing.push_back(cur[i].first.first + "-" + std::to_string(cur[i].first.second));
+                }
+            }
+            if (!missing.empty()) {
+                std::string msg = "no size for moving partitions ";
+                for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + missing[i];
+                if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
+                throw std::runtime_error(msg + " (give them in --sizes or set --default-size)");
+            }
+        }
         int rc = kao_init(device);
         if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
         std::vector<int32_t> wave(std::max<size_t>(P, 1));
         int32_t n_waves = 0, lb = 0;
-        rc = kao_plan_waves(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), k, seed, wave.data(), &n_waves, &lb);
-        if (rc) throw std::runtime_error(std::string("kao_plan_waves: ") + kao_strerror(rc) + " " + kao_last_error());
+        if (sized) {
+            rc = kao_plan_waves_sized(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), size.data(), cap_bytes, k, seed, wave.data(), &n_waves, &lb);
+            if (rc) throw std::runtime_error(std::string("kao_plan_waves_sized: ") + kao_strerror(rc) + " " + kao_last_error());
+        } else {
+            rc = kao_plan_waves(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), k, seed, wave.data(), &n_waves, &lb);
+            if (rc) throw std::runtime_error(std::string("kao_plan_waves: ") + kao_strerror(rc) + " " + kao_last_error());
+        }
         std::vector<int> sizes((size_t)n_waves, 0);
         for (int w = 0; w < n_waves; ++w) {
             const std::string path = prefix + std::to_string(w + 1) + ".json";
@@ -137,6 +284,22 @@ int main(int argc, char **argv) {
         if (report) {
             std::fprintf(stderr, "waves=%d lower_bound=%d optimal=%s partitions_per_wave=", n_waves, lb, n_waves == lb ? "yes" : "no");
             for (int w = 0; w < n_waves; ++w) std::fprintf(stderr, "%s%d", w ? "," : "", sizes[(size_t)w]);
+            if (sized) {   // bytes: the byte lower bound max_b ceil(sum_p min(t, C) / C) and each wave's busiest broker
+                std::map<std::pair<int, int>, uint64_t> load;
+                std::map<int, uint64_t> clamp;
+                for (size_t i = 0; i < P; ++i)
+                    for (auto &bn : traffic(&c[i * W], &t[i * W], W)) {
+                        const uint64_t tr = bn.second * size[i];   // below 2^62: kao_plan_waves_sized checked the totals
+                        load[{wave[i], bn.first}] += tr;
+                        if (cap_bytes) clamp[bn.first] += std::min(tr, cap_bytes);
+                    }
+                uint64_t blb = 0;
+                for (auto &kv : clamp) blb = std::max(blb, kv.second / cap_bytes + (kv.second % cap_bytes != 0));
+                std::vector<uint64_t> peak((size_t)n_waves, 0);
+                for (auto &kv : load) peak[(size_t)kv.first.first] = std::max(peak[(size_t)kv.first.first], kv.second);
+                std::fprintf(stderr, " bytes_lower_bound=%llu max_broker_bytes_per_wave=", (unsigned long long)blb);
+                for (int w = 0; w < n_waves; ++w) std::fprintf(stderr, "%s%llu", w ? "," : "", (unsigned long long)peak[(size_t)w]);
+            }
             std::fprintf(stderr, "\n");
         }
         kao_shutdown();

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define KAO_VERSION 103 /* 0.1.3: kao_lp_round (KAO-LP's primal side); 0.1.2: kao_lp_bound, kao_session_set_dual_state (KAO-LP, round 5) */
+#define KAO_VERSION 103 /* 0.1.3: kao_lp_round (KAO-LP's primal side), later kao_plan_waves and kao_plan_waves_sized (no version bump); 0.1.2: kao_lp_bound, kao_session_set_dual_state (KAO-LP, round 5) */
 #define KAO_NONE 0xFFFFu /* "no broker": replica on a broker outside the target set / empty slot */
 #define KAO_MAX_RF 8     /* replica slots per partition supported by the gfx950 kernels (RF <= 4: one 128-bit word group per
                             partition; 5..8: two) */
@@ -415,6 +415,23 @@ int kao_cycle_pair_edges(const kao_topic *t, const uint16_t *assignment, int32_t
  * KAO_NONE), a broker twice in one row, a target row without a broker. */
 int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
                    int32_t max_per_broker, uint64_t seed, int32_t *wave /* [n_partitions] */, int32_t *n_waves, int32_t *lower_bound);
+
+/* Waves capped by the bytes each broker moves.  Classification, participants, wave numbering and the
+ * metadata-only rule are those of kao_plan_waves.  size[p] = bytes of partition p (every partition of the plan).  The traffic of
+ * moving partition p at participant b, t_p(b), is size[p] at each added broker (it receives one copy) and n_added(p) * size[p]
+ * at the source current[p][0] (it sends one copy per added broker).  Byte cap C = max_bytes_per_broker: in every wave the sum of
+ * t_p(b) over the wave's partitions is <= C at each broker b, except that a partition with t_p(b) > C at some participant goes
+ * into a wave where each of its participants has byte load 0 (the fit test at b is "load == 0 || load + t_p(b) <= C"), so it
+ * ends up alone at its brokers apart from partitions that carry 0 bytes there.  Count cap k = max_per_broker as in
+ * kao_plan_waves; k = 0: no count cap; C = 0: no byte cap; with both set both hold.  *lower_bound = max over brokers of
+ * ceil(deg(b) / k) (k >= 1) and ceil(sum_p min(t_p(b), C) / C) (C >= 1), and 1 when a partition moves, with the metadata-only
+ * rule of kao_plan_waves;
+ * *n_waves == *lower_bound proves the split optimal.  Deterministic in (input, seed).  KAO_ERR_INVALID: everything
+ * kao_plan_waves rejects except max_per_broker = 0, and size == NULL, max_per_broker < 0, both caps 0, or some broker's total
+ * traffic sum_p t_p(b) reaching 2^62 bytes (checked before any device is used). */
+int kao_plan_waves_sized(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
+                         const uint64_t *size /* [n_partitions] bytes */, uint64_t max_bytes_per_broker, int32_t max_per_broker,
+                         uint64_t seed, int32_t *wave /* [n_partitions] */, int32_t *n_waves, int32_t *lower_bound);
 
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */

@@ -1,5 +1,6 @@
-// kao_waves.hip -- kao_plan_waves: a reassignment plan split into waves with at most k partition movements per broker per wave
-// (DESIGN.md section 4g).  Kernels and the C entry point.
+// kao_waves.hip -- kao_plan_waves: a reassignment plan split into waves with at most k partition movements per broker per wave;
+// kao_plan_waves_sized: the same with a cap on the bytes each broker moves per wave.  Kernels and the C
+// entry points.
 //
 // A partition p that changed and adds brokers (add(p) = target \ current) moves data: its participants S(p) are add(p) plus the
 // copy source current[p][0] (new followers fetch from the leader).  The waves are a first fit: partitions in a priority order,
@@ -14,6 +15,12 @@
 // count is at least the largest participant degree.  Keys are unique within an order ((~maxdeg) << 32 | a bijection of p), so
 // the result depends on (input, seed) only.  Order 0 is degree-descending, ties by partition index; orders 1.. break the ties by
 // a seeded bijective hash.  The order with the fewest waves wins (ties: the lowest order).
+//
+// Sized (kao_plan_waves_sized): participant b of p carries traffic t_p(b) = size[p] at an added broker, n_added(p) * size[p] at
+// the source.  The fit test at b adds "load_bytes == 0 || load_bytes + t_p(b) <= C" (C = 0: no byte cap) to the count test
+// (k = 0: no count cap); a partition above C thus goes alone.  The key's high word becomes (~code(max_b t_p(b))) << 16 |
+// ~min(maxdeg, 0xFFFF), so order 0 is first fit decreasing by traffic.  The rounds are unchanged: the argument above holds for
+// any fit test that depends on the loads a partition sees.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,10 +51,19 @@ __host__ __device__ inline uint32_t wave_salt(uint64_t seed, uint32_t o) {  // s
     return (uint32_t)(z ^ (z >> 31));
 }
 
-// priority key of partition p in order o: smaller = earlier.  Unique within an order for p < 2^32.
-__device__ inline uint64_t wave_key(uint32_t o, uint32_t p, int32_t maxdeg, uint32_t salt) {
+// priority key of partition p in order o: smaller = earlier.  Unique within an order for p < 2^32.  khi is the partition's high
+// word (k_wave_bound): ~maxdeg for the count-only planner, ~traffic code and ~degree for the sized one.
+__device__ inline uint64_t wave_key(uint32_t o, uint32_t p, uint32_t khi, uint32_t salt) {
     const uint32_t tie = o == 0 ? p : wave_mix32(p ^ salt);
-    return (uint64_t)(0xFFFFFFFFu - (uint32_t)maxdeg) << 32 | tie;
+    return (uint64_t)khi << 32 | tie;
+}
+
+// monotone 16-bit code of a byte count: 0 -> 0; otherwise (bit length e, 1..64) << 9 | the 9 bits below the leading one
+// (truncated), at most 64 << 9 | 511 = 33,279.  A logarithmic scale with a 9-bit mantissa, integer-only.
+__device__ inline uint32_t wave_bytes_code(uint64_t t) {
+    if (t == 0) return 0;
+    const int e = 64 - __clzll((long long)t);
+    return (uint32_t)e << 9 | (uint32_t)((t << (64 - e)) >> 54 & 0x1FFu);
 }
 
 // wavefront-aggregated atomics on the few global control words (one atomic per wavefront, all 64 lanes must be active)
@@ -68,9 +84,14 @@ __device__ inline void wave_max_to(int32_t v, int32_t *dst) {
 
 // One thread per partition: unchanged -> wave -1; changed without an added broker -> wave 0 (moves no data); otherwise the
 // partition joins the list of moving ones (slot order depends on timing; everything downstream is keyed by p, not by slot).
+// Sized: also each participant's traffic traf[slot][j], and per broker tot[b] = T_b = sum of t_p(b) and clamp[b] = sum of
+// min(t_p(b), C) (C = 0: no byte cap, clamp unused).
+template <bool Sized>
 __global__ void k_wave_classify(int32_t P, int32_t W, const uint16_t *__restrict__ cur, const uint16_t *__restrict__ tgt,
                                 int32_t *__restrict__ wave, uint16_t *__restrict__ part, uint8_t *__restrict__ npart,
-                                int32_t *__restrict__ mv_idx, int32_t *__restrict__ deg, int32_t *__restrict__ ctl) {
+                                int32_t *__restrict__ mv_idx, int32_t *__restrict__ deg, int32_t *__restrict__ ctl,
+                                const uint64_t *__restrict__ size, uint64_t C, uint64_t *__restrict__ traf,
+                                unsigned long long *__restrict__ tot, unsigned long long *__restrict__ clamp) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint16_t c[KAO_MAX_RF], n[KAO_MAX_RF], s[kWavePart];
     bool changed = false;
@@ -102,44 +123,88 @@ __global__ void k_wave_classify(int32_t P, int32_t W, const uint16_t *__restrict
         part[(size_t)slot * kWavePart + j] = s[j];
         atomicAdd(&deg[s[j]], 1);
     }
+    if constexpr (Sized) {
+        const int n_added = c[0] != KAO_NONE ? ns - 1 : ns;   // the source, when there is one, is the last participant
+        const uint64_t sz = size[p];
+        for (int j = 0; j < ns; ++j) {
+            const uint64_t t = j < n_added ? sz : (uint64_t)n_added * sz;   // no overflow: the host checked T_b < 2^62
+            traf[(size_t)slot * kWavePart + j] = t;
+            atomicAdd(&tot[s[j]], (unsigned long long)t);
+            if (C) atomicAdd(&clamp[s[j]], (unsigned long long)(t < C ? t : C));
+        }
+    }
 }
 
-// One thread per moving partition: its largest participant degree (the first key), the lower bound max_b ceil(deg(b) / k) and
-// the wave cap: p's first fit is at most sum_b floor((deg(b) - 1) / k), since every wave before it is full at some participant.
+// One thread per moving partition: the high word of its key (khi), the lower bound and the wave cap.
+// Count-only: khi = ~maxdeg, LB = max_b ceil(deg(b) / k), and p's first fit is at most sum_b floor((deg(b) - 1) / k) waves
+// later than wave 0, since every wave before it is full at some participant.
+// Sized: a wave before p's is blocked at some participant b, by count (at most floor((deg(b) - 1) / k) such waves, k >= 1) or
+// by bytes (C >= 1: load > C - t_p(b) and load > 0; the other partitions at b carry T_b - t_p(b) bytes and give at most
+// deg(b) - 1 nonzero loads, so at most min(deg(b) - 1, floor((T_b - t_p(b)) / max(1, C - t_p(b) + 1))) such waves).  wcap = 1 +
+// max_p of the sum of both terms over p's participants.  LB = max_b of ceil(deg(b) / k) and ceil(clamp[b] / C), at least 1.
+template <bool Sized>
 __global__ void k_wave_bound(int32_t n_mv, int32_t k, const uint16_t *__restrict__ part, const uint8_t *__restrict__ npart,
-                             const int32_t *__restrict__ deg, int32_t *__restrict__ maxdeg, int32_t *__restrict__ ctl) {
+                             const int32_t *__restrict__ deg, uint32_t *__restrict__ khi, int32_t *__restrict__ ctl, uint64_t C,
+                             const uint64_t *__restrict__ traf, const unsigned long long *__restrict__ tot,
+                             const unsigned long long *__restrict__ clamp) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t md = 0, cap = 0;
+    int32_t md = 0, cap = 0, lb = 0;
     if (i < n_mv) {
+        uint64_t mt = 0;
         for (int j = 0; j < npart[i]; ++j) {
-            const int32_t d = deg[part[(size_t)i * kWavePart + j]];
+            const int b = part[(size_t)i * kWavePart + j];
+            const int32_t d = deg[b];
             md = max(md, d);
-            cap += (d - 1) / k;
+            if constexpr (Sized) {
+                if (k) cap += (d - 1) / k;
+                const uint64_t t = traf[(size_t)i * kWavePart + j];
+                mt = max(mt, t);
+                if (C) {
+                    const uint64_t rest = tot[b] - t;                  // bytes of the other partitions at b
+                    uint64_t by = 0;
+                    if (t > C) by = rest;                              // every nonzero load blocks p
+                    else if (C - t < rest) by = rest / (C - t + 1);    // C - t + 1 <= rest: no overflow
+                    cap += (int32_t)min<uint64_t>(by, (uint64_t)(d - 1));
+                    const unsigned long long cl = clamp[b];
+                    lb = max(lb, (int32_t)(cl / C + (cl % C != 0)));
+                }
+            } else {
+                cap += (d - 1) / k;
+            }
         }
-        maxdeg[i] = md;
+        if constexpr (Sized) {
+            khi[i] = (0xFFFFu - wave_bytes_code(mt)) << 16 | (0xFFFFu - (uint32_t)min(md, 0xFFFF));
+            lb = max(lb, 1);   // a moving partition needs a wave even when every byte count is 0
+        }
+        else
+            khi[i] = 0xFFFFFFFFu - (uint32_t)md;
         cap += 1;
+        if (k) lb = max(lb, (md + k - 1) / k);
     }
-    wave_max_to((md + k - 1) / k, &ctl[CTL_LB]);
+    wave_max_to(lb, &ctl[CTL_LB]);
     wave_max_to(cap, &ctl[CTL_WCAP]);
 }
 
 // Round -1: every moving partition bids into the first round's minkeys.  grid = (slots, orders).
 __global__ void k_wave_seed(int32_t n_mv, int32_t B, uint64_t seed, const uint16_t *__restrict__ part, const uint8_t *__restrict__ npart,
-                            const int32_t *__restrict__ mv_idx, const int32_t *__restrict__ maxdeg, unsigned long long *__restrict__ mk0) {
+                            const int32_t *__restrict__ mv_idx, const uint32_t *__restrict__ khi, unsigned long long *__restrict__ mk0) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t o = blockIdx.y;
     if (i >= n_mv) return;
-    const unsigned long long key = wave_key(o, (uint32_t)mv_idx[i], maxdeg[i], wave_salt(seed, o));
+    const unsigned long long key = wave_key(o, (uint32_t)mv_idx[i], khi[i], wave_salt(seed, o));
     unsigned long long *mk = mk0 + (size_t)o * B;
     for (int j = 0; j < npart[i]; ++j) atomicMin(&mk[part[(size_t)i * kWavePart + j]], key);
 }
 
 // Round r: reads minkey buffer r % 3, bids into (r + 1) % 3, clears (r + 2) % 3 (read by round r - 1, written by round r + 1).
-// flags[(r + 1) % 3] = 1 when a partition is still unplaced after this round.  loads[o][b][w], waveo[o][slot] (-1 = unplaced).
+// flags[(r + 1) % 3] = 1 when a partition is still unplaced after this round.  loads[o][b][w] (movements; sized: only when k >= 1),
+// bytes[o][b][w] (sized), waveo[o][slot] (-1 = unplaced).
+template <bool Sized>
 __global__ void k_wave_round(int32_t r, int32_t n_ord, int32_t n_mv, int32_t B, int32_t wcap, int32_t k, uint64_t seed,
                              const uint16_t *__restrict__ part, const uint8_t *__restrict__ npart, const int32_t *__restrict__ mv_idx,
-                             const int32_t *__restrict__ maxdeg, unsigned long long *__restrict__ mk, int32_t *__restrict__ loads,
-                             int32_t *__restrict__ waveo, int32_t *__restrict__ nw, int32_t *__restrict__ flags, int32_t *__restrict__ ctl) {
+                             const uint32_t *__restrict__ khi, unsigned long long *__restrict__ mk, int32_t *__restrict__ loads,
+                             int32_t *__restrict__ waveo, int32_t *__restrict__ nw, int32_t *__restrict__ flags, int32_t *__restrict__ ctl,
+                             uint64_t C, const uint64_t *__restrict__ traf, uint64_t *__restrict__ bytes) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t o = blockIdx.y;
     const size_t per = (size_t)n_ord * B;
@@ -153,7 +218,7 @@ __global__ void k_wave_round(int32_t r, int32_t n_ord, int32_t n_mv, int32_t B, 
     bool pending = false;
     if (i < n_mv && waveo[(size_t)o * n_mv + i] < 0) {
         const uint32_t p = (uint32_t)mv_idx[i];
-        const unsigned long long key = wave_key(o, p, maxdeg[i], wave_salt(seed, o));
+        const unsigned long long key = wave_key(o, p, khi[i], wave_salt(seed, o));
         const int np = npart[i];
         uint16_t b[kWavePart];
         for (int j = 0; j < np; ++j) b[j] = part[(size_t)i * kWavePart + j];
@@ -163,13 +228,36 @@ __global__ void k_wave_round(int32_t r, int32_t n_ord, int32_t n_mv, int32_t B, 
         if (ready) {
             int32_t *L = loads + (size_t)o * B * wcap;
             int32_t w = 0;
-            for (; w < wcap; ++w) {
-                bool fit = true;
-                for (int j = 0; j < np; ++j) fit &= L[(size_t)b[j] * wcap + w] < k;
-                if (fit) break;
+            if constexpr (Sized) {
+                uint64_t t[kWavePart];
+                for (int j = 0; j < np; ++j) t[j] = traf[(size_t)i * kWavePart + j];
+                uint64_t *Y = bytes + (size_t)o * B * wcap;
+                for (; w < wcap; ++w) {
+                    bool fit = true;
+                    for (int j = 0; j < np; ++j) {
+                        const size_t e = (size_t)b[j] * wcap + w;
+                        if (k) fit &= L[e] < k;
+                        if (C) fit &= Y[e] == 0 || Y[e] + t[j] <= C;   // loads stay below 2^63: no overflow
+                    }
+                    if (fit) break;
+                }
+                if (w < wcap) {
+                    for (int j = 0; j < np; ++j) {
+                        const size_t e = (size_t)b[j] * wcap + w;
+                        if (k) L[e] += 1;
+                        Y[e] += t[j];
+                    }
+                }
+            } else {
+                for (; w < wcap; ++w) {
+                    bool fit = true;
+                    for (int j = 0; j < np; ++j) fit &= L[(size_t)b[j] * wcap + w] < k;
+                    if (fit) break;
+                }
+                if (w < wcap)
+                    for (int j = 0; j < np; ++j) L[(size_t)b[j] * wcap + w] += 1;
             }
             if (w < wcap) {
-                for (int j = 0; j < np; ++j) L[(size_t)b[j] * wcap + w] += 1;
                 waveo[(size_t)o * n_mv + i] = w;
                 atomicMax(&nw[o], w + 1);
             } else {
@@ -206,13 +294,13 @@ struct WaveBufs {
     }
 };
 
-int validate_waves(int32_t B, int32_t P, int32_t W, const uint16_t *cur, const uint16_t *tgt, int32_t k, const int32_t *wave,
+int validate_waves(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *cur, const uint16_t *tgt, const int32_t *wave,
                    const int32_t *n_waves, const int32_t *lower_bound) {
-    if (!cur || !tgt || !wave || !n_waves || !lower_bound) return fail(KAO_ERR_INVALID, "kao_plan_waves: null pointer");
-    if (k < 1) return fail(KAO_ERR_INVALID, "kao_plan_waves: max_per_broker must be >= 1");
-    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, "kao_plan_waves: width must be 1.." + std::to_string(KAO_MAX_RF));
-    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, "kao_plan_waves: n_brokers must be 1..65534");
-    if (P < 0) return fail(KAO_ERR_INVALID, "kao_plan_waves: n_partitions < 0");
+    const std::string f = fn;
+    if (!cur || !tgt || !wave || !n_waves || !lower_bound) return fail(KAO_ERR_INVALID, f + ": null pointer");
+    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, f + ": width must be 1.." + std::to_string(KAO_MAX_RF));
+    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, f + ": n_brokers must be 1..65534");
+    if (P < 0) return fail(KAO_ERR_INVALID, f + ": n_partitions < 0");
     for (int64_t p = 0; p < P; ++p) {
         for (int side = 0; side < 2; ++side) {
             const uint16_t *row = (side ? tgt : cur) + p * W;
@@ -220,25 +308,49 @@ int validate_waves(int32_t B, int32_t P, int32_t W, const uint16_t *cur, const u
             for (int i = 0; i < W; ++i) {
                 if (row[i] == KAO_NONE) continue;
                 if (row[i] >= B)
-                    return fail(KAO_ERR_INVALID, "kao_plan_waves: partition " + std::to_string(p) + ": broker index " + std::to_string(row[i]) + " >= n_brokers");
+                    return fail(KAO_ERR_INVALID, f + ": partition " + std::to_string(p) + ": broker index " + std::to_string(row[i]) + " >= n_brokers");
                 for (int j = 0; j < i; ++j)
-                    if (row[j] == row[i]) return fail(KAO_ERR_INVALID, "kao_plan_waves: partition " + std::to_string(p) + ": broker repeated in a row");
+                    if (row[j] == row[i]) return fail(KAO_ERR_INVALID, f + ": partition " + std::to_string(p) + ": broker repeated in a row");
                 ++filled;
             }
-            if (side == 1 && filled == 0) return fail(KAO_ERR_INVALID, "kao_plan_waves: partition " + std::to_string(p) + ": target row has no broker");
+            if (side == 1 && filled == 0) return fail(KAO_ERR_INVALID, f + ": partition " + std::to_string(p) + ": target row has no broker");
         }
     }
     return KAO_OK;
 }
 
-}  // namespace
+// T_b, the bytes broker b moves over the whole plan, with overflow-checked arithmetic: every load and every load + t_p(b) of the
+// kernel then stays below 2^63.  KAO_ERR_INVALID when some T_b reaches 2^62.  Rows are valid (validate_waves).
+int validate_traffic(int32_t B, int32_t P, int32_t W, const uint16_t *cur, const uint16_t *tgt, const uint64_t *size) {
+    constexpr uint64_t kLimit = uint64_t(1) << 62;
+    std::vector<uint64_t> tot((size_t)B, 0);
+    for (int64_t p = 0; p < P; ++p) {
+        const uint16_t *c = cur + p * W, *n = tgt + p * W;
+        uint16_t add[KAO_MAX_RF];
+        int na = 0;
+        for (int i = 0; i < W; ++i) {
+            if (n[i] == KAO_NONE) continue;
+            bool held = false;
+            for (int j = 0; j < W; ++j) held |= c[j] == n[i];
+            if (!held) add[na++] = n[i];
+        }
+        if (na == 0) continue;   // unchanged, or changed without moving data
+        uint64_t src = 0;
+        bool bad = __builtin_mul_overflow(size[p], (uint64_t)na, &src);
+        for (int j = 0; j < na && !bad; ++j) bad = __builtin_add_overflow(tot[add[j]], size[p], &tot[add[j]]) || tot[add[j]] >= kLimit;
+        if (!bad && c[0] != KAO_NONE) bad = __builtin_add_overflow(tot[c[0]], src, &tot[c[0]]) || tot[c[0]] >= kLimit;
+        if (bad)
+            return fail(KAO_ERR_INVALID, "kao_plan_waves_sized: partition " + std::to_string(p) + ": a broker's traffic reaches 2^62 bytes");
+    }
+    return KAO_OK;
+}
 
-extern "C" int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
-                              int32_t max_per_broker, uint64_t seed, int32_t *wave, int32_t *n_waves, int32_t *lower_bound) {
-    const int32_t B = n_brokers, P = n_partitions, W = width, k = max_per_broker;
-    int rc = validate_waves(B, P, W, current, target, k, wave, n_waves, lower_bound);
+// Both planners after validation.  Sized: size != nullptr, C = max_bytes_per_broker (0 = no byte cap), k = 0 = no count cap.
+template <bool Sized>
+int plan_waves(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *current, const uint16_t *target, const uint64_t *size,
+               uint64_t C, int32_t k, uint64_t seed, int32_t *wave, int32_t *n_waves, int32_t *lower_bound) {
+    int rc = require_init();
     if (rc) return rc;
-    if ((rc = require_init())) return rc;
     *n_waves = 0;
     *lower_bound = 0;
     if (P == 0) return KAO_OK;
@@ -248,18 +360,30 @@ extern "C" int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t w
     hipStream_t st = m.stream;
     uint16_t *d_cur, *d_tgt, *d_part;
     uint8_t *d_npart;
-    int32_t *d_wave, *d_mv, *d_deg, *d_maxdeg, *d_ctl;
+    int32_t *d_wave, *d_mv, *d_deg, *d_ctl;
+    uint32_t *d_khi;
+    uint64_t *d_size = nullptr, *d_traf = nullptr;
+    unsigned long long *d_tot = nullptr, *d_clamp = nullptr;
     const size_t PW = (size_t)P * W;
     if ((rc = m.alloc(&d_cur, PW)) || (rc = m.alloc(&d_tgt, PW)) || (rc = m.alloc(&d_part, (size_t)P * kWavePart)) ||
         (rc = m.alloc(&d_npart, (size_t)P)) || (rc = m.alloc(&d_wave, (size_t)P)) || (rc = m.alloc(&d_mv, (size_t)P)) ||
-        (rc = m.alloc(&d_deg, (size_t)B)) || (rc = m.alloc(&d_maxdeg, (size_t)P)) || (rc = m.alloc(&d_ctl, CTL_N)))
+        (rc = m.alloc(&d_deg, (size_t)B)) || (rc = m.alloc(&d_khi, (size_t)P)) || (rc = m.alloc(&d_ctl, CTL_N)))
+        return rc;
+    if (Sized && ((rc = m.alloc(&d_size, (size_t)P)) || (rc = m.alloc(&d_traf, (size_t)P * kWavePart)) ||
+                  (rc = m.alloc(&d_tot, (size_t)B)) || (rc = m.alloc(&d_clamp, (size_t)B))))
         return rc;
     HIP_TRY(hipMemcpyAsync(d_cur, current, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_tgt, target, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_deg, 0, (size_t)B * sizeof(int32_t), st));
     HIP_TRY(hipMemsetAsync(d_ctl, 0, CTL_N * sizeof(int32_t), st));
+    if (Sized) {
+        HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_tot, 0, (size_t)B * sizeof(unsigned long long), st));
+        HIP_TRY(hipMemsetAsync(d_clamp, 0, (size_t)B * sizeof(unsigned long long), st));
+    }
     const unsigned pblocks = (unsigned)(((size_t)P + kWaveThreads - 1) / kWaveThreads);
-    k_wave_classify<<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_wave, d_part, d_npart, d_mv, d_deg, d_ctl);
+    k_wave_classify<Sized><<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_wave, d_part, d_npart, d_mv, d_deg, d_ctl, d_size, C,
+                                                             d_traf, d_tot, d_clamp);
     HIP_TRY(hipGetLastError());
     int32_t ctl[CTL_N];
     HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
@@ -268,39 +392,43 @@ extern "C" int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t w
     int32_t best_waves = ctl[CTL_CHANGED] ? 1 : 0;  // metadata-only partitions share wave 0
     if (n_mv > 0) {
         const unsigned mblocks = (unsigned)((n_mv + kWaveThreads - 1) / kWaveThreads);
-        k_wave_bound<<<mblocks, kWaveThreads, 0, st>>>(n_mv, k, d_part, d_npart, d_deg, d_maxdeg, d_ctl);
+        k_wave_bound<Sized><<<mblocks, kWaveThreads, 0, st>>>(n_mv, k, d_part, d_npart, d_deg, d_khi, d_ctl, C, d_traf, d_tot, d_clamp);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const int32_t wcap = ctl[CTL_WCAP];
-        // per-order state: loads[B][wcap], waveo[n_mv], three minkey rows [B]
-        const size_t per_order = (size_t)B * wcap * 4 + (size_t)n_mv * 4 + (size_t)3 * B * 8;
+        // per-order state: loads[B][wcap] (sized: only with a count cap), bytes[B][wcap] (sized), waveo[n_mv], three minkey rows [B]
+        const bool counts = !Sized || k > 0;
+        const size_t per_order = (size_t)B * wcap * ((counts ? 4 : 0) + (Sized ? 8 : 0)) + (size_t)n_mv * 4 + (size_t)3 * B * 8;
         const int n_ord = (int)std::max<size_t>(1, std::min<size_t>(kWaveOrders, kWaveBudget / per_order));
-        int32_t *d_loads, *d_waveo, *d_nw, *d_flags;
+        int32_t *d_loads = nullptr, *d_waveo, *d_nw, *d_flags;
+        uint64_t *d_bytes = nullptr;
         unsigned long long *d_mk;
-        if ((rc = m.alloc(&d_loads, (size_t)n_ord * B * wcap)) || (rc = m.alloc(&d_waveo, (size_t)n_ord * n_mv)) ||
-            (rc = m.alloc(&d_mk, (size_t)3 * n_ord * B)) || (rc = m.alloc(&d_nw, (size_t)n_ord)) || (rc = m.alloc(&d_flags, 3)))
+        if ((counts && (rc = m.alloc(&d_loads, (size_t)n_ord * B * wcap))) || (rc = m.alloc(&d_waveo, (size_t)n_ord * n_mv)) ||
+            (rc = m.alloc(&d_mk, (size_t)3 * n_ord * B)) || (rc = m.alloc(&d_nw, (size_t)n_ord)) || (rc = m.alloc(&d_flags, 3)) ||
+            (Sized && (rc = m.alloc(&d_bytes, (size_t)n_ord * B * wcap))))
             return rc;
-        HIP_TRY(hipMemsetAsync(d_loads, 0, (size_t)n_ord * B * wcap * sizeof(int32_t), st));
+        if (counts) HIP_TRY(hipMemsetAsync(d_loads, 0, (size_t)n_ord * B * wcap * sizeof(int32_t), st));
+        if (Sized) HIP_TRY(hipMemsetAsync(d_bytes, 0, (size_t)n_ord * B * wcap * sizeof(uint64_t), st));
         HIP_TRY(hipMemsetAsync(d_waveo, 0xFF, (size_t)n_ord * n_mv * sizeof(int32_t), st));
         HIP_TRY(hipMemsetAsync(d_mk, 0xFF, (size_t)2 * n_ord * B * sizeof(unsigned long long), st));  // rows of rounds 0 and 1
         HIP_TRY(hipMemsetAsync(d_nw, 0, (size_t)n_ord * sizeof(int32_t), st));
         HIP_TRY(hipMemsetAsync(d_flags, 0, 3 * sizeof(int32_t), st));
         const dim3 grid(mblocks, (unsigned)n_ord);
-        k_wave_seed<<<grid, kWaveThreads, 0, st>>>(n_mv, B, seed, d_part, d_npart, d_mv, d_maxdeg, d_mk);
+        k_wave_seed<<<grid, kWaveThreads, 0, st>>>(n_mv, B, seed, d_part, d_npart, d_mv, d_khi, d_mk);
         HIP_TRY(hipGetLastError());
         // every round places at least the lowest key of each order: n_mv rounds always suffice
         int32_t r = 0, left = 1;
         while (left) {
-            if (r > n_mv) return fail(KAO_ERR_HIP, "kao_plan_waves: rounds did not finish");
+            if (r > n_mv) return fail(KAO_ERR_HIP, std::string(fn) + ": rounds did not finish");
             for (int i = 0; i < kWaveBatch; ++i, ++r)
-                k_wave_round<<<grid, kWaveThreads, 0, st>>>(r, n_ord, n_mv, B, wcap, k, seed, d_part, d_npart, d_mv, d_maxdeg, d_mk, d_loads,
-                                                            d_waveo, d_nw, d_flags, d_ctl);
+                k_wave_round<Sized><<<grid, kWaveThreads, 0, st>>>(r, n_ord, n_mv, B, wcap, k, seed, d_part, d_npart, d_mv, d_khi, d_mk, d_loads,
+                                                                   d_waveo, d_nw, d_flags, d_ctl, C, d_traf, d_bytes);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(&left, d_flags + r % 3, sizeof left, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if (ctl[CTL_ERR]) return fail(KAO_ERR_HIP, "kao_plan_waves: a partition found no wave below the cap");
+            if (ctl[CTL_ERR]) return fail(KAO_ERR_HIP, std::string(fn) + ": a partition found no wave below the cap");
         }
         std::vector<int32_t> nw((size_t)n_ord);
         HIP_TRY(hipMemcpyAsync(nw.data(), d_nw, nw.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -315,4 +443,30 @@ extern "C" int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t w
     *n_waves = best_waves;
     *lower_bound = n_mv > 0 ? ctl[CTL_LB] : best_waves;
     return KAO_OK;
+}
+
+}  // namespace
+
+extern "C" int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
+                              int32_t max_per_broker, uint64_t seed, int32_t *wave, int32_t *n_waves, int32_t *lower_bound) {
+    int rc = validate_waves("kao_plan_waves", n_brokers, n_partitions, width, current, target, wave, n_waves, lower_bound);
+    if (rc) return rc;
+    if (max_per_broker < 1) return fail(KAO_ERR_INVALID, "kao_plan_waves: max_per_broker must be >= 1");
+    return plan_waves<false>("kao_plan_waves", n_brokers, n_partitions, width, current, target, nullptr, 0, max_per_broker, seed, wave,
+                             n_waves, lower_bound);
+}
+
+extern "C" int kao_plan_waves_sized(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
+                                    const uint64_t *size, uint64_t max_bytes_per_broker, int32_t max_per_broker, uint64_t seed, int32_t *wave,
+                                    int32_t *n_waves, int32_t *lower_bound) {
+    const char *fn = "kao_plan_waves_sized";
+    int rc = validate_waves(fn, n_brokers, n_partitions, width, current, target, wave, n_waves, lower_bound);
+    if (rc) return rc;
+    if (!size) return fail(KAO_ERR_INVALID, "kao_plan_waves_sized: null size");
+    if (max_per_broker < 0) return fail(KAO_ERR_INVALID, "kao_plan_waves_sized: max_per_broker must be >= 0");
+    if (max_per_broker == 0 && max_bytes_per_broker == 0)
+        return fail(KAO_ERR_INVALID, "kao_plan_waves_sized: max_bytes_per_broker and max_per_broker are both 0 (no cap)");
+    if ((rc = validate_traffic(n_brokers, n_partitions, width, current, target, size))) return rc;
+    return plan_waves<true>(fn, n_brokers, n_partitions, width, current, target, size, max_bytes_per_broker, max_per_broker, seed, wave,
+                            n_waves, lower_bound);
 }

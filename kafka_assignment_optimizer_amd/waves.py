@@ -7,6 +7,10 @@ DESIGN.md section 4g).
 writes wave1.json .. waveN.json, each a reassignment document `kafka-reassign-partitions --execute` takes on its own.  A partition
 moves data when the plan adds brokers to it; its participants are the added brokers and its current preferred leader, from which
 new followers copy.  Balance bands are not enforced on the states between waves.
+
+With partition sizes (`--sizes`, the output of `kafka-log-dirs --describe` or {"partitions": [{"topic", "partition", "size"}]})
+and `--max-bytes-per-broker C`, each wave also moves at most C bytes per broker (kao_plan_waves_sized): an added broker receives
+size[p], the source sends size[p] once per added broker.  `--max-per-broker` is then optional.
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ import ctypes as C
 import json
 import sys
 from dataclasses import dataclass, field
-from typing import List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -42,6 +46,9 @@ class WavePlan:
     wave: np.ndarray              # [P] int32 per partition of WaveInput.keys; -1 = unchanged
     waves: List[dict]             # one reassignment document per wave, wave 0 first
     input: WaveInput
+    size: Optional[np.ndarray] = None                            # [P] uint64 bytes (sized plans)
+    max_broker_bytes: List[int] = field(default_factory=list)    # per wave: the largest bytes one broker moves in it (sized plans)
+    bytes_lower_bound: int = 0    # max_b ceil(sum_p min(t_p(b), C) / C) (sized plans with a byte cap)
 
 
 def _entries(doc: dict, what: str):
@@ -93,15 +100,168 @@ def plan_waves_arrays(current: np.ndarray, target: np.ndarray, n_brokers: int, m
     return wave[:P], int(nw.value), int(lb.value)
 
 
-def plan_waves(current_doc: dict, plan_doc: dict, max_per_broker: int, seed: int = 1) -> WavePlan:
-    """Split `plan_doc` (relative to `current_doc`) into waves of at most `max_per_broker` movements per broker."""
+def plan_waves_sized_arrays(current: np.ndarray, target: np.ndarray, n_brokers: int, size, max_bytes_per_broker: int,
+                            max_per_broker: int = 0, seed: int = 1):
+    """kao_plan_waves_sized on dense rows: size = bytes per partition ([P]), max_bytes_per_broker = C (0: no byte cap),
+    max_per_broker = k (0: no count cap).  (wave int32[P], n_waves, lower_bound)."""
+    cur = np.ascontiguousarray(current, dtype=np.uint16)
+    tgt = np.ascontiguousarray(target, dtype=np.uint16)
+    if cur.shape != tgt.shape or cur.ndim != 2:
+        raise ValueError("current and target must be [P, width] arrays of one shape")
+    P, W = cur.shape
+    sz = np.ascontiguousarray(size, dtype=np.uint64)
+    if sz.shape != (P,):
+        raise ValueError(f"size must hold one value per partition ({P}), got shape {sz.shape}")
+    sz = sz if P else np.zeros(1, dtype=np.uint64)
+    wave = np.zeros(max(P, 1), dtype=np.int32)
+    nw, lb = C.c_int32(0), C.c_int32(0)
+    u16, u64, i32 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    _check(_ffi.load().kao_plan_waves_sized(int(n_brokers), int(P), int(W), cur.ctypes.data_as(u16), tgt.ctypes.data_as(u16),
+                                            sz.ctypes.data_as(u64), int(max_bytes_per_broker), int(max_per_broker),
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, wave.ctypes.data_as(i32), C.byref(nw), C.byref(lb)),
+           "kao_plan_waves_sized")
+    return wave[:P], int(nw.value), int(lb.value)
+
+
+MAX_SIZE = 1 << 53   # sizes above it are not exact as JSON doubles (the C++ reader): rejected, never rounded
+
+
+def _size_value(v, what):
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= MAX_SIZE:
+        raise ValueError(f"{what}: size must be an integer 0..2^53, got {v!r}")
+    return v
+
+
+def parse_sizes(doc_or_text) -> Dict[Tuple[str, int], int]:
+    """Partition sizes in bytes, {(topic, partition): size}, from either
+      * the output of `kafka-log-dirs --describe` (text: the lines before the JSON line are skipped; or the parsed JSON):
+        {"version":1,"brokers":[{"broker":N,"logDirs":[{"partitions":[{"partition":"topic-3","size":123,"isFuture":false}]}]}]}.
+        The partition name splits at its last '-'; a partition's size is the largest size of its non-future replicas;
+      * a plain document {"partitions":[{"topic":"t","partition":3,"size":123}]}.
+    Sizes are integers 0..2^53."""
+    doc = doc_or_text
+    if isinstance(doc_or_text, (str, bytes)):
+        text = doc_or_text.decode() if isinstance(doc_or_text, bytes) else doc_or_text
+        try:
+            doc = json.loads(text)
+        except ValueError:
+            doc = None
+            for line in text.splitlines():
+                if line.lstrip().startswith("{"):
+                    doc = json.loads(line)
+                    break
+            if doc is None:
+                raise ValueError("sizes: no JSON document found") from None
+    if not isinstance(doc, dict):
+        raise ValueError("sizes: expected a JSON object")
+    out: Dict[Tuple[str, int], int] = {}
+    if "brokers" in doc:
+        for br in doc["brokers"]:
+            for ld in br.get("logDirs", []):
+                for e in ld.get("partitions", []):
+                    if e.get("isFuture", False):
+                        continue
+                    name = str(e["partition"])
+                    topic, dash, idx = name.rpartition("-")
+                    if not dash or not topic or not idx.isdigit():
+                        raise ValueError(f"sizes: partition name {name!r} is not <topic>-<partition>")
+                    key = (topic, int(idx))
+                    out[key] = max(out.get(key, 0), _size_value(e["size"], name))
+    elif "partitions" in doc:
+        for e in doc["partitions"]:
+            key = (str(e["topic"]), int(e["partition"]))
+            if key in out:
+                raise ValueError(f"sizes: partition {key[0]}-{key[1]} listed twice")
+            out[key] = _size_value(e["size"], f"{key[0]}-{key[1]}")
+    else:
+        raise ValueError('sizes: expected a "brokers" (kafka-log-dirs) or "partitions" document')
+    return out
+
+
+def traffic(current_row, target_row):
+    """Participants of one partition and their traffic in units of its size: [(dense broker, copies)] -- 1 at each added broker,
+    n_added at the source current[0]; [] when the partition moves no data."""
+    cs = {int(b) for b in current_row if b != NONE}
+    add = [int(b) for b in target_row if b != NONE and int(b) not in cs]
+    if not add:
+        return []
+    return [(b, 1) for b in add] + ([(int(current_row[0]), len(add))] if current_row[0] != NONE else [])
+
+
+def sizes_for(wi: WaveInput, sizes: Dict[Tuple[str, int], int], default_size: Optional[int] = None) -> np.ndarray:
+    """size[p] over wi.keys.  A partition that moves data and has no size takes `default_size`; without one it is a ValueError
+    naming the first few such partitions.  Partitions that move no data take their size or 0."""
+    size = np.zeros(len(wi.keys), dtype=np.uint64)
+    missing = []
+    for i, key in enumerate(wi.keys):
+        if key in sizes:
+            size[i] = sizes[key]
+        elif traffic(wi.current[i], wi.target[i]):
+            if default_size is None:
+                missing.append(f"{key[0]}-{key[1]}")
+            else:
+                size[i] = default_size
+    if missing:
+        more = f" and {len(missing) - 5} more" if len(missing) > 5 else ""
+        raise ValueError(f"no size for moving partitions {', '.join(missing[:5])}{more} (give them in --sizes or set --default-size)")
+    return size
+
+
+def wave_bytes(wi: WaveInput, size: np.ndarray, wave: np.ndarray, n_waves: int, max_bytes_per_broker: int = 0):
+    """(per wave: the largest bytes one broker moves in it, max_b ceil(sum_p min(t_p(b), C) / C) or 0 when C = 0)."""
+    load: Dict[Tuple[int, int], int] = {}
+    clamp: Dict[int, int] = {}
+    for i in range(len(wi.keys)):
+        for b, n in traffic(wi.current[i], wi.target[i]):
+            t = n * int(size[i])
+            load[(int(wave[i]), b)] = load.get((int(wave[i]), b), 0) + t
+            if max_bytes_per_broker:
+                clamp[b] = clamp.get(b, 0) + min(t, max_bytes_per_broker)
+    peak = [0] * n_waves
+    for (w, _), v in load.items():
+        peak[w] = max(peak[w], v)
+    blb = max([-(-v // max_bytes_per_broker) for v in clamp.values()], default=0)
+    return peak, blb
+
+
+def plan_waves(current_doc: dict, plan_doc: dict, max_per_broker: int = 0, seed: int = 1, *, sizes=None, max_bytes_per_broker: int = 0,
+               default_size: Optional[int] = None) -> WavePlan:
+    """Split `plan_doc` (relative to `current_doc`) into waves of at most `max_per_broker` movements per broker.  With `sizes`
+    ({(topic, partition): bytes}, e.g. from parse_sizes; or a kafka-log-dirs / sizes document or text) or `default_size`, the
+    split is kao_plan_waves_sized: at most `max_bytes_per_broker` bytes per broker per wave as well (0 = no byte cap, and
+    max_per_broker 0 = no count cap)."""
     wi = parse_pair(current_doc, plan_doc)
-    wave, nw, lb = plan_waves_arrays(wi.current, wi.target, len(wi.broker_ids), max_per_broker, seed)
+    sized = sizes is not None or default_size is not None or max_bytes_per_broker
+    size = None
+    if sized:
+        if sizes is not None and not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
+            sizes = parse_sizes(sizes)
+        size = sizes_for(wi, sizes or {}, default_size)
+        wave, nw, lb = plan_waves_sized_arrays(wi.current, wi.target, len(wi.broker_ids), size, max_bytes_per_broker, max_per_broker,
+                                               seed)
+    else:
+        wave, nw, lb = plan_waves_arrays(wi.current, wi.target, len(wi.broker_ids), max_per_broker, seed)
     docs = [{"version": 1, "partitions": []} for _ in range(nw)]
     for i, (t, p) in enumerate(wi.keys):
         if wave[i] >= 0:
             docs[int(wave[i])]["partitions"].append({"topic": t, "partition": p, "replicas": wi.target_replicas[i]})
-    return WavePlan(n_waves=nw, lower_bound=lb, optimal=nw == lb, wave=wave, waves=docs, input=wi)
+    res = WavePlan(n_waves=nw, lower_bound=lb, optimal=nw == lb, wave=wave, waves=docs, input=wi)
+    if sized:
+        res.size = size
+        res.max_broker_bytes, res.bytes_lower_bound = wave_bytes(wi, size, wave, nw, int(max_bytes_per_broker))
+    return res
+
+
+def parse_bytes(text: str) -> int:
+    """A byte count: digits with an optional K / M / G / T suffix (powers of 1024), below 2^64."""
+    t = str(text).strip()
+    mult = 1
+    if t and t[-1].upper() in "KMGT":
+        mult = 1024 ** ("KMGT".index(t[-1].upper()) + 1)
+        t = t[:-1]
+    if not t.isdigit() or int(t) * mult >= 1 << 64:
+        raise ValueError(f"not a byte count: {text!r}")
+    return int(t) * mult
 
 
 def main(argv=None) -> int:
@@ -109,20 +269,48 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="kao-waves", description="split a reassignment plan into waves capped per broker")
     ap.add_argument("--current", required=True)
     ap.add_argument("--plan", required=True)
-    ap.add_argument("--max-per-broker", type=int, required=True)
+    ap.add_argument("--max-per-broker", type=int, default=None)
     ap.add_argument("--out-prefix", required=True)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--report", action="store_true")
+    ap.add_argument("--sizes", default=None, help="kafka-log-dirs --describe output, or {\"partitions\":[{topic,partition,size}]}")
+    ap.add_argument("--max-bytes-per-broker", default=None, help="bytes, or with a K/M/G/T suffix (powers of 1024)")
+    ap.add_argument("--default-size", default=None, help="bytes of a moving partition --sizes does not list")
     a = ap.parse_args(argv)
+    sized = a.sizes is not None or a.max_bytes_per_broker is not None or a.default_size is not None
+    cap_bytes, default_size = 0, None
+    try:
+        if a.max_bytes_per_broker is not None:
+            cap_bytes = parse_bytes(a.max_bytes_per_broker)
+        if a.default_size is not None:
+            default_size = parse_bytes(a.default_size)
+            if default_size > MAX_SIZE:
+                raise ValueError(f"--default-size above 2^53: {a.default_size}")
+    except ValueError as e:
+        ap.error(str(e))
+    if not sized and a.max_per_broker is None:
+        ap.error("the following arguments are required: --max-per-broker")
+    if sized and ((a.max_per_broker or 0) < 0 or (not a.max_per_broker and cap_bytes == 0)):
+        ap.error("give --max-per-broker K >= 1 or --max-bytes-per-broker N >= 1 (K = 0: no count cap)")
     try:
         with open(a.current) as f:
             cur = json.load(f)
         with open(a.plan) as f:
             plan = json.load(f)
+        sizes = None
+        if a.sizes is not None:
+            with open(a.sizes) as f:
+                sizes = parse_sizes(f.read())
+        if sized:   # a missing size is reported before the device is touched
+            sizes_for(parse_pair(cur, plan), sizes or {}, default_size)
         from .solver import init
         init(a.device)
-        res = plan_waves(cur, plan, a.max_per_broker, a.seed)
+        if sized:
+            res = plan_waves(cur, plan, a.max_per_broker or 0, a.seed, sizes=sizes or {}, max_bytes_per_broker=cap_bytes,
+                             default_size=default_size)
+        else:
+            res = plan_waves(cur, plan, a.max_per_broker, a.seed)
         for w, doc in enumerate(res.waves):
             with open(f"{a.out_prefix}{w + 1}.json", "w") as f:
                 f.write(json.dumps(doc) + "\n")
@@ -131,8 +319,12 @@ def main(argv=None) -> int:
         return 1
     if a.report:
         sizes = ",".join(str(len(d["partitions"])) for d in res.waves)
+        extra = ""
+        if sized:
+            extra = (f" bytes_lower_bound={res.bytes_lower_bound} max_broker_bytes_per_wave="
+                     + ",".join(str(v) for v in res.max_broker_bytes))
         print(f"waves={res.n_waves} lower_bound={res.lower_bound} optimal={'yes' if res.optimal else 'no'} "
-              f"partitions_per_wave={sizes}", file=sys.stderr)
+              f"partitions_per_wave={sizes}{extra}", file=sys.stderr)
     return 0
 
 
