@@ -1552,7 +1552,8 @@ int lp_open(const kao_topic *t, LpCtx **out, const LpShard *shard) {
     const size_t nvtot = (size_t)D.NV * P + D.GV;
     c->nblk_var = (int)std::min<size_t>((nvtot + kRedBlock - 1) / kRedBlock, (size_t)kVarBlocks);
     c->nblk_p = (P + 255) / 256;
-    c->broker_waves = std::max(1, std::min(4, (int)((150 * 1024) / ((size_t)2 * mc * sizeof(double)))));
+    c->broker_waves = std::max(1, std::min(4, (int)((150 * 1024) / ((size_t)2 * mc * sizeof(double)))));   // as many as LDS holds, up to 4
+    c->broker_waves = (int)std::max<int64_t>(1, std::min<int64_t>(c->broker_waves, env_int("KAO_LP_BROKER_WAVES", c->broker_waves)));   // (test hook: fewer)
     const int n2 = 2 * R, per = 6 * n2 + R;
     c->rack_tile = std::max(1, std::min(16, (int)((64 * 1024) / ((size_t)per * sizeof(double)))));
     c->rack_chunk = std::max(c->rack_tile, ((P + 255) / 256 + c->rack_tile - 1) / c->rack_tile * c->rack_tile);   // about 256 blocks

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import have_gpu, load_golden, to_product_topic
+from lp_helpers import drift_topic as _drift, otopic as _otopic, trace_close as _trace_close
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not have_gpu(), reason="needs a GPU")]
 
@@ -16,32 +17,6 @@ def kao():
     import kafka_assignment_optimizer_amd as k
     k.init(0)
     return k
-
-
-def _drift(ko, B, R, P, dseed=1):
-    from kafka_assignment_optimizer_amd import synthetic as sy
-    pt = sy.drift(sy.make_cluster(B, R, 1, P, 3, [], []), 0.2, dseed)[0]
-    ot = ko.Topic(name=pt.name, broker_ids=np.array(pt.broker_ids), rack_of=np.array(pt.rack_of), n_racks=pt.n_racks,
-                  n_partitions=pt.n_partitions, rf=pt.rf, current=np.array(pt.current), weights=pt.weights,
-                  bounds_override=dict(pt.bounds_override))
-    return pt, ot
-
-
-def _otopic(ko, pt):
-    return ko.Topic(name=pt.name, broker_ids=np.array(pt.broker_ids), rack_of=np.array(pt.rack_of), n_racks=pt.n_racks,
-                    n_partitions=pt.n_partitions, rf=pt.rf, current=np.array(pt.current), weights=pt.weights,
-                    bounds_override=dict(pt.bounds_override))
-
-
-def _trace_close(dev, ref, rel=1e-7):
-    """mu, primal and dual objective of every iterate agree to `rel` while mu >= 1e-6 (afterwards both are at the optimum and
-    the last digits are rounding); the iteration counts differ by at most one."""
-    assert abs(len(dev) - len(ref)) <= 1
-    for a, b in zip(dev, ref):
-        if b[0] < 1e-6:
-            break
-        assert abs(a[0] - b[0]) <= rel * b[0], (a, b)
-        assert abs(a[1] - b[1]) <= rel * max(1.0, abs(b[1])) and abs(a[2] - b[2]) <= rel * max(1.0, abs(b[2])), (a, b)
 
 
 def test_lp_kat1(kao, ko, kp):
