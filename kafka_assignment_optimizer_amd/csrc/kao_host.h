@@ -3,7 +3,12 @@
 //                    upper bound (kao_upper_bound)
 //   kao_session.cpp  runtime (device, error text, arena / stream pools), K-eval plans, canonical tie-break, sessions
 //                    (K-search / K-eval steps, K-bound launches, prices)
-//   kao_solve.cpp    the solve loops on top of sessions: kao_solve, kao_solve_multi (RCCL), kao_solve_capped
+//   kao_solve.cpp    the solve loops on top of sessions: kao_solve, kao_solve_multi (several devices in lockstep), and the readers of the
+//                    last solve's counters (kao_last_solve_timing / _lp / _profile)
+//   kao_rccl.cpp     the collectives of the multi-device paths (kao_rccl.h): the lazy librccl loader, the loop-back table, communicators
+//   kao_lp_fan.cpp   ONE LP sharded over several devices (lp_open_fan, kao_lp_sharded_test)
+//   kao_capped.cpp   kao_solve_capped: Lagrangian prices over kao_solve / kao_solve_multi, through the C ABI only
+//   kao_pairs.cpp    compound edges of leader-balanced pairs for KAO-CX;  kao_round.cpp  KAO-LP's primal side: the iterate rounded to an assignment
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,10 +38,32 @@ constexpr int kMaxDevices = 64;   // device ordinals the per-device tables cover
 int num_cu(int device);
 int require_init();               // kao_init on first use, then hipSetDevice(cur_device())
 bool is_init();
-extern thread_local int t_device; // per-thread override: kao_solve_multi drives several devices from one process
-extern thread_local double g_timing[16];
-extern thread_local double g_lp[8];       // KAO-LP in the last kao_solve (kao_last_solve_lp)
-extern thread_local double g_profile[8];  // K-search as the last profiled kao_solve ran it (kao_last_solve_profile)   // wall-clock breakdown of the last solve (kao_last_solve_timing)
+extern thread_local int t_device; // per-thread override: kao_solve_multi drives several devices from one process (assigned through DeviceScope only)
+// The calling thread on another device for the scope's life: `to` sets the override and makes the device current (`rc`: how the last
+// switch went), and moves an open scope on to the next device of a list; the destructor puts the previous override back and makes
+// cur_device() current again.  Objects that close device resources in their destructors are declared AFTER the scope they live under.
+struct DeviceScope {
+    const int saved = t_device;
+    int rc = KAO_OK;
+    DeviceScope() = default;
+    explicit DeviceScope(int device) { to(device); }
+    DeviceScope(const DeviceScope &) = delete;
+    DeviceScope &operator=(const DeviceScope &) = delete;
+    int to(int device);
+    ~DeviceScope();
+};
+// The counters of this thread's last solve, under the names solver.py gives them; kao_last_solve_timing / _lp / _profile (kao_solve.cpp)
+// alone know the array layout of include/kao.h.  Times are seconds from the solve's entry; counts are kept as doubles, as they are returned.
+struct SolveTiming {
+    double session_ready, time_to_best, results_read_back, returned, launches, delta_candidates, bound_launches, elite_exchanges,
+           bound_iters, cx_calls, cx_gains, search_iters, generations, cx_further_starts, lp_solves, lp_iters;
+};
+struct SolveLp { double solves, iterations, rounded, adopted, fractional_partitions; };   // KAO-LP in the last kao_solve
+struct SolveProfile {   // K-search as the last profiled kao_solve ran it
+    double ms_search, ms_eval, search_launches, restarts, search_bytes_algo, delta_candidates, lds_bytes_search, blocks_search;
+};
+struct SolveCounters { SolveTiming timing; SolveLp lp; SolveProfile profile; };
+extern thread_local SolveCounters g_last;
 // The KAO_* environment hooks (tests, measurements, diagnostics): an unset or empty variable gives `dflt`.
 // Every host-side read goes through these, except launch_init's own clamp of KAO_INIT_WAVES (kao_kernels.hip).
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e && *e ? e : nullptr; }

@@ -188,14 +188,14 @@ struct LpCtx;
 // One LP over several devices (round 6): every shard holds a contiguous range of the topic's partitions; the coupling rows and the global
 // variables are replicated.  The sums over the partitions meet through `coll` at fixed points of the iteration (the Schur complement once
 // per factorisation, the coupling right-hand side once per solve, the scalar records of the reductions): every shard calls allreduce with
-// its own rank, buffer and stream; the call returns once the collective is ENQUEUED on every shard's stream (kao_solve.cpp: RCCL, or the
+// its own rank, buffer and stream; the call returns once the collective is ENQUEUED on every shard's stream (kao_lp_fan.cpp: RCCL, or the
 // loop-back table on logical shards).  Sums are taken in rank order, so all shards hold the same bits afterwards.
 struct LpColl {
     virtual int allreduce(int rank, double *buf, size_t n, bool is_min, void *stream) = 0;
     virtual ~LpColl() {}
 };
 struct LpShard { int p0, p1, rank; LpColl *coll; };
-// A set of shard contexts driven as ONE solve (kao_solve.cpp LpFanImpl): lp_open_fan returns shard 0's context, whose lp_begin /
+// A set of shard contexts driven as ONE solve (kao_lp_fan.cpp LpFanImpl): lp_open_fan returns shard 0's context, whose lp_begin /
 // lp_enqueue_mark / lp_poll_mark / lp_finish / lp_primal / lp_abort / lp_close forward here -- the caller (kao_solve's loop) sees one LP.
 struct LpFan {
     virtual int begin(double tol, int maxit, double pert, uint32_t salt) = 0;
@@ -209,7 +209,7 @@ struct LpFan {
 };
 extern thread_local bool t_lp_inner;   // set while the fan itself calls the lp_* functions on its shards (no forwarding then)
 void lp_set_fan(LpCtx *c, LpFan *fan);
-int lp_open_fan(const kao_topic *t, const int *devices, int n_dev, LpCtx **out);   // kao_solve.cpp
+int lp_open_fan(const kao_topic *t, const int *devices, int n_dev, LpCtx **out);   // kao_lp_fan.cpp
 int lp_open(const kao_topic *t, LpCtx **out, const LpShard *shard = nullptr);
 // multipliers (host): a[B] l[B] g[R] in K-bound's fixed point; stats[8], trace: see kao_lp.hip
 int lp_solve(LpCtx *c, double tol, int maxit, int32_t *multipliers, double stats[8], double *trace, double pert = 0.0, uint32_t salt = 0);   // one shot

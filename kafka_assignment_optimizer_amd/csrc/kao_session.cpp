@@ -16,9 +16,7 @@
 namespace kao {
 
 thread_local int t_device = -1;
-thread_local double g_timing[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-thread_local double g_profile[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-thread_local double g_lp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+thread_local SolveCounters g_last{};
 
 namespace {
 thread_local std::string g_err;
@@ -28,6 +26,11 @@ int g_num_cu_of[kMaxDevices] = {0};
 }  // namespace
 
 int cur_device() { return t_device >= 0 ? t_device : g_device; }
+int DeviceScope::to(int device) {
+    t_device = device;
+    return rc = hipSetDevice(device) == hipSuccess ? KAO_OK : fail(KAO_ERR_NO_DEVICE, "hipSetDevice");
+}
+DeviceScope::~DeviceScope() { t_device = saved; if (cur_device() >= 0) (void)hipSetDevice(cur_device()); }
 int num_cu(int device) {
     if (device < 0 || device >= kMaxDevices) return 256;
     if (!g_num_cu_of[device]) {

@@ -1,21 +1,12 @@
-// kao_solve.cpp -- host side of libkao.so, part 3 of 3 (see kao_host.h): the solve loops on top of sessions.
+// kao_solve.cpp -- host side of libkao.so (see kao_host.h): the solve loops on top of sessions.
 //   kao_solve         one device: K-search launches, K-bound beside them on its own stream, KAO-CX (kao_cycle.hip) for
 //                     incumbents the search has stopped improving, stop at the proof
 //   kao_solve_multi   several GPUs in one process: topics dealt LPT, or every GPU on every topic with the elites exchanged by
 //                     ncclAllReduce(min) / ncclBroadcast on the resident key buffers (librccl is opened on first use)
-//   kao_solve_capped  cluster-wide per-broker load caps: Lagrangian prices over independent per-topic solves
-#include <rccl/rccl.h>  // types and prototypes only: librccl.so is loaded on first use (kao_solve_multi), see Rccl below
-#include <dlfcn.h>
-
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
 
-#include "kao_host.h"
+#include "kao_rccl.h"
 
 namespace {
 
@@ -900,305 +891,52 @@ kao_opts solve_defaults(const kao_topic *topics, int32_t n_topics, const kao_opt
     return so;
 }
 
-}  // namespace
-
-namespace kao {
-int api_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
-int api_require_init() { return require_init(); }
-double api_now_s() { return now_s(); }
-}  // namespace kao
-
-extern "C" {
-
-int kao_solve(const kao_topic *topics, int32_t n_topics, const kao_opts *opts, kao_result *results) {
-    const double t0 = now_s();
-    if (!results) return fail(KAO_ERR_INVALID, "null results");
-    if (opts && (opts->team < 0 || opts->team > kTeamMax || opts->schedule < 0 || opts->schedule > 1)) return fail(KAO_ERR_INVALID, "kao_opts: team must be 0..8, schedule 0 or 1");
-    const kao_opts so = solve_defaults(topics, n_topics, opts);
-    SolveRun run;
-    int rc = run.begin(topics, n_topics, so, opts ? opts->target_objective : nullptr, t0, true, true);
-    if (rc) return rc;
-    g_timing[0] = now_s() - t0;
-    const kao_opts &o = run.s->opts;
-    bool hit_time = false;
-    for (;;) {
-        if ((rc = run.launch()) || (rc = run.after_launch())) return rc;
-        if (o.stop_at_bound && run.all_done) break;
-        if (o.max_launches > 0 && run.launches >= o.max_launches) break;
-        if (now_s() - t0 >= o.time_limit_s) { hit_time = true; break; }
-    }
-    g_timing[1] = run.t_last_improve;
-    rc = run.finish(results, hit_time);
-    g_timing[2] = now_s() - t0;
-    g_timing[5] = (double)run.s->delta_total;
-    g_timing[6] = (double)run.s->bound_launches;
-    g_timing[7] = 0;   // elite exchanges between GPUs: none on one device
-    g_timing[8] = 0;   // K-bound iterations, summed over the topics
-    for (int32_t v : run.s->dual_iters) g_timing[8] += (double)v;
-    g_timing[9] = run.cx_calls; g_timing[10] = run.cx_gains; g_timing[11] = (double)run.iters_done; g_timing[12] = run.generations;
-    g_timing[13] = run.cx_more;
-    g_timing[14] = run.lp_solves; g_timing[15] = run.lp_iters;
-    g_lp[0] = run.lp_solves; g_lp[1] = run.lp_iters; g_lp[2] = run.lp_rounded; g_lp[3] = run.lp_round_adopted; g_lp[4] = run.lp_round_fractional;
-    for (double &q : g_profile) q = 0;
-    if (o.profile) {
-        kao_stats st{};
-        if (kao_session_stats(run.s, &st) == KAO_OK) {
-            g_profile[0] = st.ms_search; g_profile[1] = st.ms_eval; g_profile[2] = (double)st.launches; g_profile[3] = st.n_restarts_total;
-            g_profile[4] = (double)st.search_bytes_algo; g_profile[5] = (double)st.delta_candidates; g_profile[6] = st.lds_bytes_search; g_profile[7] = st.blocks_search;
-        }
-    }
-    kao_session_destroy(run.s);
-    run.s = nullptr;
-    g_timing[3] = now_s() - t0;
-    g_timing[4] = run.launches;
-    return rc;
+// The counters of the last solve (kao_host.h g_last) that are summed over its runs start from zero in every call (kao_solve_multi's kept the previous kao_solve's values)
+void clear_run_counters() {
+    SolveTiming &t = g_last.timing;
+    t.time_to_best = t.delta_candidates = t.bound_launches = t.elite_exchanges = t.bound_iters = t.cx_calls = t.cx_gains = t.search_iters = 0;
+    t.generations = t.cx_further_starts = t.lp_solves = t.lp_iters = 0;
+    g_last.lp = SolveLp{};
+}
+// A finished run's counters, added into the record: kao_solve calls this once, kao_solve_multi once per device (KAO-LP over all devices: a
+// replicated topic in the LP's regime is a race, every device runs its own solve)
+void add_run_counters(const SolveRun &run) {
+    SolveTiming &t = g_last.timing;
+    t.time_to_best = std::max(t.time_to_best, run.t_last_improve);
+    t.delta_candidates += (double)run.s->delta_total; t.bound_launches += (double)run.s->bound_launches;
+    for (int32_t v : run.s->dual_iters) t.bound_iters += (double)v;   // K-bound iterations, summed over the topics
+    t.cx_calls += run.cx_calls; t.cx_gains += run.cx_gains; t.search_iters += (double)run.iters_done; t.generations += run.generations;
+    t.cx_further_starts += run.cx_more; t.lp_solves += run.lp_solves; t.lp_iters += run.lp_iters;
+    SolveLp &l = g_last.lp;
+    l.solves += run.lp_solves; l.iterations += run.lp_iters; l.rounded += run.lp_rounded; l.adopted += run.lp_round_adopted; l.fractional_partitions += run.lp_round_fractional;
 }
 
-// ------------------------------------------------------------------------------------------------
-// kao_solve_multi: one process, several GPUs
-// ------------------------------------------------------------------------------------------------
-namespace {
-// librccl.so is half a gigabyte of code objects; linking it would make every process that loads libkao.so (the CLI, a JVM)
-// pay for registering them.  It is opened on the first multi-GPU exchange instead.
-struct Rccl {
-    void *h = nullptr;
-    std::string why = "not found";   // text of the last dlopen / dlsym failure
-    decltype(&ncclCommInitAll) CommInitAll = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr;
-    decltype(&ncclBroadcast) Broadcast = nullptr;
-    bool load() {
-        if (h) return true;
-        // RCCL must sit on the SAME HIP / HSA runtime instance this library runs on (a process may hold two: PyTorch wheels
-        // bundle their own next to /opt/rocm's): look for librccl next to the libamdhip64 that serves our HIP calls first
-        std::vector<std::string> names;
-        Dl_info info;
-        if (dladdr(reinterpret_cast<void *>(&hipGetDeviceCount), &info) && info.dli_fname) {
-            std::string dir(info.dli_fname);
-            const size_t slash = dir.rfind('/');
-            if (slash != std::string::npos) { dir.resize(slash); names.push_back(dir + "/librccl.so.1"); names.push_back(dir + "/librccl.so"); }
-        }
-        names.push_back("librccl.so.1"); names.push_back("librccl.so"); names.push_back("/opt/rocm/lib/librccl.so.1");
-        for (const std::string &name : names) {
-            h = dlopen(name.c_str(), RTLD_NOW | RTLD_LOCAL);
-            if (h) break;
-            if (const char *e = dlerror()) why = e;   // dlerror() clears the message: read it once, here
-        }
-        if (!h) return false;
-        CommInitAll = reinterpret_cast<decltype(CommInitAll)>(dlsym(h, "ncclCommInitAll"));
-        CommDestroy = reinterpret_cast<decltype(CommDestroy)>(dlsym(h, "ncclCommDestroy"));
-        GetErrorString = reinterpret_cast<decltype(GetErrorString)>(dlsym(h, "ncclGetErrorString"));
-        GroupStart = reinterpret_cast<decltype(GroupStart)>(dlsym(h, "ncclGroupStart"));
-        GroupEnd = reinterpret_cast<decltype(GroupEnd)>(dlsym(h, "ncclGroupEnd"));
-        AllReduce = reinterpret_cast<decltype(AllReduce)>(dlsym(h, "ncclAllReduce"));
-        Broadcast = reinterpret_cast<decltype(Broadcast)>(dlsym(h, "ncclBroadcast"));
-        if (CommInitAll && CommDestroy && GetErrorString && GroupStart && GroupEnd && AllReduce && Broadcast) return true;
-        if (const char *e = dlerror()) why = e; else why = "missing symbol";
-        dlclose(h); h = nullptr;
-        return false;
-    }
-} g_rccl;
+// ---- kao_solve_multi: one process, several GPUs -- the pieces of the function below ----
+// One device's share of the job.  `run` closes its KAO-CX / KAO-LP contexts and its session when it goes, on every way out of
+// kao_solve_multi: the destructor's body (which runs before the members') makes the device current for that.
+struct Dev {
+    SolveRun run; std::vector<kao_topic> tp; std::vector<kao_result> res; std::vector<int64_t> tgt;
+    DeviceScope *scope = nullptr; int device = -1;   // set once the run is about to begin
+    ~Dev() { if (scope) (void)scope->to(device); }
+};
 
-// ---- loop-back collectives (test hook KAO_RCCL_LOOPBACK=1) ----------------------------------------------------------------
-// The same function table filled with an in-process implementation: "ranks" are entries of the device list -- which may name
-// one device several times -- and the two collectives kao_solve_multi uses move the data with plain copies when the group
-// closes.  It exists so that the REAL control flow of the elite exchange (grouped ncclAllReduce(ncclUint64, ncclMin) on the
-// resident key buffers, then one grouped ncclBroadcast per topic from the winner's rank) runs with several communicators on a
-// box that has one GPU (the grouped sequence had never executed with more than one rank).  Never used unless the
-// environment asks for it; results are those RCCL would deliver.
-struct LoopComm { int rank, nranks, device; };
-struct LoopOp { int kind; const void *send; void *recv; size_t count; int dtype, root; LoopComm *comm; hipStream_t st; int op; };
-thread_local std::vector<LoopOp> t_loop_ops;
-thread_local int t_loop_depth = 0;
-uint64_t g_loop_allreduces = 0, g_loop_broadcasts = 0;   // collectives completed (test hook kao_rccl_loopback_counts)
-size_t loop_elem(int dtype) { return dtype == ncclUint64 || dtype == ncclInt64 || dtype == ncclDouble ? 8 : (dtype == ncclUint8 || dtype == ncclInt8 ? 1 : 4); }
-ncclResult_t loop_run() {
-    std::vector<LoopOp> ops;
-    ops.swap(t_loop_ops);
-    if (ops.empty()) return ncclSuccess;
-    const int n = ops[0].comm->nranks;
-    if ((int)ops.size() != n) return ncclInvalidUsage;            // every rank of the communicator must take part
-    std::vector<const LoopOp *> by_rank((size_t)n, nullptr);
-    for (const LoopOp &o : ops) {
-        if (o.kind != ops[0].kind || o.count != ops[0].count || o.dtype != ops[0].dtype || o.root != ops[0].root || o.op != ops[0].op || o.comm->nranks != n) return ncclInvalidUsage;
-        if (o.comm->rank < 0 || o.comm->rank >= n || by_rank[(size_t)o.comm->rank]) return ncclInvalidUsage;
-        by_rank[(size_t)o.comm->rank] = &o;
-    }
-    const size_t bytes = ops[0].count * loop_elem(ops[0].dtype);
-    for (const LoopOp &o : ops)   // a collective is ordered behind the work already enqueued on each rank's stream
-        if (hipSetDevice(o.comm->device) != hipSuccess || hipStreamSynchronize(o.st) != hipSuccess) return ncclUnhandledCudaError;
-    if (ops[0].kind == 0 && ops[0].dtype == ncclDouble) {   // f64 sum / min (KAO-LP's shards): added in RANK order, every rank gets the same bits
-        std::vector<double> acc(ops[0].count), tmp(ops[0].count);
-        for (int r = 0; r < n; ++r) {
-            const LoopOp &o = *by_rank[(size_t)r];
-            if (hipSetDevice(o.comm->device) != hipSuccess || hipMemcpy(r ? tmp.data() : acc.data(), o.send, bytes, hipMemcpyDeviceToHost) != hipSuccess) return ncclUnhandledCudaError;
-            if (r) for (size_t i = 0; i < acc.size(); ++i) acc[i] = ops[0].op == (int)ncclMin ? std::min(acc[i], tmp[i]) : acc[i] + tmp[i];
-        }
-        for (const LoopOp &o : ops)
-            if (hipSetDevice(o.comm->device) != hipSuccess || hipMemcpy(o.recv, acc.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return ncclUnhandledCudaError;
-        ++g_loop_allreduces;
-    } else if (ops[0].kind == 0) {   // all-reduce: uint64 / min (the elite exchange)
-        if (ops[0].dtype != ncclUint64) return ncclInvalidArgument;
-        std::vector<uint64_t> acc(ops[0].count, ~0ull), tmp(ops[0].count);
-        for (const LoopOp &o : ops) {
-            if (hipSetDevice(o.comm->device) != hipSuccess || hipMemcpy(tmp.data(), o.send, bytes, hipMemcpyDeviceToHost) != hipSuccess) return ncclUnhandledCudaError;
-            for (size_t i = 0; i < acc.size(); ++i) acc[i] = std::min(acc[i], tmp[i]);
-        }
-        for (const LoopOp &o : ops)
-            if (hipSetDevice(o.comm->device) != hipSuccess || hipMemcpy(o.recv, acc.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return ncclUnhandledCudaError;
-        ++g_loop_allreduces;
-    } else {                  // broadcast from rank `root`
-        if (ops[0].root < 0 || ops[0].root >= n) return ncclInvalidArgument;
-        std::vector<unsigned char> buf(bytes);
-        const LoopOp &r = *by_rank[(size_t)ops[0].root];
-        if (hipSetDevice(r.comm->device) != hipSuccess || hipMemcpy(buf.data(), r.send, bytes, hipMemcpyDeviceToHost) != hipSuccess) return ncclUnhandledCudaError;
-        for (const LoopOp &o : ops)
-            if (hipSetDevice(o.comm->device) != hipSuccess || hipMemcpy(o.recv, buf.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return ncclUnhandledCudaError;
-        ++g_loop_broadcasts;
-    }
-    return ncclSuccess;
-}
-ncclResult_t loop_CommInitAll(ncclComm_t *comms, int ndev, const int *devlist) {
-    for (int i = 0; i < ndev; ++i) comms[i] = reinterpret_cast<ncclComm_t>(new LoopComm{i, ndev, devlist ? devlist[i] : i});
-    return ncclSuccess;
-}
-ncclResult_t loop_CommDestroy(ncclComm_t c) { delete reinterpret_cast<LoopComm *>(c); return ncclSuccess; }
-const char *loop_GetErrorString(ncclResult_t r) { return r == ncclSuccess ? "no error" : (r == ncclInvalidUsage ? "loop-back: invalid usage (a rank is missing from the group)" : "loop-back: error"); }
-ncclResult_t loop_GroupStart() { ++t_loop_depth; return ncclSuccess; }
-ncclResult_t loop_GroupEnd() { if (t_loop_depth <= 0) return ncclInvalidUsage; return --t_loop_depth == 0 ? loop_run() : ncclSuccess; }
-ncclResult_t loop_AllReduce(const void *send, void *recv, size_t count, ncclDataType_t dt, ncclRedOp_t op, ncclComm_t c, hipStream_t st) {
-    if (!((dt == ncclUint64 && op == ncclMin) || (dt == ncclDouble && (op == ncclMin || op == ncclSum)))) return ncclInvalidArgument;
-    t_loop_ops.push_back(LoopOp{0, send, recv, count, (int)dt, 0, reinterpret_cast<LoopComm *>(c), st, (int)op});
-    return t_loop_depth == 0 ? loop_run() : ncclSuccess;
-}
-ncclResult_t loop_Broadcast(const void *send, void *recv, size_t count, ncclDataType_t dt, int root, ncclComm_t c, hipStream_t st) {
-    t_loop_ops.push_back(LoopOp{1, send, recv, count, (int)dt, root, reinterpret_cast<LoopComm *>(c), st, 0});
-    return t_loop_depth == 0 ? loop_run() : ncclSuccess;
-}
-struct LoopTable : Rccl {
-    LoopTable() {
-        CommInitAll = &loop_CommInitAll; CommDestroy = &loop_CommDestroy; GetErrorString = &loop_GetErrorString;
-        GroupStart = &loop_GroupStart; GroupEnd = &loop_GroupEnd; AllReduce = &loop_AllReduce; Broadcast = &loop_Broadcast;
-    }
-} g_loop;
-bool loopback_wanted() { return env_int("KAO_RCCL_LOOPBACK", 0) != 0; }
-
-struct CommSet { std::vector<int> devices; const Rccl *api; std::vector<ncclComm_t> comms; };
-std::vector<CommSet> g_comms;   // communicators per (device list, function table) (creation costs ~100 ms with RCCL; kept until kao_shutdown)
-std::mutex g_comm_mu;
-int comms_for(const std::vector<int> &devices, std::vector<ncclComm_t> &out, const Rccl **api_out) {
-    std::lock_guard<std::mutex> lock(g_comm_mu);
-    const bool loop = loopback_wanted();
-    const Rccl *api = loop ? &g_loop : &g_rccl;
-    *api_out = api;
-    for (const CommSet &c : g_comms) if (c.devices == devices && c.api == api) { out = c.comms; return KAO_OK; }
-    if (!loop && !g_rccl.load()) return fail(KAO_ERR_HIP, std::string("librccl.so not available: ") + g_rccl.why);
-    for (int d : devices) {  // RCCL expects every device's primary context to exist already
-        if (hipSetDevice(d) != hipSuccess || hipFree(nullptr) != hipSuccess) return fail(KAO_ERR_HIP, "cannot initialise device " + std::to_string(d));
-        void *probe = nullptr;
-        if (hipMalloc(&probe, 256) == hipSuccess) (void)hipFree(probe);
-    }
-    if (cur_device() >= 0) (void)hipSetDevice(cur_device());
-    CommSet c; c.devices = devices; c.api = api; c.comms.resize(devices.size());
-    const ncclResult_t r = api->CommInitAll(c.comms.data(), (int)devices.size(), devices.data());
-    if (r != ncclSuccess) return fail(KAO_ERR_HIP, std::string("ncclCommInitAll: ") + api->GetErrorString(r));
-    g_comms.push_back(c);
-    out = c.comms;
-    return KAO_OK;
-}
-}  // namespace
-
-void kao_multi_shutdown_comms(void) {
-    std::lock_guard<std::mutex> lock(g_comm_mu);
-    for (CommSet &c : g_comms) for (ncclComm_t cm : c.comms) (void)c.api->CommDestroy(cm);
-    g_comms.clear();
-}
-
-// Diagnostic: the collectives kao_solve_multi uses, on small resident buffers of the listed (distinct) devices -- rank r holds
-// keys {100 - r, 7 + r, ~0, r}; after ncclAllReduce(ncclUint64, ncclMin) every rank must hold {101 - n, 7, ~0, 0}, and after
-// ncclBroadcast from the last rank every rank holds that rank's 64-byte pattern.  0 = ok.
-int kao_rccl_selftest(const int32_t *devices, int32_t n_dev) {
-    if (!devices || n_dev < 1 || n_dev > kMaxDevices) return fail(KAO_ERR_INVALID, "bad device list");
-    std::vector<int> devs(devices, devices + n_dev);
-    std::vector<ncclComm_t> comms;
-    const Rccl *api = nullptr;
-    int rc = comms_for(devs, comms, &api);
-    if (rc) return rc;
-    const Rccl &cc = *api;   // RCCL, or the loop-back table (KAO_RCCL_LOOPBACK=1: the list may then repeat a device)
-    std::vector<unsigned long long *> keys((size_t)n_dev, nullptr), out((size_t)n_dev, nullptr);
-    std::vector<unsigned char *> pat((size_t)n_dev, nullptr);
-    std::vector<hipStream_t> st((size_t)n_dev, nullptr);
-    bool ok = true;
-    for (int d = 0; d < n_dev && ok; ++d) {
-        ok = hipSetDevice(devs[(size_t)d]) == hipSuccess && hipMalloc(reinterpret_cast<void **>(&keys[(size_t)d]), 32) == hipSuccess &&
-             hipMalloc(reinterpret_cast<void **>(&out[(size_t)d]), 32) == hipSuccess && hipMalloc(reinterpret_cast<void **>(&pat[(size_t)d]), 64) == hipSuccess &&
-             hipStreamCreateWithFlags(&st[(size_t)d], hipStreamNonBlocking) == hipSuccess;
-        const unsigned long long h[4] = {100ull - (unsigned)d, 7ull + (unsigned)d, ~0ull, (unsigned long long)d};
-        unsigned char p[64];
-        for (int i = 0; i < 64; ++i) p[i] = (unsigned char)(d * 64 + i);
-        ok = ok && hipMemcpy(keys[(size_t)d], h, 32, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(pat[(size_t)d], p, 64, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    ncclResult_t nr = ok ? cc.GroupStart() : ncclSystemError;
-    for (int d = 0; d < n_dev && nr == ncclSuccess; ++d) nr = cc.AllReduce(keys[(size_t)d], out[(size_t)d], 4, ncclUint64, ncclMin, comms[(size_t)d], st[(size_t)d]);
-    if (nr == ncclSuccess) nr = cc.GroupEnd();
-    if (nr == ncclSuccess) nr = cc.GroupStart();
-    for (int d = 0; d < n_dev && nr == ncclSuccess; ++d) nr = cc.Broadcast(pat[(size_t)d], pat[(size_t)d], 64, ncclUint8, n_dev - 1, comms[(size_t)d], st[(size_t)d]);
-    if (nr == ncclSuccess) nr = cc.GroupEnd();
-    ok = ok && nr == ncclSuccess;
-    for (int d = 0; d < n_dev && ok; ++d) {
-        unsigned long long h[4]; unsigned char p[64];
-        ok = hipSetDevice(devs[(size_t)d]) == hipSuccess && hipStreamSynchronize(st[(size_t)d]) == hipSuccess &&
-             hipMemcpy(h, out[(size_t)d], 32, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(p, pat[(size_t)d], 64, hipMemcpyDeviceToHost) == hipSuccess;
-        ok = ok && h[0] == 101ull - (unsigned)n_dev && h[1] == 7ull && h[2] == ~0ull && h[3] == 0ull;
-        for (int i = 0; i < 64 && ok; ++i) ok = p[i] == (unsigned char)((n_dev - 1) * 64 + i);
-    }
-    for (int d = 0; d < n_dev; ++d) {
-        (void)hipSetDevice(devs[(size_t)d]);
-        (void)hipFree(keys[(size_t)d]); (void)hipFree(out[(size_t)d]); (void)hipFree(pat[(size_t)d]);
-        if (st[(size_t)d]) (void)hipStreamDestroy(st[(size_t)d]);
-    }
-    if (cur_device() >= 0) (void)hipSetDevice(cur_device());
-    if (!ok) return fail(KAO_ERR_HIP, nr != ncclSuccess ? std::string("RCCL: ") + cc.GetErrorString(nr) : std::string("RCCL self-test: wrong result"));
-    return KAO_OK;
-}
-
-int kao_solve_multi(const kao_topic *topics, int32_t n_topics, const int32_t *devices, int32_t n_dev, const kao_opts *opts,
-                    kao_result *results) {
-    const double t0 = now_s();
+int check_multi_args(const kao_topic *topics, int32_t n_topics, const int32_t *devices, int32_t n_dev, const kao_opts *opts, const kao_result *results, std::vector<int> &devs, bool &distinct) {
     if (!topics || n_topics < 1 || !results) return fail(KAO_ERR_INVALID, "no topics / null results");
     if (!devices || n_dev < 1 || n_dev > kMaxDevices) return fail(KAO_ERR_INVALID, "bad device list");
     if (opts && (opts->team < 0 || opts->team > kTeamMax || opts->schedule < 0 || opts->schedule > 1)) return fail(KAO_ERR_INVALID, "kao_opts: team must be 0..8, schedule 0 or 1");
     int n_hw = 0;
     if (hipGetDeviceCount(&n_hw) != hipSuccess || n_hw <= 0) return fail(KAO_ERR_NO_DEVICE, "no HIP device");
-    std::vector<int> devs(devices, devices + n_dev);
-    bool distinct = true;
+    devs.assign(devices, devices + n_dev);
+    distinct = true;
     for (int i = 0; i < n_dev; ++i) {
         if (devs[(size_t)i] < 0 || devs[(size_t)i] >= n_hw) return fail(KAO_ERR_INVALID, "device ordinal out of range");
         for (int j = 0; j < i; ++j) distinct &= devs[(size_t)j] != devs[(size_t)i];
     }
-    if (!is_init()) { int rc0 = kao_init(devs[0]); if (rc0) return rc0; }
-    if (n_dev == 1) {   // a list of one device: exactly kao_solve (generations, islands), on THAT device (ADVICE r03: callers used to
-                        // fall back to the kao_init device and ignore the ordinal they had been given)
-        const int saved = t_device;
-        t_device = devs[0];
-        const int rc1 = kao_solve(topics, n_topics, opts, results);
-        t_device = saved;
-        if (cur_device() >= 0) (void)hipSetDevice(cur_device());
-        return rc1;
-    }
-    const kao_opts so = solve_defaults(topics, n_topics, opts);
-    const bool replicated = n_topics < n_dev;   // fewer topics than GPUs: every GPU searches every topic, elites are exchanged
-    bool race = false;
-    for (int i = 0; replicated && i < n_topics; ++i) race |= (int64_t)topics[i].n_partitions * topics[i].rf >= 32768;
-    // KAO_MULTI_LP=shard (opt-in, round 6): instead of racing whole solves, ONE LP of such a topic runs sharded by partition range over all
-    // devices (driven by device 0's solve loop through lp_open_fan; the other devices' loops launch no K-search while it has the GPUs).
-    // Exercised on logical shards only (tests/test_gpu_parity.py); the race stays the default until a multi-GPU node has timed both.
-    bool shard_lp = false, lp_pause = false;
-    { const char *e = env_str("KAO_MULTI_LP"); shard_lp = race && e && e[0] == 's' && (distinct || loopback_wanted()); }
-    // ---- shards: LPT by brokers x partitions (independent sub-problems, README.md:146-184) ----
+    return KAO_OK;
+}
+
+// ---- shards: LPT by brokers x partitions (independent sub-problems, README.md:146-184); replicated: every device gets every topic ----
+std::vector<std::vector<int>> assign_shards(const kao_topic *topics, int n_topics, int n_dev, bool replicated) {
     std::vector<std::vector<int>> shard((size_t)n_dev);
     if (replicated) for (auto &sh : shard) for (int i = 0; i < n_topics; ++i) sh.push_back(i);
     else {
@@ -1214,18 +952,205 @@ int kao_solve_multi(const kao_topic *topics, int32_t n_topics, const int32_t *de
             load[(size_t)best] += size_of(i);
         }
     }
+    return shard;
+}
+
+// certificates: any GPU's bound is valid for the topic
+void share_certificates(std::vector<Dev> &D, int n_topics) {
+    for (int i = 0; i < n_topics; ++i) {
+        int64_t ub = INT64_MAX;
+        for (Dev &x : D) ub = std::min(ub, x.run.s->ub[(size_t)i]);
+        for (Dev &x : D) x.run.s->ub[(size_t)i] = ub;
+    }
+}
+
+// ---- elite exchange: per topic the smallest packed key of all devices and the device that holds it (true: some device's incumbent is not the global one) ...
+bool global_best_keys(const std::vector<Dev> &D, int n_topics, std::vector<uint64_t> &gmin, std::vector<int> &root) {
+    const int n_dev = (int)D.size();
+    bool differ = false;
+    for (int i = 0; i < n_topics; ++i) {
+        gmin[(size_t)i] = ~0ull; root[(size_t)i] = 0;
+        for (int d = 0; d < n_dev; ++d) {
+            const uint64_t k = D[(size_t)d].run.keys[(size_t)i] | 0;  // host copy read by after_launch
+            if (k < gmin[(size_t)i]) { gmin[(size_t)i] = k; root[(size_t)i] = d; }
+        }
+        for (int d = 0; d < n_dev; ++d) differ |= (D[(size_t)d].run.keys[(size_t)i] >> 20) != (gmin[(size_t)i] >> 20);
+    }
+    return differ;
+}
+// ... then min-allreduce of the keys on the resident buffers, winners broadcast: stages every GPU's current winners, moves the global ones to every GPU (`api`: the table of the communicators `comms`, or null: logical
+// shards on one device without KAO_RCCL_LOOPBACK=1), and has every GPU adopt them
+int exchange_elites(std::vector<Dev> &D, int n_topics, const std::vector<uint64_t> &gmin, const std::vector<int> &root, const Rccl *api, const std::vector<ncclComm_t> &comms) {
+    const int n_dev = (int)D.size();
+    int rc = KAO_OK;
+    for (int d = 0; d < n_dev && !rc; ++d) {   // stage every GPU's current winners
+        kao_session *s = D[(size_t)d].run.s;
+        if (hipSetDevice(s->device) != hipSuccess) { rc = fail(KAO_ERR_HIP, "hipSetDevice"); break; }
+        launch_gather(s->d_topics, s->n_topics, s->d_keys, s->d_best, s->d_viol, s->d_win_assign, s->d_win_viol, s->stream);
+    }
+    if (!rc && api) {
+        ncclResult_t nr = api->GroupStart();
+        for (int d = 0; d < n_dev && nr == ncclSuccess; ++d) {
+            kao_session *s = D[(size_t)d].run.s;
+            nr = api->AllReduce(s->d_keys, s->d_keys_glob, (size_t)n_topics, ncclUint64, ncclMin, comms[(size_t)d], s->stream);
+        }
+        if (nr == ncclSuccess) nr = api->GroupEnd();
+        for (int i = 0; i < n_topics && nr == ncclSuccess; ++i) {
+            if ((gmin[(size_t)i] >> 44) != 0) continue;   // no feasible assignment anywhere yet
+            nr = api->GroupStart();
+            for (int d = 0; d < n_dev && nr == ncclSuccess; ++d) {
+                kao_session *s = D[(size_t)d].run.s;
+                const TopicDev &td = s->pts[(size_t)i].d;
+                uint16_t *buf = s->d_win_assign + td.win_off;
+                nr = api->Broadcast(buf, buf, (size_t)td.P * td.RF * 2, ncclUint8, root[(size_t)i], comms[(size_t)d], s->stream);
+            }
+            if (nr == ncclSuccess) nr = api->GroupEnd();
+        }
+        if (nr != ncclSuccess) rc = fail(KAO_ERR_HIP, std::string("RCCL elite exchange: ") + api->GetErrorString(nr));
+    } else if (!rc) {   // logical shards on one device: same data movement through plain copies
+        for (int d = 0; d < n_dev && !rc; ++d) {
+            kao_session *s = D[(size_t)d].run.s;
+            if (hipSetDevice(s->device) != hipSuccess) { rc = fail(KAO_ERR_HIP, "hipSetDevice"); break; }
+            for (int r2 = 0; r2 < n_dev; ++r2) (void)hipStreamSynchronize(D[(size_t)r2].run.s->stream);
+            if (hipMemcpyAsync(s->d_keys_glob, gmin.data(), (size_t)n_topics * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess) rc = fail(KAO_ERR_HIP, "hipMemcpyAsync");
+            for (int i = 0; i < n_topics && !rc; ++i) {
+                if ((gmin[(size_t)i] >> 44) != 0 || root[(size_t)i] == d) continue;
+                kao_session *sr = D[(size_t)root[(size_t)i]].run.s;
+                const TopicDev &td = s->pts[(size_t)i].d;
+                if (hipMemcpyAsync(s->d_win_assign + td.win_off, sr->d_win_assign + td.win_off, (size_t)td.P * td.RF * 2,
+                                   hipMemcpyDeviceToDevice, s->stream) != hipSuccess) rc = fail(KAO_ERR_HIP, "hipMemcpyAsync");
+            }
+            if (!rc && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(KAO_ERR_HIP, "hipStreamSynchronize");  // gmin is reused
+        }
+    }
+    for (int d = 0; d < n_dev && !rc; ++d) {
+        kao_session *s = D[(size_t)d].run.s;
+        if (hipSetDevice(s->device) != hipSuccess) { rc = fail(KAO_ERR_HIP, "hipSetDevice"); break; }
+        launch_adopt_global(s->d_keys, s->d_keys_glob, n_topics, s->stream);
+        if (hipGetLastError() != hipSuccess) rc = fail(KAO_ERR_HIP, "k_adopt_global");
+    }
+    return rc;
+}
+
+// every device's results read back under its own device: dealt topics go to their places; of replicated ones the GPU holding the best key answers
+int collect_results(std::vector<Dev> &D, DeviceScope &scope, const std::vector<int> &devs, const std::vector<std::vector<int>> &shard, bool replicated,
+                    const kao_topic *topics, int n_topics, bool hit_time, kao_result *results) {
+    const int n_dev = (int)D.size();
+    int rc = KAO_OK;
+    for (int d = 0; d < n_dev && !rc && !replicated; ++d) {
+        Dev &x = D[(size_t)d];
+        if (!x.run.s) continue;
+        x.res.assign(x.tp.size(), kao_result{});
+        for (size_t k = 0; k < x.tp.size(); ++k) x.res[k].assignment = results[shard[(size_t)d][k]].assignment;
+        if (!(rc = scope.to(devs[(size_t)d]))) rc = x.run.finish(x.res.data(), hit_time);
+        for (size_t k = 0; k < x.tp.size() && !rc; ++k) results[shard[(size_t)d][k]] = x.res[k];
+    }
+    if (!replicated) return rc;
+    std::vector<std::vector<kao_result>> rs((size_t)n_dev, std::vector<kao_result>((size_t)n_topics));
+    std::vector<std::vector<std::vector<uint16_t>>> bufs((size_t)n_dev);
+    for (int d = 0; d < n_dev && !rc; ++d) {
+        bufs[(size_t)d].resize((size_t)n_topics);
+        for (int i = 0; i < n_topics; ++i) {
+            bufs[(size_t)d][(size_t)i].assign((size_t)topics[i].n_partitions * topics[i].rf, (uint16_t)KAO_NONE);
+            rs[(size_t)d][(size_t)i] = kao_result{};
+            rs[(size_t)d][(size_t)i].assignment = bufs[(size_t)d][(size_t)i].data();
+        }
+        if (!(rc = scope.to(devs[(size_t)d]))) rc = D[(size_t)d].run.finish(rs[(size_t)d].data(), hit_time);
+    }
+    for (int i = 0; i < n_topics && !rc; ++i) {
+        int best = 0;
+        auto better = [&](const kao_result &a, const kao_result &b) {   // feasible first, then objective
+            const bool fa = a.status != KAO_STATUS_NO_FEASIBLE && a.status != KAO_STATUS_INFEASIBLE_PROVEN;
+            const bool fb = b.status != KAO_STATUS_NO_FEASIBLE && b.status != KAO_STATUS_INFEASIBLE_PROVEN;
+            return fa != fb ? fa : a.objective > b.objective;
+        };
+        for (int d = 1; d < n_dev; ++d) if (better(rs[(size_t)d][(size_t)i], rs[(size_t)best][(size_t)i])) best = d;
+        uint16_t *dst = results[i].assignment;
+        results[i] = rs[(size_t)best][(size_t)i];
+        results[i].assignment = dst;
+        if (dst) std::memcpy(dst, bufs[(size_t)best][(size_t)i].data(), bufs[(size_t)best][(size_t)i].size() * 2);
+        int64_t ub = INT64_MAX;
+        for (int d = 0; d < n_dev; ++d) ub = std::min(ub, rs[(size_t)d][(size_t)i].upper_bound);
+        results[i].upper_bound = ub;
+        if (results[i].status == KAO_STATUS_FEASIBLE_BOUND_GAP || results[i].status == KAO_STATUS_TIME_LIMIT || results[i].status == KAO_STATUS_OPTIMAL_PROVEN)
+            results[i].status = results[i].objective >= ub ? KAO_STATUS_OPTIMAL_PROVEN : (hit_time ? KAO_STATUS_TIME_LIMIT : KAO_STATUS_FEASIBLE_BOUND_GAP);
+    }
+    return rc;
+}
+
+}  // namespace
+
+namespace kao {
+int api_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
+int api_require_init() { return require_init(); }
+double api_now_s() { return now_s(); }
+}  // namespace kao
+
+extern "C" {
+int kao_solve(const kao_topic *topics, int32_t n_topics, const kao_opts *opts, kao_result *results) {
+    const double t0 = now_s();
+    if (!results) return fail(KAO_ERR_INVALID, "null results");
+    if (opts && (opts->team < 0 || opts->team > kTeamMax || opts->schedule < 0 || opts->schedule > 1)) return fail(KAO_ERR_INVALID, "kao_opts: team must be 0..8, schedule 0 or 1");
+    const kao_opts so = solve_defaults(topics, n_topics, opts);
+    SolveRun run;
+    int rc = run.begin(topics, n_topics, so, opts ? opts->target_objective : nullptr, t0, true, true);
+    if (rc) return rc;
+    SolveTiming &tm = g_last.timing;
+    tm.session_ready = now_s() - t0;
+    const kao_opts &o = run.s->opts;
+    bool hit_time = false;
+    for (;;) {
+        if ((rc = run.launch()) || (rc = run.after_launch())) return rc;
+        if (o.stop_at_bound && run.all_done) break;
+        if (o.max_launches > 0 && run.launches >= o.max_launches) break;
+        if (now_s() - t0 >= o.time_limit_s) { hit_time = true; break; }
+    }
+    rc = run.finish(results, hit_time);
+    tm.results_read_back = now_s() - t0;
+    clear_run_counters();   // (elite exchanges between GPUs: none on one device)
+    add_run_counters(run);
+    g_last.profile = SolveProfile{};
+    if (o.profile) {
+        kao_stats st{};
+        if (kao_session_stats(run.s, &st) == KAO_OK)
+            g_last.profile = SolveProfile{st.ms_search, st.ms_eval, (double)st.launches, (double)st.n_restarts_total, (double)st.search_bytes_algo,
+                                          (double)st.delta_candidates, (double)st.lds_bytes_search, (double)st.blocks_search};
+    }
+    kao_session_destroy(run.s);
+    run.s = nullptr;
+    tm.returned = now_s() - t0; tm.launches = run.launches;
+    return rc;
+}
+
+int kao_solve_multi(const kao_topic *topics, int32_t n_topics, const int32_t *devices, int32_t n_dev, const kao_opts *opts,
+                    kao_result *results) {
+    const double t0 = now_s();
+    std::vector<int> devs;
+    bool distinct = true;
+    int rc = check_multi_args(topics, n_topics, devices, n_dev, opts, results, devs, distinct);
+    if (rc || (!is_init() && (rc = kao_init(devs[0])))) return rc;
+    if (n_dev == 1) {   // a list of one device: exactly kao_solve (generations, islands), on THAT device (ADVICE r03: callers used to
+                        // fall back to the kao_init device and ignore the ordinal they had been given)
+        DeviceScope on(devs[0]);
+        return kao_solve(topics, n_topics, opts, results);
+    }
+    const kao_opts so = solve_defaults(topics, n_topics, opts);
+    const bool replicated = n_topics < n_dev;   // fewer topics than GPUs: every GPU searches every topic, elites are exchanged
+    bool race = false;
+    for (int i = 0; replicated && i < n_topics; ++i) race |= (int64_t)topics[i].n_partitions * topics[i].rf >= 32768;
+    // KAO_MULTI_LP=shard (opt-in, round 6): instead of racing whole solves, ONE LP of such a topic runs sharded by partition range over all
+    // devices (driven by device 0's solve loop through lp_open_fan; the other devices' loops launch no K-search while it has the GPUs).
+    // Exercised on logical shards only (tests/test_gpu_parity.py); the race stays the default until a multi-GPU node has timed both.
+    bool shard_lp = false, lp_pause = false;
+    { const char *e = env_str("KAO_MULTI_LP"); shard_lp = race && e && e[0] == 's' && (distinct || loopback_wanted()); }
+    const std::vector<std::vector<int>> shard = assign_shards(topics, n_topics, n_dev, replicated);
     std::vector<ncclComm_t> comms;
     // logical shards on one device (tests) merge through plain copies -- or, with KAO_RCCL_LOOPBACK=1, through the same grouped
     // collective calls as distinct devices, served by the in-process loop-back table
-    const bool use_rccl = replicated && (distinct || loopback_wanted());
     const Rccl *api = nullptr;
-    if (use_rccl) { int rc0 = comms_for(devs, comms, &api); if (rc0) return rc0; }
-
-    struct Dev { SolveRun run; std::vector<kao_topic> tp; std::vector<kao_result> res; std::vector<int64_t> tgt; };
+    if (replicated && (distinct || loopback_wanted()) && (rc = comms_for(devs, comms, &api))) return rc;
+    DeviceScope scope;   // the caller's device comes back AFTER the devices' runs are gone (D is declared below it), on every return
     std::vector<Dev> D((size_t)n_dev);
-    const int saved_t_device = t_device;
-    auto cleanup = [&]() { t_device = saved_t_device; if (cur_device() >= 0) (void)hipSetDevice(cur_device()); };
-    int rc = KAO_OK;
     for (int d = 0; d < n_dev && !rc; ++d) {
         Dev &x = D[(size_t)d];
         for (int i : shard[(size_t)d]) { x.tp.push_back(topics[i]); if (opts && opts->target_objective) x.tgt.push_back(opts->target_objective[i]); }
@@ -1239,12 +1164,13 @@ int kao_solve_multi(const kao_topic *topics, int32_t n_topics, const int32_t *de
         if (replicated && d > 0 && (!race || shard_lp)) o.dual_iters = -1;
         x.run.lp_salt0 = replicated ? d : 0;
         if (shard_lp) { if (d == 0) x.run.lp_fan_devs = devs; else x.run.ext_pause = &lp_pause; }
-        t_device = devs[(size_t)d];
-        if (hipSetDevice(t_device) != hipSuccess) { rc = fail(KAO_ERR_NO_DEVICE, "hipSetDevice"); break; }
+        x.scope = &scope; x.device = devs[(size_t)d];
+        if ((rc = scope.to(x.device))) break;
         rc = x.run.begin(x.tp.data(), (int)x.tp.size(), o, x.tgt.empty() ? nullptr : x.tgt.data(), t0);
     }
-    if (rc) { cleanup(); return rc; }
-    g_timing[0] = now_s() - t0;
+    if (rc) return rc;
+    SolveTiming &tm = g_last.timing;
+    tm.session_ready = now_s() - t0;
     const int exch = std::max(1, so.elite_period);
     bool hit_time = false;
     int rounds = 0;
@@ -1253,77 +1179,17 @@ int kao_solve_multi(const kao_topic *topics, int32_t n_topics, const int32_t *de
     std::vector<int> root((size_t)n_topics);
     for (;;) {
         if (shard_lp && D[0].run.s) lp_pause = D[0].run.search_paused();
-        for (int d = 0; d < n_dev && !rc; ++d) if (D[(size_t)d].run.s) { t_device = devs[(size_t)d]; rc = D[(size_t)d].run.launch(); }
-        for (int d = 0; d < n_dev && !rc; ++d) if (D[(size_t)d].run.s) { t_device = devs[(size_t)d]; rc = D[(size_t)d].run.after_launch(); }
+        for (int d = 0; d < n_dev && !rc; ++d) if (D[(size_t)d].run.s && !(rc = scope.to(devs[(size_t)d]))) rc = D[(size_t)d].run.launch();
+        for (int d = 0; d < n_dev && !rc; ++d) if (D[(size_t)d].run.s && !(rc = scope.to(devs[(size_t)d]))) rc = D[(size_t)d].run.after_launch();
         if (rc) break;
         ++rounds;
         if (replicated) {
-            // certificates: any GPU's bound is valid for the topic
-            for (int i = 0; i < n_topics; ++i) {
-                int64_t ub = INT64_MAX;
-                for (Dev &x : D) ub = std::min(ub, x.run.s->ub[(size_t)i]);
-                for (Dev &x : D) x.run.s->ub[(size_t)i] = ub;
-            }
+            share_certificates(D, n_topics);
             if (rounds % exch == 0 || so.stop_at_bound) {
-                // ---- elite exchange: min-allreduce of the packed best keys on the resident buffers, winners broadcast ----
-                bool differ = false;
-                for (int i = 0; i < n_topics; ++i) {
-                    gmin[(size_t)i] = ~0ull; root[(size_t)i] = 0;
-                    for (int d = 0; d < n_dev; ++d) {
-                        const uint64_t k = D[(size_t)d].run.keys[(size_t)i] | 0;  // host copy read by after_launch
-                        if (k < gmin[(size_t)i]) { gmin[(size_t)i] = k; root[(size_t)i] = d; }
-                    }
-                    for (int d = 0; d < n_dev; ++d) differ |= (D[(size_t)d].run.keys[(size_t)i] >> 20) != (gmin[(size_t)i] >> 20);
-                }
+                const bool differ = global_best_keys(D, n_topics, gmin, root);
                 if (differ && rounds % exch == 0) {
                     ++exchanges;
-                    for (int d = 0; d < n_dev && !rc; ++d) {   // stage every GPU's current winners
-                        kao_session *s = D[(size_t)d].run.s;
-                        if (hipSetDevice(s->device) != hipSuccess) { rc = fail(KAO_ERR_HIP, "hipSetDevice"); break; }
-                        launch_gather(s->d_topics, s->n_topics, s->d_keys, s->d_best, s->d_viol, s->d_win_assign, s->d_win_viol, s->stream);
-                    }
-                    if (!rc && use_rccl) {
-                        ncclResult_t nr = api->GroupStart();
-                        for (int d = 0; d < n_dev && nr == ncclSuccess; ++d) {
-                            kao_session *s = D[(size_t)d].run.s;
-                            nr = api->AllReduce(s->d_keys, s->d_keys_glob, (size_t)n_topics, ncclUint64, ncclMin, comms[(size_t)d], s->stream);
-                        }
-                        if (nr == ncclSuccess) nr = api->GroupEnd();
-                        for (int i = 0; i < n_topics && nr == ncclSuccess; ++i) {
-                            if ((gmin[(size_t)i] >> 44) != 0) continue;   // no feasible assignment anywhere yet
-                            nr = api->GroupStart();
-                            for (int d = 0; d < n_dev && nr == ncclSuccess; ++d) {
-                                kao_session *s = D[(size_t)d].run.s;
-                                const TopicDev &td = s->pts[(size_t)i].d;
-                                uint16_t *buf = s->d_win_assign + td.win_off;
-                                nr = api->Broadcast(buf, buf, (size_t)td.P * td.RF * 2, ncclUint8, root[(size_t)i], comms[(size_t)d], s->stream);
-                            }
-                            if (nr == ncclSuccess) nr = api->GroupEnd();
-                        }
-                        if (nr != ncclSuccess) rc = fail(KAO_ERR_HIP, std::string("RCCL elite exchange: ") + api->GetErrorString(nr));
-                    } else if (!rc) {   // logical shards on one device: same data movement through plain copies
-                        for (int d = 0; d < n_dev && !rc; ++d) {
-                            kao_session *s = D[(size_t)d].run.s;
-                            if (hipSetDevice(s->device) != hipSuccess) { rc = fail(KAO_ERR_HIP, "hipSetDevice"); break; }
-                            for (int r2 = 0; r2 < n_dev; ++r2) (void)hipStreamSynchronize(D[(size_t)r2].run.s->stream);
-                            if (hipMemcpyAsync(s->d_keys_glob, gmin.data(), (size_t)n_topics * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess) rc = fail(KAO_ERR_HIP, "hipMemcpyAsync");
-                            for (int i = 0; i < n_topics && !rc; ++i) {
-                                if ((gmin[(size_t)i] >> 44) != 0 || root[(size_t)i] == d) continue;
-                                kao_session *sr = D[(size_t)root[(size_t)i]].run.s;
-                                const TopicDev &td = s->pts[(size_t)i].d;
-                                if (hipMemcpyAsync(s->d_win_assign + td.win_off, sr->d_win_assign + td.win_off, (size_t)td.P * td.RF * 2,
-                                                   hipMemcpyDeviceToDevice, s->stream) != hipSuccess) rc = fail(KAO_ERR_HIP, "hipMemcpyAsync");
-                            }
-                            if (!rc && hipStreamSynchronize(s->stream) != hipSuccess) rc = fail(KAO_ERR_HIP, "hipStreamSynchronize");  // gmin is reused
-                        }
-                    }
-                    for (int d = 0; d < n_dev && !rc; ++d) {
-                        kao_session *s = D[(size_t)d].run.s;
-                        if (hipSetDevice(s->device) != hipSuccess) { rc = fail(KAO_ERR_HIP, "hipSetDevice"); break; }
-                        launch_adopt_global(s->d_keys, s->d_keys_glob, n_topics, s->stream);
-                        if (hipGetLastError() != hipSuccess) rc = fail(KAO_ERR_HIP, "k_adopt_global");
-                    }
-                    if (rc) break;
+                    if ((rc = exchange_elites(D, n_topics, gmin, root, api, comms))) break;
                 }
                 for (Dev &x : D)   // every run now judges "done" against the global incumbents
                     for (int i = 0; i < n_topics; ++i) if (gmin[(size_t)i] < x.run.keys[(size_t)i]) x.run.keys[(size_t)i] = gmin[(size_t)i];
@@ -1339,609 +1205,37 @@ int kao_solve_multi(const kao_topic *topics, int32_t n_topics, const int32_t *de
         if (now_s() - t0 >= tl) { hit_time = true; break; }
     }
     // ---- results ----
-    double t_improve = 0, cand = 0, bl = 0;
-    if (!rc) {
-        if (replicated) {   // per topic: the GPU holding the best key answers
-            std::vector<std::vector<kao_result>> rs((size_t)n_dev, std::vector<kao_result>((size_t)n_topics));
-            std::vector<std::vector<std::vector<uint16_t>>> bufs((size_t)n_dev);
-            for (int d = 0; d < n_dev && !rc; ++d) {
-                bufs[(size_t)d].resize((size_t)n_topics);
-                for (int i = 0; i < n_topics; ++i) {
-                    bufs[(size_t)d][(size_t)i].assign((size_t)topics[i].n_partitions * topics[i].rf, (uint16_t)KAO_NONE);
-                    rs[(size_t)d][(size_t)i] = kao_result{};
-                    rs[(size_t)d][(size_t)i].assignment = bufs[(size_t)d][(size_t)i].data();
-                }
-                t_device = devs[(size_t)d];
-                rc = D[(size_t)d].run.finish(rs[(size_t)d].data(), hit_time);
-            }
-            for (int i = 0; i < n_topics && !rc; ++i) {
-                int best = 0;
-                auto better = [&](const kao_result &a, const kao_result &b) {   // feasible first, then objective
-                    const bool fa = a.status != KAO_STATUS_NO_FEASIBLE && a.status != KAO_STATUS_INFEASIBLE_PROVEN;
-                    const bool fb = b.status != KAO_STATUS_NO_FEASIBLE && b.status != KAO_STATUS_INFEASIBLE_PROVEN;
-                    return fa != fb ? fa : a.objective > b.objective;
-                };
-                for (int d = 1; d < n_dev; ++d) if (better(rs[(size_t)d][(size_t)i], rs[(size_t)best][(size_t)i])) best = d;
-                uint16_t *dst = results[i].assignment;
-                results[i] = rs[(size_t)best][(size_t)i];
-                results[i].assignment = dst;
-                if (dst) std::memcpy(dst, bufs[(size_t)best][(size_t)i].data(), bufs[(size_t)best][(size_t)i].size() * 2);
-                int64_t ub = INT64_MAX;
-                for (int d = 0; d < n_dev; ++d) ub = std::min(ub, rs[(size_t)d][(size_t)i].upper_bound);
-                results[i].upper_bound = ub;
-                if (results[i].status == KAO_STATUS_FEASIBLE_BOUND_GAP || results[i].status == KAO_STATUS_TIME_LIMIT || results[i].status == KAO_STATUS_OPTIMAL_PROVEN)
-                    results[i].status = results[i].objective >= ub ? KAO_STATUS_OPTIMAL_PROVEN : (hit_time ? KAO_STATUS_TIME_LIMIT : KAO_STATUS_FEASIBLE_BOUND_GAP);
-            }
-        } else {
-            for (int d = 0; d < n_dev && !rc; ++d) {
-                Dev &x = D[(size_t)d];
-                if (!x.run.s) continue;
-                x.res.assign(x.tp.size(), kao_result{});
-                for (size_t k = 0; k < x.tp.size(); ++k) x.res[k].assignment = results[shard[(size_t)d][k]].assignment;
-                t_device = devs[(size_t)d];
-                rc = x.run.finish(x.res.data(), hit_time);
-                for (size_t k = 0; k < x.tp.size() && !rc; ++k) results[shard[(size_t)d][k]] = x.res[k];
-            }
-        }
-    }
-    g_timing[2] = now_s() - t0;
-    for (int i = 8; i < 16; ++i) g_timing[i] = 0;   // counters of this call, summed over the devices (they kept the previous kao_solve's values)
-    for (Dev &x : D) if (x.run.s) {
-        t_improve = std::max(t_improve, x.run.t_last_improve); cand += (double)x.run.s->delta_total; bl += (double)x.run.s->bound_launches;
-        for (int32_t v : x.run.s->dual_iters) g_timing[8] += (double)v;
-        g_timing[9] += x.run.cx_calls; g_timing[10] += x.run.cx_gains; g_timing[11] += (double)x.run.iters_done;
-        g_timing[12] += x.run.generations; g_timing[13] += x.run.cx_more;
-        g_timing[14] += x.run.lp_solves; g_timing[15] += x.run.lp_iters;
-    }
-    for (double &q : g_lp) q = 0;     // KAO-LP over all devices (a replicated topic in the LP's regime is a race: every device runs its own solve)
-    for (Dev &x : D) if (x.run.s) { g_lp[0] += x.run.lp_solves; g_lp[1] += x.run.lp_iters; g_lp[2] += x.run.lp_rounded; g_lp[3] += x.run.lp_round_adopted; g_lp[4] += x.run.lp_round_fractional; }
-    for (int d = 0; d < n_dev; ++d) if (D[(size_t)d].run.s) { t_device = devs[(size_t)d]; kao_session_destroy(D[(size_t)d].run.s); D[(size_t)d].run.s = nullptr; }
-    cleanup();
-    g_timing[1] = t_improve; g_timing[3] = now_s() - t0; g_timing[4] = rounds; g_timing[5] = cand; g_timing[6] = bl; g_timing[7] = (double)exchanges;
+    if (!rc) rc = collect_results(D, scope, devs, shard, replicated, topics, n_topics, hit_time, results);
+    tm.results_read_back = now_s() - t0;
+    clear_run_counters();   // counters of this call, summed over the devices
+    for (Dev &x : D) if (x.run.s) add_run_counters(x.run);
+    tm.elite_exchanges = (double)exchanges;
+    for (int d = 0; d < n_dev; ++d) if (D[(size_t)d].run.s) { (void)scope.to(devs[(size_t)d]); kao_session_destroy(D[(size_t)d].run.s); D[(size_t)d].run.s = nullptr; }
+    tm.returned = now_s() - t0; tm.launches = rounds;
     return rc;
 }
 
-// ------------------------------------------------------------------------------------------------
-// kao_solve_capped: cluster-wide per-broker load caps, priced (Lagrangian) over independent per-topic solves
-// ------------------------------------------------------------------------------------------------
-}  // extern "C"
-
-// One run of the price loop at ONE price granularity F (price units per objective unit); kao_solve_capped below runs a portfolio of them.
-static int capped_once(const kao_topic *topics, int32_t n_topics, const int32_t *replica_cap, const int32_t *devices, int32_t n_dev,
-                       const kao_opts *opts, int32_t max_rounds, kao_result *results, int64_t *lagrangian_bound, const int F) {
-    const double t0 = now_s();
-    if (!topics || n_topics < 1 || !replica_cap || !results) return fail(KAO_ERR_INVALID, "null argument");
-    const int B = topics[0].n_brokers;
-    int wmax = 1;
-    for (int i = 0; i < n_topics; ++i) {
-        if (topics[i].n_brokers != B) return fail(KAO_ERR_INVALID, "kao_solve_capped: every topic must use the same broker set");
-        if (topics[i].broker_w || topics[i].broker_wl) return fail(KAO_ERR_UNSUPPORTED, "kao_solve_capped: topics with their own broker weights");
-        for (int a = 0; a < 2; ++a) for (int b = 0; b < 2; ++b) wmax = std::max(wmax, topics[i].w[a][b]);
-    }
-    // Price granularity F (price units per objective unit).  Quarter units (F = 4: every role weight times 4 inside the per-topic
-    // solves, prices in steps of 1/4) were tried in round 4 and tightened the Lagrangian bound of the medium golden (exact joint
-    // optimum 9175: bound 9195 with whole prices, 9189 with quarters; the 12-topic case 4100 -> 4097 = exact) -- but K-search's
-    // penalty range is tuned to the README's weights 1..4, with weights 4..16 per-topic solves came back infeasible and whole
-    // rounds yielded no cap-respecting plan (round 4, GPU calls 13-15).  Round 5: the penalty range of the per-topic solves is scaled by
-    // F as well (lam_min / lam_max times F: the ratio penalty : objective stays what K-search is tuned to) and the solves are
-    // feasible again: medium golden bound 9195 (F = 1) -> 9178 (2) -> 9176 (4) against the exact 9175, the 12-topic case 4100 -> 4097 = exact.
-    const int mu_max = std::min(1023, 4 * wmax * F);   // a price above every objective weight already repels every replica
-    kao_opts o{};
-    if (opts) o = *opts;
-    const double limit = o.time_limit_s > 0 ? o.time_limit_s : 10.0;
-    const int rounds = max_rounds > 0 ? max_rounds : 40;
-    if (o.max_launches <= 0) o.max_launches = 6;
-    if (F > 1) { o.lam_min = (o.lam_min > 0 ? o.lam_min : 1) * F; o.lam_max = (o.lam_max > 0 ? o.lam_max : 40) * F; }
-    o.stop_at_bound = 1;
-    o.target_objective = nullptr;
-    std::vector<int32_t> mu((size_t)B, 0), bw((size_t)B, 0), mu_inc((size_t)B, 0);
-    std::vector<kao_topic> tp(topics, topics + n_topics);
-    for (int i = 0; i < n_topics; ++i)
-        for (int a = 0; a < 2; ++a) for (int b = 0; b < 2; ++b) tp[(size_t)i].w[a][b] = topics[i].w[a][b] * F;
-    std::vector<std::vector<uint16_t>> buf((size_t)n_topics), inc((size_t)n_topics);
-    std::vector<kao_result> res((size_t)n_topics), inc_res((size_t)n_topics);
-    for (int i = 0; i < n_topics; ++i) buf[(size_t)i].assign((size_t)topics[i].n_partitions * topics[i].rf, (uint16_t)KAO_NONE);
-    int64_t inc_total = -1, best_L = INT64_MAX, n_slots = 0;   // inc_total in objective units, best_L = floor(dual value in objective units)
-    for (int i = 0; i < n_topics; ++i) n_slots += (int64_t)topics[i].n_partitions * topics[i].rf;
-    std::vector<int64_t> load((size_t)B);
-    auto floor_div = [](int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
-    // Rounds 0 .. rounds-1: WHOLE objective units (F price units), the loop of rounds 2-3.  Then up to rounds/2 more: with a
-    // cap-respecting plan in hand, quarter units restarted from THAT plan's prices (with quarter steps from the start -- or from the
-    // last prices -- the medium golden found no cap-respecting plan at all, and a toy lost two units: GPU calls 13 / 14); without
-    // one, prices only rise (every broker over its cap, by its excess) until a plan respects the caps.
-    int rc = KAO_OK, r = 0, fine_from = -1;
-    bool raise_only = false;
-    const int rounds_all = rounds + rounds / 2;
-    for (; r < rounds_all; ++r) {
-        const double left = limit - (now_s() - t0);
-        if (r > 0 && left <= 0) break;
-        if (r >= rounds && fine_from < 0 && !raise_only) {
-            if (inc_total >= 0 && F > 1) { fine_from = r; mu = mu_inc; }
-            else if (inc_total < 0) raise_only = true;
-            else break;
-        }
-        int M = 0;
-        for (int b = 0; b < B; ++b) M = std::max(M, mu[(size_t)b]);
-        for (int b = 0; b < B; ++b) bw[(size_t)b] = M - mu[(size_t)b];   // weights must be >= 0: a constant M per replica does not change any argmax
-        for (int i = 0; i < n_topics; ++i) {
-            tp[(size_t)i].broker_w = M ? bw.data() : nullptr;
-            res[(size_t)i] = kao_result{};
-            res[(size_t)i].assignment = buf[(size_t)i].data();
-        }
-        o.time_limit_s = std::max(0.05, left / std::max(1, std::min(rounds_all - r, 8)));
-        o.seed = (opts ? opts->seed : 0) + (uint64_t)r * 0x9E3779B97F4A7C15ull;
-        rc = (devices && n_dev > 1) ? kao_solve_multi(tp.data(), n_topics, devices, n_dev, &o, res.data())
-                                    : kao_solve(tp.data(), n_topics, &o, res.data());
-        if (rc) break;
-        // ---- broker loads over ALL topics (the allreduce(SUM) of a sharded deployment), objective without the weights ----
-        std::fill(load.begin(), load.end(), 0);
-        bool all_feasible = true;
-        int64_t total = 0, total_w = 0;   // in 1/F units
-        for (int i = 0; i < n_topics; ++i) {
-            const kao_result &x = res[(size_t)i];
-            if (x.status == KAO_STATUS_NO_FEASIBLE || x.status == KAO_STATUS_INFEASIBLE_PROVEN) { all_feasible = false; continue; }
-            int64_t wsum = 0;
-            for (size_t k = 0; k < buf[(size_t)i].size(); ++k) { const uint16_t b = buf[(size_t)i][k]; load[b]++; wsum += M ? bw[b] : 0; }
-            total += x.objective - wsum;
-            total_w += x.upper_bound;
-        }
-        int64_t worst = 0, priced = 0;
-        for (int b = 0; b < B; ++b) {
-            if (replica_cap[b] < 0) continue;
-            worst = std::max<int64_t>(worst, load[(size_t)b] - replica_cap[b]);
-            priced += (int64_t)mu[(size_t)b] * replica_cap[b];
-        }
-        // L(mu) <= sum of ANY valid per-topic upper bounds of the weighted topics - M * slots + mu . cap: round 3 -- K-bound now covers
-        // weighted topics, so the per-topic bounds are (nearly) the weighted optima whether or not the search has met them
-        if (all_feasible) best_L = std::min(best_L, floor_div(total_w - (int64_t)M * n_slots + priced, F));
-        if (all_feasible && worst <= 0 && total / F > inc_total) {   // respects every cap: a candidate answer
-            inc_total = total / F;
-            mu_inc = mu;
-            for (int i = 0; i < n_topics; ++i) {
-                inc[(size_t)i] = buf[(size_t)i];
-                inc_res[(size_t)i] = res[(size_t)i];
-                int64_t wsum = 0;
-                for (uint16_t b : buf[(size_t)i]) wsum += M ? bw[b] : 0;
-                inc_res[(size_t)i].objective = (res[(size_t)i].objective - wsum) / F;
-            }
-        }
-        if (inc_total >= 0 && best_L != INT64_MAX && inc_total >= best_L) break;   // incumbent meets the Lagrangian bound: optimal
-        // ---- projected subgradient step on the prices, diminishing: alpha = 1 / (1 + r / 3) price units of the phase ----
-        const bool fine = fine_from >= 0;
-        const int rr = fine ? r - fine_from : (raise_only ? 0 : r);
-        const int den = 1 + rr / 3;
-        const int unit = fine ? 1 : F;
-        if (raise_only && all_feasible && worst <= 0) break;   // the plan just booked respects every cap (loads are counted over feasible topics only: ADVICE r04)
-        bool moved = false;
-        for (int b = 0; b < B; ++b) {
-            if (replica_cap[b] < 0) continue;
-            const int64_t ex = load[(size_t)b] - replica_cap[b];
-            int d = 0;
-            if (ex > 0) d = unit * (int)std::max<int64_t>(1, ex / den);
-            else if (ex < 0 && mu[(size_t)b] > 0 && !raise_only)
-                d = -(int)std::min<int64_t>(mu[(size_t)b], unit * std::max<int64_t>(rr >= 6 ? 0 : 1, (-ex) / (2 * den)));
-            const int nm = std::min(mu_max, std::max(0, mu[(size_t)b] + d));
-            moved |= nm != mu[(size_t)b];
-            mu[(size_t)b] = nm;
-        }
-        if (!moved) {   // prices are stationary: the coarse phase hands over (to the fine one or to raise-only), the others end
-            if (fine || raise_only || r >= rounds - 1) break;
-            r = rounds - 1;
-        }
-    }
-    // ---- repair (round 4): one topic at a time from the incumbent plan.  Capped brokers that ended BELOW their cap were priced a
-    // little too high for somebody: every topic in turn is solved again alone with those brokers one price unit cheaper (all
-    // others as in the incumbent's round), and the new plan of that topic is taken when the topic's own objective grows and no
-    // cap breaks.  Passes repeat while one of them gained and the clock allows.
-    int repairs = 0;
-    if (!rc && inc_total >= 0 && !(best_L != INT64_MAX && inc_total >= best_L)) {
-        std::fill(load.begin(), load.end(), 0);
-        for (int i = 0; i < n_topics; ++i) for (uint16_t b : inc[(size_t)i]) load[b]++;
-        std::vector<int32_t> mu_t((size_t)B), bw_t((size_t)B);
-        std::vector<uint16_t> one;
-        bool gained = true;
-        for (int pass = 0; pass < 4 && gained && !rc; ++pass) {
-            gained = false;
-            for (int i = 0; i < n_topics && !rc; ++i) {
-                if (limit - (now_s() - t0) <= 0) break;
-                bool any_slack = false;
-                for (int b = 0; b < B; ++b) {
-                    const bool slack = replica_cap[b] >= 0 && load[(size_t)b] < replica_cap[b] && mu_inc[(size_t)b] > 0;
-                    mu_t[(size_t)b] = slack ? std::max(0, mu_inc[(size_t)b] - (pass % 2 ? 2 : 1)) : mu_inc[(size_t)b];
-                    any_slack |= slack;
-                }
-                if (!any_slack) break;
-                int M = 0;
-                for (int b = 0; b < B; ++b) M = std::max(M, mu_t[(size_t)b]);
-                for (int b = 0; b < B; ++b) bw_t[(size_t)b] = M - mu_t[(size_t)b];
-                kao_topic t1 = tp[(size_t)i];
-                t1.broker_w = M ? bw_t.data() : nullptr;
-                one.assign(inc[(size_t)i].size(), (uint16_t)KAO_NONE);
-                kao_result r1{};
-                r1.assignment = one.data();
-                o.time_limit_s = std::max(0.02, std::min(0.25, limit - (now_s() - t0)));
-                o.seed = (opts ? opts->seed : 0) + 0xD1B54A32D192ED03ull * (uint64_t)(pass * n_topics + i + 1);
-                rc = kao_solve(&t1, 1, &o, &r1);
-                if (rc) break;
-                if (r1.status == KAO_STATUS_NO_FEASIBLE || r1.status == KAO_STATUS_INFEASIBLE_PROVEN) continue;
-                int64_t wsum = 0;
-                for (uint16_t b : one) wsum += M ? bw_t[b] : 0;
-                const int64_t obj1 = (r1.objective - wsum) / F;
-                if (obj1 <= inc_res[(size_t)i].objective) continue;
-                bool ok = true;
-                for (uint16_t b : inc[(size_t)i]) load[b]--;
-                for (uint16_t b : one) load[b]++;
-                for (int b = 0; b < B && ok; ++b) ok = replica_cap[b] < 0 || load[(size_t)b] <= replica_cap[b];
-                if (!ok) {
-                    for (uint16_t b : one) load[b]--;
-                    for (uint16_t b : inc[(size_t)i]) load[b]++;
-                    continue;
-                }
-                inc_total += obj1 - inc_res[(size_t)i].objective;
-                inc[(size_t)i] = one;
-                inc_res[(size_t)i] = r1;
-                inc_res[(size_t)i].objective = obj1;
-                gained = true;
-                ++repairs;
-            }
-        }
-    }
-    if (!rc) {
-        for (int i = 0; i < n_topics; ++i) {
-            uint16_t *dst = results[i].assignment;
-            if (inc_total >= 0) {
-                results[i] = inc_res[(size_t)i];
-                results[i].status = (best_L != INT64_MAX && inc_total >= best_L) ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
-                results[i].upper_bound = best_L != INT64_MAX ? best_L : INT64_MAX;   // a bound on the SUM over all topics
-                if (dst) std::memcpy(dst, inc[(size_t)i].data(), inc[(size_t)i].size() * 2);
-            } else {
-                results[i] = res[(size_t)i];
-                results[i].status = KAO_STATUS_NO_FEASIBLE; results[i].objective = -1;
-            }
-            results[i].assignment = dst;
-        }
-        if (lagrangian_bound) *lagrangian_bound = best_L;
-    }
-    g_timing[3] = now_s() - t0; g_timing[4] = r; (void)repairs;
-    return rc;
-}
-
-extern "C" {
-
-// A portfolio over the price granularity (round 5): quarter units give the tightest Lagrangian bound (and prices between the whole
-// units, which is where the exact joint optimum's prices often lie), half and whole units different plans -- which granularity finds
-// the best cap-respecting plan varies by instance (medium golden: plan 9169 / 9175 / 9169 with F = 4 / 2 / 1, the 12-topic case 4095 /
-// 4093 / 4097).  The runs share the time limit; the best plan and the smallest bound of all runs are returned, and the portfolio ends as
-// soon as they meet.
-int kao_solve_capped(const kao_topic *topics, int32_t n_topics, const int32_t *replica_cap, const int32_t *devices, int32_t n_dev,
-                     const kao_opts *opts, int32_t max_rounds, kao_result *results, int64_t *lagrangian_bound) {
-    const double t0 = now_s();
-    if (!topics || n_topics < 1 || !replica_cap || !results) return fail(KAO_ERR_INVALID, "null argument");
-    int wmax = 1;
-    for (int i = 0; i < n_topics; ++i) for (int a = 0; a < 2; ++a) for (int b = 0; b < 2; ++b) wmax = std::max(wmax, topics[i].w[a][b]);
-    std::vector<int> fs;
-    for (int f : {4, 2, 1}) if (f == 1 || wmax * f <= 255) fs.push_back(f);   // F = 1 always runs (weights up to 1023 are valid; only the scaled runs need room)
-    kao_opts o{};
-    if (opts) o = *opts;
-    const double limit = o.time_limit_s > 0 ? o.time_limit_s : 10.0;
-    std::vector<std::vector<uint16_t>> buf((size_t)n_topics);
-    std::vector<kao_result> res((size_t)n_topics);
-    for (int i = 0; i < n_topics; ++i) buf[(size_t)i].assign((size_t)topics[i].n_partitions * topics[i].rf, (uint16_t)KAO_NONE);
-    int64_t best_total = -1, best_L = INT64_MAX;
-    int rc = KAO_OK;
-    double rounds_total = 0;
-    auto copy_out = [&]() {
-        for (int i = 0; i < n_topics; ++i) {
-            uint16_t *dst = results[i].assignment;
-            results[i] = res[(size_t)i];
-            results[i].assignment = dst;
-            if (dst) std::memcpy(dst, buf[(size_t)i].data(), buf[(size_t)i].size() * 2);
-        }
-    };
-    for (size_t k = 0; k < fs.size() && !rc; ++k) {
-        const double left = limit - (now_s() - t0);
-        if (k > 0 && left <= 0.05) break;
-        for (int i = 0; i < n_topics; ++i) { res[(size_t)i] = kao_result{}; res[(size_t)i].assignment = buf[(size_t)i].data(); }
-        o.time_limit_s = std::max(0.05, left / (double)(fs.size() - k));
-        int64_t L = INT64_MAX;
-        rc = capped_once(topics, n_topics, replica_cap, devices, n_dev, &o, max_rounds, res.data(), &L, fs[k]);
-        if (rc) break;
-        rounds_total += g_timing[4];
-        best_L = std::min(best_L, L);
-        int64_t total = 0;
-        bool ok = true;
-        for (int i = 0; i < n_topics; ++i) { ok = ok && res[(size_t)i].status != KAO_STATUS_NO_FEASIBLE; total += res[(size_t)i].objective; }
-        if ((ok && total > best_total) || best_total < 0) {   // (no cap-respecting plan yet: the last run's report -- NO_FEASIBLE -- stands until one is found)
-            if (ok) best_total = total;
-            copy_out();
-        }
-        if (best_total >= 0 && best_L != INT64_MAX && best_total >= best_L) break;
-    }
-    if (!rc) {
-        for (int i = 0; i < n_topics && best_total >= 0; ++i) {
-            results[i].status = (best_L != INT64_MAX && best_total >= best_L) ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
-            results[i].upper_bound = best_L;
-        }
-        if (lagrangian_bound) *lagrangian_bound = best_L;
-    }
-    g_timing[3] = now_s() - t0; g_timing[4] = rounds_total;
-    return rc;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// ONE LP over several devices (round 6): the collective side of kao_lp.hip's shards, and a test hook
-// ------------------------------------------------------------------------------------------------
-namespace {
-// Every shard's host thread walks the same sequence of launches; where the sequence holds a collective each thread hands in its buffer
-// and stream and waits; the LAST one to arrive issues the grouped ncclAllReduce(ncclDouble, ncclSum | ncclMin) for every rank -- the
-// single-process, one-thread-per-group calling pattern kao_solve_multi's elite exchange uses, served by RCCL on distinct devices and by
-// the loop-back table on logical shards -- and releases the others.  A thread that fails raises `failed`: nobody waits for it.
-struct LpGroup : LpColl {
-    int n = 0;
-    std::vector<ncclComm_t> comms;
-    const Rccl *api = nullptr;
-    std::mutex mu;
-    std::condition_variable cv;
-    int arrived = 0, rc = KAO_OK;
-    uint64_t gen = 0, collectives = 0;
-    bool failed = false;
-    struct Op { double *buf; size_t n; bool is_min; hipStream_t st; };
-    std::vector<Op> ops;
-    int issue() {
-        for (int r = 1; r < n; ++r)
-            if (ops[(size_t)r].n != ops[0].n || ops[(size_t)r].is_min != ops[0].is_min) return fail(KAO_ERR_HIP, "KAO-LP shards: the ranks disagree about a collective");
-        ncclResult_t nr = api->GroupStart();
-        for (int r = 0; r < n && nr == ncclSuccess; ++r) {
-            const Op &o = ops[(size_t)r];
-            nr = api->AllReduce(o.buf, o.buf, o.n, ncclDouble, o.is_min ? ncclMin : ncclSum, comms[(size_t)r], o.st);
-        }
-        if (nr == ncclSuccess) nr = api->GroupEnd();
-        ++collectives;
-        return nr == ncclSuccess ? KAO_OK : fail(KAO_ERR_HIP, std::string("KAO-LP shards: all-reduce: ") + api->GetErrorString(nr));
-    }
-    int allreduce(int rank, double *buf, size_t cnt, bool is_min, void *stream) override {
-        std::unique_lock<std::mutex> lk(mu);
-        if (failed) return rc ? rc : KAO_ERR_HIP;
-        ops[(size_t)rank] = Op{buf, cnt, is_min, static_cast<hipStream_t>(stream)};
-        const uint64_t my = gen;
-        if (++arrived == n) {
-            const int r = issue();
-            arrived = 0; ++gen;
-            if (r) { failed = true; rc = r; }
-            cv.notify_all();
-            return r;
-        }
-        cv.wait(lk, [&] { return gen != my || failed; });
-        return failed ? (rc ? rc : KAO_ERR_HIP) : KAO_OK;
-    }
-    void give_up(int code) { std::lock_guard<std::mutex> lk(mu); if (!failed) { failed = true; rc = code; } cv.notify_all(); }
-};
-
-// N shard contexts behind ONE LpCtx-shaped front (kao_internal.h LpFan): one persistent host thread per shard (its device current, the
-// collectives of LpGroup between them); a call of the front runs the same lp_* function on every shard's thread and returns when all have
-// ENQUEUED their part.  Marks are read from shard 0 (the scalars are replicated); an abort reaches every shard.
-struct LpFanImpl : LpFan {
-    const kao_topic *t = nullptr;
-    std::vector<int> devs, p0s;
-    LpGroup group;
-    std::vector<LpCtx *> ctx;
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv_go, cv_done;
-    std::function<int(int)> job;
-    uint64_t job_gen = 0;
-    int pending = 0;
-    std::vector<int> rcs;
-    bool quit = false;
-    void worker(int r) {
-        t_device = devs[(size_t)r];
-        (void)hipSetDevice(t_device);
-        t_lp_inner = true;
-        uint64_t seen = 0;
-        for (;;) {
-            std::function<int(int)> f;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv_go.wait(lk, [&] { return quit || job_gen != seen; });
-                if (quit) return;
-                seen = job_gen; f = job;
-            }
-            const int e = f(r);
-            if (e) group.give_up(e);
-            std::lock_guard<std::mutex> lk(mu);
-            rcs[(size_t)r] = e;
-            if (--pending == 0) cv_done.notify_all();
-        }
-    }
-    int run(std::function<int(int)> f) {     // f(rank) on every shard's thread; first failure
-        std::unique_lock<std::mutex> lk(mu);
-        job = std::move(f); ++job_gen; pending = (int)devs.size();
-        std::fill(rcs.begin(), rcs.end(), KAO_OK);
-        cv_go.notify_all();
-        cv_done.wait(lk, [&] { return pending == 0; });
-        for (int e : rcs) if (e) return e;
-        return KAO_OK;
-    }
-    int open(const kao_topic *topic, const int *devices, int n) {
-        t = topic;
-        devs.assign(devices, devices + n);
-        group.n = n; group.ops.resize((size_t)n);
-        int rc = comms_for(devs, group.comms, &group.api);
-        if (rc) return rc;
-        p0s.resize((size_t)n + 1);
-        for (int r = 0; r <= n; ++r) p0s[(size_t)r] = (int)((int64_t)t->n_partitions * r / n);
-        ctx.assign((size_t)n, nullptr); rcs.assign((size_t)n, KAO_OK);
-        for (int r = 0; r < n; ++r) th.emplace_back(&LpFanImpl::worker, this, r);
-        return run([&](int r) { LpShard sh{p0s[(size_t)r], p0s[(size_t)r + 1], r, &group}; return lp_open(t, &ctx[(size_t)r], &sh); });
-    }
-    int begin(double tol, int maxit, double pert, uint32_t salt) override { return run([&](int r) { return lp_begin(ctx[(size_t)r], tol, maxit, pert, salt); }); }
-    int enqueue_mark(int k, int slot) override { return run([&](int r) { return lp_enqueue_mark(ctx[(size_t)r], k, slot); }); }
-    struct Inner { bool saved; Inner() : saved(t_lp_inner) { t_lp_inner = true; } ~Inner() { t_lp_inner = saved; } };
-    int poll_mark(int slot, int *status, int *iterations, double deadline) override {
-        Inner in;
-        int st = 0, it = 0;
-        const int rc = lp_poll_mark(ctx[0], slot, &st, &it, deadline);
-        if (!rc && st == 4) for (size_t r = 1; r < ctx.size(); ++r) lp_abort(ctx[r]);     // the deadline passed: shard 0 raised its flag, the others follow
-        if (status) *status = st;
-        if (iterations) *iterations = it;
-        if (cur_device() >= 0) (void)hipSetDevice(cur_device());
-        return rc;
-    }
-    int finish(int32_t *multipliers, double stats[8], double *trace) override {
-        return run([&](int r) { return lp_finish(ctx[(size_t)r], r == 0 ? multipliers : nullptr, r == 0 ? stats : nullptr, r == 0 ? trace : nullptr); });
-    }
-    int primal(uint8_t *q, int32_t *zq) override {     // the shards' quantised rows side by side
-        const int P = t->n_partitions, K = 2 * t->rf_cur + 2 * t->n_racks;
-        std::vector<std::vector<uint8_t>> qs(ctx.size());
-        std::vector<std::vector<int32_t>> zs(ctx.size(), std::vector<int32_t>(2 * (size_t)t->n_brokers));
-        const int rc = run([&](int r) { qs[(size_t)r].resize((size_t)K * (size_t)(p0s[(size_t)r + 1] - p0s[(size_t)r])); return lp_primal(ctx[(size_t)r], qs[(size_t)r].data(), zs[(size_t)r].data()); });
-        if (rc) return rc;
-        for (size_t r = 0; r < ctx.size(); ++r) {
-            const int pa = p0s[r], pn = p0s[r + 1] - pa;
-            for (int k = 0; k < K; ++k) std::memcpy(q + (size_t)k * P + pa, qs[r].data() + (size_t)k * pn, (size_t)pn);
-        }
-        std::memcpy(zq, zs[0].data(), zs[0].size() * 4);
-        return KAO_OK;
-    }
-    void abort() override { Inner in; for (LpCtx *c : ctx) if (c) lp_abort(c); if (cur_device() >= 0) (void)hipSetDevice(cur_device()); }
-    void shutdown() {
-        if (!th.empty()) {
-            (void)run([&](int r) { if (ctx[(size_t)r]) { lp_abort(ctx[(size_t)r]); lp_close(ctx[(size_t)r]); ctx[(size_t)r] = nullptr; } return KAO_OK; });
-            { std::lock_guard<std::mutex> lk(mu); quit = true; }
-            cv_go.notify_all();
-            for (std::thread &x : th) x.join();
-            th.clear();
-        }
-        if (cur_device() >= 0) (void)hipSetDevice(cur_device());
-    }
-    void close() override { shutdown(); delete this; }
-    ~LpFanImpl() override { shutdown(); }
-};
-}  // namespace
-
-int kao::lp_open_fan(const kao_topic *t, const int *devices, int n_dev, LpCtx **out) {
-    LpFanImpl *f = new LpFanImpl();
-    const int rc = f->open(t, devices, n_dev);
-    if (rc) { delete f; return rc; }
-    lp_set_fan(f->ctx[0], f);
-    *out = f->ctx[0];
-    return KAO_OK;
-}
-
-extern "C" {
-
-// Test hook (include/kao.h): the LP of ONE topic solved by n_dev shards (contiguous partition ranges; devices may repeat with
-// KAO_RCCL_LOOPBACK=1: logical shards), then the same certificate evaluation and rounding as kao_lp_bound / kao_lp_round.
-int kao_lp_sharded_test(const kao_topic *t, const int32_t *devices, int32_t n_dev, double pert, uint32_t salt, double tol, int32_t max_iters,
-                        int64_t *bound, uint16_t *assignment, int64_t *objective, int32_t violations[8], double stats[8]) {
-    if (!t || !devices || n_dev < 1 || n_dev > kMaxDevices) return fail(KAO_ERR_INVALID, "kao_lp_sharded_test: bad arguments");
-    int rc = require_init();
-    if (rc) return rc;
-    if ((rc = validate(t))) return rc;
-    if (t->n_partitions < n_dev) return fail(KAO_ERR_INVALID, "kao_lp_sharded_test: fewer partitions than shards");
-    std::vector<int> devs(devices, devices + n_dev);
-    bool distinct = true;
-    for (int i = 0; i < n_dev; ++i) for (int j = 0; j < i; ++j) distinct &= devs[(size_t)i] != devs[(size_t)j];
-    if (!distinct && !loopback_wanted()) return fail(KAO_ERR_INVALID, "kao_lp_sharded_test: repeated devices are logical shards: set KAO_RCCL_LOOPBACK=1");
-    LpGroup g;
-    g.n = n_dev; g.ops.resize((size_t)n_dev);
-    if ((rc = comms_for(devs, g.comms, &g.api))) return rc;
-    const int P = t->n_partitions, K = 2 * t->rf_cur + 2 * t->n_racks;
-    std::vector<LpCtx *> ctx((size_t)n_dev, nullptr);
-    std::vector<int> rcs((size_t)n_dev, KAO_OK), p0s((size_t)n_dev + 1, 0);
-    for (int r = 0; r <= n_dev; ++r) p0s[(size_t)r] = (int)((int64_t)P * r / n_dev);
-    std::vector<std::vector<uint8_t>> qs((size_t)n_dev);
-    std::vector<int32_t> zq(2 * (size_t)t->n_brokers), mult(2 * (size_t)t->n_brokers + (size_t)t->n_racks);
-    double st8[8] = {0};
-    const double eps = pert > 0 ? pert : (pert < 0 ? 0.0 : lp_default_pert(t));       // pert < 0: the model's own LP (certificate only)
-    const double t0 = now_s();
-    auto work = [&](int r) {
-        t_device = devs[(size_t)r];
-        int e = hipSetDevice(t_device) == hipSuccess ? KAO_OK : fail(KAO_ERR_NO_DEVICE, "hipSetDevice");
-        LpShard sh{p0s[(size_t)r], p0s[(size_t)r + 1], r, &g};
-        if (!e) e = lp_open(t, &ctx[(size_t)r], &sh);
-        double stl[8] = {0};
-        if (!e) e = lp_solve(ctx[(size_t)r], tol > 0 ? tol : 1e-8, max_iters > 0 ? max_iters : 150, r == 0 ? mult.data() : nullptr, stl, nullptr, eps, salt);
-        if (!e) {
-            qs[(size_t)r].resize((size_t)K * (size_t)(p0s[(size_t)r + 1] - p0s[(size_t)r]));
-            std::vector<int32_t> zl(2 * (size_t)t->n_brokers);
-            e = lp_primal(ctx[(size_t)r], qs[(size_t)r].data(), zl.data());
-            if (!e && r == 0) { zq = zl; std::memcpy(st8, stl, sizeof stl); }
-        }
-        if (e) g.give_up(e);
-        rcs[(size_t)r] = e;
-    };
-    {
-        std::vector<std::thread> th;
-        for (int r = 1; r < n_dev; ++r) th.emplace_back(work, r);
-        const int saved = t_device;
-        work(0);
-        for (std::thread &x : th) x.join();
-        t_device = saved;
-        if (cur_device() >= 0) (void)hipSetDevice(cur_device());
-    }
-    for (LpCtx *c : ctx) if (c) lp_close(c);
-    for (int e : rcs) if (e) return e;
-    const double t_lp = now_s();
-    // the shards' quantised iterates side by side: row k of the whole topic = the shards' rows k, in partition order
-    std::vector<uint8_t> q((size_t)K * P);
-    for (int r = 0; r < n_dev; ++r) {
-        const int pa = p0s[(size_t)r], pn = p0s[(size_t)r + 1] - pa;
-        for (int k = 0; k < K; ++k) std::memcpy(q.data() + (size_t)k * P + pa, qs[(size_t)r].data() + (size_t)k * pn, (size_t)pn);
-    }
-    if (bound) {   // the dual value at the shards' common multipliers, in integers: one K-bound iteration from them (as kao_lp_bound)
-        kao_opts o{};
-        o.restarts = kWaves;
-        kao_session *s = nullptr;
-        if ((rc = kao_session_create(t, 1, &o, &s))) return rc;
-        if (!s->dual_ok[0]) { kao_session_destroy(s); return fail(KAO_ERR_UNSUPPORTED, "topic outside K-bound's limits"); }
-        rc = kao_session_set_dual_state(s, 0, mult.data(), mult.data() + t->n_brokers, mult.data() + 2 * (size_t)t->n_brokers);
-        const int64_t target = 0;
-        int32_t fl = 0, itn = 0;
-        int64_t bd = 0;
-        if (!rc) rc = kao_session_bound_step(s, &target, 1);
-        if (!rc) rc = kao_session_bounds(s, nullptr, &fl, &itn);
-        if (!rc) rc = kao_session_dual_state(s, 0, nullptr, nullptr, nullptr, &bd);
-        if (!rc) *bound = (fl & 4) || itn == 0 ? INT64_MAX : (bd >= 0 ? bd / kDualScale : -((-bd + kDualScale - 1) / kDualScale));
-        kao_session_destroy(s);
-        if (rc) return rc;
-    }
-    int32_t rep[4] = {0, 0, 0, 0};
-    if (assignment) {
-        if ((rc = lp_round_assignment(t, q.data(), zq.data(), nullptr, assignment, rep))) return rc;
-        int64_t obj = 0;
-        int32_t viol[8] = {0};
-        if ((rc = kao_evaluate(t, assignment, &obj, viol))) return rc;
-        if (objective) *objective = obj;
-        if (violations) std::memcpy(violations, viol, sizeof viol);
-    }
-    if (stats) { stats[0] = st8[0]; stats[1] = st8[3]; stats[2] = rep[0]; stats[3] = (double)g.collectives; stats[4] = st8[2]; stats[5] = (t_lp - t0) * 1e3; stats[6] = (now_s() - t_lp) * 1e3; stats[7] = eps; }
-    return KAO_OK;
-}
-
-int kao_rccl_loopback_counts(uint64_t out[2]) {
-    if (!out) return fail(KAO_ERR_INVALID, "null out");
-    out[0] = g_loop_allreduces; out[1] = g_loop_broadcasts;
-    return KAO_OK;
-}
-
+// The array layouts of include/kao.h: here and nowhere else.
 int kao_last_solve_lp(double out[8]) {
     if (!out) return fail(KAO_ERR_INVALID, "null out");
-    for (int i = 0; i < 8; ++i) out[i] = g_lp[i];
+    const SolveLp &l = g_last.lp;
+    const double v[8] = {l.solves, l.iterations, l.rounded, l.adopted, l.fractional_partitions, 0, 0, 0};
+    std::copy(v, v + 8, out);
     return KAO_OK;
 }
 int kao_last_solve_timing(double out[16]) {
     if (!out) return fail(KAO_ERR_INVALID, "null out");
-    for (int i = 0; i < 16; ++i) out[i] = g_timing[i];
+    const SolveTiming &t = g_last.timing;
+    const double v[16] = {t.session_ready, t.time_to_best, t.results_read_back, t.returned, t.launches, t.delta_candidates, t.bound_launches, t.elite_exchanges,
+                          t.bound_iters, t.cx_calls, t.cx_gains, t.search_iters, t.generations, t.cx_further_starts, t.lp_solves, t.lp_iters};
+    std::copy(v, v + 16, out);
     return KAO_OK;
 }
-
 int kao_last_solve_profile(double out[8]) {
     if (!out) return fail(KAO_ERR_INVALID, "null out");
-    for (int i = 0; i < 8; ++i) out[i] = g_profile[i];
+    const SolveProfile &p = g_last.profile;
+    const double v[8] = {p.ms_search, p.ms_eval, p.search_launches, p.restarts, p.search_bytes_algo, p.delta_candidates, p.lds_bytes_search, p.blocks_search};
+    std::copy(v, v + 8, out);
     return KAO_OK;
 }
-
 }  // extern "C"

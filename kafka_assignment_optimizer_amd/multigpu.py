@@ -162,7 +162,7 @@ def tri_unpack(tri: np.ndarray, mc: int, mcp: int, out: np.ndarray = None) -> np
 
 def allreduce_schur(S_local: np.ndarray, mc: int, device=None) -> np.ndarray:
     """One process per GPU: the shards' lower triangles summed (f64) over the process group, packed; every rank gets the same matrix.
-    (Inside one process the library does this itself: kao_lp_sharded_test, LpGroup in kao_solve.cpp.)"""
+    (Inside one process the library does this itself: kao_lp_sharded_test, LpGroup in kao_lp_fan.cpp.)"""
     import torch
     import torch.distributed as dist
     t = torch.from_numpy(tri_pack(S_local, mc))
