@@ -3,7 +3,7 @@
 
 The package is a thin host layer over the C ABI of ``libkao.so`` (include/kao.h): reassignment
 JSON in/out (README.md:52-63, README.md:67-78), instance preparation, and ctypes bindings.  All
-evaluation and search runs in the hand-written HIP kernels (csrc/kao_kernels.hip); there is no CPU
+evaluation and search runs in the hand-written HIP kernels (csrc/kao_search.hip, csrc/kao_eval.hip); there is no CPU
 fallback -- importing works anywhere, computing needs the GPU and the built library.
 """
 from .model import DEFAULT_WEIGHTS, NONE, Topic, assignment_to_json, topics_from_json  # noqa: F401

@@ -1,8 +1,10 @@
-// kao_device.h -- wavefront primitives shared by the gfx950 translation units (kao_kernels.hip, kao_bound.hip).
-// wave64 only; every lane of the wavefront must be active at the call.
+// kao_device.h -- wavefront primitives shared by the gfx950 translation units (kao_search.hip, kao_eval.hip, kao_canon.hip, kao_bound.hip)
+// and the host-side launch helper of kernels that carve dynamic LDS.  wave64 only; every lane of the wavefront must be active at the call.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace kao {
 
@@ -94,5 +96,19 @@ __device__ __forceinline__ long long wave_sum64(long long v) {
 // largest dynamic-LDS size a kernel has been enabled for is tracked per device (function attributes are per device)
 constexpr int kAttrDevices = 64;
 static inline int attr_slot() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < kAttrDevices) ? d : 0; }
+// Launch kKernel with `lds` bytes of dynamic LDS, raising the kernel's limit first when the request exceeds the largest one it has been
+// enabled for on the current device (`mark`: one per kernel instantiation, the kernel being a template argument).
+template <auto kKernel, typename... Args>
+static inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+    static int mark[kAttrDevices] = {0};
+    int &m = mark[attr_slot()];
+    if ((int)lds > m) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kKernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); m = (int)lds; }
+    hipLaunchKernelGGL(kKernel, grid, block, lds, st, args...);
+}
+// two run-time flags as template arguments: f(std::bool_constant<a>{}, std::bool_constant<b>{})
+template <class F> static inline void with_flags(bool a, bool b, F f) {
+    if (a) { if (b) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+    else { if (b) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
+}
 
 }  // namespace kao

@@ -65,7 +65,7 @@ struct SolveProfile {   // K-search as the last profiled kao_solve ran it
 struct SolveCounters { SolveTiming timing; SolveLp lp; SolveProfile profile; };
 extern thread_local SolveCounters g_last;
 // The KAO_* environment hooks (tests, measurements, diagnostics): an unset or empty variable gives `dflt`.
-// Every host-side read goes through these, except launch_init's own clamp of KAO_INIT_WAVES (kao_kernels.hip).
+// Every read of the environment in csrc/ goes through these; the kernel files read none.
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e && *e ? e : nullptr; }
 inline int64_t env_int(const char *name, int64_t dflt) { const char *e = env_str(name); return e ? (int64_t)std::atoll(e) : dflt; }
 inline double env_real(const char *name, double dflt) { const char *e = env_str(name); return e ? std::atof(e) : dflt; }

@@ -1,5 +1,5 @@
 // kao_internal.h -- structures shared by the host side (kao_model.cpp, kao_session.cpp, kao_solve.cpp; see kao_host.h) and the gfx950 kernels
-// (kao_kernels.hip).  Not part of the C ABI.
+// (kao_search.hip, kao_eval.hip, kao_canon.hip, kao_bound.hip, ...).  Not part of the C ABI.
 #pragma once
 #include <stdint.h>
 
@@ -159,7 +159,7 @@ size_t eval_lds_bytes(int maxP, int maxB, bool cur_in_lds, int ne = 4);
 // k_search when search_rf3_eligible (LDS-resident, unpriced, four words per partition, no team); else, and for rft = 0, the generic one
 bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, int team);
 void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team = 0, int rft = 0);
-bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, void *stream);   // K-init (topics in global memory)
+bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, int waves, void *stream);   // K-init (topics in global memory); waves = 0: automatic
 void launch_eval(const EvalPools &pools, int n_blocks, int ne, void *stream);
 // copy every topic's winning snapshot (restart id in its packed key) and violation row into contiguous
 // read-back buffers: one D2H instead of two per topic

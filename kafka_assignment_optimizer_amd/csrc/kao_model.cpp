@@ -393,7 +393,7 @@ int64_t upper_bound_w(const kao_topic *t) {
     return ub;
 }
 
-// Neighbours delta-evaluated by ONE restart over iterations [it0, it0+iters) (kao_kernels.hip, KAO-LS):
+// Neighbours delta-evaluated by ONE restart over iterations [it0, it0+iters) (kao_search.hip, KAO-LS):
 // move pattern R R X R L R X R; REPLACE scans all B brokers of one slot in even blocks of 8 iterations and
 // samples 64 lanes x 4 brokers in odd blocks; EXCHANGE scans all P*RF partner slots (a window of 512 partitions
 // when P > 512); LEADER-SWAP 64 x (RF-1).

@@ -1,312 +1,16 @@
-// kao_kernels.hip -- gfx950 (MI355X / CDNA4) kernels of the Kafka partition-assignment solver.
-//
-//   k_search : parallel-restart local search "KAO-LS" (DESIGN.md section 4).  One wavefront owns one
-//              restart.  Per iteration its 64 lanes either score random slots (tournament) and then scan
-//              every target broker / partner slot for the winning slot, or sample their own proposals;
-//              every neighbour is delta-evaluated for feasibility (C3,C4,C6,C7; C1,C2,C5 hold by
-//              construction) and move cost against broker / rack tables staged in LDS; a DPP min-reduce
-//              over the wavefront picks the move.  k_search<false> also keeps the assignment words in
-//              LDS; k_search<true> leaves them in HBM/L2 for topics that do not fit.
-//   k_bound  : Lagrangian dual bound "KAO-DB" (the optimality certificate): one workgroup per topic prices the
-//              coupling rows, rebuilds the candidate pools (wavefront arg-max per rack), one lane per partition solves
-//              the priced subproblem exactly, deflected level-controlled Polyak steps in integer fixed point.
-//   k_eval   : full evaluation (objective README.md:145-146 and rows C1..C7 README.md:148-180) of
-//              complete compact candidates streamed from HBM, one wavefront per candidate, ending in
-//              the wavefront -> workgroup -> atomicMin reduce of the packed (violation, cost, id) key.
-//
-// Integer-only (no floating point on the device path); wave64 throughout; no MFMA (nothing here is a
-// dense contraction).  The scalar CPU restatement used by the tests is oracle/kao_port.c.
-#include <hip/hip_runtime.h>
-
-#include <type_traits>
-
-#include "kao_device.h"
-#include "kao_internal.h"
+// kao_search.hip -- the K-search family (gfx950): parallel-restart local search "KAO-LS"  and its launchers.
+//   k_search      : one wavefront owns one restart.  Per iteration its 64 lanes either score random slots (tournament) and then scan
+//                   every target broker / partner slot for the winning slot, or sample their own proposals; every neighbour is
+//                   delta-evaluated for feasibility (C3,C4,C6,C7; C1,C2,C5 hold by construction) and move cost against broker / rack
+//                   tables staged in LDS; a DPP min-reduce over the wavefront picks the move.  k_search<false> also keeps the
+//                   assignment words in LDS; k_search<true> leaves them in HBM/L2 for topics that do not fit.
+//   k_search_curg : working assignment in LDS, current assignment from global memory.
+//   k_team        : the wavefronts of a workgroup as a team on ONE restart (topics in global memory).
+//   k_init        : the hole filling of an initialising launch, one workgroup per restart (topics in global memory).
+// All but k_init are instantiations of search_body.  Integer-only, wave64, no MFMA.  The scalar CPU restatement is oracle/kao_port.c.
+#include "kao_search_dev.h"
 
 namespace kao {
-
-// ------------------------------------------------------------------------------------------------
-// small device helpers
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-__device__ __forceinline__ uint32_t xs32(uint32_t &s) {
-    s ^= s << 13; s ^= s >> 17; s ^= s << 5;
-    return s;
-}
-__device__ __forceinline__ uint32_t mulhi(uint32_t a, uint32_t b) { return __umulhi(a, b); }
-__device__ __forceinline__ int band(int c, int lo, int hi) { return max(c - hi, 0) + max(lo - c, 0); }
-// band(c+1)-band(c) and band(c-1)-band(c)
-__device__ __forceinline__ int dinc(int c, int lo, int hi) { return (int)(c >= hi) - (int)(c < lo); }
-__device__ __forceinline__ int ddec(int c, int lo, int hi) { return (int)(c <= lo) - (int)(c > hi); }
-
-// A partition's replica slots as the kernels hold them: NW = 4 words (RF <= 4, one ds_read_b128) or 8 words (RF 5..8, two).
-template <int NW> struct alignas(16) Part { uint32_t w[NW]; };
-// slot k of a partition, as independent selects (keeps the compiler from building a switch)
-__device__ __forceinline__ uint32_t sel4(const Part<4> &a, int k) {
-    const uint32_t lo = (k & 2) ? a.w[2] : a.w[0];
-    const uint32_t hi = (k & 2) ? a.w[3] : a.w[1];
-    return (k & 1) ? hi : lo;
-}
-__device__ __forceinline__ uint32_t sel4(const Part<8> &a, int k) {
-    const uint32_t q0 = (k & 4) ? a.w[4] : a.w[0], q1 = (k & 4) ? a.w[5] : a.w[1], q2 = (k & 4) ? a.w[6] : a.w[2], q3 = (k & 4) ? a.w[7] : a.w[3];
-    const uint32_t lo = (k & 2) ? q2 : q0, hi = (k & 2) ? q3 : q1;
-    return (k & 1) ? hi : lo;
-}
-template <int NW> __device__ __forceinline__ void set_slot(Part<NW> &a, int k, uint32_t v) {
-#pragma unroll
-    for (int i = 0; i < NW; ++i) a.w[i] = (i == k) ? v : a.w[i];
-}
-// per-lane LCG modulo 2^24: one v_mad_u32_u24 (only the low 24 bits of the state are ever read)
-__device__ __forceinline__ uint32_t lcg24(uint32_t &s) {
-    // s = (s & 0xFFFFFF) * 0x6D2B79 + 0x3C6EF3; forced to the full-rate 24-bit multiply-add (hipcc otherwise
-    // picks the quarter-rate v_mul_lo_u32 for some call sites)
-    asm("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(s) : "s"(0x6D2B79u), "v"(0x3C6EF3u));
-    return s;
-}
-// uniform-ish draw on [0, n) from the high bits of a 24x24-bit product: one v_mul_hi_u32_u24.  n8 = n << 8.
-__device__ __forceinline__ uint32_t rnd24(uint32_t &s, uint32_t n8) {
-    const uint32_t v = lcg24(s);
-    return (uint32_t)(((unsigned long long)(v & 0xFFFFFFu) * (unsigned long long)(n8 & 0xFFFFFFu)) >> 32);
-}
-// same draw for ranges that may exceed 65535 (partition indices): floor(v24 * n / 2^24) = mulhi(v24 << 8, n)
-__device__ __forceinline__ uint32_t rnd24_wide(uint32_t &s, uint32_t n) {
-    const uint32_t v = lcg24(s);
-    return __umulhi((v & 0xFFFFFFu) << 8, n);
-}
-__device__ __forceinline__ uint32_t make_key(int lam, int S, int dV, int dObj, int lane) {
-    int delta = __mul24(lam, dV) - __mul24(S, dObj);
-    delta = min(max(delta, -kDBias), kDBias - 2);
-    return ((uint32_t)(delta + kDBias) << 8) | (uint32_t)lane;
-}
-// the same keys with a price term dP (Lagrangian prices of the broker rows, already in key units) added to the cost
-__device__ __forceinline__ uint32_t make_key_p(int lam, int S, int dV, int dObj, int dP, int lane) {
-    int delta = __mul24(lam, dV) - __mul24(S, dObj) + dP;
-    delta = min(max(delta, -kDBias), kDBias - 2);
-    return ((uint32_t)(delta + kDBias) << 8) | (uint32_t)lane;
-}
-__device__ __forceinline__ uint32_t make_key_tie_p(int lam, int S, int dV, int dObj, int dP, uint32_t tie) {
-    int delta = __mul24(lam, dV) - __mul24(S, dObj) + dP;
-    delta = min(max(delta, -kDBias), kDBias - 2);
-    return ((uint32_t)(delta + kDBias) << 8) | (tie & 0xFFu);
-}
-// packed search prices of one broker: low half = replica price a[b], high half = leader price l[b], key units
-__device__ __forceinline__ int price_rep(uint32_t pr) { return (int)(short)(pr & 0xFFFFu); }
-__device__ __forceinline__ int price_lead(uint32_t pr) { return (int)pr >> 16; }
-// Price of one more (p_in) / one fewer (p_out) unit on a priced row whose count is c: the multiplier applies only where the
-// count leaves or re-enters its band [lo, hi], i.e. exactly where the violation changes; inside a slack band a unit costs
-// nothing (a plain linear term would push the counts of rows with a positive multiplier down to the lower band end).
-__device__ __forceinline__ int p_in(int c, int lo, int hi, int price) { return ((c >= hi) | (c < lo)) ? price : 0; }
-__device__ __forceinline__ int p_out(int c, int lo, int hi, int price) { return ((c > hi) | (c <= lo)) ? -price : 0; }
-// packed broker weights (objective terms per replica / per leader on a broker, kao_topic.broker_w / broker_wl): low | high half
-__device__ __forceinline__ int bw_of(uint32_t bw, bool lead) { return (int)(bw & 0xFFFFu) + (lead ? (int)(bw >> 16) : 0); }
-// fixed point (kDualScale) -> key units (obj_scale per objective unit), rounded half up, clamped to 16 bits
-__device__ __forceinline__ int price_units(int v, int S) { return min(max((S * v + kDualScale / 2) >> kDualLog2, -32767), 32767); }
-
-// NS > 0 (the RF-3 instantiation of k_search): only words 0..NS-1 are compared.  The words beyond hold kNoneW, which equals no
-// broker word and whose rack field 0xFFFF equals no rack, so leaving them out changes no result.
-template <int NS = 0, int NW> __device__ __forceinline__ bool in4(const Part<NW> &a, uint32_t w) {
-    bool r = false;
-#pragma unroll
-    for (int i = 0; i < (NS ? NS : NW); ++i) r |= a.w[i] == w;
-    return r;
-}
-// replicas of the partition that sit in rack r (empty slots carry rack 0xFFFF and never match)
-template <int NS = 0, int NW> __device__ __forceinline__ int cnt4(const Part<NW> &a, uint32_t r) {
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < (NS ? NS : NW); ++i) n += (int)((a.w[i] >> 16) == r);
-    return n;
-}
-// slot k < NS of a partition: three slots take two selects (the words pass through an empty asm first: selects between words of
-// the struct were turned into a dynamically indexed copy of it in scratch)
-template <int NS, int NW> __device__ __forceinline__ uint32_t sel_slot(const Part<NW> &a, int k) {
-    if constexpr (NS == 3 && NW == 4) {
-        uint32_t w0 = a.w[0], w1 = a.w[1], w2 = a.w[2];
-        asm("" : "+v"(w0), "+v"(w1), "+v"(w2));
-        return (k & 2) ? w2 : ((k & 1) ? w1 : w0);
-    } else return sel4(a, k);
-}
-
-__device__ __forceinline__ uint32_t make_key_tie(int lam, int S, int dV, int dObj, uint32_t tie) {
-    int delta = __mul24(lam, dV) - __mul24(S, dObj);
-    delta = min(max(delta, -kDBias), kDBias - 2);
-    return ((uint32_t)(delta + kDBias) << 8) | (tie & 0xFFu);
-}
-
-struct TopicRegs {  // wave-uniform copy of the fields the inner loop needs
-    int P, RF, R, m, Bx;
-    uint32_t magic;
-    int rep_lo, rep_hi, lead_lo, lead_hi, rack_lo, rack_hi, prack_lo, prack_hi;
-    int w00, w01, w10, w11;
-};
-
-// objective weight of broker word w on a partition whose current replicas are c, in new role nr
-// (NS as in in4: words 0..NS-1 only)
-template <int NS = 0, int NW> __device__ __forceinline__ int role_w2(const Part<NW> &c, uint32_t w, int wl, int wf) {
-    bool fol = false;
-#pragma unroll
-    for (int i = 1; i < (NS ? NS : NW); ++i) fol |= c.w[i] == w;
-    return (c.w[0] == w) ? wl : (fol ? wf : 0);
-}
-template <int NS = 0, int NW> __device__ __forceinline__ int role_w(const TopicRegs &T, const Part<NW> &c, uint32_t w, int nr) {
-    return role_w2<NS>(c, w, nr ? T.w01 : T.w00, nr ? T.w11 : T.w10);
-}
-// internal index -> LDS word (x | rack << 16); 0xFFFF -> empty
-__device__ __forceinline__ uint32_t to_word(const TopicRegs &T, uint32_t x) {
-    return x == 0xFFFFu ? kNoneW : (x | (mulhi(x, T.magic) << 16));
-}
-// a restart's state in HBM between launches (LDS path): NW x u16 internal indices per partition
-template <int NW> __device__ __forceinline__ Part<NW> load_packed(const TopicRegs &T, const unsigned char *base, int p) {
-    Part<NW> a;
-    if (NW == 4) {
-        const uint2 s = reinterpret_cast<const uint2 *>(base)[p];
-        a.w[0] = to_word(T, s.x & 0xFFFFu); a.w[1] = to_word(T, s.x >> 16); a.w[2] = to_word(T, s.y & 0xFFFFu); a.w[3] = to_word(T, s.y >> 16);
-    } else {
-        const uint4 s = reinterpret_cast<const uint4 *>(base)[p];
-        const uint32_t v[4] = {s.x, s.y, s.z, s.w};
-#pragma unroll
-        for (int i = 0; i < NW / 2; ++i) { a.w[2 * i] = to_word(T, v[i & 3] & 0xFFFFu); a.w[2 * i + 1] = to_word(T, v[i & 3] >> 16); }
-    }
-    return a;
-}
-template <int NW> __device__ __forceinline__ void store_packed(unsigned char *base, int p, const Part<NW> &a) {
-    if (NW == 4) reinterpret_cast<uint2 *>(base)[p] = make_uint2((a.w[0] & 0xFFFFu) | (a.w[1] << 16), (a.w[2] & 0xFFFFu) | (a.w[3] << 16));
-    else reinterpret_cast<uint4 *>(base)[p] = make_uint4((a.w[0] & 0xFFFFu) | (a.w[1] << 16), (a.w[2] & 0xFFFFu) | (a.w[3] << 16),
-                                                         (a.w[4 % NW] & 0xFFFFu) | (a.w[5 % NW] << 16), (a.w[6 % NW] & 0xFFFFu) | (a.w[7 % NW] << 16));
-}
-// sum over all R racks of band(#replicas of the partition in the rack)
-template <int NW> __device__ __forceinline__ int part_rack_viol(const TopicRegs &T, const Part<NW> &a) {
-    int s = 0, touched = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-        const uint32_t rk = a.w[k] >> 16;
-        bool first = a.w[k] != kNoneW;
-#pragma unroll
-        for (int j = 0; j < k; ++j) first &= (a.w[j] >> 16) != rk;   // this rack has not been counted yet
-        if (first) { s += band(cnt4(a, rk), T.prack_lo, T.prack_hi); touched++; }
-    }
-    return s + (T.R - touched) * T.prack_lo;  // band(0, lo, hi) == lo
-}
-
-// ------------------------------------------------------------------------------------------------
-// K-search
-// ------------------------------------------------------------------------------------------------
-constexpr int kTeamRec = 12;   // ints per proposal record of a team (search_body, kTeam)
-template <int NW> struct WaveLds {
-    Part<NW> *A;  // [P] this restart's assignment, NW words per partition
-    uint32_t *C;  // [Bx] replicas | leaders << 16 per broker
-    uint16_t *W;  // [Bx] band state of every broker, derived from C and kept current with it (see band_fields); bit 15 = no candidate
-    int *K;       // [krt] replicas per rack (krt = search_rack_tab(largest rack count of the launch group))
-    int *RT;      // [krt] scratch: rack-dependent part of a REPLACE delta for the slot being scanned
-};
-
-// Band state of one broker, precomputed from its counter word c = replicas | leaders << 16 so that delta evaluation costs
-// one v_bfe_i32 per row instead of two compares, a select and a subtract.  Replica row (C3) in bits 5:0, leader row (C4) in
-// bits 11:6, each: signed 2-bit dinc = band(c + 1) - band(c), signed 2-bit ddec = band(c - 1) - band(c) (README.md:158-166),
-// and the two flags that say where a search price applies (p_in / p_out).  Bit 15 marks an index that is no candidate: padding
-// slots of the rack-major index space always, and during a REPLACE scan the brokers already in the partition (row C5,
-// README.md:168-171).
-constexpr int kWIncR = 0, kWDecR = 2, kWPinR = 4, kWPoutR = 5, kWIncL = 6, kWDecL = 8, kWPinL = 10, kWPoutL = 11;
-__device__ __forceinline__ int wfld(uint32_t w, int off) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, 2u); }
-__device__ __forceinline__ int wfldw(uint32_t w, int off, uint32_t width) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, width); }   // width 0 -> 0
-__device__ __forceinline__ int wflag(uint32_t w, int off) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, 1u); }                      // all ones / 0
-__device__ __forceinline__ int wflagw(uint32_t w, int off, uint32_t width) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, width); }
-// The six state bits of one band row as a function of where the count c stands: a = clamp(c - lo, -1, 1), b = clamp(c - hi, -1, 1)
-//   dinc = (c >= hi) - (c < lo) = (b >= 0) - (a < 0)        ddec = (c <= lo) - (c > hi) = (a <= 0) - (b > 0)
-//   pin  = (c >= hi) | (c < lo)   (one more unit leaves / re-enters the band: where a price applies, p_in)
-//   pout = (c > hi) | (c <= lo)   (one fewer unit, p_out)
-// entry = dinc & 3 | (ddec & 3) << 2 | pin << 4 | pout << 5, nine entries of 6 bits indexed by 3 * (a + 1) + (b + 1) in one 64-bit constant.
-constexpr unsigned long long band_entry_of(int a, int b) {
-    const int di = (b >= 0 ? 1 : 0) - (a < 0 ? 1 : 0), dd = (a <= 0 ? 1 : 0) - (b > 0 ? 1 : 0);
-    const int pin = (b >= 0 || a < 0) ? 1 : 0, pout = (b > 0 || a <= 0) ? 1 : 0;
-    return (unsigned long long)((di & 3) | ((dd & 3) << 2) | (pin << 4) | (pout << 5));
-}
-constexpr unsigned long long band_table() {
-    unsigned long long t = 0;
-    for (int a = -1; a <= 1; ++a) for (int b = -1; b <= 1; ++b) t |= band_entry_of(a, b) << (6 * (3 * (a + 1) + (b + 1)));
-    return t;
-}
-constexpr unsigned long long kBandTab = band_table();
-__device__ __forceinline__ uint32_t band_entry(int c, int lo, int hi) {
-    const int a = min(max(c - lo, -1), 1), b = min(max(c - hi, -1), 1);
-    return (uint32_t)(kBandTab >> (uint32_t)((__mul24(a, 3) + b + 4) * 6)) & 63u;
-}
-__device__ __forceinline__ uint32_t band_fields(const TopicRegs &T, uint32_t c) {
-    return band_entry((int)(c & 0xFFFFu), T.rep_lo, T.rep_hi) | (band_entry((int)(c >> 16), T.lead_lo, T.lead_hi) << 6);
-}
-constexpr uint32_t kWNoCand = 0x8000u;
-// Bit 14: no candidate for the SECOND slot of a fused two-slot REPLACE scan (search_body), which marks the brokers of its two partitions
-// at once, each slot with its own bit.  Padding indices carry both bits.
-constexpr uint32_t kWNoCand2 = 0x4000u;
-// W[x] for every index of the topic (XR: rack of x, `inv` = padding)
-// (`lane`, `stride`: a wavefront strides by 64; the wavefronts of a team stride together by the workgroup size)
-template <int NW> __device__ __forceinline__ void rebuild_band_state(const TopicRegs &T, const WaveLds<NW> &L, const uint8_t *XR, uint32_t inv, int lane, int stride = 64) {
-    for (int x = lane; x < ((T.Bx + 63) & ~63); x += stride) L.W[x] = (uint16_t)(XR[x] == inv ? (kWNoCand | kWNoCand2) : band_fields(T, L.C[x]));
-}
-
-// rebuild C and K from A (lanes stride partitions; LDS atomics)
-// (a team calls it between two workgroup barriers and zeroes, then counts, with a barrier in between: `stride` > 64)
-template <int NW> __device__ __forceinline__ void recount(const TopicRegs &T, const WaveLds<NW> &L, int lane, int stride, int krt) {
-    for (int x = lane; x < ((T.Bx + 63) & ~63); x += stride) L.C[x] = 0;
-    for (int r = lane; r < krt; r += stride) L.K[r] = 0;
-    if (stride > 64) __syncthreads();
-    for (int p = lane; p < T.P; p += stride) {
-        const Part<NW> a = L.A[p];
-#pragma unroll
-        for (int k = 0; k < NW; ++k)
-            if (a.w[k] != kNoneW) { atomicAdd(&L.C[a.w[k] & 0xFFFFu], k == 0 ? 0x10001u : 1u); atomicAdd(&L.K[a.w[k] >> 16], 1); }
-    }
-}
-
-// total violation magnitude and objective of the state in LDS (C, K must be current)
-// kTeam: the wavefronts of the workgroup split the passes and meet through `TS` (two ints per wavefront); every wavefront
-// returns the totals.  Integer sums: the split changes no result.
-template <int NW, bool kTeam = false> __device__ __forceinline__ void full_cost(const TopicRegs &T, const WaveLds<NW> &L, const Part<NW> *CUR, const int *RSZ,
-                                                            int lane, int stride, int &V, int &obj, const uint32_t *BW = nullptr,
-                                                            int *TS = nullptr, int wave = 0, int n_waves = 1) {
-    int v = 0, o = 0;
-    for (int p = lane; p < T.P; p += stride) {
-        const Part<NW> a = L.A[p];
-        const Part<NW> c = CUR[p];
-#pragma unroll
-        for (int k = 0; k < NW; ++k)
-            if (a.w[k] != kNoneW) o += role_w(T, c, a.w[k], k == 0 ? 0 : 1);
-        v += part_rack_viol(T, a);
-    }
-    for (int x = lane; x < T.Bx; x += stride) {
-        const int r = (int)mulhi((uint32_t)x, T.magic);
-        if (x - r * T.m < RSZ[r]) {
-            const uint32_t c = L.C[x];
-            v += band((int)(c & 0xFFFFu), T.rep_lo, T.rep_hi) + band((int)(c >> 16), T.lead_lo, T.lead_hi);
-            if (BW) { const uint32_t bw = BW[x]; o += (int)(c & 0xFFFFu) * (int)(bw & 0xFFFFu) + (int)(c >> 16) * (int)(bw >> 16); }
-        }
-    }
-    for (int r = lane; r < T.R; r += stride) v += band(L.K[r], T.rack_lo, T.rack_hi);
-    V = wave_sum(v);
-    obj = wave_sum(o);
-    if (kTeam) {
-        __syncthreads();   // (TS may still be read from the previous call)
-        if ((lane & 63) == 0) { TS[2 * wave] = V; TS[2 * wave + 1] = obj; }
-        __syncthreads();
-        int tv = 0, to = 0;
-        if ((lane & 63) < n_waves) { tv = TS[2 * (lane & 63)]; to = TS[2 * (lane & 63) + 1]; }
-        V = wave_sum(tv);
-        obj = wave_sum(to);
-    }
-}
-
-template <int NW> __device__ __forceinline__ void snapshot(const TopicRegs &T, const WaveLds<NW> &L, const uint16_t *ext, uint16_t *best, int lane, int stride = 64) {
-    for (int p = lane; p < T.P; p += stride) {
-        const Part<NW> a = L.A[p];
-        uint16_t *o = best + p * T.RF;
-#pragma unroll
-        for (int k = 0; k < NW; ++k)
-            if (k < T.RF) o[k] = ext[a.w[k] & 0xFFFFu];
-    }
-}
 
 // kGlobalA = false: the restart's assignment words and the topic's current-assignment words are staged in LDS
 //                   (topics that fit: the fast path).
@@ -348,11 +52,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     const int2 bm = pl.block_map[blockIdx.x];
     const TopicDev *TD = pl.topics + bm.x;
 
-    TopicRegs T;
-    T.P = TD->P; T.RF = RFT ? RFT : TD->RF; T.R = TD->R; T.m = TD->m; T.Bx = TD->Bx; T.magic = TD->magic;
-    T.rep_lo = TD->rep_lo; T.rep_hi = TD->rep_hi; T.lead_lo = TD->lead_lo; T.lead_hi = TD->lead_hi;
-    T.rack_lo = TD->rack_lo; T.rack_hi = TD->rack_hi; T.prack_lo = TD->prack_lo; T.prack_hi = TD->prack_hi;
-    T.w00 = TD->w00; T.w01 = TD->w01; T.w10 = TD->w10; T.w11 = TD->w11;
+    TopicRegs T = topic_regs<RFT>(TD);
     // the broker band ends are operands of per-lane compares only: held in VGPRs.  The SGPR file is full (106 + 142 spilled
     // in the plain instantiation) and every spilled scalar costs a v_readlane -- a VALU slot, the unit this kernel is bound
     // by -- where it is used; VGPRs are plentiful (68 of the 72 that keep 7 waves per SIMD).
@@ -1315,10 +1015,13 @@ __global__ __launch_bounds__(NW == 8 ? 256 : 512) void k_team(SearchPools pl, Se
 // lane -- the earliest round.  Same holes, same order, same winners -- the replays (oracle/kao_port.c::ls_init) hold bit for bit; k_search / k_team
 // then run with prm.init = 2 (state seeded and filled, everything else as in an initialising launch).
 constexpr int kInitWaves = 16;
-size_t init_lds_bytes(int maxBx, int maxR, bool priced, bool bw) {
-    const size_t bx64 = (size_t)((maxBx + 63) & ~63), krt = (size_t)search_rack_tab(maxR);
+// the carve at the top of k_init ("LDS:"), summed (pinned below)
+constexpr size_t init_lds_total(size_t maxBx, int maxR, bool priced, bool bw) {
+    const size_t bx64 = (maxBx + 63) & ~(size_t)63, krt = (size_t)search_rack_tab(maxR);
     return krt * 4 + bx64 + (priced ? (bw ? 2 : 1) * bx64 * 4 + krt * 4 : 0) + bx64 * 4 + krt * 4 + (size_t)kInitWaves * krt * 4 + 3 * 8;
 }
+size_t init_lds_bytes(int maxBx, int maxR, bool priced, bool bw) { return init_lds_total((size_t)maxBx, maxR, priced, bw); }
+static_assert(init_lds_total(500, 255, false, false) == 21016 && init_lds_total(500, 255, true, true) == 26136, "init_lds_total no longer sums the LDS carve of k_init");   // 255 racks
 template <bool kPriced, int NW>
 __global__ __launch_bounds__(64 * kInitWaves) void k_init(SearchPools pl, SearchParams prm, int per_block) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1331,11 +1034,7 @@ __global__ __launch_bounds__(64 * kInitWaves) void k_init(SearchPools pl, Search
     const int rho = bm.y + (int)(blockIdx.x % (unsigned)per_block);
     if (rho >= TD->n_restarts) return;   // (the whole workgroup)
 
-    TopicRegs T;
-    T.P = TD->P; T.RF = TD->RF; T.R = TD->R; T.m = TD->m; T.Bx = TD->Bx; T.magic = TD->magic;
-    T.rep_lo = TD->rep_lo; T.rep_hi = TD->rep_hi; T.lead_lo = TD->lead_lo; T.lead_hi = TD->lead_hi;
-    T.rack_lo = TD->rack_lo; T.rack_hi = TD->rack_hi; T.prack_lo = TD->prack_lo; T.prack_hi = TD->prack_hi;
-    T.w00 = TD->w00; T.w01 = TD->w01; T.w10 = TD->w10; T.w11 = TD->w11;
+    const TopicRegs T = topic_regs(TD);
 
     // LDS: [RSZ int[krt]] [XR u8[bx64]] ([PR u32[bx64]] [PG int[krt]] ([BW u32[bx64]])) [C u32[bx64]] [K int[krt]] [KW int[W][krt]] [BEST u64[3]]
     const int bx64 = (prm.maxBx + 63) & ~63, krt = search_rack_tab(prm.maxR);
@@ -1483,527 +1182,63 @@ __global__ __launch_bounds__(64 * kInitWaves) void k_init(SearchPools pl, Search
 }
 
 // ------------------------------------------------------------------------------------------------
-// K-eval
-// ------------------------------------------------------------------------------------------------
-// NE = replica slots handled per partition: 4 (RF and current RF <= 4) or 8.
-// kCoop = false: one wavefront per candidate (4 candidates in flight per workgroup) -- batches that fill the device.
-// kCoop = true : the WHOLE workgroup evaluates one candidate, its four wavefronts striding the partitions over one shared set
-//                of LDS counters -- few large candidates (a 30,000-partition topic has 256 restarts; KAO-CX scores <= 513
-//                realisations): one wavefront per candidate left 3 of 4 SIMDs idle and took 469 dependent trips per candidate.
-//                All sums are integers, so the split changes no result.
-// RFT > 0 (round 6): every topic of the launch has replication factor RFT -- the slot loops run RFT times without the `k >= RF` guards and the
-//                C7 compare square is RFT x RFT instead of NE x NE (RF 3 in four slots: 9 of 16); RFT = 0: RF is read per topic.
-template <int NE, bool kCoop, int RFT = 0>
-__global__ __launch_bounds__(256) void k_eval(EvalPools pl) {
-    constexpr int RFE = RFT ? RFT : NE;      // slots the loops visit
-    constexpr bool kLds = RFT > 0;           // the RF-uniform instantiation is launched only with the current assignment staged in LDS (launch_eval)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-    unsigned long long *wave_key = reinterpret_cast<unsigned long long *>(smem_all);  // [kWaves], 32 B
-    unsigned char *smem = smem_all + 32;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int4 bm = pl.block_map[blockIdx.x];
-    const TopicDev *TD = pl.topics + bm.x;
-    const int B = TD->B, R = TD->R, P = TD->P, RF = RFT ? RFT : TD->RF, rf_cur = TD->rf_cur;
-    const int rep_lo = TD->rep_lo, rep_hi = TD->rep_hi, lead_lo = TD->lead_lo, lead_hi = TD->lead_hi;
-    const int rack_lo = TD->rack_lo, rack_hi = TD->rack_hi, prack_lo = TD->prack_lo, prack_hi = TD->prack_hi;
-    const int w00 = TD->w00, w01 = TD->w01, w10 = TD->w10, w11 = TD->w11;
-    const bool cur_lds = kLds || pl.cur_in_lds != 0;
-    // C7 of a partition whose three replicas sit on one / two / three racks (RFT == 3)
-    const int c7_one = band(3, prack_lo, prack_hi) + (R - 1) * prack_lo;
-    const int c7_two = band(2, prack_lo, prack_hi) + band(1, prack_lo, prack_hi) + (R - 2) * prack_lo;
-    const int c7_three = 3 * band(1, prack_lo, prack_hi) + (R - 3) * prack_lo;
-
-    // ---- LDS carve: [wave_key 32 B] [RACK u8[maxB~]] [CURD u16[maxP][NE]] then per wave [C u32[maxB~]] [K int[256]]
-    const int r_bytes = (pl.maxB + 15) & ~15;
-    const int d_bytes = cur_lds ? pl.maxP * NE * 2 : 0;  // huge topics read the current assignment from global memory
-    const int c_bytes = (pl.maxB * 4 + 15) & ~15;
-    uint8_t *RACK = smem;
-    uint16_t *CURD = reinterpret_cast<uint16_t *>(smem + r_bytes);
-    unsigned char *wb = smem + r_bytes + ((d_bytes + 15) & ~15) + (kCoop ? 0 : wave) * (c_bytes + kRackTab * 4);
-    int *red = reinterpret_cast<int *>(smem + r_bytes + ((d_bytes + 15) & ~15) + kWaves * (c_bytes + kRackTab * 4));   // [kWaves][8] (kCoop)
-    const int tid = kCoop ? (int)threadIdx.x : lane, tstride = kCoop ? 256 : 64;
-    uint32_t *C = reinterpret_cast<uint32_t *>(wb);
-    int *K = reinterpret_cast<int *>(wb + c_bytes);
-
-    // ---- stage the broker->rack table and the current assignment (padded to NE slots with 0xFFFF) ----
-    for (int b = threadIdx.x; b < B; b += 256) RACK[b] = pl.rackof_pool[TD->rackof_off + b];
-    const uint16_t *curd = pl.curd_pool + TD->curd_off;
-    const uint32_t *bwd = TD->has_bw ? pl.bwd_pool + TD->bwd_off : nullptr;   // broker weights, dense index (global memory / L2)
-    if (cur_lds)
-        for (int i = threadIdx.x; i < P * NE; i += 256) {
-            const int p = i / NE, k = i - p * NE;
-            CURD[i] = k < rf_cur ? curd[(size_t)p * rf_cur + k] : (uint16_t)0xFFFFu;
-        }
-    __syncthreads();
-
-    unsigned long long my_key = ~0ull;
-    const int nB4 = (B + 3) >> 2;  // counters zeroed 16 bytes per lane per store (C is 16-byte aligned and padded)
-    // Rack counters: the 64 lanes of a wavefront hit only R addresses, so one LDS atomic per replica would serialise (10 racks:
-    // ~5 lanes per address).  They are privatised per 16-lane row -- 4 copies inside the same 256-entry table when R <= 64 --
-    // added without return value, and the band rows C6 are evaluated from the totals in one pass at the end.
-    const int KR = (R + 15) & ~15;
-    const int kcopy = 4 * KR <= kRackTab ? (lane >> 4) * KR : 0;
-    const bool k4 = 4 * KR <= kRackTab;
-    const bool big = !kLds && P * RF > 65535;   // only then can a 16-bit per-broker counter overflow (the RF-3 instantiation runs with the current assignment in LDS: at most 20,480 partitions x 3)
-    for (int ci = bm.y + (kCoop ? 0 : wave); ci < bm.y + bm.z; ci += (kCoop ? 1 : kWaves)) {
-        const uint16_t *cand = pl.cand + TD->best_off + (uint64_t)ci * P * RF;
-        for (int b4 = tid; b4 < nB4; b4 += tstride) reinterpret_cast<uint4 *>(C)[b4] = make_uint4(0, 0, 0, 0);
-        for (int r = tid; r < (k4 ? 4 * KR : KR); r += tstride) K[r] = 0;      // (only the entries the atomics below and the C6 pass touch)
-        if (kCoop) __syncthreads();
-        // Broker band violations are accumulated from the value each LDS atomic RETURNS: adding a replica to a
-        // broker whose count was c changes band(c) by (c >= hi) - (c < lo), and sum_b band(0) = B*lo, so
-        // no pass over all brokers is needed.  Packed partial sums: low half = #(old >= hi), high = #(old < lo).
-        int obj = 0;
-        uint32_t s12 = 0;  // v1 | v2 << 16
-        // C3 / C4 are COUNTS of lanes (old count at or above the upper end, below the lower end): each is a compare into a scalar pair and a
-        // population count, accumulated in scalar registers -- no per-lane sum, no wavefront reduction (round 6, last: they were two of the six
-        // words of wave_sum6 and five vector instructions per slot)
-        int n3hi = 0, n3lo = 0, n4hi = 0, n4lo = 0;
-        uint32_t s57 = 0;  // v5 | v7 << 16
-        bool ovf = false;
-        for (int p = tid; p < P; p += tstride) {
-            const uint16_t *ap = cand + (size_t)p * RF;  // a wavefront reads 64*RF consecutive u16: coalesced
-            uint32_t bk[NE], rk[NE], ck[NE];
-            uint32_t cw[NE / 2];   // the partition's current replicas, two u16 per word: one ds_read_b64 / b128 when staged in LDS
-            if (cur_lds) {
-                if (NE == 4) { const uint2 v = reinterpret_cast<const uint2 *>(CURD)[p]; cw[0] = v.x; cw[1] = v.y; }
-                else { const uint4 v = reinterpret_cast<const uint4 *>(CURD)[p]; cw[0] = v.x; cw[1] = v.y; cw[2 % (NE / 2)] = v.z; cw[3 % (NE / 2)] = v.w; }
-            }
-#pragma unroll
-            for (int k = 0; k < NE; ++k) {
-                bk[k] = k < RF ? (uint32_t)ap[k < RF ? k : 0] : 0xFFFFu;
-                rk[k] = 0xFFu;
-                ck[k] = cur_lds ? ((k & 1) ? cw[k >> 1] >> 16 : cw[k >> 1] & 0xFFFFu)
-                                      : (k < rf_cur ? (uint32_t)curd[(size_t)p * rf_cur + (k < rf_cur ? k : 0)] : 0xFFFFu);
-            }
-            int missing = 0;
-            // One slot of the trip (KAO_EVAL_SLOT).  VALID is the lane's own "this slot holds a broker", or the literal true when every lane of
-            // the trip has one (the usual case, tested once per trip with a ballot): the body then has no per-lane branch and the counts sit in
-            // wave-uniform control flow.  Otherwise the counts are taken where the lanes have met again -- the scalar accumulators live in every
-            // lane's copy of the loop state, and a lane that sat out a slot would miss its counts (lane 0, whose copy is read in the end, is in
-            // every trip: partitions ascend with the lane).
-#define KAO_EVAL_SLOT(VALID) do { \
-                uint32_t oc = 0; \
-                if (!(VALID)) ++missing; \
-                else { \
-                    rk[k] = RACK[b]; \
-                    oc = atomicAdd(&C[b], k == 0 ? 0x10001u : 1u); \
-                    __hip_atomic_fetch_add(&K[kcopy + rk[k]], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-                    if (big) ovf |= (oc & 0xFFFFu) == 0xFFFFu; \
-                    bool fol = false, dup = false; \
-                    _Pragma("unroll") for (int j = 1; j < NE; ++j) fol |= ck[j] == b; \
-                    _Pragma("unroll") for (int j = 0; j < k; ++j) dup |= bk[j] == b; \
-                    obj += (ck[0] == b) ? (k == 0 ? w00 : w01) : (fol ? (k == 0 ? w10 : w11) : 0); \
-                    if (bwd) { const uint32_t bw = bwd[b]; obj += (int)(bw & 0xFFFFu) + (k == 0 ? (int)(bw >> 16) : 0); } \
-                    s57 += (uint32_t)dup;  /* C5: f+l <= 1 (an earlier slot holds the same broker) */ \
-                } \
-                const int cr = (int)(oc & 0xFFFFu); \
-                n3hi += wave_count((VALID) & (cr >= rep_hi)); n3lo += wave_count((VALID) & (cr < rep_lo));         /* C3 */ \
-                if (k == 0) { \
-                    const int cl = (int)(oc >> 16); \
-                    n4hi += wave_count((VALID) & (cl >= lead_hi)); n4lo += wave_count((VALID) & (cl < lead_lo));   /* C4 */ \
-                } \
-            } while (0)
-            bool any_empty = false;
-#pragma unroll
-            for (int k = 0; k < RFE; ++k) {
-                if (!RFT && k >= RF) break;
-                any_empty |= bk[k] >= (uint32_t)B;
-            }
-            const bool trip_full = __ballot(any_empty) == 0ull;      // wave-uniform: no lane of this trip has an empty / out-of-range slot
-            if (trip_full) {
-#pragma unroll
-                for (int k = 0; k < RFE; ++k) {
-                    if (!RFT && k >= RF) break;
-                    const uint32_t b = bk[k];
-                    KAO_EVAL_SLOT(true);
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < RFE; ++k) {
-                    if (!RFT && k >= RF) break;
-                    const uint32_t b = bk[k];
-                    const bool valid = b < (uint32_t)B;
-                    KAO_EVAL_SLOT(valid);
-                }
-            }
-#undef KAO_EVAL_SLOT
-            s12 += (uint32_t)missing + ((uint32_t)(bk[0] >= (uint32_t)B) << 16);  // C1: sum_b (f+l) = RF ; C2: exactly one leader
-            // C7: replicas per partition per rack, over all R racks (each rack counted at its first slot)
-            if (RFT == 3 && trip_full) {
-                // three filled slots (no lane of this trip has an empty one: wave-uniform) fall on one, two or three racks -- the row's value
-                // in each case is a constant of the topic (c7_one / c7_two / c7_three: the sums the general loop below would form)
-                const bool e01 = rk[0] == rk[1], e02 = rk[0] == rk[2], e12 = rk[1] == rk[2];
-                s57 += (uint32_t)((e01 & e12) ? c7_one : ((e01 | e02 | e12) ? c7_two : c7_three)) << 16;
-            } else {
-                int touched = 0, s7 = 0;
-#pragma unroll
-                for (int k = 0; k < RFE; ++k) {
-                    bool first = rk[k] != 0xFFu;
-                    int cnt = 0;
-#pragma unroll
-                    for (int j = 0; j < RFE; ++j) { cnt += (int)(rk[j] == rk[k]); if (j < k) first &= rk[j] != rk[k]; }
-                    if (first) { s7 += band(cnt, prack_lo, prack_hi); touched++; }
-                }
-                s57 += (uint32_t)(s7 + (R - touched) * prack_lo) << 16;
-            }
-        }
-        // C6 from the rack totals (the wavefront's own LDS operations complete in order: no barrier needed; the cooperating
-        // wavefronts of kCoop meet at one)
-        if (kCoop) __syncthreads();
-        int s6 = 0;
-        for (int r = tid; r < R; r += tstride) {
-            const int tot = k4 ? K[r] + K[KR + r] + K[2 * KR + r] + K[3 * KR + r] : K[r];
-            s6 += band(tot, rack_lo, rack_hi);
-        }
-        if (big && __ballot(ovf) != 0ull && pl.overflow && lane == 0) atomicOr(pl.overflow, 1);
-        int v1, v2, v3, v4, v5, v6, v7;   // (v3, v4 without their constants B * lo until the partial sums have met)
-        v3 = __builtin_amdgcn_readfirstlane(n3hi - n3lo); v4 = __builtin_amdgcn_readfirstlane(n4hi - n4lo);      // lane 0's copy (see above): wave-uniform from here on
-        if (P * RF <= 32767) {  // packed halves cannot carry: every count is at most P*RF -- the four words are summed in one go (wave_sum4)
-            int t[4] = {obj, (int)s12, (int)s57, s6};
-            wave_sum4(t);
-            const uint32_t t12 = (uint32_t)t[1], t57 = (uint32_t)t[2];
-            obj = t[0]; v6 = t[3];
-            v1 = (int)(t12 & 0xFFFFu); v2 = (int)(t12 >> 16);
-            v5 = (int)(t57 & 0xFFFFu); v7 = (int)(t57 >> 16);
-        } else {  // huge topic: per-lane halves still fit 16 bits, the wavefront totals do not -> sum them unpacked
-            obj = wave_sum(obj);
-            v1 = wave_sum((int)(s12 & 0xFFFFu)); v2 = wave_sum((int)(s12 >> 16));
-            v5 = wave_sum((int)(s57 & 0xFFFFu)); v7 = wave_sum((int)(s57 >> 16));
-            v6 = wave_sum(s6);
-        }
-        if (kCoop) {   // the four wavefronts' partial sums meet in LDS; every wavefront reads the totals
-            if (lane == 0) { int *q = red + wave * 8; q[0] = obj; q[1] = v1; q[2] = v2; q[3] = v3; q[4] = v4; q[5] = v5; q[6] = v6; q[7] = v7; }
-            __syncthreads();
-            obj = v1 = v2 = v3 = v4 = v5 = v6 = v7 = 0;
-            for (int w = 0; w < kWaves; ++w) {
-                const int *q = red + w * 8;
-                obj += q[0]; v1 += q[1]; v2 += q[2]; v3 += q[3]; v4 += q[4]; v5 += q[5]; v6 += q[6]; v7 += q[7];
-            }
-            __syncthreads();   // the counters and `red` are reused by the next candidate
-        }
-        v3 += B * rep_lo; v4 += B * lead_lo;
-        const int v0 = v1 + v2 + v3 + v4 + v5 + v6 + v7;
-        const int out = bm.w + (ci - bm.y);
-        if (lane == 0 && (!kCoop || wave == 0)) {
-            if (pl.objective) pl.objective[out] = obj;
-            if (pl.violations) {
-                int4 *vo = reinterpret_cast<int4 *>(pl.violations + (size_t)out * 8);
-                vo[0] = make_int4(v0, v1, v2, v3);
-                vo[1] = make_int4(v4, v5, v6, v7);
-            }
-        }
-        const unsigned long long key = ((unsigned long long)min(v0, 0xFFFFF) << 44) |
-                                       ((unsigned long long)(kObjCap - (uint32_t)min(obj, (int)kObjCap)) << 20) |
-                                       (unsigned long long)(ci & 0xFFFFF);
-        my_key = key < my_key ? key : my_key;
-    }
-    if (pl.best_key) {  // workgroup reduce of the wave-uniform keys, one atomicMin per workgroup per topic
-        if (lane == 0) wave_key[wave] = my_key;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long k = wave_key[0];
-            for (int w = 1; w < kWaves; ++w) k = wave_key[w] < k ? wave_key[w] : k;
-            if (k != ~0ull) atomicMin(pl.best_key + bm.x, k);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K-gather: winners -> contiguous read-back buffers
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_gather(const TopicDev *topics, const unsigned long long *keys, const uint16_t *best_pool,
-                                               const int32_t *viol, uint16_t *win_assign, int32_t *win_viol) {
-    const TopicDev *TD = topics + blockIdx.x;
-    const unsigned long long key = keys[blockIdx.x];
-    if (key == ~0ull) return;
-    const int rho = (int)(key & 0xFFFFFull);
-    if (rho == (int)kExternalRestart) {  // the topic's best came from another GPU (kao_solve_multi): win_assign already holds it
-        if (threadIdx.x < 8) win_viol[blockIdx.x * 8 + threadIdx.x] = 0;  // only feasible assignments are exchanged
-        return;
-    }
-    const int n = TD->P * TD->RF;
-    const uint16_t *src = best_pool + TD->best_off + (uint64_t)rho * n;
-    uint16_t *dst = win_assign + TD->win_off;
-    for (int i = threadIdx.x; i < n; i += 64) dst[i] = src[i];
-    if (threadIdx.x < 8) win_viol[blockIdx.x * 8 + threadIdx.x] = viol[(size_t)(TD->restart_base + rho) * 8 + threadIdx.x];
-}
-
-// After the min-allreduce of the packed best keys across GPUs (kao_solve_multi, replicated topics): where another GPU's key
-// beats the local one, adopt it with the reserved restart id kExternalRestart (its assignment arrives by broadcast).
-__global__ __launch_bounds__(64) void k_adopt_global(unsigned long long *keys, const unsigned long long *glob, int n) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long g = glob[i];
-    if (g < keys[i] && (g >> 44) == 0) keys[i] = g | (unsigned long long)kExternalRestart;
-}
-
-// ------------------------------------------------------------------------------------------------
-// K-canon: canonical tie-break among equal-objective feasible assignments (kao_canonicalize)
-// ------------------------------------------------------------------------------------------------
-// Scanning partitions and slots in order, every NEWLY placed replica (its broker is not a current replica of the
-// partition) moves to the lowest DENSE broker index that keeps the assignment feasible; repeated to a fixpoint.
-// Such a move never changes the objective (neither broker carries weight on that partition) and, the state being
-// feasible, it stays feasible iff the move's violation delta is 0 -- so this is the REPLACE scan of k_search with
-// "delta == 0" as the filter and the dense index as the key.  One wavefront; the assignment and current-assignment
-// words stay in global memory (any topic size); broker / rack tables in LDS.  status = {input feasible, #moves}.
-template <int NW>
-__global__ __launch_bounds__(64) void k_canon(const TopicDev *TD, const Part<NW> *cur_words, const uint16_t *ext, const int32_t *rsz,
-                                              Part<NW> *A, int maxBx, int32_t *status) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63;
-    TopicRegs T;
-    T.P = TD->P; T.RF = TD->RF; T.R = TD->R; T.m = TD->m; T.Bx = TD->Bx; T.magic = TD->magic;
-    T.rep_lo = TD->rep_lo; T.rep_hi = TD->rep_hi; T.lead_lo = TD->lead_lo; T.lead_hi = TD->lead_hi;
-    T.rack_lo = TD->rack_lo; T.rack_hi = TD->rack_hi; T.prack_lo = TD->prack_lo; T.prack_hi = TD->prack_hi;
-    T.w00 = TD->w00; T.w01 = TD->w01; T.w10 = TD->w10; T.w11 = TD->w11;
-    const int bx64 = (maxBx + 63) & ~63;
-    int *RSZ = reinterpret_cast<int *>(smem);
-    uint8_t *XR = smem + kRackTab * 4;
-    WaveLds<NW> L;
-    L.A = A;
-    L.C = reinterpret_cast<uint32_t *>(smem + kRackTab * 4 + bx64);
-    L.K = reinterpret_cast<int *>(smem + kRackTab * 4 + bx64 + bx64 * 4);
-    L.RT = L.K;  // unused here
-    L.W = reinterpret_cast<uint16_t *>(L.C);   // unused here
-    for (int r = lane; r < kRackTab; r += 64) RSZ[r] = r < T.R ? rsz[r] : 0;
-    __syncthreads();
-    for (int x = lane; x < ((T.Bx + 63) & ~63); x += 64) {
-        const uint32_t r = mulhi((uint32_t)x, T.magic);
-        XR[x] = (x < T.Bx && (int)((uint32_t)x - r * (uint32_t)T.m) < RSZ[r < (uint32_t)kRackTab ? r : 0]) ? (uint8_t)r : (uint8_t)0xFF;
-    }
-    __syncthreads();
-    recount(T, L, lane, 64, kRackTab);
-    int V, obj;
-    full_cost(T, L, cur_words, RSZ, lane, 64, V, obj);
-    if (V != 0) {  // only feasible assignments are polished
-        if (lane == 0) { status[0] = 0; status[1] = 0; }
-        return;
-    }
-    int moves = 0;
-    bool changed = true;
-    while (changed) {
-        changed = false;
-        for (int pbase = 0; pbase < T.P; pbase += 64) {
-            bool has_new = false;
-            if (pbase + lane < T.P) {
-                const Part<NW> al = L.A[pbase + lane];
-                const Part<NW> cl = cur_words[pbase + lane];
-#pragma unroll
-                for (int k = 0; k < NW; ++k) has_new |= (k < T.RF) & !in4(cl, al.w[k]);
-            }
-            unsigned long long todo = __ballot(has_new);
-            while (todo) {
-                const int p = pbase + __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                Part<NW> a = L.A[p];
-                const Part<NW> c = cur_words[p];
-#pragma unroll
-                for (int k = 0; k < NW; ++k) {
-                    if (k >= T.RF) break;
-                    const uint32_t uw = a.w[k];
-                    if (in4(c, uw)) continue;  // a retained current replica stays where it is (wave-uniform)
-                    const uint32_t old_dense = ext[uw & 0xFFFFu];
-                    const uint32_t ro = uw >> 16;
-                    const bool lead = k == 0;
-                    const uint32_t co = L.C[uw & 0xFFFFu];
-                    int dV_old = ddec((int)(co & 0xFFFFu), T.rep_lo, T.rep_hi);
-                    if (lead) dV_old += ddec((int)(co >> 16), T.lead_lo, T.lead_hi);
-                    const int dV_rack_old = ddec(L.K[ro], T.rack_lo, T.rack_hi) + ddec(cnt4(a, ro), T.prack_lo, T.prack_hi);
-                    uint32_t key = kKeyNull;
-                    for (int base = 0; base < T.Bx; base += 64) {
-                        const uint32_t x = (uint32_t)(base + lane);
-                        const uint32_t r = XR[x];
-                        const uint32_t xw = x | (r << 16);
-                        bool ok = (r != 0xFFu) && !in4(a, xw) && !in4(c, xw);
-                        const uint32_t dense = ok ? (uint32_t)ext[x] : 0xFFFFu;
-                        ok = ok & (dense < old_dense);
-                        const uint32_t cn = L.C[x];
-                        int dV = dV_old + dinc((int)(cn & 0xFFFFu), T.rep_lo, T.rep_hi);
-                        if (lead) dV += dinc((int)(cn >> 16), T.lead_lo, T.lead_hi);
-                        if (r != ro) dV += dV_rack_old + dinc(L.K[r & 255u], T.rack_lo, T.rack_hi) + dinc(cnt4(a, r), T.prack_lo, T.prack_hi);
-                        const uint32_t kx = (ok & (dV == 0)) ? ((dense << 16) | x) : kKeyNull;
-                        key = min(key, kx);
-                    }
-                    const uint32_t kmin = wave_umin(key);
-                    if (kmin == kKeyNull) continue;
-                    const uint32_t xn = kmin & 0xFFFFu;
-                    const uint32_t rn = XR[xn];
-                    const uint32_t xw_new = xn | (rn << 16);
-                    a.w[k] = xw_new;
-                    if (lane == 0) {
-                        const uint32_t d = lead ? 0x10001u : 1u;
-                        reinterpret_cast<uint32_t *>(&L.A[p])[k] = xw_new;
-                        L.C[uw & 0xFFFFu] -= d;
-                        L.C[xn] += d;
-                        L.K[ro] -= 1;
-                        L.K[rn] += 1;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                    changed = true;
-                    ++moves;
-                }
-            }
-        }
-    }
-    if (lane == 0) { status[0] = 1; status[1] = moves; }
-}
-
-// ------------------------------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------------------------------
-size_t search_lds_bytes(int maxP, int maxBx, int waves, bool global_a, bool priced, int nw, bool bw, int maxR, int team, bool cur_global) {
-    const size_t a = global_a ? 0 : (size_t)maxP * 4 * (size_t)nw, bx64 = ((size_t)maxBx + 63) & ~(size_t)63, krt = (size_t)search_rack_tab(maxR);
+// the "LDS carve" of search_body, summed (pinned below)
+constexpr size_t search_lds_total(size_t maxP, size_t maxBx, size_t waves, bool global_a, bool priced, size_t nw, bool bw, int maxR, size_t team, bool cur_global) {
+    const size_t a = global_a ? 0 : maxP * 4 * nw, bx64 = (maxBx + 63) & ~(size_t)63, krt = (size_t)search_rack_tab(maxR);
     const size_t shared = (cur_global ? 0 : a) + krt * 4 + bx64 + (priced ? (bw ? 2 : 1) * bx64 * 4 + krt * 4 : 0);
     if (team > 0)   // one set of counters / band states / rack totals, one RT per wavefront, the proposal records, the partial sums
-        return shared + bx64 * 6 + krt * 4 + (size_t)team * krt * 4 + 2 * 16 * kTeamRec * 4 + 16 * 2 * 4;
-    return shared + (size_t)waves * (a + bx64 * 6 + krt * 8);
+        return shared + bx64 * 6 + krt * 4 + team * krt * 4 + 2 * 16 * kTeamRec * 4 + 16 * 2 * 4;
+    return shared + waves * (a + bx64 * 6 + krt * 8);
 }
-size_t eval_lds_bytes(int maxP, int maxB, bool cur_in_lds, int ne) {
-    const size_t r = ((size_t)maxB + 15) & ~(size_t)15, d = cur_in_lds ? ((size_t)maxP * 2 * (size_t)ne + 15) & ~(size_t)15 : 0;
-    const size_t c = ((size_t)maxB * 4 + 15) & ~(size_t)15;
-    return 32 + r + d + kWaves * (c + kRackTab * 4) + kWaves * 8 * 4;   // (+ the partial sums of the cooperative mode)
+size_t search_lds_bytes(int maxP, int maxBx, int waves, bool global_a, bool priced, int nw, bool bw, int maxR, int team, bool cur_global) {
+    return search_lds_total((size_t)maxP, (size_t)maxBx, (size_t)waves, global_a, priced, (size_t)nw, bw, maxR, (size_t)team, cur_global);
 }
-
-// largest dynamic-LDS size each kernel has been enabled for, per device (function attributes are per device)
-static int g_attr_eval_dev[kAttrDevices] = {0};
-
-template <bool kGlobalA, bool kPriced, int NW, bool kWide, int RFT = 0>
-static void launch_search_t(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, size_t lds, int &attr, hipStream_t st) {
-    if ((int)lds > attr) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_search<kGlobalA, kPriced, NW, kWide, RFT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_search<kGlobalA, kPriced, NW, kWide, RFT>), dim3(n_blocks), dim3(64 * waves), lds, st, pools, prm);
-}
-template <bool kGlobalA, bool kPriced, int NW>
-static void launch_search_w(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, size_t lds, int &attr, bool wide, hipStream_t st) {
-    if (wide || kGlobalA) launch_search_t<kGlobalA, kPriced, NW, true>(pools, prm, n_blocks, waves, lds, attr, st);   // (topics in global memory are always wide)
-    else launch_search_t<kGlobalA, kPriced, NW, kGlobalA>(pools, prm, n_blocks, waves, lds, attr, st);
-}
-
-template <bool kPriced, int NW>
-static void launch_team_t(const SearchPools &pools, const SearchParams &prm, int n_blocks, int team, size_t lds, int &attr, hipStream_t st) {
-    if ((int)lds > attr) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_team<kPriced, NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_team<kPriced, NW>), dim3(n_blocks), dim3(64 * team), lds, st, pools, prm);
-}
+// config 4 (50 partitions, RF 3, 500 brokers on 10 racks, 4 wavefronts); the same with 8 words per partition; priced, and with broker weights;
+// working words only (k_search_curg) at 9,800 partitions; a team of 8 on a topic in global memory
+static_assert(search_lds_total(50, 500, 4, false, false, 4, false, 10, 0, false) == 19104 && search_lds_total(50, 500, 4, false, false, 8, false, 10, 0, false) == 23104 &&
+              search_lds_total(50, 500, 4, false, true, 4, false, 10, 0, false) == 21408 && search_lds_total(50, 500, 4, false, true, 4, true, 10, 0, false) == 23456 &&
+              search_lds_total(9800, 500, 1, false, false, 4, false, 10, 0, true) == 161152 && search_lds_total(100000, 500, 1, true, false, 4, false, 10, 8, false) == 7808,
+              "search_lds_total no longer sums the LDS carve of search_body");
 
 bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, int team) { return !global_a && !cur_global && !priced && nw == 4 && team == 0; }
 
 void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team, int rft) {
-    const bool curg = prm.cur_global != 0 && !global_a;
+    const bool curg = prm.cur_global != 0 && !global_a, wide = prm.wide != 0;
     const size_t lds = search_lds_bytes(prm.maxP, prm.maxBx, waves, global_a, priced, nw, prm.bw != 0, prm.maxR, team, curg);
-    // largest dynamic-LDS size each of the instantiations has been enabled for, per device
-    static int attr[kAttrDevices][26] = {{0}};
-    const bool wide = prm.wide != 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (curg) {   // working assignment in LDS, current assignment from L2
-        int &ca = attr[attr_slot()][20 + (priced ? 2 : 0) + (nw == 8 ? 1 : 0)];
-        const void *fn = nw == 8 ? (priced ? reinterpret_cast<const void *>(k_search_curg<true, 8>) : reinterpret_cast<const void *>(k_search_curg<false, 8>))
-                                 : (priced ? reinterpret_cast<const void *>(k_search_curg<true, 4>) : reinterpret_cast<const void *>(k_search_curg<false, 4>));
-        if ((int)lds > ca) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); ca = (int)lds; }
-        if (nw == 8) { if (priced) hipLaunchKernelGGL((k_search_curg<true, 8>), dim3(n_blocks), dim3(64 * waves), lds, st, pools, prm); else hipLaunchKernelGGL((k_search_curg<false, 8>), dim3(n_blocks), dim3(64 * waves), lds, st, pools, prm); }
-        else { if (priced) hipLaunchKernelGGL((k_search_curg<true, 4>), dim3(n_blocks), dim3(64 * waves), lds, st, pools, prm); else hipLaunchKernelGGL((k_search_curg<false, 4>), dim3(n_blocks), dim3(64 * waves), lds, st, pools, prm); }
-        return;
-    }
-    if (team > 0) {   // one block per restart, `team` wavefronts each (topics in global memory only)
-        int &ta = attr[attr_slot()][16 + (priced ? 2 : 0) + (nw == 8 ? 1 : 0)];
-        if (nw == 8) { if (priced) launch_team_t<true, 8>(pools, prm, n_blocks, team, lds, ta, st); else launch_team_t<false, 8>(pools, prm, n_blocks, team, lds, ta, st); }
-        else { if (priced) launch_team_t<true, 4>(pools, prm, n_blocks, team, lds, ta, st); else launch_team_t<false, 4>(pools, prm, n_blocks, team, lds, ta, st); }
-        if ((int)lds > ta) ta = (int)lds;
-        return;
-    }
+    const dim3 grid(n_blocks), block(64 * (team > 0 && !curg ? team : waves));   // a team: one workgroup per restart, `team` wavefronts each
     if (rft == 3 && search_rf3_eligible(global_a, curg, priced, nw, team)) {   // every topic RF 3, at most 3 current replicas (kao_session.cpp)
-        int &ra = attr[attr_slot()][24 + (wide ? 1 : 0)];
-        if (wide) launch_search_t<false, false, 4, true, 3>(pools, prm, n_blocks, waves, lds, ra, st);
-        else launch_search_t<false, false, 4, false, 3>(pools, prm, n_blocks, waves, lds, ra, st);
-        if ((int)lds > ra) ra = (int)lds;
+        if (wide) launch_lds<k_search<false, false, 4, true, 3>>(grid, block, lds, st, pools, prm);
+        else launch_lds<k_search<false, false, 4, false, 3>>(grid, block, lds, st, pools, prm);
         return;
     }
-    int &a = attr[attr_slot()][(wide || global_a ? 8 : 0) + (global_a ? 4 : 0) + (priced ? 2 : 0) + (nw == 8 ? 1 : 0)];
-    if (nw == 8) {
-        if (global_a && priced) launch_search_w<true, true, 8>(pools, prm, n_blocks, waves, lds, a, wide, st);
-        else if (global_a) launch_search_w<true, false, 8>(pools, prm, n_blocks, waves, lds, a, wide, st);
-        else if (priced) launch_search_w<false, true, 8>(pools, prm, n_blocks, waves, lds, a, wide, st);
-        else launch_search_w<false, false, 8>(pools, prm, n_blocks, waves, lds, a, wide, st);
-    } else {
-        if (global_a && priced) launch_search_w<true, true, 4>(pools, prm, n_blocks, waves, lds, a, wide, st);
-        else if (global_a) launch_search_w<true, false, 4>(pools, prm, n_blocks, waves, lds, a, wide, st);
-        else if (priced) launch_search_w<false, true, 4>(pools, prm, n_blocks, waves, lds, a, wide, st);
-        else launch_search_w<false, false, 4>(pools, prm, n_blocks, waves, lds, a, wide, st);
-    }
-    if ((int)lds > a) a = (int)lds;
+    with_flags(priced, nw == 8, [&](auto p, auto k8) {
+        constexpr bool kPriced = decltype(p)::value;
+        constexpr int NW = decltype(k8)::value ? 8 : 4;
+        if (curg) launch_lds<k_search_curg<kPriced, NW>>(grid, block, lds, st, pools, prm);          // working assignment in LDS, current assignment from L2
+        else if (team > 0) launch_lds<k_team<kPriced, NW>>(grid, block, lds, st, pools, prm);        // (topics in global memory only)
+        else if (global_a) launch_lds<k_search<true, kPriced, NW, true>>(grid, block, lds, st, pools, prm);   // (topics in global memory are always wide)
+        else if (wide) launch_lds<k_search<false, kPriced, NW, true>>(grid, block, lds, st, pools, prm);
+        else launch_lds<k_search<false, kPriced, NW, false>>(grid, block, lds, st, pools, prm);
+    });
 }
 
-// K-init for one launch group of topics in global memory: `n_blocks` block-map entries of `per_block` restarts each.  False when the
-// tables do not fit (the caller leaves prm.init = 1: k_search fills the holes itself).
-bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, void *stream) {
+// K-init for one launch group of topics in global memory: `n_blocks` block-map entries of `per_block` restarts each, `waves` wavefronts per
+// restart (0 = automatic).  False when the tables do not fit (the caller leaves prm.init = 1: k_search fills the holes itself).
+bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, int waves, void *stream) {
     const size_t lds = init_lds_bytes(prm.maxBx, prm.maxR, priced, prm.bw != 0);
     if (lds > 160 * 1024) return false;
-    static int attr[kAttrDevices][4] = {{0}};
-    int &a = attr[attr_slot()][(priced ? 2 : 0) + (nw == 8 ? 1 : 0)];
-    const void *fn = nw == 8 ? (priced ? reinterpret_cast<const void *>(k_init<true, 8>) : reinterpret_cast<const void *>(k_init<false, 8>))
-                             : (priced ? reinterpret_cast<const void *>(k_init<true, 4>) : reinterpret_cast<const void *>(k_init<false, 4>));
-    if ((int)lds > a && lds > 64 * 1024) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); a = (int)lds; }
     // (config 5 as one topic, 15,000 holes x 16 rounds, per K-init: 59.2 / 21.8 / 17.3 / 18.0 ms with 1 / 4 / 8 / 16 wavefronts -- beyond two rounds
     // per wavefront the hole's fixed part, ~200 instructions of reduce / exchange / update behind one another, is what is left)
-    int waves = std::min(8, std::max(1, (prm.maxBx + 63) / 64));
-    if (const char *e = std::getenv("KAO_INIT_WAVES")) waves = std::min(kInitWaves, std::max(1, std::atoi(e)));   // measurement hook (0: see kao_session_step)
+    waves = waves > 0 ? std::min(kInitWaves, waves) : std::min(8, std::max(1, (prm.maxBx + 63) / 64));
     while (waves & (waves - 1)) waves &= waves - 1;   // a power of two (the kernel's owner-of-a-round mask)
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(n_blocks * per_block)), block((unsigned)(64 * waves));
-    if (nw == 8) { if (priced) hipLaunchKernelGGL((k_init<true, 8>), grid, block, lds, st, pools, prm, per_block); else hipLaunchKernelGGL((k_init<false, 8>), grid, block, lds, st, pools, prm, per_block); }
-    else { if (priced) hipLaunchKernelGGL((k_init<true, 4>), grid, block, lds, st, pools, prm, per_block); else hipLaunchKernelGGL((k_init<false, 4>), grid, block, lds, st, pools, prm, per_block); }
+    with_flags(priced, nw == 8, [&](auto p, auto k8) {
+        launch_lds<k_init<decltype(p)::value, decltype(k8)::value ? 8 : 4>>(grid, block, lds, static_cast<hipStream_t>(stream), pools, prm, per_block);
+    });
     return true;
-}
-
-void launch_eval(const EvalPools &pools, int n_blocks, int ne, void *stream) {
-    const size_t lds = eval_lds_bytes(pools.maxP, pools.maxB, pools.cur_in_lds != 0, ne);
-    int &g_attr_eval = g_attr_eval_dev[attr_slot()];
-    if ((int)lds > g_attr_eval) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_eval<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_eval<4, false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_eval<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_eval<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_eval<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        g_attr_eval = (int)lds;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (pools.coop) {
-        if (ne == 8) hipLaunchKernelGGL((k_eval<8, true>), dim3(n_blocks), dim3(256), lds, st, pools);
-        else hipLaunchKernelGGL((k_eval<4, true>), dim3(n_blocks), dim3(256), lds, st, pools);
-    } else {
-        if (ne == 8) hipLaunchKernelGGL((k_eval<8, false>), dim3(n_blocks), dim3(256), lds, st, pools);
-        else if (pools.rf_uniform == 3 && pools.cur_in_lds) hipLaunchKernelGGL((k_eval<4, false, 3>), dim3(n_blocks), dim3(256), lds, st, pools);
-        else hipLaunchKernelGGL((k_eval<4, false>), dim3(n_blocks), dim3(256), lds, st, pools);
-    }
-}
-
-void launch_gather(const TopicDev *topics, int n_topics, const unsigned long long *keys, const uint16_t *best_pool,
-                   const int32_t *viol, uint16_t *win_assign, int32_t *win_viol, void *stream) {
-    hipLaunchKernelGGL(k_gather, dim3(n_topics), dim3(64), 0, static_cast<hipStream_t>(stream), topics, keys, best_pool, viol,
-                       win_assign, win_viol);
-}
-
-void launch_adopt_global(unsigned long long *keys, const unsigned long long *glob, int n, void *stream) {
-    hipLaunchKernelGGL(k_adopt_global, dim3((n + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream), keys, glob, n);
-}
-
-size_t canon_lds_bytes(int maxBx) {
-    const size_t bx64 = ((size_t)maxBx + 63) & ~(size_t)63;
-    return kRackTab * 4 + bx64 + bx64 * 4 + kRackTab * 4;
-}
-
-void launch_canon(const TopicDev *topic, const uint32_t *cur_words, const uint16_t *ext, const int32_t *rsz, uint32_t *A, int maxBx,
-                  int nw, int32_t *status, void *stream) {
-    const size_t lds = canon_lds_bytes(maxBx);
-    if (nw == 8) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_canon<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_canon<8>, dim3(1), dim3(64), lds, static_cast<hipStream_t>(stream), topic, reinterpret_cast<const Part<8> *>(cur_words), ext, rsz,
-                           reinterpret_cast<Part<8> *>(A), maxBx, status);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_canon<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_canon<4>, dim3(1), dim3(64), lds, static_cast<hipStream_t>(stream), topic, reinterpret_cast<const Part<4> *>(cur_words), ext, rsz,
-                           reinterpret_cast<Part<4> *>(A), maxBx, status);
-    }
 }
 
 }  // namespace kao

@@ -1,0 +1,295 @@
+// kao_search_dev.h -- device-only helpers shared by the K-search family (kao_search.hip: k_search, k_search_curg, k_team, k_init),
+// K-canon (kao_canon.hip) and, for band(), K-eval (kao_eval.hip): the words a partition is held in, the per-lane generators, the
+// move keys, prices and bands, the topic's register copy, the per-wavefront LDS tables and the passes over them.
+// Integer-only, wave64.  The scalar CPU restatement used by the tests is oracle/kao_port.c.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "kao_device.h"
+#include "kao_internal.h"
+
+namespace kao {
+
+// ------------------------------------------------------------------------------------------------
+// small device helpers
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ uint32_t xs32(uint32_t &s) {
+    s ^= s << 13; s ^= s >> 17; s ^= s << 5;
+    return s;
+}
+__device__ __forceinline__ uint32_t mulhi(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+__device__ __forceinline__ int band(int c, int lo, int hi) { return max(c - hi, 0) + max(lo - c, 0); }
+// band(c+1)-band(c) and band(c-1)-band(c)
+__device__ __forceinline__ int dinc(int c, int lo, int hi) { return (int)(c >= hi) - (int)(c < lo); }
+__device__ __forceinline__ int ddec(int c, int lo, int hi) { return (int)(c <= lo) - (int)(c > hi); }
+
+// A partition's replica slots as the kernels hold them: NW = 4 words (RF <= 4, one ds_read_b128) or 8 words (RF 5..8, two).
+template <int NW> struct alignas(16) Part { uint32_t w[NW]; };
+// slot k of a partition, as independent selects (keeps the compiler from building a switch)
+__device__ __forceinline__ uint32_t sel4(const Part<4> &a, int k) {
+    const uint32_t lo = (k & 2) ? a.w[2] : a.w[0];
+    const uint32_t hi = (k & 2) ? a.w[3] : a.w[1];
+    return (k & 1) ? hi : lo;
+}
+__device__ __forceinline__ uint32_t sel4(const Part<8> &a, int k) {
+    const uint32_t q0 = (k & 4) ? a.w[4] : a.w[0], q1 = (k & 4) ? a.w[5] : a.w[1], q2 = (k & 4) ? a.w[6] : a.w[2], q3 = (k & 4) ? a.w[7] : a.w[3];
+    const uint32_t lo = (k & 2) ? q2 : q0, hi = (k & 2) ? q3 : q1;
+    return (k & 1) ? hi : lo;
+}
+template <int NW> __device__ __forceinline__ void set_slot(Part<NW> &a, int k, uint32_t v) {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) a.w[i] = (i == k) ? v : a.w[i];
+}
+// per-lane LCG modulo 2^24: one v_mad_u32_u24 (only the low 24 bits of the state are ever read)
+__device__ __forceinline__ uint32_t lcg24(uint32_t &s) {
+    // s = (s & 0xFFFFFF) * 0x6D2B79 + 0x3C6EF3; forced to the full-rate 24-bit multiply-add (hipcc otherwise
+    // picks the quarter-rate v_mul_lo_u32 for some call sites)
+    asm("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(s) : "s"(0x6D2B79u), "v"(0x3C6EF3u));
+    return s;
+}
+// uniform-ish draw on [0, n) from the high bits of a 24x24-bit product: one v_mul_hi_u32_u24.  n8 = n << 8.
+__device__ __forceinline__ uint32_t rnd24(uint32_t &s, uint32_t n8) {
+    const uint32_t v = lcg24(s);
+    return (uint32_t)(((unsigned long long)(v & 0xFFFFFFu) * (unsigned long long)(n8 & 0xFFFFFFu)) >> 32);
+}
+// same draw for ranges that may exceed 65535 (partition indices): floor(v24 * n / 2^24) = mulhi(v24 << 8, n)
+__device__ __forceinline__ uint32_t rnd24_wide(uint32_t &s, uint32_t n) {
+    const uint32_t v = lcg24(s);
+    return __umulhi((v & 0xFFFFFFu) << 8, n);
+}
+// A move key: the clamped, biased cost delta above a low byte that breaks ties -- the proposing lane (as it is: < 64) or eight hash bits.
+// dP: Lagrangian prices of the broker rows (already in key units) added to the cost by the priced instantiations.
+__device__ __forceinline__ uint32_t key_of(int delta, uint32_t low) {
+    delta = min(max(delta, -kDBias), kDBias - 2);
+    return ((uint32_t)(delta + kDBias) << 8) | low;
+}
+__device__ __forceinline__ uint32_t make_key_p(int lam, int S, int dV, int dObj, int dP, int lane) { return key_of(__mul24(lam, dV) - __mul24(S, dObj) + dP, (uint32_t)lane); }
+__device__ __forceinline__ uint32_t make_key(int lam, int S, int dV, int dObj, int lane) { return key_of(__mul24(lam, dV) - __mul24(S, dObj), (uint32_t)lane); }
+__device__ __forceinline__ uint32_t make_key_tie_p(int lam, int S, int dV, int dObj, int dP, uint32_t tie) { return key_of(__mul24(lam, dV) - __mul24(S, dObj) + dP, tie & 0xFFu); }
+__device__ __forceinline__ uint32_t make_key_tie(int lam, int S, int dV, int dObj, uint32_t tie) { return key_of(__mul24(lam, dV) - __mul24(S, dObj), tie & 0xFFu); }
+// packed search prices of one broker: low half = replica price a[b], high half = leader price l[b], key units
+__device__ __forceinline__ int price_rep(uint32_t pr) { return (int)(short)(pr & 0xFFFFu); }
+__device__ __forceinline__ int price_lead(uint32_t pr) { return (int)pr >> 16; }
+// Price of one more (p_in) / one fewer (p_out) unit on a priced row whose count is c: the multiplier applies only where the
+// count leaves or re-enters its band [lo, hi], i.e. exactly where the violation changes; inside a slack band a unit costs
+// nothing (a plain linear term would push the counts of rows with a positive multiplier down to the lower band end).
+__device__ __forceinline__ int p_in(int c, int lo, int hi, int price) { return ((c >= hi) | (c < lo)) ? price : 0; }
+__device__ __forceinline__ int p_out(int c, int lo, int hi, int price) { return ((c > hi) | (c <= lo)) ? -price : 0; }
+// packed broker weights (objective terms per replica / per leader on a broker, kao_topic.broker_w / broker_wl): low | high half
+__device__ __forceinline__ int bw_of(uint32_t bw, bool lead) { return (int)(bw & 0xFFFFu) + (lead ? (int)(bw >> 16) : 0); }
+// fixed point (kDualScale) -> key units (obj_scale per objective unit), rounded half up, clamped to 16 bits
+__device__ __forceinline__ int price_units(int v, int S) { return min(max((S * v + kDualScale / 2) >> kDualLog2, -32767), 32767); }
+
+// NS > 0 (the RF-3 instantiation of k_search): only words 0..NS-1 are compared.  The words beyond hold kNoneW, which equals no
+// broker word and whose rack field 0xFFFF equals no rack, so leaving them out changes no result.
+template <int NS = 0, int NW> __device__ __forceinline__ bool in4(const Part<NW> &a, uint32_t w) {
+    bool r = false;
+#pragma unroll
+    for (int i = 0; i < (NS ? NS : NW); ++i) r |= a.w[i] == w;
+    return r;
+}
+// replicas of the partition that sit in rack r (empty slots carry rack 0xFFFF and never match)
+template <int NS = 0, int NW> __device__ __forceinline__ int cnt4(const Part<NW> &a, uint32_t r) {
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < (NS ? NS : NW); ++i) n += (int)((a.w[i] >> 16) == r);
+    return n;
+}
+// slot k < NS of a partition: three slots take two selects (the words pass through an empty asm first: selects between words of
+// the struct were turned into a dynamically indexed copy of it in scratch)
+template <int NS, int NW> __device__ __forceinline__ uint32_t sel_slot(const Part<NW> &a, int k) {
+    if constexpr (NS == 3 && NW == 4) {
+        uint32_t w0 = a.w[0], w1 = a.w[1], w2 = a.w[2];
+        asm("" : "+v"(w0), "+v"(w1), "+v"(w2));
+        return (k & 2) ? w2 : ((k & 1) ? w1 : w0);
+    } else return sel4(a, k);
+}
+
+struct TopicRegs {  // wave-uniform copy of the fields the inner loop needs
+    int P, RF, R, m, Bx;
+    uint32_t magic;
+    int rep_lo, rep_hi, lead_lo, lead_hi, rack_lo, rack_hi, prack_lo, prack_hi;
+    int w00, w01, w10, w11;
+};
+
+template <int RFT = 0> __device__ __forceinline__ TopicRegs topic_regs(const TopicDev *TD) {   // RFT > 0: the replication factor of every topic of the launch
+    TopicRegs T;
+    T.P = TD->P; T.RF = RFT ? RFT : TD->RF; T.R = TD->R; T.m = TD->m; T.Bx = TD->Bx; T.magic = TD->magic;
+    T.rep_lo = TD->rep_lo; T.rep_hi = TD->rep_hi; T.lead_lo = TD->lead_lo; T.lead_hi = TD->lead_hi;
+    T.rack_lo = TD->rack_lo; T.rack_hi = TD->rack_hi; T.prack_lo = TD->prack_lo; T.prack_hi = TD->prack_hi;
+    T.w00 = TD->w00; T.w01 = TD->w01; T.w10 = TD->w10; T.w11 = TD->w11;
+    return T;
+}
+
+// objective weight of broker word w on a partition whose current replicas are c, in new role nr
+// (NS as in in4: words 0..NS-1 only)
+template <int NS = 0, int NW> __device__ __forceinline__ int role_w2(const Part<NW> &c, uint32_t w, int wl, int wf) {
+    bool fol = false;
+#pragma unroll
+    for (int i = 1; i < (NS ? NS : NW); ++i) fol |= c.w[i] == w;
+    return (c.w[0] == w) ? wl : (fol ? wf : 0);
+}
+template <int NS = 0, int NW> __device__ __forceinline__ int role_w(const TopicRegs &T, const Part<NW> &c, uint32_t w, int nr) {
+    return role_w2<NS>(c, w, nr ? T.w01 : T.w00, nr ? T.w11 : T.w10);
+}
+// internal index -> LDS word (x | rack << 16); 0xFFFF -> empty
+__device__ __forceinline__ uint32_t to_word(const TopicRegs &T, uint32_t x) {
+    return x == 0xFFFFu ? kNoneW : (x | (mulhi(x, T.magic) << 16));
+}
+// a restart's state in HBM between launches (LDS path): NW x u16 internal indices per partition
+template <int NW> __device__ __forceinline__ Part<NW> load_packed(const TopicRegs &T, const unsigned char *base, int p) {
+    Part<NW> a;
+    if (NW == 4) {
+        const uint2 s = reinterpret_cast<const uint2 *>(base)[p];
+        a.w[0] = to_word(T, s.x & 0xFFFFu); a.w[1] = to_word(T, s.x >> 16); a.w[2] = to_word(T, s.y & 0xFFFFu); a.w[3] = to_word(T, s.y >> 16);
+    } else {
+        const uint4 s = reinterpret_cast<const uint4 *>(base)[p];
+        const uint32_t v[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+        for (int i = 0; i < NW / 2; ++i) { a.w[2 * i] = to_word(T, v[i & 3] & 0xFFFFu); a.w[2 * i + 1] = to_word(T, v[i & 3] >> 16); }
+    }
+    return a;
+}
+template <int NW> __device__ __forceinline__ void store_packed(unsigned char *base, int p, const Part<NW> &a) {
+    if (NW == 4) reinterpret_cast<uint2 *>(base)[p] = make_uint2((a.w[0] & 0xFFFFu) | (a.w[1] << 16), (a.w[2] & 0xFFFFu) | (a.w[3] << 16));
+    else reinterpret_cast<uint4 *>(base)[p] = make_uint4((a.w[0] & 0xFFFFu) | (a.w[1] << 16), (a.w[2] & 0xFFFFu) | (a.w[3] << 16),
+                                                         (a.w[4 % NW] & 0xFFFFu) | (a.w[5 % NW] << 16), (a.w[6 % NW] & 0xFFFFu) | (a.w[7 % NW] << 16));
+}
+// sum over all R racks of band(#replicas of the partition in the rack)
+template <int NW> __device__ __forceinline__ int part_rack_viol(const TopicRegs &T, const Part<NW> &a) {
+    int s = 0, touched = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const uint32_t rk = a.w[k] >> 16;
+        bool first = a.w[k] != kNoneW;
+#pragma unroll
+        for (int j = 0; j < k; ++j) first &= (a.w[j] >> 16) != rk;   // this rack has not been counted yet
+        if (first) { s += band(cnt4(a, rk), T.prack_lo, T.prack_hi); touched++; }
+    }
+    return s + (T.R - touched) * T.prack_lo;  // band(0, lo, hi) == lo
+}
+
+// ------------------------------------------------------------------------------------------------
+// K-search
+// ------------------------------------------------------------------------------------------------
+constexpr int kTeamRec = 12;   // ints per proposal record of a team (search_body, kTeam)
+template <int NW> struct WaveLds {
+    Part<NW> *A;  // [P] this restart's assignment, NW words per partition
+    uint32_t *C;  // [Bx] replicas | leaders << 16 per broker
+    uint16_t *W;  // [Bx] band state of every broker, derived from C and kept current with it (see band_fields); bit 15 = no candidate
+    int *K;       // [krt] replicas per rack (krt = search_rack_tab(largest rack count of the launch group))
+    int *RT;      // [krt] scratch: rack-dependent part of a REPLACE delta for the slot being scanned
+};
+
+// Band state of one broker, precomputed from its counter word c = replicas | leaders << 16 so that delta evaluation costs
+// one v_bfe_i32 per row instead of two compares, a select and a subtract.  Replica row (C3) in bits 5:0, leader row (C4) in
+// bits 11:6, each: signed 2-bit dinc = band(c + 1) - band(c), signed 2-bit ddec = band(c - 1) - band(c) (README.md:158-166),
+// and the two flags that say where a search price applies (p_in / p_out).  Bit 15 marks an index that is no candidate: padding
+// slots of the rack-major index space always, and during a REPLACE scan the brokers already in the partition (row C5,
+// README.md:168-171).
+constexpr int kWIncR = 0, kWDecR = 2, kWPinR = 4, kWPoutR = 5, kWIncL = 6, kWDecL = 8, kWPinL = 10, kWPoutL = 11;
+__device__ __forceinline__ int wfld(uint32_t w, int off) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, 2u); }
+__device__ __forceinline__ int wfldw(uint32_t w, int off, uint32_t width) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, width); }   // width 0 -> 0
+__device__ __forceinline__ int wflag(uint32_t w, int off) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, 1u); }                      // all ones / 0
+__device__ __forceinline__ int wflagw(uint32_t w, int off, uint32_t width) { return __builtin_amdgcn_sbfe((int)w, (unsigned)off, width); }
+// The six state bits of one band row as a function of where the count c stands: a = clamp(c - lo, -1, 1), b = clamp(c - hi, -1, 1)
+//   dinc = (c >= hi) - (c < lo) = (b >= 0) - (a < 0)        ddec = (c <= lo) - (c > hi) = (a <= 0) - (b > 0)
+//   pin  = (c >= hi) | (c < lo)   (one more unit leaves / re-enters the band: where a price applies, p_in)
+//   pout = (c > hi) | (c <= lo)   (one fewer unit, p_out)
+// entry = dinc & 3 | (ddec & 3) << 2 | pin << 4 | pout << 5, nine entries of 6 bits indexed by 3 * (a + 1) + (b + 1) in one 64-bit constant.
+constexpr unsigned long long band_entry_of(int a, int b) {
+    const int di = (b >= 0 ? 1 : 0) - (a < 0 ? 1 : 0), dd = (a <= 0 ? 1 : 0) - (b > 0 ? 1 : 0);
+    const int pin = (b >= 0 || a < 0) ? 1 : 0, pout = (b > 0 || a <= 0) ? 1 : 0;
+    return (unsigned long long)((di & 3) | ((dd & 3) << 2) | (pin << 4) | (pout << 5));
+}
+constexpr unsigned long long band_table() {
+    unsigned long long t = 0;
+    for (int a = -1; a <= 1; ++a) for (int b = -1; b <= 1; ++b) t |= band_entry_of(a, b) << (6 * (3 * (a + 1) + (b + 1)));
+    return t;
+}
+constexpr unsigned long long kBandTab = band_table();
+__device__ __forceinline__ uint32_t band_entry(int c, int lo, int hi) {
+    const int a = min(max(c - lo, -1), 1), b = min(max(c - hi, -1), 1);
+    return (uint32_t)(kBandTab >> (uint32_t)((__mul24(a, 3) + b + 4) * 6)) & 63u;
+}
+__device__ __forceinline__ uint32_t band_fields(const TopicRegs &T, uint32_t c) {
+    return band_entry((int)(c & 0xFFFFu), T.rep_lo, T.rep_hi) | (band_entry((int)(c >> 16), T.lead_lo, T.lead_hi) << 6);
+}
+constexpr uint32_t kWNoCand = 0x8000u;
+// Bit 14: no candidate for the SECOND slot of a fused two-slot REPLACE scan (search_body), which marks the brokers of its two partitions
+// at once, each slot with its own bit.  Padding indices carry both bits.
+constexpr uint32_t kWNoCand2 = 0x4000u;
+// W[x] for every index of the topic (XR: rack of x, `inv` = padding)
+// (`lane`, `stride`: a wavefront strides by 64; the wavefronts of a team stride together by the workgroup size)
+template <int NW> __device__ __forceinline__ void rebuild_band_state(const TopicRegs &T, const WaveLds<NW> &L, const uint8_t *XR, uint32_t inv, int lane, int stride = 64) {
+    for (int x = lane; x < ((T.Bx + 63) & ~63); x += stride) L.W[x] = (uint16_t)(XR[x] == inv ? (kWNoCand | kWNoCand2) : band_fields(T, L.C[x]));
+}
+
+// rebuild C and K from A (lanes stride partitions; LDS atomics)
+// (a team calls it between two workgroup barriers and zeroes, then counts, with a barrier in between: `stride` > 64)
+template <int NW> __device__ __forceinline__ void recount(const TopicRegs &T, const WaveLds<NW> &L, int lane, int stride, int krt) {
+    for (int x = lane; x < ((T.Bx + 63) & ~63); x += stride) L.C[x] = 0;
+    for (int r = lane; r < krt; r += stride) L.K[r] = 0;
+    if (stride > 64) __syncthreads();
+    for (int p = lane; p < T.P; p += stride) {
+        const Part<NW> a = L.A[p];
+#pragma unroll
+        for (int k = 0; k < NW; ++k)
+            if (a.w[k] != kNoneW) { atomicAdd(&L.C[a.w[k] & 0xFFFFu], k == 0 ? 0x10001u : 1u); atomicAdd(&L.K[a.w[k] >> 16], 1); }
+    }
+}
+
+// total violation magnitude and objective of the state in LDS (C, K must be current)
+// kTeam: the wavefronts of the workgroup split the passes and meet through `TS` (two ints per wavefront); every wavefront
+// returns the totals.  Integer sums: the split changes no result.
+template <int NW, bool kTeam = false> __device__ __forceinline__ void full_cost(const TopicRegs &T, const WaveLds<NW> &L, const Part<NW> *CUR, const int *RSZ,
+                                                            int lane, int stride, int &V, int &obj, const uint32_t *BW = nullptr,
+                                                            int *TS = nullptr, int wave = 0, int n_waves = 1) {
+    int v = 0, o = 0;
+    for (int p = lane; p < T.P; p += stride) {
+        const Part<NW> a = L.A[p];
+        const Part<NW> c = CUR[p];
+#pragma unroll
+        for (int k = 0; k < NW; ++k)
+            if (a.w[k] != kNoneW) o += role_w(T, c, a.w[k], k == 0 ? 0 : 1);
+        v += part_rack_viol(T, a);
+    }
+    for (int x = lane; x < T.Bx; x += stride) {
+        const int r = (int)mulhi((uint32_t)x, T.magic);
+        if (x - r * T.m < RSZ[r]) {
+            const uint32_t c = L.C[x];
+            v += band((int)(c & 0xFFFFu), T.rep_lo, T.rep_hi) + band((int)(c >> 16), T.lead_lo, T.lead_hi);
+            if (BW) { const uint32_t bw = BW[x]; o += (int)(c & 0xFFFFu) * (int)(bw & 0xFFFFu) + (int)(c >> 16) * (int)(bw >> 16); }
+        }
+    }
+    for (int r = lane; r < T.R; r += stride) v += band(L.K[r], T.rack_lo, T.rack_hi);
+    V = wave_sum(v);
+    obj = wave_sum(o);
+    if (kTeam) {
+        __syncthreads();   // (TS may still be read from the previous call)
+        if ((lane & 63) == 0) { TS[2 * wave] = V; TS[2 * wave + 1] = obj; }
+        __syncthreads();
+        int tv = 0, to = 0;
+        if ((lane & 63) < n_waves) { tv = TS[2 * (lane & 63)]; to = TS[2 * (lane & 63) + 1]; }
+        V = wave_sum(tv);
+        obj = wave_sum(to);
+    }
+}
+
+template <int NW> __device__ __forceinline__ void snapshot(const TopicRegs &T, const WaveLds<NW> &L, const uint16_t *ext, uint16_t *best, int lane, int stride = 64) {
+    for (int p = lane; p < T.P; p += stride) {
+        const Part<NW> a = L.A[p];
+        uint16_t *o = best + p * T.RF;
+#pragma unroll
+        for (int k = 0; k < NW; ++k)
+            if (k < T.RF) o[k] = ext[a.w[k] & 0xFFFFu];
+    }
+}
+
+}  // namespace kao

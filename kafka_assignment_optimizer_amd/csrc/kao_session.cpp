@@ -2,7 +2,7 @@
 // and stream pools), K-eval plans, the canonical tie-break, and sessions -- the resident state of a batch of topics on one
 // device with its K-search / K-eval steps, K-bound launches and search prices.
 //
-// Everything that computes runs in the gfx950 kernels (kao_kernels.hip, kao_bound.hip, kao_cycle.hip); this file only prepares
+// Everything that computes runs in the gfx950 kernels (kao_search.hip, kao_eval.hip, kao_canon.hip, kao_bound.hip, kao_cycle.hip); this file only prepares
 // instances, owns the device pools, launches, and reads results back.  There is deliberately no CPU evaluation or search
 // path here: if the HIP device is missing every compute entry point fails with KAO_ERR_NO_DEVICE.
 #include <chrono>
@@ -841,7 +841,8 @@ int kao_session_step(kao_session *s) {
         prm.maxP = g.maxP; prm.maxBx = g.maxBx; prm.maxR = g.maxR; prm.wide = g.wide ? 1 : 0; prm.cur_global = g.cur_global ? 1 : 0;
         SearchParams gp = prm;
         if (gp.init && g.global_a) {   // topics in global memory: the holes are filled by a workgroup per restart (K-init), not by one wavefront
-            if (env_int("KAO_INIT_WAVES", 1) != 0 && launch_init(sp, gp, g.smap_n, g.team > 0 ? 1 : g.waves, s->priced, g.nw, s->stream)) gp.init = 2;
+            const int init_waves = (int)env_int("KAO_INIT_WAVES", -1);   // measurement hook: wavefronts per restart (unset: automatic); 0 = the one-wavefront fill inside k_search
+            if (init_waves != 0 && launch_init(sp, gp, g.smap_n, g.team > 0 ? 1 : g.waves, s->priced, g.nw, std::max(init_waves, 0), s->stream)) gp.init = 2;
             HIP_TRY(hipGetLastError());
         }
         const int rft = g.rf3 ? 3 : 0;
