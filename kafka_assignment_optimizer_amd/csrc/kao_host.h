@@ -1,8 +1,12 @@
 // kao_host.h -- host-side internals shared by the translation units behind the C ABI (include/kao.h):
 //   kao_model.cpp    the model on the host: validation, bands, dense -> rack-major index, infeasibility proofs, the closed-form
 //                    upper bound (kao_upper_bound)
-//   kao_session.cpp  runtime (device, error text, arena / stream pools), K-eval plans, canonical tie-break, sessions
-//                    (K-search / K-eval steps, K-bound launches, prices)
+//   kao_runtime.cpp  device selection, error text, kao_init / kao_shutdown, the pools of parked arenas and streams
+//   kao_evalplan.cpp K-eval plans, kao_evaluate(_batch), the canonical tie-break (kao_canonicalize)
+//   kao_session.cpp  sessions: the plan of a batch of topics on one device (options, pools, launch groups, arena layout), its
+//                    upload, the K-search / K-eval step, the read-back
+//   kao_session_bound.cpp  K-bound on a session: launches, search prices, bounds, dual state; kao_dual_bound
+//   kao_lp_api.cpp   the one-shot KAO-LP entry points (kao_lp_bound / _round / _round_host / _trace)
 //   kao_solve.cpp    the solve loops on top of sessions: kao_solve, kao_solve_multi (several devices in lockstep), and the readers of the
 //                    last solve's counters (kao_last_solve_timing / _lp / _profile)
 //   kao_rccl.cpp     the collectives of the multi-device paths (kao_rccl.h): the lazy librccl loader, the loop-back table, communicators
@@ -16,6 +20,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -24,7 +29,7 @@
 
 namespace kao {
 
-// ---- runtime (kao_session.cpp) ----
+// ---- runtime (kao_runtime.cpp) ----
 int fail(int code, const std::string &msg);   // records the text kao_last_error returns; returns `code`
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -63,12 +68,21 @@ struct SolveProfile {   // K-search as the last profiled kao_solve ran it
     double ms_search, ms_eval, search_launches, restarts, search_bytes_algo, delta_candidates, lds_bytes_search, blocks_search;
 };
 struct SolveCounters { SolveTiming timing; SolveLp lp; SolveProfile profile; };
-extern thread_local SolveCounters g_last;
+extern thread_local SolveCounters g_last;   // (kao_solve.cpp)
 // The KAO_* environment hooks (tests, measurements, diagnostics): an unset or empty variable gives `dflt`.
 // Every read of the environment in csrc/ goes through these; the kernel files read none.
 inline const char *env_str(const char *name) { const char *e = std::getenv(name); return e && *e ? e : nullptr; }
 inline int64_t env_int(const char *name, int64_t dflt) { const char *e = env_str(name); return e ? (int64_t)std::atoll(e) : dflt; }
 inline double env_real(const char *name, double dflt) { const char *e = env_str(name); return e ? std::atof(e) : dflt; }
+// hipMalloc / hipFree cost 0.1-1 ms each, a stream ~1 ms: finished sessions park their arenas and streams here for the next one
+int arena_get(size_t bytes, void **out, size_t *cap);   // a parked arena of the current device that fits, else hipMalloc
+void arena_put(void *p, size_t bytes, int device);
+int stream_get(hipStream_t *out);
+void stream_put(hipStream_t st, int device);
+void arena_drop_all();
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+// LDS / register form of a replica: internal (rack-major) index | rack << 16, m = the largest rack
+inline uint32_t replica_word(uint16_t x, int m) { return x == KAO_NONE ? kNoneW : ((uint32_t)x | ((uint32_t)(x / m) << 16)); }
 
 // ---- the model on the host (kao_model.cpp) ----
 int validate(const kao_topic *t);
@@ -218,6 +232,14 @@ struct kao_session {
 };
 
 namespace kao {
+// K-bound's dual values are fixed point (kDualScale); a bound on the integer objective is their floor -- unless the launch flagged the
+// value unusable (flag 4) or no iteration has run
+constexpr int64_t kDualNone = 0x7F7F7F7F7F7F7F7Fll;   // best dual value "none yet" (the state is cleared with bytes of 0x7F)
+inline int64_t dual_floor(int64_t best_dual) { return best_dual >= 0 ? best_dual / kDualScale : -((-best_dual + kDualScale - 1) / kDualScale); }
+inline int64_t dual_bound_value(int32_t flags, int32_t iters, int64_t best_dual) { return (flags & 4) || iters == 0 ? INT64_MAX : dual_floor(best_dual); }
+struct SessionDeleter { void operator()(kao_session *s) const { kao_session_destroy(s); } };
+using SessionPtr = std::unique_ptr<kao_session, SessionDeleter>;   // a session on its way out of kao_session_create, or a throw-away one
+int bound_only_session(const kao_topic *t, SessionPtr &out);   // one topic, no search: K-bound alone (kao_session_bound.cpp); fails outside K-bound's limits
 // the topic's winning assignment (dense [P*RF]) as of the last finished launch
 int session_topic_best(kao_session *s, int i, uint16_t *out);
 // every restart's best feasible objective (-1 = none yet) / one restart's best snapshot, as of the last finished launch

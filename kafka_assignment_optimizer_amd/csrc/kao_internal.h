@@ -1,4 +1,4 @@
-// kao_internal.h -- structures shared by the host side (kao_model.cpp, kao_session.cpp, kao_solve.cpp; see kao_host.h) and the gfx950 kernels
+// kao_internal.h -- structures shared by the host side (the .cpp files; see kao_host.h) and the gfx950 kernels
 // (kao_search.hip, kao_eval.hip, kao_canon.hip, kao_bound.hip, ...).  Not part of the C ABI.
 #pragma once
 #include <stdint.h>
@@ -14,6 +14,7 @@ constexpr int kMaxRF = 8;
 constexpr int kWaves = 4;        // wavefronts per K-eval workgroup; K-search uses 4, 2 or 1 (largest that fits LDS)
 constexpr int kTeamMax = 8;      // wavefronts of a K-search team (k_team: several wavefronts on ONE restart, topics in global memory)
 constexpr int kMaxRacks = 255;   // rack ids are u8, 0xFF marks a padding slot
+constexpr int kLdsLimit = 160 * 1024;  // bytes of LDS a workgroup may carve on gfx950 (host-side checks; the kernel files size their own carves)
 constexpr int kRackTab = 256;    // entries of the per-rack LDS tables (rack sizes, K, RT)
 constexpr uint32_t kNoneW = 0xFFFFFFFFu;  // empty slot in the LDS word layout (x | rack << 16)
 constexpr uint32_t kKeyNull = 0xFFFFFFFFu;
@@ -248,10 +249,10 @@ CycleCtx *cycle_open(const kao_topic *t, int *rc_out);
 int cycle_run(CycleCtx *c, uint16_t *assign, int32_t max_rounds, double deadline, int64_t *objective, int32_t stats[8],
               int (*poll)(void *) = nullptr, void *poll_arg = nullptr, bool pairs = true);
 void cycle_close(CycleCtx *c);
-// helpers of the host side (kao_solve.cpp) for the device translation units
 // compound edges of leader-balanced pairs (kao_pairs.cpp; host only): the cheapest pair behind every edge x -> z
 struct PairEdge { int32_t cost; int32_t set; int32_t p, q; uint16_t rowp[8], rowq[8]; };
 int pair_edges(const kao_topic *t, const uint16_t *assignment, int gmin, std::unordered_map<uint32_t, PairEdge> &edges, int64_t stats[4]);
+// fail / require_init / now_s of the host side (kao_runtime.cpp) for the device translation units
 int api_fail(int code, const char *msg);
 int api_require_init();
 double api_now_s();

@@ -429,7 +429,7 @@ int auto_period_log2(int P, int RF) {
 bool dual_supported(const kao_topic *t, bool session_bw) {
     const bool wide = t->rf > kRFP || t->rf_cur > kRFP;
     const bool hbw = t->broker_w || t->broker_wl;
-    if (bound_lds_bytes(t->n_brokers, 0, t->n_racks, false, wide ? 8 : 4, hbw || session_bw) > 160 * 1024) return false;
+    if (bound_lds_bytes(t->n_brokers, 0, t->n_racks, false, wide ? 8 : 4, hbw || session_bw) > kLdsLimit) return false;
     const int64_t n = (int64_t)t->n_partitions * t->rf;
     // Round 4: the P*RF <= 2^17 limit of rounds 1-3 was far inside the arithmetic's real headroom (BASELINE config 5 as one
     // topic is 300,000 slots).  What the integers need: a subgradient entry |s| <= n and a direction |d| <= 64 n in 32 bits

@@ -8,6 +8,10 @@
 
 #include "kao_rccl.h"
 
+namespace kao {
+thread_local SolveCounters g_last{};   // this thread's last solve (kao_host.h); kao_capped.cpp adds its rounds
+}  // namespace kao
+
 namespace {
 
 // The counts of the deterministic schedule (kao_opts.schedule == 0) for a session whose largest topic has `slots` replica
@@ -291,7 +295,7 @@ struct SolveRun {
                 const kao_topic &t = user_topics[i];
                 slots = std::max<int64_t>(slots, (int64_t)t.n_partitions * std::max(t.rf, 1));
                 const int nw = (t.rf > kRFP || t.rf_cur > kRFP) ? 2 * kRFP : kRFP;
-                hbm = hbm || (int64_t)t.n_partitions * nw * 4 + 8 * 1024 > 160 * 1024;
+                hbm = hbm || (int64_t)t.n_partitions * nw * 4 + 8 * 1024 > kLdsLimit;
             }
             if (hbm && !require_init()) {
                 // never more than the session's own automatic count (with many topics beside a large one the override
@@ -1079,12 +1083,6 @@ int collect_results(std::vector<Dev> &D, DeviceScope &scope, const std::vector<i
 }
 
 }  // namespace
-
-namespace kao {
-int api_fail(int code, const char *msg) { return fail(code, msg ? msg : ""); }
-int api_require_init() { return require_init(); }
-double api_now_s() { return now_s(); }
-}  // namespace kao
 
 extern "C" {
 int kao_solve(const kao_topic *topics, int32_t n_topics, const kao_opts *opts, kao_result *results) {
