@@ -574,11 +574,12 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 uint32_t jc = jmp_c;
                 asm volatile("" : "+v"(jc));
                 uint32_t best1 = kKeyNull, best2 = kKeyNull;   // (cost + bias) << 16 | tie << 8 | round, per slot
-                auto scan_round2 = [&](auto with_w, int base, int rd) {
+                // (the keys of one round, by reference: two plain rounds of a trip meet the running minima in one v_min3_u32 per slot)
+                auto scan_round2 = [&](auto with_w, int base, int rd, uint32_t &key1, uint32_t &key2) {
                     const uint32_t st1 = lcg24(rng);
                     uint32_t st2;
                     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(st2) : "v"(st1), "s"(jmp_a), "v"(jc));
-                    const int w = (int)(short)L.W[base + lane];   // sign-extended: bit 15 fills the upper half
+                    const int w = (int)reinterpret_cast<const short *>(L.W)[base + lane];   // one ds_read_i16: sign-extended, bit 15 fills the upper half
                     const int rt = L.RT[XR[base + lane]];
                     const int inc = wfld(w, kWIncR);
                     int d1 = __mul24(lam, inc + wfldw(w, kWIncL, lw1) + wfldw(rt, 0, 16u)) + K01;
@@ -590,9 +591,9 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         d2 -= __mul24(S, role_w2<NS>(c2, xw, wl2, wf2));
                     }
                     d1 = min(max(d1, 0), 2 * kDBias - 2);
-                    d2 = min(max(d2, 0), 2 * kDBias - 2);
-                    best1 = min(best1, ((uint32_t)d1 << 16) | (st1 & 0xFF00u) | (uint32_t)rd | ((uint32_t)w & 0xFFFF0000u));
-                    best2 = min(best2, ((uint32_t)d2 << 16) | (st2 & 0xFF00u) | (uint32_t)rd | ((uint32_t)wflag(w, 14) & 0xFFFF0000u));
+                    d2 = min(max(d2, 0), 2 * kDBias - 2) | wflag(w, 14);   // slot 2's no-candidate bit: all ones, a cost field of 0xFFFF below
+                    key1 = ((uint32_t)d1 << 16) | (st1 & 0xFF00u) | (uint32_t)rd | ((uint32_t)w & 0xFFFF0000u);
+                    key2 = ((uint32_t)d2 << 16) | (st2 & 0xFF00u) | (uint32_t)rd;
                 };
                 const int n_rd = (T.Bx + 63) >> 6;
                 int rd = 0, base = 0;
@@ -601,8 +602,15 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
 #pragma unroll
                     for (int i2 = 0; i2 < 2 * NW; ++i2)
                         if (mr[i2] >= rd) nxt = min(nxt, mr[i2]);
-                    for (; rd < nxt; ++rd, base += 64) scan_round2(std::false_type{}, base, rd);
-                    if (rd < n_rd) { scan_round2(std::true_type{}, base, rd); ++rd; base += 64; }
+                    uint32_t k1a, k2a, k1b, k2b;
+                    for (; rd + 1 < nxt; rd += 2, base += 128) {   // two rounds share the address arithmetic, as in the one-slot scan below
+                        scan_round2(std::false_type{}, base, rd, k1a, k2a);
+                        scan_round2(std::false_type{}, base + 64, rd + 1, k1b, k2b);
+                        best1 = min(best1, min(k1a, k1b));
+                        best2 = min(best2, min(k2a, k2b));
+                    }
+                    if (rd < nxt) { scan_round2(std::false_type{}, base, rd, k1a, k2a); best1 = min(best1, k1a); best2 = min(best2, k2a); ++rd; base += 64; }
+                    if (rd < n_rd) { scan_round2(std::true_type{}, base, rd, k1a, k2a); best1 = min(best1, k1a); best2 = min(best2, k2a); ++rd; base += 64; }
                 }
                 asm("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(rng) : "s"(jmp_a), "v"(jc));   // state after both slots' 2 n_rd draws
                 if (holds) L.W[ai & 0xFFFFu] = (uint16_t)w_keep;
@@ -820,7 +828,15 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const bool u_in_b = in4<NS>(b, uw);
                     // independent of the partner slot j: what u would be worth in q, and q's replicas in u's rack
                     const int u_in_q_lead = role_w2<NS>(cb, uw, T.w00, T.w10), u_in_q_fol = role_w2<NS>(cb, uw, T.w01, T.w11);
-                    const int cnt_b_ro = cnt4<NS>(b, ro);
+                    // what leaving rack ro costs (u leaves a, a replica in ro joins b): the same for every partner slot in another rack
+                    const int dv_ro = ddec(cnt_a_ru, T.prack_lo, T.prack_hi) + dinc(cnt4<NS>(b, ro), T.prack_lo, T.prack_hi);
+                    // replicas of q in the rack of each partner slot.  Three slots (RFT = 3): the three pairwise rack equalities give all
+                    // three counts (an empty word's rack, 0xFFFF, equals only another empty word's, as in cnt4); otherwise counted per slot
+                    int cnt_b_rv[3] = {0, 0, 0};
+                    if constexpr (RFT == 3) {
+                        const int e01 = (int)((b.w[0] >> 16) == (b.w[1] >> 16)), e02 = (int)((b.w[0] >> 16) == (b.w[2] >> 16)), e12 = (int)((b.w[1] >> 16) == (b.w[2] >> 16));
+                        cnt_b_rv[0] = 1 + e01 + e02; cnt_b_rv[1] = 1 + e01 + e12; cnt_b_rv[2] = 1 + e02 + e12;
+                    }
 #pragma unroll
                     for (int jj = 0; jj < NS; ++jj) {
                         if (!RFT && jj >= T.RF) break;
@@ -841,8 +857,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         }
                         const uint32_t rv = v >> 16;
                         if (rv != ro)
-                            dVx += ddec(cnt_a_ru, T.prack_lo, T.prack_hi) + dinc(cnt4<NS>(a, rv), T.prack_lo, T.prack_hi) +
-                                   ddec(cnt4<NS>(b, rv), T.prack_lo, T.prack_hi) + dinc(cnt_b_ro, T.prack_lo, T.prack_hi);
+                            dVx += dv_ro + dinc(cnt4<NS>(a, rv), T.prack_lo, T.prack_hi) + ddec(RFT == 3 ? cnt_b_rv[jj < 3 ? jj : 0] : cnt4<NS>(b, rv), T.prack_lo, T.prack_hi);
                         uint32_t keyx;
                         if (kPriced) keyx = ok ? make_key_tie_p(lam, S, dVx, dObjx, dPx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
                         else keyx = ok ? make_key_tie(lam, S, dVx, dObjx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
@@ -935,11 +950,31 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 ap[k] = uw;
             }
         }
-        if (mine) {   // band state of the two brokers whose counters may have changed: lane 0 the old broker, lane 1 the new one
-            const uint32_t xo = (uint32_t)__builtin_amdgcn_readlane((int)uw, win) & 0xFFFFu, xn = (uint32_t)__builtin_amdgcn_readlane((int)vw, win) & 0xFFFFu;
-            if (lane < 2) {
-                const uint32_t xx = lane ? xn : xo;
-                L.W[xx] = (uint16_t)band_fields(T, L.C[xx]);
+        if (mine) {   // band state of the two brokers whose counters have changed: lane 0 the old broker, lane 1 the new one
+            // Only the row whose count moved is rebuilt and inserted into the broker's word (the scan's marks have been restored by
+            // now and a padding index is never accepted, so bits 15:12 are zero either way): a REPLACE of a follower slot moves the
+            // replica counts (row C3), a LEADER-SWAP and an EXCHANGE between a leader and a follower slot the leader counts (row
+            // C4), a REPLACE of a leader slot both, an EXCHANGE between two slots of one kind no count at all.  The kind of the
+            // move is wave-uniform: the winner's slot numbers.
+            const int k_lead = __builtin_amdgcn_readlane(k, win) == 0 ? 2 : 0;
+            int rows;   // bit 0: the replica row, bit 1: the leader row
+            if (type == 0) rows = 1 | k_lead;
+            else if (type == 1) rows = k_lead ^ (__builtin_amdgcn_readlane(j, win) == 0 ? 2 : 0);
+            else rows = 2;
+            if (rows != 0) {
+                const uint32_t xo = (uint32_t)__builtin_amdgcn_readlane((int)uw, win) & 0xFFFFu, xn = (uint32_t)__builtin_amdgcn_readlane((int)vw, win) & 0xFFFFu;
+                uint32_t xx = xo;
+                asm("v_writelane_b32 %0, %1, 1" : "+v"(xx) : "s"(xn));   // lane 1: the new broker
+                int lane_w = lane;   // (through an empty asm: the mask `lane < 2` is one compare here, not a spilled scalar pair hoisted out of the loop)
+                asm volatile("" : "+v"(lane_w));
+                if (lane_w < 2) {
+                    const uint32_t cx = L.C[xx];
+                    uint32_t wx;
+                    if (rows == 3) wx = band_fields(T, cx);
+                    else if (rows == 1) wx = (L.W[xx] & ~kWRowR) | band_entry((int)(cx & 0xFFFFu), T.rep_lo, T.rep_hi);
+                    else wx = (L.W[xx] & ~kWRowL) | (band_entry((int)(cx >> 16), T.lead_lo, T.lead_hi) << 6);
+                    L.W[xx] = (uint16_t)wx;
+                }
             }
         }
         if (kGlobalA) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the winner's stores before the next loads

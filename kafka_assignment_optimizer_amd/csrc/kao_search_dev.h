@@ -214,13 +214,23 @@ constexpr unsigned long long band_table() {
     return t;
 }
 constexpr unsigned long long kBandTab = band_table();
+// clamp(x, -1, 1) as one v_med3_i32 (written as min / max it is recognised as a three-way compare and becomes two compares
+// and two selects, eight of the twelve instructions of a band_entry)
+__device__ __forceinline__ int clamp_pm1(int x) {
+    int r;
+    asm("v_med3_i32 %0, %1, -1, 1" : "=v"(r) : "v"(x));
+    return r;
+}
 __device__ __forceinline__ uint32_t band_entry(int c, int lo, int hi) {
-    const int a = min(max(c - lo, -1), 1), b = min(max(c - hi, -1), 1);
-    return (uint32_t)(kBandTab >> (uint32_t)((__mul24(a, 3) + b + 4) * 6)) & 63u;
+    const int a = clamp_pm1(c - lo), b = clamp_pm1(c - hi);
+    int t;   // 3 a + b, then the shift 6 t + 24, as 24-bit multiply-adds (on a value out of an asm a plain `*` and `+` become a v_mad_u64_u32)
+    asm("v_mad_i32_i24 %0, %1, 3, %2" : "=v"(t) : "v"(a), "v"(b));
+    return (uint32_t)(kBandTab >> (uint32_t)(__mul24(t, 6) + 24)) & 63u;
 }
 __device__ __forceinline__ uint32_t band_fields(const TopicRegs &T, uint32_t c) {
     return band_entry((int)(c & 0xFFFFu), T.rep_lo, T.rep_hi) | (band_entry((int)(c >> 16), T.lead_lo, T.lead_hi) << 6);
 }
+constexpr uint32_t kWRowR = 0x003Fu, kWRowL = 0x0FC0u;   // the replica row (C3) and the leader row (C4) of a band-state word
 constexpr uint32_t kWNoCand = 0x8000u;
 // Bit 14: no candidate for the SECOND slot of a fused two-slot REPLACE scan (search_body), which marks the brokers of its two partitions
 // at once, each slot with its own bit.  Padding indices carry both bits.

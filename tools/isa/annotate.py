@@ -1,5 +1,7 @@
 """Per basic block of one kernel (hipcc -S -gline-tables-only): instruction-class counts and the source lines (.loc) the
-block's instructions come from, as a histogram.  Usage: annotate.py file.s mangled-kernel-name-prefix [first-line last-line]"""
+block's instructions come from, as a histogram.  A block starts at a label and ends at a branch: what follows an `s_cbranch` up to
+the next label is a block of its own (`label+1`, `label+2`, ...), so an early exit is not charged to the path that takes it.
+Usage: annotate.py file.s mangled-kernel-name-prefix [first-line last-line]"""
 import re, sys, collections
 src = open(sys.argv[1]).read().split("\n")
 want = sys.argv[2]
@@ -19,6 +21,9 @@ for i in range(start, end):
     ins = s.split(";")[0].strip()
     cur["ins"].append((ins, cur_line))
     cur["lines"][cur_line] += 1
+    if ins.startswith(("s_cbranch", "s_branch")):   # the fall-through is another block
+        base, _, k = cur["name"].partition("+")
+        blocks.append(cur); cur = dict(name=f"{base}+{int(k or 0) + 1}", ins=[], lines=collections.Counter())
 blocks.append(cur)
 def cls(op):
     if op.startswith(("v_readlane", "v_readfirstlane")): return "rl"
@@ -30,6 +35,7 @@ def cls(op):
     if op.startswith(("global_", "buffer_", "flat_", "scratch_")): return "vmem"
     return "other"
 for b in blocks:
+    if not b["ins"]: continue
     c = collections.Counter(cls(i.split()[0]) for i, _ in b["ins"])
     br = [i.split()[-1] for i, _ in b["ins"] if i.startswith(("s_cbranch", "s_branch"))]
     top = " ".join(f"{ln}x{n}" for ln, n in sorted(b["lines"].items()))
