@@ -289,23 +289,132 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
         // (every lane its own slot, 4 brokers); EXCHANGE always scans; LEADER-SWAP always samples
         const bool sampled = (type == 2) || (type == 0 && ((it >> 3) & 1u));
 
-        // this lane's best proposal of the iteration
-        uint32_t key = kKeyNull;
-        int dV = 0, dObj = 0, p = 0, k = 0, q = 0, j = 0;
-        uint32_t uw = 0, vw = 0;
-        uint32_t kmin;
-        int win;
+        // ---- from a kind's winning proposal to the applied move.  Every move kind below keeps its per-lane proposal (key, p, k, uw, vw,
+        //      dV, dObj; an EXCHANGE also q, j) in its own scope and ends here, with the kind as a compile-time constant: a REPLACE never
+        //      touches q / j, a LEADER-SWAP always rebuilds the leader row, and no proposal variable is shared -- and copied at the
+        //      joins -- between the kinds.  `ty`: 0 REPLACE, 1 EXCHANGE, 2 LEADER-SWAP (= the wave-uniform `type`).  `uni`: the proposal
+        //      is wave-uniform (both REPLACE scans recompute the winner's move in every lane), so nothing is read from lane `win`. ----
+        auto finish = [&](auto ty, auto uni, uint32_t kmin, int win, int p, int k, int q, int j, uint32_t uw, uint32_t vw, int dV, int dObj) {
+            constexpr int TY = decltype(ty)::value;
+            auto of_win = [&](int v) { return decltype(uni)::value ? v : __builtin_amdgcn_readlane(v, win); };
+            if (!kTeam) {
+                if (kmin == kKeyNull) return;
+                if ((int)(kmin >> 8) - kDBias > 0) return;  // accept only non-worsening moves (cost under current lam)
+            }
+            bool mine = true;   // team: this wavefront's proposal is applied
+            int *rec = TR + ((i & 1u) * 16 + (uint32_t)wave) * kTeamRec;
+            if (kTeam) {
+                // ---- the team's proposals meet: record = {acceptable, p, q, broker out, broker in, rack out, rack in, dV, dObj, applied} ----
+                const bool ok = kmin != kKeyNull && (int)(kmin >> 8) - kDBias <= 0;
+                if (lane == win) {
+                    const uint32_t ro_ = uw >> 16, rn_ = vw >> 16;
+                    const bool racks = ok && TY == 0 && ro_ != rn_;   // only a REPLACE across racks reads and changes rack totals
+                    rec[0] = ok ? 1 : 0; rec[1] = p; rec[2] = TY == 1 ? q : p;
+                    rec[3] = (int)(uw & 0xFFFFu); rec[4] = (int)(vw & 0xFFFFu);
+                    rec[5] = racks ? (int)ro_ : 0xFFFF; rec[6] = racks ? (int)rn_ : 0xFFFF;
+                    rec[7] = dV; rec[8] = dObj;
+                }
+                __syncthreads();
+                bool clash = false;
+                if (lane < wave) {   // lane l looks at wavefront l's record: only lower-numbered wavefronts can block this one
+                    const int *o = TR + ((i & 1u) * 16 + (uint32_t)lane) * kTeamRec;
+                    if (o[0]) {
+                        const int mp = rec[1], mq = rec[2], mb0 = rec[3], mb1 = rec[4], mr0 = rec[5], mr1 = rec[6];
+                        clash = (o[1] == mp) | (o[1] == mq) | (o[2] == mp) | (o[2] == mq) | (o[3] == mb0) | (o[3] == mb1) | (o[4] == mb0) | (o[4] == mb1);
+                        if (o[5] != 0xFFFF && mr0 != 0xFFFF) clash |= (o[5] == mr0) | (o[5] == mr1) | (o[6] == mr0) | (o[6] == mr1);
+                    }
+                }
+                mine = ok && __ballot(clash) == 0ull;
+            }
+
+            if (lane == win && mine) {  // the winning lane applies its own proposal
+                uint32_t *ap = reinterpret_cast<uint32_t *>(&L.A[p]);
+                if (TY == 0) {
+                    const uint32_t d = (k == 0) ? 0x10001u : 1u;
+                    L.C[uw & 0xFFFFu] -= d;
+                    L.C[vw & 0xFFFFu] += d;
+                    if (!kTeam || (uw >> 16) != (vw >> 16)) {   // (team: moves inside one rack do not own its total -- two of them may run at once)
+                        L.K[uw >> 16] -= 1;
+                        L.K[vw >> 16] += 1;
+                    }
+                    ap[k] = vw;
+                } else if (TY == 1) {
+                    uint32_t *bp = reinterpret_cast<uint32_t *>(&L.A[q]);
+                    if ((k == 0) != (j == 0)) {
+                        const uint32_t lose = (k == 0) ? uw : vw, gain = (k == 0) ? vw : uw;
+                        L.C[lose & 0xFFFFu] -= 0x10000u;
+                        L.C[gain & 0xFFFFu] += 0x10000u;
+                    }
+                    ap[k] = vw;
+                    bp[j] = uw;
+                } else {
+                    L.C[uw & 0xFFFFu] -= 0x10000u;
+                    L.C[vw & 0xFFFFu] += 0x10000u;
+                    ap[0] = vw;
+                    ap[k] = uw;
+                }
+            }
+            if (mine) {   // band state of the two brokers whose counters have changed: lane 0 the old broker, lane 1 the new one
+                // Only the row whose count moved is rebuilt and inserted into the broker's word (the scan's marks have been restored by
+                // now and a padding index is never accepted, so bits 15:12 are zero either way): a REPLACE of a follower slot moves the
+                // replica counts (row C3), a LEADER-SWAP and an EXCHANGE between a leader and a follower slot the leader counts (row
+                // C4), a REPLACE of a leader slot both, an EXCHANGE between two slots of one kind no count at all.  The kind of the
+                // move is wave-uniform: the winner's slot numbers.
+                int rows;   // bit 0: the replica row, bit 1: the leader row
+                if (TY == 0) rows = 1 | (of_win(k) == 0 ? 2 : 0);
+                else if (TY == 1) rows = (of_win(k) == 0 ? 2 : 0) ^ (of_win(j) == 0 ? 2 : 0);
+                else rows = 2;
+                if (rows != 0) {
+                    // (a uniform proposal: masked first, the new broker's index is then the scalar the scan's winner was located by)
+                    const uint32_t xo = (uint32_t)of_win((int)uw) & 0xFFFFu, xn = decltype(uni)::value ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(vw & 0xFFFFu)) : (uint32_t)of_win((int)vw) & 0xFFFFu;
+                    uint32_t xx = xo;
+                    asm("v_writelane_b32 %0, %1, 1" : "+v"(xx) : "s"(xn));   // lane 1: the new broker
+                    int lane_w = lane;   // (through an empty asm: the mask `lane < 2` is one compare here, not a spilled scalar pair hoisted out of the loop)
+                    asm volatile("" : "+v"(lane_w));
+                    if (lane_w < 2) {
+                        const uint32_t cx = L.C[xx];
+                        uint32_t wx;
+                        if (rows == 3) wx = band_fields(T, cx);
+                        else if (rows == 1) wx = (L.W[xx] & ~kWRowR) | band_entry((int)(cx & 0xFFFFu), T.rep_lo, T.rep_hi);
+                        else wx = (L.W[xx] & ~kWRowL) | (band_entry((int)(cx >> 16), T.lead_lo, T.lead_hi) << 6);
+                        L.W[xx] = (uint16_t)wx;
+                    }
+                }
+            }
+            if (kGlobalA) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the winner's stores before the next loads
+            if (kTeam) {
+                if (lane == 0) rec[9] = mine ? 1 : 0;
+                __syncthreads();
+                int dVs = 0, dOs = 0, na = 0;
+                if (lane < n_waves) {
+                    const int *o = TR + ((i & 1u) * 16 + (uint32_t)lane) * kTeamRec;
+                    if (o[9]) { dVs = o[7]; dOs = o[8]; na = 1; }
+                }
+                V += wave_sum(dVs);
+                obj += wave_sum(dOs);
+                accepted += wave_sum(na);
+            } else {
+                V += of_win(dV);
+                obj += of_win(dObj);
+                accepted++;
+            }
+        };
+        constexpr std::integral_constant<int, 0> kReplace{};
+        constexpr std::integral_constant<int, 1> kExchange{};
+        constexpr std::integral_constant<int, 2> kLeaderSwap{};
 
         // Every violation delta of the broker rows (C3, C4) below comes from the brokers' band state W (band_fields): a signed
         // 2-bit field per (row, direction) instead of two compares, a select and a subtract on the counter word; the prices
         // of the priced instantiation apply where the matching "count leaves / re-enters its band" flag is set.
         if (sampled) {
-            p = (int)rnd24_wide(rng, (uint32_t)T.P);
+            const int p = (int)rnd24_wide(rng, (uint32_t)T.P);
             const Part<NW> a = L.A[p];
             const Part<NW> c = CUR[p];
+            uint32_t key = kKeyNull, vw = 0;   // this lane's best proposal of the iteration
+            int dV = 0, dObj = 0;
             if (type == 0) {  // REPLACE (p,k) <- x_g: 2 candidates of any rack, 2 of the old broker's rack
-                k = (int)rnd24(rng, RF8);
-                uw = sel_slot<NS>(a, k);
+                const int k = (int)rnd24(rng, RF8);
+                const uint32_t uw = sel_slot<NS>(a, k);
                 const uint32_t ro = uw >> 16;
                 const bool lead = k == 0;
                 const uint32_t lw = lead ? 2u : 0u;   // width of a leader field: a zero-width extract yields 0 for follower slots
@@ -356,8 +465,11 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     else keyg = okg ? make_key(lam, S, dVg, dObjg, lane) : kKeyNull;
                     if (keyg < key) { key = keyg; vw = xw; dV = dVg; dObj = dObjg; }
                 }
+                const uint32_t kmin = wave_umin(key);  // wavefront min-scan over the lanes' best proposals
+                finish(kReplace, std::false_type{}, kmin, (int)(kmin & 63u), p, k, 0, 0, uw, vw, dV, dObj);
             } else {  // LEADER SWAP inside p: slot 0 <-> slot k, every k = 1..RF-1 is a candidate
-                uw = a.w[0];
+                const uint32_t uw = a.w[0];
+                int k = 0;
                 const int u_lead = role_w2<NS>(c, uw, T.w00, T.w10), u_fol = role_w2<NS>(c, uw, T.w01, T.w11);
                 const uint32_t wu = L.W[uw & 0xFFFFu];
                 const int dV_u = wfld(wu, kWDecL);
@@ -375,9 +487,9 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     else keyg = make_key(lam, S, dVg, dObjg, lane);
                     if (keyg < key) { key = keyg; vw = xw; k = kk; dV = dVg; dObj = dObjg; }
                 }
+                const uint32_t kmin = wave_umin(key);
+                finish(kLeaderSwap, std::false_type{}, kmin, (int)(kmin & 63u), p, k, 0, 0, uw, vw, dV, dObj);
             }
-            kmin = wave_umin(key);  // wavefront min-scan over the lanes' best proposals
-            win = (int)(kmin & 63u);
         } else {
             // ---- phase A: tournament over T_tour random slots; lowest removal score wins the iteration ----
             // Score one random slot: the cost of taking its replica out under the current penalty.  REPLACE: the replica
@@ -618,47 +730,57 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 // lowest key; ties go to slot 1, then to the lowest lane -- the rule of two minima, a compare and a ballot.
                 const uint32_t kw = wave_umin(min(((best1 >> 1) & ~127u) | (uint32_t)lane, ((best2 >> 1) & ~127u) | 64u | (uint32_t)lane));
                 const bool two = (kw & 64u) != 0u;   // wave-uniform
-                kmin = kw >> 7;
-                win = (int)(kw & 63u);
-                p = two ? ps[1] : ps[0]; k = two ? ks[1] : ks[0]; uw = two ? us[1] : us[0];
-                if ((int)(kmin >> 8) - kDBias <= 0) {   // will be accepted: the winner's move, wave-uniform
+                const uint32_t kmin = kw >> 7;
+                const int win = (int)(kw & 63u);
+                const int p = two ? ps[1] : ps[0], k = two ? ks[1] : ks[0];
+                const uint32_t uw = two ? us[1] : us[0];
+                if ((int)(kmin >> 8) - kDBias <= 0) {   // will be accepted: the winner's move, wave-uniform -- p, k, uw as scalars
                     const bool lead = k == 0;
                     const uint32_t bw_ = (uint32_t)__builtin_amdgcn_readlane((int)(two ? best2 : best1), win);
                     const uint32_t xs = ((bw_ & 255u) << 6) + (uint32_t)win;
                     const uint32_t rs = XR[xs];
                     const uint32_t ws = L.W[xs];
                     const int rts = L.RT[rs];
-                    vw = xs | (rs << 16);
-                    dV = wfld(ws, kWIncR) + wfldw(ws, kWIncL, lead ? 2u : 0u) + (two ? dvos[1] : dvos[0]) + (two ? (rts >> 16) : wfldw(rts, 0, 16u));
+                    const uint32_t vw = xs | (rs << 16);
+                    const int dV = wfld(ws, kWIncR) + wfldw(ws, kWIncL, lead ? 2u : 0u) + (two ? dvos[1] : dvos[0]) + (two ? (rts >> 16) : wfldw(rts, 0, 16u));
                     int mx1 = -1, mx2 = -1;   // (each slot's own maximum, then a select: `two ? mr[NW + i2] : mr[i2]` became a dynamically indexed scratch array)
 #pragma unroll
                     for (int i2 = 0; i2 < NW; ++i2) { mx1 = max(mx1, mr[i2]); mx2 = max(mx2, mr[NW + i2]); }
                     const bool has_missing = (two ? mx2 : mx1) >= 0;
-                    dObj = -(two ? gs[1] : gs[0]) + (has_missing ? (two ? role_w2<NS>(c2, vw, wl2, wf2) : role_w2<NS>(c1, vw, wl1, wf1)) : 0);
+                    const int dObj = -(two ? gs[1] : gs[0]) + (has_missing ? (two ? role_w2<NS>(c2, vw, wl2, wf2) : role_w2<NS>(c1, vw, wl1, wf1)) : 0);
+                    finish(kReplace, std::true_type{}, kmin, win, p, k, 0, 0, uw, vw, dV, dObj);
                 }
             } else {
+            // the slot (p,k) of tournament lane wA, wave-uniform: what taking its replica out is worth, and its partition's words
+            auto slot_of = [&](int wA, int &p, int &k, uint32_t &uw, int &g_old, int &dV_old, int &dV_rack_old, Part<NW> &a, Part<NW> &c) {
+                p = __builtin_amdgcn_readlane(pl_, wA);
+                k = __builtin_amdgcn_readlane(kl_, wA);
+                uw = (uint32_t)__builtin_amdgcn_readlane((int)oldw_l, wA);
+                g_old = __builtin_amdgcn_readlane(g_old_l, wA);
+                dV_old = __builtin_amdgcn_readlane(dvo_l, wA);
+                dV_rack_old = __builtin_amdgcn_readlane(dvr_l, wA);
+                if constexpr (kGlobalA) {
+#pragma unroll
+                    for (int i2 = 0; i2 < NW; ++i2) { a.w[i2] = (uint32_t)__builtin_amdgcn_readlane((int)a_l.w[i2], wA); c.w[i2] = (uint32_t)__builtin_amdgcn_readlane((int)c_l.w[i2], wA); }
+                } else {
+                    a = L.A[p];   // same address in every lane: LDS broadcast
+                    c = CUR[p];
+                }
+            };
+            if (type == 0) {
+            // the move of the first slot is final when it is the only one; a second slot's replaces it when its wave minimum is lower
             uint32_t b_kmin = kKeyNull, b_uw = 0, b_vw = 0;
             int b_win = 0, b_p = 0, b_k = 0, b_dV = 0, b_dObj = 0;
 #pragma nounroll
             for (int si = 0; si < (wA2 >= 0 ? 2 : 1); ++si) {
-            const int wA = si == 0 ? wA1 : wA2;
-            p = __builtin_amdgcn_readlane(pl_, wA);
-            k = __builtin_amdgcn_readlane(kl_, wA);
-            uw = (uint32_t)__builtin_amdgcn_readlane((int)oldw_l, wA);
-            const int g_old = __builtin_amdgcn_readlane(g_old_l, wA);
-            const int dV_old = __builtin_amdgcn_readlane(dvo_l, wA);
-            const int dV_rack_old = __builtin_amdgcn_readlane(dvr_l, wA);
-            Part<NW> a, c;
-            if constexpr (kGlobalA) {
-#pragma unroll
-                for (int i2 = 0; i2 < NW; ++i2) { a.w[i2] = (uint32_t)__builtin_amdgcn_readlane((int)a_l.w[i2], wA); c.w[i2] = (uint32_t)__builtin_amdgcn_readlane((int)c_l.w[i2], wA); }
-            } else {
-                a = L.A[p];   // same address in every lane: LDS broadcast
-                c = CUR[p];
-            }
-            const bool lead = k == 0;  // wave-uniform
-            const uint32_t ro = uw >> 16;
-            if (type == 0) {
+                int p, k, g_old, dV_old, dV_rack_old;
+                uint32_t uw;
+                Part<NW> a, c;
+                slot_of(si == 0 ? wA1 : wA2, p, k, uw, g_old, dV_old, dV_rack_old, a, c);
+                const bool lead = k == 0;  // wave-uniform
+                const uint32_t ro = uw >> 16;
+                uint32_t vw = 0;   // the winner's move, recomputed in every lane: wave-uniform like p, k, uw
+                int dV = 0, dObj = 0;
                 // ---- phase B (REPLACE): every target broker for slot (p,k), 64 per round -- the band-state scan.  A candidate
                 //      costs one W read (band deltas + where its rack's entry of RT lives), one RT read, two bit-field
                 //      extracts, the cost and the key; the per-lane running minimum is a plain v_min_u32 because the key carries
@@ -791,10 +913,10 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     if ((bestc >> 8) < (bestA >> 8)) { bestA = bestc; chunkA = cb; }   // strict: ties stay with the earlier round
                 }
                 if (!kTeam && holds) L.W[ai & 0xFFFFu] = (uint16_t)w_keep;
-                key = bestA >> 8;   // (cost + bias) << 8 | tie: the key format of every other move type
-                kmin = wave_umin(key);
+                const uint32_t key = bestA >> 8;   // (cost + bias) << 8 | tie: the key format of every other move type
+                const uint32_t kmin = wave_umin(key);
                 const unsigned long long bal = __ballot(key == kmin);
-                win = __ffsll((long long)bal) - 1;  // ties inside the wave go to the lowest lane
+                const int win = __ffsll((long long)bal) - 1;  // ties inside the wave go to the lowest lane
                 if ((int)(kmin >> 8) - kDBias <= 0) {   // will be accepted: the winner's move, wave-uniform
                     const uint32_t bw_ = (uint32_t)__builtin_amdgcn_readlane((int)bestA, win);
                     const uint32_t xs = (uint32_t)__builtin_amdgcn_readlane(chunkA, win) + ((bw_ & 255u) << 6) + (uint32_t)win;
@@ -806,8 +928,18 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     dObj = -g_old + (has_missing ? role_w2<NS>(c, vw, wl, wf) : 0) + (hbw ? bw_of(BW[xs], lead) : 0);
                 }
                 if (si == 0 || kmin < b_kmin) { b_kmin = kmin; b_win = win; b_p = p; b_k = k; b_uw = uw; b_vw = vw; b_dV = dV; b_dObj = dObj; }
+            }   // (the two scan slots)
+            finish(kReplace, std::true_type{}, b_kmin, b_win, b_p, b_k, 0, 0, b_uw, b_vw, b_dV, b_dObj);
             } else {
                 // ---- phase B (EXCHANGE): every partner slot (q,j) for slot (p,k), 64 partitions per round ----
+                int p, k, g_old, dV_old, dV_rack_old;
+                uint32_t uw;
+                Part<NW> a, c;
+                slot_of(wA1, p, k, uw, g_old, dV_old, dV_rack_old, a, c);
+                const bool lead = k == 0;  // wave-uniform
+                const uint32_t ro = uw >> 16;
+                uint32_t key = kKeyNull, vw = 0;   // this lane's best partner slot
+                int dV = 0, dObj = 0, q = 0, j = 0;
                 const int nrp = lead ? 0 : 1;
                 const int cnt_a_ru = cnt4<NS>(a, ro);
                 const uint32_t wu = L.W[uw & 0xFFFFu];
@@ -885,116 +1017,14 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         x_round(rd, b, cb);
                     }
                 }
-                kmin = wave_umin(key);
+                const uint32_t kmin = wave_umin(key);
                 const unsigned long long bal = __ballot(key == kmin);
-                win = __ffsll((long long)bal) - 1;  // ties inside the wave go to the lowest lane
+                const int win = __ffsll((long long)bal) - 1;  // ties inside the wave go to the lowest lane
+                finish(kExchange, std::false_type{}, kmin, win, p, k, q, j, uw, vw, dV, dObj);
             }
-            }   // (the two scan slots)
-            if (type == 0) { kmin = b_kmin; win = b_win; p = b_p; k = b_k; uw = b_uw; vw = b_vw; dV = b_dV; dObj = b_dObj; }
             }   // (one slot at a time)
         }
-        if (!kTeam) {
-            if (kmin == kKeyNull) continue;
-            if ((int)(kmin >> 8) - kDBias > 0) continue;  // accept only non-worsening moves (cost under current lam)
-        }
-        bool mine = true;   // team: this wavefront's proposal is applied
-        int *rec = TR + ((i & 1u) * 16 + (uint32_t)wave) * kTeamRec;
-        if (kTeam) {
-            // ---- the team's proposals meet: record = {acceptable, p, q, broker out, broker in, rack out, rack in, dV, dObj, applied} ----
-            const bool ok = kmin != kKeyNull && (int)(kmin >> 8) - kDBias <= 0;
-            if (lane == win) {
-                const uint32_t ro_ = uw >> 16, rn_ = vw >> 16;
-                const bool racks = ok && type == 0 && ro_ != rn_;   // only a REPLACE across racks reads and changes rack totals
-                rec[0] = ok ? 1 : 0; rec[1] = p; rec[2] = type == 1 ? q : p;
-                rec[3] = (int)(uw & 0xFFFFu); rec[4] = (int)(vw & 0xFFFFu);
-                rec[5] = racks ? (int)ro_ : 0xFFFF; rec[6] = racks ? (int)rn_ : 0xFFFF;
-                rec[7] = dV; rec[8] = dObj;
-            }
-            __syncthreads();
-            bool clash = false;
-            if (lane < wave) {   // lane l looks at wavefront l's record: only lower-numbered wavefronts can block this one
-                const int *o = TR + ((i & 1u) * 16 + (uint32_t)lane) * kTeamRec;
-                if (o[0]) {
-                    const int mp = rec[1], mq = rec[2], mb0 = rec[3], mb1 = rec[4], mr0 = rec[5], mr1 = rec[6];
-                    clash = (o[1] == mp) | (o[1] == mq) | (o[2] == mp) | (o[2] == mq) | (o[3] == mb0) | (o[3] == mb1) | (o[4] == mb0) | (o[4] == mb1);
-                    if (o[5] != 0xFFFF && mr0 != 0xFFFF) clash |= (o[5] == mr0) | (o[5] == mr1) | (o[6] == mr0) | (o[6] == mr1);
-                }
-            }
-            mine = ok && __ballot(clash) == 0ull;
-        }
-
-        if (lane == win && mine) {  // the winning lane applies its own proposal
-            uint32_t *ap = reinterpret_cast<uint32_t *>(&L.A[p]);
-            if (type == 0) {
-                const uint32_t d = (k == 0) ? 0x10001u : 1u;
-                L.C[uw & 0xFFFFu] -= d;
-                L.C[vw & 0xFFFFu] += d;
-                if (!kTeam || (uw >> 16) != (vw >> 16)) {   // (team: moves inside one rack do not own its total -- two of them may run at once)
-                    L.K[uw >> 16] -= 1;
-                    L.K[vw >> 16] += 1;
-                }
-                ap[k] = vw;
-            } else if (type == 1) {
-                uint32_t *bp = reinterpret_cast<uint32_t *>(&L.A[q]);
-                if ((k == 0) != (j == 0)) {
-                    const uint32_t lose = (k == 0) ? uw : vw, gain = (k == 0) ? vw : uw;
-                    L.C[lose & 0xFFFFu] -= 0x10000u;
-                    L.C[gain & 0xFFFFu] += 0x10000u;
-                }
-                ap[k] = vw;
-                bp[j] = uw;
-            } else {
-                L.C[uw & 0xFFFFu] -= 0x10000u;
-                L.C[vw & 0xFFFFu] += 0x10000u;
-                ap[0] = vw;
-                ap[k] = uw;
-            }
-        }
-        if (mine) {   // band state of the two brokers whose counters have changed: lane 0 the old broker, lane 1 the new one
-            // Only the row whose count moved is rebuilt and inserted into the broker's word (the scan's marks have been restored by
-            // now and a padding index is never accepted, so bits 15:12 are zero either way): a REPLACE of a follower slot moves the
-            // replica counts (row C3), a LEADER-SWAP and an EXCHANGE between a leader and a follower slot the leader counts (row
-            // C4), a REPLACE of a leader slot both, an EXCHANGE between two slots of one kind no count at all.  The kind of the
-            // move is wave-uniform: the winner's slot numbers.
-            const int k_lead = __builtin_amdgcn_readlane(k, win) == 0 ? 2 : 0;
-            int rows;   // bit 0: the replica row, bit 1: the leader row
-            if (type == 0) rows = 1 | k_lead;
-            else if (type == 1) rows = k_lead ^ (__builtin_amdgcn_readlane(j, win) == 0 ? 2 : 0);
-            else rows = 2;
-            if (rows != 0) {
-                const uint32_t xo = (uint32_t)__builtin_amdgcn_readlane((int)uw, win) & 0xFFFFu, xn = (uint32_t)__builtin_amdgcn_readlane((int)vw, win) & 0xFFFFu;
-                uint32_t xx = xo;
-                asm("v_writelane_b32 %0, %1, 1" : "+v"(xx) : "s"(xn));   // lane 1: the new broker
-                int lane_w = lane;   // (through an empty asm: the mask `lane < 2` is one compare here, not a spilled scalar pair hoisted out of the loop)
-                asm volatile("" : "+v"(lane_w));
-                if (lane_w < 2) {
-                    const uint32_t cx = L.C[xx];
-                    uint32_t wx;
-                    if (rows == 3) wx = band_fields(T, cx);
-                    else if (rows == 1) wx = (L.W[xx] & ~kWRowR) | band_entry((int)(cx & 0xFFFFu), T.rep_lo, T.rep_hi);
-                    else wx = (L.W[xx] & ~kWRowL) | (band_entry((int)(cx >> 16), T.lead_lo, T.lead_hi) << 6);
-                    L.W[xx] = (uint16_t)wx;
-                }
-            }
-        }
-        if (kGlobalA) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the winner's stores before the next loads
-        if (kTeam) {
-            if (lane == 0) rec[9] = mine ? 1 : 0;
-            __syncthreads();
-            int dVs = 0, dOs = 0, na = 0;
-            if (lane < n_waves) {
-                const int *o = TR + ((i & 1u) * 16 + (uint32_t)lane) * kTeamRec;
-                if (o[9]) { dVs = o[7]; dOs = o[8]; na = 1; }
-            }
-            V += wave_sum(dVs);
-            obj += wave_sum(dOs);
-            accepted += wave_sum(na);
-        } else {
-            V += __builtin_amdgcn_readlane(dV, win);
-            obj += __builtin_amdgcn_readlane(dObj, win);
-            accepted++;
-        }
-        if (V == 0 && obj > best_obj) { best_obj = obj; snapshot(T, L, ext, best, tid, nthr); }
+        if (V == 0 && obj > best_obj) { best_obj = obj; snapshot(T, L, ext, best, tid, nthr); }   // (V, obj: as the iteration's move, if any, left them)
     }
 
     // ---- end of launch: verify the incremental bookkeeping against a from-scratch recount ----

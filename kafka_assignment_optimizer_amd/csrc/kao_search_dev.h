@@ -101,13 +101,15 @@ template <int NS = 0, int NW> __device__ __forceinline__ int cnt4(const Part<NW>
     for (int i = 0; i < (NS ? NS : NW); ++i) n += (int)((a.w[i] >> 16) == r);
     return n;
 }
-// slot k < NS of a partition: three slots take two selects (the words pass through an empty asm first: selects between words of
-// the struct were turned into a dynamically indexed copy of it in scratch)
+// slot k < NS of a partition: three slots take two selects (the first select passes through an empty asm: selects between words of
+// the struct were turned into a dynamically indexed copy of it in scratch; through the asm goes a fresh value, not the three words
+// themselves, which stay live and were copied, three v_mov per call)
 template <int NS, int NW> __device__ __forceinline__ uint32_t sel_slot(const Part<NW> &a, int k) {
     if constexpr (NS == 3 && NW == 4) {
-        uint32_t w0 = a.w[0], w1 = a.w[1], w2 = a.w[2];
-        asm("" : "+v"(w0), "+v"(w1), "+v"(w2));
-        return (k & 2) ? w2 : ((k & 1) ? w1 : w0);
+        int k1 = k & 1, k2 = k & 2;
+        asm("" : "+v"(k1), "+v"(k2));
+        const uint32_t w0 = a.w[0], w1 = a.w[1], w2 = a.w[2];
+        return k2 ? w2 : (k1 ? w1 : w0);
     } else return sel4(a, k);
 }
 

@@ -49,6 +49,10 @@ __global__ __launch_bounds__(256) void k(uint32_t *out, int iters, uint32_t s0, 
                              "v_min_u32_dpp %4, %4, %4 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n v_min_u32_dpp %5, %5, %5 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
                              "v_min_u32_dpp %6, %6, %6 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n v_min_u32_dpp %7, %7, %7 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
                              : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
+            } else if (KIND == 11) {  // v_mul_hi_u32 (full 32-bit multiply, high half: rnd24_wide's draw) against KIND 3, its 24-bit form
+                asm volatile("v_mul_hi_u32 %0, %1, %8\n v_mul_hi_u32 %1, %2, %8\n v_mul_hi_u32 %2, %3, %8\n v_mul_hi_u32 %3, %4, %8\n"
+                             "v_mul_hi_u32 %4, %5, %8\n v_mul_hi_u32 %5, %6, %8\n v_mul_hi_u32 %6, %7, %8\n v_mul_hi_u32 %7, %0, %8\n"
+                             : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "s"(s1));
             } else if (KIND == 8) {  // CONTROL: v_fma_f32 (the guide's table quotes 2 cycles per wave64 instruction for it)
                 asm volatile("v_fma_f32 %0, %0, %8, %1\n v_fma_f32 %1, %1, %8, %2\n v_fma_f32 %2, %2, %8, %3\n v_fma_f32 %3, %3, %8, %4\n"
                              "v_fma_f32 %4, %4, %8, %5\n v_fma_f32 %5, %5, %8, %6\n v_fma_f32 %6, %6, %8, %7\n v_fma_f32 %7, %7, %8, %0\n"
@@ -108,6 +112,7 @@ int main() {
     run<2>("v_mad_u32_u24", d_out, blocks);
     run<3>("v_mul_hi_u32_u24", d_out, blocks);
     run<5>("v_mul_lo_u32", d_out, blocks);
+    run<11>("v_mul_hi_u32", d_out, blocks);
     run<6>("v_min_u32_dpp", d_out, blocks);
     // controls: does this harness reproduce the guide's 2-cycle figure for the fp32 FMA path?
     run<8>("CONTROL v_fma_f32", d_out, blocks);
