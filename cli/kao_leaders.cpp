@@ -1,0 +1,189 @@
+// kao-leaders -- leader-only rebalancing: the fewest preferred-leader changes that put every broker inside the leader band, replica
+// sets kept (kao_balance_leaders).
+//
+//   kao-leaders --current current.json --broker-list 0,1,2 --racks racks.json [--out plan.json] [--slack N] [--auto-slack]
+//               [--device D] [--report]
+//
+// writes a reassignment document holding only the partitions whose preferred leader changes; every row is the current row with the
+// new leader swapped to the front, so executing it moves no data (kao-waves puts the whole plan into one wave).  Topics are balanced
+// one by one; the band is floor / ceil of partitions / brokers per topic, --slack N widens it by N on both sides, --auto-slack takes
+// the smallest N >= --slack that is feasible for the topic.  A partition with a replica outside --broker-list is an error: replica
+// sets are kept here, moving replicas is kao-cli's job.  All computation happens in libkao.so on the GPU; the answer is exact.
+// Exit status: 0 = ok, 1 = error or a topic is infeasible, 2 = usage.
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../include/kao.h"
+#include "kao_json.h"
+
+namespace {
+
+[[noreturn]] void usage(const char *msg) {
+    if (msg) std::fprintf(stderr, "kao-leaders: %s\n", msg);
+    std::fprintf(stderr,
+        "usage: kao-leaders --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
+        "                   [--out <file>] [--slack N] [--auto-slack] [--device D] [--report]\n"
+        "writes the partitions whose preferred leader changes; exit status: 0 = ok, 1 = error or infeasible, 2 = usage\n");
+    std::exit(2);
+}
+
+std::vector<std::string> split(const std::string &s, char sep) {
+    std::vector<std::string> out; std::string cur;
+    for (char c : s) { if (c == sep) { out.push_back(cur); cur.clear(); } else if (!std::isspace((unsigned char)c)) cur += c; }
+    if (!cur.empty() || !s.empty()) out.push_back(cur);
+    return out;
+}
+
+std::string quoted(const std::string &s) {
+    std::string o = "\"";
+    for (char c : s) {
+        if (c == '"' || c == '\\') o += '\\';
+        o += c;
+    }
+    return o + "\"";
+}
+
+struct TopicData {
+    std::string name;
+    std::vector<int> partition_ids;
+    std::vector<uint16_t> current;  // [P * rf]
+    int rf = 0;
+};
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    std::string cur_path, brokers_csv, racks_arg, out_path;
+    int device = 0, slack0 = 0;
+    bool report = false, auto_slack = false;
+    for (int i = 1; i < argc; ++i) {
+        std::string a = argv[i];
+        auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
+        if (a == "--current") cur_path = need("--current");
+        else if (a == "--broker-list") brokers_csv = need("--broker-list");
+        else if (a == "--racks") racks_arg = need("--racks");
+        else if (a == "--out") out_path = need("--out");
+        else if (a == "--slack") {
+            const std::string v = need("--slack");
+            if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage("--slack needs a value >= 0");
+            slack0 = std::atoi(v.c_str());
+        }
+        else if (a == "--auto-slack") auto_slack = true;
+        else if (a == "--device") device = std::atoi(need("--device").c_str());
+        else if (a == "--report") report = true;
+        else if (a == "-h" || a == "--help") usage(nullptr);
+        else usage(("unknown flag " + a).c_str());
+    }
+    if (cur_path.empty() || brokers_csv.empty() || racks_arg.empty()) usage("--current, --broker-list and --racks are required");
+    try {
+        // ---- brokers and racks, as kao-cli reads them ----------------------------------------------
+        std::vector<int> brokers;
+        for (auto &t : split(brokers_csv, ',')) if (!t.empty()) brokers.push_back(std::atoi(t.c_str()));
+        if (brokers.empty()) throw std::runtime_error("empty broker list");
+        std::map<int, int> dense;
+        for (size_t i = 0; i < brokers.size(); ++i) if (!dense.emplace(brokers[i], (int)i).second) throw std::runtime_error("duplicate id in broker list");
+        std::map<int, std::string> rack_name;
+        if (racks_arg.find(':') != std::string::npos && racks_arg.find('{') == std::string::npos) {
+            for (auto &t : split(racks_arg, ',')) { auto kv = split(t, ':'); if (kv.size() != 2) throw std::runtime_error("bad --racks entry " + t); rack_name[std::atoi(kv[0].c_str())] = kv[1]; }
+        } else {
+            std::string txt = slurp(racks_arg);
+            JValue doc = JParser(txt).parse();
+            if (doc.kind != JValue::Obj) throw std::runtime_error("racks file must be a JSON object {\"<brokerId>\": \"<rack>\"}");
+            for (auto &kv : doc.obj) rack_name[std::atoi(kv.first.c_str())] = kv.second.kind == JValue::Str ? kv.second.str : std::to_string((long long)kv.second.num);
+        }
+        std::set<std::string> names;
+        for (int b : brokers) { auto it = rack_name.find(b); if (it == rack_name.end()) throw std::runtime_error("no rack given for broker " + std::to_string(b)); names.insert(it->second); }
+        std::map<std::string, int> rack_idx; for (auto &n : names) { int k = (int)rack_idx.size(); rack_idx[n] = k; }
+        std::vector<uint8_t> rack_of; for (int b : brokers) rack_of.push_back((uint8_t)rack_idx[rack_name[b]]);
+
+        // ---- current assignment: complete rows over the broker list ---------------------------------
+        std::string cur_txt = slurp(cur_path);
+        JValue doc = JParser(cur_txt).parse();
+        const JValue *parts = doc.get("partitions");
+        if (!parts || parts->kind != JValue::Arr) throw std::runtime_error("missing \"partitions\" array");
+        std::map<std::string, std::map<int, std::vector<int>>> by_topic;
+        for (auto &e : parts->arr) {
+            const JValue *t = e.get("topic"), *p = e.get("partition"), *r = e.get("replicas");
+            if (!t || !p || !r || r->kind != JValue::Arr) throw std::runtime_error("partition entry needs topic/partition/replicas");
+            std::vector<int> reps; for (auto &x : r->arr) reps.push_back((int)x.num);
+            by_topic[t->str][(int)p->num] = reps;
+        }
+        std::vector<TopicData> tds;
+        for (auto &kv : by_topic) {
+            TopicData td; td.name = kv.first;
+            for (auto &pr : kv.second) td.rf = std::max(td.rf, (int)pr.second.size());
+            for (auto &pr : kv.second) {
+                bool complete = (int)pr.second.size() == td.rf;
+                for (int b : pr.second) complete = complete && dense.count(b);
+                if (!complete)
+                    throw std::runtime_error("partition " + td.name + "-" + std::to_string(pr.first) + " has a replica outside --broker-list or fewer replicas than "
+                                             "its topic's other partitions: leader-only rebalancing keeps every replica set (use kao-cli to move replicas)");
+                td.partition_ids.push_back(pr.first);
+                for (int b : pr.second) td.current.push_back((uint16_t)dense[b]);
+            }
+            tds.push_back(std::move(td));
+        }
+        int rc = kao_init(device);
+        if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+
+        // ---- balance topic by topic, collect the changed rows ---------------------------------------
+        int exit_code = 0, n_out = 0;
+        std::string body;
+        for (auto &td : tds) {
+            kao_topic t{};
+            const int P = (int)td.partition_ids.size(), B = (int)brokers.size(), RF = td.rf;
+            t.n_brokers = B; t.n_racks = (int)rack_idx.size(); t.n_partitions = P; t.rf = t.rf_cur = RF;
+            t.rack_of = rack_of.data(); t.current = td.current.data();
+            t.w[0][0] = 4; t.w[0][1] = 1; t.w[1][0] = 2; t.w[1][1] = 2;
+            t.rep_lo = t.rep_hi = t.rack_lo = t.rack_hi = t.prack_lo = t.prack_hi = -1;
+            std::vector<uint16_t> rows;
+            int32_t n_changed = 0, status = 0, stats[8] = {0};
+            int64_t objective = 0;
+            int slack = slack0;
+            for (;; ++slack) {   // --auto-slack: the smallest slack >= --slack that is feasible
+                t.lead_lo = std::max(0, P / B - slack);
+                t.lead_hi = (P + B - 1) / B + slack;
+                rows = td.current;
+                rc = kao_balance_leaders(&t, rows.data(), &n_changed, &objective, &status, stats);
+                if (rc) throw std::runtime_error(std::string("kao_balance_leaders: ") + kao_strerror(rc) + " " + kao_last_error());
+                if (status == KAO_STATUS_OPTIMAL_PROVEN || !auto_slack || slack > P) break;
+            }
+            if (status != KAO_STATUS_OPTIMAL_PROVEN) {
+                std::fprintf(stderr, "kao-leaders: topic %s: no choice of leaders among the replicas meets the band (slack %d; %d units unrouted); "
+                                     "try --slack N or --auto-slack\n", td.name.c_str(), slack, stats[7]);
+                exit_code = 1;
+            } else {
+                for (int p = 0; p < P; ++p) {
+                    if (std::equal(rows.begin() + (size_t)p * RF, rows.begin() + (size_t)(p + 1) * RF, td.current.begin() + (size_t)p * RF)) continue;
+                    body += (n_out++ ? ",\n" : "\n");
+                    body += "    {\"topic\":" + quoted(td.name) + ",\"partition\":" + std::to_string(td.partition_ids[(size_t)p]) + ",\"replicas\":[";
+                    for (int k = 0; k < RF; ++k) body += (k ? "," : "") + std::to_string(brokers[rows[(size_t)p * RF + k]]);
+                    body += "]}";
+                }
+            }
+            if (report)
+                std::fprintf(stderr, "topic %s: status=%s leader_changes=%d objective=%lld slack=%d over_before=%d under_before=%d phases=%d rounds=%d "
+                                     "paths=%d longest_path=%d launches=%d\n", td.name.c_str(),
+                             status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "INFEASIBLE_PROVEN", n_changed, (long long)objective, slack,
+                             stats[4], stats[5], stats[0], stats[1], stats[2], stats[3], stats[6]);
+        }
+        const std::string text = "{\"version\":1,\"partitions\":[" + body + "\n]}\n";
+        if (out_path.empty()) std::fputs(text.c_str(), stdout);
+        else {
+            std::ofstream f(out_path);
+            f << text;
+            if (!f) throw std::runtime_error("cannot write " + out_path);
+        }
+        kao_shutdown();
+        return exit_code;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "kao-leaders: %s\n", e.what());
+        return 1;
+    }
+}

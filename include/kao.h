@@ -433,6 +433,24 @@ int kao_plan_waves_sized(int32_t n_brokers, int32_t n_partitions, int32_t width,
                          const uint64_t *size /* [n_partitions] bytes */, uint64_t max_bytes_per_broker, int32_t max_per_broker,
                          uint64_t seed, int32_t *wave /* [n_partitions] */, int32_t *n_waves, int32_t *lower_bound);
 
+/* ---- Leaders: leader-only rebalancing ---------------------------------------------------------------
+ * The fewest preferred-leader changes that put every broker inside the leader band [lead_lo, lead_hi] (as kao_derive_bounds gives
+ * it, overrides honoured), moving no data: the README model with every variable of a broker that holds no replica of the
+ * partition fixed to 0.  `assignment` [P*rf] holds COMPLETE rows (every slot a dense index below n_brokers, no broker twice in a
+ * row; anything else is KAO_ERR_INVALID, checked before the device is used).  For each partition a leader slot j(p) is chosen and
+ * the row is overwritten by itself with slots 0 and j(p) swapped; the other followers keep their places.  *n_changed = the
+ * partitions with j(p) != 0, the minimum over all choices that meet the band: the restricted model is a min-cost flow, solved
+ * exactly on the GPU by successive shortest paths (parallel relaxation over the P*rf implicit arcs, integers only).
+ * *status = KAO_STATUS_OPTIMAL_PROVEN, or KAO_STATUS_INFEASIBLE_PROVEN when no choice of leaders among the replicas meets the band
+ * (the assignment is then left untouched and *n_changed = 0); the return code is KAO_OK in both cases.  The result depends on the
+ * input alone.  *objective (may be NULL) = the README objective of the returned assignment against t->current, by K-eval.
+ * stats (may be NULL): [0] phases, [1] relaxation rounds, [2] augmenting paths, [3] longest path in arcs, [4] sum over brokers of
+ * max(0, leaders - lead_hi) before, [5] of max(0, lead_lo - leaders) before, [6] kernel launches, [7] units left unrouted (0 unless
+ * infeasible).  Limits: rf <= KAO_MAX_RF, n_brokers <= 65534, P*rf <= 4,000,000 (beyond them: KAO_ERR_UNSUPPORTED, as everywhere). */
+int kao_balance_leaders(const kao_topic *t, uint16_t *assignment /* [P*rf] in / out */, int32_t *n_changed,
+                        int64_t *objective /* README objective of the result by K-eval; may be NULL */,
+                        int32_t *status, int32_t stats[8] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

@@ -1,0 +1,317 @@
+"""Test-side restatements of kao_balance_leaders: the fewest preferred-leader changes that put every
+broker's leader count inside [lo, hi], replica sets kept.
+
+  lp_optimum    the HiGHS LP of the restricted model (a network matrix, so the LP value is the integer optimum); None = infeasible
+  balance_ref   successive shortest paths on the residual graph, ONE path at a time: Bellman-Ford distances from the nodes with
+                excess, a breadth-first walk over the tight arcs to the nearest deficit node
+  kernel_model  the kernels' phases step by step (keys of (distance, arcs), lowest tight arc id as predecessor, deficit nodes
+                served in index order): rows, n_changed and stats[0..5, 7] bit for bit
+and the instance families of the tests.  Rows are [P, RF] arrays of dense broker indices, slot 0 = preferred leader."""
+import math
+from collections import deque
+
+import numpy as np
+
+INF = np.iinfo(np.int64).max
+SOURCE = 1 << 62   # key of distance 0 and no arc: (distance + 2^30) << 32 | arcs
+
+
+def lp_optimum(rows, B, lo, hi):
+    """min sum of x[p][j] over j != 0  s.t.  sum_j x[p][j] = 1,  lo <= sum over (p, j) with rows[p][j] == b of x[p][j] <= hi."""
+    from scipy import sparse
+    from scipy.optimize import linprog
+    rows = np.asarray(rows, dtype=np.int64)
+    P, RF = rows.shape
+    n = P * RF
+    var = np.arange(n)
+    cost = np.ones((P, RF))
+    cost[:, 0] = 0.0
+    a_eq = sparse.csr_matrix((np.ones(n), (var // RF, var)), shape=(P, n))
+    per_broker = sparse.csr_matrix((np.ones(n), (rows.ravel(), var)), shape=(B, n))
+    a_ub = sparse.vstack([per_broker, -per_broker]).tocsr()
+    b_ub = np.concatenate([np.full(B, float(hi)), np.full(B, -float(lo))])
+    res = linprog(cost.ravel(), A_ub=a_ub, b_ub=b_ub, A_eq=a_eq, b_eq=np.ones(P), bounds=(0, 1), method="highs")
+    if res.status == 2:
+        return None
+    assert res.status == 0, res.message
+    value = int(round(res.fun))
+    assert abs(res.fun - value) < 1e-6, res.fun
+    return value
+
+
+def _arcs(rows, lead):
+    """Residual partition arcs: tails, heads, costs and slot ids s = p * RF + j of every slot j != lead[p]."""
+    P, RF = rows.shape
+    p = np.repeat(np.arange(P), RF)
+    j = np.tile(np.arange(RF), P)
+    keep = j != lead[p]
+    p, j = p[keep], j[keep]
+    cost = np.where(j == 0, -1, np.where(lead[p] == 0, 1, 0))
+    return rows[p, lead[p]], rows[p, j], cost, p * RF + j
+
+
+def _start(rows, B, lo, hi):
+    P = rows.shape[0]
+    cnt = np.bincount(rows[:, 0], minlength=B).astype(np.int64)
+    f = np.clip(cnt, lo, hi)
+    e = np.concatenate([cnt - f, [int(f.sum()) - P]])
+    over, under = int(np.maximum(cnt - hi, 0).sum()), int(np.maximum(lo - cnt, 0).sum())
+    return f, e, over, under
+
+
+def swap_rows(rows, lead):
+    out = rows.copy()
+    idx = np.arange(rows.shape[0])
+    out[idx, 0] = rows[idx, lead]
+    out[idx, lead] = rows[idx, 0]
+    return out
+
+
+def balance_ref(rows, B, lo, hi):
+    """(feasible, output rows, n_changed), one augmenting path per shortest-path solve."""
+    rows = np.asarray(rows, dtype=np.int64)
+    P, RF = rows.shape
+    T = B
+    lead = np.zeros(P, dtype=np.int64)
+    f, e, _, _ = _start(rows, B, lo, hi)
+    while (e > 0).any():
+        u, v, c, s = _arcs(rows, lead)
+        up = np.nonzero(f < hi)[0]      # b -> T
+        down = np.nonzero(f > lo)[0]    # T -> b
+        u = np.concatenate([u, up, np.full(len(down), T)])
+        v = np.concatenate([v, np.full(len(up), T), down])
+        c = np.concatenate([c, np.zeros(len(up) + len(down), dtype=np.int64)])
+        s = np.concatenate([s, -1 - up, np.full(len(down), -1 - T)])   # node arcs: -1 - b for b -> T, -1 - T for T -> b
+        big = 1 << 40
+        dist = np.where(e > 0, 0, big).astype(np.int64)
+        for _ in range(B + 2):
+            cand = np.where(dist[u] < big, dist[u] + c, big)
+            new = dist.copy()
+            np.minimum.at(new, v, cand)
+            if (new == dist).all():
+                break
+            dist = new
+        else:
+            raise AssertionError("negative cycle")
+        deficit = np.nonzero((e < 0) & (dist < big))[0]
+        if len(deficit) == 0:
+            return False, rows.copy(), 0
+        t = int(deficit[np.argmin(dist[deficit])])
+        tight = np.nonzero((dist[u] < big) & (dist[u] + c == dist[v]))[0]
+        out = {}
+        for a in tight:
+            out.setdefault(int(u[a]), []).append(int(a))
+        # breadth first from every node that has excess AND distance 0 (a path from it along tight arcs costs dist[t])
+        parent = {int(b): None for b in np.nonzero((e > 0) & (dist == 0))[0]}
+        queue = deque(parent)
+        while queue and t not in parent:
+            x = queue.popleft()
+            for a in out.get(x, []):
+                y = int(v[a])
+                if y not in parent:
+                    parent[y] = a
+                    queue.append(y)
+        assert t in parent
+        x = t
+        while parent[x] is not None:
+            a = parent[x]
+            if s[a] >= 0:
+                lead[s[a] // RF] = s[a] % RF
+            elif v[a] == T:
+                f[u[a]] += 1
+            else:
+                f[v[a]] -= 1
+            x = int(u[a])
+        e[x] -= 1
+        e[t] += 1
+    return True, swap_rows(rows, lead), int((lead != 0).sum())
+
+
+def kernel_model(rows, B, lo, hi):
+    """The kernels' schedule on the host: (feasible, output rows, n_changed, stats) with stats[0..5] and stats[7] as
+    kao_balance_leaders reports them (stats[6], the launches, depends on the regime and stays 0)."""
+    rows = np.asarray(rows, dtype=np.int64)
+    P, RF = rows.shape
+    T, PRF = B, P * RF
+    lead = np.zeros(P, dtype=np.int64)
+    f, e, over, under = _start(rows, B, lo, hi)
+    left = over + max(int(e[T]), 0)
+    claim = np.zeros(P, dtype=np.int64)
+    phases = rounds = paths = maxlen = 0
+    while left > 0:
+        phases += 1
+        u, v, c, s = _arcs(rows, lead)
+        step = c * (1 << 32) + 1
+        key = np.where(e > 0, SOURCE, INF).astype(np.int64)
+        while True:
+            rounds += 1
+            new = key.copy()
+            ok = key[u] != INF
+            np.minimum.at(new, v[ok], key[u[ok]] + step[ok])
+            up = np.nonzero((f < hi) & (key[:B] != INF))[0]
+            if len(up):
+                new[T] = min(new[T], int(key[up].min()) + 1)
+            if key[T] != INF:
+                down = np.nonzero(f > lo)[0]
+                new[down] = np.minimum(new[down], key[T] + 1)
+            if (new == key).all():
+                break
+            key = new
+        pred = np.full(B + 1, 0xFFFFFFFF, dtype=np.int64)
+        ok = key[u] != INF
+        ok[ok] = key[u[ok]] + step[ok] == key[v[ok]]
+        np.minimum.at(pred, v[ok], s[ok])
+        for b in range(B):
+            if f[b] < hi and key[b] != INF and key[b] + 1 == key[T]:
+                pred[T] = min(pred[T], PRF + b)
+            if f[b] > lo and key[T] != INF and key[T] + 1 == key[b]:
+                pred[b] = min(pred[b], PRF + B)
+        naug = 0
+        for t in range(B + 1):
+            while e[t] < 0 and key[t] != INF:
+                ok, x = True, t
+                while key[x] & 0xFFFFFFFF:
+                    a = int(pred[x])
+                    if a < PRF:
+                        p = a // RF
+                        if claim[p] == phases:
+                            ok = False
+                            break
+                        y = int(rows[p, lead[p]])
+                    elif a < PRF + B:
+                        y = a - PRF
+                        if f[y] >= hi:
+                            ok = False
+                            break
+                    else:
+                        y = T
+                        if f[x] <= lo:
+                            ok = False
+                            break
+                    x = y
+                if not ok or e[x] <= 0:
+                    break
+                x = t
+                while key[x] & 0xFFFFFFFF:
+                    a = int(pred[x])
+                    if a < PRF:
+                        p = a // RF
+                        y = int(rows[p, lead[p]])
+                        lead[p] = a - p * RF
+                        claim[p] = phases
+                    elif a < PRF + B:
+                        y = a - PRF
+                        f[y] += 1
+                    else:
+                        y = T
+                        f[x] -= 1
+                    x = y
+                e[x] -= 1
+                e[t] += 1
+                naug += 1
+                maxlen = max(maxlen, int(key[t] & 0xFFFFFFFF))
+        paths += naug
+        left -= naug
+        if naug == 0:
+            break
+    stats = [phases, rounds, paths, maxlen, over, under, 0, left]
+    if left:
+        return False, rows.copy(), 0, stats
+    return True, swap_rows(rows, lead), int((lead != 0).sum()), stats
+
+
+# ---- instance families --------------------------------------------------------------------------------------------------------
+def small_family(trials=400):
+    """(rows, B, lo, hi) of the small random family, `trials` instances from one generator seeded 1."""
+    rng = np.random.default_rng(1)
+    out = []
+    for _ in range(trials):
+        B = int(rng.integers(3, 10))
+        P = int(rng.integers(2, 30))
+        RF = int(rng.integers(2, 4))
+        rows = np.array([rng.choice(B, RF, replace=False) for _ in range(P)], dtype=np.int64)
+        if rng.random() < 0.5:
+            for p in range(P):
+                if rng.random() < 0.6:
+                    j = int(np.argmin(rows[p]))
+                    rows[p, 0], rows[p, j] = rows[p, j], rows[p, 0]
+        lo, hi = P // B, math.ceil(P / B)
+        if rng.random() < 0.3:
+            lo = max(0, lo - 1)
+        out.append((rows, B, lo, hi))
+    return out
+
+
+RING_CASES = [(seed, B, P) for (B, P) in ((60, 1800), (61, 1900)) for seed in range(4)]
+# HiGHS optima of ring_instance(seed, B, P), keyed (seed, B)
+RING_LP = {(0, 60): 700, (1, 60): 644, (2, 60): 726, (3, 60): 779, (0, 61): 986, (1, 61): 813, (2, 61): 894, (3, 61): 961}
+
+
+def ring_instance(seed, B, P):
+    """Rows (s + [0, 5, 13]) mod B with a fifth of the starts squeezed into the first quarter of the ring: leadership has to
+    travel several arcs.  The band is floor / ceil of P / B, widened by one on each side when they coincide."""
+    rng = np.random.default_rng(seed)
+    s = np.where(rng.random(P) < 0.2, rng.integers(0, B // 4, P), rng.integers(0, B, P))
+    rows = (s[:, None] + np.array([0, 5, 13])) % B
+    lo, hi = P // B, math.ceil(P / B)
+    if lo == hi:
+        lo, hi = lo - 1, hi + 1
+    return rows.astype(np.int64), B, lo, hi
+
+
+def large_instance(B=1000, P=100000, n_racks=10, seed=5):
+    """1000 brokers x 100,000 partitions at RF 3: each row has one broker from each of three distinct racks out of 10 (broker b is
+    in rack b mod 10); 40 % of the rows have the leader rotated to their lowest rack.  Band = floor / ceil of P / B."""
+    rng = np.random.default_rng(seed)
+    per = B // n_racks
+    racks = np.argsort(rng.random((P, n_racks)), axis=1)[:, :3]
+    rows = racks + n_racks * rng.integers(0, per, (P, 3))
+    rot = rng.random(P) < 0.4
+    j = np.argmin(racks, axis=1)
+    idx = np.nonzero(rot)[0]
+    first = rows[idx, 0].copy()
+    rows[idx, 0] = rows[idx, j[idx]]
+    rows[idx, j[idx]] = first
+    return rows.astype(np.int64), B, P // B, math.ceil(P / B)
+
+
+def complete_rows(current, B, seed):
+    """`current` ([P, RF], 0xFFFF = a replica on a broker outside the target set) with every hole filled by a target broker the
+    row does not hold yet, drawn from a generator seeded `seed`."""
+    rng = np.random.default_rng(seed)
+    rows = np.asarray(current, dtype=np.int64).copy()
+    for p, k in zip(*np.nonzero(rows >= B)):
+        while True:
+            b = int(rng.integers(0, B))
+            if b not in rows[p]:
+                rows[p, k] = b
+                break
+    return rows
+
+
+def config4_topics():
+    """BASELINE config 4 after a 20 % drift, the holes its replaced brokers leave filled: 200 product topics with complete rows."""
+    from kafka_assignment_optimizer_amd import Topic
+    from kafka_assignment_optimizer_amd import synthetic as sy
+    out = []
+    for i, t in enumerate(sy.drift(sy.make_config(4), 0.2, 1)):
+        rows = complete_rows(t.current, t.n_brokers, 1000 + i)
+        out.append(Topic(name=t.name, broker_ids=t.broker_ids, rack_of=t.rack_of, n_racks=t.n_racks, n_partitions=t.n_partitions,
+                         rf=t.rf, current=rows.astype(np.uint16), weights=t.weights))
+    return out
+
+
+def check_swap(before, after):
+    """Every output row is its input row with slot 0 and one slot swapped; returns the partitions changed."""
+    before, after = np.asarray(before, dtype=np.int64), np.asarray(after, dtype=np.int64)
+    assert before.shape == after.shape
+    changed = 0
+    for p in range(before.shape[0]):
+        if (before[p] == after[p]).all():
+            continue
+        j = int(np.nonzero(before[p] == after[p, 0])[0][0])
+        want = before[p].copy()
+        want[0], want[j] = want[j], want[0]
+        assert j != 0 and (want == after[p]).all(), (p, before[p], after[p])
+        changed += 1
+    return changed
