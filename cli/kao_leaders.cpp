@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../include/kao.h"
+#include "kao_cluster.h"
 #include "kao_json.h"
 
 namespace {
@@ -31,22 +32,6 @@ namespace {
         "                   [--out <file>] [--slack N] [--auto-slack] [--device D] [--report]\n"
         "writes the partitions whose preferred leader changes; exit status: 0 = ok, 1 = error or infeasible, 2 = usage\n");
     std::exit(2);
-}
-
-std::vector<std::string> split(const std::string &s, char sep) {
-    std::vector<std::string> out; std::string cur;
-    for (char c : s) { if (c == sep) { out.push_back(cur); cur.clear(); } else if (!std::isspace((unsigned char)c)) cur += c; }
-    if (!cur.empty() || !s.empty()) out.push_back(cur);
-    return out;
-}
-
-std::string quoted(const std::string &s) {
-    std::string o = "\"";
-    for (char c : s) {
-        if (c == '"' || c == '\\') o += '\\';
-        o += c;
-    }
-    return o + "\"";
 }
 
 struct TopicData {
@@ -82,25 +67,10 @@ int main(int argc, char **argv) {
     }
     if (cur_path.empty() || brokers_csv.empty() || racks_arg.empty()) usage("--current, --broker-list and --racks are required");
     try {
-        // ---- brokers and racks, as kao-cli reads them ----------------------------------------------
-        std::vector<int> brokers;
-        for (auto &t : split(brokers_csv, ',')) if (!t.empty()) brokers.push_back(std::atoi(t.c_str()));
-        if (brokers.empty()) throw std::runtime_error("empty broker list");
-        std::map<int, int> dense;
-        for (size_t i = 0; i < brokers.size(); ++i) if (!dense.emplace(brokers[i], (int)i).second) throw std::runtime_error("duplicate id in broker list");
-        std::map<int, std::string> rack_name;
-        if (racks_arg.find(':') != std::string::npos && racks_arg.find('{') == std::string::npos) {
-            for (auto &t : split(racks_arg, ',')) { auto kv = split(t, ':'); if (kv.size() != 2) throw std::runtime_error("bad --racks entry " + t); rack_name[std::atoi(kv[0].c_str())] = kv[1]; }
-        } else {
-            std::string txt = slurp(racks_arg);
-            JValue doc = JParser(txt).parse();
-            if (doc.kind != JValue::Obj) throw std::runtime_error("racks file must be a JSON object {\"<brokerId>\": \"<rack>\"}");
-            for (auto &kv : doc.obj) rack_name[std::atoi(kv.first.c_str())] = kv.second.kind == JValue::Str ? kv.second.str : std::to_string((long long)kv.second.num);
-        }
-        std::set<std::string> names;
-        for (int b : brokers) { auto it = rack_name.find(b); if (it == rack_name.end()) throw std::runtime_error("no rack given for broker " + std::to_string(b)); names.insert(it->second); }
-        std::map<std::string, int> rack_idx; for (auto &n : names) { int k = (int)rack_idx.size(); rack_idx[n] = k; }
-        std::vector<uint8_t> rack_of; for (int b : brokers) rack_of.push_back((uint8_t)rack_idx[rack_name[b]]);
+        const Cluster cl = read_cluster(brokers_csv, racks_arg);
+        const std::vector<int> &brokers = cl.brokers;
+        const std::map<int, int> &dense = cl.dense;
+        const std::vector<uint8_t> &rack_of = cl.rack_of;
 
         // ---- current assignment: complete rows over the broker list ---------------------------------
         std::string cur_txt = slurp(cur_path);
@@ -125,7 +95,7 @@ int main(int argc, char **argv) {
                     throw std::runtime_error("partition " + td.name + "-" + std::to_string(pr.first) + " has a replica outside --broker-list or fewer replicas than "
                                              "its topic's other partitions: leader-only rebalancing keeps every replica set (use kao-cli to move replicas)");
                 td.partition_ids.push_back(pr.first);
-                for (int b : pr.second) td.current.push_back((uint16_t)dense[b]);
+                for (int b : pr.second) td.current.push_back((uint16_t)dense.at(b));
             }
             tds.push_back(std::move(td));
         }
@@ -138,7 +108,7 @@ int main(int argc, char **argv) {
         for (auto &td : tds) {
             kao_topic t{};
             const int P = (int)td.partition_ids.size(), B = (int)brokers.size(), RF = td.rf;
-            t.n_brokers = B; t.n_racks = (int)rack_idx.size(); t.n_partitions = P; t.rf = t.rf_cur = RF;
+            t.n_brokers = B; t.n_racks = (int)cl.rack_names.size(); t.n_partitions = P; t.rf = t.rf_cur = RF;
             t.rack_of = rack_of.data(); t.current = td.current.data();
             t.w[0][0] = 4; t.w[0][1] = 1; t.w[1][0] = 2; t.w[1][1] = 2;
             t.rep_lo = t.rep_hi = t.rack_lo = t.rack_hi = t.prack_lo = t.prack_hi = -1;

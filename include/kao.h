@@ -451,6 +451,37 @@ int kao_balance_leaders(const kao_topic *t, uint16_t *assignment /* [P*rf] in / 
                         int64_t *objective /* README objective of the result by K-eval; may be NULL */,
                         int32_t *status, int32_t stats[8] /* may be NULL */);
 
+/* ---- Failover: failover-aware follower order -------------------------------------------------------
+ * When a broker or a rack goes down Kafka hands each orphaned partition to the first live replica of its list, so the order of
+ * the followers decides who inherits the leaders.  Rows of `width` (1..KAO_MAX_RF) entries per partition over ONE broker index,
+ * partitions of all topics concatenated (the load a failure shifts is a cluster quantity): row p holds k_p >= 1 distinct dense
+ * broker indices < n_brokers followed by width - k_p entries of KAO_NONE (mixed RF by padding); slot 0 is the preferred leader;
+ * lead[b] = #{p : rows[p][0] == b}.  Scenarios: n_scen = n_brokers for scope 0, n_racks for scope 1; scenario g takes down
+ * D_g = {g} (scope 0) or {b : rack_of[b] == g} (scope 1); every replica is assumed in sync.  Partition p belongs to the one
+ * scenario g with rows[p][0] in D_g; its eligible slots are E_p = {j >= 1 : rows[p][j] != KAO_NONE and rows[p][j] not in D_g};
+ * with E_p empty p is OFFLINE in g, otherwise it is AFFECTED and e(p) = min E_p is the slot Kafka would elect today.  A choice
+ * gives each affected p a slot j(p) in E_p; inherit_g(b) = #{affected p of g : rows[p][j(p)] == b}; peak_g = max over b not in
+ * D_g of lead[b] + inherit_g(b) (0 when no broker survives).  peak_before[g] = peak_g at j = e; peak_after[g] = the minimum of
+ * peak_g over all choices; reordered[g] = the minimum of #{p : j(p) != e(p)} over the choices that attain peak_after[g]
+ * (scenarios of one scope share no partition, so all minima are attained together).  Output rows: for every p with
+ * j(p) != e(p) the slots e(p) and j(p) are swapped; nothing else moves, slot 0 never moves, no data moves.  dry_run != 0 leaves
+ * the rows untouched and reports everything else as if they had been applied.  scen[5g .. 5g+4] = {affected, offline,
+ * peak_before, peak_after, reordered}; *n_reordered = the sum of reordered[g].  stats (may be NULL): [0] scenarios with an
+ * affected partition, [1] probes of the peak (full solves, the final min-cost solve included), [2] phases, [3] relaxation rounds,
+ * [4] augmenting paths, [5] longest path in arcs, [6] kernel launches, [7] partitions of the largest scenario.
+ * Exact: for a fixed cap M scenario g is a min-cost flow (each affected partition sends one unit to a broker of E_p, cost 0 for
+ * e(p) and 1 otherwise, broker b takes at most M - lead[b]); M is bisected, every scenario in its own workgroup of one launch.
+ * The result depends on the input alone.  Checked on the host before any device is used: KAO_ERR_INVALID for a null pointer
+ * (stats excepted), scope outside 0..1, width outside 1..KAO_MAX_RF, n_brokers outside 1..65534, n_racks outside
+ * 1..KAO_MAX_RACKS, n_partitions < 0, rack_of[b] >= n_racks, slot 0 not a broker, a broker after a KAO_NONE, an index
+ * >= n_brokers, a broker twice in one row; KAO_ERR_UNSUPPORTED for n_partitions * width > 4,000,000 or n_brokers >
+ * KAO_FAILOVER_MAX_BROKERS (a scenario's node state, 16 bytes per broker, lives in the LDS of one workgroup). */
+#define KAO_FAILOVER_MAX_BROKERS 8000
+int kao_failover_order(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of /* [n_brokers] */,
+                       int32_t n_partitions, int32_t width, uint16_t *rows /* [n_partitions*width] in / out */,
+                       int32_t scope /* 0 = single-broker failures, 1 = rack failures */, int32_t dry_run,
+                       int32_t *scen /* [n_scen*5] */, int32_t *n_reordered, int32_t stats[8] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);
