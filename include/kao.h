@@ -227,6 +227,11 @@ int kao_session_best_keys(kao_session *s, uint64_t *keys);
  * without a host round trip (kafka_assignment_optimizer_amd/multigpu.py::allreduce_best_resident). */
 int kao_session_device_keys(kao_session *s, void **d_keys);
 int kao_session_stats(kao_session *s, kao_stats *out);
+/* K-search launches so far (of those counted in kao_stats.search_rf3_launches) that ran the small-cost form of the RF-3
+ * instantiation: the host has shown from lam_max, obj_scale and the topics' role weights that no move cost of the launch leaves 16 bits
+ * (8 lam_max + 4 obj_scale max|w| <= 16384, unpriced), so the kernel forms costs without the clamp and two at a time.  Same results
+ * either way; the environment variable KAO_SEARCH_SMALL=0 (read when the session is created) keeps the count at 0. */
+int kao_session_small_launches(kao_session *s, int64_t *out);
 /* K-bound: the optimality certificate beyond the closed-form bound (kao_upper_bound).  lp_solve proves optimality
  * by branch-and-bound over the LP relaxation (README.md:135-136); K-bound instead minimises the Lagrangian dual of
  * the same 0-1 model (README.md:144-185) on the device: rows C3, C4, C6 priced with integer multipliers, rows

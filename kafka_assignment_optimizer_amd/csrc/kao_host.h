@@ -155,6 +155,7 @@ struct kao_session {
         int waves = kWaves;  // restarts per K-search workgroup: 4, 2 or 1 -- the largest whose LDS carve fits 160 KiB
         int nw = kRFP;       // replica words per partition of the group's topics: 4 or 8 (template instantiation)
         int rf_uniform = -1; // the RF all topics of the group share (0: mixed; -1: no topic yet)
+        int w_abs_max = 0;   // the largest |w00..w11| over the group's topics (search_small_cost)
         bool rf3 = true;     // every topic has RF 3 and at most 3 current replicas per partition: K-search may run its RF-3 instantiation
         bool global_a = false;   // topic too large for LDS: assignment + current words stay in global memory
         bool cur_global = false; // (round 5) only the current-assignment words stay in global memory / L2, the working words are in LDS (~4,900 .. 9,800 partitions)
@@ -229,6 +230,8 @@ struct kao_session {
     uint64_t eval_bytes_per_launch = 0;
     uint64_t delta_total = 0, search_bytes_total = 0;
     uint64_t search_rf3_launches = 0;   // K-search launches that ran the RF-3 instantiation (kao_stats)
+    uint64_t search_small_launches = 0; // of those, the launches that ran its small-cost form (kao_session_small_launches)
+    bool small_on = true;               // KAO_SEARCH_SMALL (read when the session is created; 0 = never the small-cost form)
 };
 
 namespace kao {

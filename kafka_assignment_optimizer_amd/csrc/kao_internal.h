@@ -159,7 +159,11 @@ size_t eval_lds_bytes(int maxP, int maxB, bool cur_in_lds, int ne = 4);
 // rft = 3: every topic of the group has RF 3 and at most 3 current replicas per partition -- the launch runs the RF-3 instantiation of
 // k_search when search_rf3_eligible (LDS-resident, unpriced, four words per partition, no team); else, and for rft = 0, the generic one
 bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, int team);
-void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team = 0, int rft = 0);
+// small: the RF-3 instantiation may form its costs in 16 bits -- search_small_cost of the launch's penalty range, objective scale and
+// the largest |role weight| of the group's topics (derivation: kao_search.hip); ignored unless the RF-3 instantiation runs
+constexpr int kSmallCostMax = 16384;
+bool search_small_cost(int lam_min, int lam_max, int obj_scale, int w_abs_max, bool priced);
+void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team = 0, int rft = 0, bool small = false);
 bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, int waves, void *stream);   // K-init (topics in global memory); waves = 0: automatic
 void launch_eval(const EvalPools &pools, int n_blocks, int ne, void *stream);
 // copy every topic's winning snapshot (restart id in its packed key) and violation row into contiguous

@@ -39,11 +39,15 @@ namespace kao {
 //                   both the working and the current words is always kNoneW (no move writes a slot k >= RF).  The move arithmetic
 //                   visits words 0..2 only and the slot loops run 2 / 3 times without `k >= RF` guards; memory layout and results
 //                   are those of RFT = 0 (RF read per topic).
-template <bool kGlobalA, bool kPriced, int NW, bool kWide, bool kTeam, bool kCurG = false, int RFT = 0>
+// kSmall         : (RFT = 3 only) the host has shown that no cost this launch forms leaves int16 (search_small_cost below): the keys
+//                   are multiply-adds without the clamp, and the fused scan keeps its two slots' costs in the halves of one register
+//                   (v_pk_mad_i16 / v_pk_add_i16).  Same draws, keys, winners, stores and counters as kSmall = false.
+template <bool kGlobalA, bool kPriced, int NW, bool kWide, bool kTeam, bool kCurG = false, int RFT = 0, bool kSmall = false>
 __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPools &pl, const SearchParams &prm) {
     static_assert(!kTeam || kGlobalA, "teams run topics that live in global memory");
     static_assert(!kCurG || !kGlobalA, "kCurG: the working assignment is in LDS");
     static_assert(RFT == 0 || (RFT == 3 && NW == 4 && !kGlobalA && !kTeam), "RFT = 3: LDS-resident topics of four words per partition");
+    static_assert(!kSmall || (RFT == 3 && !kPriced && !kCurG), "kSmall: the unpriced RF-3 instantiation");
     constexpr int NS = RFT ? RFT : NW;   // words of a partition the move arithmetic visits
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -431,6 +435,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     if (lead) dP_old -= wflag(wo, kWPoutL) & price_lead(pro);
                     dP_rack_old = p_out(L.K[ro], T.rack_lo, T.rack_hi, PG[ro]);
                 }
+                // (small cost: cost + bias = lam * dV + (S * g_old + bias) - S * weight of the candidate; the winner's dObj from its weight)
+                const int base_s = kSmall ? mad24s(S, g_old, kDBias) : 0;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     uint32_t r, jj;
@@ -453,9 +459,10 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         if (r != ro)
                             dVg += dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + dinc(cnt4<NS>(a, r), T.prack_lo, T.prack_hi);
                     }
-                    const int dObjg = role_w2<NS>(c, xw, wl, wf) + (hbw ? bw_of(BW[x], lead) : 0) - g_old;
+                    const int dObjg = role_w2<NS>(c, xw, wl, wf) + (hbw ? bw_of(BW[x], lead) : 0) - (kSmall ? 0 : g_old);
                     uint32_t keyg;
-                    if (kPriced) {
+                    if constexpr (kSmall) keyg = okg ? key_small(mad24s(-S, dObjg, mad24(lam, dVg, base_s)), (uint32_t)lane) : kKeyNull;
+                    else if (kPriced) {
                         const uint32_t prx = PR[x];
                         int dPg = dP_old + (wflag(wn, kWPinR) & price_rep(prx));
                         if (lead) dPg += wflag(wn, kWPinL) & price_lead(prx);
@@ -465,6 +472,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     else keyg = okg ? make_key(lam, S, dVg, dObjg, lane) : kKeyNull;
                     if (keyg < key) { key = keyg; vw = xw; dV = dVg; dObj = dObjg; }
                 }
+                if constexpr (kSmall) dObj -= g_old;
                 const uint32_t kmin = wave_umin(key);  // wavefront min-scan over the lanes' best proposals
                 finish(kReplace, std::false_type{}, kmin, (int)(kmin & 63u), p, k, 0, 0, uw, vw, dV, dObj);
             } else {  // LEADER SWAP inside p: slot 0 <-> slot k, every k = 1..RF-1 is a candidate
@@ -483,7 +491,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const uint32_t wx = L.W[xw & 0xFFFFu];
                     const int dVg = dV_u + wfld(wx, kWIncL);
                     uint32_t keyg;
-                    if (kPriced) keyg = make_key_p(lam, S, dVg, dObjg, dP_u + (wflag(wx, kWPinL) & price_lead(PR[xw & 0xFFFFu])), lane);
+                    if constexpr (kSmall) keyg = key_small(mad24(lam, dVg, mad24s(-S, dObjg, kDBias)), (uint32_t)lane);
+                    else if (kPriced) keyg = make_key_p(lam, S, dVg, dObjg, dP_u + (wflag(wx, kWPinL) & price_lead(PR[xw & 0xFFFFu])), lane);
                     else keyg = make_key(lam, S, dVg, dObjg, lane);
                     if (keyg < key) { key = keyg; vw = xw; k = kk; dV = dVg; dObj = dObjg; }
                 }
@@ -521,7 +530,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int dvl = wfld(wo, leadl ? kWDecL : kWIncL);
                     sc = min(dv7, 0) + min(dvl, 0);
                 }
-                if (kPriced) {
+                if constexpr (kSmall) key_o = key_small(mad24(lam, sc, mad24s(S, g_o, kDBias)), (uint32_t)lane) | tour_off;
+                else if (kPriced) {
                     int dPs = 0;
                     if (TY == 0) {
                         const uint32_t pro = PR[oldw_o & 0xFFFFu];
@@ -649,7 +659,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int dk = dinc(L.K[r], T.rack_lo, T.rack_hi);
                     const int v1 = ((uint32_t)r != ro1) ? v_rk[0] + dk + dinc(cnt4<NS>(a1, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
                     const int v2 = ((uint32_t)r != ro2) ? v_rk[1] + dk + dinc(cnt4<NS>(a2, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
-                    L.RT[r] = (int)(((uint32_t)v1 & 0xFFFFu) | ((uint32_t)v2 << 16));
+                    // (small cost: slot 1 rides in the HIGH half -- its no-candidate mark, bit 15 of W, is the upper half of the sign-extended word)
+                    L.RT[r] = kSmall ? (int)(((uint32_t)v2 & 0xFFFFu) | ((uint32_t)v1 << 16)) : (int)(((uint32_t)v1 & 0xFFFFu) | ((uint32_t)v2 << 16));
                 }
                 // lanes 0..NW-1 look after slot 1's partition, lanes NW..2NW-1 after slot 2's: their brokers are marked, their
                 // displaced current replicas listed.  (Each lane reads its own word.  The lane number goes through an empty asm: the
@@ -683,6 +694,13 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 const int wl1 = lead1 ? T.w00 : T.w01, wf1 = lead1 ? T.w10 : T.w11, wl2 = lead2 ? T.w00 : T.w01, wf2 = lead2 ? T.w10 : T.w11;
                 const int K01 = __mul24(S, gs[0]) + kDBias + __mul24(lam, dvos[0]);
                 const int K02 = __mul24(S, gs[1]) + kDBias + __mul24(lam, dvos[1]);
+                // small cost: both slots' costs in the int16 halves of one register, slot 1 high / slot 2 low.  The bias stays inside K0: the
+                // low 16 bits of a product-sum are the same signed and unsigned, so each half IS that slot's cost field.  The weights of a
+                // weighted round are scaled once, each in its slot's half.
+                const uint32_t leadp = (lead2 ? 1u : 0u) | (lead1 ? 0x10000u : 0u);
+                const uint32_t K0p = ((uint32_t)K02 & 0xFFFFu) | ((uint32_t)K01 << 16);
+                const int wl1h = (int)((uint32_t)(S * wl1) << 16), wf1h = (int)((uint32_t)(S * wf1) << 16);
+                const int wl2s = (int)((uint32_t)(S * wl2) & 0xFFFFu), wf2s = (int)((uint32_t)(S * wf2) & 0xFFFFu);
                 uint32_t jc = jmp_c;
                 asm volatile("" : "+v"(jc));
                 uint32_t best1 = kKeyNull, best2 = kKeyNull;   // (cost + bias) << 16 | tie << 8 | round, per slot
@@ -694,6 +712,32 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int w = (int)reinterpret_cast<const short *>(L.W)[base + lane];   // one ds_read_i16: sign-extended, bit 15 fills the upper half
                     const int rt = L.RT[XR[base + lane]];
                     const int inc = wfld(w, kWIncR);
+                    if constexpr (kSmall) {
+                        // (inc + incL * lead1 | inc + incL * lead2) + RT's word, times lam, plus (K01 | K02): three packed instructions
+                        uint32_t d = pk_mad_s(pk_add(pk_mad_lo((uint32_t)wfld(w, kWIncL), leadp, (uint32_t)inc), (uint32_t)rt), (uint32_t)lam, K0p);
+                        if (decltype(with_w)::value) {
+                            const uint32_t x = (uint32_t)(base + lane);
+                            const uint32_t xw = x | ((uint32_t)XR[x] << 16);
+                            // role_w2 of both slots, each weight already scaled and in its slot's half: a mask per (slot, role) AND-ed with
+                            // the wave-uniform weight (a select would copy each of the four scalars into a VGPR first).  A partition's
+                            // current replicas are distinct brokers (kao_model.cpp refuses anything else): at most one mask per slot is set.
+                            auto mask_of = [](bool b) { uint32_t m = b ? ~0u : 0u; asm("" : "+v"(m)); return m; };
+                            const bool l1 = c1.w[0] == xw, l2 = c2.w[0] == xw;
+                            bool f1 = false, f2 = false;
+#pragma unroll
+                            for (int i2 = 1; i2 < NS; ++i2) { f1 |= c1.w[i2] == xw; f2 |= c2.w[i2] == xw; }
+                            auto and_or = [](uint32_t m, uint32_t w, uint32_t acc) { uint32_t r; asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(m), "s"(w), "v"(acc)); return r; };
+                            uint32_t ws = mask_of(l1) & (uint32_t)wl1h;
+                            ws = and_or(mask_of(f1), (uint32_t)wf1h, ws);
+                            ws = and_or(mask_of(l2), (uint32_t)wl2s, ws);
+                            ws = and_or(mask_of(f2), (uint32_t)wf2s, ws);
+                            d = pk_sub(d, ws);
+                        }
+                        // no candidate: slot 1's half all ones from the sign-extended word, slot 2's from bit 14
+                        key1 = ((d | (uint32_t)w) & 0xFFFF0000u) | (st1 & 0xFF00u) | (uint32_t)rd;
+                        key2 = ((d | (uint32_t)wflag(w, 14)) << 16) | (st2 & 0xFF00u) | (uint32_t)rd;
+                        return;
+                    }
                     int d1 = __mul24(lam, inc + wfldw(w, kWIncL, lw1) + wfldw(rt, 0, 16u)) + K01;
                     int d2 = __mul24(lam, inc + wfldw(w, kWIncL, lw2) + (rt >> 16)) + K02;
                     if (decltype(with_w)::value) {
@@ -742,7 +786,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const uint32_t ws = L.W[xs];
                     const int rts = L.RT[rs];
                     const uint32_t vw = xs | (rs << 16);
-                    const int dV = wfld(ws, kWIncR) + wfldw(ws, kWIncL, lead ? 2u : 0u) + (two ? dvos[1] : dvos[0]) + (two ? (rts >> 16) : wfldw(rts, 0, 16u));
+                    const int dV = wfld(ws, kWIncR) + wfldw(ws, kWIncL, lead ? 2u : 0u) + (two ? dvos[1] : dvos[0]) + ((two != kSmall) ? (rts >> 16) : wfldw(rts, 0, 16u));
                     int mx1 = -1, mx2 = -1;   // (each slot's own maximum, then a select: `two ? mr[NW + i2] : mr[i2]` became a dynamically indexed scratch array)
 #pragma unroll
                     for (int i2 = 0; i2 < NW; ++i2) { mx1 = max(mx1, mr[i2]); mx2 = max(mx2, mr[NW + i2]); }
@@ -991,7 +1035,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         if (rv != ro)
                             dVx += dv_ro + dinc(cnt4<NS>(a, rv), T.prack_lo, T.prack_hi) + ddec(RFT == 3 ? cnt_b_rv[jj < 3 ? jj : 0] : cnt4<NS>(b, rv), T.prack_lo, T.prack_hi);
                         uint32_t keyx;
-                        if (kPriced) keyx = ok ? make_key_tie_p(lam, S, dVx, dObjx, dPx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
+                        if constexpr (kSmall) keyx = ok ? key_small(mad24(lam, dVx, mad24s(-S, dObjx, kDBias)), (tie0 + (uint32_t)jj * 0x55u) & 0xFFu) : kKeyNull;
+                        else if (kPriced) keyx = ok ? make_key_tie_p(lam, S, dVx, dObjx, dPx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
                         else keyx = ok ? make_key_tie(lam, S, dVx, dObjx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
                         if (keyx < key) { key = keyx; vw = v; q = qq; j = jj; dV = dVx; dObj = dObjx; }
                     }
@@ -1051,10 +1096,10 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
 #define KAO_WPE_WIDE 6
 #endif
 template <bool kGlobalA, bool kPriced, int NW, bool kWide> constexpr int search_min_waves() { return kGlobalA ? 1 : (kWide ? KAO_WPE_WIDE : KAO_WPE_SMALL); }
-template <bool kGlobalA, bool kPriced, int NW, bool kWide, int RFT = 0>
+template <bool kGlobalA, bool kPriced, int NW, bool kWide, int RFT = 0, bool kSmall = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(search_min_waves<kGlobalA, kPriced, NW, kWide>(), 8))) void k_search(SearchPools pl, SearchParams prm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    search_body<kGlobalA, kPriced, NW, kWide, false, false, RFT>(smem, pl, prm);
+    search_body<kGlobalA, kPriced, NW, kWide, false, false, RFT, kSmall>(smem, pl, prm);
 }
 // working assignment in LDS, current assignment from global memory / L2 (kCurG; ~4,900 .. 9,800 partitions: always wide)
 template <bool kPriced, int NW>
@@ -1269,13 +1314,38 @@ static_assert(search_lds_total(50, 500, 4, false, false, 4, false, 10, 0, false)
 
 bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, int team) { return !global_a && !cur_global && !priced && nw == 4 && team == 0; }
 
-void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team, int rft) {
+// The "small cost" property of a launch: no cost the kernel forms can leave int16, so the clamp to +-32768 in key_of and in the scans
+// changes nothing and two costs fit the halves of one register (search_body, kSmall).  Costs are lam * dV - S * dObj with
+// lam_min <= lam <= lam_max, S = obj_scale, and w = the largest |w00..w11| over the topics of the launch group.
+//   |dV|: every row a move touches changes its band violation by -1, 0 or +1 (dinc / ddec), so |dV| <= rows touched.
+//     REPLACE (p,k) u -> x : replica rows of u and x (2), their leader rows when k = 0 (2), the rack totals of both racks (2), the
+//                            partition's counts in both racks (2)                                                    -> |dV| <= 8
+//     EXCHANGE (p,k) <-> (q,j): leader rows of u and v (2), each partition's counts in both racks (4)             -> |dV| <= 6
+//     LEADER-SWAP            : leader rows of the two brokers                                                      -> |dV| <= 2
+//     tournament score       : a part of a REPLACE's (at most 4 rows) or of an EXCHANGE's (2)                      -> |sc| <= 4
+//   |dObj|: a sum of role weights with signs: REPLACE new - old (2 terms), EXCHANGE and LEADER-SWAP 4 terms, the tournament 1 -> <= 4 w
+//   the scans: the constant K0 = S * g_old + lam * dV_old (|dV_old| <= 2) alone is within 2 lam + S w; a candidate adds lam * dVx with
+//     |dVx| <= 6 (replica and leader row of x, 4 rows of racks) and subtracts S * weight: K0 + lam * dVx - S * w within 8 lam + 2 S w
+//   So every cost, and every partial sum a packed instruction forms on the way, is within 8 lam_max + 4 S w.  The rule admits half of
+//   int16's range, kSmallCostMax = 16384: the biased cost field then stays inside [16384, 49152], far from both the clamp's ends and
+//   the no-candidate value 0xFFFF.  (The default options give 8 * 40 + 4 * 4 * 4 = 384.)
+// False whenever the launch is priced (prices are added to the cost; broker weights make a session priced).
+bool search_small_cost(int lam_min, int lam_max, int obj_scale, int w_abs_max, bool priced) {
+    if (priced || lam_min < 0 || lam_max < lam_min || obj_scale < 1 || w_abs_max < 0) return false;
+    return 8 * (int64_t)lam_max + 4 * (int64_t)obj_scale * (int64_t)w_abs_max <= (int64_t)kSmallCostMax;
+}
+
+void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team, int rft, bool small) {
     const bool curg = prm.cur_global != 0 && !global_a, wide = prm.wide != 0;
     const size_t lds = search_lds_bytes(prm.maxP, prm.maxBx, waves, global_a, priced, nw, prm.bw != 0, prm.maxR, team, curg);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(n_blocks), block(64 * (team > 0 && !curg ? team : waves));   // a team: one workgroup per restart, `team` wavefronts each
     if (rft == 3 && search_rf3_eligible(global_a, curg, priced, nw, team)) {   // every topic RF 3, at most 3 current replicas (kao_session.cpp)
-        if (wide) launch_lds<k_search<false, false, 4, true, 3>>(grid, block, lds, st, pools, prm);
+        if (small) {   // (the caller: search_small_cost of this launch's options and the group's weights)
+            if (wide) launch_lds<k_search<false, false, 4, true, 3, true>>(grid, block, lds, st, pools, prm);
+            else launch_lds<k_search<false, false, 4, false, 3, true>>(grid, block, lds, st, pools, prm);
+        }
+        else if (wide) launch_lds<k_search<false, false, 4, true, 3>>(grid, block, lds, st, pools, prm);
         else launch_lds<k_search<false, false, 4, false, 3>>(grid, block, lds, st, pools, prm);
         return;
     }

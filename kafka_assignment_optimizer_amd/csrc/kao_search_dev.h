@@ -73,6 +73,45 @@ __device__ __forceinline__ uint32_t make_key_p(int lam, int S, int dV, int dObj,
 __device__ __forceinline__ uint32_t make_key(int lam, int S, int dV, int dObj, int lane) { return key_of(__mul24(lam, dV) - __mul24(S, dObj), (uint32_t)lane); }
 __device__ __forceinline__ uint32_t make_key_tie_p(int lam, int S, int dV, int dObj, int dP, uint32_t tie) { return key_of(__mul24(lam, dV) - __mul24(S, dObj) + dP, tie & 0xFFu); }
 __device__ __forceinline__ uint32_t make_key_tie(int lam, int S, int dV, int dObj, uint32_t tie) { return key_of(__mul24(lam, dV) - __mul24(S, dObj), tie & 0xFFu); }
+// Small-cost launches (search_small_cost, kao_search.hip: the host has shown that no cost of the launch leaves int16): the clamp of
+// key_of changes nothing, so a key is the biased cost as it comes out of a chain of 24-bit multiply-adds -- the caller writes the
+// cost as lam * dV + S * gain, with whatever part of it is the same for several candidates formed once.
+// (as instructions: written with __mul24 and `+` the sums are re-associated and end in v_mul_lo_u32 / v_mad_u64_u32.  mad24s takes a
+// wave-uniform factor first; the bias is the addend of the first multiply-add of a chain, so a key is two multiply-adds and a shift-or.)
+__device__ __forceinline__ int mad24(int a, int b, int c) {
+    int r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ int mad24s(int s, int b, int c) {
+    int r;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "s"(s), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t key_small(int biased_cost, uint32_t low) { return ((uint32_t)biased_cost << 8) | low; }
+// Two int16 lanes in one register (the fused scan keeps its two slots' costs in them).  pk_mad_lo: (a.lo * b.lo + c.lo, a.lo * b.hi + c.lo)
+// -- a and c broadcast from their low halves, b a wave-uniform pair; pk_mad_s: (a.lo * s.lo + c.lo, a.hi * s.lo + c.hi) -- the
+// wave-uniform factor s broadcast from its low half.  16-bit wrap-around, no clamp.
+__device__ __forceinline__ uint32_t pk_mad_lo(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_mad_i16 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_mad_s(uint32_t a, uint32_t s, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_mad_i16 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(s), "v"(c));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_pk_add_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) {
+    uint32_t r;
+    asm("v_pk_sub_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 // packed search prices of one broker: low half = replica price a[b], high half = leader price l[b], key units
 __device__ __forceinline__ int price_rep(uint32_t pr) { return (int)(short)(pr & 0xFFFFu); }
 __device__ __forceinline__ int price_lead(uint32_t pr) { return (int)pr >> 16; }

@@ -190,6 +190,7 @@ void plan_topic(kao_session &s, int t, bool curg_on, int n_cu, SessionPlan &pl) 
 int plan_groups(kao_session &s, int n_cu, SessionPlan &pl) {
     const kao_opts &o = s.opts;
     const bool rft_on = env_int("KAO_SEARCH_RFT", 1) != 0;   // (read per session: a test hook; 0 = the generic K-search kernel throughout)
+    s.small_on = env_int("KAO_SEARCH_SMALL", 1) != 0;        // (the same kind of hook; 0 = the RF-3 kernel always with the general cost arithmetic)
     std::vector<int> order((size_t)s.n_topics);
     for (int t = 0; t < s.n_topics; ++t) order[(size_t)t] = t;
     auto need1 = [&](int t) {  // topics kept in global memory sort last (their LDS need is tiny but they form their own groups)
@@ -227,6 +228,7 @@ int plan_groups(kao_session &s, int n_cu, SessionPlan &pl) {
         for (int t : mem) {
             const TopicDev &d = s.pts[(size_t)t].d;
             g.rf_uniform = g.rf_uniform < 0 ? d.RF : (g.rf_uniform == d.RF ? d.RF : 0);
+            for (const int w : {d.w00, d.w01, d.w10, d.w11}) g.w_abs_max = std::max(g.w_abs_max, w < 0 ? (w == INT32_MIN ? INT32_MAX : -w) : w);
             g.rf3 = g.rf3 && d.RF == 3 && d.rf_cur <= 3;   // (RF 3 with four current replicas: word 3 of CUR is a real replica)
             g.maxP = std::max(g.maxP, d.P); g.maxBx = std::max(g.maxBx, d.Bx); g.maxB = std::max(g.maxB, d.B); g.maxR = std::max(g.maxR, d.R); g.wide = g.wide || (int64_t)d.P * d.RF >= 512;
         }
@@ -479,8 +481,11 @@ int kao_session_step(kao_session *s) {
             HIP_TRY(hipGetLastError());
         }
         const int rft = g.rf3 ? 3 : 0;
-        launch_search(sp, gp, g.smap_n, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team, rft);
-        if (rft && search_rf3_eligible(g.global_a, g.cur_global, s->priced, g.nw, g.team)) s->search_rf3_launches++;
+        const bool rf3_runs = rft && search_rf3_eligible(g.global_a, g.cur_global, s->priced, g.nw, g.team);
+        const bool small = rf3_runs && s->small_on && search_small_cost(gp.lam_min, gp.lam_max, gp.obj_scale, g.w_abs_max, s->priced);
+        launch_search(sp, gp, g.smap_n, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team, rft, small);
+        if (rf3_runs) s->search_rf3_launches++;
+        if (small) s->search_small_launches++;
         HIP_TRY(hipGetLastError());
     }
     if (prof) HIP_TRY(hipEventRecord(e[1], s->stream));
@@ -589,6 +594,12 @@ int kao_session_stats(kao_session *s, kao_stats *out) {
     out->blocks_search = s->blocks_search;
     out->search_rf3_launches = (int32_t)std::min<uint64_t>(s->search_rf3_launches, (uint64_t)INT32_MAX);
     HIP_TRY(hipMemcpy(&out->drift, s->d_drift, 4, hipMemcpyDeviceToHost));
+    return KAO_OK;
+}
+
+int kao_session_small_launches(kao_session *s, int64_t *out) {
+    if (!s || !out) return fail(KAO_ERR_INVALID, "null argument");
+    *out = (int64_t)s->search_small_launches;
     return KAO_OK;
 }
 

@@ -304,6 +304,12 @@ class Session:
         _check(_ffi.load().kao_session_stats(self._h, C.byref(st)), "kao_session_stats")
         return {k: getattr(st, k) for k, _ in _ffi.KaoStats._fields_}
 
+    def small_launches(self) -> int:
+        """K-search launches that ran the small-cost form of the RF-3 instantiation (include/kao.h)."""
+        n = C.c_int64(0)
+        _check(_ffi.load().kao_session_small_launches(self._h, C.byref(n)), "kao_session_small_launches")
+        return int(n.value)
+
     def restart_state(self, topic: int, restart: int) -> dict:
         t = self.topics[topic]
         n = t.n_partitions * t.rf

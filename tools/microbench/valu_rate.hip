@@ -53,6 +53,15 @@ __global__ __launch_bounds__(256) void k(uint32_t *out, int iters, uint32_t s0, 
                 asm volatile("v_mul_hi_u32 %0, %1, %8\n v_mul_hi_u32 %1, %2, %8\n v_mul_hi_u32 %2, %3, %8\n v_mul_hi_u32 %3, %4, %8\n"
                              "v_mul_hi_u32 %4, %5, %8\n v_mul_hi_u32 %5, %6, %8\n v_mul_hi_u32 %6, %7, %8\n v_mul_hi_u32 %7, %0, %8\n"
                              : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "s"(s1));
+            } else if (KIND == 12) {  // v_pk_mad_i16 with op_sel_hi broadcasting a scalar factor's low half (the fused scan's packed costs)
+                asm volatile("v_pk_mad_i16 %0, %0, %8, %1 op_sel_hi:[1,0,1]\n v_pk_mad_i16 %1, %1, %8, %2 op_sel_hi:[1,0,1]\n v_pk_mad_i16 %2, %2, %8, %3 op_sel_hi:[1,0,1]\n"
+                             "v_pk_mad_i16 %3, %3, %8, %4 op_sel_hi:[1,0,1]\n v_pk_mad_i16 %4, %4, %8, %5 op_sel_hi:[0,1,0]\n v_pk_mad_i16 %5, %5, %8, %6 op_sel_hi:[0,1,0]\n"
+                             "v_pk_mad_i16 %6, %6, %8, %7 op_sel_hi:[0,1,0]\n v_pk_mad_i16 %7, %7, %8, %0 op_sel_hi:[0,1,0]\n"
+                             : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h) : "s"(s1));
+            } else if (KIND == 13) {  // v_pk_add_i16
+                asm volatile("v_pk_add_i16 %0, %0, %1\n v_pk_add_i16 %1, %1, %2\n v_pk_add_i16 %2, %2, %3\n v_pk_add_i16 %3, %3, %4\n"
+                             "v_pk_add_i16 %4, %4, %5\n v_pk_add_i16 %5, %5, %6\n v_pk_add_i16 %6, %6, %7\n v_pk_add_i16 %7, %7, %0\n"
+                             : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
             } else if (KIND == 8) {  // CONTROL: v_fma_f32 (the guide's table quotes 2 cycles per wave64 instruction for it)
                 asm volatile("v_fma_f32 %0, %0, %8, %1\n v_fma_f32 %1, %1, %8, %2\n v_fma_f32 %2, %2, %8, %3\n v_fma_f32 %3, %3, %8, %4\n"
                              "v_fma_f32 %4, %4, %8, %5\n v_fma_f32 %5, %5, %8, %6\n v_fma_f32 %6, %6, %8, %7\n v_fma_f32 %7, %7, %8, %0\n"
@@ -114,6 +123,8 @@ int main() {
     run<5>("v_mul_lo_u32", d_out, blocks);
     run<11>("v_mul_hi_u32", d_out, blocks);
     run<6>("v_min_u32_dpp", d_out, blocks);
+    run<12>("v_pk_mad_i16 (op_sel_hi)", d_out, blocks);
+    run<13>("v_pk_add_i16", d_out, blocks);
     // controls: does this harness reproduce the guide's 2-cycle figure for the fp32 FMA path?
     run<8>("CONTROL v_fma_f32", d_out, blocks);
     run<9>("CONTROL v_pk_fma_f32 (2 FMAs per lane)", d_out, blocks);
@@ -128,5 +139,7 @@ int main() {
     run<2>("v_mad_u32_u24, 1 wave per SIMD", d_out, 256, 256);
     run<2>("v_mad_u32_u24, 4 waves per SIMD", d_out, 1024, 256);
     run<2>("v_mad_u32_u24, 6 waves per SIMD", d_out, 1536, 256);
+    run<12>("v_pk_mad_i16 (op_sel_hi), 6 waves per SIMD", d_out, 1536, 256);
+    run<13>("v_pk_add_i16, 6 waves per SIMD", d_out, 1536, 256);
     return 0;
 }
