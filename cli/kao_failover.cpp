@@ -63,32 +63,9 @@ int main(int argc, char **argv) {
         const std::vector<std::string> &rack_names = cl.rack_names;
 
         // ---- current assignment: rows of all topics over the broker list, ordered by (topic, partition) ----
-        std::string cur_txt = slurp(cur_path);
-        JValue doc = JParser(cur_txt).parse();
-        const JValue *parts = doc.get("partitions");
-        if (!parts || parts->kind != JValue::Arr) throw std::runtime_error("missing \"partitions\" array");
-        std::map<std::pair<std::string, int>, std::vector<int>> by_key;
-        for (auto &e : parts->arr) {
-            const JValue *t = e.get("topic"), *p = e.get("partition"), *r = e.get("replicas");
-            if (!t || !p || !r || r->kind != JValue::Arr) throw std::runtime_error("partition entry needs topic/partition/replicas");
-            std::vector<int> reps; for (auto &x : r->arr) reps.push_back((int)x.num);
-            by_key[{t->str, (int)p->num}] = reps;
-        }
-        size_t width = 1;
-        for (auto &kv : by_key) width = std::max(width, kv.second.size());
-        const int P = (int)by_key.size(), B = (int)brokers.size(), W = (int)width;
-        std::vector<uint16_t> cur((size_t)std::max(P, 1) * W, (uint16_t)KAO_NONE);
-        std::vector<const std::pair<const std::pair<std::string, int>, std::vector<int>> *> keys;
-        for (auto &kv : by_key) {
-            const std::string name = kv.first.first + "-" + std::to_string(kv.first.second);
-            if (kv.second.empty()) throw std::runtime_error("partition " + name + " has no replica");
-            for (size_t j = 0; j < kv.second.size(); ++j) {
-                auto it = cl.dense.find(kv.second[j]);
-                if (it == cl.dense.end()) throw std::runtime_error("partition " + name + " has a replica outside --broker-list (broker " + std::to_string(kv.second[j]) + ")");
-                cur[keys.size() * W + j] = (uint16_t)it->second;
-            }
-            keys.push_back(&kv);
-        }
+        const ClusterRows cr = read_rows(cur_path, cl);
+        const std::vector<uint16_t> &cur = cr.rows;
+        const int P = (int)cr.keys.size(), B = (int)brokers.size(), W = cr.width;
         int rc = kao_init(device);
         if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
 
@@ -99,15 +76,6 @@ int main(int argc, char **argv) {
         rc = kao_failover_order(B, (int)rack_names.size(), cl.rack_of.data(), P, W, rows.data(), scope, dry_run ? 1 : 0, scen.data(), &n_reordered, stats);
         if (rc) throw std::runtime_error(std::string("kao_failover_order: ") + kao_strerror(rc) + " " + kao_last_error());
 
-        int n_out = 0;
-        std::string body;
-        for (int p = 0; p < P; ++p) {
-            if (std::equal(rows.begin() + (size_t)p * W, rows.begin() + (size_t)(p + 1) * W, cur.begin() + (size_t)p * W)) continue;
-            body += (n_out++ ? ",\n" : "\n");
-            body += "    {\"topic\":" + quoted(keys[(size_t)p]->first.first) + ",\"partition\":" + std::to_string(keys[(size_t)p]->first.second) + ",\"replicas\":[";
-            for (int k = 0; k < W && rows[(size_t)p * W + k] != KAO_NONE; ++k) body += (k ? "," : "") + std::to_string(brokers[rows[(size_t)p * W + k]]);
-            body += "]}";
-        }
         if (report) {
             int worst_before = 0, worst_after = 0;
             long long offline = 0;
@@ -123,7 +91,7 @@ int main(int argc, char **argv) {
             std::fprintf(stderr, "scope=%s scenarios=%d worst_peak_before=%d worst_peak_after=%d offline=%lld reordered=%d\n", scope_arg.c_str(), G,
                          worst_before, worst_after, offline, n_reordered);
         }
-        const std::string text = "{\"version\":1,\"partitions\":[" + body + "\n]}\n";
+        const std::string text = changed_rows_text(cr, rows, brokers);
         if (out_path.empty()) std::fputs(text.c_str(), stdout);
         else {
             std::ofstream f(out_path);

@@ -2,13 +2,17 @@
 // sets kept (kao_balance_leaders).
 //
 //   kao-leaders --current current.json --broker-list 0,1,2 --racks racks.json [--out plan.json] [--slack N] [--auto-slack]
-//               [--device D] [--report]
+//               [--cluster] [--cluster-lo N] [--cluster-hi N] [--device D] [--report]
 //
 // writes a reassignment document holding only the partitions whose preferred leader changes; every row is the current row with the
 // new leader swapped to the front, so executing it moves no data (kao-waves puts the whole plan into one wave).  Topics are balanced
 // one by one; the band is floor / ceil of partitions / brokers per topic, --slack N widens it by N on both sides, --auto-slack takes
 // the smallest N >= --slack that is feasible for the topic.  A partition with a replica outside --broker-list is an error: replica
-// sets are kept here, moving replicas is kao-cli's job.  All computation happens in libkao.so on the GPU; the answer is exact.
+// sets are kept here, moving replicas is kao-cli's job.  --cluster balances the leaders of all topics together instead
+// (kao_balance_leaders_cluster): every topic keeps its band (--slack as above), and the largest number of
+// partitions any broker leads over the whole cluster is made as low as leader changes alone can make it, or held to --cluster-hi N
+// (which implies --cluster), every broker leading at least --cluster-lo N; topics of different RF are padded; --auto-slack is a usage
+// error there.  All computation happens in libkao.so on the GPU; the answer is exact.
 // Exit status: 0 = ok, 1 = error or a topic is infeasible, 2 = usage.
 #include <algorithm>
 #include <cstdint>
@@ -29,7 +33,8 @@ namespace {
     if (msg) std::fprintf(stderr, "kao-leaders: %s\n", msg);
     std::fprintf(stderr,
         "usage: kao-leaders --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
-        "                   [--out <file>] [--slack N] [--auto-slack] [--device D] [--report]\n"
+        "                   [--out <file>] [--slack N] [--auto-slack] [--cluster] [--cluster-lo N] [--cluster-hi N]\n"
+        "                   [--device D] [--report]\n"
         "writes the partitions whose preferred leader changes; exit status: 0 = ok, 1 = error or infeasible, 2 = usage\n");
     std::exit(2);
 }
@@ -41,12 +46,56 @@ struct TopicData {
     int rf = 0;
 };
 
+// --cluster: all topics together (kao_balance_leaders_cluster)
+int balance_cluster(const Cluster &cl, const std::string &cur_path, const std::string &out_path, int device, int slack, int cluster_lo,
+                    int cluster_hi, bool report) {
+    const ClusterRows cr = read_rows(cur_path, cl);
+    const int P = (int)cr.keys.size(), B = (int)cl.brokers.size(), W = cr.width;
+    std::vector<int32_t> topic_of((size_t)std::max(P, 1), 0), sizes;
+    for (int p = 0; p < P; ++p) {
+        if (p == 0 || cr.keys[(size_t)p].first != cr.keys[(size_t)p - 1].first) sizes.push_back(0);
+        topic_of[(size_t)p] = (int32_t)sizes.size() - 1;
+        ++sizes.back();
+    }
+    if (sizes.empty()) sizes.push_back(0);
+    std::vector<int32_t> tlo, thi;
+    for (int32_t n : sizes) { tlo.push_back(std::max(0, n / B - slack)); thi.push_back((n + B - 1) / B + slack); }
+    int rc = kao_init(device);
+    if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+    std::vector<uint16_t> rows = cr.rows;
+    int32_t n_changed = 0, before = 0, after = 0, status = 0, stats[8] = {0};
+    rc = kao_balance_leaders_cluster(B, P, W, rows.data(), topic_of.data(), (int32_t)sizes.size(), tlo.data(), thi.data(), cluster_lo, cluster_hi, 0,
+                                     &n_changed, &before, &after, &status, stats);
+    if (rc) throw std::runtime_error(std::string("kao_balance_leaders_cluster: ") + kao_strerror(rc) + " " + kao_last_error());
+    const bool ok = status == KAO_STATUS_OPTIMAL_PROVEN;
+    if (!ok)
+        std::fprintf(stderr, "kao-leaders: no choice of leaders among the replicas meets every topic's band (slack %d) and the cluster band "
+                             "(%d units unrouted); try --slack N\n", slack, stats[7]);
+    if (report)
+        std::fprintf(stderr, "cluster: status=%s peak_before=%d peak_after=%d leader_changes=%d probes=%d phases=%d rounds=%d paths=%d "
+                             "longest_path=%d launches=%d pair_nodes=%d unrouted=%d\n", ok ? "OPTIMAL_PROVEN" : "INFEASIBLE_PROVEN", before, after,
+                     n_changed, stats[0], stats[1], stats[2], stats[3], stats[4], stats[5], stats[6], stats[7]);
+    const std::string text = changed_rows_text(cr, rows, cl.brokers);
+    if (out_path.empty()) std::fputs(text.c_str(), stdout);
+    else {
+        std::ofstream f(out_path);
+        f << text;
+        if (!f) throw std::runtime_error("cannot write " + out_path);
+    }
+    kao_shutdown();
+    return ok ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     std::string cur_path, brokers_csv, racks_arg, out_path;
-    int device = 0, slack0 = 0;
-    bool report = false, auto_slack = false;
+    int device = 0, slack0 = 0, cluster_lo = 0, cluster_hi = -1;
+    bool report = false, auto_slack = false, cluster = false;
+    auto count_arg = [](const std::string &v, const char *msg) {
+        if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
+        return std::atoi(v.c_str());
+    };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
@@ -60,15 +109,22 @@ int main(int argc, char **argv) {
             slack0 = std::atoi(v.c_str());
         }
         else if (a == "--auto-slack") auto_slack = true;
+        else if (a == "--cluster") cluster = true;
+        else if (a == "--cluster-lo") cluster_lo = count_arg(need("--cluster-lo"), "--cluster-lo needs a value >= 0");
+        else if (a == "--cluster-hi") { cluster_hi = count_arg(need("--cluster-hi"), "--cluster-hi needs a value >= 0"); cluster = true; }
         else if (a == "--device") device = std::atoi(need("--device").c_str());
         else if (a == "--report") report = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown flag " + a).c_str());
     }
     if (cur_path.empty() || brokers_csv.empty() || racks_arg.empty()) usage("--current, --broker-list and --racks are required");
+    if (cluster_lo && !cluster) usage("--cluster-lo needs --cluster");
+    if (cluster && auto_slack) usage("--auto-slack cannot be combined with --cluster");
+    if (cluster && cluster_hi >= 0 && cluster_hi < cluster_lo) usage("--cluster-hi must be >= --cluster-lo");
     try {
         const Cluster cl = read_cluster(brokers_csv, racks_arg);
         const std::vector<int> &brokers = cl.brokers;
+        if (cluster) return balance_cluster(cl, cur_path, out_path, device, slack0, cluster_lo, cluster_hi, report);
         const std::map<int, int> &dense = cl.dense;
         const std::vector<uint8_t> &rack_of = cl.rack_of;
 

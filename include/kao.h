@@ -487,6 +487,39 @@ int kao_failover_order(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_o
                        int32_t scope /* 0 = single-broker failures, 1 = rack failures */, int32_t dry_run,
                        int32_t *scen /* [n_scen*5] */, int32_t *n_reordered, int32_t stats[8] /* may be NULL */);
 
+/* ---- Leaders across topics: cluster-wide leader balance ------------------------------------------------
+ * kao_balance_leaders balances one topic; a topic's band says nothing about how many partitions of the whole cluster a broker
+ * leads.  Rows as for kao_failover_order: `width` (1..KAO_MAX_RF) entries per partition over ONE broker index, the partitions of
+ * all topics concatenated, row p = k_p >= 1 distinct dense indices < n_brokers, then KAO_NONE padding; slot 0 is the preferred
+ * leader; topic_of[p] in 0..n_topics-1 is the topic of row p.  A choice picks a non-empty slot j(p) per partition;
+ * L(b) = #{p : rows[p][j(p)] == b}, L(t,b) the same count within topic t.  It is ADMISSIBLE at cap M when
+ * topic_lo[t] <= L(t,b) <= topic_hi[t] for every topic t and every broker b of the index (a broker that holds no replica of t has
+ * L(t,b) = 0, so topic_lo[t] > 0 is infeasible there), L(b) >= cluster_lo and L(b) <= M for every broker.
+ * *peak_before = max_b L(b) at j = 0.  cluster_hi = -1: *peak_after = the smallest M with an admissible choice (it may exceed
+ * *peak_before when the input breaks a band), *n_changed = the minimum of #{p : j(p) != 0} over the choices admissible at that M.
+ * cluster_hi >= 0: M = cluster_hi, *n_changed = that minimum at M, *peak_after = max_b L(b) of the chosen rows.  Output rows: the
+ * input row with slots 0 and j(p) swapped, the other slots in place; no data moves.  dry_run != 0 leaves the rows untouched and
+ * reports the same numbers.  *status = KAO_STATUS_OPTIMAL_PROVEN, or KAO_STATUS_INFEASIBLE_PROVEN when no choice is admissible at
+ * any M (at cluster_hi); the rows are then untouched, *n_changed = 0 and *peak_after = *peak_before.  The return code is KAO_OK in
+ * both cases.  There is no seed: the result depends on the input alone.
+ * Exact: for a fixed M this is a min-cost flow on partition -> (topic, broker) -> broker -> sink (bands on the two inner levels,
+ * cost 1 for a slot other than 0), solved on the GPU by successive shortest paths over implicit arcs, integers only; feasibility
+ * is monotone in M, so M is bisected over max-flow probes and one min-cost solve runs at the optimum, each from j = 0.
+ * stats (may be NULL): [0] probes (full solves, the final min-cost solve included), [1] phases, [2] relaxation rounds,
+ * [3] augmenting paths, [4] longest path in arcs, [5] kernel launches, [6] (topic, broker) nodes, [7] units the last failed probe
+ * left unrouted (0 otherwise).  Checked on the host before any device is used: KAO_ERR_INVALID for a null pointer (stats
+ * excepted), width outside 1..KAO_MAX_RF, n_brokers outside 1..65534, n_partitions < 0, n_topics < 1, topic_of out of range,
+ * topic_lo < 0 or topic_lo > topic_hi, cluster_lo < 0, cluster_hi < -1, 0 <= cluster_hi < cluster_lo, slot 0 not a broker, a
+ * broker after a KAO_NONE, an index >= n_brokers, a broker twice in one row; KAO_ERR_UNSUPPORTED for n_partitions * width >
+ * 4,000,000. */
+int kao_balance_leaders_cluster(int32_t n_brokers, int32_t n_partitions, int32_t width,
+                                uint16_t *rows /* [n_partitions*width] in / out */,
+                                const int32_t *topic_of /* [n_partitions], 0..n_topics-1 */, int32_t n_topics,
+                                const int32_t *topic_lo, const int32_t *topic_hi /* [n_topics] */,
+                                int32_t cluster_lo, int32_t cluster_hi /* -1 = minimise the peak */, int32_t dry_run,
+                                int32_t *n_changed, int32_t *peak_before, int32_t *peak_after, int32_t *status,
+                                int32_t stats[8] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

@@ -107,7 +107,10 @@ SIGNATURES = {
     "kao_balance_leaders": (C.c_int, [_P(KaoTopic), _P(C.c_uint16), _P(C.c_int32), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
     "kao_failover_order": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_uint8), C.c_int32, C.c_int32, _P(C.c_uint16), C.c_int32, C.c_int32,
                                      _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
-    "kao_last_solve_timing": (C.c_int, [_P(C.c_double)]),
+    "kao_balance_leaders_cluster": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_int32), C.c_int32, _P(C.c_int32),
+                                              _P(C.c_int32), C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                              _P(C.c_int32), _P(C.c_int32)]),
+    "kao_last_solve_timing":(C.c_int, [_P(C.c_double)]),
     "kao_last_solve_profile": (C.c_int, [_P(C.c_double)]),
     "kao_last_solve_lp": (C.c_int, [_P(C.c_double)]),
 }

@@ -8,6 +8,10 @@ the new leader swapped to the front, so `kafka-reassign-partitions --execute` mo
 wave).  Topics are balanced one by one: the band is floor / ceil of partitions / brokers per topic, `--slack N` widens it by N on
 both sides, `--auto-slack` takes the smallest N that is feasible.  The answer is exact: n_changed is the proven minimum, or the
 topic is proven infeasible (no choice of leaders among its replicas meets the band).
+
+`--cluster` balances the leaders of all topics together instead (kao_balance_leaders_cluster): every topic
+keeps its band, and the largest number of partitions any broker leads over the whole cluster is made as low as leader changes alone
+can make it (or held to `--cluster-hi N`), every broker leading at least `--cluster-lo N`, with the fewest changes.
 """
 from __future__ import annotations
 
@@ -16,8 +20,8 @@ import ctypes as C
 import dataclasses
 import json
 import sys
-from dataclasses import dataclass
-from typing import Optional
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -25,6 +29,7 @@ from . import _ffi
 from .model import NONE, Topic, topics_from_json
 from .solver import STATUS_NAMES, _check, _CTopics
 
+CLUSTER_STAT_KEYS = ("probes", "phases", "rounds", "paths", "longest_path", "launches", "pair_nodes", "unrouted")
 STAT_KEYS = ("phases", "rounds", "paths", "longest_path", "over_before", "under_before", "launches", "unrouted")
 
 
@@ -70,6 +75,100 @@ def balance_topic(topic: Topic, slack: int = 0, auto_slack: bool = False):
         slack += 1
 
 
+@dataclass
+class ClusterLeaderResult:
+    rows: np.ndarray         # [P, width] uint16: the input rows, slot 0 swapped with the chosen leader's slot (untouched with dry_run / infeasible)
+    n_changed: int           # partitions whose preferred leader changes: the minimum at peak_after
+    peak_before: int         # the most partitions a broker leads, over all topics, in the input
+    peak_after: int          # ... in the chosen rows: the lowest reachable with cluster_hi = -1
+    status: str              # "OPTIMAL_PROVEN" | "INFEASIBLE_PROVEN"
+    stats: np.ndarray        # int32[8], see CLUSTER_STAT_KEYS / include/kao.h
+
+
+@dataclass
+class ClusterLeaderPlan:
+    result: ClusterLeaderResult
+    keys: List[Tuple[str, int]]                                                # (topic, partition) per row
+    entries: List[Tuple[str, int, List[int]]] = field(default_factory=list)   # (topic, partition, replicas as broker ids) of the changed rows
+    assignments: Optional[List[np.ndarray]] = None                            # per topic, when topics were given
+
+
+def balance_leaders_cluster_arrays(rows, n_brokers: int, topic_of, topic_lo, topic_hi, cluster_lo: int = 0, cluster_hi: int = -1,
+                                   dry_run: bool = False) -> ClusterLeaderResult:
+    """kao_balance_leaders_cluster on dense rows ([P, width], NONE-padded, slot 0 = preferred leader) of all topics over one
+    broker index; topic_of[p] is the topic of row p, topic_lo / topic_hi the topics' bands."""
+    r = np.array(rows, dtype=np.uint16, order="C")
+    if r.ndim != 2:
+        raise ValueError("rows must be a [P, width] array")
+    P, W = r.shape
+    tof = np.ascontiguousarray(topic_of, dtype=np.int32).reshape(-1)
+    if tof.shape != (P,):
+        raise ValueError(f"topic_of must hold one topic per row ({P}), got {tof.shape[0]}")
+    tlo = np.ascontiguousarray(topic_lo, dtype=np.int32).reshape(-1)
+    thi = np.ascontiguousarray(topic_hi, dtype=np.int32).reshape(-1)
+    if tlo.shape != thi.shape:
+        raise ValueError("topic_lo and topic_hi must have one entry per topic each")
+    flat = r.reshape(-1) if r.size else np.zeros(1, dtype=np.uint16)
+    tof_buf = tof if P else np.zeros(1, dtype=np.int32)
+    n, before, after, status = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    stats = np.zeros(8, dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    _check(_ffi.load().kao_balance_leaders_cluster(int(n_brokers), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                   tof_buf.ctypes.data_as(i32), int(tlo.shape[0]), tlo.ctypes.data_as(i32), thi.ctypes.data_as(i32),
+                                                   int(cluster_lo), int(cluster_hi), int(bool(dry_run)), C.byref(n), C.byref(before),
+                                                   C.byref(after), C.byref(status), stats.ctypes.data_as(i32)), "kao_balance_leaders_cluster")
+    return ClusterLeaderResult(rows=r, n_changed=int(n.value), peak_before=int(before.value), peak_after=int(after.value),
+                               status=STATUS_NAMES[int(status.value)], stats=stats)
+
+
+def _plan_cluster(keys, rows, broker_ids, n_brokers, slack, cluster_lo, cluster_hi, dry_run) -> ClusterLeaderPlan:
+    """The rows of `keys` ((topic, partition), grouped by topic) through kao_balance_leaders_cluster: each topic's band is floor /
+    ceil of its partitions / brokers, widened by `slack` on both sides."""
+    names, topic_of = [], np.zeros(len(keys), dtype=np.int32)
+    for i, (name, _) in enumerate(keys):
+        if not names or names[-1] != name:
+            names.append(name)
+        topic_of[i] = len(names) - 1
+    if len(set(names)) != len(names):
+        raise ValueError("the rows of a topic must be contiguous")
+    sizes = np.bincount(topic_of, minlength=max(len(names), 1))
+    tlo = np.maximum(0, sizes // n_brokers - slack)
+    thi = -(-sizes // n_brokers) + slack
+    res = balance_leaders_cluster_arrays(rows, n_brokers, topic_of, tlo, thi, cluster_lo, cluster_hi, dry_run)
+    changed = np.nonzero((res.rows != rows).any(axis=1))[0]
+    entries = [(keys[p][0], keys[p][1], [int(broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
+    return ClusterLeaderPlan(result=res, keys=list(keys), entries=entries)
+
+
+def balance_leaders_cluster(topics: Sequence[Topic], slack: int = 0, cluster_lo: int = 0, cluster_hi: int = -1, dry_run: bool = False,
+                            assignments=None) -> ClusterLeaderPlan:
+    """kao_balance_leaders_cluster on topics that share one broker index (broker_ids); rows = `assignments`, default each topic's
+    current; topics of different RF are padded.  Returns the per-topic assignments and the plan entries of the changed rows."""
+    from .failover import _from_topics
+    topics = list(topics)
+    if not topics:
+        raise ValueError("no topic given")
+    if slack < 0:
+        raise ValueError("slack must be >= 0")
+    if len({t.name for t in topics}) != len(topics):
+        raise ValueError("topic names must be distinct")
+    fi = _from_topics(topics, assignments)
+    plan = _plan_cluster(fi.keys, fi.rows, fi.broker_ids, len(fi.broker_ids), slack, cluster_lo, cluster_hi, dry_run)
+    plan.assignments, at = [], 0
+    for i, t in enumerate(topics):
+        w = t.current.shape[1] if assignments is None else np.asarray(assignments[i]).reshape(t.n_partitions, -1).shape[1]
+        plan.assignments.append(plan.result.rows[at:at + t.n_partitions, :w].copy())
+        at += t.n_partitions
+    return plan
+
+
+def cluster_report_line(res: ClusterLeaderResult) -> str:
+    """The --cluster --report text, as cli/kao-leaders prints it."""
+    s = res.stats
+    return (f"cluster: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} leader_changes={res.n_changed} "
+            f"probes={s[0]} phases={s[1]} rounds={s[2]} paths={s[3]} longest_path={s[4]} launches={s[5]} pair_nodes={s[6]} unrouted={s[7]}")
+
+
 def plan_text(entries) -> str:
     """The reassignment document of [(topic, partition, replicas)], byte for byte as cli/kao-leaders writes it."""
     rows = ['    {"topic":"%s","partition":%d,"replicas":[%s]}' % (t.replace("\\", "\\\\").replace('"', '\\"'), p, ",".join(str(b) for b in r))
@@ -95,13 +194,44 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--slack", type=int, default=0, help="widen the leader band by N on both sides")
     ap.add_argument("--auto-slack", action="store_true", help="use the smallest slack >= --slack that is feasible, per topic")
+    ap.add_argument("--cluster", action="store_true", help="balance the leaders of all topics together: lowest cluster-wide peak, topic bands kept")
+    ap.add_argument("--cluster-lo", type=int, default=0, help="with --cluster: every broker leads at least N partitions")
+    ap.add_argument("--cluster-hi", type=int, default=-1, help="every broker leads at most N partitions instead of the lowest peak; implies --cluster")
     a = ap.parse_args(argv)
     if a.slack < 0:
         ap.error("--slack must be >= 0")
+    cluster = a.cluster or a.cluster_hi != -1
+    if a.cluster_lo < 0 or a.cluster_hi < -1:
+        ap.error("--cluster-lo and --cluster-hi need a value >= 0")
+    if a.cluster_lo and not cluster:
+        ap.error("--cluster-lo needs --cluster")
+    if cluster and a.auto_slack:
+        ap.error("--auto-slack cannot be combined with --cluster")
+    if cluster and a.cluster_hi >= 0 and a.cluster_hi < a.cluster_lo:
+        ap.error("--cluster-hi must be >= --cluster-lo")
     rc = 0
     try:
         with open(a.current) as f:
             doc = json.load(f)
+        if cluster:
+            from .failover import parse_current
+            fi = parse_current(doc, [int(b) for b in a.broker_list.split(",") if b], _racks(a.racks))   # input errors before the device is touched
+            from .solver import init
+            init(a.device)
+            plan = _plan_cluster(fi.keys, fi.rows, fi.broker_ids, len(fi.broker_ids), a.slack, a.cluster_lo, a.cluster_hi, False)
+            if plan.result.status != "OPTIMAL_PROVEN":
+                print(f"kao-leaders: no choice of leaders among the replicas meets every topic's band (slack {a.slack}) and the cluster "
+                      f"band ({int(plan.result.stats[7])} units unrouted); try --slack N", file=sys.stderr)
+                rc = 1
+            if a.report:
+                print(cluster_report_line(plan.result), file=sys.stderr)
+            text = plan_text(plan.entries)
+            if a.out:
+                with open(a.out, "w") as f:
+                    f.write(text)
+            else:
+                sys.stdout.write(text)
+            return rc
         topics = topics_from_json(doc, [int(b) for b in a.broker_list.split(",") if b], _racks(a.racks))
         for t in topics:
             bad = np.nonzero((t.current == NONE).any(axis=1))[0]
