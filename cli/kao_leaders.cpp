@@ -3,6 +3,8 @@
 //
 //   kao-leaders --current current.json --broker-list 0,1,2 --racks racks.json [--out plan.json] [--slack N] [--auto-slack]
 //               [--cluster] [--cluster-lo N] [--cluster-hi N] [--device D] [--report]
+//   kao-leaders --current current.json --broker-list 0,1,2 --racks racks.json (--traffic traffic.json | --sizes log-dirs.txt)
+//               [--default-weight N] [--min-gain N] [--max-rounds N] [--out plan.json] [--device D] [--report]
 //
 // writes a reassignment document holding only the partitions whose preferred leader changes; every row is the current row with the
 // new leader swapped to the front, so executing it moves no data (kao-waves puts the whole plan into one wave).  Topics are balanced
@@ -13,8 +15,16 @@
 // partitions any broker leads over the whole cluster is made as low as leader changes alone can make it, or held to --cluster-hi N
 // (which implies --cluster), every broker leading at least --cluster-lo N; topics of different RF are padded; --auto-slack is a usage
 // error there.  All computation happens in libkao.so on the GPU; the answer is exact.
+// --traffic FILE ({"version":1,"partitions":[{"topic":..,"partition":..,"weight":N}]}) or --sizes FILE (kafka-log-dirs --describe
+// output, as kao-waves reads it: the partition's size is its weight) weighs the partitions instead (kao_balance_leaders_weighted,
+// DESIGN.md section 4k): the traffic a broker leads, over all topics together, is made even by a deterministic descent, and a lower
+// bound computed beside it proves the peak optimal where the two meet (status OPTIMAL_PROVEN, else FEASIBLE_BOUND_GAP; exit status
+// 0 both times).  --default-weight N weighs the partitions the file does not name (without it they are an error); --min-gain N moves
+// a leader only when the gap it closes exceeds N; --max-rounds N stops the descent early.  Combining them with --slack,
+// --auto-slack or the --cluster flags is a usage error.
 // Exit status: 0 = ok, 1 = error or a topic is infeasible, 2 = usage.
 #include <algorithm>
+#include <cerrno>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +36,7 @@
 #include "../include/kao.h"
 #include "kao_cluster.h"
 #include "kao_json.h"
+#include "kao_sizes.h"
 
 namespace {
 
@@ -35,6 +46,7 @@ namespace {
         "usage: kao-leaders --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
         "                   [--out <file>] [--slack N] [--auto-slack] [--cluster] [--cluster-lo N] [--cluster-hi N]\n"
         "                   [--device D] [--report]\n"
+        "       weighted: --traffic <traffic.json> | --sizes <kafka-log-dirs output> [--default-weight N] [--min-gain N] [--max-rounds N]\n"
         "writes the partitions whose preferred leader changes; exit status: 0 = ok, 1 = error or infeasible, 2 = usage\n");
     std::exit(2);
 }
@@ -86,12 +98,67 @@ int balance_cluster(const Cluster &cl, const std::string &cur_path, const std::s
     return ok ? 0 : 1;
 }
 
+// --traffic / --sizes: all topics together, every partition weighed (kao_balance_leaders_weighted)
+int balance_weighted(const Cluster &cl, const std::string &cur_path, const std::string &out_path, int device, const std::string &traffic_path,
+                     const std::string &sizes_path, bool have_default, uint64_t default_weight, uint64_t min_gain, int max_rounds, bool report) {
+    const ClusterRows cr = read_rows(cur_path, cl);
+    const int P = (int)cr.keys.size(), B = (int)cl.brokers.size(), W = cr.width;
+    const std::map<Key, uint64_t> known = traffic_path.empty() ? load_sizes(sizes_path) : load_traffic(traffic_path);
+    std::vector<uint64_t> weight((size_t)std::max(P, 1), 0);
+    std::vector<std::string> missing;
+    for (int p = 0; p < P; ++p) {
+        auto it = known.find(cr.keys[(size_t)p]);
+        if (it != known.end()) weight[(size_t)p] = it->second;
+        else if (have_default) weight[(size_t)p] = default_weight;
+        else missing.push_back(cr.keys[(size_t)p].first + "-" + std::to_string(cr.keys[(size_t)p].second));
+    }
+    if (!missing.empty()) {
+        std::string msg = "no weight for partitions ";
+        for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + missing[i];
+        if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
+        throw std::runtime_error(msg + " (name them in the file or set --default-weight)");
+    }
+    int rc = kao_init(device);
+    if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+    std::vector<uint16_t> rows = cr.rows;
+    int32_t n_changed = 0, status = 0;
+    uint64_t before = 0, after = 0, bound = 0;
+    int64_t stats[8] = {0};
+    rc = kao_balance_leaders_weighted(B, P, W, rows.data(), weight.data(), min_gain, max_rounds, 0, &n_changed, &before, &after, &bound, &status, stats);
+    if (rc) throw std::runtime_error(std::string("kao_balance_leaders_weighted: ") + kao_strerror(rc) + " " + kao_last_error());
+    if (report)
+        std::fprintf(stderr, "weighted: status=%s peak_before=%llu peak_after=%llu lower_bound=%llu leader_changes=%d rounds=%lld moves=%lld "
+                             "launches=%lld\n", status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP",
+                     (unsigned long long)before, (unsigned long long)after, (unsigned long long)bound, n_changed, (long long)stats[0],
+                     (long long)stats[1], (long long)stats[3]);
+    const std::string text = changed_rows_text(cr, rows, cl.brokers);
+    if (out_path.empty()) std::fputs(text.c_str(), stdout);
+    else {
+        std::ofstream f(out_path);
+        f << text;
+        if (!f) throw std::runtime_error("cannot write " + out_path);
+    }
+    kao_shutdown();
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     std::string cur_path, brokers_csv, racks_arg, out_path;
     int device = 0, slack0 = 0, cluster_lo = 0, cluster_hi = -1;
-    bool report = false, auto_slack = false, cluster = false;
+    bool report = false, auto_slack = false, cluster = false, have_slack = false, have_cluster_lo = false, have_cluster_hi = false;
+    std::string traffic_path, sizes_path;
+    bool have_traffic = false, have_sizes = false, have_default = false, have_gain = false, have_rounds = false;
+    uint64_t default_weight = 0, min_gain = 0;
+    int max_rounds = 0;
+    auto u64_arg = [](const std::string &v, uint64_t limit, const char *msg) {   // digits only, at most `limit`
+        if (v.empty() || v.size() > 20 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
+        errno = 0;
+        const unsigned long long x = std::strtoull(v.c_str(), nullptr, 10);
+        if (errno == ERANGE || x > limit) usage(msg);
+        return (uint64_t)x;
+    };
     auto count_arg = [](const std::string &v, const char *msg) {
         if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
         return std::atoi(v.c_str());
@@ -107,23 +174,36 @@ int main(int argc, char **argv) {
             const std::string v = need("--slack");
             if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage("--slack needs a value >= 0");
             slack0 = std::atoi(v.c_str());
+            have_slack = true;
         }
         else if (a == "--auto-slack") auto_slack = true;
         else if (a == "--cluster") cluster = true;
-        else if (a == "--cluster-lo") cluster_lo = count_arg(need("--cluster-lo"), "--cluster-lo needs a value >= 0");
-        else if (a == "--cluster-hi") { cluster_hi = count_arg(need("--cluster-hi"), "--cluster-hi needs a value >= 0"); cluster = true; }
+        else if (a == "--cluster-lo") { cluster_lo = count_arg(need("--cluster-lo"), "--cluster-lo needs a value >= 0"); have_cluster_lo = true; }
+        else if (a == "--cluster-hi") { cluster_hi = count_arg(need("--cluster-hi"), "--cluster-hi needs a value >= 0"); cluster = have_cluster_hi = true; }
+        else if (a == "--traffic") { traffic_path = need("--traffic"); have_traffic = true; }
+        else if (a == "--sizes") { sizes_path = need("--sizes"); have_sizes = true; }
+        else if (a == "--default-weight") { default_weight = u64_arg(need("--default-weight"), kMaxSize, "--default-weight needs a value 0..2^53"); have_default = true; }
+        else if (a == "--min-gain") { min_gain = u64_arg(need("--min-gain"), UINT64_MAX, "--min-gain needs a value 0..2^64-1"); have_gain = true; }
+        else if (a == "--max-rounds") { max_rounds = count_arg(need("--max-rounds"), "--max-rounds needs a value >= 0"); have_rounds = true; }
         else if (a == "--device") device = std::atoi(need("--device").c_str());
         else if (a == "--report") report = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown flag " + a).c_str());
     }
     if (cur_path.empty() || brokers_csv.empty() || racks_arg.empty()) usage("--current, --broker-list and --racks are required");
+    const bool weighted = have_traffic || have_sizes;
+    if (have_traffic && have_sizes) usage("give one of --traffic and --sizes");
+    if (weighted && (have_slack || auto_slack || cluster || have_cluster_lo || have_cluster_hi))
+        usage("--traffic / --sizes cannot be combined with --slack, --auto-slack, --cluster, --cluster-lo or --cluster-hi");
+    if (!weighted && (have_default || have_gain || have_rounds)) usage("--default-weight, --min-gain and --max-rounds need --traffic or --sizes");
     if (cluster_lo && !cluster) usage("--cluster-lo needs --cluster");
     if (cluster && auto_slack) usage("--auto-slack cannot be combined with --cluster");
     if (cluster && cluster_hi >= 0 && cluster_hi < cluster_lo) usage("--cluster-hi must be >= --cluster-lo");
     try {
         const Cluster cl = read_cluster(brokers_csv, racks_arg);
         const std::vector<int> &brokers = cl.brokers;
+        if (weighted)
+            return balance_weighted(cl, cur_path, out_path, device, traffic_path, sizes_path, have_default, default_weight, min_gain, max_rounds, report);
         if (cluster) return balance_cluster(cl, cur_path, out_path, device, slack0, cluster_lo, cluster_hi, report);
         const std::map<int, int> &dense = cl.dense;
         const std::vector<uint8_t> &rack_of = cl.rack_of;

@@ -1,0 +1,103 @@
+// kao_sizes.h -- what kao-waves and kao-leaders share: partition sizes read from `kafka-log-dirs --describe` output or a sizes
+// document (kao-waves --sizes, kao-leaders --sizes), and the traffic document of kao-leaders --traffic.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <map>
+#include <sstream>
+#include <stdexcept>
+#include <string>
+#include <utility>
+
+#include "kao_json.h"
+
+using Key = std::pair<std::string, int>;   // (topic, partition)
+
+constexpr uint64_t kMaxSize = uint64_t(1) << 53;   // JSON numbers are doubles here: exact up to 2^53, larger sizes are rejected
+
+inline uint64_t size_value(const JValue *v, const std::string &what) {
+    uint64_t x = 0;
+    if (!v || v->kind != JValue::Num || v->raw.empty() || v->raw.size() > 16 || v->raw.find_first_not_of("0123456789") != std::string::npos ||
+        (x = std::strtoull(v->raw.c_str(), nullptr, 10)) > kMaxSize)
+        throw std::runtime_error("sizes: " + what + ": size must be an integer 0..2^53");
+    return x;
+}
+
+// partition sizes, from `kafka-log-dirs --describe` output (the largest non-future replica; names split at the last '-') or from a
+// {"partitions":[{"topic","partition","size"}]} document
+inline std::map<Key, uint64_t> load_sizes(const std::string &path) {
+    const std::string txt = slurp(path);
+    JValue doc;
+    try {
+        doc = JParser(txt).parse();
+    } catch (const std::runtime_error &) {   // kafka-log-dirs prints status lines before its JSON line
+        std::istringstream in(txt);
+        std::string line;
+        bool found = false;
+        while (!found && std::getline(in, line)) {
+            const size_t b = line.find_first_not_of(" \t\r");
+            if (b != std::string::npos && line[b] == '{') { doc = JParser(line).parse(); found = true; }
+        }
+        if (!found) throw std::runtime_error("sizes: no JSON document found");
+    }
+    std::map<Key, uint64_t> out;
+    if (const JValue *brokers = doc.get("brokers")) {
+        for (auto &br : brokers->arr) {
+            const JValue *dirs = br.get("logDirs");
+            if (!dirs) continue;
+            for (auto &d : dirs->arr) {
+                const JValue *parts = d.get("partitions");
+                if (!parts) continue;
+                for (auto &e : parts->arr) {
+                    const JValue *fut = e.get("isFuture"), *name = e.get("partition");
+                    if (fut && fut->kind == JValue::Bool && fut->b) continue;
+                    if (!name || name->kind != JValue::Str) throw std::runtime_error("sizes: log-dir entry without a partition name");
+                    const size_t dash = name->str.rfind('-');
+                    const std::string idx = dash == std::string::npos ? "" : name->str.substr(dash + 1);
+                    if (dash == std::string::npos || dash == 0 || idx.empty() || idx.size() > 9 || idx.find_first_not_of("0123456789") != std::string::npos)
+                        throw std::runtime_error("sizes: partition name '" + name->str + "' is not <topic>-<partition>");
+                    const Key k{name->str.substr(0, dash), std::atoi(idx.c_str())};
+                    const uint64_t v = size_value(e.get("size"), name->str);
+                    auto it = out.find(k);
+                    if (it == out.end()) out[k] = v;
+                    else it->second = std::max(it->second, v);
+                }
+            }
+        }
+    } else if (const JValue *parts = doc.get("partitions")) {
+        for (auto &e : parts->arr) {
+            const JValue *t = e.get("topic"), *p = e.get("partition");
+            if (!t || !p) throw std::runtime_error("sizes: partition entry needs topic/partition/size");
+            const Key k{t->str, (int)p->num};
+            const std::string what = k.first + "-" + std::to_string(k.second);
+            if (out.count(k)) throw std::runtime_error("sizes: partition " + what + " listed twice");
+            out[k] = size_value(e.get("size"), what);
+        }
+    } else {
+        throw std::runtime_error("sizes: expected a \"brokers\" (kafka-log-dirs) or \"partitions\" document");
+    }
+    return out;
+}
+
+// partition weights from {"version":1,"partitions":[{"topic":..,"partition":..,"weight":N}]}: N an integer 0..2^53, no partition twice
+inline std::map<Key, uint64_t> load_traffic(const std::string &path) {
+    const std::string txt = slurp(path);
+    const JValue doc = JParser(txt).parse();
+    const JValue *parts = doc.get("partitions");
+    if (!parts || parts->kind != JValue::Arr) throw std::runtime_error("traffic: missing \"partitions\" array");
+    std::map<Key, uint64_t> out;
+    for (auto &e : parts->arr) {
+        const JValue *t = e.get("topic"), *p = e.get("partition"), *v = e.get("weight");
+        if (!t || !p) throw std::runtime_error("traffic: partition entry needs topic/partition/weight");
+        const Key k{t->str, (int)p->num};
+        const std::string what = k.first + "-" + std::to_string(k.second);
+        if (out.count(k)) throw std::runtime_error("traffic: partition " + what + " listed twice");
+        uint64_t x = 0;
+        if (!v || v->kind != JValue::Num || v->raw.empty() || v->raw.size() > 16 || v->raw.find_first_not_of("0123456789") != std::string::npos ||
+            (x = std::strtoull(v->raw.c_str(), nullptr, 10)) > kMaxSize)
+            throw std::runtime_error("traffic: " + what + ": weight must be an integer 0..2^53");
+        out[k] = x;
+    }
+    return out;
+}

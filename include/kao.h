@@ -520,6 +520,42 @@ int kao_balance_leaders_cluster(int32_t n_brokers, int32_t n_partitions, int32_t
                                 int32_t *n_changed, int32_t *peak_before, int32_t *peak_after, int32_t *status,
                                 int32_t stats[8] /* may be NULL */);
 
+/* ---- Leaders weighted by traffic -------------------------------------------------------------------------
+ * The entry points above count every partition as one unit; here partition p carries weight[p] (produce / fetch traffic, or its
+ * size on disk) and W(b) = the sum of weight[p] over the partitions b leads.  Rows as for kao_failover_order and
+ * kao_balance_leaders_cluster: `width` (1..KAO_MAX_RF) entries per partition over ONE broker index, all topics concatenated, row
+ * p = k_p >= 1 distinct dense indices < n_brokers, then KAO_NONE padding; slot 0 is the preferred leader.
+ * Minimising max_b W(b) is NP-hard, so this is a deterministic descent with a certificate.  Synchronous rounds on a leader slot
+ * j(p) per partition (0 at the start), each using the loads as they stand at its start: every partition with weight > 0 and
+ * k_p >= 2 takes b* = its other replica with the lowest W (ties: the lowest slot) and, a being its leader, proposes a -> b* iff
+ * W(b*) + weight[p] + min_gain < W(a); a proposal wins iff its key (0xFFFF - code(W(a))) << 48 | (0xFFFF - code(weight[p])) << 32 | p
+ * (code: a monotone 16-bit logarithmic code) is the lowest of all proposals that touch a and of all that touch b*; all winners are
+ * applied together; the rounds end when one has no proposal, or after max_rounds rounds (<= 0: no limit).  Every move lowers the
+ * sum of W^2 and leaves both loads below the old W(a): the rounds end and the peak never rises.
+ * Output rows: the input row with slots 0 and j(p) swapped, the other slots in place; no data moves.  dry_run != 0 leaves the rows
+ * untouched and reports the same numbers.  *n_changed = #{p : j(p) != 0}; *peak_before / *peak_after = max_b W(b) before / after.
+ * *lower_bound holds for ANY choice of leaders: with the brokers ranked by final load descending (ties: index ascending), m_p the
+ * largest rank in row p, A_k the weight of the rows with m_p < k and forced(b) the weight of the rows whose only replica is b, it
+ * is max(max_p weight[p], max_b forced(b), max_k ceil(A_k / k)).  *status = KAO_STATUS_OPTIMAL_PROVEN iff *peak_after ==
+ * *lower_bound (the peak is then optimal; the number of changes is not claimed minimal), else KAO_STATUS_FEASIBLE_BOUND_GAP; the
+ * return code is KAO_OK either way.  There is no seed: the result depends on the input alone.
+ * stats (may be NULL): [0] rounds that had a proposal, [1] moves applied, [2] proposals summed over the rounds, [3] kernel
+ * launches, [4] 1 = every round ran in one launch of a single workgroup (small inputs), [5] 1 = stopped by max_rounds with a
+ * proposal left, [6] the lowest k that attains the level-set term (0 when that term is below the bound), [7] brokers that lead a
+ * partition afterwards.  Checked on the host before any device is used: KAO_ERR_INVALID for a null pointer (stats excepted),
+ * width outside 1..KAO_MAX_RF, n_brokers outside 1..65534, n_partitions < 0, slot 0 not a broker, a broker after a KAO_NONE, an
+ * index >= n_brokers, a broker twice in one row, weights that sum to 2^62 or more; KAO_ERR_UNSUPPORTED for n_partitions * width >
+ * 4,000,000. */
+int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partitions, int32_t width,
+                                 uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *weight /* [n_partitions] */,
+                                 uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run,
+                                 int32_t *n_changed, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound,
+                                 int32_t *status, int64_t stats[8] /* may be NULL */);
+/* Test hook.  kao_balance_leaders_weighted picks its kernel path by size; this sets the calling thread's choice for its later calls:
+ * 0 = by size, 1 = the single workgroup (KAO_ERR_UNSUPPORTED from the call when the brokers do not fit its LDS), 2 = one launch
+ * pair per round.  Both paths give the same bytes.  Returns the previous choice, or KAO_ERR_INVALID. */
+int kao_wleaders_test_path(int32_t path);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

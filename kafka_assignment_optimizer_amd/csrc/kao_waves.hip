@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "kao_bytes_code.h"   // wave_bytes_code
 #include "kao_host.h"
 
 namespace {
@@ -56,14 +57,6 @@ __host__ __device__ inline uint32_t wave_salt(uint64_t seed, uint32_t o) {  // s
 __device__ inline uint64_t wave_key(uint32_t o, uint32_t p, uint32_t khi, uint32_t salt) {
     const uint32_t tie = o == 0 ? p : wave_mix32(p ^ salt);
     return (uint64_t)khi << 32 | tie;
-}
-
-// monotone 16-bit code of a byte count: 0 -> 0; otherwise (bit length e, 1..64) << 9 | the 9 bits below the leading one
-// (truncated), at most 64 << 9 | 511 = 33,279.  A logarithmic scale with a 9-bit mantissa, integer-only.
-__device__ inline uint32_t wave_bytes_code(uint64_t t) {
-    if (t == 0) return 0;
-    const int e = 64 - __clzll((long long)t);
-    return (uint32_t)e << 9 | (uint32_t)((t << (64 - e)) >> 54 & 0x1FFu);
 }
 
 // wavefront-aggregated atomics on the few global control words (one atomic per wavefront, all 64 lanes must be active)

@@ -12,6 +12,10 @@ topic is proven infeasible (no choice of leaders among its replicas meets the ba
 `--cluster` balances the leaders of all topics together instead (kao_balance_leaders_cluster): every topic
 keeps its band, and the largest number of partitions any broker leads over the whole cluster is made as low as leader changes alone
 can make it (or held to `--cluster-hi N`), every broker leading at least `--cluster-lo N`, with the fewest changes.
+
+`--traffic FILE` or `--sizes FILE` weighs every partition instead (kao_balance_leaders_weighted): the traffic a
+broker leads is made even by a deterministic descent over all topics together, and a lower bound computed beside it proves the peak
+optimal where the two meet (status OPTIMAL_PROVEN; FEASIBLE_BOUND_GAP otherwise, exit status 0 both times).
 """
 from __future__ import annotations
 
@@ -19,9 +23,10 @@ import argparse
 import ctypes as C
 import dataclasses
 import json
+import re
 import sys
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -30,6 +35,7 @@ from .model import NONE, Topic, topics_from_json
 from .solver import STATUS_NAMES, _check, _CTopics
 
 CLUSTER_STAT_KEYS = ("probes", "phases", "rounds", "paths", "longest_path", "launches", "pair_nodes", "unrouted")
+WEIGHTED_STAT_KEYS = ("rounds", "moves", "proposals", "launches", "single_workgroup", "stopped_by_max_rounds", "level_k", "leading_brokers")
 STAT_KEYS = ("phases", "rounds", "paths", "longest_path", "over_before", "under_before", "launches", "unrouted")
 
 
@@ -169,6 +175,143 @@ def cluster_report_line(res: ClusterLeaderResult) -> str:
             f"probes={s[0]} phases={s[1]} rounds={s[2]} paths={s[3]} longest_path={s[4]} launches={s[5]} pair_nodes={s[6]} unrouted={s[7]}")
 
 
+MAX_WEIGHT = 1 << 53   # weights above it are not exact as JSON doubles (the C++ reader): rejected, never rounded
+
+
+@dataclass
+class WeightedLeaderResult:
+    rows: np.ndarray         # [P, width] uint16: the input rows, slot 0 swapped with the chosen leader's slot (untouched with dry_run)
+    n_changed: int           # partitions whose preferred leader changes
+    peak_before: int         # the largest weight a broker leads in the input
+    peak_after: int          # ... in the chosen rows; never above peak_before
+    lower_bound: int         # no choice of leaders has a peak below it
+    status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound) | "FEASIBLE_BOUND_GAP"
+    stats: np.ndarray        # int64[8], see WEIGHTED_STAT_KEYS / include/kao.h
+
+
+@dataclass
+class WeightedLeaderPlan:
+    result: WeightedLeaderResult
+    keys: List[Tuple[str, int]]                                                # (topic, partition) per row
+    weight: np.ndarray                                                         # [P] uint64
+    entries: List[Tuple[str, int, List[int]]] = field(default_factory=list)   # (topic, partition, replicas as broker ids) of the changed rows
+    assignments: Optional[List[np.ndarray]] = None                            # per topic, when topics were given
+
+
+def balance_leaders_weighted_arrays(rows, n_brokers: int, weight, min_gain: int = 0, max_rounds: int = 0,
+                                    dry_run: bool = False) -> WeightedLeaderResult:
+    """kao_balance_leaders_weighted on dense rows ([P, width], NONE-padded, slot 0 = preferred leader) of all topics over one
+    broker index; weight[p] is the traffic of row p."""
+    r = np.array(rows, dtype=np.uint16, order="C")
+    if r.ndim != 2:
+        raise ValueError("rows must be a [P, width] array")
+    P, W = r.shape
+    wt = np.asarray(weight).reshape(-1)
+    if wt.shape != (P,):
+        raise ValueError(f"weight must hold one value per row ({P}), got {wt.shape[0]}")
+    if P and wt.dtype.kind not in "ui":
+        raise ValueError("weights must be integers")
+    if P and wt.dtype.kind == "i" and (wt < 0).any():
+        raise ValueError("weights must be >= 0")
+    if not 0 <= int(min_gain) < 1 << 64:
+        raise ValueError("min_gain must be 0..2^64-1")
+    wt = np.ascontiguousarray(wt, dtype=np.uint64)
+    flat = r.reshape(-1) if r.size else np.zeros(1, dtype=np.uint16)
+    wbuf = wt if P else np.zeros(1, dtype=np.uint64)
+    n, status = C.c_int32(0), C.c_int32(0)
+    before, after, bound = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    stats = np.zeros(8, dtype=np.int64)
+    _check(_ffi.load().kao_balance_leaders_weighted(int(n_brokers), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                                    wbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(min_gain), int(max_rounds), int(bool(dry_run)),
+                                                    C.byref(n), C.byref(before), C.byref(after), C.byref(bound), C.byref(status),
+                                                    stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_leaders_weighted")
+    return WeightedLeaderResult(rows=r, n_changed=int(n.value), peak_before=int(before.value), peak_after=int(after.value),
+                                lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats)
+
+
+def _weight_value(v, what):
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= MAX_WEIGHT:
+        raise ValueError(f"traffic: {what}: weight must be an integer 0..2^53, got {v!r}")
+    return v
+
+
+def parse_traffic(doc) -> Dict[Tuple[str, int], int]:
+    """{(topic, partition): weight} from {"version":1,"partitions":[{"topic":..,"partition":..,"weight":N}]}; N is an integer
+    0..2^53, a partition listed twice is an error."""
+    parts = doc.get("partitions") if isinstance(doc, dict) else None
+    if not isinstance(parts, list):
+        raise ValueError('traffic: missing "partitions" array')
+    out: Dict[Tuple[str, int], int] = {}
+    for e in parts:
+        if not isinstance(e, dict) or "topic" not in e or "partition" not in e:
+            raise ValueError("traffic: partition entry needs topic/partition/weight")
+        key = (str(e["topic"]), int(e["partition"]))
+        if key in out:
+            raise ValueError(f"traffic: partition {key[0]}-{key[1]} listed twice")
+        out[key] = _weight_value(e.get("weight"), f"{key[0]}-{key[1]}")
+    return out
+
+
+def weights_for(keys, table: Dict[Tuple[str, int], int], default_weight: Optional[int] = None) -> np.ndarray:
+    """weight[p] over `keys`.  A partition the table does not name takes `default_weight`; without one it is a ValueError naming
+    the first few such partitions."""
+    weight = np.zeros(len(keys), dtype=np.uint64)
+    missing = []
+    for i, key in enumerate(keys):
+        if key in table:
+            weight[i] = table[key]
+        elif default_weight is None:
+            missing.append(f"{key[0]}-{key[1]}")
+        else:
+            weight[i] = default_weight
+    if missing:
+        more = f" and {len(missing) - 5} more" if len(missing) > 5 else ""
+        raise ValueError(f"no weight for partitions {', '.join(missing[:5])}{more} (name them in the file or set --default-weight)")
+    return weight
+
+
+def _plan_weighted(keys, rows, broker_ids, weight, min_gain, max_rounds, dry_run) -> WeightedLeaderPlan:
+    res = balance_leaders_weighted_arrays(rows, len(broker_ids), weight, min_gain, max_rounds, dry_run)
+    changed = np.nonzero((res.rows != rows).any(axis=1))[0]
+    entries = [(keys[p][0], keys[p][1], [int(broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
+    return WeightedLeaderPlan(result=res, keys=list(keys), weight=np.asarray(weight, dtype=np.uint64), entries=entries)
+
+
+def balance_leaders_weighted(topics: Sequence[Topic], weights, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False,
+                             assignments=None, default_weight: Optional[int] = None) -> WeightedLeaderPlan:
+    """kao_balance_leaders_weighted on topics that share one broker index (broker_ids); rows = `assignments`, default each topic's
+    current; topics of different RF are padded.  `weights` is {(topic name, partition id): weight} (partitions it does not name
+    take `default_weight`) or one array per topic.  Returns the per-topic assignments and the plan entries of the changed rows."""
+    from .failover import _from_topics
+    topics = list(topics)
+    if not topics:
+        raise ValueError("no topic given")
+    if len({t.name for t in topics}) != len(topics):
+        raise ValueError("topic names must be distinct")
+    fi = _from_topics(topics, assignments)
+    if isinstance(weights, dict):
+        weight = weights_for(fi.keys, weights, default_weight)
+    else:
+        per = [np.asarray(w).reshape(-1) for w in weights]
+        if len(per) != len(topics) or any(len(w) != t.n_partitions for w, t in zip(per, topics)):
+            raise ValueError("weights: one array of n_partitions values per topic")
+        weight = np.concatenate(per)
+    plan = _plan_weighted(fi.keys, fi.rows, fi.broker_ids, weight, min_gain, max_rounds, dry_run)
+    plan.assignments, at = [], 0
+    for i, t in enumerate(topics):
+        w = t.current.shape[1] if assignments is None else np.asarray(assignments[i]).reshape(t.n_partitions, -1).shape[1]
+        plan.assignments.append(plan.result.rows[at:at + t.n_partitions, :w].copy())
+        at += t.n_partitions
+    return plan
+
+
+def weighted_report_line(res: WeightedLeaderResult) -> str:
+    """The --traffic / --sizes --report text, as cli/kao-leaders prints it."""
+    s = res.stats
+    return (f"weighted: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
+            f"leader_changes={res.n_changed} rounds={s[0]} moves={s[1]} launches={s[3]}")
+
+
 def plan_text(entries) -> str:
     """The reassignment document of [(topic, partition, replicas)], byte for byte as cli/kao-leaders writes it."""
     rows = ['    {"topic":"%s","partition":%d,"replicas":[%s]}' % (t.replace("\\", "\\\\").replace('"', '\\"'), p, ",".join(str(b) for b in r))
@@ -192,12 +335,42 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--slack", type=int, default=0, help="widen the leader band by N on both sides")
+    def count(text):   # as cli/kao-leaders reads a count: digits only
+        if not re.fullmatch(r"[0-9]{1,9}", text):
+            raise argparse.ArgumentTypeError("needs a value >= 0")
+        return int(text)
+
+    def u64(text):
+        if not re.fullmatch(r"[0-9]{1,20}", text) or int(text) >= 1 << 64:
+            raise argparse.ArgumentTypeError("needs a value 0..2^64-1")
+        return int(text)
+
+    def weight_arg(text):
+        if not re.fullmatch(r"[0-9]{1,16}", text) or int(text) > MAX_WEIGHT:
+            raise argparse.ArgumentTypeError("needs a value 0..2^53")
+        return int(text)
+
+    ap.add_argument("--slack", type=int, default=None, help="widen the leader band by N on both sides")
     ap.add_argument("--auto-slack", action="store_true", help="use the smallest slack >= --slack that is feasible, per topic")
     ap.add_argument("--cluster", action="store_true", help="balance the leaders of all topics together: lowest cluster-wide peak, topic bands kept")
-    ap.add_argument("--cluster-lo", type=int, default=0, help="with --cluster: every broker leads at least N partitions")
-    ap.add_argument("--cluster-hi", type=int, default=-1, help="every broker leads at most N partitions instead of the lowest peak; implies --cluster")
+    ap.add_argument("--cluster-lo", type=int, default=None, help="with --cluster: every broker leads at least N partitions")
+    ap.add_argument("--cluster-hi", type=int, default=None, help="every broker leads at most N partitions instead of the lowest peak; implies --cluster")
+    ap.add_argument("--traffic", default=None, help='weigh the partitions: {"version":1,"partitions":[{"topic":..,"partition":..,"weight":N}]}')
+    ap.add_argument("--sizes", default=None, help="weigh the partitions by their size: kafka-log-dirs --describe output")
+    ap.add_argument("--default-weight", type=weight_arg, default=None, help="weight of the partitions the file does not name")
+    ap.add_argument("--min-gain", type=u64, default=None, help="weighted: a leader moves only when it lowers its broker's lead over the target by more than N")
+    ap.add_argument("--max-rounds", type=count, default=None, help="weighted: stop after N rounds")
     a = ap.parse_args(argv)
+    weighted = a.traffic is not None or a.sizes is not None
+    if a.traffic is not None and a.sizes is not None:
+        ap.error("give one of --traffic and --sizes")
+    if weighted and (a.slack is not None or a.auto_slack or a.cluster or a.cluster_lo is not None or a.cluster_hi is not None):
+        ap.error("--traffic / --sizes cannot be combined with --slack, --auto-slack, --cluster, --cluster-lo or --cluster-hi")
+    if not weighted and (a.default_weight is not None or a.min_gain is not None or a.max_rounds is not None):
+        ap.error("--default-weight, --min-gain and --max-rounds need --traffic or --sizes")
+    a.slack = 0 if a.slack is None else a.slack
+    a.cluster_lo = 0 if a.cluster_lo is None else a.cluster_lo
+    a.cluster_hi = -1 if a.cluster_hi is None else a.cluster_hi
     if a.slack < 0:
         ap.error("--slack must be >= 0")
     cluster = a.cluster or a.cluster_hi != -1
@@ -213,6 +386,29 @@ def main(argv=None) -> int:
     try:
         with open(a.current) as f:
             doc = json.load(f)
+        if weighted:
+            from .failover import parse_current
+            fi = parse_current(doc, [int(b) for b in a.broker_list.split(",") if b], _racks(a.racks))   # input errors before the device is touched
+            if a.traffic is not None:
+                with open(a.traffic) as f:
+                    table = parse_traffic(json.load(f))
+            else:
+                from .waves import parse_sizes
+                with open(a.sizes) as f:
+                    table = parse_sizes(f.read())
+            weight = weights_for(fi.keys, table, a.default_weight)
+            from .solver import init
+            init(a.device)
+            plan = _plan_weighted(fi.keys, fi.rows, fi.broker_ids, weight, a.min_gain or 0, a.max_rounds or 0, False)
+            if a.report:
+                print(weighted_report_line(plan.result), file=sys.stderr)
+            text = plan_text(plan.entries)
+            if a.out:
+                with open(a.out, "w") as f:
+                    f.write(text)
+            else:
+                sys.stdout.write(text)
+            return 0
         if cluster:
             from .failover import parse_current
             fi = parse_current(doc, [int(b) for b in a.broker_list.split(",") if b], _racks(a.racks))   # input errors before the device is touched
