@@ -1,5 +1,6 @@
-// kao_sizes.h -- what kao-waves and kao-leaders share: partition sizes read from `kafka-log-dirs --describe` output or a sizes
-// document (kao-waves --sizes, kao-leaders --sizes), and the traffic document of kao-leaders --traffic.
+// kao_sizes.h -- what kao-waves, kao-leaders and kao-failover share: partition sizes read from `kafka-log-dirs --describe` output or a
+// sizes document (kao-waves --sizes, kao-leaders --sizes, kao-failover --sizes), and the traffic document of kao-leaders --traffic and
+// kao-failover --traffic.
 #pragma once
 #include <algorithm>
 #include <cstdint>

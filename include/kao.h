@@ -556,6 +556,44 @@ int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partitions, int32_
  * pair per round.  Both paths give the same bytes.  Returns the previous choice, or KAO_ERR_INVALID. */
 int kao_wleaders_test_path(int32_t path);
 
+/* ---- Failover weighted by traffic -----------------------------------------------------------------------
+ * kao_failover_order counts every orphaned partition as one unit; here partition p carries weight[p] (a uint64_t; the weights sum
+ * to less than 2^62).  Rows, scopes, the scenarios D_g, the scenario a partition belongs to, its eligible slots E_p, OFFLINE /
+ * AFFECTED and e(p) are exactly those of kao_failover_order.  Wlead(b) = the sum of weight[p] over the partitions with
+ * rows[p][0] == b.  For scenario g a choice gives each affected p a slot j(p) in E_p, L_g(b) = Wlead(b) + the sum of weight[p] over
+ * the affected p of g with rows[p][j(p)] == b, and peak_g = max of L_g(b) over b not in D_g (0 when no broker survives).
+ * Minimising peak_g is restricted-assignment makespan with fixed base loads (NP-hard), so every scenario runs, independently, the
+ * deterministic descent of kao_balance_leaders_weighted on L_g, with a lower bound computed beside it.  Start: j = e.  A round uses
+ * the loads as they stand at its start: every affected p with weight[p] > 0 and |E_p| >= 2 takes b* = its eligible broker other than
+ * the current one a = rows[p][j(p)] with the lowest L_g (ties: the lowest slot) and proposes a -> b* iff
+ * L_g(b*) + weight[p] + min_gain < L_g(a); a proposal wins iff its key (0xFFFF - code(L_g(a))) << 48 |
+ * (0xFFFF - code(weight[p])) << 32 | p (p = the row index, code as in section 4k) is the lowest of all proposals of the round that
+ * touch a and of all that touch b*; all winners are applied together.  A scenario ends when a round has no proposal, or after
+ * max_rounds rounds of that scenario (<= 0: no limit).  Every move lowers the sum of L_g^2 and leaves both loads below the old
+ * L_g(a): the rounds end and the peak never rises.
+ * Output rows: for every p with j(p) != e(p) the slots e(p) and j(p) are swapped; nothing else moves, slot 0 never moves, no data
+ * moves.  dry_run != 0 leaves the rows untouched and reports the same numbers.  There is no seed.
+ * The lower bound of scenario g holds for ANY choice of slots: with T_g = the surviving brokers eligible for at least one affected
+ * partition, ranked by final L_g descending (ties: index ascending), m_p = the largest rank among p's eligible brokers and
+ * A_k = the Wlead of the brokers of rank < k + the weight of the affected p with m_p < k, it is the maximum of: Wlead(b) over the
+ * surviving b; weight[p] + the smallest Wlead among p's eligible brokers, over the affected p; Wlead(b) + the weight of the
+ * partitions whose only eligible broker is b, over b in T_g; ceil(A_k / k) for k = 1..|T_g|.
+ * scen[6g .. 6g+5] = {affected, offline, peak_before, peak_after, lower_bound, reordered}, reordered = #{p : j(p) != e(p)} (not
+ * claimed minimal); a scenario without an affected partition reports peak_before = peak_after = lower_bound = the survivors' largest
+ * Wlead (0 when no broker survives).  *n_reordered = the sum of reordered.  *status = KAO_STATUS_OPTIMAL_PROVEN iff peak_after ==
+ * lower_bound in every scenario, else KAO_STATUS_FEASIBLE_BOUND_GAP; the return code is KAO_OK either way.
+ * stats (may be NULL): [0] scenarios with an affected partition, [1] rounds that had a proposal, summed over the scenarios,
+ * [2] moves applied, [3] proposals, summed, [4] kernel launches, [5] scenarios stopped by max_rounds with a proposal left,
+ * [6] scenarios with peak_after == lower_bound (those without an affected partition included), [7] the most rounds any one scenario
+ * ran.  Checked on the host before any device is used: everything kao_failover_order checks, with the same limits (4,000,000 slots,
+ * KAO_FAILOVER_MAX_BROKERS: the load and one key word per broker, 16 bytes, live in the LDS of the scenario's workgroup), and
+ * KAO_ERR_INVALID for weight == NULL, status == NULL or weights that sum to 2^62 or more. */
+int kao_failover_order_weighted(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
+                                uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *weight /* [n_partitions] */,
+                                int32_t scope, uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run,
+                                uint64_t *scen /* [n_scen*6] */, int32_t *n_reordered, int32_t *status,
+                                int64_t stats[8] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

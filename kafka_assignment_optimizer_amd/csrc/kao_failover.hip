@@ -5,6 +5,7 @@
 // leader of p down, the slot e(p) = the first eligible follower inherits p.  Choosing another eligible slot j(p) and swapping it
 // with e(p) moves no data.  For a cap M on every surviving broker's leaders, scenario g is a min-cost flow: each affected partition
 // sends one unit to a broker of an eligible slot (cost 0 for e(p), 1 otherwise), broker b takes at most M - lead[b] units.
+// (the first three kernels and the host-side checks live in kao_failover_dev.h, shared with kao_wfailover.hip)
 //   k_fo_classify  one pass over the partitions: lead[], the scenario of p, its eligible slots, e(p), the scenarios' sizes
 //   k_fo_offsets   exclusive scan of the sizes (one workgroup)
 //   k_fo_scatter   the affected partitions bucketed by scenario (counting sort; the order inside a bucket is not used)
@@ -31,77 +32,15 @@
 #include <cstdint>
 #include <string>
 
-#include "kao_host.h"
+#include "kao_failover_dev.h"
 
 namespace {
 
-constexpr int kFoThreads = 256;         // the passes over partitions
-constexpr int kFoSoloSmall = 256;       // lanes of a scenario's workgroup while the largest scenario has at most kFoSmallSlots slots
-constexpr int kFoSoloLarge = 1024;
-constexpr int kFoSmallSlots = 1024;
-constexpr int kFoMaxBrokers = KAO_FAILOVER_MAX_BROKERS;   // 16 bytes of LDS per broker + the bitmap: 129,000 of 163,840 bytes
 constexpr uint32_t kFoInf = 0xFFFFFFFFu;
 constexpr uint32_t kFoSource = 1u << 30;   // distance 0, no arc
 constexpr uint32_t kFoNoPred = 0xFFFFFFFFu;
-enum { FS_SCEN = 0, FS_PROBES = 1, FS_PHASES = 2, FS_ROUNDS = 3, FS_PATHS = 4, FS_MAXLEN = 5, FS_REORDERED = 6, FS_ERR = 7, FS_MAXN = 8, FS_N = 16 };
 enum { SH_FLAG = 0, SH_LEFT = 1, SH_DMIN = 2, SH_AUG = 3, SH_MAXLEN = 4, SH_MAXLEAD = 5, SH_SUMLEAD = 6, SH_ALIVE = 7, SH_PEAK = 8,
        SH_CNT = 9, SH_ERR = 10, SH_N = 16 };
-
-__device__ __forceinline__ bool fo_dead(int b, int g, int scope, const uint8_t *__restrict__ rack_of) {
-    return scope == 0 ? b == g : rack_of[b] == g;
-}
-
-// meta[p] = e(p) | eligible slots << 8 (e = 0: offline); scen_of[p]; lead[]; the scenarios' affected / offline counts
-__global__ void k_fo_classify(int P, int W, int scope, const uint16_t *__restrict__ rows, const uint8_t *__restrict__ rack_of,
-                              int32_t *__restrict__ lead, int32_t *__restrict__ scen_of, uint16_t *__restrict__ meta,
-                              uint8_t *__restrict__ cur, int32_t *__restrict__ claim, int32_t *__restrict__ cnt, int32_t *__restrict__ off) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    const uint16_t *row = rows + (size_t)p * W;
-    const int l = row[0], g = scope == 0 ? l : rack_of[l];
-    int mask = 0, e = 0;
-    for (int j = W - 1; j >= 1; --j) {
-        const int b = row[j];
-        if (b != KAO_NONE && !fo_dead(b, g, scope, rack_of)) { mask |= 1 << j; e = j; }
-    }
-    atomicAdd(&lead[l], 1);
-    scen_of[p] = g;
-    meta[p] = (uint16_t)(e | (mask << 8));
-    cur[p] = (uint8_t)e;
-    claim[p] = 0;
-    atomicAdd(e ? &cnt[g] : &off[g], 1);
-}
-
-// start[g] = sum of cnt[0..g), fill[g] = 0; ctl[FS_MAXN] = the largest cnt.  One workgroup.
-__global__ __launch_bounds__(1024) void k_fo_offsets(int G, const int32_t *__restrict__ cnt, int32_t *__restrict__ start,
-                                                      int32_t *__restrict__ fill, int32_t *__restrict__ ctl) {
-    __shared__ int32_t part[1024];
-    __shared__ int32_t mx;
-    const int tid = threadIdx.x, NT = blockDim.x, per = (G + NT - 1) / NT, lo = min(tid * per, G), hi = min(lo + per, G);
-    if (tid == 0) mx = 0;
-    __syncthreads();
-    int s = 0, m = 0;
-    for (int g = lo; g < hi; ++g) { s += cnt[g]; m = max(m, cnt[g]); }
-    part[tid] = s;
-    if (m) atomicMax(&mx, m);
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int i = 0; i < NT; ++i) { const int v = part[i]; part[i] = acc; acc += v; }
-        ctl[FS_MAXN] = mx;
-    }
-    __syncthreads();
-    s = part[tid];
-    for (int g = lo; g < hi; ++g) { start[g] = s; fill[g] = 0; s += cnt[g]; }
-}
-
-__global__ void k_fo_scatter(int P, const int32_t *__restrict__ scen_of, const uint16_t *__restrict__ meta, const int32_t *__restrict__ start,
-                             int32_t *__restrict__ fill, int32_t *__restrict__ list) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P || (meta[p] & 0xFF) == 0) return;
-    const int g = scen_of[p];
-    list[start[g] + atomicAdd(&fill[g], 1)] = p;
-}
 
 // tail, head and cost of the arc of local slot i of the scenario (partition list[i / W], slot i % W); false when there is none
 __device__ __forceinline__ bool fo_arc(int i, int W, bool costed, const int32_t *__restrict__ list, const uint16_t *__restrict__ rows,
@@ -337,51 +276,12 @@ __global__ __launch_bounds__(kFoSoloLarge) void k_fo_solve(int B, int W, int sco
     }
 }
 
-// the device memory and the stream of one call, handed back to the runtime's pools on every return path
-struct FoBufs {
-    void *arena = nullptr;
-    size_t cap = 0;
-    hipStream_t stream = nullptr;
-    ~FoBufs() {
-        if (stream) { (void)hipStreamSynchronize(stream); stream_put(stream, cur_device()); }
-        if (arena) arena_put(arena, cap, cur_device());
-    }
-};
-
-int validate_failover(int32_t B, int32_t R, const uint8_t *rack_of, int32_t P, int32_t W, const uint16_t *rows, int32_t scope,
-                      const int32_t *scen, const int32_t *n_reordered) {
-    const std::string fn = "kao_failover_order: ";
-    if (!rack_of || !rows || !scen || !n_reordered) return fail(KAO_ERR_INVALID, fn + "null pointer");
-    if (scope < 0 || scope > 1) return fail(KAO_ERR_INVALID, fn + "scope must be 0 (brokers) or 1 (racks)");
-    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, fn + "width outside 1.." + std::to_string(KAO_MAX_RF));
-    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, fn + "n_brokers outside 1..65534");
-    if (R < 1 || R > KAO_MAX_RACKS) return fail(KAO_ERR_INVALID, fn + "n_racks outside 1.." + std::to_string(KAO_MAX_RACKS));
-    if (P < 0) return fail(KAO_ERR_INVALID, fn + "n_partitions < 0");
-    if ((int64_t)P * W > 4000000) return fail(KAO_ERR_UNSUPPORTED, fn + "more than 4,000,000 replica slots");
-    if (B > kFoMaxBrokers) return fail(KAO_ERR_UNSUPPORTED, fn + "more than " + std::to_string(kFoMaxBrokers) + " brokers (the node state of a scenario lives in LDS)");
-    for (int b = 0; b < B; ++b)
-        if (rack_of[b] >= R) return fail(KAO_ERR_INVALID, fn + "rack_of[" + std::to_string(b) + "] >= n_racks");
-    for (int64_t p = 0; p < P; ++p) {
-        const uint16_t *row = rows + p * W;
-        const std::string at = fn + "partition " + std::to_string(p) + ": ";
-        if (row[0] == KAO_NONE) return fail(KAO_ERR_INVALID, at + "slot 0 holds no broker");
-        bool ended = false;
-        for (int i = 0; i < W; ++i) {
-            if (row[i] == KAO_NONE) { ended = true; continue; }
-            if (ended) return fail(KAO_ERR_INVALID, at + "a broker after an empty slot");
-            if (row[i] >= B) return fail(KAO_ERR_INVALID, at + "broker index >= n_brokers");
-            for (int j = 0; j < i; ++j)
-                if (row[j] == row[i]) return fail(KAO_ERR_INVALID, at + "broker repeated in a row");
-        }
-    }
-    return KAO_OK;
-}
 
 }  // namespace
 
 extern "C" int kao_failover_order(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
                                   uint16_t *rows, int32_t scope, int32_t dry_run, int32_t *scen, int32_t *n_reordered, int32_t stats[8]) {
-    int rc = validate_failover(n_brokers, n_racks, rack_of, n_partitions, width, rows, scope, scen, n_reordered);
+    int rc = validate_failover("kao_failover_order: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, scope, scen, n_reordered);
     if (rc) return rc;
     if ((rc = require_init())) return rc;
     const int B = n_brokers, P = n_partitions, W = width, G = scope == 0 ? n_brokers : n_racks;

@@ -10,12 +10,17 @@ data and changes no preferred leader (kao-waves puts the whole plan in one wave)
 one broker index: the load a failure shifts is a cluster quantity.  Balance the preferred leaders first (kao-leaders), then run
 this.  The answer is exact per scenario: peak_after is the lowest peak any follower order reaches, reordered the fewest swaps that
 reach it.
+
+`--traffic FILE` or `--sizes FILE` weighs every partition instead (kao_failover_order_weighted): the peak is
+the traffic a surviving broker leads after the failure, every scenario runs a deterministic descent, and a lower bound computed
+beside it proves the scenario's peak optimal where the two meet.
 """
 from __future__ import annotations
 
 import argparse
 import ctypes as C
 import json
+import re
 import sys
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -24,10 +29,12 @@ import numpy as np
 
 from . import _ffi
 from .model import NONE, Topic
-from .solver import _check
+from .solver import STATUS_NAMES, _check
 
 STAT_KEYS = ("scenarios", "probes", "phases", "rounds", "paths", "longest_path", "launches", "largest_scenario")
 SCEN_KEYS = ("affected", "offline", "peak_before", "peak_after", "reordered")
+WEIGHTED_STAT_KEYS = ("scenarios", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven_scenarios", "most_rounds")
+WEIGHTED_SCEN_KEYS = ("affected", "offline", "peak_before", "peak_after", "lower_bound", "reordered")
 SCOPES = {"broker": 0, "rack": 1, 0: 0, 1: 1}
 
 
@@ -37,6 +44,15 @@ class FailoverResult:
     scen: np.ndarray         # [n_scen, 5] int32, see SCEN_KEYS; n_scen = n_brokers (scope 0) or n_racks (scope 1)
     n_reordered: int         # rows that changed (would change with dry_run): the sum of scen[:, 4]
     stats: np.ndarray        # int32[8], see STAT_KEYS / include/kao.h
+
+
+@dataclass
+class WeightedFailoverResult:
+    rows: np.ndarray         # [P, width] uint16: the input rows, e(p) swapped with the chosen slot (the input rows with dry_run)
+    scen: np.ndarray         # [n_scen, 6] uint64, see WEIGHTED_SCEN_KEYS
+    n_reordered: int         # rows that changed (would change with dry_run): the sum of scen[:, 5]
+    status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound in every scenario) | "FEASIBLE_BOUND_GAP"
+    stats: np.ndarray        # int64[8], see WEIGHTED_STAT_KEYS / include/kao.h
 
 
 @dataclass
@@ -51,9 +67,10 @@ class FailoverInput:
 
 @dataclass
 class FailoverPlan:
-    result: FailoverResult
+    result: FailoverResult        # a WeightedFailoverResult from the weighted entry points
     input: FailoverInput
     scope: int
+    weight: Optional[np.ndarray] = None   # [P] uint64 per row (weighted plans)
     entries: List[Tuple[str, int, List[int]]] = field(default_factory=list)   # (topic, partition, replicas as broker ids) of the reordered rows
     assignments: Optional[List[np.ndarray]] = None                           # per topic, when topics were given
 
@@ -84,6 +101,42 @@ def failover_order_arrays(rows, n_brokers: int, rack_of, n_racks: int, scope, dr
                                           flat.ctypes.data_as(C.POINTER(C.c_uint16)), scope, int(bool(dry_run)), scen.ctypes.data_as(i32),
                                           C.byref(n), stats.ctypes.data_as(i32)), "kao_failover_order")
     return FailoverResult(rows=r, scen=scen[:n_scen], n_reordered=int(n.value), stats=stats)
+
+
+def failover_order_weighted_arrays(rows, n_brokers: int, rack_of, n_racks: int, scope, weight, min_gain: int = 0, max_rounds: int = 0,
+                                   dry_run: bool = False) -> WeightedFailoverResult:
+    """kao_failover_order_weighted on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); weight[p] is the traffic of
+    row p."""
+    scope = _scope(scope)
+    r = np.array(rows, dtype=np.uint16, order="C")
+    if r.ndim != 2:
+        raise ValueError("rows must be a [P, width] array")
+    rk = np.ascontiguousarray(rack_of, dtype=np.uint8)
+    if rk.shape != (int(n_brokers),):
+        raise ValueError(f"rack_of must hold one rack per broker ({n_brokers}), got shape {rk.shape}")
+    P, W = r.shape
+    wt = np.asarray(weight).reshape(-1)
+    if wt.shape != (P,):
+        raise ValueError(f"weight must hold one value per row ({P}), got {wt.shape[0]}")
+    if P and wt.dtype.kind not in "ui":
+        raise ValueError("weights must be integers")
+    if P and wt.dtype.kind == "i" and (wt < 0).any():
+        raise ValueError("weights must be >= 0")
+    if not 0 <= int(min_gain) < 1 << 64:
+        raise ValueError("min_gain must be 0..2^64-1")
+    wt = np.ascontiguousarray(wt, dtype=np.uint64)
+    flat = r.reshape(-1) if r.size else np.zeros(1, dtype=np.uint16)
+    wbuf = wt if P else np.zeros(1, dtype=np.uint64)
+    n_scen = int(n_brokers) if scope == 0 else int(n_racks)
+    scen = np.zeros((max(n_scen, 1), 6), dtype=np.uint64)
+    stats = np.zeros(8, dtype=np.int64)
+    n, status = C.c_int32(0), C.c_int32(0)
+    _check(_ffi.load().kao_failover_order_weighted(int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W),
+                                                   flat.ctypes.data_as(C.POINTER(C.c_uint16)), wbuf.ctypes.data_as(C.POINTER(C.c_uint64)), scope,
+                                                   int(min_gain), int(max_rounds), int(bool(dry_run)), scen.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   C.byref(n), C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))),
+           "kao_failover_order_weighted")
+    return WeightedFailoverResult(rows=r, scen=scen[:n_scen], n_reordered=int(n.value), status=STATUS_NAMES[int(status.value)], stats=stats)
 
 
 def parse_current(doc: dict, broker_list: Sequence[int], racks: dict) -> FailoverInput:
@@ -180,6 +233,65 @@ def plan_input(fi: FailoverInput, scope, dry_run: bool = False) -> FailoverPlan:
     return FailoverPlan(result=res, input=fi, scope=scope, entries=entries)
 
 
+def plan_input_weighted(fi: FailoverInput, scope, weight, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> FailoverPlan:
+    """kao_failover_order_weighted on a FailoverInput, weight[p] per row of it; the entries are the rows that changed."""
+    scope = _scope(scope)
+    res = failover_order_weighted_arrays(fi.rows, len(fi.broker_ids), fi.rack_of, len(fi.rack_names), scope, weight, min_gain, max_rounds, dry_run)
+    changed = np.nonzero((res.rows != fi.rows).any(axis=1))[0]
+    entries = [(fi.keys[p][0], fi.keys[p][1], [int(fi.broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
+    return FailoverPlan(result=res, input=fi, scope=scope, weight=np.asarray(weight, dtype=np.uint64), entries=entries)
+
+
+def failover_order_weighted(topics_or_doc, scope, weights, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, *, broker_list=None,
+                            racks=None, assignments=None, default_weight: Optional[int] = None) -> FailoverPlan:
+    """kao_failover_order_weighted on a whole cluster, given as for failover_order.  `weights` is {(topic name, partition id): weight}
+    (partitions it does not name take `default_weight`; without one they are an error) or, with topics, one array per topic."""
+    from .leaders import weights_for
+    scope = _scope(scope)
+    topics = None
+    if isinstance(topics_or_doc, dict):
+        if broker_list is None or racks is None:
+            raise ValueError("a reassignment document needs broker_list and racks")
+        fi = parse_current(topics_or_doc, broker_list, racks)
+    else:
+        topics = list(topics_or_doc)
+        if not topics:
+            raise ValueError("no topic given")
+        if len({t.name for t in topics}) != len(topics):
+            raise ValueError("topic names must be distinct")
+        fi = _from_topics(topics, assignments)
+    if isinstance(weights, dict):
+        weight = weights_for(fi.keys, weights, default_weight)
+    else:
+        per = [np.asarray(w).reshape(-1) for w in weights]
+        if topics is None or len(per) != len(topics) or any(len(w) != t.n_partitions for w, t in zip(per, topics)):
+            raise ValueError("weights: a table, or with topics one array of n_partitions values per topic")
+        weight = np.concatenate(per)
+    plan = plan_input_weighted(fi, scope, weight, min_gain, max_rounds, dry_run)
+    if topics is not None:
+        plan.assignments, at = [], 0
+        for i, t in enumerate(topics):
+            w = t.current.shape[1] if assignments is None else np.asarray(assignments[i]).reshape(t.n_partitions, -1).shape[1]
+            plan.assignments.append(plan.result.rows[at:at + t.n_partitions, :w].copy())
+            at += t.n_partitions
+    return plan
+
+
+def weighted_report_lines(plan: FailoverPlan) -> List[str]:
+    """The --traffic / --sizes --report text, line for line as cli/kao-failover prints it."""
+    fi, res = plan.input, plan.result
+    scen, s = [[int(x) for x in row] for row in res.scen.tolist()], res.stats
+    out = []
+    for g, (aff, off, before, after, bound, re_) in enumerate(scen):
+        if aff or off:
+            name = str(int(fi.broker_ids[g])) if plan.scope == 0 else fi.rack_names[g]
+            out.append(f"scenario={name} affected={aff} offline={off} peak_before={before} peak_after={after} lower_bound={bound} reordered={re_}")
+    out.append(f"weighted: scope={'broker' if plan.scope == 0 else 'rack'} scenarios={len(scen)} worst_peak_before={max(r[2] for r in scen)} "
+               f"worst_peak_after={max(r[3] for r in scen)} worst_lower_bound={max(r[4] for r in scen)} proven={s[6]} "
+               f"offline={sum(r[1] for r in scen)} reordered={res.n_reordered} rounds={s[1]} moves={s[2]} launches={s[4]}")
+    return out
+
+
 def report_lines(plan: FailoverPlan) -> List[str]:
     """The --report text, line for line as cli/kao-failover prints it."""
     fi, scen = plan.input, plan.result.scen
@@ -202,7 +314,7 @@ def _racks(arg: str) -> dict:
 
 def main(argv=None) -> int:
     """Python twin of cli/kao-failover: same flags, same bytes, same exit status (0 ok, 1 error, 2 usage)."""
-    from .leaders import plan_text
+    from .leaders import MAX_WEIGHT, parse_traffic, plan_text, weights_for
     ap = argparse.ArgumentParser(prog="kao-failover", description="follower order that keeps the peak leader count after a failure lowest; moves no data")
     ap.add_argument("--current", required=True, help="reassignment JSON of the cluster as it is")
     ap.add_argument("--broker-list", required=True, help="brokers of the cluster, CSV")
@@ -212,16 +324,54 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
+
+    def count(text):   # as cli/kao-failover reads a count: digits only
+        if not re.fullmatch(r"[0-9]{1,9}", text):
+            raise argparse.ArgumentTypeError("needs a value >= 0")
+        return int(text)
+
+    def u64(text):
+        if not re.fullmatch(r"[0-9]{1,20}", text) or int(text) >= 1 << 64:
+            raise argparse.ArgumentTypeError("needs a value 0..2^64-1")
+        return int(text)
+
+    def weight_arg(text):
+        if not re.fullmatch(r"[0-9]{1,16}", text) or int(text) > MAX_WEIGHT:
+            raise argparse.ArgumentTypeError("needs a value 0..2^53")
+        return int(text)
+
+    ap.add_argument("--traffic", default=None, help='weigh the partitions: {"version":1,"partitions":[{"topic":..,"partition":..,"weight":N}]}')
+    ap.add_argument("--sizes", default=None, help="weigh the partitions by their size: kafka-log-dirs --describe output")
+    ap.add_argument("--default-weight", type=weight_arg, default=None, help="weight of the partitions the file does not name")
+    ap.add_argument("--min-gain", type=u64, default=None, help="weighted: an heir changes only when that closes a gap of more than N")
+    ap.add_argument("--max-rounds", type=count, default=None, help="weighted: stop every scenario after N rounds")
     a = ap.parse_args(argv)
+    weighted = a.traffic is not None or a.sizes is not None
+    if a.traffic is not None and a.sizes is not None:
+        ap.error("give one of --traffic and --sizes")
+    if not weighted and (a.default_weight is not None or a.min_gain is not None or a.max_rounds is not None):
+        ap.error("--default-weight, --min-gain and --max-rounds need --traffic or --sizes")
     try:
         with open(a.current) as f:
             doc = json.load(f)
         fi = parse_current(doc, [int(b) for b in a.broker_list.split(",") if b], _racks(a.racks))   # input errors before the device is touched
+        if weighted:
+            if a.traffic is not None:
+                with open(a.traffic) as f:
+                    table = parse_traffic(json.load(f))
+            else:
+                from .waves import parse_sizes
+                with open(a.sizes) as f:
+                    table = parse_sizes(f.read())
+            weight = weights_for(fi.keys, table, a.default_weight)
         from .solver import init
         init(a.device)
-        plan = plan_input(fi, a.scope, a.dry_run)
+        if weighted:
+            plan = plan_input_weighted(fi, a.scope, weight, a.min_gain or 0, a.max_rounds or 0, a.dry_run)
+        else:
+            plan = plan_input(fi, a.scope, a.dry_run)
         if a.report:
-            for line in report_lines(plan):
+            for line in weighted_report_lines(plan) if weighted else report_lines(plan):
                 print(line, file=sys.stderr)
         text = plan_text(plan.entries)
         if a.out:
