@@ -5,14 +5,16 @@
 // leader of p down, the slot e(p) = the first eligible follower inherits p.  Choosing another eligible slot j(p) and swapping it
 // with e(p) moves no data.  For a cap M on every surviving broker's leaders, scenario g is a min-cost flow: each affected partition
 // sends one unit to a broker of an eligible slot (cost 0 for e(p), 1 otherwise), broker b takes at most M - lead[b] units.
-// (the first three kernels and the host-side checks live in kao_failover_dev.h, shared with kao_wfailover.hip)
+// (the first three kernels, the host function that runs them and the host-side checks live in kao_failover_dev.h, shared with
+// kao_wfailover.hip)
 //   k_fo_classify  one pass over the partitions: lead[], the scenario of p, its eligible slots, e(p), the scenarios' sizes
 //   k_fo_offsets   exclusive scan of the sizes (one workgroup)
 //   k_fo_scatter   the affected partitions bucketed by scenario (counting sort; the order inside a bucket is not used)
 //   k_fo_solve     ONE WORKGROUP PER SCENARIO, all scenarios in one launch: bisection on M between the lower end
 //                  max(max lead, ceil(leaders left / brokers left)) and peak_before, every probe a max-flow from the start state
 //                  j = e, then one min-cost solve at peak_after, then the swaps
-// A solve at cap M is successive shortest paths as in kao_leaders.hip, on the residual graph whose arcs are never stored: partition
+// A solve at cap M is successive shortest paths as in kao_leaders.hip (but with 32-bit keys in LDS, below: not the 64-bit flow keys
+// of kao_plan_dev.h), on the residual graph whose arcs are never stored: partition
 // p on slot c = cur[p] gives rows[p][c] -> rows[p][j] for every other eligible slot j, cost -1 when j == e(p), +1 when c == e(p),
 // 0 otherwise (all 0 in a probe).  room[b] = M - lead[b] - inherit(b): negative = excess (sources), positive = free capacity.
 // A PHASE:
@@ -276,7 +278,6 @@ __global__ __launch_bounds__(kFoSoloLarge) void k_fo_solve(int B, int W, int sco
     }
 }
 
-
 }  // namespace
 
 extern "C" int kao_failover_order(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
@@ -287,56 +288,35 @@ extern "C" int kao_failover_order(int32_t n_brokers, int32_t n_racks, const uint
     const int B = n_brokers, P = n_partitions, W = width, G = scope == 0 ? n_brokers : n_racks;
     const size_t PW = (size_t)P * W;
 
-    FoBufs m;
     // one arena: ctl i32[FS_N] | lead i32[B] | cnt, off i32[G] (zeroed up to here) | start, fill i32[G] | scen i32[5G] | scen_of i32[P] |
     //            list i32[P] | claim i32[P] | rows u16[PW] | meta u16[P] | cur u8[P] | rack_of u8[B]
-    const size_t o_ctl = 0, o_lead = o_ctl + align_up(FS_N * 4), o_cnt = o_lead + align_up((size_t)B * 4), o_off = o_cnt + align_up((size_t)G * 4),
-                 o_start = o_off + align_up((size_t)G * 4), o_fill = o_start + align_up((size_t)G * 4), o_scen = o_fill + align_up((size_t)G * 4),
-                 o_sof = o_scen + align_up((size_t)G * 20), o_list = o_sof + align_up((size_t)P * 4), o_claim = o_list + align_up((size_t)P * 4),
-                 o_rows = o_claim + align_up((size_t)P * 4), o_meta = o_rows + align_up(PW * 2), o_cur = o_meta + align_up((size_t)P * 2),
-                 o_rack = o_cur + align_up((size_t)P), total = o_rack + align_up((size_t)B);
-    if ((rc = arena_get(total, &m.arena, &m.cap))) return rc;
-    if ((rc = stream_get(&m.stream))) return rc;
+    Carve cv;
+    const size_t o_ctl = cv.take<int32_t>(FS_N), o_lead = cv.take<int32_t>(B), o_cnt = cv.take<int32_t>(G), o_off = cv.take<int32_t>(G),
+                 zeroed = cv.end(), o_start = cv.take<int32_t>(G), o_fill = cv.take<int32_t>(G), o_scen = cv.take<int32_t>(5 * (size_t)G),
+                 o_sof = cv.take<int32_t>(P), o_list = cv.take<int32_t>(P), o_claim = cv.take<int32_t>(P), o_rows = cv.take<uint16_t>(PW),
+                 o_meta = cv.take<uint16_t>(P), o_cur = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
-    unsigned char *db = static_cast<unsigned char *>(m.arena);
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(db + o); };
-    int32_t *d_ctl = i32(o_ctl), *d_lead = i32(o_lead), *d_cnt = i32(o_cnt), *d_off = i32(o_off), *d_start = i32(o_start), *d_fill = i32(o_fill),
-            *d_scen = i32(o_scen), *d_sof = i32(o_sof), *d_list = i32(o_list), *d_claim = i32(o_claim);
-    uint16_t *d_rows = reinterpret_cast<uint16_t *>(db + o_rows), *d_meta = reinterpret_cast<uint16_t *>(db + o_meta);
-    uint8_t *d_cur = db + o_cur, *d_rack = db + o_rack;
+    const FoScen d{m.at<int32_t>(o_lead), m.at<int32_t>(o_sof), m.at<int32_t>(o_cnt), m.at<int32_t>(o_off), m.at<int32_t>(o_start), m.at<int32_t>(o_fill),
+                   m.at<int32_t>(o_list), m.at<int32_t>(o_claim), m.at<int32_t>(o_ctl), m.at<uint16_t>(o_meta), m.at<uint8_t>(o_cur)};
+    int32_t *d_scen = m.at<int32_t>(o_scen);
+    uint16_t *d_rows = m.at<uint16_t>(o_rows);
+    uint8_t *d_rack = m.at<uint8_t>(o_rack);
 
-    HIP_TRY(hipMemsetAsync(db, 0, o_start, st));
+    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
     HIP_TRY(hipMemcpyAsync(d_rack, rack_of, (size_t)B, hipMemcpyHostToDevice, st));
     if (P) HIP_TRY(hipMemcpyAsync(d_rows, rows, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    const unsigned pblocks = (unsigned)((P + kFoThreads - 1) / kFoThreads);
     int32_t launches = 0, ctl[FS_N] = {0};
-    if (P) {
-        k_fo_classify<<<pblocks, kFoThreads, 0, st>>>(P, W, scope, d_rows, d_rack, d_lead, d_sof, d_meta, d_cur, d_claim, d_cnt, d_off);
-        ++launches;
-    }
-    k_fo_offsets<<<1, 1024, 0, st>>>(G, d_cnt, d_start, d_fill, d_ctl);
-    ++launches;
-    if (P) {
-        k_fo_scatter<<<pblocks, kFoThreads, 0, st>>>(P, d_sof, d_meta, d_start, d_fill, d_list);
-        ++launches;
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int max_n = ctl[FS_MAXN];
-    const int threads = (int64_t)max_n * W <= kFoSmallSlots ? kFoSoloSmall : kFoSoloLarge;
+    int max_n = 0, threads = 0;
     const size_t lds = (size_t)B * 16 + (size_t)((B + 31) / 32) * 4;
-    static int lds_set[kMaxDevices] = {0};   // the largest dynamic LDS size the kernel has been opened for, per device
-    const int dev = cur_device();
-    if (lds > 48 * 1024 && dev >= 0 && dev < kMaxDevices && (int)lds > lds_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fo_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set[dev] = (int)lds;
-    }
-    k_fo_solve<<<(unsigned)G, threads, lds, st>>>(B, W, scope, dry_run, d_rows, d_rack, d_lead, d_meta, d_cur, d_claim, d_cnt, d_off, d_start,
-                                                 d_list, d_scen, d_ctl);
+    if ((rc = fo_prelude(st, P, W, G, scope, d_rows, d_rack, d, reinterpret_cast<const void *>(k_fo_solve), lds, 48 * 1024, &launches, &max_n, &threads)))
+        return rc;
+    k_fo_solve<<<(unsigned)G, threads, lds, st>>>(B, W, scope, dry_run, d_rows, d_rack, d.lead, d.meta, d.cur, d.claim, d.cnt, d.off, d.start,
+                                                 d.list, d_scen, d.ctl);
     HIP_TRY(hipGetLastError());
     ++launches;
-    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctl, d.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(scen, d_scen, (size_t)G * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (ctl[FS_ERR]) return fail(KAO_ERR_HIP, "kao_failover_order: a solve did not settle");

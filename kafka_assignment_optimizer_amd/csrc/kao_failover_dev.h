@@ -1,7 +1,7 @@
 // kao_failover_dev.h -- what kao_failover_order (kao_failover.hip) and kao_failover_order_weighted
-// (kao_wfailover.hip, section 4l) share: the scenario model's passes over the partitions (classify, offsets, scatter), the host-side
-// checks of the arguments and the holder of one call's device memory.  Included by those two .hip files only: everything sits in an
-// unnamed namespace, so each gets its own copy of the kernels.
+// (kao_wfailover.hip, section 4l) share: the scenario model's passes over the partitions (classify, offsets, scatter), the host
+// function that runs them (fo_prelude) and the host-side checks of the arguments.  Included by those two .hip files only: everything
+// sits in an unnamed namespace, so each gets its own copy of the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,44 +75,54 @@ __global__ void k_fo_scatter(int P, const int32_t *__restrict__ scen_of, const u
     list[start[g] + atomicAdd(&fill[g], 1)] = p;
 }
 
-// the device memory and the stream of one call, handed back to the runtime's pools on every return path
-struct FoBufs {
-    void *arena = nullptr;
-    size_t cap = 0;
-    hipStream_t stream = nullptr;
-    ~FoBufs() {
-        if (stream) { (void)hipStreamSynchronize(stream); stream_put(stream, cur_device()); }
-        if (arena) arena_put(arena, cap, cur_device());
-    }
+// The scenarios of one call on the device: classify, offsets and scatter enqueued on `st` and awaited.  *max_n = the affected
+// partitions of the largest scenario, *threads = the lanes of a scenario's workgroup for it.  `solve` is the caller's scenario kernel,
+// opened here for `lds` bytes of dynamic LDS when that is more than `lds_free` (what a launch may ask for unopened) and more than it
+// has been opened for on this device.
+struct FoScen {
+    int32_t *lead, *scen_of, *cnt, *off, *start, *fill, *list, *claim, *ctl;   // [B], [P], [G] x 4, [P], [P], [FS_N]
+    uint16_t *meta;                                                            // [P]
+    uint8_t *cur;                                                              // [P]
 };
-
+int fo_prelude(hipStream_t st, int P, int W, int G, int scope, const uint16_t *d_rows, const uint8_t *d_rack, const FoScen &d, const void *solve,
+               size_t lds, size_t lds_free, int *launches, int *max_n, int *threads) {
+    const unsigned pblocks = grid_for(P, kFoThreads);
+    if (P) {
+        k_fo_classify<<<pblocks, kFoThreads, 0, st>>>(P, W, scope, d_rows, d_rack, d.lead, d.scen_of, d.meta, d.cur, d.claim, d.cnt, d.off);
+        ++*launches;
+    }
+    k_fo_offsets<<<1, 1024, 0, st>>>(G, d.cnt, d.start, d.fill, d.ctl);
+    ++*launches;
+    if (P) {
+        k_fo_scatter<<<pblocks, kFoThreads, 0, st>>>(P, d.scen_of, d.meta, d.start, d.fill, d.list);
+        ++*launches;
+    }
+    HIP_TRY(hipGetLastError());
+    int32_t ctl[FS_N];
+    HIP_TRY(hipMemcpyAsync(ctl, d.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *max_n = ctl[FS_MAXN];
+    *threads = (int64_t)*max_n * W <= kFoSmallSlots ? kFoSoloSmall : kFoSoloLarge;
+    static int lds_set[kMaxDevices] = {0};   // the largest dynamic LDS size the kernel has been opened for, per device
+    const int dev = cur_device();
+    if (lds > lds_free && dev >= 0 && dev < kMaxDevices && (int)lds > lds_set[dev]) {
+        HIP_TRY(hipFuncSetAttribute(solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set[dev] = (int)lds;
+    }
+    return KAO_OK;
+}
 
 int validate_failover(const std::string &fn, int32_t B, int32_t R, const uint8_t *rack_of, int32_t P, int32_t W, const uint16_t *rows, int32_t scope,
                       const void *scen, const int32_t *n_reordered) {
     if (!rack_of || !rows || !scen || !n_reordered) return fail(KAO_ERR_INVALID, fn + "null pointer");
     if (scope < 0 || scope > 1) return fail(KAO_ERR_INVALID, fn + "scope must be 0 (brokers) or 1 (racks)");
-    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, fn + "width outside 1.." + std::to_string(KAO_MAX_RF));
-    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, fn + "n_brokers outside 1..65534");
-    if (R < 1 || R > KAO_MAX_RACKS) return fail(KAO_ERR_INVALID, fn + "n_racks outside 1.." + std::to_string(KAO_MAX_RACKS));
-    if (P < 0) return fail(KAO_ERR_INVALID, fn + "n_partitions < 0");
-    if ((int64_t)P * W > 4000000) return fail(KAO_ERR_UNSUPPORTED, fn + "more than 4,000,000 replica slots");
+    int rc = check_dims(fn, B, P, W, R);
+    if (!rc) rc = check_slot_cap(fn, P, W);
+    if (rc) return rc;
     if (B > kFoMaxBrokers) return fail(KAO_ERR_UNSUPPORTED, fn + "more than " + std::to_string(kFoMaxBrokers) + " brokers (the node state of a scenario lives in LDS)");
     for (int b = 0; b < B; ++b)
         if (rack_of[b] >= R) return fail(KAO_ERR_INVALID, fn + "rack_of[" + std::to_string(b) + "] >= n_racks");
-    for (int64_t p = 0; p < P; ++p) {
-        const uint16_t *row = rows + p * W;
-        const std::string at = fn + "partition " + std::to_string(p) + ": ";
-        if (row[0] == KAO_NONE) return fail(KAO_ERR_INVALID, at + "slot 0 holds no broker");
-        bool ended = false;
-        for (int i = 0; i < W; ++i) {
-            if (row[i] == KAO_NONE) { ended = true; continue; }
-            if (ended) return fail(KAO_ERR_INVALID, at + "a broker after an empty slot");
-            if (row[i] >= B) return fail(KAO_ERR_INVALID, at + "broker index >= n_brokers");
-            for (int j = 0; j < i; ++j)
-                if (row[j] == row[i]) return fail(KAO_ERR_INVALID, at + "broker repeated in a row");
-        }
-    }
-    return KAO_OK;
+    return check_rows(fn, B, P, W, rows);
 }
 
 }  // namespace

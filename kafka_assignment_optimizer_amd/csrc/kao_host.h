@@ -13,6 +13,10 @@
 //   kao_lp_fan.cpp   ONE LP sharded over several devices (lp_open_fan, kao_lp_sharded_test)
 //   kao_capped.cpp   kao_solve_capped: Lagrangian prices over kao_solve / kao_solve_multi, through the C ABI only
 //   kao_pairs.cpp    compound edges of leader-balanced pairs for KAO-CX;  kao_round.cpp  KAO-LP's primal side: the iterate rounded to an assignment
+//   kao_waves.hip    kao_plan_waves(_sized): a reassignment plan split into waves
+//   kao_leaders.hip, kao_leaders_cluster.hip, kao_wleaders.hip, kao_failover.hip, kao_wfailover.hip  the one-shot planners of leaders
+//                    and follower orders (kernels and entry point in one file each; device code they share: kao_plan_dev.h, the
+//                    failover scenario passes: kao_failover_dev.h; host code they share: "one-shot planner calls" below)
 // Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -83,6 +87,59 @@ void arena_drop_all();
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // LDS / register form of a replica: internal (rack-major) index | rack << 16, m = the largest rack
 inline uint32_t replica_word(uint16_t x, int m) { return x == KAO_NONE ? kNoneW : ((uint32_t)x | ((uint32_t)(x / m) << 16)); }
+
+// ---- one-shot planner calls (kao_runtime.cpp): what the leader and failover planners share on the host ----
+// The device memory and the stream of one call, handed back to the runtime's pools on every return path.
+struct CallBufs {
+    void *arena = nullptr;
+    size_t cap = 0;
+    hipStream_t stream = nullptr;
+    CallBufs() = default;
+    CallBufs(const CallBufs &) = delete;
+    CallBufs &operator=(const CallBufs &) = delete;
+    int open(size_t bytes);   // arena_get, then stream_get
+    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(static_cast<unsigned char *>(arena) + off); }
+    ~CallBufs();              // synchronises the stream
+};
+// The layout of one call's arena: take<T>(count) is the offset of the next buffer, each one aligned to 256 bytes; end() is where the
+// next one would start (the total, or the end of a prefix that one memset or copy covers).
+struct Carve {
+    size_t next = 0;
+    template <class T> size_t take(size_t count) { const size_t o = next; next += align_up(count * sizeof(T)); return o; }
+    size_t end() const { return next; }
+};
+inline unsigned grid_for(int64_t n, int threads) { return (unsigned)((std::max<int64_t>(n, 1) + threads - 1) / threads); }
+// Argument checks; `fn` is the text in front of every message ("kao_...: ").  check_dims: width, brokers, racks (of the calls that
+// have them), partitions, in that order.  check_row: slot 0 holds a broker, no broker after an empty slot, every index below
+// n_brokers, no broker twice; check_rows: every row.
+int check_dims(const std::string &fn, int32_t B, int32_t P, int32_t W, int32_t R = 1);
+int check_slot_cap(const std::string &fn, int32_t P, int32_t W);   // 4,000,000 replica slots
+int check_row(const std::string &fn, int32_t B, int32_t W, int64_t p, const uint16_t *row);
+int check_rows(const std::string &fn, int32_t B, int32_t P, int32_t W, const uint16_t *rows);
+int check_weight_sum(const std::string &fn, int32_t P, const uint64_t *weight);   // below 2^62: every load of the kernels stays below 2^63
+// The relaxation rounds of one phase of successive shortest paths (kao_plan_dev.h: flow keys): launch(r, flag) enqueues round r,
+// whose kernel sets *flag when it changed a key.  kSettleBatch rounds are enqueued between two reads of the flags (the seed kernel
+// cleared them for the first batch); `rounds` counts up to and including the first round that changed nothing.  N = the nodes: keys
+// settle within N rounds.
+constexpr int kSettleBatch = 8;
+template <class Launch>
+int settle_rounds(const char *fn, hipStream_t st, int N, int32_t *d_flags, int32_t &rounds, int32_t &launches, Launch launch) {
+    int32_t flags[kSettleBatch];
+    for (int r = 0, settled = 0; !settled;) {
+        if (r > N + kSettleBatch) return fail(KAO_ERR_HIP, std::string(fn) + "relaxation did not settle");
+        if (r) { HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof flags, st)); }
+        for (int i = 0; i < kSettleBatch; ++i, ++r) launch(r, d_flags + i);
+        launches += kSettleBatch;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int i = 0; i < kSettleBatch && !settled; ++i) {   // the first round that changed nothing ends the phase's rounds
+            ++rounds;
+            settled = flags[i] == 0;
+        }
+    }
+    return KAO_OK;
+}
 
 // ---- the model on the host (kao_model.cpp) ----
 int validate(const kao_topic *t);

@@ -25,7 +25,7 @@
 // The loop ends with no excess left (the flow is a min-cost flow: OPTIMAL_PROVEN) or with such a phase (INFEASIBLE_PROVEN).
 // Two regimes: topics of at most kLeadSoloSlots replica slots and kLeadSoloNodes nodes run the whole solve in ONE workgroup with the
 // node state in LDS (k_lead_solo); larger ones launch one kernel per relaxation round over all arcs, the host reading the rounds'
-// "changed" flags every kLeadBatch rounds.
+// "changed" flags every kSettleBatch rounds (settle_rounds, kao_host.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +33,7 @@
 #include <string>
 
 #include "kao_host.h"
+#include "kao_plan_dev.h"   // the 64-bit flow keys, lane_count_to, swap_leader
 
 namespace {
 
@@ -40,17 +41,8 @@ constexpr int kLeadThreads = 256;        // per-round launches
 constexpr int kLeadSoloThreads = 1024;   // the persistent workgroup
 constexpr int kLeadSoloNodes = 2048;     // B + 1 nodes whose state fits the persistent kernel's LDS (28 bytes per node)
 constexpr int kLeadSoloSlots = 1 << 16;  // replica slots up to which one workgroup runs the whole solve
-constexpr int kLeadBatch = 8;            // rounds enqueued between two reads of the "changed" flags
-constexpr unsigned long long kLeadInf = ~0ull;
-constexpr unsigned long long kLeadSource = (unsigned long long)(1u << 30) << 32;   // distance 0, no arc
-constexpr uint32_t kLeadNoPred = 0xFFFFFFFFu;
 enum { LC_PHASES = 0, LC_ROUNDS = 1, LC_PATHS = 2, LC_MAXLEN = 3, LC_OVER = 4, LC_UNDER = 5, LC_LAUNCHES = 6, LC_LEFT = 7,
        LC_CHANGED = 8, LC_AUG = 9, LC_SUMF = 10, LC_ERR = 11, LC_N = 16 };
-
-// key of the head of an arc of cost c whose tail has key ku
-__device__ __forceinline__ unsigned long long lead_step(unsigned long long ku, int c) {
-    return ku + ((unsigned long long)(long long)c << 32) + 1ull;
-}
 
 // tail, head and cost of the arc of slot s = p * RF + j; false when j is the leader's slot (no arc)
 __device__ __forceinline__ bool lead_arc(int s, int RF, const uint16_t *__restrict__ rows, const uint8_t *lead, int &u, int &v, int &c) {
@@ -58,73 +50,66 @@ __device__ __forceinline__ bool lead_arc(int s, int RF, const uint16_t *__restri
     if (j == l) return false;
     u = rows[p * RF + l];
     v = rows[s];
-    c = j == 0 ? -1 : (l == 0 ? 1 : 0);
+    c = flow_slot_cost(j, l, true);
     return true;
-}
-
-__device__ __forceinline__ void lead_seed(int v, const int32_t *e, unsigned long long *k0, unsigned long long *k1, uint32_t *pred) {
-    const unsigned long long k = e[v] > 0 ? kLeadSource : kLeadInf;
-    k0[v] = k;
-    k1[v] = k;
-    pred[v] = kLeadNoPred;
 }
 
 // one Jacobi round, the part of slot s: X is read, Y takes the bids
 __device__ __forceinline__ bool lead_relax_slot(int s, int RF, const uint16_t *__restrict__ rows, const uint8_t *lead,
-                                                const unsigned long long *X, unsigned long long *Y) {
+                                                const u64 *X, u64 *Y) {
     int u, v, c;
     if (!lead_arc(s, RF, rows, lead, u, v, c)) return false;
-    const unsigned long long ku = X[u];
-    if (ku == kLeadInf) return false;
-    const unsigned long long nk = lead_step(ku, c);
+    const u64 ku = X[u];
+    if (ku == kFlowInf) return false;
+    const u64 nk = flow_step(ku, c);
     if (nk >= X[v]) return false;
     atomicMin(&Y[v], nk);
     return true;
 }
 
 // ... the part of node v (v == B: the sink, which only bids its own key)
-__device__ __forceinline__ bool lead_relax_node(int v, int B, int lo, int hi, const int32_t *f, const unsigned long long *X,
-                                                unsigned long long *Y) {
-    const unsigned long long kv = X[v];
-    if (kv != kLeadInf) atomicMin(&Y[v], kv);
+__device__ __forceinline__ bool lead_relax_node(int v, int B, int lo, int hi, const int32_t *f, const u64 *X,
+                                                u64 *Y) {
+    const u64 kv = X[v];
+    if (kv != kFlowInf) atomicMin(&Y[v], kv);
     if (v == B) return false;
-    const unsigned long long kt = X[B];
-    bool ch = false;
-    if (f[v] < hi && kv != kLeadInf && kv + 1 < kt) { atomicMin(&Y[B], kv + 1); ch = true; }
-    if (f[v] > lo && kt != kLeadInf && kt + 1 < kv) { atomicMin(&Y[v], kt + 1); ch = true; }
+    const u64 kt = X[B];
+    bool ch = false;   // (the two bids spelled out: through lc_bid of kao_leaders_cluster.hip the same tests compile to other code here)
+    if (f[v] < hi && kv != kFlowInf && kv + 1 < kt) { atomicMin(&Y[B], kv + 1); ch = true; }
+    if (f[v] > lo && kt != kFlowInf && kt + 1 < kv) { atomicMin(&Y[v], kt + 1); ch = true; }
     return ch;
 }
 
 // predecessor bids: arc ids are s for the partition arcs, PRF + b for b -> T, PRF + B for T -> b
 __device__ __forceinline__ void lead_pred_slot(int s, int RF, const uint16_t *__restrict__ rows, const uint8_t *lead,
-                                               const unsigned long long *K, uint32_t *pred) {
+                                               const u64 *K, uint32_t *pred) {
     int u, v, c;
     if (!lead_arc(s, RF, rows, lead, u, v, c)) return;
-    const unsigned long long ku = K[u];
-    if (ku != kLeadInf && lead_step(ku, c) == K[v]) atomicMin(&pred[v], (uint32_t)s);
+    const u64 ku = K[u];
+    if (ku != kFlowInf && flow_step(ku, c) == K[v]) atomicMin(&pred[v], (uint32_t)s);
 }
 
-__device__ __forceinline__ void lead_pred_node(int b, int B, int PRF, int lo, int hi, const int32_t *f, const unsigned long long *K,
+__device__ __forceinline__ void lead_pred_node(int b, int B, int PRF, int lo, int hi, const int32_t *f, const u64 *K,
                                                uint32_t *pred) {
-    const unsigned long long kb = K[b], kt = K[B];
-    if (f[b] < hi && kb != kLeadInf && kb + 1 == kt) atomicMin(&pred[B], (uint32_t)(PRF + b));
-    if (f[b] > lo && kt != kLeadInf && kt + 1 == kb) atomicMin(&pred[b], (uint32_t)(PRF + B));
+    const u64 kb = K[b], kt = K[B];
+    if (f[b] < hi && kb != kFlowInf && kb + 1 == kt) atomicMin(&pred[B], (uint32_t)(PRF + b));
+    if (f[b] > lo && kt != kFlowInf && kt + 1 == kb) atomicMin(&pred[b], (uint32_t)(PRF + B));
 }
 
 // Step 3 of a phase, one lane: returns the paths augmented, *maxlen the longest of them in arcs.
 __device__ __forceinline__ int lead_extract(int P, int RF, int B, int lo, int hi, int32_t stamp, const uint16_t *__restrict__ rows,
-                                            uint8_t *lead, int32_t *claim, const unsigned long long *K, const uint32_t *pred,
+                                            uint8_t *lead, int32_t *claim, const u64 *K, const uint32_t *pred,
                                             int32_t *e, int32_t *f, int32_t *maxlen) {
     const int PRF = P * RF;
     int naug = 0;
     for (int t = 0; t <= B; ++t) {
-        while (e[t] < 0 && K[t] != kLeadInf) {
+        while (e[t] < 0 && K[t] != kFlowInf) {
             bool ok = true;
             int v = t, steps = 0;
             while ((uint32_t)K[v] != 0u) {   // arcs on the way here: 0 at the path's first node
                 const uint32_t a = pred[v];
                 int u = 0;
-                if (a == kLeadNoPred || ++steps > B + 1) { ok = false; break; }   // (a tight path always has its predecessors)
+                if (a == kFlowNoPred || ++steps > B + 1) { ok = false; break; }   // (a tight path always has its predecessors)
                 if (a < (uint32_t)PRF) {
                     const int p = (int)a / RF;
                     if (claim[p] == stamp) { ok = false; break; }
@@ -170,9 +155,7 @@ __device__ __forceinline__ int lead_extract(int P, int RF, int B, int lo, int hi
 __device__ __forceinline__ bool lead_swap(int p, int RF, uint16_t *rows, const uint8_t *lead) {
     const int l = lead[p];
     if (l == 0) return false;
-    const uint16_t a = rows[p * RF], b = rows[p * RF + l];
-    rows[p * RF] = b;
-    rows[p * RF + l] = a;
+    swap_leader(rows + p * RF, l);
     return true;
 }
 
@@ -180,7 +163,7 @@ __device__ __forceinline__ bool lead_swap(int p, int RF, uint16_t *rows, const u
 __global__ __launch_bounds__(kLeadSoloThreads) void k_lead_solo(int P, int RF, int B, int lo, int hi, uint16_t *__restrict__ rows,
                                                                 uint8_t *__restrict__ lead, int32_t *__restrict__ claim,
                                                                 int32_t *__restrict__ ctl) {
-    __shared__ unsigned long long key0[kLeadSoloNodes], key1[kLeadSoloNodes];
+    __shared__ u64 key0[kLeadSoloNodes], key1[kLeadSoloNodes];
     __shared__ uint32_t pred[kLeadSoloNodes];
     __shared__ int32_t e[kLeadSoloNodes], f[kLeadSoloNodes];
     __shared__ int32_t sh[LC_N];
@@ -211,13 +194,13 @@ __global__ __launch_bounds__(kLeadSoloThreads) void k_lead_solo(int P, int RF, i
     int phases = 0, rounds = 0, paths = 0;
     while (sh[LC_LEFT] > 0) {
         ++phases;
-        for (int v = tid; v < N; v += NT) lead_seed(v, e, key0, key1, pred);
+        for (int v = tid; v < N; v += NT) flow_seed(v, e, key0, key1, pred);
         __syncthreads();
         for (int r = 0;; ++r) {
             if (tid == 0) sh[LC_AUG] = 0;
             __syncthreads();
-            const unsigned long long *X = (r & 1) ? key1 : key0;
-            unsigned long long *Y = (r & 1) ? key0 : key1;
+            const u64 *X = (r & 1) ? key1 : key0;
+            u64 *Y = (r & 1) ? key0 : key1;
             bool ch = false;
             for (int s = tid; s < PRF; s += NT) ch |= lead_relax_slot(s, RF, rows, lead, X, Y);
             for (int v = tid; v < N; v += NT) ch |= lead_relax_node(v, B, lo, hi, f, X, Y);
@@ -285,20 +268,20 @@ __global__ void k_lead_start(int P, int B, int lo, int hi, int32_t *__restrict__
     atomicAdd(&e[B], b == 0 ? fb - P : fb);
 }
 
-__global__ void k_lead_seed(int B, const int32_t *__restrict__ e, unsigned long long *__restrict__ k0, unsigned long long *__restrict__ k1,
+__global__ void k_lead_seed(int B, const int32_t *__restrict__ e, u64 *__restrict__ k0, u64 *__restrict__ k1,
                             uint32_t *__restrict__ pred, int32_t *__restrict__ flags) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < kLeadBatch) flags[v] = 0;
-    if (v <= B) lead_seed(v, e, k0, k1, pred);
+    if (v < kSettleBatch) flags[v] = 0;
+    if (v <= B) flow_seed(v, e, k0, k1, pred);
 }
 
 // round r of a batch: thread i handles slot i and node i; flags[slot of the round in its batch] = 1 when the round changed a key
 __global__ void k_lead_round(int r, int P, int RF, int B, int lo, int hi, const uint16_t *__restrict__ rows, const uint8_t *__restrict__ lead,
-                             const int32_t *__restrict__ f, unsigned long long *__restrict__ k0, unsigned long long *__restrict__ k1,
+                             const int32_t *__restrict__ f, u64 *__restrict__ k0, u64 *__restrict__ k1,
                              int32_t *__restrict__ flag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long *X = (r & 1) ? k1 : k0;
-    unsigned long long *Y = (r & 1) ? k0 : k1;
+    const u64 *X = (r & 1) ? k1 : k0;
+    u64 *Y = (r & 1) ? k0 : k1;
     bool ch = false;
     if (i < P * RF) ch |= lead_relax_slot(i, RF, rows, lead, X, Y);
     if (i <= B) ch |= lead_relax_node(i, B, lo, hi, f, X, Y);
@@ -306,14 +289,14 @@ __global__ void k_lead_round(int r, int P, int RF, int B, int lo, int hi, const 
 }
 
 __global__ void k_lead_pred(int P, int RF, int B, int lo, int hi, const uint16_t *__restrict__ rows, const uint8_t *__restrict__ lead,
-                            const int32_t *__restrict__ f, const unsigned long long *__restrict__ K, uint32_t *__restrict__ pred) {
+                            const int32_t *__restrict__ f, const u64 *__restrict__ K, uint32_t *__restrict__ pred) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < P * RF) lead_pred_slot(i, RF, rows, lead, K, pred);
     if (i < B) lead_pred_node(i, B, P * RF, lo, hi, f, K, pred);
 }
 
 __global__ void k_lead_extract(int P, int RF, int B, int lo, int hi, int32_t stamp, const uint16_t *__restrict__ rows, uint8_t *__restrict__ lead,
-                               int32_t *__restrict__ claim, const unsigned long long *__restrict__ K, const uint32_t *__restrict__ pred,
+                               int32_t *__restrict__ claim, const u64 *__restrict__ K, const uint32_t *__restrict__ pred,
                                int32_t *__restrict__ e, int32_t *__restrict__ f, int32_t *__restrict__ ctl) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     int32_t maxlen = ctl[LC_MAXLEN];
@@ -325,22 +308,10 @@ __global__ void k_lead_extract(int P, int RF, int B, int lo, int hi, int32_t sta
 
 __global__ void k_lead_apply(int P, int RF, uint16_t *__restrict__ rows, const uint8_t *__restrict__ lead, int32_t *__restrict__ ctl) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool ch = p < P && lead_swap(p, RF, rows, lead);
-    const unsigned long long m = __ballot(ch);
-    if (m != 0ull && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(&ctl[LC_CHANGED], __popcll(m));
+    lane_count_to(p < P && lead_swap(p, RF, rows, lead), &ctl[LC_CHANGED]);
 }
 
-// the device memory and the stream of one call, handed back to the runtime's pools on every return path
-struct LeadBufs {
-    void *arena = nullptr;
-    size_t cap = 0;
-    hipStream_t stream = nullptr;
-    ~LeadBufs() {
-        if (stream) { (void)hipStreamSynchronize(stream); stream_put(stream, cur_device()); }
-        if (arena) arena_put(arena, cap, cur_device());
-    }
-};
-
+// keeps its own row loop: complete rows only, under messages of its own (the other planners: check_rows, kao_host.h)
 int validate_leaders(const kao_topic *t, const uint16_t *a, const int32_t *n_changed, const int32_t *status, int32_t bd[8]) {
     if (!t || !a || !n_changed || !status) return fail(KAO_ERR_INVALID, "kao_balance_leaders: null pointer");
     int rc = validate(t);   // also the limits: rf <= KAO_MAX_RF, n_brokers <= 65534, P * rf <= 4,000,000 (KAO_ERR_UNSUPPORTED)
@@ -372,23 +343,20 @@ extern "C" int kao_balance_leaders(const kao_topic *t, uint16_t *assignment, int
     const int P = t->n_partitions, RF = t->rf, B = t->n_brokers, N = B + 1, PRF = P * RF, lo = bd[2], hi = bd[3];
     const bool solo = N <= kLeadSoloNodes && PRF <= kLeadSoloSlots;
 
-    LeadBufs m;
-    // one arena: rows u16[PRF] | lead u8[P] | claim i32[P] | ctl i32[LC_N] | flags i32[kLeadBatch] | e, f i32[N] | pred u32[N] | keys u64[2][N]
-    const size_t o_rows = 0, o_lead = align_up((size_t)PRF * 2), o_claim = o_lead + align_up((size_t)P), o_ctl = o_claim + align_up((size_t)P * 4),
-                 o_flags = o_ctl + align_up(LC_N * 4), o_e = o_flags + align_up(kLeadBatch * 4), o_f = o_e + align_up((size_t)N * 4),
-                 o_pred = o_f + align_up((size_t)N * 4), o_k0 = o_pred + align_up((size_t)N * 4), o_k1 = o_k0 + align_up((size_t)N * 8),
-                 total = o_k1 + align_up((size_t)N * 8);
-    if ((rc = arena_get(total, &m.arena, &m.cap))) return rc;
-    if ((rc = stream_get(&m.stream))) return rc;
+    // one arena: rows u16[PRF] | lead u8[P] | claim i32[P] | ctl i32[LC_N] | flags i32[kSettleBatch] | e, f i32[N] | pred u32[N] | keys u64[2][N]
+    Carve cv;
+    const size_t o_rows = cv.take<uint16_t>(PRF), o_lead = cv.take<uint8_t>(P), o_claim = cv.take<int32_t>(P), o_ctl = cv.take<int32_t>(LC_N),
+                 o_flags = cv.take<int32_t>(kSettleBatch), o_e = cv.take<int32_t>(N), o_f = cv.take<int32_t>(N), o_pred = cv.take<uint32_t>(N),
+                 o_k0 = cv.take<u64>(N), o_k1 = cv.take<u64>(N);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
-    unsigned char *db = static_cast<unsigned char *>(m.arena);
-    uint16_t *d_rows = reinterpret_cast<uint16_t *>(db + o_rows);
-    uint8_t *d_lead = db + o_lead;
-    int32_t *d_claim = reinterpret_cast<int32_t *>(db + o_claim), *d_ctl = reinterpret_cast<int32_t *>(db + o_ctl),
-            *d_flags = reinterpret_cast<int32_t *>(db + o_flags), *d_e = reinterpret_cast<int32_t *>(db + o_e),
-            *d_f = reinterpret_cast<int32_t *>(db + o_f);
-    uint32_t *d_pred = reinterpret_cast<uint32_t *>(db + o_pred);
-    unsigned long long *d_k0 = reinterpret_cast<unsigned long long *>(db + o_k0), *d_k1 = reinterpret_cast<unsigned long long *>(db + o_k1);
+    uint16_t *d_rows = m.at<uint16_t>(o_rows);
+    uint8_t *d_lead = m.at<uint8_t>(o_lead);
+    int32_t *d_claim = m.at<int32_t>(o_claim), *d_ctl = m.at<int32_t>(o_ctl), *d_flags = m.at<int32_t>(o_flags), *d_e = m.at<int32_t>(o_e),
+            *d_f = m.at<int32_t>(o_f);
+    uint32_t *d_pred = m.at<uint32_t>(o_pred);
+    u64 *d_k0 = m.at<u64>(o_k0), *d_k1 = m.at<u64>(o_k1);
 
     HIP_TRY(hipMemcpyAsync(d_rows, assignment, (size_t)PRF * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     int32_t ctl[LC_N] = {0};
@@ -401,9 +369,8 @@ extern "C" int kao_balance_leaders(const kao_topic *t, uint16_t *assignment, int
         HIP_TRY(hipStreamSynchronize(st));
         if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, "kao_balance_leaders: relaxation did not settle");
     } else {
-        const unsigned pblocks = (unsigned)((P + kLeadThreads - 1) / kLeadThreads), nblocks = (unsigned)((N + kLeadThreads - 1) / kLeadThreads),
-                       ablocks = (unsigned)((std::max(PRF, N) + kLeadThreads - 1) / kLeadThreads);
-        HIP_TRY(hipMemsetAsync(db + o_ctl, 0, o_f - o_ctl, st));   // ctl, flags, e
+        const unsigned pblocks = grid_for(P, kLeadThreads), nblocks = grid_for(N, kLeadThreads), ablocks = grid_for(std::max(PRF, N), kLeadThreads);
+        HIP_TRY(hipMemsetAsync(d_ctl, 0, o_f - o_ctl, st));   // ctl, flags, e
         k_lead_count<<<pblocks, kLeadThreads, 0, st>>>(P, RF, d_rows, d_lead, d_claim, d_e);
         k_lead_start<<<nblocks, kLeadThreads, 0, st>>>(P, B, lo, hi, d_e, d_f, d_ctl);
         HIP_TRY(hipGetLastError());
@@ -417,21 +384,10 @@ extern "C" int kao_balance_leaders(const kao_topic *t, uint16_t *assignment, int
             ++phases;
             k_lead_seed<<<nblocks, kLeadThreads, 0, st>>>(B, d_e, d_k0, d_k1, d_pred, d_flags);
             ++launches;
-            int32_t flags[kLeadBatch];
-            for (int r = 0, settled = 0; !settled;) {
-                if (r > N + kLeadBatch) return fail(KAO_ERR_HIP, "kao_balance_leaders: relaxation did not settle");
-                if (r) { HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof flags, st)); }
-                for (int i = 0; i < kLeadBatch; ++i, ++r)
-                    k_lead_round<<<ablocks, kLeadThreads, 0, st>>>(r, P, RF, B, lo, hi, d_rows, d_lead, d_f, d_k0, d_k1, d_flags + i);
-                launches += kLeadBatch;
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                for (int i = 0; i < kLeadBatch && !settled; ++i) {   // the first round that changed nothing ends the phase's rounds
-                    ++rounds;
-                    settled = flags[i] == 0;
-                }
-            }
+            if ((rc = settle_rounds("kao_balance_leaders: ", st, N, d_flags, rounds, launches, [&](int r, int32_t *flag) {
+                    k_lead_round<<<ablocks, kLeadThreads, 0, st>>>(r, P, RF, B, lo, hi, d_rows, d_lead, d_f, d_k0, d_k1, flag);
+                })))
+                return rc;
             k_lead_pred<<<ablocks, kLeadThreads, 0, st>>>(P, RF, B, lo, hi, d_rows, d_lead, d_f, d_k0, d_pred);
             k_lead_extract<<<1, 64, 0, st>>>(P, RF, B, lo, hi, phases, d_rows, d_lead, d_claim, d_k0, d_pred, d_e, d_f, d_ctl);
             launches += 2;

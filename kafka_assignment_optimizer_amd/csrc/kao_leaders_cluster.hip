@@ -12,8 +12,8 @@
 //   - broker b -> T while f(b) < M (id PW + 2Q + b), T -> b while f(b) > cluster_lo (id PW + 2Q + B + b).  One lane per broker.
 // A SOLVE at cap M starts from j = 0 with the pseudoflow clamped into its bounds on both levels: g = clamp(leaders(q)), e(q) =
 // leaders(q) - g, f = clamp(sum of g over the pairs of b), e(b) = that sum - f, e(T) = sum f - P.  No residual arc is negative there.
-// Its PHASES are those of kao_leaders.hip: (1) keys (distance + 2^30) << 32 | arcs of every node from the nodes with e > 0, Jacobi
-// rounds between two buffers until a round changes nothing; (2) every tight arc bids its id into pred[head], the lowest id wins;
+// Its PHASES are those of kao_leaders.hip, on the flow keys of kao_plan_dev.h: (1) keys (distance + 2^30) << 32 | arcs of every node
+// from the nodes with e > 0, Jacobi rounds between two buffers until a round changes nothing; (2) every tight arc bids its id into pred[head], the lowest id wins;
 // the nodes below T with e < 0 and a key are marked, and when T has e < 0 so are the brokers with room whose distance equals T's
 // (their arcs into T have reduced cost 0); (3) one lane serves the marked nodes in index order, then the marked brokers in index
 // order, and augments a node's predecessor path while it uses no partition an earlier path of the phase used, keeps every g and f
@@ -24,7 +24,7 @@
 // INFEASIBLE_PROVEN, the cap is bisected over probes (max-flows: all costs 0) between max(ceil(P / B), cluster_lo) and the peak of the
 // last feasible probe, and one min-cost solve runs at the optimum; every one of them starts over from j = 0.
 // Node state lives in HBM / L2 (config 4 has 28,038 pair nodes): one launch per relaxation round, the host reading the rounds'
-// "changed" flags every kLcBatch rounds and the counters after every phase.
+// "changed" flags every kSettleBatch rounds (settle_rounds, kao_host.h) and the counters after every phase.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,14 +33,11 @@
 #include <vector>
 
 #include "kao_host.h"
+#include "kao_plan_dev.h"   // the 64-bit flow keys, lane_count_to, swap_leader
 
 namespace {
 
 constexpr int kLcThreads = 256;
-constexpr int kLcBatch = 8;            // rounds enqueued between two reads of the "changed" flags
-constexpr unsigned long long kLcInf = ~0ull;
-constexpr unsigned long long kLcSource = (unsigned long long)(1u << 30) << 32;   // distance 0, no arc
-constexpr uint32_t kLcNoPred = 0xFFFFFFFFu;
 enum { CC_PATHS = 0, CC_MAXLEN = 1, CC_AUG = 2, CC_OVER = 3, CC_PEAK0 = 4, CC_PEAK = 5, CC_CHANGED = 6, CC_N = 8 };
 
 struct LcNet {   // the network of one call; every pointer is device memory
@@ -54,15 +51,11 @@ struct LcNet {   // the network of one call; every pointer is device memory
     int32_t *c0;                // [Q] leaders of a pair at j = 0
     int32_t *g, *f, *inb;       // [Q], [B], [B]
     int32_t *e;                 // [N]
-    unsigned long long *k0, *k1;   // [N]
+    u64 *k0, *k1;   // [N]
     uint32_t *pred;             // [N]
     uint8_t *mark;              // [N]: bit 0 = a node below T to serve, bit 1 = broker b (at Q + b) is a tight way into T while T is served
     int32_t *ctl;               // [CC_N]
 };
-
-__device__ __forceinline__ unsigned long long lc_step(unsigned long long ku, int c) {
-    return ku + ((unsigned long long)(long long)c << 32) + 1ull;
-}
 
 // tail, head and cost of the arc of slot s = p * W + j; false when j is the leader's slot or empty
 __device__ __forceinline__ bool lc_arc(int s, const LcNet &n, bool costed, int &u, int &v, int &c) {
@@ -71,12 +64,13 @@ __device__ __forceinline__ bool lc_arc(int s, const LcNet &n, bool costed, int &
     const int p = s / n.W, j = s - p * n.W, l = n.lead[p];
     if (j == l) return false;
     u = n.pair_of[p * n.W + l];
-    c = !costed ? 0 : (j == 0 ? -1 : (l == 0 ? 1 : 0));
+    c = flow_slot_cost(j, l, costed);
     return true;
 }
 
-__device__ __forceinline__ bool lc_bid(unsigned long long ku, unsigned long long kv, unsigned long long *yv) {
-    if (ku == kLcInf || ku + 1 >= kv) return false;
+// an arc of cost 0 from a node with key ku to one with key kv bids into the head's word of the other buffer when it lowers the key
+__device__ __forceinline__ bool lc_bid(u64 ku, u64 kv, u64 *yv) {
+    if (ku == kFlowInf || ku + 1 >= kv) return false;
     atomicMin(yv, ku + 1);
     return true;
 }
@@ -121,46 +115,43 @@ __global__ void k_lc_start_brokers(LcNet n, int clo, int M) {
 // ---- a phase ------------------------------------------------------------------------------------------------------------------------
 __global__ void k_lc_seed(LcNet n, int32_t *__restrict__ flags) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v < kLcBatch) flags[v] = 0;
+    if (v < kSettleBatch) flags[v] = 0;
     if (v >= n.N) return;
-    const unsigned long long k = n.e[v] > 0 ? kLcSource : kLcInf;
-    n.k0[v] = k;
-    n.k1[v] = k;
-    n.pred[v] = kLcNoPred;
+    flow_seed(v, n.e, n.k0, n.k1, n.pred);
     n.mark[v] = 0;
 }
 
 // round r: thread i handles slot i, pair i, broker i and the own bid of node i
 __global__ void k_lc_round(LcNet n, int r, int costed, int clo, int M, int32_t *__restrict__ flag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long *X = (r & 1) ? n.k1 : n.k0;
-    unsigned long long *Y = (r & 1) ? n.k0 : n.k1;
+    const u64 *X = (r & 1) ? n.k1 : n.k0;
+    u64 *Y = (r & 1) ? n.k0 : n.k1;
     bool ch = false;
     if (i < n.PW) {
         int u, v, c;
         if (lc_arc(i, n, costed != 0, u, v, c)) {
-            const unsigned long long ku = X[u];
-            if (ku != kLcInf) {
-                const unsigned long long nk = lc_step(ku, c);
+            const u64 ku = X[u];
+            if (ku != kFlowInf) {
+                const u64 nk = flow_step(ku, c);
                 if (nk < X[v]) { atomicMin(&Y[v], nk); ch = true; }
             }
         }
     }
     if (i < n.Q) {
         const int nb = n.Q + n.bro[i], gq = n.g[i];
-        const unsigned long long kq = X[i], kb = X[nb];
+        const u64 kq = X[i], kb = X[nb];
         if (gq < n.phi[i]) ch |= lc_bid(kq, kb, &Y[nb]);
         if (gq > n.plo[i]) ch |= lc_bid(kb, kq, &Y[i]);
     }
     if (i < n.B) {
         const int nb = n.Q + i, T = n.N - 1, fb = n.f[i];
-        const unsigned long long kb = X[nb], kt = X[T];
+        const u64 kb = X[nb], kt = X[T];
         if (fb < M) ch |= lc_bid(kb, kt, &Y[T]);
         if (fb > clo) ch |= lc_bid(kt, kb, &Y[nb]);
     }
     if (i < n.N) {
-        const unsigned long long kv = X[i];
-        if (kv != kLcInf) atomicMin(&Y[i], kv);
+        const u64 kv = X[i];
+        if (kv != kFlowInf) atomicMin(&Y[i], kv);
     }
     if (__any(ch) && __lane_id() == 0) *flag = 1;
 }
@@ -168,35 +159,36 @@ __global__ void k_lc_round(LcNet n, int r, int costed, int clo, int M, int32_t *
 // the settled keys are in both buffers
 __global__ void k_lc_pred(LcNet n, int costed, int clo, int M) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long *K = n.k0;
+    const u64 *K = n.k0;
     const int T = n.N - 1;
     if (i < n.PW) {
         int u, v, c;
         if (lc_arc(i, n, costed != 0, u, v, c)) {
-            const unsigned long long ku = K[u];
-            if (ku != kLcInf && lc_step(ku, c) == K[v]) atomicMin(&n.pred[v], (uint32_t)i);
+            const u64 ku = K[u];
+            if (ku != kFlowInf && flow_step(ku, c) == K[v]) atomicMin(&n.pred[v], (uint32_t)i);
         }
     }
     if (i < n.Q) {
         const int nb = n.Q + n.bro[i], gq = n.g[i];
-        const unsigned long long kq = K[i], kb = K[nb];
-        if (gq < n.phi[i] && kq != kLcInf && kq + 1 == kb) atomicMin(&n.pred[nb], (uint32_t)(n.PW + i));
-        if (gq > n.plo[i] && kb != kLcInf && kb + 1 == kq) atomicMin(&n.pred[i], (uint32_t)(n.PW + n.Q + i));
-        if (n.e[i] < 0 && kq != kLcInf) n.mark[i] = 1;
+        const u64 kq = K[i], kb = K[nb];
+        if (gq < n.phi[i] && kq != kFlowInf && kq + 1 == kb) atomicMin(&n.pred[nb], (uint32_t)(n.PW + i));
+        if (gq > n.plo[i] && kb != kFlowInf && kb + 1 == kq) atomicMin(&n.pred[i], (uint32_t)(n.PW + n.Q + i));
+        if (n.e[i] < 0 && kq != kFlowInf) n.mark[i] = 1;
     }
     if (i < n.B) {
         const int nb = n.Q + i, fb = n.f[i];
-        const unsigned long long kb = K[nb], kt = K[T];
-        if (fb < M && kb != kLcInf && kb + 1 == kt) atomicMin(&n.pred[T], (uint32_t)(n.PW + 2 * n.Q + i));
-        if (fb > clo && kt != kLcInf && kt + 1 == kb) atomicMin(&n.pred[nb], (uint32_t)(n.PW + 2 * n.Q + n.B + i));
+        const u64 kb = K[nb], kt = K[T];
+        if (fb < M && kb != kFlowInf && kb + 1 == kt) atomicMin(&n.pred[T], (uint32_t)(n.PW + 2 * n.Q + i));
+        if (fb > clo && kt != kFlowInf && kt + 1 == kb) atomicMin(&n.pred[nb], (uint32_t)(n.PW + 2 * n.Q + n.B + i));
         // bit 0: a deficit node to serve; bit 1: a way into T of reduced cost 0, tried when T is served
         uint8_t m = 0;
-        if (n.e[nb] < 0 && kb != kLcInf) m |= 1;
-        if (n.e[T] < 0 && kt != kLcInf && fb < M && kb != kLcInf && (kb >> 32) == (kt >> 32)) m |= 2;
+        if (n.e[nb] < 0 && kb != kFlowInf) m |= 1;
+        if (n.e[T] < 0 && kt != kFlowInf && fb < M && kb != kFlowInf && (kb >> 32) == (kt >> 32)) m |= 2;
         n.mark[nb] = m;
     }
 }
 
+// (the walk differs from lead_extract of kao_leaders.hip in its arc classes and its two passes: not shared)
 // One lane: the predecessor path of node v0 back to its first node.  apply = false checks it against the paths this phase has
 // already taken (returns -1 when it is blocked), apply = true takes it.  Returns the first node.
 __device__ int lc_walk(const LcNet &n, int v0, int32_t stamp, int clo, int M, bool apply) {
@@ -205,7 +197,7 @@ __device__ int lc_walk(const LcNet &n, int v0, int32_t stamp, int clo, int M, bo
     while ((uint32_t)n.k0[v] != 0u) {   // arcs on the way here: 0 at the path's first node
         const uint32_t a = n.pred[v];
         int u;
-        if (a == kLcNoPred || ++steps > n.N) return -1;   // (a tight path always has its predecessors)
+        if (a == kFlowNoPred || ++steps > n.N) return -1;   // (a tight path always has its predecessors)
         if (a < (uint32_t)a_up) {
             const int p = (int)a / n.W;
             if (!apply && n.claim[p] == stamp) return -1;
@@ -243,7 +235,7 @@ __global__ __launch_bounds__(64) void k_lc_extract(LcNet n, int32_t stamp, int c
     int naug = 0, maxlen = 0;
     for (int base = 0; base < T; base += 64) {
         const int v = base + lane;
-        unsigned long long m = __ballot(v < T && (n.mark[v] & 1));
+        u64 m = __ballot(v < T && (n.mark[v] & 1));
         while (lane == 0 && m) {
             const int t = base + __ffsll((long long)m) - 1;
             m &= m - 1;
@@ -260,7 +252,7 @@ __global__ __launch_bounds__(64) void k_lc_extract(LcNet n, int32_t stamp, int c
     }
     for (int base = 0; base < n.B; base += 64) {
         const int b = base + lane;
-        unsigned long long m = __ballot(b < n.B && (n.mark[n.Q + b] & 2));
+        u64 m = __ballot(b < n.B && (n.mark[n.Q + b] & 2));
         while (lane == 0 && m) {
             const int t = base + __ffsll((long long)m) - 1;
             m &= m - 1;
@@ -290,55 +282,28 @@ __global__ void k_lc_apply(LcNet n, uint16_t *__restrict__ rows, int dry_run) {
     if (p < n.P) {
         const int l = n.lead[p];
         ch = l != 0;
-        if (ch && !dry_run) {
-            const uint16_t a = rows[(size_t)p * n.W], b = rows[(size_t)p * n.W + l];
-            rows[(size_t)p * n.W] = b;
-            rows[(size_t)p * n.W + l] = a;
-        }
+        if (ch && !dry_run) swap_leader(rows + (size_t)p * n.W, l);
     }
-    const unsigned long long m = __ballot(ch);
-    if (m != 0ull && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(&n.ctl[CC_CHANGED], __popcll(m));
+    lane_count_to(ch, &n.ctl[CC_CHANGED]);
 }
-
-// the device memory and the stream of one call, handed back to the runtime's pools on every return path
-struct LcBufs {
-    void *arena = nullptr;
-    size_t cap = 0;
-    hipStream_t stream = nullptr;
-    ~LcBufs() {
-        if (stream) { (void)hipStreamSynchronize(stream); stream_put(stream, cur_device()); }
-        if (arena) arena_put(arena, cap, cur_device());
-    }
-};
 
 int validate_cluster(int32_t B, int32_t P, int32_t W, const uint16_t *rows, const int32_t *topic_of, int32_t T, const int32_t *tlo,
                      const int32_t *thi, int32_t clo, int32_t chi, const int32_t *n_changed, const int32_t *peak_before,
                      const int32_t *peak_after, const int32_t *status) {
     const std::string fn = "kao_balance_leaders_cluster: ";
     if (!rows || !topic_of || !tlo || !thi || !n_changed || !peak_before || !peak_after || !status) return fail(KAO_ERR_INVALID, fn + "null pointer");
-    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, fn + "width outside 1.." + std::to_string(KAO_MAX_RF));
-    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, fn + "n_brokers outside 1..65534");
-    if (P < 0) return fail(KAO_ERR_INVALID, fn + "n_partitions < 0");
+    int rc = check_dims(fn, B, P, W);
+    if (rc) return rc;
     if (T < 1) return fail(KAO_ERR_INVALID, fn + "n_topics < 1");
     if (clo < 0) return fail(KAO_ERR_INVALID, fn + "cluster_lo < 0");
     if (chi < -1) return fail(KAO_ERR_INVALID, fn + "cluster_hi < -1");
     if (chi >= 0 && chi < clo) return fail(KAO_ERR_INVALID, fn + "cluster_hi < cluster_lo");
-    if ((int64_t)P * W > 4000000) return fail(KAO_ERR_UNSUPPORTED, fn + "more than 4,000,000 replica slots");
+    if ((rc = check_slot_cap(fn, P, W))) return rc;
     for (int t = 0; t < T; ++t)
         if (tlo[t] < 0 || tlo[t] > thi[t]) return fail(KAO_ERR_INVALID, fn + "topic " + std::to_string(t) + ": band needs 0 <= topic_lo <= topic_hi");
-    for (int64_t p = 0; p < P; ++p) {
-        const uint16_t *row = rows + p * W;
-        const std::string at = fn + "partition " + std::to_string(p) + ": ";
-        if (topic_of[p] < 0 || topic_of[p] >= T) return fail(KAO_ERR_INVALID, at + "topic_of outside 0..n_topics-1");
-        if (row[0] == KAO_NONE) return fail(KAO_ERR_INVALID, at + "slot 0 holds no broker");
-        bool ended = false;
-        for (int i = 0; i < W; ++i) {
-            if (row[i] == KAO_NONE) { ended = true; continue; }
-            if (ended) return fail(KAO_ERR_INVALID, at + "a broker after an empty slot");
-            if (row[i] >= B) return fail(KAO_ERR_INVALID, at + "broker index >= n_brokers");
-            for (int j = 0; j < i; ++j)
-                if (row[j] == row[i]) return fail(KAO_ERR_INVALID, at + "broker repeated in a row");
-        }
+    for (int64_t p = 0; p < P; ++p) {   // (check_rows, with the row's topic checked in front of it)
+        if (topic_of[p] < 0 || topic_of[p] >= T) return fail(KAO_ERR_INVALID, fn + "partition " + std::to_string(p) + ": topic_of outside 0..n_topics-1");
+        if ((rc = check_row(fn, B, W, p, rows + p * W))) return rc;
     }
     return KAO_OK;
 }
@@ -379,43 +344,39 @@ extern "C" int kao_balance_leaders_cluster(int32_t n_brokers, int32_t n_partitio
     bool possible = true;   // a broker that holds no replica of t leads none of it: topic_lo[t] > 0 cannot be met there
     for (int t = 0; t < n_topics; ++t) possible = possible && (topic_lo[t] == 0 || held[(size_t)t] == B);
 
-    LcBufs m;
-    // one arena: ctl i32[CC_N] | flags i32[kLcBatch] | cnt0 i32[B] | c0 i32[Q] (zeroed once up to here) | inb i32[B] | e i32[N] (zeroed per
-    //            solve) | g i32[Q] | f i32[B] | pred u32[N] | k0, k1 u64[N] | pair_of i32[PW] | bro, plo, phi i32[Q] | claim i32[P] |
+    // one arena: ctl i32[CC_N] | flags i32[kSettleBatch] | cnt0 i32[B] | c0 i32[Q] (zeroed once up to here) | inb i32[B] | e i32[N] (zeroed
+    //            per solve) | g i32[Q] | f i32[B] | pred u32[N] | k0, k1 u64[N] | pair_of i32[PW] | bro, plo, phi i32[Q] | claim i32[P] |
     //            rows u16[PW] | lead u8[P] | mark u8[N]
-    const size_t o_ctl = 0, o_flags = o_ctl + align_up(CC_N * 4), o_cnt0 = o_flags + align_up(kLcBatch * 4), o_c0 = o_cnt0 + align_up((size_t)B * 4),
-                 o_inb = o_c0 + align_up((size_t)Q * 4), o_e = o_inb + align_up((size_t)B * 4), o_g = o_e + align_up((size_t)N * 4),
-                 o_f = o_g + align_up((size_t)Q * 4), o_pred = o_f + align_up((size_t)B * 4), o_k0 = o_pred + align_up((size_t)N * 4),
-                 o_k1 = o_k0 + align_up((size_t)N * 8), o_pair = o_k1 + align_up((size_t)N * 8), o_bro = o_pair + align_up((size_t)PW * 4),
-                 o_plo = o_bro + align_up((size_t)Q * 4), o_phi = o_plo + align_up((size_t)Q * 4), o_claim = o_phi + align_up((size_t)Q * 4),
-                 o_rows = o_claim + align_up((size_t)P * 4), o_lead = o_rows + align_up((size_t)PW * 2), o_mark = o_lead + align_up((size_t)P),
-                 total = o_mark + align_up((size_t)N);
-    if ((rc = arena_get(total, &m.arena, &m.cap))) return rc;
-    if ((rc = stream_get(&m.stream))) return rc;
+    Carve cv;
+    const size_t o_ctl = cv.take<int32_t>(CC_N), o_flags = cv.take<int32_t>(kSettleBatch), o_cnt0 = cv.take<int32_t>(B), o_c0 = cv.take<int32_t>(Q),
+                 zeroed_once = cv.end(), o_inb = cv.take<int32_t>(B), o_e = cv.take<int32_t>(N), per_solve = cv.end() - o_inb,
+                 o_g = cv.take<int32_t>(Q), o_f = cv.take<int32_t>(B), o_pred = cv.take<uint32_t>(N), o_k0 = cv.take<u64>(N), o_k1 = cv.take<u64>(N),
+                 o_pair = cv.take<int32_t>(PW), o_bro = cv.take<int32_t>(Q), o_plo = cv.take<int32_t>(Q), o_phi = cv.take<int32_t>(Q),
+                 o_claim = cv.take<int32_t>(P), o_rows = cv.take<uint16_t>(PW), o_lead = cv.take<uint8_t>(P), o_mark = cv.take<uint8_t>(N);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
-    unsigned char *db = static_cast<unsigned char *>(m.arena);
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(db + o); };
-    uint16_t *d_rows = reinterpret_cast<uint16_t *>(db + o_rows);
-    int32_t *d_flags = i32(o_flags), *d_cnt0 = i32(o_cnt0);
+    uint16_t *d_rows = m.at<uint16_t>(o_rows);
+    int32_t *d_flags = m.at<int32_t>(o_flags), *d_cnt0 = m.at<int32_t>(o_cnt0);
     LcNet n;
     n.P = P; n.W = W; n.B = B; n.Q = Q; n.N = N; n.PW = PW;
-    n.rows = d_rows; n.pair_of = i32(o_pair); n.bro = i32(o_bro); n.plo = i32(o_plo); n.phi = i32(o_phi);
-    n.lead = db + o_lead; n.claim = i32(o_claim); n.c0 = i32(o_c0); n.g = i32(o_g); n.f = i32(o_f); n.inb = i32(o_inb); n.e = i32(o_e);
-    n.k0 = reinterpret_cast<unsigned long long *>(db + o_k0); n.k1 = reinterpret_cast<unsigned long long *>(db + o_k1);
-    n.pred = reinterpret_cast<uint32_t *>(db + o_pred); n.mark = db + o_mark; n.ctl = i32(o_ctl);
+    n.rows = d_rows; n.pair_of = m.at<int32_t>(o_pair); n.bro = m.at<int32_t>(o_bro); n.plo = m.at<int32_t>(o_plo); n.phi = m.at<int32_t>(o_phi);
+    n.lead = m.at<uint8_t>(o_lead); n.claim = m.at<int32_t>(o_claim); n.c0 = m.at<int32_t>(o_c0); n.g = m.at<int32_t>(o_g); n.f = m.at<int32_t>(o_f);
+    n.inb = m.at<int32_t>(o_inb); n.e = m.at<int32_t>(o_e); n.k0 = m.at<u64>(o_k0); n.k1 = m.at<u64>(o_k1);
+    n.pred = m.at<uint32_t>(o_pred); n.mark = m.at<uint8_t>(o_mark); n.ctl = m.at<int32_t>(o_ctl);
 
-    HIP_TRY(hipMemsetAsync(db, 0, o_inb, st));
+    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed_once, st));
     if (PW) {
         HIP_TRY(hipMemcpyAsync(d_rows, rows, (size_t)PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(db + o_pair, h_pair.data(), (size_t)PW * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<int32_t>(o_pair), h_pair.data(), (size_t)PW * sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
     if (Q) {
-        HIP_TRY(hipMemcpyAsync(db + o_bro, h_bro.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(db + o_plo, h_plo.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(db + o_phi, h_phi.data(), (size_t)Q * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<int32_t>(o_bro), h_bro.data(), (size_t)Q * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<int32_t>(o_plo), h_plo.data(), (size_t)Q * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<int32_t>(o_phi), h_phi.data(), (size_t)Q * sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
-    auto blocks = [](int x) { return (unsigned)((std::max(x, 1) + kLcThreads - 1) / kLcThreads); };
-    const unsigned pblocks = blocks(P), bblocks = blocks(B), nblocks = blocks(N), ablocks = blocks(std::max(PW, N)), sblocks = blocks(std::max(P, Q));
+    const unsigned pblocks = grid_for(P, kLcThreads), bblocks = grid_for(B, kLcThreads), nblocks = grid_for(N, kLcThreads),
+                   ablocks = grid_for(std::max(PW, N), kLcThreads), sblocks = grid_for(std::max(P, Q), kLcThreads);
     int32_t launches = 0, ctl[CC_N] = {0};
     if (P) {
         k_lc_count<<<pblocks, kLcThreads, 0, st>>>(n, d_cnt0);
@@ -429,7 +390,7 @@ extern "C" int kao_balance_leaders_cluster(int32_t n_brokers, int32_t n_partitio
     // one solve at cap M from j = 0; *feasible, and ctl[CC_PEAK] = the largest f when it is
     auto solve = [&](int M, bool costed, bool *feasible) -> int {
         ++probes;
-        HIP_TRY(hipMemsetAsync(db + o_inb, 0, o_g - o_inb, st));   // inb, e
+        HIP_TRY(hipMemsetAsync(n.inb, 0, per_solve, st));   // inb, e
         HIP_TRY(hipMemsetAsync(n.ctl + CC_OVER, 0, 4, st));
         k_lc_start_pairs<<<sblocks, kLcThreads, 0, st>>>(n);
         k_lc_start_brokers<<<bblocks, kLcThreads, 0, st>>>(n, cluster_lo, M);
@@ -444,20 +405,10 @@ extern "C" int kao_balance_leaders_cluster(int32_t n_brokers, int32_t n_partitio
             ++phases;
             k_lc_seed<<<nblocks, kLcThreads, 0, st>>>(n, d_flags);
             ++launches;
-            int32_t flags[kLcBatch];
-            for (int r = 0, settled = 0; !settled;) {
-                if (r > N + kLcBatch) return fail(KAO_ERR_HIP, "kao_balance_leaders_cluster: relaxation did not settle");
-                if (r) { HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof flags, st)); }
-                for (int i = 0; i < kLcBatch; ++i, ++r) k_lc_round<<<ablocks, kLcThreads, 0, st>>>(n, r, costed ? 1 : 0, cluster_lo, M, d_flags + i);
-                launches += kLcBatch;
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                for (int i = 0; i < kLcBatch && !settled; ++i) {   // the first round that changed nothing ends the phase's rounds
-                    ++rounds;
-                    settled = flags[i] == 0;
-                }
-            }
+            if ((rc = settle_rounds("kao_balance_leaders_cluster: ", st, N, d_flags, rounds, launches, [&](int r, int32_t *flag) {
+                    k_lc_round<<<ablocks, kLcThreads, 0, st>>>(n, r, costed ? 1 : 0, cluster_lo, M, flag);
+                })))
+                return rc;
             k_lc_pred<<<ablocks, kLcThreads, 0, st>>>(n, costed ? 1 : 0, cluster_lo, M);
             k_lc_extract<<<1, 64, 0, st>>>(n, phases, cluster_lo, M);
             launches += 2;

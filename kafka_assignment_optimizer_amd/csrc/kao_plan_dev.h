@@ -1,0 +1,64 @@
+// kao_plan_dev.h -- device code the one-shot planners share: the 64-bit keys of successive shortest paths (kao_leaders.hip,
+// kao_leaders_cluster.hip; DESIGN.md sections 4h, 4j), the wavefront count, the leader swap, and the pieces of the weighted descent
+// (kao_wleaders.hip, kao_wfailover.hip; sections 4k, 4l).  Everything sits in an unnamed namespace and is inlined into its callers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "kao_bytes_code.h"   // wave_bytes_code
+
+namespace {
+
+typedef unsigned long long u64;
+
+// ---- flow keys: (distance + 2^30) << 32 | arcs on the path, minimised as one word -------------------------------------------------
+constexpr u64 kFlowInf = ~0ull;
+constexpr u64 kFlowSource = (u64)(1u << 30) << 32;   // distance 0, no arc
+constexpr uint32_t kFlowNoPred = 0xFFFFFFFFu;
+
+// key of the head of an arc of cost c whose tail has key ku
+__device__ __forceinline__ u64 flow_step(u64 ku, int c) { return ku + ((u64)(long long)c << 32) + 1ull; }
+
+// cost of moving a partition's leader from slot l to slot j: -1 back to slot 0, +1 away from it, 0 otherwise (all 0 in a probe)
+__device__ __forceinline__ int flow_slot_cost(int j, int l, bool costed) { return !costed ? 0 : (j == 0 ? -1 : (l == 0 ? 1 : 0)); }
+
+// the start of a phase at node v: the nodes with excess are the sources
+__device__ __forceinline__ void flow_seed(int v, const int32_t *e, u64 *k0, u64 *k1, uint32_t *pred) {
+    const u64 k = e[v] > 0 ? kFlowSource : kFlowInf;
+    k0[v] = k;
+    k1[v] = k;
+    pred[v] = kFlowNoPred;
+}
+
+// ---- the lanes of a wavefront for which `one` holds, added to *dst by the lowest of them (all 64 lanes active) ---------------------
+template <class T>
+__device__ __forceinline__ void lane_count_to(bool one, T *dst) {
+    const u64 m = __ballot(one);
+    if (m != 0ull && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(dst, (T)__popcll(m));
+}
+
+// the output row of a partition whose leader is slot l != 0: slot 0 and slot l swapped
+__device__ __forceinline__ void swap_leader(uint16_t *row, int l) {
+    const uint16_t a = row[0], b = row[l];
+    row[0] = b;
+    row[l] = a;
+}
+
+// ---- the weighted descent ---------------------------------------------------------------------------------------------------------
+// key of the proposal of partition p (weight w) whose source carries `load`: the heaviest source first, then the heaviest
+// partition, then the lowest index
+// (a macro: as a function it changes the operand order of the kernels' v_or3_b32, whatever its spelling)
+#define DESCENT_KEY(load, w, p) ((u64)(0xFFFFu - wave_bytes_code(load)) << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)(p))
+
+// L(b*) + w + min_gain < L(a) without overflow: the loads and w stay below 2^62, min_gain is any u64
+__device__ __forceinline__ bool descent_gains(u64 la, u64 best, u64 w, u64 min_gain) { return !(la <= best + w || la - best - w <= min_gain); }
+
+// a bid: atomicMin only lowers a word, so a word already at or below the key needs no atomic (all the proposals of one source collide
+// there; most of them find a lower key in place).  Scope: __HIP_MEMORY_SCOPE_AGENT for a word in HBM, _WORKGROUP for one in LDS.
+template <int Scope>
+__device__ __forceinline__ void descent_bid(u64 *word, u64 key) {
+    if (__hip_atomic_load(word, __ATOMIC_RELAXED, Scope) > key) atomicMin(word, key);
+}
+
+}  // namespace

@@ -121,6 +121,52 @@ void arena_drop_all() {
     if (g_device >= 0) (void)hipSetDevice(g_device);
 }
 
+// ---- one-shot planner calls ----
+int CallBufs::open(size_t bytes) {
+    int rc = arena_get(bytes, &arena, &cap);
+    return rc ? rc : stream_get(&stream);
+}
+CallBufs::~CallBufs() {
+    if (stream) { (void)hipStreamSynchronize(stream); stream_put(stream, cur_device()); }
+    if (arena) arena_put(arena, cap, cur_device());
+}
+
+int check_dims(const std::string &fn, int32_t B, int32_t P, int32_t W, int32_t R) {
+    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, fn + "width outside 1.." + std::to_string(KAO_MAX_RF));
+    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, fn + "n_brokers outside 1..65534");
+    if (R < 1 || R > KAO_MAX_RACKS) return fail(KAO_ERR_INVALID, fn + "n_racks outside 1.." + std::to_string(KAO_MAX_RACKS));
+    if (P < 0) return fail(KAO_ERR_INVALID, fn + "n_partitions < 0");
+    return KAO_OK;
+}
+int check_slot_cap(const std::string &fn, int32_t P, int32_t W) {
+    return (int64_t)P * W > 4000000 ? fail(KAO_ERR_UNSUPPORTED, fn + "more than 4,000,000 replica slots") : KAO_OK;
+}
+int check_row(const std::string &fn, int32_t B, int32_t W, int64_t p, const uint16_t *row) {
+    const auto bad = [&](const char *what) { return fail(KAO_ERR_INVALID, fn + "partition " + std::to_string(p) + ": " + what); };
+    if (row[0] == KAO_NONE) return bad("slot 0 holds no broker");
+    bool ended = false;
+    for (int i = 0; i < W; ++i) {
+        if (row[i] == KAO_NONE) { ended = true; continue; }
+        if (ended) return bad("a broker after an empty slot");
+        if (row[i] >= B) return bad("broker index >= n_brokers");
+        for (int j = 0; j < i; ++j)
+            if (row[j] == row[i]) return bad("broker repeated in a row");
+    }
+    return KAO_OK;
+}
+int check_rows(const std::string &fn, int32_t B, int32_t P, int32_t W, const uint16_t *rows) {
+    int rc = KAO_OK;
+    for (int64_t p = 0; p < P && !rc; ++p) rc = check_row(fn, B, W, p, rows + p * W);
+    return rc;
+}
+int check_weight_sum(const std::string &fn, int32_t P, const uint64_t *weight) {
+    uint64_t total = 0;
+    for (int64_t p = 0; p < P; ++p)
+        if (__builtin_add_overflow(total, weight[p], &total) || total >= (uint64_t(1) << 62))
+            return fail(KAO_ERR_INVALID, fn + "partition " + std::to_string(p) + ": the weights sum to 2^62 or more");
+    return KAO_OK;
+}
+
 }  // namespace kao
 
 extern "C" {

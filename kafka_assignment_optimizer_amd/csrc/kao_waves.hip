@@ -270,7 +270,8 @@ __global__ void k_wave_scatter(int32_t n_mv, const int32_t *__restrict__ waveo, 
     if (i < n_mv) wave[mv_idx[i]] = waveo[i];
 }
 
-// device buffers of one call, released on every return path
+// device buffers of one call, released on every return path (not CallBufs of kao_host.h: a call allocates up to 1 GiB, which must
+// not be parked in the arena pool)
 struct WaveBufs {
     std::vector<void *> ptrs;
     hipStream_t stream = nullptr;

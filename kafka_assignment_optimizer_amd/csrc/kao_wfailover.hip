@@ -29,12 +29,10 @@
 #include <cstdint>
 #include <string>
 
-#include "kao_bytes_code.h"   // wave_bytes_code
 #include "kao_failover_dev.h"
+#include "kao_plan_dev.h"   // DESCENT_KEY, descent_gains, descent_bid
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr u64 kWfNoKey = ~0ull;
 constexpr int kWfHardRounds = 1 << 26;   // no descent gets here; a guard against an endless loop
@@ -66,12 +64,8 @@ __global__ void k_wfo_wlead(int P, int W, const uint16_t *__restrict__ rows, con
     if (w) atomicAdd(&wlead[rows[(size_t)p * W]], w);
 }
 
-// a bid: atomicMin only lowers a word, so a word already at or below the key needs no atomic
-__device__ __forceinline__ void wf_bid(u64 *word, u64 key) {
-    if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > key) atomicMin(word, key);
-}
-
-// PROPOSE for partition p against the loads `load`: false when p proposes nothing
+// PROPOSE for partition p against the loads `load`: false when p proposes nothing (the eligible slots come from meta[p];
+// wl_propose of kao_wleaders.hip takes every replica but the leader, so the two loops stay apart)
 __device__ __forceinline__ bool wf_propose(const WfNet &n, int p, const u64 *load, int &a, int &b, int &slot, u64 &key) {
     const u64 w = n.weight[p];
     if (w == 0) return false;
@@ -88,9 +82,8 @@ __device__ __forceinline__ bool wf_propose(const WfNet &n, int p, const u64 *loa
     }
     if (slot < 0) return false;
     const u64 la = load[a];
-    // L(b*) + w + min_gain < L(a) without overflow: the loads and w stay below 2^62, min_gain is any u64
-    if (la <= best + w || la - best - w <= n.min_gain) return false;
-    key = (u64)(0xFFFFu - wave_bytes_code(la)) << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)p;
+    if (!descent_gains(la, best, w, n.min_gain)) return false;
+    key = DESCENT_KEY(la, w, p);
     return true;
 }
 
@@ -154,8 +147,8 @@ __global__ __launch_bounds__(kFoSoloLarge) void k_wfo_solve(WfNet n) {
             n.key[p] = key;   // key[p], slot[p] and cur[p] are read back by this lane alone
             if (prop) {
                 n.slot[p] = (uint8_t)slot;
-                wf_bid(&mk[a], key);
-                wf_bid(&mk[b], key);
+                descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[a], key);
+                descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[b], key);
                 ++mine;
             }
         }
@@ -190,6 +183,7 @@ __global__ __launch_bounds__(kFoSoloLarge) void k_wfo_solve(WfNet n) {
         __syncthreads();
     }
     __syncthreads();
+    // (the certificate ranks a compacted set inside the workgroup; kao_wleaders.hip runs rank, histogram and scan as launches: not shared)
     // ---- peak_after; T = the brokers some affected partition is eligible for, compacted; their ranks ----
     {
         u64 mx = 0;
@@ -330,76 +324,49 @@ extern "C" int kao_failover_order_weighted(int32_t n_brokers, int32_t n_racks, c
     if (!weight || !status) return fail(KAO_ERR_INVALID, fn + "null pointer");
     int rc = validate_failover(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, scope, scen, n_reordered);
     if (rc) return rc;
-    {   // every load and every L(b*) + weight of the kernels then stays below 2^63
-        uint64_t total = 0;
-        for (int64_t p = 0; p < n_partitions; ++p)
-            if (__builtin_add_overflow(total, weight[p], &total) || total >= (uint64_t(1) << 62))
-                return fail(KAO_ERR_INVALID, fn + "partition " + std::to_string(p) + ": the weights sum to 2^62 or more");
-    }
+    if ((rc = check_weight_sum(fn, n_partitions, weight))) return rc;
     if ((rc = require_init())) return rc;
     const int B = n_brokers, P = n_partitions, W = width, G = scope == 0 ? n_brokers : n_racks;
     const size_t PW = (size_t)P * W;
 
-    FoBufs m;
     // one arena: ctl32 i32[FS_N] | ctl u64[WC_N] | lead i32[B] | wlead u64[B] | cnt, off i32[G] (zeroed up to here) | start, fill i32[G] |
     //            scen u64[6G] | scen_of, list, claim i32[P] | tlist, trank i32[PW] | key, weight u64[P] | rows u16[PW] | meta u16[P] |
     //            cur, slot u8[P] | rack_of u8[B]
-    const size_t o_ctl32 = 0, o_ctl = o_ctl32 + align_up(FS_N * 4), o_lead = o_ctl + align_up(WC_N * 8), o_wlead = o_lead + align_up((size_t)B * 4),
-                 o_cnt = o_wlead + align_up((size_t)B * 8), o_off = o_cnt + align_up((size_t)G * 4), o_start = o_off + align_up((size_t)G * 4),
-                 o_fill = o_start + align_up((size_t)G * 4), o_scen = o_fill + align_up((size_t)G * 4), o_sof = o_scen + align_up((size_t)G * 48),
-                 o_list = o_sof + align_up((size_t)P * 4), o_claim = o_list + align_up((size_t)P * 4), o_tlist = o_claim + align_up((size_t)P * 4),
-                 o_trank = o_tlist + align_up(PW * 4), o_key = o_trank + align_up(PW * 4), o_w = o_key + align_up((size_t)P * 8),
-                 o_rows = o_w + align_up((size_t)P * 8), o_meta = o_rows + align_up(PW * 2), o_cur = o_meta + align_up((size_t)P * 2),
-                 o_slot = o_cur + align_up((size_t)P), o_rack = o_slot + align_up((size_t)P), total = o_rack + align_up((size_t)B);
-    if ((rc = arena_get(total, &m.arena, &m.cap))) return rc;
-    if ((rc = stream_get(&m.stream))) return rc;
+    Carve cv;
+    const size_t o_ctl32 = cv.take<int32_t>(FS_N), o_ctl = cv.take<u64>(WC_N), o_lead = cv.take<int32_t>(B), o_wlead = cv.take<u64>(B),
+                 o_cnt = cv.take<int32_t>(G), o_off = cv.take<int32_t>(G), zeroed = cv.end(), o_start = cv.take<int32_t>(G),
+                 o_fill = cv.take<int32_t>(G), o_scen = cv.take<u64>(6 * (size_t)G), o_sof = cv.take<int32_t>(P), o_list = cv.take<int32_t>(P),
+                 o_claim = cv.take<int32_t>(P), o_tlist = cv.take<int32_t>(PW), o_trank = cv.take<int32_t>(PW), o_key = cv.take<u64>(P),
+                 o_w = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW), o_meta = cv.take<uint16_t>(P), o_cur = cv.take<uint8_t>(P),
+                 o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
-    unsigned char *db = static_cast<unsigned char *>(m.arena);
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(db + o); };
-    auto u64p = [&](size_t o) { return reinterpret_cast<u64 *>(db + o); };
-    int32_t *d_ctl32 = i32(o_ctl32), *d_lead = i32(o_lead), *d_cnt = i32(o_cnt), *d_off = i32(o_off), *d_start = i32(o_start), *d_fill = i32(o_fill),
-            *d_sof = i32(o_sof), *d_list = i32(o_list), *d_claim = i32(o_claim);
-    uint16_t *d_rows = reinterpret_cast<uint16_t *>(db + o_rows), *d_meta = reinterpret_cast<uint16_t *>(db + o_meta);
-    uint8_t *d_cur = db + o_cur, *d_rack = db + o_rack;
-    u64 *d_wlead = u64p(o_wlead), *d_w = u64p(o_w);
+    const FoScen d{m.at<int32_t>(o_lead), m.at<int32_t>(o_sof), m.at<int32_t>(o_cnt), m.at<int32_t>(o_off), m.at<int32_t>(o_start), m.at<int32_t>(o_fill),
+                   m.at<int32_t>(o_list), m.at<int32_t>(o_claim), m.at<int32_t>(o_ctl32), m.at<uint16_t>(o_meta), m.at<uint8_t>(o_cur)};
+    uint16_t *d_rows = m.at<uint16_t>(o_rows);
+    uint8_t *d_rack = m.at<uint8_t>(o_rack);
+    u64 *d_wlead = m.at<u64>(o_wlead), *d_w = m.at<u64>(o_w);
 
-    HIP_TRY(hipMemsetAsync(db, 0, o_start, st));
+    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
     HIP_TRY(hipMemcpyAsync(d_rack, rack_of, (size_t)B, hipMemcpyHostToDevice, st));
     if (P) {
         HIP_TRY(hipMemcpyAsync(d_rows, rows, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_w, weight, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
-    const unsigned pblocks = (unsigned)((P + kFoThreads - 1) / kFoThreads);
-    int64_t launches = 0;
-    int32_t ctl32[FS_N] = {0};
+    int launches = 0, max_n = 0, threads = 0;
     if (P) {
-        k_fo_classify<<<pblocks, kFoThreads, 0, st>>>(P, W, scope, d_rows, d_rack, d_lead, d_sof, d_meta, d_cur, d_claim, d_cnt, d_off);
-        k_wfo_wlead<<<pblocks, kFoThreads, 0, st>>>(P, W, d_rows, d_w, d_wlead);
-        launches += 2;
-    }
-    k_fo_offsets<<<1, 1024, 0, st>>>(G, d_cnt, d_start, d_fill, d_ctl32);
-    ++launches;
-    if (P) {
-        k_fo_scatter<<<pblocks, kFoThreads, 0, st>>>(P, d_sof, d_meta, d_start, d_fill, d_list);
+        k_wfo_wlead<<<grid_for(P, kFoThreads), kFoThreads, 0, st>>>(P, W, d_rows, d_w, d_wlead);
         ++launches;
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ctl32, d_ctl32, sizeof ctl32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int max_n = ctl32[FS_MAXN];
-    const int threads = (int64_t)max_n * W <= kFoSmallSlots ? kFoSoloSmall : kFoSoloLarge;
-    const size_t lds = (size_t)B * 16;
-    static int lds_set[kMaxDevices] = {0};   // the largest dynamic LDS size the kernel has been opened for, per device
-    const int dev = cur_device();
-    if (lds > 32 * 1024 && dev >= 0 && dev < kMaxDevices && (int)lds > lds_set[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_wfo_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set[dev] = (int)lds;
-    }
+    const size_t lds = 2 * (size_t)B * sizeof(u64);
+    if ((rc = fo_prelude(st, P, W, G, scope, d_rows, d_rack, d, reinterpret_cast<const void *>(k_wfo_solve), lds, 32 * 1024, &launches, &max_n, &threads)))
+        return rc;
     WfNet n;
     n.B = B; n.W = W; n.scope = scope; n.dry_run = dry_run; n.max_rounds = max_rounds; n.min_gain = min_gain;
-    n.rows = d_rows; n.rack_of = d_rack; n.weight = d_w; n.wlead = d_wlead; n.meta = d_meta; n.cur = d_cur; n.slot = db + o_slot;
-    n.key = u64p(o_key); n.cnt = d_cnt; n.offl = d_off; n.start = d_start; n.list = d_list; n.tlist = i32(o_tlist); n.trank = i32(o_trank);
-    n.scen = u64p(o_scen); n.ctl = u64p(o_ctl);
+    n.rows = d_rows; n.rack_of = d_rack; n.weight = d_w; n.wlead = d_wlead; n.meta = d.meta; n.cur = d.cur; n.slot = m.at<uint8_t>(o_slot);
+    n.key = m.at<u64>(o_key); n.cnt = d.cnt; n.offl = d.off; n.start = d.start; n.list = d.list; n.tlist = m.at<int32_t>(o_tlist);
+    n.trank = m.at<int32_t>(o_trank); n.scen = m.at<u64>(o_scen); n.ctl = m.at<u64>(o_ctl);
     k_wfo_solve<<<(unsigned)G, threads, lds, st>>>(n);
     HIP_TRY(hipGetLastError());
     ++launches;

@@ -32,12 +32,10 @@
 #include <string>
 #include <vector>
 
-#include "kao_bytes_code.h"   // wave_bytes_code
 #include "kao_host.h"
+#include "kao_plan_dev.h"   // DESCENT_KEY, descent_gains, descent_bid, lane_count_to, swap_leader
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int kWlThreads = 256;
 constexpr int kWlBatch = 32;            // rounds enqueued between two reads of the proposal counts
@@ -68,12 +66,8 @@ __device__ inline void wl_max_to(u64 v, u64 *dst) {   // all 64 lanes active
     if (__lane_id() == 0 && v > 0) atomicMax(dst, v);
 }
 
-__device__ inline void wl_add_to(bool one, u64 *dst) {   // all 64 lanes active
-    const u64 m = __ballot(one);
-    if (m != 0ull && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(dst, (u64)__popcll(m));
-}
-
-// Step 1 and 2 for partition p against the loads `load`: false when p proposes nothing
+// Step 1 and 2 for partition p against the loads `load`: false when p proposes nothing (every replica but the leader is eligible;
+// wf_propose of kao_wfailover.hip reads its eligible slots from a mask, so the two loops stay apart)
 __device__ inline bool wl_propose(const WlNet &n, int p, const u64 *load, int &a, int &b, int &slot, u64 &key) {
     const u64 w = n.weight[p];
     if (w == 0) return false;
@@ -91,16 +85,9 @@ __device__ inline bool wl_propose(const WlNet &n, int p, const u64 *load, int &a
     }
     if (slot < 0) return false;
     const u64 wa = load[a];
-    // W(b*) + w + min_gain < W(a) without overflow: the loads and w stay below 2^62, min_gain is any u64
-    if (wa <= best + w || wa - best - w <= n.min_gain) return false;
-    key = (u64)(0xFFFFu - wave_bytes_code(wa)) << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)p;
+    if (!descent_gains(wa, best, w, n.min_gain)) return false;
+    key = DESCENT_KEY(wa, w, p);
     return true;
-}
-
-// a bid: atomicMin only lowers a word, so a value already at or below the key needs no atomic (all the proposals of one source
-// collide there; most of them find a lower key in place)
-__device__ inline void wl_bid(u64 *word, u64 key) {
-    if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(word, key);
 }
 
 // ---- once per call ------------------------------------------------------------------------------------------------------------------
@@ -137,12 +124,11 @@ __global__ void k_wl_propose(WlNet n, int r, uint32_t *__restrict__ count) {
         if (prop) {
             n.slot[p] = (uint8_t)slot;
             u64 *row = n.mk + (size_t)(r & 1) * n.B;
-            wl_bid(&row[a], key);
-            wl_bid(&row[b], key);
+            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[a], key);
+            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[b], key);
         }
     }
-    const u64 m = __ballot(prop);
-    if (m != 0ull && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(count, (uint32_t)__popcll(m));
+    lane_count_to(prop, count);
 }
 
 __global__ void k_wl_apply(WlNet n, int r) {
@@ -167,7 +153,7 @@ __global__ void k_wl_apply(WlNet n, int r) {
             }
         }
     }
-    wl_add_to(won, &n.ctl[U_MOVES]);
+    lane_count_to(won, &n.ctl[U_MOVES]);
 }
 
 // ---- every round in one launch: one workgroup, loads and minkey rows in LDS ---------------------------------------------------------
@@ -229,6 +215,8 @@ __global__ __launch_bounds__(kWlOneThreads) void k_wl_one(WlNet n, int max_round
 }
 
 // ---- the certificate and the result -------------------------------------------------------------------------------------------------
+// (rank, histogram and scan in three launches over all brokers; k_wfo_solve of kao_wfailover.hip ranks a compacted set inside its
+// workgroup and reuses its LDS for the histogram: not shared)
 // rank[b] = brokers ahead of b by (load descending, index ascending); the peak on the way
 __global__ __launch_bounds__(kWlThreads) void k_wl_rank(int B, const u64 *__restrict__ load, int32_t *__restrict__ rank, u64 *__restrict__ peak) {
     __shared__ u64 tile[kWlThreads];
@@ -263,13 +251,9 @@ __global__ void k_wl_finish(WlNet n, const int32_t *__restrict__ rank, u64 *__re
         if (w) atomicAdd(&hist[m], w);
         atomicAdd(&led[row[l]], 1);
         ch = l != 0;
-        if (ch && !dry_run) {
-            const uint16_t x = row[0], y = row[l];
-            row[0] = y;
-            row[l] = x;
-        }
+        if (ch && !dry_run) swap_leader(row, l);
     }
-    wl_add_to(ch, &n.ctl[U_CHANGED]);
+    lane_count_to(ch, &n.ctl[U_CHANGED]);
 }
 
 // one workgroup: A_k = hist[0] + .. + hist[k - 1], the level-set term max_k ceil(A_k / k) with the lowest k that attains it, the
@@ -310,42 +294,14 @@ __global__ __launch_bounds__(kWlThreads) void k_wl_scan(int B, const u64 *__rest
     }
 }
 
-// the device memory and the stream of one call, handed back to the runtime's pools on every return path
-struct WlBufs {
-    void *arena = nullptr;
-    size_t cap = 0;
-    hipStream_t stream = nullptr;
-    ~WlBufs() {
-        if (stream) { (void)hipStreamSynchronize(stream); stream_put(stream, cur_device()); }
-        if (arena) arena_put(arena, cap, cur_device());
-    }
-};
-
 int validate_weighted(int32_t B, int32_t P, int32_t W, const uint16_t *rows, const uint64_t *weight, const int32_t *n_changed,
                       const uint64_t *peak_before, const uint64_t *peak_after, const uint64_t *lower_bound, const int32_t *status) {
     const std::string fn = "kao_balance_leaders_weighted: ";
     if (!rows || !weight || !n_changed || !peak_before || !peak_after || !lower_bound || !status) return fail(KAO_ERR_INVALID, fn + "null pointer");
-    if (W < 1 || W > KAO_MAX_RF) return fail(KAO_ERR_INVALID, fn + "width outside 1.." + std::to_string(KAO_MAX_RF));
-    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, fn + "n_brokers outside 1..65534");
-    if (P < 0) return fail(KAO_ERR_INVALID, fn + "n_partitions < 0");
-    if ((int64_t)P * W > 4000000) return fail(KAO_ERR_UNSUPPORTED, fn + "more than 4,000,000 replica slots");
-    uint64_t total = 0;
-    for (int64_t p = 0; p < P; ++p) {
-        const uint16_t *row = rows + p * W;
-        const std::string at = fn + "partition " + std::to_string(p) + ": ";
-        if (row[0] == KAO_NONE) return fail(KAO_ERR_INVALID, at + "slot 0 holds no broker");
-        bool ended = false;
-        for (int i = 0; i < W; ++i) {
-            if (row[i] == KAO_NONE) { ended = true; continue; }
-            if (ended) return fail(KAO_ERR_INVALID, at + "a broker after an empty slot");
-            if (row[i] >= B) return fail(KAO_ERR_INVALID, at + "broker index >= n_brokers");
-            for (int j = 0; j < i; ++j)
-                if (row[j] == row[i]) return fail(KAO_ERR_INVALID, at + "broker repeated in a row");
-        }
-        // every load and every W(b*) + weight of the kernels then stays below 2^63
-        if (__builtin_add_overflow(total, weight[p], &total) || total >= (uint64_t(1) << 62)) return fail(KAO_ERR_INVALID, at + "the weights sum to 2^62 or more");
-    }
-    return KAO_OK;
+    int rc = check_dims(fn, B, P, W);
+    if (!rc) rc = check_slot_cap(fn, P, W);
+    if (!rc) rc = check_rows(fn, B, P, W, rows);
+    return rc ? rc : check_weight_sum(fn, P, weight);
 }
 
 }  // namespace
@@ -367,36 +323,32 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
     const bool one = t_wl_path == 1 || (t_wl_path == 0 && B <= kWlOneMaxB && P <= kWlOneMaxP);
     if (one && B > kWlOneMaxB) return fail(KAO_ERR_UNSUPPORTED, "kao_balance_leaders_weighted: the single-workgroup path holds at most " + std::to_string(kWlOneMaxB) + " brokers");
 
-    WlBufs m;
     // one arena: ctl u64[U_N] | count u32[kWlBatch] | load, forced, hist u64[B] | led, rank i32[B] (zeroed up to here) | mk u64[2B]
     //            (all ones) | key, weight u64[P] | rows u16[PW] | lead, slot u8[P]
-    const size_t o_ctl = 0, o_cnt = o_ctl + align_up(U_N * 8), o_load = o_cnt + align_up(kWlBatch * 4), o_forced = o_load + align_up((size_t)B * 8),
-                 o_hist = o_forced + align_up((size_t)B * 8), o_led = o_hist + align_up((size_t)B * 8), o_rank = o_led + align_up((size_t)B * 4),
-                 o_mk = o_rank + align_up((size_t)B * 4), o_key = o_mk + align_up((size_t)B * 16), o_w = o_key + align_up((size_t)P * 8),
-                 o_rows = o_w + align_up((size_t)P * 8), o_lead = o_rows + align_up((size_t)PW * 2), o_slot = o_lead + align_up((size_t)P),
-                 total = o_slot + align_up((size_t)P);
-    if ((rc = arena_get(total, &m.arena, &m.cap))) return rc;
-    if ((rc = stream_get(&m.stream))) return rc;
+    Carve cv;
+    const size_t o_ctl = cv.take<u64>(U_N), o_cnt = cv.take<uint32_t>(kWlBatch), o_load = cv.take<u64>(B), o_forced = cv.take<u64>(B),
+                 o_hist = cv.take<u64>(B), o_led = cv.take<int32_t>(B), o_rank = cv.take<int32_t>(B), zeroed = cv.end(),
+                 o_mk = cv.take<u64>(2 * (size_t)B), o_key = cv.take<u64>(P), o_w = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW),
+                 o_lead = cv.take<uint8_t>(P), o_slot = cv.take<uint8_t>(P);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
-    unsigned char *db = static_cast<unsigned char *>(m.arena);
-    auto u64p = [&](size_t o) { return reinterpret_cast<u64 *>(db + o); };
-    uint16_t *d_rows = reinterpret_cast<uint16_t *>(db + o_rows);
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(db + o_cnt);
-    int32_t *d_led = reinterpret_cast<int32_t *>(db + o_led), *d_rank = reinterpret_cast<int32_t *>(db + o_rank);
-    u64 *d_forced = u64p(o_forced), *d_hist = u64p(o_hist);
+    uint16_t *d_rows = m.at<uint16_t>(o_rows);
+    uint32_t *d_cnt = m.at<uint32_t>(o_cnt);
+    int32_t *d_led = m.at<int32_t>(o_led), *d_rank = m.at<int32_t>(o_rank);
+    u64 *d_forced = m.at<u64>(o_forced), *d_hist = m.at<u64>(o_hist);
     WlNet n;
     n.P = P; n.W = W; n.B = B; n.min_gain = min_gain;
-    n.rows = d_rows; n.weight = u64p(o_w); n.lead = db + o_lead; n.slot = db + o_slot; n.key = u64p(o_key); n.load = u64p(o_load);
-    n.mk = u64p(o_mk); n.ctl = u64p(o_ctl);
+    n.rows = d_rows; n.weight = m.at<u64>(o_w); n.lead = m.at<uint8_t>(o_lead); n.slot = m.at<uint8_t>(o_slot); n.key = m.at<u64>(o_key);
+    n.load = m.at<u64>(o_load); n.mk = m.at<u64>(o_mk); n.ctl = m.at<u64>(o_ctl);
 
-    HIP_TRY(hipMemsetAsync(db, 0, o_mk, st));
-    HIP_TRY(hipMemsetAsync(db + o_mk, 0xFF, (size_t)B * 16, st));
+    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
+    HIP_TRY(hipMemsetAsync(n.mk, 0xFF, 2 * (size_t)B * sizeof(u64), st));
     if (P) {
         HIP_TRY(hipMemcpyAsync(d_rows, rows, (size_t)PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(db + o_w, weight, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<u64>(o_w), weight, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
-    auto blocks = [](int x) { return (unsigned)((std::max(x, 1) + kWlThreads - 1) / kWlThreads); };
-    const unsigned pblocks = blocks(P), bblocks = blocks(B);
+    const unsigned pblocks = grid_for(P, kWlThreads), bblocks = grid_for(B, kWlThreads);
     int64_t launches = 0, rounds = 0, props = 0;
     bool more = false;
     if (P) {
@@ -409,7 +361,7 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
 
     if (one) {
         if (P) {
-            k_wl_one<<<1, kWlOneThreads, (size_t)B * 24, st>>>(n, max_rounds);
+            k_wl_one<<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(n, max_rounds);
             ++launches;
             HIP_TRY(hipGetLastError());
         }

@@ -20,7 +20,6 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import json
-import re
 import sys
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -28,6 +27,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
+from ._plan_args import _racks, count, dense_rows, u64, weight_arg, weight_buffer
 from .model import NONE, Topic
 from .solver import STATUS_NAMES, _check
 
@@ -81,17 +81,18 @@ def _scope(scope) -> int:
     return SCOPES[scope]
 
 
-def failover_order_arrays(rows, n_brokers: int, rack_of, n_racks: int, scope, dry_run: bool = False) -> FailoverResult:
-    """kao_failover_order on dense rows ([P, width], NONE-padded, slot 0 = preferred leader)."""
-    scope = _scope(scope)
-    r = np.array(rows, dtype=np.uint16, order="C")
-    if r.ndim != 2:
-        raise ValueError("rows must be a [P, width] array")
+def _rack_buffer(rack_of, n_brokers) -> np.ndarray:
     rk = np.ascontiguousarray(rack_of, dtype=np.uint8)
     if rk.shape != (int(n_brokers),):
         raise ValueError(f"rack_of must hold one rack per broker ({n_brokers}), got shape {rk.shape}")
-    P, W = r.shape
-    flat = r.reshape(-1) if r.size else np.zeros(1, dtype=np.uint16)
+    return rk
+
+
+def failover_order_arrays(rows, n_brokers: int, rack_of, n_racks: int, scope, dry_run: bool = False) -> FailoverResult:
+    """kao_failover_order on dense rows ([P, width], NONE-padded, slot 0 = preferred leader)."""
+    scope = _scope(scope)
+    r, flat, P, W = dense_rows(rows)
+    rk = _rack_buffer(rack_of, n_brokers)
     n_scen = int(n_brokers) if scope == 0 else int(n_racks)
     scen = np.zeros((max(n_scen, 1), 5), dtype=np.int32)
     stats = np.zeros(8, dtype=np.int32)
@@ -108,25 +109,9 @@ def failover_order_weighted_arrays(rows, n_brokers: int, rack_of, n_racks: int, 
     """kao_failover_order_weighted on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); weight[p] is the traffic of
     row p."""
     scope = _scope(scope)
-    r = np.array(rows, dtype=np.uint16, order="C")
-    if r.ndim != 2:
-        raise ValueError("rows must be a [P, width] array")
-    rk = np.ascontiguousarray(rack_of, dtype=np.uint8)
-    if rk.shape != (int(n_brokers),):
-        raise ValueError(f"rack_of must hold one rack per broker ({n_brokers}), got shape {rk.shape}")
-    P, W = r.shape
-    wt = np.asarray(weight).reshape(-1)
-    if wt.shape != (P,):
-        raise ValueError(f"weight must hold one value per row ({P}), got {wt.shape[0]}")
-    if P and wt.dtype.kind not in "ui":
-        raise ValueError("weights must be integers")
-    if P and wt.dtype.kind == "i" and (wt < 0).any():
-        raise ValueError("weights must be >= 0")
-    if not 0 <= int(min_gain) < 1 << 64:
-        raise ValueError("min_gain must be 0..2^64-1")
-    wt = np.ascontiguousarray(wt, dtype=np.uint64)
-    flat = r.reshape(-1) if r.size else np.zeros(1, dtype=np.uint16)
-    wbuf = wt if P else np.zeros(1, dtype=np.uint64)
+    r, flat, P, W = dense_rows(rows)
+    rk = _rack_buffer(rack_of, n_brokers)
+    wbuf = weight_buffer(weight, P, min_gain)
     n_scen = int(n_brokers) if scope == 0 else int(n_racks)
     scen = np.zeros((max(n_scen, 1), 6), dtype=np.uint64)
     stats = np.zeros(8, dtype=np.int64)
@@ -305,16 +290,9 @@ def report_lines(plan: FailoverPlan) -> List[str]:
     return out
 
 
-def _racks(arg: str) -> dict:
-    if ":" in arg and "{" not in arg and not arg.endswith(".json"):
-        return {int(k): v for k, v in (kv.split(":") for kv in arg.split(",") if kv)}
-    with open(arg) as f:
-        return {int(k): str(v) for k, v in json.load(f).items()}
-
-
 def main(argv=None) -> int:
     """Python twin of cli/kao-failover: same flags, same bytes, same exit status (0 ok, 1 error, 2 usage)."""
-    from .leaders import MAX_WEIGHT, parse_traffic, plan_text, weights_for
+    from .leaders import parse_traffic, plan_text, weights_for
     ap = argparse.ArgumentParser(prog="kao-failover", description="follower order that keeps the peak leader count after a failure lowest; moves no data")
     ap.add_argument("--current", required=True, help="reassignment JSON of the cluster as it is")
     ap.add_argument("--broker-list", required=True, help="brokers of the cluster, CSV")
@@ -324,21 +302,6 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
-
-    def count(text):   # as cli/kao-failover reads a count: digits only
-        if not re.fullmatch(r"[0-9]{1,9}", text):
-            raise argparse.ArgumentTypeError("needs a value >= 0")
-        return int(text)
-
-    def u64(text):
-        if not re.fullmatch(r"[0-9]{1,20}", text) or int(text) >= 1 << 64:
-            raise argparse.ArgumentTypeError("needs a value 0..2^64-1")
-        return int(text)
-
-    def weight_arg(text):
-        if not re.fullmatch(r"[0-9]{1,16}", text) or int(text) > MAX_WEIGHT:
-            raise argparse.ArgumentTypeError("needs a value 0..2^53")
-        return int(text)
 
     ap.add_argument("--traffic", default=None, help='weigh the partitions: {"version":1,"partitions":[{"topic":..,"partition":..,"weight":N}]}')
     ap.add_argument("--sizes", default=None, help="weigh the partitions by their size: kafka-log-dirs --describe output")

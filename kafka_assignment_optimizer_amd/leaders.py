@@ -23,7 +23,6 @@ import argparse
 import ctypes as C
 import dataclasses
 import json
-import re
 import sys
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -31,6 +30,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _ffi
+from ._plan_args import MAX_WEIGHT, _racks, count, dense_rows, u64, weight_arg, weight_buffer
 from .model import NONE, Topic, topics_from_json
 from .solver import STATUS_NAMES, _check, _CTopics
 
@@ -103,10 +103,7 @@ def balance_leaders_cluster_arrays(rows, n_brokers: int, topic_of, topic_lo, top
                                    dry_run: bool = False) -> ClusterLeaderResult:
     """kao_balance_leaders_cluster on dense rows ([P, width], NONE-padded, slot 0 = preferred leader) of all topics over one
     broker index; topic_of[p] is the topic of row p, topic_lo / topic_hi the topics' bands."""
-    r = np.array(rows, dtype=np.uint16, order="C")
-    if r.ndim != 2:
-        raise ValueError("rows must be a [P, width] array")
-    P, W = r.shape
+    r, flat, P, W = dense_rows(rows)
     tof = np.ascontiguousarray(topic_of, dtype=np.int32).reshape(-1)
     if tof.shape != (P,):
         raise ValueError(f"topic_of must hold one topic per row ({P}), got {tof.shape[0]}")
@@ -114,7 +111,6 @@ def balance_leaders_cluster_arrays(rows, n_brokers: int, topic_of, topic_lo, top
     thi = np.ascontiguousarray(topic_hi, dtype=np.int32).reshape(-1)
     if tlo.shape != thi.shape:
         raise ValueError("topic_lo and topic_hi must have one entry per topic each")
-    flat = r.reshape(-1) if r.size else np.zeros(1, dtype=np.uint16)
     tof_buf = tof if P else np.zeros(1, dtype=np.int32)
     n, before, after, status = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
     stats = np.zeros(8, dtype=np.int32)
@@ -175,9 +171,6 @@ def cluster_report_line(res: ClusterLeaderResult) -> str:
             f"probes={s[0]} phases={s[1]} rounds={s[2]} paths={s[3]} longest_path={s[4]} launches={s[5]} pair_nodes={s[6]} unrouted={s[7]}")
 
 
-MAX_WEIGHT = 1 << 53   # weights above it are not exact as JSON doubles (the C++ reader): rejected, never rounded
-
-
 @dataclass
 class WeightedLeaderResult:
     rows: np.ndarray         # [P, width] uint16: the input rows, slot 0 swapped with the chosen leader's slot (untouched with dry_run)
@@ -202,22 +195,8 @@ def balance_leaders_weighted_arrays(rows, n_brokers: int, weight, min_gain: int 
                                     dry_run: bool = False) -> WeightedLeaderResult:
     """kao_balance_leaders_weighted on dense rows ([P, width], NONE-padded, slot 0 = preferred leader) of all topics over one
     broker index; weight[p] is the traffic of row p."""
-    r = np.array(rows, dtype=np.uint16, order="C")
-    if r.ndim != 2:
-        raise ValueError("rows must be a [P, width] array")
-    P, W = r.shape
-    wt = np.asarray(weight).reshape(-1)
-    if wt.shape != (P,):
-        raise ValueError(f"weight must hold one value per row ({P}), got {wt.shape[0]}")
-    if P and wt.dtype.kind not in "ui":
-        raise ValueError("weights must be integers")
-    if P and wt.dtype.kind == "i" and (wt < 0).any():
-        raise ValueError("weights must be >= 0")
-    if not 0 <= int(min_gain) < 1 << 64:
-        raise ValueError("min_gain must be 0..2^64-1")
-    wt = np.ascontiguousarray(wt, dtype=np.uint64)
-    flat = r.reshape(-1) if r.size else np.zeros(1, dtype=np.uint16)
-    wbuf = wt if P else np.zeros(1, dtype=np.uint64)
+    r, flat, P, W = dense_rows(rows)
+    wbuf = weight_buffer(weight, P, min_gain)
     n, status = C.c_int32(0), C.c_int32(0)
     before, after, bound = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     stats = np.zeros(8, dtype=np.int64)
@@ -319,13 +298,6 @@ def plan_text(entries) -> str:
     return '{"version":1,"partitions":[' + "".join(("\n" if i == 0 else ",\n") + r for i, r in enumerate(rows)) + "\n]}\n"
 
 
-def _racks(arg: str) -> dict:
-    if ":" in arg and "{" not in arg and not arg.endswith(".json"):
-        return {int(k): v for k, v in (kv.split(":") for kv in arg.split(",") if kv)}
-    with open(arg) as f:
-        return {int(k): str(v) for k, v in json.load(f).items()}
-
-
 def main(argv=None) -> int:
     """Python twin of cli/kao-leaders: same flags, same bytes, same exit status (0 ok, 1 error or infeasible, 2 usage)."""
     ap = argparse.ArgumentParser(prog="kao-leaders", description="fewest preferred-leader changes that balance the leaders; moves no data")
@@ -335,21 +307,6 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
-    def count(text):   # as cli/kao-leaders reads a count: digits only
-        if not re.fullmatch(r"[0-9]{1,9}", text):
-            raise argparse.ArgumentTypeError("needs a value >= 0")
-        return int(text)
-
-    def u64(text):
-        if not re.fullmatch(r"[0-9]{1,20}", text) or int(text) >= 1 << 64:
-            raise argparse.ArgumentTypeError("needs a value 0..2^64-1")
-        return int(text)
-
-    def weight_arg(text):
-        if not re.fullmatch(r"[0-9]{1,16}", text) or int(text) > MAX_WEIGHT:
-            raise argparse.ArgumentTypeError("needs a value 0..2^53")
-        return int(text)
-
     ap.add_argument("--slack", type=int, default=None, help="widen the leader band by N on both sides")
     ap.add_argument("--auto-slack", action="store_true", help="use the smallest slack >= --slack that is feasible, per topic")
     ap.add_argument("--cluster", action="store_true", help="balance the leaders of all topics together: lowest cluster-wide peak, topic bands kept")

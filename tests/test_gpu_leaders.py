@@ -82,6 +82,21 @@ def test_ring_family_matches_highs(kao, seed, B, P):
     assert res.stats[3] >= 2   # leadership travels over several arcs
 
 
+# Both sides of the regime choice at the smallest size that reaches it: 65,535 replica slots run in the single workgroup, 65,538 in
+# the per-round launches (whose rounds the host settles batch by batch).  HiGHS optimum per case.
+@pytest.mark.parametrize("P,optimum,solo", [(21845, 8226, True), (21846, 8530, False)])
+def test_regime_threshold_matches_highs_and_the_model(kao, P, optimum, solo):
+    rows, B, lo, hi = lr.ring_instance(0, 60, P)
+    assert rows.size == 3 * P
+    opt = lr.lp_optimum(rows, B, lo, hi)
+    assert opt == optimum
+    res = _checked(kao, _topic(rows, B, lo, hi), opt, model=True)
+    if solo:
+        assert res.stats[6] == 1
+    else:
+        assert res.stats[6] > res.stats[1]   # one launch per round
+
+
 def _restricted_exact(ko, t):
     """HiGHS on the README model of product topic `t` with every variable of a broker that holds no replica of the partition fixed
     to 0 (one cut row) and the replica, rack and partition-rack bands opened: the model kao_balance_leaders solves."""

@@ -6,9 +6,11 @@
 
 A kernel is the text from its label to the end of its function: the instructions and the .amdhsa_* descriptor (registers, scratch, LDS).
 Comments, blank lines, .file / .ident lines and the __hip_cuid_* symbol are ignored, and the function number in local labels (.LBB12_3 ->
-.LBB_3) is dropped, so a kernel may move between translation units.  Exit status 0 iff both sides hold the same kernel names and every
+.LBB_3) is dropped, so a kernel may move between translation units.  A kernel of an unnamed namespace that several files define (a
+shared header) is compared per file.  Exit status 0 iff both sides hold the same kernel names and every
 kernel compares equal."""
 import argparse
+import os
 import re
 import sys
 
@@ -17,7 +19,7 @@ LOCAL = re.compile(r"\.L(BB|func_end|func_begin|post_getpc|JTI|CPI|tmp)(\d+)")
 
 
 def kernels(paths):
-    out = {}
+    found = []
     for path in paths:
         lines = open(path).read().split("\n")
         names = {m.group(1) for m in (re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l) for l in lines) if m}
@@ -33,8 +35,16 @@ def kernels(paths):
             if text.strip() and not re.match(r"\s*\.(file|ident)\b", text) and "__hip_cuid_" not in text:
                 body.append(LOCAL.sub(lambda g: ".L" + g.group(1), text))
             if re.match(r"\.Lfunc_end\d+:", line):
-                assert name not in out, "kernel defined twice: " + name
-                out[name], name = body, None
+                found.append((name, os.path.basename(path), body))
+                name = None
+    count = {}
+    for name, _, _ in found:
+        count[name] = count.get(name, 0) + 1
+    out = {}
+    for name, base, body in found:
+        key = name if count[name] == 1 else name + " in " + base
+        assert key not in out, "kernel defined twice: " + key
+        out[key] = body
     return out
 
 
