@@ -1,4 +1,4 @@
-// kao_cluster.h -- what kao-leaders and kao-failover share: the --broker-list / --racks arguments as kao-cli reads them, the rows of
+// kao_cluster.h -- what kao-leaders, kao-failover and kao-disk share: the --broker-list / --racks arguments as kao-cli reads them, the rows of
 // a reassignment document over that broker index, and the reassignment documents they write.
 #pragma once
 #include <algorithm>

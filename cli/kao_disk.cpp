@@ -1,0 +1,130 @@
+// kao-disk -- disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk, DESIGN.md
+// section 4m).
+//
+//   kao-disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt [--default-size N]
+//            [--max-per-rack N] [--keep-leaders] [--min-gain BYTES] [--max-rounds N] [--dry-run] --out plan.json [--report] [--device D]
+//
+// Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
+// output or a sizes document, as kao-waves reads them) and moves replicas to brokers outside their row until no single move closes a
+// gap of more than --min-gain bytes (N, or N with K/M/G/T).  A move keeps its slot, so the follower order stays; --keep-leaders keeps
+// every preferred leader where it is; --max-per-rack N lets no move raise a partition's count in a rack above N (counts already
+// above it may stay).  The rows of all topics are taken together over one broker index.  --default-size N sizes the partitions the
+// file does not name (without it they are an error).  The answer is a deterministic descent with a lower bound beside it: where
+// peak_after == lower_bound the peak is proven optimal.  The plan holds the changed rows only and is what kao-waves --plan takes;
+// --dry-run reports and leaves the plan empty.  All computation happens in libkao.so on the GPU.
+// Exit status: 0 = ok, 1 = error, 2 = usage.
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../include/kao.h"
+#include "kao_cluster.h"
+#include "kao_json.h"
+#include "kao_sizes.h"
+
+namespace {
+
+[[noreturn]] void usage(const char *msg) {
+    if (msg) std::fprintf(stderr, "kao-disk: %s\n", msg);
+    std::fprintf(stderr,
+        "usage: kao-disk --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
+        "                --sizes <kafka-log-dirs output | sizes.json> [--default-size N] [--max-per-rack N] [--keep-leaders]\n"
+        "                [--min-gain N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report] [--device D]\n"
+        "writes the partitions whose replicas move; exit status: 0 = ok, 1 = error, 2 = usage\n");
+    std::exit(2);
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path;
+    int device = 0, max_per_rack = 0, max_rounds = 0;
+    bool report = false, dry_run = false, keep_leaders = false, have_default = false;
+    uint64_t default_size = 0, min_gain = 0;
+    auto count_arg = [](const std::string &v, const char *msg) {
+        if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
+        return std::atoi(v.c_str());
+    };
+    for (int i = 1; i < argc; ++i) {
+        std::string a = argv[i];
+        auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
+        if (a == "--current") cur_path = need("--current");
+        else if (a == "--broker-list") brokers_csv = need("--broker-list");
+        else if (a == "--racks") racks_arg = need("--racks");
+        else if (a == "--sizes") sizes_path = need("--sizes");
+        else if (a == "--out") out_path = need("--out");
+        else if (a == "--dry-run") dry_run = true;
+        else if (a == "--keep-leaders") keep_leaders = true;
+        else if (a == "--device") device = std::atoi(need("--device").c_str());
+        else if (a == "--report") report = true;
+        else if (a == "--default-size") {
+            if (!parse_bytes(need("--default-size"), default_size) || default_size > kMaxSize) usage("--default-size needs a byte count up to 2^53");
+            have_default = true;
+        } else if (a == "--min-gain") {
+            if (!parse_bytes(need("--min-gain"), min_gain)) usage("--min-gain needs a byte count (N, or N with K/M/G/T)");
+        } else if (a == "--max-per-rack") max_per_rack = count_arg(need("--max-per-rack"), "--max-per-rack needs a value >= 0");
+        else if (a == "--max-rounds") max_rounds = count_arg(need("--max-rounds"), "--max-rounds needs a value >= 0");
+        else if (a == "-h" || a == "--help") usage(nullptr);
+        else usage(("unknown flag " + a).c_str());
+    }
+    if (cur_path.empty() || brokers_csv.empty() || racks_arg.empty() || sizes_path.empty() || out_path.empty())
+        usage("--current, --broker-list, --racks, --sizes and --out are required");
+    try {
+        const Cluster cl = read_cluster(brokers_csv, racks_arg);
+        const ClusterRows cr = read_rows(cur_path, cl);
+        const int P = (int)cr.keys.size(), B = (int)cl.brokers.size(), W = cr.width;
+        std::vector<uint64_t> size((size_t)std::max(P, 1), 0);
+        {
+            const std::map<Key, uint64_t> known = load_sizes(sizes_path);
+            std::vector<std::string> missing;
+            for (int p = 0; p < P; ++p) {
+                auto it = known.find(cr.keys[(size_t)p]);
+                if (it != known.end()) size[(size_t)p] = it->second;
+                else if (have_default) size[(size_t)p] = default_size;
+                else missing.push_back(cr.keys[(size_t)p].first + "-" + std::to_string(cr.keys[(size_t)p].second));
+            }
+            if (!missing.empty()) {
+                std::string msg = "no size for partitions ";
+                for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + missing[i];
+                if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
+                throw std::runtime_error(msg + " (give them in --sizes or set --default-size)");
+            }
+        }
+        int rc = kao_init(device);
+        if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+
+        std::vector<uint16_t> rows = cr.rows;
+        int32_t n_moved = 0, status = 0;
+        uint64_t bytes_moved = 0, before = 0, after = 0, bound = 0;
+        int64_t stats[8] = {0};
+        rc = kao_balance_disk(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1, min_gain,
+                              max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
+        if (rc) throw std::runtime_error(std::string("kao_balance_disk: ") + kao_strerror(rc) + " " + kao_last_error());
+        if (report) {
+            static const char *const terms[3] = {"largest_partition", "mean_load", "fixed_leaders"};
+            unsigned long long total = 0;
+            for (int p = 0; p < P; ++p)
+                for (int j = 0; j < W && cr.rows[(size_t)p * W + j] != KAO_NONE; ++j) total += size[(size_t)p];
+            std::fprintf(stderr, "disk: status=%s peak_before=%llu peak_after=%llu lower_bound=%llu bound_term=%s replicas_moved=%d bytes_moved=%llu "
+                                 "bytes_total=%llu rows_changed=%lld brokers_changed=%lld rounds=%lld moves=%lld launches=%lld\n",
+                         status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", (unsigned long long)before, (unsigned long long)after,
+                         (unsigned long long)bound, terms[stats[6] >= 0 && stats[6] < 3 ? stats[6] : 0], n_moved, (unsigned long long)bytes_moved, total,
+                         (long long)stats[4], (long long)stats[7], (long long)stats[0], (long long)stats[1], (long long)stats[3]);
+        }
+        const std::string text = changed_rows_text(cr, rows, cl.brokers);
+        std::ofstream f(out_path);
+        f << text;
+        f.close();
+        if (!f) throw std::runtime_error("cannot write " + out_path);
+        kao_shutdown();
+        return 0;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "kao-disk: %s\n", e.what());
+        return 1;
+    }
+}

@@ -1,10 +1,13 @@
-// kao_sizes.h -- what kao-waves, kao-leaders and kao-failover share: partition sizes read from `kafka-log-dirs --describe` output or a
+// kao_sizes.h -- what kao-waves, kao-leaders, kao-failover and kao-disk share: partition sizes read from `kafka-log-dirs --describe` output or a
 // sizes document (kao-waves --sizes, kao-leaders --sizes, kao-failover --sizes), and the traffic document of kao-leaders --traffic and
-// kao-failover --traffic.
+// kao-failover --traffic; byte counts with a K / M / G / T suffix (kao-waves --max-bytes-per-broker, kao-disk --min-gain).
 #pragma once
 #include <algorithm>
+#include <cctype>
+#include <cerrno>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <sstream>
 #include <stdexcept>
@@ -16,6 +19,26 @@
 using Key = std::pair<std::string, int>;   // (topic, partition)
 
 constexpr uint64_t kMaxSize = uint64_t(1) << 53;   // JSON numbers are doubles here: exact up to 2^53, larger sizes are rejected
+
+// N, or N with a K / M / G / T suffix (powers of 1024), below 2^64; false when it is not one
+inline bool parse_bytes(const std::string &text, uint64_t &out) {
+    std::string t = text;
+    uint64_t mult = 1;
+    if (!t.empty()) {
+        const char c = (char)std::toupper((unsigned char)t.back());
+        const char *units = "KMGT", *u = std::strchr(units, c);
+        if (c && u) {
+            for (int i = 0; i <= u - units; ++i) mult *= 1024;
+            t.pop_back();
+        }
+    }
+    if (t.empty() || t.size() > 20 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+    errno = 0;
+    const unsigned long long v = std::strtoull(t.c_str(), nullptr, 10);
+    if (errno == ERANGE || (mult > 1 && v > UINT64_MAX / mult)) return false;
+    out = (uint64_t)v * mult;
+    return true;
+}
 
 inline uint64_t size_value(const JValue *v, const std::string &what) {
     uint64_t x = 0;

@@ -62,26 +62,6 @@ std::vector<std::pair<Key, std::vector<int>>> entries(const std::string &path, c
     return out;
 }
 
-// N, or N with a K / M / G / T suffix (powers of 1024), below 2^64; false when it is not one
-bool parse_bytes(const std::string &text, uint64_t &out) {
-    std::string t = text;
-    uint64_t mult = 1;
-    if (!t.empty()) {
-        const char c = (char)std::toupper((unsigned char)t.back());
-        const char *units = "KMGT", *u = std::strchr(units, c);
-        if (c && u) {
-            for (int i = 0; i <= u - units; ++i) mult *= 1024;
-            t.pop_back();
-        }
-    }
-    if (t.empty() || t.size() > 20 || t.find_first_not_of("0123456789") != std::string::npos) return false;
-    errno = 0;
-    const unsigned long long v = std::strtoull(t.c_str(), nullptr, 10);
-    if (errno == ERANGE || (mult > 1 && v > UINT64_MAX / mult)) return false;
-    out = (uint64_t)v * mult;
-    return true;
-}
-
 // participants of one partition and their copies of it: 1 at each added broker, n_added at the source; empty when it moves no data
 std::vector<std::pair<int, uint64_t>> traffic(const uint16_t *c, const uint16_t *t, size_t W) {
     std::vector<std::pair<int, uint64_t>> out;

@@ -594,6 +594,48 @@ int kao_failover_order_weighted(int32_t n_brokers, int32_t n_racks, const uint8_
                                 uint64_t *scen /* [n_scen*6] */, int32_t *n_reordered, int32_t *status,
                                 int64_t stats[8] /* may be NULL */);
 
+/* ---- Disk-usage balance ---------------------------------------------------------------------------------
+ * Every planner above treats a replica as one unit or moves no data; here partition p stores size[p] bytes (a uint64_t) on every
+ * broker of its row, S(b) = the sum of size[p] over the rows that contain b, and replicas MOVE to lower max_b S(b).  Rows as for
+ * kao_failover_order: `width` (1..KAO_MAX_RF) entries per partition over ONE broker index, all topics concatenated, row p = k_p >= 1
+ * distinct dense indices < n_brokers, then KAO_NONE padding; slot 0 is the preferred leader; rack_of[b] < n_racks; the sum of
+ * k_p * size[p] stays below 2^62.
+ * A move takes the replica in slot j of row p from broker a to broker c; the slot keeps its place in the row.  Slot 0 may move only
+ * when move_leaders != 0 (the preferred leadership goes with it).  c is admissible for (p, j) iff c is not in row p and
+ * (max_per_rack <= 0, or rack_of[c] == rack_of[a], or row p holds fewer than max_per_rack brokers of rack_of[c]): a partition's count
+ * in a rack never rises above max(max_per_rack, its count there in the input).
+ * Synchronous rounds, each using the loads as they stand at its start.  The brokers are ranked by S descending (ties: index
+ * ascending; rank 0 is the heaviest).  Every partition with size[p] > 0 makes at most one proposal: it takes its movable slots in
+ * ascending rank of their broker; for slot j on a of rank r, c1 = the first admissible broker among the ranks n_brokers-1-r,
+ * n_brokers-2-r, .., r+1, and the proposal is (p, j, a -> c1) iff S(c1) + size[p] + min_gain < S(a); otherwise c2 = the first
+ * admissible broker among the ranks n_brokers-1, n_brokers-2, .., n_brokers-r, under the same test; otherwise the next slot.  A
+ * proposal wins iff its key rank(a) << 48 | (0xFFFF - code(size[p])) << 32 | p (code: the 16-bit logarithmic code of section 4k) is
+ * the lowest of all proposals of the round that touch a and of all that touch its destination; all winners are applied together.
+ * The rounds end when one has no proposal, or after max_rounds rounds (<= 0: no limit).  Every move lowers the sum of S^2 and leaves
+ * both loads below the old S(a): the rounds end, the peak never rises, and the end state is move-stable (no single admissible move
+ * closes a gap of more than min_gain).
+ * Rows are rewritten in place; dry_run != 0 leaves them untouched and reports the same numbers.  *n_moved = the sum over p of
+ * |final set of row p - input set of row p| (the copies Kafka must make; a replica that left and came back counts 0), *bytes_moved
+ * the same sum weighted by size[p]; *peak_before / *peak_after = max_b S(b) before / after.  *lower_bound holds for every outcome
+ * the moves can reach: the maximum of (0) max_p size[p], (1) ceil(sum of k_p * size[p] / n_brokers), (2) with move_leaders == 0, the
+ * largest sum of the slot-0 replicas of one broker.  *status = KAO_STATUS_OPTIMAL_PROVEN iff *peak_after == *lower_bound, else
+ * KAO_STATUS_FEASIBLE_BOUND_GAP; the return code is KAO_OK either way (the proof covers the peak, not the bytes moved).  There is no
+ * seed: the result depends on the input alone.
+ * stats (may be NULL): [0] rounds that had a proposal, [1] moves applied, [2] proposals summed over the rounds, [3] kernel
+ * launches, [4] partitions whose row changed, [5] 1 = stopped by max_rounds with a proposal left, [6] the term that gives the bound
+ * (0, 1, 2 as numbered above; the lowest on ties), [7] brokers whose load changed.  Checked on the host before any device is used:
+ * KAO_ERR_INVALID for a null pointer (stats excepted), width outside 1..KAO_MAX_RF, n_brokers outside 1..65534, n_racks outside
+ * 1..KAO_MAX_RACKS, n_partitions < 0, rack_of[b] >= n_racks, slot 0 not a broker, a broker after a KAO_NONE, an index >= n_brokers,
+ * a broker twice in one row, replica sizes that sum to 2^62 or more; KAO_ERR_UNSUPPORTED for n_partitions * width > 4,000,000 or
+ * n_brokers > KAO_DISK_MAX_BROKERS (every round ranks the brokers by comparing all pairs). */
+#define KAO_DISK_MAX_BROKERS 8000
+int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
+                     uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *size /* [n_partitions] */,
+                     int32_t max_per_rack /* <= 0: no rack rule */, int32_t move_leaders, uint64_t min_gain,
+                     int32_t max_rounds /* <= 0: no limit */, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                     uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *status,
+                     int64_t stats[8] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

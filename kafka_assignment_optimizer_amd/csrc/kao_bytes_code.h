@@ -1,5 +1,5 @@
-// kao_bytes_code.h -- the monotone 16-bit code of a 64-bit quantity that the wave planner (kao_waves.hip) and the traffic-weighted
-// leader balance (kao_wleaders.hip) put into their priority keys.  Device code only.
+// kao_bytes_code.h -- the monotone 16-bit code of a 64-bit quantity that the wave planner (kao_waves.hip), the traffic-weighted
+// planners (kao_wleaders.hip, kao_wfailover.hip) and the disk-usage balance (kao_disk.hip) put into their priority keys.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,393 @@
+// kao_disk.hip -- kao_balance_disk: replica moves that lower the peak of the bytes a broker stores, S(b) = sum of size[p] over the
+// rows that contain b.  Kernels and the C entry point.
+//
+// A move takes the replica in slot j of row p from broker a to a broker c OUTSIDE the row; the slot keeps its place.  c is
+// admissible iff it is not in the row and (no rack rule, or rack(c) == rack(a), or the row holds fewer than max_per_rack brokers of
+// rack(c)).  Slot 0 moves only with move_leaders.  Minimising the peak is makespan scheduling (NP-hard), so this is the deterministic
+// parallel DESCENT of section 4k with another move, and a lower bound beside it.  A ROUND uses the loads as they stand at its start:
+//   1. RANK the brokers by S descending (ties: index ascending); order[r] = the broker of rank r;
+//   2. every partition with size > 0 takes its movable slots heaviest broker first; for slot j on a of rank r, c1 = the first
+//      admissible broker among the ranks B-1-r, B-2-r, .., r+1 (the i-th heaviest is paired with the i-th lightest, then the walk goes
+//      toward the heavier); it PROPOSES (p, j, a -> c1) iff S(c1) + size + min_gain < S(a); otherwise c2 = the first admissible among
+//      the ranks B-1, B-2, .., B-r (the lighter ones the first walk skipped) under the same test; otherwise the next slot.  A walk
+//      stops at its first admissible broker: every later one is heavier;
+//   3. key = rank(a) << 48 | (0xFFFF - code(size[p])) << 32 | p, code = wave_bytes_code: the heaviest source (exact), then the heaviest
+//      partition, then the lowest index;
+//   4. a proposal WINS iff its key is the lowest of all proposals that touch a and of all that touch c: one descent_bid per
+//      participant into minkey[b].  Winners share no broker and no partition wins twice, so row[j] = c, S(a) -= size, S(c) += size
+//      are plain stores;
+//   5. until a round has no proposal (or max_rounds rounds have run).
+// The globally lowest key wins at both its brokers, every move lowers sum S^2 by 2w(S(a) - S(c) - w) > 0 and leaves both loads below
+// the old S(a): the rounds end and the peak never rises.
+// The snapshot "loads as of the round's start" holds by construction: a round is three kernels that do not overlap.  RANK reads the
+// loads and writes rank[] and order[]; PROPOSE reads loads, ranks and rows and writes key[p], slot[p], dest[p] and the round's minkey
+// row; APPLY reads what its lane owns and the minkey row, and the winners write rows and loads.  Two minkey rows rotate (the apply of
+// round r clears the row of round r + 1); the host reads the rounds' proposal counts every kDkBatch rounds, and the rounds enqueued
+// after the first empty one change nothing (no proposal, no winner, the same ranks).
+// The lower bound holds for every state the moves can reach: max(max size, ceil(sum k_p size[p] / B), and, when the leaders stay,
+// the largest sum of the slot-0 replicas of one broker).  Integers only.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+
+#include "kao_host.h"
+#include "kao_plan_dev.h"   // descent_gains, descent_bid, lane_count_to, wave_bytes_code
+
+namespace {
+
+constexpr int kDkThreads = 256;
+constexpr int kDkBatch = 32;            // rounds enqueued between two reads of the proposal counts
+constexpr int kDkHardRounds = 1 << 26;  // no descent gets here; a guard against an endless loop
+constexpr u64 kDkNoKey = ~0ull;
+enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_N = 16 };
+
+struct DkNet {   // one call; every pointer is device memory
+    int P, W, B, cap, first;   // first = the lowest movable slot: 0 with move_leaders, else 1
+    u64 min_gain;
+    uint16_t *rows;            // [PW] rewritten by the winners
+    const uint16_t *rows0;     // [PW] the input
+    const u64 *size;           // [P]
+    const uint8_t *rack;       // [B]
+    uint8_t *slot;             // [P] slot proposed in this round
+    uint16_t *dest;            // [P] its destination
+    u64 *key;                  // [P] key of this round's proposal, kDkNoKey = none
+    u64 *load;                 // [B]
+    int32_t *rank, *order;     // [B] rank of a broker, broker of a rank
+    u64 *mk;                   // [2][B] minkey rows
+    u64 *ctl;                  // [D_N]
+};
+
+__device__ inline void dk_max_to(u64 v, u64 *dst) {   // all 64 lanes active
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (u64)__shfl_xor((long long)v, off));
+    if (__lane_id() == 0 && v > 0) atomicMax(dst, v);
+}
+
+__device__ inline void dk_sum_to(u64 v, u64 *dst) {   // all 64 lanes active
+    for (int off = 32; off > 0; off >>= 1) v += (u64)__shfl_xor((long long)v, off);
+    if (__lane_id() == 0 && v > 0) atomicAdd(dst, v);
+}
+
+// ---- once per call ------------------------------------------------------------------------------------------------------------------
+// loads, the largest size, sum k_p size[p], the bytes of the slot-0 replicas per broker
+__global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    u64 w = 0, all = 0;
+    if (p < n.P) {
+        w = n.size[p];
+        n.key[p] = kDkNoKey;
+        const uint16_t *row = n.rows0 + (size_t)p * n.W;
+        if (w) {
+            for (int j = 0; j < n.W; ++j) {
+                const int x = row[j];
+                if (x == KAO_NONE) break;
+                atomicAdd(&n.load[x], w);
+                all += w;
+            }
+            atomicAdd(&fixed[row[0]], w);
+        }
+    }
+    dk_max_to(w, &n.ctl[D_MAXSIZE]);
+    dk_sum_to(all, &n.ctl[D_TOTAL]);
+}
+
+// the peak before and the largest fixed load; the loads kept for the finish
+__global__ void k_dk_peak0(DkNet n, const u64 *__restrict__ fixed, u64 *__restrict__ load0) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    u64 s = 0, f = 0;
+    if (b < n.B) {
+        s = n.load[b];
+        f = fixed[b];
+        load0[b] = s;
+    }
+    dk_max_to(s, &n.ctl[D_PEAK0]);
+    dk_max_to(f, &n.ctl[D_FIXED]);
+}
+
+// ---- a round ------------------------------------------------------------------------------------------------------------------------
+// rank[b] = brokers ahead of b by (load descending, index ascending), order[rank[b]] = b: all pairs, tiled through LDS (the scheme of
+// k_wl_rank in kao_wleaders.hip, which keeps no order[])
+__global__ __launch_bounds__(kDkThreads) void k_dk_rank(int B, const u64 *__restrict__ load, int32_t *__restrict__ rank, int32_t *__restrict__ order) {
+    __shared__ u64 tile[kDkThreads];
+    const int b = blockIdx.x * kDkThreads + threadIdx.x;
+    const u64 mine = b < B ? load[b] : 0;
+    int r = 0;
+    for (int base = 0; base < B; base += kDkThreads) {
+        const int cnt = min(kDkThreads, B - base);
+        if ((int)threadIdx.x < cnt) tile[threadIdx.x] = load[base + threadIdx.x];
+        __syncthreads();
+        for (int j = 0; j < cnt; ++j) {
+            const u64 x = tile[j];
+            r += (x > mine || (x == mine && base + j < b)) ? 1 : 0;
+        }
+        __syncthreads();
+    }
+    if (b < B) {   // ranks are a permutation: r < B
+        rank[b] = r;
+        order[r] = b;
+    }
+}
+
+// a row in registers: brokers, their racks (-1 in an empty slot), their ranks
+struct DkRow {
+    int b[KAO_MAX_RF], rk[KAO_MAX_RF], rr[KAO_MAX_RF];
+};
+
+// c is admissible for a replica that leaves rack ra: not in the row; no rack rule, the same rack, or room in rack(c)
+__device__ __forceinline__ bool dk_admissible(const DkRow &row, int c, int rc, int ra, int cap) {
+    bool in_row = false;
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < KAO_MAX_RF; ++j) {
+        in_row |= row.b[j] == c;
+        cnt += row.rk[j] == rc ? 1 : 0;
+    }
+    return !in_row && (cap <= 0 || rc == ra || cnt < cap);
+}
+
+// the first admissible broker among the ranks hi, hi - 1, .., lo; -1 when there is none
+__device__ __forceinline__ int dk_walk(const DkNet &n, const DkRow &row, int hi, int lo, int ra) {
+    for (int q = hi; q >= lo; --q) {
+        const int c = n.order[q];
+        if (dk_admissible(row, c, n.rack[c], ra, n.cap)) return c;
+    }
+    return -1;
+}
+
+__global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    bool prop = false;
+    if (p < n.P) {
+        u64 key = kDkNoKey;
+        const u64 w = n.size[p];
+        if (w) {
+            const uint16_t *src = n.rows + (size_t)p * n.W;
+            DkRow row;
+#pragma unroll
+            for (int j = 0; j < KAO_MAX_RF; ++j) {
+                const int x = j < n.W ? (int)src[j] : (int)KAO_NONE;
+                const bool held = x != KAO_NONE;
+                row.b[j] = x;
+                row.rk[j] = held ? (int)n.rack[x] : -1;
+                row.rr[j] = held ? n.rank[x] : -1;
+            }
+            int last = -1;   // the rank of the slot tried before: ranks are distinct, so the slots come heaviest first
+            for (int t = n.first; t < n.W && !prop; ++t) {
+                int ra_rank = n.B, a = 0, ra = 0, slot = 0;
+#pragma unroll
+                for (int j = 0; j < KAO_MAX_RF; ++j) {
+                    if (j >= n.first && row.rr[j] > last && row.rr[j] < ra_rank) { ra_rank = row.rr[j]; a = row.b[j]; ra = row.rk[j]; slot = j; }
+                }
+                if (ra_rank == n.B) break;   // no movable slot is left
+                last = ra_rank;
+                const u64 sa = n.load[a];
+                int c = dk_walk(n, row, n.B - 1 - ra_rank, ra_rank + 1, ra);
+                if (c < 0 || !descent_gains(sa, n.load[c], w, n.min_gain)) {
+                    c = dk_walk(n, row, n.B - 1, n.B - ra_rank, ra);
+                    if (c >= 0 && !descent_gains(sa, n.load[c], w, n.min_gain)) c = -1;
+                }
+                if (c >= 0) {
+                    prop = true;
+                    key = (u64)(uint32_t)ra_rank << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)p;
+                    n.slot[p] = (uint8_t)slot;
+                    n.dest[p] = (uint16_t)c;
+                    u64 *mine = n.mk + (size_t)(r & 1) * n.B;
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&mine[a], key);
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&mine[c], key);
+                }
+            }
+        }
+        n.key[p] = key;
+    }
+    lane_count_to(prop, count);
+}
+
+__global__ void k_dk_apply(DkNet n, int r) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    {   // the row of round r + 1 was last read by the apply of round r - 1
+        u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
+        for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kDkNoKey;
+    }
+    bool won = false;
+    if (p < n.P) {
+        const u64 key = n.key[p];
+        if (key != kDkNoKey) {
+            uint16_t *row = n.rows + (size_t)p * n.W;
+            const int slot = n.slot[p], a = row[slot], c = n.dest[p];
+            const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
+            won = mine[a] == key && mine[c] == key;
+            if (won) {   // no other winner touches a or c
+                const u64 w = n.size[p];
+                n.load[a] -= w;
+                n.load[c] += w;
+                row[slot] = (uint16_t)c;
+            }
+        }
+    }
+    lane_count_to(won, &n.ctl[D_MOVES]);
+}
+
+// ---- the result ---------------------------------------------------------------------------------------------------------------------
+// one lane per partition: the brokers of the final row that the input row did not hold, their bytes, the rows that changed
+__global__ void k_dk_finish(DkNet n) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    bool ch = false;
+    u64 fresh = 0, bytes = 0;
+    if (p < n.P) {
+        const uint16_t *now = n.rows + (size_t)p * n.W, *was = n.rows0 + (size_t)p * n.W;
+        for (int j = 0; j < n.W; ++j) {
+            const int x = now[j];
+            if (x == KAO_NONE) break;
+            ch |= x != was[j];
+            bool old = false;
+            for (int i = 0; i < n.W; ++i) old |= was[i] == x;
+            fresh += old ? 0 : 1;
+        }
+        bytes = fresh * n.size[p];
+    }
+    dk_sum_to(fresh, &n.ctl[D_NMOVED]);
+    dk_sum_to(bytes, &n.ctl[D_BYTES]);
+    lane_count_to(ch, &n.ctl[D_ROWS]);
+}
+
+// the peak after; the brokers whose load changed
+__global__ void k_dk_peak1(DkNet n, const u64 *__restrict__ load0) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    u64 s = 0;
+    bool ch = false;
+    if (b < n.B) {
+        s = n.load[b];
+        ch = s != load0[b];
+    }
+    dk_max_to(s, &n.ctl[D_PEAK1]);
+    lane_count_to(ch, &n.ctl[D_BROKERS]);
+}
+
+int validate_disk(int32_t B, int32_t R, const uint8_t *rack_of, int32_t P, int32_t W, const uint16_t *rows, const uint64_t *size, const void *const *outs,
+                  int n_outs) {
+    const std::string fn = "kao_balance_disk: ";
+    bool null = !rack_of || !rows || !size;
+    for (int i = 0; i < n_outs; ++i) null |= !outs[i];
+    if (null) return fail(KAO_ERR_INVALID, fn + "null pointer");
+    int rc = check_dims(fn, B, P, W, R);
+    if (!rc) rc = check_slot_cap(fn, P, W);
+    if (rc) return rc;
+    if (B > KAO_DISK_MAX_BROKERS) return fail(KAO_ERR_UNSUPPORTED, fn + "more than " + std::to_string(KAO_DISK_MAX_BROKERS) + " brokers (every round ranks all pairs of them)");
+    for (int b = 0; b < B; ++b)
+        if (rack_of[b] >= R) return fail(KAO_ERR_INVALID, fn + "rack_of[" + std::to_string(b) + "] >= n_racks");
+    if ((rc = check_rows(fn, B, P, W, rows))) return rc;
+    uint64_t total = 0;   // sum k_p size[p] below 2^62: every load of the kernels stays below 2^63
+    for (int64_t p = 0; p < P; ++p) {
+        uint64_t k = 0, all = 0;
+        while (k < (uint64_t)W && rows[p * W + (int64_t)k] != KAO_NONE) ++k;
+        if (__builtin_mul_overflow(k, size[p], &all) || __builtin_add_overflow(total, all, &total) || total >= (uint64_t(1) << 62))
+            return fail(KAO_ERR_INVALID, fn + "partition " + std::to_string(p) + ": the replica sizes sum to 2^62 or more");
+    }
+    return KAO_OK;
+}
+
+}  // namespace
+
+extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                                const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, int32_t max_rounds, int32_t dry_run,
+                                int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound,
+                                int32_t *status, int64_t stats[8]) {
+    const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, lower_bound, status};
+    int rc = validate_disk(n_brokers, n_racks, rack_of, n_partitions, width, rows, size, outs, 6);
+    if (rc) return rc;
+    if ((rc = require_init())) return rc;
+    const int B = n_brokers, P = n_partitions, W = width, PW = P * W;
+
+    // one arena: ctl u64[D_N] | count u32[kDkBatch] | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] |
+    //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B]
+    Carve cv;
+    const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
+                 o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_rank = cv.take<int32_t>(B), o_order = cv.take<int32_t>(B),
+                 o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW), o_rows0 = cv.take<uint16_t>(PW),
+                 o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
+    hipStream_t st = m.stream;
+    uint32_t *d_cnt = m.at<uint32_t>(o_cnt);
+    u64 *d_fixed = m.at<u64>(o_fixed), *d_load0 = m.at<u64>(o_load0);
+    uint16_t *d_rows = m.at<uint16_t>(o_rows), *d_rows0 = m.at<uint16_t>(o_rows0);
+    DkNet n;
+    n.P = P; n.W = W; n.B = B; n.cap = max_per_rack; n.first = move_leaders ? 0 : 1; n.min_gain = min_gain;
+    n.rows = d_rows; n.rows0 = d_rows0; n.size = m.at<u64>(o_size); n.rack = m.at<uint8_t>(o_rack); n.slot = m.at<uint8_t>(o_slot);
+    n.dest = m.at<uint16_t>(o_dest); n.key = m.at<u64>(o_key); n.load = m.at<u64>(o_load); n.rank = m.at<int32_t>(o_rank);
+    n.order = m.at<int32_t>(o_order); n.mk = m.at<u64>(o_mk); n.ctl = m.at<u64>(o_ctl);
+
+    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
+    HIP_TRY(hipMemsetAsync(n.mk, 0xFF, 2 * (size_t)B * sizeof(u64), st));
+    HIP_TRY(hipMemcpyAsync(m.at<uint8_t>(o_rack), rack_of, (size_t)B, hipMemcpyHostToDevice, st));
+    if (P) {
+        HIP_TRY(hipMemcpyAsync(d_rows0, rows, (size_t)PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_rows, d_rows0, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<u64>(o_size), size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    }
+    const unsigned pblocks = grid_for(P, kDkThreads), bblocks = grid_for(B, kDkThreads);
+    int64_t launches = 0, rounds = 0, props = 0;
+    bool more = false;
+    if (P) {
+        k_dk_init<<<pblocks, kDkThreads, 0, st>>>(n, d_fixed);
+        ++launches;
+    }
+    k_dk_peak0<<<bblocks, kDkThreads, 0, st>>>(n, d_fixed, d_load0);
+    ++launches;
+    HIP_TRY(hipGetLastError());
+
+    if (P) {
+        uint32_t cnt[kDkBatch];
+        for (int r = 0, done = 0; !done;) {
+            if (r >= kDkHardRounds) return fail(KAO_ERR_HIP, "kao_balance_disk: the rounds did not finish");
+            const int nb = max_rounds > 0 ? std::min(kDkBatch, max_rounds - r) : kDkBatch;
+            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
+            if (nb == 0) {   // max_rounds rounds have run, every one with a move: is there more to do?
+                k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
+                k_dk_propose<<<pblocks, kDkThreads, 0, st>>>(n, r, d_cnt);
+                launches += 2;
+            }
+            for (int i = 0; i < nb; ++i) {
+                k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
+                k_dk_propose<<<pblocks, kDkThreads, 0, st>>>(n, r + i, d_cnt + i);
+                k_dk_apply<<<pblocks, kDkThreads, 0, st>>>(n, r + i);
+                launches += 3;
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (nb == 0) { more = cnt[0] != 0; break; }
+            for (int i = 0; i < nb && !done; ++i) {   // the first round without a proposal ends the descent; the ones after it changed nothing
+                if (cnt[i] == 0) done = 1;
+                else { ++rounds; props += cnt[i]; }
+            }
+            r += nb;
+        }
+        k_dk_finish<<<pblocks, kDkThreads, 0, st>>>(n);
+        ++launches;
+    }
+    k_dk_peak1<<<bblocks, kDkThreads, 0, st>>>(n, d_load0);
+    ++launches;
+    HIP_TRY(hipGetLastError());
+    u64 ctl[D_N];
+    HIP_TRY(hipMemcpyAsync(ctl, n.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    if (P && !dry_run) HIP_TRY(hipMemcpyAsync(rows, d_rows, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    const uint64_t terms[3] = {(uint64_t)ctl[D_MAXSIZE], ((uint64_t)ctl[D_TOTAL] + (uint64_t)B - 1) / (uint64_t)B, move_leaders ? 0 : (uint64_t)ctl[D_FIXED]};
+    int which = 0;
+    for (int i = 1; i < 3; ++i)
+        if (terms[i] > terms[which]) which = i;   // the lowest term on ties
+    *n_moved = (int32_t)ctl[D_NMOVED];
+    *bytes_moved = ctl[D_BYTES];
+    *peak_before = ctl[D_PEAK0];
+    *peak_after = ctl[D_PEAK1];
+    *lower_bound = terms[which];
+    *status = ctl[D_PEAK1] == terms[which] ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    if (stats) {
+        stats[0] = rounds; stats[1] = (int64_t)ctl[D_MOVES]; stats[2] = props; stats[3] = launches; stats[4] = (int64_t)ctl[D_ROWS];
+        stats[5] = more ? 1 : 0; stats[6] = which; stats[7] = (int64_t)ctl[D_BROKERS];
+    }
+    return KAO_OK;
+}

@@ -1,0 +1,166 @@
+"""Disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk).
+
+    python -m kafka_assignment_optimizer_amd.disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt \
+        --max-per-rack 1 --out plan.json --report
+
+Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
+output, as kao-waves reads it) and moves replicas to brokers outside their row until no single move closes a gap of more than
+--min-gain bytes.  A move keeps its slot, so the follower order stays; --keep-leaders keeps every preferred leader where it is;
+--max-per-rack N lets no move raise a partition's count in a rack above N (counts already above it may stay).  The rows of all
+topics are taken together over one broker index.  The answer is a deterministic descent with a lower bound beside it: where
+peak_after == lower_bound the peak is proven optimal.  The plan holds the changed rows only and is what kao-waves --plan takes.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import sys
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _ffi
+from ._plan_args import _racks, count, dense_rows, weight_buffer
+from .failover import FailoverInput, _rack_buffer, parse_current
+from .model import NONE
+from .solver import STATUS_NAMES, _check
+
+STAT_KEYS = ("rounds", "moves", "proposals", "launches", "rows_changed", "stopped_by_max_rounds", "bound_term", "brokers_changed")
+BOUND_TERMS = ("largest_partition", "mean_load", "fixed_leaders")
+
+
+@dataclass
+class DiskResult:
+    rows: np.ndarray         # [P, width] uint16: the rows after the moves (the input rows with dry_run)
+    n_moved: int             # replicas Kafka must copy: the brokers of the final rows that the input rows did not hold
+    bytes_moved: int         # ... weighted by the partition sizes
+    peak_before: int         # max_b S(b) of the input
+    peak_after: int
+    lower_bound: int         # no outcome of the moves has a lower peak
+    status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound) | "FEASIBLE_BOUND_GAP"
+    stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h
+
+
+@dataclass
+class DiskPlan:
+    result: DiskResult
+    input: FailoverInput
+    size: np.ndarray                                                           # [P] uint64 per row
+    entries: List[Tuple[str, int, List[int]]] = field(default_factory=list)    # (topic, partition, replicas as broker ids) of the changed rows
+
+    @property
+    def document(self) -> dict:
+        """The reassignment document of the changed rows (what kao-waves --plan takes)."""
+        return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": r} for t, p, r in self.entries]}
+
+
+def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0,
+                        max_rounds: int = 0, dry_run: bool = False) -> DiskResult:
+    """kao_balance_disk on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); size[p] is the bytes of one replica of
+    row p."""
+    r, flat, P, W = dense_rows(rows)
+    rk = _rack_buffer(rack_of, n_brokers)
+    sbuf = weight_buffer(size, P, min_gain)
+    stats = np.zeros(8, dtype=np.int64)
+    n, status = C.c_int32(0), C.c_int32(0)
+    moved, before, after, bound = (C.c_uint64(0) for _ in range(4))
+    _check(_ffi.load().kao_balance_disk(int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W),
+                                        flat.ctypes.data_as(C.POINTER(C.c_uint16)), sbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_per_rack),
+                                        int(bool(move_leaders)), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
+                                        C.byref(before), C.byref(after), C.byref(bound), C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))),
+           "kao_balance_disk")
+    return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
+                      lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats)
+
+
+def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int] = None) -> np.ndarray:
+    """size[p] over `keys` (leaders.weights_for with this tool's words): every partition counts here, so one the table does not name
+    takes `default_size` or is a ValueError; waves.sizes_for sizes only the partitions a given plan moves."""
+    from .leaders import weights_for
+    return weights_for(keys, sizes, default_size, "size", "give them in --sizes or set --default-size")
+
+
+def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0,
+               dry_run: bool = False) -> DiskPlan:
+    """kao_balance_disk on a FailoverInput, size[p] per row of it; the entries are the rows that changed (none with dry_run)."""
+    res = balance_disk_arrays(fi.rows, len(fi.broker_ids), fi.rack_of, len(fi.rack_names), size, max_per_rack, move_leaders, min_gain, max_rounds,
+                              dry_run)
+    changed = np.nonzero((res.rows != fi.rows).any(axis=1))[0]
+    entries = [(fi.keys[p][0], fi.keys[p][1], [int(fi.broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
+    return DiskPlan(result=res, input=fi, size=np.asarray(size, dtype=np.uint64), entries=entries)
+
+
+def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, default_size: Optional[int] = None, max_per_rack: int = 0,
+                 move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> DiskPlan:
+    """kao_balance_disk on a reassignment document with `broker_list` and `racks` ({broker id: rack name}).  `sizes` is
+    {(topic, partition): bytes}, or a kafka-log-dirs / sizes document or text (waves.parse_sizes).  plan.document is the
+    reassignment document of the changed rows."""
+    from .waves import parse_sizes
+    fi = parse_current(doc, broker_list, racks)
+    if not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
+        sizes = parse_sizes(sizes)
+    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run)
+
+
+def report_lines(plan: DiskPlan) -> List[str]:
+    """The --report text, line for line as cli/kao-disk prints it."""
+    res, s = plan.result, plan.result.stats
+    total = int(sum(int(x) * int((row != NONE).sum()) for x, row in zip(plan.size, plan.input.rows)))
+    return [f"disk: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
+            f"bound_term={BOUND_TERMS[int(s[6])]} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
+            f"rows_changed={s[4]} brokers_changed={s[7]} rounds={s[0]} moves={s[1]} launches={s[3]}"]
+
+
+def main(argv=None) -> int:
+    """Python twin of cli/kao-disk: same flags, same bytes, same exit status (0 ok, 1 error, 2 usage)."""
+    from .leaders import plan_text
+    from .waves import MAX_SIZE, parse_bytes, parse_sizes
+    ap = argparse.ArgumentParser(prog="kao-disk", description="replica moves that lower the peak bytes per broker")
+    ap.add_argument("--current", required=True, help="reassignment JSON of the cluster as it is")
+    ap.add_argument("--broker-list", required=True, help="brokers of the cluster, CSV")
+    ap.add_argument("--racks", required=True, help='{"<brokerId>": "<rack>"} JSON file or id:rack,id:rack')
+    ap.add_argument("--sizes", required=True, help="kafka-log-dirs --describe output, or {\"partitions\":[{topic,partition,size}]}")
+    ap.add_argument("--default-size", default=None, help="bytes of the partitions --sizes does not list")
+    ap.add_argument("--max-per-rack", type=count, default=0, help="no move raises a partition's count in a rack above N (0: no rack rule)")
+    ap.add_argument("--keep-leaders", action="store_true", help="slot 0 of every partition stays where it is")
+    ap.add_argument("--min-gain", default=None, help="move only to close a gap of more than N bytes (N, or N with K/M/G/T)")
+    ap.add_argument("--max-rounds", type=count, default=0, help="stop after N rounds")
+    ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--report", action="store_true")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    min_gain, default_size = 0, None
+    try:
+        if a.min_gain is not None:
+            min_gain = parse_bytes(a.min_gain)
+        if a.default_size is not None:
+            default_size = parse_bytes(a.default_size)
+            if default_size > MAX_SIZE:
+                raise ValueError(f"--default-size above 2^53: {a.default_size}")
+    except ValueError as e:
+        ap.error(str(e))
+    try:
+        with open(a.current) as f:
+            doc = json.load(f)
+        fi = parse_current(doc, [int(b) for b in a.broker_list.split(",") if b], _racks(a.racks))   # input errors before the device is touched
+        with open(a.sizes) as f:
+            size = sizes_of(fi.keys, parse_sizes(f.read()), default_size)
+        from .solver import init
+        init(a.device)
+        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run)
+        if a.report:
+            for line in report_lines(plan):
+                print(line, file=sys.stderr)
+        with open(a.out, "w") as f:
+            f.write(plan_text(plan.entries))
+    except Exception as e:  # noqa: BLE001 -- reported, exit status 1
+        print(f"kao-disk: {e}", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

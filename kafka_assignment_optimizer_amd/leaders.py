@@ -231,9 +231,10 @@ def parse_traffic(doc) -> Dict[Tuple[str, int], int]:
     return out
 
 
-def weights_for(keys, table: Dict[Tuple[str, int], int], default_weight: Optional[int] = None) -> np.ndarray:
+def weights_for(keys, table: Dict[Tuple[str, int], int], default_weight: Optional[int] = None, what: str = "weight",
+                hint: str = "name them in the file or set --default-weight") -> np.ndarray:
     """weight[p] over `keys`.  A partition the table does not name takes `default_weight`; without one it is a ValueError naming
-    the first few such partitions."""
+    the first few such partitions (`what` and `hint` word it for the tools that weigh by something else: disk.py)."""
     weight = np.zeros(len(keys), dtype=np.uint64)
     missing = []
     for i, key in enumerate(keys):
@@ -245,7 +246,7 @@ def weights_for(keys, table: Dict[Tuple[str, int], int], default_weight: Optiona
             weight[i] = default_weight
     if missing:
         more = f" and {len(missing) - 5} more" if len(missing) > 5 else ""
-        raise ValueError(f"no weight for partitions {', '.join(missing[:5])}{more} (name them in the file or set --default-weight)")
+        raise ValueError(f"no {what} for partitions {', '.join(missing[:5])}{more} ({hint})")
     return weight
 
 

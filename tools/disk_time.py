@@ -1,0 +1,76 @@
+"""Times kao_balance_disk on: BASELINE config 4 after a drift with its 200 topics concatenated over the one broker index (500
+brokers x 10,000 partitions, its own racks, no rack rule) and the large instance of tests/leaders_ref.py (1000 brokers x 100,000
+partitions, RF 3, 10 racks, max_per_rack 1), each with log-normal sizes of sigma 0.7 and 1.5.  One JSON line per case: peaks, lower
+bound, peak_after / lower_bound, replicas and bytes moved, the bytes stored, the stats (rounds, moves, proposals, kernel launches)
+and the wall time of the call with dry_run (median of --reps after one warm-up; it includes the host validation, the upload and the
+read-back of the counters, and ends in a stream synchronise).  For kernel times run it under
+`rocprofv3 --kernel-trace --stats --` (in a run of its own, --reps 1).  Writes the lines to profiles/disk_time.txt with --write."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--cases", default="config4,large")
+    ap.add_argument("--sigmas", default="0.7,1.5")
+    ap.add_argument("--keep-leaders", action="store_true")
+    ap.add_argument("--write", action="store_true", help="write the lines to profiles/disk_time.txt as well")
+    a = ap.parse_args()
+    import numpy as np
+    import kafka_assignment_optimizer_amd as kao
+    from kafka_assignment_optimizer_amd.disk import STAT_KEYS, balance_disk_arrays
+    import leaders_ref as lr
+    kao.init(0)
+
+    def sizes(P, sigma, seed):
+        rng = np.random.default_rng(seed)
+        return np.maximum(1, np.round(np.exp(rng.normal(np.log(2.0 ** 20), sigma, P)))).astype(np.int64)
+
+    def timed(rows, B, rack_of, R, size, cap):
+        args = (rows, B, rack_of, R, size, cap, not a.keep_leaders)
+        res = balance_disk_arrays(*args, dry_run=True)   # warm-up
+        ms = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            res = balance_disk_arrays(*args, dry_run=True)
+            ms.append(1e3 * (time.perf_counter() - t0))
+        return res, round(float(np.median(ms)), 3)
+
+    cases = {}   # name -> rows, B, rack_of, R, max_per_rack
+    if "config4" in a.cases:
+        topics = lr.config4_topics()
+        cases["config4"] = (np.concatenate([np.asarray(t.current, dtype=np.int64) for t in topics]), topics[0].n_brokers,
+                            np.asarray(topics[0].rack_of, dtype=np.uint8), topics[0].n_racks, 0)
+    if "large" in a.cases:
+        rows, B, _, _ = lr.large_instance()
+        cases["large"] = (rows, B, (np.arange(B) % 10).astype(np.uint8), 10, 1)
+    lines = []
+    for name, (rows, B, rack_of, R, cap) in cases.items():
+        for sigma in (float(s) for s in a.sigmas.split(",")):
+            size = sizes(len(rows), sigma, 11)
+            res, ms = timed(rows, B, rack_of, R, size, cap)
+            total = int((size[:, None] * (rows != 0xFFFF)).sum())
+            line = {"workload": name, "sigma": sigma, "brokers": B, "racks": R, "partitions": len(rows), "max_per_rack": cap,
+                    "move_leaders": not a.keep_leaders, "status": res.status, "peak_before": res.peak_before, "peak_after": res.peak_after,
+                    "lower_bound": res.lower_bound, "peak_over_bound": round(res.peak_after / max(res.lower_bound, 1), 5),
+                    "largest_partition": int(size.max()), "replicas_moved": res.n_moved, "bytes_moved": res.bytes_moved, "bytes_total": total,
+                    "moved_share": round(res.bytes_moved / max(total, 1), 5)}
+            line.update({k: int(v) for k, v in zip(STAT_KEYS, res.stats)})
+            line["wall_ms_median"] = ms
+            lines.append(json.dumps(line))
+            print(lines[-1], flush=True)
+    if a.write:
+        with open(os.path.join(ROOT, "profiles", "disk_time.txt"), "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
