@@ -1,8 +1,9 @@
 // kao-disk -- disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk, DESIGN.md
-// section 4m).
+// section 4m; under --max-bytes kao_balance_disk_budget, section 4n).
 //
 //   kao-disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt [--default-size N]
-//            [--max-per-rack N] [--keep-leaders] [--min-gain BYTES] [--max-rounds N] [--dry-run] --out plan.json [--report] [--device D]
+//            [--max-per-rack N] [--keep-leaders] [--min-gain BYTES] [--max-bytes BYTES] [--max-rounds N] [--dry-run] --out plan.json
+//            [--report] [--device D]
 //
 // Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
 // output or a sizes document, as kao-waves reads them) and moves replicas to brokers outside their row until no single move closes a
@@ -11,7 +12,10 @@
 // above it may stay).  The rows of all topics are taken together over one broker index.  --default-size N sizes the partitions the
 // file does not name (without it they are an error).  The answer is a deterministic descent with a lower bound beside it: where
 // peak_after == lower_bound the peak is proven optimal.  The plan holds the changed rows only and is what kao-waves --plan takes;
-// --dry-run reports and leaves the plan empty.  All computation happens in libkao.so on the GPU.
+// --dry-run reports and leaves the plan empty.  --max-bytes N caps the bytes the whole plan copies: a move that would copy more than
+// what is left of N is no candidate, and of a round's winners the heaviest sources are served first; the report line then ends in
+// max_bytes, bytes_left, refused (winners the budget turned down) and budget_bound (1: the budget is what stopped the descent).
+// All computation happens in libkao.so on the GPU.
 // Exit status: 0 = ok, 1 = error, 2 = usage.
 #include <algorithm>
 #include <cstdint>
@@ -34,7 +38,8 @@ namespace {
     std::fprintf(stderr,
         "usage: kao-disk --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
         "                --sizes <kafka-log-dirs output | sizes.json> [--default-size N] [--max-per-rack N] [--keep-leaders]\n"
-        "                [--min-gain N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report] [--device D]\n"
+        "                [--min-gain N[K|M|G|T]] [--max-bytes N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report]\n"
+        "                [--device D]\n"
         "writes the partitions whose replicas move; exit status: 0 = ok, 1 = error, 2 = usage\n");
     std::exit(2);
 }
@@ -44,8 +49,8 @@ namespace {
 int main(int argc, char **argv) {
     std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path;
     int device = 0, max_per_rack = 0, max_rounds = 0;
-    bool report = false, dry_run = false, keep_leaders = false, have_default = false;
-    uint64_t default_size = 0, min_gain = 0;
+    bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false;
+    uint64_t default_size = 0, min_gain = 0, max_bytes = 0;
     auto count_arg = [](const std::string &v, const char *msg) {
         if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
         return std::atoi(v.c_str());
@@ -67,6 +72,9 @@ int main(int argc, char **argv) {
             have_default = true;
         } else if (a == "--min-gain") {
             if (!parse_bytes(need("--min-gain"), min_gain)) usage("--min-gain needs a byte count (N, or N with K/M/G/T)");
+        } else if (a == "--max-bytes") {
+            if (!parse_bytes(need("--max-bytes"), max_bytes)) usage("--max-bytes needs a byte count (N, or N with K/M/G/T)");
+            have_budget = true;
         } else if (a == "--max-per-rack") max_per_rack = count_arg(need("--max-per-rack"), "--max-per-rack needs a value >= 0");
         else if (a == "--max-rounds") max_rounds = count_arg(need("--max-rounds"), "--max-rounds needs a value >= 0");
         else if (a == "-h" || a == "--help") usage(nullptr);
@@ -101,20 +109,28 @@ int main(int argc, char **argv) {
         std::vector<uint16_t> rows = cr.rows;
         int32_t n_moved = 0, status = 0;
         uint64_t bytes_moved = 0, before = 0, after = 0, bound = 0;
-        int64_t stats[8] = {0};
-        rc = kao_balance_disk(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1, min_gain,
-                              max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
-        if (rc) throw std::runtime_error(std::string("kao_balance_disk: ") + kao_strerror(rc) + " " + kao_last_error());
+        int64_t stats[10] = {0};
+        if (have_budget)
+            rc = kao_balance_disk_budget(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1,
+                                         min_gain, max_bytes, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
+        else
+            rc = kao_balance_disk(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1, min_gain,
+                                  max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
+        if (rc) throw std::runtime_error(std::string(have_budget ? "kao_balance_disk_budget: " : "kao_balance_disk: ") + kao_strerror(rc) + " " + kao_last_error());
         if (report) {
             static const char *const terms[3] = {"largest_partition", "mean_load", "fixed_leaders"};
             unsigned long long total = 0;
             for (int p = 0; p < P; ++p)
                 for (int j = 0; j < W && cr.rows[(size_t)p * W + j] != KAO_NONE; ++j) total += size[(size_t)p];
             std::fprintf(stderr, "disk: status=%s peak_before=%llu peak_after=%llu lower_bound=%llu bound_term=%s replicas_moved=%d bytes_moved=%llu "
-                                 "bytes_total=%llu rows_changed=%lld brokers_changed=%lld rounds=%lld moves=%lld launches=%lld\n",
+                                 "bytes_total=%llu rows_changed=%lld brokers_changed=%lld rounds=%lld moves=%lld launches=%lld",
                          status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", (unsigned long long)before, (unsigned long long)after,
                          (unsigned long long)bound, terms[stats[6] >= 0 && stats[6] < 3 ? stats[6] : 0], n_moved, (unsigned long long)bytes_moved, total,
                          (long long)stats[4], (long long)stats[7], (long long)stats[0], (long long)stats[1], (long long)stats[3]);
+            if (have_budget)
+                std::fprintf(stderr, " max_bytes=%llu bytes_left=%llu refused=%lld budget_bound=%lld", (unsigned long long)max_bytes,
+                             (unsigned long long)(max_bytes - bytes_moved), (long long)stats[8], (long long)stats[9]);
+            std::fprintf(stderr, "\n");
         }
         const std::string text = changed_rows_text(cr, rows, cl.brokers);
         std::ofstream f(out_path);

@@ -636,6 +636,34 @@ int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of,
                      uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *status,
                      int64_t stats[8] /* may be NULL */);
 
+/* ---- Disk-usage balance under a byte budget ---------------------------------------------------------------
+ * kao_balance_disk with a cap on the bytes the whole plan copies.  Everything of kao_balance_disk holds: rows, admissibility, rank,
+ * the two walks, key, win, the bound, status, n_moved / bytes_moved.  Three things are added, all in terms of the INPUT row set in(p).
+ * COST: a move (p, j, a -> c) costs size[p] * ([c not in in(p)] - [a not in in(p)]): +size[p], 0, or -size[p] (a refund: a replica
+ * that was a fresh copy goes home), so the costs of all applied moves sum to exactly *bytes_moved.  charge = max(cost, 0): size[p] iff
+ * a is in in(p) and c is not, else 0.  rem = max_bytes - spent at the round's start, spent = the sum of the costs so far.
+ * AFFORDABLE: broker c is a candidate of slot j only if it is admissible as before AND charge(p, j, a -> c) <= rem, that is
+ * size[p] <= rem, or a not in in(p), or c in in(p).  Both walks still stop at their first candidate (every later one is heavier), so
+ * "no proposal from slot j" means that no admissible, affordable broker passes the gain test.
+ * GRANT: winners are found as before.  A winner with charge == 0 is applied.  A winner with charge > 0 is applied iff the charges of
+ * all winners of the round whose source has a lower rank (applied or not) plus its own charge are <= rem: winners share no broker,
+ * so winners and source ranks correspond one to one, and the charged winners that are applied are the longest prefix, heaviest
+ * source first, that fits.  A refused winner changes nothing: no row, no load, not spent, not the move count.
+ * The round's lowest key has the lowest source rank of all proposals, so its prefix is its own charge, which is <= rem: every round
+ * with a proposal applies a move, the sum of S^2 falls, the peak never rises, and spent <= max_bytes after every round.  The end
+ * state is stable UNDER THE BUDGET: no admissible move with charge <= max_bytes - *bytes_moved closes a gap of more than min_gain.
+ * max_bytes = UINT64_MAX (no budget) gives byte for byte the rows, numbers and stats[0..2], [4..7] of kao_balance_disk;
+ * max_bytes = 0 applies nothing.  Every value of max_bytes is valid.
+ * stats (may be NULL): [0..7] as for kao_balance_disk (a round is four kernel launches here), [8] winners refused by the grant rule,
+ * summed over the rounds, [9] 1 iff the budget is what stopped the descent: it was not stopped by max_rounds, and the final state is
+ * not move-stable for an unlimited budget.  Checks, limits and refusals are those of kao_balance_disk. */
+int kao_balance_disk_budget(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
+                            uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *size /* [n_partitions] */,
+                            int32_t max_per_rack /* <= 0: no rack rule */, int32_t move_leaders, uint64_t min_gain,
+                            uint64_t max_bytes /* UINT64_MAX: no budget */, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run,
+                            int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                            uint64_t *lower_bound, int32_t *status, int64_t stats[10] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

@@ -1,5 +1,6 @@
 // kao_disk.hip -- kao_balance_disk: replica moves that lower the peak of the bytes a broker stores, S(b) = sum of size[p] over the
-// rows that contain b.  Kernels and the C entry point.
+// rows that contain b, and kao_balance_disk_budget: the same under a budget of bytes copied (section 4n).
+// Kernels and the C entry points.
 //
 // A move takes the replica in slot j of row p from broker a to a broker c OUTSIDE the row; the slot keeps its place.  c is
 // admissible iff it is not in the row and (no rack rule, or rack(c) == rack(a), or the row holds fewer than max_per_rack brokers of
@@ -26,6 +27,15 @@
 // after the first empty one change nothing (no proposal, no winner, the same ranks).
 // The lower bound holds for every state the moves can reach: max(max size, ceil(sum k_p size[p] / B), and, when the leaders stay,
 // the largest sum of the slot-0 replicas of one broker).  Integers only.
+//
+// UNDER A BUDGET (kao_balance_disk_budget) a move (p, j, a -> c) COSTS size[p] * ([c not in in(p)] - [a not in in(p)]), in(p) = the
+// input row: +size, 0, or -size when a fresh copy goes home, so the costs of the applied moves sum to bytes_moved.  Its CHARGE is
+// max(cost, 0), and rem = max_bytes - spent at the round's start.  PROPOSE<true> takes c as a candidate only if charge <= rem; a new
+// kernel GRANT, between propose and apply, settles the winners from the broker side: in rank order q, order[q] is the source of a
+// winner iff its minkey word carries rank q and the destination's word holds the same key; a winner with a charge is granted iff the
+// charges of all winners of lower source rank plus its own are <= rem (one workgroup, a block scan over the ranks).  APPLY<true>
+// applies the granted winners and adds their costs to spent (one wrapping u64 add per wavefront).  The lowest key of a round has
+// the lowest source rank, so its prefix is its own charge <= rem: every round with a proposal still applies a move.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,7 +51,8 @@ constexpr int kDkThreads = 256;
 constexpr int kDkBatch = 32;            // rounds enqueued between two reads of the proposal counts
 constexpr int kDkHardRounds = 1 << 26;  // no descent gets here; a guard against an endless loop
 constexpr u64 kDkNoKey = ~0ull;
-enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_N = 16 };
+constexpr int kDkGrantThreads = 1024;   // k_dk_grant: one workgroup, one rank per lane and chunk
+enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_SPENT, D_REFUSED, D_N = 16 };
 
 struct DkNet {   // one call; every pointer is device memory
     int P, W, B, cap, first;   // first = the lowest movable slot: 0 with move_leaders, else 1
@@ -57,6 +68,8 @@ struct DkNet {   // one call; every pointer is device memory
     int32_t *rank, *order;     // [B] rank of a broker, broker of a rank
     u64 *mk;                   // [2][B] minkey rows
     u64 *ctl;                  // [D_N]
+    uint8_t *grant;            // [B] under a budget: the winner that leaves b is applied in this round
+    u64 max_bytes;             // the budget; ctl[D_SPENT] = the costs of the moves applied so far
 };
 
 __device__ inline void dk_max_to(u64 v, u64 *dst) {   // all 64 lanes active
@@ -146,15 +159,38 @@ __device__ __forceinline__ bool dk_admissible(const DkRow &row, int c, int rc, i
     return !in_row && (cap <= 0 || rc == ra || cnt < cap);
 }
 
-// the first admissible broker among the ranks hi, hi - 1, .., lo; -1 when there is none
-__device__ __forceinline__ int dk_walk(const DkNet &n, const DkRow &row, int hi, int lo, int ra) {
+// the input row in registers (under a budget only)
+struct DkHome {
+    int b[KAO_MAX_RF];
+};
+
+__device__ __forceinline__ DkHome dk_home_row(const DkNet &n, int p) {
+    DkHome h;
+    const uint16_t *src = n.rows0 + (size_t)p * n.W;
+#pragma unroll
+    for (int j = 0; j < KAO_MAX_RF; ++j) h.b[j] = j < n.W ? (int)src[j] : (int)KAO_NONE;
+    return h;
+}
+
+__device__ __forceinline__ bool dk_home(const DkHome &h, int c) {   // c < KAO_NONE
+    bool in = false;
+#pragma unroll
+    for (int j = 0; j < KAO_MAX_RF; ++j) in |= h.b[j] == c;
+    return in;
+}
+
+// the first admissible broker among the ranks hi, hi - 1, .., lo; -1 when there is none.  Under a budget the broker must be
+// affordable too: `free` (the size fits what is left, or the replica is a fresh copy), or a broker of the input row
+template <bool Budget>
+__device__ __forceinline__ int dk_first(const DkNet &n, const DkRow &row, const DkHome &home, bool free, int hi, int lo, int ra) {
     for (int q = hi; q >= lo; --q) {
         const int c = n.order[q];
-        if (dk_admissible(row, c, n.rack[c], ra, n.cap)) return c;
+        if (dk_admissible(row, c, n.rack[c], ra, n.cap) && (!Budget || free || dk_home(home, c))) return c;
     }
     return -1;
 }
 
+template <bool Budget>
 __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     bool prop = false;
@@ -172,6 +208,12 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
                 row.rk[j] = held ? (int)n.rack[x] : -1;
                 row.rr[j] = held ? n.rank[x] : -1;
             }
+            DkHome home;
+            bool fits = true;   // the size fits what is left of the budget: tested first, so the home compares run only when it is nearly spent
+            if (Budget) {
+                home = dk_home_row(n, p);
+                fits = w <= n.max_bytes - n.ctl[D_SPENT];
+            }
             int last = -1;   // the rank of the slot tried before: ranks are distinct, so the slots come heaviest first
             for (int t = n.first; t < n.W && !prop; ++t) {
                 int ra_rank = n.B, a = 0, ra = 0, slot = 0;
@@ -182,9 +224,10 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
                 if (ra_rank == n.B) break;   // no movable slot is left
                 last = ra_rank;
                 const u64 sa = n.load[a];
-                int c = dk_walk(n, row, n.B - 1 - ra_rank, ra_rank + 1, ra);
+                const bool free = !Budget || fits || !dk_home(home, a);
+                int c = dk_first<Budget>(n, row, home, free, n.B - 1 - ra_rank, ra_rank + 1, ra);
                 if (c < 0 || !descent_gains(sa, n.load[c], w, n.min_gain)) {
-                    c = dk_walk(n, row, n.B - 1, n.B - ra_rank, ra);
+                    c = dk_first<Budget>(n, row, home, free, n.B - 1, n.B - ra_rank, ra);
                     if (c >= 0 && !descent_gains(sa, n.load[c], w, n.min_gain)) c = -1;
                 }
                 if (c >= 0) {
@@ -203,6 +246,62 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
     lane_count_to(prop, count);
 }
 
+// under a budget, between propose and apply: which winners are applied.  ONE workgroup walks the ranks q = 0, 1, ..; lane t of a chunk
+// takes rank base + t.  b = order[q] is the source of a winner iff its minkey word carries rank q (a word with another rank is a
+// proposal INTO b) and the destination's word holds the same key.  The charges get an exclusive u64 prefix sum over the ranks:
+// shuffles inside a wavefront, the wavefront totals through LDS, a carry from chunk to chunk.  Sums stay below 2^62.
+__global__ __launch_bounds__(kDkGrantThreads) void k_dk_grant(DkNet n, int r) {
+    constexpr int kWaves = kDkGrantThreads / 64;
+    __shared__ u64 wave_sum[kWaves];
+    const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
+    const u64 rem = n.max_bytes - n.ctl[D_SPENT];
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    u64 carry = 0;   // the charges of the chunks before this one
+    for (int base = 0; base < n.B; base += kDkGrantThreads) {
+        const int q = base + (int)threadIdx.x;
+        bool win = false;
+        u64 charge = 0;
+        int b = 0;
+        if (q < n.B) {
+            b = n.order[q];
+            const u64 key = mine[b];
+            if (key != kDkNoKey && (int)(key >> 48) == q) {
+                const uint32_t p = (uint32_t)key;   // a key of this round: p < P, slot[p] and dest[p] are this round's
+                const int c = n.dest[p];
+                if (mine[c] == key) {
+                    win = true;
+                    const uint16_t *was = n.rows0 + (size_t)p * n.W;
+                    bool a_home = false, c_home = false;
+                    for (int j = 0; j < n.W; ++j) {
+                        a_home |= was[j] == b;
+                        c_home |= was[j] == c;
+                    }
+                    charge = a_home && !c_home ? n.size[p] : 0;
+                }
+            }
+        }
+        u64 incl = charge;   // inclusive scan of the wavefront
+        for (int off = 1; off < 64; off <<= 1) {
+            const u64 up = (u64)__shfl_up((long long)incl, off);
+            if (lane >= off) incl += up;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        u64 before = carry, chunk = 0;   // the wavefronts below this one; the whole chunk
+        for (int v = 0; v < kWaves; ++v) {
+            const u64 x = wave_sum[v];
+            before += v < wave ? x : 0;
+            chunk += x;
+        }
+        __syncthreads();   // wave_sum is rewritten by the next chunk
+        carry += chunk;
+        const bool ok = win && (charge == 0 || before + incl <= rem);   // before + incl = the exclusive prefix + the own charge
+        if (q < n.B) n.grant[b] = ok ? 1 : 0;
+        lane_count_to(win && !ok, &n.ctl[D_REFUSED]);
+    }
+}
+
+template <bool Budget>
 __global__ void k_dk_apply(DkNet n, int r) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     {   // the row of round r + 1 was last read by the apply of round r - 1
@@ -210,6 +309,7 @@ __global__ void k_dk_apply(DkNet n, int r) {
         for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kDkNoKey;
     }
     bool won = false;
+    u64 cost = 0;   // under a budget: +size, 0 or -size (wrapping)
     if (p < n.P) {
         const u64 key = n.key[p];
         if (key != kDkNoKey) {
@@ -217,8 +317,13 @@ __global__ void k_dk_apply(DkNet n, int r) {
             const int slot = n.slot[p], a = row[slot], c = n.dest[p];
             const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
             won = mine[a] == key && mine[c] == key;
+            if (Budget) won = won && n.grant[a] != 0;   // grant[] was settled from the spend before this kernel, which changes it
             if (won) {   // no other winner touches a or c
                 const u64 w = n.size[p];
+                if (Budget) {
+                    const DkHome home = dk_home_row(n, p);
+                    cost = (dk_home(home, c) ? 0 : w) - (dk_home(home, a) ? 0 : w);
+                }
                 n.load[a] -= w;
                 n.load[c] += w;
                 row[slot] = (uint16_t)c;
@@ -226,6 +331,7 @@ __global__ void k_dk_apply(DkNet n, int r) {
         }
     }
     lane_count_to(won, &n.ctl[D_MOVES]);
+    if (Budget) dk_sum_to(cost, &n.ctl[D_SPENT]);   // the sum of a wavefront wraps as its terms do; it adds nothing when it is 0
 }
 
 // ---- the result ---------------------------------------------------------------------------------------------------------------------
@@ -264,9 +370,8 @@ __global__ void k_dk_peak1(DkNet n, const u64 *__restrict__ load0) {
     lane_count_to(ch, &n.ctl[D_BROKERS]);
 }
 
-int validate_disk(int32_t B, int32_t R, const uint8_t *rack_of, int32_t P, int32_t W, const uint16_t *rows, const uint64_t *size, const void *const *outs,
-                  int n_outs) {
-    const std::string fn = "kao_balance_disk: ";
+int validate_disk(const std::string &fn, int32_t B, int32_t R, const uint8_t *rack_of, int32_t P, int32_t W, const uint16_t *rows, const uint64_t *size,
+                  const void *const *outs, int n_outs) {
     bool null = !rack_of || !rows || !size;
     for (int i = 0; i < n_outs; ++i) null |= !outs[i];
     if (null) return fail(KAO_ERR_INVALID, fn + "null pointer");
@@ -287,25 +392,25 @@ int validate_disk(int32_t B, int32_t R, const uint8_t *rack_of, int32_t P, int32
     return KAO_OK;
 }
 
-}  // namespace
-
-extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
-                                const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, int32_t max_rounds, int32_t dry_run,
-                                int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound,
-                                int32_t *status, int64_t stats[8]) {
+// both entry points: Budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]
+template <bool Budget>
+int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                 const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes, int32_t max_rounds, int32_t dry_run,
+                 int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *status,
+                 int64_t *stats) {
     const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, lower_bound, status};
-    int rc = validate_disk(n_brokers, n_racks, rack_of, n_partitions, width, rows, size, outs, 6);
+    int rc = validate_disk(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, outs, 6);
     if (rc) return rc;
     if ((rc = require_init())) return rc;
     const int B = n_brokers, P = n_partitions, W = width, PW = P * W;
 
     // one arena: ctl u64[D_N] | count u32[kDkBatch] | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] |
-    //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B]
+    //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B]
     Carve cv;
     const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
                  o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_rank = cv.take<int32_t>(B), o_order = cv.take<int32_t>(B),
                  o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW), o_rows0 = cv.take<uint16_t>(PW),
-                 o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B);
+                 o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B), o_grant = cv.take<uint8_t>(Budget ? B : 0);
     CallBufs m;
     if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
@@ -317,6 +422,7 @@ extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_
     n.rows = d_rows; n.rows0 = d_rows0; n.size = m.at<u64>(o_size); n.rack = m.at<uint8_t>(o_rack); n.slot = m.at<uint8_t>(o_slot);
     n.dest = m.at<uint16_t>(o_dest); n.key = m.at<u64>(o_key); n.load = m.at<u64>(o_load); n.rank = m.at<int32_t>(o_rank);
     n.order = m.at<int32_t>(o_order); n.mk = m.at<u64>(o_mk); n.ctl = m.at<u64>(o_ctl);
+    n.grant = m.at<uint8_t>(o_grant); n.max_bytes = max_bytes;
 
     HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
     HIP_TRY(hipMemsetAsync(n.mk, 0xFF, 2 * (size_t)B * sizeof(u64), st));
@@ -328,7 +434,7 @@ extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_
     }
     const unsigned pblocks = grid_for(P, kDkThreads), bblocks = grid_for(B, kDkThreads);
     int64_t launches = 0, rounds = 0, props = 0;
-    bool more = false;
+    bool more = false, open = false;   // open: the budget stopped the descent
     if (P) {
         k_dk_init<<<pblocks, kDkThreads, 0, st>>>(n, d_fixed);
         ++launches;
@@ -340,19 +446,20 @@ extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_
     if (P) {
         uint32_t cnt[kDkBatch];
         for (int r = 0, done = 0; !done;) {
-            if (r >= kDkHardRounds) return fail(KAO_ERR_HIP, "kao_balance_disk: the rounds did not finish");
+            if (r >= kDkHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
             const int nb = max_rounds > 0 ? std::min(kDkBatch, max_rounds - r) : kDkBatch;
             HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
             if (nb == 0) {   // max_rounds rounds have run, every one with a move: is there more to do?
                 k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
-                k_dk_propose<<<pblocks, kDkThreads, 0, st>>>(n, r, d_cnt);
+                k_dk_propose<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r, d_cnt);
                 launches += 2;
             }
             for (int i = 0; i < nb; ++i) {
                 k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
-                k_dk_propose<<<pblocks, kDkThreads, 0, st>>>(n, r + i, d_cnt + i);
-                k_dk_apply<<<pblocks, kDkThreads, 0, st>>>(n, r + i);
-                launches += 3;
+                k_dk_propose<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r + i, d_cnt + i);
+                if (Budget) k_dk_grant<<<1, kDkGrantThreads, 0, st>>>(n, r + i);
+                k_dk_apply<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r + i);
+                launches += Budget ? 4 : 3;
             }
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
@@ -363,6 +470,17 @@ extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_
                 else { ++rounds; props += cnt[i]; }
             }
             r += nb;
+        }
+        if (Budget && !more) {   // no affordable proposal is left: is there one without the budget?  (no row changes: nothing is applied)
+            uint32_t left = 0;
+            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof left, st));
+            k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
+            k_dk_propose<false><<<pblocks, kDkThreads, 0, st>>>(n, 0, d_cnt);
+            launches += 2;
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&left, d_cnt, sizeof left, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            open = left != 0;
         }
         k_dk_finish<<<pblocks, kDkThreads, 0, st>>>(n);
         ++launches;
@@ -388,6 +506,25 @@ extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_
     if (stats) {
         stats[0] = rounds; stats[1] = (int64_t)ctl[D_MOVES]; stats[2] = props; stats[3] = launches; stats[4] = (int64_t)ctl[D_ROWS];
         stats[5] = more ? 1 : 0; stats[6] = which; stats[7] = (int64_t)ctl[D_BROKERS];
+        if (Budget) { stats[8] = (int64_t)ctl[D_REFUSED]; stats[9] = open ? 1 : 0; }
     }
     return KAO_OK;
+}
+
+}  // namespace
+
+extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                                const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, int32_t max_rounds, int32_t dry_run,
+                                int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound,
+                                int32_t *status, int64_t stats[8]) {
+    return balance_disk<false>("kao_balance_disk: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, max_per_rack, move_leaders, min_gain,
+                               UINT64_MAX, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
+}
+
+extern "C" int kao_balance_disk_budget(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                                       const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes,
+                                       int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before,
+                                       uint64_t *peak_after, uint64_t *lower_bound, int32_t *status, int64_t stats[10]) {
+    return balance_disk<true>("kao_balance_disk_budget: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, max_per_rack, move_leaders,
+                              min_gain, max_bytes, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
 }

@@ -1,7 +1,7 @@
 """Disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk).
 
     python -m kafka_assignment_optimizer_amd.disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt \
-        --max-per-rack 1 --out plan.json --report
+        --max-per-rack 1 [--max-bytes 500G] --out plan.json --report
 
 Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
 output, as kao-waves reads it) and moves replicas to brokers outside their row until no single move closes a gap of more than
@@ -9,6 +9,8 @@ output, as kao-waves reads it) and moves replicas to brokers outside their row u
 --max-per-rack N lets no move raise a partition's count in a rack above N (counts already above it may stay).  The rows of all
 topics are taken together over one broker index.  The answer is a deterministic descent with a lower bound beside it: where
 peak_after == lower_bound the peak is proven optimal.  The plan holds the changed rows only and is what kao-waves --plan takes.
+--max-bytes N caps the bytes the whole plan copies (kao_balance_disk_budget, section 4n): the same descent, a move that would copy
+more than what is left of N is no candidate, and of a round's winners the heaviest sources are served first.
 """
 from __future__ import annotations
 
@@ -28,6 +30,7 @@ from .model import NONE
 from .solver import STATUS_NAMES, _check
 
 STAT_KEYS = ("rounds", "moves", "proposals", "launches", "rows_changed", "stopped_by_max_rounds", "bound_term", "brokers_changed")
+BUDGET_STAT_KEYS = STAT_KEYS + ("refused", "budget_bound")   # kao_balance_disk_budget
 BOUND_TERMS = ("largest_partition", "mean_load", "fixed_leaders")
 
 
@@ -40,7 +43,8 @@ class DiskResult:
     peak_after: int
     lower_bound: int         # no outcome of the moves has a lower peak
     status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound) | "FEASIBLE_BOUND_GAP"
-    stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h
+    stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h; int64[10] under a byte budget (BUDGET_STAT_KEYS)
+    max_bytes: Optional[int] = None   # the byte budget of the call, None without one
 
 
 @dataclass
@@ -56,23 +60,37 @@ class DiskPlan:
         return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": r} for t, p, r in self.entries]}
 
 
+def _budget(max_bytes) -> int:
+    """max_bytes as the C call takes it; a ValueError outside 0..2^64-1, before any library is loaded."""
+    if isinstance(max_bytes, bool) or not isinstance(max_bytes, (int, np.integer)):
+        raise ValueError("max_bytes must be an integer")
+    if not 0 <= int(max_bytes) < 1 << 64:
+        raise ValueError("max_bytes must be 0..2^64-1")
+    return int(max_bytes)
+
+
 def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0,
-                        max_rounds: int = 0, dry_run: bool = False) -> DiskResult:
+                        max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None) -> DiskResult:
     """kao_balance_disk on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); size[p] is the bytes of one replica of
-    row p."""
+    row p.  With max_bytes (0..2^64-1) it is kao_balance_disk_budget: the moves copy at most that many bytes."""
+    if max_bytes is not None:
+        max_bytes = _budget(max_bytes)
     r, flat, P, W = dense_rows(rows)
     rk = _rack_buffer(rack_of, n_brokers)
     sbuf = weight_buffer(size, P, min_gain)
-    stats = np.zeros(8, dtype=np.int64)
+    stats = np.zeros(8 if max_bytes is None else 10, dtype=np.int64)
     n, status = C.c_int32(0), C.c_int32(0)
     moved, before, after, bound = (C.c_uint64(0) for _ in range(4))
-    _check(_ffi.load().kao_balance_disk(int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W),
-                                        flat.ctypes.data_as(C.POINTER(C.c_uint16)), sbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_per_rack),
-                                        int(bool(move_leaders)), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
-                                        C.byref(before), C.byref(after), C.byref(bound), C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))),
-           "kao_balance_disk")
+    head = [int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
+            sbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_per_rack), int(bool(move_leaders)), int(min_gain)]
+    tail = [int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), C.byref(before), C.byref(after), C.byref(bound), C.byref(status),
+            stats.ctypes.data_as(C.POINTER(C.c_int64))]
+    if max_bytes is None:
+        _check(_ffi.load().kao_balance_disk(*head, *tail), "kao_balance_disk")
+    else:
+        _check(_ffi.load().kao_balance_disk_budget(*head, max_bytes, *tail), "kao_balance_disk_budget")
     return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
-                      lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats)
+                      lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes)
 
 
 def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int] = None) -> np.ndarray:
@@ -83,25 +101,28 @@ def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int
 
 
 def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0,
-               dry_run: bool = False) -> DiskPlan:
-    """kao_balance_disk on a FailoverInput, size[p] per row of it; the entries are the rows that changed (none with dry_run)."""
+               dry_run: bool = False, max_bytes: Optional[int] = None) -> DiskPlan:
+    """kao_balance_disk on a FailoverInput, size[p] per row of it; the entries are the rows that changed (none with dry_run).  With
+    max_bytes it is kao_balance_disk_budget."""
     res = balance_disk_arrays(fi.rows, len(fi.broker_ids), fi.rack_of, len(fi.rack_names), size, max_per_rack, move_leaders, min_gain, max_rounds,
-                              dry_run)
+                              dry_run, max_bytes)
     changed = np.nonzero((res.rows != fi.rows).any(axis=1))[0]
     entries = [(fi.keys[p][0], fi.keys[p][1], [int(fi.broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
     return DiskPlan(result=res, input=fi, size=np.asarray(size, dtype=np.uint64), entries=entries)
 
 
 def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, default_size: Optional[int] = None, max_per_rack: int = 0,
-                 move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> DiskPlan:
+                 move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None) -> DiskPlan:
     """kao_balance_disk on a reassignment document with `broker_list` and `racks` ({broker id: rack name}).  `sizes` is
     {(topic, partition): bytes}, or a kafka-log-dirs / sizes document or text (waves.parse_sizes).  plan.document is the
-    reassignment document of the changed rows."""
+    reassignment document of the changed rows.  With max_bytes the moves copy at most that many bytes (kao_balance_disk_budget)."""
     from .waves import parse_sizes
+    if max_bytes is not None:
+        max_bytes = _budget(max_bytes)
     fi = parse_current(doc, broker_list, racks)
     if not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
         sizes = parse_sizes(sizes)
-    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run)
+    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes)
 
 
 def report_lines(plan: DiskPlan) -> List[str]:
@@ -110,7 +131,8 @@ def report_lines(plan: DiskPlan) -> List[str]:
     total = int(sum(int(x) * int((row != NONE).sum()) for x, row in zip(plan.size, plan.input.rows)))
     return [f"disk: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
             f"bound_term={BOUND_TERMS[int(s[6])]} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
-            f"rows_changed={s[4]} brokers_changed={s[7]} rounds={s[0]} moves={s[1]} launches={s[3]}"]
+            f"rows_changed={s[4]} brokers_changed={s[7]} rounds={s[0]} moves={s[1]} launches={s[3]}"
+            + ("" if res.max_bytes is None else f" max_bytes={res.max_bytes} bytes_left={res.max_bytes - res.bytes_moved} refused={s[8]} budget_bound={s[9]}")]
 
 
 def main(argv=None) -> int:
@@ -127,15 +149,18 @@ def main(argv=None) -> int:
     ap.add_argument("--keep-leaders", action="store_true", help="slot 0 of every partition stays where it is")
     ap.add_argument("--min-gain", default=None, help="move only to close a gap of more than N bytes (N, or N with K/M/G/T)")
     ap.add_argument("--max-rounds", type=count, default=0, help="stop after N rounds")
+    ap.add_argument("--max-bytes", default=None, help="copy at most N bytes in all (N, or N with K/M/G/T)")
     ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
-    min_gain, default_size = 0, None
+    min_gain, default_size, max_bytes = 0, None, None
     try:
         if a.min_gain is not None:
             min_gain = parse_bytes(a.min_gain)
+        if a.max_bytes is not None:
+            max_bytes = parse_bytes(a.max_bytes)
         if a.default_size is not None:
             default_size = parse_bytes(a.default_size)
             if default_size > MAX_SIZE:
@@ -150,7 +175,7 @@ def main(argv=None) -> int:
             size = sizes_of(fi.keys, parse_sizes(f.read()), default_size)
         from .solver import init
         init(a.device)
-        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run)
+        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes)
         if a.report:
             for line in report_lines(plan):
                 print(line, file=sys.stderr)

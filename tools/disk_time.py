@@ -4,7 +4,10 @@ partitions, RF 3, 10 racks, max_per_rack 1), each with log-normal sizes of sigma
 bound, peak_after / lower_bound, replicas and bytes moved, the bytes stored, the stats (rounds, moves, proposals, kernel launches)
 and the wall time of the call with dry_run (median of --reps after one warm-up; it includes the host validation, the upload and the
 read-back of the counters, and ends in a stream synchronise).  For kernel times run it under
-`rocprofv3 --kernel-trace --stats --` (in a run of its own, --reps 1).  Writes the lines to profiles/disk_time.txt with --write."""
+`rocprofv3 --kernel-trace --stats --` (in a run of its own, --reps 1).  Writes the lines to profiles/disk_time.txt with --write.
+--max-bytes-pct 1,2,5,none times kao_balance_disk_budget instead, once per value: a budget of that share of
+the bytes stored, `none` = UINT64_MAX; the lines gain the budget, what is left of it, the refused winners, budget_bound and the time
+of every repeat, and --write puts them into profiles/disk_budget_time.txt."""
 import argparse
 import json
 import os
@@ -22,11 +25,12 @@ def main():
     ap.add_argument("--cases", default="config4,large")
     ap.add_argument("--sigmas", default="0.7,1.5")
     ap.add_argument("--keep-leaders", action="store_true")
-    ap.add_argument("--write", action="store_true", help="write the lines to profiles/disk_time.txt as well")
+    ap.add_argument("--max-bytes-pct", default=None, help="CSV of budgets in percent of the bytes stored, or `none`: times kao_balance_disk_budget")
+    ap.add_argument("--write", action="store_true", help="write the lines to profiles/disk_time.txt (disk_budget_time.txt with --max-bytes-pct) as well")
     a = ap.parse_args()
     import numpy as np
     import kafka_assignment_optimizer_amd as kao
-    from kafka_assignment_optimizer_amd.disk import STAT_KEYS, balance_disk_arrays
+    from kafka_assignment_optimizer_amd.disk import BUDGET_STAT_KEYS, STAT_KEYS, balance_disk_arrays
     import leaders_ref as lr
     kao.init(0)
 
@@ -34,15 +38,15 @@ def main():
         rng = np.random.default_rng(seed)
         return np.maximum(1, np.round(np.exp(rng.normal(np.log(2.0 ** 20), sigma, P)))).astype(np.int64)
 
-    def timed(rows, B, rack_of, R, size, cap):
+    def timed(rows, B, rack_of, R, size, cap, max_bytes):
         args = (rows, B, rack_of, R, size, cap, not a.keep_leaders)
-        res = balance_disk_arrays(*args, dry_run=True)   # warm-up
+        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes)   # warm-up
         ms = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            res = balance_disk_arrays(*args, dry_run=True)
-            ms.append(1e3 * (time.perf_counter() - t0))
-        return res, round(float(np.median(ms)), 3)
+            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes)
+            ms.append(round(1e3 * (time.perf_counter() - t0), 3))
+        return res, ms
 
     cases = {}   # name -> rows, B, rack_of, R, max_per_rack
     if "config4" in a.cases:
@@ -56,19 +60,25 @@ def main():
     for name, (rows, B, rack_of, R, cap) in cases.items():
         for sigma in (float(s) for s in a.sigmas.split(",")):
             size = sizes(len(rows), sigma, 11)
-            res, ms = timed(rows, B, rack_of, R, size, cap)
             total = int((size[:, None] * (rows != 0xFFFF)).sum())
-            line = {"workload": name, "sigma": sigma, "brokers": B, "racks": R, "partitions": len(rows), "max_per_rack": cap,
-                    "move_leaders": not a.keep_leaders, "status": res.status, "peak_before": res.peak_before, "peak_after": res.peak_after,
-                    "lower_bound": res.lower_bound, "peak_over_bound": round(res.peak_after / max(res.lower_bound, 1), 5),
-                    "largest_partition": int(size.max()), "replicas_moved": res.n_moved, "bytes_moved": res.bytes_moved, "bytes_total": total,
-                    "moved_share": round(res.bytes_moved / max(total, 1), 5)}
-            line.update({k: int(v) for k, v in zip(STAT_KEYS, res.stats)})
-            line["wall_ms_median"] = ms
-            lines.append(json.dumps(line))
-            print(lines[-1], flush=True)
+            for pct in [None] if a.max_bytes_pct is None else a.max_bytes_pct.split(","):   # None: kao_balance_disk
+                max_bytes = None if pct is None else 2 ** 64 - 1 if pct == "none" else int(total * float(pct) / 100)
+                res, ms = timed(rows, B, rack_of, R, size, cap, max_bytes)
+                line = {"workload": name, "sigma": sigma, "brokers": B, "racks": R, "partitions": len(rows), "max_per_rack": cap,
+                        "move_leaders": not a.keep_leaders, "status": res.status, "peak_before": res.peak_before, "peak_after": res.peak_after,
+                        "lower_bound": res.lower_bound, "peak_over_bound": round(res.peak_after / max(res.lower_bound, 1), 5),
+                        "largest_partition": int(size.max()), "replicas_moved": res.n_moved, "bytes_moved": res.bytes_moved, "bytes_total": total,
+                        "moved_share": round(res.bytes_moved / max(total, 1), 5)}
+                if pct is not None:
+                    line.update({"max_bytes_pct": pct, "max_bytes": max_bytes, "bytes_left": max_bytes - res.bytes_moved})
+                line.update({k: int(v) for k, v in zip(STAT_KEYS if pct is None else BUDGET_STAT_KEYS, res.stats)})
+                line["wall_ms_median"] = round(float(np.median(ms)), 3)
+                if pct is not None:
+                    line["wall_ms"] = ms
+                lines.append(json.dumps(line))
+                print(lines[-1], flush=True)
     if a.write:
-        with open(os.path.join(ROOT, "profiles", "disk_time.txt"), "w") as f:
+        with open(os.path.join(ROOT, "profiles", "disk_time.txt" if a.max_bytes_pct is None else "disk_budget_time.txt"), "w") as f:
             f.write("\n".join(lines) + "\n")
 
 
