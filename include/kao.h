@@ -319,6 +319,12 @@ int kao_lp_round_host(const kao_topic *t, const uint8_t *q, const int32_t *zq, i
  * [64][64] = the inverses of L's diagonal tiles, x[n] = the solution of A x = rhs (rhs NULL: all ones), ms[2] = HIP-event milliseconds of
  * the factorisation and of the two triangular solves (second of two runs).  Any output may be NULL. */
 int kao_dense_spd_test(const double *A, int32_t n, const double *rhs, double *factor, double *linv, double *x, double ms[2]);
+/* Test hooks: the lookup forms of K-search's band arithmetic, as the kernels build them (kao_search_dev.h), on the host.
+ * kao_search_band_row: the six state bits of a band row whose count is c against [lo, hi] -- by the per-topic table when the band fits
+ * one (*fits = 1; force_plain = 0), by the arithmetic form otherwise or when force_plain is set.  kao_search_rack_delta: the violation
+ * delta of a partition-rack count c (0..8) against [lo, hi] for one more (dec = 0) or one fewer (dec = 1) replica, out of the bit table. */
+int kao_search_band_row(int32_t lo, int32_t hi, int32_t c, int32_t force_plain, int32_t *fits);
+int kao_search_rack_delta(int32_t lo, int32_t hi, int32_t c, int32_t dec);
 /* Test hook (round 6): the LP of ONE topic solved by n_dev SHARDS -- shard r holds the partitions [P r / n_dev, P (r + 1) / n_dev) with their
  * variables and local rows; the 3R + 2B coupling rows and the global variables are replicated; per interior-point iteration the shards'
  * parts of the Schur complement meet in one all-reduce (f64 sum), the coupling right-hand sides in one per solve, the scalar records of the

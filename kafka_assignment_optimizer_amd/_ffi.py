@@ -84,6 +84,8 @@ SIGNATURES = {
     "kao_lp_round": (C.c_int, [_P(KaoTopic), C.c_double, C.c_uint32, C.c_double, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_int64), _P(C.c_int32), _P(C.c_double)]),
     "kao_lp_round_host": (C.c_int, [_P(KaoTopic), _P(C.c_uint8), _P(C.c_int32), C.c_int32, _P(C.c_uint16), _P(C.c_int32)]),
     "kao_dense_spd_test": (C.c_int, [_P(C.c_double), C.c_int32, _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
+    "kao_search_band_row": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32)]),
+    "kao_search_rack_delta": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "kao_lp_sharded_test": (C.c_int, [_P(KaoTopic), _P(C.c_int32), C.c_int32, C.c_double, C.c_uint32, C.c_double, C.c_int32, _P(C.c_int64), _P(C.c_uint16),
                                       _P(C.c_int64), _P(C.c_int32), _P(C.c_double)]),
     "kao_lp_trace": (C.c_int, [_P(KaoTopic), C.c_double, C.c_int32, _P(C.c_double), _P(C.c_double), _P(C.c_int32)]),

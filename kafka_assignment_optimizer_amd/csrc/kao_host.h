@@ -213,6 +213,7 @@ struct kao_session {
         int nw = kRFP;       // replica words per partition of the group's topics: 4 or 8 (template instantiation)
         int rf_uniform = -1; // the RF all topics of the group share (0: mixed; -1: no topic yet)
         int w_abs_max = 0;   // the largest |w00..w11| over the group's topics (search_small_cost)
+        bool band_tabs = true;   // every topic's replica and leader band fits a band-row table (search_band_tabs): the small-cost form may run
         bool rf3 = true;     // every topic has RF 3 and at most 3 current replicas per partition: K-search may run its RF-3 instantiation
         bool global_a = false;   // topic too large for LDS: assignment + current words stay in global memory
         bool cur_global = false; // (round 5) only the current-assignment words stay in global memory / L2, the working words are in LDS (~4,900 .. 9,800 partitions)

@@ -163,6 +163,8 @@ bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, in
 // the largest |role weight| of the group's topics (derivation: kao_search.hip); ignored unless the RF-3 instantiation runs
 constexpr int kSmallCostMax = 16384;
 bool search_small_cost(int lam_min, int lam_max, int obj_scale, int w_abs_max, bool priced);
+// ... and looks band rows up in per-topic tables: every topic's replica and leader band must fit one (kao_search.hip)
+bool search_band_tabs(int rep_lo, int rep_hi, int lead_lo, int lead_hi);
 void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team = 0, int rft = 0, bool small = false);
 bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, int waves, void *stream);   // K-init (topics in global memory); waves = 0: automatic
 void launch_eval(const EvalPools &pools, int n_blocks, int ne, void *stream);

@@ -41,7 +41,9 @@ namespace kao {
 //                   are those of RFT = 0 (RF read per topic).
 // kSmall         : (RFT = 3 only) the host has shown that no cost this launch forms leaves int16 (search_small_cost below): the keys
 //                   are multiply-adds without the clamp, and the fused scan keeps its two slots' costs in the halves of one register
-//                   (v_pk_mad_i16 / v_pk_add_i16).  Same draws, keys, winners, stores and counters as kSmall = false.
+//                   (v_pk_mad_i16 / v_pk_add_i16), the penalty's parameters come out of one packed scalar and a broker's band rows out
+//                   of per-topic tables (the host has also shown that every band fits one: search_band_tabs).  Same draws, keys,
+//                   winners, stores and counters as kSmall = false.
 template <bool kGlobalA, bool kPriced, int NW, bool kWide, bool kTeam, bool kCurG = false, int RFT = 0, bool kSmall = false>
 __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPools &pl, const SearchParams &prm) {
     static_assert(!kTeam || kGlobalA, "teams run topics that live in global memory");
@@ -57,10 +59,15 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     const TopicDev *TD = pl.topics + bm.x;
 
     TopicRegs T = topic_regs<RFT>(TD);
-    // the broker band ends are operands of per-lane compares only: held in VGPRs.  The SGPR file is full (106 + 142 spilled
-    // in the plain instantiation) and every spilled scalar costs a v_readlane -- a VALU slot, the unit this kernel is bound
-    // by -- where it is used; VGPRs are plentiful (68 of the 72 that keep 7 waves per SIMD).
-    asm volatile("" : "+v"(T.rep_lo), "+v"(T.rep_hi), "+v"(T.lead_lo), "+v"(T.lead_hi));
+    // What the iteration loop rebuilds a broker's band rows from (finish), four registers: per row the lookup's bias and table in the
+    // small-cost form (the host picks it only for groups whose bands all fit a band_tab: search_band_tabs), the band's ends for
+    // band_entry otherwise.  They are operands of per-lane arithmetic only: held in VGPRs.  The SGPR file is full and every spilled
+    // scalar costs a v_readlane -- a VALU slot, the unit this kernel is bound by -- where it is used.  (The band ends themselves are
+    // read again from the topic behind the loop: nothing else in it needs them.)
+    constexpr bool kBandTabs = kSmall;
+    int bq_r0 = kBandTabs ? band_tab_bias(T.rep_lo) : T.rep_lo, bq_r1 = kBandTabs ? (int)band_tab(T.rep_lo, T.rep_hi) : T.rep_hi;
+    int bq_l0 = kBandTabs ? band_tab_bias(T.lead_lo) : T.lead_lo, bq_l1 = kBandTabs ? (int)band_tab(T.lead_lo, T.lead_hi) : T.lead_hi;
+    asm volatile("" : "+v"(bq_r0), "+v"(bq_r1), "+v"(bq_l0), "+v"(bq_l1));
 
     // ---- LDS carve: [CUR uint4[maxP]]* [RSZ int[krt]] [XR u8[Bx rounded to 64]] then per wave
     //      [A uint4[maxP]]* [C u32[Bx rounded to 64]] [W u16[same]] [K int[krt]] [RT int[krt]]        (* only when !kGlobalA)
@@ -268,14 +275,25 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     // tuple (the kernarg load) that the allocator spills and restores WHOLE -- three times per iteration, 24 v_readlane
     int lam_lo = prm.lam_min, lam_hi = prm.lam_max;
     uint32_t n_iters = prm.iters, it_base = prm.launch * prm.iters;
-    uint32_t scan_two = TD->P * TD->RF <= prm.scan2_max ? 1u : 0u;   // REPLACE scan over two tournament slots (topics up to kScanTwoSlots replica slots)
+    // One scalar for the loop's wave-uniform choice -- bit 29: REPLACE scan over two tournament slots (topics up to kScanTwoSlots
+    // replica slots) -- and, small cost, for the penalty's parameters as well: lam_min in bits 11:0, lam_max in bits 23:12
+    // (0 <= lam_min <= lam_max <= 2048 by search_small_cost), the period's exponent (at most 23) in bits 28:24.  Read through an empty
+    // asm where it is used: a field taken out in front of the loop is one more live scalar there, and the SGPR file is full -- each is
+    // a spill restore, a v_readlane, per use.
+    constexpr uint32_t kLpScanTwo = 1u << 29;
+    uint32_t loop_pack = TD->P * TD->RF <= prm.scan2_max ? kLpScanTwo : 0u;
+    if (kSmall) loop_pack |= ((uint32_t)prm.lam_min & 0xFFFu) | (((uint32_t)prm.lam_max & 0xFFFu) << 12) | (((uint32_t)plog & 31u) << 24);
     {   // through a VGPR and back: a plain scalar copy is coalesced with the tuple again
-        uint32_t v0 = (uint32_t)lam_lo, v1 = (uint32_t)lam_hi, v2 = n_iters, v3 = it_base, v4 = scan_two;
-        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3), "+v"(v4));
-        lam_lo = (int)__builtin_amdgcn_readfirstlane(v0); lam_hi = (int)__builtin_amdgcn_readfirstlane(v1);
+        uint32_t v0 = (uint32_t)lam_lo, v1 = (uint32_t)lam_hi, v2 = n_iters, v3 = it_base, v4 = loop_pack;
+        asm volatile("" : "+v"(v2), "+v"(v3), "+v"(v4));
+        if constexpr (!kSmall) {   // (small cost: the penalty's parameters come out of loop_pack alone)
+            asm volatile("" : "+v"(v0), "+v"(v1));
+            lam_lo = (int)__builtin_amdgcn_readfirstlane(v0); lam_hi = (int)__builtin_amdgcn_readfirstlane(v1);
+        }
         n_iters = __builtin_amdgcn_readfirstlane(v2); it_base = __builtin_amdgcn_readfirstlane(v3);
-        scan_two = __builtin_amdgcn_readfirstlane(v4);
+        loop_pack = __builtin_amdgcn_readfirstlane(v4);
     }
+    auto loop_flag = [&](uint32_t bit) { uint32_t lp = loop_pack; asm volatile("" : "+s"(lp)); return (lp & bit) != 0u; };
     // Fused two-slot REPLACE scan (LDS-resident, unpriced, one chunk of at most 256 rounds): slot 2's draw of round rd is the generator
     // state n_rd steps after slot 1's, s' = A_n s + C_n (mod 2^24) -- the jump-ahead of lcg24 over n_rd = rounds of the topic's scan
     constexpr bool kFuse = !kGlobalA && !kTeam && !kPriced;
@@ -283,12 +301,29 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     uint32_t jmp_a = 1u, jmp_c = 0u;
     if (fuse_ok)
         for (int n = (T.Bx + 63) >> 6; n > 0; --n) { jmp_a = (jmp_a * 0x6D2B79u) & 0xFFFFFFu; jmp_c = (jmp_c * 0x6D2B79u + 0x3C6EF3u) & 0xFFFFFFu; }
+    // best_obj is wave-uniform and changes only at a snapshot, behind a wave-uniform branch (snapshot() loops a uniform number of
+    // times for that: a lane-dependent loop bound merged with the branch and made everything set behind it a per-lane value).  Its
+    // sign is "has been feasible once", what the penalty depends on: a scalar compare
+    best_obj = __builtin_amdgcn_readfirstlane(best_obj);
     for (uint32_t i = 0; i < n_iters; ++i) {
         const uint32_t it = it_base + i;
         const int type = (int)((0x1210u >> ((it & 7u) * 2u)) & 3u);  // pattern R R X R L R X R
-        const uint32_t ph = it & pmask;
-        // no oscillation before the restart has been feasible once (best_obj < 0): the penalty stays at lam_max
-        const int lam = best_obj < 0 ? lam_hi : min(lam_hi, lam_lo + (int)((2u * ph * lrange) >> plog));
+        // no oscillation before the restart has been feasible once (best_obj < 0): the penalty stays at lam_max.  Formed on the scalar
+        // unit -- a scalar register is what the keys' multiply-adds take it from (mad24s, pk_mad_ss).  Small cost: its four parameters
+        // come out of one packed scalar each iteration (opaque to the compiler: unpacked once in front of the loop they are four
+        // more live scalars, each a spill restore -- a v_readlane -- per iteration)
+        int lam;
+        if constexpr (kSmall) {
+            uint32_t lp = loop_pack;
+            asm volatile("" : "+s"(lp));
+            const uint32_t plg = (lp >> 24) & 31u;
+            const int lo_ = (int)(lp & 0xFFFu), hi_ = (int)((lp >> 12) & 0xFFFu);
+            const uint32_t ph = it & ((1u << plg) - 1u);
+            lam = best_obj < 0 ? hi_ : min(hi_, lo_ + (int)((2u * ph * (uint32_t)(hi_ - lo_ + 1)) >> plg));
+        } else {
+            const uint32_t ph = it & pmask;
+            lam = best_obj < 0 ? lam_hi : min(lam_hi, lam_lo + (int)((2u * ph * lrange) >> plog));
+        }
         // REPLACE alternates, in blocks of 8 iterations, between "scan" (one slot, every broker) and "sample"
         // (every lane its own slot, 4 brokers); EXCHANGE always scans; LEADER-SWAP always samples
         const bool sampled = (type == 2) || (type == 0 && ((it >> 3) & 1u));
@@ -378,9 +413,9 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     if (lane_w < 2) {
                         const uint32_t cx = L.C[xx];
                         uint32_t wx;
-                        if (rows == 3) wx = band_fields(T, cx);
-                        else if (rows == 1) wx = (L.W[xx] & ~kWRowR) | band_entry((int)(cx & 0xFFFFu), T.rep_lo, T.rep_hi);
-                        else wx = (L.W[xx] & ~kWRowL) | (band_entry((int)(cx >> 16), T.lead_lo, T.lead_hi) << 6);
+                        if (rows == 3) wx = band_row<kBandTabs>((int)(cx & 0xFFFFu), bq_r0, bq_r1) | (band_row<kBandTabs>((int)(cx >> 16), bq_l0, bq_l1) << 6);
+                        else if (rows == 1) wx = (L.W[xx] & ~kWRowR) | band_row<kBandTabs>((int)(cx & 0xFFFFu), bq_r0, bq_r1);
+                        else wx = (L.W[xx] & ~kWRowL) | (band_row<kBandTabs>((int)(cx >> 16), bq_l0, bq_l1) << 6);
                         L.W[xx] = (uint16_t)wx;
                     }
                 }
@@ -426,7 +461,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 const int g_old = role_w2<NS>(c, uw, wl, wf) + (hbw ? bw_of(BW[uw & 0xFFFFu], lead) : 0);
                 const uint32_t wo = L.W[uw & 0xFFFFu];
                 const int dV_old = wfld(wo, kWDecR) + wfldw(wo, kWDecL, lw);
-                const int dV_rack_old = ddec(L.K[ro], T.rack_lo, T.rack_hi) + ddec(cnt4<NS>(a, ro), T.prack_lo, T.prack_hi);
+                const int dV_rack_old = ddec(L.K[ro], T.rack_lo, T.rack_hi) + c7_delta(T.c7_dec, cnt4x2<NS>(a, ro));
                 const int rsz_ro = RSZ[ro];
                 int dP_old = 0, dP_rack_old = 0;
                 if (kPriced) {
@@ -457,11 +492,11 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     int dVg = dV_old + wfld(wn, kWIncR) + wfldw(wn, kWIncL, lw);
                     if (g < 2) {
                         if (r != ro)
-                            dVg += dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + dinc(cnt4<NS>(a, r), T.prack_lo, T.prack_hi);
+                            dVg += dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + c7_delta(T.c7_inc, cnt4x2<NS>(a, r));
                     }
                     const int dObjg = role_w2<NS>(c, xw, wl, wf) + (hbw ? bw_of(BW[x], lead) : 0) - (kSmall ? 0 : g_old);
                     uint32_t keyg;
-                    if constexpr (kSmall) keyg = okg ? key_small(mad24s(-S, dObjg, mad24(lam, dVg, base_s)), (uint32_t)lane) : kKeyNull;
+                    if constexpr (kSmall) keyg = okg ? key_small(mad24s(-S, dObjg, mad24s(lam, dVg, base_s)), (uint32_t)lane) : kKeyNull;
                     else if (kPriced) {
                         const uint32_t prx = PR[x];
                         int dPg = dP_old + (wflag(wn, kWPinR) & price_rep(prx));
@@ -491,7 +526,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const uint32_t wx = L.W[xw & 0xFFFFu];
                     const int dVg = dV_u + wfld(wx, kWIncL);
                     uint32_t keyg;
-                    if constexpr (kSmall) keyg = key_small(mad24(lam, dVg, mad24s(-S, dObjg, kDBias)), (uint32_t)lane);
+                    if constexpr (kSmall) keyg = key_small(mad24s(lam, dVg, mad24s(-S, dObjg, kDBias)), (uint32_t)lane);
                     else if (kPriced) keyg = make_key_p(lam, S, dVg, dObjg, dP_u + (wflag(wx, kWPinL) & price_lead(PR[xw & 0xFFFFu])), lane);
                     else keyg = make_key(lam, S, dVg, dObjg, lane);
                     if (keyg < key) { key = keyg; vw = xw; k = kk; dV = dVg; dObj = dObjg; }
@@ -520,7 +555,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 g_o = role_w2<NS>(cl, oldw_o, leadl ? T.w00 : T.w01, leadl ? T.w10 : T.w11);
                 if (hbw && TY == 0) g_o += bw_of(BW[oldw_o & 0xFFFFu], leadl);   // a REPLACE also gives up the broker's own weight
                 const uint32_t wo = L.W[oldw_o & 0xFFFFu];
-                const int dv7 = ddec(cnt4<NS>(al, rol), T.prack_lo, T.prack_hi);
+                const int dv7 = c7_delta(T.c7_dec, cnt4x2<NS>(al, rol));
                 int sc;
                 if (TY == 0) {
                     dvo_o = wfld(wo, kWDecR) + wfldw(wo, kWDecL, leadl ? 2u : 0u);
@@ -530,7 +565,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int dvl = wfld(wo, leadl ? kWDecL : kWIncL);
                     sc = min(dv7, 0) + min(dvl, 0);
                 }
-                if constexpr (kSmall) key_o = key_small(mad24(lam, sc, mad24s(S, g_o, kDBias)), (uint32_t)lane) | tour_off;
+                if constexpr (kSmall) key_o = key_small(mad24s(lam, sc, mad24s(S, g_o, kDBias)), (uint32_t)lane) | tour_off;
                 else if (kPriced) {
                     int dPs = 0;
                     if (TY == 0) {
@@ -628,7 +663,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
             // the two moves is the proposal (ties: the first slot's).  Loop head, penalty, acceptance and bookkeeping are paid once
             // for twice the neighbours (they were two thirds of the instruction stream at 500 brokers, docs/notes_r03.md section 6).
             int wA2 = -1;
-            if (type == 0 && scan_two) {   // (large topics scan one slot: their iterations are what they are short of)
+            if (type == 0 && loop_flag(kLpScanTwo)) {   // (large topics scan one slot: their iterations are what they are short of)
                 const uint32_t k2 = wave_umin(lane == wA1 ? kKeyNull : keyA);
                 wA2 = k2 == kKeyNull ? -1 : (int)(k2 & 63u);   // (no other lane takes part: one slot)
             }
@@ -657,8 +692,8 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 const uint32_t ro1 = us[0] >> 16, ro2 = us[1] >> 16;
                 for (int r = lane; r < T.R; r += 64) {
                     const int dk = dinc(L.K[r], T.rack_lo, T.rack_hi);
-                    const int v1 = ((uint32_t)r != ro1) ? v_rk[0] + dk + dinc(cnt4<NS>(a1, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
-                    const int v2 = ((uint32_t)r != ro2) ? v_rk[1] + dk + dinc(cnt4<NS>(a2, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
+                    const int v1 = ((uint32_t)r != ro1) ? v_rk[0] + dk + c7_delta(T.c7_inc, cnt4x2<NS>(a1, (uint32_t)r)) : 0;
+                    const int v2 = ((uint32_t)r != ro2) ? v_rk[1] + dk + c7_delta(T.c7_inc, cnt4x2<NS>(a2, (uint32_t)r)) : 0;
                     // (small cost: slot 1 rides in the HIGH half -- its no-candidate mark, bit 15 of W, is the upper half of the sign-extended word)
                     L.RT[r] = kSmall ? (int)(((uint32_t)v2 & 0xFFFFu) | ((uint32_t)v1 << 16)) : (int)(((uint32_t)v1 & 0xFFFFu) | ((uint32_t)v2 << 16));
                 }
@@ -714,7 +749,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     const int inc = wfld(w, kWIncR);
                     if constexpr (kSmall) {
                         // (inc + incL * lead1 | inc + incL * lead2) + RT's word, times lam, plus (K01 | K02): three packed instructions
-                        uint32_t d = pk_mad_s(pk_add(pk_mad_lo((uint32_t)wfld(w, kWIncL), leadp, (uint32_t)inc), (uint32_t)rt), (uint32_t)lam, K0p);
+                        uint32_t d = pk_mad_ss(pk_add(pk_mad_lo((uint32_t)wfld(w, kWIncL), leadp, (uint32_t)inc), (uint32_t)rt), (uint32_t)lam, K0p);
                         if (decltype(with_w)::value) {
                             const uint32_t x = (uint32_t)(base + lane);
                             const uint32_t xw = x | ((uint32_t)XR[x] << 16);
@@ -833,7 +868,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 {   // rack-dependent part of the delta, racks strided over the lanes
                     const int dP_rack_old = kPriced ? p_out(L.K[ro], T.rack_lo, T.rack_hi, PG[ro]) : 0;
                     for (int r = lane; r < T.R; r += 64) {
-                        int v = ((uint32_t)r != ro) ? dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + dinc(cnt4<NS>(a, (uint32_t)r), T.prack_lo, T.prack_hi) : 0;
+                        int v = ((uint32_t)r != ro) ? dV_rack_old + dinc(L.K[r], T.rack_lo, T.rack_hi) + c7_delta(T.c7_inc, cnt4x2<NS>(a, (uint32_t)r)) : 0;
                         if (kPriced)  // rack part of the price delta rides in the upper 24 bits (the violation delta is within -8..8)
                             v = (v & 0xFF) | ((((uint32_t)r != ro) ? dP_rack_old + p_in(L.K[r], T.rack_lo, T.rack_hi, PG[r]) : 0) * 256);
                         L.RT[r] = v;
@@ -985,7 +1020,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 uint32_t key = kKeyNull, vw = 0;   // this lane's best partner slot
                 int dV = 0, dObj = 0, q = 0, j = 0;
                 const int nrp = lead ? 0 : 1;
-                const int cnt_a_ru = cnt4<NS>(a, ro);
+                const int cnt_a_ru2 = cnt4x2<NS>(a, ro);   // (counts in twos: c7_delta)
                 const uint32_t wu = L.W[uw & 0xFFFFu];
                 const int pl_u = kPriced ? price_lead(PR[uw & 0xFFFFu]) : 0;
                 const int bwl_u = hbw ? (int)(BW[uw & 0xFFFFu] >> 16) : 0;
@@ -1005,13 +1040,13 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     // independent of the partner slot j: what u would be worth in q, and q's replicas in u's rack
                     const int u_in_q_lead = role_w2<NS>(cb, uw, T.w00, T.w10), u_in_q_fol = role_w2<NS>(cb, uw, T.w01, T.w11);
                     // what leaving rack ro costs (u leaves a, a replica in ro joins b): the same for every partner slot in another rack
-                    const int dv_ro = ddec(cnt_a_ru, T.prack_lo, T.prack_hi) + dinc(cnt4<NS>(b, ro), T.prack_lo, T.prack_hi);
-                    // replicas of q in the rack of each partner slot.  Three slots (RFT = 3): the three pairwise rack equalities give all
+                    const int dv_ro = c7_delta(T.c7_dec, cnt_a_ru2) + c7_delta(T.c7_inc, cnt4x2<NS>(b, ro));
+                    // replicas of q in the rack of each partner slot, in twos.  Three slots (RFT = 3): the three pairwise rack equalities give all
                     // three counts (an empty word's rack, 0xFFFF, equals only another empty word's, as in cnt4); otherwise counted per slot
                     int cnt_b_rv[3] = {0, 0, 0};
                     if constexpr (RFT == 3) {
                         const int e01 = (int)((b.w[0] >> 16) == (b.w[1] >> 16)), e02 = (int)((b.w[0] >> 16) == (b.w[2] >> 16)), e12 = (int)((b.w[1] >> 16) == (b.w[2] >> 16));
-                        cnt_b_rv[0] = 1 + e01 + e02; cnt_b_rv[1] = 1 + e01 + e12; cnt_b_rv[2] = 1 + e02 + e12;
+                        cnt_b_rv[0] = (1 + e01 + e02) << 1; cnt_b_rv[1] = (1 + e01 + e12) << 1; cnt_b_rv[2] = (1 + e02 + e12) << 1;
                     }
 #pragma unroll
                     for (int jj = 0; jj < NS; ++jj) {
@@ -1033,9 +1068,9 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         }
                         const uint32_t rv = v >> 16;
                         if (rv != ro)
-                            dVx += dv_ro + dinc(cnt4<NS>(a, rv), T.prack_lo, T.prack_hi) + ddec(RFT == 3 ? cnt_b_rv[jj < 3 ? jj : 0] : cnt4<NS>(b, rv), T.prack_lo, T.prack_hi);
+                            dVx += dv_ro + c7_delta(T.c7_inc, cnt4x2<NS>(a, rv)) + c7_delta(T.c7_dec, RFT == 3 ? cnt_b_rv[jj < 3 ? jj : 0] : cnt4x2<NS>(b, rv));
                         uint32_t keyx;
-                        if constexpr (kSmall) keyx = ok ? key_small(mad24(lam, dVx, mad24s(-S, dObjx, kDBias)), (tie0 + (uint32_t)jj * 0x55u) & 0xFFu) : kKeyNull;
+                        if constexpr (kSmall) keyx = ok ? key_small(mad24s(lam, dVx, mad24s(-S, dObjx, kDBias)), (tie0 + (uint32_t)jj * 0x55u) & 0xFFu) : kKeyNull;
                         else if (kPriced) keyx = ok ? make_key_tie_p(lam, S, dVx, dObjx, dPx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
                         else keyx = ok ? make_key_tie(lam, S, dVx, dObjx, tie0 + (uint32_t)jj * 0x55u) : kKeyNull;
                         if (keyx < key) { key = keyx; vw = v; q = qq; j = jj; dV = dVx; dObj = dObjx; }
@@ -1069,7 +1104,9 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
             }
             }   // (one slot at a time)
         }
-        if (V == 0 && obj > best_obj) { best_obj = obj; snapshot(T, L, ext, best, tid, nthr); }   // (V, obj: as the iteration's move, if any, left them)
+        // (V, obj: as the iteration's move, if any, left them.  Both are scalars, and so is best_obj: snapshot() loops a wave-uniform
+        //  number of times, so this branch stays a scalar one and what is set behind it a scalar)
+        if (V == 0 && obj > best_obj) { best_obj = obj; snapshot(T, L, ext, best, tid, nthr); }
     }
 
     // ---- end of launch: verify the incremental bookkeeping against a from-scratch recount ----
@@ -1077,6 +1114,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     recount(T, L, tid, nthr, krt);
     if (kTeam) __syncthreads();
     int V2, obj2;
+    T = topic_regs<RFT>(TD);   // (the band ends: not kept across the loop)
     full_cost<NW, kTeam>(T, L, CUR, RSZ, tid, nthr, V2, obj2, hbw ? BW : nullptr, TS, wave, n_waves);
     if ((V2 != V || obj2 != obj) && tid == 0) atomicAdd(pl.drift, 1);
     if (!kGlobalA)
@@ -1330,6 +1368,10 @@ bool search_rf3_eligible(bool global_a, bool cur_global, bool priced, int nw, in
 //   int16's range, kSmallCostMax = 16384: the biased cost field then stays inside [16384, 49152], far from both the clamp's ends and
 //   the no-candidate value 0xFFFF.  (The default options give 8 * 40 + 4 * 4 * 4 = 384.)
 // False whenever the launch is priced (prices are added to the cost; broker weights make a session priced).
+// The small-cost form also looks a broker's band rows up in per-topic tables (band_tab, kao_search_dev.h): a launch group takes it
+// only when the replica and the leader band of every topic fit one (hi - lo <= 2; a balanced topic has hi - lo <= 1, wider bands come
+// from bounds_override), so the kernel holds one form of the row, chosen per launch on the host.
+bool search_band_tabs(int rep_lo, int rep_hi, int lead_lo, int lead_hi) { return band_tab_fits(rep_lo, rep_hi) && band_tab_fits(lead_lo, lead_hi); }
 bool search_small_cost(int lam_min, int lam_max, int obj_scale, int w_abs_max, bool priced) {
     if (priced || lam_min < 0 || lam_max < lam_min || obj_scale < 1 || w_abs_max < 0) return false;
     return 8 * (int64_t)lam_max + 4 * (int64_t)obj_scale * (int64_t)w_abs_max <= (int64_t)kSmallCostMax;
@@ -1377,3 +1419,18 @@ bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks
 }
 
 }  // namespace kao
+
+// Test hooks (include/kao.h): the band-row and C7 lookups on the host, through the table builders the kernels use.
+extern "C" int kao_search_band_row(int32_t lo, int32_t hi, int32_t c, int32_t force_plain, int32_t *fits) {
+    using namespace kao;
+    const bool tab = band_tab_fits(lo, hi);
+    if (fits) *fits = tab ? 1 : 0;
+    if (tab && !force_plain) return (int)band_lookup_plain(c, band_tab_bias(lo), band_tab(lo, hi));
+    const int a = std::min(std::max(c - lo, -1), 1), b = std::min(std::max(c - hi, -1), 1);   // band_entry: the two clamps, 3 a + b, the shift
+    return (int)((kBandTab >> (uint32_t)(6 * (3 * a + b) + 24)) & 63u);
+}
+extern "C" int kao_search_rack_delta(int32_t lo, int32_t hi, int32_t c, int32_t dec) {
+    const uint32_t tab = kao::c7_tab(dec != 0, lo, hi);
+    const uint32_t f = (tab >> ((2u * (uint32_t)c) & 31u)) & 3u;   // v_bfe_i32 at twice the count, two bits, sign-extended
+    return (int)(f ^ 2u) - 2;
+}

@@ -102,6 +102,13 @@ __device__ __forceinline__ uint32_t pk_mad_s(uint32_t a, uint32_t s, uint32_t c)
     asm("v_pk_mad_i16 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(s), "v"(c));
     return r;
 }
+// pk_mad_s with the factor in a scalar register (the penalty: search_body forms it on the scalar unit); the addend is then a vector
+// operand -- a VALU instruction of this ISA reads one scalar register
+__device__ __forceinline__ uint32_t pk_mad_ss(uint32_t a, uint32_t s, uint32_t c) {
+    uint32_t r;
+    asm("v_pk_mad_i16 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "s"(s), "v"(c));
+    return r;
+}
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b) {
     uint32_t r;
     asm("v_pk_add_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -140,6 +147,9 @@ template <int NS = 0, int NW> __device__ __forceinline__ int cnt4(const Part<NW>
     for (int i = 0; i < (NS ? NS : NW); ++i) n += (int)((a.w[i] >> 16) == r);
     return n;
 }
+// twice that count: the bit offset of the count's field in a c7_tab (one shift behind the count: summed as selects of 0 / 2 every
+// compare's mask is a live scalar pair, and they spill)
+template <int NS = 0, int NW> __device__ __forceinline__ int cnt4x2(const Part<NW> &a, uint32_t r) { return cnt4<NS>(a, r) << 1; }
 // slot k < NS of a partition: three slots take two selects (the first select passes through an empty asm: selects between words of
 // the struct were turned into a dynamically indexed copy of it in scratch; through the asm goes a fresh value, not the three words
 // themselves, which stay live and were copied, three v_mov per call)
@@ -152,11 +162,25 @@ template <int NS, int NW> __device__ __forceinline__ uint32_t sel_slot(const Par
     } else return sel4(a, k);
 }
 
+// Row C7 (a partition's replicas per rack, band [prack_lo, prack_hi]) as two bit tables: a count is at most the partition's words, 8,
+// so the nine values of dinc and of ddec, signed 2-bit fields, fill 18 bits of a register each and a delta is one v_bfe_i32 of the
+// wave-uniform table at twice the count (cnt4x2 counts in twos) -- against two compares, a select and a subtract.
+constexpr uint32_t c7_tab(bool dec, int lo, int hi) {
+    uint32_t t = 0;
+    for (int c = 0; c <= 8; ++c) {
+        const int d = dec ? (c <= lo ? 1 : 0) - (c > hi ? 1 : 0) : (c >= hi ? 1 : 0) - (c < lo ? 1 : 0);   // ddec / dinc
+        t |= ((uint32_t)d & 3u) << (2 * c);
+    }
+    return t;
+}
+__device__ __forceinline__ int c7_delta(uint32_t tab, int cnt2) { return __builtin_amdgcn_sbfe((int)tab, (unsigned)cnt2, 2u); }
+
 struct TopicRegs {  // wave-uniform copy of the fields the inner loop needs
     int P, RF, R, m, Bx;
     uint32_t magic;
     int rep_lo, rep_hi, lead_lo, lead_hi, rack_lo, rack_hi, prack_lo, prack_hi;
     int w00, w01, w10, w11;
+    uint32_t c7_inc, c7_dec;   // c7_tab of [prack_lo, prack_hi]
 };
 
 template <int RFT = 0> __device__ __forceinline__ TopicRegs topic_regs(const TopicDev *TD) {   // RFT > 0: the replication factor of every topic of the launch
@@ -165,6 +189,7 @@ template <int RFT = 0> __device__ __forceinline__ TopicRegs topic_regs(const Top
     T.rep_lo = TD->rep_lo; T.rep_hi = TD->rep_hi; T.lead_lo = TD->lead_lo; T.lead_hi = TD->lead_hi;
     T.rack_lo = TD->rack_lo; T.rack_hi = TD->rack_hi; T.prack_lo = TD->prack_lo; T.prack_hi = TD->prack_hi;
     T.w00 = TD->w00; T.w01 = TD->w01; T.w10 = TD->w10; T.w11 = TD->w11;
+    T.c7_inc = c7_tab(false, T.prack_lo, T.prack_hi); T.c7_dec = c7_tab(true, T.prack_lo, T.prack_hi);
     return T;
 }
 
@@ -268,6 +293,42 @@ __device__ __forceinline__ uint32_t band_entry(int c, int lo, int hi) {
     asm("v_mad_i32_i24 %0, %1, 3, %2" : "=v"(t) : "v"(a), "v"(b));
     return (uint32_t)(kBandTab >> (uint32_t)(__mul24(t, 6) + 24)) & 63u;
 }
+// The same entry as a lookup.  Which of the nine combinations (a, b) a count stands for depends only on where it stands against
+// [lo, hi], so a row with a narrow band gets a table of its own, built once per launch: entry i = band_entry of the count lo - 1 + i
+// (i = 0: below the band, i = 1: at lo, ..., i = hi - lo + 2: above it), six bits each, and every entry behind the last one repeats
+// it -- the index is then clamped to the same [0, kBandTabLast] for every band and a row costs three instructions, the multiply-add
+// 6 c + (6 - 6 lo), a v_med3_i32 with two inline constants and a v_bfe_u32, against band_entry's eight.  kBandTabLast + 1 = 5 entries
+// fill one 32-bit register: bands with hi - lo <= 2 (a balanced topic has hi - lo <= 1; wider ones come from bounds_override).  Wider
+// bands keep band_entry, the same function (the host picks per launch group, search_band_tabs; tests/test_gpu_search_tables.py walks
+// both over every band).
+constexpr int kBandTabLast = 4;
+constexpr bool band_tab_fits(int lo, int hi) { return lo >= 0 && lo <= hi && hi <= 0xFFFF && hi - lo + 2 <= kBandTabLast; }
+constexpr uint32_t band_tab(int lo, int hi) {
+    uint32_t t = 0;
+    for (int i = 0; i <= kBandTabLast; ++i) {
+        const int c = lo - 1 + (i < hi - lo + 2 ? i : hi - lo + 2);
+        const int a = c < lo ? -1 : (c > lo ? 1 : 0), b = c < hi ? -1 : (c > hi ? 1 : 0);
+        t |= (uint32_t)band_entry_of(a, b) << (6 * i);
+    }
+    return t;
+}
+constexpr int band_tab_bias(int lo) { return 6 - 6 * lo; }
+// the lookup as plain arithmetic (the host's restatement of band_lookup, for the tests: kao_search_band_row)
+constexpr uint32_t band_lookup_plain(int c, int bias, uint32_t tab) {
+    const int x = 6 * c + bias;
+    return (tab >> (x < 0 ? 0 : (x > 6 * kBandTabLast ? 6 * kBandTabLast : x))) & 63u;
+}
+__device__ __forceinline__ uint32_t band_lookup(int c, int bias, uint32_t tab) {
+    int x;
+    asm("v_mad_i32_i24 %0, %1, 6, %2\n\tv_med3_i32 %0, %0, 0, 24" : "=&v"(x) : "v"(c), "v"(bias));
+    static_assert(6 * kBandTabLast == 24, "the clamp's inline constant");
+    return __builtin_amdgcn_ubfe(tab, (uint32_t)x, 6u);
+}
+// a row by the form the instantiation holds (search_body): r0, r1 = bias, table (kTab) or lo, hi
+template <bool kTab> __device__ __forceinline__ uint32_t band_row(int c, int r0, int r1) {
+    if constexpr (kTab) return band_lookup(c, r0, (uint32_t)r1);
+    else return band_entry(c, r0, r1);
+}
 __device__ __forceinline__ uint32_t band_fields(const TopicRegs &T, uint32_t c) {
     return band_entry((int)(c & 0xFFFFu), T.rep_lo, T.rep_hi) | (band_entry((int)(c >> 16), T.lead_lo, T.lead_hi) << 6);
 }
@@ -333,13 +394,18 @@ template <int NW, bool kTeam = false> __device__ __forceinline__ void full_cost(
     }
 }
 
+// (the trip count is wave-uniform and the lanes beyond P sit out inside the body: with `p = lane; p < P` as the loop's own bound the
+//  caller's "is this a new best" branch was merged with a per-lane one, and what it sets -- best_obj -- stopped being a scalar)
 template <int NW> __device__ __forceinline__ void snapshot(const TopicRegs &T, const WaveLds<NW> &L, const uint16_t *ext, uint16_t *best, int lane, int stride = 64) {
-    for (int p = lane; p < T.P; p += stride) {
-        const Part<NW> a = L.A[p];
-        uint16_t *o = best + p * T.RF;
+    for (int p0 = 0; p0 < T.P; p0 += stride) {
+        const int p = p0 + lane;
+        if (p < T.P) {
+            const Part<NW> a = L.A[p];
+            uint16_t *o = best + p * T.RF;
 #pragma unroll
-        for (int k = 0; k < NW; ++k)
-            if (k < T.RF) o[k] = ext[a.w[k] & 0xFFFFu];
+            for (int k = 0; k < NW; ++k)
+                if (k < T.RF) o[k] = ext[a.w[k] & 0xFFFFu];
+        }
     }
 }
 

@@ -229,6 +229,7 @@ int plan_groups(kao_session &s, int n_cu, SessionPlan &pl) {
             const TopicDev &d = s.pts[(size_t)t].d;
             g.rf_uniform = g.rf_uniform < 0 ? d.RF : (g.rf_uniform == d.RF ? d.RF : 0);
             for (const int w : {d.w00, d.w01, d.w10, d.w11}) g.w_abs_max = std::max(g.w_abs_max, w < 0 ? (w == INT32_MIN ? INT32_MAX : -w) : w);
+            g.band_tabs = g.band_tabs && search_band_tabs(d.rep_lo, d.rep_hi, d.lead_lo, d.lead_hi);
             g.rf3 = g.rf3 && d.RF == 3 && d.rf_cur <= 3;   // (RF 3 with four current replicas: word 3 of CUR is a real replica)
             g.maxP = std::max(g.maxP, d.P); g.maxBx = std::max(g.maxBx, d.Bx); g.maxB = std::max(g.maxB, d.B); g.maxR = std::max(g.maxR, d.R); g.wide = g.wide || (int64_t)d.P * d.RF >= 512;
         }
@@ -482,7 +483,7 @@ int kao_session_step(kao_session *s) {
         }
         const int rft = g.rf3 ? 3 : 0;
         const bool rf3_runs = rft && search_rf3_eligible(g.global_a, g.cur_global, s->priced, g.nw, g.team);
-        const bool small = rf3_runs && s->small_on && search_small_cost(gp.lam_min, gp.lam_max, gp.obj_scale, g.w_abs_max, s->priced);
+        const bool small = rf3_runs && s->small_on && g.band_tabs && search_small_cost(gp.lam_min, gp.lam_max, gp.obj_scale, g.w_abs_max, s->priced);
         launch_search(sp, gp, g.smap_n, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team, rft, small);
         if (rf3_runs) s->search_rf3_launches++;
         if (small) s->search_small_launches++;
