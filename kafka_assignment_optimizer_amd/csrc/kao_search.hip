@@ -4,6 +4,10 @@
 //                   delta-evaluated for feasibility (C3,C4,C6,C7; C1,C2,C5 hold by construction) and move cost against broker / rack
 //                   tables staged in LDS; a DPP min-reduce over the wavefront picks the move.  k_search<false> also keeps the
 //                   assignment words in LDS; k_search<true> leaves them in HBM/L2 for topics that do not fit.
+//                   An initialising launch first fills the holes of the current assignment by best insertion, scored from the same
+//                   band state the loop scans with: W is built in front of the fill, the partition's brokers are marked in it, a
+//                   rack table is built per hole and the winner's counters and band rows are updated at once (fill_hole,
+//                   kao_search_dev.h), so the loop starts from the W the fill leaves.
 //   k_search_curg : working assignment in LDS, current assignment from global memory.
 //   k_team        : the wavefronts of a workgroup as a team on ONE restart (topics in global memory).
 //   k_init        : the hole filling of an initialising launch, one workgroup per restart (topics in global memory).
@@ -59,6 +63,13 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     const TopicDev *TD = pl.topics + bm.x;
 
     TopicRegs T = topic_regs<RFT>(TD);
+    // both C7 tables are formed here, once: the hole filling reads c7_inc, the loop both, and left to itself the compiler builds the second
+    // table behind the fill from the first one's compare masks, kept alive across it as twelve spilled scalars
+    {
+        uint32_t v0 = T.c7_inc, v1 = T.c7_dec;
+        asm volatile("" : "+v"(v0), "+v"(v1));
+        T.c7_inc = (uint32_t)__builtin_amdgcn_readfirstlane((int)v0); T.c7_dec = (uint32_t)__builtin_amdgcn_readfirstlane((int)v1);
+    }
     // What the iteration loop rebuilds a broker's band rows from (finish), four registers: per row the lookup's bias and table in the
     // small-cost form (the host picks it only for groups whose bands all fit a band_tab: search_band_tabs), the band's ends for
     // band_entry otherwise.  They are operands of per-lane arithmetic only: held in VGPRs.  The SGPR file is full and every spilled
@@ -182,15 +193,30 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     recount(T, L, tid, nthr, krt);
     if (kTeam) __syncthreads();
 
+    // W from the counters: current with C from here on -- through the hole filling, which scores its candidates from it, and through every
+    // accepted move of the loop below.  (A team strides it together; its first wavefront then fills the holes alone.)
+    rebuild_band_state(T, L, XR, inv, tid, nthr);
+    if (lane == 0) L.RT[krt - 1] = 0;                 // the spare entry padding lanes read
+    if (kTeam) __syncthreads();
+
     if (prm.init == 1) {
-        // ---- hole filling by best insertion, holes in (p,k) order.  Partitions are inspected 64 at a time (one per
-        //      lane); only those with a hole are visited, in ascending order. ----
+        // ---- hole filling by best insertion, holes in (p,k) order, in band-state form (fill_hole, kao_search_dev.h): per listed
+        //      partition its brokers are marked in W, per hole a rack table is built and every index is scored from W and RT, 64 per
+        //      round; the winner's counters and band rows are brought up to date at once, so W stays what rebuild_band_state would
+        //      compute, and the winner is marked before the partition's next hole is scanned. ----
         // Two passes: leader holes of all partitions first, then follower holes (leaders are the scarcer resource).
         // Round 4: the partitions that have a hole are listed by the host (TopicDev::hole_off: static, they depend on the current
         // assignment only) -- inspecting all P partitions twice, 64 per trip with a global load each, was most of the 70-ms first
         // launch of a 100,000-partition topic, holes or not.  Same holes, same order.
+        // Objective weights: a candidate has one only as a current replica of the partition that is not in its working words.  RFT = 3:
+        // the working words start as the current ones and the fill only adds, so no candidate has a weight and none is scored.
+        // Elsewhere the current RF may exceed RF: the rounds that hold a dropped current replica are scored with weights.
+        constexpr bool kFillWeights = RFT != 3;
         const uint32_t *HL = pl.cur_pool + TD->hole_off;
-        if (!kTeam || wave == 0)   // (a team: its first wavefront fills the holes, in the same order as a single one)
+        const FillTabs F{L.W, XR, L.K, L.RT, PR, PG, hbw ? BW : nullptr};
+        // (a team: its first wavefront fills the holes, in the same order as a single one; the others wait at the barrier behind the
+        //  fill and read nothing before it, so the marks in the shared W are this wavefront's own business)
+        if (!kTeam || wave == 0)
         for (int pass = 0; pass < 2; ++pass) {
             const uint32_t n_holes = HL[pass], *hl = HL + 2 + (pass ? HL[0] : 0u);
             // the next hole's rows are loaded while this one is scanned (a pass lists every partition once, so the rows of the next
@@ -202,47 +228,32 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 Part<NW> a = a_n;  // same address in every lane: broadcast
                 const Part<NW> c = c_n;
                 if (hi + 1 < n_holes) { p_n = (int)hl[hi + 1]; a_n = L.A[p_n]; c_n = CUR[p_n]; }
-#pragma unroll
-                for (int k = 0; k < NW; ++k) {
-                    if (k >= T.RF) break;
-                    if ((k == 0) != (pass == 0)) continue;  // this pass handles the other kind of slot
-                    if (a.w[k] != kNoneW) continue;  // wave-uniform
-                    // best insertion: every valid broker not in the partition, 64 per round (lane = internal index)
+                fill_mark<NS>(L.W, a, lane);   // (all slots empty: nothing to mark)
+                // (one body for every slot, the slot a scalar: unrolled over the words it was three copies, each with scalars of its own
+                //  hoisted in front of the hole loop, in a kernel whose SGPR file is full)
+#pragma nounroll
+                for (int k = pass; k < (pass ? T.RF : 1); ++k) {   // pass 0: the leader slot; pass 1: the follower slots
+                    if ((uint32_t)__builtin_amdgcn_readfirstlane((int)sel_slot<NS>(a, k)) != kNoneW) continue;
                     const uint32_t hmix = slo ^ fmix32(shi + (uint32_t)rho * 0x9E3779B1u + (uint32_t)(p * NW + k) * 0x27D4EB2Fu + 0x5BD1E995u + prm.gen * 0x632BE5ABu);
-                    const int wl = k == 0 ? T.w00 : T.w01, wf = k == 0 ? T.w10 : T.w11;
-                    uint32_t key = kKeyNull, xw_l = kNoneW;
-#pragma unroll 2
-                    for (int base = 0; base < T.Bx; base += 64) {
-                        const uint32_t x = (uint32_t)(base + lane);
-                        const uint32_t r = XR[x];
-                        const uint32_t xw = x | (r << 16);
-                        const bool okx = (r != inv) & !in4(a, xw);
-                        const uint32_t cn = L.C[x];
-                        const uint32_t rk = r;   // (padding lanes, no candidates anyway, read the spare entry krt - 1)
-                        int dV = dinc((int)(cn & 0xFFFFu), T.rep_lo, T.rep_hi) + dinc(L.K[rk], T.rack_lo, T.rack_hi) +
-                                 dinc(cnt4(a, r), T.prack_lo, T.prack_hi);
-                        if (k == 0) dV += dinc((int)(cn >> 16), T.lead_lo, T.lead_hi);
-                        const uint32_t tie = fmix32(hmix + x * 0x165667B1u) >> 24;
-                        uint32_t keyx;
-                        if (kPriced) {
-                            const uint32_t prx = PR[x];
-                            int dP = p_in((int)(cn & 0xFFFFu), T.rep_lo, T.rep_hi, price_rep(prx)) + p_in(L.K[rk], T.rack_lo, T.rack_hi, PG[rk]);
-                            if (k == 0) dP += p_in((int)(cn >> 16), T.lead_lo, T.lead_hi, price_lead(prx));
-                            keyx = okx ? make_key_tie_p(prm.lam_max, S, dV, role_w2(c, xw, wl, wf) + (hbw ? bw_of(BW[x], k == 0) : 0), dP, tie) : kKeyNull;
-                        }
-                        else keyx = okx ? make_key_tie(prm.lam_max, S, dV, role_w2(c, xw, wl, wf), tie) : kKeyNull;
-                        if (keyx < key) { key = keyx; xw_l = xw; }
-                    }
-                    const uint32_t kmin = wave_umin(key);
-                    const unsigned long long bal = __ballot(key == kmin);
-                    const uint32_t xw_win = (uint32_t)__builtin_amdgcn_readlane((int)xw_l, __ffsll((long long)bal) - 1);  // ties: lowest lane
-                    a.w[k] = xw_win;
+                    // (small cost: no clamp -- a hole's cost is lam_max * dV with |dV| <= 4, inside search_small_cost's 8 lam_max + 4 S w_max)
+                    const uint32_t xw_win = fill_hole<NS, kPriced, !kSmall, kFillWeights>(T, F, a, c, k == 0, hmix, prm.lam_max, S, lane);
+                    if (xw_win == kNoneW) continue;   // (no candidate: fewer valid brokers than replicas, refused by the model)
+                    set_slot(a, k, xw_win);
                     if (lane == 0) {
+                        // the winner's counters, then its band rows from them (the replica row; the leader row too for a leader hole),
+                        // written with the mark: it is a broker of the partition now
+                        const uint32_t xs = xw_win & 0xFFFFu;
                         reinterpret_cast<uint32_t *>(&L.A[p])[k] = xw_win;
-                        L.C[xw_win & 0xFFFFu] += (k == 0) ? 0x10001u : 1u;
+                        const uint32_t cx = L.C[xs] + ((k == 0) ? 0x10001u : 1u);
+                        L.C[xs] = cx;
                         L.K[xw_win >> 16] += 1;
+                        uint32_t wx = band_row<kBandTabs>((int)(cx & 0xFFFFu), bq_r0, bq_r1);
+                        if (k == 0) wx |= band_row<kBandTabs>((int)(cx >> 16), bq_l0, bq_l1) << 6;
+                        else wx |= L.W[xs] & kWRowL;
+                        L.W[xs] = (uint16_t)(wx | kWNoCand);
                     }
                 }
+                fill_unmark<NS>(L.W, a, lane);   // the words as they are now: the winners' rows stay, without the mark
             }
         }
         if (kGlobalA) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -252,8 +263,6 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     int V, obj;
     full_cost<NW, kTeam>(T, L, CUR, RSZ, tid, nthr, V, obj, hbw ? BW : nullptr, TS, wave, n_waves);
     if (V == 0 && obj > best_obj) { best_obj = obj; snapshot(T, L, ext, best, tid, nthr); }
-    rebuild_band_state(T, L, XR, inv, tid, nthr);     // W from the counters; kept current by every accepted move below
-    if (lane == 0) L.RT[krt - 1] = 0;                 // the spare entry padding lanes read
     if (kTeam) __syncthreads();
 
     // ---- per-lane RNG stream of this launch (LCG mod 2^24, re-keyed every launch) ----

@@ -343,6 +343,118 @@ template <int NW> __device__ __forceinline__ void rebuild_band_state(const Topic
     for (int x = lane; x < ((T.Bx + 63) & ~63); x += stride) L.W[x] = (uint16_t)(XR[x] == inv ? (kWNoCand | kWNoCand2) : band_fields(T, L.C[x]));
 }
 
+// ------------------------------------------------------------------------------------------------
+// Hole filling of an initialising launch in band-state form (search_body's `init == 1` block; specification: oracle/kao_port.c::ls_init).
+// A hole (p,k) takes the valid broker outside the partition with the lowest lam_max * dV - S * dObj of its insertion, ties by eight
+// hashed bits, then the lowest lane, then the earliest round.  The scan has the form of the iteration loop's one-slot REPLACE scan:
+// the brokers of the partition carry kWNoCand in W (the caller marks them, fill_mark / fill_unmark), the rack-dependent part of the
+// delta comes out of a table built once per hole, and a candidate costs one W read, one RT read, two bit-field extracts, a
+// multiply-add, the hash and the key; the running minimum is one v_min_u32.  The tables come by pointer, so that k_init can take the
+// helper over once its LDS carve holds a W.
+// ------------------------------------------------------------------------------------------------
+struct FillTabs {
+    uint16_t *W;          // [Bx to 64] band state, current with C; the partition's brokers marked kWNoCand
+    const uint8_t *XR;    // [Bx to 64] rack of index x, padding: the spare entry krt - 1
+    const int *K;         // [krt] replicas per rack
+    int *RT;              // [krt] the hole's rack table; RT[krt - 1] == 0 (the caller's)
+    const uint32_t *PR;   // priced: packed broker prices
+    const int *PG;        //         rack prices
+    const uint32_t *BW;   //         broker weights (nullptr: none)
+};
+constexpr uint32_t kFillTieStep = 0x165667B1u;   // the tie hash of index x is fmix32(hmix + x * kFillTieStep) >> 24
+// lane i < NS looks after word i of the partition: its broker is no candidate (row C5) while the partition's holes are filled.  The
+// marks come off by clearing the bit -- a valid index carries it for no other reason -- on the words as they are AFTER the fill, so
+// the winners, whose rows fill_insert has written with the mark, lose it too and keep their updated rows.
+template <int NS, int NW> __device__ __forceinline__ void fill_mark(uint16_t *W, const Part<NW> &a, int lane) {
+    const uint32_t ai = sel_slot<NS>(a, lane & (NW - 1));
+    if ((lane < NS) & (ai != kNoneW)) W[ai & 0xFFFFu] |= (uint16_t)kWNoCand;
+}
+template <int NS, int NW> __device__ __forceinline__ void fill_unmark(uint16_t *W, const Part<NW> &a, int lane) {
+    const uint32_t ai = sel_slot<NS>(a, lane & (NW - 1));
+    if ((lane < NS) & (ai != kNoneW)) W[ai & 0xFFFFu] &= (uint16_t)~kWNoCand;
+}
+// RT[r] = what one more replica in rack r does to the rack's total (C6) and to the partition's count in it (C7); priced: that
+// violation delta in the low byte, the rack's price -- where its total leaves or re-enters the band -- above it, as in the REPLACE scan
+template <int NS, bool kPriced, int NW> __device__ __forceinline__ void fill_rack_table(const TopicRegs &T, const FillTabs &F, const Part<NW> &a, int lane) {
+    for (int r = lane; r < T.R; r += 64) {
+        const int kr = F.K[r];
+        int v = dinc(kr, T.rack_lo, T.rack_hi) + c7_delta(T.c7_inc, cnt4x2<NS>(a, (uint32_t)r));
+        if (kPriced) v = (v & 0xFF) | (p_in(kr, T.rack_lo, T.rack_hi, F.PG[r]) * 256);
+        F.RT[r] = v;
+    }
+}
+// One round: the key of candidate x, (cost + bias) << 16 | tie << 8 | rd, cost field 0xFFFF where x is no candidate (W's bit 15,
+// sign-extended).  `h` = hmix + x * kFillTieStep.  fmix32's last xor-shift does not reach bits 31:24 and is left out.
+// kClamp = false: small-cost launches.  A hole's cost is lam_max * dV with 0 <= |dV| <= 4 (replica row, leader row, rack total, the
+// partition's count in the rack) and no objective term (kWithW is false there), inside search_small_cost's 8 lam_max + 4 S w_max.
+template <int NS, bool kPriced, bool kClamp, bool kWithW, int NW>
+__device__ __forceinline__ uint32_t fill_round(const TopicRegs &T, const FillTabs &F, const Part<NW> &c, int x, int rd, uint32_t h, int lam, int S, bool lead) {
+    const int w = (int)reinterpret_cast<const short *>(F.W)[x];
+    const uint32_t r = F.XR[x];
+    const int rt = F.RT[r];
+    const uint32_t lw = lead ? 2u : 0u, lf = lead ? 1u : 0u;   // widths of the leader field / flag: zero for follower holes
+    int cost;
+    if (kPriced) {
+        const uint32_t prx = F.PR[x];
+        const int dVx = wfld(w, kWIncR) + wfldw(w, kWIncL, lw) + (int)(signed char)(rt & 0xFF);
+        cost = __mul24(lam, dVx) + kDBias + (rt >> 8) + (wflag(w, kWPinR) & price_rep(prx)) + (wflagw(w, kWPinL, lf) & price_lead(prx));
+        if (F.BW) cost -= __mul24(S, bw_of(F.BW[x], lead));
+    } else {
+        cost = mad24s(lam, wfld(w, kWIncR) + wfldw(w, kWIncL, lw) + rt, kDBias);
+    }
+    if (kWithW) cost -= __mul24(S, role_w2<NS>(c, (uint32_t)x | (r << 16), lead ? T.w00 : T.w01, lead ? T.w10 : T.w11));
+    if (kClamp) cost = min(max(cost, 0), 2 * kDBias - 2);
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u;
+    return ((uint32_t)cost << 16) | ((h >> 16) & 0xFF00u) | (uint32_t)rd | ((uint32_t)w & 0xFFFF0000u);
+}
+// One hole of partition words `a` (current words `c`): the winner's word x | rack << 16, wave-uniform; kNoneW when no index is a
+// candidate (fewer valid brokers than replicas: the model refuses such a topic).
+// kWeights: a candidate has an objective weight only as a current replica of the partition that is not in `a`; the rounds that hold
+// one (at most NS) are scored through the kWithW body.  False for the RF-3 instantiation: `a` starts as the current words and the
+// fill only adds, so every current replica is in `a` and marked.
+template <int NS, bool kPriced, bool kClamp, bool kWeights, int NW>
+__device__ __forceinline__ uint32_t fill_hole(const TopicRegs &T, const FillTabs &F, const Part<NW> &a, const Part<NW> &c, bool lead, uint32_t hmix, int lam, int S, int lane) {
+    fill_rack_table<NS, kPriced>(T, F, a, lane);
+    int mr[NS] = {};
+    if constexpr (kWeights) {
+        const uint32_t ci = sel_slot<NS>(c, lane & (NW - 1));
+        const int mr_l = ((lane < NS) & (ci != kNoneW) & !in4<NS>(a, ci)) ? (int)((ci & 0xFFFFu) >> 6) : -1;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) mr[i] = __builtin_amdgcn_readlane(mr_l, i);
+    }
+    uint32_t h = hmix + (uint32_t)lane * kFillTieStep;
+    uint32_t best = kKeyNull;
+    int chunk = 0;
+    for (int cb = 0; cb < T.Bx; cb += 16384) {   // the key holds the round in eight bits: chunks of 256 rounds
+        uint32_t bestc = kKeyNull;
+        const int n_rd = (min(T.Bx, cb + 16384) - cb + 63) >> 6;
+        int rd = 0, x = cb + lane;
+        if constexpr (!kWeights) {
+            for (; rd + 1 < n_rd; rd += 2, x += 128, h += 128u * kFillTieStep) {   // two rounds share the address arithmetic and one v_min3_u32
+                const uint32_t k0 = fill_round<NS, kPriced, kClamp, false>(T, F, c, x, rd, h, lam, S, lead);
+                const uint32_t k1 = fill_round<NS, kPriced, kClamp, false>(T, F, c, x + 64, rd + 1, h + 64u * kFillTieStep, lam, S, lead);
+                bestc = min(bestc, min(k0, k1));
+            }
+            if (rd < n_rd) { bestc = min(bestc, fill_round<NS, kPriced, kClamp, false>(T, F, c, x, rd, h, lam, S, lead)); h += 64u * kFillTieStep; }
+        } else {
+            for (; rd < n_rd; ++rd, x += 64, h += 64u * kFillTieStep) {
+                bool wgt = false;   // wave-uniform
+#pragma unroll
+                for (int i = 0; i < NS; ++i) wgt |= mr[i] == (cb >> 6) + rd;
+                bestc = min(bestc, wgt ? fill_round<NS, kPriced, kClamp, true>(T, F, c, x, rd, h, lam, S, lead) : fill_round<NS, kPriced, kClamp, false>(T, F, c, x, rd, h, lam, S, lead));
+            }
+        }
+        if ((bestc >> 8) < (best >> 8)) { best = bestc; chunk = cb; }   // strict: ties stay with the earlier round
+    }
+    // one reduction: (cost, tie) << 7 | lane -- lowest key, then lowest lane; the round is read from the winner's lane
+    const uint32_t m = wave_umin(((best >> 1) & ~127u) | (uint32_t)lane);
+    if ((m >> 15) == 0xFFFFu) return kNoneW;
+    const int win = (int)(m & 63u);
+    const uint32_t bw = (uint32_t)__builtin_amdgcn_readlane((int)best, win);
+    const uint32_t xs = (uint32_t)__builtin_amdgcn_readlane(chunk, win) + ((bw & 255u) << 6) + (uint32_t)win;
+    return xs | ((uint32_t)F.XR[xs] << 16);
+}
+
 // rebuild C and K from A (lanes stride partitions; LDS atomics)
 // (a team calls it between two workgroup barriers and zeroes, then counts, with a barrier in between: `stride` > 64)
 template <int NW> __device__ __forceinline__ void recount(const TopicRegs &T, const WaveLds<NW> &L, int lane, int stride, int krt) {
@@ -397,7 +509,9 @@ template <int NW, bool kTeam = false> __device__ __forceinline__ void full_cost(
 // (the trip count is wave-uniform and the lanes beyond P sit out inside the body: with `p = lane; p < P` as the loop's own bound the
 //  caller's "is this a new best" branch was merged with a per-lane one, and what it sets -- best_obj -- stopped being a scalar)
 template <int NW> __device__ __forceinline__ void snapshot(const TopicRegs &T, const WaveLds<NW> &L, const uint16_t *ext, uint16_t *best, int lane, int stride = 64) {
-    for (int p0 = 0; p0 < T.P; p0 += stride) {
+    int p0 = 0;
+    do {   // (bottom-tested: a topic has a partition, and the lanes beyond P sit out anyway -- a top-tested loop keeps its guard `P < 1` as a
+           //  scalar pair across the iteration loop, which has none to spare)
         const int p = p0 + lane;
         if (p < T.P) {
             const Part<NW> a = L.A[p];
@@ -406,7 +520,8 @@ template <int NW> __device__ __forceinline__ void snapshot(const TopicRegs &T, c
             for (int k = 0; k < NW; ++k)
                 if (k < T.RF) o[k] = ext[a.w[k] & 0xFFFFu];
         }
-    }
+        p0 += stride;
+    } while (p0 < T.P);
 }
 
 }  // namespace kao
