@@ -1,0 +1,220 @@
+// kao-logdirs -- log-dir balance: the replica moves between the log dirs of one broker that lower the peak of the bytes a dir stores
+// (kao_balance_logdirs).
+//
+//   kao-logdirs --current current.json --log-dirs log-dirs.txt [--broker-list a,b,..] [--min-gain BYTES] [--max-rounds N] [--dry-run]
+//               --out plan.json [--report] [--device D]
+//
+// Every other planner treats a broker as one disk.  A JBOD broker has several log dirs, Kafka places a new replica in the dir with
+// the fewest partitions, not the fewest bytes, and the broker dies on its fullest dir.  This tool reads `kafka-log-dirs --describe`
+// output WITH its directories and moves replicas between the dirs of their own broker (disk to disk, no network) until no single
+// move closes a gap of more than --min-gain bytes (N, or N with K/M/G/T).
+// From the documents to the arrays of the call:
+//   brokers   those of --broker-list in that order (default: every broker of --log-dirs, ascending id); one outside it is left alone;
+//   dirs      a broker's dirs byte-wise ascending by name; a dir whose "error" is non-null is left out (no destination, its entries
+//             ignored, counted in the report);
+//   replicas  the partitions of --current by (topic, partition), the slots of a row in order; a slot is a movable replica iff its
+//             broker is in the list and has a non-future entry for the partition in a usable dir, whose size it takes;
+//   base      every other entry of a usable dir adds its size to the bytes of that dir that never move: future replicas,
+//             partitions --current does not hold, brokers that are not in the partition's row.
+// The same partition non-future twice on one broker is an error.  The plan lists the partitions with a moved replica: "replicas" is
+// the row of --current, "log_dirs" has the same length, the new dir's name for a moved slot and "any" for every other: what
+// kafka-reassign-partitions --execute takes for an intra-broker move.  --dry-run reports and leaves the plan empty.  --report prints
+// one line per broker and one for the call.  All computation happens in libkao.so on the GPU.
+// Exit status: 0 = ok, 1 = error, 2 = usage.
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <map>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../include/kao.h"
+#include "kao_cluster.h"
+#include "kao_json.h"
+#include "kao_sizes.h"
+
+namespace {
+
+[[noreturn]] void usage(const char *msg) {
+    if (msg) std::fprintf(stderr, "kao-logdirs: %s\n", msg);
+    std::fprintf(stderr,
+        "usage: kao-logdirs --current <reassignment.json> --log-dirs <kafka-log-dirs output> [--broker-list <id,id,...>]\n"
+        "                   [--min-gain N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report] [--device D]\n"
+        "writes the partitions with a replica that moves to another log dir of its broker; exit status: 0 = ok, 1 = error, 2 = usage\n");
+    std::exit(2);
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    std::string cur_path, brokers_csv, out_path, dirs_path;
+    int device = 0, max_rounds = 0;
+    bool report = false, dry_run = false, have_list = false;
+    uint64_t min_gain = 0;
+    for (int i = 1; i < argc; ++i) {
+        std::string a = argv[i];
+        auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
+        if (a == "--current") cur_path = need("--current");
+        else if (a == "--log-dirs") dirs_path = need("--log-dirs");
+        else if (a == "--broker-list") { brokers_csv = need("--broker-list"); have_list = true; }
+        else if (a == "--out") out_path = need("--out");
+        else if (a == "--dry-run") dry_run = true;
+        else if (a == "--device") device = std::atoi(need("--device").c_str());
+        else if (a == "--report") report = true;
+        else if (a == "--min-gain") {
+            if (!parse_bytes(need("--min-gain"), min_gain)) usage("--min-gain needs a byte count (N, or N with K/M/G/T)");
+        } else if (a == "--max-rounds") {
+            const std::string v = need("--max-rounds");
+            if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage("--max-rounds needs a value >= 0");
+            max_rounds = std::atoi(v.c_str());
+        } else if (a == "-h" || a == "--help") usage(nullptr);
+        else usage(("unknown flag " + a).c_str());
+    }
+    if (cur_path.empty() || dirs_path.empty() || out_path.empty()) usage("--current, --log-dirs and --out are required");
+    try {
+        // the rows of --current by (topic, partition)
+        std::map<Key, std::vector<int>> by_key;
+        {
+            const std::string txt = slurp(cur_path);
+            const JValue doc = JParser(txt).parse();
+            const JValue *parts = doc.get("partitions");
+            for (size_t i = 0; parts && i < parts->arr.size(); ++i) {
+                const JValue &e = parts->arr[i];
+                const JValue *t = e.get("topic"), *p = e.get("partition"), *r = e.get("replicas");
+                if (!t || !p || !r || r->kind != JValue::Arr) throw std::runtime_error("partition entry needs topic/partition/replicas");
+                const Key k{t->str, (int)p->num};
+                if (by_key.count(k)) throw std::runtime_error("current: partition " + k.first + "-" + std::to_string(k.second) + " listed twice");
+                std::vector<int> &reps = by_key[k];
+                for (auto &x : r->arr) reps.push_back((int)x.num);
+            }
+        }
+        const std::map<int, std::vector<LogDir>> table = load_log_dirs(dirs_path);
+        std::vector<int> ids;
+        if (have_list) {
+            for (auto &t : split(brokers_csv, ',')) if (!t.empty()) ids.push_back(std::atoi(t.c_str()));
+        } else {
+            for (auto &kv : table) ids.push_back(kv.first);
+        }
+        if (ids.empty()) throw std::runtime_error("empty broker list");
+        std::map<int, int> dense;
+        for (size_t i = 0; i < ids.size(); ++i) if (!dense.emplace(ids[i], (int)i).second) throw std::runtime_error("duplicate id in broker list");
+        const int B = (int)ids.size();
+
+        // the usable dirs of every broker, byte-wise ascending; where each partition sits on it
+        struct Held { int dir; uint64_t size; };
+        std::vector<std::vector<const LogDir *>> usable((size_t)B);
+        std::vector<int> skipped((size_t)B, 0);
+        std::vector<int32_t> dir_start(1, 0);
+        std::vector<std::map<Key, Held>> where((size_t)B);
+        std::vector<std::string> flat;   // global dir index -> name
+        for (int i = 0; i < B; ++i) {
+            auto it = table.find(ids[(size_t)i]);
+            if (it != table.end())
+                for (auto &d : it->second) {
+                    if (d.failed) ++skipped[(size_t)i];
+                    else usable[(size_t)i].push_back(&d);
+                }
+            std::sort(usable[(size_t)i].begin(), usable[(size_t)i].end(), [](const LogDir *x, const LogDir *y) { return x->name < y->name; });
+            for (size_t li = 0; li < usable[(size_t)i].size(); ++li) {
+                flat.push_back(usable[(size_t)i][li]->name);
+                for (auto &e : usable[(size_t)i][li]->entries) {
+                    if (e.future) continue;
+                    if (!where[(size_t)i].emplace(e.key, Held{dir_start.back() + (int)li, e.size}).second)
+                        throw std::runtime_error("log-dirs: broker " + std::to_string(ids[(size_t)i]) + " holds partition " + e.key.first + "-" + std::to_string(e.key.second) + " twice");
+                }
+            }
+            dir_start.push_back(dir_start.back() + (int32_t)usable[(size_t)i].size());
+        }
+        const int D = dir_start.back();
+
+        // the movable replicas; every other entry of a usable dir is base
+        struct Slot { const Key *key; const std::vector<int> *row; int j; };
+        std::vector<int32_t> dir;
+        std::vector<uint64_t> size;
+        std::vector<Slot> slots;
+        std::set<std::pair<int, Key>> claimed;
+        for (auto &kv : by_key)
+            for (size_t j = 0; j < kv.second.size(); ++j) {
+                auto di = dense.find(kv.second[j]);
+                if (di == dense.end()) continue;
+                auto h = where[(size_t)di->second].find(kv.first);
+                if (h == where[(size_t)di->second].end()) continue;
+                dir.push_back(h->second.dir);
+                size.push_back(h->second.size);
+                slots.push_back(Slot{&kv.first, &kv.second, (int)j});
+                claimed.insert({di->second, kv.first});
+            }
+        std::vector<uint64_t> base((size_t)std::max(D, 1), 0);
+        for (int i = 0; i < B; ++i)
+            for (size_t li = 0; li < usable[(size_t)i].size(); ++li)
+                for (auto &e : usable[(size_t)i][li]->entries)
+                    if (e.future || !claimed.count({i, e.key})) base[(size_t)dir_start[(size_t)i] + li] += e.size;
+        const int R = (int)dir.size();
+        const std::vector<int32_t> dir0 = dir;
+        if (dir.empty()) { dir.push_back(0); size.push_back(0); }   // the library takes no null pointer
+
+        int rc = kao_init(device);
+        if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+        int32_t n_moved = 0, status = 0;
+        uint64_t bytes_moved = 0, before = 0, after = 0;
+        int64_t stats[8] = {0};
+        std::vector<uint64_t> per((size_t)B * 6, 0);
+        rc = kao_balance_logdirs(B, dir_start.data(), base.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved,
+                                 &before, &after, per.data(), &status, stats);
+        if (rc) throw std::runtime_error(std::string("kao_balance_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
+        if (report) {
+            std::vector<int> replicas((size_t)B, 0);
+            for (int r = 0; r < R; ++r) ++replicas[(size_t)(std::upper_bound(dir_start.begin(), dir_start.end(), dir0[(size_t)r]) - dir_start.begin() - 1)];
+            unsigned long long total = 0, all_skipped = 0;
+            for (int r = 0; r < R; ++r) total += size[(size_t)r];
+            for (int d = 0; d < D; ++d) total += base[(size_t)d];
+            for (int i = 0; i < B; ++i) {
+                const uint64_t *p = per.data() + (size_t)i * 6;
+                all_skipped += (unsigned long long)skipped[(size_t)i];
+                std::fprintf(stderr, "logdirs: broker=%d dirs=%d skipped_dirs=%d replicas=%d peak_before=%llu peak_after=%llu lower_bound=%llu moved=%llu "
+                                     "bytes_moved=%llu rounds=%llu\n",
+                             ids[(size_t)i], (int)usable[(size_t)i].size(), skipped[(size_t)i], replicas[(size_t)i], (unsigned long long)p[0], (unsigned long long)p[1],
+                             (unsigned long long)p[2], (unsigned long long)p[3], (unsigned long long)p[4], (unsigned long long)p[5]);
+            }
+            std::fprintf(stderr, "logdirs: status=%s brokers=%d dirs=%d skipped_dirs=%llu replicas=%d peak_before=%llu peak_after=%llu replicas_moved=%d "
+                                 "bytes_moved=%llu bytes_total=%llu brokers_moved=%lld rounds=%lld moves=%lld proposals=%lld launches=%lld "
+                                 "stopped_by_max_rounds=%lld proven=%lld max_rounds_of_a_broker=%lld\n",
+                         status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, R, (unsigned long long)before,
+                         (unsigned long long)after, n_moved, (unsigned long long)bytes_moved, total, (long long)stats[0], (long long)stats[1], (long long)stats[2],
+                         (long long)stats[3], (long long)stats[4], (long long)stats[5], (long long)stats[6], (long long)stats[7]);
+        }
+        // the partitions with a moved replica, in (topic, partition) order: the replicas come out in that order already
+        std::string body;
+        int n_out = 0;
+        for (int r = 0; r < R;) {
+            int e = r;
+            bool moved = false;
+            while (e < R && slots[(size_t)e].key == slots[(size_t)r].key) { moved |= dir[(size_t)e] != dir0[(size_t)e]; ++e; }
+            if (moved) {
+                const std::vector<int> &row = *slots[(size_t)r].row;
+                std::vector<std::string> names(row.size(), "any");
+                for (int q = r; q < e; ++q)
+                    if (dir[(size_t)q] != dir0[(size_t)q]) names[(size_t)slots[(size_t)q].j] = flat[(size_t)dir[(size_t)q]];
+                body += (n_out++ ? ",\n" : "\n");
+                body += "    {\"topic\":" + quoted(slots[(size_t)r].key->first) + ",\"partition\":" + std::to_string(slots[(size_t)r].key->second) + ",\"replicas\":[";
+                for (size_t k = 0; k < row.size(); ++k) body += (k ? "," : "") + std::to_string(row[k]);
+                body += "],\"log_dirs\":[";
+                for (size_t k = 0; k < names.size(); ++k) body += (k ? "," : "") + quoted(names[k]);
+                body += "]}";
+            }
+            r = e;
+        }
+        std::ofstream f(out_path);
+        f << "{\"version\":1,\"partitions\":[" << body << "\n]}\n";
+        f.close();
+        if (!f) throw std::runtime_error("cannot write " + out_path);
+        kao_shutdown();
+        return 0;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "kao-logdirs: %s\n", e.what());
+        return 1;
+    }
+}

@@ -1,6 +1,7 @@
-// kao_sizes.h -- what kao-waves, kao-leaders, kao-failover and kao-disk share: partition sizes read from `kafka-log-dirs --describe` output or a
-// sizes document (kao-waves --sizes, kao-leaders --sizes, kao-failover --sizes), and the traffic document of kao-leaders --traffic and
-// kao-failover --traffic; byte counts with a K / M / G / T suffix (kao-waves --max-bytes-per-broker, kao-disk --min-gain).
+// kao_sizes.h -- what kao-waves, kao-leaders, kao-failover, kao-disk and kao-logdirs share: partition sizes read from `kafka-log-dirs --describe` output or a
+// sizes document (kao-waves --sizes, kao-leaders --sizes, kao-failover --sizes), the same output WITH its directories (kao-logdirs
+// --log-dirs), and the traffic document of kao-leaders --traffic and kao-failover --traffic; byte counts with a K / M / G / T suffix
+// (kao-waves --max-bytes-per-broker, kao-disk --min-gain).
 #pragma once
 #include <algorithm>
 #include <cctype>
@@ -13,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "kao_json.h"
 
@@ -100,6 +102,74 @@ inline std::map<Key, uint64_t> load_sizes(const std::string &path) {
         }
     } else {
         throw std::runtime_error("sizes: expected a \"brokers\" (kafka-log-dirs) or \"partitions\" document");
+    }
+    return out;
+}
+
+// `kafka-log-dirs --describe` output with what load_sizes folds away: per broker its log dirs in the order of the document, each with
+// its name, whether its "error" is non-null, and its entries (partition names split at the last '-'; sizes 0..2^53; isFuture).
+struct LogDirEntry {
+    Key key;
+    uint64_t size = 0;
+    bool future = false;
+};
+struct LogDir {
+    std::string name;
+    bool failed = false;
+    std::vector<LogDirEntry> entries;
+};
+inline std::map<int, std::vector<LogDir>> load_log_dirs(const std::string &path) {
+    const std::string txt = slurp(path);
+    JValue doc;
+    try {
+        doc = JParser(txt).parse();
+    } catch (const std::runtime_error &) {   // kafka-log-dirs prints status lines before its JSON line
+        std::istringstream in(txt);
+        std::string line;
+        bool found = false;
+        while (!found && std::getline(in, line)) {
+            const size_t b = line.find_first_not_of(" \t\r");
+            if (b != std::string::npos && line[b] == '{') { doc = JParser(line).parse(); found = true; }
+        }
+        if (!found) throw std::runtime_error("log-dirs: no JSON document found");
+    }
+    const JValue *brokers = doc.get("brokers");
+    if (!brokers || brokers->kind != JValue::Arr) throw std::runtime_error("log-dirs: expected a \"brokers\" (kafka-log-dirs) document");
+    std::map<int, std::vector<LogDir>> out;
+    for (auto &br : brokers->arr) {
+        const JValue *id = br.get("broker");
+        if (!id || id->kind != JValue::Num || id->raw.find_first_not_of("-0123456789") != std::string::npos) throw std::runtime_error("log-dirs: broker entry without an integer id");
+        const int b = (int)id->num;
+        if (out.count(b)) throw std::runtime_error("log-dirs: broker " + std::to_string(b) + " listed twice");
+        std::vector<LogDir> &dirs = out[b];
+        const JValue *lds = br.get("logDirs");
+        if (!lds) continue;
+        for (auto &ld : lds->arr) {
+            const JValue *name = ld.get("logDir"), *err = ld.get("error"), *parts = ld.get("partitions");
+            if (!name || name->kind != JValue::Str) throw std::runtime_error("log-dirs: broker " + std::to_string(b) + ": log dir without a name");
+            for (auto &d : dirs)
+                if (d.name == name->str) throw std::runtime_error("log-dirs: broker " + std::to_string(b) + ": log dir " + name->str + " listed twice");
+            LogDir dir;
+            dir.name = name->str;
+            dir.failed = err && err->kind != JValue::Null;
+            for (size_t i = 0; parts && i < parts->arr.size(); ++i) {
+                const JValue &e = parts->arr[i];
+                const JValue *fut = e.get("isFuture"), *pn = e.get("partition"), *v = e.get("size");
+                if (!pn || pn->kind != JValue::Str) throw std::runtime_error("log-dirs: log-dir entry without a partition name");
+                const size_t dash = pn->str.rfind('-');
+                const std::string idx = dash == std::string::npos ? "" : pn->str.substr(dash + 1);
+                if (dash == std::string::npos || dash == 0 || idx.empty() || idx.size() > 9 || idx.find_first_not_of("0123456789") != std::string::npos)
+                    throw std::runtime_error("log-dirs: partition name '" + pn->str + "' is not <topic>-<partition>");
+                LogDirEntry en;
+                en.key = Key{pn->str.substr(0, dash), std::atoi(idx.c_str())};
+                if (!v || v->kind != JValue::Num || v->raw.empty() || v->raw.size() > 16 || v->raw.find_first_not_of("0123456789") != std::string::npos ||
+                    (en.size = std::strtoull(v->raw.c_str(), nullptr, 10)) > kMaxSize)
+                    throw std::runtime_error("log-dirs: " + pn->str + ": size must be an integer 0..2^53");
+                en.future = fut && fut->kind == JValue::Bool && fut->b;
+                dir.entries.push_back(en);
+            }
+            dirs.push_back(dir);
+        }
     }
     return out;
 }

@@ -670,6 +670,45 @@ int kao_balance_disk_budget(int32_t n_brokers, int32_t n_racks, const uint8_t *r
                             int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
                             uint64_t *lower_bound, int32_t *status, int64_t stats[10] /* may be NULL */);
 
+/* ---- Log-dir balance inside each broker ---------------------------------------------------------------------
+ * Every planner above treats a broker as one disk; a JBOD broker has several log dirs and dies on the fullest of them.  Broker b
+ * owns the dirs dir_start[b] .. dir_start[b+1]-1 of ONE global dir index (CSR; n_dirs = dir_start[n_brokers]; a broker may own no
+ * dir, and at most KAO_LOGDIRS_MAX_DIRS).  Dir d carries base[d] bytes that never move (base == NULL: all 0).  Replica r sits in dir
+ * dir[r] and holds size[r] bytes; its broker is the one that owns dir[r] (nothing says which partition a replica belongs to).
+ * L(d) = base[d] + the sum of size[r] over the replicas with dir[r] == d.  A move takes replica r from dir a to another dir c OF THE
+ * SAME BROKER (Kafka copies disk to disk, no network traffic); the goal per broker is a low max_d L(d) over its dirs.
+ * Per broker, independently, synchronous rounds, each using the loads as they stand at its start.  The broker's n dirs are ranked by
+ * L descending (ties: dir index ascending; rank 0 is the heaviest, order[q] = the dir of rank q).  Every replica with size[r] > 0 on
+ * a broker with n >= 2 makes at most one proposal; a = its dir, q = rank(a): if q < n-1-q, c1 = order[n-1-q] (the i-th heaviest is
+ * paired with the i-th lightest) and the proposal is a -> c1 iff L(c1) + size[r] + min_gain < L(a) (evaluated without overflow;
+ * min_gain is any uint64_t); otherwise, if q >= 1, c2 = order[n-1], the lightest dir, under the same test; otherwise no proposal.
+ * Every dir of the broker is admissible, and if any dir passes the test the lightest one does: "no proposal" means that no single
+ * move of r closes a gap of more than min_gain.  A proposal wins iff its key q << 48 | (0xFFFF - code(size[r])) << 32 | r (code: the
+ * 16-bit logarithmic code of section 4k; r = the replica's index in the call's arrays; keys are unique) is the lowest of all
+ * proposals of the round that touch a and of all that touch its destination; all winners are applied together (they share no dir).
+ * A broker stops when a round has no proposal, or after max_rounds rounds of that broker (<= 0: no limit).  Every move lowers the
+ * sum of L^2 and leaves both loads below the old L(a): the rounds end, the peak never rises, the end state is move-stable.
+ * dir[] is rewritten in place; dry_run != 0 leaves it untouched and reports the same numbers.  *n_moved = the replicas whose final
+ * dir differs from their input dir (one that left and came back counts 0), *bytes_moved the same weighted by size; *peak_before /
+ * *peak_after = the maximum over all dirs.  per_broker[6b..6b+5] = {peak_before, peak_after, lower_bound, moved, bytes_moved,
+ * rounds} of broker b; a broker without dirs reports zeros and counts as proven; one with dirs and no replica reports its largest
+ * base three times.  lower_bound holds for every placement of the broker's replicas over its dirs: the maximum of
+ * (0) max_r size[r] + min_d base[d] over the broker's replicas (0 with none), (1) ceil((sum of base + sum of size) / n),
+ * (2) max_d base[d].  *status = KAO_STATUS_OPTIMAL_PROVEN iff peak_after == lower_bound on every broker, else
+ * KAO_STATUS_FEASIBLE_BOUND_GAP; the return code is KAO_OK either way.  There is no seed: the result depends on the input alone.
+ * stats (may be NULL): [0] brokers that applied a move, [1] rounds that had a proposal, summed over the brokers, [2] moves applied,
+ * [3] proposals summed, [4] kernel launches, [5] brokers stopped by max_rounds with a proposal left, [6] brokers with peak_after ==
+ * lower_bound, [7] the most rounds any one broker ran.  Checked on the host before any device is used (dir[] stays as it was):
+ * KAO_ERR_INVALID for a null pointer (base and stats excepted), n_brokers outside 1..65534, dir_start[0] != 0 or dir_start
+ * decreasing, n_replicas < 0, dir[r] outside 0..n_dirs-1, sum of base + sum of size >= 2^62; KAO_ERR_UNSUPPORTED for a broker with
+ * more than KAO_LOGDIRS_MAX_DIRS dirs or n_replicas > 4,000,000. */
+#define KAO_LOGDIRS_MAX_DIRS 64   /* dirs of one broker: a wavefront ranks them */
+int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start /* [n_brokers+1] */, const uint64_t *base /* [n_dirs] or NULL */,
+                        int32_t n_replicas, int32_t *dir /* [n_replicas] in / out */, const uint64_t *size /* [n_replicas] */,
+                        uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run,
+                        int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                        uint64_t *per_broker /* [n_brokers*6] */, int32_t *status, int64_t stats[8] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

@@ -1,5 +1,6 @@
 // kao_bytes_code.h -- the monotone 16-bit code of a 64-bit quantity that the wave planner (kao_waves.hip), the traffic-weighted
-// planners (kao_wleaders.hip, kao_wfailover.hip) and the disk-usage balance (kao_disk.hip) put into their priority keys.  Device code only.
+// planners (kao_wleaders.hip, kao_wfailover.hip) and the disk-usage and log-dir balances (kao_disk.hip, kao_logdirs.hip) put into their
+// priority keys.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -14,8 +14,8 @@
 //   kao_capped.cpp   kao_solve_capped: Lagrangian prices over kao_solve / kao_solve_multi, through the C ABI only
 //   kao_pairs.cpp    compound edges of leader-balanced pairs for KAO-CX;  kao_round.cpp  KAO-LP's primal side: the iterate rounded to an assignment
 //   kao_waves.hip    kao_plan_waves(_sized): a reassignment plan split into waves
-//   kao_leaders.hip, kao_leaders_cluster.hip, kao_wleaders.hip, kao_failover.hip, kao_wfailover.hip, kao_disk.hip  the one-shot planners of
-//                    leaders, follower orders and replica moves by disk usage (kernels and entry point in one file each; device code they share: kao_plan_dev.h, the
+//   kao_leaders.hip, kao_leaders_cluster.hip, kao_wleaders.hip, kao_failover.hip, kao_wfailover.hip, kao_disk.hip, kao_logdirs.hip  the one-shot planners of
+//                    leaders, follower orders and replica moves by disk usage, between brokers and between the log dirs of one (kernels and entry point in one file each; device code they share: kao_plan_dev.h, the
 //                    failover scenario passes: kao_failover_dev.h; host code they share: "one-shot planner calls" below)
 // Not part of the C ABI.
 #pragma once

@@ -1,0 +1,357 @@
+// kao_logdirs.hip -- kao_balance_logdirs: replica moves between the log dirs of ONE broker that lower the peak of the bytes a dir
+// stores, every broker of the call at once.  Kernels and the C entry point.
+//
+// Broker b owns the dirs dir_start[b] .. dir_start[b+1]-1 (at most KAO_LOGDIRS_MAX_DIRS), dir d carries base[d] bytes that never move,
+// replica r sits in dir[r] with size[r] bytes, L(d) = base[d] + the sizes of its replicas.  A move takes r to another dir of the same
+// broker: the brokers are independent sub-problems, and each is the descent of section 4k with the pairing of section 4m:
+//   k_ld_count, k_ld_offsets, k_ld_scatter   the replicas bucketed by broker (count, prefix sum + largest bucket, scatter)
+//   k_ld_solve   ONE WORKGROUP PER BROKER, all brokers in one launch: every round, then the bound, then the row of per_broker
+// A ROUND uses the loads as they stand at its start and has four parts with a barrier after each:
+//   RANK     the lanes below n rank the broker's n dirs by L descending (ties: index ascending) by all pairs out of LDS;
+//   PROPOSE  every replica with size > 0 (n >= 2) on a of rank q takes c1 = order[n-1-q] when q < n-1-q and proposes a -> c1 iff
+//            L(c1) + size + min_gain < L(a); otherwise, when q >= 1, c2 = order[n-1] under the same test.  It bids
+//            key = q << 48 | (0xFFFF - code(size)) << 32 | r into the minkey word of a and of its destination (LDS atomicMin, skipped
+//            when the word is already lower).  The barrier is __syncthreads_or("I proposed"): the end test;
+//   DECIDE   a proposal wins iff both words hold its key; only minkey words are read, only the replica's own flag is written;
+//   APPLY    winners store L(a) -= size, L(c) += size and their dir (no two winners share a dir), every proposer clears its two words.
+// No lane reads a load in the part in which another lane can write it: the snapshot rule of section 4k.  LDS per workgroup: load and
+// minkey u64[64], rank and order u8[64], a few words of reduction: under 2 KiB, static, so many brokers share a compute unit.  The
+// round state of a replica (key, destination | won) sits in HBM / L2 at the replica's place in its bucket and is read back by the lane
+// that wrote it; its dir is dir[r].
+// The BOUND of a broker, valid for every placement of its replicas, integers only: the maximum of (0) the largest size + the smallest
+// base, (1) ceil(sum of L / n), (2) the largest base.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "kao_host.h"
+#include "kao_plan_dev.h"   // descent_gains, descent_bid, wave_bytes_code
+
+namespace {
+
+constexpr int kLdThreads = 256;          // the passes over replicas
+constexpr int kLdSoloSmall = 256;        // lanes of a broker's workgroup while the largest bucket holds at most kLdSmallBucket replicas
+constexpr int kLdSoloLarge = 1024;       // (the kFoSoloSmall / kFoSoloLarge rule of kao_failover_dev.h)
+constexpr int kLdSmallBucket = 1024;
+constexpr int kLdMaxDirs = KAO_LOGDIRS_MAX_DIRS;
+constexpr int kLdMaxReplicas = 4000000;
+constexpr int kLdHardRounds = 1 << 26;   // no descent gets here; a guard against an endless loop
+constexpr u64 kLdNoKey = ~0ull;
+constexpr int kLdWon = 0x80;             // flag in dst[]: this round's proposal won (a destination is below 64)
+enum { LC_PEAK0 = 0, LC_PEAK1, LC_NMOVED, LC_BYTES, LC_BROKERS, LC_ROUNDS, LC_MOVES, LC_PROPS, LC_MORE, LC_PROVEN, LC_MAXROUNDS, LC_ERR, LC_MAXN, LC_N = 16 };
+enum { LS_PEAK0 = 0, LS_PEAK1, LS_MAXSIZE, LS_MINBASE, LS_MAXBASE, LS_TOTAL, LS_NMOVED, LS_BYTES, LS_MOVES, LS_PROPS, LS_N = 16 };
+static_assert(kLdMaxDirs == 64, "a wavefront ranks the dirs of a broker; a destination and kLdWon share a byte");
+
+struct LdNet {   // one call; every pointer is device memory
+    int max_rounds;
+    u64 min_gain;
+    const int32_t *dir_start;   // [B + 1]
+    const u64 *base;            // [n_dirs]
+    const u64 *size;            // [R]
+    int32_t *dir;               // [R] rewritten by the winners
+    const int32_t *dir0;        // [R] the input
+    const int32_t *cnt, *start, *list;   // [B], [B], [R]: the brokers' buckets of replica indices
+    u64 *key;                   // [R] by place in the bucket: key of this round's proposal, kLdNoKey = none
+    uint8_t *dst;               // [R] by place in the bucket: its destination (index inside the broker) | kLdWon
+    u64 *per_broker;            // [6B]
+    u64 *ctl;                   // [LC_N]
+};
+
+// ---- the buckets --------------------------------------------------------------------------------------------------------------------
+__global__ void k_ld_count(int R, const int32_t *__restrict__ dir, const int32_t *__restrict__ broker_of_dir, int32_t *__restrict__ cnt) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < R) atomicAdd(&cnt[broker_of_dir[dir[r]]], 1);
+}
+
+// start[b] = sum of cnt[0..b), fill[b] = 0; *max_n = the largest cnt.  One workgroup.  (k_fo_offsets of kao_failover_dev.h is this pass;
+// that header carries the scenario kernels, their host driver and the failover control block whose FS_MAXN word the kernel writes,
+// all in an unnamed namespace: including it here would compile the failover passes into this file, and moving the kernel out would
+// change the two files that use it.  So the twenty lines are written once more, with the maximum going to a word of the caller's.)
+__global__ __launch_bounds__(1024) void k_ld_offsets(int B, const int32_t *__restrict__ cnt, int32_t *__restrict__ start, int32_t *__restrict__ fill,
+                                                      u64 *__restrict__ max_n) {
+    __shared__ int32_t part[1024];
+    __shared__ int32_t mx;
+    const int tid = threadIdx.x, NT = blockDim.x, per = (B + NT - 1) / NT, lo = min(tid * per, B), hi = min(lo + per, B);
+    if (tid == 0) mx = 0;
+    __syncthreads();
+    int s = 0, m = 0;
+    for (int b = lo; b < hi; ++b) { s += cnt[b]; m = max(m, cnt[b]); }
+    part[tid] = s;
+    if (m) atomicMax(&mx, m);
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int i = 0; i < NT; ++i) { const int v = part[i]; part[i] = acc; acc += v; }
+        *max_n = (u64)mx;
+    }
+    __syncthreads();
+    s = part[tid];
+    for (int b = lo; b < hi; ++b) { start[b] = s; fill[b] = 0; s += cnt[b]; }
+}
+
+// the order inside a bucket does not reach the result: the keys carry r
+__global__ void k_ld_scatter(int R, const int32_t *__restrict__ dir, const int32_t *__restrict__ broker_of_dir, const int32_t *__restrict__ start,
+                             int32_t *__restrict__ fill, int32_t *__restrict__ list) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int b = broker_of_dir[dir[r]];
+    list[start[b] + atomicAdd(&fill[b], 1)] = r;
+}
+
+// ---- one broker ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
+    __shared__ u64 load[kLdMaxDirs], mk[kLdMaxDirs], sh[LS_N];
+    __shared__ uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+    const int ds = n.dir_start[b], nd = n.dir_start[b + 1] - ds, nr = n.cnt[b], at = n.start[b];
+    u64 *o = n.per_broker + 6 * (size_t)b;
+    if (nd == 0) {   // no dir, so no replica: zeros, and nothing to prove
+        if (tid == 0) {
+            for (int i = 0; i < 6; ++i) o[i] = 0;
+            atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        }
+        return;
+    }
+    const int32_t *list = n.list + at;
+    u64 *key = n.key + at;
+    uint8_t *dst = n.dst + at;
+    if (tid < LS_N) sh[tid] = tid == LS_MINBASE ? kLdNoKey : 0;
+    if (tid < nd) { load[tid] = n.base[ds + tid]; mk[tid] = kLdNoKey; }
+    __syncthreads();
+    {   // the loads of the input, the largest size
+        u64 mx = 0;
+        for (int q = tid; q < nr; q += NT) {
+            const int r = list[q];
+            const u64 w = n.size[r];
+            if (w) atomicAdd(&load[n.dir[r] - ds], w);
+            mx = max(mx, w);
+        }
+        if (mx) atomicMax(&sh[LS_MAXSIZE], mx);
+        if (tid < nd) {
+            const u64 x = n.base[ds + tid];
+            atomicMin(&sh[LS_MINBASE], x);
+            if (x) atomicMax(&sh[LS_MAXBASE], x);
+        }
+    }
+    __syncthreads();
+    if (tid < nd) {
+        const u64 x = load[tid];
+        if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
+    }
+    // ---- the rounds ----
+    u64 props = 0, moves = 0;
+    int rounds = 0, more = 0;
+    for (;;) {
+        if (tid < nd) {   // RANK
+            const u64 mine = load[tid];
+            int q = 0;
+            for (int j = 0; j < nd; ++j) {
+                const u64 x = load[j];
+                q += (x > mine || (x == mine && j < tid)) ? 1 : 0;
+            }
+            rank[tid] = (uint8_t)q;   // ranks are a permutation: q < nd
+            order[q] = (uint8_t)tid;
+        }
+        __syncthreads();
+        int mine = 0;
+        for (int q = tid; q < nr; q += NT) {   // PROPOSE
+            const int r = list[q];
+            const u64 w = n.size[r];
+            u64 k = kLdNoKey;
+            if (w && nd >= 2) {
+                const int a = n.dir[r] - ds, ra = rank[a];
+                const u64 la = load[a];
+                int c = -1;
+                if (ra < nd - 1 - ra) {
+                    const int c1 = order[nd - 1 - ra];
+                    if (descent_gains(la, load[c1], w, n.min_gain)) c = c1;
+                }
+                if (c < 0 && ra >= 1) {
+                    const int c2 = order[nd - 1];   // (a itself when a is the lightest: it does not pass)
+                    if (descent_gains(la, load[c2], w, n.min_gain)) c = c2;
+                }
+                if (c >= 0) {
+                    k = (u64)(uint32_t)ra << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)r;
+                    dst[q] = (uint8_t)c;
+                    descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[a], k);
+                    descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[c], k);
+                    ++mine;
+                }
+            }
+            key[q] = k;   // key[q], dst[q] and dir[r] are read back by this lane alone
+        }
+        if (!__syncthreads_or(mine)) break;
+        if ((n.max_rounds > 0 && rounds >= n.max_rounds) || rounds >= kLdHardRounds) { more = 1; break; }
+        ++rounds;
+        props += (u64)mine;
+        for (int q = tid; q < nr; q += NT) {   // DECIDE
+            const u64 k = key[q];
+            if (k == kLdNoKey) continue;
+            const int c = dst[q];
+            if (mk[n.dir[list[q]] - ds] == k && mk[c] == k) dst[q] = (uint8_t)(c | kLdWon);
+        }
+        __syncthreads();
+        for (int q = tid; q < nr; q += NT) {   // APPLY
+            if (key[q] == kLdNoKey) continue;
+            const int r = list[q], s = dst[q], c = s & (kLdWon - 1), a = n.dir[r] - ds;
+            if (s & kLdWon) {   // no other winner touches a or c
+                const u64 w = n.size[r];
+                load[a] -= w;
+                load[c] += w;
+                n.dir[r] = ds + c;
+                ++moves;
+            }
+            mk[a] = kLdNoKey;
+            mk[c] = kLdNoKey;
+        }
+        __syncthreads();
+    }
+    // ---- the result ----
+    if (tid < nd) {
+        const u64 x = load[tid];
+        if (x) atomicMax(&sh[LS_PEAK1], x);
+    }
+    {
+        u64 moved = 0, bytes = 0;
+        for (int q = tid; q < nr; q += NT) {
+            const int r = list[q];
+            if (n.dir[r] != n.dir0[r]) { ++moved; bytes += n.size[r]; }
+        }
+        if (moved) { atomicAdd(&sh[LS_NMOVED], moved); atomicAdd(&sh[LS_BYTES], bytes); }
+        if (moves) atomicAdd(&sh[LS_MOVES], moves);
+        if (props) atomicAdd(&sh[LS_PROPS], props);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const u64 t0 = nr ? sh[LS_MAXSIZE] + sh[LS_MINBASE] : 0, t1 = (sh[LS_TOTAL] + (u64)nd - 1) / (u64)nd;
+        const u64 lb = max(max(t0, t1), sh[LS_MAXBASE]);
+        o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = sh[LS_NMOVED]; o[4] = sh[LS_BYTES]; o[5] = (u64)rounds;
+        atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
+        atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
+        if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        if (rounds) {
+            atomicAdd(&n.ctl[LC_BROKERS], 1ull);   // every round with a proposal applies a move
+            atomicAdd(&n.ctl[LC_ROUNDS], (u64)rounds);
+            atomicAdd(&n.ctl[LC_MOVES], sh[LS_MOVES]);
+            atomicAdd(&n.ctl[LC_PROPS], sh[LS_PROPS]);
+            atomicMax(&n.ctl[LC_MAXROUNDS], (u64)rounds);
+            atomicAdd(&n.ctl[LC_NMOVED], sh[LS_NMOVED]);
+            atomicAdd(&n.ctl[LC_BYTES], sh[LS_BYTES]);
+        }
+        if (more) atomicAdd(&n.ctl[LC_MORE], 1ull);
+        if (rounds >= kLdHardRounds) atomicAdd(&n.ctl[LC_ERR], 1ull);
+    }
+}
+
+int validate_logdirs(const std::string &fn, int32_t B, const int32_t *dir_start, const uint64_t *base, int32_t R, const int32_t *dir, const uint64_t *size,
+                     const void *const *outs, int n_outs) {
+    bool null = !dir_start || !dir || !size;
+    for (int i = 0; i < n_outs; ++i) null |= !outs[i];
+    if (null) return fail(KAO_ERR_INVALID, fn + "null pointer");
+    if (B < 1 || B > 65534) return fail(KAO_ERR_INVALID, fn + "n_brokers must be 1..65534");
+    if (dir_start[0] != 0) return fail(KAO_ERR_INVALID, fn + "dir_start[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (dir_start[b + 1] < dir_start[b]) return fail(KAO_ERR_INVALID, fn + "dir_start decreases at broker " + std::to_string(b));
+    if (R < 0) return fail(KAO_ERR_INVALID, fn + "n_replicas must be >= 0");
+    for (int b = 0; b < B; ++b)
+        if (dir_start[b + 1] - dir_start[b] > kLdMaxDirs)
+            return fail(KAO_ERR_UNSUPPORTED, fn + "broker " + std::to_string(b) + " has more than " + std::to_string(kLdMaxDirs) + " dirs (a wavefront ranks the dirs of a broker)");
+    if (R > kLdMaxReplicas) return fail(KAO_ERR_UNSUPPORTED, fn + "more than 4,000,000 replicas");
+    const int32_t D = dir_start[B];
+    for (int64_t r = 0; r < R; ++r)
+        if (dir[r] < 0 || dir[r] >= D) return fail(KAO_ERR_INVALID, fn + "dir[" + std::to_string(r) + "] is outside 0..n_dirs-1");
+    uint64_t total = 0;   // below 2^62: every load of the kernel stays below 2^63
+    const uint64_t lim = uint64_t(1) << 62;
+    for (int64_t d = 0; base && d < D; ++d)
+        if (__builtin_add_overflow(total, base[d], &total) || total >= lim) return fail(KAO_ERR_INVALID, fn + "base and size sum to 2^62 or more");
+    for (int64_t r = 0; r < R; ++r)
+        if (__builtin_add_overflow(total, size[r], &total) || total >= lim) return fail(KAO_ERR_INVALID, fn + "base and size sum to 2^62 or more");
+    return KAO_OK;
+}
+
+}  // namespace
+
+extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, int32_t n_replicas, int32_t *dir, const uint64_t *size,
+                                   uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before,
+                                   uint64_t *peak_after, uint64_t *per_broker, int32_t *status, int64_t stats[8]) {
+    const std::string fn = "kao_balance_logdirs: ";
+    const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, per_broker, status};
+    int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 6);
+    if (rc) return rc;
+    if ((rc = require_init())) return rc;
+    const int B = n_brokers, R = n_replicas, D = dir_start[B];
+    std::vector<int32_t> bod((size_t)std::max(D, 1), 0);   // broker_of_dir
+    for (int b = 0; b < B; ++b)
+        for (int d = dir_start[b]; d < dir_start[b + 1]; ++d) bod[(size_t)d] = b;
+
+    // one arena: ctl u64[LC_N] | cnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] | bod i32[D] |
+    //            per_broker u64[6B] | key, size u64[R] | dir, dir0, list i32[R] | dst u8[R]
+    Carve cv;
+    const size_t o_ctl = cv.take<u64>(LC_N), o_cnt = cv.take<int32_t>(B), o_base = cv.take<u64>(D), zeroed = cv.end(), o_start = cv.take<int32_t>(B),
+                 o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_bod = cv.take<int32_t>(D), o_pb = cv.take<u64>(6 * (size_t)B),
+                 o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R), o_list = cv.take<int32_t>(R),
+                 o_dst = cv.take<uint8_t>(R);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
+    hipStream_t st = m.stream;
+    int32_t *d_cnt = m.at<int32_t>(o_cnt), *d_start = m.at<int32_t>(o_start), *d_fill = m.at<int32_t>(o_fill), *d_ds = m.at<int32_t>(o_ds),
+            *d_bod = m.at<int32_t>(o_bod), *d_dir = m.at<int32_t>(o_dir), *d_dir0 = m.at<int32_t>(o_dir0), *d_list = m.at<int32_t>(o_list);
+    u64 *d_ctl = m.at<u64>(o_ctl), *d_base = m.at<u64>(o_base), *d_size = m.at<u64>(o_size), *d_pb = m.at<u64>(o_pb);
+
+    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
+    HIP_TRY(hipMemcpyAsync(d_ds, dir_start, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (D) {
+        HIP_TRY(hipMemcpyAsync(d_bod, bod.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (base) HIP_TRY(hipMemcpyAsync(d_base, base, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    }
+    if (R) {
+        HIP_TRY(hipMemcpyAsync(d_dir0, dir, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_dir, d_dir0, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)R * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    }
+    int launches = 0;
+    const unsigned rblocks = grid_for(R, kLdThreads);
+    if (R) {
+        k_ld_count<<<rblocks, kLdThreads, 0, st>>>(R, d_dir0, d_bod, d_cnt);
+        ++launches;
+    }
+    k_ld_offsets<<<1, 1024, 0, st>>>(B, d_cnt, d_start, d_fill, d_ctl + LC_MAXN);
+    ++launches;
+    if (R) {
+        k_ld_scatter<<<rblocks, kLdThreads, 0, st>>>(R, d_dir0, d_bod, d_start, d_fill, d_list);
+        ++launches;
+    }
+    HIP_TRY(hipGetLastError());
+    u64 max_n = 0;
+    HIP_TRY(hipMemcpyAsync(&max_n, d_ctl + LC_MAXN, sizeof max_n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int threads = max_n <= (u64)kLdSmallBucket ? kLdSoloSmall : kLdSoloLarge;
+
+    LdNet n;
+    n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
+    n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
+    k_ld_solve<<<(unsigned)B, threads, 0, st>>>(n);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    u64 ctl[LC_N];
+    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
+    if (!dry_run && ctl[LC_NMOVED]) {
+        HIP_TRY(hipMemcpyAsync(dir, d_dir, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_moved = (int32_t)ctl[LC_NMOVED];
+    *bytes_moved = ctl[LC_BYTES];
+    *peak_before = ctl[LC_PEAK0];
+    *peak_after = ctl[LC_PEAK1];
+    *status = ctl[LC_PROVEN] == (u64)B ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    if (stats) {
+        stats[0] = (int64_t)ctl[LC_BROKERS]; stats[1] = (int64_t)ctl[LC_ROUNDS]; stats[2] = (int64_t)ctl[LC_MOVES]; stats[3] = (int64_t)ctl[LC_PROPS];
+        stats[4] = launches; stats[5] = (int64_t)ctl[LC_MORE]; stats[6] = (int64_t)ctl[LC_PROVEN]; stats[7] = (int64_t)ctl[LC_MAXROUNDS];
+    }
+    return KAO_OK;
+}

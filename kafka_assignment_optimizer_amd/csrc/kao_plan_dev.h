@@ -1,6 +1,6 @@
 // kao_plan_dev.h -- device code the one-shot planners share: the 64-bit keys of successive shortest paths (kao_leaders.hip,
 // kao_leaders_cluster.hip; DESIGN.md sections 4h, 4j), the wavefront count, the leader swap, and the pieces of the weighted descent
-// (kao_wleaders.hip, kao_wfailover.hip, kao_disk.hip; sections 4k, 4l, 4m).  Everything sits in an unnamed namespace and is inlined into its callers.
+// (kao_wleaders.hip, kao_wfailover.hip, kao_disk.hip, kao_logdirs.hip; sections 4k, 4l, 4m, 4o).  Everything sits in an unnamed namespace and is inlined into its callers.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,310 @@
+"""Log-dir balance: the replica moves between the log dirs of one broker that lower the peak of the bytes a dir stores
+(kao_balance_logdirs).
+
+    python -m kafka_assignment_optimizer_amd.logdirs --current current.json --log-dirs log-dirs.txt [--broker-list 0,1,2] \
+        [--min-gain 1G] [--max-rounds N] [--dry-run] --out plan.json --report
+
+Every other planner treats a broker as one disk.  A JBOD broker has several log dirs, Kafka places a new replica in the dir with the
+fewest partitions, not the fewest bytes, and the broker dies on its fullest dir.  This one reads `kafka-log-dirs --describe` output
+WITH its directories and moves replicas between the dirs of their own broker (an intra-broker move: disk to disk, no network) until
+no single move closes a gap of more than --min-gain bytes.  The brokers are independent; each gets a deterministic descent with a
+lower bound beside it: where peak_after == lower_bound on every broker the peaks are proven optimal.  The plan lists the partitions
+with a moved replica, `replicas` as they are and a `log_dirs` list beside them ("any" for a slot that stays), which is what
+kafka-reassign-partitions --execute takes.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import sys
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _ffi
+from .solver import STATUS_NAMES, _check
+
+STAT_KEYS = ("brokers_moved", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven", "max_rounds_of_a_broker")
+PER_BROKER_KEYS = ("peak_before", "peak_after", "lower_bound", "moved", "bytes_moved", "rounds")
+
+
+@dataclass
+class LogDir:
+    error: Optional[str]                                                        # non-null: the dir is offline and left out
+    entries: List[Tuple[str, int, int, bool]] = field(default_factory=list)    # (topic, partition, size, isFuture)
+
+
+@dataclass
+class LogDirsResult:
+    dir: np.ndarray          # [R] int32: the dir of every replica after the moves (the input with dry_run)
+    n_moved: int             # replicas whose final dir differs from their input dir
+    bytes_moved: int         # ... weighted by their sizes
+    peak_before: int         # max_d L(d) of the input, over all dirs
+    peak_after: int
+    per_broker: np.ndarray   # [B, 6] uint64, see PER_BROKER_KEYS
+    status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound on every broker) | "FEASIBLE_BOUND_GAP"
+    stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h
+
+
+def parse_log_dirs(doc_or_text) -> Dict[int, Dict[str, LogDir]]:
+    """{broker id: {dir name: LogDir}} from the output of `kafka-log-dirs --describe` (text: the status lines before the JSON line are
+    skipped; or the parsed JSON).  What waves.parse_sizes folds into one number per partition stays apart here: the directory, its
+    error, the future replicas.  Partition names split at their last '-'; sizes are integers 0..2^53."""
+    from .waves import _size_value
+    doc = doc_or_text
+    if isinstance(doc_or_text, (str, bytes)):
+        text = doc_or_text.decode() if isinstance(doc_or_text, bytes) else doc_or_text
+        try:
+            doc = json.loads(text)
+        except ValueError:
+            doc = None
+            for line in text.splitlines():
+                if line.lstrip().startswith("{"):
+                    doc = json.loads(line)
+                    break
+            if doc is None:
+                raise ValueError("log-dirs: no JSON document found") from None
+    if not isinstance(doc, dict) or not isinstance(doc.get("brokers"), list):
+        raise ValueError('log-dirs: expected a "brokers" (kafka-log-dirs) document')
+    out: Dict[int, Dict[str, LogDir]] = {}
+    for br in doc["brokers"]:
+        if isinstance(br.get("broker"), bool) or not isinstance(br.get("broker"), int):
+            raise ValueError("log-dirs: broker entry without an integer id")
+        b = int(br["broker"])
+        if b in out:
+            raise ValueError(f"log-dirs: broker {b} listed twice")
+        dirs = out[b] = {}
+        for ld in br.get("logDirs") or []:
+            name = ld.get("logDir")
+            if not isinstance(name, str):
+                raise ValueError(f"log-dirs: broker {b}: log dir without a name")
+            if name in dirs:
+                raise ValueError(f"log-dirs: broker {b}: log dir {name} listed twice")
+            err = ld.get("error")
+            d = dirs[name] = LogDir(error=None if err is None else str(err))
+            for e in ld.get("partitions") or []:
+                pname = e.get("partition")
+                if not isinstance(pname, str):
+                    raise ValueError("log-dirs: log-dir entry without a partition name")
+                topic, dash, idx = pname.rpartition("-")
+                if not dash or not topic or not idx.isdigit() or len(idx) > 9:
+                    raise ValueError(f"log-dirs: partition name '{pname}' is not <topic>-<partition>")
+                d.entries.append((topic, int(idx), _size_value(e.get("size"), "log-dirs: " + pname), e.get("isFuture") is True))
+    return out
+
+
+def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> LogDirsResult:
+    """kao_balance_logdirs on arrays: broker b owns the dirs dir_start[b] .. dir_start[b+1]-1, replica r sits in dir[r] with size[r]
+    bytes, dir d carries base[d] bytes that never move."""
+    ds = np.ascontiguousarray(np.asarray(dir_start).reshape(-1), dtype=np.int32)
+    if ds.shape[0] < 2:
+        raise ValueError("dir_start must hold n_brokers + 1 values, n_brokers >= 1")
+    B = ds.shape[0] - 1
+    d = np.array(np.asarray(dir).reshape(-1), dtype=np.int32, order="C")
+    R = d.shape[0]
+    sz = np.asarray(size).reshape(-1)
+    if sz.shape != (R,):
+        raise ValueError(f"size must hold one value per replica ({R}), got {sz.shape[0]}")
+    if R and (sz.dtype.kind not in "ui" or (sz.dtype.kind == "i" and (sz < 0).any())):
+        raise ValueError("sizes must be integers >= 0")
+    if isinstance(min_gain, bool) or not 0 <= int(min_gain) < 1 << 64:
+        raise ValueError("min_gain must be 0..2^64-1")
+    sbuf = np.ascontiguousarray(sz, dtype=np.uint64) if R else np.zeros(1, dtype=np.uint64)
+    dbuf = d if R else np.zeros(1, dtype=np.int32)
+    bbuf = None
+    if base is not None:
+        bs = np.asarray(base).reshape(-1)
+        if bs.shape != (max(int(ds[-1]), 0),):
+            raise ValueError(f"base must hold one value per dir ({int(ds[-1])}), got {bs.shape[0]}")
+        if bs.size and (bs.dtype.kind not in "ui" or (bs.dtype.kind == "i" and (bs < 0).any())):
+            raise ValueError("bases must be integers >= 0")
+        bbuf = np.ascontiguousarray(bs, dtype=np.uint64) if bs.size else np.zeros(1, dtype=np.uint64)
+    stats = np.zeros(8, dtype=np.int64)
+    per = np.zeros((B, 6), dtype=np.uint64)
+    n, status = C.c_int32(0), C.c_int32(0)
+    moved, before, after = (C.c_uint64(0) for _ in range(3))
+    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    _check(_ffi.load().kao_balance_logdirs(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, dbuf.ctypes.data_as(i32p),
+                                           sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
+                                           C.byref(before), C.byref(after), per.ctypes.data_as(u64p), C.byref(status),
+                                           stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_logdirs")
+    return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
+                         per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
+
+
+@dataclass
+class LogDirsInput:
+    """The documents as the arrays of the call (the mapping is that of cli/kao-logdirs, so both write the same bytes)."""
+    broker_ids: List[int]                 # dense broker index -> broker id
+    dir_names: List[List[str]]            # per broker: its usable dirs, byte-wise ascending
+    skipped: List[int]                    # per broker: dirs left out for their error
+    dir_start: np.ndarray                 # [B + 1] int32
+    base: np.ndarray                      # [n_dirs] uint64
+    dir: np.ndarray                       # [R] int32
+    size: np.ndarray                      # [R] uint64
+    slots: List[Tuple[int, int]]          # per replica: (index into keys, slot of the row)
+    keys: List[Tuple[str, int]]           # (topic, partition) ascending
+    rows: List[List[int]]                 # per key: the replicas of --current as broker ids
+
+
+def parse_input(current_doc: dict, log_dirs, broker_list: Optional[Sequence[int]] = None) -> LogDirsInput:
+    """Brokers: those of broker_list in that order (default: every broker of the log-dirs document, ascending id); a broker outside
+    the list is left alone.  Dirs: a broker's usable dirs (error null) byte-wise ascending by name.  Replicas: the partitions of the
+    current document by (topic, partition), the slots of a row in order; a slot is a movable replica iff its broker is in the list
+    and has a non-future entry for the partition in a usable dir, whose size it takes.  Every other entry of a usable dir (future
+    replicas, partitions the current document does not hold, brokers outside the partition's row) adds its size to the dir's base.
+    The same partition non-future twice on one broker is a ValueError."""
+    from .waves import _entries
+    table = log_dirs if isinstance(log_dirs, dict) and "brokers" not in log_dirs else parse_log_dirs(log_dirs)   # a parse_log_dirs table as it is
+    ids = sorted(table) if broker_list is None else [int(b) for b in broker_list]
+    if not ids:
+        raise ValueError("empty broker list")
+    if len(set(ids)) != len(ids):
+        raise ValueError("duplicate id in broker list")
+    by_key = _entries(current_doc, "current")
+    keys = sorted(by_key, key=lambda k: (k[0].encode(), k[1]))
+    names, skipped, dir_start = [], [], [0]
+    where: List[Dict[Tuple[str, int], Tuple[int, int]]] = []   # per broker: partition -> (global dir, size) of its non-future entry
+    for b in ids:
+        dirs = table.get(b, {})
+        usable = sorted((n for n, d in dirs.items() if d.error is None), key=lambda n: n.encode())
+        names.append(usable)
+        skipped.append(len(dirs) - len(usable))
+        at: Dict[Tuple[str, int], Tuple[int, int]] = {}
+        for i, n in enumerate(usable):
+            for topic, part, sz, fut in dirs[n].entries:
+                if fut:
+                    continue
+                if (topic, part) in at:
+                    raise ValueError(f"log-dirs: broker {b} holds partition {topic}-{part} twice")
+                at[(topic, part)] = (dir_start[-1] + i, sz)
+        where.append(at)
+        dir_start.append(dir_start[-1] + len(usable))
+    dense = {b: i for i, b in enumerate(ids)}
+    rdir, rsize, slots, claimed = [], [], [], set()
+    for k, key in enumerate(keys):
+        for j, x in enumerate(by_key[key]):
+            i = dense.get(x)
+            if i is None or key not in where[i]:
+                continue
+            d, sz = where[i][key]
+            rdir.append(d)
+            rsize.append(sz)
+            slots.append((k, j))
+            claimed.add((i, key))
+    base = [0] * dir_start[-1]
+    for i, b in enumerate(ids):
+        for li, n in enumerate(names[i]):
+            for topic, part, sz, fut in table[b][n].entries:
+                if fut or (i, (topic, part)) not in claimed:
+                    base[dir_start[i] + li] += sz
+    return LogDirsInput(broker_ids=ids, dir_names=names, skipped=skipped, dir_start=np.asarray(dir_start, dtype=np.int32),
+                        base=np.asarray(base, dtype=np.uint64).reshape(-1), dir=np.asarray(rdir, dtype=np.int32).reshape(-1),
+                        size=np.asarray(rsize, dtype=np.uint64).reshape(-1), slots=slots, keys=keys, rows=[by_key[k] for k in keys])
+
+
+def _quoted(s: str) -> str:
+    return '"' + s.replace("\\", "\\\\").replace('"', '\\"') + '"'
+
+
+@dataclass
+class LogDirsPlan:
+    result: LogDirsResult
+    input: LogDirsInput
+    entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs) of the partitions with a move
+
+    def document(self) -> dict:
+        """The reassignment document of the partitions with a moved replica (what kafka-reassign-partitions --execute takes)."""
+        return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": r, "log_dirs": d} for t, p, r, d in self.entries]}
+
+    def text(self) -> str:
+        """The document byte for byte as cli/kao-logdirs writes it."""
+        rows = ['    {"topic":%s,"partition":%d,"replicas":[%s],"log_dirs":[%s]}' % (_quoted(t), p, ",".join(str(b) for b in r), ",".join(_quoted(x) for x in d))
+                for t, p, r, d in self.entries]
+        return '{"version":1,"partitions":[' + "".join(("\n" if i == 0 else ",\n") + r for i, r in enumerate(rows)) + "\n]}\n"
+
+    def report_lines(self) -> List[str]:
+        return report_lines(self)
+
+
+def plan_input(li: LogDirsInput, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> LogDirsPlan:
+    """kao_balance_logdirs on a LogDirsInput; the entries are the partitions with a moved replica (none with dry_run)."""
+    res = balance_logdirs_arrays(li.dir_start, li.dir, li.size, li.base, min_gain, max_rounds, dry_run)
+    flat = [n for names in li.dir_names for n in names]
+    lists: Dict[int, List[str]] = {}
+    for r in np.nonzero(res.dir != li.dir)[0]:
+        k, j = li.slots[int(r)]
+        lists.setdefault(k, ["any"] * len(li.rows[k]))[j] = flat[int(res.dir[r])]
+    entries = [(li.keys[k][0], li.keys[k][1], list(li.rows[k]), lists[k]) for k in sorted(lists)]
+    return LogDirsPlan(result=res, input=li, entries=entries)
+
+
+def balance_logdirs(current_doc: dict, log_dirs, *, broker_list: Optional[Sequence[int]] = None, min_gain: int = 0, max_rounds: int = 0,
+                    dry_run: bool = False) -> LogDirsPlan:
+    """kao_balance_logdirs on a reassignment document and the `kafka-log-dirs --describe` output of its cluster (text, parsed JSON, or
+    the table of parse_log_dirs).  plan.document() is the reassignment document with its log_dirs lists."""
+    return plan_input(parse_input(current_doc, log_dirs, broker_list), min_gain, max_rounds, dry_run)
+
+
+def report_lines(plan: LogDirsPlan) -> List[str]:
+    """The --report text, line for line as cli/kao-logdirs prints it: one line per broker, one for the call."""
+    res, li, s = plan.result, plan.input, plan.result.stats
+    per_replicas = np.bincount(np.searchsorted(li.dir_start, li.dir, side="right") - 1, minlength=len(li.broker_ids)) if len(li.dir) else [0] * len(li.broker_ids)
+    out = []
+    for i, b in enumerate(li.broker_ids):
+        p = [int(x) for x in res.per_broker[i]]
+        out.append(f"logdirs: broker={b} dirs={len(li.dir_names[i])} skipped_dirs={li.skipped[i]} replicas={int(per_replicas[i])} peak_before={p[0]} "
+                   f"peak_after={p[1]} lower_bound={p[2]} moved={p[3]} bytes_moved={p[4]} rounds={p[5]}")
+    total = sum(int(x) for x in li.size) + sum(int(x) for x in li.base)
+    out.append(f"logdirs: status={res.status} brokers={len(li.broker_ids)} dirs={int(li.dir_start[-1])} skipped_dirs={sum(li.skipped)} replicas={len(li.dir)} "
+               f"peak_before={res.peak_before} peak_after={res.peak_after} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
+               + " ".join(f"{k}={int(v)}" for k, v in zip(STAT_KEYS, s)))
+    return out
+
+
+def main(argv=None) -> int:
+    """Python twin of cli/kao-logdirs: same flags, same bytes, same exit status (0 ok, 1 error, 2 usage)."""
+    from ._plan_args import count
+    from .waves import parse_bytes
+    ap = argparse.ArgumentParser(prog="kao-logdirs", description="replica moves between the log dirs of a broker that lower the peak bytes per dir")
+    ap.add_argument("--current", required=True, help="reassignment JSON of the cluster as it is")
+    ap.add_argument("--log-dirs", required=True, help="kafka-log-dirs --describe output")
+    ap.add_argument("--broker-list", default=None, help="brokers to balance, CSV (default: every broker of --log-dirs)")
+    ap.add_argument("--min-gain", default=None, help="move only to close a gap of more than N bytes (N, or N with K/M/G/T)")
+    ap.add_argument("--max-rounds", type=count, default=0, help="stop every broker after N rounds")
+    ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--report", action="store_true")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    min_gain = 0
+    try:
+        if a.min_gain is not None:
+            min_gain = parse_bytes(a.min_gain)
+    except ValueError as e:
+        ap.error(str(e))
+    try:
+        with open(a.current) as f:
+            doc = json.load(f)
+        with open(a.log_dirs) as f:
+            text = f.read()
+        ids = None if a.broker_list is None else [int(b) for b in a.broker_list.split(",") if b]
+        li = parse_input(doc, text, ids)   # input errors before the device is touched
+        from .solver import init
+        init(a.device)
+        plan = plan_input(li, min_gain, a.max_rounds, a.dry_run)
+        if a.report:
+            for line in report_lines(plan):
+                print(line, file=sys.stderr)
+        with open(a.out, "w") as f:
+            f.write(plan.text())
+    except Exception as e:  # noqa: BLE001 -- reported, exit status 1
+        print(f"kao-logdirs: {e}", file=sys.stderr)
+        return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
