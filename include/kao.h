@@ -398,6 +398,11 @@ int kao_improve_cycles(const kao_topic *t, uint16_t *assignment, int32_t max_rou
  * may be NULL). */
 int kao_cycle_matrices(const kao_topic *t, const uint16_t *assignment, int32_t layer, int32_t level, int32_t *dist, int32_t *mid,
                        uint32_t *slot);
+/* How a squaring of a graph of n = B + R + 1 nodes (1..2048) is launched, by the host function kao_improve_cycles itself calls (no
+ * device needed): out = (np, slices, kchunk) -- the row stride (n rounded up to 64), 1 = the unsplit kernel k_cx_square, >= 2 =
+ * k_cx_square_part over that many slices of kchunk midpoints (the last may be shorter).  Honours the test hook
+ * KAO_CX_SQUARE_SPLIT (unset or 0: the production rule; 1: never split; N >= 2: N slices requested). */
+int kao_cycle_square_plan(int32_t n, int32_t out[3]);
 /* The seed table table[P * n_cfg * 2] = (total, completing broker) per partition and configuration (oracle/kao_cycle.py
  * gives the numbering); *n_cfg is always set; table may be NULL to query n_cfg only. */
 int kao_cycle_seeds(const kao_topic *t, const uint16_t *assignment, int32_t *table, int32_t *n_cfg);

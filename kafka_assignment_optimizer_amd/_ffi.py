@@ -100,6 +100,7 @@ SIGNATURES = {
     "kao_rccl_loopback_counts": (C.c_int, [_P(C.c_uint64)]),
     "kao_improve_cycles": (C.c_int, [_P(KaoTopic), _P(C.c_uint16), C.c_int32, _P(C.c_int64), _P(C.c_int32)]),
     "kao_cycle_matrices": (C.c_int, [_P(KaoTopic), _P(C.c_uint16), C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_uint32)]),
+    "kao_cycle_square_plan": (C.c_int, [C.c_int32, _P(C.c_int32)]),
     "kao_cycle_seeds": (C.c_int, [_P(KaoTopic), _P(C.c_uint16), _P(C.c_int32), _P(C.c_int32)]),
     "kao_cycle_pair_edges": (C.c_int, [_P(KaoTopic), _P(C.c_uint16), C.c_int32, _P(C.c_int32), _P(C.c_int64)]),
     "kao_plan_waves": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint16), C.c_int32, C.c_uint64,

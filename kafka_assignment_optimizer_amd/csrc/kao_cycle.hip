@@ -9,7 +9,9 @@
 //   k_cx_edges_l : L, generalised leader transfers (five variants of "the partition led by u gets leader v", each priced with
 //                  the F path that compensates its replica effect), built on the closure of F;
 //   k_cx_dist0   : edge keys -> cost matrices, slack node Z (brokers with room inside their band absorb / give a unit);
-//   k_cx_square  : min-plus squaring with the midpoint of every pair, three times: cheapest paths of <= 8 edges;
+//   k_cx_square  : min-plus squaring with the midpoint of every pair, three times: cheapest paths of <= 8 edges; small matrices
+//                  are split over the midpoints (k_cx_square_part + k_cx_square_fin; cx_square_plan chooses, test hook
+//                  KAO_CX_SQUARE_SPLIT: 1 = never split, N >= 2 = N slices);
 //   k_cx_seeds   : for every partition every new row that replaces <= 2 replicas (one by a current replica) with any
 //                  leader, priced as gain - closure of its replica imbalance (F) - of its leader imbalance (S);
 // the host unrolls the best candidates into slot changes (a partition is used once), K-eval scores them exactly, and the
@@ -549,6 +551,20 @@ int cx_ncfg(int rf, int rfc) { return (rf - 1) + rf * rf + (rf * (rf - 1) / 2) *
 // a realisation = the partitions it rewrites (each at most once) and their new rows
 struct CxReal { std::vector<int> used; std::vector<uint16_t> rows; };
 
+// How one squaring of an np x np matrix (np a multiple of 64) runs: ks = 1 is ONE launch of k_cx_square; ks >= 2 is k_cx_square_part
+// with ks slices of kchunk midpoints each (a multiple of 16, the last slice may be shorter) and k_cx_square_fin.  Below 200 output
+// tiles the midpoints are split so that about 512 workgroups run, into 8 slices at most.  Test hook KAO_CX_SQUARE_SPLIT (read at
+// every squaring: the tests switch it inside one process): 1 = never split, N >= 2 = N slices requested, rounded the same way.
+struct CxSquarePlan { int ks, kchunk; };
+CxSquarePlan cx_square_plan(int np) {
+    const int nt = np / 64, tiles = nt * nt;
+    const int64_t forced = env_int("KAO_CX_SQUARE_SPLIT", 0);
+    int ks = forced >= 1 ? (int)std::min<int64_t>(forced, np) : tiles < 200 ? std::min(8, std::max(2, (512 + tiles - 1) / tiles)) : 1;
+    const int kchunk = ((np + ks - 1) / ks + 15) / 16 * 16;
+    ks = (np + kchunk - 1) / kchunk;
+    return {ks, kchunk};
+}
+
 // Device buffers and host images of one topic's KAO-CX state
 struct Cx {
     const kao_topic *t = nullptr;
@@ -628,12 +644,11 @@ struct Cx {
     }
 
     // edges, closures (device); diagonals to the host
-    // one min-plus squaring; small matrices are split over the midpoints so that the launch fills the chip
+    // one min-plus squaring; small matrices are split over the midpoints so that the launch fills the chip (cx_square_plan)
     int square(const int32_t *Din, int32_t *Dout, uint16_t *Mout) {
-        const int nt = q.np / 64, tiles = nt * nt;
-        int ks = tiles < 200 ? std::min(8, std::max(2, (512 + tiles - 1) / tiles)) : 1;
-        const int kchunk = ((q.np + ks - 1) / ks + 15) / 16 * 16;
-        ks = (q.np + kchunk - 1) / kchunk;
+        const int nt = q.np / 64;
+        const CxSquarePlan sp = cx_square_plan(q.np);
+        const int ks = sp.ks, kchunk = sp.kchunk;
         if (ks <= 1) { hipLaunchKernelGGL(k_cx_square, dim3(nt, nt), dim3(256), 0, stream, q.np, Din, Dout, Mout); return KAO_OK; }
         const size_t nn = (size_t)q.np * q.np;
         if (!d_sqkey) CX_TRY(hipMalloc(reinterpret_cast<void **>(&d_sqkey), nn * 4));
@@ -1315,6 +1330,15 @@ int kao_cycle_matrices(const kao_topic *t, const uint16_t *assignment, int32_t l
         CX_TRY(hipMemcpy(E.data(), cx.d_E[layer], nn * 8, hipMemcpyDeviceToHost));
         for (int i = 0; i < q.n; ++i) for (int j = 0; j < q.n; ++j) slot[(size_t)i * q.n + j] = (uint32_t)(E[(size_t)i * q.np + j] & 0xFFFFFFFFu);
     }
+    return KAO_OK;
+}
+
+int kao_cycle_square_plan(int32_t n, int32_t out[3]) {
+    using namespace kao;
+    if (n < 1 || n > 2048 || !out) return api_fail(KAO_ERR_INVALID, "bad arguments");
+    const int np = (n + 63) & ~63;
+    const CxSquarePlan sp = cx_square_plan(np);
+    out[0] = np; out[1] = sp.ks; out[2] = sp.kchunk;
     return KAO_OK;
 }
 

@@ -162,6 +162,15 @@ def cycle_matrices(topic: Topic, assign, layer: int, level: int) -> tuple:
     return dist, mid, slot
 
 
+def cycle_square_plan(n: int) -> tuple:
+    """Parity hook of KAO-CX (host only, no GPU): (np, slices, kchunk) of one squaring of a graph of n = B + R + 1 nodes -- the row
+    stride, 1 = the unsplit kernel or the number of midpoint slices of the split one, and the midpoints per slice.  Honours the
+    test hook KAO_CX_SQUARE_SPLIT like the squarings themselves."""
+    out = (C.c_int32 * 3)()
+    _check(_ffi.load().kao_cycle_square_plan(int(n), out), "kao_cycle_square_plan")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def cycle_seeds(topic: Topic, assign) -> np.ndarray:
     """Parity hook of KAO-CX: the seed table [P, n_cfg, 2] = (total, completing broker)."""
     ct = _CTopics([topic])

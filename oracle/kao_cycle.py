@@ -78,7 +78,9 @@ def _wt_tables(t):
 class Round:
     """All intermediate objects of one round (the parity tests compare them with the device's)."""
 
-    def __init__(self, t, A):
+    def __init__(self, t, A, closures: bool = True):
+        """closures=False stops after the level-0 edges (EF, ES): at 2048 nodes a squaring takes minutes here, and the parity
+        tests of that size compare level 0 and then single rows of every squaring."""
         self.t = t
         self.A = np.asarray(A).astype(np.int64).reshape(t.n_partitions, t.rf)
         self.B, self.P, self.RF, self.R = t.n_brokers, t.n_partitions, t.rf, t.n_racks
@@ -92,7 +94,8 @@ class Round:
         self.l = np.bincount(self.A[:, 0], minlength=self.B)
         self.K = np.bincount(self.rack[self.A.reshape(-1)], minlength=self.R)     # replicas per rack (C6)
         self._edges()
-        self._closures()
+        if closures:
+            self._closures()
 
     # ---- C7 of a row completed by one more broker: which brokers y may complete `base` (README.md:178-180) ----
     def _completions(self, base: List[int]) -> Optional[np.ndarray]:
