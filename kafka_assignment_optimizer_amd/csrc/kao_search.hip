@@ -375,6 +375,70 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 mine = ok && __ballot(clash) == 0ull;
             }
 
+            // The small-cost instantiations take the one-trip form below.  The others keep the form a team needs: with the one-trip form
+            // k_search<0,0,4,1,3,0> and <0,0,4,0,0,0> spilled a vector register to scratch (8 B, docs/notes_r15.md section 1).
+            constexpr bool kOneTrip = !kTeam && kSmall;
+            if constexpr (kOneTrip) {
+                // ---- one wavefront, one restart.  The winning lane writes the partition words.  The counters the move changes -- the two
+                //      brokers' words of C and, for a REPLACE across racks, the two racks' totals in K -- are each owned by one of lanes
+                //      0..3: lane 0 the old broker, lane 1 the new one, lane 2 the old rack, lane 3 the new one.  All read together and
+                //      write together, and lanes 0 / 1 read their broker's band-state word along with its counter and rebuild its rows
+                //      from the counter value they have just formed: ONE dependent LDS round trip where four read-modify-writes behind
+                //      one another (the compiler cannot tell that the addresses differ), a second read of C and one of W took six.
+                //      Old and new broker always differ (a partition's own brokers are no candidates, the two slots of an EXCHANGE or a
+                //      LEADER-SWAP hold different brokers); a REPLACE inside one rack leaves its total alone: lanes 2 / 3 sit out. ----
+                if (lane == win) {
+                    uint32_t *ap = reinterpret_cast<uint32_t *>(&L.A[p]);
+                    if (TY == 0) ap[k] = vw;
+                    else if (TY == 1) { ap[k] = vw; reinterpret_cast<uint32_t *>(&L.A[q])[j] = uw; }
+                    else { ap[0] = vw; ap[k] = uw; }
+                }
+                // Which rows move: a REPLACE of a follower slot moves the replica counts (row C3), a LEADER-SWAP and an EXCHANGE between a
+                // leader and a follower slot the leader counts (row C4), a REPLACE of a leader slot both, an EXCHANGE between two slots of
+                // one kind no count at all.  The kind of the move is wave-uniform: the winner's slot numbers.  Only the row whose count
+                // moved is rebuilt and inserted into the broker's word (the scan's marks have been restored by now and a padding index
+                // is never accepted, so bits 15:12 are zero either way).
+                const int kw = of_win(k);
+                int rows;   // bit 0: the replica row, bit 1: the leader row
+                if (TY == 0) rows = 1 | (kw == 0 ? 2 : 0);
+                else if (TY == 1) rows = (kw == 0 ? 2 : 0) ^ (of_win(j) == 0 ? 2 : 0);
+                else rows = 2;
+                if (rows != 0) {
+                    // (the winner's two words as scalars: a uniform proposal holds the new one in a vector register, the same in every lane)
+                    const uint32_t uws = (uint32_t)of_win((int)uw);
+                    const uint32_t vws = decltype(uni)::value ? (uint32_t)__builtin_amdgcn_readfirstlane((int)vw) : (uint32_t)of_win((int)vw);
+                    const uint32_t xo = uws & 0xFFFFu, xn = vws & 0xFFFFu;
+                    uint32_t xx = xo;   // the broker a lane reads W of (lanes 2 / 3: the old broker's, a value they drop)
+                    asm("v_writelane_b32 %0, %1, 1" : "+v"(xx) : "s"(xn));
+                    uint32_t xi = xx;   // the entry a lane owns: an index of C (lanes 0 / 1) or of K (lanes 2 / 3)
+                    // what the old broker's word loses (the new one's gains): a replica, with the leader when the slot is the leader's; an
+                    // EXCHANGE moves the leader from u to v (k the leader slot) or from v to u
+                    const uint32_t d0 = TY == 0 ? (kw == 0 ? 0x10001u : 1u) : (TY == 1 ? (kw == 0 ? 0x10000u : 0u - 0x10000u) : 0x10000u);
+                    int n_own = 2;
+                    if (TY == 0) {
+                        const uint32_t ro_ = uws >> 16, rn_ = vws >> 16;
+                        asm("v_writelane_b32 %0, %1, 2\n\tv_writelane_b32 %0, %2, 3" : "+v"(xi) : "s"(ro_), "s"(rn_));
+                        n_own = ro_ != rn_ ? 4 : 2;
+                    }
+                    int lane_w = lane;   // (through an empty asm: the masks are compares here, not spilled scalar pairs hoisted out of the loop)
+                    asm volatile("" : "+v"(lane_w));
+                    if (lane_w < n_own) {
+                        uint32_t *cp = (lane_w < 2 ? L.C : reinterpret_cast<uint32_t *>(L.K)) + xi;
+                        const uint32_t c_old = *cp;
+                        const uint32_t w_old = L.W[xx];
+                        const uint32_t dl = lane_w < 2 ? d0 : 1u;
+                        const uint32_t cx = (lane_w & 1) ? c_old + dl : c_old - dl;
+                        *cp = cx;
+                        if (lane_w < 2) {
+                            uint32_t wx;
+                            if (rows == 3) wx = band_row<kBandTabs>((int)(cx & 0xFFFFu), bq_r0, bq_r1) | (band_row<kBandTabs>((int)(cx >> 16), bq_l0, bq_l1) << 6);
+                            else if (rows == 1) wx = (w_old & ~kWRowR) | band_row<kBandTabs>((int)(cx & 0xFFFFu), bq_r0, bq_r1);
+                            else wx = (w_old & ~kWRowL) | (band_row<kBandTabs>((int)(cx >> 16), bq_l0, bq_l1) << 6);
+                            L.W[xx] = (uint16_t)wx;
+                        }
+                    }
+                }
+            } else {
             if (lane == win && mine) {  // the winning lane applies its own proposal
                 uint32_t *ap = reinterpret_cast<uint32_t *>(&L.A[p]);
                 if (TY == 0) {
@@ -429,6 +493,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     }
                 }
             }
+            }   // (!kOneTrip; a team: the form its record exchange orders)
             if (kGlobalA) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the winner's stores before the next loads
             if (kTeam) {
                 if (lane == 0) rec[9] = mine ? 1 : 0;
@@ -748,13 +813,17 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 uint32_t jc = jmp_c;
                 asm volatile("" : "+v"(jc));
                 uint32_t best1 = kKeyNull, best2 = kKeyNull;   // (cost + bias) << 16 | tie << 8 | round, per slot
+                // A round is its loads -- W (one ds_read_i16: sign-extended, bit 15 fills the upper half) and XR of the lane's index, then RT
+                // of that rack -- and its arithmetic (scan_round2).  The rounds of a scan do not depend on each other, but a wavefront
+                // waits for every LDS round trip it has started before it uses one: a trip of two rounds issues its four W / XR reads
+                // together and its two RT reads together, two dependent trips where round after round took four.  Only indices of
+                // rounds the scan scores anyway are read.
+                const short *Ws = reinterpret_cast<const short *>(L.W);
                 // (the keys of one round, by reference: two plain rounds of a trip meet the running minima in one v_min3_u32 per slot)
-                auto scan_round2 = [&](auto with_w, int base, int rd, uint32_t &key1, uint32_t &key2) {
+                auto scan_round2 = [&](auto with_w, int base, int rd, int w, int rt, uint32_t &key1, uint32_t &key2) {
                     const uint32_t st1 = lcg24(rng);
                     uint32_t st2;
                     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(st2) : "v"(st1), "s"(jmp_a), "v"(jc));
-                    const int w = (int)reinterpret_cast<const short *>(L.W)[base + lane];   // one ds_read_i16: sign-extended, bit 15 fills the upper half
-                    const int rt = L.RT[XR[base + lane]];
                     const int inc = wfld(w, kWIncR);
                     if constexpr (kSmall) {
                         // (inc + incL * lead1 | inc + incL * lead2) + RT's word, times lam, plus (K01 | K02): three packed instructions
@@ -804,13 +873,16 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                         if (mr[i2] >= rd) nxt = min(nxt, mr[i2]);
                     uint32_t k1a, k2a, k1b, k2b;
                     for (; rd + 1 < nxt; rd += 2, base += 128) {   // two rounds share the address arithmetic, as in the one-slot scan below
-                        scan_round2(std::false_type{}, base, rd, k1a, k2a);
-                        scan_round2(std::false_type{}, base + 64, rd + 1, k1b, k2b);
+                        const int wa = Ws[base + lane], wb = Ws[base + 64 + lane];
+                        const uint32_t ra = XR[base + lane], rb = XR[base + 64 + lane];
+                        const int rta = L.RT[ra], rtb = L.RT[rb];
+                        scan_round2(std::false_type{}, base, rd, wa, rta, k1a, k2a);
+                        scan_round2(std::false_type{}, base + 64, rd + 1, wb, rtb, k1b, k2b);
                         best1 = min(best1, min(k1a, k1b));
                         best2 = min(best2, min(k2a, k2b));
                     }
-                    if (rd < nxt) { scan_round2(std::false_type{}, base, rd, k1a, k2a); best1 = min(best1, k1a); best2 = min(best2, k2a); ++rd; base += 64; }
-                    if (rd < n_rd) { scan_round2(std::true_type{}, base, rd, k1a, k2a); best1 = min(best1, k1a); best2 = min(best2, k2a); ++rd; base += 64; }
+                    if (rd < nxt) { const int wa = Ws[base + lane]; scan_round2(std::false_type{}, base, rd, wa, L.RT[XR[base + lane]], k1a, k2a); best1 = min(best1, k1a); best2 = min(best2, k2a); ++rd; base += 64; }
+                    if (rd < n_rd) { const int wa = Ws[base + lane]; scan_round2(std::true_type{}, base, rd, wa, L.RT[XR[base + lane]], k1a, k2a); best1 = min(best1, k1a); best2 = min(best2, k2a); ++rd; base += 64; }
                 }
                 asm("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(rng) : "s"(jmp_a), "v"(jc));   // state after both slots' 2 n_rd draws
                 if (holds) L.W[ai & 0xFFFFu] = (uint16_t)w_keep;
@@ -925,10 +997,11 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                 int chunkA = 0;
                 // one round: 64 candidates x = base + lane, `rd` = round within the chunk of 256; `with_w` (compile time): the
                 // round holds a displaced current replica of the partition and is scored with objective weights
-                auto scan_round = [&](auto with_w, int base, int rd) -> uint32_t {
+                // (a round's loads apart from its arithmetic, as in the fused scan: `w` = W of the lane's index, sign-extended so that
+                //  bit 15 fills the upper half, `rt` = RT of its rack; a trip of two rounds issues each kind together)
+                const short *Ws = reinterpret_cast<const short *>(L.W);
+                auto scan_round_on = [&](auto with_w, int base, int rd, int w, int rt) -> uint32_t {
                     const uint32_t st = lcg24(rng);   // tie bits = bits 8..15 of the draw, as make_key_tie(lcg24 >> 8)
-                    const int w = (int)(short)L.W[base + lane];   // sign-extended: bit 15 fills the upper half
-                    const int rt = L.RT[XR[base + lane]];
                     int dsc;
                     if (kPriced) {   // RT entry: violation delta in the low byte, rack price above it
                         const uint32_t prx = PR[base + lane];
@@ -950,6 +1023,19 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                     // a "no candidate" index gets a cost field of 0xFFFF: above every real cost (<= 2 * kDBias - 2) and never accepted
                     return ((uint32_t)dsc << 16) | (st & 0xFF00u) | (uint32_t)rd | ((uint32_t)w & 0xFFFF0000u) | member;
                 };
+                auto scan_round = [&](auto with_w, int base, int rd) -> uint32_t {
+                    const int w = Ws[base + lane];
+                    return scan_round_on(with_w, base, rd, w, L.RT[XR[base + lane]]);
+                };
+                // two plain rounds of one trip, their minimum
+                auto scan_pair = [&](int base, int rd) -> uint32_t {
+                    const int wa = Ws[base + lane], wb = Ws[base + 64 + lane];
+                    const uint32_t ra = XR[base + lane], rb = XR[base + 64 + lane];
+                    const int rta = L.RT[ra], rtb = L.RT[rb];
+                    const uint32_t k0 = scan_round_on(std::false_type{}, base, rd, wa, rta);
+                    const uint32_t k1 = scan_round_on(std::false_type{}, base + 64, rd + 1, wb, rtb);
+                    return min(k0, k1);
+                };
                 auto is_weighted = [&](int rdg) {   // wave-uniform
                     bool wgt = false;
 #pragma unroll
@@ -966,11 +1052,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                             if (is_weighted(rdg) || is_weighted(rdg + 1)) {   // rare: at most NW rounds of a scan carry weights
                                 bestc = min(bestc, is_weighted(rdg) ? scan_round(std::true_type{}, base, rd) : scan_round(std::false_type{}, base, rd));
                                 bestc = min(bestc, is_weighted(rdg + 1) ? scan_round(std::true_type{}, base + 64, rd + 1) : scan_round(std::false_type{}, base + 64, rd + 1));
-                            } else {
-                                const uint32_t k0 = scan_round(std::false_type{}, base, rd);
-                                const uint32_t k1 = scan_round(std::false_type{}, base + 64, rd + 1);
-                                bestc = min(bestc, min(k0, k1));
-                            }
+                            } else bestc = min(bestc, scan_pair(base, rd));
                         }
                     }
                     if (kWide || kTeam) {
@@ -989,11 +1071,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
                                 const int m = mr[i2] - rd0;
                                 if (m >= rd) nxt = min(nxt, m);
                             }
-                            for (; rd + 1 < nxt; rd += 2, base += 128) {   // two rounds share the address arithmetic and one v_min3_u32
-                                const uint32_t k0 = scan_round(std::false_type{}, base, rd);
-                                const uint32_t k1 = scan_round(std::false_type{}, base + 64, rd + 1);
-                                bestc = min(bestc, min(k0, k1));
-                            }
+                            for (; rd + 1 < nxt; rd += 2, base += 128) bestc = min(bestc, scan_pair(base, rd));   // two rounds share the address arithmetic and one v_min3_u32
                             if (rd < nxt) { bestc = min(bestc, scan_round(std::false_type{}, base, rd)); ++rd; base += 64; }
                             if (rd < n_rd) { bestc = min(bestc, scan_round(std::true_type{}, base, rd)); ++rd; base += 64; }
                         }

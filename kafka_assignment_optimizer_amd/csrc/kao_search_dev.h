@@ -387,11 +387,10 @@ template <int NS, bool kPriced, int NW> __device__ __forceinline__ void fill_rac
 // sign-extended).  `h` = hmix + x * kFillTieStep.  fmix32's last xor-shift does not reach bits 31:24 and is left out.
 // kClamp = false: small-cost launches.  A hole's cost is lam_max * dV with 0 <= |dV| <= 4 (replica row, leader row, rack total, the
 // partition's count in the rack) and no objective term (kWithW is false there), inside search_small_cost's 8 lam_max + 4 S w_max.
+// The round's loads come in: `w` = W[x] sign-extended, `r` = XR[x], `rt` = RT[r].  A trip of two rounds issues its W / XR reads together
+// and its RT reads together (fill_hole): the wavefront waits for two dependent LDS round trips per pair, not four.
 template <int NS, bool kPriced, bool kClamp, bool kWithW, int NW>
-__device__ __forceinline__ uint32_t fill_round(const TopicRegs &T, const FillTabs &F, const Part<NW> &c, int x, int rd, uint32_t h, int lam, int S, bool lead) {
-    const int w = (int)reinterpret_cast<const short *>(F.W)[x];
-    const uint32_t r = F.XR[x];
-    const int rt = F.RT[r];
+__device__ __forceinline__ uint32_t fill_round_on(const TopicRegs &T, const FillTabs &F, const Part<NW> &c, int x, int rd, uint32_t h, int lam, int S, bool lead, int w, uint32_t r, int rt) {
     const uint32_t lw = lead ? 2u : 0u, lf = lead ? 1u : 0u;   // widths of the leader field / flag: zero for follower holes
     int cost;
     if (kPriced) {
@@ -406,6 +405,12 @@ __device__ __forceinline__ uint32_t fill_round(const TopicRegs &T, const FillTab
     if (kClamp) cost = min(max(cost, 0), 2 * kDBias - 2);
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u;
     return ((uint32_t)cost << 16) | ((h >> 16) & 0xFF00u) | (uint32_t)rd | ((uint32_t)w & 0xFFFF0000u);
+}
+template <int NS, bool kPriced, bool kClamp, bool kWithW, int NW>
+__device__ __forceinline__ uint32_t fill_round(const TopicRegs &T, const FillTabs &F, const Part<NW> &c, int x, int rd, uint32_t h, int lam, int S, bool lead) {
+    const int w = (int)reinterpret_cast<const short *>(F.W)[x];
+    const uint32_t r = F.XR[x];
+    return fill_round_on<NS, kPriced, kClamp, kWithW>(T, F, c, x, rd, h, lam, S, lead, w, r, F.RT[r]);
 }
 // One hole of partition words `a` (current words `c`): the winner's word x | rack << 16, wave-uniform; kNoneW when no index is a
 // candidate (fewer valid brokers than replicas: the model refuses such a topic).
@@ -431,8 +436,11 @@ __device__ __forceinline__ uint32_t fill_hole(const TopicRegs &T, const FillTabs
         int rd = 0, x = cb + lane;
         if constexpr (!kWeights) {
             for (; rd + 1 < n_rd; rd += 2, x += 128, h += 128u * kFillTieStep) {   // two rounds share the address arithmetic and one v_min3_u32
-                const uint32_t k0 = fill_round<NS, kPriced, kClamp, false>(T, F, c, x, rd, h, lam, S, lead);
-                const uint32_t k1 = fill_round<NS, kPriced, kClamp, false>(T, F, c, x + 64, rd + 1, h + 64u * kFillTieStep, lam, S, lead);
+                const int wa = (int)reinterpret_cast<const short *>(F.W)[x], wb = (int)reinterpret_cast<const short *>(F.W)[x + 64];
+                const uint32_t ra = F.XR[x], rb = F.XR[x + 64];
+                const int rta = F.RT[ra], rtb = F.RT[rb];
+                const uint32_t k0 = fill_round_on<NS, kPriced, kClamp, false>(T, F, c, x, rd, h, lam, S, lead, wa, ra, rta);
+                const uint32_t k1 = fill_round_on<NS, kPriced, kClamp, false>(T, F, c, x + 64, rd + 1, h + 64u * kFillTieStep, lam, S, lead, wb, rb, rtb);
                 bestc = min(bestc, min(k0, k1));
             }
             if (rd < n_rd) { bestc = min(bestc, fill_round<NS, kPriced, kClamp, false>(T, F, c, x, rd, h, lam, S, lead)); h += 64u * kFillTieStep; }
