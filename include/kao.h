@@ -232,6 +232,25 @@ int kao_session_stats(kao_session *s, kao_stats *out);
  * (8 lam_max + 4 obj_scale max|w| <= 16384, unpriced), so the kernel forms costs without the clamp and two at a time.  Same results
  * either way; the environment variable KAO_SEARCH_SMALL=0 (read when the session is created) keeps the count at 0. */
 int kao_session_small_launches(kao_session *s, int64_t *out);
+/* K-search launches so far that ran as ticketed chunks: a launch group with at least twice as many
+ * block-map entries as the device holds workgroups at once runs entries' launches as C shorter pieces inside one grid, handed on through global memory, so
+ * that the work dispatched last -- what the device empties on -- comes in pieces of 1 / C.  Only the LDS-resident, non-team K-search
+ * kernels chunk; topics in global memory, teams and K-init never do.  Same results either way, bit for bit.  The environment variable
+ * KAO_SEARCH_CHUNKS (read when the session is created): unset or 0 = the automatic rule (kao_search_chunk_plan; applied only to launch
+ * groups that run the small-cost RF-3 kernel on topics below 512 replica slots, the kernel it was measured on), 1 = never,
+ * N >= 2 (at most 64) = N uniform chunks on every eligible launch whatever its size.  The schedule is planned once, when the session
+ * is created: a step with another iteration count, and every step after prices were switched on in a session created without them
+ * (kao_session_set_prices, K-bound's export), launches in one piece -- this counter says what ran.  A chunk that gave up waiting for the one before
+ * it (never seen; the wait is bounded so that the kernel always ends) makes the next kao_session_sync / kao_session_best_keys /
+ * kao_session_best / kao_session_stats fail with KAO_ERR_HIP -- and every one after it: the error is never cleared, the session's
+ * restart states are no longer those of a whole launch and the session can only be destroyed. */
+int kao_session_chunked_launches(kao_session *s, int64_t *out);
+/* The schedule of a chunked K-search launch, by the host function the session itself calls (no device needed): `entries` block-map
+ * entries, `resident` workgroups the device holds at once, `iters` iterations per launch, `forced` as KAO_SEARCH_CHUNKS.  Returns the
+ * number of tickets (= entries when the launch stays in one piece; negative: an error) and, when out != NULL and cap >= that number,
+ * out[4 t ..] = (entry, chunk, first iteration, iterations) of ticket t.  The automatic rule chunks only when entries >= 2 x resident
+ * (a tail of one resident round behind at least as many entries in one piece) and every chunk keeps at least 64 iterations. */
+int kao_search_chunk_plan(int32_t entries, int32_t resident, int32_t iters, int32_t forced, int32_t *out, int32_t cap);
 /* K-bound: the optimality certificate beyond the closed-form bound (kao_upper_bound).  lp_solve proves optimality
  * by branch-and-bound over the LP relaxation (README.md:135-136); K-bound instead minimises the Lagrangian dual of
  * the same 0-1 model (README.md:144-185) on the device: rows C3, C4, C6 priced with integer multipliers, rows

@@ -70,6 +70,8 @@ SIGNATURES = {
     "kao_session_device_keys": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "kao_session_stats": (C.c_int, [C.c_void_p, _P(KaoStats)]),
     "kao_session_small_launches": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
+    "kao_session_chunked_launches": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
+    "kao_search_chunk_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P(C.c_int32), C.c_int32]),
     "kao_session_restart_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint16),
                                             _P(C.c_int32)]),
     "kao_session_bound_step": (C.c_int, [C.c_void_p, _P(C.c_int64), C.c_int32]),

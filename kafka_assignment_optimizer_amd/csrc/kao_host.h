@@ -221,6 +221,10 @@ struct kao_session {
         bool cur_in_lds = true;  // K-eval stages the current assignment in LDS (false: reads it from global)
         bool eval_coop = false;  // K-eval: one candidate per workgroup, wavefronts cooperating (few large candidates)
         int smap_off = 0, smap_n = 0, emap_off = 0, emap_n = 0;
+        // K-search as ticketed chunks (plan_chunks): tickets of a launch (0 = one piece per entry, the launch as it always was), chunks
+        // per entry, the group's first record in d_sched, the iterations per launch and the pricing the schedule was made for
+        int chunk_tickets = 0, chunk_n = 0, sched_off = 0, chunk_iters = 0;
+        bool chunk_priced = false;
     };
     std::vector<LaunchGroup> groups;
     int blocks_search = 0, blocks_eval = 0;
@@ -290,6 +294,17 @@ struct kao_session {
     uint64_t search_rf3_launches = 0;   // K-search launches that ran the RF-3 instantiation (kao_stats)
     uint64_t search_small_launches = 0; // of those, the launches that ran its small-cost form (kao_session_small_launches)
     bool small_on = true;               // KAO_SEARCH_SMALL (read when the session is created; 0 = never the small-cost form)
+    // K-search as ticketed chunks (kao.h: kao_session_chunked_launches).  The buffers exist only in sessions with a group that chunks.
+    int chunks_forced = 0;               // KAO_SEARCH_CHUNKS (read when the session is created): 0 automatic, 1 never, N >= 2 forced
+    bool can_chunk = false;              // some launch group runs chunked
+    int4 *d_sched = nullptr;             // the groups' schedules (read-only arena)
+    uint32_t *d_chunk_ctl = nullptr;     // [0] the ticket counter (zero between launches: the holder of the last ticket resets it)
+    uint32_t *d_chunk_progress = nullptr;// one word per block-map entry: launch serial * 256 + chunks done
+    uint32_t *d_chunk_rng = nullptr;     // 64 generator words per restart, handed from chunk to chunk
+    uint32_t chunk_serial = 0;           // serial of the last chunked launch (the progress words carry it: nothing is cleared per launch)
+    uint64_t search_chunked_launches = 0;
+    int32_t *h_chunk_err = nullptr;      // chunking sessions: pinned read-back of the error word behind the drift counter.  Once set it stays
+                                         // set (nothing clears the device word): every later synchronising call of the session fails
 };
 
 namespace kao {

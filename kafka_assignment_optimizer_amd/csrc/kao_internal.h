@@ -85,6 +85,12 @@ struct SearchParams {
     int32_t cur_global;          // 1 = the launch group keeps only the working assignment in LDS (k_search_curg): the current assignment is read from global memory
     int32_t elite;               // 1 = restarts that trail their topic's best feasible objective may re-seed from it (KAO-LS
                                  //     "elite" rule)
+    int32_t chunks;              // > 0: the launch runs as ticketed chunks (SearchPools::chunk_sched; the grid is the number of tickets);
+                                 //     0 = one workgroup per block-map entry, the whole launch in one piece
+    uint32_t serial;             // chunked launches: this launch's serial number, carried by the progress words (value = serial * 256 +
+                                 //     chunks done), so that nothing is cleared between launches.  (The value wraps after 2^24 chunked
+                                 //     launches of a session; a stale word would have to hold exactly the awaited count of a launch 2^24
+                                 //     serials back to be mistaken, and every entry's word is rewritten by every chunked launch.)
 };
 
 struct SearchPools {
@@ -102,7 +108,18 @@ struct SearchPools {
     const uint16_t *int_pool;    // dense -> internal broker index per topic
     const uint16_t *elite_assign;// [sum P*RF] every topic's best feasible assignment so far (dense; k_gather's output), at win_off
     const unsigned long long *elite_key;  // [n_topics] packed key of that assignment as of the previous step (~0 = none)
+    // ---- a launch as ticketed chunks (SearchParams::chunks > 0; LDS-resident, non-team k_search only) ----
+    uint32_t *chunk_ticket;      // [1] next ticket; the holder of the last ticket of a launch puts it back to 0
+    uint32_t *chunk_progress;    // [block-map entries of the group] serial * 256 + chunks of the entry done (kChunkPoison: given up)
+    uint32_t *chunk_rng;         // [n_restarts_total][64] every lane's generator word at the end of a chunk
+    const int4 *chunk_sched;     // [tickets] {entry, chunk | chunks of the entry << 8, first iteration, iterations} (search_chunk_plan)
 };
+constexpr int kChunkMax = 64;             // chunks per block-map entry (the progress word keeps 8 bits for the count)
+constexpr uint32_t kChunkPoison = 255u;   // count field of a progress word whose entry gave up waiting: its later chunks give up at once
+constexpr int kChunkAuto = 4;             // automatic rule: chunks per entry (fewer while a chunk would fall below kChunkMinIters)
+constexpr int kChunkTailPct = 100;        // automatic rule: the entries chunked, the last of the block map, in percent of the resident workgroups
+constexpr int kChunkMinRounds = 2;        // automatic rule: only launch groups of at least this many resident rounds of entries chunk
+constexpr int kChunkMinIters = 64;        // automatic rule: every chunk keeps at least this many iterations
 
 struct EvalPools {
     const TopicDev *topics;
@@ -166,6 +183,18 @@ bool search_small_cost(int lam_min, int lam_max, int obj_scale, int w_abs_max, b
 // ... and looks band rows up in per-topic tables: every topic's replica and leader band must fit one (kao_search.hip)
 bool search_band_tabs(int rep_lo, int rep_hi, int lead_lo, int lead_hi);
 void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team = 0, int rft = 0, bool small = false);
+// the instantiations that can run a launch as ticketed chunks: LDS-resident, no team (topics in global memory, k_search_curg, k_team and
+// k_init keep one piece per launch)
+inline bool search_chunk_eligible(bool global_a, bool cur_global, int team) { return !global_a && !cur_global && team == 0; }
+// workgroups of the instantiation launch_search would pick that one compute unit holds at this LDS size (the occupancy query of the
+// runtime); 0 when the query fails
+int search_resident_blocks(int waves, bool priced, int nw, bool wide, int rft, bool small, size_t lds);
+// The schedule of a chunked launch, a pure function (kao_session.cpp): ticket -> {entry, chunk, first iteration, iterations}, 4 ints
+// per ticket in `out` (may be null: the count alone).  Returns the number of tickets: `entries` when the launch stays in one piece.
+// forced: 0 = the automatic rule (chunk only when the entries reach kChunkMinRounds x `resident` workgroups and every chunk keeps kChunkMinIters
+// iterations; then only a tail of the entries is chunked), 1 = never, n >= 2 = n uniform chunks on every entry whatever the size (fewer
+// when there are fewer iterations than chunks).
+int search_chunk_plan(int entries, int resident, int iters, int forced, int32_t *out);
 bool launch_init(const SearchPools &pools, const SearchParams &prm, int n_blocks, int per_block, bool priced, int nw, int waves, void *stream);   // K-init (topics in global memory); waves = 0: automatic
 void launch_eval(const EvalPools &pools, int n_blocks, int ne, void *stream);
 // copy every topic's winning snapshot (restart id in its packed key) and violation row into contiguous

@@ -14,6 +14,10 @@
 // All but k_init are instantiations of search_body.  Integer-only, wave64, no MFMA.  The scalar CPU restatement is oracle/kao_port.c.
 #include "kao_search_dev.h"
 
+#include <map>
+#include <mutex>
+#include <tuple>
+
 namespace kao {
 
 // kGlobalA = false: the restart's assignment words and the topic's current-assignment words are staged in LDS
@@ -48,9 +52,44 @@ namespace kao {
 //                   (v_pk_mad_i16 / v_pk_add_i16), the penalty's parameters come out of one packed scalar and a broker's band rows out
 //                   of per-topic tables (the host has also shown that every band fits one: search_band_tabs).  Same draws, keys,
 //                   winners, stores and counters as kSmall = false.
-template <bool kGlobalA, bool kPriced, int NW, bool kWide, bool kTeam, bool kCurG = false, int RFT = 0, bool kSmall = false>
-__device__ __forceinline__ void search_body(unsigned char *smem, const SearchPools &pl, const SearchParams &prm) {
+// What one workgroup runs of a launch: everything (whole_launch) or one chunk of a chunked launch (chunk_take, below).  A chunk other than
+// the first is the launch carried on -- the non-initialising prologue without the elite rule, the generator words of the chunk before
+// it, its own range of iterations.
+struct SearchPiece {
+    uint32_t entry;      // index into the block map (the whole launch: blockIdx.x)
+    int32_t init, elite; // SearchParams::init / elite as this piece sees them (a later chunk: 0)
+    uint32_t first, n;   // its iterations: first .. first + n - 1 of the launch's
+    bool later;          // a chunk behind the first: per-lane generator words from SearchPools::chunk_rng, no re-keying
+    uint32_t ticket;     // chunked launches: the workgroup's ticket
+};
+__device__ __forceinline__ void chunk_pass(uint32_t ticket);
+// A kernel argument read where it is used, behind the iteration loop: taken from `pl` / `prm` there it is loaded with the others in
+// front of the loop and stays live across it -- in kernels whose scalar file is full and whose vector file has no register to spare
+// (the k_search kernels take SearchPools, then SearchParams: the kernel-argument segment holds them in that order).
+template <class T> __device__ __forceinline__ T late_kernarg(size_t off) {
+    auto p = (const __attribute__((address_space(4))) unsigned char *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *reinterpret_cast<const __attribute__((address_space(4))) T *>(p + off);
+}
+static_assert(sizeof(SearchPools) % alignof(SearchParams) == 0, "late_kernarg: SearchParams follows SearchPools without padding");
+constexpr size_t kArgPrm = sizeof(SearchPools);
+// a record of the chunk schedule (host-written: through the constant address space, a scalar load)
+__device__ __forceinline__ int4 sched_record(const int4 *sched, uint32_t ticket) {
+    auto p = (const __attribute__((address_space(4))) int *)sched + 4 * (size_t)ticket;
+    return make_int4(p[0], p[1], p[2], p[3]);
+}
+__device__ __forceinline__ SearchPiece whole_launch(const SearchParams &prm) { return SearchPiece{blockIdx.x, prm.init, prm.elite, 0u, prm.iters, false, 0u}; }
+
+// kChunked        : (LDS-resident, no team, not kCurG) the instantiation a chunked launch runs: the workgroup's piece comes from
+//                   chunk_take, not from blockIdx.x and the launch parameters.  Launches in one piece run kChunked = false, whose code
+//                   takes nothing from `pc`.
+template <bool kGlobalA, bool kPriced, int NW, bool kWide, bool kTeam, bool kCurG = false, int RFT = 0, bool kSmall = false, bool kChunked = false>
+__device__ __forceinline__ void search_body(unsigned char *smem, const SearchPools &pl, const SearchParams &prm, const SearchPiece pc) {
+    static_assert(!kChunked || (!kGlobalA && !kTeam && !kCurG), "chunked launches: LDS-resident topics, one wavefront per restart");
     static_assert(!kTeam || kGlobalA, "teams run topics that live in global memory");
+    constexpr bool kCanChunk = kChunked;
+    const uint32_t pc_entry = kChunked ? pc.entry : blockIdx.x;
+    const int32_t pc_init = kChunked ? pc.init : prm.init, pc_elite = kChunked ? pc.elite : prm.elite;
     static_assert(!kCurG || !kGlobalA, "kCurG: the working assignment is in LDS");
     static_assert(RFT == 0 || (RFT == 3 && NW == 4 && !kGlobalA && !kTeam), "RFT = 3: LDS-resident topics of four words per partition");
     static_assert(!kSmall || (RFT == 3 && !kPriced && !kCurG), "kSmall: the unpriced RF-3 instantiation");
@@ -59,7 +98,15 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n_waves = kTeam ? __builtin_amdgcn_readfirstlane((int)(blockDim.x >> 6)) : 1;   // team size W
     const int tid = kTeam ? (int)threadIdx.x : lane, nthr = kTeam ? (int)blockDim.x : 64;   // who strides the O(P) / O(B) passes
-    const int2 bm = pl.block_map[blockIdx.x];
+    // The chunk-capable instantiations read the block map through the constant address space: a scalar load whatever stands in front
+    // of it.  (Left to itself the compiler issues a scalar load only where it can show that nothing in the kernel wrote the location
+    // before; behind the ticket's atomics it cannot.  The map is written by the host alone.  The topic's descriptor is NOT read that
+    // way: its loads then count as invariant, are kept across the iteration loop instead of repeated behind it, and the loop paid
+    // 4 % in restored scalars -- docs/notes_r16.md.)
+    using MapPtr = std::conditional_t<kCanChunk, const __attribute__((address_space(4))) int *, const int *>;
+    int2 bm;
+    if constexpr (kChunked) bm = make_int2(((MapPtr)pl.block_map)[2 * pc_entry], ((MapPtr)pl.block_map)[2 * pc_entry + 1]);
+    else bm = pl.block_map[pc_entry];
     const TopicDev *TD = pl.topics + bm.x;
 
     TopicRegs T = topic_regs<RFT>(TD);
@@ -138,7 +185,10 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     __syncthreads();
 
     const int rho = bm.y + (kTeam ? 0 : wave);
-    if (rho >= TD->n_restarts) return;  // no block-level barrier below this point (a team is one restart: all or none)
+    if (rho >= TD->n_restarts) {  // no block-level barrier below this point (a team is one restart: all or none) ...
+        if constexpr (kCanChunk) chunk_pass(pc.ticket);   // ... but the hand-off's: a wavefront without a restart meets the others there
+        return;
+    }
     const int g = TD->restart_base + rho;
     // restart state in HBM: packed 4 x u16 per partition (LDS path, loaded / stored around the launch) or the
     // working words themselves, 16 B per partition, updated in place (global path)
@@ -151,9 +201,9 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     const int S = prm.obj_scale;
 
     int best_obj, accepted;
-    if (prm.init) {
+    if (pc_init) {
         // surviving current replicas stay in their slots (init == 2: k_init has seeded the state and filled its holes)
-        if (prm.init == 1)
+        if (pc_init == 1)
         for (int p = tid; p < T.P; p += nthr) {
             Part<NW> c = CUR[p];
 #pragma unroll
@@ -165,11 +215,14 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     } else {
         best_obj = pl.restart_info[g * 4 + 0];
         accepted = pl.restart_info[g * 4 + 3];
+        // (a later chunk reads what another workgroup wrote in this launch: a vector load behind chunk_take's fence, never a scalar
+        //  one; the two values are wave-uniform and the loop counts `accepted` on the scalar unit)
+        if constexpr (kCanChunk) { best_obj = __builtin_amdgcn_readfirstlane(best_obj); accepted = __builtin_amdgcn_readfirstlane(accepted); }
         // Elite rule: a restart whose best feasible objective trails the topic's best (as of the previous step) re-seeds
         // its state from that assignment with probability 1/2 (hash of seed, restart, launch); the elite's own restart and
         // the restarts that tie with it keep going, so the population stays diverse.
         bool reseed = false;
-        if (prm.elite) {
+        if (pc_elite) {
             const unsigned long long ek = pl.elite_key[bm.x];
             const int e_obj = (int)kObjCap - (int)((ek >> 20) & 0xFFFFFFull);
             reseed = ek != ~0ull && (ek >> 44) == 0 && (int)(ek & 0xFFFFFull) != rho && best_obj < e_obj &&
@@ -199,7 +252,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     if (lane == 0) L.RT[krt - 1] = 0;                 // the spare entry padding lanes read
     if (kTeam) __syncthreads();
 
-    if (prm.init == 1) {
+    if (pc_init == 1) {
         // ---- hole filling by best insertion, holes in (p,k) order, in band-state form (fill_hole, kao_search_dev.h): per listed
         //      partition its brokers are marked in W, per hole a rack table is built and every index is scored from W and RT, 64 per
         //      round; the winner's counters and band rows are brought up to date at once, so W stays what rebuild_band_state would
@@ -267,6 +320,12 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
 
     // ---- per-lane RNG stream of this launch (LCG mod 2^24, re-keyed every launch) ----
     uint32_t rng = fmix32(slo ^ fmix32(shi + (uint32_t)rho * 0x9E3779B1u + prm.launch * 0x85EBCA77u + (uint32_t)tid * 0xC2B2AE3Du));   // (team: wavefront w's lanes are streams 64 w .. 64 w + 63)
+    if constexpr (kCanChunk) {   // a later chunk carries the launch's streams on: the words its predecessor stored
+        if (pc.later) rng = pl.chunk_rng[(size_t)g * 64 + lane];
+        // The ticket waits in the wavefront's generator words, dead until the epilogue stores the next ones, and is read back behind
+        // the loop: one scalar fewer live across it (every lane its own word: a plain vector store and load of the same address).
+        pl.chunk_rng[(size_t)g * 64 + lane] = pc.ticket;
+    }
 
     const int plog = TD->period_log2 + (rho & 3);
     const uint32_t pmask = (1u << plog) - 1u;
@@ -283,7 +342,7 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     // the launch parameters the loop needs, as scalars of their own: read straight from `prm` they stay one 8-dword register
     // tuple (the kernarg load) that the allocator spills and restores WHOLE -- three times per iteration, 24 v_readlane
     int lam_lo = prm.lam_min, lam_hi = prm.lam_max;
-    uint32_t n_iters = prm.iters, it_base = prm.launch * prm.iters;
+    uint32_t n_iters = kChunked ? pc.n : prm.iters, it_base = prm.launch * prm.iters + (kChunked ? pc.first : 0u);
     // One scalar for the loop's wave-uniform choice -- bit 29: REPLACE scan over two tournament slots (topics up to kScanTwoSlots
     // replica slots) -- and, small cost, for the penalty's parameters as well: lam_min in bits 11:0, lam_max in bits 23:12
     // (0 <= lam_min <= lam_max <= 2048 by search_small_cost), the period's exponent (at most 23) in bits 28:24.  Read through an empty
@@ -1203,15 +1262,80 @@ __device__ __forceinline__ void search_body(unsigned char *smem, const SearchPoo
     int V2, obj2;
     T = topic_regs<RFT>(TD);   // (the band ends: not kept across the loop)
     full_cost<NW, kTeam>(T, L, CUR, RSZ, tid, nthr, V2, obj2, hbw ? BW : nullptr, TS, wave, n_waves);
-    if ((V2 != V || obj2 != obj) && tid == 0) atomicAdd(pl.drift, 1);
+    // (the chunked instantiation reads the arguments it needs behind the loop there: late_kernarg)
+    if ((V2 != V || obj2 != obj) && tid == 0) atomicAdd(kChunked ? late_kernarg<int32_t *>(offsetof(SearchPools, drift)) : pl.drift, 1);
     if (!kGlobalA)
         for (int p = lane; p < T.P; p += 64) store_packed<NW>(state_packed, p, L.A[p]);
     if (tid == 0) {
-        pl.restart_info[g * 4 + 0] = best_obj;
-        pl.restart_info[g * 4 + 1] = V2;
-        pl.restart_info[g * 4 + 2] = obj2;
-        pl.restart_info[g * 4 + 3] = accepted;
+        int32_t *info = (kChunked ? late_kernarg<int32_t *>(offsetof(SearchPools, restart_info)) : pl.restart_info) + g * 4;
+        info[0] = best_obj;
+        info[1] = V2;
+        info[2] = obj2;
+        info[3] = accepted;
     }
+    if constexpr (kCanChunk) {   // chunked launch: the generator words for the chunk behind this one (the last chunk's are never read)
+        uint32_t *words = late_kernarg<uint32_t *>(offsetof(SearchPools, chunk_rng)) + (size_t)g * 64 + lane;
+        const uint32_t ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)*words);
+        *words = rng;
+        chunk_pass(ticket);
+    }
+}
+
+// ---- a launch as ticketed chunks ----
+// chunk_take: the workgroup takes the next ticket and looks its piece up in the schedule.  The schedule lists the chunks of one entry in
+// increasing ticket order, so the chunk before this one was taken by a workgroup that is already running (or has finished): waiting for
+// its record cannot deadlock, and a first chunk never waits.  The wait is bounded all the same: after kChunkPolls polls the workgroup
+// counts itself in the error word behind `drift`, marks the entry as given up and runs nothing; the entry's later chunks see the mark
+// and do the same at once, so the kernel always ends and the session reports the error at its next synchronising call.
+// Returns false when the workgroup has nothing to run.  `smem`: two words at the start of the carve, free before the body stages.
+constexpr uint32_t kChunkPolls = 1u << 22;   // x (s_sleep 16 + one load that misses the caches) = several seconds: hundreds of launches
+__device__ __forceinline__ bool chunk_take(unsigned char *smem, const SearchPools &pl, const SearchParams &prm, SearchPiece &pc, uint32_t &ticket) {
+    uint32_t *bc = reinterpret_cast<uint32_t *>(smem);
+    if (threadIdx.x == 0) {
+        const uint32_t t = atomicAdd(pl.chunk_ticket, 1u);
+        if (t + 1u == gridDim.x) __hip_atomic_store(pl.chunk_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every ticket is out: ready for the next launch
+        const int4 sc = pl.chunk_sched[t];
+        const uint32_t c = (uint32_t)sc.y & 0xFFu, nc = (uint32_t)sc.y >> 8;
+        uint32_t ok = 1u;
+        if (c > 0u) {
+            uint32_t *word = pl.chunk_progress + sc.x;
+            const uint32_t want = prm.serial * 256u + c, gone = prm.serial * 256u + kChunkPoison;
+            for (uint32_t n = 0;; ++n) {
+                const uint32_t v = __hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+                if (v == want) break;
+                if (v == gone || n >= kChunkPolls) { ok = 0u; break; }
+                __builtin_amdgcn_s_sleep(16);
+            }
+            if (!ok) {
+                atomicAdd(pl.drift + 1, 1);
+                if (c + 1u < nc) __hip_atomic_store(word, gone, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        bc[0] = t; bc[1] = ok;
+    }
+    __syncthreads();
+    ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)bc[0]);
+    const bool ok = __builtin_amdgcn_readfirstlane((int)bc[1]) != 0;
+    __syncthreads();   // (the two words are the start of the carve: the body stages over them)
+    // every wavefront: no load of the predecessor's record (packed state, restart_info, generator words) before this point
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const int4 sc = sched_record(pl.chunk_sched, ticket);
+    const bool later = ((uint32_t)sc.y & 0xFFu) != 0u;
+    pc = SearchPiece{(uint32_t)sc.x, later ? 0 : prm.init, later ? 0 : prm.elite, (uint32_t)sc.z, (uint32_t)sc.w, later, ticket};
+    return ok;
+}
+// chunk_pass: at the end of the body, every wavefront of the workgroup (one without a restart too, from where the body returns early
+// for it: it must not miss the barrier).  Every wavefront's stores are released at agent scope -- the chunks of one entry land on different compute
+// units and XCDs --, the workgroup meets, and thread 0 publishes the entry's count of finished chunks.
+__device__ __forceinline__ void chunk_pass(uint32_t ticket) {
+    const int4 sc = sched_record(late_kernarg<const int4 *>(offsetof(SearchPools, chunk_sched)), ticket);
+    const uint32_t c = (uint32_t)sc.y & 0xFFu, nc = (uint32_t)sc.y >> 8;
+    if (c + 1u >= nc) return;   // the last chunk: nobody waits for it
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (threadIdx.x == 0)
+        __hip_atomic_store(late_kernarg<uint32_t *>(offsetof(SearchPools, chunk_progress)) + sc.x,
+                           late_kernarg<uint32_t>(kArgPrm + offsetof(SearchParams, serial)) * 256u + c + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 #ifndef KAO_WPE_SMALL
@@ -1224,19 +1348,32 @@ template <bool kGlobalA, bool kPriced, int NW, bool kWide> constexpr int search_
 template <bool kGlobalA, bool kPriced, int NW, bool kWide, int RFT = 0, bool kSmall = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(search_min_waves<kGlobalA, kPriced, NW, kWide>(), 8))) void k_search(SearchPools pl, SearchParams prm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    search_body<kGlobalA, kPriced, NW, kWide, false, false, RFT, kSmall>(smem, pl, prm);
+    search_body<kGlobalA, kPriced, NW, kWide, false, false, RFT, kSmall>(smem, pl, prm, whole_launch(prm));
 }
+// the same for a chunked launch (LDS-resident topics): one workgroup per ticket.  Its arguments are (SearchPools, SearchParams), in that
+// order and nothing else: late_kernarg reads them by offset.
+template <bool kPriced, int NW, bool kWide, int RFT = 0, bool kSmall = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(search_min_waves<false, kPriced, NW, kWide>(), 8))) void k_search_chunked(SearchPools pl, SearchParams prm) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    SearchPiece pc;
+    uint32_t ticket;
+    if (!chunk_take(smem, pl, prm, pc, ticket)) return;   // (wave-uniform: a word broadcast through LDS)
+    search_body<false, kPriced, NW, kWide, false, false, RFT, kSmall, true>(smem, pl, prm, pc);
+}
+static_assert(std::is_same_v<decltype(&k_search_chunked<false, 4, false, 3, true>), void (*)(SearchPools, SearchParams)> &&
+              std::is_same_v<decltype(&k_search_chunked<true, 8, true>), void (*)(SearchPools, SearchParams)>,
+              "late_kernarg reads k_search_chunked's arguments by offset: (SearchPools, SearchParams) by value, in that order, nothing else");
 // working assignment in LDS, current assignment from global memory / L2 (kCurG; ~4,900 .. 9,800 partitions: always wide)
 template <bool kPriced, int NW>
 __global__ __launch_bounds__(256) void k_search_curg(SearchPools pl, SearchParams prm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    search_body<false, kPriced, NW, true, false, true>(smem, pl, prm);
+    search_body<false, kPriced, NW, true, false, true>(smem, pl, prm, whole_launch(prm));
 }
 // a team of up to 8 wavefronts per restart (topics in global memory; see search_body)
 template <bool kPriced, int NW>
 __global__ __launch_bounds__(NW == 8 ? 256 : 512) void k_team(SearchPools pl, SearchParams prm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    search_body<true, kPriced, NW, true, true>(smem, pl, prm);
+    search_body<true, kPriced, NW, true, true>(smem, pl, prm, whole_launch(prm));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1464,29 +1601,67 @@ bool search_small_cost(int lam_min, int lam_max, int obj_scale, int w_abs_max, b
     return 8 * (int64_t)lam_max + 4 * (int64_t)obj_scale * (int64_t)w_abs_max <= (int64_t)kSmallCostMax;
 }
 
-void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team, int rft, bool small) {
-    const bool curg = prm.cur_global != 0 && !global_a, wide = prm.wide != 0;
-    const size_t lds = search_lds_bytes(prm.maxP, prm.maxBx, waves, global_a, priced, nw, prm.bw != 0, prm.maxR, team, curg);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(n_blocks), block(64 * (team > 0 && !curg ? team : waves));   // a team: one workgroup per restart, `team` wavefronts each
-    if (rft == 3 && search_rf3_eligible(global_a, curg, priced, nw, team)) {   // every topic RF 3, at most 3 current replicas (kao_session.cpp)
-        if (small) {   // (the caller: search_small_cost of this launch's options and the group's weights)
-            if (wide) launch_lds<k_search<false, false, 4, true, 3, true>>(grid, block, lds, st, pools, prm);
-            else launch_lds<k_search<false, false, 4, false, 3, true>>(grid, block, lds, st, pools, prm);
+// The K-search kernel for a launch group, chosen in ONE place for the launch and for the occupancy query: f is called with the kernel
+// as a compile-time constant (launch_lds keeps its per-kernel state by it).  rft = 3: every topic RF 3, at most 3 current replicas
+// (kao_session.cpp); small: search_small_cost of the launch's options and the group's weights; chunked: one workgroup per ticket
+// (search_chunk_eligible groups only).
+using SearchKernel = void (*)(SearchPools, SearchParams);
+template <SearchKernel kKernel> using KernelConst = std::integral_constant<SearchKernel, kKernel>;
+template <class F>
+static void with_search_kernel(bool global_a, bool curg, int team, bool priced, int nw, bool wide, int rft, bool small, bool chunked, F f) {
+    chunked = chunked && search_chunk_eligible(global_a, curg, team);
+    if (rft == 3 && search_rf3_eligible(global_a, curg, priced, nw, team)) {
+        if (chunked) {
+            if (small) { if (wide) f(KernelConst<k_search_chunked<false, 4, true, 3, true>>{}); else f(KernelConst<k_search_chunked<false, 4, false, 3, true>>{}); }
+            else if (wide) f(KernelConst<k_search_chunked<false, 4, true, 3>>{});
+            else f(KernelConst<k_search_chunked<false, 4, false, 3>>{});
         }
-        else if (wide) launch_lds<k_search<false, false, 4, true, 3>>(grid, block, lds, st, pools, prm);
-        else launch_lds<k_search<false, false, 4, false, 3>>(grid, block, lds, st, pools, prm);
+        else if (small) { if (wide) f(KernelConst<k_search<false, false, 4, true, 3, true>>{}); else f(KernelConst<k_search<false, false, 4, false, 3, true>>{}); }
+        else if (wide) f(KernelConst<k_search<false, false, 4, true, 3>>{});
+        else f(KernelConst<k_search<false, false, 4, false, 3>>{});
         return;
     }
     with_flags(priced, nw == 8, [&](auto p, auto k8) {
         constexpr bool kPriced = decltype(p)::value;
         constexpr int NW = decltype(k8)::value ? 8 : 4;
-        if (curg) launch_lds<k_search_curg<kPriced, NW>>(grid, block, lds, st, pools, prm);          // working assignment in LDS, current assignment from L2
-        else if (team > 0) launch_lds<k_team<kPriced, NW>>(grid, block, lds, st, pools, prm);        // (topics in global memory only)
-        else if (global_a) launch_lds<k_search<true, kPriced, NW, true>>(grid, block, lds, st, pools, prm);   // (topics in global memory are always wide)
-        else if (wide) launch_lds<k_search<false, kPriced, NW, true>>(grid, block, lds, st, pools, prm);
-        else launch_lds<k_search<false, kPriced, NW, false>>(grid, block, lds, st, pools, prm);
+        if (curg) f(KernelConst<k_search_curg<kPriced, NW>>{});          // working assignment in LDS, current assignment from L2
+        else if (team > 0) f(KernelConst<k_team<kPriced, NW>>{});        // (topics in global memory only)
+        else if (global_a) f(KernelConst<k_search<true, kPriced, NW, true>>{});   // (topics in global memory are always wide)
+        else if (chunked) { if (wide) f(KernelConst<k_search_chunked<kPriced, NW, true>>{}); else f(KernelConst<k_search_chunked<kPriced, NW, false>>{}); }
+        else if (wide) f(KernelConst<k_search<false, kPriced, NW, true>>{});
+        else f(KernelConst<k_search<false, kPriced, NW, false>>{});
     });
+}
+
+void launch_search(const SearchPools &pools, const SearchParams &prm, int n_blocks, int waves, bool global_a, bool priced, int nw, void *stream, int team, int rft, bool small) {
+    const bool curg = prm.cur_global != 0 && !global_a, wide = prm.wide != 0;
+    const size_t lds = search_lds_bytes(prm.maxP, prm.maxBx, waves, global_a, priced, nw, prm.bw != 0, prm.maxR, team, curg);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(n_blocks), block(64 * (team > 0 && !curg ? team : waves));   // a team: one workgroup per restart, `team` wavefronts each; a chunked launch: one per ticket
+    with_search_kernel(global_a, curg, team, priced, nw, wide, rft, small, prm.chunks != 0, [&](auto k) {
+        launch_lds<decltype(k)::value>(grid, block, lds, st, pools, prm);
+    });
+}
+
+// Workgroups per compute unit of the kernel a chunked launch of these flags runs, from the runtime's occupancy query for its block size
+// and LDS carve.
+int search_resident_blocks(int waves, bool priced, int nw, bool wide, int rft, bool small, size_t lds) {
+    // (asked at every session creation that might chunk; the runtime's query costs a few tenths of a millisecond, which a solve of two
+    //  milliseconds would notice: the answer per kernel, block size, LDS carve and device is kept)
+    static std::mutex mu;
+    static std::map<std::tuple<const void *, int, size_t, int>, int> known;
+    int n = 0, dev = 0;
+    (void)hipGetDevice(&dev);
+    with_search_kernel(false, false, 0, priced, nw, wide, rft, small, true, [&](auto k) {
+        const void *fn = reinterpret_cast<const void *>(decltype(k)::value);
+        const auto key = std::make_tuple(fn, 64 * waves, lds, dev);
+        std::lock_guard<std::mutex> lock(mu);
+        const auto it = known.find(key);
+        if (it != known.end()) { n = it->second; return; }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 64 * waves, lds) != hipSuccess) { (void)hipGetLastError(); n = 0; return; }
+        known[key] = n;
+    });
+    return n;
 }
 
 // K-init for one launch group of topics in global memory: `n_blocks` block-map entries of `per_block` restarts each, `waves` wavefronts per

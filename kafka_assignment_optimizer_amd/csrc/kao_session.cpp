@@ -10,6 +10,7 @@
 namespace {
 
 constexpr int kEvRing = 32;
+constexpr const char *kChunkGaveUp = "K-search: a chunk gave up waiting for the chunk before it";
 
 // Physical workgroup order: the dispatcher places workgroup b on XCD b % 8 (observed, used for L2
 // affinity only), so the workgroups of one topic -- which read the same tables -- are dealt to one XCD.
@@ -114,6 +115,7 @@ struct SessionPlan {
     std::vector<int4> emap;   // K-eval workgroups: {topic, first candidate, n candidates, out base}
     std::vector<uint32_t> cur_pool, bw_pool, bwd_pool; std::vector<uint16_t> ext_pool, curd_pool, int_pool; std::vector<int32_t> rsz_pool;
     std::vector<uint8_t> rackof_pool;
+    std::vector<int4> sched;  // chunked K-search: every chunking group's schedule, ticket -> {entry, chunk | chunks << 8, first iteration, iterations}
     uint64_t state_bytes = 0, best_u16 = 0, win_u16 = 0, dual_i32 = 0, price_i32 = 0, wide_slices = 0;
 };
 template <typename T>
@@ -307,6 +309,103 @@ int plan_session(kao_session &s, const kao_topic *topics, int n_cu, SessionPlan 
     return rc;
 }
 
+// Does the group's K-search run its small-cost form?  (The options it depends on are the session's: the same answer at every step.)
+bool group_small(const kao_session &s, const kao_session::LaunchGroup &g) {
+    const bool rf3_runs = g.rf3 && search_rf3_eligible(g.global_a, g.cur_global, s.priced, g.nw, g.team);
+    return rf3_runs && s.small_on && g.band_tabs && search_small_cost(s.opts.lam_min, s.opts.lam_max, s.opts.obj_scale, g.w_abs_max, s.priced);
+}
+
+}  // namespace
+
+namespace kao {
+// The schedule of a chunked launch.  Two shapes, both chunk-major over the entries they chunk, so that an entry's chunks are as many
+// tickets apart as there are chunked entries and the tickets dispatched last -- the ones the device empties on -- are last chunks,
+// pieces of 1 / C of a launch:
+//   forced (KAO_SEARCH_CHUNKS=N): every entry in N chunks, ticket c * entries + e = chunk c of entry e;
+//   automatic (only from kChunkMinRounds resident rounds of entries on: with fewer, most of the batch would be tail and pay the
+//     hand-off, the uniform shape that measured worse; kao_solve's default batch of 1.3 rounds stays in one piece): only a tail is chunked -- the last K entries of the block map, K = kChunkTailPct of the resident workgroups -- and
+//     everything in front of it stays one piece: tickets 0 .. entries - K - 1 are whole entries, then chunk c of tail entry e is
+//     ticket (entries - K) + c * K + (e - (entries - K)).  A hand-off costs about 1.6 % of a 128-iteration chunk (docs/notes_r16.md):
+//     the tail pays it on K / entries of the work only.  K of one resident round is the default (tails of 100 and 150 % compared on one build, 200 / 300 % on another:
+//     docs/notes_r16.md): the chunk before was taken a whole round of tickets earlier and has all but finished when its successor
+//     starts to wait.
+// The iterations are split evenly, the first iters % C chunks one longer.
+int search_chunk_plan(int entries, int resident, int iters, int forced, int32_t *out) {
+    if (entries < 1) return 0;
+    iters = std::max(iters, 0);
+    int C = 1, K = entries;
+    if (forced >= 2) C = std::min(forced, kChunkMax);
+    else if (forced == 0 && entries >= kChunkMinRounds * (int64_t)std::max(resident, 1)) {
+        C = kChunkAuto;
+        while (C > 1 && iters / C < kChunkMinIters) C /= 2;
+        K = (int)std::min<int64_t>(entries, std::max<int64_t>(1, (int64_t)std::max(resident, 1) * kChunkTailPct / 100));
+    }
+    C = std::max(1, std::min(C, iters));   // no empty chunk: fewer chunks when there are fewer iterations
+    if (C == 1) K = entries;
+    const int whole = entries - K;          // entries in front of the tail: one piece each
+    if (out) {
+        for (int e = 0; e < whole; ++e) { int32_t *o = out + 4 * (size_t)e; o[0] = e; o[1] = 0; o[2] = 0; o[3] = iters; }
+        for (int c = 0; c < C; ++c) {
+            const int first = c * (iters / C) + std::min(c, iters % C), n = iters / C + (c < iters % C ? 1 : 0);
+            for (int e = 0; e < K; ++e) {
+                int32_t *o = out + 4 * ((size_t)whole + (size_t)c * K + e);
+                o[0] = whole + e; o[1] = c; o[2] = first; o[3] = n;
+            }
+        }
+    }
+    return whole + C * K;
+}
+}  // namespace kao
+
+extern "C" int kao_search_chunk_plan(int32_t entries, int32_t resident, int32_t iters, int32_t forced, int32_t *out, int32_t cap) {
+    if (entries < 1 || resident < 0 || iters < 0 || forced < 0) return fail(KAO_ERR_INVALID, "kao_search_chunk_plan: bad argument");
+    const int n = kao::search_chunk_plan(entries, resident, iters, forced, nullptr);
+    if (out && cap >= n) kao::search_chunk_plan(entries, resident, iters, forced, out);
+    return n;
+}
+
+namespace {
+
+// K-search as ticketed chunks: per eligible launch group the schedule search_chunk_plan gives for its entries, the workgroups the
+// device holds of its kernel (the runtime's occupancy query x compute units) and the session's iterations per launch.  A group whose
+// plan has one ticket per entry launches exactly as before.
+void plan_chunks(kao_session &s, int n_cu, SessionPlan &pl) {
+    s.chunks_forced = (int)std::min<int64_t>(std::max<int64_t>(env_int("KAO_SEARCH_CHUNKS", 0), 0), kChunkMax);   // (read per session: a test hook)
+    if (s.chunks_forced == 1) return;
+    for (kao_session::LaunchGroup &g : s.groups) {
+        if (!search_chunk_eligible(g.global_a, g.cur_global, g.team)) continue;
+        // The automatic rule chunks only what has been measured to win: the small-cost RF-3 kernel of topics below 512 replica slots
+        // (the benchmark's shape, +4.6 %, docs/notes_r16.md).  The chunked kernels of the other instantiations -- wide, general cost,
+        // generic RF, priced -- carry more scratch than the kernels they would replace and have not been timed on an oversubscribed
+        // batch: they run only when KAO_SEARCH_CHUNKS=N forces them.
+        if (s.chunks_forced == 0 && !(group_small(s, g) && !g.wide)) continue;
+        // (a compute unit holds at least one workgroup: a group of no more entries than compute units is one resident round whatever
+        //  the occupancy, and a launch too short for two chunks of kChunkMinIters never chunks -- no query for kao_solve's sessions)
+        if (s.chunks_forced == 0 && (g.smap_n <= std::max(n_cu, 1) || s.opts.iters_per_launch < 2 * kChunkMinIters)) continue;
+        const size_t lds = search_lds_bytes(g.maxP, g.maxBx, g.waves, false, s.priced, g.nw, s.any_bw, g.maxR, 0, false);
+        const int per_cu = search_resident_blocks(g.waves, s.priced, g.nw, g.wide, g.rf3 ? 3 : 0, group_small(s, g), lds);
+        const int resident = per_cu > 0 ? per_cu * std::max(n_cu, 1) : INT32_MAX;   // (query failed: the automatic rule never chunks)
+        const int iters = s.opts.iters_per_launch;
+        const int tickets = search_chunk_plan(g.smap_n, resident, iters, s.chunks_forced, nullptr);
+        if (tickets <= g.smap_n) continue;
+        std::vector<int32_t> plan((size_t)tickets * 4);
+        search_chunk_plan(g.smap_n, resident, iters, s.chunks_forced, plan.data());
+        g.chunk_tickets = tickets;
+        g.chunk_n = 1;
+        for (int t = 0; t < tickets; ++t) g.chunk_n = std::max(g.chunk_n, plan[(size_t)t * 4 + 1] + 1);
+        g.chunk_iters = iters;
+        g.chunk_priced = s.priced;
+        g.sched_off = (int)pl.sched.size();
+        std::vector<int> per_entry((size_t)g.smap_n, 0);
+        for (int t = 0; t < tickets; ++t) per_entry[(size_t)plan[(size_t)t * 4]]++;
+        for (int t = 0; t < tickets; ++t) {
+            const int32_t *r = &plan[(size_t)t * 4];
+            pl.sched.push_back(make_int4(r[0], r[1] | (per_entry[(size_t)r[0]] << 8), r[2], r[3]));
+        }
+        s.can_chunk = true;
+    }
+}
+
 // The sections of one device arena in order, each starting on a 256-byte boundary.  A section is added once, with the session's
 // pointer to it, its size and (read-only arena) the host image to upload: offsets, the total, the staging copy and the device
 // pointers all come from this one list.
@@ -343,6 +442,7 @@ ArenaLayout layout_ro(kao_session &s, const SessionPlan &pl) {
     a.add(s.d_int, pl.int_pool);
     a.add(s.d_bw, pl.bw_pool);
     a.add(s.d_bwd, pl.bwd_pool);
+    if (s.can_chunk) a.add(s.d_sched, pl.sched);
     return a;
 }
 
@@ -374,6 +474,11 @@ ArenaLayout layout_rw(kao_session &s, const SessionPlan &pl) {
     a.add(s.d_dual_rb, s.dual_rb_bytes);
     a.add(s.d_price, 2 * s.price_half_i32 * 4);
     a.add(s.d_keys_glob, n_topics * 8);
+    if (s.can_chunk) {   // (sessions that never chunk carry none of this: the generator words are 256 B per restart)
+        a.add(s.d_chunk_ctl, 256);
+        a.add(s.d_chunk_progress, (size_t)s.blocks_search * 4);
+        a.add(s.d_chunk_rng, n_restarts * 256);
+    }
     return a;
 }
 
@@ -390,6 +495,7 @@ void kao_session_destroy(kao_session *s) {
     if (s->ev_bound1) (void)hipEventDestroy(s->ev_bound1);
     if (s->ev_search) (void)hipEventDestroy(s->ev_search);
     if (s->stream_bound) (void)hipStreamDestroy(s->stream_bound);
+    if (s->h_chunk_err) (void)hipHostFree(s->h_chunk_err);
     arena_put(s->arena_ro, s->arena_ro_bytes, s->device);
     arena_put(s->arena_rw, s->arena_rw_bytes, s->device);
     for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
@@ -412,6 +518,7 @@ int kao_session_create(const kao_topic *topics, int32_t n_topics, const kao_opts
     if ((rc = resolve_opts(topics, n_topics, opts_in, n_cu, total_b, s->opts))) return rc;
     SessionPlan pl;
     if ((rc = plan_session(*s, topics, n_cu, pl))) return rc;
+    plan_chunks(*s, n_cu, pl);
 
     const ArenaLayout ro = layout_ro(*s, pl), rw = layout_rw(*s, pl);
     if ((rc = arena_get(ro.total, &s->arena_ro, &s->arena_ro_bytes))) return rc;
@@ -435,6 +542,14 @@ int kao_session_create(const kao_topic *topics, int32_t n_topics, const kao_opts
     hipError_t e3 = hipMemsetAsync(s->d_readback, 0xFF, (size_t)n_topics * 8, s->stream);
     hipError_t e4 = hipMemsetAsync(s->d_drift, 0, 16, s->stream);
     if (e4 == hipSuccess) e4 = hipMemsetAsync(s->d_price, 0, price_b ? price_b : 4, s->stream);  // no prices yet
+    if (s->can_chunk && e4 == hipSuccess) {   // (a failure is reported below, behind the synchronisation, with the others)
+        e4 = hipHostMalloc(reinterpret_cast<void **>(&s->h_chunk_err), 16);
+        if (e4 == hipSuccess) *s->h_chunk_err = 0; else s->h_chunk_err = nullptr;
+    }
+    if (s->can_chunk && e4 == hipSuccess) {   // ticket counter and progress words: zero once, never again (arenas are reused)
+        e4 = hipMemsetAsync(s->d_chunk_ctl, 0, 256, s->stream);
+        if (e4 == hipSuccess) e4 = hipMemsetAsync(s->d_chunk_progress, 0, (size_t)s->blocks_search * 4, s->stream);
+    }
     hipError_t e5 = hipStreamSynchronize(s->stream);  // `stage` is pageable host memory and goes out of scope
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess) return fail(KAO_ERR_HIP, "session upload failed");
     if (s->opts.profile) {
@@ -483,8 +598,18 @@ int kao_session_step(kao_session *s) {
         }
         const int rft = g.rf3 ? 3 : 0;
         const bool rf3_runs = rft && search_rf3_eligible(g.global_a, g.cur_global, s->priced, g.nw, g.team);
-        const bool small = rf3_runs && s->small_on && g.band_tabs && search_small_cost(gp.lam_min, gp.lam_max, gp.obj_scale, g.w_abs_max, s->priced);
-        launch_search(sp, gp, g.smap_n, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team, rft, small);
+        const bool small = group_small(*s, g);
+        int n_blocks = g.smap_n;
+        // (the schedule splits the iterations it was planned for, with the kernel it was planned for: a step with another count --
+        //  kao_solve's short first launch -- or with prices switched on since runs in one piece)
+        if (g.chunk_tickets && (int)gp.iters == g.chunk_iters && s->priced == g.chunk_priced) {   // one workgroup per ticket; the progress words of this group's entries carry this launch's serial
+            gp.chunks = g.chunk_n; gp.serial = ++s->chunk_serial;
+            sp.chunk_ticket = s->d_chunk_ctl; sp.chunk_progress = s->d_chunk_progress + g.smap_off; sp.chunk_rng = s->d_chunk_rng;
+            sp.chunk_sched = s->d_sched + g.sched_off;
+            n_blocks = g.chunk_tickets;
+            s->search_chunked_launches++;
+        }
+        launch_search(sp, gp, n_blocks, g.waves, g.global_a, s->priced, g.nw, s->stream, g.team, rft, small);
         if (rf3_runs) s->search_rf3_launches++;
         if (small) s->search_small_launches++;
         HIP_TRY(hipGetLastError());
@@ -527,7 +652,10 @@ int kao_session_new_generation(kao_session *s) {
 int kao_session_sync(kao_session *s) {
     if (!s) return fail(KAO_ERR_INVALID, "null session");
     HIP_TRY(hipSetDevice(s->device));
+    // (chunking sessions: the error word rides in front of the synchronisation, four bytes into pinned memory)
+    if (s->h_chunk_err) HIP_TRY(hipMemcpyAsync(s->h_chunk_err, s->d_drift + 1, 4, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->h_chunk_err && *s->h_chunk_err) return fail(KAO_ERR_HIP, kChunkGaveUp);
     if (s->opts.profile) return session_drain_events(s);
     return KAO_OK;
 }
@@ -535,6 +663,15 @@ int kao_session_sync(kao_session *s) {
 int kao_session_best_keys(kao_session *s, uint64_t *keys) {
     if (!s || !keys) return fail(KAO_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(s->device));
+    if (s->h_chunk_err) {   // chunking sessions: still ONE copy -- the drift block stands behind the keys in the read-back block
+        const size_t nk = (size_t)s->n_topics * 8;
+        HIP_TRY(hipMemcpyAsync(s->h_readback.data(), s->d_keys, nk + 8, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        std::memcpy(keys, s->h_readback.data(), nk);
+        std::memcpy(s->h_chunk_err, s->h_readback.data() + nk + 4, 4);
+        if (*s->h_chunk_err) return fail(KAO_ERR_HIP, kChunkGaveUp);
+        return KAO_OK;
+    }
     HIP_TRY(hipMemcpyAsync(keys, s->d_keys, (size_t)s->n_topics * 8, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return KAO_OK;
@@ -595,6 +732,12 @@ int kao_session_stats(kao_session *s, kao_stats *out) {
     out->blocks_search = s->blocks_search;
     out->search_rf3_launches = (int32_t)std::min<uint64_t>(s->search_rf3_launches, (uint64_t)INT32_MAX);
     HIP_TRY(hipMemcpy(&out->drift, s->d_drift, 4, hipMemcpyDeviceToHost));
+    return KAO_OK;
+}
+
+int kao_session_chunked_launches(kao_session *s, int64_t *out) {
+    if (!s || !out) return fail(KAO_ERR_INVALID, "null argument");
+    *out = (int64_t)s->search_chunked_launches;
     return KAO_OK;
 }
 

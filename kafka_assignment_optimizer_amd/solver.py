@@ -171,6 +171,18 @@ def cycle_square_plan(n: int) -> tuple:
     return int(out[0]), int(out[1]), int(out[2])
 
 
+def search_chunk_plan(entries: int, resident: int, iters: int, forced: int = 0) -> np.ndarray:
+    """The schedule of a chunked K-search launch (include/kao.h kao_search_chunk_plan; host only): int32 [tickets, 4] =
+    (entry, chunk, first iteration, iterations) per ticket.  `entries` rows when the launch stays in one piece."""
+    lib = _ffi.load()
+    n = lib.kao_search_chunk_plan(int(entries), int(resident), int(iters), int(forced), None, 0)
+    _check(min(n, 0), "kao_search_chunk_plan")
+    out = np.zeros((n, 4), dtype=np.int32)
+    n2 = lib.kao_search_chunk_plan(int(entries), int(resident), int(iters), int(forced), out.ctypes.data_as(C.POINTER(C.c_int32)), n)
+    _check(min(n2, 0), "kao_search_chunk_plan")
+    return out
+
+
 def cycle_seeds(topic: Topic, assign) -> np.ndarray:
     """Parity hook of KAO-CX: the seed table [P, n_cfg, 2] = (total, completing broker)."""
     ct = _CTopics([topic])
@@ -317,6 +329,12 @@ class Session:
         """K-search launches that ran the small-cost form of the RF-3 instantiation (include/kao.h)."""
         n = C.c_int64(0)
         _check(_ffi.load().kao_session_small_launches(self._h, C.byref(n)), "kao_session_small_launches")
+        return int(n.value)
+
+    def chunked_launches(self) -> int:
+        """K-search launches that ran as ticketed chunks (include/kao.h; KAO_SEARCH_CHUNKS)."""
+        n = C.c_int64(0)
+        _check(_ffi.load().kao_session_chunked_launches(self._h, C.byref(n)), "kao_session_chunked_launches")
         return int(n.value)
 
     def restart_state(self, topic: int, restart: int) -> dict:
