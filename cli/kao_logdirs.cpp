@@ -20,6 +20,23 @@
 // the row of --current, "log_dirs" has the same length, the new dir's name for a moved slot and "any" for every other: what
 // kafka-reassign-partitions --execute takes for an intra-broker move.  --dry-run reports and leaves the plan empty.  --report prints
 // one line per broker and one for the call.  All computation happens in libkao.so on the GPU.
+//
+// With --plan and / or --evacuate the tool gives log dirs to replicas that have none yet (kao_place_logdirs):
+//   kao-logdirs --current current.json --log-dirs log-dirs.txt [--plan plan.json] [--evacuate BROKER:DIR]... [--rebalance]
+//               [--default-size BYTES] [--broker-list a,b,..] [--min-gain BYTES] [--max-rounds N] [--dry-run] --out plan.json [--report]
+//   --plan      a reassignment document for some partitions of --current; for a planned partition its row decides.  A broker of the
+//               row that the current row lacks gets an ARRIVAL, a homeless replica of the size of the largest non-future entry of the
+//               partition anywhere in --log-dirs (--default-size without one, else an error), if the broker is in the list and has
+//               a usable dir; otherwise the slot stays "any".  A broker of the current row that the plan's row lacks is a DEPARTURE:
+//               its entry is neither a replica nor base (the result is made for the end state; Kafka keeps the old copy until the
+//               new one is in sync);
+//   --evacuate  BROKER:DIR, split at the first ':', repeatable: the dir leaves the broker's dir list, its non-future entries of
+//               partitions whose row still holds the broker become homeless on that broker, its other entries are stranded (neither
+//               planned nor counted; reported as stranded_bytes);
+//   --rebalance the resident replicas may move as well: the rounds of the balance run after the placement.
+// Every homeless replica goes to the dir with the fewest bytes at that moment, the largest replica first.  The plan lists the
+// partitions of --plan and those with a placed or moved replica: "replicas" is the plan's row where there is one, else the row of
+// --current; "log_dirs" names the dir of a placed or moved slot and says "any" for every other.
 // Exit status: 0 = ok, 1 = error, 2 = usage.
 #include <algorithm>
 #include <cstdint>
@@ -43,17 +60,239 @@ namespace {
     std::fprintf(stderr,
         "usage: kao-logdirs --current <reassignment.json> --log-dirs <kafka-log-dirs output> [--broker-list <id,id,...>]\n"
         "                   [--min-gain N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report] [--device D]\n"
+        "                   [--plan <reassignment.json>] [--evacuate <broker>:<dir>]... [--rebalance] [--default-size N[K|M|G|T]]\n"
         "writes the partitions with a replica that moves to another log dir of its broker; exit status: 0 = ok, 1 = error, 2 = usage\n");
     std::exit(2);
+}
+
+// --plan / --evacuate: kao_place_logdirs (the mapping is in the head of this file).  Returns when the plan is written.
+void place(const std::string &cur_path, const std::string &dirs_path, const std::string &plan_path, const std::vector<std::pair<int, std::string>> &evacuate,
+           bool have_list, const std::string &brokers_csv, bool rebalance, bool have_default, uint64_t default_size, uint64_t min_gain, int max_rounds,
+           bool dry_run, bool report, int device, const std::string &out_path) {
+    auto rows_of = [](const std::string &path, const char *what) {
+        std::map<Key, std::vector<int>> out;
+        const std::string txt = slurp(path);
+        const JValue doc = JParser(txt).parse();
+        const JValue *parts = doc.get("partitions");
+        for (size_t i = 0; parts && i < parts->arr.size(); ++i) {
+            const JValue &e = parts->arr[i];
+            const JValue *t = e.get("topic"), *p = e.get("partition"), *r = e.get("replicas");
+            if (!t || !p || !r || r->kind != JValue::Arr) throw std::runtime_error("partition entry needs topic/partition/replicas");
+            const Key k{t->str, (int)p->num};
+            if (out.count(k)) throw std::runtime_error(std::string(what) + ": partition " + k.first + "-" + std::to_string(k.second) + " listed twice");
+            std::vector<int> &reps = out[k];
+            for (auto &x : r->arr) reps.push_back((int)x.num);
+        }
+        return out;
+    };
+    const std::map<Key, std::vector<int>> by_key = rows_of(cur_path, "current");
+    std::map<Key, std::vector<int>> plan;
+    if (!plan_path.empty()) plan = rows_of(plan_path, "plan");
+    for (auto &kv : plan) {
+        const std::string what = kv.first.first + "-" + std::to_string(kv.first.second);
+        if (!by_key.count(kv.first)) throw std::runtime_error("plan: partition " + what + " is not in the current assignment");
+        if (std::set<int>(kv.second.begin(), kv.second.end()).size() != kv.second.size()) throw std::runtime_error("plan: partition " + what + " lists a broker twice");
+    }
+    const std::map<int, std::vector<LogDir>> table = load_log_dirs(dirs_path);
+    std::vector<int> ids;
+    if (have_list) {
+        for (auto &t : split(brokers_csv, ',')) if (!t.empty()) ids.push_back(std::atoi(t.c_str()));
+    } else {
+        for (auto &kv : table) ids.push_back(kv.first);
+    }
+    if (ids.empty()) throw std::runtime_error("empty broker list");
+    std::map<int, int> dense;
+    for (size_t i = 0; i < ids.size(); ++i) if (!dense.emplace(ids[i], (int)i).second) throw std::runtime_error("duplicate id in broker list");
+    const int B = (int)ids.size();
+    std::vector<std::set<std::string>> out_of((size_t)B);
+    for (auto &ev : evacuate) {
+        auto di = dense.find(ev.first);
+        auto it = table.find(ev.first);
+        bool ok = false;
+        if (di != dense.end() && it != table.end())
+            for (auto &d : it->second) ok |= d.name == ev.second && !d.failed;
+        if (!ok) throw std::runtime_error("evacuate: " + std::to_string(ev.first) + ":" + ev.second + " is not a usable log dir of a listed broker");
+        out_of[(size_t)di->second].insert(ev.second);
+    }
+    std::map<Key, uint64_t> psize;   // the largest non-future size of a partition anywhere: the size of an arrival
+    for (auto &kv : table)
+        for (auto &d : kv.second)
+            for (auto &e : d.entries)
+                if (!e.future) { uint64_t &x = psize[e.key]; x = std::max(x, e.size); }
+
+    // the usable dirs of every broker, byte-wise ascending, without the evacuated ones; where each partition sits on it
+    struct Held { int dir; uint64_t size; };
+    std::vector<std::vector<const LogDir *>> stay((size_t)B), gone((size_t)B);
+    std::vector<int> skipped((size_t)B, 0);
+    std::vector<int32_t> dir_start(1, 0);
+    std::vector<std::map<Key, Held>> where((size_t)B);
+    std::vector<std::map<Key, uint64_t>> leaving((size_t)B);
+    std::vector<std::string> flat;   // global dir index -> name
+    for (int i = 0; i < B; ++i) {
+        std::vector<const LogDir *> usable;
+        auto it = table.find(ids[(size_t)i]);
+        if (it != table.end())
+            for (auto &d : it->second) {
+                if (d.failed) ++skipped[(size_t)i];
+                else usable.push_back(&d);
+            }
+        std::sort(usable.begin(), usable.end(), [](const LogDir *x, const LogDir *y) { return x->name < y->name; });
+        for (auto *d : usable) (out_of[(size_t)i].count(d->name) ? gone : stay)[(size_t)i].push_back(d);
+        if (!out_of[(size_t)i].empty() && stay[(size_t)i].empty())
+            throw std::runtime_error("evacuate: broker " + std::to_string(ids[(size_t)i]) + " is left without a usable log dir");
+        for (auto *d : usable) {
+            const bool out = out_of[(size_t)i].count(d->name) != 0;
+            const int li = out ? 0 : (int)(std::find(stay[(size_t)i].begin(), stay[(size_t)i].end(), d) - stay[(size_t)i].begin());
+            for (auto &e : d->entries) {
+                if (e.future) continue;
+                if (where[(size_t)i].count(e.key) || leaving[(size_t)i].count(e.key))
+                    throw std::runtime_error("log-dirs: broker " + std::to_string(ids[(size_t)i]) + " holds partition " + e.key.first + "-" + std::to_string(e.key.second) + " twice");
+                if (out) leaving[(size_t)i][e.key] = e.size;
+                else where[(size_t)i][e.key] = Held{dir_start.back() + li, e.size};
+            }
+        }
+        for (auto *d : stay[(size_t)i]) flat.push_back(d->name);
+        dir_start.push_back(dir_start.back() + (int32_t)stay[(size_t)i].size());
+    }
+    const int D = dir_start.back();
+
+    // the replicas: residents, and the homeless ones (dir -1) of evacuated dirs and of the plan's arrivals
+    struct Slot { const Key *key; const std::vector<int> *row; int j; };
+    std::vector<int32_t> broker, dir;
+    std::vector<uint64_t> size;
+    std::vector<Slot> slots;
+    std::set<std::pair<int, Key>> claimed, rescued, departed;
+    for (auto &kv : by_key) {
+        auto pl = plan.find(kv.first);
+        const std::vector<int> &row = pl == plan.end() ? kv.second : pl->second;
+        const std::set<int> was(kv.second.begin(), kv.second.end());
+        for (int x : was)
+            if (std::find(row.begin(), row.end(), x) == row.end() && dense.count(x)) departed.insert({dense[x], kv.first});
+        for (size_t j = 0; j < row.size(); ++j) {
+            auto di = dense.find(row[j]);
+            if (di == dense.end()) continue;
+            const size_t i = (size_t)di->second;
+            int32_t d = -1;
+            uint64_t sz = 0;
+            auto lv = leaving[i].find(kv.first);
+            if (lv != leaving[i].end()) {   // its dir is being evacuated
+                sz = lv->second;
+                rescued.insert({di->second, kv.first});
+            } else if (was.count(row[j])) {
+                auto h = where[i].find(kv.first);
+                if (h == where[i].end()) continue;
+                d = h->second.dir;
+                sz = h->second.size;
+                claimed.insert({di->second, kv.first});
+            } else {   // an arrival
+                if (stay[i].empty()) continue;
+                auto ps = psize.find(kv.first);
+                if (ps != psize.end()) sz = ps->second;
+                else if (have_default) sz = default_size;
+                else
+                    throw std::runtime_error("log-dirs: no size for partition " + kv.first.first + "-" + std::to_string(kv.first.second) + ", which the plan brings to broker " +
+                                             std::to_string(row[j]) + " (give a default size)");
+            }
+            broker.push_back(di->second);
+            dir.push_back(d);
+            size.push_back(sz);
+            slots.push_back(Slot{&kv.first, &row, (int)j});
+        }
+    }
+    std::vector<uint64_t> base((size_t)std::max(D, 1), 0);
+    std::vector<unsigned long long> stranded((size_t)B, 0);
+    for (int i = 0; i < B; ++i) {
+        for (size_t li = 0; li < stay[(size_t)i].size(); ++li)
+            for (auto &e : stay[(size_t)i][li]->entries) {
+                if (!e.future && departed.count({i, e.key})) continue;
+                if (e.future || !claimed.count({i, e.key})) base[(size_t)dir_start[(size_t)i] + li] += e.size;
+            }
+        for (auto *d : gone[(size_t)i])
+            for (auto &e : d->entries)
+                if (e.future || !rescued.count({i, e.key})) stranded[(size_t)i] += e.size;
+    }
+    const int R = (int)dir.size();
+    const std::vector<int32_t> dir0 = dir;
+    if (dir.empty()) { broker.push_back(0); dir.push_back(0); size.push_back(0); }   // the library takes no null pointer
+
+    int rc = kao_init(device);
+    if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+    int32_t n_placed = 0, n_moved = 0, status = 0;
+    uint64_t bytes_placed = 0, bytes_moved = 0, before = 0, after = 0;
+    int64_t stats[10] = {0};
+    std::vector<uint64_t> per((size_t)B * 8, 0);
+    rc = kao_place_logdirs(B, dir_start.data(), base.data(), R, broker.data(), dir.data(), size.data(), rebalance ? 1 : 0, min_gain, max_rounds, dry_run ? 1 : 0,
+                           &n_placed, &bytes_placed, &n_moved, &bytes_moved, &before, &after, per.data(), &status, stats);
+    if (rc) throw std::runtime_error(std::string("kao_place_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
+    if (report) {
+        std::vector<int> residents((size_t)B, 0), homeless((size_t)B, 0);
+        unsigned long long total = 0, all_skipped = 0, all_out = 0, all_stranded = 0;
+        int all_res = 0, all_home = 0;
+        for (int r = 0; r < R; ++r) {
+            ++(dir0[(size_t)r] < 0 ? homeless : residents)[(size_t)broker[(size_t)r]];
+            ++(dir0[(size_t)r] < 0 ? all_home : all_res);
+            total += size[(size_t)r];
+        }
+        for (int d = 0; d < D; ++d) total += base[(size_t)d];
+        for (int i = 0; i < B; ++i) {
+            const uint64_t *p = per.data() + (size_t)i * 8;
+            all_skipped += (unsigned long long)skipped[(size_t)i];
+            all_out += (unsigned long long)out_of[(size_t)i].size();
+            all_stranded += stranded[(size_t)i];
+            std::fprintf(stderr, "logdirs: broker=%d dirs=%d skipped_dirs=%d evacuated_dirs=%d replicas=%d residents=%d homeless=%d peak_before=%llu peak_after=%llu "
+                                 "lower_bound=%llu placed=%llu bytes_placed=%llu moved=%llu bytes_moved=%llu rounds=%llu stranded_bytes=%llu\n",
+                         ids[(size_t)i], (int)stay[(size_t)i].size(), skipped[(size_t)i], (int)out_of[(size_t)i].size(), residents[(size_t)i] + homeless[(size_t)i],
+                         residents[(size_t)i], homeless[(size_t)i], (unsigned long long)p[0], (unsigned long long)p[1], (unsigned long long)p[2], (unsigned long long)p[3],
+                         (unsigned long long)p[4], (unsigned long long)p[5], (unsigned long long)p[6], (unsigned long long)p[7], stranded[(size_t)i]);
+        }
+        std::fprintf(stderr, "logdirs: status=%s brokers=%d dirs=%d skipped_dirs=%llu evacuated_dirs=%llu replicas=%d residents=%d homeless=%d peak_before=%llu "
+                             "peak_after=%llu replicas_placed=%d bytes_placed=%llu replicas_moved=%d bytes_moved=%llu bytes_total=%llu stranded_bytes=%llu "
+                             "brokers_placed=%lld brokers_moved=%lld rounds=%lld moves=%lld proposals=%lld launches=%lld stopped_by_max_rounds=%lld proven=%lld "
+                             "max_rounds_of_a_broker=%lld max_homeless_of_a_broker=%lld\n",
+                     status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, all_out, R, all_res, all_home,
+                     (unsigned long long)before, (unsigned long long)after, n_placed, (unsigned long long)bytes_placed, n_moved, (unsigned long long)bytes_moved, total,
+                     all_stranded, (long long)stats[0], (long long)stats[1], (long long)stats[2], (long long)stats[3], (long long)stats[4], (long long)stats[5],
+                     (long long)stats[6], (long long)stats[7], (long long)stats[8], (long long)stats[9]);
+    }
+    // the partitions of the plan and those with a placed or moved replica, in (topic, partition) order
+    std::map<Key, std::vector<std::string>> lists;
+    if (!dry_run) {
+        for (auto &kv : plan) lists[kv.first] = std::vector<std::string>(kv.second.size(), "any");
+        for (int r = 0; r < R; ++r) {
+            if (dir[(size_t)r] == dir0[(size_t)r]) continue;
+            const Slot &sl = slots[(size_t)r];
+            auto it = lists.find(*sl.key);
+            if (it == lists.end()) it = lists.emplace(*sl.key, std::vector<std::string>(sl.row->size(), "any")).first;
+            it->second[(size_t)sl.j] = flat[(size_t)dir[(size_t)r]];
+        }
+    }
+    std::string body;
+    int n_out = 0;
+    for (auto &kv : lists) {
+        auto pl = plan.find(kv.first);
+        const std::vector<int> &row = pl == plan.end() ? by_key.at(kv.first) : pl->second;
+        body += (n_out++ ? ",\n" : "\n");
+        body += "    {\"topic\":" + quoted(kv.first.first) + ",\"partition\":" + std::to_string(kv.first.second) + ",\"replicas\":[";
+        for (size_t k = 0; k < row.size(); ++k) body += (k ? "," : "") + std::to_string(row[k]);
+        body += "],\"log_dirs\":[";
+        for (size_t k = 0; k < kv.second.size(); ++k) body += (k ? "," : "") + quoted(kv.second[k]);
+        body += "]}";
+    }
+    std::ofstream f(out_path);
+    f << "{\"version\":1,\"partitions\":[" << body << "\n]}\n";
+    f.close();
+    if (!f) throw std::runtime_error("cannot write " + out_path);
+    kao_shutdown();
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string cur_path, brokers_csv, out_path, dirs_path;
+    std::string cur_path, brokers_csv, out_path, dirs_path, plan_path;
+    std::vector<std::pair<int, std::string>> evacuate;
     int device = 0, max_rounds = 0;
-    bool report = false, dry_run = false, have_list = false;
-    uint64_t min_gain = 0;
+    bool report = false, dry_run = false, have_list = false, rebalance = false, have_default = false;
+    uint64_t min_gain = 0, default_size = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
@@ -64,7 +303,20 @@ int main(int argc, char **argv) {
         else if (a == "--dry-run") dry_run = true;
         else if (a == "--device") device = std::atoi(need("--device").c_str());
         else if (a == "--report") report = true;
-        else if (a == "--min-gain") {
+        else if (a == "--plan") plan_path = need("--plan");
+        else if (a == "--rebalance") rebalance = true;
+        else if (a == "--evacuate") {
+            const std::string v = need("--evacuate");
+            const size_t colon = v.find(':');
+            const std::string b = colon == std::string::npos ? "" : v.substr(0, colon);
+            const std::string digits = !b.empty() && b[0] == '-' ? b.substr(1) : b;
+            if (colon == std::string::npos || colon + 1 >= v.size() || digits.empty() || b.size() > 10 || digits.find_first_not_of("0123456789") != std::string::npos)
+                usage("--evacuate needs BROKER:DIR");
+            evacuate.emplace_back(std::atoi(b.c_str()), v.substr(colon + 1));
+        } else if (a == "--default-size") {
+            if (!parse_bytes(need("--default-size"), default_size)) usage("--default-size needs a byte count (N, or N with K/M/G/T)");
+            have_default = true;
+        } else if (a == "--min-gain") {
             if (!parse_bytes(need("--min-gain"), min_gain)) usage("--min-gain needs a byte count (N, or N with K/M/G/T)");
         } else if (a == "--max-rounds") {
             const std::string v = need("--max-rounds");
@@ -74,7 +326,14 @@ int main(int argc, char **argv) {
         else usage(("unknown flag " + a).c_str());
     }
     if (cur_path.empty() || dirs_path.empty() || out_path.empty()) usage("--current, --log-dirs and --out are required");
+    const bool placing = !plan_path.empty() || !evacuate.empty();
+    if ((rebalance || have_default) && !placing) usage("--rebalance and --default-size need --plan or --evacuate");
     try {
+        if (placing) {
+            place(cur_path, dirs_path, plan_path, evacuate, have_list, brokers_csv, rebalance, have_default, default_size, min_gain, max_rounds, dry_run, report, device,
+                  out_path);
+            return 0;
+        }
         // the rows of --current by (topic, partition)
         std::map<Key, std::vector<int>> by_key;
         {

@@ -733,6 +733,51 @@ int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start /* [n_broker
                         int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
                         uint64_t *per_broker /* [n_brokers*6] */, int32_t *status, int64_t stats[8] /* may be NULL */);
 
+/* ---- Log dirs for arriving and evacuated replicas -----------------------------------------------------------
+ * Dirs, base, size and L(d) are those of kao_balance_logdirs.  Replica r belongs to broker broker[r].  It is a RESIDENT when
+ * dir[r] >= 0, and that dir must be one of broker[r]'s; it is HOMELESS when dir[r] == -1: a replica that a plan brings to the broker,
+ * or one whose dir is being evacuated.  Every broker is handled on its own.
+ * PLACE.  F(d) = base[d] + the sizes of the residents of d.  The broker's homeless replicas are taken in the order size descending,
+ * then r ascending (r = the index in the call's arrays, so the result depends on the input alone); each goes to the dir with the
+ * lowest load at that moment (ties: the lowest dir index), whose load grows by its size.  Zero-size replicas are placed the same
+ * way and come last.
+ * move_residents == 0: the residents stay and no round runs; min_gain and max_rounds are not used.  None is needed: after PLACE no
+ * single move of a placed replica closes any gap.  Let r be the LAST replica put on dir a; it went there when a was the lightest
+ * dir, so L(a) - size[r] <= L(c) held for every dir c then and holds at the end (loads only grow, and a's only by r's size).  Every
+ * earlier replica x on a has size[x] >= size[r], so L(c) + size[x] >= L(c) + size[r] >= L(a): no move a -> c of a placed replica
+ * passes the test L(c) + size + min_gain < L(a), even at min_gain 0.
+ * move_residents != 0: the rounds of kao_balance_logdirs run from the placed state over ALL replicas of the broker: same rank,
+ * pairing, test, key with r, win rule and stop rule.
+ * lower_bound of a broker holds for every outcome.  M = the replicas that may change dir (the homeless ones; all with
+ * move_residents), F' = the fixed load (F; base with move_residents): the maximum of (0) max_{r in M} size[r] + min_d F'(d) (0 when
+ * M is empty), (1) ceil((sum of F' + sum over M of size) / n), (2) max_d F'(d).  *status = KAO_STATUS_OPTIMAL_PROVEN iff peak_after
+ * == lower_bound on every broker.
+ * *peak_before = max_d F(d) of the input: the homeless replicas are nowhere yet, so *peak_after may exceed it.  *n_placed /
+ * *bytes_placed = the homeless replicas and their sizes; *n_moved / *bytes_moved = the RESIDENTS whose final dir differs from their
+ * input dir.  per_broker[8b..8b+7] = {peak_before, peak_after, lower_bound, placed, bytes_placed, moved, bytes_moved, rounds}; a
+ * broker without dirs reports zeros and counts as proven.  dry_run != 0 leaves dir[] as it was (homeless replicas still at -1) and
+ * reports the same numbers.
+ * Two identities.  With no homeless replica and move_residents != 0 the call gives byte for byte the dir[], the peaks, n_moved and
+ * bytes_moved of kao_balance_logdirs, whose six per_broker columns appear at {0, 1, 2, 5, 6, 7} of the eight.  With no homeless
+ * replica and move_residents == 0 nothing changes and every broker is proven.
+ * stats (may be NULL): [0] brokers that placed a replica, [1] brokers that applied a move, [2] rounds summed, [3] moves applied,
+ * [4] proposals summed, [5] kernel launches, [6] brokers stopped by max_rounds, [7] brokers proven, [8] the most rounds of one
+ * broker, [9] the most homeless replicas of one broker.
+ * Checked on the host before any device is used (dir[] stays as it was): KAO_ERR_INVALID for every such case of
+ * kao_balance_logdirs (dir[r] may be -1 here), a null broker or output pointer, broker[r] outside 0..n_brokers-1, dir[r] below -1
+ * or >= n_dirs, a resident whose dir is not its broker's, a homeless replica on a broker without dirs, base and size summing to
+ * 2^62 or more; KAO_ERR_UNSUPPORTED for a broker with more than KAO_LOGDIRS_MAX_DIRS dirs or n_replicas > 4,000,000. */
+int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start /* [n_brokers+1] */, const uint64_t *base /* [n_dirs] or NULL */,
+                      int32_t n_replicas, const int32_t *broker /* [n_replicas] */, int32_t *dir /* [n_replicas] in / out, -1 = homeless */,
+                      const uint64_t *size /* [n_replicas] */, int32_t move_residents, uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */,
+                      int32_t dry_run, int32_t *n_placed, uint64_t *bytes_placed, int32_t *n_moved, uint64_t *bytes_moved,
+                      uint64_t *peak_before, uint64_t *peak_after, uint64_t *per_broker /* [n_brokers*8] */, int32_t *status,
+                      int64_t stats[10] /* may be NULL */);
+/* Test hook: how kao_place_logdirs sorts a broker's homeless replicas in THIS thread's calls: 0 = by the largest homeless count of
+ * the call (the default), 1 = in LDS (the call returns KAO_ERR_UNSUPPORTED when a broker has more than 4,096), 2 = in global
+ * memory.  Returns the previous choice; both paths give the same bytes. */
+int kao_logdirs_test_sort(int32_t path);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

@@ -1,4 +1,4 @@
-// kao_logdirs.hip -- kao_balance_logdirs: replica moves between the log dirs of ONE broker that lower the peak of the bytes a dir
+// kao_logdirs.hip -- kao_balance_logdirs and kao_place_logdirs.  kao_balance_logdirs: replica moves between the log dirs of ONE broker that lower the peak of the bytes a dir
 // stores, every broker of the call at once.  Kernels and the C entry point.
 //
 // Broker b owns the dirs dir_start[b] .. dir_start[b+1]-1 (at most KAO_LOGDIRS_MAX_DIRS), dir d carries base[d] bytes that never move,
@@ -20,6 +20,17 @@
 // that wrote it; its dir is dir[r].
 // The BOUND of a broker, valid for every placement of its replicas, integers only: the maximum of (0) the largest size + the smallest
 // base, (1) ceil(sum of L / n), (2) the largest base.
+//
+// kao_place_logdirs shares the file: replica r belongs to broker[r] and is a resident (dir[r] >= 0) or homeless
+// (dir[r] == -1: a replica that a plan brings to the broker, or one of a dir that is being emptied).  The buckets are keyed by
+// broker[r], through the same three passes, which also count the homeless replicas of a broker and the largest such count.
+//   k_ld_place   ONE WORKGROUP PER BROKER: the loads F of the residents into LDS, the homeless replicas compacted into (~size, r)
+//                entries and sorted (size descending, then r ascending) by a bitonic network, in dynamic LDS up to kLdSortLds entries
+//                a broker and else in the bucket's own scratch in global memory; wavefront 0 then takes them one by one, each to the
+//                dir with the lowest load at that moment (ties: the lowest index); with move_residents the rounds above follow
+//                (ld_rounds, the one copy of the loop that k_ld_solve calls too); then the bound and the row of per_broker.
+// Its bound: M = the replicas that may change dir (the homeless; all with move_residents), F' = the fixed loads (F; base with
+// move_residents): the maximum of (0) the largest size in M + the smallest F', (1) ceil((sum of base + sum of size) / n), (2) the largest F'.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -40,8 +51,10 @@ constexpr int kLdMaxReplicas = 4000000;
 constexpr int kLdHardRounds = 1 << 26;   // no descent gets here; a guard against an endless loop
 constexpr u64 kLdNoKey = ~0ull;
 constexpr int kLdWon = 0x80;             // flag in dst[]: this round's proposal won (a destination is below 64)
-enum { LC_PEAK0 = 0, LC_PEAK1, LC_NMOVED, LC_BYTES, LC_BROKERS, LC_ROUNDS, LC_MOVES, LC_PROPS, LC_MORE, LC_PROVEN, LC_MAXROUNDS, LC_ERR, LC_MAXN, LC_N = 16 };
-enum { LS_PEAK0 = 0, LS_PEAK1, LS_MAXSIZE, LS_MINBASE, LS_MAXBASE, LS_TOTAL, LS_NMOVED, LS_BYTES, LS_MOVES, LS_PROPS, LS_N = 16 };
+constexpr int kLdSortLds = 4096;         // kao_place_logdirs: homeless replicas of one broker sorted in dynamic LDS (12 bytes each: 48 KiB of the 64 KiB a launch gets unasked)
+enum { LC_PEAK0 = 0, LC_PEAK1, LC_NMOVED, LC_BYTES, LC_BROKERS, LC_ROUNDS, LC_MOVES, LC_PROPS, LC_MORE, LC_PROVEN, LC_MAXROUNDS, LC_ERR, LC_MAXN, LC_MAXH /* = LC_MAXN + 1 */,
+       LC_NPLACED, LC_BPLACED, LC_PLACERS, LC_N = 24 };
+enum { LS_PEAK0 = 0, LS_PEAK1, LS_MAXSIZE, LS_MINBASE, LS_MAXBASE, LS_TOTAL, LS_NMOVED, LS_BYTES, LS_MOVES, LS_PROPS, LS_MINF, LS_HBYTES, LS_N = 16 };
 static_assert(kLdMaxDirs == 64, "a wavefront ranks the dirs of a broker; a destination and kLdWon share a byte");
 
 struct LdNet {   // one call; every pointer is device memory
@@ -55,36 +68,49 @@ struct LdNet {   // one call; every pointer is device memory
     const int32_t *cnt, *start, *list;   // [B], [B], [R]: the brokers' buckets of replica indices
     u64 *key;                   // [R] by place in the bucket: key of this round's proposal, kLdNoKey = none
     uint8_t *dst;               // [R] by place in the bucket: its destination (index inside the broker) | kLdWon
-    u64 *per_broker;            // [6B]
+    u64 *per_broker;            // [6B]; [8B] for k_ld_place
     u64 *ctl;                   // [LC_N]
+    // k_ld_place alone
+    int move_residents, sort_lds, sort_cap;   // the rounds follow PLACE; the sort runs in dynamic LDS of sort_cap entries (else in the bucket)
+    const int32_t *hcnt;        // [B] homeless replicas of a broker
+    uint32_t *sr;               // [R] by place in the bucket: the r of a sort entry on the global path (its size sits in key[])
 };
 
 // ---- the buckets --------------------------------------------------------------------------------------------------------------------
-__global__ void k_ld_count(int R, const int32_t *__restrict__ dir, const int32_t *__restrict__ broker_of_dir, int32_t *__restrict__ cnt) {
+// The broker of replica r is map[idx[r]] (kao_balance_logdirs: the broker of its dir), or idx[r] when map is null (kao_place_logdirs:
+// broker[r]); hcnt, when not null, counts the replicas with dir[r] < 0 beside.
+__global__ void k_ld_count(int R, const int32_t *__restrict__ idx, const int32_t *__restrict__ map, const int32_t *__restrict__ dir, int32_t *__restrict__ cnt,
+                           int32_t *__restrict__ hcnt) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < R) atomicAdd(&cnt[broker_of_dir[dir[r]]], 1);
+    if (r >= R) return;
+    const int b = map ? map[idx[r]] : idx[r];
+    atomicAdd(&cnt[b], 1);
+    if (hcnt && dir[r] < 0) atomicAdd(&hcnt[b], 1);
 }
 
-// start[b] = sum of cnt[0..b), fill[b] = 0; *max_n = the largest cnt.  One workgroup.  (k_fo_offsets of kao_failover_dev.h is this pass;
+// start[b] = sum of cnt[0..b), fill[b] = 0; max_n[0] = the largest cnt, max_n[1] = the largest hcnt (0 without hcnt).  One workgroup.  (k_fo_offsets of kao_failover_dev.h is this pass;
 // that header carries the scenario kernels, their host driver and the failover control block whose FS_MAXN word the kernel writes,
 // all in an unnamed namespace: including it here would compile the failover passes into this file, and moving the kernel out would
 // change the two files that use it.  So the twenty lines are written once more, with the maximum going to a word of the caller's.)
-__global__ __launch_bounds__(1024) void k_ld_offsets(int B, const int32_t *__restrict__ cnt, int32_t *__restrict__ start, int32_t *__restrict__ fill,
-                                                      u64 *__restrict__ max_n) {
+__global__ __launch_bounds__(1024) void k_ld_offsets(int B, const int32_t *__restrict__ cnt, const int32_t *__restrict__ hcnt, int32_t *__restrict__ start,
+                                                      int32_t *__restrict__ fill, u64 *__restrict__ max_n) {
     __shared__ int32_t part[1024];
-    __shared__ int32_t mx;
+    __shared__ int32_t mx, mh;
     const int tid = threadIdx.x, NT = blockDim.x, per = (B + NT - 1) / NT, lo = min(tid * per, B), hi = min(lo + per, B);
-    if (tid == 0) mx = 0;
+    if (tid == 0) { mx = 0; mh = 0; }
     __syncthreads();
-    int s = 0, m = 0;
+    int s = 0, m = 0, h = 0;
     for (int b = lo; b < hi; ++b) { s += cnt[b]; m = max(m, cnt[b]); }
+    for (int b = lo; hcnt && b < hi; ++b) h = max(h, hcnt[b]);
     part[tid] = s;
     if (m) atomicMax(&mx, m);
+    if (h) atomicMax(&mh, h);
     __syncthreads();
     if (tid == 0) {
         int acc = 0;
         for (int i = 0; i < NT; ++i) { const int v = part[i]; part[i] = acc; acc += v; }
-        *max_n = (u64)mx;
+        max_n[0] = (u64)mx;
+        max_n[1] = (u64)mh;
     }
     __syncthreads();
     s = part[tid];
@@ -92,12 +118,90 @@ __global__ __launch_bounds__(1024) void k_ld_offsets(int B, const int32_t *__res
 }
 
 // the order inside a bucket does not reach the result: the keys carry r
-__global__ void k_ld_scatter(int R, const int32_t *__restrict__ dir, const int32_t *__restrict__ broker_of_dir, const int32_t *__restrict__ start,
+__global__ void k_ld_scatter(int R, const int32_t *__restrict__ idx, const int32_t *__restrict__ map, const int32_t *__restrict__ start,
                              int32_t *__restrict__ fill, int32_t *__restrict__ list) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
-    const int b = broker_of_dir[dir[r]];
+    const int b = map ? map[idx[r]] : idx[r];
     list[start[b] + atomicAdd(&fill[b], 1)] = r;
+}
+
+// ---- the rounds of one broker (RANK / PROPOSE / DECIDE / APPLY of the head of this file), called by every lane of its workgroup with the
+// loads in place, mk[] at kLdNoKey and every replica of the bucket in a dir.  rounds and more are the workgroup's, props and moves this lane's.
+struct LdTally {
+    int rounds = 0, more = 0;
+    u64 props = 0, moves = 0;
+};
+__device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int nr, const int32_t *list, u64 *key, uint8_t *dst, u64 *load, u64 *mk, uint8_t *rank,
+                                             uint8_t *order) {
+    const int tid = threadIdx.x, NT = blockDim.x;
+    LdTally t;
+    for (;;) {
+        if (tid < nd) {   // RANK
+            const u64 mine = load[tid];
+            int q = 0;
+            for (int j = 0; j < nd; ++j) {
+                const u64 x = load[j];
+                q += (x > mine || (x == mine && j < tid)) ? 1 : 0;
+            }
+            rank[tid] = (uint8_t)q;   // ranks are a permutation: q < nd
+            order[q] = (uint8_t)tid;
+        }
+        __syncthreads();
+        int mine = 0;
+        for (int q = tid; q < nr; q += NT) {   // PROPOSE
+            const int r = list[q];
+            const u64 w = n.size[r];
+            u64 k = kLdNoKey;
+            if (w && nd >= 2) {
+                const int a = n.dir[r] - ds, ra = rank[a];
+                const u64 la = load[a];
+                int c = -1;
+                if (ra < nd - 1 - ra) {
+                    const int c1 = order[nd - 1 - ra];
+                    if (descent_gains(la, load[c1], w, n.min_gain)) c = c1;
+                }
+                if (c < 0 && ra >= 1) {
+                    const int c2 = order[nd - 1];   // (a itself when a is the lightest: it does not pass)
+                    if (descent_gains(la, load[c2], w, n.min_gain)) c = c2;
+                }
+                if (c >= 0) {
+                    k = (u64)(uint32_t)ra << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)r;
+                    dst[q] = (uint8_t)c;
+                    descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[a], k);
+                    descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[c], k);
+                    ++mine;
+                }
+            }
+            key[q] = k;   // key[q], dst[q] and dir[r] are read back by this lane alone
+        }
+        if (!__syncthreads_or(mine)) break;
+        if ((n.max_rounds > 0 && t.rounds >= n.max_rounds) || t.rounds >= kLdHardRounds) { t.more = 1; break; }
+        ++t.rounds;
+        t.props += (u64)mine;
+        for (int q = tid; q < nr; q += NT) {   // DECIDE
+            const u64 k = key[q];
+            if (k == kLdNoKey) continue;
+            const int c = dst[q];
+            if (mk[n.dir[list[q]] - ds] == k && mk[c] == k) dst[q] = (uint8_t)(c | kLdWon);
+        }
+        __syncthreads();
+        for (int q = tid; q < nr; q += NT) {   // APPLY
+            if (key[q] == kLdNoKey) continue;
+            const int r = list[q], s = dst[q], c = s & (kLdWon - 1), a = n.dir[r] - ds;
+            if (s & kLdWon) {   // no other winner touches a or c
+                const u64 w = n.size[r];
+                load[a] -= w;
+                load[c] += w;
+                n.dir[r] = ds + c;
+                ++t.moves;
+            }
+            mk[a] = kLdNoKey;
+            mk[c] = kLdNoKey;
+        }
+        __syncthreads();
+    }
+    return t;
 }
 
 // ---- one broker ---------------------------------------------------------------------------------------------------------------------
@@ -140,74 +244,9 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
         const u64 x = load[tid];
         if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
     }
-    // ---- the rounds ----
-    u64 props = 0, moves = 0;
-    int rounds = 0, more = 0;
-    for (;;) {
-        if (tid < nd) {   // RANK
-            const u64 mine = load[tid];
-            int q = 0;
-            for (int j = 0; j < nd; ++j) {
-                const u64 x = load[j];
-                q += (x > mine || (x == mine && j < tid)) ? 1 : 0;
-            }
-            rank[tid] = (uint8_t)q;   // ranks are a permutation: q < nd
-            order[q] = (uint8_t)tid;
-        }
-        __syncthreads();
-        int mine = 0;
-        for (int q = tid; q < nr; q += NT) {   // PROPOSE
-            const int r = list[q];
-            const u64 w = n.size[r];
-            u64 k = kLdNoKey;
-            if (w && nd >= 2) {
-                const int a = n.dir[r] - ds, ra = rank[a];
-                const u64 la = load[a];
-                int c = -1;
-                if (ra < nd - 1 - ra) {
-                    const int c1 = order[nd - 1 - ra];
-                    if (descent_gains(la, load[c1], w, n.min_gain)) c = c1;
-                }
-                if (c < 0 && ra >= 1) {
-                    const int c2 = order[nd - 1];   // (a itself when a is the lightest: it does not pass)
-                    if (descent_gains(la, load[c2], w, n.min_gain)) c = c2;
-                }
-                if (c >= 0) {
-                    k = (u64)(uint32_t)ra << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)r;
-                    dst[q] = (uint8_t)c;
-                    descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[a], k);
-                    descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[c], k);
-                    ++mine;
-                }
-            }
-            key[q] = k;   // key[q], dst[q] and dir[r] are read back by this lane alone
-        }
-        if (!__syncthreads_or(mine)) break;
-        if ((n.max_rounds > 0 && rounds >= n.max_rounds) || rounds >= kLdHardRounds) { more = 1; break; }
-        ++rounds;
-        props += (u64)mine;
-        for (int q = tid; q < nr; q += NT) {   // DECIDE
-            const u64 k = key[q];
-            if (k == kLdNoKey) continue;
-            const int c = dst[q];
-            if (mk[n.dir[list[q]] - ds] == k && mk[c] == k) dst[q] = (uint8_t)(c | kLdWon);
-        }
-        __syncthreads();
-        for (int q = tid; q < nr; q += NT) {   // APPLY
-            if (key[q] == kLdNoKey) continue;
-            const int r = list[q], s = dst[q], c = s & (kLdWon - 1), a = n.dir[r] - ds;
-            if (s & kLdWon) {   // no other winner touches a or c
-                const u64 w = n.size[r];
-                load[a] -= w;
-                load[c] += w;
-                n.dir[r] = ds + c;
-                ++moves;
-            }
-            mk[a] = kLdNoKey;
-            mk[c] = kLdNoKey;
-        }
-        __syncthreads();
-    }
+    const LdTally t = ld_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
+    const int rounds = t.rounds, more = t.more;
+    const u64 props = t.props, moves = t.moves;
     // ---- the result ----
     if (tid < nd) {
         const u64 x = load[tid];
@@ -245,8 +284,193 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
     }
 }
 
+// ---- kao_place_logdirs -----------------------------------------------------------------------------------------
+// A sort entry is (~size, r): ascending by both is size descending, then r ascending, and the r make every entry distinct.  The
+// network is the bitonic one whose comparators all point the same way (the first step of a merge pairs i with i ^ (k - 1), the
+// others i with i | j): the lower index takes the lower entry.  The entries from h up to the next power of two are the padding
+// that sorts last; no comparator would ever move one, so they are not stored and a comparator that reaches past h is skipped.
+template <class K, class I>
+__device__ __forceinline__ void ld_sort(K sk, I sr, int h) {
+    const int tid = threadIdx.x, NT = blockDim.x;
+    int half = 1;
+    while (half * 2 < h) half *= 2;   // half the padded length (h >= 2)
+    for (int k = 2; k <= 2 * half; k <<= 1) {
+        for (int j = k >> 1; j >= 1; j >>= 1) {
+            for (int t = tid; t < half; t += NT) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));   // the t-th index with bit j clear
+                const int l = j == (k >> 1) ? (i ^ (k - 1)) : (i | j);
+                if (l < h) {
+                    const u64 ki = sk[i], kl = sk[l];
+                    const uint32_t ri = sr[i], rl = sr[l];
+                    if (ki > kl || (ki == kl && ri > rl)) { sk[i] = kl; sk[l] = ki; sr[i] = rl; sr[l] = ri; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__device__ __forceinline__ u64 ld_readlane(u64 x, int lane) {   // lane is the same in every lane
+    return (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane) | (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane) << 32;
+}
+
+// PLACE by wavefront 0, all 64 lanes active: lane d < nd keeps L(d), the others the maximum.  The sorted entries come in chunks of 64,
+// lane j loading entry j; per entry a butterfly over the first `span` lanes (the power of two >= nd) leaves the lowest (L, d) in
+// lane 0, a true 64-bit compare with the lane as the tie.  The winner adds the size; lane j keeps the dir of its own entry and
+// stores it after the chunk, off the chain.
+template <class K, class I>
+__device__ __forceinline__ void ld_greedy(const LdNet &n, K sk, I sr, int h, int ds, int nd, u64 *load) {
+    const int lane = threadIdx.x;
+    int span = 1;
+    while (span < nd) span *= 2;
+    u64 L = lane < nd ? load[lane] : kLdNoKey;
+    for (int c = 0; c < h; c += 64) {
+        const int m = min(64, h - c);
+        u64 ks = 0;
+        uint32_t rr = 0;
+        if (lane < m) { ks = sk[c + lane]; rr = sr[c + lane]; }
+        int mine = 0;
+        for (int i = 0; i < m; ++i) {
+            const u64 w = ~ld_readlane(ks, i);
+            u64 bl = L;
+            int bd = lane;
+            for (int x = span >> 1; x >= 1; x >>= 1) {
+                const u64 ol = __shfl_xor(bl, x);
+                const int od = __shfl_xor(bd, x);
+                const bool lower = ol < bl || (ol == bl && od < bd);
+                bl = lower ? ol : bl;
+                bd = lower ? od : bd;
+            }
+            bd = __builtin_amdgcn_readlane(bd, 0);
+            if (lane == bd) L += w;
+            if (lane == i) mine = bd;
+        }
+        if (lane < m) n.dir[rr] = ds + mine;
+    }
+    if (lane < nd) load[lane] = L;
+}
+
+// One workgroup per broker: the loads F of the residents, the homeless replicas compacted and sorted, PLACE, with move_residents the
+// rounds over every replica of the broker, then the bound and the row of per_broker.  Dynamic LDS: the sort entries of the LDS path,
+// sizes u64[sort_cap] and then r u32[sort_cap]; the other path sorts in key[] and sr[] at the bucket's place, which this workgroup
+// alone touches (the rounds write key[] before they read it).
+__global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
+    extern __shared__ u64 ld_dyn[];
+    __shared__ u64 load[kLdMaxDirs], mk[kLdMaxDirs], sh[LS_N];
+    __shared__ uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
+    __shared__ int fill;
+    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+    const int ds = n.dir_start[b], nd = n.dir_start[b + 1] - ds, nr = n.cnt[b], at = n.start[b], h = n.hcnt[b];
+    u64 *o = n.per_broker + 8 * (size_t)b;
+    if (nd == 0) {   // no dir, so no replica: zeros, and nothing to prove
+        if (tid == 0) {
+            for (int i = 0; i < 8; ++i) o[i] = 0;
+            atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        }
+        return;
+    }
+    const int32_t *list = n.list + at;
+    u64 *key = n.key + at;
+    uint8_t *dst = n.dst + at;
+    uint32_t *sr = n.sr + at;
+    u64 *lk = ld_dyn;
+    uint32_t *lr = reinterpret_cast<uint32_t *>(ld_dyn + n.sort_cap);
+    if (tid < LS_N) sh[tid] = (tid == LS_MINBASE || tid == LS_MINF) ? kLdNoKey : 0;
+    if (tid < nd) { load[tid] = n.base[ds + tid]; mk[tid] = kLdNoKey; }
+    if (tid == 0) fill = 0;
+    __syncthreads();
+    {   // the loads of the residents; the homeless replicas into the sort's entries, in any order; the largest size of those that may change dir
+        u64 mx = 0, hb = 0;
+        for (int q = tid; q < nr; q += NT) {
+            const int r = list[q], d = n.dir[r];
+            const u64 w = n.size[r];
+            if (d >= 0) {
+                if (w) atomicAdd(&load[d - ds], w);
+                if (n.move_residents) mx = max(mx, w);
+            } else {
+                const int e = atomicAdd(&fill, 1);   // below h = hcnt[b] <= sort_cap
+                if (n.sort_lds) { lk[e] = ~w; lr[e] = (uint32_t)r; }
+                else { key[e] = ~w; sr[e] = (uint32_t)r; }
+                hb += w;
+                mx = max(mx, w);
+            }
+        }
+        if (mx) atomicMax(&sh[LS_MAXSIZE], mx);
+        if (hb) atomicAdd(&sh[LS_HBYTES], hb);
+        if (tid < nd) {
+            const u64 x = n.base[ds + tid];
+            atomicMin(&sh[LS_MINBASE], x);
+            if (x) atomicMax(&sh[LS_MAXBASE], x);
+        }
+    }
+    __syncthreads();
+    if (tid < nd) {
+        const u64 x = load[tid];
+        atomicMin(&sh[LS_MINF], x);
+        if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
+    }
+    if (h >= 2) {
+        if (n.sort_lds) ld_sort(lk, lr, h);
+        else ld_sort(key, sr, h);
+    }
+    if (h >= 1) {
+        if (tid < 64) {
+            if (n.sort_lds) ld_greedy(n, lk, lr, h, ds, nd, load);
+            else ld_greedy(n, key, sr, h, ds, nd, load);
+        }
+        __syncthreads();   // the loads and the dirs of the placed replicas, for every lane
+    }
+    LdTally t;
+    if (n.move_residents) t = ld_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
+    // ---- the result ----
+    if (tid < nd) {
+        const u64 x = load[tid];
+        if (x) atomicMax(&sh[LS_PEAK1], x);
+    }
+    if (n.move_residents) {
+        u64 moved = 0, bytes = 0;
+        for (int q = tid; q < nr; q += NT) {
+            const int r = list[q], d0 = n.dir0[r];
+            if (d0 >= 0 && n.dir[r] != d0) { ++moved; bytes += n.size[r]; }
+        }
+        if (moved) { atomicAdd(&sh[LS_NMOVED], moved); atomicAdd(&sh[LS_BYTES], bytes); }
+        if (t.moves) atomicAdd(&sh[LS_MOVES], t.moves);
+        if (t.props) atomicAdd(&sh[LS_PROPS], t.props);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        // M = the replicas that may change dir, F' = the fixed loads: the homeless over F, or with move_residents all over base
+        const bool any = n.move_residents ? nr > 0 : h > 0;
+        const u64 t0 = any ? sh[LS_MAXSIZE] + (n.move_residents ? sh[LS_MINBASE] : sh[LS_MINF]) : 0;
+        const u64 t1 = (sh[LS_TOTAL] + sh[LS_HBYTES] + (u64)nd - 1) / (u64)nd;   // sum of F + the homeless = sum of base + every size
+        const u64 lb = max(max(t0, t1), n.move_residents ? sh[LS_MAXBASE] : sh[LS_PEAK0]);
+        o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = (u64)h; o[4] = sh[LS_HBYTES]; o[5] = sh[LS_NMOVED]; o[6] = sh[LS_BYTES]; o[7] = (u64)t.rounds;
+        atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
+        atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
+        if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        if (h) {
+            atomicAdd(&n.ctl[LC_PLACERS], 1ull);
+            atomicAdd(&n.ctl[LC_NPLACED], (u64)h);
+            atomicAdd(&n.ctl[LC_BPLACED], sh[LS_HBYTES]);
+        }
+        if (t.rounds) {
+            atomicAdd(&n.ctl[LC_BROKERS], 1ull);   // every round with a proposal applies a move
+            atomicAdd(&n.ctl[LC_ROUNDS], (u64)t.rounds);
+            atomicAdd(&n.ctl[LC_MOVES], sh[LS_MOVES]);
+            atomicAdd(&n.ctl[LC_PROPS], sh[LS_PROPS]);
+            atomicMax(&n.ctl[LC_MAXROUNDS], (u64)t.rounds);
+            atomicAdd(&n.ctl[LC_NMOVED], sh[LS_NMOVED]);
+            atomicAdd(&n.ctl[LC_BYTES], sh[LS_BYTES]);
+        }
+        if (t.more) atomicAdd(&n.ctl[LC_MORE], 1ull);
+        if (t.rounds >= kLdHardRounds) atomicAdd(&n.ctl[LC_ERR], 1ull);
+    }
+}
+
+thread_local int t_ld_sort = 0;   // kao_logdirs_test_sort: 0 = by size, 1 = dynamic LDS, 2 = global memory
+
 int validate_logdirs(const std::string &fn, int32_t B, const int32_t *dir_start, const uint64_t *base, int32_t R, const int32_t *dir, const uint64_t *size,
-                     const void *const *outs, int n_outs) {
+                     const void *const *outs, int n_outs, int lowest_dir = 0) {
     bool null = !dir_start || !dir || !size;
     for (int i = 0; i < n_outs; ++i) null |= !outs[i];
     if (null) return fail(KAO_ERR_INVALID, fn + "null pointer");
@@ -261,7 +485,8 @@ int validate_logdirs(const std::string &fn, int32_t B, const int32_t *dir_start,
     if (R > kLdMaxReplicas) return fail(KAO_ERR_UNSUPPORTED, fn + "more than 4,000,000 replicas");
     const int32_t D = dir_start[B];
     for (int64_t r = 0; r < R; ++r)
-        if (dir[r] < 0 || dir[r] >= D) return fail(KAO_ERR_INVALID, fn + "dir[" + std::to_string(r) + "] is outside 0..n_dirs-1");
+        if (dir[r] < lowest_dir || dir[r] >= D)
+            return fail(KAO_ERR_INVALID, fn + "dir[" + std::to_string(r) + "] is outside " + (lowest_dir ? "-1" : "0") + "..n_dirs-1");
     uint64_t total = 0;   // below 2^62: every load of the kernel stays below 2^63
     const uint64_t lim = uint64_t(1) << 62;
     for (int64_t d = 0; base && d < D; ++d)
@@ -314,10 +539,10 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
     int launches = 0;
     const unsigned rblocks = grid_for(R, kLdThreads);
     if (R) {
-        k_ld_count<<<rblocks, kLdThreads, 0, st>>>(R, d_dir0, d_bod, d_cnt);
+        k_ld_count<<<rblocks, kLdThreads, 0, st>>>(R, d_dir0, d_bod, nullptr, d_cnt, nullptr);
         ++launches;
     }
-    k_ld_offsets<<<1, 1024, 0, st>>>(B, d_cnt, d_start, d_fill, d_ctl + LC_MAXN);
+    k_ld_offsets<<<1, 1024, 0, st>>>(B, d_cnt, nullptr, d_start, d_fill, d_ctl + LC_MAXN);
     ++launches;
     if (R) {
         k_ld_scatter<<<rblocks, kLdThreads, 0, st>>>(R, d_dir0, d_bod, d_start, d_fill, d_list);
@@ -332,6 +557,7 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
     LdNet n;
     n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
     n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
+    n.move_residents = 1; n.sort_lds = 0; n.sort_cap = 0; n.hcnt = nullptr; n.sr = nullptr;
     k_ld_solve<<<(unsigned)B, threads, 0, st>>>(n);
     HIP_TRY(hipGetLastError());
     ++launches;
@@ -352,6 +578,110 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
     if (stats) {
         stats[0] = (int64_t)ctl[LC_BROKERS]; stats[1] = (int64_t)ctl[LC_ROUNDS]; stats[2] = (int64_t)ctl[LC_MOVES]; stats[3] = (int64_t)ctl[LC_PROPS];
         stats[4] = launches; stats[5] = (int64_t)ctl[LC_MORE]; stats[6] = (int64_t)ctl[LC_PROVEN]; stats[7] = (int64_t)ctl[LC_MAXROUNDS];
+    }
+    return KAO_OK;
+}
+
+extern "C" int kao_logdirs_test_sort(int32_t path) {
+    if (path < 0 || path > 2) return fail(KAO_ERR_INVALID, "kao_logdirs_test_sort: path outside 0..2");
+    const int was = t_ld_sort;
+    t_ld_sort = path;
+    return was;
+}
+
+extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, int32_t n_replicas, const int32_t *broker, int32_t *dir,
+                                 const uint64_t *size, int32_t move_residents, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_placed,
+                                 uint64_t *bytes_placed, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                                 uint64_t *per_broker, int32_t *status, int64_t stats[10]) {
+    const std::string fn = "kao_place_logdirs: ";
+    const void *outs[] = {broker, n_placed, bytes_placed, n_moved, bytes_moved, peak_before, peak_after, per_broker, status};
+    int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 9, -1);
+    if (rc) return rc;
+    const int B = n_brokers, R = n_replicas, D = dir_start[B];
+    for (int64_t r = 0; r < R; ++r) {
+        const int32_t b = broker[r], d = dir[r];
+        if (b < 0 || b >= B) return fail(KAO_ERR_INVALID, fn + "broker[" + std::to_string(r) + "] is outside 0..n_brokers-1");
+        if (d >= 0 && (d < dir_start[b] || d >= dir_start[b + 1]))
+            return fail(KAO_ERR_INVALID, fn + "dir[" + std::to_string(r) + "] is not a dir of broker " + std::to_string(b));
+        if (d < 0 && dir_start[b + 1] == dir_start[b])
+            return fail(KAO_ERR_INVALID, fn + "replica " + std::to_string(r) + " is homeless on broker " + std::to_string(b) + ", which has no dir");
+    }
+    if ((rc = require_init())) return rc;
+
+    // one arena: ctl u64[LC_N] | cnt, hcnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] | per_broker u64[8B] |
+    //            key, size u64[R] | broker, dir, dir0, list i32[R] | sr u32[R] | dst u8[R]
+    Carve cv;
+    const size_t o_ctl = cv.take<u64>(LC_N), o_cnt = cv.take<int32_t>(B), o_hcnt = cv.take<int32_t>(B), o_base = cv.take<u64>(D), zeroed = cv.end(),
+                 o_start = cv.take<int32_t>(B), o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_pb = cv.take<u64>(8 * (size_t)B),
+                 o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_broker = cv.take<int32_t>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R),
+                 o_list = cv.take<int32_t>(R), o_sr = cv.take<uint32_t>(R), o_dst = cv.take<uint8_t>(R);
+    CallBufs m;
+    if ((rc = m.open(cv.end()))) return rc;
+    hipStream_t st = m.stream;
+    int32_t *d_cnt = m.at<int32_t>(o_cnt), *d_hcnt = m.at<int32_t>(o_hcnt), *d_start = m.at<int32_t>(o_start), *d_fill = m.at<int32_t>(o_fill),
+            *d_ds = m.at<int32_t>(o_ds), *d_broker = m.at<int32_t>(o_broker), *d_dir = m.at<int32_t>(o_dir), *d_dir0 = m.at<int32_t>(o_dir0),
+            *d_list = m.at<int32_t>(o_list);
+    u64 *d_ctl = m.at<u64>(o_ctl), *d_base = m.at<u64>(o_base), *d_size = m.at<u64>(o_size), *d_pb = m.at<u64>(o_pb);
+
+    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
+    HIP_TRY(hipMemcpyAsync(d_ds, dir_start, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (D && base) HIP_TRY(hipMemcpyAsync(d_base, base, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (R) {
+        HIP_TRY(hipMemcpyAsync(d_broker, broker, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_dir0, dir, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_dir, d_dir0, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)R * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    }
+    int launches = 0;
+    const unsigned rblocks = grid_for(R, kLdThreads);
+    if (R) {
+        k_ld_count<<<rblocks, kLdThreads, 0, st>>>(R, d_broker, nullptr, d_dir0, d_cnt, d_hcnt);
+        ++launches;
+    }
+    k_ld_offsets<<<1, 1024, 0, st>>>(B, d_cnt, d_hcnt, d_start, d_fill, d_ctl + LC_MAXN);
+    ++launches;
+    if (R) {
+        k_ld_scatter<<<rblocks, kLdThreads, 0, st>>>(R, d_broker, nullptr, d_start, d_fill, d_list);
+        ++launches;
+    }
+    HIP_TRY(hipGetLastError());
+    u64 max_n[2] = {0, 0};   // the largest bucket, the most homeless replicas of one broker
+    HIP_TRY(hipMemcpyAsync(max_n, d_ctl + LC_MAXN, sizeof max_n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int threads = max_n[0] <= (u64)kLdSmallBucket ? kLdSoloSmall : kLdSoloLarge;
+    const bool fits = max_n[1] <= (u64)kLdSortLds;
+    if (t_ld_sort == 1 && !fits)
+        return fail(KAO_ERR_UNSUPPORTED, fn + "a broker has " + std::to_string(max_n[1]) + " homeless replicas: more than the " + std::to_string(kLdSortLds) +
+                                             " the LDS sort holds");
+    const bool lds = t_ld_sort == 2 ? false : fits;
+
+    LdNet n;
+    n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
+    n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
+    n.move_residents = move_residents ? 1 : 0; n.sort_lds = lds ? 1 : 0; n.sort_cap = lds ? (int)max_n[1] : 0; n.hcnt = d_hcnt; n.sr = m.at<uint32_t>(o_sr);
+    k_ld_place<<<(unsigned)B, threads, (size_t)n.sort_cap * (sizeof(u64) + sizeof(uint32_t)), st>>>(n);
+    HIP_TRY(hipGetLastError());
+    ++launches;
+    u64 ctl[LC_N];
+    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
+    if (!dry_run && (ctl[LC_NPLACED] || ctl[LC_NMOVED])) {
+        HIP_TRY(hipMemcpyAsync(dir, d_dir, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_placed = (int32_t)ctl[LC_NPLACED];
+    *bytes_placed = ctl[LC_BPLACED];
+    *n_moved = (int32_t)ctl[LC_NMOVED];
+    *bytes_moved = ctl[LC_BYTES];
+    *peak_before = ctl[LC_PEAK0];
+    *peak_after = ctl[LC_PEAK1];
+    *status = ctl[LC_PROVEN] == (u64)B ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    if (stats) {
+        stats[0] = (int64_t)ctl[LC_PLACERS]; stats[1] = (int64_t)ctl[LC_BROKERS]; stats[2] = (int64_t)ctl[LC_ROUNDS]; stats[3] = (int64_t)ctl[LC_MOVES];
+        stats[4] = (int64_t)ctl[LC_PROPS]; stats[5] = launches; stats[6] = (int64_t)ctl[LC_MORE]; stats[7] = (int64_t)ctl[LC_PROVEN];
+        stats[8] = (int64_t)ctl[LC_MAXROUNDS]; stats[9] = (int64_t)max_n[1];
     }
     return KAO_OK;
 }

@@ -11,6 +11,12 @@ no single move closes a gap of more than --min-gain bytes.  The brokers are inde
 lower bound beside it: where peak_after == lower_bound on every broker the peaks are proven optimal.  The plan lists the partitions
 with a moved replica, `replicas` as they are and a `log_dirs` list beside them ("any" for a slot that stays), which is what
 kafka-reassign-partitions --execute takes.
+
+With --plan FILE and / or --evacuate BROKER:DIR (repeatable) the replicas that have no dir yet get one (kao_place_logdirs, DESIGN.md
+section 4p): those that the plan brings to a listed broker and those of a dir that is being emptied go, the largest first, to the
+dir of their broker with the fewest bytes at that moment; --rebalance lets the residents move as well (the rounds above, in the same
+call), --default-size N gives a size to an arrival that --log-dirs does not list.  The plan then lists the partitions of --plan and
+those with a placed or moved replica, with the dir's name in the slot of such a replica.
 """
 from __future__ import annotations
 
@@ -132,6 +138,71 @@ def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, m
                                            stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_logdirs")
     return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
                          per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
+
+
+PLACE_STAT_KEYS = ("brokers_placed", "brokers_moved", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven", "max_rounds_of_a_broker",
+                   "max_homeless_of_a_broker")
+PLACE_PER_BROKER_KEYS = ("peak_before", "peak_after", "lower_bound", "placed", "bytes_placed", "moved", "bytes_moved", "rounds")
+
+
+@dataclass
+class PlaceLogDirsResult:
+    dir: np.ndarray          # [R] int32: the dir of every replica after the call (the input, homeless replicas at -1, with dry_run)
+    n_placed: int            # homeless replicas, each given a dir
+    bytes_placed: int
+    n_moved: int             # residents whose final dir differs from their input dir
+    bytes_moved: int
+    peak_before: int         # max_d F(d): the input without the homeless replicas
+    peak_after: int
+    per_broker: np.ndarray   # [B, 8] uint64, see PLACE_PER_BROKER_KEYS
+    status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound on every broker) | "FEASIBLE_BOUND_GAP"
+    stats: np.ndarray        # int64[10], see PLACE_STAT_KEYS / include/kao.h
+
+
+def place_logdirs_arrays(dir_start, broker, dir, size, base=None, move_residents: bool = False, min_gain: int = 0, max_rounds: int = 0,
+                         dry_run: bool = False) -> PlaceLogDirsResult:
+    """kao_place_logdirs on arrays: replica r belongs to broker[r] and sits in dir[r], or is homeless (dir[r] == -1) and gets the
+    lightest dir of its broker, the largest replica first; with move_residents the rounds of kao_balance_logdirs follow."""
+    ds = np.ascontiguousarray(np.asarray(dir_start).reshape(-1), dtype=np.int32)
+    if ds.shape[0] < 2:
+        raise ValueError("dir_start must hold n_brokers + 1 values, n_brokers >= 1")
+    B = ds.shape[0] - 1
+    d = np.array(np.asarray(dir).reshape(-1), dtype=np.int32, order="C")
+    R = d.shape[0]
+    br = np.asarray(broker).reshape(-1)
+    if br.shape != (R,):
+        raise ValueError(f"broker must hold one value per replica ({R}), got {br.shape[0]}")
+    if R and br.dtype.kind not in "ui":
+        raise ValueError("brokers must be integers")
+    sz = np.asarray(size).reshape(-1)
+    if sz.shape != (R,):
+        raise ValueError(f"size must hold one value per replica ({R}), got {sz.shape[0]}")
+    if R and (sz.dtype.kind not in "ui" or (sz.dtype.kind == "i" and (sz < 0).any())):
+        raise ValueError("sizes must be integers >= 0")
+    if isinstance(min_gain, bool) or not 0 <= int(min_gain) < 1 << 64:
+        raise ValueError("min_gain must be 0..2^64-1")
+    sbuf = np.ascontiguousarray(sz, dtype=np.uint64) if R else np.zeros(1, dtype=np.uint64)
+    dbuf = d if R else np.zeros(1, dtype=np.int32)
+    rbuf = np.ascontiguousarray(br, dtype=np.int32) if R else np.zeros(1, dtype=np.int32)
+    bbuf = None
+    if base is not None:
+        bs = np.asarray(base).reshape(-1)
+        if bs.shape != (max(int(ds[-1]), 0),):
+            raise ValueError(f"base must hold one value per dir ({int(ds[-1])}), got {bs.shape[0]}")
+        if bs.size and (bs.dtype.kind not in "ui" or (bs.dtype.kind == "i" and (bs < 0).any())):
+            raise ValueError("bases must be integers >= 0")
+        bbuf = np.ascontiguousarray(bs, dtype=np.uint64) if bs.size else np.zeros(1, dtype=np.uint64)
+    stats = np.zeros(10, dtype=np.int64)
+    per = np.zeros((B, 8), dtype=np.uint64)
+    placed, n, status = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    pbytes, moved, before, after = (C.c_uint64(0) for _ in range(4))
+    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    _check(_ffi.load().kao_place_logdirs(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, rbuf.ctypes.data_as(i32p),
+                                         dbuf.ctypes.data_as(i32p), sbuf.ctypes.data_as(u64p), int(bool(move_residents)), int(min_gain), int(max_rounds),
+                                         int(bool(dry_run)), C.byref(placed), C.byref(pbytes), C.byref(n), C.byref(moved), C.byref(before), C.byref(after),
+                                         per.ctypes.data_as(u64p), C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_place_logdirs")
+    return PlaceLogDirsResult(dir=d, n_placed=int(placed.value), bytes_placed=int(pbytes.value), n_moved=int(n.value), bytes_moved=int(moved.value),
+                              peak_before=int(before.value), peak_after=int(after.value), per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
 
 
 @dataclass
@@ -264,6 +335,203 @@ def report_lines(plan: LogDirsPlan) -> List[str]:
     return out
 
 
+# ---- placement: log dirs for the replicas a plan brings to a broker and for those of an evacuated dir ----------
+@dataclass
+class PlaceInput:
+    """The documents as the arrays of kao_place_logdirs (the mapping is that of cli/kao-logdirs --plan / --evacuate)."""
+    broker_ids: List[int]                 # dense broker index -> broker id
+    dir_names: List[List[str]]            # per broker: its usable dirs without the evacuated ones, byte-wise ascending
+    skipped: List[int]                    # per broker: dirs left out for their error
+    evacuated: List[int]                  # per broker: dirs that are being evacuated
+    stranded: List[int]                   # per broker: bytes of the entries of its evacuated dirs that are not planned
+    dir_start: np.ndarray                 # [B + 1] int32
+    base: np.ndarray                      # [n_dirs] uint64
+    broker: np.ndarray                    # [R] int32
+    dir: np.ndarray                       # [R] int32, -1 = homeless
+    size: np.ndarray                      # [R] uint64
+    slots: List[Tuple[int, int]]          # per replica: (index into keys, slot of the row)
+    keys: List[Tuple[str, int]]           # (topic, partition) ascending
+    rows: List[List[int]]                 # per key: the plan's row where there is one, else the row of --current
+    planned: List[bool]                   # per key: the plan lists it
+
+
+def parse_place_input(current_doc: dict, log_dirs, plan_doc: Optional[dict] = None, evacuate: Sequence[Tuple[int, str]] = (),
+                      broker_list: Optional[Sequence[int]] = None, default_size: Optional[int] = None) -> PlaceInput:
+    """parse_input's mapping with a plan and evacuations.  The plan is a reassignment document for a subset of the partitions of the
+    current one; for a planned partition its row decides.  A broker of the row that the current row lacks gets an ARRIVAL: a homeless
+    replica whose size is the largest non-future size of the partition in the whole log-dirs document (default_size without one),
+    provided the broker is in the list and has a usable dir.  A broker of the current row that the plan's row lacks is a DEPARTURE:
+    its entry counts neither as a replica nor as base (the result is made for the end state; Kafka keeps the old copy until the new
+    one is in sync).  An evacuated dir leaves its broker's dir list; its non-future entries of partitions whose row still holds the
+    broker become homeless there, its other entries are stranded: neither planned nor counted."""
+    from .waves import _entries
+    table = log_dirs if isinstance(log_dirs, dict) and "brokers" not in log_dirs else parse_log_dirs(log_dirs)
+    ids = sorted(table) if broker_list is None else [int(b) for b in broker_list]
+    if not ids:
+        raise ValueError("empty broker list")
+    if len(set(ids)) != len(ids):
+        raise ValueError("duplicate id in broker list")
+    dense = {b: i for i, b in enumerate(ids)}
+    by_key = _entries(current_doc, "current")
+    plan = _entries(plan_doc, "plan") if plan_doc is not None else {}
+    for key, row in plan.items():
+        if key not in by_key:
+            raise ValueError(f"plan: partition {key[0]}-{key[1]} is not in the current assignment")
+        if len(set(row)) != len(row):
+            raise ValueError(f"plan: partition {key[0]}-{key[1]} lists a broker twice")
+    keys = sorted(by_key, key=lambda k: (k[0].encode(), k[1]))
+    out_of: List[set] = [set() for _ in ids]
+    for b, name in evacuate:
+        i = dense.get(int(b))
+        d = table.get(int(b), {}).get(name) if i is not None else None
+        if d is None or d.error is not None:
+            raise ValueError(f"evacuate: {b}:{name} is not a usable log dir of a listed broker")
+        out_of[i].add(name)
+    psize: Dict[Tuple[str, int], int] = {}   # the largest non-future size of a partition anywhere: the size of an arrival
+    for dirs in table.values():
+        for d in dirs.values():
+            for topic, part, sz, fut in d.entries:
+                if not fut:
+                    psize[(topic, part)] = max(psize.get((topic, part), 0), sz)
+    names, skipped, dir_start = [], [], [0]
+    where: List[Dict[Tuple[str, int], Tuple[int, int]]] = []   # per broker: partition -> (global dir, size) of its non-future entry in a dir that stays
+    leaving: List[Dict[Tuple[str, int], int]] = []             # ... -> size of its non-future entry in an evacuated dir
+    for i, b in enumerate(ids):
+        dirs = table.get(b, {})
+        usable = sorted((n for n, d in dirs.items() if d.error is None), key=lambda n: n.encode())
+        stay = [n for n in usable if n not in out_of[i]]
+        if out_of[i] and not stay:
+            raise ValueError(f"evacuate: broker {b} is left without a usable log dir")
+        names.append(stay)
+        skipped.append(len(dirs) - len(usable))
+        at: Dict[Tuple[str, int], Tuple[int, int]] = {}
+        gone: Dict[Tuple[str, int], int] = {}
+        for n in usable:
+            for topic, part, sz, fut in dirs[n].entries:
+                if fut:
+                    continue
+                if (topic, part) in at or (topic, part) in gone:
+                    raise ValueError(f"log-dirs: broker {b} holds partition {topic}-{part} twice")
+                if n in out_of[i]:
+                    gone[(topic, part)] = sz
+                else:
+                    at[(topic, part)] = (dir_start[-1] + stay.index(n), sz)
+        where.append(at)
+        leaving.append(gone)
+        dir_start.append(dir_start[-1] + len(stay))
+    rbroker, rdir, rsize, slots, claimed, rescued, departed = [], [], [], [], set(), set(), set()
+    rows = [plan.get(k, by_key[k]) for k in keys]
+    for k, key in enumerate(keys):
+        was = set(by_key[key])
+        for x in was - set(rows[k]):
+            if x in dense:
+                departed.add((dense[x], key))
+        for j, x in enumerate(rows[k]):
+            i = dense.get(x)
+            if i is None:
+                continue
+            if key in leaving[i]:                       # its dir is being evacuated
+                d, sz = -1, leaving[i][key]
+                rescued.add((i, key))
+            elif x in was:
+                if key not in where[i]:
+                    continue
+                d, sz = where[i][key]
+                claimed.add((i, key))
+            else:                                       # an arrival
+                if not names[i]:
+                    continue
+                if key in psize:
+                    d, sz = -1, psize[key]
+                elif default_size is not None:
+                    d, sz = -1, int(default_size)
+                else:
+                    raise ValueError(f"log-dirs: no size for partition {key[0]}-{key[1]}, which the plan brings to broker {x} (give a default size)")
+            rbroker.append(i)
+            rdir.append(d)
+            rsize.append(sz)
+            slots.append((k, j))
+    base = [0] * dir_start[-1]
+    stranded = [0] * len(ids)
+    for i, b in enumerate(ids):
+        for li, n in enumerate(names[i]):
+            for topic, part, sz, fut in table[b][n].entries:
+                if not fut and (i, (topic, part)) in departed:
+                    continue
+                if fut or (i, (topic, part)) not in claimed:
+                    base[dir_start[i] + li] += sz
+        for n in out_of[i]:
+            for topic, part, sz, fut in table[b][n].entries:
+                if fut or (i, (topic, part)) not in rescued:
+                    stranded[i] += sz
+    return PlaceInput(broker_ids=ids, dir_names=names, skipped=skipped, evacuated=[len(s) for s in out_of], stranded=stranded,
+                      dir_start=np.asarray(dir_start, dtype=np.int32), base=np.asarray(base, dtype=np.uint64).reshape(-1),
+                      broker=np.asarray(rbroker, dtype=np.int32).reshape(-1), dir=np.asarray(rdir, dtype=np.int32).reshape(-1),
+                      size=np.asarray(rsize, dtype=np.uint64).reshape(-1), slots=slots, keys=keys, rows=rows, planned=[k in plan for k in keys])
+
+
+@dataclass
+class PlaceLogDirsPlan:
+    result: PlaceLogDirsResult
+    input: PlaceInput
+    entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs)
+
+    def document(self) -> dict:
+        """The reassignment document: the partitions of the plan and those with a placed or moved replica, each with its log_dirs."""
+        return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": r, "log_dirs": d} for t, p, r, d in self.entries]}
+
+    def text(self) -> str:
+        """The document byte for byte as cli/kao-logdirs writes it."""
+        return LogDirsPlan.text(self)
+
+    def report_lines(self) -> List[str]:
+        return place_report_lines(self)
+
+
+def place_input(pi: PlaceInput, rebalance: bool = False, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> PlaceLogDirsPlan:
+    """kao_place_logdirs on a PlaceInput; the entries are the partitions of the plan and those with a placed or moved replica, the
+    dir's name in the slot of such a replica and "any" in every other (no entry with dry_run)."""
+    res = place_logdirs_arrays(pi.dir_start, pi.broker, pi.dir, pi.size, pi.base, rebalance, min_gain, max_rounds, dry_run)
+    entries = []
+    if not dry_run:
+        flat = [n for names in pi.dir_names for n in names]
+        lists: Dict[int, List[str]] = {k: ["any"] * len(pi.rows[k]) for k in range(len(pi.keys)) if pi.planned[k]}
+        for r in np.nonzero(res.dir != pi.dir)[0]:
+            k, j = pi.slots[int(r)]
+            lists.setdefault(k, ["any"] * len(pi.rows[k]))[j] = flat[int(res.dir[r])]
+        entries = [(pi.keys[k][0], pi.keys[k][1], list(pi.rows[k]), lists[k]) for k in sorted(lists)]
+    return PlaceLogDirsPlan(result=res, input=pi, entries=entries)
+
+
+def place_logdirs(current_doc: dict, log_dirs, plan_doc: Optional[dict] = None, evacuate: Sequence[Tuple[int, str]] = (),
+                  broker_list: Optional[Sequence[int]] = None, rebalance: bool = False, min_gain: int = 0, max_rounds: int = 0,
+                  default_size: Optional[int] = None, dry_run: bool = False) -> PlaceLogDirsPlan:
+    """kao_place_logdirs on a reassignment document, the `kafka-log-dirs --describe` output of its cluster, a plan for some of its
+    partitions and a list of (broker id, dir name) to evacuate: every replica the plan brings to a listed broker and every replica
+    of an evacuated dir gets a dir by name; with rebalance the residents may move as well (the rounds of balance_logdirs)."""
+    return place_input(parse_place_input(current_doc, log_dirs, plan_doc, evacuate, broker_list, default_size), rebalance, min_gain, max_rounds, dry_run)
+
+
+def place_report_lines(plan: PlaceLogDirsPlan) -> List[str]:
+    """The --report text of a placement, line for line as cli/kao-logdirs prints it: one line per broker, one for the call."""
+    res, pi, s = plan.result, plan.input, plan.result.stats
+    B = len(pi.broker_ids)
+    homeless = np.bincount(pi.broker[pi.dir < 0], minlength=B) if len(pi.dir) else np.zeros(B, dtype=np.int64)
+    residents = np.bincount(pi.broker[pi.dir >= 0], minlength=B) if len(pi.dir) else np.zeros(B, dtype=np.int64)
+    out = []
+    for i, b in enumerate(pi.broker_ids):
+        p = [int(x) for x in res.per_broker[i]]
+        out.append(f"logdirs: broker={b} dirs={len(pi.dir_names[i])} skipped_dirs={pi.skipped[i]} evacuated_dirs={pi.evacuated[i]} "
+                   f"replicas={int(residents[i] + homeless[i])} residents={int(residents[i])} homeless={int(homeless[i])} peak_before={p[0]} peak_after={p[1]} "
+                   f"lower_bound={p[2]} placed={p[3]} bytes_placed={p[4]} moved={p[5]} bytes_moved={p[6]} rounds={p[7]} stranded_bytes={pi.stranded[i]}")
+    total = sum(int(x) for x in pi.size) + sum(int(x) for x in pi.base)
+    out.append(f"logdirs: status={res.status} brokers={B} dirs={int(pi.dir_start[-1])} skipped_dirs={sum(pi.skipped)} evacuated_dirs={sum(pi.evacuated)} "
+               f"replicas={len(pi.dir)} residents={int(residents.sum())} homeless={int(homeless.sum())} peak_before={res.peak_before} peak_after={res.peak_after} "
+               f"replicas_placed={res.n_placed} bytes_placed={res.bytes_placed} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
+               f"stranded_bytes={sum(pi.stranded)} " + " ".join(f"{k}={int(v)}" for k, v in zip(PLACE_STAT_KEYS, s)))
+    return out
+
+
 def main(argv=None) -> int:
     """Python twin of cli/kao-logdirs: same flags, same bytes, same exit status (0 ok, 1 error, 2 usage)."""
     from ._plan_args import count
@@ -275,14 +543,28 @@ def main(argv=None) -> int:
     ap.add_argument("--min-gain", default=None, help="move only to close a gap of more than N bytes (N, or N with K/M/G/T)")
     ap.add_argument("--max-rounds", type=count, default=0, help="stop every broker after N rounds")
     ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
+    ap.add_argument("--plan", default=None, help="reassignment JSON for some partitions of --current: its arrivals get a log dir")
+    ap.add_argument("--evacuate", action="append", default=[], metavar="BROKER:DIR", help="empty this log dir into the broker's others (repeatable)")
+    ap.add_argument("--rebalance", action="store_true", help="with --plan / --evacuate: the resident replicas may move as well")
+    ap.add_argument("--default-size", default=None, help="with --plan / --evacuate: size of an arrival that --log-dirs does not list (N, or N with K/M/G/T)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
-    min_gain = 0
+    min_gain, default_size, evacuate = 0, None, []
+    placing = a.plan is not None or bool(a.evacuate)
+    if (a.rebalance or a.default_size is not None) and not placing:
+        ap.error("--rebalance and --default-size need --plan or --evacuate")
     try:
         if a.min_gain is not None:
             min_gain = parse_bytes(a.min_gain)
+        if a.default_size is not None:
+            default_size = parse_bytes(a.default_size)
+        for item in a.evacuate:
+            b, colon, name = item.partition(":")
+            if not colon or not name or not (b[1:] if b.startswith("-") else b).isdigit() or len(b) > 10:
+                raise ValueError("--evacuate needs BROKER:DIR")
+            evacuate.append((int(b), name))
     except ValueError as e:
         ap.error(str(e))
     try:
@@ -291,12 +573,21 @@ def main(argv=None) -> int:
         with open(a.log_dirs) as f:
             text = f.read()
         ids = None if a.broker_list is None else [int(b) for b in a.broker_list.split(",") if b]
-        li = parse_input(doc, text, ids)   # input errors before the device is touched
         from .solver import init
-        init(a.device)
-        plan = plan_input(li, min_gain, a.max_rounds, a.dry_run)
+        if placing:
+            plan_doc = None
+            if a.plan is not None:
+                with open(a.plan) as f:
+                    plan_doc = json.load(f)
+            pi = parse_place_input(doc, text, plan_doc, evacuate, ids, default_size)   # input errors before the device is touched
+            init(a.device)
+            plan = place_input(pi, a.rebalance, min_gain, a.max_rounds, a.dry_run)
+        else:
+            li = parse_input(doc, text, ids)   # input errors before the device is touched
+            init(a.device)
+            plan = plan_input(li, min_gain, a.max_rounds, a.dry_run)
         if a.report:
-            for line in report_lines(plan):
+            for line in plan.report_lines():
                 print(line, file=sys.stderr)
         with open(a.out, "w") as f:
             f.write(plan.text())

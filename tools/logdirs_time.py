@@ -6,7 +6,16 @@ bytes moved, the bytes stored, the stats (rounds summed and of the slowest broke
 time of the call with dry_run (median of --reps after one warm-up; it includes the host validation, the upload and the read-back of
 the counters and of per_broker, and ends in a stream synchronise).  --ref times the numpy restatement on the single-broker case as
 well, on one host core.  For kernel times run it under `rocprofv3 --kernel-trace --stats --` (in a run of its own, --reps 1).
-Writes the lines to profiles/logdirs_time.txt with --write."""
+Writes the lines to profiles/logdirs_time.txt with --write.
+
+--place times kao_place_logdirs instead, on the same family with a third of each broker's replicas homeless:
+1000 x 12 x (200 residents + 100 homeless), 100 x 24 x (2,000 + 1,000) and one broker x 12 x (0 + 2,500), each at both sigmas and
+both values of move_residents.  Per line the peak before and after, the peak that Kafka's own rule gives on the same arrivals (each,
+in array order, to the dir with the fewest partitions, ties to the lowest index; computed here on the host), peak / bound worst and
+mean, the brokers proven, the rounds and the wall time as above; beside it the wall time of kao_balance_logdirs on the same brokers
+with the arrivals already resident where Kafka's rule put them, and with --ref that of the numpy restatement (tests/place_ref.py) on
+one host core.  The last lines time the single broker with its 2,500 replicas resident and nothing to place: the difference to the
+line with 2,500 homeless replicas is what compaction, sort and the greedy pass cost.  Writes profiles/place_time.txt with --write."""
 import argparse
 import json
 import os
@@ -18,6 +27,79 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SHAPES = {"cluster": (1000, 12, 300), "dense": (100, 24, 3000), "one": (1, 12, 2500)}   # brokers, dirs a broker, replicas a broker
+HOMELESS = {"cluster": 100, "dense": 1000, "one": 2500}                                 # --place: of those, homeless
+
+
+def kafka_rule(np, B, n, broker, local, home):
+    """[R] the dir inside its broker that Kafka gives every homeless replica: in array order, the dir with the fewest partitions."""
+    counts = np.zeros((B, n), dtype=np.int64)
+    np.add.at(counts, (broker[~home], local[~home]), 1)
+    out = local.copy()
+    idx = np.nonzero(home)[0]
+    order = idx[np.argsort(broker[idx], kind="stable")]            # by broker, array order inside
+    per = np.bincount(broker[idx], minlength=B)
+    start = np.concatenate([[0], np.cumsum(per)])
+    for j in range(int(per.max(initial=0))):                        # the j-th arrival of every broker that has one
+        bs = np.nonzero(per > j)[0]
+        r = order[start[bs] + j]
+        c = np.argmin(counts[bs], axis=1)
+        counts[bs, c] += 1
+        out[r] = c
+    return out
+
+
+def time_place(a, np, lr):
+    import place_ref as pr
+    from kafka_assignment_optimizer_amd.logdirs import PLACE_STAT_KEYS, balance_logdirs_arrays, place_logdirs_arrays
+
+    def timed(fn):
+        fn()   # warm-up
+        ms = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            res = fn()
+            ms.append(round(1e3 * (time.perf_counter() - t0), 3))
+        return res, ms
+
+    lines = []
+    cases = [(name, HOMELESS[name]) for name in a.cases.split(",")] + ([("one", 0)] if "one" in a.cases.split(",") else [])
+    for name, h in cases:
+        B, n, k = SHAPES[name]
+        for sigma in (float(s) for s in a.sigmas.split(",")):
+            c = lr.lognormal_case(B, n, k, sigma, 11, zeros=0.0)
+            broker, local = c["dir"] // n, c["dir"] % n
+            rank = np.empty(len(broker), dtype=np.int64)           # the place of a replica among its broker's, in array order
+            order = np.argsort(broker, kind="stable")
+            rank[order] = np.arange(len(broker)) - np.repeat(np.arange(B) * k, k)
+            home = rank >= k - h
+            d = np.where(home, -1, c["dir"])
+            kafka = kafka_rule(np, B, n, broker, local, home) + n * broker
+            kafka_peak = int(lr.loads(c["dir_start"], kafka, c["size"], c["base"]).max())
+            _, bal_ms = timed(lambda: balance_logdirs_arrays(c["dir_start"], kafka, c["size"], c["base"], dry_run=True))
+            for move in (False, True):
+                args = (c["dir_start"], broker, d, c["size"], c["base"], move)
+                res, ms = timed(lambda: place_logdirs_arrays(*args, dry_run=True))
+                per = res.per_broker.astype(np.float64)
+                ratio = per[:, 1] / np.maximum(per[:, 2], 1)
+                line = {"workload": name, "sigma": sigma, "brokers": B, "dirs_per_broker": n, "residents_per_broker": k - h, "homeless_per_broker": h,
+                        "move_residents": move, "status": res.status, "peak_before": res.peak_before, "peak_after": res.peak_after, "peak_kafka_rule": kafka_peak,
+                        "peak_over_bound_worst": round(float(ratio.max()), 5), "peak_over_bound_mean": round(float(ratio.mean()), 5),
+                        "largest_replica": int(c["size"].max()), "replicas_placed": res.n_placed, "bytes_placed": res.bytes_placed, "replicas_moved": res.n_moved,
+                        "bytes_moved": res.bytes_moved}
+                line.update({key: int(v) for key, v in zip(PLACE_STAT_KEYS, res.stats)})
+                line["wall_ms"] = ms
+                line["wall_ms_median"] = round(float(np.median(ms)), 3)
+                line["balance_after_kafka_rule_wall_ms_median"] = round(float(np.median(bal_ms)), 3)
+                if a.ref:
+                    t0 = time.perf_counter()
+                    ref = pr.place(*args)
+                    line["restatement_one_core_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+                    assert ref["dir"].tobytes() == place_logdirs_arrays(*args).dir.astype(np.int64).tobytes()
+                lines.append(json.dumps(line))
+                print(lines[-1], flush=True)
+    if a.write:
+        with open(os.path.join(ROOT, "profiles", "place_time.txt"), "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 def main():
@@ -26,13 +108,16 @@ def main():
     ap.add_argument("--cases", default="cluster,dense,one")
     ap.add_argument("--sigmas", default="0.7,1.5")
     ap.add_argument("--ref", action="store_true", help="time tests/logdirs_ref.descend on the single-broker case too")
-    ap.add_argument("--write", action="store_true", help="write the lines to profiles/logdirs_time.txt as well")
+    ap.add_argument("--write", action="store_true", help="write the lines to profiles/logdirs_time.txt (profiles/place_time.txt with --place) as well")
+    ap.add_argument("--place", action="store_true", help="time kao_place_logdirs instead (see the head of this file)")
     a = ap.parse_args()
     import numpy as np
     import kafka_assignment_optimizer_amd as kao
     from kafka_assignment_optimizer_amd.logdirs import STAT_KEYS, balance_logdirs_arrays
     import logdirs_ref as lr
     kao.init(0)
+    if a.place:
+        return time_place(a, np, lr)
     lines = []
     for name in a.cases.split(","):
         B, n, k = SHAPES[name]
