@@ -1,9 +1,9 @@
 // kao-disk -- disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk, DESIGN.md
-// section 4m; under --max-bytes kao_balance_disk_budget, section 4n).
+// section 4m; under --max-bytes kao_balance_disk_budget, section 4n; with --capacities kao_balance_disk_capacity, section 4q).
 //
 //   kao-disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt [--default-size N]
 //            [--max-per-rack N] [--keep-leaders] [--min-gain BYTES] [--max-bytes BYTES] [--max-rounds N] [--dry-run] --out plan.json
-//            [--report] [--device D]
+//            [--capacities caps.json | id:bytes,...] [--default-capacity BYTES] [--report] [--device D]
 //
 // Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
 // output or a sizes document, as kao-waves reads them) and moves replicas to brokers outside their row until no single move closes a
@@ -15,6 +15,10 @@
 // --dry-run reports and leaves the plan empty.  --max-bytes N caps the bytes the whole plan copies: a move that would copy more than
 // what is left of N is no candidate, and of a round's winners the heaviest sources are served first; the report line then ends in
 // max_bytes, bytes_left, refused (winners the budget turned down) and budget_bound (1: the budget is what stopped the descent).
+// --capacities (a JSON file {"<brokerId>": bytes} or id:bytes,id:bytes; a value is a number or a string with K/M/G/T) gives every
+// broker its disk size, --default-capacity N that of the brokers the table does not name; a broker of --broker-list without either
+// is a usage error.  The moves then lower the peak UTILISATION S(b) / capacity(b), the answer for brokers with unequal disks, and the
+// report line ends in peak_before_ppm, peak_after_ppm, lower_bound_ppm (parts per million, rounded down) and thorough_rounds.
 // All computation happens in libkao.so on the GPU.
 // Exit status: 0 = ok, 1 = error, 2 = usage.
 #include <algorithm>
@@ -39,18 +43,54 @@ namespace {
         "usage: kao-disk --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
         "                --sizes <kafka-log-dirs output | sizes.json> [--default-size N] [--max-per-rack N] [--keep-leaders]\n"
         "                [--min-gain N[K|M|G|T]] [--max-bytes N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report]\n"
-        "                [--device D]\n"
+        "                [--capacities <caps.json | id:bytes,...>] [--default-capacity N[K|M|G|T]] [--device D]\n"
         "writes the partitions whose replicas move; exit status: 0 = ok, 1 = error, 2 = usage\n");
     std::exit(2);
+}
+
+// --capacities: id:bytes,id:bytes or a JSON file {"<brokerId>": bytes}, a value a number or a string, each N or N with K/M/G/T
+std::map<int, uint64_t> read_capacities(const std::string &arg) {
+    std::map<int, uint64_t> out;
+    auto put = [&](const std::string &id, const std::string &text) {
+        uint64_t v = 0;
+        if (id.empty() || id.find_first_not_of("0123456789") != std::string::npos || !parse_bytes(text, v))
+            throw std::runtime_error("capacity of broker " + id + ": not a byte count: " + text);
+        out[std::atoi(id.c_str())] = v;
+    };
+    if (arg.find(':') != std::string::npos && arg.find('{') == std::string::npos && (arg.size() < 5 || arg.compare(arg.size() - 5, 5, ".json") != 0)) {
+        for (auto &t : split(arg, ',')) {
+            if (t.empty()) continue;
+            auto kv = split(t, ':');
+            if (kv.size() != 2) throw std::runtime_error("bad --capacities entry " + t);
+            put(kv[0], kv[1]);
+        }
+    } else {
+        const std::string txt = slurp(arg);
+        const JValue doc = JParser(txt).parse();
+        if (doc.kind != JValue::Obj) throw std::runtime_error("capacities file must be a JSON object {\"<brokerId>\": bytes}");
+        for (auto &kv : doc.obj) {
+            if (kv.second.kind != JValue::Num && kv.second.kind != JValue::Str) throw std::runtime_error("capacity of broker " + kv.first + ": not a byte count");
+            put(kv.first, kv.second.kind == JValue::Num ? kv.second.raw : kv.second.str);
+        }
+    }
+    return out;
+}
+
+// floor(num * 10^6 / den) in decimal; the product passes 64 bits
+std::string ppm(uint64_t num, uint64_t den) {
+    unsigned __int128 v = (unsigned __int128)num * 1000000u / den;
+    std::string s;
+    do { s.insert(s.begin(), (char)('0' + (int)(v % 10))); v /= 10; } while (v);
+    return s;
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path;
+    std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path, caps_arg;
     int device = 0, max_per_rack = 0, max_rounds = 0;
-    bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false;
-    uint64_t default_size = 0, min_gain = 0, max_bytes = 0;
+    bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false, have_caps = false, have_default_cap = false;
+    uint64_t default_size = 0, min_gain = 0, max_bytes = 0, default_cap = 0;
     auto count_arg = [](const std::string &v, const char *msg) {
         if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
         return std::atoi(v.c_str());
@@ -75,6 +115,12 @@ int main(int argc, char **argv) {
         } else if (a == "--max-bytes") {
             if (!parse_bytes(need("--max-bytes"), max_bytes)) usage("--max-bytes needs a byte count (N, or N with K/M/G/T)");
             have_budget = true;
+        } else if (a == "--capacities") {
+            caps_arg = need("--capacities");
+            have_caps = true;
+        } else if (a == "--default-capacity") {
+            if (!parse_bytes(need("--default-capacity"), default_cap)) usage("--default-capacity needs a byte count (N, or N with K/M/G/T)");
+            have_default_cap = true;
         } else if (a == "--max-per-rack") max_per_rack = count_arg(need("--max-per-rack"), "--max-per-rack needs a value >= 0");
         else if (a == "--max-rounds") max_rounds = count_arg(need("--max-rounds"), "--max-rounds needs a value >= 0");
         else if (a == "-h" || a == "--help") usage(nullptr);
@@ -82,6 +128,31 @@ int main(int argc, char **argv) {
     }
     if (cur_path.empty() || brokers_csv.empty() || racks_arg.empty() || sizes_path.empty() || out_path.empty())
         usage("--current, --broker-list, --racks, --sizes and --out are required");
+    const bool by_capacity = have_caps || have_default_cap;
+    std::vector<uint64_t> capacity;   // per broker of --broker-list, in its order
+    if (by_capacity) {                // a broker without a capacity is a usage error
+        std::string msg;
+        try {
+            const std::map<int, uint64_t> table = have_caps ? read_capacities(caps_arg) : std::map<int, uint64_t>();
+            std::vector<std::string> missing;
+            for (auto &t : split(brokers_csv, ',')) {
+                if (t.empty()) continue;
+                auto it = table.find(std::atoi(t.c_str()));
+                if (it != table.end()) capacity.push_back(it->second);
+                else if (have_default_cap) capacity.push_back(default_cap);
+                else missing.push_back(std::to_string(std::atoi(t.c_str())));
+            }
+            if (!missing.empty()) {
+                msg = "no capacity for brokers ";
+                for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + missing[i];
+                if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
+                msg += " (give them in --capacities or set --default-capacity)";
+            }
+        } catch (const std::exception &e) {
+            msg = std::string("--capacities: ") + e.what();
+        }
+        if (!msg.empty()) usage(msg.c_str());
+    }
     try {
         const Cluster cl = read_cluster(brokers_csv, racks_arg);
         const ClusterRows cr = read_rows(cur_path, cl);
@@ -108,28 +179,37 @@ int main(int argc, char **argv) {
 
         std::vector<uint16_t> rows = cr.rows;
         int32_t n_moved = 0, status = 0;
-        uint64_t bytes_moved = 0, before = 0, after = 0, bound = 0;
-        int64_t stats[10] = {0};
-        if (have_budget)
+        uint64_t bytes_moved = 0, before = 0, after = 0, bound = 0, before2[2] = {0, 1}, after2[2] = {0, 1}, bound2[2] = {0, 1};
+        int64_t stats[11] = {0};
+        const char *entry = by_capacity ? "kao_balance_disk_capacity: " : have_budget ? "kao_balance_disk_budget: " : "kao_balance_disk: ";
+        if (by_capacity) {
+            rc = kao_balance_disk_capacity(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), capacity.data(), max_per_rack,
+                                           keep_leaders ? 0 : 1, min_gain, have_budget ? max_bytes : UINT64_MAX, max_rounds, dry_run ? 1 : 0, &n_moved,
+                                           &bytes_moved, before2, after2, bound2, &status, stats);
+            before = before2[0]; after = after2[0]; bound = bound2[0];
+        } else if (have_budget)
             rc = kao_balance_disk_budget(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1,
                                          min_gain, max_bytes, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
         else
             rc = kao_balance_disk(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1, min_gain,
                                   max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
-        if (rc) throw std::runtime_error(std::string(have_budget ? "kao_balance_disk_budget: " : "kao_balance_disk: ") + kao_strerror(rc) + " " + kao_last_error());
+        if (rc) throw std::runtime_error(std::string(entry) + kao_strerror(rc) + " " + kao_last_error());
         if (report) {
-            static const char *const terms[3] = {"largest_partition", "mean_load", "fixed_leaders"};
+            static const char *const terms[4] = {"largest_partition", "mean_load", "fixed_leaders", "integrality"};
             unsigned long long total = 0;
             for (int p = 0; p < P; ++p)
                 for (int j = 0; j < W && cr.rows[(size_t)p * W + j] != KAO_NONE; ++j) total += size[(size_t)p];
             std::fprintf(stderr, "disk: status=%s peak_before=%llu peak_after=%llu lower_bound=%llu bound_term=%s replicas_moved=%d bytes_moved=%llu "
                                  "bytes_total=%llu rows_changed=%lld brokers_changed=%lld rounds=%lld moves=%lld launches=%lld",
                          status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", (unsigned long long)before, (unsigned long long)after,
-                         (unsigned long long)bound, terms[stats[6] >= 0 && stats[6] < 3 ? stats[6] : 0], n_moved, (unsigned long long)bytes_moved, total,
+                         (unsigned long long)bound, terms[stats[6] >= 0 && stats[6] < 4 ? stats[6] : 0], n_moved, (unsigned long long)bytes_moved, total,
                          (long long)stats[4], (long long)stats[7], (long long)stats[0], (long long)stats[1], (long long)stats[3]);
             if (have_budget)
                 std::fprintf(stderr, " max_bytes=%llu bytes_left=%llu refused=%lld budget_bound=%lld", (unsigned long long)max_bytes,
                              (unsigned long long)(max_bytes - bytes_moved), (long long)stats[8], (long long)stats[9]);
+            if (by_capacity)
+                std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s lower_bound_ppm=%s thorough_rounds=%lld", ppm(before2[0], before2[1]).c_str(),
+                             ppm(after2[0], after2[1]).c_str(), ppm(bound2[0], bound2[1]).c_str(), (long long)stats[10]);
             std::fprintf(stderr, "\n");
         }
         const std::string text = changed_rows_text(cr, rows, cl.brokers);

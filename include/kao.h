@@ -694,6 +694,51 @@ int kao_balance_disk_budget(int32_t n_brokers, int32_t n_racks, const uint8_t *r
                             int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
                             uint64_t *lower_bound, int32_t *status, int64_t stats[10] /* may be NULL */);
 
+/* ---- Disk-usage balance by utilisation ---------------------------------------------------------------------
+ * kao_balance_disk_budget for brokers with unequal disks: cap[b] is the bytes of disk broker b has, 1 <= cap[b], the sum of cap[b]
+ * below 2^62, and the peak to lower is that of the UTILISATION u(b) = S(b) / cap(b).  max_bytes is as there (UINT64_MAX: no budget).
+ * Rows, sizes, S(b), admissibility, the rack rule, move_leaders, the movable slots, key, win rule, grant rule, cost / charge / refund,
+ * dry_run and *n_moved / *bytes_moved are those of kao_balance_disk and kao_balance_disk_budget.  Four things change.
+ * UTILISATION is never computed as a quotient: x / cx is above y / cy iff S(x) * cap(y) > S(y) * cap(x) in 128-bit unsigned
+ * arithmetic (both factors stay below 2^62).
+ * RANK: the brokers are ranked by u descending, ties to the lower index; rank 0 is the fullest.
+ * GAIN TEST: a move (p, j, a -> c) passes iff (S(c) + size[p] + min_gain) * cap(a) < S(a) * cap(c); if the 64-bit sum on the left
+ * overflows the move does not pass.  min_gain is any uint64_t, in bytes at the destination.  With equal capacities this is the test
+ * of kao_balance_disk.
+ * TWO KINDS OF ROUND.  A FAST round is the round of kao_balance_disk: the two walks, each stopping at its first admissible (and,
+ * under a budget, affordable) broker, then the test.  With unequal capacities "every later one is heavier" no longer implies that
+ * every later one fails: a fuller but larger broker can pass where the emptiest small one does not.  So once a FAST round has no
+ * proposal every later round is THOROUGH: for slot j on a of rank r the walk goes over the ranks n_brokers-1, n_brokers-2, .., r+1
+ * and proposes the first admissible (and affordable) broker THAT PASSES THE TEST.  (A broker that passes is strictly emptier than a
+ * and so ranks behind it: the walk misses no move.)  The descent ends when a THOROUGH round has no proposal, or after max_rounds
+ * rounds of either kind that had a proposal.
+ * A winner leaves both of its brokers strictly below the old u(a), and winners share no broker: the utilisations sorted descending
+ * fall lexicographically in every round, so the rounds end and the peak utilisation never rises.  (The sum of S^2 may rise: cap 1 /
+ * S 10 -> cap 100 / S 500 with size 10 passes.)  Without a budget and with max_rounds <= 0 the end state is move-stable: no
+ * admissible single move passes the test; under a budget it is stable for the affordable moves.
+ * peak_before[2] / peak_after[2] = {S(b*), cap(b*)} of the broker with the highest utilisation before / after (ties: the lowest
+ * index).  lower_bound[2] = {numerator, denominator} of the largest, compared as fractions (the lowest-numbered on ties), of
+ * (0) {max_p size[p], max_b cap[b]}, (1) {sum of k_p * size[p], sum of cap[b]}, (2) with move_leaders == 0, {fixed(b), cap(b)} of the
+ * broker whose slot-0 bytes fixed(b) have the highest ratio (ties: the lowest index; {0, 1} with move_leaders != 0).
+ * *status = KAO_STATUS_OPTIMAL_PROVEN iff peak_after equals lower_bound as fractions, or the INTEGRALITY test passes: the sum over b
+ * of (ceil(S* * cap(b) / cap*) - 1) is below the sum of k_p * size[p], {S*, cap*} = peak_after, so no placement puts every broker
+ * strictly below the achieved utilisation (with equal capacities: peak == ceil(total / n_brokers)); else
+ * KAO_STATUS_FEASIBLE_BOUND_GAP.
+ * With all cap[b] equal, whatever the common value, the call gives byte for byte the rows of kao_balance_disk and, with a finite
+ * max_bytes, those of kao_balance_disk_budget, the same *n_moved, *bytes_moved, peak_before[0], peak_after[0], *status and
+ * stats[0..2], [4], [5], [7..9], and stats[10] == 0.
+ * stats (may be NULL): [0..9] as for kao_balance_disk_budget; [0] counts the rounds of either kind that had a proposal; [6] is 0, 1 or
+ * 2 as there, or 3 when only the integrality test proves the peak; [9]'s probe is a THOROUGH round without the budget; [10] the
+ * THOROUGH rounds that had a proposal.  Checks, limits and refusals are those of kao_balance_disk, and KAO_ERR_INVALID for
+ * cap == NULL, a cap[b] == 0, or capacities that sum to 2^62 or more. */
+int kao_balance_disk_capacity(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
+                              uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *size /* [n_partitions] */,
+                              const uint64_t *cap /* [n_brokers] */, int32_t max_per_rack /* <= 0: no rack rule */,
+                              int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes /* UINT64_MAX: no budget */,
+                              int32_t max_rounds /* <= 0: no limit */, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                              uint64_t peak_before[2], uint64_t peak_after[2], uint64_t lower_bound[2], int32_t *status,
+                              int64_t stats[11] /* may be NULL */);
+
 /* ---- Log-dir balance inside each broker ---------------------------------------------------------------------
  * Every planner above treats a broker as one disk; a JBOD broker has several log dirs and dies on the fullest of them.  Broker b
  * owns the dirs dir_start[b] .. dir_start[b+1]-1 of ONE global dir index (CSR; n_dirs = dir_start[n_brokers]; a broker may own no

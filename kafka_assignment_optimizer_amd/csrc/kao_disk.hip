@@ -36,11 +36,21 @@
 // charges of all winners of lower source rank plus its own are <= rem (one workgroup, a block scan over the ranks).  APPLY<true>
 // applies the granted winners and adds their costs to spent (one wrapping u64 add per wavefront).  The lowest key of a round has
 // the lowest source rank, so its prefix is its own charge <= rem: every round with a proposal still applies a move.
+//
+// BY UTILISATION (kao_balance_disk_capacity, section 4q) broker b has cap[b] bytes of disk and the peak to lower is that of
+// u(b) = S(b) / cap(b), never computed as a quotient: x / cx is above y / cy iff x * cy > y * cx in 128 bits.  RANK<Cap> ranks by u; the
+// gain test is (S(c) + size + min_gain) * cap(a) < S(a) * cap(c); and "every later one is heavier" no longer means "every later one
+// fails", so once a FAST round (the two walks above) has no proposal every later round is THOROUGH: one walk over the ranks
+// B-1 .. r+1 that takes the first admissible, affordable broker that PASSES the test.  A broker that passes is strictly emptier than
+// a, so it ranks behind a: the THOROUGH walk sees every move there is, and a round of it without a proposal ends the descent.  A
+// winner leaves both of its brokers strictly below the old u(a), so the utilisations sorted descending fall lexicographically.
+// Grant, apply and finish work on ranks and bytes and are the ones above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "kao_host.h"
 #include "kao_plan_dev.h"   // descent_gains, descent_bid, lane_count_to, wave_bytes_code
@@ -49,6 +59,7 @@ namespace {
 
 constexpr int kDkThreads = 256;
 constexpr int kDkBatch = 32;            // rounds enqueued between two reads of the proposal counts
+constexpr int kDkThoroughBatch = 4;     // ... of THOROUGH rounds: few of them have a proposal, and an empty one costs a full walk per slot
 constexpr int kDkHardRounds = 1 << 26;  // no descent gets here; a guard against an endless loop
 constexpr u64 kDkNoKey = ~0ull;
 constexpr int kDkGrantThreads = 1024;   // k_dk_grant: one workgroup, one rank per lane and chunk
@@ -70,7 +81,10 @@ struct DkNet {   // one call; every pointer is device memory
     u64 *ctl;                  // [D_N]
     uint8_t *grant;            // [B] under a budget: the winner that leaves b is applied in this round
     u64 max_bytes;             // the budget; ctl[D_SPENT] = the costs of the moves applied so far
+    const u64 *capacity;       // [B] by utilisation only: the bytes of disk a broker has
 };
+
+typedef unsigned __int128 u128;
 
 __device__ inline void dk_max_to(u64 v, u64 *dst) {   // all 64 lanes active
     for (int off = 32; off > 0; off >>= 1) v = max(v, (u64)__shfl_xor((long long)v, off));
@@ -142,6 +156,33 @@ __global__ __launch_bounds__(kDkThreads) void k_dk_rank(int B, const u64 *__rest
     }
 }
 
+// the same by utilisation: x ranks ahead of b iff load(x) * cap(b) > load(b) * cap(x), or the products are equal and x < b.  Loads and
+// capacities stay below 2^62, so the products fit 128 bits
+__global__ __launch_bounds__(kDkThreads) void k_dk_rank_cap(int B, const u64 *__restrict__ load, const u64 *__restrict__ capacity, int32_t *__restrict__ rank,
+                                                            int32_t *__restrict__ order) {
+    __shared__ u64 tile[kDkThreads], tcap[kDkThreads];
+    const int b = blockIdx.x * kDkThreads + threadIdx.x;
+    const u64 mine = b < B ? load[b] : 0, mcap = b < B ? capacity[b] : 1;
+    int r = 0;
+    for (int base = 0; base < B; base += kDkThreads) {
+        const int cnt = min(kDkThreads, B - base);
+        if ((int)threadIdx.x < cnt) {
+            tile[threadIdx.x] = load[base + threadIdx.x];
+            tcap[threadIdx.x] = capacity[base + threadIdx.x];
+        }
+        __syncthreads();
+        for (int j = 0; j < cnt; ++j) {
+            const u128 theirs = (u128)tile[j] * mcap, ours = (u128)mine * tcap[j];
+            r += (theirs > ours || (theirs == ours && base + j < b)) ? 1 : 0;
+        }
+        __syncthreads();
+    }
+    if (b < B) {   // ranks are a permutation: r < B
+        rank[b] = r;
+        order[r] = b;
+    }
+}
+
 // a row in registers: brokers, their racks (-1 in an empty slot), their ranks
 struct DkRow {
     int b[KAO_MAX_RF], rk[KAO_MAX_RF], rr[KAO_MAX_RF];
@@ -190,7 +231,27 @@ __device__ __forceinline__ int dk_first(const DkNet &n, const DkRow &row, const 
     return -1;
 }
 
+// the gain test of a move a -> c.  By bytes: descent_gains.  By utilisation: (S(c) + w + min_gain) * cap(a) < S(a) * cap(c); S(c) + w
+// stays below 2^63, and a sum that min_gain takes past 2^64 does not pass
+template <bool Cap>
+__device__ __forceinline__ bool dk_gains(const DkNet &n, u64 sa, u64 ca, int c, u64 w) {
+    if (!Cap) return descent_gains(sa, n.load[c], w, n.min_gain);
+    u64 left;
+    if (__builtin_add_overflow(n.load[c] + w, n.min_gain, &left)) return false;
+    return (u128)left * ca < (u128)sa * n.capacity[c];
+}
+
+// THOROUGH: the first admissible (and affordable) broker among the ranks hi, hi - 1, .., lo that passes the gain test; -1 when none does
 template <bool Budget>
+__device__ __forceinline__ int dk_first_gain(const DkNet &n, const DkRow &row, const DkHome &home, bool free, int hi, int lo, int ra, u64 sa, u64 ca, u64 w) {
+    for (int q = hi; q >= lo; --q) {
+        const int c = n.order[q];
+        if (dk_admissible(row, c, n.rack[c], ra, n.cap) && (!Budget || free || dk_home(home, c)) && dk_gains<true>(n, sa, ca, c, w)) return c;
+    }
+    return -1;
+}
+
+template <bool Budget, bool Cap = false, bool Thorough = false>
 __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     bool prop = false;
@@ -225,10 +286,16 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
                 last = ra_rank;
                 const u64 sa = n.load[a];
                 const bool free = !Budget || fits || !dk_home(home, a);
-                int c = dk_first<Budget>(n, row, home, free, n.B - 1 - ra_rank, ra_rank + 1, ra);
-                if (c < 0 || !descent_gains(sa, n.load[c], w, n.min_gain)) {
-                    c = dk_first<Budget>(n, row, home, free, n.B - 1, n.B - ra_rank, ra);
-                    if (c >= 0 && !descent_gains(sa, n.load[c], w, n.min_gain)) c = -1;
+                const u64 ca = Cap ? n.capacity[a] : 0;
+                int c;
+                if (Thorough) {
+                    c = dk_first_gain<Budget>(n, row, home, free, n.B - 1, ra_rank + 1, ra, sa, ca, w);
+                } else {
+                    c = dk_first<Budget>(n, row, home, free, n.B - 1 - ra_rank, ra_rank + 1, ra);
+                    if (c < 0 || !dk_gains<Cap>(n, sa, ca, c, w)) {
+                        c = dk_first<Budget>(n, row, home, free, n.B - 1, n.B - ra_rank, ra);
+                        if (c >= 0 && !dk_gains<Cap>(n, sa, ca, c, w)) c = -1;
+                    }
                 }
                 if (c >= 0) {
                     prop = true;
@@ -392,23 +459,70 @@ int validate_disk(const std::string &fn, int32_t B, int32_t R, const uint8_t *ra
     return KAO_OK;
 }
 
-// both entry points: Budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]
-template <bool Budget>
+// one PROPOSE of the round's kind
+template <bool Budget, bool Cap>
+void dk_propose(const DkNet &n, bool thorough, unsigned blocks, hipStream_t st, int r, uint32_t *count) {
+    if constexpr (Cap) {
+        if (thorough) {
+            k_dk_propose<Budget, true, true><<<blocks, kDkThreads, 0, st>>>(n, r, count);
+            return;
+        }
+    }
+    k_dk_propose<Budget, Cap, false><<<blocks, kDkThreads, 0, st>>>(n, r, count);
+}
+
+// a fraction {numerator, denominator}, compared by the two 128-bit products; every part stays below 2^62 (denominators are >= 1)
+struct DkFrac {
+    uint64_t num, den;
+};
+bool frac_above(const DkFrac &x, const DkFrac &y) { return (u128)x.num * y.den > (u128)y.num * x.den; }
+bool frac_equal(const DkFrac &x, const DkFrac &y) { return (u128)x.num * y.den == (u128)y.num * x.den; }
+
+// {v[b], cap[b]} of the broker with the highest ratio, the lowest index on ties
+DkFrac frac_peak(const std::vector<uint64_t> &v, const uint64_t *cap) {
+    size_t at = 0;
+    for (size_t b = 1; b < v.size(); ++b)
+        if (frac_above({v[b], cap[b]}, {v[at], cap[at]})) at = b;
+    return {v[at], cap[at]};
+}
+
+// the integrality test: the sum over b of ceil(S* cap(b) / cap*) - 1 is below `total`, so no placement puts every broker strictly
+// below the utilisation S* / cap*.  (S* == 0 only when total == 0, and then the peak equals the bound.)
+bool frac_integral(const DkFrac &peak, const uint64_t *cap, int B, uint64_t total) {
+    if (peak.num == 0) return false;
+    u128 sum = 0;
+    for (int b = 0; b < B && sum < total; ++b) sum += ((u128)peak.num * cap[b] + peak.den - 1) / peak.den - 1;   // each term >= 0: the product is >= 1
+    return sum < total;
+}
+
+// the entry points: Budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]; Cap (cap != NULL) is
+// the descent by utilisation: another rank kernel, the capacity form of the test, THOROUGH rounds, fractions as outputs, stats[10]
+template <bool Budget, bool Cap>
 int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
-                 const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes, int32_t max_rounds, int32_t dry_run,
-                 int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *status,
-                 int64_t *stats) {
+                 const uint64_t *size, const uint64_t *cap, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes,
+                 int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                 uint64_t *lower_bound, int32_t *status, int64_t *stats) {
     const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, lower_bound, status};
     int rc = validate_disk(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, outs, 6);
     if (rc) return rc;
+    uint64_t cap_sum = 0, cap_max = 0;
+    if (Cap) {   // 1 <= cap[b], and a sum below 2^62: with the loads below 2^62 every product of the two fits 128 bits
+        for (int b = 0; b < n_brokers; ++b) {
+            if (cap[b] == 0) return fail(KAO_ERR_INVALID, fn + "cap[" + std::to_string(b) + "] is 0");
+            if (__builtin_add_overflow(cap_sum, cap[b], &cap_sum) || cap_sum >= (uint64_t(1) << 62))
+                return fail(KAO_ERR_INVALID, fn + "cap[" + std::to_string(b) + "]: the capacities sum to 2^62 or more");
+            cap_max = std::max(cap_max, cap[b]);
+        }
+    }
     if ((rc = require_init())) return rc;
     const int B = n_brokers, P = n_partitions, W = width, PW = P * W;
 
     // one arena: ctl u64[D_N] | count u32[kDkBatch] | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] |
-    //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B]
+    //            capacity u64[B] | rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B]
     Carve cv;
     const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
-                 o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_rank = cv.take<int32_t>(B), o_order = cv.take<int32_t>(B),
+                 o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_cap = cv.take<u64>(Cap ? B : 0), o_rank = cv.take<int32_t>(B),
+                 o_order = cv.take<int32_t>(B),
                  o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW), o_rows0 = cv.take<uint16_t>(PW),
                  o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B), o_grant = cv.take<uint8_t>(Budget ? B : 0);
     CallBufs m;
@@ -432,8 +546,14 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
         HIP_TRY(hipMemcpyAsync(d_rows, d_rows0, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(m.at<u64>(o_size), size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
+    if (Cap) {
+        n.capacity = m.at<u64>(o_cap);
+        HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), cap, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    } else {
+        n.capacity = nullptr;
+    }
     const unsigned pblocks = grid_for(P, kDkThreads), bblocks = grid_for(B, kDkThreads);
-    int64_t launches = 0, rounds = 0, props = 0;
+    int64_t launches = 0, rounds = 0, props = 0, thorough_rounds = 0;
     bool more = false, open = false;   // open: the budget stopped the descent
     if (P) {
         k_dk_init<<<pblocks, kDkThreads, 0, st>>>(n, d_fixed);
@@ -442,21 +562,27 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
     k_dk_peak0<<<bblocks, kDkThreads, 0, st>>>(n, d_fixed, d_load0);
     ++launches;
     HIP_TRY(hipGetLastError());
+    auto rank = [&] {
+        if (Cap) k_dk_rank_cap<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.capacity, n.rank, n.order);
+        else k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
+    };
 
     if (P) {
         uint32_t cnt[kDkBatch];
+        bool thorough = false;   // by utilisation: a FAST round had no proposal
         for (int r = 0, done = 0; !done;) {
             if (r >= kDkHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
-            const int nb = max_rounds > 0 ? std::min(kDkBatch, max_rounds - r) : kDkBatch;
+            const int batch = thorough ? kDkThoroughBatch : kDkBatch;
+            const int nb = max_rounds > 0 ? std::min(batch, max_rounds - r) : batch;
             HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
-            if (nb == 0) {   // max_rounds rounds have run, every one with a move: is there more to do?
-                k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
-                k_dk_propose<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r, d_cnt);
+            if (nb == 0) {   // max_rounds rounds have run, every one with a move: is there more to do?  (THOROUGH sees every move a FAST round sees)
+                rank();
+                dk_propose<Budget, Cap>(n, Cap, pblocks, st, r, d_cnt);
                 launches += 2;
             }
             for (int i = 0; i < nb; ++i) {
-                k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
-                k_dk_propose<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r + i, d_cnt + i);
+                rank();
+                dk_propose<Budget, Cap>(n, thorough, pblocks, st, r + i, d_cnt + i);
                 if (Budget) k_dk_grant<<<1, kDkGrantThreads, 0, st>>>(n, r + i);
                 k_dk_apply<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r + i);
                 launches += Budget ? 4 : 3;
@@ -465,17 +591,23 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
             HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             if (nb == 0) { more = cnt[0] != 0; break; }
-            for (int i = 0; i < nb && !done; ++i) {   // the first round without a proposal ends the descent; the ones after it changed nothing
-                if (cnt[i] == 0) done = 1;
-                else { ++rounds; props += cnt[i]; }
+            int ran = 0;   // the rounds of the batch before the first one without a proposal; the ones after it changed nothing
+            while (ran < nb && cnt[ran] != 0) props += cnt[ran++];
+            rounds += ran;
+            if (thorough) thorough_rounds += ran;
+            if (ran < nb && Cap && !thorough) {   // the first empty FAST round: THOROUGH from here on.  It and the empty rounds behind it left
+                thorough = true;                  // both minkey rows clear and every key[p] empty, so the count of rounds goes on from `ran`
+                r += ran;
+            } else {
+                done = ran < nb;                  // the first round without a proposal ends the descent
+                r += nb;
             }
-            r += nb;
         }
         if (Budget && !more) {   // no affordable proposal is left: is there one without the budget?  (no row changes: nothing is applied)
             uint32_t left = 0;
             HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof left, st));
-            k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
-            k_dk_propose<false><<<pblocks, kDkThreads, 0, st>>>(n, 0, d_cnt);
+            rank();
+            dk_propose<false, Cap>(n, Cap, pblocks, st, 0, d_cnt);
             launches += 2;
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(&left, d_cnt, sizeof left, hipMemcpyDeviceToHost, st));
@@ -489,24 +621,46 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
     ++launches;
     HIP_TRY(hipGetLastError());
     u64 ctl[D_N];
+    std::vector<uint64_t> h_load0, h_load, h_fixed;   // by utilisation: a maximum over fractions is taken on the host, from one read at the end
     HIP_TRY(hipMemcpyAsync(ctl, n.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    if (Cap) {
+        h_load0.resize(B); h_load.resize(B); h_fixed.resize(B);
+        HIP_TRY(hipMemcpyAsync(h_load0.data(), d_load0, (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_load.data(), n.load, (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_fixed.data(), d_fixed, (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    }
     if (P && !dry_run) HIP_TRY(hipMemcpyAsync(rows, d_rows, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
 
-    const uint64_t terms[3] = {(uint64_t)ctl[D_MAXSIZE], ((uint64_t)ctl[D_TOTAL] + (uint64_t)B - 1) / (uint64_t)B, move_leaders ? 0 : (uint64_t)ctl[D_FIXED]};
-    int which = 0;
-    for (int i = 1; i < 3; ++i)
-        if (terms[i] > terms[which]) which = i;   // the lowest term on ties
     *n_moved = (int32_t)ctl[D_NMOVED];
     *bytes_moved = ctl[D_BYTES];
-    *peak_before = ctl[D_PEAK0];
-    *peak_after = ctl[D_PEAK1];
-    *lower_bound = terms[which];
-    *status = ctl[D_PEAK1] == terms[which] ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    int which = 0;
+    if (Cap) {
+        const DkFrac terms[3] = {{(uint64_t)ctl[D_MAXSIZE], cap_max}, {(uint64_t)ctl[D_TOTAL], cap_sum}, move_leaders ? DkFrac{0, 1} : frac_peak(h_fixed, cap)};
+        for (int i = 1; i < 3; ++i)
+            if (frac_above(terms[i], terms[which])) which = i;   // the lowest term on ties
+        const DkFrac before = frac_peak(h_load0, cap), after = frac_peak(h_load, cap);
+        peak_before[0] = before.num; peak_before[1] = before.den;
+        peak_after[0] = after.num; peak_after[1] = after.den;
+        lower_bound[0] = terms[which].num; lower_bound[1] = terms[which].den;
+        bool proven = frac_equal(after, terms[which]);
+        if (!proven && frac_integral(after, cap, B, (uint64_t)ctl[D_TOTAL])) { proven = true; which = 3; }
+        *status = proven ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    } else {
+        const uint64_t terms[3] = {(uint64_t)ctl[D_MAXSIZE], ((uint64_t)ctl[D_TOTAL] + (uint64_t)B - 1) / (uint64_t)B, move_leaders ? 0 : (uint64_t)ctl[D_FIXED]};
+        for (int i = 1; i < 3; ++i)
+            if (terms[i] > terms[which]) which = i;   // the lowest term on ties
+        *peak_before = ctl[D_PEAK0];
+        *peak_after = ctl[D_PEAK1];
+        *lower_bound = terms[which];
+        *status = ctl[D_PEAK1] == terms[which] ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    }
     if (stats) {
         stats[0] = rounds; stats[1] = (int64_t)ctl[D_MOVES]; stats[2] = props; stats[3] = launches; stats[4] = (int64_t)ctl[D_ROWS];
         stats[5] = more ? 1 : 0; stats[6] = which; stats[7] = (int64_t)ctl[D_BROKERS];
         if (Budget) { stats[8] = (int64_t)ctl[D_REFUSED]; stats[9] = open ? 1 : 0; }
+        else if (Cap) stats[8] = stats[9] = 0;
+        if (Cap) stats[10] = thorough_rounds;
     }
     return KAO_OK;
 }
@@ -517,7 +671,7 @@ extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_
                                 const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, int32_t max_rounds, int32_t dry_run,
                                 int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound,
                                 int32_t *status, int64_t stats[8]) {
-    return balance_disk<false>("kao_balance_disk: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, max_per_rack, move_leaders, min_gain,
+    return balance_disk<false, false>("kao_balance_disk: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain,
                                UINT64_MAX, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
 }
 
@@ -525,6 +679,19 @@ extern "C" int kao_balance_disk_budget(int32_t n_brokers, int32_t n_racks, const
                                        const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes,
                                        int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before,
                                        uint64_t *peak_after, uint64_t *lower_bound, int32_t *status, int64_t stats[10]) {
-    return balance_disk<true>("kao_balance_disk_budget: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, max_per_rack, move_leaders,
+    return balance_disk<true, false>("kao_balance_disk_budget: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders,
                               min_gain, max_bytes, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
+}
+
+extern "C" int kao_balance_disk_capacity(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                                         const uint64_t *size, const uint64_t *cap, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain,
+                                         uint64_t max_bytes, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                                         uint64_t peak_before[2], uint64_t peak_after[2], uint64_t lower_bound[2], int32_t *status, int64_t stats[11]) {
+    const std::string fn = "kao_balance_disk_capacity: ";
+    if (!cap) return fail(KAO_ERR_INVALID, fn + "null pointer");
+    if (max_bytes == UINT64_MAX)   // no budget: no grant kernel, stats[8] = stats[9] = 0
+        return balance_disk<false, true>(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, cap, max_per_rack, move_leaders, min_gain, max_bytes,
+                                         max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
+    return balance_disk<true, true>(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, cap, max_per_rack, move_leaders, min_gain, max_bytes,
+                                    max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
 }

@@ -11,6 +11,9 @@ topics are taken together over one broker index.  The answer is a deterministic 
 peak_after == lower_bound the peak is proven optimal.  The plan holds the changed rows only and is what kao-waves --plan takes.
 --max-bytes N caps the bytes the whole plan copies (kao_balance_disk_budget, section 4n): the same descent, a move that would copy
 more than what is left of N is no candidate, and of a round's winners the heaviest sources are served first.
+--capacities FILE|id:bytes,id:bytes (with --default-capacity N for the brokers it does not name) gives every broker its disk size
+and lowers the peak UTILISATION S(b) / capacity(b) instead (kao_balance_disk_capacity, section 4q): the answer for a cluster whose
+brokers do not have equal disks.  The report line then ends in the three ratios in parts per million and the thorough rounds.
 """
 from __future__ import annotations
 
@@ -31,7 +34,8 @@ from .solver import STATUS_NAMES, _check
 
 STAT_KEYS = ("rounds", "moves", "proposals", "launches", "rows_changed", "stopped_by_max_rounds", "bound_term", "brokers_changed")
 BUDGET_STAT_KEYS = STAT_KEYS + ("refused", "budget_bound")   # kao_balance_disk_budget
-BOUND_TERMS = ("largest_partition", "mean_load", "fixed_leaders")
+CAPACITY_STAT_KEYS = BUDGET_STAT_KEYS + ("thorough_rounds",)   # kao_balance_disk_capacity
+BOUND_TERMS = ("largest_partition", "mean_load", "fixed_leaders", "integrality")
 
 
 @dataclass
@@ -45,6 +49,11 @@ class DiskResult:
     status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound) | "FEASIBLE_BOUND_GAP"
     stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h; int64[10] under a byte budget (BUDGET_STAT_KEYS)
     max_bytes: Optional[int] = None   # the byte budget of the call, None without one
+    # with capacities (kao_balance_disk_capacity): the peaks are {S(b*), cap(b*)} of the broker with the highest utilisation, the bound
+    # is a fraction, stats is int64[11] (CAPACITY_STAT_KEYS); None without capacities
+    peak_before_capacity: Optional[int] = None
+    peak_after_capacity: Optional[int] = None
+    lower_bound_den: Optional[int] = None
 
 
 @dataclass
@@ -69,12 +78,44 @@ def _budget(max_bytes) -> int:
     return int(max_bytes)
 
 
+def _capacity_buffer(capacity, n_brokers: int) -> np.ndarray:
+    """capacity as the C call takes it: one integer >= 1 per broker index, the sum below 2^62; a ValueError otherwise."""
+    values = [v for v in np.asarray(capacity, dtype=object).reshape(-1)]
+    if len(values) != int(n_brokers):
+        raise ValueError(f"capacity must hold one capacity per broker ({n_brokers}), got {len(values)}")
+    if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in values):
+        raise ValueError("capacity: every capacity must be an integer >= 1")
+    if sum(int(v) for v in values) >= 1 << 62:
+        raise ValueError("capacity: the capacities sum to 2^62 or more")
+    return np.array([int(v) for v in values], dtype=np.uint64)
+
+
+def capacity_of(broker_ids: Sequence[int], capacities: Dict[int, object], default_capacity: Optional[int] = None) -> np.ndarray:
+    """capacity[b] over `broker_ids`: {broker id: bytes}, a value an integer or a string with K/M/G/T; a broker the table does not name
+    takes `default_capacity` or is a ValueError (entries of brokers outside the list are ignored, as for the racks)."""
+    from .waves import parse_bytes
+    table = {}
+    for k, v in capacities.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer, str)):
+            raise ValueError(f"capacity of broker {k}: not a byte count: {v!r}")
+        table[int(k)] = parse_bytes(str(int(v)) if not isinstance(v, str) else v)
+    missing = [int(b) for b in broker_ids if int(b) not in table]
+    if missing and default_capacity is None:
+        raise ValueError("no capacity for brokers " + ", ".join(str(b) for b in missing[:5]) + (f" and {len(missing) - 5} more" if len(missing) > 5 else "")
+                         + " (give them in --capacities or set --default-capacity)")
+    return np.array([table.get(int(b), default_capacity) for b in broker_ids], dtype=object)
+
+
 def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0,
-                        max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None) -> DiskResult:
+                        max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None) -> DiskResult:
     """kao_balance_disk on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); size[p] is the bytes of one replica of
-    row p.  With max_bytes (0..2^64-1) it is kao_balance_disk_budget: the moves copy at most that many bytes."""
+    row p.  With max_bytes (0..2^64-1) it is kao_balance_disk_budget: the moves copy at most that many bytes.  With capacity (one
+    value >= 1 per broker index) it is kao_balance_disk_capacity: the peak of S(b) / capacity[b] is what the moves lower."""
     if max_bytes is not None:
         max_bytes = _budget(max_bytes)
+    if capacity is not None:
+        return _balance_disk_capacity(rows, n_brokers, rack_of, n_racks, size, _capacity_buffer(capacity, n_brokers), max_per_rack, move_leaders, min_gain,
+                                      max_rounds, dry_run, max_bytes)
     r, flat, P, W = dense_rows(rows)
     rk = _rack_buffer(rack_of, n_brokers)
     sbuf = weight_buffer(size, P, min_gain)
@@ -93,6 +134,23 @@ def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_p
                       lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes)
 
 
+def _balance_disk_capacity(rows, n_brokers, rack_of, n_racks, size, cbuf, max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes) -> DiskResult:
+    r, flat, P, W = dense_rows(rows)
+    rk = _rack_buffer(rack_of, n_brokers)
+    sbuf = weight_buffer(size, P, min_gain)
+    stats = np.zeros(11, dtype=np.int64)
+    n, status, moved = C.c_int32(0), C.c_int32(0), C.c_uint64(0)
+    before, after, bound = ((C.c_uint64 * 2)() for _ in range(3))
+    _check(_ffi.load().kao_balance_disk_capacity(
+        int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
+        sbuf.ctypes.data_as(C.POINTER(C.c_uint64)), cbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_per_rack), int(bool(move_leaders)), int(min_gain),
+        (1 << 64) - 1 if max_bytes is None else max_bytes, int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), before, after, bound,
+        C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_disk_capacity")
+    return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before[0]), peak_after=int(after[0]),
+                      lower_bound=int(bound[0]), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes,
+                      peak_before_capacity=int(before[1]), peak_after_capacity=int(after[1]), lower_bound_den=int(bound[1]))
+
+
 def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int] = None) -> np.ndarray:
     """size[p] over `keys` (leaders.weights_for with this tool's words): every partition counts here, so one the table does not name
     takes `default_size` or is a ValueError; waves.sizes_for sizes only the partitions a given plan moves."""
@@ -101,28 +159,33 @@ def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int
 
 
 def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0,
-               dry_run: bool = False, max_bytes: Optional[int] = None) -> DiskPlan:
+               dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None) -> DiskPlan:
     """kao_balance_disk on a FailoverInput, size[p] per row of it; the entries are the rows that changed (none with dry_run).  With
-    max_bytes it is kao_balance_disk_budget."""
+    max_bytes it is kao_balance_disk_budget; with capacity (per broker index of fi) kao_balance_disk_capacity."""
     res = balance_disk_arrays(fi.rows, len(fi.broker_ids), fi.rack_of, len(fi.rack_names), size, max_per_rack, move_leaders, min_gain, max_rounds,
-                              dry_run, max_bytes)
+                              dry_run, max_bytes, capacity)
     changed = np.nonzero((res.rows != fi.rows).any(axis=1))[0]
     entries = [(fi.keys[p][0], fi.keys[p][1], [int(fi.broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
     return DiskPlan(result=res, input=fi, size=np.asarray(size, dtype=np.uint64), entries=entries)
 
 
 def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, default_size: Optional[int] = None, max_per_rack: int = 0,
-                 move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None) -> DiskPlan:
+                 move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None,
+                 capacity=None, default_capacity: Optional[int] = None) -> DiskPlan:
     """kao_balance_disk on a reassignment document with `broker_list` and `racks` ({broker id: rack name}).  `sizes` is
     {(topic, partition): bytes}, or a kafka-log-dirs / sizes document or text (waves.parse_sizes).  plan.document is the
-    reassignment document of the changed rows.  With max_bytes the moves copy at most that many bytes (kao_balance_disk_budget)."""
+    reassignment document of the changed rows.  With max_bytes the moves copy at most that many bytes (kao_balance_disk_budget).
+    With capacity, a {broker id: bytes} mapping (default_capacity for the brokers it does not name) or an array in the order of
+    `broker_list`, the moves lower the peak utilisation (kao_balance_disk_capacity)."""
     from .waves import parse_sizes
     if max_bytes is not None:
         max_bytes = _budget(max_bytes)
     fi = parse_current(doc, broker_list, racks)
+    if isinstance(capacity, dict):
+        capacity = capacity_of(fi.broker_ids, capacity, default_capacity)
     if not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
         sizes = parse_sizes(sizes)
-    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes)
+    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes, capacity)
 
 
 def report_lines(plan: DiskPlan) -> List[str]:
@@ -132,7 +195,18 @@ def report_lines(plan: DiskPlan) -> List[str]:
     return [f"disk: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
             f"bound_term={BOUND_TERMS[int(s[6])]} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
             f"rows_changed={s[4]} brokers_changed={s[7]} rounds={s[0]} moves={s[1]} launches={s[3]}"
-            + ("" if res.max_bytes is None else f" max_bytes={res.max_bytes} bytes_left={res.max_bytes - res.bytes_moved} refused={s[8]} budget_bound={s[9]}")]
+            + ("" if res.max_bytes is None else f" max_bytes={res.max_bytes} bytes_left={res.max_bytes - res.bytes_moved} refused={s[8]} budget_bound={s[9]}")
+            + ("" if res.lower_bound_den is None else f" peak_before_ppm={res.peak_before * 10 ** 6 // res.peak_before_capacity} "
+               f"peak_after_ppm={res.peak_after * 10 ** 6 // res.peak_after_capacity} lower_bound_ppm={res.lower_bound * 10 ** 6 // res.lower_bound_den} "
+               f"thorough_rounds={s[10]}")]
+
+
+def _capacities(arg: str) -> dict:
+    """--capacities: id:bytes,id:bytes or a JSON file {"<brokerId>": bytes}; the values as capacity_of takes them."""
+    if ":" in arg and "{" not in arg and not arg.endswith(".json"):
+        return {int(k): v for k, v in (kv.split(":") for kv in arg.split(",") if kv)}
+    with open(arg) as f:
+        return {int(k): v for k, v in json.load(f).items()}
 
 
 def main(argv=None) -> int:
@@ -150,13 +224,22 @@ def main(argv=None) -> int:
     ap.add_argument("--min-gain", default=None, help="move only to close a gap of more than N bytes (N, or N with K/M/G/T)")
     ap.add_argument("--max-rounds", type=count, default=0, help="stop after N rounds")
     ap.add_argument("--max-bytes", default=None, help="copy at most N bytes in all (N, or N with K/M/G/T)")
+    ap.add_argument("--capacities", default=None, help='{"<brokerId>": bytes} JSON file or id:bytes,id:bytes: lower the peak utilisation')
+    ap.add_argument("--default-capacity", default=None, help="bytes of disk of the brokers --capacities does not name")
     ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
-    min_gain, default_size, max_bytes = 0, None, None
+    min_gain, default_size, max_bytes, capacity = 0, None, None, None
     try:
+        if a.capacities is not None or a.default_capacity is not None:   # a broker without a capacity is a usage error
+            default_capacity = None if a.default_capacity is None else parse_bytes(a.default_capacity)
+            try:
+                table = {} if a.capacities is None else _capacities(a.capacities)
+            except (OSError, json.JSONDecodeError) as e:
+                raise ValueError(f"--capacities: {e}")
+            capacity = capacity_of([int(b) for b in a.broker_list.split(",") if b], table, default_capacity)
         if a.min_gain is not None:
             min_gain = parse_bytes(a.min_gain)
         if a.max_bytes is not None:
@@ -175,7 +258,7 @@ def main(argv=None) -> int:
             size = sizes_of(fi.keys, parse_sizes(f.read()), default_size)
         from .solver import init
         init(a.device)
-        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes)
+        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes, capacity)
         if a.report:
             for line in report_lines(plan):
                 print(line, file=sys.stderr)

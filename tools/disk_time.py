@@ -7,7 +7,12 @@ read-back of the counters, and ends in a stream synchronise).  For kernel times 
 `rocprofv3 --kernel-trace --stats --` (in a run of its own, --reps 1).  Writes the lines to profiles/disk_time.txt with --write.
 --max-bytes-pct 1,2,5,none times kao_balance_disk_budget instead, once per value: a budget of that share of
 the bytes stored, `none` = UINT64_MAX; the lines gain the budget, what is left of it, the refused winners, budget_bound and the time
-of every repeat, and --write puts them into profiles/disk_budget_time.txt."""
+of every repeat, and --write puts them into profiles/disk_budget_time.txt.
+--capacity 4:1 times kao_balance_disk_capacity on the same families with a bimodal capacity vector: even
+brokers have 4 * 2^36 bytes of disk, odd ones 2^36.  --capacity equal gives every broker 2^36 (the byte planner's plan: the cost of
+the 128-bit rank and test).  The lines gain the peaks and the bound as fractions and in parts per million, the mean utilisation,
+the thorough rounds and, for the same instance, the peak utilisation that kao_balance_disk's plan reaches; --write puts them into
+profiles/disk_capacity_time.txt."""
 import argparse
 import json
 import os
@@ -26,11 +31,12 @@ def main():
     ap.add_argument("--sigmas", default="0.7,1.5")
     ap.add_argument("--keep-leaders", action="store_true")
     ap.add_argument("--max-bytes-pct", default=None, help="CSV of budgets in percent of the bytes stored, or `none`: times kao_balance_disk_budget")
+    ap.add_argument("--capacity", default=None, choices=["4:1", "equal"], help="times kao_balance_disk_capacity with this capacity vector")
     ap.add_argument("--write", action="store_true", help="write the lines to profiles/disk_time.txt (disk_budget_time.txt with --max-bytes-pct) as well")
     a = ap.parse_args()
     import numpy as np
     import kafka_assignment_optimizer_amd as kao
-    from kafka_assignment_optimizer_amd.disk import BUDGET_STAT_KEYS, STAT_KEYS, balance_disk_arrays
+    from kafka_assignment_optimizer_amd.disk import BUDGET_STAT_KEYS, CAPACITY_STAT_KEYS, STAT_KEYS, balance_disk_arrays
     import leaders_ref as lr
     kao.init(0)
 
@@ -38,13 +44,13 @@ def main():
         rng = np.random.default_rng(seed)
         return np.maximum(1, np.round(np.exp(rng.normal(np.log(2.0 ** 20), sigma, P)))).astype(np.int64)
 
-    def timed(rows, B, rack_of, R, size, cap, max_bytes):
+    def timed(rows, B, rack_of, R, size, cap, max_bytes, capacity=None):
         args = (rows, B, rack_of, R, size, cap, not a.keep_leaders)
-        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes)   # warm-up
+        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity)   # warm-up
         ms = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes)
+            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity)
             ms.append(round(1e3 * (time.perf_counter() - t0), 3))
         return res, ms
 
@@ -63,7 +69,8 @@ def main():
             total = int((size[:, None] * (rows != 0xFFFF)).sum())
             for pct in [None] if a.max_bytes_pct is None else a.max_bytes_pct.split(","):   # None: kao_balance_disk
                 max_bytes = None if pct is None else 2 ** 64 - 1 if pct == "none" else int(total * float(pct) / 100)
-                res, ms = timed(rows, B, rack_of, R, size, cap, max_bytes)
+                capacity = None if a.capacity is None else np.where((np.arange(B) % 2 == 0) & (a.capacity == "4:1"), 4, 1).astype(np.int64) * 2 ** 36
+                res, ms = timed(rows, B, rack_of, R, size, cap, max_bytes, capacity)
                 line = {"workload": name, "sigma": sigma, "brokers": B, "racks": R, "partitions": len(rows), "max_per_rack": cap,
                         "move_leaders": not a.keep_leaders, "status": res.status, "peak_before": res.peak_before, "peak_after": res.peak_after,
                         "lower_bound": res.lower_bound, "peak_over_bound": round(res.peak_after / max(res.lower_bound, 1), 5),
@@ -71,14 +78,29 @@ def main():
                         "moved_share": round(res.bytes_moved / max(total, 1), 5)}
                 if pct is not None:
                     line.update({"max_bytes_pct": pct, "max_bytes": max_bytes, "bytes_left": max_bytes - res.bytes_moved})
-                line.update({k: int(v) for k, v in zip(STAT_KEYS if pct is None else BUDGET_STAT_KEYS, res.stats)})
+                if capacity is not None:
+                    def peak_ppm(S):
+                        b = max(range(B), key=lambda i: (int(S[i]) * 10 ** 6 // int(capacity[i]), -i))
+                        return int(S[b]) * 10 ** 6 // int(capacity[b])
+                    held = rows != 0xFFFF
+                    plain = balance_disk_arrays(rows, B, rack_of, R, size, cap, not a.keep_leaders, max_bytes=max_bytes)   # the byte planner's plan
+                    S = np.zeros(B, dtype=np.int64)
+                    np.add.at(S, plain.rows.astype(np.int64)[held], np.broadcast_to(size[:, None], rows.shape)[held])
+                    line.update({"capacity": a.capacity, "peak_before_capacity": res.peak_before_capacity, "peak_after_capacity": res.peak_after_capacity,
+                                 "lower_bound_den": res.lower_bound_den, "peak_before_ppm": res.peak_before * 10 ** 6 // res.peak_before_capacity,
+                                 "peak_after_ppm": res.peak_after * 10 ** 6 // res.peak_after_capacity,
+                                 "lower_bound_ppm": res.lower_bound * 10 ** 6 // res.lower_bound_den, "mean_ppm": total * 10 ** 6 // int(capacity.sum()),
+                                 "byte_plan_peak_ppm": peak_ppm(S), "byte_plan_rounds": int(plain.stats[0])})
+                    line["peak_over_bound"] = round((res.peak_after * res.lower_bound_den) / max(res.lower_bound * res.peak_after_capacity, 1), 5)
+                line.update({k: int(v) for k, v in zip(CAPACITY_STAT_KEYS if capacity is not None else STAT_KEYS if pct is None else BUDGET_STAT_KEYS, res.stats)})
                 line["wall_ms_median"] = round(float(np.median(ms)), 3)
                 if pct is not None:
                     line["wall_ms"] = ms
                 lines.append(json.dumps(line))
                 print(lines[-1], flush=True)
     if a.write:
-        with open(os.path.join(ROOT, "profiles", "disk_time.txt" if a.max_bytes_pct is None else "disk_budget_time.txt"), "w") as f:
+        name = "disk_capacity_time.txt" if a.capacity is not None else "disk_time.txt" if a.max_bytes_pct is None else "disk_budget_time.txt"
+        with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write("\n".join(lines) + "\n")
 
 
