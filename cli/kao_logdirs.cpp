@@ -37,6 +37,13 @@
 // Every homeless replica goes to the dir with the fewest bytes at that moment, the largest replica first.  The plan lists the
 // partitions of --plan and those with a placed or moved replica: "replicas" is the plan's row where there is one, else the row of
 // --current; "log_dirs" names the dir of a placed or moved slot and says "any" for every other.
+// With --utilisation, --capacities FILE or --default-capacity BYTES the dirs have sizes, and every mode above lowers the peak
+// UTILISATION L(d) / capacity(d) instead of the peak bytes (kao_balance_logdirs_capacity, kao_place_logdirs_capacity, DESIGN.md
+// section 4r).  A usable dir takes its capacity from its entry in FILE ({"<brokerId>": {"<logDir>": bytes}}, or {"<brokerId>":
+// bytes} for every dir of that broker; a value is a number or a string with K/M/G/T), else with --utilisation from the totalBytes of
+// --log-dirs when above 0 (Kafka >= 3.3), else from --default-capacity; a usable dir of a listed broker with none is a usage
+// error.  The plan keeps its format; the report gains peak_before_ppm, peak_after_ppm, lower_bound_ppm and proof per broker, the two
+// peaks in ppm for the call, and a warning line for a dir whose base alone exceeds its capacity.
 // Exit status: 0 = ok, 1 = error, 2 = usage.
 #include <algorithm>
 #include <cstdint>
@@ -61,12 +68,90 @@ namespace {
         "usage: kao-logdirs --current <reassignment.json> --log-dirs <kafka-log-dirs output> [--broker-list <id,id,...>]\n"
         "                   [--min-gain N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report] [--device D]\n"
         "                   [--plan <reassignment.json>] [--evacuate <broker>:<dir>]... [--rebalance] [--default-size N[K|M|G|T]]\n"
+        "                   [--utilisation] [--capacities <caps.json>] [--default-capacity N[K|M|G|T]]\n"
         "writes the partitions with a replica that moves to another log dir of its broker; exit status: 0 = ok, 1 = error, 2 = usage\n");
     std::exit(2);
 }
 
+// --utilisation / --capacities / --default-capacity: where a dir's capacity comes from
+struct Capacities {
+    bool on = false, utilisation = false, have_default = false;
+    uint64_t default_cap = 0;
+    std::map<int, uint64_t> of_broker;                           // {"<brokerId>": bytes}
+    std::map<std::pair<int, std::string>, uint64_t> of_dir;      // {"<brokerId>": {"<logDir>": bytes}}
+    std::set<int> by_dir;                                        // brokers listed with an object
+};
+
+// --capacities: a JSON file {"<brokerId>": {"<logDir>": bytes} | bytes}, a value a number or a string, each N or N with K/M/G/T
+void read_capacities(const std::string &path, Capacities &c) {
+    auto value = [](const JValue &v, const std::string &what) {
+        uint64_t x = 0;
+        if ((v.kind != JValue::Num && v.kind != JValue::Str) || !parse_bytes(v.kind == JValue::Num ? v.raw : v.str, x))
+            throw std::runtime_error("capacity of " + what + ": not a byte count");
+        return x;
+    };
+    const std::string txt = slurp(path);
+    const JValue doc = JParser(txt).parse();
+    if (doc.kind != JValue::Obj) throw std::runtime_error("capacities file must be a JSON object {\"<brokerId>\": {\"<logDir>\": bytes} | bytes}");
+    for (auto &kv : doc.obj) {
+        if (kv.first.empty() || kv.first.size() > 9 || kv.first.find_first_not_of("0123456789") != std::string::npos)
+            throw std::runtime_error("capacity of broker " + kv.first + ": not a broker id");
+        const int b = std::atoi(kv.first.c_str());
+        if (kv.second.kind == JValue::Obj) {
+            c.by_dir.insert(b);
+            for (auto &dv : kv.second.obj) c.of_dir[{b, dv.first}] = value(dv.second, "log dir " + std::to_string(b) + ":" + dv.first);
+        } else {
+            c.of_broker[b] = value(kv.second, "broker " + std::to_string(b));
+        }
+    }
+}
+
+// capacity[d] of every dir of the call: the entry of --capacities, else totalBytes > 0 under --utilisation, else the default; a dir
+// with none is a usage error
+std::vector<uint64_t> dir_capacities(const Capacities &c, const std::vector<int> &ids, const std::vector<std::vector<const LogDir *>> &dirs) {
+    std::vector<uint64_t> out;
+    std::vector<std::string> missing;
+    for (size_t i = 0; i < ids.size(); ++i)
+        for (auto *d : dirs[i]) {
+            auto dv = c.of_dir.find({ids[i], d->name});
+            auto bv = c.of_broker.find(ids[i]);
+            if (c.by_dir.count(ids[i]) && dv != c.of_dir.end()) out.push_back(dv->second);
+            else if (!c.by_dir.count(ids[i]) && bv != c.of_broker.end()) out.push_back(bv->second);
+            else if (c.utilisation && d->has_total && d->total_bytes > 0) out.push_back(d->total_bytes);
+            else if (c.have_default) out.push_back(c.default_cap);
+            else missing.push_back(std::to_string(ids[i]) + ":" + d->name);
+        }
+    if (!missing.empty()) {
+        std::string msg = "no capacity for log dirs ";
+        for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + missing[i];
+        if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
+        usage((msg + " (give them in --capacities, read totalBytes with --utilisation or set --default-capacity)").c_str());
+    }
+    if (out.empty()) out.push_back(1);   // the library takes no null pointer
+    return out;
+}
+
+// floor(num * 10^6 / den) in decimal; the product passes 64 bits
+std::string ppm(uint64_t num, uint64_t den) {
+    unsigned __int128 v = (unsigned __int128)num * 1000000u / den;
+    std::string s;
+    do { s.insert(s.begin(), (char)('0' + (int)(v % 10))); v /= 10; } while (v);
+    return s;
+}
+
+void warn_full(const std::vector<int> &ids, const std::vector<std::vector<const LogDir *>> &dirs, const std::vector<int32_t> &dir_start,
+               const std::vector<uint64_t> &base, const std::vector<uint64_t> &cap) {
+    for (size_t i = 0; i < ids.size(); ++i)
+        for (size_t li = 0; li < dirs[i].size(); ++li) {
+            const size_t d = (size_t)dir_start[i] + li;
+            if (base[d] > cap[d])
+                std::fprintf(stderr, "logdirs: warning: broker=%d dir=%s base=%llu exceeds capacity=%llu\n", ids[i], dirs[i][li]->name.c_str(),
+                             (unsigned long long)base[d], (unsigned long long)cap[d]);
+        }
+}
+
 // --plan / --evacuate: kao_place_logdirs (the mapping is in the head of this file).  Returns when the plan is written.
-void place(const std::string &cur_path, const std::string &dirs_path, const std::string &plan_path, const std::vector<std::pair<int, std::string>> &evacuate,
+void place(const Capacities &caps, const std::string &cur_path, const std::string &dirs_path, const std::string &plan_path, const std::vector<std::pair<int, std::string>> &evacuate,
            bool have_list, const std::string &brokers_csv, bool rebalance, bool have_default, uint64_t default_size, uint64_t min_gain, int max_rounds,
            bool dry_run, bool report, int device, const std::string &out_path) {
     auto rows_of = [](const std::string &path, const char *what) {
@@ -214,17 +299,26 @@ void place(const std::string &cur_path, const std::string &dirs_path, const std:
     const int R = (int)dir.size();
     const std::vector<int32_t> dir0 = dir;
     if (dir.empty()) { broker.push_back(0); dir.push_back(0); size.push_back(0); }   // the library takes no null pointer
+    const std::vector<uint64_t> cap = caps.on ? dir_capacities(caps, ids, stay) : std::vector<uint64_t>();
 
     int rc = kao_init(device);
     if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
     int32_t n_placed = 0, n_moved = 0, status = 0;
-    uint64_t bytes_placed = 0, bytes_moved = 0, before = 0, after = 0;
+    uint64_t bytes_placed = 0, bytes_moved = 0, before[2] = {0, 1}, after[2] = {0, 1};
     int64_t stats[10] = {0};
-    std::vector<uint64_t> per((size_t)B * 8, 0);
-    rc = kao_place_logdirs(B, dir_start.data(), base.data(), R, broker.data(), dir.data(), size.data(), rebalance ? 1 : 0, min_gain, max_rounds, dry_run ? 1 : 0,
-                           &n_placed, &bytes_placed, &n_moved, &bytes_moved, &before, &after, per.data(), &status, stats);
-    if (rc) throw std::runtime_error(std::string("kao_place_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
+    const size_t W = caps.on ? 12 : 8;
+    std::vector<uint64_t> per((size_t)B * W, 0);
+    if (caps.on) {
+        rc = kao_place_logdirs_capacity(B, dir_start.data(), base.data(), cap.data(), R, broker.data(), dir.data(), size.data(), rebalance ? 1 : 0, min_gain,
+                                        max_rounds, dry_run ? 1 : 0, &n_placed, &bytes_placed, &n_moved, &bytes_moved, before, after, per.data(), &status, stats);
+        if (rc) throw std::runtime_error(std::string("kao_place_logdirs_capacity: ") + kao_strerror(rc) + " " + kao_last_error());
+    } else {
+        rc = kao_place_logdirs(B, dir_start.data(), base.data(), R, broker.data(), dir.data(), size.data(), rebalance ? 1 : 0, min_gain, max_rounds, dry_run ? 1 : 0,
+                               &n_placed, &bytes_placed, &n_moved, &bytes_moved, before, after, per.data(), &status, stats);
+        if (rc) throw std::runtime_error(std::string("kao_place_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
+    }
     if (report) {
+        if (caps.on) warn_full(ids, stay, dir_start, base, cap);
         std::vector<int> residents((size_t)B, 0), homeless((size_t)B, 0);
         unsigned long long total = 0, all_skipped = 0, all_out = 0, all_stranded = 0;
         int all_res = 0, all_home = 0;
@@ -235,24 +329,33 @@ void place(const std::string &cur_path, const std::string &dirs_path, const std:
         }
         for (int d = 0; d < D; ++d) total += base[(size_t)d];
         for (int i = 0; i < B; ++i) {
-            const uint64_t *p = per.data() + (size_t)i * 8;
+            const uint64_t *q = per.data() + (size_t)i * W;
+            // with capacities {peak_before, cap, peak_after, cap, bound num, den, placed, bytes_placed, moved, bytes_moved, rounds, proof}
+            const uint64_t p[8] = {q[0], caps.on ? q[2] : q[1], caps.on ? q[4] : q[2], caps.on ? q[6] : q[3], caps.on ? q[7] : q[4], caps.on ? q[8] : q[5],
+                                   caps.on ? q[9] : q[6], caps.on ? q[10] : q[7]};
             all_skipped += (unsigned long long)skipped[(size_t)i];
             all_out += (unsigned long long)out_of[(size_t)i].size();
             all_stranded += stranded[(size_t)i];
             std::fprintf(stderr, "logdirs: broker=%d dirs=%d skipped_dirs=%d evacuated_dirs=%d replicas=%d residents=%d homeless=%d peak_before=%llu peak_after=%llu "
-                                 "lower_bound=%llu placed=%llu bytes_placed=%llu moved=%llu bytes_moved=%llu rounds=%llu stranded_bytes=%llu\n",
+                                 "lower_bound=%llu placed=%llu bytes_placed=%llu moved=%llu bytes_moved=%llu rounds=%llu stranded_bytes=%llu",
                          ids[(size_t)i], (int)stay[(size_t)i].size(), skipped[(size_t)i], (int)out_of[(size_t)i].size(), residents[(size_t)i] + homeless[(size_t)i],
                          residents[(size_t)i], homeless[(size_t)i], (unsigned long long)p[0], (unsigned long long)p[1], (unsigned long long)p[2], (unsigned long long)p[3],
                          (unsigned long long)p[4], (unsigned long long)p[5], (unsigned long long)p[6], (unsigned long long)p[7], stranded[(size_t)i]);
+            if (caps.on)
+                std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s lower_bound_ppm=%s proof=%llu", ppm(q[0], q[1]).c_str(), ppm(q[2], q[3]).c_str(),
+                             ppm(q[4], q[5]).c_str(), (unsigned long long)q[11]);
+            std::fprintf(stderr, "\n");
         }
         std::fprintf(stderr, "logdirs: status=%s brokers=%d dirs=%d skipped_dirs=%llu evacuated_dirs=%llu replicas=%d residents=%d homeless=%d peak_before=%llu "
                              "peak_after=%llu replicas_placed=%d bytes_placed=%llu replicas_moved=%d bytes_moved=%llu bytes_total=%llu stranded_bytes=%llu "
                              "brokers_placed=%lld brokers_moved=%lld rounds=%lld moves=%lld proposals=%lld launches=%lld stopped_by_max_rounds=%lld proven=%lld "
-                             "max_rounds_of_a_broker=%lld max_homeless_of_a_broker=%lld\n",
+                             "max_rounds_of_a_broker=%lld max_homeless_of_a_broker=%lld",
                      status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, all_out, R, all_res, all_home,
-                     (unsigned long long)before, (unsigned long long)after, n_placed, (unsigned long long)bytes_placed, n_moved, (unsigned long long)bytes_moved, total,
+                     (unsigned long long)before[0], (unsigned long long)after[0], n_placed, (unsigned long long)bytes_placed, n_moved, (unsigned long long)bytes_moved, total,
                      all_stranded, (long long)stats[0], (long long)stats[1], (long long)stats[2], (long long)stats[3], (long long)stats[4], (long long)stats[5],
                      (long long)stats[6], (long long)stats[7], (long long)stats[8], (long long)stats[9]);
+        if (caps.on) std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s", ppm(before[0], before[1]).c_str(), ppm(after[0], after[1]).c_str());
+        std::fprintf(stderr, "\n");
     }
     // the partitions of the plan and those with a placed or moved replica, in (topic, partition) order
     std::map<Key, std::vector<std::string>> lists;
@@ -293,6 +396,8 @@ int main(int argc, char **argv) {
     int device = 0, max_rounds = 0;
     bool report = false, dry_run = false, have_list = false, rebalance = false, have_default = false;
     uint64_t min_gain = 0, default_size = 0;
+    Capacities caps;
+    std::string caps_path;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
@@ -316,6 +421,13 @@ int main(int argc, char **argv) {
         } else if (a == "--default-size") {
             if (!parse_bytes(need("--default-size"), default_size)) usage("--default-size needs a byte count (N, or N with K/M/G/T)");
             have_default = true;
+        } else if (a == "--utilisation") {
+            caps.utilisation = true;
+        } else if (a == "--capacities") {
+            caps_path = need("--capacities");
+        } else if (a == "--default-capacity") {
+            if (!parse_bytes(need("--default-capacity"), caps.default_cap)) usage("--default-capacity needs a byte count (N, or N with K/M/G/T)");
+            caps.have_default = true;
         } else if (a == "--min-gain") {
             if (!parse_bytes(need("--min-gain"), min_gain)) usage("--min-gain needs a byte count (N, or N with K/M/G/T)");
         } else if (a == "--max-rounds") {
@@ -328,9 +440,19 @@ int main(int argc, char **argv) {
     if (cur_path.empty() || dirs_path.empty() || out_path.empty()) usage("--current, --log-dirs and --out are required");
     const bool placing = !plan_path.empty() || !evacuate.empty();
     if ((rebalance || have_default) && !placing) usage("--rebalance and --default-size need --plan or --evacuate");
+    caps.on = caps.utilisation || !caps_path.empty() || caps.have_default;
+    if (!caps_path.empty()) {
+        std::string msg;
+        try {
+            read_capacities(caps_path, caps);
+        } catch (const std::exception &e) {
+            msg = std::string("--capacities: ") + e.what();
+        }
+        if (!msg.empty()) usage(msg.c_str());
+    }
     try {
         if (placing) {
-            place(cur_path, dirs_path, plan_path, evacuate, have_list, brokers_csv, rebalance, have_default, default_size, min_gain, max_rounds, dry_run, report, device,
+            place(caps, cur_path, dirs_path, plan_path, evacuate, have_list, brokers_csv, rebalance, have_default, default_size, min_gain, max_rounds, dry_run, report, device,
                   out_path);
             return 0;
         }
@@ -414,36 +536,53 @@ int main(int argc, char **argv) {
         const int R = (int)dir.size();
         const std::vector<int32_t> dir0 = dir;
         if (dir.empty()) { dir.push_back(0); size.push_back(0); }   // the library takes no null pointer
+        const std::vector<uint64_t> cap = caps.on ? dir_capacities(caps, ids, usable) : std::vector<uint64_t>();
 
         int rc = kao_init(device);
         if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
         int32_t n_moved = 0, status = 0;
-        uint64_t bytes_moved = 0, before = 0, after = 0;
+        uint64_t bytes_moved = 0, before[2] = {0, 1}, after[2] = {0, 1};
         int64_t stats[8] = {0};
-        std::vector<uint64_t> per((size_t)B * 6, 0);
-        rc = kao_balance_logdirs(B, dir_start.data(), base.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved,
-                                 &before, &after, per.data(), &status, stats);
-        if (rc) throw std::runtime_error(std::string("kao_balance_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
+        const size_t W = caps.on ? 10 : 6;
+        std::vector<uint64_t> per((size_t)B * W, 0);
+        if (caps.on) {
+            rc = kao_balance_logdirs_capacity(B, dir_start.data(), base.data(), cap.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved,
+                                              &bytes_moved, before, after, per.data(), &status, stats);
+            if (rc) throw std::runtime_error(std::string("kao_balance_logdirs_capacity: ") + kao_strerror(rc) + " " + kao_last_error());
+        } else {
+            rc = kao_balance_logdirs(B, dir_start.data(), base.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved,
+                                     before, after, per.data(), &status, stats);
+            if (rc) throw std::runtime_error(std::string("kao_balance_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
+        }
         if (report) {
+            if (caps.on) warn_full(ids, usable, dir_start, base, cap);
             std::vector<int> replicas((size_t)B, 0);
             for (int r = 0; r < R; ++r) ++replicas[(size_t)(std::upper_bound(dir_start.begin(), dir_start.end(), dir0[(size_t)r]) - dir_start.begin() - 1)];
             unsigned long long total = 0, all_skipped = 0;
             for (int r = 0; r < R; ++r) total += size[(size_t)r];
             for (int d = 0; d < D; ++d) total += base[(size_t)d];
             for (int i = 0; i < B; ++i) {
-                const uint64_t *p = per.data() + (size_t)i * 6;
+                const uint64_t *q = per.data() + (size_t)i * W;
+                // with capacities {peak_before, cap, peak_after, cap, bound num, den, moved, bytes_moved, rounds, proof}
+                const uint64_t p[6] = {q[0], caps.on ? q[2] : q[1], caps.on ? q[4] : q[2], caps.on ? q[6] : q[3], caps.on ? q[7] : q[4], caps.on ? q[8] : q[5]};
                 all_skipped += (unsigned long long)skipped[(size_t)i];
                 std::fprintf(stderr, "logdirs: broker=%d dirs=%d skipped_dirs=%d replicas=%d peak_before=%llu peak_after=%llu lower_bound=%llu moved=%llu "
-                                     "bytes_moved=%llu rounds=%llu\n",
+                                     "bytes_moved=%llu rounds=%llu",
                              ids[(size_t)i], (int)usable[(size_t)i].size(), skipped[(size_t)i], replicas[(size_t)i], (unsigned long long)p[0], (unsigned long long)p[1],
                              (unsigned long long)p[2], (unsigned long long)p[3], (unsigned long long)p[4], (unsigned long long)p[5]);
+                if (caps.on)
+                    std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s lower_bound_ppm=%s proof=%llu", ppm(q[0], q[1]).c_str(), ppm(q[2], q[3]).c_str(),
+                                 ppm(q[4], q[5]).c_str(), (unsigned long long)q[9]);
+                std::fprintf(stderr, "\n");
             }
             std::fprintf(stderr, "logdirs: status=%s brokers=%d dirs=%d skipped_dirs=%llu replicas=%d peak_before=%llu peak_after=%llu replicas_moved=%d "
                                  "bytes_moved=%llu bytes_total=%llu brokers_moved=%lld rounds=%lld moves=%lld proposals=%lld launches=%lld "
-                                 "stopped_by_max_rounds=%lld proven=%lld max_rounds_of_a_broker=%lld\n",
-                         status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, R, (unsigned long long)before,
-                         (unsigned long long)after, n_moved, (unsigned long long)bytes_moved, total, (long long)stats[0], (long long)stats[1], (long long)stats[2],
+                                 "stopped_by_max_rounds=%lld proven=%lld max_rounds_of_a_broker=%lld",
+                         status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, R, (unsigned long long)before[0],
+                         (unsigned long long)after[0], n_moved, (unsigned long long)bytes_moved, total, (long long)stats[0], (long long)stats[1], (long long)stats[2],
                          (long long)stats[3], (long long)stats[4], (long long)stats[5], (long long)stats[6], (long long)stats[7]);
+            if (caps.on) std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s", ppm(before[0], before[1]).c_str(), ppm(after[0], after[1]).c_str());
+            std::fprintf(stderr, "\n");
         }
         // the partitions with a moved replica, in (topic, partition) order: the replicas come out in that order already
         std::string body;

@@ -107,7 +107,8 @@ inline std::map<Key, uint64_t> load_sizes(const std::string &path) {
 }
 
 // `kafka-log-dirs --describe` output with what load_sizes folds away: per broker its log dirs in the order of the document, each with
-// its name, whether its "error" is non-null, and its entries (partition names split at the last '-'; sizes 0..2^53; isFuture).
+// its name, whether its "error" is non-null, its entries (partition names split at the last '-'; sizes 0..2^53; isFuture), and the
+// totalBytes / usableBytes of its volume where the document has them (Kafka >= 3.3; absent or null: has_* stays false).
 struct LogDirEntry {
     Key key;
     uint64_t size = 0;
@@ -117,7 +118,17 @@ struct LogDir {
     std::string name;
     bool failed = false;
     std::vector<LogDirEntry> entries;
+    bool has_total = false, has_usable = false;
+    uint64_t total_bytes = 0, usable_bytes = 0;
 };
+// totalBytes / usableBytes of a log dir: false when absent or null, else an integer 0..2^53 under the rules of a size
+inline bool volume_bytes(const JValue *v, const std::string &what, uint64_t &out) {
+    if (!v || v->kind == JValue::Null) return false;
+    if (v->kind != JValue::Num || v->raw.empty() || v->raw.size() > 16 || v->raw.find_first_not_of("0123456789") != std::string::npos ||
+        (out = std::strtoull(v->raw.c_str(), nullptr, 10)) > kMaxSize)
+        throw std::runtime_error(what + ": size must be an integer 0..2^53");
+    return true;
+}
 inline std::map<int, std::vector<LogDir>> load_log_dirs(const std::string &path) {
     const std::string txt = slurp(path);
     JValue doc;
@@ -152,6 +163,8 @@ inline std::map<int, std::vector<LogDir>> load_log_dirs(const std::string &path)
             LogDir dir;
             dir.name = name->str;
             dir.failed = err && err->kind != JValue::Null;
+            dir.has_total = volume_bytes(ld.get("totalBytes"), "log-dirs: broker " + std::to_string(b) + ": " + name->str + ": totalBytes", dir.total_bytes);
+            dir.has_usable = volume_bytes(ld.get("usableBytes"), "log-dirs: broker " + std::to_string(b) + ": " + name->str + ": usableBytes", dir.usable_bytes);
             for (size_t i = 0; parts && i < parts->arr.size(); ++i) {
                 const JValue &e = parts->arr[i];
                 const JValue *fut = e.get("isFuture"), *pn = e.get("partition"), *v = e.get("size");

@@ -823,6 +823,61 @@ int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start /* [n_brokers+
  * memory.  Returns the previous choice; both paths give the same bytes. */
 int kao_logdirs_test_sort(int32_t path);
 
+/* ---- Log-dir planners by utilisation ------------------------------------------------------------------------
+ * kao_balance_logdirs and kao_place_logdirs even out bytes; a broker's volumes are often unequal, and it takes a dir offline when
+ * that dir fills.  Here cap[d] >= 1 is the bytes of disk behind dir d (the sum over all dirs below 2^62) and the quantity that the
+ * moves lower is the UTILISATION u(d) = L(d) / cap(d).  Dirs, base, size, L(d), F(d), residents, homeless replicas, the CSR layout,
+ * the limits, the checks, dry_run and the counters are those of the two calls above; only what follows changes.
+ * NO QUOTIENT.  x / cx is above y / cy iff x * cy > y * cx in unsigned 128-bit arithmetic (both factors stay below 2^62); a
+ * utilisation is never a double or a division in anything that decides a move.
+ * RANK.  A broker's dirs are ranked by u descending (ties: dir index ascending; rank 0 is the fullest, order[q] = the dir of rank q).
+ * GAIN TEST.  r: a -> c passes iff (L(c) + size[r] + min_gain) * cap(a) < L(a) * cap(c); if the 64-bit sum on the left overflows the
+ * move does not pass (min_gain is any uint64_t).
+ * PROPOSAL.  Every replica r with size[r] > 0 on a broker with n >= 2 dirs makes at most one; a = its dir, q = rank(a).  If
+ * q < n-1-q and c1 = order[n-1-q] passes the test, the proposal is a -> c1.  Otherwise the ranks n-1, n-2, ..., q+1 are walked in
+ * that order and the first dir that passes is proposed.  A dir that passes is strictly emptier than a and so ranks behind it: the walk
+ * sees every move there is, and "no proposal" means that no single move of r passes the test.  (With bytes, if any dir passes the
+ * lightest does; not so here: a fuller but larger dir can pass where the emptiest small one does not.)
+ * KEY, WIN RULE, APPLY, STOP RULE: those of kao_balance_logdirs, q being the utilisation rank.  A winner leaves both of its dirs
+ * strictly below the old u(a) and winners share no dir, so the broker's utilisations sorted descending fall lexicographically every
+ * round: the rounds end, the peak utilisation never rises, the end state is move-stable.  (The sum of L^2 may rise.)
+ * PLACE (kao_place_logdirs_capacity).  The homeless replicas are taken size descending, then r ascending; each goes to the dir with
+ * the lowest (L(d) + size[r]) / cap(d) at that moment, compared by products (ties: the lowest dir index).  After PLACE no single move
+ * of a placed replica passes the test, even at min_gain 0: let r be the LAST replica put on a, L_then the loads just before.  Then
+ * u_final(a) = (L_then(a) + size[r]) / cap(a) <= (L_then(c) + size[r]) / cap(c) for every dir c by the choice of a, and for every
+ * earlier replica x on a, size[x] >= size[r] and loads only grow, so (L_then(c) + size[r]) / cap(c) <= (L_final(c) + size[x]) / cap(c):
+ * the test (L(c) + size[x]) * cap(a) < L(a) * cap(c) fails.  With move_residents != 0 the rounds above run from the placed state over
+ * ALL replicas of the broker.
+ * BOUND of a broker, a fraction {num, den} that no outcome undercuts.  M = the replicas that may change dir and F' = the fixed loads
+ * as for kao_place_logdirs (the balance call: M = every replica, F' = base).  The bound is the largest, as fractions (ties: the
+ * lowest-numbered term), of (0) the lowest over d of {F'(d) + max_{r in M} size[r], cap(d)}, and {0, 1} when M is empty; (1) {sum of
+ * F' + sum over M of size, sum of cap(d)}; (2) the highest over d of {F'(d), cap(d)}; inside (0) and (2) ties go to the lowest dir.
+ * INTEGRALITY TEST, a second proof: {L*, cap*} = the broker's peak after; room(d) = max(0, ceil(L* * cap(d) / cap*) - 1 - F'(d)), each
+ * cut at the sum over M of size; the test passes iff the rooms sum to less than that sum: a dir strictly below the achieved
+ * utilisation holds at most ceil(L* * cap(d) / cap*) - 1 bytes, so no outcome puts every dir strictly below it.  A broker is PROVEN
+ * iff its peak equals the bound as fractions or the test passes; *status = KAO_STATUS_OPTIMAL_PROVEN iff every broker is.  With
+ * equal capacities "proven" coincides with peak_after == lower_bound of the byte calls.
+ * peak_before[2] / peak_after[2] = {L, cap} of the fullest dir of the call (ties: the lowest global dir index; {0, 1} without dirs;
+ * for the place call peak_before is taken over F).  per_broker, balance: [10b..10b+9] = {L_before, cap_before, L_after, cap_after,
+ * lb_num, lb_den, moved, bytes_moved, rounds, proof}; place: [12b..12b+11] = {L_before, cap_before, L_after, cap_after, lb_num,
+ * lb_den, placed, bytes_placed, moved, bytes_moved, rounds, proof}; proof: 0 = gap, 1 = bound met, 2 = integrality test only.  A
+ * broker without dirs reports {0, 1, 0, 1, 0, 1, 0, ..., 0, proof 1}.  stats are those of the byte calls ("proven" by either proof).
+ * IDENTITY.  With all cap[d] equal each call gives the dir[], n_moved, bytes_moved, n_placed, bytes_placed, peak_*[0], status, the L,
+ * moved, bytes, placed and rounds columns and every stats entry but the launch count of its byte sibling.
+ * Checked on the host before any device is used: everything the byte calls check, and KAO_ERR_INVALID for cap == NULL, a cap[d] == 0,
+ * or capacities summing to 2^62 or more. */
+int kao_balance_logdirs_capacity(int32_t n_brokers, const int32_t *dir_start /* [n_brokers+1] */, const uint64_t *base /* [n_dirs] or NULL */,
+                                 const uint64_t *cap /* [n_dirs] */, int32_t n_replicas, int32_t *dir /* [n_replicas] in / out */,
+                                 const uint64_t *size /* [n_replicas] */, uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run,
+                                 int32_t *n_moved, uint64_t *bytes_moved, uint64_t peak_before[2], uint64_t peak_after[2],
+                                 uint64_t *per_broker /* [n_brokers*10] */, int32_t *status, int64_t stats[8] /* may be NULL */);
+int kao_place_logdirs_capacity(int32_t n_brokers, const int32_t *dir_start /* [n_brokers+1] */, const uint64_t *base /* [n_dirs] or NULL */,
+                               const uint64_t *cap /* [n_dirs] */, int32_t n_replicas, const int32_t *broker /* [n_replicas] */,
+                               int32_t *dir /* [n_replicas] in / out, -1 = homeless */, const uint64_t *size /* [n_replicas] */, int32_t move_residents,
+                               uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run, int32_t *n_placed, uint64_t *bytes_placed,
+                               int32_t *n_moved, uint64_t *bytes_moved, uint64_t peak_before[2], uint64_t peak_after[2],
+                               uint64_t *per_broker /* [n_brokers*12] */, int32_t *status, int64_t stats[10] /* may be NULL */);
+
 /* Diagnostic: runs the two collectives kao_solve_multi uses (ncclAllReduce(ncclUint64, ncclMin) and ncclBroadcast) on
  * small resident buffers of the listed distinct devices and checks the results.  0 = ok. */
 int kao_rccl_selftest(const int32_t *devices, int32_t n_dev);

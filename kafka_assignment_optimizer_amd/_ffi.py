@@ -135,6 +135,12 @@ SIGNATURES = {
                                     C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64),
                                     _P(C.c_uint64), _P(C.c_int32), _P(C.c_int64)]),
     "kao_logdirs_test_sort": (C.c_int, [C.c_int32]),
+    "kao_balance_logdirs_capacity": (C.c_int, [C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), C.c_int32, _P(C.c_int32), _P(C.c_uint64), C.c_uint64,
+                                               C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32),
+                                               _P(C.c_int64)]),
+    "kao_place_logdirs_capacity": (C.c_int, [C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_uint64),
+                                             C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_int32), _P(C.c_uint64),
+                                             _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32), _P(C.c_int64)]),
     "kao_last_solve_timing":(C.c_int, [_P(C.c_double)]),
     "kao_last_solve_profile": (C.c_int, [_P(C.c_double)]),
     "kao_last_solve_lp": (C.c_int, [_P(C.c_double)]),

@@ -54,7 +54,8 @@ constexpr int kLdWon = 0x80;             // flag in dst[]: this round's proposal
 constexpr int kLdSortLds = 4096;         // kao_place_logdirs: homeless replicas of one broker sorted in dynamic LDS (12 bytes each: 48 KiB of the 64 KiB a launch gets unasked)
 enum { LC_PEAK0 = 0, LC_PEAK1, LC_NMOVED, LC_BYTES, LC_BROKERS, LC_ROUNDS, LC_MOVES, LC_PROPS, LC_MORE, LC_PROVEN, LC_MAXROUNDS, LC_ERR, LC_MAXN, LC_MAXH /* = LC_MAXN + 1 */,
        LC_NPLACED, LC_BPLACED, LC_PLACERS, LC_N = 24 };
-enum { LS_PEAK0 = 0, LS_PEAK1, LS_MAXSIZE, LS_MINBASE, LS_MAXBASE, LS_TOTAL, LS_NMOVED, LS_BYTES, LS_MOVES, LS_PROPS, LS_MINF, LS_HBYTES, LS_N = 16 };
+enum { LS_PEAK0 = 0, LS_PEAK1, LS_MAXSIZE, LS_MINBASE, LS_MAXBASE, LS_TOTAL, LS_NMOVED, LS_BYTES, LS_MOVES, LS_PROPS, LS_MINF, LS_HBYTES, LS_PEAK0DEN /* Cap */, LS_N = 16 };
+typedef unsigned __int128 u128;
 static_assert(kLdMaxDirs == 64, "a wavefront ranks the dirs of a broker; a destination and kLdWon share a byte");
 
 struct LdNet {   // one call; every pointer is device memory
@@ -74,7 +75,81 @@ struct LdNet {   // one call; every pointer is device memory
     int move_residents, sort_lds, sort_cap;   // the rounds follow PLACE; the sort runs in dynamic LDS of sort_cap entries (else in the bucket)
     const int32_t *hcnt;        // [B] homeless replicas of a broker
     uint32_t *sr;               // [R] by place in the bucket: the r of a sort entry on the global path (its size sits in key[])
+    // the capacity calls alone (Cap; per_broker is then [10B], [12B] for k_ld_place)
+    const u64 *cap;             // [n_dirs] bytes of disk behind a dir, >= 1
 };
+
+// ---- Cap: the descent by utilisation u(d) = L(d) / cap(d) -------------------------------------------------------
+// The loads of a broker sit in LDS as load[d] (Cap = false) or as the pairs {load, cap} = load[2d], load[2d + 1] (Cap = true): one
+// 128-bit read brings both.  No quotient is formed: x / cx is above y / cy iff x * cy > y * cx in 128 bits (loads < 2^62, caps < 2^62).
+template <bool Cap>
+__device__ __forceinline__ u64 &ld_load(u64 *load, int d) { return load[Cap ? 2 * d : d]; }
+struct LdPair {
+    u64 l, c;
+};
+__device__ __forceinline__ LdPair ld_pair(const u64 *load, int d) {
+    const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(load + 2 * d);
+    return {v.x, v.y};
+}
+// (L(c) + w + min_gain) * cap(a) < L(a) * cap(c); a 64-bit sum that overflows does not pass (L(c) + w stays below 2^63)
+__device__ __forceinline__ bool ld_gains_cap(LdPair a, LdPair c, u64 w, u64 min_gain) {
+    u64 s;
+    if (__builtin_add_overflow(c.l + w, min_gain, &s)) return false;
+    return (u128)s * a.c < (u128)a.l * c.c;
+}
+// Over the 64 lanes of a wavefront, all active: the highest (Max) or the lowest fraction num / den, ties to the lowest idx (the idx
+// are distinct); every lane ends with the same {num, den, idx}.
+template <bool Max>
+__device__ __forceinline__ void ld_frac_reduce(u64 &num, u64 &den, int &idx) {
+    for (int x = 32; x >= 1; x >>= 1) {
+        const u64 on = __shfl_xor(num, x), od = __shfl_xor(den, x);
+        const int oi = __shfl_xor(idx, x);
+        const u128 theirs = (u128)on * den, ours = (u128)num * od;
+        const bool take = (Max ? theirs > ours : theirs < ours) || (theirs == ours && oi < idx);
+        num = take ? on : num;
+        den = take ? od : den;
+        idx = take ? oi : idx;
+    }
+}
+// the sum over the 64 lanes, cut at 2^62 (every v is at most 2^62)
+__device__ __forceinline__ u64 ld_wave_sum(u64 v) {
+    for (int x = 32; x >= 1; x >>= 1) v = min(v + __shfl_xor(v, x), 1ull << 62);
+    return v;
+}
+// The peak after, the bound and the proof of one broker (include/kao.h: kao_balance_logdirs_capacity), by the 64 lanes of wavefront
+// 0: lane d < nd brings L = its load, c = its capacity, f = its fixed load F'(d); mx = the largest size in M, any = M is not empty.
+// o[0..1] = the peak {L, cap}, o[2..3] = the bound {num, den}; returns the proof (0 gap, 1 bound met, 2 integrality test only).
+__device__ __forceinline__ int ld_cap_bound(int nd, u64 L, u64 c, u64 f, u64 mx, bool any, u64 *o) {
+    const int lane = threadIdx.x;
+    const bool v = lane < nd;
+    u64 pn = v ? L : 0, pd = v ? c : 1;
+    int pi = lane;
+    ld_frac_reduce<true>(pn, pd, pi);
+    u64 bn = 0, bd = 1;                       // term (0): the lowest {F'(d) + mx, cap(d)}; a lane past nd sorts after every dir
+    if (any) {
+        bn = v ? f + mx : kLdNoKey;
+        bd = v ? c : 1;
+        int bi = lane;
+        ld_frac_reduce<false>(bn, bd, bi);
+    }
+    const u64 total = ld_wave_sum(v ? L : 0), fsum = ld_wave_sum(v ? f : 0), csum = ld_wave_sum(v ? c : 0);   // below 2^62: not cut
+    if ((u128)total * bd > (u128)bn * csum) { bn = total; bd = csum; }   // term (1): sum of F' + sum over M = the sum of the loads
+    u64 tn = v ? f : 0, td = v ? c : 1;       // term (2)
+    int ti = lane;
+    ld_frac_reduce<true>(tn, td, ti);
+    if ((u128)tn * bd > (u128)bn * td) { bn = tn; bd = td; }
+    if (lane == 0) { o[0] = pn; o[1] = pd; o[2] = bn; o[3] = bd; }
+    if ((u128)pn * bd == (u128)bn * pd) return 1;
+    // the integrality test: a dir strictly below the peak pn / pd holds at most ceil(pn * cap(d) / pd) - 1 bytes, so room(d) of them
+    // for M; when the rooms sum to less than M's bytes no outcome is strictly below the peak everywhere.  (pn >= 1: the peak is above the bound.)
+    const u64 msum = total - fsum;
+    u64 room = 0;
+    if (v) {
+        const u128 q = ((u128)pn * c + pd - 1) / pd - 1;
+        if (q > f) room = q - f > msum ? msum : (u64)(q - f);
+    }
+    return ld_wave_sum(room) < msum ? 2 : 0;
+}
 
 // ---- the buckets --------------------------------------------------------------------------------------------------------------------
 // The broker of replica r is map[idx[r]] (kao_balance_logdirs: the broker of its dir), or idx[r] when map is null (kao_place_logdirs:
@@ -132,17 +207,27 @@ struct LdTally {
     int rounds = 0, more = 0;
     u64 props = 0, moves = 0;
 };
+template <bool Cap>
 __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int nr, const int32_t *list, u64 *key, uint8_t *dst, u64 *load, u64 *mk, uint8_t *rank,
                                              uint8_t *order) {
     const int tid = threadIdx.x, NT = blockDim.x;
     LdTally t;
     for (;;) {
         if (tid < nd) {   // RANK
-            const u64 mine = load[tid];
             int q = 0;
-            for (int j = 0; j < nd; ++j) {
-                const u64 x = load[j];
-                q += (x > mine || (x == mine && j < tid)) ? 1 : 0;
+            if constexpr (Cap) {   // by u descending: all pairs by products
+                const LdPair me = ld_pair(load, tid);
+                for (int j = 0; j < nd; ++j) {
+                    const LdPair x = ld_pair(load, j);
+                    const u128 theirs = (u128)x.l * me.c, ours = (u128)me.l * x.c;
+                    q += (theirs > ours || (theirs == ours && j < tid)) ? 1 : 0;
+                }
+            } else {
+                const u64 mine = load[tid];
+                for (int j = 0; j < nd; ++j) {
+                    const u64 x = load[j];
+                    q += (x > mine || (x == mine && j < tid)) ? 1 : 0;
+                }
             }
             rank[tid] = (uint8_t)q;   // ranks are a permutation: q < nd
             order[q] = (uint8_t)tid;
@@ -155,15 +240,29 @@ __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int
             u64 k = kLdNoKey;
             if (w && nd >= 2) {
                 const int a = n.dir[r] - ds, ra = rank[a];
-                const u64 la = load[a];
                 int c = -1;
-                if (ra < nd - 1 - ra) {
-                    const int c1 = order[nd - 1 - ra];
-                    if (descent_gains(la, load[c1], w, n.min_gain)) c = c1;
-                }
-                if (c < 0 && ra >= 1) {
-                    const int c2 = order[nd - 1];   // (a itself when a is the lightest: it does not pass)
-                    if (descent_gains(la, load[c2], w, n.min_gain)) c = c2;
+                if constexpr (Cap) {   // c1, then the walk over the ranks n-1 .. q+1: the first dir that passes (a fuller but larger dir can pass where the emptiest does not)
+                    const LdPair pa = ld_pair(load, a);
+                    const int p1 = nd - 1 - ra;
+                    if (ra < p1) {
+                        const int c1 = order[p1];
+                        if (ld_gains_cap(pa, ld_pair(load, c1), w, n.min_gain)) c = c1;
+                    }
+                    for (int p = nd - 1; c < 0 && p > ra; --p) {
+                        if (p == p1) continue;   // c1, which did not pass
+                        const int cw = order[p];
+                        if (ld_gains_cap(pa, ld_pair(load, cw), w, n.min_gain)) c = cw;
+                    }
+                } else {
+                    const u64 la = load[a];
+                    if (ra < nd - 1 - ra) {
+                        const int c1 = order[nd - 1 - ra];
+                        if (descent_gains(la, load[c1], w, n.min_gain)) c = c1;
+                    }
+                    if (c < 0 && ra >= 1) {
+                        const int c2 = order[nd - 1];   // (a itself when a is the lightest: it does not pass)
+                        if (descent_gains(la, load[c2], w, n.min_gain)) c = c2;
+                    }
                 }
                 if (c >= 0) {
                     k = (u64)(uint32_t)ra << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)r;
@@ -191,8 +290,8 @@ __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int
             const int r = list[q], s = dst[q], c = s & (kLdWon - 1), a = n.dir[r] - ds;
             if (s & kLdWon) {   // no other winner touches a or c
                 const u64 w = n.size[r];
-                load[a] -= w;
-                load[c] += w;
+                ld_load<Cap>(load, a) -= w;
+                ld_load<Cap>(load, c) += w;
                 n.dir[r] = ds + c;
                 ++t.moves;
             }
@@ -205,15 +304,19 @@ __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int
 }
 
 // ---- one broker ---------------------------------------------------------------------------------------------------------------------
+template <bool Cap>
 __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
-    __shared__ u64 load[kLdMaxDirs], mk[kLdMaxDirs], sh[LS_N];
+    __shared__ alignas(16) u64 load[(Cap ? 2 : 1) * kLdMaxDirs];   // 16 bytes: RANK reads two loads (Cap: one {load, cap}) with one 128-bit LDS read
+    __shared__ u64 mk[kLdMaxDirs], sh[LS_N];
     __shared__ uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
+    constexpr int W = Cap ? 10 : 6;   // columns of a row of per_broker
     const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
     const int ds = n.dir_start[b], nd = n.dir_start[b + 1] - ds, nr = n.cnt[b], at = n.start[b];
-    u64 *o = n.per_broker + 6 * (size_t)b;
-    if (nd == 0) {   // no dir, so no replica: zeros, and nothing to prove
+    u64 *o = n.per_broker + W * (size_t)b;
+    if (nd == 0) {   // no dir, so no replica: zeros (the fractions 0 / 1), and nothing to prove
         if (tid == 0) {
-            for (int i = 0; i < 6; ++i) o[i] = 0;
+            for (int i = 0; i < W; ++i) o[i] = 0;
+            if constexpr (Cap) { o[1] = o[3] = o[5] = 1; o[9] = 1; }
             atomicAdd(&n.ctl[LC_PROVEN], 1ull);
         }
         return;
@@ -222,33 +325,45 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
     u64 *key = n.key + at;
     uint8_t *dst = n.dst + at;
     if (tid < LS_N) sh[tid] = tid == LS_MINBASE ? kLdNoKey : 0;
-    if (tid < nd) { load[tid] = n.base[ds + tid]; mk[tid] = kLdNoKey; }
+    if (tid < nd) {
+        ld_load<Cap>(load, tid) = n.base[ds + tid];
+        if constexpr (Cap) load[2 * tid + 1] = n.cap[ds + tid];
+        mk[tid] = kLdNoKey;
+    }
     __syncthreads();
     {   // the loads of the input, the largest size
         u64 mx = 0;
         for (int q = tid; q < nr; q += NT) {
             const int r = list[q];
             const u64 w = n.size[r];
-            if (w) atomicAdd(&load[n.dir[r] - ds], w);
+            if (w) atomicAdd(&ld_load<Cap>(load, n.dir[r] - ds), w);
             mx = max(mx, w);
         }
         if (mx) atomicMax(&sh[LS_MAXSIZE], mx);
-        if (tid < nd) {
+        if (!Cap && tid < nd) {
             const u64 x = n.base[ds + tid];
             atomicMin(&sh[LS_MINBASE], x);
             if (x) atomicMax(&sh[LS_MAXBASE], x);
         }
     }
     __syncthreads();
-    if (tid < nd) {
+    if constexpr (Cap) {   // the fullest dir of the input: a maximum over fractions, by wavefront 0
+        if (tid < 64) {
+            const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
+            u64 pn = me.l, pd = me.c;
+            int pi = tid;
+            ld_frac_reduce<true>(pn, pd, pi);
+            if (tid == 0) { sh[LS_PEAK0] = pn; sh[LS_PEAK0DEN] = pd; }
+        }
+    } else if (tid < nd) {
         const u64 x = load[tid];
         if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
     }
-    const LdTally t = ld_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
+    const LdTally t = ld_rounds<Cap>(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
     const int rounds = t.rounds, more = t.more;
     const u64 props = t.props, moves = t.moves;
     // ---- the result ----
-    if (tid < nd) {
+    if (!Cap && tid < nd) {
         const u64 x = load[tid];
         if (x) atomicMax(&sh[LS_PEAK1], x);
     }
@@ -263,13 +378,24 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
         if (props) atomicAdd(&sh[LS_PROPS], props);
     }
     __syncthreads();
+    int proof = 0;
+    if constexpr (Cap) {   // M = every replica, F' = base; the call's peaks are reduced from the rows on the host
+        if (tid >= 64) return;
+        const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
+        proof = ld_cap_bound(nd, me.l, me.c, tid < nd ? n.base[ds + tid] : 0, sh[LS_MAXSIZE], nr > 0, o + 2);
+    }
     if (tid == 0) {
-        const u64 t0 = nr ? sh[LS_MAXSIZE] + sh[LS_MINBASE] : 0, t1 = (sh[LS_TOTAL] + (u64)nd - 1) / (u64)nd;
-        const u64 lb = max(max(t0, t1), sh[LS_MAXBASE]);
-        o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = sh[LS_NMOVED]; o[4] = sh[LS_BYTES]; o[5] = (u64)rounds;
-        atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
-        atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
-        if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        if constexpr (Cap) {
+            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK0DEN]; o[6] = sh[LS_NMOVED]; o[7] = sh[LS_BYTES]; o[8] = (u64)rounds; o[9] = (u64)proof;
+            if (proof) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        } else {
+            const u64 t0 = nr ? sh[LS_MAXSIZE] + sh[LS_MINBASE] : 0, t1 = (sh[LS_TOTAL] + (u64)nd - 1) / (u64)nd;
+            const u64 lb = max(max(t0, t1), sh[LS_MAXBASE]);
+            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = sh[LS_NMOVED]; o[4] = sh[LS_BYTES]; o[5] = (u64)rounds;
+            atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
+            atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
+            if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        }
         if (rounds) {
             atomicAdd(&n.ctl[LC_BROKERS], 1ull);   // every round with a proposal applies a move
             atomicAdd(&n.ctl[LC_ROUNDS], (u64)rounds);
@@ -318,12 +444,14 @@ __device__ __forceinline__ u64 ld_readlane(u64 x, int lane) {   // lane is the s
 // lane j loading entry j; per entry a butterfly over the first `span` lanes (the power of two >= nd) leaves the lowest (L, d) in
 // lane 0, a true 64-bit compare with the lane as the tie.  The winner adds the size; lane j keeps the dir of its own entry and
 // stores it after the chunk, off the chain.
-template <class K, class I>
+// Cap: the lowest (L + w) / cap instead, by products; a lane past nd carries the highest key over 1 and sorts after every dir.
+template <bool Cap, class K, class I>
 __device__ __forceinline__ void ld_greedy(const LdNet &n, K sk, I sr, int h, int ds, int nd, u64 *load) {
     const int lane = threadIdx.x;
     int span = 1;
     while (span < nd) span *= 2;
-    u64 L = lane < nd ? load[lane] : kLdNoKey;
+    u64 L = lane < nd ? ld_load<Cap>(load, lane) : kLdNoKey;
+    const u64 C = Cap && lane < nd ? load[2 * lane + 1] : 1;
     for (int c = 0; c < h; c += 64) {
         const int m = min(64, h - c);
         u64 ks = 0;
@@ -332,14 +460,27 @@ __device__ __forceinline__ void ld_greedy(const LdNet &n, K sk, I sr, int h, int
         int mine = 0;
         for (int i = 0; i < m; ++i) {
             const u64 w = ~ld_readlane(ks, i);
-            u64 bl = L;
+            u64 bl = Cap && lane < nd ? L + w : L;
             int bd = lane;
-            for (int x = span >> 1; x >= 1; x >>= 1) {
-                const u64 ol = __shfl_xor(bl, x);
-                const int od = __shfl_xor(bd, x);
-                const bool lower = ol < bl || (ol == bl && od < bd);
-                bl = lower ? ol : bl;
-                bd = lower ? od : bd;
+            if constexpr (Cap) {
+                u64 bc = C;
+                for (int x = span >> 1; x >= 1; x >>= 1) {
+                    const u64 ol = __shfl_xor(bl, x), oc = __shfl_xor(bc, x);
+                    const int od = __shfl_xor(bd, x);
+                    const u128 theirs = (u128)ol * bc, ours = (u128)bl * oc;
+                    const bool lower = theirs < ours || (theirs == ours && od < bd);
+                    bl = lower ? ol : bl;
+                    bc = lower ? oc : bc;
+                    bd = lower ? od : bd;
+                }
+            } else {
+                for (int x = span >> 1; x >= 1; x >>= 1) {
+                    const u64 ol = __shfl_xor(bl, x);
+                    const int od = __shfl_xor(bd, x);
+                    const bool lower = ol < bl || (ol == bl && od < bd);
+                    bl = lower ? ol : bl;
+                    bd = lower ? od : bd;
+                }
             }
             bd = __builtin_amdgcn_readlane(bd, 0);
             if (lane == bd) L += w;
@@ -347,24 +488,28 @@ __device__ __forceinline__ void ld_greedy(const LdNet &n, K sk, I sr, int h, int
         }
         if (lane < m) n.dir[rr] = ds + mine;
     }
-    if (lane < nd) load[lane] = L;
+    if (lane < nd) ld_load<Cap>(load, lane) = L;
 }
 
 // One workgroup per broker: the loads F of the residents, the homeless replicas compacted and sorted, PLACE, with move_residents the
 // rounds over every replica of the broker, then the bound and the row of per_broker.  Dynamic LDS: the sort entries of the LDS path,
 // sizes u64[sort_cap] and then r u32[sort_cap]; the other path sorts in key[] and sr[] at the bucket's place, which this workgroup
 // alone touches (the rounds write key[] before they read it).
+template <bool Cap>
 __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
     extern __shared__ u64 ld_dyn[];
-    __shared__ u64 load[kLdMaxDirs], mk[kLdMaxDirs], sh[LS_N];
+    __shared__ alignas(16) u64 load[(Cap ? 2 : 1) * kLdMaxDirs];   // 16 bytes: RANK reads two loads (Cap: one {load, cap}) with one 128-bit LDS read
+    __shared__ u64 mk[kLdMaxDirs], sh[LS_N];
     __shared__ uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
     __shared__ int fill;
+    constexpr int W = Cap ? 12 : 8;   // columns of a row of per_broker
     const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
     const int ds = n.dir_start[b], nd = n.dir_start[b + 1] - ds, nr = n.cnt[b], at = n.start[b], h = n.hcnt[b];
-    u64 *o = n.per_broker + 8 * (size_t)b;
-    if (nd == 0) {   // no dir, so no replica: zeros, and nothing to prove
+    u64 *o = n.per_broker + W * (size_t)b;
+    if (nd == 0) {   // no dir, so no replica: zeros (the fractions 0 / 1), and nothing to prove
         if (tid == 0) {
-            for (int i = 0; i < 8; ++i) o[i] = 0;
+            for (int i = 0; i < W; ++i) o[i] = 0;
+            if constexpr (Cap) { o[1] = o[3] = o[5] = 1; o[11] = 1; }
             atomicAdd(&n.ctl[LC_PROVEN], 1ull);
         }
         return;
@@ -376,7 +521,11 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
     u64 *lk = ld_dyn;
     uint32_t *lr = reinterpret_cast<uint32_t *>(ld_dyn + n.sort_cap);
     if (tid < LS_N) sh[tid] = (tid == LS_MINBASE || tid == LS_MINF) ? kLdNoKey : 0;
-    if (tid < nd) { load[tid] = n.base[ds + tid]; mk[tid] = kLdNoKey; }
+    if (tid < nd) {
+        ld_load<Cap>(load, tid) = n.base[ds + tid];
+        if constexpr (Cap) load[2 * tid + 1] = n.cap[ds + tid];
+        mk[tid] = kLdNoKey;
+    }
     if (tid == 0) fill = 0;
     __syncthreads();
     {   // the loads of the residents; the homeless replicas into the sort's entries, in any order; the largest size of those that may change dir
@@ -385,7 +534,7 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
             const int r = list[q], d = n.dir[r];
             const u64 w = n.size[r];
             if (d >= 0) {
-                if (w) atomicAdd(&load[d - ds], w);
+                if (w) atomicAdd(&ld_load<Cap>(load, d - ds), w);
                 if (n.move_residents) mx = max(mx, w);
             } else {
                 const int e = atomicAdd(&fill, 1);   // below h = hcnt[b] <= sort_cap
@@ -397,14 +546,24 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
         }
         if (mx) atomicMax(&sh[LS_MAXSIZE], mx);
         if (hb) atomicAdd(&sh[LS_HBYTES], hb);
-        if (tid < nd) {
+        if (!Cap && tid < nd) {
             const u64 x = n.base[ds + tid];
             atomicMin(&sh[LS_MINBASE], x);
             if (x) atomicMax(&sh[LS_MAXBASE], x);
         }
     }
     __syncthreads();
-    if (tid < nd) {
+    u64 fixed = 0;   // Cap: F'(d) in lane d of wavefront 0
+    if constexpr (Cap) {   // the fullest dir by F: a maximum over fractions, by wavefront 0
+        if (tid < 64) {
+            const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
+            fixed = me.l;
+            u64 pn = me.l, pd = me.c;
+            int pi = tid;
+            ld_frac_reduce<true>(pn, pd, pi);
+            if (tid == 0) { sh[LS_PEAK0] = pn; sh[LS_PEAK0DEN] = pd; }
+        }
+    } else if (tid < nd) {
         const u64 x = load[tid];
         atomicMin(&sh[LS_MINF], x);
         if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
@@ -415,15 +574,15 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
     }
     if (h >= 1) {
         if (tid < 64) {
-            if (n.sort_lds) ld_greedy(n, lk, lr, h, ds, nd, load);
-            else ld_greedy(n, key, sr, h, ds, nd, load);
+            if (n.sort_lds) ld_greedy<Cap>(n, lk, lr, h, ds, nd, load);
+            else ld_greedy<Cap>(n, key, sr, h, ds, nd, load);
         }
         __syncthreads();   // the loads and the dirs of the placed replicas, for every lane
     }
     LdTally t;
-    if (n.move_residents) t = ld_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
+    if (n.move_residents) t = ld_rounds<Cap>(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
     // ---- the result ----
-    if (tid < nd) {
+    if (!Cap && tid < nd) {
         const u64 x = load[tid];
         if (x) atomicMax(&sh[LS_PEAK1], x);
     }
@@ -438,16 +597,29 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
         if (t.props) atomicAdd(&sh[LS_PROPS], t.props);
     }
     __syncthreads();
+    // M = the replicas that may change dir, F' = the fixed loads: the homeless over F, or with move_residents all over base
+    const bool any = n.move_residents ? nr > 0 : h > 0;
+    int proof = 0;
+    if constexpr (Cap) {   // the call's peaks are reduced from the rows on the host
+        if (tid >= 64) return;
+        const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
+        if (n.move_residents) fixed = tid < nd ? n.base[ds + tid] : 0;
+        proof = ld_cap_bound(nd, me.l, me.c, fixed, sh[LS_MAXSIZE], any, o + 2);
+    }
     if (tid == 0) {
-        // M = the replicas that may change dir, F' = the fixed loads: the homeless over F, or with move_residents all over base
-        const bool any = n.move_residents ? nr > 0 : h > 0;
-        const u64 t0 = any ? sh[LS_MAXSIZE] + (n.move_residents ? sh[LS_MINBASE] : sh[LS_MINF]) : 0;
-        const u64 t1 = (sh[LS_TOTAL] + sh[LS_HBYTES] + (u64)nd - 1) / (u64)nd;   // sum of F + the homeless = sum of base + every size
-        const u64 lb = max(max(t0, t1), n.move_residents ? sh[LS_MAXBASE] : sh[LS_PEAK0]);
-        o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = (u64)h; o[4] = sh[LS_HBYTES]; o[5] = sh[LS_NMOVED]; o[6] = sh[LS_BYTES]; o[7] = (u64)t.rounds;
-        atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
-        atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
-        if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        if constexpr (Cap) {
+            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK0DEN]; o[6] = (u64)h; o[7] = sh[LS_HBYTES]; o[8] = sh[LS_NMOVED]; o[9] = sh[LS_BYTES]; o[10] = (u64)t.rounds;
+            o[11] = (u64)proof;
+            if (proof) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        } else {
+            const u64 t0 = any ? sh[LS_MAXSIZE] + (n.move_residents ? sh[LS_MINBASE] : sh[LS_MINF]) : 0;
+            const u64 t1 = (sh[LS_TOTAL] + sh[LS_HBYTES] + (u64)nd - 1) / (u64)nd;   // sum of F + the homeless = sum of base + every size
+            const u64 lb = max(max(t0, t1), n.move_residents ? sh[LS_MAXBASE] : sh[LS_PEAK0]);
+            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = (u64)h; o[4] = sh[LS_HBYTES]; o[5] = sh[LS_NMOVED]; o[6] = sh[LS_BYTES]; o[7] = (u64)t.rounds;
+            atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
+            atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
+            if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+        }
         if (h) {
             atomicAdd(&n.ctl[LC_PLACERS], 1ull);
             atomicAdd(&n.ctl[LC_NPLACED], (u64)h);
@@ -496,15 +668,39 @@ int validate_logdirs(const std::string &fn, int32_t B, const int32_t *dir_start,
     return KAO_OK;
 }
 
-}  // namespace
+// the capacity calls: every cap[d] >= 1 and a sum below 2^62, so with the loads below 2^62 every product of the two fits 128 bits
+int validate_capacity(const std::string &fn, int32_t D, const uint64_t *cap) {
+    uint64_t total = 0;
+    for (int64_t d = 0; d < D; ++d) {
+        if (cap[d] == 0) return fail(KAO_ERR_INVALID, fn + "cap[" + std::to_string(d) + "] is 0");
+        if (__builtin_add_overflow(total, cap[d], &total) || total >= (uint64_t(1) << 62)) return fail(KAO_ERR_INVALID, fn + "the capacities sum to 2^62 or more");
+    }
+    return KAO_OK;
+}
 
-extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, int32_t n_replicas, int32_t *dir, const uint64_t *size,
-                                   uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before,
-                                   uint64_t *peak_after, uint64_t *per_broker, int32_t *status, int64_t stats[8]) {
-    const std::string fn = "kao_balance_logdirs: ";
-    const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, per_broker, status};
-    int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 6);
+// {L, cap} of the fullest dir of the call from the rows of per_broker (W columns, the fraction at column `at`): the brokers in
+// order, a later one only when strictly fuller, so ties go to the lowest dir index; {0, 1} without dirs
+void peak_of_rows(const int32_t *dir_start, int B, const uint64_t *per_broker, int W, int at, uint64_t out[2]) {
+    bool have = false;
+    out[0] = 0; out[1] = 1;
+    for (int b = 0; b < B; ++b) {
+        if (dir_start[b + 1] == dir_start[b]) continue;
+        const uint64_t *o = per_broker + (size_t)W * b + at;
+        if (!have || (u128)o[0] * out[1] > (u128)out[0] * o[1]) { out[0] = o[0]; out[1] = o[1]; have = true; }
+    }
+}
+
+// the entry points: Cap (cap != NULL) is the descent by utilisation: the other instantiation of the kernels, rows of 10 / 12 columns
+// with fractions, the call's peaks reduced from the rows
+template <bool Cap>
+int balance_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, const uint64_t *cap, int32_t n_replicas,
+                    int32_t *dir, const uint64_t *size, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                    uint64_t *peak_before, uint64_t *peak_after, uint64_t *per_broker, int32_t *status, int64_t *stats) {
+    constexpr int W = Cap ? 10 : 6;
+    const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, per_broker, status, Cap ? (const void *)cap : (const void *)status};
+    int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 7);
     if (rc) return rc;
+    if (Cap && (rc = validate_capacity(fn, dir_start[n_brokers], cap))) return rc;
     if ((rc = require_init())) return rc;
     const int B = n_brokers, R = n_replicas, D = dir_start[B];
     std::vector<int32_t> bod((size_t)std::max(D, 1), 0);   // broker_of_dir
@@ -512,12 +708,12 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
         for (int d = dir_start[b]; d < dir_start[b + 1]; ++d) bod[(size_t)d] = b;
 
     // one arena: ctl u64[LC_N] | cnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] | bod i32[D] |
-    //            per_broker u64[6B] | key, size u64[R] | dir, dir0, list i32[R] | dst u8[R]
+    //            per_broker u64[6B] ([10B] with Cap) | key, size u64[R] | dir, dir0, list i32[R] | dst u8[R] | Cap: cap u64[D]
     Carve cv;
     const size_t o_ctl = cv.take<u64>(LC_N), o_cnt = cv.take<int32_t>(B), o_base = cv.take<u64>(D), zeroed = cv.end(), o_start = cv.take<int32_t>(B),
-                 o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_bod = cv.take<int32_t>(D), o_pb = cv.take<u64>(6 * (size_t)B),
+                 o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_bod = cv.take<int32_t>(D), o_pb = cv.take<u64>(W * (size_t)B),
                  o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R), o_list = cv.take<int32_t>(R),
-                 o_dst = cv.take<uint8_t>(R);
+                 o_dst = cv.take<uint8_t>(R), o_cap = cv.take<u64>(Cap ? D : 0);
     CallBufs m;
     if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
@@ -530,6 +726,7 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
     if (D) {
         HIP_TRY(hipMemcpyAsync(d_bod, bod.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, st));
         if (base) HIP_TRY(hipMemcpyAsync(d_base, base, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (Cap) HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), cap, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
     if (R) {
         HIP_TRY(hipMemcpyAsync(d_dir0, dir, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -557,13 +754,13 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
     LdNet n;
     n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
     n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
-    n.move_residents = 1; n.sort_lds = 0; n.sort_cap = 0; n.hcnt = nullptr; n.sr = nullptr;
-    k_ld_solve<<<(unsigned)B, threads, 0, st>>>(n);
+    n.move_residents = 1; n.sort_lds = 0; n.sort_cap = 0; n.hcnt = nullptr; n.sr = nullptr; n.cap = Cap ? m.at<u64>(o_cap) : nullptr;
+    k_ld_solve<Cap><<<(unsigned)B, threads, 0, st>>>(n);
     HIP_TRY(hipGetLastError());
     ++launches;
     u64 ctl[LC_N];
     HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * W * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
     if (!dry_run && ctl[LC_NMOVED]) {
@@ -572,8 +769,13 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
     }
     *n_moved = (int32_t)ctl[LC_NMOVED];
     *bytes_moved = ctl[LC_BYTES];
-    *peak_before = ctl[LC_PEAK0];
-    *peak_after = ctl[LC_PEAK1];
+    if (Cap) {
+        peak_of_rows(dir_start, B, per_broker, W, 0, peak_before);
+        peak_of_rows(dir_start, B, per_broker, W, 2, peak_after);
+    } else {
+        *peak_before = ctl[LC_PEAK0];
+        *peak_after = ctl[LC_PEAK1];
+    }
     *status = ctl[LC_PROVEN] == (u64)B ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
     if (stats) {
         stats[0] = (int64_t)ctl[LC_BROKERS]; stats[1] = (int64_t)ctl[LC_ROUNDS]; stats[2] = (int64_t)ctl[LC_MOVES]; stats[3] = (int64_t)ctl[LC_PROPS];
@@ -582,20 +784,14 @@ extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, 
     return KAO_OK;
 }
 
-extern "C" int kao_logdirs_test_sort(int32_t path) {
-    if (path < 0 || path > 2) return fail(KAO_ERR_INVALID, "kao_logdirs_test_sort: path outside 0..2");
-    const int was = t_ld_sort;
-    t_ld_sort = path;
-    return was;
-}
-
-extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, int32_t n_replicas, const int32_t *broker, int32_t *dir,
-                                 const uint64_t *size, int32_t move_residents, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_placed,
-                                 uint64_t *bytes_placed, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
-                                 uint64_t *per_broker, int32_t *status, int64_t stats[10]) {
-    const std::string fn = "kao_place_logdirs: ";
-    const void *outs[] = {broker, n_placed, bytes_placed, n_moved, bytes_moved, peak_before, peak_after, per_broker, status};
-    int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 9, -1);
+template <bool Cap>
+int place_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, const uint64_t *cap, int32_t n_replicas,
+                  const int32_t *broker, int32_t *dir, const uint64_t *size, int32_t move_residents, uint64_t min_gain, int32_t max_rounds, int32_t dry_run,
+                  int32_t *n_placed, uint64_t *bytes_placed, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                  uint64_t *per_broker, int32_t *status, int64_t *stats) {
+    constexpr int W = Cap ? 12 : 8;
+    const void *outs[] = {broker, n_placed, bytes_placed, n_moved, bytes_moved, peak_before, peak_after, per_broker, status, Cap ? (const void *)cap : (const void *)status};
+    int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 10, -1);
     if (rc) return rc;
     const int B = n_brokers, R = n_replicas, D = dir_start[B];
     for (int64_t r = 0; r < R; ++r) {
@@ -606,15 +802,16 @@ extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, co
         if (d < 0 && dir_start[b + 1] == dir_start[b])
             return fail(KAO_ERR_INVALID, fn + "replica " + std::to_string(r) + " is homeless on broker " + std::to_string(b) + ", which has no dir");
     }
+    if (Cap && (rc = validate_capacity(fn, D, cap))) return rc;
     if ((rc = require_init())) return rc;
 
-    // one arena: ctl u64[LC_N] | cnt, hcnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] | per_broker u64[8B] |
-    //            key, size u64[R] | broker, dir, dir0, list i32[R] | sr u32[R] | dst u8[R]
+    // one arena: ctl u64[LC_N] | cnt, hcnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] |
+    //            per_broker u64[8B] ([12B] with Cap) | key, size u64[R] | broker, dir, dir0, list i32[R] | sr u32[R] | dst u8[R] | Cap: cap u64[D]
     Carve cv;
     const size_t o_ctl = cv.take<u64>(LC_N), o_cnt = cv.take<int32_t>(B), o_hcnt = cv.take<int32_t>(B), o_base = cv.take<u64>(D), zeroed = cv.end(),
-                 o_start = cv.take<int32_t>(B), o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_pb = cv.take<u64>(8 * (size_t)B),
+                 o_start = cv.take<int32_t>(B), o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_pb = cv.take<u64>(W * (size_t)B),
                  o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_broker = cv.take<int32_t>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R),
-                 o_list = cv.take<int32_t>(R), o_sr = cv.take<uint32_t>(R), o_dst = cv.take<uint8_t>(R);
+                 o_list = cv.take<int32_t>(R), o_sr = cv.take<uint32_t>(R), o_dst = cv.take<uint8_t>(R), o_cap = cv.take<u64>(Cap ? D : 0);
     CallBufs m;
     if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
@@ -626,6 +823,7 @@ extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, co
     HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
     HIP_TRY(hipMemcpyAsync(d_ds, dir_start, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (D && base) HIP_TRY(hipMemcpyAsync(d_base, base, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (Cap && D) HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), cap, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (R) {
         HIP_TRY(hipMemcpyAsync(d_broker, broker, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_dir0, dir, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -659,12 +857,13 @@ extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, co
     n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
     n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
     n.move_residents = move_residents ? 1 : 0; n.sort_lds = lds ? 1 : 0; n.sort_cap = lds ? (int)max_n[1] : 0; n.hcnt = d_hcnt; n.sr = m.at<uint32_t>(o_sr);
-    k_ld_place<<<(unsigned)B, threads, (size_t)n.sort_cap * (sizeof(u64) + sizeof(uint32_t)), st>>>(n);
+    n.cap = Cap ? m.at<u64>(o_cap) : nullptr;
+    k_ld_place<Cap><<<(unsigned)B, threads, (size_t)n.sort_cap * (sizeof(u64) + sizeof(uint32_t)), st>>>(n);
     HIP_TRY(hipGetLastError());
     ++launches;
     u64 ctl[LC_N];
     HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * W * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
     if (!dry_run && (ctl[LC_NPLACED] || ctl[LC_NMOVED])) {
@@ -675,8 +874,13 @@ extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, co
     *bytes_placed = ctl[LC_BPLACED];
     *n_moved = (int32_t)ctl[LC_NMOVED];
     *bytes_moved = ctl[LC_BYTES];
-    *peak_before = ctl[LC_PEAK0];
-    *peak_after = ctl[LC_PEAK1];
+    if (Cap) {
+        peak_of_rows(dir_start, B, per_broker, W, 0, peak_before);
+        peak_of_rows(dir_start, B, per_broker, W, 2, peak_after);
+    } else {
+        *peak_before = ctl[LC_PEAK0];
+        *peak_after = ctl[LC_PEAK1];
+    }
     *status = ctl[LC_PROVEN] == (u64)B ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
     if (stats) {
         stats[0] = (int64_t)ctl[LC_PLACERS]; stats[1] = (int64_t)ctl[LC_BROKERS]; stats[2] = (int64_t)ctl[LC_ROUNDS]; stats[3] = (int64_t)ctl[LC_MOVES];
@@ -684,4 +888,44 @@ extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, co
         stats[8] = (int64_t)ctl[LC_MAXROUNDS]; stats[9] = (int64_t)max_n[1];
     }
     return KAO_OK;
+}
+
+}  // namespace
+
+extern "C" int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, int32_t n_replicas, int32_t *dir, const uint64_t *size,
+                                   uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before,
+                                   uint64_t *peak_after, uint64_t *per_broker, int32_t *status, int64_t stats[8]) {
+    return balance_logdirs<false>("kao_balance_logdirs: ", n_brokers, dir_start, base, nullptr, n_replicas, dir, size, min_gain, max_rounds, dry_run, n_moved,
+                                  bytes_moved, peak_before, peak_after, per_broker, status, stats);
+}
+
+extern "C" int kao_balance_logdirs_capacity(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, const uint64_t *cap, int32_t n_replicas,
+                                            int32_t *dir, const uint64_t *size, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved,
+                                            uint64_t *bytes_moved, uint64_t peak_before[2], uint64_t peak_after[2], uint64_t *per_broker, int32_t *status,
+                                            int64_t stats[8]) {
+    return balance_logdirs<true>("kao_balance_logdirs_capacity: ", n_brokers, dir_start, base, cap, n_replicas, dir, size, min_gain, max_rounds, dry_run, n_moved,
+                                 bytes_moved, peak_before, peak_after, per_broker, status, stats);
+}
+
+extern "C" int kao_logdirs_test_sort(int32_t path) {
+    if (path < 0 || path > 2) return fail(KAO_ERR_INVALID, "kao_logdirs_test_sort: path outside 0..2");
+    const int was = t_ld_sort;
+    t_ld_sort = path;
+    return was;
+}
+
+extern "C" int kao_place_logdirs(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, int32_t n_replicas, const int32_t *broker, int32_t *dir,
+                                 const uint64_t *size, int32_t move_residents, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_placed,
+                                 uint64_t *bytes_placed, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                                 uint64_t *per_broker, int32_t *status, int64_t stats[10]) {
+    return place_logdirs<false>("kao_place_logdirs: ", n_brokers, dir_start, base, nullptr, n_replicas, broker, dir, size, move_residents, min_gain, max_rounds,
+                                dry_run, n_placed, bytes_placed, n_moved, bytes_moved, peak_before, peak_after, per_broker, status, stats);
+}
+
+extern "C" int kao_place_logdirs_capacity(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, const uint64_t *cap, int32_t n_replicas,
+                                          const int32_t *broker, int32_t *dir, const uint64_t *size, int32_t move_residents, uint64_t min_gain,
+                                          int32_t max_rounds, int32_t dry_run, int32_t *n_placed, uint64_t *bytes_placed, int32_t *n_moved, uint64_t *bytes_moved,
+                                          uint64_t peak_before[2], uint64_t peak_after[2], uint64_t *per_broker, int32_t *status, int64_t stats[10]) {
+    return place_logdirs<true>("kao_place_logdirs_capacity: ", n_brokers, dir_start, base, cap, n_replicas, broker, dir, size, move_residents, min_gain,
+                               max_rounds, dry_run, n_placed, bytes_placed, n_moved, bytes_moved, peak_before, peak_after, per_broker, status, stats);
 }

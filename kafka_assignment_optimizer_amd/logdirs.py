@@ -17,6 +17,13 @@ section 4p): those that the plan brings to a listed broker and those of a dir th
 dir of their broker with the fewest bytes at that moment; --rebalance lets the residents move as well (the rounds above, in the same
 call), --default-size N gives a size to an arrival that --log-dirs does not list.  The plan then lists the partitions of --plan and
 those with a placed or moved replica, with the dir's name in the slot of such a replica.
+
+With --utilisation, --capacities FILE or --default-capacity N the dirs have sizes and every mode above lowers the peak UTILISATION
+L(d) / capacity(d) instead of the peak bytes (kao_balance_logdirs_capacity, kao_place_logdirs_capacity): the
+answer for a broker whose volumes are unequal.  A usable dir takes its capacity from its entry in FILE ({"<brokerId>": {"<logDir>":
+bytes}} or {"<brokerId>": bytes} for every dir of the broker; a value is a number or a string with K/M/G/T), else with --utilisation
+from the totalBytes of the document when above 0 (Kafka >= 3.3), else from --default-capacity; a usable dir of a listed broker with
+none is a usage error.  The plan has the same format; the report gains the utilisations in parts per million and the proof.
 """
 from __future__ import annotations
 
@@ -34,12 +41,18 @@ from .solver import STATUS_NAMES, _check
 
 STAT_KEYS = ("brokers_moved", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven", "max_rounds_of_a_broker")
 PER_BROKER_KEYS = ("peak_before", "peak_after", "lower_bound", "moved", "bytes_moved", "rounds")
+# the capacity calls: the peaks and the bound are fractions {bytes, capacity}; proof: 0 gap, 1 bound met, 2 integrality test only
+CAP_PER_BROKER_KEYS = ("peak_before", "cap_before", "peak_after", "cap_after", "lower_bound_num", "lower_bound_den", "moved", "bytes_moved", "rounds", "proof")
+CAP_PLACE_PER_BROKER_KEYS = ("peak_before", "cap_before", "peak_after", "cap_after", "lower_bound_num", "lower_bound_den", "placed", "bytes_placed", "moved",
+                             "bytes_moved", "rounds", "proof")
 
 
 @dataclass
 class LogDir:
     error: Optional[str]                                                        # non-null: the dir is offline and left out
     entries: List[Tuple[str, int, int, bool]] = field(default_factory=list)    # (topic, partition, size, isFuture)
+    total_bytes: Optional[int] = None                                           # totalBytes / usableBytes of the volume (Kafka >= 3.3, KIP-827); None when absent or null
+    usable_bytes: Optional[int] = None
 
 
 @dataclass
@@ -52,6 +65,10 @@ class LogDirsResult:
     per_broker: np.ndarray   # [B, 6] uint64, see PER_BROKER_KEYS
     status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound on every broker) | "FEASIBLE_BOUND_GAP"
     stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h
+    # with capacity= alone (else None): the fullest dir as {bytes, capacity}; peak_before / peak_after are then its bytes and
+    # per_broker is [B, 10], see CAP_PER_BROKER_KEYS
+    peak_before_frac: Optional[Tuple[int, int]] = None
+    peak_after_frac: Optional[Tuple[int, int]] = None
 
 
 def parse_log_dirs(doc_or_text) -> Dict[int, Dict[str, LogDir]]:
@@ -90,6 +107,9 @@ def parse_log_dirs(doc_or_text) -> Dict[int, Dict[str, LogDir]]:
                 raise ValueError(f"log-dirs: broker {b}: log dir {name} listed twice")
             err = ld.get("error")
             d = dirs[name] = LogDir(error=None if err is None else str(err))
+            for attr, field_name in (("total_bytes", "totalBytes"), ("usable_bytes", "usableBytes")):
+                if ld.get(field_name) is not None:
+                    setattr(d, attr, _size_value(ld[field_name], f"log-dirs: broker {b}: {name}: {field_name}"))
             for e in ld.get("partitions") or []:
                 pname = e.get("partition")
                 if not isinstance(pname, str):
@@ -101,9 +121,33 @@ def parse_log_dirs(doc_or_text) -> Dict[int, Dict[str, LogDir]]:
     return out
 
 
-def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> LogDirsResult:
+def _capacity_buffer(capacity, n_dirs: int) -> np.ndarray:
+    """cap[] of a capacity call as a uint64 buffer (one spare word for a call without dirs): one integer >= 1 per dir, the sum below
+    2^62; a ValueError otherwise."""
+    if isinstance(capacity, np.ndarray) and capacity.dtype.kind in "ui" and capacity.dtype != np.bool_:   # no Python loop over an integer array
+        cp = capacity.reshape(-1)
+        if cp.shape[0] != max(n_dirs, 0):
+            raise ValueError(f"capacity must hold one value per dir ({n_dirs}), got {cp.shape[0]}")
+        if cp.size and int(cp.min()) < 1:
+            raise ValueError("capacity: every capacity must be an integer >= 1")
+        u = np.ascontiguousarray(cp, dtype=np.uint64)
+        if (int((u >> np.uint64(32)).sum()) << 32) + int((u & np.uint64(0xFFFFFFFF)).sum()) >= 1 << 62:   # the two halves: no sum passes 64 bits
+            raise ValueError("capacity: the capacities sum to 2^62 or more")
+        return u if u.size else np.ones(1, dtype=np.uint64)
+    values = list(np.asarray(capacity, dtype=object).reshape(-1))
+    if len(values) != max(n_dirs, 0):
+        raise ValueError(f"capacity must hold one value per dir ({n_dirs}), got {len(values)}")
+    if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in values):
+        raise ValueError("capacity: every capacity must be an integer >= 1")
+    if sum(int(v) for v in values) >= 1 << 62:
+        raise ValueError("capacity: the capacities sum to 2^62 or more")
+    return np.array([int(v) for v in values] or [1], dtype=np.uint64)
+
+
+def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity=None) -> LogDirsResult:
     """kao_balance_logdirs on arrays: broker b owns the dirs dir_start[b] .. dir_start[b+1]-1, replica r sits in dir[r] with size[r]
-    bytes, dir d carries base[d] bytes that never move."""
+    bytes, dir d carries base[d] bytes that never move.  capacity[d] >= 1 (the bytes of disk behind dir d) selects
+    kao_balance_logdirs_capacity: the descent lowers L(d) / capacity[d], the result carries fractions."""
     ds = np.ascontiguousarray(np.asarray(dir_start).reshape(-1), dtype=np.int32)
     if ds.shape[0] < 2:
         raise ValueError("dir_start must hold n_brokers + 1 values, n_brokers >= 1")
@@ -128,10 +172,22 @@ def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, m
             raise ValueError("bases must be integers >= 0")
         bbuf = np.ascontiguousarray(bs, dtype=np.uint64) if bs.size else np.zeros(1, dtype=np.uint64)
     stats = np.zeros(8, dtype=np.int64)
-    per = np.zeros((B, 6), dtype=np.uint64)
     n, status = C.c_int32(0), C.c_int32(0)
-    moved, before, after = (C.c_uint64(0) for _ in range(3))
     u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    if capacity is not None:
+        cbuf = _capacity_buffer(capacity, int(ds[-1]))
+        per = np.zeros((B, 10), dtype=np.uint64)
+        moved, peaks = C.c_uint64(0), np.zeros((2, 2), dtype=np.uint64)
+        _check(_ffi.load().kao_balance_logdirs_capacity(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), cbuf.ctypes.data_as(u64p),
+                                                        R, dbuf.ctypes.data_as(i32p), sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds),
+                                                        int(bool(dry_run)), C.byref(n), C.byref(moved), peaks[0].ctypes.data_as(u64p),
+                                                        peaks[1].ctypes.data_as(u64p), per.ctypes.data_as(u64p), C.byref(status),
+                                                        stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_logdirs_capacity")
+        return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(peaks[0, 0]), peak_after=int(peaks[1, 0]),
+                             per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats, peak_before_frac=(int(peaks[0, 0]), int(peaks[0, 1])),
+                             peak_after_frac=(int(peaks[1, 0]), int(peaks[1, 1])))
+    per = np.zeros((B, 6), dtype=np.uint64)
+    moved, before, after = (C.c_uint64(0) for _ in range(3))
     _check(_ffi.load().kao_balance_logdirs(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, dbuf.ctypes.data_as(i32p),
                                            sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
                                            C.byref(before), C.byref(after), per.ctypes.data_as(u64p), C.byref(status),
@@ -157,12 +213,17 @@ class PlaceLogDirsResult:
     per_broker: np.ndarray   # [B, 8] uint64, see PLACE_PER_BROKER_KEYS
     status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound on every broker) | "FEASIBLE_BOUND_GAP"
     stats: np.ndarray        # int64[10], see PLACE_STAT_KEYS / include/kao.h
+    # with capacity= alone (else None): the fullest dir as {bytes, capacity}; per_broker is then [B, 12], see CAP_PLACE_PER_BROKER_KEYS
+    peak_before_frac: Optional[Tuple[int, int]] = None
+    peak_after_frac: Optional[Tuple[int, int]] = None
 
 
 def place_logdirs_arrays(dir_start, broker, dir, size, base=None, move_residents: bool = False, min_gain: int = 0, max_rounds: int = 0,
-                         dry_run: bool = False) -> PlaceLogDirsResult:
+                         dry_run: bool = False, capacity=None) -> PlaceLogDirsResult:
     """kao_place_logdirs on arrays: replica r belongs to broker[r] and sits in dir[r], or is homeless (dir[r] == -1) and gets the
-    lightest dir of its broker, the largest replica first; with move_residents the rounds of kao_balance_logdirs follow."""
+    lightest dir of its broker, the largest replica first; with move_residents the rounds of kao_balance_logdirs follow.
+    capacity[d] >= 1 selects kao_place_logdirs_capacity: a homeless replica goes to the dir that is the least full with it, the
+    rounds lower L(d) / capacity[d], the result carries fractions."""
     ds = np.ascontiguousarray(np.asarray(dir_start).reshape(-1), dtype=np.int32)
     if ds.shape[0] < 2:
         raise ValueError("dir_start must hold n_brokers + 1 values, n_brokers >= 1")
@@ -193,10 +254,22 @@ def place_logdirs_arrays(dir_start, broker, dir, size, base=None, move_residents
             raise ValueError("bases must be integers >= 0")
         bbuf = np.ascontiguousarray(bs, dtype=np.uint64) if bs.size else np.zeros(1, dtype=np.uint64)
     stats = np.zeros(10, dtype=np.int64)
-    per = np.zeros((B, 8), dtype=np.uint64)
     placed, n, status = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     pbytes, moved, before, after = (C.c_uint64(0) for _ in range(4))
     u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    if capacity is not None:
+        cbuf = _capacity_buffer(capacity, int(ds[-1]))
+        per = np.zeros((B, 12), dtype=np.uint64)
+        peaks = np.zeros((2, 2), dtype=np.uint64)
+        _check(_ffi.load().kao_place_logdirs_capacity(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), cbuf.ctypes.data_as(u64p), R,
+                                                      rbuf.ctypes.data_as(i32p), dbuf.ctypes.data_as(i32p), sbuf.ctypes.data_as(u64p), int(bool(move_residents)),
+                                                      int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(placed), C.byref(pbytes), C.byref(n),
+                                                      C.byref(moved), peaks[0].ctypes.data_as(u64p), peaks[1].ctypes.data_as(u64p), per.ctypes.data_as(u64p),
+                                                      C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_place_logdirs_capacity")
+        return PlaceLogDirsResult(dir=d, n_placed=int(placed.value), bytes_placed=int(pbytes.value), n_moved=int(n.value), bytes_moved=int(moved.value),
+                                  peak_before=int(peaks[0, 0]), peak_after=int(peaks[1, 0]), per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats,
+                                  peak_before_frac=(int(peaks[0, 0]), int(peaks[0, 1])), peak_after_frac=(int(peaks[1, 0]), int(peaks[1, 1])))
+    per = np.zeros((B, 8), dtype=np.uint64)
     _check(_ffi.load().kao_place_logdirs(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, rbuf.ctypes.data_as(i32p),
                                          dbuf.ctypes.data_as(i32p), sbuf.ctypes.data_as(u64p), int(bool(move_residents)), int(min_gain), int(max_rounds),
                                          int(bool(dry_run)), C.byref(placed), C.byref(pbytes), C.byref(n), C.byref(moved), C.byref(before), C.byref(after),
@@ -276,6 +349,64 @@ def parse_input(current_doc: dict, log_dirs, broker_list: Optional[Sequence[int]
                         size=np.asarray(rsize, dtype=np.uint64).reshape(-1), slots=slots, keys=keys, rows=[by_key[k] for k in keys])
 
 
+def dir_capacities(broker_ids: Sequence[int], dir_names: Sequence[Sequence[str]], table: Dict[int, Dict[str, LogDir]], capacity: Optional[dict] = None,
+                   default_capacity: Optional[int] = None, use_total_bytes: bool = False) -> List[int]:
+    """capacity[d] of every usable dir, in the order of the call's dirs.  Per dir: its entry in `capacity` ({broker id: {dir name:
+    bytes}} or {broker id: bytes} for every dir of that broker; a value an integer or a string with K/M/G/T, as disk.capacity_of takes
+    them), else with use_total_bytes the totalBytes of the document when above 0, else default_capacity; a dir with none is a
+    ValueError.  Entries of brokers and dirs that the call does not hold are ignored."""
+    from .waves import parse_bytes
+
+    def value(v, what):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer, str)):
+            raise ValueError(f"capacity of {what}: not a byte count: {v!r}")
+        try:
+            return parse_bytes(str(int(v)) if not isinstance(v, str) else v)
+        except ValueError:
+            raise ValueError(f"capacity of {what}: not a byte count: {v!r}") from None
+
+    given: Dict[int, object] = {}
+    for k, v in (capacity or {}).items():
+        if isinstance(v, dict):
+            given[int(k)] = {str(n): value(x, f"log dir {int(k)}:{n}") for n, x in v.items()}
+        else:
+            given[int(k)] = value(v, f"broker {int(k)}")
+    out, missing = [], []
+    for b, names in zip(broker_ids, dir_names):
+        mine = given.get(int(b))
+        for n in names:
+            total = table.get(int(b), {}).get(n).total_bytes if use_total_bytes else None
+            if isinstance(mine, dict) and n in mine:
+                out.append(mine[n])
+            elif mine is not None and not isinstance(mine, dict):
+                out.append(mine)
+            elif total:
+                out.append(int(total))
+            elif default_capacity is not None:
+                out.append(int(default_capacity))
+            else:
+                missing.append(f"{int(b)}:{n}")
+    if missing:
+        raise ValueError("no capacity for log dirs " + ", ".join(missing[:5]) + (f" and {len(missing) - 5} more" if len(missing) > 5 else "")
+                         + " (give them in --capacities, read totalBytes with --utilisation or set --default-capacity)")
+    return out
+
+
+def _ppm(num: int, den: int) -> int:
+    return int(num) * 10 ** 6 // int(den)
+
+
+def _capacity_warnings(broker_ids, dir_names, dir_start, base, capacity) -> List[str]:
+    """One line per dir whose base alone exceeds its capacity."""
+    out = []
+    for i, b in enumerate(broker_ids):
+        for li, n in enumerate(dir_names[i]):
+            d = int(dir_start[i]) + li
+            if int(base[d]) > int(capacity[d]):
+                out.append(f"logdirs: warning: broker={b} dir={n} base={int(base[d])} exceeds capacity={int(capacity[d])}")
+    return out
+
+
 def _quoted(s: str) -> str:
     return '"' + s.replace("\\", "\\\\").replace('"', '\\"') + '"'
 
@@ -285,6 +416,7 @@ class LogDirsPlan:
     result: LogDirsResult
     input: LogDirsInput
     entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs) of the partitions with a move
+    capacity: Optional[List[int]] = None                                                  # per dir of the call, with capacities alone
 
     def document(self) -> dict:
         """The reassignment document of the partitions with a moved replica (what kafka-reassign-partitions --execute takes)."""
@@ -300,38 +432,55 @@ class LogDirsPlan:
         return report_lines(self)
 
 
-def plan_input(li: LogDirsInput, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> LogDirsPlan:
-    """kao_balance_logdirs on a LogDirsInput; the entries are the partitions with a moved replica (none with dry_run)."""
-    res = balance_logdirs_arrays(li.dir_start, li.dir, li.size, li.base, min_gain, max_rounds, dry_run)
+def plan_input(li: LogDirsInput, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity: Optional[Sequence[int]] = None) -> LogDirsPlan:
+    """kao_balance_logdirs on a LogDirsInput (kao_balance_logdirs_capacity with capacity, one value per dir of li); the entries are the
+    partitions with a moved replica (none with dry_run)."""
+    res = balance_logdirs_arrays(li.dir_start, li.dir, li.size, li.base, min_gain, max_rounds, dry_run, **({} if capacity is None else {"capacity": capacity}))
     flat = [n for names in li.dir_names for n in names]
     lists: Dict[int, List[str]] = {}
     for r in np.nonzero(res.dir != li.dir)[0]:
         k, j = li.slots[int(r)]
         lists.setdefault(k, ["any"] * len(li.rows[k]))[j] = flat[int(res.dir[r])]
     entries = [(li.keys[k][0], li.keys[k][1], list(li.rows[k]), lists[k]) for k in sorted(lists)]
-    return LogDirsPlan(result=res, input=li, entries=entries)
+    return LogDirsPlan(result=res, input=li, entries=entries, capacity=None if capacity is None else [int(x) for x in capacity])
+
+
+def _table_of(log_dirs) -> Dict[int, Dict[str, LogDir]]:
+    return log_dirs if isinstance(log_dirs, dict) and "brokers" not in log_dirs else parse_log_dirs(log_dirs)   # a parse_log_dirs table as it is
 
 
 def balance_logdirs(current_doc: dict, log_dirs, *, broker_list: Optional[Sequence[int]] = None, min_gain: int = 0, max_rounds: int = 0,
-                    dry_run: bool = False) -> LogDirsPlan:
+                    dry_run: bool = False, capacity: Optional[dict] = None, default_capacity: Optional[int] = None,
+                    use_total_bytes: bool = False) -> LogDirsPlan:
     """kao_balance_logdirs on a reassignment document and the `kafka-log-dirs --describe` output of its cluster (text, parsed JSON, or
-    the table of parse_log_dirs).  plan.document() is the reassignment document with its log_dirs lists."""
-    return plan_input(parse_input(current_doc, log_dirs, broker_list), min_gain, max_rounds, dry_run)
+    the table of parse_log_dirs).  plan.document() is the reassignment document with its log_dirs lists.  Any of capacity,
+    default_capacity and use_total_bytes gives the dirs their sizes (dir_capacities) and selects kao_balance_logdirs_capacity."""
+    table = _table_of(log_dirs)
+    li = parse_input(current_doc, table, broker_list)
+    cap = None
+    if capacity is not None or default_capacity is not None or use_total_bytes:
+        cap = dir_capacities(li.broker_ids, li.dir_names, table, capacity, default_capacity, use_total_bytes)
+    return plan_input(li, min_gain, max_rounds, dry_run, cap)
 
 
 def report_lines(plan: LogDirsPlan) -> List[str]:
     """The --report text, line for line as cli/kao-logdirs prints it: one line per broker, one for the call."""
     res, li, s = plan.result, plan.input, plan.result.stats
     per_replicas = np.bincount(np.searchsorted(li.dir_start, li.dir, side="right") - 1, minlength=len(li.broker_ids)) if len(li.dir) else [0] * len(li.broker_ids)
-    out = []
+    by_cap = res.peak_after_frac is not None
+    out = _capacity_warnings(li.broker_ids, li.dir_names, li.dir_start, li.base, plan.capacity) if by_cap else []
     for i, b in enumerate(li.broker_ids):
         p = [int(x) for x in res.per_broker[i]]
+        if by_cap:   # {peak_before, cap, peak_after, cap, bound num, den, moved, bytes_moved, rounds, proof}
+            p = [p[0], p[2], p[4], p[6], p[7], p[8], _ppm(p[0], p[1]), _ppm(p[2], p[3]), _ppm(p[4], p[5]), p[9]]
         out.append(f"logdirs: broker={b} dirs={len(li.dir_names[i])} skipped_dirs={li.skipped[i]} replicas={int(per_replicas[i])} peak_before={p[0]} "
-                   f"peak_after={p[1]} lower_bound={p[2]} moved={p[3]} bytes_moved={p[4]} rounds={p[5]}")
+                   f"peak_after={p[1]} lower_bound={p[2]} moved={p[3]} bytes_moved={p[4]} rounds={p[5]}"
+                   + (f" peak_before_ppm={p[6]} peak_after_ppm={p[7]} lower_bound_ppm={p[8]} proof={p[9]}" if by_cap else ""))
     total = sum(int(x) for x in li.size) + sum(int(x) for x in li.base)
     out.append(f"logdirs: status={res.status} brokers={len(li.broker_ids)} dirs={int(li.dir_start[-1])} skipped_dirs={sum(li.skipped)} replicas={len(li.dir)} "
                f"peak_before={res.peak_before} peak_after={res.peak_after} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
-               + " ".join(f"{k}={int(v)}" for k, v in zip(STAT_KEYS, s)))
+               + " ".join(f"{k}={int(v)}" for k, v in zip(STAT_KEYS, s))
+               + (f" peak_before_ppm={_ppm(*res.peak_before_frac)} peak_after_ppm={_ppm(*res.peak_after_frac)}" if by_cap else ""))
     return out
 
 
@@ -475,6 +624,7 @@ class PlaceLogDirsPlan:
     result: PlaceLogDirsResult
     input: PlaceInput
     entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs)
+    capacity: Optional[List[int]] = None                                                  # per dir of the call, with capacities alone
 
     def document(self) -> dict:
         """The reassignment document: the partitions of the plan and those with a placed or moved replica, each with its log_dirs."""
@@ -488,10 +638,13 @@ class PlaceLogDirsPlan:
         return place_report_lines(self)
 
 
-def place_input(pi: PlaceInput, rebalance: bool = False, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False) -> PlaceLogDirsPlan:
-    """kao_place_logdirs on a PlaceInput; the entries are the partitions of the plan and those with a placed or moved replica, the
-    dir's name in the slot of such a replica and "any" in every other (no entry with dry_run)."""
-    res = place_logdirs_arrays(pi.dir_start, pi.broker, pi.dir, pi.size, pi.base, rebalance, min_gain, max_rounds, dry_run)
+def place_input(pi: PlaceInput, rebalance: bool = False, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False,
+                capacity: Optional[Sequence[int]] = None) -> PlaceLogDirsPlan:
+    """kao_place_logdirs on a PlaceInput (kao_place_logdirs_capacity with capacity, one value per dir of pi); the entries are the
+    partitions of the plan and those with a placed or moved replica, the dir's name in the slot of such a replica and "any" in every
+    other (no entry with dry_run)."""
+    res = place_logdirs_arrays(pi.dir_start, pi.broker, pi.dir, pi.size, pi.base, rebalance, min_gain, max_rounds, dry_run,
+                               **({} if capacity is None else {"capacity": capacity}))
     entries = []
     if not dry_run:
         flat = [n for names in pi.dir_names for n in names]
@@ -500,16 +653,24 @@ def place_input(pi: PlaceInput, rebalance: bool = False, min_gain: int = 0, max_
             k, j = pi.slots[int(r)]
             lists.setdefault(k, ["any"] * len(pi.rows[k]))[j] = flat[int(res.dir[r])]
         entries = [(pi.keys[k][0], pi.keys[k][1], list(pi.rows[k]), lists[k]) for k in sorted(lists)]
-    return PlaceLogDirsPlan(result=res, input=pi, entries=entries)
+    return PlaceLogDirsPlan(result=res, input=pi, entries=entries, capacity=None if capacity is None else [int(x) for x in capacity])
 
 
 def place_logdirs(current_doc: dict, log_dirs, plan_doc: Optional[dict] = None, evacuate: Sequence[Tuple[int, str]] = (),
                   broker_list: Optional[Sequence[int]] = None, rebalance: bool = False, min_gain: int = 0, max_rounds: int = 0,
-                  default_size: Optional[int] = None, dry_run: bool = False) -> PlaceLogDirsPlan:
+                  default_size: Optional[int] = None, dry_run: bool = False, capacity: Optional[dict] = None, default_capacity: Optional[int] = None,
+                  use_total_bytes: bool = False) -> PlaceLogDirsPlan:
     """kao_place_logdirs on a reassignment document, the `kafka-log-dirs --describe` output of its cluster, a plan for some of its
     partitions and a list of (broker id, dir name) to evacuate: every replica the plan brings to a listed broker and every replica
-    of an evacuated dir gets a dir by name; with rebalance the residents may move as well (the rounds of balance_logdirs)."""
-    return place_input(parse_place_input(current_doc, log_dirs, plan_doc, evacuate, broker_list, default_size), rebalance, min_gain, max_rounds, dry_run)
+    of an evacuated dir gets a dir by name; with rebalance the residents may move as well (the rounds of balance_logdirs).  Any of
+    capacity, default_capacity and use_total_bytes gives the dirs that stay their sizes (dir_capacities) and selects
+    kao_place_logdirs_capacity."""
+    table = _table_of(log_dirs)
+    pi = parse_place_input(current_doc, table, plan_doc, evacuate, broker_list, default_size)
+    cap = None
+    if capacity is not None or default_capacity is not None or use_total_bytes:
+        cap = dir_capacities(pi.broker_ids, pi.dir_names, table, capacity, default_capacity, use_total_bytes)
+    return place_input(pi, rebalance, min_gain, max_rounds, dry_run, cap)
 
 
 def place_report_lines(plan: PlaceLogDirsPlan) -> List[str]:
@@ -518,17 +679,36 @@ def place_report_lines(plan: PlaceLogDirsPlan) -> List[str]:
     B = len(pi.broker_ids)
     homeless = np.bincount(pi.broker[pi.dir < 0], minlength=B) if len(pi.dir) else np.zeros(B, dtype=np.int64)
     residents = np.bincount(pi.broker[pi.dir >= 0], minlength=B) if len(pi.dir) else np.zeros(B, dtype=np.int64)
-    out = []
+    by_cap = res.peak_after_frac is not None
+    out = _capacity_warnings(pi.broker_ids, pi.dir_names, pi.dir_start, pi.base, plan.capacity) if by_cap else []
     for i, b in enumerate(pi.broker_ids):
         p = [int(x) for x in res.per_broker[i]]
+        if by_cap:   # {peak_before, cap, peak_after, cap, bound num, den, placed, bytes_placed, moved, bytes_moved, rounds, proof}
+            p = [p[0], p[2], p[4], p[6], p[7], p[8], p[9], p[10], _ppm(p[0], p[1]), _ppm(p[2], p[3]), _ppm(p[4], p[5]), p[11]]
         out.append(f"logdirs: broker={b} dirs={len(pi.dir_names[i])} skipped_dirs={pi.skipped[i]} evacuated_dirs={pi.evacuated[i]} "
                    f"replicas={int(residents[i] + homeless[i])} residents={int(residents[i])} homeless={int(homeless[i])} peak_before={p[0]} peak_after={p[1]} "
-                   f"lower_bound={p[2]} placed={p[3]} bytes_placed={p[4]} moved={p[5]} bytes_moved={p[6]} rounds={p[7]} stranded_bytes={pi.stranded[i]}")
+                   f"lower_bound={p[2]} placed={p[3]} bytes_placed={p[4]} moved={p[5]} bytes_moved={p[6]} rounds={p[7]} stranded_bytes={pi.stranded[i]}"
+                   + (f" peak_before_ppm={p[8]} peak_after_ppm={p[9]} lower_bound_ppm={p[10]} proof={p[11]}" if by_cap else ""))
     total = sum(int(x) for x in pi.size) + sum(int(x) for x in pi.base)
     out.append(f"logdirs: status={res.status} brokers={B} dirs={int(pi.dir_start[-1])} skipped_dirs={sum(pi.skipped)} evacuated_dirs={sum(pi.evacuated)} "
                f"replicas={len(pi.dir)} residents={int(residents.sum())} homeless={int(homeless.sum())} peak_before={res.peak_before} peak_after={res.peak_after} "
                f"replicas_placed={res.n_placed} bytes_placed={res.bytes_placed} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
-               f"stranded_bytes={sum(pi.stranded)} " + " ".join(f"{k}={int(v)}" for k, v in zip(PLACE_STAT_KEYS, s)))
+               f"stranded_bytes={sum(pi.stranded)} " + " ".join(f"{k}={int(v)}" for k, v in zip(PLACE_STAT_KEYS, s))
+               + (f" peak_before_ppm={_ppm(*res.peak_before_frac)} peak_after_ppm={_ppm(*res.peak_after_frac)}" if by_cap else ""))
+    return out
+
+
+def _capacity_file(path: str) -> dict:
+    """--capacities: a JSON file {"<brokerId>": {"<logDir>": bytes}} or {"<brokerId>": bytes}; the values as dir_capacities takes them."""
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict):
+        raise ValueError('capacities file must be a JSON object {"<brokerId>": {"<logDir>": bytes} | bytes}')
+    out = {}
+    for k, v in doc.items():
+        if not k.isdigit():
+            raise ValueError(f"capacity of broker {k}: not a broker id")
+        out[int(k)] = v
     return out
 
 
@@ -547,11 +727,15 @@ def main(argv=None) -> int:
     ap.add_argument("--evacuate", action="append", default=[], metavar="BROKER:DIR", help="empty this log dir into the broker's others (repeatable)")
     ap.add_argument("--rebalance", action="store_true", help="with --plan / --evacuate: the resident replicas may move as well")
     ap.add_argument("--default-size", default=None, help="with --plan / --evacuate: size of an arrival that --log-dirs does not list (N, or N with K/M/G/T)")
+    ap.add_argument("--utilisation", action="store_true", help="lower the peak utilisation: a dir's capacity is the totalBytes of --log-dirs (Kafka >= 3.3)")
+    ap.add_argument("--capacities", default=None, help='{"<brokerId>": {"<logDir>": bytes} | bytes} JSON file: lower the peak utilisation')
+    ap.add_argument("--default-capacity", default=None, help="bytes of disk of the dirs that have no other capacity (N, or N with K/M/G/T)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     min_gain, default_size, evacuate = 0, None, []
+    by_capacity, cap_table, default_capacity = a.utilisation or a.capacities is not None or a.default_capacity is not None, None, None
     placing = a.plan is not None or bool(a.evacuate)
     if (a.rebalance or a.default_size is not None) and not placing:
         ap.error("--rebalance and --default-size need --plan or --evacuate")
@@ -565,8 +749,27 @@ def main(argv=None) -> int:
             if not colon or not name or not (b[1:] if b.startswith("-") else b).isdigit() or len(b) > 10:
                 raise ValueError("--evacuate needs BROKER:DIR")
             evacuate.append((int(b), name))
+        if a.default_capacity is not None:
+            try:
+                default_capacity = parse_bytes(a.default_capacity)
+            except ValueError:
+                raise ValueError("--default-capacity needs a byte count (N, or N with K/M/G/T)") from None
+        if a.capacities is not None:
+            try:
+                cap_table = _capacity_file(a.capacities)
+                dir_capacities([], [], {}, cap_table)   # its values, before any document is read
+            except (OSError, ValueError) as e:
+                raise ValueError(f"--capacities: {e}")
     except ValueError as e:
         ap.error(str(e))
+
+    def capacities_of(table, inp):   # a usable dir without a capacity is a usage error
+        if not by_capacity:
+            return None
+        try:
+            return dir_capacities(inp.broker_ids, inp.dir_names, table, cap_table, default_capacity, a.utilisation)
+        except ValueError as e:
+            ap.error(str(e))
     try:
         with open(a.current) as f:
             doc = json.load(f)
@@ -579,13 +782,17 @@ def main(argv=None) -> int:
             if a.plan is not None:
                 with open(a.plan) as f:
                     plan_doc = json.load(f)
-            pi = parse_place_input(doc, text, plan_doc, evacuate, ids, default_size)   # input errors before the device is touched
+            table = parse_log_dirs(text)
+            pi = parse_place_input(doc, table, plan_doc, evacuate, ids, default_size)   # input errors before the device is touched
+            cap = capacities_of(table, pi)
             init(a.device)
-            plan = place_input(pi, a.rebalance, min_gain, a.max_rounds, a.dry_run)
+            plan = place_input(pi, a.rebalance, min_gain, a.max_rounds, a.dry_run, cap)
         else:
-            li = parse_input(doc, text, ids)   # input errors before the device is touched
+            table = parse_log_dirs(text)
+            li = parse_input(doc, table, ids)   # input errors before the device is touched
+            cap = capacities_of(table, li)
             init(a.device)
-            plan = plan_input(li, min_gain, a.max_rounds, a.dry_run)
+            plan = plan_input(li, min_gain, a.max_rounds, a.dry_run, cap)
         if a.report:
             for line in plan.report_lines():
                 print(line, file=sys.stderr)

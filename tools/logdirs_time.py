@@ -15,7 +15,14 @@ in array order, to the dir with the fewest partitions, ties to the lowest index;
 mean, the brokers proven, the rounds and the wall time as above; beside it the wall time of kao_balance_logdirs on the same brokers
 with the arrivals already resident where Kafka's rule put them, and with --ref that of the numpy restatement (tests/place_ref.py) on
 one host core.  The last lines time the single broker with its 2,500 replicas resident and nothing to place: the difference to the
-line with 2,500 homeless replicas is what compaction, sort and the greedy pass cost.  Writes profiles/place_time.txt with --write."""
+line with 2,500 homeless replicas is what compaction, sort and the greedy pass cost.  Writes profiles/place_time.txt with --write.
+
+--capacity equal|4:1 times kao_balance_logdirs_capacity and kao_place_logdirs_capacity on the shapes of both
+tables: every dir 16 GiB (equal), or every fourth dir of a broker a quarter of that (4:1).  Per line the peak utilisation before and
+after in parts per million, the utilisation that the BYTE planner's plan reaches on the same input and capacities (its dirs read
+back and measured here on the host), rounds, moves, proposals and the wall time as above; beside it, from the same session, the wall
+time of the byte sibling on the same input.  With equal capacities the two calls give the same plan, and the difference in time is
+what the 128-bit compares and the walk cost.  Writes profiles/logdirs_capacity_time.txt with --write."""
 import argparse
 import json
 import os
@@ -102,6 +109,64 @@ def time_place(a, np, lr):
             f.write("\n".join(lines) + "\n")
 
 
+def time_capacity(a, np, lr):
+    from kafka_assignment_optimizer_amd.logdirs import PLACE_STAT_KEYS, STAT_KEYS, balance_logdirs_arrays, place_logdirs_arrays
+
+    def timed(fn):
+        fn()   # warm-up
+        ms = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            res = fn()
+            ms.append(round(1e3 * (time.perf_counter() - t0), 3))
+        return res, ms
+
+    def ppm(L, cap):   # the peak utilisation of the loads L, in parts per million (integer division, as the reports print it)
+        at = max(range(len(L)), key=lambda d: (int(L[d]) * 10 ** 6 // int(cap[d]), -d))
+        return int(L[at]) * 10 ** 6 // int(cap[at])
+
+    lines = []
+    for name in a.cases.split(","):
+        B, n, k = SHAPES[name]
+        cap = np.full(B * n, 1 << 34, dtype=np.uint64)
+        if a.capacity == "4:1":
+            cap[np.arange(B * n) % n % 4 == 0] = 1 << 32
+        for sigma in (float(s) for s in a.sigmas.split(",")):
+            c = lr.lognormal_case(B, n, k, sigma, 11, zeros=0.0)
+            forms = [("balance", None)]
+            if a.place:
+                broker = c["dir"] // n
+                rank = np.empty(len(broker), dtype=np.int64)
+                rank[np.argsort(broker, kind="stable")] = np.arange(len(broker)) - np.repeat(np.arange(B) * k, k)
+                d = np.where(rank >= k - HOMELESS[name], -1, c["dir"])
+                forms = [("place", False), ("place", True)]
+            for form, move in forms:
+                if form == "balance":
+                    call = lambda **kw: balance_logdirs_arrays(c["dir_start"], c["dir"], c["size"], c["base"], **kw)
+                else:
+                    call = lambda **kw: place_logdirs_arrays(c["dir_start"], broker, d, c["size"], c["base"], move, **kw)
+                res, ms = timed(lambda: call(dry_run=True, capacity=cap))
+                _, byte_ms = timed(lambda: call(dry_run=True))
+                L_byte = lr.loads(c["dir_start"], call().dir, c["size"], c["base"])
+                L_cap = lr.loads(c["dir_start"], call(capacity=cap).dir, c["size"], c["base"])
+                assert ppm(L_cap, cap) == res.peak_after * 10 ** 6 // res.peak_after_frac[1]
+                proofs = np.bincount(res.per_broker[:, -1].astype(np.int64), minlength=3)
+                line = {"workload": name, "call": form, "capacity": a.capacity, "sigma": sigma, "brokers": B, "dirs_per_broker": n, "replicas_per_broker": k,
+                        "status": res.status, "peak_before_ppm": res.peak_before * 10 ** 6 // res.peak_before_frac[1], "peak_after_ppm": ppm(L_cap, cap),
+                        "byte_plan_peak_ppm": ppm(L_byte, cap), "replicas_moved": res.n_moved, "bytes_moved": res.bytes_moved,
+                        "proof_gap_bound_test": [int(x) for x in proofs[:3]]}
+                if form == "place":
+                    line.update({"homeless_per_broker": HOMELESS[name], "move_residents": move, "replicas_placed": res.n_placed})
+                line.update({key: int(v) for key, v in zip(PLACE_STAT_KEYS if form == "place" else STAT_KEYS, res.stats)})
+                line.update({"wall_ms": ms, "wall_ms_median": round(float(np.median(ms)), 3), "byte_sibling_wall_ms": byte_ms,
+                             "byte_sibling_wall_ms_median": round(float(np.median(byte_ms)), 3)})
+                lines.append(json.dumps(line))
+                print(lines[-1], flush=True)
+    if a.write:
+        with open(os.path.join(ROOT, "profiles", "logdirs_capacity_time.txt"), "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -110,12 +175,16 @@ def main():
     ap.add_argument("--ref", action="store_true", help="time tests/logdirs_ref.descend on the single-broker case too")
     ap.add_argument("--write", action="store_true", help="write the lines to profiles/logdirs_time.txt (profiles/place_time.txt with --place) as well")
     ap.add_argument("--place", action="store_true", help="time kao_place_logdirs instead (see the head of this file)")
+    ap.add_argument("--capacity", choices=("equal", "4:1"), default=None, help="time the capacity calls (with --place: kao_place_logdirs_capacity); "
+                    "--write appends to profiles/logdirs_capacity_time.txt")
     a = ap.parse_args()
     import numpy as np
     import kafka_assignment_optimizer_amd as kao
     from kafka_assignment_optimizer_amd.logdirs import STAT_KEYS, balance_logdirs_arrays
     import logdirs_ref as lr
     kao.init(0)
+    if a.capacity:
+        return time_capacity(a, np, lr)
     if a.place:
         return time_place(a, np, lr)
     lines = []
