@@ -1,6 +1,7 @@
 """Reference logic for kao_plan_waves (tests only): an independent checker of a wave split, the sequential first fit in
-degree-descending order, a host restatement of the kernel's best-of-orders first fit, and the exact optimum of small
-instances as a HiGHS ILP (scipy.optimize.milp).  Rows are [P, width] dense broker indices padded with NONE."""
+degree-descending order, a host restatement of the kernel's best-of-orders first fit, of its wave cap and of its order
+budget, and the exact optimum of small instances as a HiGHS ILP (scipy.optimize.milp).  Rows are [P, width] dense broker
+indices padded with NONE."""
 import numpy as np
 
 NONE = 0xFFFF
@@ -112,24 +113,53 @@ def _salt(seed, o):
     return (z ^ (z >> 31)) & M32
 
 
-def kernel_model(cur, tgt, k, seed, n_orders=64):
-    """What kao_plan_waves computes (small instances, all 64 orders): (wave, n_waves, lower_bound)."""
+def order_fits(cur, tgt, k, seed, n_orders=64):
+    """The sequential first fit of each of the kernel's first `n_orders` priority orders: a list of wave-per-partition lists
+    (empty when nothing moves)."""
     cls, parts = classify(cur, tgt)
+    if not any(c > 0 for c in cls):
+        return []
+    return [first_fit(parts, k, degree_order(parts, None if o == 0 else (lambda p, s=_salt(seed, o): _mix32(p ^ s))))
+            for o in range(n_orders)]
+
+
+def _best_of(cls, fits, lb, with_winner):
+    """The kernel's choice among `fits`: the fewest waves, the lowest order on ties."""
     wave = np.array(cls, dtype=np.int64)
     wave[wave > 0] = -2
-    best = None
-    if any(c > 0 for c in cls):
-        for o in range(n_orders):
-            salt = _salt(seed, o)
-            ww = first_fit(parts, k, degree_order(parts, None if o == 0 else (lambda p, s=salt: _mix32(p ^ s))))
-            nw = max(ww) + 1
-            if best is None or nw < best[0]:
-                best = (nw, ww)
+    winner = -1
+    n_waves = 1 if any(c == 0 for c in cls) else 0
+    if fits:
+        counts = [max(ww) + 1 for ww in fits]
+        winner = counts.index(min(counts))
+        n_waves = counts[winner]
         for p, c in enumerate(cls):
             if c > 0:
-                wave[p] = best[1][p]
-    n_waves = best[0] if best else (1 if any(c == 0 for c in cls) else 0)
-    return wave, n_waves, lower_bound(cur, tgt, k)
+                wave[p] = fits[winner][p]
+    return (wave, n_waves, lb, winner) if with_winner else (wave, n_waves, lb)
+
+
+def kernel_model(cur, tgt, k, seed, n_orders=64, with_winner=False):
+    """What kao_plan_waves computes when it runs `n_orders` orders (order_count; 64 unless the order budget binds):
+    (wave, n_waves, lower_bound), and with `with_winner` also the index of the winning order (-1: nothing moves)."""
+    return _best_of(classify(cur, tgt)[0], order_fits(cur, tgt, k, seed, n_orders), lower_bound(cur, tgt, k), with_winner)
+
+
+def wave_cap(cur, tgt, k):
+    """The second dimension of the kernel's load array: 1 + max over moving p of the sum over p's participants
+    of floor((deg(b) - 1) / k).  0 when nothing moves (the kernel then allocates no loads)."""
+    _, parts = classify(cur, tgt)
+    deg = degrees(parts)
+    return max((1 + sum((deg[b] - 1) // k for b in s) for s in parts if s), default=0)
+
+
+def order_count(B, wcap, n_mv, sized, k):
+    """Orders one call runs (order budget): as many of the 64 as fit 1 GiB of per-order state, at least 1.  Per
+    order and (broker, wave): 4 bytes of movement counts (count-only planner, or sized with k >= 1) and 8 bytes of byte loads
+    (sized); per order also 4 bytes per moving partition and three 8-byte minimum-key rows over the brokers."""
+    per_pair = (4 if (not sized or k > 0) else 0) + (8 if sized else 0)
+    per_order = B * wcap * per_pair + 4 * n_mv + 24 * B
+    return max(1, min(64, (1 << 30) // per_order))
 
 
 def ilp_min_waves(cur, tgt, k):

@@ -1,9 +1,10 @@
 """Reference logic for kao_plan_waves_sized (tests only): traffic per participant, an independent checker of a byte-capped wave
-split, the sequential first fit under both caps, a host restatement of the kernel's 64 priority orders (bit for bit), the exact
+split, the sequential first fit under both caps, a host restatement of the kernel's priority orders (bit for bit) and of its wave cap, the exact
 optimum of small instances as a HiGHS ILP, and a deterministic heavy-tailed size generator.  Rows as in waves_ref."""
 import numpy as np
 
-from waves_ref import M32, NONE, _mix32, _salt, classify, config4_pair, drift100k_pair, random_instance  # noqa: F401
+from waves_ref import (M32, NONE, _best_of, _mix32, _salt, classify, config4_pair, drift100k_pair, order_count,  # noqa: F401
+                       random_instance)
 
 LIMIT = 1 << 62
 
@@ -141,23 +142,52 @@ def first_fit_sized_waves(cur, tgt, size, C, k):
     return max(first_fit_sized(parts, traf, C, k, sized_order(parts, traf))) + 1
 
 
-def kernel_model_sized(cur, tgt, size, C, k, seed, n_orders=64):
-    """What kao_plan_waves_sized computes (small instances, all 64 orders): (wave, n_waves, lower_bound)."""
+def order_fits_sized(cur, tgt, size, C, k, seed, n_orders=64):
+    """The sequential first fit of each of the kernel's first `n_orders` priority orders (empty when nothing moves)."""
     cls, parts, traf = traffic(cur, tgt, size)
-    wave = np.array(cls, dtype=np.int64)
-    wave[wave > 0] = -2
-    best = None
-    if any(c > 0 for c in cls):
-        for o in range(n_orders):
-            ww = first_fit_sized(parts, traf, C, k, sized_order(parts, traf, o, seed))
-            nw = max(ww) + 1
-            if best is None or nw < best[0]:
-                best = (nw, ww)
-        for p, c in enumerate(cls):
-            if c > 0:
-                wave[p] = best[1][p]
-    n_waves = best[0] if best else (1 if any(c == 0 for c in cls) else 0)
-    return wave, n_waves, lower_bound_sized(cur, tgt, size, C, k)
+    if not any(c > 0 for c in cls):
+        return []
+    return [first_fit_sized(parts, traf, C, k, sized_order(parts, traf, o, seed)) for o in range(n_orders)]
+
+
+def kernel_model_sized(cur, tgt, size, C, k, seed, n_orders=64, with_winner=False):
+    """What kao_plan_waves_sized computes when it runs `n_orders` orders (order_count; 64 unless the order budget binds):
+    (wave, n_waves, lower_bound), and with `with_winner` also the index of the winning order (-1: nothing moves)."""
+    return _best_of(classify(cur, tgt)[0], order_fits_sized(cur, tgt, size, C, k, seed, n_orders),
+                    lower_bound_sized(cur, tgt, size, C, k), with_winner)
+
+
+def wave_cap_sized(cur, tgt, size, C, k):
+    """The second dimension of the kernel's load arrays: 1 + max over moving p of the sum over p's participants
+    b of the waves that can be blocked at b ahead of p's -- by count floor((deg(b) - 1) / k) (k >= 1), by bytes at most
+    min(deg(b) - 1, by) (C >= 1), where the other partitions at b carry rest = T_b - t_p(b) bytes and by = rest when
+    t_p(b) > C (every nonzero load blocks), floor(rest / (C - t_p(b) + 1)) when a blocking load (> C - t_p(b)) fits into rest at
+    all, else 0.  0 when nothing moves."""
+    _, parts, traf = traffic(cur, tgt, size)
+    tot, _ = totals(parts, traf)
+    deg = {}
+    for s in parts:
+        for b in s:
+            deg[b] = deg.get(b, 0) + 1
+    cap = 0
+    for s, ts in zip(parts, traf):
+        if not s:
+            continue
+        blocked = 0
+        for b, t in zip(s, ts):
+            if k >= 1:
+                blocked += (deg[b] - 1) // k
+            if C >= 1:
+                rest = tot[b] - t
+                if t > C:
+                    by = rest
+                elif C - t < rest:
+                    by = rest // (C - t + 1)
+                else:
+                    by = 0
+                blocked += min(deg[b] - 1, by)
+        cap = max(cap, 1 + blocked)
+    return cap
 
 
 def ilp_min_waves_sized(cur, tgt, size, C, k):
