@@ -7,7 +7,8 @@ cluster-wide leader count is as low as it can be, and the fewest leaders change.
   enumerate_all the same by trying every choice (tiny instances)
   kernel_model  the kernels' probes and phases step by step (keys of (distance, arcs), lowest tight arc id as predecessor, deficit
                 nodes served in index order, the sink's tight brokers in index order): rows, numbers and stats[0..4, 6, 7]
-and the instance families of the tests.  Rows are [P, W] arrays of dense broker indices over one broker index, NONE-padded,
+  launches      stats[5] from the solves kernel_model logged, as the entry point enqueues its kernels
+and the instance families of the tests, those on the kernels' dispatch edges at the end.  Rows are [P, W] arrays of dense broker indices over one broker index, NONE-padded,
 slot 0 = preferred leader; topic_of[p] is the topic of row p."""
 import itertools
 
@@ -150,6 +151,7 @@ class _Net:
         self.claim = np.zeros(self.P, dtype=np.int64)
         self.stamp = 0
         self.stats = dict(probes=0, phases=0, rounds=0, paths=0, maxlen=0, left=0)
+        self.solves = []   # per solve: dict(M, costed, rounds = the rounds of each phase, feasible, lead)
 
 
 def _solve(net, LO, M, costed):
@@ -167,8 +169,11 @@ def _solve(net, LO, M, costed):
     sp = np.repeat(np.arange(P), W)
     sj = np.tile(np.arange(W), P)
     ok_slot = net.pair_of[sp, sj] >= 0
+    log = dict(M=M, costed=costed, rounds=[], feasible=False, lead=lead)
+    net.solves.append(log)
     while left > 0:
         st["phases"] += 1
+        log["rounds"].append(0)
         net.stamp += 1
         keep = ok_slot & (sj != lead[sp])
         ap, aj = sp[keep], sj[keep]
@@ -187,6 +192,7 @@ def _solve(net, LO, M, costed):
         key = np.where(e > 0, SOURCE, INF).astype(np.int64)
         while True:
             st["rounds"] += 1
+            log["rounds"][-1] += 1
             new = key.copy()
             ok = key[u] != INF
             np.minimum.at(new, v[ok], key[u[ok]] + step[ok])
@@ -275,13 +281,18 @@ def _solve(net, LO, M, costed):
         if naug == 0:
             break
     st["left"] = left
+    log["feasible"] = left == 0
     return left == 0, lead, f
 
 
-def kernel_model(rows, topic_of, B, LO, tlo, thi, cluster_hi=-1):
+def kernel_model(rows, topic_of, B, LO, tlo, thi, cluster_hi=-1, solves=None):
     """(feasible, output rows, n_changed, peak_before, peak_after, stats) as kao_balance_leaders_cluster reports them; stats[5], the
-    launches, stays 0."""
+    launches, stays 0 (launches() states it).  A list given as `solves` takes one dict per solve in the order they run: its cap M,
+    costed, the rounds of each of its phases (the quiet round included), feasible and the leader slots it ended with."""
     net = _Net(rows, topic_of, B, tlo, thi)
+    if solves is not None:
+        solves.clear()
+        net.solves = solves
     rows = net.rows
     P = net.P
     peak_before = int(np.bincount(rows[:, 0], minlength=B).max()) if P else 0
@@ -317,6 +328,17 @@ def kernel_model(rows, topic_of, B, LO, tlo, thi, cluster_hi=-1):
     out[idx, 0] = rows[idx, lead]
     out[idx, lead] = rows[idx, 0]
     return True, out, int((lead != 0).sum()), peak_before, peak, stats
+
+
+def launches(P, solves, feasible):
+    """stats[5] of kao_balance_leaders_cluster from the solves kernel_model logged, as the entry point enqueues them:
+    the count (with any partition) and the input's peak; per solve the two start kernels and, when it is feasible, the peak of f; per
+    phase the seed, the rounds in batches of eight between two reads of their flags (settle_rounds: a batch is enqueued whole), the
+    predecessor bids and the extract; the apply of a feasible call with any partition."""
+    n = (1 if P else 0) + 1
+    for s in solves:
+        n += 2 + sum(1 + 8 * -(-r // 8) + 2 for r in s["rounds"]) + (1 if s["feasible"] else 0)
+    return n + (1 if feasible and P else 0)
 
 
 # ---- instance families --------------------------------------------------------------------------------------------------------
@@ -373,3 +395,71 @@ def tiny_case(seed):
         s = int(rng.integers(0, 2)); tlo.append(max(0, Pt // B - s)); thi.append(-(-Pt // B) + s)
     LO = int(rng.integers(0, 2))
     return np.array(rows, dtype=np.int64), np.array(topic_of, dtype=np.int64), B, LO, np.array(tlo), np.array(thi)
+
+
+# ---- the dispatch edges of the kernels (tests/test_flow_paths_ref.py, tests/test_gpu_cluster_leaders_paths.py) -------------------
+def chain(L, B=None):
+    """Partitions [i, i + 1] for i < L and one more [0, 1], one topic with the band [0, P], cluster_lo = 0, cluster_hi = 1, B brokers
+    (L + 1 when not given; the others idle): broker 0 leads two, and the one path runs from broker 0 to its pair, over the L partition
+    arcs, to broker L and into the sink.  One solve of one phase, one path of L + 3 arcs, L + 4 rounds with the quiet one: (rows, topic_of, B, 0, [0], [P], 1)."""
+    B = L + 1 if B is None else B
+    assert L >= 1 and B >= L + 1
+    rows = np.array([[i, i + 1] for i in range(L)] + [[0, 1]], dtype=np.int64)
+    case = rows, np.zeros(L + 1, dtype=np.int64), B, 0, np.array([0]), np.array([L + 1]), 1
+    solves = []
+    ok, out, n, before, after, stats = kernel_model(*case, solves=solves)
+    assert ok and (n, before, after) == (L, 2, 1) and (out[:L] == rows[:L, ::-1]).all() and (out[L] == rows[L]).all()
+    assert [s["rounds"] for s in solves] == [[L + 4]] and stats[:5] == [1, 1, L + 4, 1, L + 3]
+    return case
+
+
+def probes_case():
+    """P = 257 partitions of one topic on four brokers (Q = 4), cluster_hi = -1.  Broker 0 leads 104, and only the last three rows
+    (254, 255, 256) can move, one to each other broker; row 256 is the only way into broker 3.  The bisection runs infeasible probes
+    that move all three, then feasible ones: a solve that did not start from lead[256] = 0 (the row sits in the second block of
+    256) finds no arc into broker 3 and calls the optimum, 101, infeasible."""
+    one = lambda b, n: [[b, NONE, NONE]] * n
+    rows = np.array(one(0, 101) + one(1, 60) + one(2, 60) + one(3, 33) + [[0, 1, NONE], [0, 2, NONE], [0, 3, NONE]], dtype=np.int64)
+    case = rows, np.zeros(len(rows), dtype=np.int64), 4, 0, np.array([0]), np.array([len(rows)])
+    solves = []
+    ok, out, n, before, after, stats = kernel_model(*case, solves=solves)
+    assert len(rows) == 257 and stats[6] == 4 and ok and (n, before, after) == (3, 104, 101) and stats[0] >= 4
+    moved = [int(s["lead"][256]) for s in solves]
+    assert moved[-1] == 1 and any(m == 1 and not s["feasible"] for m, s in zip(moved[:-1], solves)), moved
+    return case
+
+
+def wide_index_case():
+    """chain(5) among 600 brokers: N = Q + B + 1 = 607 nodes against PW = 12 slots, so the grid of the rounds comes from N."""
+    case = chain(5, 600)
+    assert _Net(case[0], case[1], 600, case[4], case[5]).N > case[0].size
+    return case
+
+
+def deficit_case(extra):
+    """cluster_lo = 1 on 32 brokers: rows [k, 16 + k] twice for k < 16, so brokers 16..31 lead nothing and are deficit nodes.  With
+    extra = 0 one topic: Q = 32, T = 64, the last deficit node is 63 = T - 1, the last of the one 64-wide ballot.  With extra = 1 a
+    second topic of one row [0] adds a pair: Q = 33, T = 65, deficit nodes at 63 and at 64 = T - 1, alone in the second ballot."""
+    rows = [[p // 2, 16 + p // 2] for p in range(32)] + [[0, NONE]] * extra
+    topic_of = [0] * 32 + [1] * extra
+    case = np.array(rows, dtype=np.int64), np.array(topic_of, dtype=np.int64), 32, 1, np.zeros(1 + extra, dtype=np.int64), np.full(1 + extra, 2)
+    net = _Net(case[0], case[1], 32, case[4], case[5])
+    inb = np.bincount(net.bro, weights=np.clip(net.c0, net.plo, net.phi), minlength=32)
+    nodes = (net.Q + np.nonzero(inb < 1)[0]).tolist()
+    assert net.T == 64 + extra and net.T % 64 == extra and 63 in nodes and net.T - 1 in nodes and (extra == 0 or 64 in nodes), nodes
+    ok, _, n, before, after, _ = kernel_model(*case)
+    assert ok and (n, before) == (16, 2 + extra) and after == 1 + extra
+    return case
+
+
+def width8_case(seed=3):
+    """Three topics on 12 brokers in rows of width 8, 2 to 6 replicas each and NONE behind them, leaders skewed as in small_case."""
+    rng = np.random.default_rng(seed)
+    rows, topic_of = [], []
+    for t in range(3):
+        for p in range(30):
+            rf = int(rng.integers(2, 7))
+            rows.append(list(_row(rng, 12, rf, 3, 0.7)) + [NONE] * (8 - rf)); topic_of.append(t)
+    rows = np.array(rows, dtype=np.int64)
+    assert rows.shape == (90, 8) and (rows[:, 2:] == NONE).any() and (rows[:, 5] != NONE).any() and (rows[:, 6:] == NONE).all()
+    return rows, np.array(topic_of, dtype=np.int64), 12, 1, np.zeros(3, dtype=np.int64), np.full(3, 4)

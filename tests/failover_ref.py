@@ -6,10 +6,10 @@ broker or rack failure as low as it can be, with the fewest follower swaps.
   scenario_optimum  the five reported values per scenario: the HiGHS LP of the flow at a fixed cap M (a network matrix, so the LP
                     value is the integer optimum), M searched upwards from the lower end
   brute_force       the same by enumerating every choice (tiny instances)
-  kernel_model      the kernels' probes and phases step by step: output rows and the five values
+  kernel_model      the kernels' probes and phases step by step: output rows, the five values and, on request, the counters
   check_rows        the output rows are the input rows with at most one swap of e(p) and another eligible slot per row
-and the instance families of the tests.  Rows are [P, width] arrays of dense broker indices padded with NONE, slot 0 = preferred
-leader; scope 0 = single-broker failures, 1 = rack failures."""
+and the instance families of the tests, those on the kernels' dispatch edges at the end.  Rows are [P, width] arrays of dense broker
+indices padded with NONE, slot 0 = preferred leader; scope 0 = single-broker failures, 1 = rack failures."""
 import functools
 import itertools
 
@@ -160,9 +160,13 @@ K_INF = 0xFFFFFFFF
 K_SRC = 1 << 30   # (distance + 2^14) << 16 | arcs
 
 
-def _solve_model(rows, W, aff, elig, e, lead, alive, M, costed, cur):
-    """One probe at cap M from the start state j = e.  Returns feasible; cur[p] holds the chosen slots."""
+def _solve_model(rows, W, aff, elig, e, lead, alive, M, costed, cur, st=None):
+    """One probe at cap M from the start state j = e.  Returns feasible; cur[p] holds the chosen slots.  `st` ([probes, phases,
+    rounds, paths, maxlen]) takes the counters as k_fo_solve keeps them: a round is counted up to and including the quiet one; a
+    sixth entry, a set, collects the brokers marked as targets (those with room at the smallest distance) over all phases."""
     B = len(lead)
+    st = [0] * 5 if st is None else st
+    st[0] += 1
     room = np.where(alive, M - lead, 0).astype(np.int64)
     for p in aff:
         cur[p] = e[p]
@@ -170,8 +174,10 @@ def _solve_model(rows, W, aff, elig, e, lead, alive, M, costed, cur):
     left = int(np.maximum(-room, 0).sum())
     arcs = [(p, j) for p in aff for j in range(1, W) if elig[p, j]]
     while left > 0:
+        st[1] += 1
         key = np.where(room < 0, K_SRC, K_INF).astype(np.int64)
         for _ in range(B + 2):
+            st[2] += 1
             new = key.copy()
             for p, j in arcs:
                 if j == cur[p]:
@@ -189,6 +195,8 @@ def _solve_model(rows, W, aff, elig, e, lead, alive, M, costed, cur):
         if len(roomy) == 0:
             return False
         dmin = int((key[roomy] >> 16).min())
+        if len(st) > 5:
+            st[5].update(int(t) for t in roomy if (key[t] >> 16) == dmin)
         pred = {}
         for p, j in arcs:
             if j == cur[p]:
@@ -217,13 +225,18 @@ def _solve_model(rows, W, aff, elig, e, lead, alive, M, costed, cur):
                 room[v] += 1
                 room[t] -= 1
                 n += 1
+                st[4] = max(st[4], int(key[t] & 0xFFFF))
         assert n > 0
+        st[3] += n
         left -= n
     return True
 
 
-def kernel_model(rows, B, rack_of, scope, n_racks=None):
-    """(output rows, [n_scen, 5]) as the kernels compute them."""
+def kernel_model(rows, B, rack_of, scope, n_racks=None, with_stats=False, targets=None):
+    """(output rows, [n_scen, 5]) as the kernels compute them; with_stats adds [scenarios with affected partitions, probes, phases,
+    rounds, paths, maxlen] as k_fo_solve accumulates them into ctl[FS_SCEN..FS_MAXLEN]: sums over the scenarios (maxlen: their
+    max), a scenario without an affected partition contributing nothing.  A set given as `targets` collects the brokers any phase
+    marked as targets."""
     rows = np.asarray(rows, dtype=np.int64)
     W = rows.shape[1]
     cls = classify(rows, B, rack_of, scope)
@@ -231,28 +244,31 @@ def kernel_model(rows, B, rack_of, scope, n_racks=None):
     sim = simulate(rows, B, rack_of, scope, n_racks)
     out = np.zeros((len(sim), 5), dtype=np.int64)
     cur = e.copy()
+    stats = [0] * 6
     for g in range(len(sim)):
         aff, alive = _scenario_parts(rows, B, rack_of, scope, g, cls)
         out[g, :3] = sim[g]
         out[g, 3] = sim[g, 2]
         if len(aff) == 0:
             continue
+        st = [0] * 5 + ([] if targets is None else [targets])
         n_alive = int(alive.sum())
         lo = max(lower_end(lead, alive), -(-(int(lead[alive].sum()) + len(aff)) // n_alive))
         hi = int(sim[g, 2])
         while lo < hi:
             mid = (lo + hi) // 2
-            if _solve_model(rows, W, aff, elig, e, lead, alive, mid, False, cur):
+            if _solve_model(rows, W, aff, elig, e, lead, alive, mid, False, cur, st):
                 hi = mid
             else:
                 lo = mid + 1
-        assert _solve_model(rows, W, aff, elig, e, lead, alive, hi, True, cur)
+        assert _solve_model(rows, W, aff, elig, e, lead, alive, hi, True, cur, st)
         out[g, 3] = hi
         out[g, 4] = int((cur[aff] != e[aff]).sum())
+        stats = [stats[0] + 1] + [a + b for a, b in zip(stats[1:5], st[:4])] + [max(stats[5], st[4])]
     after = rows.copy()
     for p in np.nonzero(cur != e)[0]:
         after[p, e[p]], after[p, cur[p]] = rows[p, cur[p]], rows[p, e[p]]
-    return after, out
+    return (after, out, stats) if with_stats else (after, out)
 
 
 # ---- instance families ------------------------------------------------------------------------------------------------------------
@@ -359,3 +375,55 @@ def limit_instance(B, P=2000, seed=9):
     leaders = np.concatenate([[B - 1], rng.permutation(B - 1)[:39]])
     rows = np.array([leaders[rng.permutation(40)[:3]] for _ in range(P)], dtype=np.int64)
     return rows, B, rack_of, 16
+
+
+# ---- the dispatch edges of the kernels (tests/test_flow_paths_ref.py, tests/test_gpu_failover_paths.py) --------------------------
+def lds_bytes(B):
+    """Dynamic LDS of a k_fo_solve workgroup: two key buffers, pred and room of 4 bytes per broker, and the bitmap's words."""
+    return 16 * B + 4 * ((B + 31) // 32)
+
+
+def weighted_lds_bytes(B):
+    """... of a k_wfo_solve workgroup: load and mark of 8 bytes per broker."""
+    return 16 * B
+
+
+def largest_slots(rows, B, rack_of, scope, n_racks=None):
+    """affected partitions of the largest scenario x width: what picks 256 or 1,024 lanes per workgroup (at most 1,024: 256)."""
+    return int(simulate(rows, B, rack_of, scope, n_racks)[:, 0].max()) * np.asarray(rows).shape[1]
+
+
+def hot_leader_instance(n, seed=4):
+    """40 brokers in 5 racks (rack = broker % 5), width 4.  Broker 0 leads n partitions of four replicas whose first follower is, four
+    times in five, one of the brokers 1, 2, 3, 4, 6; 300 filler rows of 2 to 4 replicas led by the other brokers.  In broker scope
+    scenario 0 is the largest by far: n * 4 slots."""
+    rng = np.random.default_rng(seed)
+    B, R, W = 40, 5, 4
+    rows = np.full((n + 300, W), NONE, dtype=np.int64)
+    few = np.array([1, 2, 3, 4, 6])
+    for p in range(n):
+        rest = 1 + rng.permutation(B - 1)[:3]
+        if rng.random() < 0.8:
+            f = int(few[rng.integers(0, 5)])
+            rest = np.concatenate([[f], [b for b in rest if b != f][:2]])
+        rows[p] = np.concatenate([[0], rest])
+    for p in range(n, n + 300):
+        k = int(rng.integers(2, W + 1))
+        rows[p, :k] = 1 + rng.permutation(B - 1)[:k]
+    rack_of = np.arange(B, dtype=np.int64) % R
+    sizes = simulate(rows, B, rack_of, 0, R)[:, 0]
+    assert sizes[0] == n and sizes[1:].max() < n and largest_slots(rows, B, rack_of, 0, R) == 4 * n
+    return rows, B, rack_of, R
+
+
+def bitmap_instance(B):
+    """Broker 0 leads 2 (B - 2) partitions [0, 1, x], x running twice over 2 .. B - 1, in five racks (rack = broker % 5).  Broker 1
+    inherits them all by order, so in scenario 0 every other surviving broker has room at distance 0 and is a target of the first phase:
+    brokers 31 and 32 (the last bit of a bitmap word and the first of the next) and B - 1 among them."""
+    rows = np.array([[0, 1, 2 + p % (B - 2)] for p in range(2 * (B - 2))], dtype=np.int64)
+    rack_of = np.arange(B, dtype=np.int64) % 5
+    for scope in (0, 1):
+        targets = set()
+        kernel_model(rows, B, rack_of, scope, 5, targets=targets)
+        assert {31, 32, B - 1} <= targets, sorted(targets)
+    return rows, B, rack_of, 5

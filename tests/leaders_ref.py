@@ -6,7 +6,8 @@ broker's leader count inside [lo, hi], replica sets kept.
                 excess, a breadth-first walk over the tight arcs to the nearest deficit node
   kernel_model  the kernels' phases step by step (keys of (distance, arcs), lowest tight arc id as predecessor, deficit nodes
                 served in index order): rows, n_changed and stats[0..5, 7] bit for bit
-and the instance families of the tests.  Rows are [P, RF] arrays of dense broker indices, slot 0 = preferred leader."""
+  launches      stats[6] of the per-round regime from the rounds of each phase, as the entry point enqueues its kernels
+and the instance families of the tests (chain: one phase of a chosen length, for the settle batches and the node threshold).  Rows are [P, RF] arrays of dense broker indices, slot 0 = preferred leader."""
 import math
 from collections import deque
 
@@ -127,9 +128,10 @@ def balance_ref(rows, B, lo, hi):
     return True, swap_rows(rows, lead), int((lead != 0).sum())
 
 
-def kernel_model(rows, B, lo, hi):
+def kernel_model(rows, B, lo, hi, per_phase=None):
     """The kernels' schedule on the host: (feasible, output rows, n_changed, stats) with stats[0..5] and stats[7] as
-    kao_balance_leaders reports them (stats[6], the launches, depends on the regime and stays 0)."""
+    kao_balance_leaders reports them (stats[6], the launches, depends on the regime and stays 0; launches() states it for the
+    per-round regime).  A list given as `per_phase` takes the rounds of each phase, the quiet round included."""
     rows = np.asarray(rows, dtype=np.int64)
     P, RF = rows.shape
     T, PRF = B, P * RF
@@ -138,13 +140,17 @@ def kernel_model(rows, B, lo, hi):
     left = over + max(int(e[T]), 0)
     claim = np.zeros(P, dtype=np.int64)
     phases = rounds = paths = maxlen = 0
+    per_phase = [] if per_phase is None else per_phase
+    per_phase.clear()
     while left > 0:
         phases += 1
+        per_phase.append(0)
         u, v, c, s = _arcs(rows, lead)
         step = c * (1 << 32) + 1
         key = np.where(e > 0, SOURCE, INF).astype(np.int64)
         while True:
             rounds += 1
+            per_phase[-1] += 1
             new = key.copy()
             ok = key[u] != INF
             np.minimum.at(new, v[ok], key[u[ok]] + step[ok])
@@ -218,6 +224,29 @@ def kernel_model(rows, B, lo, hi):
     if left:
         return False, rows.copy(), 0, stats
     return True, swap_rows(rows, lead), int((lead != 0).sum()), stats
+
+
+def launches(per_phase, feasible):
+    """stats[6] of kao_balance_leaders in the per-round regime from the rounds of each phase, as the entry point enqueues them
+    (DESIGN.md 4h): the count and the start; per phase the seed, the rounds in batches of eight between two reads of their flags
+    (settle_rounds: a batch is enqueued whole), the predecessor bids and the extract; the apply when no excess is left."""
+    return 2 + sum(1 + 8 * -(-r // 8) + 2 for r in per_phase) + (1 if feasible else 0)
+
+
+def chain(L, B, lo=0):
+    """Partitions [i, i + 1] for i < L and one more [0, 1] on B brokers, of which those above L are idle, band [lo, 1]: broker 0 leads
+    two, and with lo = 0 the one path runs over the L partition arcs to broker L and into the sink: one phase, one path of L + 1
+    arcs, L + 2 rounds with the quiet one.  With lo = 1 and idle brokers the band cannot be met.  (rows, B, lo, 1)"""
+    assert L >= 1 and B >= L + 1 and lo in (0, 1)
+    rows = np.array([[i, i + 1] for i in range(L)] + [[0, 1]], dtype=np.int64)
+    per_phase = []
+    ok, out, n, stats = kernel_model(rows, B, lo, 1, per_phase)
+    if lo == 0:
+        assert ok and n == L and (out[:L] == rows[:L, ::-1]).all() and (out[L] == rows[L]).all()
+        assert per_phase == [L + 2] and stats == [1, L + 2, 1, L + 1, 1, 0, 0, 0], (per_phase, stats)
+    else:
+        assert B > L + 1 and not ok and stats[5] == B - L and stats[7] == B - L - 1, stats   # broker L is served, the idle ones are not
+    return rows, B, lo, 1
 
 
 # ---- instance families --------------------------------------------------------------------------------------------------------

@@ -143,6 +143,44 @@ def test_broker_limit(call):
     assert res.stats[0] == 40 and res.n_reordered > 0 and int(res.scen[B - 1, 0]) > 0
 
 
+CHILD = """
+import pickle, sys
+sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
+import failover_ref as fr
+import wfailover_ref as wf
+import kafka_assignment_optimizer_amd as k
+from kafka_assignment_optimizer_amd.failover import failover_order_weighted_arrays as call
+k.init(0)
+rows, B, rack_of, R = fr.limit_instance({B})
+weight = wf.lognormal_weights(len(rows), 0.7, 8)
+out = [call(rows, B, rack_of, R, 0, weight, 0, 0, dry_run=dry) for dry in (False, False, True)]   # the calls of _checked, in its order
+pickle.dump(out, open({out!r}, "wb"))
+"""
+
+
+@pytest.mark.parametrize("B", [2048, 2049])
+def test_dynamic_lds_opt_in_edge_in_a_fresh_process(kao, tmp_path, B):
+    """16 B bytes of dynamic LDS: exactly 32 KiB at B = 2048, which the entry point launches without opening the kernel, and 16
+    bytes more at B = 2049, which it opens the kernel for.  The opt-in is remembered per process, so the three calls of `_checked`
+    run in a fresh child process, the first of them the first launch of k_wfo_solve there; the parent compares what the child got."""
+    import pickle
+    assert fr.weighted_lds_bytes(B) == {2048: 32768, 2049: 32784}[B]
+    out = str(tmp_path / "result.pkl")
+    code = CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests"), B=B, out=out)
+    r = subprocess.run([sys.executable, "-c", code], timeout=120, capture_output=True, cwd=ROOT)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    got = iter(pickle.load(open(out, "rb")))
+    dry_flags = iter((False, False, True))
+
+    def replay(rows, B, rack_of, R, scope, weight, min_gain=0, max_rounds=0, dry_run=False):
+        assert dry_run == next(dry_flags)
+        return next(got)
+
+    rows, B, rack_of, R = fr.limit_instance(B)
+    res, _ = _checked(replay, rows, B, rack_of, R, 0, wf.lognormal_weights(len(rows), 0.7, 8))
+    assert res.stats[0] == 40 and res.n_reordered > 0 and int(res.scen[B - 1, 0]) > 0
+
+
 def test_edge_cases(call):
     res = call(np.zeros((0, 3)), 4, [0, 1, 0, 1], 2, 0, np.zeros(0, dtype=np.int64))   # no partition
     assert res.scen.tolist() == [[0] * 6] * 4 and res.status == "OPTIMAL_PROVEN" and res.n_reordered == 0
