@@ -20,6 +20,10 @@
 // the row of --current, "log_dirs" has the same length, the new dir's name for a moved slot and "any" for every other: what
 // kafka-reassign-partitions --execute takes for an intra-broker move.  --dry-run reports and leaves the plan empty.  --report prints
 // one line per broker and one for the call.  All computation happens in libkao.so on the GPU.
+// With --exchange a broker that has no such move left goes on with exchanges of two replicas between two of its dirs until no
+// exchange closes a gap of more than --min-gain either (kao_balance_logdirs_exchange); the report gains
+// exchange_rounds and exchanges per broker and four counters for the call.  By bytes only: a usage error together with --plan,
+// --evacuate, --rebalance, --utilisation, --capacities or --default-capacity.
 //
 // With --plan and / or --evacuate the tool gives log dirs to replicas that have none yet (kao_place_logdirs):
 //   kao-logdirs --current current.json --log-dirs log-dirs.txt [--plan plan.json] [--evacuate BROKER:DIR]... [--rebalance]
@@ -69,6 +73,7 @@ namespace {
         "                   [--min-gain N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report] [--device D]\n"
         "                   [--plan <reassignment.json>] [--evacuate <broker>:<dir>]... [--rebalance] [--default-size N[K|M|G|T]]\n"
         "                   [--utilisation] [--capacities <caps.json>] [--default-capacity N[K|M|G|T]]\n"
+        "                   [--exchange]   (the plain balance only: not with --plan, --evacuate, --rebalance or capacities)\n"
         "writes the partitions with a replica that moves to another log dir of its broker; exit status: 0 = ok, 1 = error, 2 = usage\n");
     std::exit(2);
 }
@@ -394,7 +399,7 @@ int main(int argc, char **argv) {
     std::string cur_path, brokers_csv, out_path, dirs_path, plan_path;
     std::vector<std::pair<int, std::string>> evacuate;
     int device = 0, max_rounds = 0;
-    bool report = false, dry_run = false, have_list = false, rebalance = false, have_default = false;
+    bool report = false, dry_run = false, have_list = false, rebalance = false, have_default = false, exchange = false;
     uint64_t min_gain = 0, default_size = 0;
     Capacities caps;
     std::string caps_path;
@@ -410,6 +415,7 @@ int main(int argc, char **argv) {
         else if (a == "--report") report = true;
         else if (a == "--plan") plan_path = need("--plan");
         else if (a == "--rebalance") rebalance = true;
+        else if (a == "--exchange") exchange = true;
         else if (a == "--evacuate") {
             const std::string v = need("--evacuate");
             const size_t colon = v.find(':');
@@ -441,6 +447,8 @@ int main(int argc, char **argv) {
     const bool placing = !plan_path.empty() || !evacuate.empty();
     if ((rebalance || have_default) && !placing) usage("--rebalance and --default-size need --plan or --evacuate");
     caps.on = caps.utilisation || !caps_path.empty() || caps.have_default;
+    if (exchange && (placing || caps.on))
+        usage("--exchange cannot be combined with --utilisation, --capacities, --default-capacity, --plan, --evacuate or --rebalance");
     if (!caps_path.empty()) {
         std::string msg;
         try {
@@ -542,10 +550,14 @@ int main(int argc, char **argv) {
         if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
         int32_t n_moved = 0, status = 0;
         uint64_t bytes_moved = 0, before[2] = {0, 1}, after[2] = {0, 1};
-        int64_t stats[8] = {0};
-        const size_t W = caps.on ? 10 : 6;
+        int64_t stats[12] = {0};
+        const size_t W = caps.on ? 10 : exchange ? 8 : 6;
         std::vector<uint64_t> per((size_t)B * W, 0);
-        if (caps.on) {
+        if (exchange) {
+            rc = kao_balance_logdirs_exchange(B, dir_start.data(), base.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved,
+                                              &bytes_moved, before, after, per.data(), &status, stats);
+            if (rc) throw std::runtime_error(std::string("kao_balance_logdirs_exchange: ") + kao_strerror(rc) + " " + kao_last_error());
+        } else if (caps.on) {
             rc = kao_balance_logdirs_capacity(B, dir_start.data(), base.data(), cap.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved,
                                               &bytes_moved, before, after, per.data(), &status, stats);
             if (rc) throw std::runtime_error(std::string("kao_balance_logdirs_capacity: ") + kao_strerror(rc) + " " + kao_last_error());
@@ -573,6 +585,7 @@ int main(int argc, char **argv) {
                 if (caps.on)
                     std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s lower_bound_ppm=%s proof=%llu", ppm(q[0], q[1]).c_str(), ppm(q[2], q[3]).c_str(),
                                  ppm(q[4], q[5]).c_str(), (unsigned long long)q[9]);
+                if (exchange) std::fprintf(stderr, " exchange_rounds=%llu exchanges=%llu", (unsigned long long)q[6], (unsigned long long)q[7]);
                 std::fprintf(stderr, "\n");
             }
             std::fprintf(stderr, "logdirs: status=%s brokers=%d dirs=%d skipped_dirs=%llu replicas=%d peak_before=%llu peak_after=%llu replicas_moved=%d "
@@ -581,6 +594,9 @@ int main(int argc, char **argv) {
                          status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, R, (unsigned long long)before[0],
                          (unsigned long long)after[0], n_moved, (unsigned long long)bytes_moved, total, (long long)stats[0], (long long)stats[1], (long long)stats[2],
                          (long long)stats[3], (long long)stats[4], (long long)stats[5], (long long)stats[6], (long long)stats[7]);
+            if (exchange)
+                std::fprintf(stderr, " exchange_rounds=%lld exchanges=%lld exchange_proposals=%lld brokers_lowered_by_exchange=%lld", (long long)stats[8],
+                             (long long)stats[9], (long long)stats[10], (long long)stats[11]);
             if (caps.on) std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s", ppm(before[0], before[1]).c_str(), ppm(after[0], after[1]).c_str());
             std::fprintf(stderr, "\n");
         }

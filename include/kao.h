@@ -778,6 +778,54 @@ int kao_balance_logdirs(int32_t n_brokers, const int32_t *dir_start /* [n_broker
                         int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
                         uint64_t *per_broker /* [n_brokers*6] */, int32_t *status, int64_t stats[8] /* may be NULL */);
 
+/* ---- Log-dir balance with exchange moves --------------------------------------------------------------------
+ * kao_balance_logdirs stops at a MOVE-STABLE state: no single move closes a gap.  On the small sub-problems of a broker that is often
+ * not the best state; this call is the same descent with a second kind of round that runs only when a move round would find nothing.
+ * By bytes only.  Dirs, base, size, L(d), the CSR layout, the checks and the limits are those of kao_balance_logdirs; so are dry_run,
+ * rank, order[], the move proposal, its key and the win rule.  Each broker is handled on its own, in synchronous rounds, and every
+ * round uses the loads as they stand at its start.
+ * MOVE round.  The move proposals of kao_balance_logdirs are computed; if the broker has at least one, this round is exactly a round
+ * of kao_balance_logdirs.
+ * EXCHANGE round, only when the broker has no move proposal.  PI = the broker's replicas in the order size descending, then r
+ * ascending (sizes never change: PI is fixed for the whole call).  Every replica x with size[x] > 0, on dir a of rank q, walks the
+ * dirs c of the ranks n-1, n-2, .., q+1 in that order (lightest first).  For a dir c, D = L(a) - L(c); the dir is skipped when
+ * D <= 0.  g = the number of the broker's replicas whose size s has 2 s > 2 size[x] - D (signed 64-bit arithmetic; every term stays
+ * below 2^63).  The two candidates: y_lo, the first replica of PI at a position >= g that sits on c, and y_hi, the last replica of PI
+ * at a position < g that sits on c.  A candidate y PASSES iff, with delta = size[x] - size[y]: size[y] > 0, delta > 0 and
+ * delta + min_gain < D (evaluated without overflow; min_gain is any uint64_t).  Of the passing candidates the one with the lower
+ * |2 delta - D| is taken; a tie goes to y_lo.  The first dir c of the walk that has a passing candidate gives x's proposal
+ * (x, y, a <-> c); x makes at most one proposal.  Its key is q << 48 | (0xFFFF - code(delta)) << 32 | x: the heaviest source, then the
+ * largest delta by the 16-bit code of section 4k, then the lowest index; keys are unique.  A proposal wins iff its key is the lowest
+ * of all the round's proposals that touch a and of all that touch c.  All winners are applied together: L(a) -= delta,
+ * L(c) += delta, dir[x] = c, dir[y] = a.
+ * STOP.  A broker stops when a round has neither kind of proposal, or after max_rounds rounds of that broker, both kinds counted
+ * (<= 0: no limit).
+ * WINNERS ARE DISJOINT.  Winners share no dir.  The partner y of a winner never wins in the same round: its own key carries the rank
+ * of c, which is larger than q, so it loses at c.  Hence no replica is touched twice.
+ * THE ROUNDS END AND THE PEAK NEVER RISES.  An exchange leaves both loads strictly below the old L(a) and lowers the sum of L^2 by
+ * 2 delta (D - delta) > 0.  The globally lowest key wins, so every round with a proposal applies something.
+ * COMPLETENESS.  If any y on c passes for x, then one of y_lo / y_hi does: the passing sizes form the interval
+ * (size[x] - D + min_gain, size[x]), and the two candidates bracket its midpoint size[x] - D / 2.  So the end state is move-stable AND
+ * EXCHANGE-STABLE: no pair of replicas on two dirs of a broker has 0 < delta and delta + min_gain < D.
+ * IDENTITY.  The state at the broker's first exchange round is the end state of kao_balance_logdirs, so peak_after here is <= that
+ * call's, on every broker.  On an input whose move-stable state is already exchange-stable (all positive sizes equal, for one) the
+ * two calls agree in dir[], n_moved, bytes_moved, the peaks and the shared columns.
+ * *n_moved, *bytes_moved, *peak_before, *peak_after, *status and the lower_bound terms are as in kao_balance_logdirs; moved counts the
+ * replicas whose final dir differs from their input dir.  per_broker[8b..8b+7] = {peak_before, peak_after, lower_bound, moved,
+ * bytes_moved, rounds, exchange_rounds, exchanges}.  stats (may be NULL): [0]..[7] those of kao_balance_logdirs, where rounds, moves
+ * and proposals count both kinds; [8] exchange rounds summed, [9] exchanges applied, [10] exchange proposals, [11] brokers whose
+ * peak an exchange round lowered.  Host checks and error codes are those of kao_balance_logdirs, run before any device is used, and
+ * dir[] stays untouched on error. */
+int kao_balance_logdirs_exchange(int32_t n_brokers, const int32_t *dir_start /* [n_brokers+1] */, const uint64_t *base /* [n_dirs] or NULL */,
+                                 int32_t n_replicas, int32_t *dir /* [n_replicas] in / out */, const uint64_t *size /* [n_replicas] */,
+                                 uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run,
+                                 int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                                 uint64_t *per_broker /* [n_brokers*8] */, int32_t *status, int64_t stats[12] /* may be NULL */);
+/* Test hook: where kao_balance_logdirs_exchange keeps PI and the dir masks of a broker in THIS thread's calls: 0 = by the largest
+ * bucket and the most dirs of the call (the default), 1 = in LDS (the call returns KAO_ERR_UNSUPPORTED when they do not fit), 2 = in
+ * global memory.  Returns the previous choice; both paths give the same bytes. */
+int kao_logdirs_test_exchange(int32_t path);
+
 /* ---- Log dirs for arriving and evacuated replicas -----------------------------------------------------------
  * Dirs, base, size and L(d) are those of kao_balance_logdirs.  Replica r belongs to broker broker[r].  It is a RESIDENT when
  * dir[r] >= 0, and that dir must be one of broker[r]'s; it is HOMELESS when dir[r] == -1: a replica that a plan brings to the broker,

@@ -135,6 +135,10 @@ SIGNATURES = {
                                     C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64),
                                     _P(C.c_uint64), _P(C.c_int32), _P(C.c_int64)]),
     "kao_logdirs_test_sort": (C.c_int, [C.c_int32]),
+    "kao_balance_logdirs_exchange": (C.c_int, [C.c_int32, _P(C.c_int32), _P(C.c_uint64), C.c_int32, _P(C.c_int32), _P(C.c_uint64), C.c_uint64, C.c_int32,
+                                               C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32),
+                                               _P(C.c_int64)]),
+    "kao_logdirs_test_exchange": (C.c_int, [C.c_int32]),
     "kao_balance_logdirs_capacity": (C.c_int, [C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), C.c_int32, _P(C.c_int32), _P(C.c_uint64), C.c_uint64,
                                                C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32),
                                                _P(C.c_int64)]),

@@ -31,10 +31,25 @@
 //                (ld_rounds, the one copy of the loop that k_ld_solve calls too); then the bound and the row of per_broker.
 // Its bound: M = the replicas that may change dir (the homeless; all with move_residents), F' = the fixed loads (F; base with
 // move_residents): the maximum of (0) the largest size in M + the smallest F', (1) ceil((sum of base + sum of size) / n), (2) the largest F'.
+//
+// kao_balance_logdirs_exchange is k_ld_solve<false, true>: the rounds above, and when a round has no move
+// proposal an EXCHANGE round in its place (ld_rounds<Cap, true>).  Before the rounds the workgroup sorts the bucket once into PI
+// (size descending, then r ascending; ld_sort, the network of k_ld_place) and keeps one bitmask over the positions of PI per dir: bit
+// p of mask[d] is set iff the replica at position p sits in d.  The lanes then stride over the positions of PI, not over the bucket:
+// list[] is PI's r, and key[], dst[] and partner[] are by position.  EXCHANGE PROPOSE of the replica x at position p, on a of rank q:
+// for the dirs c of the ranks n-1 .. q+1, D = L(a) - L(c) > 0, g = the first position whose size s has 2 s <= 2 size[x] - D (a binary
+// search in PI), y_lo = the next set bit of mask[c] from g, y_hi = the last one before g (word scans); the better passing candidate of
+// the first dir that has one is bid with key q << 48 | (0xFFFF - code(delta)) << 32 | x.  DECIDE is the one above.  APPLY: only a
+// winner works; it alone touches the loads and the mask rows of a and c (winners share no dir) and stores dir[x] and dir[y]: y is no
+// winner, and no lane reads the dir of a replica other than a winner's own in this part; the lanes below n clear the minkey words.
+// PI and the masks sit in dynamic LDS while the call's largest bucket holds at most kLdSortLds replicas and 12 bytes a replica + 8
+// bytes a mask word fit kLdXchgLds for that bucket and the most dirs of a broker, else in global memory at the bucket's place
+// (kao_logdirs_test_exchange forces either).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kao_host.h"
@@ -52,9 +67,12 @@ constexpr int kLdHardRounds = 1 << 26;   // no descent gets here; a guard agains
 constexpr u64 kLdNoKey = ~0ull;
 constexpr int kLdWon = 0x80;             // flag in dst[]: this round's proposal won (a destination is below 64)
 constexpr int kLdSortLds = 4096;         // kao_place_logdirs: homeless replicas of one broker sorted in dynamic LDS (12 bytes each: 48 KiB of the 64 KiB a launch gets unasked)
+constexpr int kLdXchgLds = 60 << 10;      // kao_balance_logdirs_exchange: dynamic LDS for PI and the masks of one broker; with the static 1.5 KiB a workgroup stays under the
+                                         // 64 KiB that a launch gets unasked, and two such workgroups share the 160 KiB of a compute unit
 enum { LC_PEAK0 = 0, LC_PEAK1, LC_NMOVED, LC_BYTES, LC_BROKERS, LC_ROUNDS, LC_MOVES, LC_PROPS, LC_MORE, LC_PROVEN, LC_MAXROUNDS, LC_ERR, LC_MAXN, LC_MAXH /* = LC_MAXN + 1 */,
-       LC_NPLACED, LC_BPLACED, LC_PLACERS, LC_N = 24 };
-enum { LS_PEAK0 = 0, LS_PEAK1, LS_MAXSIZE, LS_MINBASE, LS_MAXBASE, LS_TOTAL, LS_NMOVED, LS_BYTES, LS_MOVES, LS_PROPS, LS_MINF, LS_HBYTES, LS_PEAK0DEN /* Cap */, LS_N = 16 };
+       LC_NPLACED, LC_BPLACED, LC_PLACERS, LC_XROUNDS, LC_XCH, LC_XPROPS, LC_XLOWER, LC_N = 24 };
+enum { LS_PEAK0 = 0, LS_PEAK1, LS_MAXSIZE, LS_MINBASE, LS_MAXBASE, LS_TOTAL, LS_NMOVED, LS_BYTES, LS_MOVES, LS_PROPS, LS_MINF, LS_HBYTES, LS_PEAK0DEN /* Cap */, LS_XCH, LS_XPROPS,
+       LS_N = 16 };
 typedef unsigned __int128 u128;
 static_assert(kLdMaxDirs == 64, "a wavefront ranks the dirs of a broker; a destination and kLdWon share a byte");
 
@@ -77,6 +95,12 @@ struct LdNet {   // one call; every pointer is device memory
     uint32_t *sr;               // [R] by place in the bucket: the r of a sort entry on the global path (its size sits in key[])
     // the capacity calls alone (Cap; per_broker is then [10B], [12B] for k_ld_place)
     const u64 *cap;             // [n_dirs] bytes of disk behind a dir, >= 1
+};
+struct LdNetX : LdNet {         // the exchange call (X; per_broker is then [8B]): sr is PI's r on the global path.  A type of its own: the other kernels keep their arguments
+    int x_lds, x_cap, x_mcap;   // PI and the masks sit in dynamic LDS of x_cap entries and x_mcap mask words (else at the bucket's place)
+    u64 *xs;                    // [R] by place in the bucket: PI's sizes on the global path
+    u64 *xm;                    // [R + n_dirs] the masks of broker b on the global path, from word start[b] + dir_start[b]
+    uint32_t *xp;               // [R] by position in PI: the position of the partner of this round's proposal
 };
 
 // ---- Cap: the descent by utilisation u(d) = L(d) / cap(d) -------------------------------------------------------
@@ -207,11 +231,57 @@ struct LdTally {
     int rounds = 0, more = 0;
     u64 props = 0, moves = 0;
 };
-template <bool Cap>
-__device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int nr, const int32_t *list, u64 *key, uint8_t *dst, u64 *load, u64 *mk, uint8_t *rank,
-                                             uint8_t *order) {
+struct LdTallyX : LdTally {          // X: rounds, props and moves count both kinds
+    int xrounds = 0, xlowered = 0;   // the workgroup's exchange rounds; one of them lowered the peak
+    u64 xprops = 0, xch = 0;         // this lane's exchange proposals and exchanges
+};
+// X: PI and the masks of the broker: ps[p] the size at position p (descending), bit p & 63 of mask[d * words + (p >> 6)] = the replica
+// at position p sits in dir d, partner[p] the position of the partner of p's proposal.  list[] is then PI's r.
+struct LdXchg {
+    const u64 *ps = nullptr;
+    u64 *mask = nullptr;
+    uint32_t *partner = nullptr;
+    int words = 0;
+};
+// the first set bit of the mask row m at a position >= g, the last one at a position < g; -1 without one (no bit is set past nr)
+__device__ __forceinline__ int ld_next_bit(const u64 *m, int words, int g, int nr) {
+    if (g >= nr) return -1;
+    int wi = g >> 6;
+    u64 v = m[wi] & (~0ull << (g & 63));
+    while (!v) {
+        if (++wi >= words) return -1;
+        v = m[wi];
+    }
+    return wi * 64 + __ffsll((unsigned long long)v) - 1;
+}
+__device__ __forceinline__ int ld_prev_bit(const u64 *m, int g) {
+    if (g <= 0) return -1;
+    const int h = g - 1;
+    int wi = h >> 6;
+    u64 v = m[wi] & (~0ull >> (63 - (h & 63)));
+    while (!v) {
+        if (--wi < 0) return -1;
+        v = m[wi];
+    }
+    return wi * 64 + 63 - __clzll((long long)v);
+}
+// one candidate of an exchange: y of size sy for x of size w across the gap D; passes iff sy > 0, delta = w - sy > 0 and
+// delta + min_gain < D (delta < D and D - delta > min_gain: no overflow); far = |2 delta - D|
+__device__ __forceinline__ bool ld_xchg_passes(u64 w, u64 sy, u64 D, u64 min_gain, u64 &delta, u64 &far) {
+    if (!sy || w <= sy) return false;
+    delta = w - sy;
+    if (delta >= D || D - delta <= min_gain) return false;
+    far = 2 * delta > D ? 2 * delta - D : D - 2 * delta;
+    return true;
+}
+template <bool Cap, bool X = false>
+__device__ __forceinline__ std::conditional_t<X, LdTallyX, LdTally> ld_rounds(const LdNet &n, int ds, int nd, int nr, const int32_t *list, u64 *key, uint8_t *dst, u64 *load, u64 *mk, uint8_t *rank,
+                                             uint8_t *order, const LdXchg x = LdXchg()) {
+    static_assert(!(Cap && X), "exchange rounds are by bytes");
     const int tid = threadIdx.x, NT = blockDim.x;
-    LdTally t;
+    std::conditional_t<X, LdTallyX, LdTally> t;
+    [[maybe_unused]] u64 peak = 0;         // X: the peak at the start of the round before
+    [[maybe_unused]] bool was_x = false;   // X: that round was an exchange round
     for (;;) {
         if (tid < nd) {   // RANK
             int q = 0;
@@ -233,6 +303,11 @@ __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int
             order[q] = (uint8_t)tid;
         }
         __syncthreads();
+        if constexpr (X) {   // the peak is the load of the dir of rank 0
+            const u64 now = load[order[0]];
+            if (was_x && now < peak) t.xlowered = 1;
+            peak = now;
+        }
         int mine = 0;
         for (int q = tid; q < nr; q += NT) {   // PROPOSE
             const int r = list[q];
@@ -274,10 +349,59 @@ __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int
             }
             key[q] = k;   // key[q], dst[q] and dir[r] are read back by this lane alone
         }
-        if (!__syncthreads_or(mine)) break;
+        [[maybe_unused]] bool isx = false;
+        if constexpr (X) {
+            if (!__syncthreads_or(mine)) {   // no move proposal: EXCHANGE PROPOSE (every key[q] is kLdNoKey and no minkey word was bid)
+                isx = true;
+                for (int q = tid; q < nr; q += NT) {
+                    const u64 w = x.ps[q];
+                    u64 k = kLdNoKey;
+                    if (w) {
+                        const int r = list[q], a = n.dir[r] - ds, ra = rank[a];
+                        const u64 la = load[a];
+                        for (int p = nd - 1; p > ra && k == kLdNoKey; --p) {   // the lightest dir first
+                            const int c = order[p];
+                            const u64 lc = load[c];
+                            if (la <= lc || la - lc <= n.min_gain) continue;   // D <= 0; D <= min_gain: no delta > 0 has delta + min_gain < D
+                            const u64 D = la - lc;
+                            const int64_t T = 2 * (int64_t)w - (int64_t)D;     // every term below 2^63
+                            int g = 0, hi = nr;                                // g = the sizes s with 2 s > T: they come first in PI
+                            while (g < hi) {
+                                const int mid = (g + hi) >> 1;
+                                if ((int64_t)(2 * x.ps[mid]) > T) g = mid + 1;
+                                else hi = mid;
+                            }
+                            const u64 *m = x.mask + (size_t)c * x.words;
+                            const int jl = ld_next_bit(m, x.words, g, nr), jh = ld_prev_bit(m, g);
+                            int j = -1;
+                            u64 delta = 0, far = 0, dh = 0, fh = 0;
+                            if (jl >= 0 && ld_xchg_passes(w, x.ps[jl], D, n.min_gain, delta, far)) j = jl;
+                            if (jh >= 0 && ld_xchg_passes(w, x.ps[jh], D, n.min_gain, dh, fh) && (j < 0 || fh < far)) {   // a tie goes to y_lo
+                                j = jh;
+                                delta = dh;
+                            }
+                            if (j >= 0) {
+                                k = (u64)(uint32_t)ra << 48 | (u64)(0xFFFFu - wave_bytes_code(delta)) << 32 | (u64)(uint32_t)r;
+                                dst[q] = (uint8_t)c;
+                                x.partner[q] = (uint32_t)j;
+                                descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[a], k);
+                                descent_bid<__HIP_MEMORY_SCOPE_WORKGROUP>(&mk[c], k);
+                                ++mine;
+                            }
+                        }
+                    }
+                    key[q] = k;
+                }
+                if (!__syncthreads_or(mine)) break;
+            }
+        } else if (!__syncthreads_or(mine)) break;
         if ((n.max_rounds > 0 && t.rounds >= n.max_rounds) || t.rounds >= kLdHardRounds) { t.more = 1; break; }
         ++t.rounds;
         t.props += (u64)mine;
+        if constexpr (X) {
+            was_x = isx;
+            if (isx) { ++t.xrounds; t.xprops += (u64)mine; }
+        }
         for (int q = tid; q < nr; q += NT) {   // DECIDE
             const u64 k = key[q];
             if (k == kLdNoKey) continue;
@@ -285,6 +409,31 @@ __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int
             if (mk[n.dir[list[q]] - ds] == k && mk[c] == k) dst[q] = (uint8_t)(c | kLdWon);
         }
         __syncthreads();
+        if constexpr (X) {   // APPLY by the winners alone: no other lane writes a winner's dir[x] (its partner y never wins), the mask rows of a and c are its own
+            if (tid < nd) mk[tid] = kLdNoKey;   // (no lane reads a minkey word in this part)
+            for (int q = tid; q < nr; q += NT) {
+                if (key[q] == kLdNoKey || !(dst[q] & kLdWon)) continue;
+                const int r = list[q], c = dst[q] & (kLdWon - 1), a = n.dir[r] - ds;
+                u64 *ma = x.mask + (size_t)a * x.words, *mc = x.mask + (size_t)c * x.words;
+                u64 d = x.ps[q];
+                ma[q >> 6] &= ~(1ull << (q & 63));
+                mc[q >> 6] |= 1ull << (q & 63);
+                if (isx) {
+                    const int j = (int)x.partner[q];
+                    d -= x.ps[j];
+                    n.dir[list[j]] = ds + a;
+                    mc[j >> 6] &= ~(1ull << (j & 63));
+                    ma[j >> 6] |= 1ull << (j & 63);
+                    ++t.xch;
+                }
+                load[a] -= d;
+                load[c] += d;
+                n.dir[r] = ds + c;
+                ++t.moves;
+            }
+            __syncthreads();
+            continue;
+        }
         for (int q = tid; q < nr; q += NT) {   // APPLY
             if (key[q] == kLdNoKey) continue;
             const int r = list[q], s = dst[q], c = s & (kLdWon - 1), a = n.dir[r] - ds;
@@ -303,13 +452,51 @@ __device__ __forceinline__ LdTally ld_rounds(const LdNet &n, int ds, int nd, int
     return t;
 }
 
+template <class K, class I>
+__device__ __forceinline__ void ld_sort(K sk, I sr, int h);   // below, with k_ld_place
+
+// ---- the rounds with exchanges of one broker: PI into ps[] / pr[] (nr entries each), the masks into mask[]
+// (nd rows of nr / 64 + 1 words), then ld_rounds<false, true> over the positions of PI.  Called by every lane of the workgroup.
+__device__ __forceinline__ LdTallyX ld_xchg_rounds(const LdNet &n, int ds, int nd, int nr, const int32_t *list, u64 *key, uint8_t *dst, u64 *load, u64 *mk,
+                                                  uint8_t *rank, uint8_t *order, u64 *ps, u64 *mask, uint32_t *pr, uint32_t *partner) {
+    const int tid = threadIdx.x, NT = blockDim.x, words = nr / 64 + 1;
+    for (int q = tid; q < nr; q += NT) {   // the sort's entries (~size, r), in any order
+        const int r = list[q];
+        ps[q] = ~n.size[r];
+        pr[q] = (uint32_t)r;
+    }
+    for (int i = tid; i < nd * words; i += NT) mask[i] = 0;
+    __syncthreads();
+    if (nr >= 2) ld_sort(ps, pr, nr);
+    for (int q0 = tid & ~63; q0 < nr; q0 += NT) {   // 64 positions a wavefront and step: they share a mask word, one lane of each dir stores the dir's bits
+        const int q = q0 + (tid & 63);
+        int d = -1;
+        if (q < nr) {
+            ps[q] = ~ps[q];
+            d = n.dir[pr[q]] - ds;
+        }
+        for (u64 left = __ballot(d >= 0); left;) {
+            const int d0 = __shfl(d, __ffsll((unsigned long long)left) - 1);
+            const u64 same = __ballot(d == d0);
+            if ((tid & 63) == __ffsll((unsigned long long)same) - 1) mask[(size_t)d0 * words + (q0 >> 6)] = same;
+            left &= ~same;
+        }
+    }
+    // (the barrier of the first RANK comes before any read of ps[] and mask[])
+    LdXchg x;
+    x.ps = ps; x.mask = mask; x.partner = partner; x.words = words;
+    return ld_rounds<false, true>(n, ds, nd, nr, reinterpret_cast<const int32_t *>(pr), key, dst, load, mk, rank, order, x);
+}
+
 // ---- one broker ---------------------------------------------------------------------------------------------------------------------
-template <bool Cap>
-__global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
+// X (kao_balance_logdirs_exchange): dynamic LDS on the LDS path: PI's sizes u64[x_cap], the masks u64[x_mcap], PI's r u32[x_cap]; the
+// other path keeps them in xs[], xm[] and sr[] at the bucket's place, which this workgroup alone touches.
+template <bool Cap, bool X = false>
+__global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(std::conditional_t<X, LdNetX, LdNet> n) {
     __shared__ alignas(16) u64 load[(Cap ? 2 : 1) * kLdMaxDirs];   // 16 bytes: RANK reads two loads (Cap: one {load, cap}) with one 128-bit LDS read
     __shared__ u64 mk[kLdMaxDirs], sh[LS_N];
     __shared__ uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
-    constexpr int W = Cap ? 10 : 6;   // columns of a row of per_broker
+    constexpr int W = X ? 8 : Cap ? 10 : 6;   // columns of a row of per_broker
     const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
     const int ds = n.dir_start[b], nd = n.dir_start[b + 1] - ds, nr = n.cnt[b], at = n.start[b];
     u64 *o = n.per_broker + W * (size_t)b;
@@ -359,7 +546,14 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
         const u64 x = load[tid];
         if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
     }
-    const LdTally t = ld_rounds<Cap>(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
+    std::conditional_t<X, LdTallyX, LdTally> t;
+    if constexpr (X) {
+        extern __shared__ u64 ld_dyn[];
+        if (n.x_lds) t = ld_xchg_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order, ld_dyn, ld_dyn + n.x_cap, reinterpret_cast<uint32_t *>(ld_dyn + n.x_cap + n.x_mcap), n.xp + at);
+        else t = ld_xchg_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order, n.xs + at, n.xm + at + ds, n.sr + at, n.xp + at);
+    } else {
+        t = ld_rounds<Cap>(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
+    }
     const int rounds = t.rounds, more = t.more;
     const u64 props = t.props, moves = t.moves;
     // ---- the result ----
@@ -376,6 +570,10 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
         if (moved) { atomicAdd(&sh[LS_NMOVED], moved); atomicAdd(&sh[LS_BYTES], bytes); }
         if (moves) atomicAdd(&sh[LS_MOVES], moves);
         if (props) atomicAdd(&sh[LS_PROPS], props);
+        if constexpr (X) {
+            if (t.xch) atomicAdd(&sh[LS_XCH], t.xch);
+            if (t.xprops) atomicAdd(&sh[LS_XPROPS], t.xprops);
+        }
     }
     __syncthreads();
     int proof = 0;
@@ -395,6 +593,15 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(LdNet n) {
             atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
             atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
             if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+            if constexpr (X) {
+                o[6] = (u64)t.xrounds; o[7] = sh[LS_XCH];
+                if (t.xrounds) {
+                    atomicAdd(&n.ctl[LC_XROUNDS], (u64)t.xrounds);
+                    atomicAdd(&n.ctl[LC_XCH], sh[LS_XCH]);
+                    atomicAdd(&n.ctl[LC_XPROPS], sh[LS_XPROPS]);
+                    if (t.xlowered) atomicAdd(&n.ctl[LC_XLOWER], 1ull);
+                }
+            }
         }
         if (rounds) {
             atomicAdd(&n.ctl[LC_BROKERS], 1ull);   // every round with a proposal applies a move
@@ -640,6 +847,7 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
 }
 
 thread_local int t_ld_sort = 0;   // kao_logdirs_test_sort: 0 = by size, 1 = dynamic LDS, 2 = global memory
+thread_local int t_ld_xchg = 0;   // kao_logdirs_test_exchange: the same three for PI and the masks of kao_balance_logdirs_exchange
 
 int validate_logdirs(const std::string &fn, int32_t B, const int32_t *dir_start, const uint64_t *base, int32_t R, const int32_t *dir, const uint64_t *size,
                      const void *const *outs, int n_outs, int lowest_dir = 0) {
@@ -692,11 +900,12 @@ void peak_of_rows(const int32_t *dir_start, int B, const uint64_t *per_broker, i
 
 // the entry points: Cap (cap != NULL) is the descent by utilisation: the other instantiation of the kernels, rows of 10 / 12 columns
 // with fractions, the call's peaks reduced from the rows
-template <bool Cap>
+// X (kao_balance_logdirs_exchange): k_ld_solve<false, true>, rows of 8 columns, stats[12]
+template <bool Cap, bool X = false>
 int balance_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, const uint64_t *cap, int32_t n_replicas,
                     int32_t *dir, const uint64_t *size, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
                     uint64_t *peak_before, uint64_t *peak_after, uint64_t *per_broker, int32_t *status, int64_t *stats) {
-    constexpr int W = Cap ? 10 : 6;
+    constexpr int W = X ? 8 : Cap ? 10 : 6;
     const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, per_broker, status, Cap ? (const void *)cap : (const void *)status};
     int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 7);
     if (rc) return rc;
@@ -714,6 +923,8 @@ int balance_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir
                  o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_bod = cv.take<int32_t>(D), o_pb = cv.take<u64>(W * (size_t)B),
                  o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R), o_list = cv.take<int32_t>(R),
                  o_dst = cv.take<uint8_t>(R), o_cap = cv.take<u64>(Cap ? D : 0);
+    // X: xs u64[R] | xm u64[R + D] | sr, xp u32[R]
+    const size_t o_xs = cv.take<u64>(X ? R : 0), o_xm = cv.take<u64>(X ? (size_t)R + D : 0), o_sr = cv.take<uint32_t>(X ? R : 0), o_xp = cv.take<uint32_t>(X ? R : 0);
     CallBufs m;
     if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
@@ -751,11 +962,26 @@ int balance_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir
     HIP_TRY(hipStreamSynchronize(st));
     const int threads = max_n <= (u64)kLdSmallBucket ? kLdSoloSmall : kLdSoloLarge;
 
-    LdNet n;
+    std::conditional_t<X, LdNetX, LdNet> n;
     n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
     n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
     n.move_residents = 1; n.sort_lds = 0; n.sort_cap = 0; n.hcnt = nullptr; n.sr = nullptr; n.cap = Cap ? m.at<u64>(o_cap) : nullptr;
-    k_ld_solve<Cap><<<(unsigned)B, threads, 0, st>>>(n);
+    if constexpr (X) {   // PI and the masks in LDS when those of the largest bucket, with the most dirs of a broker, fit
+        int max_nd = 0;
+        for (int b = 0; b < B; ++b) max_nd = std::max(max_nd, dir_start[b + 1] - dir_start[b]);
+        const size_t mcap = (size_t)max_nd * (size_t)(max_n / 64 + 1);
+        const size_t bytes = (size_t)max_n * (sizeof(u64) + sizeof(uint32_t)) + mcap * sizeof(u64);
+        const bool fits = max_n <= (u64)kLdSortLds && bytes <= (size_t)kLdXchgLds;   // the sort's limit of k_ld_place, and the masks beside the entries
+        if (t_ld_xchg == 1 && !fits)
+            return fail(KAO_ERR_UNSUPPORTED, fn + "a broker's " + std::to_string(max_n) + " replicas on " + std::to_string(max_nd) + " dirs need " +
+                                                 std::to_string(bytes) + " bytes of LDS: more than the " + std::to_string(kLdXchgLds) + " of the LDS path");
+        const bool lds = t_ld_xchg == 2 ? false : fits;
+        n.x_lds = lds ? 1 : 0; n.x_cap = lds ? (int)max_n : 0; n.x_mcap = lds ? (int)mcap : 0;
+        n.xs = m.at<u64>(o_xs); n.xm = m.at<u64>(o_xm); n.sr = m.at<uint32_t>(o_sr); n.xp = m.at<uint32_t>(o_xp);
+        k_ld_solve<false, true><<<(unsigned)B, threads, lds ? bytes : 0, st>>>(n);
+    } else {
+        k_ld_solve<Cap><<<(unsigned)B, threads, 0, st>>>(n);
+    }
     HIP_TRY(hipGetLastError());
     ++launches;
     u64 ctl[LC_N];
@@ -780,6 +1006,7 @@ int balance_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir
     if (stats) {
         stats[0] = (int64_t)ctl[LC_BROKERS]; stats[1] = (int64_t)ctl[LC_ROUNDS]; stats[2] = (int64_t)ctl[LC_MOVES]; stats[3] = (int64_t)ctl[LC_PROPS];
         stats[4] = launches; stats[5] = (int64_t)ctl[LC_MORE]; stats[6] = (int64_t)ctl[LC_PROVEN]; stats[7] = (int64_t)ctl[LC_MAXROUNDS];
+        if (X) { stats[8] = (int64_t)ctl[LC_XROUNDS]; stats[9] = (int64_t)ctl[LC_XCH]; stats[10] = (int64_t)ctl[LC_XPROPS]; stats[11] = (int64_t)ctl[LC_XLOWER]; }
     }
     return KAO_OK;
 }
@@ -905,6 +1132,20 @@ extern "C" int kao_balance_logdirs_capacity(int32_t n_brokers, const int32_t *di
                                             int64_t stats[8]) {
     return balance_logdirs<true>("kao_balance_logdirs_capacity: ", n_brokers, dir_start, base, cap, n_replicas, dir, size, min_gain, max_rounds, dry_run, n_moved,
                                  bytes_moved, peak_before, peak_after, per_broker, status, stats);
+}
+
+extern "C" int kao_balance_logdirs_exchange(int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, int32_t n_replicas, int32_t *dir,
+                                            const uint64_t *size, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                                            uint64_t *peak_before, uint64_t *peak_after, uint64_t *per_broker, int32_t *status, int64_t stats[12]) {
+    return balance_logdirs<false, true>("kao_balance_logdirs_exchange: ", n_brokers, dir_start, base, nullptr, n_replicas, dir, size, min_gain, max_rounds, dry_run,
+                                        n_moved, bytes_moved, peak_before, peak_after, per_broker, status, stats);
+}
+
+extern "C" int kao_logdirs_test_exchange(int32_t path) {
+    if (path < 0 || path > 2) return fail(KAO_ERR_INVALID, "kao_logdirs_test_exchange: path outside 0..2");
+    const int was = t_ld_xchg;
+    t_ld_xchg = path;
+    return was;
 }
 
 extern "C" int kao_logdirs_test_sort(int32_t path) {

@@ -2,7 +2,7 @@
 (kao_balance_logdirs).
 
     python -m kafka_assignment_optimizer_amd.logdirs --current current.json --log-dirs log-dirs.txt [--broker-list 0,1,2] \
-        [--min-gain 1G] [--max-rounds N] [--dry-run] --out plan.json --report
+        [--min-gain 1G] [--max-rounds N] [--dry-run] [--exchange] --out plan.json --report
 
 Every other planner treats a broker as one disk.  A JBOD broker has several log dirs, Kafka places a new replica in the dir with the
 fewest partitions, not the fewest bytes, and the broker dies on its fullest dir.  This one reads `kafka-log-dirs --describe` output
@@ -10,7 +10,9 @@ WITH its directories and moves replicas between the dirs of their own broker (an
 no single move closes a gap of more than --min-gain bytes.  The brokers are independent; each gets a deterministic descent with a
 lower bound beside it: where peak_after == lower_bound on every broker the peaks are proven optimal.  The plan lists the partitions
 with a moved replica, `replicas` as they are and a `log_dirs` list beside them ("any" for a slot that stays), which is what
-kafka-reassign-partitions --execute takes.
+kafka-reassign-partitions --execute takes.  With --exchange a broker that has no such move left goes on with exchanges of two replicas
+between two of its dirs (kao_balance_logdirs_exchange) until no exchange closes a gap either: the peaks are never
+higher and often lower, for more bytes copied; by bytes only, so not with the placement or the utilisation modes below.
 
 With --plan FILE and / or --evacuate BROKER:DIR (repeatable) the replicas that have no dir yet get one (kao_place_logdirs, DESIGN.md
 section 4p): those that the plan brings to a listed broker and those of a dir that is being emptied go, the largest first, to the
@@ -41,6 +43,9 @@ from .solver import STATUS_NAMES, _check
 
 STAT_KEYS = ("brokers_moved", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven", "max_rounds_of_a_broker")
 PER_BROKER_KEYS = ("peak_before", "peak_after", "lower_bound", "moved", "bytes_moved", "rounds")
+# kao_balance_logdirs_exchange: rounds, moves and proposals count both kinds of round
+X_STAT_KEYS = STAT_KEYS + ("exchange_rounds", "exchanges", "exchange_proposals", "brokers_lowered_by_exchange")
+X_PER_BROKER_KEYS = PER_BROKER_KEYS + ("exchange_rounds", "exchanges")
 # the capacity calls: the peaks and the bound are fractions {bytes, capacity}; proof: 0 gap, 1 bound met, 2 integrality test only
 CAP_PER_BROKER_KEYS = ("peak_before", "cap_before", "peak_after", "cap_after", "lower_bound_num", "lower_bound_den", "moved", "bytes_moved", "rounds", "proof")
 CAP_PLACE_PER_BROKER_KEYS = ("peak_before", "cap_before", "peak_after", "cap_after", "lower_bound_num", "lower_bound_den", "placed", "bytes_placed", "moved",
@@ -62,9 +67,9 @@ class LogDirsResult:
     bytes_moved: int         # ... weighted by their sizes
     peak_before: int         # max_d L(d) of the input, over all dirs
     peak_after: int
-    per_broker: np.ndarray   # [B, 6] uint64, see PER_BROKER_KEYS
+    per_broker: np.ndarray   # [B, 6] uint64, see PER_BROKER_KEYS; [B, 8] with exchange=True, see X_PER_BROKER_KEYS
     status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound on every broker) | "FEASIBLE_BOUND_GAP"
-    stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h
+    stats: np.ndarray        # int64[8], see STAT_KEYS / include/kao.h; int64[12] with exchange=True, see X_STAT_KEYS
     # with capacity= alone (else None): the fullest dir as {bytes, capacity}; peak_before / peak_after are then its bytes and
     # per_broker is [B, 10], see CAP_PER_BROKER_KEYS
     peak_before_frac: Optional[Tuple[int, int]] = None
@@ -144,10 +149,14 @@ def _capacity_buffer(capacity, n_dirs: int) -> np.ndarray:
     return np.array([int(v) for v in values] or [1], dtype=np.uint64)
 
 
-def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity=None) -> LogDirsResult:
+def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity=None,
+                           exchange: bool = False) -> LogDirsResult:
     """kao_balance_logdirs on arrays: broker b owns the dirs dir_start[b] .. dir_start[b+1]-1, replica r sits in dir[r] with size[r]
     bytes, dir d carries base[d] bytes that never move.  capacity[d] >= 1 (the bytes of disk behind dir d) selects
-    kao_balance_logdirs_capacity: the descent lowers L(d) / capacity[d], the result carries fractions."""
+    kao_balance_logdirs_capacity: the descent lowers L(d) / capacity[d], the result carries fractions.  exchange=True selects
+    kao_balance_logdirs_exchange (bytes only): exchange rounds follow when no move is left; per_broker is [B, 8], stats int64[12]."""
+    if exchange and capacity is not None:
+        raise ValueError("exchange moves are by bytes only: exchange=True cannot be combined with capacity")
     ds = np.ascontiguousarray(np.asarray(dir_start).reshape(-1), dtype=np.int32)
     if ds.shape[0] < 2:
         raise ValueError("dir_start must hold n_brokers + 1 values, n_brokers >= 1")
@@ -186,8 +195,16 @@ def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, m
         return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(peaks[0, 0]), peak_after=int(peaks[1, 0]),
                              per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats, peak_before_frac=(int(peaks[0, 0]), int(peaks[0, 1])),
                              peak_after_frac=(int(peaks[1, 0]), int(peaks[1, 1])))
-    per = np.zeros((B, 6), dtype=np.uint64)
     moved, before, after = (C.c_uint64(0) for _ in range(3))
+    if exchange:
+        per, stats = np.zeros((B, 8), dtype=np.uint64), np.zeros(12, dtype=np.int64)
+        _check(_ffi.load().kao_balance_logdirs_exchange(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, dbuf.ctypes.data_as(i32p),
+                                                        sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
+                                                        C.byref(before), C.byref(after), per.ctypes.data_as(u64p), C.byref(status),
+                                                        stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_logdirs_exchange")
+        return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
+                             per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
+    per = np.zeros((B, 6), dtype=np.uint64)
     _check(_ffi.load().kao_balance_logdirs(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, dbuf.ctypes.data_as(i32p),
                                            sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
                                            C.byref(before), C.byref(after), per.ctypes.data_as(u64p), C.byref(status),
@@ -417,6 +434,7 @@ class LogDirsPlan:
     input: LogDirsInput
     entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs) of the partitions with a move
     capacity: Optional[List[int]] = None                                                  # per dir of the call, with capacities alone
+    exchange: bool = False                                                                # the call was kao_balance_logdirs_exchange
 
     def document(self) -> dict:
         """The reassignment document of the partitions with a moved replica (what kafka-reassign-partitions --execute takes)."""
@@ -432,17 +450,19 @@ class LogDirsPlan:
         return report_lines(self)
 
 
-def plan_input(li: LogDirsInput, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity: Optional[Sequence[int]] = None) -> LogDirsPlan:
-    """kao_balance_logdirs on a LogDirsInput (kao_balance_logdirs_capacity with capacity, one value per dir of li); the entries are the
-    partitions with a moved replica (none with dry_run)."""
-    res = balance_logdirs_arrays(li.dir_start, li.dir, li.size, li.base, min_gain, max_rounds, dry_run, **({} if capacity is None else {"capacity": capacity}))
+def plan_input(li: LogDirsInput, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity: Optional[Sequence[int]] = None,
+               exchange: bool = False) -> LogDirsPlan:
+    """kao_balance_logdirs on a LogDirsInput (kao_balance_logdirs_capacity with capacity, one value per dir of li;
+    kao_balance_logdirs_exchange with exchange); the entries are the partitions with a moved replica (none with dry_run)."""
+    res = balance_logdirs_arrays(li.dir_start, li.dir, li.size, li.base, min_gain, max_rounds, dry_run, **({} if capacity is None else {"capacity": capacity}),
+                                 **({"exchange": True} if exchange else {}))
     flat = [n for names in li.dir_names for n in names]
     lists: Dict[int, List[str]] = {}
     for r in np.nonzero(res.dir != li.dir)[0]:
         k, j = li.slots[int(r)]
         lists.setdefault(k, ["any"] * len(li.rows[k]))[j] = flat[int(res.dir[r])]
     entries = [(li.keys[k][0], li.keys[k][1], list(li.rows[k]), lists[k]) for k in sorted(lists)]
-    return LogDirsPlan(result=res, input=li, entries=entries, capacity=None if capacity is None else [int(x) for x in capacity])
+    return LogDirsPlan(result=res, input=li, entries=entries, capacity=None if capacity is None else [int(x) for x in capacity], exchange=bool(exchange))
 
 
 def _table_of(log_dirs) -> Dict[int, Dict[str, LogDir]]:
@@ -451,16 +471,19 @@ def _table_of(log_dirs) -> Dict[int, Dict[str, LogDir]]:
 
 def balance_logdirs(current_doc: dict, log_dirs, *, broker_list: Optional[Sequence[int]] = None, min_gain: int = 0, max_rounds: int = 0,
                     dry_run: bool = False, capacity: Optional[dict] = None, default_capacity: Optional[int] = None,
-                    use_total_bytes: bool = False) -> LogDirsPlan:
+                    use_total_bytes: bool = False, exchange: bool = False) -> LogDirsPlan:
     """kao_balance_logdirs on a reassignment document and the `kafka-log-dirs --describe` output of its cluster (text, parsed JSON, or
     the table of parse_log_dirs).  plan.document() is the reassignment document with its log_dirs lists.  Any of capacity,
-    default_capacity and use_total_bytes gives the dirs their sizes (dir_capacities) and selects kao_balance_logdirs_capacity."""
+    default_capacity and use_total_bytes gives the dirs their sizes (dir_capacities) and selects kao_balance_logdirs_capacity.
+    exchange=True selects kao_balance_logdirs_exchange (bytes only: a ValueError together with capacities)."""
+    if exchange and (capacity is not None or default_capacity is not None or use_total_bytes):
+        raise ValueError("exchange moves are by bytes only: exchange=True cannot be combined with capacities")
     table = _table_of(log_dirs)
     li = parse_input(current_doc, table, broker_list)
     cap = None
     if capacity is not None or default_capacity is not None or use_total_bytes:
         cap = dir_capacities(li.broker_ids, li.dir_names, table, capacity, default_capacity, use_total_bytes)
-    return plan_input(li, min_gain, max_rounds, dry_run, cap)
+    return plan_input(li, min_gain, max_rounds, dry_run, cap, exchange)
 
 
 def report_lines(plan: LogDirsPlan) -> List[str]:
@@ -475,11 +498,12 @@ def report_lines(plan: LogDirsPlan) -> List[str]:
             p = [p[0], p[2], p[4], p[6], p[7], p[8], _ppm(p[0], p[1]), _ppm(p[2], p[3]), _ppm(p[4], p[5]), p[9]]
         out.append(f"logdirs: broker={b} dirs={len(li.dir_names[i])} skipped_dirs={li.skipped[i]} replicas={int(per_replicas[i])} peak_before={p[0]} "
                    f"peak_after={p[1]} lower_bound={p[2]} moved={p[3]} bytes_moved={p[4]} rounds={p[5]}"
-                   + (f" peak_before_ppm={p[6]} peak_after_ppm={p[7]} lower_bound_ppm={p[8]} proof={p[9]}" if by_cap else ""))
+                   + (f" peak_before_ppm={p[6]} peak_after_ppm={p[7]} lower_bound_ppm={p[8]} proof={p[9]}" if by_cap else "")
+                   + (f" exchange_rounds={p[6]} exchanges={p[7]}" if plan.exchange else ""))
     total = sum(int(x) for x in li.size) + sum(int(x) for x in li.base)
     out.append(f"logdirs: status={res.status} brokers={len(li.broker_ids)} dirs={int(li.dir_start[-1])} skipped_dirs={sum(li.skipped)} replicas={len(li.dir)} "
                f"peak_before={res.peak_before} peak_after={res.peak_after} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
-               + " ".join(f"{k}={int(v)}" for k, v in zip(STAT_KEYS, s))
+               + " ".join(f"{k}={int(v)}" for k, v in zip(X_STAT_KEYS if plan.exchange else STAT_KEYS, s))
                + (f" peak_before_ppm={_ppm(*res.peak_before_frac)} peak_after_ppm={_ppm(*res.peak_after_frac)}" if by_cap else ""))
     return out
 
@@ -730,6 +754,7 @@ def main(argv=None) -> int:
     ap.add_argument("--utilisation", action="store_true", help="lower the peak utilisation: a dir's capacity is the totalBytes of --log-dirs (Kafka >= 3.3)")
     ap.add_argument("--capacities", default=None, help='{"<brokerId>": {"<logDir>": bytes} | bytes} JSON file: lower the peak utilisation')
     ap.add_argument("--default-capacity", default=None, help="bytes of disk of the dirs that have no other capacity (N, or N with K/M/G/T)")
+    ap.add_argument("--exchange", action="store_true", help="exchange two replicas of two dirs where no single move is left (bytes only)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
@@ -739,6 +764,8 @@ def main(argv=None) -> int:
     placing = a.plan is not None or bool(a.evacuate)
     if (a.rebalance or a.default_size is not None) and not placing:
         ap.error("--rebalance and --default-size need --plan or --evacuate")
+    if a.exchange and (placing or by_capacity):
+        ap.error("--exchange cannot be combined with --utilisation, --capacities, --default-capacity, --plan, --evacuate or --rebalance")
     try:
         if a.min_gain is not None:
             min_gain = parse_bytes(a.min_gain)
@@ -792,7 +819,7 @@ def main(argv=None) -> int:
             li = parse_input(doc, table, ids)   # input errors before the device is touched
             cap = capacities_of(table, li)
             init(a.device)
-            plan = plan_input(li, min_gain, a.max_rounds, a.dry_run, cap)
+            plan = plan_input(li, min_gain, a.max_rounds, a.dry_run, cap, a.exchange)
         if a.report:
             for line in plan.report_lines():
                 print(line, file=sys.stderr)

@@ -22,7 +22,12 @@ tables: every dir 16 GiB (equal), or every fourth dir of a broker a quarter of t
 after in parts per million, the utilisation that the BYTE planner's plan reaches on the same input and capacities (its dirs read
 back and measured here on the host), rounds, moves, proposals and the wall time as above; beside it, from the same session, the wall
 time of the byte sibling on the same input.  With equal capacities the two calls give the same plan, and the difference in time is
-what the 128-bit compares and the walk cost.  Writes profiles/logdirs_capacity_time.txt with --write."""
+what the 128-bit compares and the walk cost.  Writes profiles/logdirs_capacity_time.txt with --write.
+
+--exchange times kao_balance_logdirs_exchange beside kao_balance_logdirs, from the same session and on the
+shapes of the first table: per line, for each of the two calls, the peak after, peak / bound worst and mean, the brokers proven,
+replicas and bytes moved, the rounds and the wall time as above; for the exchange call the rounds of both kinds, the exchanges, the
+exchange proposals and the brokers that end with a lower peak.  Writes profiles/logdirs_x_time.txt with --write."""
 import argparse
 import json
 import os
@@ -167,6 +172,44 @@ def time_capacity(a, np, lr):
             f.write("\n".join(lines) + "\n")
 
 
+def time_exchange(a, np, lr):
+    from kafka_assignment_optimizer_amd.logdirs import X_STAT_KEYS, balance_logdirs_arrays
+
+    def timed(fn):
+        fn()   # warm-up
+        ms = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            res = fn()
+            ms.append(round(1e3 * (time.perf_counter() - t0), 3))
+        return res, ms
+
+    lines = []
+    for name in a.cases.split(","):
+        B, n, k = SHAPES[name]
+        for sigma in (float(s) for s in a.sigmas.split(",")):
+            c = lr.lognormal_case(B, n, k, sigma, 11, zeros=0.0)
+            args = (c["dir_start"], c["dir"], c["size"], c["base"])
+            plain, plain_ms = timed(lambda: balance_logdirs_arrays(*args, dry_run=True))
+            res, ms = timed(lambda: balance_logdirs_arrays(*args, dry_run=True, exchange=True))
+            assert (res.per_broker[:, 1] <= plain.per_broker[:, 1]).all()
+            line = {"workload": name, "sigma": sigma, "brokers": B, "dirs_per_broker": n, "replicas_per_broker": k}
+            for tag, r in (("plain", plain), ("exchange", res)):
+                per = r.per_broker.astype(np.float64)
+                ratio = per[:, 1] / np.maximum(per[:, 2], 1)
+                line.update({f"{tag}_status": r.status, f"{tag}_peak_after": r.peak_after, f"{tag}_peak_over_bound_worst": round(float(ratio.max()), 6),
+                             f"{tag}_peak_over_bound_mean": round(float(ratio.mean()), 6), f"{tag}_proven": int(r.stats[6]), f"{tag}_replicas_moved": r.n_moved,
+                             f"{tag}_bytes_moved": r.bytes_moved, f"{tag}_rounds": int(r.stats[1]), f"{tag}_max_rounds_of_a_broker": int(r.stats[7])})
+            line.update({key: int(v) for key, v in zip(X_STAT_KEYS, res.stats)})
+            line.update({"brokers_with_a_lower_peak": int((res.per_broker[:, 1] < plain.per_broker[:, 1]).sum()), "plain_wall_ms": plain_ms,
+                         "plain_wall_ms_median": round(float(np.median(plain_ms)), 3), "wall_ms": ms, "wall_ms_median": round(float(np.median(ms)), 3)})
+            lines.append(json.dumps(line))
+            print(lines[-1], flush=True)
+    if a.write:
+        with open(os.path.join(ROOT, "profiles", "logdirs_x_time.txt"), "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -177,12 +220,17 @@ def main():
     ap.add_argument("--place", action="store_true", help="time kao_place_logdirs instead (see the head of this file)")
     ap.add_argument("--capacity", choices=("equal", "4:1"), default=None, help="time the capacity calls (with --place: kao_place_logdirs_capacity); "
                     "--write appends to profiles/logdirs_capacity_time.txt")
+    ap.add_argument("--exchange", action="store_true", help="time kao_balance_logdirs_exchange beside kao_balance_logdirs (see the head of this file)")
     a = ap.parse_args()
+    if a.exchange and (a.place or a.capacity):
+        ap.error("--exchange times the plain balance alone: not with --place or --capacity")
     import numpy as np
     import kafka_assignment_optimizer_amd as kao
     from kafka_assignment_optimizer_amd.logdirs import STAT_KEYS, balance_logdirs_arrays
     import logdirs_ref as lr
     kao.init(0)
+    if a.exchange:
+        return time_exchange(a, np, lr)
     if a.capacity:
         return time_capacity(a, np, lr)
     if a.place:
