@@ -4,7 +4,7 @@
 //   kao-leaders --current current.json --broker-list 0,1,2 --racks racks.json [--out plan.json] [--slack N] [--auto-slack]
 //               [--cluster] [--cluster-lo N] [--cluster-hi N] [--device D] [--report]
 //   kao-leaders --current current.json --broker-list 0,1,2 --racks racks.json (--traffic traffic.json | --sizes log-dirs.txt)
-//               [--default-weight N] [--min-gain N] [--max-rounds N] [--out plan.json] [--device D] [--report]
+//               [--default-weight N] [--min-gain N] [--max-rounds N] [--exchange] [--out plan.json] [--device D] [--report]
 //
 // writes a reassignment document holding only the partitions whose preferred leader changes; every row is the current row with the
 // new leader swapped to the front, so executing it moves no data (kao-waves puts the whole plan into one wave).  Topics are balanced
@@ -21,7 +21,9 @@
 // bound computed beside it proves the peak optimal where the two meet (status OPTIMAL_PROVEN, else FEASIBLE_BOUND_GAP; exit status
 // 0 both times).  --default-weight N weighs the partitions the file does not name (without it they are an error); --min-gain N moves
 // a leader only when the gap it closes exceeds N; --max-rounds N stops the descent early.  Combining them with --slack,
-// --auto-slack or the --cluster flags is a usage error.
+// --auto-slack or the --cluster flags is a usage error.  --exchange goes on from the state where no single leader change helps: two
+// partitions on one broker pair swap their leaders (kao_balance_leaders_weighted_exchange); the peak is never
+// higher than without it, the plan is longer, no data moves; the report gains a line.  It needs --traffic or --sizes.
 // Exit status: 0 = ok, 1 = error or a topic is infeasible, 2 = usage.
 #include <algorithm>
 #include <cerrno>
@@ -47,6 +49,7 @@ namespace {
         "                   [--out <file>] [--slack N] [--auto-slack] [--cluster] [--cluster-lo N] [--cluster-hi N]\n"
         "                   [--device D] [--report]\n"
         "       weighted: --traffic <traffic.json> | --sizes <kafka-log-dirs output> [--default-weight N] [--min-gain N] [--max-rounds N]\n"
+        "                 [--exchange]\n"
         "writes the partitions whose preferred leader changes; exit status: 0 = ok, 1 = error or infeasible, 2 = usage\n");
     std::exit(2);
 }
@@ -98,9 +101,10 @@ int balance_cluster(const Cluster &cl, const std::string &cur_path, const std::s
     return ok ? 0 : 1;
 }
 
-// --traffic / --sizes: all topics together, every partition weighed (kao_balance_leaders_weighted)
+// --traffic / --sizes: all topics together, every partition weighed (kao_balance_leaders_weighted; with --exchange
+// kao_balance_leaders_weighted_exchange)
 int balance_weighted(const Cluster &cl, const std::string &cur_path, const std::string &out_path, int device, const std::string &traffic_path,
-                     const std::string &sizes_path, bool have_default, uint64_t default_weight, uint64_t min_gain, int max_rounds, bool report) {
+                     const std::string &sizes_path, bool have_default, uint64_t default_weight, uint64_t min_gain, int max_rounds, bool exchange, bool report) {
     const ClusterRows cr = read_rows(cur_path, cl);
     const int P = (int)cr.keys.size(), B = (int)cl.brokers.size(), W = cr.width;
     const std::map<Key, uint64_t> known = traffic_path.empty() ? load_sizes(sizes_path) : load_traffic(traffic_path);
@@ -123,14 +127,18 @@ int balance_weighted(const Cluster &cl, const std::string &cur_path, const std::
     std::vector<uint16_t> rows = cr.rows;
     int32_t n_changed = 0, status = 0;
     uint64_t before = 0, after = 0, bound = 0;
-    int64_t stats[8] = {0};
-    rc = kao_balance_leaders_weighted(B, P, W, rows.data(), weight.data(), min_gain, max_rounds, 0, &n_changed, &before, &after, &bound, &status, stats);
-    if (rc) throw std::runtime_error(std::string("kao_balance_leaders_weighted: ") + kao_strerror(rc) + " " + kao_last_error());
+    int64_t stats[12] = {0};
+    rc = (exchange ? kao_balance_leaders_weighted_exchange : kao_balance_leaders_weighted)(B, P, W, rows.data(), weight.data(), min_gain, max_rounds, 0,
+                                                                                           &n_changed, &before, &after, &bound, &status, stats);
+    if (rc) throw std::runtime_error(std::string(exchange ? "kao_balance_leaders_weighted_exchange: " : "kao_balance_leaders_weighted: ") + kao_strerror(rc) + " " + kao_last_error());
     if (report)
         std::fprintf(stderr, "weighted: status=%s peak_before=%llu peak_after=%llu lower_bound=%llu leader_changes=%d rounds=%lld moves=%lld "
                              "launches=%lld\n", status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP",
                      (unsigned long long)before, (unsigned long long)after, (unsigned long long)bound, n_changed, (long long)stats[0],
                      (long long)stats[1], (long long)stats[3]);
+    if (report && exchange)
+        std::fprintf(stderr, "exchange: rounds=%lld exchanges=%lld proposals=%lld pair_index_entries=%lld\n", (long long)stats[8], (long long)stats[9],
+                     (long long)stats[10], (long long)stats[11]);
     const std::string text = changed_rows_text(cr, rows, cl.brokers);
     if (out_path.empty()) std::fputs(text.c_str(), stdout);
     else {
@@ -149,7 +157,7 @@ int main(int argc, char **argv) {
     int device = 0, slack0 = 0, cluster_lo = 0, cluster_hi = -1;
     bool report = false, auto_slack = false, cluster = false, have_slack = false, have_cluster_lo = false, have_cluster_hi = false;
     std::string traffic_path, sizes_path;
-    bool have_traffic = false, have_sizes = false, have_default = false, have_gain = false, have_rounds = false;
+    bool have_traffic = false, have_sizes = false, have_default = false, have_gain = false, have_rounds = false, exchange = false;
     uint64_t default_weight = 0, min_gain = 0;
     int max_rounds = 0;
     auto u64_arg = [](const std::string &v, uint64_t limit, const char *msg) {   // digits only, at most `limit`
@@ -185,6 +193,7 @@ int main(int argc, char **argv) {
         else if (a == "--default-weight") { default_weight = u64_arg(need("--default-weight"), kMaxSize, "--default-weight needs a value 0..2^53"); have_default = true; }
         else if (a == "--min-gain") { min_gain = u64_arg(need("--min-gain"), UINT64_MAX, "--min-gain needs a value 0..2^64-1"); have_gain = true; }
         else if (a == "--max-rounds") { max_rounds = count_arg(need("--max-rounds"), "--max-rounds needs a value >= 0"); have_rounds = true; }
+        else if (a == "--exchange") exchange = true;
         else if (a == "--device") device = std::atoi(need("--device").c_str());
         else if (a == "--report") report = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
@@ -196,6 +205,7 @@ int main(int argc, char **argv) {
     if (weighted && (have_slack || auto_slack || cluster || have_cluster_lo || have_cluster_hi))
         usage("--traffic / --sizes cannot be combined with --slack, --auto-slack, --cluster, --cluster-lo or --cluster-hi");
     if (!weighted && (have_default || have_gain || have_rounds)) usage("--default-weight, --min-gain and --max-rounds need --traffic or --sizes");
+    if (exchange && !weighted) usage("--exchange needs --traffic or --sizes");
     if (cluster_lo && !cluster) usage("--cluster-lo needs --cluster");
     if (cluster && auto_slack) usage("--auto-slack cannot be combined with --cluster");
     if (cluster && cluster_hi >= 0 && cluster_hi < cluster_lo) usage("--cluster-hi must be >= --cluster-lo");
@@ -203,7 +213,7 @@ int main(int argc, char **argv) {
         const Cluster cl = read_cluster(brokers_csv, racks_arg);
         const std::vector<int> &brokers = cl.brokers;
         if (weighted)
-            return balance_weighted(cl, cur_path, out_path, device, traffic_path, sizes_path, have_default, default_weight, min_gain, max_rounds, report);
+            return balance_weighted(cl, cur_path, out_path, device, traffic_path, sizes_path, have_default, default_weight, min_gain, max_rounds, exchange, report);
         if (cluster) return balance_cluster(cl, cur_path, out_path, device, slack0, cluster_lo, cluster_hi, report);
         const std::map<int, int> &dense = cl.dense;
         const std::vector<uint8_t> &rack_of = cl.rack_of;

@@ -583,8 +583,47 @@ int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partitions, int32_
                                  int32_t *status, int64_t stats[8] /* may be NULL */);
 /* Test hook.  kao_balance_leaders_weighted picks its kernel path by size; this sets the calling thread's choice for its later calls:
  * 0 = by size, 1 = the single workgroup (KAO_ERR_UNSUPPORTED from the call when the brokers do not fit its LDS), 2 = one launch
- * pair per round.  Both paths give the same bytes.  Returns the previous choice, or KAO_ERR_INVALID. */
+ * pair per round.  Both paths give the same bytes.  Returns the previous choice, or KAO_ERR_INVALID.  It governs
+ * kao_balance_leaders_weighted_exchange too. */
 int kao_wleaders_test_path(int32_t path);
+
+/* ---- Leaders weighted by traffic, with exchange moves ----------------------------------------------------
+ * kao_balance_leaders_weighted stops at a move-stable state: no single leader change closes a gap.  This call goes on from there
+ * with EXCHANGES: two partitions that both sit on the brokers a and c, one led by a and one by c, swap their leaders.  A leader
+ * change moves no data, so a lower peak costs only a longer election list.  Rows, weights, j(p), W(b), code, min_gain and dry_run
+ * are those of kao_balance_leaders_weighted.
+ * PI = the partitions by weight descending, then p ascending; fixed for the call.  Each round uses the loads as they stand at its
+ * start.  It is a MOVE round of kao_balance_leaders_weighted, unchanged, if any partition has a move proposal, else an EXCHANGE
+ * round; the call ends when a round has neither kind of proposal, or after max_rounds rounds of both kinds together (<= 0: no
+ * limit).
+ * EXCHANGE round: a partition x with weight[x] > 0, two replicas or more and leader a walks its other replicas c by W(c) ascending,
+ * ties to the lowest slot.  D = W(a) - W(c); a c with D <= 0 is skipped.  S(a, c) = the sub-list of PI of the partitions y != x with
+ * weight[y] > 0 whose row holds both a and c and whose current leader is c.  With delta = weight[x] - weight[y], y PASSES iff
+ * delta > 0 and delta + min_gain < D (evaluated without overflow).  The passing y are a contiguous run of S(a, c); it is split at
+ * g = the number of its members with 2 weight[y] > 2 weight[x] - D; y_hi = the last passing member before the split, y_lo = the
+ * first at or after it; the one with the lower |2 delta - D| is taken, a tie goes to y_lo.  (The split lies inside the passing run:
+ * if any y passes, one of the two exists, also for 2 min_gain >= D.)  The first c with a passing y gives the proposal (x, y, a <-> c).
+ * Its key is (0xFFFF - code(W(a))) << 48 | (0xFFFF - code(delta)) << 32 | x, and it wins iff that key is the lowest of all exchange
+ * proposals that touch a, and likewise at c.  Winners are applied together: W(a) -= delta, W(c) += delta, j(x) = the slot of c in
+ * row x, j(y) = the slot of a in row y.  Every role of a partition in a proposal touches its leader's broker and winners share no
+ * broker, so no partition is touched twice; the globally lowest key wins, so every round applies something; an exchange lowers
+ * the sum of W^2 by 2 delta (D - delta) > 0 and leaves both loads below the old W(a): the rounds end and the peak never rises.
+ * The state at the first exchange round is kao_balance_leaders_weighted's end state, so without a max_rounds stop *peak_after is
+ * never above that call's, the end state is move-stable and exchange-stable (no pair x led by a, y led by c, both rows holding
+ * both brokers, has 0 < delta and delta + min_gain < W(a) - W(c)), and an input whose move-stable state is exchange-stable (all
+ * positive weights equal, for one) gets the same bytes from both calls.
+ * Outputs, status, return codes and the host checks are those of kao_balance_leaders_weighted.  stats (may be NULL): [0] rounds,
+ * [1] changes applied and [2] proposals count both kinds of round; [3]..[7] as there ([5]: stopped by max_rounds with a proposal of
+ * either kind left); [8] exchange rounds, [9] exchanges applied, [10] exchange proposals, [11] entries of the pair index (one per
+ * partition with weight > 0 and unordered pair of its replicas). */
+int kao_balance_leaders_weighted_exchange(int32_t n_brokers, int32_t n_partitions, int32_t width,
+                                          uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *weight /* [n_partitions] */,
+                                          uint64_t min_gain, int32_t max_rounds /* <= 0: no limit */, int32_t dry_run,
+                                          int32_t *n_changed, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound,
+                                          int32_t *status, int64_t stats[12] /* may be NULL */);
+/* Measurement hook: the microseconds the calling thread's last kao_balance_leaders_weighted_exchange spent on the host building PI
+ * and the pair index (tools/wleaders_time.py reports it as a share of the call). */
+int64_t kao_wleaders_last_setup_us(void);
 
 /* ---- Failover weighted by traffic -----------------------------------------------------------------------
  * kao_failover_order counts every orphaned partition as one unit; here partition p carries weight[p] (a uint64_t; the weights sum

@@ -118,6 +118,10 @@ SIGNATURES = {
     "kao_balance_leaders_weighted": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint64), C.c_uint64, C.c_int32, C.c_int32,
                                                _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32), _P(C.c_int64)]),
     "kao_wleaders_test_path": (C.c_int, [C.c_int32]),
+    "kao_balance_leaders_weighted_exchange": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint64), C.c_uint64, C.c_int32,
+                                                        C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32),
+                                                        _P(C.c_int64)]),
+    "kao_wleaders_last_setup_us": (C.c_int64, []),
     "kao_failover_order_weighted": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_uint8), C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint64), C.c_int32,
                                               C.c_uint64, C.c_int32, C.c_int32, _P(C.c_uint64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
     "kao_balance_disk": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_uint8), C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint64), C.c_int32, C.c_int32,

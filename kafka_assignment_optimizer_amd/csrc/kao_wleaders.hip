@@ -25,6 +25,9 @@
 // max_k ceil(A_k / k)), valid for ANY leader choice: a partition with every replica among the k highest-ranked brokers is led by
 // one of them, so one of them carries at least their average.  Rank (all pairs, tiled through LDS), one pass over the rows into a
 // u64 histogram over m_p, one scan.  Integers only.
+// kao_balance_leaders_weighted_exchange is the same call with a second kind of round, run when a round has
+// no move proposal: two partitions on one broker pair swap their leaders (see EXCHANGE rounds below).  Its kernels take WlxNet, a
+// type of their own; the kernels above the line "EXCHANGE rounds" and their arguments are those of the plain call alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,7 +47,7 @@ constexpr int kWlOneMaxB = 2048;        // ... holds loads + two minkey rows in 
 constexpr int kWlOneMaxP = 4096;        // ... and is chosen up to this many partitions (threshold)
 constexpr int kWlHardRounds = 1 << 26;  // no descent gets here; a guard against an endless loop
 constexpr u64 kWlNoKey = ~0ull;
-enum { U_PEAK0 = 0, U_PEAK1, U_MOVES, U_PROPS, U_ROUNDS, U_MAXW, U_FORCED, U_LEVEL, U_LEVELK, U_CHANGED, U_LEADING, U_MORE, U_N = 16 };
+enum { U_PEAK0 = 0, U_PEAK1, U_MOVES, U_PROPS, U_ROUNDS, U_MAXW, U_FORCED, U_LEVEL, U_LEVELK, U_CHANGED, U_LEADING, U_MORE, U_XROUNDS, U_XCH, U_XPROPS, U_N = 16 };
 
 thread_local int t_wl_path = 0;   // kao_wleaders_test_path: 0 = by size, 1 = single workgroup, 2 = multi-launch
 
@@ -59,6 +62,16 @@ struct WlNet {   // one call; every pointer is device memory
     u64 *load;              // [B]
     u64 *mk;                // [2][B] minkey rows
     u64 *ctl;               // [U_N]
+};
+
+struct WlxNet {   // one call of kao_balance_leaders_weighted_exchange: the plain call's state and the pair index
+    WlNet n;
+    int NP;                   // slot pairs of a row: W (W - 1) / 2
+    const uint32_t *ent;      // [entries] the partitions of the pair index: one segment per broker pair, each in the order PI
+    const uint32_t *seg_lo;   // [segments + 1] where a segment starts
+    const uint32_t *pseg;     // [P * NP] the segment of (partition, slot pair); unused where weight is 0
+    uint32_t *partner;        // [P] the y of this round's exchange proposal
+    uint16_t *pa, *pc;        // [P] its two brokers: apply never reads lead[]
 };
 
 __device__ inline void wl_max_to(u64 v, u64 *dst) {   // all 64 lanes active
@@ -214,6 +227,224 @@ __global__ __launch_bounds__(kWlOneThreads) void k_wl_one(WlNet n, int max_round
     }
 }
 
+// ---- EXCHANGE rounds -----------------------------------------------------------------------------------------
+// A round without a move proposal is an EXCHANGE round: x (led by a) and y (led by c, lighter than x), both rows holding both
+// brokers, swap leaders: W(a) -= delta, W(c) += delta, delta = weight[x] - weight[y].  The rows of a broker pair are one segment of
+// the pair index, heaviest first, so x finds its partner by a binary search and a short scan, never by comparing pairs.
+constexpr uint32_t kWlxNoY = 0xFFFFFFFFu;
+
+// first e in [lo, hi) whose weight fails `pred` (pred holds on a prefix: the segment is in weight order, heaviest first)
+template <class Pred>
+__device__ __forceinline__ uint32_t wlx_first_not(const WlxNet &x, uint32_t lo, uint32_t hi, Pred pred) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (pred(x.n.weight[x.ent[mid]])) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The exchange proposal of partition p against the loads `load`: false when it has none.  Reads loads and lead[], writes nothing.
+__device__ inline bool wlx_propose(const WlxNet &x, int p, const u64 *load, int &a, int &c, int &slot, uint32_t &y, u64 &key) {
+    const WlNet &n = x.n;
+    const u64 w = n.weight[p], mg = n.min_gain;
+    if (w == 0) return false;
+    const uint16_t *row = n.rows + (size_t)p * n.W;
+    const int l = n.lead[p];
+    a = row[l];
+    const u64 wa = load[a];
+    for (uint32_t done = 1u << l;;) {   // the other replicas by load ascending, ties to the lowest slot
+        int j = -1;
+        u64 wc = 0;
+        for (int s = 0; s < n.W; ++s) {
+            const int b = row[s];
+            if (b == KAO_NONE) break;
+            if (done >> s & 1u) continue;
+            const u64 v = load[b];
+            if (j < 0 || v < wc) { j = s; wc = v; }
+        }
+        if (j < 0 || wc >= wa) return false;   // D <= 0, and no later candidate has a larger D
+        done |= 1u << j;
+        const u64 D = wa - wc;
+        if (D <= mg) return false;             // delta + min_gain < D has no delta >= 1
+        c = row[j];
+        const int i0 = min(l, j), i1 = max(l, j);
+        const uint32_t seg = x.pseg[(size_t)p * x.NP + i0 * (2 * n.W - i0 - 1) / 2 + (i1 - i0 - 1)];
+        const uint32_t lo = x.seg_lo[seg], hi = x.seg_lo[seg + 1];
+        // the split: members before s have 2 weight > 2 w - D (delta below D / 2); every sum stays below 2^64
+        const uint32_t s = wlx_first_not(x, lo, hi, [&](u64 wq) { return 2 * wq + D > 2 * w; });
+        // ... clamped into the passing run: for 2 min_gain >= D the members next to the split fail delta + min_gain < D
+        const uint32_t h = mg < D - mg ? s : wlx_first_not(x, lo, s, [&](u64 wq) { return wq >= w || D - (w - wq) > mg; });
+        uint32_t y_hi = kWlxNoY, y_lo = kWlxNoY;
+        u64 d_hi = 0, d_lo = 0;
+        for (uint32_t e = h; e-- > lo;) {      // heavier and heavier: until delta <= 0
+            const uint32_t q = x.ent[e];
+            const u64 wq = n.weight[q];
+            if (wq >= w) break;
+            if (n.rows[(size_t)q * n.W + n.lead[q]] == c) { y_hi = q; d_hi = w - wq; break; }
+        }
+        for (uint32_t e = s; e < hi; ++e) {    // lighter and lighter: until delta + min_gain >= D (weight < w from s on)
+            const uint32_t q = x.ent[e];
+            const u64 d = w - n.weight[q];
+            if (d >= D || D - d <= mg) break;
+            if (n.rows[(size_t)q * n.W + n.lead[q]] == c) { y_lo = q; d_lo = d; break; }
+        }
+        if (y_hi == kWlxNoY && y_lo == kWlxNoY) continue;
+        const bool take_hi = y_hi != kWlxNoY && (y_lo == kWlxNoY || D - 2 * d_hi < 2 * d_lo - D);   // a tie goes to y_lo
+        y = take_hi ? y_hi : y_lo;
+        slot = j;
+        key = DESCENT_KEY(wa, take_hi ? d_hi : d_lo, p);
+        return true;
+    }
+}
+
+// apply of a MOVE proposal, as k_wl_apply does it: true when it won
+__device__ __forceinline__ bool wlx_apply_move(const WlNet &n, int p, u64 key, const u64 *mine, u64 *load) {
+    const uint16_t *row = n.rows + (size_t)p * n.W;
+    const int slot = n.slot[p], a = row[n.lead[p]], b = row[slot];
+    if (mine[a] != key || mine[b] != key) return false;
+    const u64 w = n.weight[p];
+    load[a] -= w;
+    load[b] += w;
+    n.lead[p] = (uint8_t)slot;
+    return true;
+}
+
+// apply of an EXCHANGE proposal: its brokers come from what propose stored, because a winner writes lead[y] of another partition
+__device__ __forceinline__ bool wlx_apply_swap(const WlxNet &x, int p, u64 key, const u64 *mine, u64 *load) {
+    const WlNet &n = x.n;
+    const int a = x.pa[p], c = x.pc[p];
+    if (mine[a] != key || mine[c] != key) return false;   // no other winner touches a or c, x or y
+    const uint32_t y = x.partner[p];
+    const u64 d = n.weight[p] - n.weight[y];
+    load[a] -= d;
+    load[c] += d;
+    n.lead[p] = n.slot[p];
+    const uint16_t *ry = n.rows + (size_t)y * n.W;
+    int ja = 0;
+    while (ja < n.W - 1 && ry[ja] != a) ++ja;
+    n.lead[y] = (uint8_t)ja;
+    return true;
+}
+
+// enqueued behind every k_wl_propose: returns at once when that round has a move proposal
+__global__ void k_wlx_propose(WlxNet x, int r, const uint32_t *__restrict__ moves, uint32_t *__restrict__ count) {
+    if (*moves) return;
+    const WlNet &n = x.n;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    bool prop = false;
+    if (p < n.P) {   // key[p] is kWlNoKey: k_wl_propose found nothing
+        int a = 0, c = 0, slot = 0;
+        uint32_t y = 0;
+        u64 key = kWlNoKey;
+        prop = wlx_propose(x, p, n.load, a, c, slot, y, key);
+        if (prop) {
+            n.key[p] = key;
+            n.slot[p] = (uint8_t)slot;
+            x.partner[p] = y;
+            x.pa[p] = (uint16_t)a;
+            x.pc[p] = (uint16_t)c;
+            u64 *row = n.mk + (size_t)(r & 1) * n.B;
+            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[a], key);
+            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[c], key);
+        }
+    }
+    lane_count_to(prop, count);
+}
+
+// the apply of either kind of round
+__global__ void k_wlx_apply(WlxNet x, int r, const uint32_t *__restrict__ moves) {
+    const WlNet &n = x.n;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    {   // the row of round r + 1 was last read by the apply of round r - 1
+        u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
+        for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kWlNoKey;
+    }
+    const bool move = *moves != 0;
+    bool won = false;
+    if (p < n.P) {
+        const u64 key = n.key[p];
+        if (key != kWlNoKey) {
+            const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
+            won = move ? wlx_apply_move(n, p, key, mine, n.load) : wlx_apply_swap(x, p, key, mine, n.load);
+        }
+    }
+    lane_count_to(won, &n.ctl[move ? U_MOVES : U_XCH]);
+}
+
+// every round of both kinds in one launch: one workgroup, loads and minkey rows in LDS, the pair index in global memory
+__global__ __launch_bounds__(kWlOneThreads) void k_wlx_one(WlxNet x, int max_rounds) {
+    extern __shared__ u64 wl_lds[];
+    const WlNet &n = x.n;
+    u64 *load = wl_lds, *mk = wl_lds + n.B;
+    const int tid = threadIdx.x;
+    for (int b = tid; b < n.B; b += kWlOneThreads) {
+        load[b] = n.load[b];
+        mk[b] = kWlNoKey;
+        mk[n.B + b] = kWlNoKey;
+    }
+    __syncthreads();
+    u64 props = 0, moves = 0, xprops = 0, swaps = 0;
+    int rounds = 0, xrounds = 0, more = 0;
+    for (int r = 0; r < kWlHardRounds; ++r) {
+        u64 *row = mk + (size_t)(r & 1) * n.B, *other = mk + (size_t)((r + 1) & 1) * n.B;
+        int mine = 0;
+        for (int p = tid; p < n.P; p += kWlOneThreads) {
+            int a = 0, b = 0, slot = 0;
+            u64 key = kWlNoKey;
+            const bool prop = wl_propose(n, p, load, a, b, slot, key);
+            n.key[p] = key;   // read back by this thread alone
+            if (prop) {
+                n.slot[p] = (uint8_t)slot;
+                atomicMin(&row[a], key);
+                atomicMin(&row[b], key);
+                ++mine;
+            }
+        }
+        const bool move = __syncthreads_or(mine) != 0;
+        if (!move) {   // an EXCHANGE round: the lead[] of other partitions was written before the barrier that ended the last round
+            for (int p = tid; p < n.P; p += kWlOneThreads) {
+                int a = 0, c = 0, slot = 0;
+                uint32_t y = 0;
+                u64 key = kWlNoKey;
+                if (!wlx_propose(x, p, load, a, c, slot, y, key)) continue;
+                n.key[p] = key;
+                n.slot[p] = (uint8_t)slot;
+                x.partner[p] = y;
+                x.pa[p] = (uint16_t)a;
+                x.pc[p] = (uint16_t)c;
+                atomicMin(&row[a], key);
+                atomicMin(&row[c], key);
+                ++mine;
+            }
+            if (!__syncthreads_or(mine)) break;
+        }
+        if (max_rounds > 0 && r >= max_rounds) { more = 1; break; }
+        ++rounds;
+        props += (u64)mine;
+        if (!move) { ++xrounds; xprops += (u64)mine; }
+        for (int p = tid; p < n.P; p += kWlOneThreads) {
+            const u64 key = n.key[p];
+            if (key == kWlNoKey) continue;
+            if (move) moves += wlx_apply_move(n, p, key, row, load) ? 1 : 0;
+            else swaps += wlx_apply_swap(x, p, key, row, load) ? 1 : 0;
+        }
+        for (int b = tid; b < n.B; b += kWlOneThreads) other[b] = kWlNoKey;
+        __syncthreads();
+    }
+    __syncthreads();
+    for (int b = tid; b < n.B; b += kWlOneThreads) n.load[b] = load[b];
+    if (props) atomicAdd(&n.ctl[U_PROPS], props);
+    if (moves) atomicAdd(&n.ctl[U_MOVES], moves);
+    if (xprops) atomicAdd(&n.ctl[U_XPROPS], xprops);
+    if (swaps) atomicAdd(&n.ctl[U_XCH], swaps);
+    if (tid == 0) {
+        n.ctl[U_ROUNDS] = (u64)rounds;
+        n.ctl[U_XROUNDS] = (u64)xrounds;
+        n.ctl[U_MORE] = (u64)more;
+    }
+}
+
 // ---- the certificate and the result -------------------------------------------------------------------------------------------------
 // (rank, histogram and scan in three launches over all brokers; k_wfo_solve of kao_wfailover.hip ranks a compacted set inside its
 // workgroup and reuses its LDS for the histogram: not shared)
@@ -294,9 +525,8 @@ __global__ __launch_bounds__(kWlThreads) void k_wl_scan(int B, const u64 *__rest
     }
 }
 
-int validate_weighted(int32_t B, int32_t P, int32_t W, const uint16_t *rows, const uint64_t *weight, const int32_t *n_changed,
+int validate_weighted(const std::string &fn, int32_t B, int32_t P, int32_t W, const uint16_t *rows, const uint64_t *weight, const int32_t *n_changed,
                       const uint64_t *peak_before, const uint64_t *peak_after, const uint64_t *lower_bound, const int32_t *status) {
-    const std::string fn = "kao_balance_leaders_weighted: ";
     if (!rows || !weight || !n_changed || !peak_before || !peak_after || !lower_bound || !status) return fail(KAO_ERR_INVALID, fn + "null pointer");
     int rc = check_dims(fn, B, P, W);
     if (!rc) rc = check_slot_cap(fn, P, W);
@@ -304,32 +534,81 @@ int validate_weighted(int32_t B, int32_t P, int32_t W, const uint16_t *rows, con
     return rc ? rc : check_weight_sum(fn, P, weight);
 }
 
-}  // namespace
+// ---- the pair index of the exchange call, built on the host once per call -----------------------------------------------------------
+// One entry per partition with weight > 0 and per unordered pair of its replicas, sorted by (lower broker, higher broker, position in
+// PI): every broker pair is then one segment in weight order.  The entries are made in the order PI, so two stable counting passes
+// over the broker indices (higher, then lower) sort them; pseg is the table from (partition, slot pair) to its segment.
+struct WlxIndex {
+    int NP = 0;
+    std::vector<uint32_t> ent, seg_lo, pseg;
+};
 
-extern "C" int kao_wleaders_test_path(int32_t path) {
-    if (path < 0 || path > 2) return fail(KAO_ERR_INVALID, "kao_wleaders_test_path: path outside 0..2");
-    const int was = t_wl_path;
-    t_wl_path = path;
-    return was;
+thread_local int64_t t_wlx_setup_us = 0;   // kao_wleaders_last_setup_us
+
+void wlx_build_index(int B, int P, int W, const uint16_t *rows, const uint64_t *weight, WlxIndex &ix) {
+    ix.NP = W * (W - 1) / 2;
+    ix.pseg.assign((size_t)P * ix.NP, 0);
+    std::vector<uint32_t> pi;
+    for (int p = 0; p < P; ++p)
+        if (weight[p] && W >= 2 && rows[(size_t)p * W + 1] != KAO_NONE) pi.push_back((uint32_t)p);
+    std::sort(pi.begin(), pi.end(), [&](uint32_t x, uint32_t y) { return weight[x] != weight[y] ? weight[x] > weight[y] : x < y; });
+    struct Ent { uint32_t pair, at; };   // lower broker << 16 | higher broker; partition << 5 | slot pair
+    std::vector<Ent> e, t;
+    for (uint32_t p : pi) {
+        const uint16_t *row = rows + (size_t)p * W;
+        for (int i = 0; i < W && row[i] != KAO_NONE; ++i)
+            for (int j = i + 1; j < W && row[j] != KAO_NONE; ++j)
+                e.push_back({(uint32_t)std::min(row[i], row[j]) << 16 | std::max(row[i], row[j]), p << 5 | (uint32_t)(i * (2 * W - i - 1) / 2 + (j - i - 1))});
+    }
+    t.resize(e.size());
+    for (int shift = 0; shift <= 16; shift += 16) {
+        std::vector<uint32_t> at((size_t)B + 1, 0);
+        for (const Ent &v : e) ++at[(v.pair >> shift & 0xFFFFu) + 1];
+        for (int b = 0; b < B; ++b) at[(size_t)b + 1] += at[b];
+        for (const Ent &v : e) t[at[v.pair >> shift & 0xFFFFu]++] = v;
+        e.swap(t);
+    }
+    ix.ent.resize(e.size());
+    for (size_t i = 0; i < e.size(); ++i) {
+        if (i == 0 || e[i].pair != e[i - 1].pair) ix.seg_lo.push_back((uint32_t)i);
+        ix.ent[i] = e[i].at >> 5;
+        ix.pseg[(size_t)(e[i].at >> 5) * ix.NP + (e[i].at & 31u)] = (uint32_t)ix.seg_lo.size() - 1;
+    }
+    ix.seg_lo.push_back((uint32_t)e.size());
 }
 
-extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partitions, int32_t width, uint16_t *rows, const uint64_t *weight,
-                                            uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_changed, uint64_t *peak_before,
-                                            uint64_t *peak_after, uint64_t *lower_bound, int32_t *status, int64_t stats[8]) {
-    int rc = validate_weighted(n_brokers, n_partitions, width, rows, weight, n_changed, peak_before, peak_after, lower_bound, status);
+// Both entry points: `exchange` adds the pair index, the exchange kernels and stats[8..11]; without it every launch and every byte is
+// the plain call's.
+int wl_call(bool exchange, const std::string &fn, int32_t n_brokers, int32_t n_partitions, int32_t width, uint16_t *rows, const uint64_t *weight,
+            uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_changed, uint64_t *peak_before, uint64_t *peak_after,
+            uint64_t *lower_bound, int32_t *status, int64_t *stats) {
+    int rc = validate_weighted(fn, n_brokers, n_partitions, width, rows, weight, n_changed, peak_before, peak_after, lower_bound, status);
     if (rc) return rc;
     if ((rc = require_init())) return rc;
     const int B = n_brokers, P = n_partitions, W = width, PW = P * W;
     const bool one = t_wl_path == 1 || (t_wl_path == 0 && B <= kWlOneMaxB && P <= kWlOneMaxP);
-    if (one && B > kWlOneMaxB) return fail(KAO_ERR_UNSUPPORTED, "kao_balance_leaders_weighted: the single-workgroup path holds at most " + std::to_string(kWlOneMaxB) + " brokers");
+    if (one && B > kWlOneMaxB) return fail(KAO_ERR_UNSUPPORTED, fn + "the single-workgroup path holds at most " + std::to_string(kWlOneMaxB) + " brokers");
+    WlxIndex ix;
+    if (exchange) {
+        const double t0 = now_s();
+        wlx_build_index(B, P, W, rows, weight, ix);
+        t_wlx_setup_us = (int64_t)((now_s() - t0) * 1e6);
+    }
+    const int ncnt = exchange ? 2 * kWlBatch : kWlBatch;   // the rounds' move proposals, then their exchange proposals
 
-    // one arena: ctl u64[U_N] | count u32[kWlBatch] | load, forced, hist u64[B] | led, rank i32[B] (zeroed up to here) | mk u64[2B]
-    //            (all ones) | key, weight u64[P] | rows u16[PW] | lead, slot u8[P]
+    // one arena: ctl u64[U_N] | count u32[ncnt] | load, forced, hist u64[B] | led, rank i32[B] (zeroed up to here) | mk u64[2B]
+    //            (all ones) | key, weight u64[P] | rows u16[PW] | lead, slot u8[P] | the exchange call's: ent, seg_lo, pseg, partner
+    //            u32 | pa, pc u16[P]
     Carve cv;
-    const size_t o_ctl = cv.take<u64>(U_N), o_cnt = cv.take<uint32_t>(kWlBatch), o_load = cv.take<u64>(B), o_forced = cv.take<u64>(B),
+    const size_t o_ctl = cv.take<u64>(U_N), o_cnt = cv.take<uint32_t>(ncnt), o_load = cv.take<u64>(B), o_forced = cv.take<u64>(B),
                  o_hist = cv.take<u64>(B), o_led = cv.take<int32_t>(B), o_rank = cv.take<int32_t>(B), zeroed = cv.end(),
                  o_mk = cv.take<u64>(2 * (size_t)B), o_key = cv.take<u64>(P), o_w = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW),
                  o_lead = cv.take<uint8_t>(P), o_slot = cv.take<uint8_t>(P);
+    size_t o_ent = 0, o_seg = 0, o_pseg = 0, o_partner = 0, o_pa = 0, o_pc = 0;
+    if (exchange) {
+        o_ent = cv.take<uint32_t>(ix.ent.size()); o_seg = cv.take<uint32_t>(ix.seg_lo.size()); o_pseg = cv.take<uint32_t>(ix.pseg.size());
+        o_partner = cv.take<uint32_t>(P); o_pa = cv.take<uint16_t>(P); o_pc = cv.take<uint16_t>(P);
+    }
     CallBufs m;
     if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
@@ -337,10 +616,13 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
     uint32_t *d_cnt = m.at<uint32_t>(o_cnt);
     int32_t *d_led = m.at<int32_t>(o_led), *d_rank = m.at<int32_t>(o_rank);
     u64 *d_forced = m.at<u64>(o_forced), *d_hist = m.at<u64>(o_hist);
-    WlNet n;
+    WlxNet x;
+    WlNet &n = x.n;
     n.P = P; n.W = W; n.B = B; n.min_gain = min_gain;
     n.rows = d_rows; n.weight = m.at<u64>(o_w); n.lead = m.at<uint8_t>(o_lead); n.slot = m.at<uint8_t>(o_slot); n.key = m.at<u64>(o_key);
     n.load = m.at<u64>(o_load); n.mk = m.at<u64>(o_mk); n.ctl = m.at<u64>(o_ctl);
+    x.NP = ix.NP; x.ent = m.at<uint32_t>(o_ent); x.seg_lo = m.at<uint32_t>(o_seg); x.pseg = m.at<uint32_t>(o_pseg);
+    x.partner = m.at<uint32_t>(o_partner); x.pa = m.at<uint16_t>(o_pa); x.pc = m.at<uint16_t>(o_pc);
 
     HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
     HIP_TRY(hipMemsetAsync(n.mk, 0xFF, 2 * (size_t)B * sizeof(u64), st));
@@ -348,8 +630,13 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
         HIP_TRY(hipMemcpyAsync(d_rows, rows, (size_t)PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(m.at<u64>(o_w), weight, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
+    if (exchange) {
+        if (!ix.ent.empty()) HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_ent), ix.ent.data(), ix.ent.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_seg), ix.seg_lo.data(), ix.seg_lo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (!ix.pseg.empty()) HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pseg), ix.pseg.data(), ix.pseg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
     const unsigned pblocks = grid_for(P, kWlThreads), bblocks = grid_for(B, kWlThreads);
-    int64_t launches = 0, rounds = 0, props = 0;
+    int64_t launches = 0, rounds = 0, props = 0, xrounds = 0, xprops = 0;
     bool more = false;
     if (P) {
         k_wl_init<<<pblocks, kWlThreads, 0, st>>>(n, d_forced);
@@ -361,14 +648,15 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
 
     if (one) {
         if (P) {
-            k_wl_one<<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(n, max_rounds);
+            if (exchange) k_wlx_one<<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(x, max_rounds);
+            else k_wl_one<<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(n, max_rounds);
             ++launches;
             HIP_TRY(hipGetLastError());
         }
-    } else if (P) {
+    } else if (P && !exchange) {
         uint32_t cnt[kWlBatch];
         for (int r = 0, done = 0; !done;) {
-            if (r >= kWlHardRounds) return fail(KAO_ERR_HIP, "kao_balance_leaders_weighted: the rounds did not finish");
+            if (r >= kWlHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
             const int nb = max_rounds > 0 ? std::min(kWlBatch, max_rounds - r) : kWlBatch;
             HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
             if (nb == 0) {   // max_rounds rounds have run, every one with a move: is there more to do?
@@ -390,6 +678,37 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
             }
             r += nb;
         }
+    } else if (P) {   // three launches per round: the exchange propose sees the round's move count and steps aside, the apply does either kind
+        uint32_t cnt[2 * kWlBatch];
+        for (int r = 0, done = 0; !done;) {
+            if (r >= kWlHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
+            const int nb = max_rounds > 0 ? std::min(kWlBatch, max_rounds - r) : kWlBatch;
+            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
+            if (nb == 0) {   // max_rounds rounds have run, every one with a proposal: is there more to do?
+                k_wl_propose<<<pblocks, kWlThreads, 0, st>>>(n, r, d_cnt);
+                k_wlx_propose<<<pblocks, kWlThreads, 0, st>>>(x, r, d_cnt, d_cnt + kWlBatch);
+                launches += 2;
+            }
+            for (int i = 0; i < nb; ++i) {
+                k_wl_propose<<<pblocks, kWlThreads, 0, st>>>(n, r + i, d_cnt + i);
+                k_wlx_propose<<<pblocks, kWlThreads, 0, st>>>(x, r + i, d_cnt + i, d_cnt + kWlBatch + i);
+                k_wlx_apply<<<pblocks, kWlThreads, 0, st>>>(x, r + i, d_cnt + i);
+                launches += 3;
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (nb == 0) { more = cnt[0] != 0 || cnt[kWlBatch] != 0; break; }
+            for (int i = 0; i < nb && !done; ++i) {   // the first round with neither kind of proposal ends the call; the ones after it changed nothing
+                const uint32_t cm = cnt[i], cx = cnt[kWlBatch + i];
+                if (cm == 0 && cx == 0) done = 1;
+                else {
+                    ++rounds; props += cm + cx;
+                    if (cm == 0) { ++xrounds; xprops += cx; }
+                }
+            }
+            r += nb;
+        }
     }
 
     k_wl_rank<<<bblocks, kWlThreads, 0, st>>>(B, n.load, d_rank, n.ctl + U_PEAK1);
@@ -405,8 +724,11 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
     HIP_TRY(hipMemcpyAsync(ctl, n.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
     if (P && !dry_run) HIP_TRY(hipMemcpyAsync(rows, d_rows, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (one) { rounds = (int64_t)ctl[U_ROUNDS]; props = (int64_t)ctl[U_PROPS]; more = ctl[U_MORE] != 0; }
-    if (rounds >= kWlHardRounds) return fail(KAO_ERR_HIP, "kao_balance_leaders_weighted: the rounds did not finish");
+    if (one) {
+        rounds = (int64_t)ctl[U_ROUNDS]; props = (int64_t)ctl[U_PROPS]; more = ctl[U_MORE] != 0;
+        xrounds = (int64_t)ctl[U_XROUNDS]; xprops = (int64_t)ctl[U_XPROPS];
+    }
+    if (rounds >= kWlHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
     const uint64_t lb = std::max({(uint64_t)ctl[U_MAXW], (uint64_t)ctl[U_FORCED], (uint64_t)ctl[U_LEVEL]});
     *n_changed = (int32_t)ctl[U_CHANGED];
     *peak_before = ctl[U_PEAK0];
@@ -414,8 +736,35 @@ extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partiti
     *lower_bound = lb;
     *status = ctl[U_PEAK1] == lb ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
     if (stats) {
-        stats[0] = rounds; stats[1] = (int64_t)ctl[U_MOVES]; stats[2] = props; stats[3] = launches; stats[4] = one ? 1 : 0;
+        stats[0] = rounds; stats[1] = (int64_t)(ctl[U_MOVES] + ctl[U_XCH]); stats[2] = props; stats[3] = launches; stats[4] = one ? 1 : 0;
         stats[5] = more ? 1 : 0; stats[6] = ctl[U_LEVEL] == lb ? (int64_t)ctl[U_LEVELK] : 0; stats[7] = (int64_t)ctl[U_LEADING];
+        if (exchange) { stats[8] = xrounds; stats[9] = (int64_t)ctl[U_XCH]; stats[10] = xprops; stats[11] = (int64_t)ix.ent.size(); }
     }
     return KAO_OK;
+}
+
+}  // namespace
+
+extern "C" int kao_wleaders_test_path(int32_t path) {
+    if (path < 0 || path > 2) return fail(KAO_ERR_INVALID, "kao_wleaders_test_path: path outside 0..2");
+    const int was = t_wl_path;
+    t_wl_path = path;
+    return was;
+}
+
+extern "C" int64_t kao_wleaders_last_setup_us(void) { return t_wlx_setup_us; }
+
+extern "C" int kao_balance_leaders_weighted(int32_t n_brokers, int32_t n_partitions, int32_t width, uint16_t *rows, const uint64_t *weight,
+                                            uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_changed, uint64_t *peak_before,
+                                            uint64_t *peak_after, uint64_t *lower_bound, int32_t *status, int64_t stats[8]) {
+    return wl_call(false, "kao_balance_leaders_weighted: ", n_brokers, n_partitions, width, rows, weight, min_gain, max_rounds, dry_run, n_changed,
+                   peak_before, peak_after, lower_bound, status, stats);
+}
+
+extern "C" int kao_balance_leaders_weighted_exchange(int32_t n_brokers, int32_t n_partitions, int32_t width, uint16_t *rows, const uint64_t *weight,
+                                                     uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_changed,
+                                                     uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *status,
+                                                     int64_t stats[12]) {
+    return wl_call(true, "kao_balance_leaders_weighted_exchange: ", n_brokers, n_partitions, width, rows, weight, min_gain, max_rounds, dry_run,
+                   n_changed, peak_before, peak_after, lower_bound, status, stats);
 }

@@ -15,7 +15,10 @@ can make it (or held to `--cluster-hi N`), every broker leading at least `--clus
 
 `--traffic FILE` or `--sizes FILE` weighs every partition instead (kao_balance_leaders_weighted): the traffic a
 broker leads is made even by a deterministic descent over all topics together, and a lower bound computed beside it proves the peak
-optimal where the two meet (status OPTIMAL_PROVEN; FEASIBLE_BOUND_GAP otherwise, exit status 0 both times).
+optimal where the two meet (status OPTIMAL_PROVEN; FEASIBLE_BOUND_GAP otherwise, exit status 0 both times).  `--exchange` goes on
+from the state where no single leader change helps: two partitions that share a broker pair swap their leaders
+(kao_balance_leaders_weighted_exchange).  No data moves either way: the peak is never higher than without the
+flag, the election list is longer.
 """
 from __future__ import annotations
 
@@ -36,6 +39,8 @@ from .solver import STATUS_NAMES, _check, _CTopics
 
 CLUSTER_STAT_KEYS = ("probes", "phases", "rounds", "paths", "longest_path", "launches", "pair_nodes", "unrouted")
 WEIGHTED_STAT_KEYS = ("rounds", "moves", "proposals", "launches", "single_workgroup", "stopped_by_max_rounds", "level_k", "leading_brokers")
+# kao_balance_leaders_weighted_exchange: rounds, moves and proposals count both kinds of round
+WEIGHTED_X_STAT_KEYS = WEIGHTED_STAT_KEYS + ("exchange_rounds", "exchanges", "exchange_proposals", "pair_index_entries")
 STAT_KEYS = ("phases", "rounds", "paths", "longest_path", "over_before", "under_before", "launches", "unrouted")
 
 
@@ -179,7 +184,10 @@ class WeightedLeaderResult:
     peak_after: int          # ... in the chosen rows; never above peak_before
     lower_bound: int         # no choice of leaders has a peak below it
     status: str              # "OPTIMAL_PROVEN" (peak_after == lower_bound) | "FEASIBLE_BOUND_GAP"
-    stats: np.ndarray        # int64[8], see WEIGHTED_STAT_KEYS / include/kao.h
+    stats: np.ndarray        # int64[8], see WEIGHTED_STAT_KEYS / include/kao.h; int64[12], WEIGHTED_X_STAT_KEYS, with exchange
+    exchange: bool = False   # the call was kao_balance_leaders_weighted_exchange
+    exchange_rounds: int = 0 # stats[8]: rounds that swapped the leaders of two partitions
+    exchanges: int = 0       # stats[9]: such swaps applied
 
 
 @dataclass
@@ -192,20 +200,23 @@ class WeightedLeaderPlan:
 
 
 def balance_leaders_weighted_arrays(rows, n_brokers: int, weight, min_gain: int = 0, max_rounds: int = 0,
-                                    dry_run: bool = False) -> WeightedLeaderResult:
+                                    dry_run: bool = False, exchange: bool = False) -> WeightedLeaderResult:
     """kao_balance_leaders_weighted on dense rows ([P, width], NONE-padded, slot 0 = preferred leader) of all topics over one
-    broker index; weight[p] is the traffic of row p."""
+    broker index; weight[p] is the traffic of row p.  exchange=True calls kao_balance_leaders_weighted_exchange: exchange rounds
+    follow when no move is left; stats is int64[12]."""
     r, flat, P, W = dense_rows(rows)
     wbuf = weight_buffer(weight, P, min_gain)
     n, status = C.c_int32(0), C.c_int32(0)
     before, after, bound = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    stats = np.zeros(8, dtype=np.int64)
-    _check(_ffi.load().kao_balance_leaders_weighted(int(n_brokers), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                                    wbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(min_gain), int(max_rounds), int(bool(dry_run)),
-                                                    C.byref(n), C.byref(before), C.byref(after), C.byref(bound), C.byref(status),
-                                                    stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_leaders_weighted")
+    stats = np.zeros(12 if exchange else 8, dtype=np.int64)
+    name = "kao_balance_leaders_weighted_exchange" if exchange else "kao_balance_leaders_weighted"
+    _check(getattr(_ffi.load(), name)(int(n_brokers), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                      wbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(min_gain), int(max_rounds), int(bool(dry_run)),
+                                      C.byref(n), C.byref(before), C.byref(after), C.byref(bound), C.byref(status),
+                                      stats.ctypes.data_as(C.POINTER(C.c_int64))), name)
     return WeightedLeaderResult(rows=r, n_changed=int(n.value), peak_before=int(before.value), peak_after=int(after.value),
-                                lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats)
+                                lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats, exchange=bool(exchange),
+                                exchange_rounds=int(stats[8]) if exchange else 0, exchanges=int(stats[9]) if exchange else 0)
 
 
 def _weight_value(v, what):
@@ -250,18 +261,19 @@ def weights_for(keys, table: Dict[Tuple[str, int], int], default_weight: Optiona
     return weight
 
 
-def _plan_weighted(keys, rows, broker_ids, weight, min_gain, max_rounds, dry_run) -> WeightedLeaderPlan:
-    res = balance_leaders_weighted_arrays(rows, len(broker_ids), weight, min_gain, max_rounds, dry_run)
+def _plan_weighted(keys, rows, broker_ids, weight, min_gain, max_rounds, dry_run, exchange=False) -> WeightedLeaderPlan:
+    res = balance_leaders_weighted_arrays(rows, len(broker_ids), weight, min_gain, max_rounds, dry_run, exchange)
     changed = np.nonzero((res.rows != rows).any(axis=1))[0]
     entries = [(keys[p][0], keys[p][1], [int(broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
     return WeightedLeaderPlan(result=res, keys=list(keys), weight=np.asarray(weight, dtype=np.uint64), entries=entries)
 
 
 def balance_leaders_weighted(topics: Sequence[Topic], weights, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False,
-                             assignments=None, default_weight: Optional[int] = None) -> WeightedLeaderPlan:
+                             assignments=None, default_weight: Optional[int] = None, exchange: bool = False) -> WeightedLeaderPlan:
     """kao_balance_leaders_weighted on topics that share one broker index (broker_ids); rows = `assignments`, default each topic's
     current; topics of different RF are padded.  `weights` is {(topic name, partition id): weight} (partitions it does not name
-    take `default_weight`) or one array per topic.  Returns the per-topic assignments and the plan entries of the changed rows."""
+    take `default_weight`) or one array per topic.  exchange=True selects kao_balance_leaders_weighted_exchange.  Returns the
+    per-topic assignments and the plan entries of the changed rows."""
     from .failover import _from_topics
     topics = list(topics)
     if not topics:
@@ -276,7 +288,7 @@ def balance_leaders_weighted(topics: Sequence[Topic], weights, min_gain: int = 0
         if len(per) != len(topics) or any(len(w) != t.n_partitions for w, t in zip(per, topics)):
             raise ValueError("weights: one array of n_partitions values per topic")
         weight = np.concatenate(per)
-    plan = _plan_weighted(fi.keys, fi.rows, fi.broker_ids, weight, min_gain, max_rounds, dry_run)
+    plan = _plan_weighted(fi.keys, fi.rows, fi.broker_ids, weight, min_gain, max_rounds, dry_run, exchange)
     plan.assignments, at = [], 0
     for i, t in enumerate(topics):
         w = t.current.shape[1] if assignments is None else np.asarray(assignments[i]).reshape(t.n_partitions, -1).shape[1]
@@ -286,10 +298,11 @@ def balance_leaders_weighted(topics: Sequence[Topic], weights, min_gain: int = 0
 
 
 def weighted_report_line(res: WeightedLeaderResult) -> str:
-    """The --traffic / --sizes --report text, as cli/kao-leaders prints it."""
+    """The --traffic / --sizes --report text, as cli/kao-leaders prints it: a second line with --exchange."""
     s = res.stats
-    return (f"weighted: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
+    line = (f"weighted: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
             f"leader_changes={res.n_changed} rounds={s[0]} moves={s[1]} launches={s[3]}")
+    return line + (f"\nexchange: rounds={s[8]} exchanges={s[9]} proposals={s[10]} pair_index_entries={s[11]}" if res.exchange else "")
 
 
 def plan_text(entries) -> str:
@@ -318,6 +331,7 @@ def main(argv=None) -> int:
     ap.add_argument("--default-weight", type=weight_arg, default=None, help="weight of the partitions the file does not name")
     ap.add_argument("--min-gain", type=u64, default=None, help="weighted: a leader moves only when it lowers its broker's lead over the target by more than N")
     ap.add_argument("--max-rounds", type=count, default=None, help="weighted: stop after N rounds")
+    ap.add_argument("--exchange", action="store_true", help="weighted: when no single leader change helps, swap the leaders of two partitions on one broker pair")
     a = ap.parse_args(argv)
     weighted = a.traffic is not None or a.sizes is not None
     if a.traffic is not None and a.sizes is not None:
@@ -326,6 +340,8 @@ def main(argv=None) -> int:
         ap.error("--traffic / --sizes cannot be combined with --slack, --auto-slack, --cluster, --cluster-lo or --cluster-hi")
     if not weighted and (a.default_weight is not None or a.min_gain is not None or a.max_rounds is not None):
         ap.error("--default-weight, --min-gain and --max-rounds need --traffic or --sizes")
+    if a.exchange and not weighted:
+        ap.error("--exchange needs --traffic or --sizes")
     a.slack = 0 if a.slack is None else a.slack
     a.cluster_lo = 0 if a.cluster_lo is None else a.cluster_lo
     a.cluster_hi = -1 if a.cluster_hi is None else a.cluster_hi
@@ -357,7 +373,7 @@ def main(argv=None) -> int:
             weight = weights_for(fi.keys, table, a.default_weight)
             from .solver import init
             init(a.device)
-            plan = _plan_weighted(fi.keys, fi.rows, fi.broker_ids, weight, a.min_gain or 0, a.max_rounds or 0, False)
+            plan = _plan_weighted(fi.keys, fi.rows, fi.broker_ids, weight, a.min_gain or 0, a.max_rounds or 0, False, a.exchange)
             if a.report:
                 print(weighted_report_line(plan.result), file=sys.stderr)
             text = plan_text(plan.entries)

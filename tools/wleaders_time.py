@@ -4,6 +4,11 @@ with log-normal weights of sigma 0.7 and 1.5.  One JSON line per case: peaks, lo
 changes, the stats (rounds, moves, proposals, kernel launches, path) and the wall time of the call (median of --reps after one
 warm-up; it includes the host validation, the upload and the read-back).  --threshold times both kernel paths (kao_wleaders_test_path)
 on 300 brokers x P partitions for a ladder of P: where the single workgroup stops paying is the size threshold of DESIGN.md 4k.
+--exchange times kao_balance_leaders_weighted_exchange beside kao_balance_leaders_weighted, in one process and on
+the same inputs: wleaders_ref.lognormal_case(B, P, 3, sigma, 7) at 12 x 1,200, 100 x 10,000 (sigma 0.7 and 1.5), 500 x 10,000 and
+1000 x 100,000, and 12 x 1,200 on each forced kernel path.  Per instance and call: peak / bound, leader changes, the rounds of both
+kinds, the exchanges, the launches, the wall time, and for the exchange call the share of it the host spends building PI and the pair
+index (kao_wleaders_last_setup_us).  Writes profiles/wleaders_x_time.txt with --write.
 For kernel times run it under `rocprofv3 --kernel-trace --stats --` (in a run of its own).  Writes the lines to
 profiles/wleaders_time.txt with --write."""
 import argparse
@@ -23,7 +28,10 @@ def main():
     ap.add_argument("--cases", default="config4,large")
     ap.add_argument("--threshold", action="store_true", help="time both kernel paths on a ladder of sizes instead")
     ap.add_argument("--write", action="store_true", help="write the lines to profiles/wleaders_time.txt as well")
+    ap.add_argument("--exchange", action="store_true", help="time kao_balance_leaders_weighted_exchange beside kao_balance_leaders_weighted (see the head of this file)")
     a = ap.parse_args()
+    if a.exchange and a.threshold:
+        ap.error("--exchange and --threshold are two runs")
     import numpy as np
     import kafka_assignment_optimizer_amd as kao
     from kafka_assignment_optimizer_amd import _ffi
@@ -36,17 +44,37 @@ def main():
         rng = np.random.default_rng(seed)
         return np.maximum(1, np.round(np.exp(rng.normal(np.log(2.0 ** 20), sigma, P)))).astype(np.int64)
 
-    def timed(rows, B, weight):
-        res = balance_leaders_weighted_arrays(rows, B, weight, dry_run=True)   # warm-up
+    def timed(rows, B, weight, exchange=False):
+        res = balance_leaders_weighted_arrays(rows, B, weight, dry_run=True, exchange=exchange)   # warm-up
         ms = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            res = balance_leaders_weighted_arrays(rows, B, weight, dry_run=True)
+            res = balance_leaders_weighted_arrays(rows, B, weight, dry_run=True, exchange=exchange)
             ms.append(1e3 * (time.perf_counter() - t0))
         return res, round(float(np.median(ms)), 3)
 
     lines = []
-    if a.threshold:
+    if a.exchange:
+        lib = _ffi.load()
+        for B, P, sigma, path in ((12, 1200, 0.7, 0), (100, 10000, 0.7, 0), (100, 10000, 1.5, 0), (500, 10000, 0.7, 0), (1000, 100000, 0.7, 0),
+                                  (12, 1200, 0.7, 1), (12, 1200, 0.7, 2)):
+            rows, weight = wr.lognormal_case(B, P, 3, sigma, 7)
+            lib.kao_wleaders_test_path(path)
+            plain, plain_ms = timed(rows, B, weight)
+            res, ms = timed(rows, B, weight, exchange=True)
+            setup_ms = lib.kao_wleaders_last_setup_us() / 1e3
+            lib.kao_wleaders_test_path(0)
+            line = {"workload": "lognormal", "brokers": B, "partitions": P, "sigma": sigma, "forced_path": path}
+            for tag, r, t in (("plain", plain, plain_ms), ("exchange", res, ms)):
+                line.update({f"{tag}_peak_over_bound": round(r.peak_after / max(r.lower_bound, 1), 6), f"{tag}_n_changed": r.n_changed,
+                             f"{tag}_all_rounds": int(r.stats[0]), f"{tag}_launches": int(r.stats[3]), f"{tag}_wall_ms_median": t})
+            line.update({"single_workgroup": int(res.stats[4]), "move_rounds": int(res.stats[0] - res.stats[8]), "exchange_rounds": int(res.stats[8]),
+                         "exchanges": int(res.stats[9]), "exchange_proposals": int(res.stats[10]), "pair_index_entries": int(res.stats[11]),
+                         "setup_ms_last": round(setup_ms, 3), "setup_share": round(setup_ms / ms, 3)})
+            assert res.peak_after <= plain.peak_after
+            lines.append(json.dumps(line))
+            print(lines[-1], flush=True)
+    elif a.threshold:
         set_path = _ffi.load().kao_wleaders_test_path
         for P in (500, 1000, 2000, 4000, 8000, 16000, 32000, 64000):
             rows, weight = wr.lognormal_case(300, P, 3, 0.7, 5)
@@ -79,7 +107,7 @@ def main():
                 lines.append(json.dumps(line))
                 print(lines[-1], flush=True)
     if a.write:
-        with open(os.path.join(ROOT, "profiles", "wleaders_time.txt"), "a" if a.threshold else "w") as f:
+        with open(os.path.join(ROOT, "profiles", "wleaders_x_time.txt" if a.exchange else "wleaders_time.txt"), "a" if a.threshold else "w") as f:
             f.write("\n".join(lines) + "\n")
 
 
