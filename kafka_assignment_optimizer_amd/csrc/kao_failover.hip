@@ -5,10 +5,10 @@
 // leader of p down, the slot e(p) = the first eligible follower inherits p.  Choosing another eligible slot j(p) and swapping it
 // with e(p) moves no data.  For a cap M on every surviving broker's leaders, scenario g is a min-cost flow: each affected partition
 // sends one unit to a broker of an eligible slot (cost 0 for e(p), 1 otherwise), broker b takes at most M - lead[b] units.
-// (the first three kernels, the host function that runs them and the host-side checks live in kao_failover_dev.h, shared with
-// kao_wfailover.hip)
+// (the first and the third kernel, the host function that runs the three and the host-side checks live in kao_failover_dev.h, shared
+// with kao_wfailover.hip; the second in kao_plan_dev.h)
 //   k_fo_classify  one pass over the partitions: lead[], the scenario of p, its eligible slots, e(p), the scenarios' sizes
-//   k_fo_offsets   exclusive scan of the sizes (one workgroup)
+//   k_bucket_offsets  exclusive scan of the sizes (one workgroup)
 //   k_fo_scatter   the affected partitions bucketed by scenario (counting sort; the order inside a bucket is not used)
 //   k_fo_solve     ONE WORKGROUP PER SCENARIO, all scenarios in one launch: bisection on M between the lower end
 //                  max(max lead, ceil(leaders left / brokers left)) and peak_before, every probe a max-flow from the start state

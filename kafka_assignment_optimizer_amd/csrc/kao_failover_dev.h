@@ -1,7 +1,7 @@
 // kao_failover_dev.h -- what kao_failover_order (kao_failover.hip) and kao_failover_order_weighted
-// (kao_wfailover.hip, section 4l) share: the scenario model's passes over the partitions (classify, offsets, scatter), the host
-// function that runs them (fo_prelude) and the host-side checks of the arguments.  Included by those two .hip files only: everything
-// sits in an unnamed namespace, so each gets its own copy of the kernels.
+// (kao_wfailover.hip, section 4l) share: the scenario model's passes over the partitions (classify and scatter; the offsets between
+// them are k_bucket_offsets of kao_plan_dev.h), the host function that runs them (fo_prelude) and the host-side checks of the
+// arguments.  Included by those two .hip files only: everything sits in an unnamed namespace, so each gets its own copy of the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include <string>
 
 #include "kao_host.h"
+#include "kao_plan_dev.h"   // k_bucket_offsets
 
 namespace {
 
@@ -44,29 +45,6 @@ __global__ void k_fo_classify(int P, int W, int scope, const uint16_t *__restric
     atomicAdd(e ? &cnt[g] : &off[g], 1);
 }
 
-// start[g] = sum of cnt[0..g), fill[g] = 0; ctl[FS_MAXN] = the largest cnt.  One workgroup.
-__global__ __launch_bounds__(1024) void k_fo_offsets(int G, const int32_t *__restrict__ cnt, int32_t *__restrict__ start,
-                                                      int32_t *__restrict__ fill, int32_t *__restrict__ ctl) {
-    __shared__ int32_t part[1024];
-    __shared__ int32_t mx;
-    const int tid = threadIdx.x, NT = blockDim.x, per = (G + NT - 1) / NT, lo = min(tid * per, G), hi = min(lo + per, G);
-    if (tid == 0) mx = 0;
-    __syncthreads();
-    int s = 0, m = 0;
-    for (int g = lo; g < hi; ++g) { s += cnt[g]; m = max(m, cnt[g]); }
-    part[tid] = s;
-    if (m) atomicMax(&mx, m);
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int i = 0; i < NT; ++i) { const int v = part[i]; part[i] = acc; acc += v; }
-        ctl[FS_MAXN] = mx;
-    }
-    __syncthreads();
-    s = part[tid];
-    for (int g = lo; g < hi; ++g) { start[g] = s; fill[g] = 0; s += cnt[g]; }
-}
-
 __global__ void k_fo_scatter(int P, const int32_t *__restrict__ scen_of, const uint16_t *__restrict__ meta, const int32_t *__restrict__ start,
                              int32_t *__restrict__ fill, int32_t *__restrict__ list) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -91,7 +69,7 @@ int fo_prelude(hipStream_t st, int P, int W, int G, int scope, const uint16_t *d
         k_fo_classify<<<pblocks, kFoThreads, 0, st>>>(P, W, scope, d_rows, d_rack, d.lead, d.scen_of, d.meta, d.cur, d.claim, d.cnt, d.off);
         ++*launches;
     }
-    k_fo_offsets<<<1, 1024, 0, st>>>(G, d.cnt, d.start, d.fill, d.ctl);
+    k_bucket_offsets<<<1, 1024, 0, st>>>(G, d.cnt, nullptr, d.start, d.fill, d.ctl + FS_MAXN);   // start[], fill[] = 0, ctl[FS_MAXN] = the largest cnt
     ++*launches;
     if (P) {
         k_fo_scatter<<<pblocks, kFoThreads, 0, st>>>(P, d.scen_of, d.meta, d.start, d.fill, d.list);

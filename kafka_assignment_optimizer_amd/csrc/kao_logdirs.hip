@@ -4,8 +4,15 @@
 // Broker b owns the dirs dir_start[b] .. dir_start[b+1]-1 (at most KAO_LOGDIRS_MAX_DIRS), dir d carries base[d] bytes that never move,
 // replica r sits in dir[r] with size[r] bytes, L(d) = base[d] + the sizes of its replicas.  A move takes r to another dir of the same
 // broker: the brokers are independent sub-problems, and each is the descent of section 4k with the pairing of section 4m:
-//   k_ld_count, k_ld_offsets, k_ld_scatter   the replicas bucketed by broker (count, prefix sum + largest bucket, scatter)
+//   k_ld_count, k_bucket_offsets (kao_plan_dev.h), k_ld_scatter   the replicas bucketed by broker (count, prefix sum + largest bucket, scatter)
 //   k_ld_solve   ONE WORKGROUP PER BROKER, all brokers in one launch: every round, then the bound, then the row of per_broker
+// THE FRAME of a broker's workgroup is written once and shared by k_ld_solve and k_ld_place (below): its static LDS is one LdLds, its
+// broker one LdBroker.  ld_begin: a broker without dirs gets its row at once; else base (and cap) into the loads, one pass over the
+// bucket that adds the residents' sizes and hands a homeless replica to the caller, the peak before and the statistics of the bound.
+// ld_end: the peak after, the replicas that left their input dir, the bound and its proof, the row of per_broker (its columns per
+// kernel: kLdRow) and the call's counters.  Between the two stands what is the kernel's own: the rounds (ld_rounds, ld_xchg_rounds)
+// for k_ld_solve; sort, greedy pass and, when asked, the rounds for k_ld_place.  On the host LdCall is the same frame around the
+// launch: open (arena, uploads, buckets, lane count, common arguments), finish (read-back and outputs).
 // A ROUND uses the loads as they stand at its start and has four parts with a barrier after each:
 //   RANK     the lanes below n rank the broker's n dirs by L descending (ties: index ascending) by all pairs out of LDS;
 //   PROPOSE  every replica with size > 0 (n >= 2) on a of rank q takes c1 = order[n-1-q] when q < n-1-q and proposes a -> c1 iff
@@ -25,10 +32,11 @@
 // (dir[r] == -1: a replica that a plan brings to the broker, or one of a dir that is being emptied).  The buckets are keyed by
 // broker[r], through the same three passes, which also count the homeless replicas of a broker and the largest such count.
 //   k_ld_place   ONE WORKGROUP PER BROKER: the loads F of the residents into LDS, the homeless replicas compacted into (~size, r)
-//                entries and sorted (size descending, then r ascending) by a bitonic network, in dynamic LDS up to kLdSortLds entries
-//                a broker and else in the bucket's own scratch in global memory; wavefront 0 then takes them one by one, each to the
-//                dir with the lowest load at that moment (ties: the lowest index); with move_residents the rounds above follow
-//                (ld_rounds, the one copy of the loop that k_ld_solve calls too); then the bound and the row of per_broker.
+//                entries (both in the pass of ld_begin) and sorted (size descending, then r ascending) by a bitonic network, in
+//                dynamic LDS up to kLdSortLds entries a broker and else in the bucket's own scratch in global memory; wavefront 0
+//                then takes them one by one, each to the dir with the lowest load at that moment (ties: the lowest index); with
+//                move_residents the rounds above follow (ld_rounds, the one copy of the loop that k_ld_solve calls too); then
+//                ld_end: the bound and the row of per_broker.
 // Its bound: M = the replicas that may change dir (the homeless; all with move_residents), F' = the fixed loads (F; base with
 // move_residents): the maximum of (0) the largest size in M + the smallest F', (1) ceil((sum of base + sum of size) / n), (2) the largest F'.
 //
@@ -102,6 +110,31 @@ struct LdNetX : LdNet {         // the exchange call (X; per_broker is then [8B]
     u64 *xm;                    // [R + n_dirs] the masks of broker b on the global path, from word start[b] + dir_start[b]
     uint32_t *xp;               // [R] by position in PI: the position of the partner of this round's proposal
 };
+
+// The static LDS of a broker's workgroup: the loads (Cap: the pairs {load, cap}), the minkey words, the LS_* words, the ranks of the dirs and the dirs by rank.
+template <bool Cap>
+struct LdLds {
+    alignas(16) u64 load[(Cap ? 2 : 1) * kLdMaxDirs];   // 16 bytes: RANK reads two loads (Cap: one {load, cap}) with one 128-bit LDS read
+    u64 mk[kLdMaxDirs], sh[LS_N];
+    uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
+};
+// The broker of a workgroup: its dirs ds .. ds + nd - 1, its bucket (nr replicas, h of them homeless) with the round state at the bucket's place `at`, its row of per_broker.
+struct LdBroker {
+    int ds, nd, nr, h, at;
+    const int32_t *list;
+    u64 *key;
+    uint8_t *dst;
+    u64 *o;
+    u64 fixed;   // Cap: F(d), the load of dir d with its residents alone, in lane d of wavefront 0
+};
+// A row of per_broker: {peak before, peak after, bound}, with Cap the three as fractions {peak, its cap, peak, its cap, bound num, den}, then {placed, bytes
+// placed} from column `placed`, {moved, bytes moved, rounds} from `moved`, {exchange rounds, exchanges} from `xch`, the proof at `proof`; -1 = not in the row.
+struct LdRow {
+    int w, placed, moved, xch, proof;
+};
+template <bool Cap, bool X, bool Place>
+constexpr LdRow kLdRow = Place ? (Cap ? LdRow{12, 6, 8, -1, 11} : LdRow{8, 3, 5, -1, -1})   // k_ld_place
+                               : X ? LdRow{8, -1, 3, 6, -1} : Cap ? LdRow{10, -1, 6, -1, 9} : LdRow{6, -1, 3, -1, -1};   // k_ld_solve
 
 // ---- Cap: the descent by utilisation u(d) = L(d) / cap(d) -------------------------------------------------------
 // The loads of a broker sit in LDS as load[d] (Cap = false) or as the pairs {load, cap} = load[2d], load[2d + 1] (Cap = true): one
@@ -187,35 +220,7 @@ __global__ void k_ld_count(int R, const int32_t *__restrict__ idx, const int32_t
     if (hcnt && dir[r] < 0) atomicAdd(&hcnt[b], 1);
 }
 
-// start[b] = sum of cnt[0..b), fill[b] = 0; max_n[0] = the largest cnt, max_n[1] = the largest hcnt (0 without hcnt).  One workgroup.  (k_fo_offsets of kao_failover_dev.h is this pass;
-// that header carries the scenario kernels, their host driver and the failover control block whose FS_MAXN word the kernel writes,
-// all in an unnamed namespace: including it here would compile the failover passes into this file, and moving the kernel out would
-// change the two files that use it.  So the twenty lines are written once more, with the maximum going to a word of the caller's.)
-__global__ __launch_bounds__(1024) void k_ld_offsets(int B, const int32_t *__restrict__ cnt, const int32_t *__restrict__ hcnt, int32_t *__restrict__ start,
-                                                      int32_t *__restrict__ fill, u64 *__restrict__ max_n) {
-    __shared__ int32_t part[1024];
-    __shared__ int32_t mx, mh;
-    const int tid = threadIdx.x, NT = blockDim.x, per = (B + NT - 1) / NT, lo = min(tid * per, B), hi = min(lo + per, B);
-    if (tid == 0) { mx = 0; mh = 0; }
-    __syncthreads();
-    int s = 0, m = 0, h = 0;
-    for (int b = lo; b < hi; ++b) { s += cnt[b]; m = max(m, cnt[b]); }
-    for (int b = lo; hcnt && b < hi; ++b) h = max(h, hcnt[b]);
-    part[tid] = s;
-    if (m) atomicMax(&mx, m);
-    if (h) atomicMax(&mh, h);
-    __syncthreads();
-    if (tid == 0) {
-        int acc = 0;
-        for (int i = 0; i < NT; ++i) { const int v = part[i]; part[i] = acc; acc += v; }
-        max_n[0] = (u64)mx;
-        max_n[1] = (u64)mh;
-    }
-    __syncthreads();
-    s = part[tid];
-    for (int b = lo; b < hi; ++b) { start[b] = s; fill[b] = 0; s += cnt[b]; }
-}
-
+// (between the two: k_bucket_offsets of kao_plan_dev.h, whose maxima, the largest cnt and the largest hcnt, go to ctl[LC_MAXN] and ctl[LC_MAXH])
 // the order inside a bucket does not reach the result: the keys carry r
 __global__ void k_ld_scatter(int R, const int32_t *__restrict__ idx, const int32_t *__restrict__ map, const int32_t *__restrict__ start,
                              int32_t *__restrict__ fill, int32_t *__restrict__ list) {
@@ -275,10 +280,12 @@ __device__ __forceinline__ bool ld_xchg_passes(u64 w, u64 sy, u64 D, u64 min_gai
     return true;
 }
 template <bool Cap, bool X = false>
-__device__ __forceinline__ std::conditional_t<X, LdTallyX, LdTally> ld_rounds(const LdNet &n, int ds, int nd, int nr, const int32_t *list, u64 *key, uint8_t *dst, u64 *load, u64 *mk, uint8_t *rank,
-                                             uint8_t *order, const LdXchg x = LdXchg()) {
+__device__ __forceinline__ std::conditional_t<X, LdTallyX, LdTally> ld_rounds(const LdNet &n, const LdBroker &br, LdLds<Cap> &s, const LdXchg x = LdXchg()) {
     static_assert(!(Cap && X), "exchange rounds are by bytes");
-    const int tid = threadIdx.x, NT = blockDim.x;
+    const int tid = threadIdx.x, NT = blockDim.x, ds = br.ds, nd = br.nd, nr = br.nr;
+    const int32_t *list = br.list;
+    u64 *key = br.key, *load = s.load, *mk = s.mk;
+    uint8_t *dst = br.dst, *rank = s.rank, *order = s.order;
     std::conditional_t<X, LdTallyX, LdTally> t;
     [[maybe_unused]] u64 peak = 0;         // X: the peak at the start of the round before
     [[maybe_unused]] bool was_x = false;   // X: that round was an exchange round
@@ -457,11 +464,10 @@ __device__ __forceinline__ void ld_sort(K sk, I sr, int h);   // below, with k_l
 
 // ---- the rounds with exchanges of one broker: PI into ps[] / pr[] (nr entries each), the masks into mask[]
 // (nd rows of nr / 64 + 1 words), then ld_rounds<false, true> over the positions of PI.  Called by every lane of the workgroup.
-__device__ __forceinline__ LdTallyX ld_xchg_rounds(const LdNet &n, int ds, int nd, int nr, const int32_t *list, u64 *key, uint8_t *dst, u64 *load, u64 *mk,
-                                                  uint8_t *rank, uint8_t *order, u64 *ps, u64 *mask, uint32_t *pr, uint32_t *partner) {
-    const int tid = threadIdx.x, NT = blockDim.x, words = nr / 64 + 1;
+__device__ __forceinline__ LdTallyX ld_xchg_rounds(const LdNet &n, const LdBroker &br, LdLds<false> &s, u64 *ps, u64 *mask, uint32_t *pr, uint32_t *partner) {
+    const int tid = threadIdx.x, NT = blockDim.x, ds = br.ds, nd = br.nd, nr = br.nr, words = nr / 64 + 1;
     for (int q = tid; q < nr; q += NT) {   // the sort's entries (~size, r), in any order
-        const int r = list[q];
+        const int r = br.list[q];
         ps[q] = ~n.size[r];
         pr[q] = (uint32_t)r;
     }
@@ -485,48 +491,56 @@ __device__ __forceinline__ LdTallyX ld_xchg_rounds(const LdNet &n, int ds, int n
     // (the barrier of the first RANK comes before any read of ps[] and mask[])
     LdXchg x;
     x.ps = ps; x.mask = mask; x.partner = partner; x.words = words;
-    return ld_rounds<false, true>(n, ds, nd, nr, reinterpret_cast<const int32_t *>(pr), key, dst, load, mk, rank, order, x);
+    LdBroker pi = br;   // the rounds stride over the positions of PI
+    pi.list = reinterpret_cast<const int32_t *>(pr);
+    return ld_rounds<false, true>(n, pi, s, x);
 }
 
-// ---- one broker ---------------------------------------------------------------------------------------------------------------------
-// X (kao_balance_logdirs_exchange): dynamic LDS on the LDS path: PI's sizes u64[x_cap], the masks u64[x_mcap], PI's r u32[x_cap]; the
-// other path keeps them in xs[], xm[] and sr[] at the bucket's place, which this workgroup alone touches.
-template <bool Cap, bool X = false>
-__global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(std::conditional_t<X, LdNetX, LdNet> n) {
-    __shared__ alignas(16) u64 load[(Cap ? 2 : 1) * kLdMaxDirs];   // 16 bytes: RANK reads two loads (Cap: one {load, cap}) with one 128-bit LDS read
-    __shared__ u64 mk[kLdMaxDirs], sh[LS_N];
-    __shared__ uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
-    constexpr int W = X ? 8 : Cap ? 10 : 6;   // columns of a row of per_broker
+// ---- the frame of one broker: what k_ld_solve and k_ld_place do before and after the parts of their own ------------------------------
+// BEGIN, by every lane: the broker of this workgroup into br.  Without a dir its row is written here (zeros, the fractions 0 / 1,
+// nothing to prove) and the answer is true: the workgroup is done.  Else the LS_* words are cleared, base and cap go into the loads,
+// mk[] to kLdNoKey, and one pass over the bucket adds a resident's size to the load of its dir and, with Place, hands a homeless
+// replica to homeless(r, size) and sums LS_HBYTES; LS_MAXSIZE = the largest size of the replicas that may change dir.  Then the peak
+// before: Cap: the fullest dir as a fraction by wavefront 0, with F(d) into br.fixed; else LS_PEAK0 and LS_TOTAL, with Place LS_MINF,
+// beside the smallest and the largest base.  No barrier closes it: the caller's next one does.
+template <bool Cap, bool X, bool Place, class Homeless>
+__device__ __forceinline__ bool ld_begin(const LdNet &n, LdLds<Cap> &s, LdBroker &br, Homeless homeless) {
+    constexpr LdRow row = kLdRow<Cap, X, Place>;
     const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
     const int ds = n.dir_start[b], nd = n.dir_start[b + 1] - ds, nr = n.cnt[b], at = n.start[b];
-    u64 *o = n.per_broker + W * (size_t)b;
-    if (nd == 0) {   // no dir, so no replica: zeros (the fractions 0 / 1), and nothing to prove
+    u64 *sh = s.sh, *o = n.per_broker + row.w * (size_t)b;
+    br = {ds, nd, nr, Place ? n.hcnt[b] : 0, at, n.list + at, n.key + at, n.dst + at, o, 0};
+    if (nd == 0) {   // no dir, so no replica
         if (tid == 0) {
-            for (int i = 0; i < W; ++i) o[i] = 0;
-            if constexpr (Cap) { o[1] = o[3] = o[5] = 1; o[9] = 1; }
+            for (int i = 0; i < row.w; ++i) o[i] = 0;
+            if constexpr (Cap) { o[1] = o[3] = o[5] = 1; o[row.proof] = 1; }
             atomicAdd(&n.ctl[LC_PROVEN], 1ull);
         }
-        return;
+        return true;
     }
-    const int32_t *list = n.list + at;
-    u64 *key = n.key + at;
-    uint8_t *dst = n.dst + at;
-    if (tid < LS_N) sh[tid] = tid == LS_MINBASE ? kLdNoKey : 0;
+    if (tid < LS_N) sh[tid] = (tid == LS_MINBASE || tid == LS_MINF) ? kLdNoKey : 0;
     if (tid < nd) {
-        ld_load<Cap>(load, tid) = n.base[ds + tid];
-        if constexpr (Cap) load[2 * tid + 1] = n.cap[ds + tid];
-        mk[tid] = kLdNoKey;
+        ld_load<Cap>(s.load, tid) = n.base[ds + tid];
+        if constexpr (Cap) s.load[2 * tid + 1] = n.cap[ds + tid];
+        s.mk[tid] = kLdNoKey;
     }
     __syncthreads();
-    {   // the loads of the input, the largest size
-        u64 mx = 0;
+    {
+        u64 mx = 0, hb = 0;
         for (int q = tid; q < nr; q += NT) {
-            const int r = list[q];
+            const int r = br.list[q], d = n.dir[r];
             const u64 w = n.size[r];
-            if (w) atomicAdd(&ld_load<Cap>(load, n.dir[r] - ds), w);
-            mx = max(mx, w);
+            if (!Place || d >= 0) {
+                if (w) atomicAdd(&ld_load<Cap>(s.load, d - ds), w);
+                if (!Place || n.move_residents) mx = max(mx, w);
+            } else {
+                homeless(r, w);
+                hb += w;
+                mx = max(mx, w);
+            }
         }
         if (mx) atomicMax(&sh[LS_MAXSIZE], mx);
+        if (hb) atomicAdd(&sh[LS_HBYTES], hb);
         if (!Cap && tid < nd) {
             const u64 x = n.base[ds + tid];
             atomicMin(&sh[LS_MINBASE], x);
@@ -534,87 +548,121 @@ __global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(std::conditional_t<X,
         }
     }
     __syncthreads();
-    if constexpr (Cap) {   // the fullest dir of the input: a maximum over fractions, by wavefront 0
+    if constexpr (Cap) {   // a maximum over fractions
         if (tid < 64) {
-            const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
+            const LdPair me = tid < nd ? ld_pair(s.load, tid) : LdPair{0, 1};
+            br.fixed = me.l;
             u64 pn = me.l, pd = me.c;
             int pi = tid;
             ld_frac_reduce<true>(pn, pd, pi);
             if (tid == 0) { sh[LS_PEAK0] = pn; sh[LS_PEAK0DEN] = pd; }
         }
     } else if (tid < nd) {
-        const u64 x = load[tid];
+        const u64 x = s.load[tid];
+        if (Place) atomicMin(&sh[LS_MINF], x);
         if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
     }
-    std::conditional_t<X, LdTallyX, LdTally> t;
-    if constexpr (X) {
-        extern __shared__ u64 ld_dyn[];
-        if (n.x_lds) t = ld_xchg_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order, ld_dyn, ld_dyn + n.x_cap, reinterpret_cast<uint32_t *>(ld_dyn + n.x_cap + n.x_mcap), n.xp + at);
-        else t = ld_xchg_rounds(n, ds, nd, nr, list, key, dst, load, mk, rank, order, n.xs + at, n.xm + at + ds, n.sr + at, n.xp + at);
-    } else {
-        t = ld_rounds<Cap>(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
-    }
-    const int rounds = t.rounds, more = t.more;
-    const u64 props = t.props, moves = t.moves;
-    // ---- the result ----
+    return false;
+}
+
+// END, by every lane, t = the tallies of the rounds (zeros without rounds): the peak after, the replicas that left their input dir and
+// their bytes, the bound and its proof, the row of per_broker (kLdRow) and the call's counters in ctl.  M = the replicas that may
+// change dir, F' = the fixed loads: every replica over base where the residents may move, else the homeless over F.
+// The bound without Cap: the maximum of (0) the largest size in M + the smallest F', (1) ceil(sum of L / n), (2) the largest F'.
+template <bool Cap, bool X, bool Place>
+__device__ __forceinline__ void ld_end(const LdNet &n, LdLds<Cap> &s, const LdBroker &br, const std::conditional_t<X, LdTallyX, LdTally> &t) {
+    constexpr LdRow row = kLdRow<Cap, X, Place>;
+    const int tid = threadIdx.x, NT = blockDim.x, ds = br.ds, nd = br.nd, nr = br.nr, h = br.h;
+    const bool residents = !Place || n.move_residents;
+    u64 *sh = s.sh, *o = br.o;
     if (!Cap && tid < nd) {
-        const u64 x = load[tid];
+        const u64 x = s.load[tid];
         if (x) atomicMax(&sh[LS_PEAK1], x);
     }
-    {
+    if (residents) {
         u64 moved = 0, bytes = 0;
         for (int q = tid; q < nr; q += NT) {
-            const int r = list[q];
-            if (n.dir[r] != n.dir0[r]) { ++moved; bytes += n.size[r]; }
+            const int r = br.list[q], d0 = n.dir0[r];
+            if (d0 >= 0 && n.dir[r] != d0) { ++moved; bytes += n.size[r]; }   // a placed replica is no move
         }
         if (moved) { atomicAdd(&sh[LS_NMOVED], moved); atomicAdd(&sh[LS_BYTES], bytes); }
-        if (moves) atomicAdd(&sh[LS_MOVES], moves);
-        if (props) atomicAdd(&sh[LS_PROPS], props);
+        if (t.moves) atomicAdd(&sh[LS_MOVES], t.moves);
+        if (t.props) atomicAdd(&sh[LS_PROPS], t.props);
         if constexpr (X) {
             if (t.xch) atomicAdd(&sh[LS_XCH], t.xch);
             if (t.xprops) atomicAdd(&sh[LS_XPROPS], t.xprops);
         }
     }
     __syncthreads();
+    const bool any = residents ? nr > 0 : h > 0;   // M is not empty
     int proof = 0;
-    if constexpr (Cap) {   // M = every replica, F' = base; the call's peaks are reduced from the rows on the host
+    if constexpr (Cap) {   // the call's peaks are reduced from the rows on the host
         if (tid >= 64) return;
-        const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
-        proof = ld_cap_bound(nd, me.l, me.c, tid < nd ? n.base[ds + tid] : 0, sh[LS_MAXSIZE], nr > 0, o + 2);
+        const LdPair me = tid < nd ? ld_pair(s.load, tid) : LdPair{0, 1};
+        const u64 fixed = !residents ? br.fixed : tid < nd ? n.base[ds + tid] : 0;
+        proof = ld_cap_bound(nd, me.l, me.c, fixed, sh[LS_MAXSIZE], any, o + 2);
     }
-    if (tid == 0) {
-        if constexpr (Cap) {
-            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK0DEN]; o[6] = sh[LS_NMOVED]; o[7] = sh[LS_BYTES]; o[8] = (u64)rounds; o[9] = (u64)proof;
-            if (proof) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
-        } else {
-            const u64 t0 = nr ? sh[LS_MAXSIZE] + sh[LS_MINBASE] : 0, t1 = (sh[LS_TOTAL] + (u64)nd - 1) / (u64)nd;
-            const u64 lb = max(max(t0, t1), sh[LS_MAXBASE]);
-            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = sh[LS_NMOVED]; o[4] = sh[LS_BYTES]; o[5] = (u64)rounds;
-            atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
-            atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
-            if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
-            if constexpr (X) {
-                o[6] = (u64)t.xrounds; o[7] = sh[LS_XCH];
-                if (t.xrounds) {
-                    atomicAdd(&n.ctl[LC_XROUNDS], (u64)t.xrounds);
-                    atomicAdd(&n.ctl[LC_XCH], sh[LS_XCH]);
-                    atomicAdd(&n.ctl[LC_XPROPS], sh[LS_XPROPS]);
-                    if (t.xlowered) atomicAdd(&n.ctl[LC_XLOWER], 1ull);
-                }
-            }
-        }
-        if (rounds) {
-            atomicAdd(&n.ctl[LC_BROKERS], 1ull);   // every round with a proposal applies a move
-            atomicAdd(&n.ctl[LC_ROUNDS], (u64)rounds);
-            atomicAdd(&n.ctl[LC_MOVES], sh[LS_MOVES]);
-            atomicAdd(&n.ctl[LC_PROPS], sh[LS_PROPS]);
-            atomicMax(&n.ctl[LC_MAXROUNDS], (u64)rounds);
-            atomicAdd(&n.ctl[LC_NMOVED], sh[LS_NMOVED]);
-            atomicAdd(&n.ctl[LC_BYTES], sh[LS_BYTES]);
-        }
-        if (more) atomicAdd(&n.ctl[LC_MORE], 1ull);
-        if (rounds >= kLdHardRounds) atomicAdd(&n.ctl[LC_ERR], 1ull);
+    if (tid != 0) return;
+    if constexpr (Cap) {
+        o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK0DEN]; o[row.proof] = (u64)proof;
+        if (proof) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
+    } else {
+        const u64 t0 = any ? sh[LS_MAXSIZE] + (residents ? sh[LS_MINBASE] : sh[LS_MINF]) : 0;
+        const u64 t1 = (sh[LS_TOTAL] + sh[LS_HBYTES] + (u64)nd - 1) / (u64)nd;   // sum of F + the homeless = sum of base + every size
+        const u64 lb = max(max(t0, t1), residents ? sh[LS_MAXBASE] : sh[LS_PEAK0]);
+        o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb;
+        atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
+        atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
+        if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
     }
+    o[row.moved] = sh[LS_NMOVED]; o[row.moved + 1] = sh[LS_BYTES]; o[row.moved + 2] = (u64)t.rounds;
+    if constexpr (Place) {
+        o[row.placed] = (u64)h; o[row.placed + 1] = sh[LS_HBYTES];
+        if (h) {
+            atomicAdd(&n.ctl[LC_PLACERS], 1ull);
+            atomicAdd(&n.ctl[LC_NPLACED], (u64)h);
+            atomicAdd(&n.ctl[LC_BPLACED], sh[LS_HBYTES]);
+        }
+    }
+    if constexpr (X) {
+        o[row.xch] = (u64)t.xrounds; o[row.xch + 1] = sh[LS_XCH];
+        if (t.xrounds) {
+            atomicAdd(&n.ctl[LC_XROUNDS], (u64)t.xrounds);
+            atomicAdd(&n.ctl[LC_XCH], sh[LS_XCH]);
+            atomicAdd(&n.ctl[LC_XPROPS], sh[LS_XPROPS]);
+            if (t.xlowered) atomicAdd(&n.ctl[LC_XLOWER], 1ull);
+        }
+    }
+    if (t.rounds) {
+        atomicAdd(&n.ctl[LC_BROKERS], 1ull);   // every round with a proposal applies a move
+        atomicAdd(&n.ctl[LC_ROUNDS], (u64)t.rounds);
+        atomicAdd(&n.ctl[LC_MOVES], sh[LS_MOVES]);
+        atomicAdd(&n.ctl[LC_PROPS], sh[LS_PROPS]);
+        atomicMax(&n.ctl[LC_MAXROUNDS], (u64)t.rounds);
+        atomicAdd(&n.ctl[LC_NMOVED], sh[LS_NMOVED]);
+        atomicAdd(&n.ctl[LC_BYTES], sh[LS_BYTES]);
+    }
+    if (t.more) atomicAdd(&n.ctl[LC_MORE], 1ull);
+    if (t.rounds >= kLdHardRounds) atomicAdd(&n.ctl[LC_ERR], 1ull);
+}
+
+// ---- kao_balance_logdirs: one broker ---------------------------------------------------------------------------------------------------
+// X (kao_balance_logdirs_exchange): dynamic LDS on the LDS path: PI's sizes u64[x_cap], the masks u64[x_mcap], PI's r u32[x_cap]; the
+// other path keeps them in xs[], xm[] and sr[] at the bucket's place, which this workgroup alone touches.
+template <bool Cap, bool X = false>
+__global__ __launch_bounds__(kLdSoloLarge) void k_ld_solve(std::conditional_t<X, LdNetX, LdNet> n) {
+    __shared__ LdLds<Cap> s;
+    LdBroker br;
+    if (ld_begin<Cap, X, false>(n, s, br, [](int, u64) {})) return;
+    std::conditional_t<X, LdTallyX, LdTally> t;
+    if constexpr (X) {
+        extern __shared__ u64 ld_dyn[];
+        if (n.x_lds) t = ld_xchg_rounds(n, br, s, ld_dyn, ld_dyn + n.x_cap, reinterpret_cast<uint32_t *>(ld_dyn + n.x_cap + n.x_mcap), n.xp + br.at);
+        else t = ld_xchg_rounds(n, br, s, n.xs + br.at, n.xm + br.at + br.ds, n.sr + br.at, n.xp + br.at);
+    } else {
+        t = ld_rounds<Cap>(n, br, s);
+    }
+    ld_end<Cap, X, false>(n, s, br, t);
 }
 
 // ---- kao_place_logdirs -----------------------------------------------------------------------------------------
@@ -652,9 +700,12 @@ __device__ __forceinline__ u64 ld_readlane(u64 x, int lane) {   // lane is the s
 // lane 0, a true 64-bit compare with the lane as the tie.  The winner adds the size; lane j keeps the dir of its own entry and
 // stores it after the chunk, off the chain.
 // Cap: the lowest (L + w) / cap instead, by products; a lane past nd carries the highest key over 1 and sorts after every dir.
+// (h, ds and nd come as values, not as the LdBroker: read through the struct, the compiler keeps the bound of the loop over a chunk's
+// entries in a vector register and ends every step of the chain with a vector compare.)
 template <bool Cap, class K, class I>
-__device__ __forceinline__ void ld_greedy(const LdNet &n, K sk, I sr, int h, int ds, int nd, u64 *load) {
+__device__ __forceinline__ void ld_greedy(const LdNet &n, LdLds<Cap> &s, K sk, I sr, int h, int ds, int nd) {
     const int lane = threadIdx.x;
+    u64 *load = s.load;
     int span = 1;
     while (span < nd) span *= 2;
     u64 L = lane < nd ? ld_load<Cap>(load, lane) : kLdNoKey;
@@ -705,145 +756,36 @@ __device__ __forceinline__ void ld_greedy(const LdNet &n, K sk, I sr, int h, int
 template <bool Cap>
 __global__ __launch_bounds__(kLdSoloLarge) void k_ld_place(LdNet n) {
     extern __shared__ u64 ld_dyn[];
-    __shared__ alignas(16) u64 load[(Cap ? 2 : 1) * kLdMaxDirs];   // 16 bytes: RANK reads two loads (Cap: one {load, cap}) with one 128-bit LDS read
-    __shared__ u64 mk[kLdMaxDirs], sh[LS_N];
-    __shared__ uint8_t rank[kLdMaxDirs], order[kLdMaxDirs];
+    __shared__ LdLds<Cap> s;
     __shared__ int fill;
-    constexpr int W = Cap ? 12 : 8;   // columns of a row of per_broker
-    const int b = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
-    const int ds = n.dir_start[b], nd = n.dir_start[b + 1] - ds, nr = n.cnt[b], at = n.start[b], h = n.hcnt[b];
-    u64 *o = n.per_broker + W * (size_t)b;
-    if (nd == 0) {   // no dir, so no replica: zeros (the fractions 0 / 1), and nothing to prove
-        if (tid == 0) {
-            for (int i = 0; i < W; ++i) o[i] = 0;
-            if constexpr (Cap) { o[1] = o[3] = o[5] = 1; o[11] = 1; }
-            atomicAdd(&n.ctl[LC_PROVEN], 1ull);
-        }
-        return;
-    }
-    const int32_t *list = n.list + at;
-    u64 *key = n.key + at;
-    uint8_t *dst = n.dst + at;
-    uint32_t *sr = n.sr + at;
+    const int tid = threadIdx.x;
     u64 *lk = ld_dyn;
     uint32_t *lr = reinterpret_cast<uint32_t *>(ld_dyn + n.sort_cap);
-    if (tid < LS_N) sh[tid] = (tid == LS_MINBASE || tid == LS_MINF) ? kLdNoKey : 0;
-    if (tid < nd) {
-        ld_load<Cap>(load, tid) = n.base[ds + tid];
-        if constexpr (Cap) load[2 * tid + 1] = n.cap[ds + tid];
-        mk[tid] = kLdNoKey;
-    }
-    if (tid == 0) fill = 0;
-    __syncthreads();
-    {   // the loads of the residents; the homeless replicas into the sort's entries, in any order; the largest size of those that may change dir
-        u64 mx = 0, hb = 0;
-        for (int q = tid; q < nr; q += NT) {
-            const int r = list[q], d = n.dir[r];
-            const u64 w = n.size[r];
-            if (d >= 0) {
-                if (w) atomicAdd(&ld_load<Cap>(load, d - ds), w);
-                if (n.move_residents) mx = max(mx, w);
-            } else {
-                const int e = atomicAdd(&fill, 1);   // below h = hcnt[b] <= sort_cap
-                if (n.sort_lds) { lk[e] = ~w; lr[e] = (uint32_t)r; }
-                else { key[e] = ~w; sr[e] = (uint32_t)r; }
-                hb += w;
-                mx = max(mx, w);
-            }
-        }
-        if (mx) atomicMax(&sh[LS_MAXSIZE], mx);
-        if (hb) atomicAdd(&sh[LS_HBYTES], hb);
-        if (!Cap && tid < nd) {
-            const u64 x = n.base[ds + tid];
-            atomicMin(&sh[LS_MINBASE], x);
-            if (x) atomicMax(&sh[LS_MAXBASE], x);
-        }
-    }
-    __syncthreads();
-    u64 fixed = 0;   // Cap: F'(d) in lane d of wavefront 0
-    if constexpr (Cap) {   // the fullest dir by F: a maximum over fractions, by wavefront 0
-        if (tid < 64) {
-            const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
-            fixed = me.l;
-            u64 pn = me.l, pd = me.c;
-            int pi = tid;
-            ld_frac_reduce<true>(pn, pd, pi);
-            if (tid == 0) { sh[LS_PEAK0] = pn; sh[LS_PEAK0DEN] = pd; }
-        }
-    } else if (tid < nd) {
-        const u64 x = load[tid];
-        atomicMin(&sh[LS_MINF], x);
-        if (x) { atomicMax(&sh[LS_PEAK0], x); atomicAdd(&sh[LS_TOTAL], x); }
-    }
+    u64 *gk = n.key + n.start[blockIdx.x];   // the entries of the other path
+    uint32_t *sr = n.sr + n.start[blockIdx.x];
+    LdBroker br;
+    if (tid == 0) fill = 0;   // (the first barrier of BEGIN comes before its pass)
+    const bool done = ld_begin<Cap, false, true>(n, s, br, [lk, lr, gk, sr, lds = n.sort_lds](int r, u64 w) {   // a homeless replica into the sort's entries, in any order
+        const int e = atomicAdd(&fill, 1);                                       // below h = hcnt[b] <= sort_cap
+        if (lds) { lk[e] = ~w; lr[e] = (uint32_t)r; }
+        else { gk[e] = ~w; sr[e] = (uint32_t)r; }
+    });
+    if (done) return;
+    const int h = br.h;
     if (h >= 2) {
         if (n.sort_lds) ld_sort(lk, lr, h);
-        else ld_sort(key, sr, h);
+        else ld_sort(gk, sr, h);
     }
     if (h >= 1) {
         if (tid < 64) {
-            if (n.sort_lds) ld_greedy<Cap>(n, lk, lr, h, ds, nd, load);
-            else ld_greedy<Cap>(n, key, sr, h, ds, nd, load);
+            if (n.sort_lds) ld_greedy<Cap>(n, s, lk, lr, h, br.ds, br.nd);
+            else ld_greedy<Cap>(n, s, gk, sr, h, br.ds, br.nd);
         }
         __syncthreads();   // the loads and the dirs of the placed replicas, for every lane
     }
     LdTally t;
-    if (n.move_residents) t = ld_rounds<Cap>(n, ds, nd, nr, list, key, dst, load, mk, rank, order);
-    // ---- the result ----
-    if (!Cap && tid < nd) {
-        const u64 x = load[tid];
-        if (x) atomicMax(&sh[LS_PEAK1], x);
-    }
-    if (n.move_residents) {
-        u64 moved = 0, bytes = 0;
-        for (int q = tid; q < nr; q += NT) {
-            const int r = list[q], d0 = n.dir0[r];
-            if (d0 >= 0 && n.dir[r] != d0) { ++moved; bytes += n.size[r]; }
-        }
-        if (moved) { atomicAdd(&sh[LS_NMOVED], moved); atomicAdd(&sh[LS_BYTES], bytes); }
-        if (t.moves) atomicAdd(&sh[LS_MOVES], t.moves);
-        if (t.props) atomicAdd(&sh[LS_PROPS], t.props);
-    }
-    __syncthreads();
-    // M = the replicas that may change dir, F' = the fixed loads: the homeless over F, or with move_residents all over base
-    const bool any = n.move_residents ? nr > 0 : h > 0;
-    int proof = 0;
-    if constexpr (Cap) {   // the call's peaks are reduced from the rows on the host
-        if (tid >= 64) return;
-        const LdPair me = tid < nd ? ld_pair(load, tid) : LdPair{0, 1};
-        if (n.move_residents) fixed = tid < nd ? n.base[ds + tid] : 0;
-        proof = ld_cap_bound(nd, me.l, me.c, fixed, sh[LS_MAXSIZE], any, o + 2);
-    }
-    if (tid == 0) {
-        if constexpr (Cap) {
-            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK0DEN]; o[6] = (u64)h; o[7] = sh[LS_HBYTES]; o[8] = sh[LS_NMOVED]; o[9] = sh[LS_BYTES]; o[10] = (u64)t.rounds;
-            o[11] = (u64)proof;
-            if (proof) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
-        } else {
-            const u64 t0 = any ? sh[LS_MAXSIZE] + (n.move_residents ? sh[LS_MINBASE] : sh[LS_MINF]) : 0;
-            const u64 t1 = (sh[LS_TOTAL] + sh[LS_HBYTES] + (u64)nd - 1) / (u64)nd;   // sum of F + the homeless = sum of base + every size
-            const u64 lb = max(max(t0, t1), n.move_residents ? sh[LS_MAXBASE] : sh[LS_PEAK0]);
-            o[0] = sh[LS_PEAK0]; o[1] = sh[LS_PEAK1]; o[2] = lb; o[3] = (u64)h; o[4] = sh[LS_HBYTES]; o[5] = sh[LS_NMOVED]; o[6] = sh[LS_BYTES]; o[7] = (u64)t.rounds;
-            atomicMax(&n.ctl[LC_PEAK0], sh[LS_PEAK0]);
-            atomicMax(&n.ctl[LC_PEAK1], sh[LS_PEAK1]);
-            if (sh[LS_PEAK1] == lb) atomicAdd(&n.ctl[LC_PROVEN], 1ull);
-        }
-        if (h) {
-            atomicAdd(&n.ctl[LC_PLACERS], 1ull);
-            atomicAdd(&n.ctl[LC_NPLACED], (u64)h);
-            atomicAdd(&n.ctl[LC_BPLACED], sh[LS_HBYTES]);
-        }
-        if (t.rounds) {
-            atomicAdd(&n.ctl[LC_BROKERS], 1ull);   // every round with a proposal applies a move
-            atomicAdd(&n.ctl[LC_ROUNDS], (u64)t.rounds);
-            atomicAdd(&n.ctl[LC_MOVES], sh[LS_MOVES]);
-            atomicAdd(&n.ctl[LC_PROPS], sh[LS_PROPS]);
-            atomicMax(&n.ctl[LC_MAXROUNDS], (u64)t.rounds);
-            atomicAdd(&n.ctl[LC_NMOVED], sh[LS_NMOVED]);
-            atomicAdd(&n.ctl[LC_BYTES], sh[LS_BYTES]);
-        }
-        if (t.more) atomicAdd(&n.ctl[LC_MORE], 1ull);
-        if (t.rounds >= kLdHardRounds) atomicAdd(&n.ctl[LC_ERR], 1ull);
-    }
+    if (n.move_residents) t = ld_rounds<Cap>(n, br, s);
+    ld_end<Cap, false, true>(n, s, br, t);
 }
 
 thread_local int t_ld_sort = 0;   // kao_logdirs_test_sort: 0 = by size, 1 = dynamic LDS, 2 = global memory
@@ -898,6 +840,109 @@ void peak_of_rows(const int32_t *dir_start, int B, const uint64_t *per_broker, i
     }
 }
 
+// ---- one call on the host, from checked arguments to filled outputs ---------------------------------------------------------------------
+// open: the arena, the uploads, the buckets by broker (keyed by broker[r], or without broker[] by the broker of dir[r]), the lanes of
+// a broker's workgroup and the kernel arguments that every call has.  The caller then chooses its path, completes n and launches its
+// kernel; finish: the read-back and the outputs that every call has.  cap, broker and x say which optional buffers the arena holds:
+//   ctl u64[LC_N] | cnt i32[B] | broker: hcnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] |
+//   broker i32[R], else the broker of every dir i32[D] | per_broker u64[W * B] | key, size u64[R] | dir, dir0, list i32[R] | dst u8[R] |
+//   broker or x: sr u32[R] | cap u64[D] | x: xs u64[R] | xm u64[R + D] | xp u32[R]
+struct LdCall {
+    CallBufs m;
+    LdNetX n{};                 // k_ld_solve<Cap> and k_ld_place take the LdNet of it
+    const int32_t *dir_start = nullptr;
+    int B = 0, R = 0, W = 0, launches = 0, threads = 0;
+    u64 max_n[2] = {0, 0};      // the largest bucket, the most homeless replicas of one broker
+    u64 ctl[LC_N];              // after finish
+
+    int open(int32_t n_brokers, const int32_t *dir_start_, const uint64_t *base, const uint64_t *cap, int32_t n_replicas, const int32_t *broker,
+             const int32_t *dir, const uint64_t *size, uint64_t min_gain, int32_t max_rounds, int row_width, bool x) {
+        dir_start = dir_start_; B = n_brokers; R = n_replicas; W = row_width;
+        const int D = dir_start[B];
+        std::vector<int32_t> bod;   // broker_of_dir
+        if (!broker) {
+            bod.assign((size_t)std::max(D, 1), 0);
+            for (int b = 0; b < B; ++b)
+                for (int d = dir_start[b]; d < dir_start[b + 1]; ++d) bod[(size_t)d] = b;
+        }
+        Carve cv;
+        const size_t o_ctl = cv.take<u64>(LC_N), o_cnt = cv.take<int32_t>(B), o_hcnt = cv.take<int32_t>(broker ? B : 0), o_base = cv.take<u64>(D), zeroed = cv.end(),
+                     o_start = cv.take<int32_t>(B), o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_idx = cv.take<int32_t>(broker ? R : D),
+                     o_pb = cv.take<u64>(W * (size_t)B), o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R),
+                     o_list = cv.take<int32_t>(R), o_dst = cv.take<uint8_t>(R), o_sr = cv.take<uint32_t>(broker || x ? R : 0), o_cap = cv.take<u64>(cap ? D : 0),
+                     o_xs = cv.take<u64>(x ? R : 0), o_xm = cv.take<u64>(x ? (size_t)R + D : 0), o_xp = cv.take<uint32_t>(x ? R : 0);
+        int rc = m.open(cv.end());
+        if (rc) return rc;
+        hipStream_t st = m.stream;
+        int32_t *d_cnt = m.at<int32_t>(o_cnt), *d_hcnt = broker ? m.at<int32_t>(o_hcnt) : nullptr, *d_start = m.at<int32_t>(o_start), *d_fill = m.at<int32_t>(o_fill),
+                *d_ds = m.at<int32_t>(o_ds), *d_idx = m.at<int32_t>(o_idx), *d_dir = m.at<int32_t>(o_dir), *d_dir0 = m.at<int32_t>(o_dir0), *d_list = m.at<int32_t>(o_list);
+        u64 *d_ctl = m.at<u64>(o_ctl), *d_base = m.at<u64>(o_base), *d_size = m.at<u64>(o_size), *d_cap = cap ? m.at<u64>(o_cap) : nullptr;
+
+        HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
+        HIP_TRY(hipMemcpyAsync(d_ds, dir_start, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        if (D) {
+            if (!broker) HIP_TRY(hipMemcpyAsync(d_idx, bod.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            if (base) HIP_TRY(hipMemcpyAsync(d_base, base, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            if (cap) HIP_TRY(hipMemcpyAsync(d_cap, cap, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        }
+        if (R) {
+            if (broker) HIP_TRY(hipMemcpyAsync(d_idx, broker, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_dir0, dir, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_dir, d_dir0, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)R * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        }
+        const int32_t *key_of = broker ? d_idx : d_dir0, *map = broker ? nullptr : d_idx;   // the broker of r is map[key_of[r]], key_of[r] without a map
+        const unsigned rblocks = grid_for(R, kLdThreads);
+        if (R) {
+            k_ld_count<<<rblocks, kLdThreads, 0, st>>>(R, key_of, map, d_dir0, d_cnt, d_hcnt);
+            ++launches;
+        }
+        k_bucket_offsets<<<1, 1024, 0, st>>>(B, d_cnt, d_hcnt, d_start, d_fill, d_ctl + LC_MAXN);
+        ++launches;
+        if (R) {
+            k_ld_scatter<<<rblocks, kLdThreads, 0, st>>>(R, key_of, map, d_start, d_fill, d_list);
+            ++launches;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(max_n, d_ctl + LC_MAXN, sizeof max_n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        threads = max_n[0] <= (u64)kLdSmallBucket ? kLdSoloSmall : kLdSoloLarge;
+
+        n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
+        n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = m.at<u64>(o_pb); n.ctl = d_ctl;
+        n.move_residents = 1; n.hcnt = d_hcnt; n.sr = broker || x ? m.at<uint32_t>(o_sr) : nullptr; n.cap = d_cap;
+        if (x) { n.xs = m.at<u64>(o_xs); n.xm = m.at<u64>(o_xm); n.xp = m.at<uint32_t>(o_xp); }
+        return KAO_OK;
+    }
+
+    // after the caller's launch; peak_before and peak_after are fractions {L, cap} in a capacity call
+    int finish(const std::string &fn, int32_t *dir, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+               uint64_t *per_broker, int32_t *status) {
+        hipStream_t st = m.stream;
+        HIP_TRY(hipGetLastError());
+        ++launches;
+        HIP_TRY(hipMemcpyAsync(ctl, n.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(per_broker, n.per_broker, (size_t)B * W * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
+        if (!dry_run && (ctl[LC_NPLACED] || ctl[LC_NMOVED])) {
+            HIP_TRY(hipMemcpyAsync(dir, n.dir, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        *n_moved = (int32_t)ctl[LC_NMOVED];
+        *bytes_moved = ctl[LC_BYTES];
+        if (n.cap) {
+            peak_of_rows(dir_start, B, per_broker, W, 0, peak_before);
+            peak_of_rows(dir_start, B, per_broker, W, 2, peak_after);
+        } else {
+            *peak_before = ctl[LC_PEAK0];
+            *peak_after = ctl[LC_PEAK1];
+        }
+        *status = ctl[LC_PROVEN] == (u64)B ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+        return KAO_OK;
+    }
+};
+
 // the entry points: Cap (cap != NULL) is the descent by utilisation: the other instantiation of the kernels, rows of 10 / 12 columns
 // with fractions, the call's peaks reduced from the rows
 // X (kao_balance_logdirs_exchange): k_ld_solve<false, true>, rows of 8 columns, stats[12]
@@ -905,70 +950,17 @@ template <bool Cap, bool X = false>
 int balance_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir_start, const uint64_t *base, const uint64_t *cap, int32_t n_replicas,
                     int32_t *dir, const uint64_t *size, uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
                     uint64_t *peak_before, uint64_t *peak_after, uint64_t *per_broker, int32_t *status, int64_t *stats) {
-    constexpr int W = X ? 8 : Cap ? 10 : 6;
     const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, per_broker, status, Cap ? (const void *)cap : (const void *)status};
     int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 7);
     if (rc) return rc;
     if (Cap && (rc = validate_capacity(fn, dir_start[n_brokers], cap))) return rc;
     if ((rc = require_init())) return rc;
-    const int B = n_brokers, R = n_replicas, D = dir_start[B];
-    std::vector<int32_t> bod((size_t)std::max(D, 1), 0);   // broker_of_dir
-    for (int b = 0; b < B; ++b)
-        for (int d = dir_start[b]; d < dir_start[b + 1]; ++d) bod[(size_t)d] = b;
-
-    // one arena: ctl u64[LC_N] | cnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] | bod i32[D] |
-    //            per_broker u64[6B] ([10B] with Cap) | key, size u64[R] | dir, dir0, list i32[R] | dst u8[R] | Cap: cap u64[D]
-    Carve cv;
-    const size_t o_ctl = cv.take<u64>(LC_N), o_cnt = cv.take<int32_t>(B), o_base = cv.take<u64>(D), zeroed = cv.end(), o_start = cv.take<int32_t>(B),
-                 o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_bod = cv.take<int32_t>(D), o_pb = cv.take<u64>(W * (size_t)B),
-                 o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R), o_list = cv.take<int32_t>(R),
-                 o_dst = cv.take<uint8_t>(R), o_cap = cv.take<u64>(Cap ? D : 0);
-    // X: xs u64[R] | xm u64[R + D] | sr, xp u32[R]
-    const size_t o_xs = cv.take<u64>(X ? R : 0), o_xm = cv.take<u64>(X ? (size_t)R + D : 0), o_sr = cv.take<uint32_t>(X ? R : 0), o_xp = cv.take<uint32_t>(X ? R : 0);
-    CallBufs m;
-    if ((rc = m.open(cv.end()))) return rc;
-    hipStream_t st = m.stream;
-    int32_t *d_cnt = m.at<int32_t>(o_cnt), *d_start = m.at<int32_t>(o_start), *d_fill = m.at<int32_t>(o_fill), *d_ds = m.at<int32_t>(o_ds),
-            *d_bod = m.at<int32_t>(o_bod), *d_dir = m.at<int32_t>(o_dir), *d_dir0 = m.at<int32_t>(o_dir0), *d_list = m.at<int32_t>(o_list);
-    u64 *d_ctl = m.at<u64>(o_ctl), *d_base = m.at<u64>(o_base), *d_size = m.at<u64>(o_size), *d_pb = m.at<u64>(o_pb);
-
-    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
-    HIP_TRY(hipMemcpyAsync(d_ds, dir_start, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (D) {
-        HIP_TRY(hipMemcpyAsync(d_bod, bod.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        if (base) HIP_TRY(hipMemcpyAsync(d_base, base, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        if (Cap) HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), cap, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    }
-    if (R) {
-        HIP_TRY(hipMemcpyAsync(d_dir0, dir, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_dir, d_dir0, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)R * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    }
-    int launches = 0;
-    const unsigned rblocks = grid_for(R, kLdThreads);
-    if (R) {
-        k_ld_count<<<rblocks, kLdThreads, 0, st>>>(R, d_dir0, d_bod, nullptr, d_cnt, nullptr);
-        ++launches;
-    }
-    k_ld_offsets<<<1, 1024, 0, st>>>(B, d_cnt, nullptr, d_start, d_fill, d_ctl + LC_MAXN);
-    ++launches;
-    if (R) {
-        k_ld_scatter<<<rblocks, kLdThreads, 0, st>>>(R, d_dir0, d_bod, d_start, d_fill, d_list);
-        ++launches;
-    }
-    HIP_TRY(hipGetLastError());
-    u64 max_n = 0;
-    HIP_TRY(hipMemcpyAsync(&max_n, d_ctl + LC_MAXN, sizeof max_n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int threads = max_n <= (u64)kLdSmallBucket ? kLdSoloSmall : kLdSoloLarge;
-
-    std::conditional_t<X, LdNetX, LdNet> n;
-    n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
-    n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
-    n.move_residents = 1; n.sort_lds = 0; n.sort_cap = 0; n.hcnt = nullptr; n.sr = nullptr; n.cap = Cap ? m.at<u64>(o_cap) : nullptr;
+    LdCall c;
+    if ((rc = c.open(n_brokers, dir_start, base, cap, n_replicas, nullptr, dir, size, min_gain, max_rounds, kLdRow<Cap, X, false>.w, X))) return rc;
     if constexpr (X) {   // PI and the masks in LDS when those of the largest bucket, with the most dirs of a broker, fit
+        const u64 max_n = c.max_n[0];
         int max_nd = 0;
-        for (int b = 0; b < B; ++b) max_nd = std::max(max_nd, dir_start[b + 1] - dir_start[b]);
+        for (int b = 0; b < n_brokers; ++b) max_nd = std::max(max_nd, dir_start[b + 1] - dir_start[b]);
         const size_t mcap = (size_t)max_nd * (size_t)(max_n / 64 + 1);
         const size_t bytes = (size_t)max_n * (sizeof(u64) + sizeof(uint32_t)) + mcap * sizeof(u64);
         const bool fits = max_n <= (u64)kLdSortLds && bytes <= (size_t)kLdXchgLds;   // the sort's limit of k_ld_place, and the masks beside the entries
@@ -976,36 +968,16 @@ int balance_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir
             return fail(KAO_ERR_UNSUPPORTED, fn + "a broker's " + std::to_string(max_n) + " replicas on " + std::to_string(max_nd) + " dirs need " +
                                                  std::to_string(bytes) + " bytes of LDS: more than the " + std::to_string(kLdXchgLds) + " of the LDS path");
         const bool lds = t_ld_xchg == 2 ? false : fits;
-        n.x_lds = lds ? 1 : 0; n.x_cap = lds ? (int)max_n : 0; n.x_mcap = lds ? (int)mcap : 0;
-        n.xs = m.at<u64>(o_xs); n.xm = m.at<u64>(o_xm); n.sr = m.at<uint32_t>(o_sr); n.xp = m.at<uint32_t>(o_xp);
-        k_ld_solve<false, true><<<(unsigned)B, threads, lds ? bytes : 0, st>>>(n);
+        c.n.x_lds = lds ? 1 : 0; c.n.x_cap = lds ? (int)max_n : 0; c.n.x_mcap = lds ? (int)mcap : 0;
+        k_ld_solve<false, true><<<(unsigned)n_brokers, c.threads, lds ? bytes : 0, c.m.stream>>>(c.n);
     } else {
-        k_ld_solve<Cap><<<(unsigned)B, threads, 0, st>>>(n);
+        k_ld_solve<Cap><<<(unsigned)n_brokers, c.threads, 0, c.m.stream>>>(c.n);
     }
-    HIP_TRY(hipGetLastError());
-    ++launches;
-    u64 ctl[LC_N];
-    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * W * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
-    if (!dry_run && ctl[LC_NMOVED]) {
-        HIP_TRY(hipMemcpyAsync(dir, d_dir, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    *n_moved = (int32_t)ctl[LC_NMOVED];
-    *bytes_moved = ctl[LC_BYTES];
-    if (Cap) {
-        peak_of_rows(dir_start, B, per_broker, W, 0, peak_before);
-        peak_of_rows(dir_start, B, per_broker, W, 2, peak_after);
-    } else {
-        *peak_before = ctl[LC_PEAK0];
-        *peak_after = ctl[LC_PEAK1];
-    }
-    *status = ctl[LC_PROVEN] == (u64)B ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    if ((rc = c.finish(fn, dir, dry_run, n_moved, bytes_moved, peak_before, peak_after, per_broker, status))) return rc;
+    const u64 *ctl = c.ctl;
     if (stats) {
         stats[0] = (int64_t)ctl[LC_BROKERS]; stats[1] = (int64_t)ctl[LC_ROUNDS]; stats[2] = (int64_t)ctl[LC_MOVES]; stats[3] = (int64_t)ctl[LC_PROPS];
-        stats[4] = launches; stats[5] = (int64_t)ctl[LC_MORE]; stats[6] = (int64_t)ctl[LC_PROVEN]; stats[7] = (int64_t)ctl[LC_MAXROUNDS];
+        stats[4] = c.launches; stats[5] = (int64_t)ctl[LC_MORE]; stats[6] = (int64_t)ctl[LC_PROVEN]; stats[7] = (int64_t)ctl[LC_MAXROUNDS];
         if (X) { stats[8] = (int64_t)ctl[LC_XROUNDS]; stats[9] = (int64_t)ctl[LC_XCH]; stats[10] = (int64_t)ctl[LC_XPROPS]; stats[11] = (int64_t)ctl[LC_XLOWER]; }
     }
     return KAO_OK;
@@ -1016,7 +988,6 @@ int place_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir_s
                   const int32_t *broker, int32_t *dir, const uint64_t *size, int32_t move_residents, uint64_t min_gain, int32_t max_rounds, int32_t dry_run,
                   int32_t *n_placed, uint64_t *bytes_placed, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
                   uint64_t *per_broker, int32_t *status, int64_t *stats) {
-    constexpr int W = Cap ? 12 : 8;
     const void *outs[] = {broker, n_placed, bytes_placed, n_moved, bytes_moved, peak_before, peak_after, per_broker, status, Cap ? (const void *)cap : (const void *)status};
     int rc = validate_logdirs(fn, n_brokers, dir_start, base, n_replicas, dir, size, outs, 10, -1);
     if (rc) return rc;
@@ -1031,88 +1002,24 @@ int place_logdirs(const std::string &fn, int32_t n_brokers, const int32_t *dir_s
     }
     if (Cap && (rc = validate_capacity(fn, D, cap))) return rc;
     if ((rc = require_init())) return rc;
-
-    // one arena: ctl u64[LC_N] | cnt, hcnt i32[B] | base u64[D] (zeroed up to here) | start, fill i32[B] | dir_start i32[B + 1] |
-    //            per_broker u64[8B] ([12B] with Cap) | key, size u64[R] | broker, dir, dir0, list i32[R] | sr u32[R] | dst u8[R] | Cap: cap u64[D]
-    Carve cv;
-    const size_t o_ctl = cv.take<u64>(LC_N), o_cnt = cv.take<int32_t>(B), o_hcnt = cv.take<int32_t>(B), o_base = cv.take<u64>(D), zeroed = cv.end(),
-                 o_start = cv.take<int32_t>(B), o_fill = cv.take<int32_t>(B), o_ds = cv.take<int32_t>((size_t)B + 1), o_pb = cv.take<u64>(W * (size_t)B),
-                 o_key = cv.take<u64>(R), o_size = cv.take<u64>(R), o_broker = cv.take<int32_t>(R), o_dir = cv.take<int32_t>(R), o_dir0 = cv.take<int32_t>(R),
-                 o_list = cv.take<int32_t>(R), o_sr = cv.take<uint32_t>(R), o_dst = cv.take<uint8_t>(R), o_cap = cv.take<u64>(Cap ? D : 0);
-    CallBufs m;
-    if ((rc = m.open(cv.end()))) return rc;
-    hipStream_t st = m.stream;
-    int32_t *d_cnt = m.at<int32_t>(o_cnt), *d_hcnt = m.at<int32_t>(o_hcnt), *d_start = m.at<int32_t>(o_start), *d_fill = m.at<int32_t>(o_fill),
-            *d_ds = m.at<int32_t>(o_ds), *d_broker = m.at<int32_t>(o_broker), *d_dir = m.at<int32_t>(o_dir), *d_dir0 = m.at<int32_t>(o_dir0),
-            *d_list = m.at<int32_t>(o_list);
-    u64 *d_ctl = m.at<u64>(o_ctl), *d_base = m.at<u64>(o_base), *d_size = m.at<u64>(o_size), *d_pb = m.at<u64>(o_pb);
-
-    HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
-    HIP_TRY(hipMemcpyAsync(d_ds, dir_start, ((size_t)B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (D && base) HIP_TRY(hipMemcpyAsync(d_base, base, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (Cap && D) HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), cap, (size_t)D * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (R) {
-        HIP_TRY(hipMemcpyAsync(d_broker, broker, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_dir0, dir, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_dir, d_dir0, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)R * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    }
-    int launches = 0;
-    const unsigned rblocks = grid_for(R, kLdThreads);
-    if (R) {
-        k_ld_count<<<rblocks, kLdThreads, 0, st>>>(R, d_broker, nullptr, d_dir0, d_cnt, d_hcnt);
-        ++launches;
-    }
-    k_ld_offsets<<<1, 1024, 0, st>>>(B, d_cnt, d_hcnt, d_start, d_fill, d_ctl + LC_MAXN);
-    ++launches;
-    if (R) {
-        k_ld_scatter<<<rblocks, kLdThreads, 0, st>>>(R, d_broker, nullptr, d_start, d_fill, d_list);
-        ++launches;
-    }
-    HIP_TRY(hipGetLastError());
-    u64 max_n[2] = {0, 0};   // the largest bucket, the most homeless replicas of one broker
-    HIP_TRY(hipMemcpyAsync(max_n, d_ctl + LC_MAXN, sizeof max_n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int threads = max_n[0] <= (u64)kLdSmallBucket ? kLdSoloSmall : kLdSoloLarge;
-    const bool fits = max_n[1] <= (u64)kLdSortLds;
+    LdCall c;
+    if ((rc = c.open(B, dir_start, base, cap, R, broker, dir, size, min_gain, max_rounds, kLdRow<Cap, false, true>.w, false))) return rc;
+    const u64 max_h = c.max_n[1];
+    const bool fits = max_h <= (u64)kLdSortLds;
     if (t_ld_sort == 1 && !fits)
-        return fail(KAO_ERR_UNSUPPORTED, fn + "a broker has " + std::to_string(max_n[1]) + " homeless replicas: more than the " + std::to_string(kLdSortLds) +
+        return fail(KAO_ERR_UNSUPPORTED, fn + "a broker has " + std::to_string(max_h) + " homeless replicas: more than the " + std::to_string(kLdSortLds) +
                                              " the LDS sort holds");
     const bool lds = t_ld_sort == 2 ? false : fits;
-
-    LdNet n;
-    n.max_rounds = max_rounds; n.min_gain = min_gain; n.dir_start = d_ds; n.base = d_base; n.size = d_size; n.dir = d_dir; n.dir0 = d_dir0;
-    n.cnt = d_cnt; n.start = d_start; n.list = d_list; n.key = m.at<u64>(o_key); n.dst = m.at<uint8_t>(o_dst); n.per_broker = d_pb; n.ctl = d_ctl;
-    n.move_residents = move_residents ? 1 : 0; n.sort_lds = lds ? 1 : 0; n.sort_cap = lds ? (int)max_n[1] : 0; n.hcnt = d_hcnt; n.sr = m.at<uint32_t>(o_sr);
-    n.cap = Cap ? m.at<u64>(o_cap) : nullptr;
-    k_ld_place<Cap><<<(unsigned)B, threads, (size_t)n.sort_cap * (sizeof(u64) + sizeof(uint32_t)), st>>>(n);
-    HIP_TRY(hipGetLastError());
-    ++launches;
-    u64 ctl[LC_N];
-    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(per_broker, d_pb, (size_t)B * W * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ctl[LC_ERR]) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
-    if (!dry_run && (ctl[LC_NPLACED] || ctl[LC_NMOVED])) {
-        HIP_TRY(hipMemcpyAsync(dir, d_dir, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    c.n.move_residents = move_residents ? 1 : 0; c.n.sort_lds = lds ? 1 : 0; c.n.sort_cap = lds ? (int)max_h : 0;
+    k_ld_place<Cap><<<(unsigned)B, c.threads, (size_t)c.n.sort_cap * (sizeof(u64) + sizeof(uint32_t)), c.m.stream>>>(c.n);
+    if ((rc = c.finish(fn, dir, dry_run, n_moved, bytes_moved, peak_before, peak_after, per_broker, status))) return rc;
+    const u64 *ctl = c.ctl;
     *n_placed = (int32_t)ctl[LC_NPLACED];
     *bytes_placed = ctl[LC_BPLACED];
-    *n_moved = (int32_t)ctl[LC_NMOVED];
-    *bytes_moved = ctl[LC_BYTES];
-    if (Cap) {
-        peak_of_rows(dir_start, B, per_broker, W, 0, peak_before);
-        peak_of_rows(dir_start, B, per_broker, W, 2, peak_after);
-    } else {
-        *peak_before = ctl[LC_PEAK0];
-        *peak_after = ctl[LC_PEAK1];
-    }
-    *status = ctl[LC_PROVEN] == (u64)B ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
     if (stats) {
         stats[0] = (int64_t)ctl[LC_PLACERS]; stats[1] = (int64_t)ctl[LC_BROKERS]; stats[2] = (int64_t)ctl[LC_ROUNDS]; stats[3] = (int64_t)ctl[LC_MOVES];
-        stats[4] = (int64_t)ctl[LC_PROPS]; stats[5] = launches; stats[6] = (int64_t)ctl[LC_MORE]; stats[7] = (int64_t)ctl[LC_PROVEN];
-        stats[8] = (int64_t)ctl[LC_MAXROUNDS]; stats[9] = (int64_t)max_n[1];
+        stats[4] = (int64_t)ctl[LC_PROPS]; stats[5] = c.launches; stats[6] = (int64_t)ctl[LC_MORE]; stats[7] = (int64_t)ctl[LC_PROVEN];
+        stats[8] = (int64_t)ctl[LC_MAXROUNDS]; stats[9] = (int64_t)max_h;
     }
     return KAO_OK;
 }

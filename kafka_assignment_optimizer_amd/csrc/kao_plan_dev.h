@@ -1,6 +1,8 @@
 // kao_plan_dev.h -- device code the one-shot planners share: the 64-bit keys of successive shortest paths (kao_leaders.hip,
-// kao_leaders_cluster.hip; DESIGN.md sections 4h, 4j), the wavefront count, the leader swap, and the pieces of the weighted descent
-// (kao_wleaders.hip, kao_wfailover.hip, kao_disk.hip, kao_logdirs.hip; sections 4k, 4l, 4m, 4o).  Everything sits in an unnamed namespace and is inlined into its callers.
+// kao_leaders_cluster.hip; DESIGN.md sections 4h, 4j), the wavefront count, the leader swap, the offsets of buckets
+// (kao_failover_dev.h, kao_logdirs.hip; sections 4i, 4o) and the pieces of the weighted descent (kao_wleaders.hip, kao_wfailover.hip,
+// kao_disk.hip, kao_logdirs.hip; sections 4k, 4l, 4m, 4o).  Everything sits in an unnamed namespace; the device functions are inlined
+// into their callers, and the one kernel is a template that only the files that launch it instantiate.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +45,35 @@ __device__ __forceinline__ void swap_leader(uint16_t *row, int l) {
     const uint16_t a = row[0], b = row[l];
     row[0] = b;
     row[l] = a;
+}
+
+// ---- the offsets of n buckets (the scenarios of kao_failover_dev.h, the brokers of kao_logdirs.hip) from their sizes: start[i] = sum of
+// cnt[0..i), fill[i] = 0; max_n[0] = the largest cnt and, with a second count array, max_n[1] = the largest cnt2; max_n points into the
+// caller's control block, whose words are Word.  One workgroup of 1,024 lanes.
+template <class Word>
+__global__ __launch_bounds__(1024) void k_bucket_offsets(int n, const int32_t *__restrict__ cnt, const int32_t *__restrict__ cnt2, int32_t *__restrict__ start,
+                                                          int32_t *__restrict__ fill, Word *__restrict__ max_n) {
+    __shared__ int32_t part[1024];
+    __shared__ int32_t mx, mx2;
+    const int tid = threadIdx.x, NT = blockDim.x, per = (n + NT - 1) / NT, lo = min(tid * per, n), hi = min(lo + per, n);
+    if (tid == 0) { mx = 0; mx2 = 0; }
+    __syncthreads();
+    int s = 0, m = 0, m2 = 0;
+    for (int i = lo; i < hi; ++i) { s += cnt[i]; m = max(m, cnt[i]); }
+    for (int i = lo; cnt2 && i < hi; ++i) m2 = max(m2, cnt2[i]);
+    part[tid] = s;
+    if (m) atomicMax(&mx, m);
+    if (m2) atomicMax(&mx2, m2);
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int i = 0; i < NT; ++i) { const int v = part[i]; part[i] = acc; acc += v; }
+        max_n[0] = (Word)mx;
+        if (cnt2) max_n[1] = (Word)mx2;
+    }
+    __syncthreads();
+    s = part[tid];
+    for (int i = lo; i < hi; ++i) { start[i] = s; fill[i] = 0; s += cnt[i]; }
 }
 
 // ---- the weighted descent ---------------------------------------------------------------------------------------------------------

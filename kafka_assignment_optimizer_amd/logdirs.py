@@ -126,6 +126,10 @@ def parse_log_dirs(doc_or_text) -> Dict[int, Dict[str, LogDir]]:
     return out
 
 
+def _table_of(log_dirs) -> Dict[int, Dict[str, LogDir]]:
+    return log_dirs if isinstance(log_dirs, dict) and "brokers" not in log_dirs else parse_log_dirs(log_dirs)   # a parse_log_dirs table as it is
+
+
 def _capacity_buffer(capacity, n_dirs: int) -> np.ndarray:
     """cap[] of a capacity call as a uint64 buffer (one spare word for a call without dirs): one integer >= 1 per dir, the sum below
     2^62; a ValueError otherwise."""
@@ -149,20 +153,32 @@ def _capacity_buffer(capacity, n_dirs: int) -> np.ndarray:
     return np.array([int(v) for v in values] or [1], dtype=np.uint64)
 
 
-def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity=None,
-                           exchange: bool = False) -> LogDirsResult:
-    """kao_balance_logdirs on arrays: broker b owns the dirs dir_start[b] .. dir_start[b+1]-1, replica r sits in dir[r] with size[r]
-    bytes, dir d carries base[d] bytes that never move.  capacity[d] >= 1 (the bytes of disk behind dir d) selects
-    kao_balance_logdirs_capacity: the descent lowers L(d) / capacity[d], the result carries fractions.  exchange=True selects
-    kao_balance_logdirs_exchange (bytes only): exchange rounds follow when no move is left; per_broker is [B, 8], stats int64[12]."""
-    if exchange and capacity is not None:
-        raise ValueError("exchange moves are by bytes only: exchange=True cannot be combined with capacity")
+@dataclass
+class _Arrays:
+    """The arrays of a call, checked: dir_start and the result's copy of dir, and the buffers the library reads (one spare word where an
+    array is empty; base and broker None when not given)."""
+    ds: np.ndarray
+    d: np.ndarray
+    dbuf: np.ndarray
+    sbuf: np.ndarray
+    bbuf: Optional[np.ndarray]
+    rbuf: Optional[np.ndarray]
+
+
+def _checked_arrays(dir_start, dir, size, base, min_gain, broker=None) -> _Arrays:
     ds = np.ascontiguousarray(np.asarray(dir_start).reshape(-1), dtype=np.int32)
     if ds.shape[0] < 2:
         raise ValueError("dir_start must hold n_brokers + 1 values, n_brokers >= 1")
-    B = ds.shape[0] - 1
     d = np.array(np.asarray(dir).reshape(-1), dtype=np.int32, order="C")
     R = d.shape[0]
+    rbuf = None
+    if broker is not None:
+        br = np.asarray(broker).reshape(-1)
+        if br.shape != (R,):
+            raise ValueError(f"broker must hold one value per replica ({R}), got {br.shape[0]}")
+        if R and br.dtype.kind not in "ui":
+            raise ValueError("brokers must be integers")
+        rbuf = np.ascontiguousarray(br, dtype=np.int32) if R else np.zeros(1, dtype=np.int32)
     sz = np.asarray(size).reshape(-1)
     if sz.shape != (R,):
         raise ValueError(f"size must hold one value per replica ({R}), got {sz.shape[0]}")
@@ -170,8 +186,6 @@ def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, m
         raise ValueError("sizes must be integers >= 0")
     if isinstance(min_gain, bool) or not 0 <= int(min_gain) < 1 << 64:
         raise ValueError("min_gain must be 0..2^64-1")
-    sbuf = np.ascontiguousarray(sz, dtype=np.uint64) if R else np.zeros(1, dtype=np.uint64)
-    dbuf = d if R else np.zeros(1, dtype=np.int32)
     bbuf = None
     if base is not None:
         bs = np.asarray(base).reshape(-1)
@@ -180,37 +194,44 @@ def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, m
         if bs.size and (bs.dtype.kind not in "ui" or (bs.dtype.kind == "i" and (bs < 0).any())):
             raise ValueError("bases must be integers >= 0")
         bbuf = np.ascontiguousarray(bs, dtype=np.uint64) if bs.size else np.zeros(1, dtype=np.uint64)
-    stats = np.zeros(8, dtype=np.int64)
-    n, status = C.c_int32(0), C.c_int32(0)
+    return _Arrays(ds=ds, d=d, dbuf=d if R else np.zeros(1, dtype=np.int32), sbuf=np.ascontiguousarray(sz, dtype=np.uint64) if R else np.zeros(1, dtype=np.uint64),
+                   bbuf=bbuf, rbuf=rbuf)
+
+
+def _call(entry: str, a: _Arrays, capacity, options: Sequence[int], n_outs: int, row: int, n_stats: int):
+    """entry(n_brokers, dir_start, base, [cap,] n_replicas, [broker,] dir, size, *options, n_outs pairs {int32 *count, uint64 *bytes},
+    peak_before, peak_after, per_broker[B, row], status, stats[n_stats]), checked.  Returns the counts and bytes in that order and the
+    fields that every result class has.  A call by bytes writes the first word of a peak alone."""
     u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
-    if capacity is not None:
-        cbuf = _capacity_buffer(capacity, int(ds[-1]))
-        per = np.zeros((B, 10), dtype=np.uint64)
-        moved, peaks = C.c_uint64(0), np.zeros((2, 2), dtype=np.uint64)
-        _check(_ffi.load().kao_balance_logdirs_capacity(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), cbuf.ctypes.data_as(u64p),
-                                                        R, dbuf.ctypes.data_as(i32p), sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds),
-                                                        int(bool(dry_run)), C.byref(n), C.byref(moved), peaks[0].ctypes.data_as(u64p),
-                                                        peaks[1].ctypes.data_as(u64p), per.ctypes.data_as(u64p), C.byref(status),
-                                                        stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_logdirs_capacity")
-        return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(peaks[0, 0]), peak_after=int(peaks[1, 0]),
-                             per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats, peak_before_frac=(int(peaks[0, 0]), int(peaks[0, 1])),
-                             peak_after_frac=(int(peaks[1, 0]), int(peaks[1, 1])))
-    moved, before, after = (C.c_uint64(0) for _ in range(3))
-    if exchange:
-        per, stats = np.zeros((B, 8), dtype=np.uint64), np.zeros(12, dtype=np.int64)
-        _check(_ffi.load().kao_balance_logdirs_exchange(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, dbuf.ctypes.data_as(i32p),
-                                                        sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
-                                                        C.byref(before), C.byref(after), per.ctypes.data_as(u64p), C.byref(status),
-                                                        stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_logdirs_exchange")
-        return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
-                             per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
-    per = np.zeros((B, 6), dtype=np.uint64)
-    _check(_ffi.load().kao_balance_logdirs(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, dbuf.ctypes.data_as(i32p),
-                                           sbuf.ctypes.data_as(u64p), int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved),
-                                           C.byref(before), C.byref(after), per.ctypes.data_as(u64p), C.byref(status),
-                                           stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_logdirs")
-    return LogDirsResult(dir=d, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
-                         per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
+    B, R = a.ds.shape[0] - 1, a.d.shape[0]
+    cbuf = None if capacity is None else _capacity_buffer(capacity, int(a.ds[-1]))
+    per, stats, peaks, status = np.zeros((B, row), dtype=np.uint64), np.zeros(n_stats, dtype=np.int64), np.zeros((2, 2), dtype=np.uint64), C.c_int32(0)
+    outs = [x for _ in range(n_outs) for x in (C.c_int32(0), C.c_uint64(0))]
+    args = [B, a.ds.ctypes.data_as(i32p), None if a.bbuf is None else a.bbuf.ctypes.data_as(u64p)]
+    args += [] if cbuf is None else [cbuf.ctypes.data_as(u64p)]
+    args += [R] + ([] if a.rbuf is None else [a.rbuf.ctypes.data_as(i32p)]) + [a.dbuf.ctypes.data_as(i32p), a.sbuf.ctypes.data_as(u64p)]
+    args += [int(o) for o in options] + [C.byref(x) for x in outs]
+    args += [peaks[0].ctypes.data_as(u64p), peaks[1].ctypes.data_as(u64p), per.ctypes.data_as(u64p), C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))]
+    _check(getattr(_ffi.load(), entry)(*args), entry)
+    rest = dict(dir=a.d, peak_before=int(peaks[0, 0]), peak_after=int(peaks[1, 0]), per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
+    if cbuf is not None:
+        rest.update(peak_before_frac=(int(peaks[0, 0]), int(peaks[0, 1])), peak_after_frac=(int(peaks[1, 0]), int(peaks[1, 1])))
+    return [int(x.value) for x in outs], rest
+
+
+def balance_logdirs_arrays(dir_start, dir, size, base=None, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, capacity=None,
+                           exchange: bool = False) -> LogDirsResult:
+    """kao_balance_logdirs on arrays: broker b owns the dirs dir_start[b] .. dir_start[b+1]-1, replica r sits in dir[r] with size[r]
+    bytes, dir d carries base[d] bytes that never move.  capacity[d] >= 1 (the bytes of disk behind dir d) selects
+    kao_balance_logdirs_capacity: the descent lowers L(d) / capacity[d], the result carries fractions.  exchange=True selects
+    kao_balance_logdirs_exchange (bytes only): exchange rounds follow when no move is left; per_broker is [B, 8], stats int64[12]."""
+    if exchange and capacity is not None:
+        raise ValueError("exchange moves are by bytes only: exchange=True cannot be combined with capacity")
+    a = _checked_arrays(dir_start, dir, size, base, min_gain)
+    entry, row, n_stats = ("kao_balance_logdirs_capacity", 10, 8) if capacity is not None else ("kao_balance_logdirs_exchange", 8, 12) if exchange \
+        else ("kao_balance_logdirs", 6, 8)
+    (n, moved), rest = _call(entry, a, capacity, (min_gain, max_rounds, bool(dry_run)), 1, row, n_stats)
+    return LogDirsResult(n_moved=n, bytes_moved=moved, **rest)
 
 
 PLACE_STAT_KEYS = ("brokers_placed", "brokers_moved", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven", "max_rounds_of_a_broker",
@@ -241,58 +262,10 @@ def place_logdirs_arrays(dir_start, broker, dir, size, base=None, move_residents
     lightest dir of its broker, the largest replica first; with move_residents the rounds of kao_balance_logdirs follow.
     capacity[d] >= 1 selects kao_place_logdirs_capacity: a homeless replica goes to the dir that is the least full with it, the
     rounds lower L(d) / capacity[d], the result carries fractions."""
-    ds = np.ascontiguousarray(np.asarray(dir_start).reshape(-1), dtype=np.int32)
-    if ds.shape[0] < 2:
-        raise ValueError("dir_start must hold n_brokers + 1 values, n_brokers >= 1")
-    B = ds.shape[0] - 1
-    d = np.array(np.asarray(dir).reshape(-1), dtype=np.int32, order="C")
-    R = d.shape[0]
-    br = np.asarray(broker).reshape(-1)
-    if br.shape != (R,):
-        raise ValueError(f"broker must hold one value per replica ({R}), got {br.shape[0]}")
-    if R and br.dtype.kind not in "ui":
-        raise ValueError("brokers must be integers")
-    sz = np.asarray(size).reshape(-1)
-    if sz.shape != (R,):
-        raise ValueError(f"size must hold one value per replica ({R}), got {sz.shape[0]}")
-    if R and (sz.dtype.kind not in "ui" or (sz.dtype.kind == "i" and (sz < 0).any())):
-        raise ValueError("sizes must be integers >= 0")
-    if isinstance(min_gain, bool) or not 0 <= int(min_gain) < 1 << 64:
-        raise ValueError("min_gain must be 0..2^64-1")
-    sbuf = np.ascontiguousarray(sz, dtype=np.uint64) if R else np.zeros(1, dtype=np.uint64)
-    dbuf = d if R else np.zeros(1, dtype=np.int32)
-    rbuf = np.ascontiguousarray(br, dtype=np.int32) if R else np.zeros(1, dtype=np.int32)
-    bbuf = None
-    if base is not None:
-        bs = np.asarray(base).reshape(-1)
-        if bs.shape != (max(int(ds[-1]), 0),):
-            raise ValueError(f"base must hold one value per dir ({int(ds[-1])}), got {bs.shape[0]}")
-        if bs.size and (bs.dtype.kind not in "ui" or (bs.dtype.kind == "i" and (bs < 0).any())):
-            raise ValueError("bases must be integers >= 0")
-        bbuf = np.ascontiguousarray(bs, dtype=np.uint64) if bs.size else np.zeros(1, dtype=np.uint64)
-    stats = np.zeros(10, dtype=np.int64)
-    placed, n, status = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    pbytes, moved, before, after = (C.c_uint64(0) for _ in range(4))
-    u64p, i32p = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
-    if capacity is not None:
-        cbuf = _capacity_buffer(capacity, int(ds[-1]))
-        per = np.zeros((B, 12), dtype=np.uint64)
-        peaks = np.zeros((2, 2), dtype=np.uint64)
-        _check(_ffi.load().kao_place_logdirs_capacity(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), cbuf.ctypes.data_as(u64p), R,
-                                                      rbuf.ctypes.data_as(i32p), dbuf.ctypes.data_as(i32p), sbuf.ctypes.data_as(u64p), int(bool(move_residents)),
-                                                      int(min_gain), int(max_rounds), int(bool(dry_run)), C.byref(placed), C.byref(pbytes), C.byref(n),
-                                                      C.byref(moved), peaks[0].ctypes.data_as(u64p), peaks[1].ctypes.data_as(u64p), per.ctypes.data_as(u64p),
-                                                      C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_place_logdirs_capacity")
-        return PlaceLogDirsResult(dir=d, n_placed=int(placed.value), bytes_placed=int(pbytes.value), n_moved=int(n.value), bytes_moved=int(moved.value),
-                                  peak_before=int(peaks[0, 0]), peak_after=int(peaks[1, 0]), per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats,
-                                  peak_before_frac=(int(peaks[0, 0]), int(peaks[0, 1])), peak_after_frac=(int(peaks[1, 0]), int(peaks[1, 1])))
-    per = np.zeros((B, 8), dtype=np.uint64)
-    _check(_ffi.load().kao_place_logdirs(B, ds.ctypes.data_as(i32p), None if bbuf is None else bbuf.ctypes.data_as(u64p), R, rbuf.ctypes.data_as(i32p),
-                                         dbuf.ctypes.data_as(i32p), sbuf.ctypes.data_as(u64p), int(bool(move_residents)), int(min_gain), int(max_rounds),
-                                         int(bool(dry_run)), C.byref(placed), C.byref(pbytes), C.byref(n), C.byref(moved), C.byref(before), C.byref(after),
-                                         per.ctypes.data_as(u64p), C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_place_logdirs")
-    return PlaceLogDirsResult(dir=d, n_placed=int(placed.value), bytes_placed=int(pbytes.value), n_moved=int(n.value), bytes_moved=int(moved.value),
-                              peak_before=int(before.value), peak_after=int(after.value), per_broker=per, status=STATUS_NAMES[int(status.value)], stats=stats)
+    a = _checked_arrays(dir_start, dir, size, base, min_gain, broker)
+    entry, row = ("kao_place_logdirs_capacity", 12) if capacity is not None else ("kao_place_logdirs", 8)
+    (placed, pbytes, n, moved), rest = _call(entry, a, capacity, (bool(move_residents), min_gain, max_rounds, bool(dry_run)), 2, row, 10)
+    return PlaceLogDirsResult(n_placed=placed, bytes_placed=pbytes, n_moved=n, bytes_moved=moved, **rest)
 
 
 @dataclass
@@ -318,7 +291,7 @@ def parse_input(current_doc: dict, log_dirs, broker_list: Optional[Sequence[int]
     replicas, partitions the current document does not hold, brokers outside the partition's row) adds its size to the dir's base.
     The same partition non-future twice on one broker is a ValueError."""
     from .waves import _entries
-    table = log_dirs if isinstance(log_dirs, dict) and "brokers" not in log_dirs else parse_log_dirs(log_dirs)   # a parse_log_dirs table as it is
+    table = _table_of(log_dirs)
     ids = sorted(table) if broker_list is None else [int(b) for b in broker_list]
     if not ids:
         raise ValueError("empty broker list")
@@ -428,16 +401,11 @@ def _quoted(s: str) -> str:
     return '"' + s.replace("\\", "\\\\").replace('"', '\\"') + '"'
 
 
-@dataclass
-class LogDirsPlan:
-    result: LogDirsResult
-    input: LogDirsInput
-    entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs) of the partitions with a move
-    capacity: Optional[List[int]] = None                                                  # per dir of the call, with capacities alone
-    exchange: bool = False                                                                # the call was kao_balance_logdirs_exchange
+class _PlanDocument:
+    """What LogDirsPlan and PlaceLogDirsPlan do with their entries."""
 
     def document(self) -> dict:
-        """The reassignment document of the partitions with a moved replica (what kafka-reassign-partitions --execute takes)."""
+        """The reassignment document of the entries, each with its log_dirs (what kafka-reassign-partitions --execute takes)."""
         return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": r, "log_dirs": d} for t, p, r, d in self.entries]}
 
     def text(self) -> str:
@@ -445,6 +413,15 @@ class LogDirsPlan:
         rows = ['    {"topic":%s,"partition":%d,"replicas":[%s],"log_dirs":[%s]}' % (_quoted(t), p, ",".join(str(b) for b in r), ",".join(_quoted(x) for x in d))
                 for t, p, r, d in self.entries]
         return '{"version":1,"partitions":[' + "".join(("\n" if i == 0 else ",\n") + r for i, r in enumerate(rows)) + "\n]}\n"
+
+
+@dataclass
+class LogDirsPlan(_PlanDocument):
+    result: LogDirsResult
+    input: LogDirsInput
+    entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs) of the partitions with a move
+    capacity: Optional[List[int]] = None                                                  # per dir of the call, with capacities alone
+    exchange: bool = False                                                                # the call was kao_balance_logdirs_exchange
 
     def report_lines(self) -> List[str]:
         return report_lines(self)
@@ -463,10 +440,6 @@ def plan_input(li: LogDirsInput, min_gain: int = 0, max_rounds: int = 0, dry_run
         lists.setdefault(k, ["any"] * len(li.rows[k]))[j] = flat[int(res.dir[r])]
     entries = [(li.keys[k][0], li.keys[k][1], list(li.rows[k]), lists[k]) for k in sorted(lists)]
     return LogDirsPlan(result=res, input=li, entries=entries, capacity=None if capacity is None else [int(x) for x in capacity], exchange=bool(exchange))
-
-
-def _table_of(log_dirs) -> Dict[int, Dict[str, LogDir]]:
-    return log_dirs if isinstance(log_dirs, dict) and "brokers" not in log_dirs else parse_log_dirs(log_dirs)   # a parse_log_dirs table as it is
 
 
 def balance_logdirs(current_doc: dict, log_dirs, *, broker_list: Optional[Sequence[int]] = None, min_gain: int = 0, max_rounds: int = 0,
@@ -538,7 +511,7 @@ def parse_place_input(current_doc: dict, log_dirs, plan_doc: Optional[dict] = No
     one is in sync).  An evacuated dir leaves its broker's dir list; its non-future entries of partitions whose row still holds the
     broker become homeless there, its other entries are stranded: neither planned nor counted."""
     from .waves import _entries
-    table = log_dirs if isinstance(log_dirs, dict) and "brokers" not in log_dirs else parse_log_dirs(log_dirs)
+    table = _table_of(log_dirs)
     ids = sorted(table) if broker_list is None else [int(b) for b in broker_list]
     if not ids:
         raise ValueError("empty broker list")
@@ -644,19 +617,11 @@ def parse_place_input(current_doc: dict, log_dirs, plan_doc: Optional[dict] = No
 
 
 @dataclass
-class PlaceLogDirsPlan:
+class PlaceLogDirsPlan(_PlanDocument):
     result: PlaceLogDirsResult
     input: PlaceInput
-    entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs)
+    entries: List[Tuple[str, int, List[int], List[str]]] = field(default_factory=list)   # (topic, partition, replicas, log_dirs) of the plan's partitions and those with a placed or moved replica
     capacity: Optional[List[int]] = None                                                  # per dir of the call, with capacities alone
-
-    def document(self) -> dict:
-        """The reassignment document: the partitions of the plan and those with a placed or moved replica, each with its log_dirs."""
-        return {"version": 1, "partitions": [{"topic": t, "partition": p, "replicas": r, "log_dirs": d} for t, p, r, d in self.entries]}
-
-    def text(self) -> str:
-        """The document byte for byte as cli/kao-logdirs writes it."""
-        return LogDirsPlan.text(self)
 
     def report_lines(self) -> List[str]:
         return place_report_lines(self)

@@ -135,3 +135,29 @@ def test_fails_loudly_without_gpu():
                 dict(broker=[0, 0]), dict(broker=[0.0, 0.0, 0.0])):
         with pytest.raises(ValueError):   # the binding's own checks come before the library
             place_logdirs_arrays(**dict(dict(dir_start=[0, 2], broker=[0, 0, 0], dir=[0, -1, 1], size=[4, 5, 6]), **bad))
+
+
+ARRAY_CHECKS = [   # in the order of the checks: a case with two faults gets the text of the earlier one
+    (dict(dir_start=[0], broker=[0, 0]), "dir_start must hold n_brokers + 1 values, n_brokers >= 1"),
+    (dict(broker=[0, 0], size=[4, 5]), "broker must hold one value per replica (3), got 2"),
+    (dict(broker=[0.0, 0.0, 0.0], size=[4, 5]), "brokers must be integers"),
+    (dict(size=[4, 5], min_gain=-1), "size must hold one value per replica (3), got 2"),
+    (dict(size=[4, -5, 6], min_gain=-1), "sizes must be integers >= 0"),
+    (dict(size=[4.0, 5.0, 6.0]), "sizes must be integers >= 0"),
+    (dict(min_gain=-1, base=[1]), "min_gain must be 0..2^64-1"),
+    (dict(min_gain=2 ** 64), "min_gain must be 0..2^64-1"),
+    (dict(min_gain=True), "min_gain must be 0..2^64-1"),
+    (dict(base=[1], capacity=[0, 0]), "base must hold one value per dir (2), got 1"),
+    (dict(base=[1, -1]), "bases must be integers >= 0"),
+    (dict(base=[1.0, 2.0]), "bases must be integers >= 0"),
+    (dict(capacity=[10]), "capacity must hold one value per dir (2), got 1"),
+]
+
+
+@pytest.mark.parametrize("bad,text", ARRAY_CHECKS, ids=[f"{i}-{t[:24]}" for i, (_, t) in enumerate(ARRAY_CHECKS)])
+def test_array_checks_refuse_with_their_texts(bad, text):
+    """The checks of place_logdirs_arrays before the library is called, with or without a device: the text, and the order of the checks."""
+    from kafka_assignment_optimizer_amd.logdirs import place_logdirs_arrays
+    with pytest.raises(ValueError) as e:
+        place_logdirs_arrays(**dict(dict(dir_start=[0, 2], broker=[0, 0, 0], dir=[0, -1, 1], size=[4, 5, 6]), **bad))
+    assert str(e.value) == text
