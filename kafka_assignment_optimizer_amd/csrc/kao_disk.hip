@@ -53,7 +53,7 @@
 #include <vector>
 
 #include "kao_host.h"
-#include "kao_plan_dev.h"   // descent_gains, descent_bid, lane_count_to, wave_bytes_code
+#include "kao_plan_dev.h"   // descent_gains, descent_bid, lane_count_to, wave_max_to, wave_sum_to, rank_ahead, wave_bytes_code
 
 namespace {
 
@@ -84,18 +84,6 @@ struct DkNet {   // one call; every pointer is device memory
     const u64 *capacity;       // [B] by utilisation only: the bytes of disk a broker has
 };
 
-typedef unsigned __int128 u128;
-
-__device__ inline void dk_max_to(u64 v, u64 *dst) {   // all 64 lanes active
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (u64)__shfl_xor((long long)v, off));
-    if (__lane_id() == 0 && v > 0) atomicMax(dst, v);
-}
-
-__device__ inline void dk_sum_to(u64 v, u64 *dst) {   // all 64 lanes active
-    for (int off = 32; off > 0; off >>= 1) v += (u64)__shfl_xor((long long)v, off);
-    if (__lane_id() == 0 && v > 0) atomicAdd(dst, v);
-}
-
 // ---- once per call ------------------------------------------------------------------------------------------------------------------
 // loads, the largest size, sum k_p size[p], the bytes of the slot-0 replicas per broker
 __global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) {
@@ -115,8 +103,8 @@ __global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) {
             atomicAdd(&fixed[row[0]], w);
         }
     }
-    dk_max_to(w, &n.ctl[D_MAXSIZE]);
-    dk_sum_to(all, &n.ctl[D_TOTAL]);
+    wave_max_to(w, &n.ctl[D_MAXSIZE]);
+    wave_sum_to(all, &n.ctl[D_TOTAL]);
 }
 
 // the peak before and the largest fixed load; the loads kept for the finish
@@ -128,55 +116,19 @@ __global__ void k_dk_peak0(DkNet n, const u64 *__restrict__ fixed, u64 *__restri
         f = fixed[b];
         load0[b] = s;
     }
-    dk_max_to(s, &n.ctl[D_PEAK0]);
-    dk_max_to(f, &n.ctl[D_FIXED]);
+    wave_max_to(s, &n.ctl[D_PEAK0]);
+    wave_max_to(f, &n.ctl[D_FIXED]);
 }
 
 // ---- a round ------------------------------------------------------------------------------------------------------------------------
-// rank[b] = brokers ahead of b by (load descending, index ascending), order[rank[b]] = b: all pairs, tiled through LDS (the scheme of
-// k_wl_rank in kao_wleaders.hip, which keeps no order[])
-__global__ __launch_bounds__(kDkThreads) void k_dk_rank(int B, const u64 *__restrict__ load, int32_t *__restrict__ rank, int32_t *__restrict__ order) {
-    __shared__ u64 tile[kDkThreads];
+// rank[b] = brokers ahead of b by (load descending, index ascending), order[rank[b]] = b.  Cap: by utilisation, x ahead of b iff
+// load(x) * cap(b) > load(b) * cap(x), or the products are equal and x < b (rank_ahead of kao_plan_dev.h)
+template <bool Cap>
+__global__ __launch_bounds__(kDkThreads) void k_dk_rank(int B, const u64 *__restrict__ load, const u64 *__restrict__ capacity, int32_t *__restrict__ rank,
+                                                        int32_t *__restrict__ order) {
     const int b = blockIdx.x * kDkThreads + threadIdx.x;
-    const u64 mine = b < B ? load[b] : 0;
-    int r = 0;
-    for (int base = 0; base < B; base += kDkThreads) {
-        const int cnt = min(kDkThreads, B - base);
-        if ((int)threadIdx.x < cnt) tile[threadIdx.x] = load[base + threadIdx.x];
-        __syncthreads();
-        for (int j = 0; j < cnt; ++j) {
-            const u64 x = tile[j];
-            r += (x > mine || (x == mine && base + j < b)) ? 1 : 0;
-        }
-        __syncthreads();
-    }
-    if (b < B) {   // ranks are a permutation: r < B
-        rank[b] = r;
-        order[r] = b;
-    }
-}
-
-// the same by utilisation: x ranks ahead of b iff load(x) * cap(b) > load(b) * cap(x), or the products are equal and x < b.  Loads and
-// capacities stay below 2^62, so the products fit 128 bits
-__global__ __launch_bounds__(kDkThreads) void k_dk_rank_cap(int B, const u64 *__restrict__ load, const u64 *__restrict__ capacity, int32_t *__restrict__ rank,
-                                                            int32_t *__restrict__ order) {
-    __shared__ u64 tile[kDkThreads], tcap[kDkThreads];
-    const int b = blockIdx.x * kDkThreads + threadIdx.x;
-    const u64 mine = b < B ? load[b] : 0, mcap = b < B ? capacity[b] : 1;
-    int r = 0;
-    for (int base = 0; base < B; base += kDkThreads) {
-        const int cnt = min(kDkThreads, B - base);
-        if ((int)threadIdx.x < cnt) {
-            tile[threadIdx.x] = load[base + threadIdx.x];
-            tcap[threadIdx.x] = capacity[base + threadIdx.x];
-        }
-        __syncthreads();
-        for (int j = 0; j < cnt; ++j) {
-            const u128 theirs = (u128)tile[j] * mcap, ours = (u128)mine * tcap[j];
-            r += (theirs > ours || (theirs == ours && base + j < b)) ? 1 : 0;
-        }
-        __syncthreads();
-    }
+    const u64 mine = b < B ? load[b] : 0, mcap = Cap && b < B ? capacity[b] : 1;
+    const int r = rank_ahead<kDkThreads, Cap>(B, b, mine, mcap, load, capacity);
     if (b < B) {   // ranks are a permutation: r < B
         rank[b] = r;
         order[r] = b;
@@ -398,7 +350,7 @@ __global__ void k_dk_apply(DkNet n, int r) {
         }
     }
     lane_count_to(won, &n.ctl[D_MOVES]);
-    if (Budget) dk_sum_to(cost, &n.ctl[D_SPENT]);   // the sum of a wavefront wraps as its terms do; it adds nothing when it is 0
+    if (Budget) wave_sum_to(cost, &n.ctl[D_SPENT]);   // the sum of a wavefront wraps as its terms do; it adds nothing when it is 0
 }
 
 // ---- the result ---------------------------------------------------------------------------------------------------------------------
@@ -419,8 +371,8 @@ __global__ void k_dk_finish(DkNet n) {
         }
         bytes = fresh * n.size[p];
     }
-    dk_sum_to(fresh, &n.ctl[D_NMOVED]);
-    dk_sum_to(bytes, &n.ctl[D_BYTES]);
+    wave_sum_to(fresh, &n.ctl[D_NMOVED]);
+    wave_sum_to(bytes, &n.ctl[D_BYTES]);
     lane_count_to(ch, &n.ctl[D_ROWS]);
 }
 
@@ -433,7 +385,7 @@ __global__ void k_dk_peak1(DkNet n, const u64 *__restrict__ load0) {
         s = n.load[b];
         ch = s != load0[b];
     }
-    dk_max_to(s, &n.ctl[D_PEAK1]);
+    wave_max_to(s, &n.ctl[D_PEAK1]);
     lane_count_to(ch, &n.ctl[D_BROKERS]);
 }
 
@@ -496,7 +448,7 @@ bool frac_integral(const DkFrac &peak, const uint64_t *cap, int B, uint64_t tota
 }
 
 // the entry points: Budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]; Cap (cap != NULL) is
-// the descent by utilisation: another rank kernel, the capacity form of the test, THOROUGH rounds, fractions as outputs, stats[10]
+// the descent by utilisation: the rank by utilisation, the capacity form of the test, THOROUGH rounds, fractions as outputs, stats[10]
 template <bool Budget, bool Cap>
 int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
                  const uint64_t *size, const uint64_t *cap, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes,
@@ -562,10 +514,7 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
     k_dk_peak0<<<bblocks, kDkThreads, 0, st>>>(n, d_fixed, d_load0);
     ++launches;
     HIP_TRY(hipGetLastError());
-    auto rank = [&] {
-        if (Cap) k_dk_rank_cap<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.capacity, n.rank, n.order);
-        else k_dk_rank<<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.rank, n.order);
-    };
+    const auto rank = [&] { k_dk_rank<Cap><<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.capacity, n.rank, n.order); };
 
     if (P) {
         uint32_t cnt[kDkBatch];

@@ -1,8 +1,10 @@
 // kao_plan_dev.h -- device code the one-shot planners share: the 64-bit keys of successive shortest paths (kao_leaders.hip,
 // kao_leaders_cluster.hip; DESIGN.md sections 4h, 4j), the wavefront count, the leader swap, the offsets of buckets
-// (kao_failover_dev.h, kao_logdirs.hip; sections 4i, 4o) and the pieces of the weighted descent (kao_wleaders.hip, kao_wfailover.hip,
-// kao_disk.hip, kao_logdirs.hip; sections 4k, 4l, 4m, 4o).  Everything sits in an unnamed namespace; the device functions are inlined
-// into their callers, and the one kernel is a template that only the files that launch it instantiate.
+// (kao_failover_dev.h, kao_logdirs.hip; sections 4i, 4o), the pieces of the weighted descent (kao_wleaders.hip, kao_wfailover.hip,
+// kao_disk.hip, kao_logdirs.hip; sections 4k, 4l, 4m, 4o), and what the two descents over all brokers share (kao_wleaders.hip,
+// kao_disk.hip; sections 4k, 4m, 4q): the wavefront maximum and sum into a control word and the all-pairs rank.  Everything sits in an
+// unnamed namespace; the device functions are inlined into their callers, and the one kernel is a template that only the files that
+// launch it instantiate.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +15,7 @@
 namespace {
 
 typedef unsigned long long u64;
+typedef unsigned __int128 u128;
 
 // ---- flow keys: (distance + 2^30) << 32 | arcs on the path, minimised as one word -------------------------------------------------
 constexpr u64 kFlowInf = ~0ull;
@@ -38,6 +41,17 @@ template <class T>
 __device__ __forceinline__ void lane_count_to(bool one, T *dst) {
     const u64 m = __ballot(one);
     if (m != 0ull && (int)__lane_id() == __ffsll((long long)m) - 1) atomicAdd(dst, (T)__popcll(m));
+}
+
+// the maximum and the sum of v over a wavefront, into *dst by lane 0 unless it is 0 (all 64 lanes active)
+__device__ inline void wave_max_to(u64 v, u64 *dst) {
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (u64)__shfl_xor((long long)v, off));
+    if (__lane_id() == 0 && v > 0) atomicMax(dst, v);
+}
+
+__device__ inline void wave_sum_to(u64 v, u64 *dst) {
+    for (int off = 32; off > 0; off >>= 1) v += (u64)__shfl_xor((long long)v, off);
+    if (__lane_id() == 0 && v > 0) atomicAdd(dst, v);
 }
 
 // the output row of a partition whose leader is slot l != 0: slot 0 and slot l swapped
@@ -90,6 +104,35 @@ __device__ __forceinline__ bool descent_gains(u64 la, u64 best, u64 w, u64 min_g
 template <int Scope>
 __device__ __forceinline__ void descent_bid(u64 *word, u64 key) {
     if (__hip_atomic_load(word, __ATOMIC_RELAXED, Scope) > key) atomicMin(word, key);
+}
+
+// ---- the all-pairs rank of the descents over all brokers: how many brokers x are AHEAD of b, all pairs tiled through LDS.  By load:
+// load[x] > mine, mine = load[b].  Cap, by utilisation: load[x] * mcap > mine * capacity[x], mcap = capacity[b]; loads and capacities
+// stay below 2^62, so the products fit 128 bits.  Ties: x < b.  Every lane of a workgroup of T calls it (two barriers per tile); a
+// lane with b >= B passes mine = 0, mcap = 1 and drops the result.  Static LDS: 8 T bytes, 16 T with Cap.
+template <int T, bool Cap>
+__device__ __forceinline__ int rank_ahead(int B, int b, u64 mine, u64 mcap, const u64 *__restrict__ load, const u64 *__restrict__ capacity) {
+    __shared__ u64 tile[T], tcap[Cap ? T : 1];   // (tcap is never touched without Cap, and takes no LDS then)
+    int r = 0;
+    for (int base = 0; base < B; base += T) {
+        const int cnt = min(T, B - base);
+        if ((int)threadIdx.x < cnt) {
+            tile[threadIdx.x] = load[base + threadIdx.x];
+            if (Cap) tcap[threadIdx.x] = capacity[base + threadIdx.x];
+        }
+        __syncthreads();
+        for (int j = 0; j < cnt; ++j) {
+            if constexpr (Cap) {
+                const u128 theirs = (u128)tile[j] * mcap, ours = (u128)mine * tcap[j];
+                r += (theirs > ours || (theirs == ours && base + j < b)) ? 1 : 0;
+            } else {
+                const u64 x = tile[j];
+                r += (x > mine || (x == mine && base + j < b)) ? 1 : 0;
+            }
+        }
+        __syncthreads();
+    }
+    return r;
 }
 
 }  // namespace

@@ -26,17 +26,19 @@
 // one of them, so one of them carries at least their average.  Rank (all pairs, tiled through LDS), one pass over the rows into a
 // u64 histogram over m_p, one scan.  Integers only.
 // kao_balance_leaders_weighted_exchange is the same call with a second kind of round, run when a round has
-// no move proposal: two partitions on one broker pair swap their leaders (see EXCHANGE rounds below).  Its kernels take WlxNet, a
-// type of their own; the kernels above the line "EXCHANGE rounds" and their arguments are those of the plain call alone.
+// no move proposal: two partitions on one broker pair swap their leaders (see EXCHANGE rounds below).  Its state is WlxNet, the plain
+// call's WlNet and the pair index.  The two calls share every text: a round's apply kernel and the single-workgroup kernel are
+// templates on X, the exchange call, and take WlxNet or WlNet; the instantiations without X hold nothing of the exchange.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kao_host.h"
-#include "kao_plan_dev.h"   // DESCENT_KEY, descent_gains, descent_bid, lane_count_to, swap_leader
+#include "kao_plan_dev.h"   // DESCENT_KEY, descent_gains, descent_bid, lane_count_to, wave_max_to, rank_ahead, swap_leader
 
 namespace {
 
@@ -74,10 +76,9 @@ struct WlxNet {   // one call of kao_balance_leaders_weighted_exchange: the plai
     uint16_t *pa, *pc;        // [P] its two brokers: apply never reads lead[]
 };
 
-__device__ inline void wl_max_to(u64 v, u64 *dst) {   // all 64 lanes active
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (u64)__shfl_xor((long long)v, off));
-    if (__lane_id() == 0 && v > 0) atomicMax(dst, v);
-}
+// the plain call's state inside the argument of a kernel of either call
+__device__ __forceinline__ const WlNet &wl_net(const WlNet &n) { return n; }
+__device__ __forceinline__ const WlNet &wl_net(const WlxNet &x) { return x.n; }
 
 // Step 1 and 2 for partition p against the loads `load`: false when p proposes nothing (every replica but the leader is eligible;
 // wf_propose of kao_wfailover.hip reads its eligible slots from a mask, so the two loops stay apart)
@@ -117,114 +118,47 @@ __global__ void k_wl_init(WlNet n, u64 *__restrict__ forced) {
             if (n.W == 1 || row[1] == KAO_NONE) atomicAdd(&forced[row[0]], w);
         }
     }
-    wl_max_to(w, &n.ctl[U_MAXW]);
+    wave_max_to(w, &n.ctl[U_MAXW]);
 }
 
 __global__ void k_wl_max(int B, const u64 *__restrict__ x, u64 *__restrict__ dst) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    wl_max_to(b < B ? x[b] : 0, dst);
+    wave_max_to(b < B ? x[b] : 0, dst);
 }
 
-// ---- a round on the multi-launch path -----------------------------------------------------------------------------------------------
+// ---- a round ----------------------------------------------------------------------------------------------------------------------
+// What a propose found for partition p is posted: key[p] (kWlNoKey when `prop` is false) and, for a proposal, slot[p], a bid at both of
+// its brokers in the minkey row of round r (mk = both rows) and one more in `posted`.  Scope as descent_bid has it; rows in LDS
+// (_WORKGROUP) take the plain atomicMin, without descent_bid's load.
+// (`posted` is counted here, in the branch that bids, and the row is taken after the stores: counted by the caller from a returned
+// flag, the loop of the single workgroup gains a second test of it and selects)
+template <int Scope>
+__device__ __forceinline__ void wl_post(const WlNet &n, int p, bool prop, u64 key, int slot, u64 *mk, int r, int a, int b, int &posted) {
+    n.key[p] = key;
+    if (!prop) return;
+    n.slot[p] = (uint8_t)slot;
+    u64 *row = mk + (size_t)(r & 1) * n.B;
+    if constexpr (Scope == __HIP_MEMORY_SCOPE_WORKGROUP) {
+        atomicMin(&row[a], key);
+        atomicMin(&row[b], key);
+    } else {
+        descent_bid<Scope>(&row[a], key);
+        descent_bid<Scope>(&row[b], key);
+    }
+    ++posted;
+}
+
+// the PROPOSE of a round on the multi-launch path
 __global__ void k_wl_propose(WlNet n, int r, uint32_t *__restrict__ count) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    bool prop = false;
+    int prop = 0;
     if (p < n.P) {
         int a = 0, b = 0, slot = 0;
         u64 key = kWlNoKey;
-        prop = wl_propose(n, p, n.load, a, b, slot, key);
-        n.key[p] = key;
-        if (prop) {
-            n.slot[p] = (uint8_t)slot;
-            u64 *row = n.mk + (size_t)(r & 1) * n.B;
-            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[a], key);
-            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[b], key);
-        }
+        const bool found = wl_propose(n, p, n.load, a, b, slot, key);
+        wl_post<__HIP_MEMORY_SCOPE_AGENT>(n, p, found, key, slot, n.mk, r, a, b, prop);
     }
-    lane_count_to(prop, count);
-}
-
-__global__ void k_wl_apply(WlNet n, int r) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    {   // the row of round r + 1 was last read by the apply of round r - 1
-        u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
-        for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kWlNoKey;
-    }
-    bool won = false;
-    if (p < n.P) {
-        const u64 key = n.key[p];
-        if (key != kWlNoKey) {
-            const uint16_t *row = n.rows + (size_t)p * n.W;
-            const int slot = n.slot[p], a = row[n.lead[p]], b = row[slot];
-            const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
-            won = mine[a] == key && mine[b] == key;
-            if (won) {   // no other winner touches a or b
-                const u64 w = n.weight[p];
-                n.load[a] -= w;
-                n.load[b] += w;
-                n.lead[p] = (uint8_t)slot;
-            }
-        }
-    }
-    lane_count_to(won, &n.ctl[U_MOVES]);
-}
-
-// ---- every round in one launch: one workgroup, loads and minkey rows in LDS ---------------------------------------------------------
-__global__ __launch_bounds__(kWlOneThreads) void k_wl_one(WlNet n, int max_rounds) {
-    extern __shared__ u64 wl_lds[];
-    u64 *load = wl_lds, *mk = wl_lds + n.B;
-    const int tid = threadIdx.x;
-    for (int b = tid; b < n.B; b += kWlOneThreads) {
-        load[b] = n.load[b];
-        mk[b] = kWlNoKey;
-        mk[n.B + b] = kWlNoKey;
-    }
-    __syncthreads();
-    u64 props = 0, moves = 0;
-    int rounds = 0, more = 0;
-    for (int r = 0; r < kWlHardRounds; ++r) {
-        u64 *row = mk + (size_t)(r & 1) * n.B, *other = mk + (size_t)((r + 1) & 1) * n.B;
-        int mine = 0;
-        for (int p = tid; p < n.P; p += kWlOneThreads) {
-            int a = 0, b = 0, slot = 0;
-            u64 key = kWlNoKey;
-            const bool prop = wl_propose(n, p, load, a, b, slot, key);
-            n.key[p] = key;   // read back by this thread alone
-            if (prop) {
-                n.slot[p] = (uint8_t)slot;
-                atomicMin(&row[a], key);
-                atomicMin(&row[b], key);
-                ++mine;
-            }
-        }
-        if (!__syncthreads_or(mine)) break;
-        if (max_rounds > 0 && r >= max_rounds) { more = 1; break; }
-        ++rounds;
-        props += (u64)mine;
-        for (int p = tid; p < n.P; p += kWlOneThreads) {
-            const u64 key = n.key[p];
-            if (key == kWlNoKey) continue;
-            const uint16_t *rw = n.rows + (size_t)p * n.W;
-            const int slot = n.slot[p], a = rw[n.lead[p]], b = rw[slot];
-            if (row[a] == key && row[b] == key) {
-                const u64 w = n.weight[p];
-                load[a] -= w;
-                load[b] += w;
-                n.lead[p] = (uint8_t)slot;
-                ++moves;
-            }
-        }
-        for (int b = tid; b < n.B; b += kWlOneThreads) other[b] = kWlNoKey;
-        __syncthreads();
-    }
-    __syncthreads();
-    for (int b = tid; b < n.B; b += kWlOneThreads) n.load[b] = load[b];
-    if (props) atomicAdd(&n.ctl[U_PROPS], props);
-    if (moves) atomicAdd(&n.ctl[U_MOVES], moves);
-    if (tid == 0) {
-        n.ctl[U_ROUNDS] = (u64)rounds;
-        n.ctl[U_MORE] = (u64)more;
-    }
+    lane_count_to(prop != 0, count);
 }
 
 // ---- EXCHANGE rounds -----------------------------------------------------------------------------------------
@@ -298,23 +232,25 @@ __device__ inline bool wlx_propose(const WlxNet &x, int p, const u64 *load, int 
     }
 }
 
-// apply of a MOVE proposal, as k_wl_apply does it: true when it won
-__device__ __forceinline__ bool wlx_apply_move(const WlNet &n, int p, u64 key, const u64 *mine, u64 *load) {
+// apply of a MOVE proposal against the round's minkey row `mine`: a winner (no other winner touches a or b) moves its leader and adds 1
+// to `won`, inside the branch that moves (see wl_post)
+__device__ __forceinline__ void wl_apply_move(const WlNet &n, int p, u64 key, const u64 *mine, u64 *load, u64 &won) {
     const uint16_t *row = n.rows + (size_t)p * n.W;
     const int slot = n.slot[p], a = row[n.lead[p]], b = row[slot];
-    if (mine[a] != key || mine[b] != key) return false;
+    if (mine[a] != key || mine[b] != key) return;
     const u64 w = n.weight[p];
     load[a] -= w;
     load[b] += w;
     n.lead[p] = (uint8_t)slot;
-    return true;
+    ++won;
 }
 
-// apply of an EXCHANGE proposal: its brokers come from what propose stored, because a winner writes lead[y] of another partition
-__device__ __forceinline__ bool wlx_apply_swap(const WlxNet &x, int p, u64 key, const u64 *mine, u64 *load) {
+// apply of an EXCHANGE proposal, counted likewise: its brokers come from what propose stored, because a winner writes lead[y] of another
+// partition
+__device__ __forceinline__ void wlx_apply_swap(const WlxNet &x, int p, u64 key, const u64 *mine, u64 *load, u64 &won) {
     const WlNet &n = x.n;
     const int a = x.pa[p], c = x.pc[p];
-    if (mine[a] != key || mine[c] != key) return false;   // no other winner touches a or c, x or y
+    if (mine[a] != key || mine[c] != key) return;   // no other winner touches a or c, x or y
     const uint32_t y = x.partner[p];
     const u64 d = n.weight[p] - n.weight[y];
     load[a] -= d;
@@ -324,7 +260,14 @@ __device__ __forceinline__ bool wlx_apply_swap(const WlxNet &x, int p, u64 key, 
     int ja = 0;
     while (ja < n.W - 1 && ry[ja] != a) ++ja;
     n.lead[y] = (uint8_t)ja;
-    return true;
+    ++won;
+}
+
+// what an exchange proposal stores beside wl_post
+__device__ __forceinline__ void wlx_post_pair(const WlxNet &x, int p, uint32_t y, int a, int c) {
+    x.partner[p] = y;
+    x.pa[p] = (uint16_t)a;
+    x.pc[p] = (uint16_t)c;
 }
 
 // enqueued behind every k_wl_propose: returns at once when that round has a move proposal
@@ -332,50 +275,48 @@ __global__ void k_wlx_propose(WlxNet x, int r, const uint32_t *__restrict__ move
     if (*moves) return;
     const WlNet &n = x.n;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    bool prop = false;
+    int prop = 0;
     if (p < n.P) {   // key[p] is kWlNoKey: k_wl_propose found nothing
         int a = 0, c = 0, slot = 0;
         uint32_t y = 0;
         u64 key = kWlNoKey;
-        prop = wlx_propose(x, p, n.load, a, c, slot, y, key);
-        if (prop) {
-            n.key[p] = key;
-            n.slot[p] = (uint8_t)slot;
-            x.partner[p] = y;
-            x.pa[p] = (uint16_t)a;
-            x.pc[p] = (uint16_t)c;
-            u64 *row = n.mk + (size_t)(r & 1) * n.B;
-            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[a], key);
-            descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&row[c], key);
+        if (wlx_propose(x, p, n.load, a, c, slot, y, key)) {
+            wlx_post_pair(x, p, y, a, c);
+            wl_post<__HIP_MEMORY_SCOPE_AGENT>(n, p, true, key, slot, n.mk, r, a, c, prop);
         }
     }
-    lane_count_to(prop, count);
+    lane_count_to(prop != 0, count);
 }
 
-// the apply of either kind of round
-__global__ void k_wlx_apply(WlxNet x, int r, const uint32_t *__restrict__ moves) {
-    const WlNet &n = x.n;
+// ---- the apply of a round, and every round in one launch: both calls, X = the exchange call -------------------------------------------
+// `moves` (X only) = the round's move proposals: 0 in an exchange round
+template <bool X>
+__global__ void k_wl_apply(std::conditional_t<X, WlxNet, WlNet> net, int r, const uint32_t *__restrict__ moves) {
+    const WlNet &n = wl_net(net);
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     {   // the row of round r + 1 was last read by the apply of round r - 1
         u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
         for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kWlNoKey;
     }
-    const bool move = *moves != 0;
-    bool won = false;
+    bool move = true;
+    if constexpr (X) move = *moves != 0;
+    u64 won = 0;   // 1: the proposal of this lane won
     if (p < n.P) {
         const u64 key = n.key[p];
         if (key != kWlNoKey) {
             const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
-            won = move ? wlx_apply_move(n, p, key, mine, n.load) : wlx_apply_swap(x, p, key, mine, n.load);
+            if (move) wl_apply_move(n, p, key, mine, n.load, won);
+            else if constexpr (X) wlx_apply_swap(net, p, key, mine, n.load, won);
         }
     }
-    lane_count_to(won, &n.ctl[move ? U_MOVES : U_XCH]);
+    lane_count_to(won != 0, &n.ctl[move ? U_MOVES : U_XCH]);
 }
 
-// every round of both kinds in one launch: one workgroup, loads and minkey rows in LDS, the pair index in global memory
-__global__ __launch_bounds__(kWlOneThreads) void k_wlx_one(WlxNet x, int max_rounds) {
+// one workgroup, loads and minkey rows in LDS (X: the pair index in global memory)
+template <bool X>
+__global__ __launch_bounds__(kWlOneThreads) void k_wl_one(std::conditional_t<X, WlxNet, WlNet> net, int max_rounds) {
     extern __shared__ u64 wl_lds[];
-    const WlNet &n = x.n;
+    const WlNet &n = wl_net(net);
     u64 *load = wl_lds, *mk = wl_lds + n.B;
     const int tid = threadIdx.x;
     for (int b = tid; b < n.B; b += kWlOneThreads) {
@@ -384,8 +325,10 @@ __global__ __launch_bounds__(kWlOneThreads) void k_wlx_one(WlxNet x, int max_rou
         mk[n.B + b] = kWlNoKey;
     }
     __syncthreads();
-    u64 props = 0, moves = 0, xprops = 0, swaps = 0;
-    int rounds = 0, xrounds = 0, more = 0;
+    u64 props = 0, moves = 0;
+    int rounds = 0, more = 0;
+    [[maybe_unused]] u64 xprops = 0, swaps = 0;   // X
+    [[maybe_unused]] int xrounds = 0;
     for (int r = 0; r < kWlHardRounds; ++r) {
         u64 *row = mk + (size_t)(r & 1) * n.B, *other = mk + (size_t)((r + 1) & 1) * n.B;
         int mine = 0;
@@ -393,41 +336,38 @@ __global__ __launch_bounds__(kWlOneThreads) void k_wlx_one(WlxNet x, int max_rou
             int a = 0, b = 0, slot = 0;
             u64 key = kWlNoKey;
             const bool prop = wl_propose(n, p, load, a, b, slot, key);
-            n.key[p] = key;   // read back by this thread alone
-            if (prop) {
-                n.slot[p] = (uint8_t)slot;
-                atomicMin(&row[a], key);
-                atomicMin(&row[b], key);
-                ++mine;
-            }
+            wl_post<__HIP_MEMORY_SCOPE_WORKGROUP>(n, p, prop, key, slot, mk, r, a, b, mine);
         }
         const bool move = __syncthreads_or(mine) != 0;
-        if (!move) {   // an EXCHANGE round: the lead[] of other partitions was written before the barrier that ended the last round
-            for (int p = tid; p < n.P; p += kWlOneThreads) {
-                int a = 0, c = 0, slot = 0;
-                uint32_t y = 0;
-                u64 key = kWlNoKey;
-                if (!wlx_propose(x, p, load, a, c, slot, y, key)) continue;
-                n.key[p] = key;
-                n.slot[p] = (uint8_t)slot;
-                x.partner[p] = y;
-                x.pa[p] = (uint16_t)a;
-                x.pc[p] = (uint16_t)c;
-                atomicMin(&row[a], key);
-                atomicMin(&row[c], key);
-                ++mine;
+        if constexpr (X) {
+            if (!move) {   // an EXCHANGE round: the lead[] of other partitions was written before the barrier that ended the last round
+                for (int p = tid; p < n.P; p += kWlOneThreads) {
+                    int a = 0, c = 0, slot = 0;
+                    uint32_t y = 0;
+                    u64 key = kWlNoKey;
+                    if (!wlx_propose(net, p, load, a, c, slot, y, key)) continue;
+                    wlx_post_pair(net, p, y, a, c);
+                    wl_post<__HIP_MEMORY_SCOPE_WORKGROUP>(n, p, true, key, slot, mk, r, a, c, mine);
+                }
+                if (!__syncthreads_or(mine)) break;
             }
-            if (!__syncthreads_or(mine)) break;
+        } else if (!move) {
+            break;
         }
         if (max_rounds > 0 && r >= max_rounds) { more = 1; break; }
         ++rounds;
         props += (u64)mine;
-        if (!move) { ++xrounds; xprops += (u64)mine; }
+        if (X && !move) { ++xrounds; xprops += (u64)mine; }
         for (int p = tid; p < n.P; p += kWlOneThreads) {
             const u64 key = n.key[p];
             if (key == kWlNoKey) continue;
-            if (move) moves += wlx_apply_move(n, p, key, row, load) ? 1 : 0;
-            else swaps += wlx_apply_swap(x, p, key, row, load) ? 1 : 0;
+            if constexpr (X) {
+                if (!move) {
+                    wlx_apply_swap(net, p, key, row, load, swaps);
+                    continue;
+                }
+            }
+            wl_apply_move(n, p, key, row, load, moves);
         }
         for (int b = tid; b < n.B; b += kWlOneThreads) other[b] = kWlNoKey;
         __syncthreads();
@@ -436,11 +376,13 @@ __global__ __launch_bounds__(kWlOneThreads) void k_wlx_one(WlxNet x, int max_rou
     for (int b = tid; b < n.B; b += kWlOneThreads) n.load[b] = load[b];
     if (props) atomicAdd(&n.ctl[U_PROPS], props);
     if (moves) atomicAdd(&n.ctl[U_MOVES], moves);
-    if (xprops) atomicAdd(&n.ctl[U_XPROPS], xprops);
-    if (swaps) atomicAdd(&n.ctl[U_XCH], swaps);
+    if constexpr (X) {
+        if (xprops) atomicAdd(&n.ctl[U_XPROPS], xprops);
+        if (swaps) atomicAdd(&n.ctl[U_XCH], swaps);
+    }
     if (tid == 0) {
         n.ctl[U_ROUNDS] = (u64)rounds;
-        n.ctl[U_XROUNDS] = (u64)xrounds;
+        if constexpr (X) n.ctl[U_XROUNDS] = (u64)xrounds;
         n.ctl[U_MORE] = (u64)more;
     }
 }
@@ -450,22 +392,11 @@ __global__ __launch_bounds__(kWlOneThreads) void k_wlx_one(WlxNet x, int max_rou
 // workgroup and reuses its LDS for the histogram: not shared)
 // rank[b] = brokers ahead of b by (load descending, index ascending); the peak on the way
 __global__ __launch_bounds__(kWlThreads) void k_wl_rank(int B, const u64 *__restrict__ load, int32_t *__restrict__ rank, u64 *__restrict__ peak) {
-    __shared__ u64 tile[kWlThreads];
     const int b = blockIdx.x * kWlThreads + threadIdx.x;
     const u64 mine = b < B ? load[b] : 0;
-    int r = 0;
-    for (int base = 0; base < B; base += kWlThreads) {
-        const int cnt = min(kWlThreads, B - base);
-        if ((int)threadIdx.x < cnt) tile[threadIdx.x] = load[base + threadIdx.x];
-        __syncthreads();
-        for (int j = 0; j < cnt; ++j) {
-            const u64 x = tile[j];
-            r += (x > mine || (x == mine && base + j < b)) ? 1 : 0;
-        }
-        __syncthreads();
-    }
+    const int r = rank_ahead<kWlThreads, false>(B, b, mine, 1, load, nullptr);
     if (b < B) rank[b] = r;
-    wl_max_to(mine, peak);
+    wave_max_to(mine, peak);
 }
 
 // one lane per partition: the row's largest rank into the histogram, the leader's count, the swap
@@ -577,8 +508,7 @@ void wlx_build_index(int B, int P, int W, const uint16_t *rows, const uint64_t *
     ix.seg_lo.push_back((uint32_t)e.size());
 }
 
-// Both entry points: `exchange` adds the pair index, the exchange kernels and stats[8..11]; without it every launch and every byte is
-// the plain call's.
+// Both entry points: `exchange` adds the pair index, k_wlx_propose, the X instantiations of the two templates and stats[8..11].
 int wl_call(bool exchange, const std::string &fn, int32_t n_brokers, int32_t n_partitions, int32_t width, uint16_t *rows, const uint64_t *weight,
             uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_changed, uint64_t *peak_before, uint64_t *peak_after,
             uint64_t *lower_bound, int32_t *status, int64_t *stats) {
@@ -648,58 +578,34 @@ int wl_call(bool exchange, const std::string &fn, int32_t n_brokers, int32_t n_p
 
     if (one) {
         if (P) {
-            if (exchange) k_wlx_one<<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(x, max_rounds);
-            else k_wl_one<<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(n, max_rounds);
+            if (exchange) k_wl_one<true><<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(x, max_rounds);
+            else k_wl_one<false><<<1, kWlOneThreads, 3 * (size_t)B * sizeof(u64), st>>>(n, max_rounds);
             ++launches;
             HIP_TRY(hipGetLastError());
         }
-    } else if (P && !exchange) {
-        uint32_t cnt[kWlBatch];
+    } else if (P) {   // two launches per round; with exchange three: its propose sees the round's move count and steps aside, the apply does either kind
+        uint32_t cnt[2 * kWlBatch] = {};   // the second row stays 0 without exchange
+        const auto propose = [&](int r, int i) {   // round r, counted in column i
+            k_wl_propose<<<pblocks, kWlThreads, 0, st>>>(n, r, d_cnt + i);
+            if (exchange) k_wlx_propose<<<pblocks, kWlThreads, 0, st>>>(x, r, d_cnt + i, d_cnt + kWlBatch + i);
+            launches += exchange ? 2 : 1;
+        };
         for (int r = 0, done = 0; !done;) {
             if (r >= kWlHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
             const int nb = max_rounds > 0 ? std::min(kWlBatch, max_rounds - r) : kWlBatch;
-            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
-            if (nb == 0) {   // max_rounds rounds have run, every one with a move: is there more to do?
-                k_wl_propose<<<pblocks, kWlThreads, 0, st>>>(n, r, d_cnt);
+            HIP_TRY(hipMemsetAsync(d_cnt, 0, ncnt * sizeof(uint32_t), st));
+            if (nb == 0) propose(r, 0);   // max_rounds rounds have run, every one with a proposal: is there more to do?
+            for (int i = 0; i < nb; ++i) {
+                propose(r + i, i);
+                if (exchange) k_wl_apply<true><<<pblocks, kWlThreads, 0, st>>>(x, r + i, d_cnt + i);
+                else k_wl_apply<false><<<pblocks, kWlThreads, 0, st>>>(n, r + i, nullptr);
                 ++launches;
             }
-            for (int i = 0; i < nb; ++i) {
-                k_wl_propose<<<pblocks, kWlThreads, 0, st>>>(n, r + i, d_cnt + i);
-                k_wl_apply<<<pblocks, kWlThreads, 0, st>>>(n, r + i);
-                launches += 2;
-            }
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (nb == 0) { more = cnt[0] != 0; break; }
-            for (int i = 0; i < nb && !done; ++i) {   // the first round without a proposal ends the descent; the ones after it changed nothing
-                if (cnt[i] == 0) done = 1;
-                else { ++rounds; props += cnt[i]; }
-            }
-            r += nb;
-        }
-    } else if (P) {   // three launches per round: the exchange propose sees the round's move count and steps aside, the apply does either kind
-        uint32_t cnt[2 * kWlBatch];
-        for (int r = 0, done = 0; !done;) {
-            if (r >= kWlHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
-            const int nb = max_rounds > 0 ? std::min(kWlBatch, max_rounds - r) : kWlBatch;
-            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
-            if (nb == 0) {   // max_rounds rounds have run, every one with a proposal: is there more to do?
-                k_wl_propose<<<pblocks, kWlThreads, 0, st>>>(n, r, d_cnt);
-                k_wlx_propose<<<pblocks, kWlThreads, 0, st>>>(x, r, d_cnt, d_cnt + kWlBatch);
-                launches += 2;
-            }
-            for (int i = 0; i < nb; ++i) {
-                k_wl_propose<<<pblocks, kWlThreads, 0, st>>>(n, r + i, d_cnt + i);
-                k_wlx_propose<<<pblocks, kWlThreads, 0, st>>>(x, r + i, d_cnt + i, d_cnt + kWlBatch + i);
-                k_wlx_apply<<<pblocks, kWlThreads, 0, st>>>(x, r + i, d_cnt + i);
-                launches += 3;
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(cnt, d_cnt, ncnt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             if (nb == 0) { more = cnt[0] != 0 || cnt[kWlBatch] != 0; break; }
-            for (int i = 0; i < nb && !done; ++i) {   // the first round with neither kind of proposal ends the call; the ones after it changed nothing
+            for (int i = 0; i < nb && !done; ++i) {   // the first round with no proposal of either kind ends the call; the ones after it changed nothing
                 const uint32_t cm = cnt[i], cx = cnt[kWlBatch + i];
                 if (cm == 0 && cx == 0) done = 1;
                 else {

@@ -137,6 +137,30 @@ def test_both_paths_give_the_same_bytes(call, mid):
             _checked(call, rows, weight, B, path=MULTI, **kw)
 
 
+# ---- 4b. the rounds against the batches of the multi-launch path (32 rounds between two reads of the counts) -------------------------
+@pytest.mark.parametrize("path", [ONE, MULTI])
+def test_last_round_with_a_proposal_is_the_last_of_a_batch(call, path):
+    """The descent takes exactly 32 rounds (tests/test_wleaders_ref.py holds the generator to it): the first batch is full and the
+    first round of the second is empty.  Launches: init and the peak before, two batches of 32 rounds of two, rank, finish, scan."""
+    rows, weight = wr.lognormal_case(6, 200, 3, 0.7, 26)
+    res, _ = _checked(call, rows, weight, 6, path=path)
+    assert res.stats[0] == 32 and res.stats[5] == 0
+    if path == MULTI:
+        assert res.stats[3] == 2 + 2 * 64 + 3
+
+
+@pytest.mark.parametrize("path", [ONE, MULTI])
+def test_max_rounds_at_and_around_a_batch(call, path):
+    """Launches on the multi-launch path: the 5 around the rounds, 2 a round enqueued (a batch is cut at max_rounds) and, when every
+    one of max_rounds rounds had a proposal, the probe of 1.  At 64 the second batch holds the first empty round: no probe."""
+    rows, weight = wr.lognormal_case(6, 300, 3, 0.7, 7)
+    for limit, rounds, more, launches in ((31, 31, 1, 5 + 2 * 31 + 1), (32, 32, 1, 5 + 2 * 32 + 1), (33, 33, 1, 5 + 2 * 33 + 1), (64, 52, 0, 5 + 2 * 64)):
+        res, _ = _checked(call, rows, weight, 6, max_rounds=limit, path=path)
+        assert (res.stats[0], res.stats[5]) == (rounds, more), limit
+        if path == MULTI:
+            assert res.stats[3] == launches, limit
+
+
 # ---- 5. unit weights against the exact solver of section 4j --------------------------------------------------------------------------
 def test_unit_weights_bracket_the_exact_cluster_balance(call):
     from kafka_assignment_optimizer_amd.leaders import balance_leaders_cluster_arrays

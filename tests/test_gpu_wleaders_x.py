@@ -240,6 +240,31 @@ def test_max_rounds_edges(call, path):
             assert res.stats[8] == x_rounds, limit
 
 
+# ---- 7b. the rounds against the batches of the multi-launch path (32 rounds between two reads of the counts) -------------------------
+@BOTH
+def test_last_round_with_a_proposal_is_the_last_of_a_batch(call, path):
+    """The descent takes exactly 32 rounds, 13 of them exchange rounds (tests/test_wleaders_x_ref.py holds the generator to it): the
+    first batch is full and the first round of the second is empty.  Launches: init and the peak before, two batches of 32 rounds of
+    three, rank, finish, scan."""
+    rows, weight = wr.lognormal_case(5, 120, 3, 0.7, 28)
+    res, _, _ = _checked(call, rows, weight, 5, path=path)
+    assert res.stats[0] == 32 and res.stats[5] == 0 and res.stats[8] == 13
+    if path == MULTI:
+        assert res.stats[3] == 2 + 3 * 64 + 3
+
+
+@BOTH
+def test_max_rounds_at_and_around_a_batch(call, path):
+    """Launches on the multi-launch path: the 5 around the rounds, 3 a round and, every one of the max_rounds rounds having had a
+    proposal, the probe of 2."""
+    rows, weight = wr.lognormal_case(6, 300, 3, 0.7, 7)
+    for limit, rounds, more, x_rounds in ((31, 31, 1, 0), (32, 32, 1, 0), (33, 33, 1, 0), (64, 64, 1, 10)):
+        res, _, _ = _checked(call, rows, weight, 6, max_rounds=limit, path=path)
+        assert (res.stats[0], res.stats[5], res.stats[8]) == (rounds, more, x_rounds), limit
+        if path == MULTI:
+            assert res.stats[3] == 5 + 3 * limit + 2, limit
+
+
 # ---- 8. the command-line tools and the Python API ------------------------------------------------------------------------------------
 PROGS = ([os.path.join(ROOT, "cli", "kao-leaders")], [sys.executable, "-m", "kafka_assignment_optimizer_amd.leaders"])
 

@@ -69,6 +69,13 @@ def test_restatement_on_the_contention_shapes_and_limits():
         assert none["rounds"] == 0 and none["n_changed"] == 0 and (none["rows"] == rows).all()
 
 
+def test_batch_boundary_case_takes_exactly_one_batch_of_rounds():
+    """tests/test_gpu_wleaders.py relies on it: 32 rounds, the batch of the multi-launch path, so its last round with a proposal is
+    the last of a batch."""
+    res = wr.descend(*wr.lognormal_case(6, 200, 3, 0.7, 26), 6)
+    assert res["rounds"] == 32 and not res["more"]
+
+
 # ---- the entry point ---------------------------------------------------------------------------------------------------------------
 def _call(rows, B, weight, min_gain=0, max_rounds=0, null=None, P=None, W=None):
     from kafka_assignment_optimizer_amd import _ffi

@@ -117,6 +117,13 @@ def test_max_rounds_edges_set_the_more_flag():
     assert no_x["rows"].tobytes() == plain["rows"].tobytes() and no_x["x_rounds"] == 0
 
 
+def test_batch_boundary_case_takes_exactly_one_batch_of_rounds():
+    """tests/test_gpu_wleaders_x.py relies on it: 32 rounds of both kinds, the batch of the multi-launch path, so its last round with
+    a proposal is the last of a batch."""
+    res = xr.descend(*wr.lognormal_case(5, 120, 3, 0.7, 28), 5)
+    assert (res["rounds"], res["x_rounds"]) == (32, 13) and not res["more"]
+
+
 def test_pair_index_holds_every_pair_once_in_weight_order():
     rows, weight, B = wr.small_case(5)
     pi, segs = xr.pair_index(rows, weight)
