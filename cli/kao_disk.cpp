@@ -1,9 +1,10 @@
 // kao-disk -- disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk, DESIGN.md
-// section 4m; under --max-bytes kao_balance_disk_budget, section 4n; with --capacities kao_balance_disk_capacity, section 4q).
+// section 4m; under --max-bytes kao_balance_disk_budget, section 4n; with --capacities kao_balance_disk_capacity, section 4q; with
+// --exchange kao_balance_disk_exchange, section 4u).
 //
 //   kao-disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt [--default-size N]
 //            [--max-per-rack N] [--keep-leaders] [--min-gain BYTES] [--max-bytes BYTES] [--max-rounds N] [--dry-run] --out plan.json
-//            [--capacities caps.json | id:bytes,...] [--default-capacity BYTES] [--report] [--device D]
+//            [--capacities caps.json | id:bytes,...] [--default-capacity BYTES] [--exchange] [--report] [--device D]
 //
 // Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
 // output or a sizes document, as kao-waves reads them) and moves replicas to brokers outside their row until no single move closes a
@@ -19,6 +20,9 @@
 // broker its disk size, --default-capacity N that of the brokers the table does not name; a broker of --broker-list without either
 // is a usage error.  The moves then lower the peak UTILISATION S(b) / capacity(b), the answer for brokers with unequal disks, and the
 // report line ends in peak_before_ppm, peak_after_ppm, lower_bound_ppm (parts per million, rounded down) and thorough_rounds.
+// --exchange goes on from the move-stable state with exchanges: two replicas of different partitions trade places across a broker
+// pair.  It works by bytes only, so it is refused together with --max-bytes, --capacities or --default-capacity; the report line then
+// ends in peak_of_moves (the peak the moves alone reach), exchange_rounds, exchanges and exchange_proposals.
 // All computation happens in libkao.so on the GPU.
 // Exit status: 0 = ok, 1 = error, 2 = usage.
 #include <algorithm>
@@ -43,7 +47,9 @@ namespace {
         "usage: kao-disk --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
         "                --sizes <kafka-log-dirs output | sizes.json> [--default-size N] [--max-per-rack N] [--keep-leaders]\n"
         "                [--min-gain N[K|M|G|T]] [--max-bytes N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report]\n"
-        "                [--capacities <caps.json | id:bytes,...>] [--default-capacity N[K|M|G|T]] [--device D]\n"
+        "                [--capacities <caps.json | id:bytes,...>] [--default-capacity N[K|M|G|T]] [--exchange] [--device D]\n"
+        "--exchange: exchanges of two replicas across a broker pair go on from the move-stable state (by bytes only: not with\n"
+        "            --max-bytes, --capacities or --default-capacity)\n"
         "writes the partitions whose replicas move; exit status: 0 = ok, 1 = error, 2 = usage\n");
     std::exit(2);
 }
@@ -89,7 +95,7 @@ std::string ppm(uint64_t num, uint64_t den) {
 int main(int argc, char **argv) {
     std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path, caps_arg;
     int device = 0, max_per_rack = 0, max_rounds = 0;
-    bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false, have_caps = false, have_default_cap = false;
+    bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false, have_caps = false, have_default_cap = false, exchange = false;
     uint64_t default_size = 0, min_gain = 0, max_bytes = 0, default_cap = 0;
     auto count_arg = [](const std::string &v, const char *msg) {
         if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
@@ -105,6 +111,7 @@ int main(int argc, char **argv) {
         else if (a == "--out") out_path = need("--out");
         else if (a == "--dry-run") dry_run = true;
         else if (a == "--keep-leaders") keep_leaders = true;
+        else if (a == "--exchange") exchange = true;
         else if (a == "--device") device = std::atoi(need("--device").c_str());
         else if (a == "--report") report = true;
         else if (a == "--default-size") {
@@ -129,6 +136,7 @@ int main(int argc, char **argv) {
     if (cur_path.empty() || brokers_csv.empty() || racks_arg.empty() || sizes_path.empty() || out_path.empty())
         usage("--current, --broker-list, --racks, --sizes and --out are required");
     const bool by_capacity = have_caps || have_default_cap;
+    if (exchange && (have_budget || by_capacity)) usage("--exchange works by bytes only: not together with --max-bytes, --capacities or --default-capacity");
     std::vector<uint64_t> capacity;   // per broker of --broker-list, in its order
     if (by_capacity) {                // a broker without a capacity is a usage error
         std::string msg;
@@ -180,8 +188,8 @@ int main(int argc, char **argv) {
         std::vector<uint16_t> rows = cr.rows;
         int32_t n_moved = 0, status = 0;
         uint64_t bytes_moved = 0, before = 0, after = 0, bound = 0, before2[2] = {0, 1}, after2[2] = {0, 1}, bound2[2] = {0, 1};
-        int64_t stats[11] = {0};
-        const char *entry = by_capacity ? "kao_balance_disk_capacity: " : have_budget ? "kao_balance_disk_budget: " : "kao_balance_disk: ";
+        int64_t stats[12] = {0};
+        const char *entry = by_capacity ? "kao_balance_disk_capacity: " : have_budget ? "kao_balance_disk_budget: " : exchange ? "kao_balance_disk_exchange: " : "kao_balance_disk: ";
         if (by_capacity) {
             rc = kao_balance_disk_capacity(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), capacity.data(), max_per_rack,
                                            keep_leaders ? 0 : 1, min_gain, have_budget ? max_bytes : UINT64_MAX, max_rounds, dry_run ? 1 : 0, &n_moved,
@@ -190,6 +198,9 @@ int main(int argc, char **argv) {
         } else if (have_budget)
             rc = kao_balance_disk_budget(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1,
                                          min_gain, max_bytes, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
+        else if (exchange)
+            rc = kao_balance_disk_exchange(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1,
+                                           min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
         else
             rc = kao_balance_disk(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1, min_gain,
                                   max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
@@ -210,6 +221,9 @@ int main(int argc, char **argv) {
             if (by_capacity)
                 std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s lower_bound_ppm=%s thorough_rounds=%lld", ppm(before2[0], before2[1]).c_str(),
                              ppm(after2[0], after2[1]).c_str(), ppm(bound2[0], bound2[1]).c_str(), (long long)stats[10]);
+            if (exchange)
+                std::fprintf(stderr, " peak_of_moves=%lld exchange_rounds=%lld exchanges=%lld exchange_proposals=%lld", (long long)stats[11], (long long)stats[8],
+                             (long long)stats[9], (long long)stats[10]);
             std::fprintf(stderr, "\n");
         }
         const std::string text = changed_rows_text(cr, rows, cl.brokers);

@@ -778,6 +778,49 @@ int kao_balance_disk_capacity(int32_t n_brokers, int32_t n_racks, const uint8_t 
                               uint64_t peak_before[2], uint64_t peak_after[2], uint64_t lower_bound[2], int32_t *status,
                               int64_t stats[11] /* may be NULL */);
 
+/* ---- Disk-usage balance with exchange moves ------------------------------------------------------------------
+ * kao_balance_disk ends at a move-stable state; this call goes on from there with EXCHANGES: two replicas of different partitions
+ * trade places across a broker pair.  By bytes only: no byte budget, no capacities.  Rows, sizes, S(b), admissibility, the rack rule,
+ * move_leaders, the movable slots, rank, order[], code, min_gain, dry_run, *n_moved / *bytes_moved, the lower bound and *status are
+ * those of kao_balance_disk (the bound still holds: an exchange keeps every k_p and, without move_leaders, never touches slot 0).
+ * PI is the list of the partitions with size > 0, by size descending and then index ascending; it is fixed for the call.  Rounds are
+ * synchronous and use the loads and ranks as they stand at the round's start.
+ * MOVE round: the move proposals of kao_balance_disk are computed; if there is at least one, the round is exactly a round of that call.
+ * EXCHANGE round: only when there is no move proposal.  A partition x with size > 0 takes its movable slots in ascending rank of their
+ * broker.  For slot j on a of rank q it walks c over the ranks n_brokers-1, n_brokers-2, .., q+1, lightest first.  c is skipped unless
+ * it is admissible for (x, j).  Let D = S(a) - S(c); c is skipped when D <= 0.  M is the sub-list of PI of the partitions y != x that
+ * have a movable slot k with row y[k] == c and for which a is admissible for (y, k): a is not in row y, and the rack rule holds for
+ * the replica that leaves rack_of[c].  With delta = size[x] - size[y], y PASSES iff delta > 0 and delta + min_gain < D (evaluated
+ * without overflow; min_gain is any uint64_t).  The passing members are a contiguous run of M.  It is split at g = the number of its
+ * members with 2 * size[y] > 2 * size[x] - D (signed; every term stays below 2^63): y_hi is the last passing member before the
+ * split, y_lo the first passing member at or after it; the one with the lower |2 * delta - D| is taken, a tie goes to y_lo.  The first
+ * (slot, c) with a passing y gives x's one proposal (x, j, y, k, a <-> c), key = q << 48 | (0xFFFF - code(delta)) << 32 | x.
+ * WIN: a proposal wins iff its key is the lowest of all the round's exchange proposals that touch a, of all that touch c, of all that
+ * name partition x in either role, and of all that name partition y in either role.  (A partition has several replicas that can each
+ * take a role; without the two partition words one row could be written by two winners, and its rack rule checked by neither.)  The
+ * globally lowest key wins at all four words, so every round with a proposal applies something.
+ * APPLY: winners share no broker and no partition.  For each: S(a) -= delta, S(c) += delta, row x[j] = c, row y[k] = a.  Each
+ * exchange lowers the sum of S^2 by 2 * delta * (D - delta) > 0 and leaves both loads below the old S(a): the rounds end and the peak
+ * never rises.
+ * STOP: when a round has neither kind of proposal, or after max_rounds rounds of both kinds counted together (<= 0: no limit).
+ * Without a max_rounds stop the end state is move-stable AND exchange-stable: no (x, j, a), (y, k, c) with both sides admissible has
+ * 0 < delta and delta + min_gain < S(a) - S(c).  The state at the first exchange round is kao_balance_disk's end state, so
+ * *peak_after is never above that call's; an input whose move-stable state is exchange-stable (all positive sizes equal, for one)
+ * gets that call's bytes.
+ * stats (may be NULL): [0..7] as for kao_balance_disk (rounds, applied moves and proposals count both kinds, an exchange counts 1; a
+ * round is four kernel launches), [8] exchange rounds that had a proposal, [9] exchanges applied, [10] exchange proposals, [11] the
+ * peak at the start of the first exchange round, 0 when there was none: what kao_balance_disk ends at.
+ * Checks, limits and refusals are those of kao_balance_disk, before any device is used, the rows untouched on error; and
+ * KAO_ERR_UNSUPPORTED when n_brokers * ceil(N / 64) > KAO_DISK_EXCHANGE_MAX_WORDS, N = the partitions with size > 0: the call keeps
+ * one bit per broker and position of PI (1 GiB at the limit; 1000 brokers x 100,000 partitions need 12.5 MB). */
+#define KAO_DISK_EXCHANGE_MAX_WORDS (1ull << 27)
+int kao_balance_disk_exchange(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
+                              uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *size /* [n_partitions] */,
+                              int32_t max_per_rack /* <= 0: no rack rule */, int32_t move_leaders, uint64_t min_gain,
+                              int32_t max_rounds /* <= 0: no limit */, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                              uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *status,
+                              int64_t stats[12] /* may be NULL */);
+
 /* ---- Log-dir balance inside each broker ---------------------------------------------------------------------
  * Every planner above treats a broker as one disk; a JBOD broker has several log dirs and dies on the fullest of them.  Broker b
  * owns the dirs dir_start[b] .. dir_start[b+1]-1 of ONE global dir index (CSR; n_dirs = dir_start[n_brokers]; a broker may own no

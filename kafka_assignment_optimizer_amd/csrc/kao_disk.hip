@@ -1,5 +1,6 @@
 // kao_disk.hip -- kao_balance_disk: replica moves that lower the peak of the bytes a broker stores, S(b) = sum of size[p] over the
-// rows that contain b, and kao_balance_disk_budget: the same under a budget of bytes copied (section 4n).
+// rows that contain b, and kao_balance_disk_budget: the same under a budget of bytes copied (section 4n);
+// kao_balance_disk_capacity (section 4q) and kao_balance_disk_exchange (section 4u; its text stands before its kernels below).
 // Kernels and the C entry points.
 //
 // A move takes the replica in slot j of row p from broker a to a broker c OUTSIDE the row; the slot keeps its place.  c is
@@ -63,7 +64,7 @@ constexpr int kDkThoroughBatch = 4;     // ... of THOROUGH rounds: few of them h
 constexpr int kDkHardRounds = 1 << 26;  // no descent gets here; a guard against an endless loop
 constexpr u64 kDkNoKey = ~0ull;
 constexpr int kDkGrantThreads = 1024;   // k_dk_grant: one workgroup, one rank per lane and chunk
-enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_SPENT, D_REFUSED, D_N = 16 };
+enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_SPENT, D_REFUSED, D_XCH, D_XPEAK, D_XSEEN, D_DONE, D_N = 16 };
 
 struct DkNet {   // one call; every pointer is device memory
     int P, W, B, cap, first;   // first = the lowest movable slot: 0 with move_leaders, else 1
@@ -353,6 +354,232 @@ __global__ void k_dk_apply(DkNet n, int r) {
     if (Budget) wave_sum_to(cost, &n.ctl[D_SPENT]);   // the sum of a wavefront wraps as its terms do; it adds nothing when it is 0
 }
 
+// ---- exchange rounds (kao_balance_disk_exchange) -----------------------------------------------------------------
+// Where a round has no move proposal, two replicas of different partitions trade places across a broker pair (include/kao.h has the
+// definition).  x walks the lighter brokers c lightest first; the partners y on c whose size lies in (size[x] - D + min_gain, size[x]),
+// D = S(a) - S(c), pass; of those the one whose delta = size[x] - size[y] is nearest D / 2 is taken (the neighbours of the split
+// 2 size[y] > 2 size[x] - D inside the passing run).  A proposal wins iff its key is the lowest at both brokers AND at both
+// partitions: a partition has several replicas, so two winners at four distinct brokers could otherwise write one row.
+// A type of its own: the kernels above keep their arguments.  PI (the partitions with size > 0, size descending, then index ascending)
+// is sorted by the host once; bit t & 63 of mask[b * words + (t >> 6)] is set iff the partition at position t of PI has a movable slot on
+// broker b.  k_dkx_index builds the masks from the input rows; k_dkx_apply keeps them current through rounds of BOTH kinds (a move
+// flips two bits, an exchange four; a winner alone touches the mask rows of its two brokers), so no round rebuilds them.
+struct DkNetX : DkNet {
+    int N, words;              // positions of PI; mask words per broker
+    const uint32_t *pi;        // [N] the partition at a position
+    const u64 *ps;             // [N] its size: descending
+    const uint32_t *pos;       // [P] the position of a partition (unset for size 0)
+    u64 *mask;                 // [B * words]
+    u64 *pk;                   // [2][P] minkey rows of the partitions: a partition named by two proposals, in either role, is won by one
+    uint16_t *xsrc;            // [P] what the proposer of an exchange stores beside slot[] and dest[]: a,
+    uint32_t *xpart;           // [P] the partner y,
+    uint8_t *xslot;            // [P] and y's slot k on c.  APPLY reads these, never a row another winner may write
+};
+
+__global__ void k_dkx_index(DkNetX n) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n.N) return;
+    const uint16_t *row = n.rows0 + (size_t)n.pi[t] * n.W;
+    for (int j = n.first; j < n.W; ++j) {
+        const int b = row[j];
+        if (b == KAO_NONE) break;
+        atomicOr(&n.mask[(size_t)b * n.words + (t >> 6)], 1ull << (t & 63));
+    }
+}
+
+// the first position in [lo, hi) whose size is <= lim (hi when there is none); sizes descend.  2 * size when Twice: both stay below 2^63
+template <bool Twice>
+__device__ __forceinline__ int dkx_first_le(const u64 *__restrict__ ps, int lo, int hi, long long lim) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const long long v = (long long)(Twice ? 2 * ps[mid] : ps[mid]);
+        if (v <= lim) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// the partner test of the partition at a position of c's mask: a is not in row y and the rack rule holds for the replica that leaves
+// rack(c) for rack(a).  Returns y's slot on c, -1 when y is no partner
+__device__ __forceinline__ int dkx_partner(const DkNetX &n, int y, int a, int c, int rka, int rkc) {
+    const uint16_t *row = n.rows + (size_t)y * n.W;
+    bool in_row = false;
+    int cnt = 0, k = -1;
+    for (int j = 0; j < n.W; ++j) {
+        const int b = row[j];
+        if (b == KAO_NONE) break;
+        in_row |= b == a;
+        cnt += (int)n.rack[b] == rka ? 1 : 0;
+        if (b == c && j >= n.first) k = j;
+    }
+    return !in_row && (n.cap <= 0 || rka == rkc || cnt < n.cap) ? k : -1;
+}
+
+// the first position in [from, to) set in the mask row m whose partition is a partner (upward), the last one (downward); -1 without one.
+// *k = the partner's slot
+template <bool Up>
+__device__ __forceinline__ int dkx_scan(const DkNetX &n, const u64 *__restrict__ m, int from, int to, int a, int c, int rka, int rkc, int *k) {
+    if (from >= to) return -1;
+    if (Up) {
+        for (int wd = from >> 6; wd <= (to - 1) >> 6; ++wd) {
+            u64 bits = m[wd];
+            if (wd == from >> 6) bits &= ~0ull << (from & 63);
+            while (bits) {
+                const int t = wd * 64 + __ffsll((long long)bits) - 1;
+                if (t >= to) return -1;
+                if ((*k = dkx_partner(n, (int)n.pi[t], a, c, rka, rkc)) >= 0) return t;
+                bits &= bits - 1;
+            }
+        }
+    } else {
+        for (int wd = (to - 1) >> 6; wd >= from >> 6; --wd) {
+            u64 bits = m[wd];
+            if (wd == (to - 1) >> 6) bits &= ~0ull >> (63 - ((to - 1) & 63));
+            while (bits) {
+                const int hi = 63 - __clzll((long long)bits), t = wd * 64 + hi;
+                if (t < from) return -1;
+                if ((*k = dkx_partner(n, (int)n.pi[t], a, c, rka, rkc)) >= 0) return t;
+                bits &= ~(1ull << hi);
+            }
+        }
+    }
+    return -1;
+}
+
+// the EXCHANGE proposals of round r: nothing when the round has a move proposal (*count != 0) or the call has ended (ctl[D_DONE]: a
+// round had neither kind).  One lane per partition x, the row in registers as in k_dk_propose.  Lane 0 of the grid notes the peak at
+// the first exchange round: order[0] is the heaviest broker, and no load changes in this phase.
+__global__ void k_dkx_propose(DkNetX n, int r, const uint32_t *__restrict__ count, uint32_t *__restrict__ xcount) {
+    if (n.ctl[D_DONE] != 0 || *count != 0) return;   // (uniform over the grid)
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p == 0 && n.ctl[D_XSEEN] == 0) {
+        n.ctl[D_XSEEN] = 1;
+        n.ctl[D_XPEAK] = n.load[n.order[0]];
+    }
+    bool prop = false;
+    if (p < n.P) {
+        const u64 w = n.size[p];
+        if (w) {
+            const uint16_t *src = n.rows + (size_t)p * n.W;
+            DkRow row;
+#pragma unroll
+            for (int j = 0; j < KAO_MAX_RF; ++j) {
+                const int x = j < n.W ? (int)src[j] : (int)KAO_NONE;
+                const bool held = x != KAO_NONE;
+                row.b[j] = x;
+                row.rk[j] = held ? (int)n.rack[x] : -1;
+                row.rr[j] = held ? n.rank[x] : -1;
+            }
+            const int top = dkx_first_le<false>(n.ps, (int)n.pos[p], n.N, (long long)w - 1);   // delta > 0 from here on
+            int last = -1;
+            for (int t = n.first; t < n.W && !prop; ++t) {
+                int ra_rank = n.B, a = 0, ra = 0, slot = 0;
+#pragma unroll
+                for (int j = 0; j < KAO_MAX_RF; ++j) {
+                    if (j >= n.first && row.rr[j] > last && row.rr[j] < ra_rank) { ra_rank = row.rr[j]; a = row.b[j]; ra = row.rk[j]; slot = j; }
+                }
+                if (ra_rank == n.B) break;
+                last = ra_rank;
+                const u64 sa = n.load[a];
+                int end = n.N;   // D only shrinks along the walk, and the end of the passing interval with it
+                for (int q = n.B - 1; q > ra_rank; --q) {
+                    const int c = n.order[q], rc = n.rack[c];
+                    if (!dk_admissible(row, c, rc, ra, n.cap)) continue;
+                    const u64 sc = n.load[c];
+                    if (sa <= sc) continue;
+                    const u64 D = sa - sc;
+                    if (n.min_gain >= D) break;   // nothing passes here, nor at any later (heavier) c
+                    end = dkx_first_le<false>(n.ps, top, end, (long long)w - (long long)(D - n.min_gain));   // size > size[x] - D + min_gain before it
+                    if (end <= top) break;        // the passing interval holds no position of PI: none for a smaller D either
+                    const int g = dkx_first_le<true>(n.ps, top, end, 2 * (long long)w - (long long)D);   // the split inside the passing run
+                    const u64 *m = n.mask + (size_t)c * n.words;
+                    int k_lo = -1, k_hi = -1;
+                    const int t_lo = dkx_scan<true>(n, m, g, end, a, c, ra, rc, &k_lo), t_hi = dkx_scan<false>(n, m, top, g, a, c, ra, rc, &k_hi);
+                    if (t_lo < 0 && t_hi < 0) continue;
+                    bool take_lo = t_hi < 0;
+                    if (t_lo >= 0 && t_hi >= 0) {   // |2 delta - D|: 2 delta >= D at y_lo, 2 delta < D at y_hi; a tie goes to y_lo
+                        const u64 m_lo = 2 * (w - n.ps[t_lo]) - D, m_hi = D - 2 * (w - n.ps[t_hi]);
+                        take_lo = m_lo <= m_hi;
+                    }
+                    const int ty = take_lo ? t_lo : t_hi;
+                    const uint32_t y = n.pi[ty];
+                    const u64 key = (u64)(uint32_t)ra_rank << 48 | (u64)(0xFFFFu - wave_bytes_code(w - n.ps[ty])) << 32 | (u64)(uint32_t)p;
+                    prop = true;
+                    n.key[p] = key;
+                    n.slot[p] = (uint8_t)slot;
+                    n.dest[p] = (uint16_t)c;
+                    n.xsrc[p] = (uint16_t)a;
+                    n.xpart[p] = y;
+                    n.xslot[p] = (uint8_t)(take_lo ? k_lo : k_hi);
+                    u64 *mine = n.mk + (size_t)(r & 1) * n.B, *part = n.pk + (size_t)(r & 1) * n.P;
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&mine[a], key);
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&mine[c], key);
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&part[p], key);
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&part[y], key);
+                    break;
+                }
+            }
+        }
+    }
+    lane_count_to(prop, xcount);
+}
+
+// the apply of the exchange call: whichever kind round r is.  It clears the words of round r + 1, keeps the masks current and sets
+// ctl[D_DONE] once a round has had neither kind of proposal.  A winner of an exchange reads only what its proposer stored.
+__global__ void k_dkx_apply(DkNetX n, int r, const uint32_t *__restrict__ count, const uint32_t *__restrict__ xcount) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    {
+        u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
+        for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kDkNoKey;
+        if (p < n.P) n.pk[(size_t)((r + 1) & 1) * n.P + p] = kDkNoKey;
+    }
+    const bool isx = *count == 0;   // the round's move proposals
+    if (p == 0 && isx && *xcount == 0) n.ctl[D_DONE] = 1;
+    bool won = false;
+    if (p < n.P) {
+        const u64 key = n.key[p];
+        if (key != kDkNoKey) {
+            const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
+            uint16_t *row = n.rows + (size_t)p * n.W;
+            const int slot = n.slot[p], c = n.dest[p];
+            const uint32_t px = n.pos[p];
+            const u64 bx = 1ull << (px & 63);
+            if (!isx) {
+                const int a = row[slot];   // a move: no other lane writes this row
+                won = mine[a] == key && mine[c] == key;
+                if (won) {
+                    const u64 w = n.size[p];
+                    n.load[a] -= w;
+                    n.load[c] += w;
+                    row[slot] = (uint16_t)c;
+                    n.mask[(size_t)a * n.words + (px >> 6)] &= ~bx;
+                    n.mask[(size_t)c * n.words + (px >> 6)] |= bx;
+                }
+            } else {
+                const int a = n.xsrc[p];
+                const uint32_t y = n.xpart[p];
+                const u64 *part = n.pk + (size_t)(r & 1) * n.P;
+                won = mine[a] == key && mine[c] == key && part[p] == key && part[y] == key;
+                if (won) {   // no other winner touches a, c, x or y
+                    const u64 d = n.size[p] - n.size[y];
+                    const uint32_t py = n.pos[y];
+                    const u64 by = 1ull << (py & 63);
+                    u64 *ma = n.mask + (size_t)a * n.words, *mc = n.mask + (size_t)c * n.words;
+                    n.load[a] -= d;
+                    n.load[c] += d;
+                    row[slot] = (uint16_t)c;
+                    n.rows[(size_t)y * n.W + n.xslot[p]] = (uint16_t)a;
+                    ma[px >> 6] &= ~bx;
+                    ma[py >> 6] |= by;
+                    mc[px >> 6] |= bx;
+                    mc[py >> 6] &= ~by;
+                }
+            }
+        }
+    }
+    lane_count_to(won, &n.ctl[D_MOVES]);
+    lane_count_to(won && isx, &n.ctl[D_XCH]);
+}
+
 // ---- the result ---------------------------------------------------------------------------------------------------------------------
 // one lane per partition: the brokers of the final row that the input row did not hold, their bytes, the rows that changed
 __global__ void k_dk_finish(DkNet n) {
@@ -448,8 +675,11 @@ bool frac_integral(const DkFrac &peak, const uint64_t *cap, int B, uint64_t tota
 }
 
 // the entry points: Budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]; Cap (cap != NULL) is
-// the descent by utilisation: the rank by utilisation, the capacity form of the test, THOROUGH rounds, fractions as outputs, stats[10]
-template <bool Budget, bool Cap>
+// the descent by utilisation: the rank by utilisation, the capacity form of the test, THOROUGH rounds, fractions as outputs, stats[10];
+// X (kao_balance_disk_exchange, by bytes and without a budget) adds PI, the masks and the partition words, makes a round RANK, PROPOSE,
+// the exchange PROPOSE (which returns at once in a round with a move proposal, and after the call has ended) and k_dkx_apply, and
+// fills stats[8..11]
+template <bool Budget, bool Cap, bool X = false>
 int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
                  const uint64_t *size, const uint64_t *cap, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes,
                  int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
@@ -466,21 +696,42 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
             cap_max = std::max(cap_max, cap[b]);
         }
     }
+    static_assert(!X || (!Budget && !Cap), "exchange rounds are by bytes, without a budget");
+    std::vector<uint32_t> h_pi, h_pos;   // X: PI, and the position of a partition in it
+    std::vector<uint64_t> h_ps;
+    if (X) {
+        for (int32_t p = 0; p < n_partitions; ++p)
+            if (size[p]) h_pi.push_back((uint32_t)p);
+        if ((uint64_t)n_brokers * ((h_pi.size() + 63) / 64) > KAO_DISK_EXCHANGE_MAX_WORDS)
+            return fail(KAO_ERR_UNSUPPORTED, fn + "n_brokers * ceil(N / 64) is above 2^27 mask words (N = the partitions with size > 0)");
+        std::sort(h_pi.begin(), h_pi.end(), [&](uint32_t x, uint32_t y) { return size[x] != size[y] ? size[x] > size[y] : x < y; });
+        h_pos.assign((size_t)n_partitions, 0);
+        h_ps.resize(h_pi.size());
+        for (size_t t = 0; t < h_pi.size(); ++t) {
+            h_pos[h_pi[t]] = (uint32_t)t;
+            h_ps[t] = size[h_pi[t]];
+        }
+    }
     if ((rc = require_init())) return rc;
-    const int B = n_brokers, P = n_partitions, W = width, PW = P * W;
+    const int B = n_brokers, P = n_partitions, W = width, PW = P * W, N = (int)h_pi.size(), words = (N + 63) / 64;
 
-    // one arena: ctl u64[D_N] | count u32[kDkBatch] | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] |
+    // one arena: ctl u64[D_N] | count u32[kDkBatch] (2 kDkBatch with X: the exchange proposals behind the moves') | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] |
     //            capacity u64[B] | rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B]
     Carve cv;
-    const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
+    const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>((X ? 2 : 1) * kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
                  o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_cap = cv.take<u64>(Cap ? B : 0), o_rank = cv.take<int32_t>(B),
                  o_order = cv.take<int32_t>(B),
                  o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW), o_rows0 = cv.take<uint16_t>(PW),
                  o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B), o_grant = cv.take<uint8_t>(Budget ? B : 0);
+    // X: pk u64[2P] (all ones) | mask u64[B words] (zeroed) | ps u64[N] | pi u32[N] | pos, xpart u32[P] | xsrc u16[P] | xslot u8[P]
+    const size_t o_pk = cv.take<u64>(X ? 2 * (size_t)P : 0), o_mask = cv.take<u64>(X ? (size_t)B * words : 0), o_ps = cv.take<u64>(N), o_pi = cv.take<uint32_t>(N),
+                 o_pos = cv.take<uint32_t>(X ? P : 0), o_xpart = cv.take<uint32_t>(X ? P : 0), o_xsrc = cv.take<uint16_t>(X ? P : 0),
+                 o_xslot = cv.take<uint8_t>(X ? P : 0);
     CallBufs m;
     if ((rc = m.open(cv.end()))) return rc;
     hipStream_t st = m.stream;
     uint32_t *d_cnt = m.at<uint32_t>(o_cnt);
+    [[maybe_unused]] uint32_t *d_xcnt = d_cnt + kDkBatch;
     u64 *d_fixed = m.at<u64>(o_fixed), *d_load0 = m.at<u64>(o_load0);
     uint16_t *d_rows = m.at<uint16_t>(o_rows), *d_rows0 = m.at<uint16_t>(o_rows0);
     DkNet n;
@@ -505,7 +756,24 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
         n.capacity = nullptr;
     }
     const unsigned pblocks = grid_for(P, kDkThreads), bblocks = grid_for(B, kDkThreads);
-    int64_t launches = 0, rounds = 0, props = 0, thorough_rounds = 0;
+    int64_t launches = 0, rounds = 0, props = 0, thorough_rounds = 0, x_rounds = 0, x_props = 0;
+    [[maybe_unused]] DkNetX nx;
+    if constexpr (X) {
+        static_cast<DkNet &>(nx) = n;
+        nx.N = N; nx.words = words; nx.pi = m.at<uint32_t>(o_pi); nx.ps = m.at<u64>(o_ps); nx.pos = m.at<uint32_t>(o_pos); nx.mask = m.at<u64>(o_mask);
+        nx.pk = m.at<u64>(o_pk); nx.xsrc = m.at<uint16_t>(o_xsrc); nx.xpart = m.at<uint32_t>(o_xpart); nx.xslot = m.at<uint8_t>(o_xslot);
+        if (P) {
+            HIP_TRY(hipMemsetAsync(nx.pk, 0xFF, 2 * (size_t)P * sizeof(u64), st));
+            HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pos), h_pos.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        }
+        if (N) {
+            HIP_TRY(hipMemsetAsync(nx.mask, 0, (size_t)B * words * sizeof(u64), st));
+            HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pi), h_pi.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(m.at<u64>(o_ps), h_ps.data(), (size_t)N * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            k_dkx_index<<<grid_for(N, kDkThreads), kDkThreads, 0, st>>>(nx);
+            ++launches;
+        }
+    }
     bool more = false, open = false;   // open: the budget stopped the descent
     if (P) {
         k_dk_init<<<pblocks, kDkThreads, 0, st>>>(n, d_fixed);
@@ -517,7 +785,7 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
     const auto rank = [&] { k_dk_rank<Cap><<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.capacity, n.rank, n.order); };
 
     if (P) {
-        uint32_t cnt[kDkBatch];
+        uint32_t cnt[(X ? 2 : 1) * kDkBatch];
         bool thorough = false;   // by utilisation: a FAST round had no proposal
         for (int r = 0, done = 0; !done;) {
             if (r >= kDkHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
@@ -528,20 +796,37 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
                 rank();
                 dk_propose<Budget, Cap>(n, Cap, pblocks, st, r, d_cnt);
                 launches += 2;
+                if constexpr (X) {
+                    k_dkx_propose<<<pblocks, kDkThreads, 0, st>>>(nx, r, d_cnt, d_xcnt);
+                    ++launches;
+                }
             }
             for (int i = 0; i < nb; ++i) {
                 rank();
                 dk_propose<Budget, Cap>(n, thorough, pblocks, st, r + i, d_cnt + i);
                 if (Budget) k_dk_grant<<<1, kDkGrantThreads, 0, st>>>(n, r + i);
-                k_dk_apply<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r + i);
-                launches += Budget ? 4 : 3;
+                if constexpr (X) {
+                    k_dkx_propose<<<pblocks, kDkThreads, 0, st>>>(nx, r + i, d_cnt + i, d_xcnt + i);
+                    k_dkx_apply<<<pblocks, kDkThreads, 0, st>>>(nx, r + i, d_cnt + i, d_xcnt + i);
+                } else {
+                    k_dk_apply<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r + i);
+                }
+                launches += Budget || X ? 4 : 3;
             }
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if (nb == 0) { more = cnt[0] != 0; break; }
+            if (nb == 0) { more = cnt[0] != 0 || (X && cnt[X ? kDkBatch : 0] != 0); break; }
             int ran = 0;   // the rounds of the batch before the first one without a proposal; the ones after it changed nothing
-            while (ran < nb && cnt[ran] != 0) props += cnt[ran++];
+            if constexpr (X) {   // a round without a move proposal is an exchange round
+                for (; ran < nb && (cnt[ran] != 0 || cnt[kDkBatch + ran] != 0); ++ran) {
+                    props += cnt[ran] + cnt[kDkBatch + ran];
+                    x_props += cnt[kDkBatch + ran];
+                    x_rounds += cnt[ran] == 0;
+                }
+            } else {
+                while (ran < nb && cnt[ran] != 0) props += cnt[ran++];
+            }
             rounds += ran;
             if (thorough) thorough_rounds += ran;
             if (ran < nb && Cap && !thorough) {   // the first empty FAST round: THOROUGH from here on.  It and the empty rounds behind it left
@@ -610,6 +895,7 @@ int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, cons
         if (Budget) { stats[8] = (int64_t)ctl[D_REFUSED]; stats[9] = open ? 1 : 0; }
         else if (Cap) stats[8] = stats[9] = 0;
         if (Cap) stats[10] = thorough_rounds;
+        if (X) { stats[8] = x_rounds; stats[9] = (int64_t)ctl[D_XCH]; stats[10] = x_props; stats[11] = (int64_t)ctl[D_XPEAK]; }
     }
     return KAO_OK;
 }
@@ -643,4 +929,13 @@ extern "C" int kao_balance_disk_capacity(int32_t n_brokers, int32_t n_racks, con
                                          max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
     return balance_disk<true, true>(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, cap, max_per_rack, move_leaders, min_gain, max_bytes,
                                     max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
+}
+
+extern "C" int kao_balance_disk_exchange(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                                         const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, int32_t max_rounds,
+                                         int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                                         uint64_t *lower_bound, int32_t *status, int64_t stats[12]) {
+    return balance_disk<false, false, true>("kao_balance_disk_exchange: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack,
+                                            move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound,
+                                            status, stats);
 }

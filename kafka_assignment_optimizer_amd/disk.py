@@ -14,6 +14,9 @@ more than what is left of N is no candidate, and of a round's winners the heavie
 --capacities FILE|id:bytes,id:bytes (with --default-capacity N for the brokers it does not name) gives every broker its disk size
 and lowers the peak UTILISATION S(b) / capacity(b) instead (kao_balance_disk_capacity, section 4q): the answer for a cluster whose
 brokers do not have equal disks.  The report line then ends in the three ratios in parts per million and the thorough rounds.
+--exchange goes on from the move-stable state with exchanges: two replicas of different partitions trade places across a broker pair
+(kao_balance_disk_exchange, section 4u).  By bytes only: it is refused together with --max-bytes, --capacities and
+--default-capacity.  The report line then ends in the peak the moves alone reach and the exchange counts.
 """
 from __future__ import annotations
 
@@ -35,6 +38,7 @@ from .solver import STATUS_NAMES, _check
 STAT_KEYS = ("rounds", "moves", "proposals", "launches", "rows_changed", "stopped_by_max_rounds", "bound_term", "brokers_changed")
 BUDGET_STAT_KEYS = STAT_KEYS + ("refused", "budget_bound")   # kao_balance_disk_budget
 CAPACITY_STAT_KEYS = BUDGET_STAT_KEYS + ("thorough_rounds",)   # kao_balance_disk_capacity
+EXCHANGE_STAT_KEYS = STAT_KEYS + ("exchange_rounds", "exchanges", "exchange_proposals", "peak_of_moves")   # kao_balance_disk_exchange (section 4u)
 BOUND_TERMS = ("largest_partition", "mean_load", "fixed_leaders", "integrality")
 
 
@@ -54,6 +58,11 @@ class DiskResult:
     peak_before_capacity: Optional[int] = None
     peak_after_capacity: Optional[int] = None
     lower_bound_den: Optional[int] = None
+    # with exchange=True (kao_balance_disk_exchange): stats is int64[12] (EXCHANGE_STAT_KEYS) and these are stats[8..11]; None otherwise
+    exchange_rounds: Optional[int] = None
+    exchanges: Optional[int] = None
+    exchange_proposals: Optional[int] = None
+    peak_of_moves: Optional[int] = None      # the peak at the start of the first exchange round (what kao_balance_disk ends at), 0 without one
 
 
 @dataclass
@@ -107,10 +116,14 @@ def capacity_of(broker_ids: Sequence[int], capacities: Dict[int, object], defaul
 
 
 def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0,
-                        max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None) -> DiskResult:
+                        max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False) -> DiskResult:
     """kao_balance_disk on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); size[p] is the bytes of one replica of
     row p.  With max_bytes (0..2^64-1) it is kao_balance_disk_budget: the moves copy at most that many bytes.  With capacity (one
-    value >= 1 per broker index) it is kao_balance_disk_capacity: the peak of S(b) / capacity[b] is what the moves lower."""
+    value >= 1 per broker index) it is kao_balance_disk_capacity: the peak of S(b) / capacity[b] is what the moves lower.  With
+    exchange=True it is kao_balance_disk_exchange: exchanges go on from the move-stable state (by bytes only: a ValueError together
+    with max_bytes or capacity)."""
+    if exchange and (max_bytes is not None or capacity is not None):
+        raise ValueError("exchange=True works by bytes only: not together with max_bytes or capacity")
     if max_bytes is not None:
         max_bytes = _budget(max_bytes)
     if capacity is not None:
@@ -119,19 +132,23 @@ def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_p
     r, flat, P, W = dense_rows(rows)
     rk = _rack_buffer(rack_of, n_brokers)
     sbuf = weight_buffer(size, P, min_gain)
-    stats = np.zeros(8 if max_bytes is None else 10, dtype=np.int64)
+    stats = np.zeros(12 if exchange else 8 if max_bytes is None else 10, dtype=np.int64)
     n, status = C.c_int32(0), C.c_int32(0)
     moved, before, after, bound = (C.c_uint64(0) for _ in range(4))
     head = [int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
             sbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_per_rack), int(bool(move_leaders)), int(min_gain)]
     tail = [int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), C.byref(before), C.byref(after), C.byref(bound), C.byref(status),
             stats.ctypes.data_as(C.POINTER(C.c_int64))]
-    if max_bytes is None:
+    if exchange:
+        _check(_ffi.load().kao_balance_disk_exchange(*head, *tail), "kao_balance_disk_exchange")
+    elif max_bytes is None:
         _check(_ffi.load().kao_balance_disk(*head, *tail), "kao_balance_disk")
     else:
         _check(_ffi.load().kao_balance_disk_budget(*head, max_bytes, *tail), "kao_balance_disk_budget")
     return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
-                      lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes)
+                      lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes,
+                      **(dict(exchange_rounds=int(stats[8]), exchanges=int(stats[9]), exchange_proposals=int(stats[10]), peak_of_moves=int(stats[11]))
+                         if exchange else {}))
 
 
 def _balance_disk_capacity(rows, n_brokers, rack_of, n_racks, size, cbuf, max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes) -> DiskResult:
@@ -159,11 +176,12 @@ def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int
 
 
 def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0,
-               dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None) -> DiskPlan:
+               dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False) -> DiskPlan:
     """kao_balance_disk on a FailoverInput, size[p] per row of it; the entries are the rows that changed (none with dry_run).  With
-    max_bytes it is kao_balance_disk_budget; with capacity (per broker index of fi) kao_balance_disk_capacity."""
+    max_bytes it is kao_balance_disk_budget; with capacity (per broker index of fi) kao_balance_disk_capacity; with exchange
+    kao_balance_disk_exchange."""
     res = balance_disk_arrays(fi.rows, len(fi.broker_ids), fi.rack_of, len(fi.rack_names), size, max_per_rack, move_leaders, min_gain, max_rounds,
-                              dry_run, max_bytes, capacity)
+                              dry_run, max_bytes, capacity, exchange)
     changed = np.nonzero((res.rows != fi.rows).any(axis=1))[0]
     entries = [(fi.keys[p][0], fi.keys[p][1], [int(fi.broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
     return DiskPlan(result=res, input=fi, size=np.asarray(size, dtype=np.uint64), entries=entries)
@@ -171,13 +189,16 @@ def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: boo
 
 def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, default_size: Optional[int] = None, max_per_rack: int = 0,
                  move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None,
-                 capacity=None, default_capacity: Optional[int] = None) -> DiskPlan:
+                 capacity=None, default_capacity: Optional[int] = None, exchange: bool = False) -> DiskPlan:
     """kao_balance_disk on a reassignment document with `broker_list` and `racks` ({broker id: rack name}).  `sizes` is
     {(topic, partition): bytes}, or a kafka-log-dirs / sizes document or text (waves.parse_sizes).  plan.document is the
     reassignment document of the changed rows.  With max_bytes the moves copy at most that many bytes (kao_balance_disk_budget).
     With capacity, a {broker id: bytes} mapping (default_capacity for the brokers it does not name) or an array in the order of
-    `broker_list`, the moves lower the peak utilisation (kao_balance_disk_capacity)."""
+    `broker_list`, the moves lower the peak utilisation (kao_balance_disk_capacity).  With exchange=True exchanges go on from the
+    move-stable state (kao_balance_disk_exchange; a ValueError together with max_bytes or capacity)."""
     from .waves import parse_sizes
+    if exchange and (max_bytes is not None or capacity is not None):
+        raise ValueError("exchange=True works by bytes only: not together with max_bytes or capacity")
     if max_bytes is not None:
         max_bytes = _budget(max_bytes)
     fi = parse_current(doc, broker_list, racks)
@@ -185,7 +206,7 @@ def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, d
         capacity = capacity_of(fi.broker_ids, capacity, default_capacity)
     if not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
         sizes = parse_sizes(sizes)
-    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes, capacity)
+    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes, capacity, exchange)
 
 
 def report_lines(plan: DiskPlan) -> List[str]:
@@ -198,7 +219,9 @@ def report_lines(plan: DiskPlan) -> List[str]:
             + ("" if res.max_bytes is None else f" max_bytes={res.max_bytes} bytes_left={res.max_bytes - res.bytes_moved} refused={s[8]} budget_bound={s[9]}")
             + ("" if res.lower_bound_den is None else f" peak_before_ppm={res.peak_before * 10 ** 6 // res.peak_before_capacity} "
                f"peak_after_ppm={res.peak_after * 10 ** 6 // res.peak_after_capacity} lower_bound_ppm={res.lower_bound * 10 ** 6 // res.lower_bound_den} "
-               f"thorough_rounds={s[10]}")]
+               f"thorough_rounds={s[10]}")
+            + ("" if res.exchanges is None else f" peak_of_moves={res.peak_of_moves} exchange_rounds={res.exchange_rounds} exchanges={res.exchanges} "
+               f"exchange_proposals={res.exchange_proposals}")]
 
 
 def _capacities(arg: str) -> dict:
@@ -226,12 +249,16 @@ def main(argv=None) -> int:
     ap.add_argument("--max-bytes", default=None, help="copy at most N bytes in all (N, or N with K/M/G/T)")
     ap.add_argument("--capacities", default=None, help='{"<brokerId>": bytes} JSON file or id:bytes,id:bytes: lower the peak utilisation')
     ap.add_argument("--default-capacity", default=None, help="bytes of disk of the brokers --capacities does not name")
+    ap.add_argument("--exchange", action="store_true", help="go on from the move-stable state with exchanges of two replicas across a broker pair "
+                    "(not with --max-bytes, --capacities or --default-capacity)")
     ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     min_gain, default_size, max_bytes, capacity = 0, None, None, None
+    if a.exchange and (a.max_bytes is not None or a.capacities is not None or a.default_capacity is not None):
+        ap.error("--exchange works by bytes only: not together with --max-bytes, --capacities or --default-capacity")
     try:
         if a.capacities is not None or a.default_capacity is not None:   # a broker without a capacity is a usage error
             default_capacity = None if a.default_capacity is None else parse_bytes(a.default_capacity)
@@ -258,7 +285,7 @@ def main(argv=None) -> int:
             size = sizes_of(fi.keys, parse_sizes(f.read()), default_size)
         from .solver import init
         init(a.device)
-        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes, capacity)
+        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes, capacity, a.exchange)
         if a.report:
             for line in report_lines(plan):
                 print(line, file=sys.stderr)

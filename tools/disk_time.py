@@ -12,7 +12,13 @@ of every repeat, and --write puts them into profiles/disk_budget_time.txt.
 brokers have 4 * 2^36 bytes of disk, odd ones 2^36.  --capacity equal gives every broker 2^36 (the byte planner's plan: the cost of
 the 128-bit rank and test).  The lines gain the peaks and the bound as fractions and in parts per million, the mean utilisation,
 the thorough rounds and, for the same instance, the peak utilisation that kao_balance_disk's plan reaches; --write puts them into
-profiles/disk_capacity_time.txt."""
+profiles/disk_capacity_time.txt.
+--exchange times kao_balance_disk and kao_balance_disk_exchange in one process, case by case, each the median
+of --reps after a warm-up, with dry_run.  The cases `small` (12 brokers x 1,200 partitions, 3 racks, max_per_rack 1) and `mid` (100 x
+10,000, 10 racks, max_per_rack 1) of tests/disk_ref.py's log-normal family may be named in --cases beside the two above.  A line
+carries, as plain call -> this call: peak / bound, bytes moved, rounds (move + exchange), launches and wall time, then the exchanges
+and the cost of one exchange round against one move round (the extra wall time over the exchange rounds; the plain call's wall time
+over its rounds).  --write appends the lines to profiles/disk_x_time.txt.  --max-rounds N caps the rounds of both calls."""
 import argparse
 import json
 import os
@@ -32,6 +38,8 @@ def main():
     ap.add_argument("--keep-leaders", action="store_true")
     ap.add_argument("--max-bytes-pct", default=None, help="CSV of budgets in percent of the bytes stored, or `none`: times kao_balance_disk_budget")
     ap.add_argument("--capacity", default=None, choices=["4:1", "equal"], help="times kao_balance_disk_capacity with this capacity vector")
+    ap.add_argument("--exchange", action="store_true", help="times kao_balance_disk and kao_balance_disk_exchange side by side")
+    ap.add_argument("--max-rounds", type=int, default=0)
     ap.add_argument("--write", action="store_true", help="write the lines to profiles/disk_time.txt (disk_budget_time.txt with --max-bytes-pct) as well")
     a = ap.parse_args()
     import numpy as np
@@ -44,13 +52,13 @@ def main():
         rng = np.random.default_rng(seed)
         return np.maximum(1, np.round(np.exp(rng.normal(np.log(2.0 ** 20), sigma, P)))).astype(np.int64)
 
-    def timed(rows, B, rack_of, R, size, cap, max_bytes, capacity=None):
-        args = (rows, B, rack_of, R, size, cap, not a.keep_leaders)
-        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity)   # warm-up
+    def timed(rows, B, rack_of, R, size, cap, max_bytes, capacity=None, exchange=False):
+        args = (rows, B, rack_of, R, size, cap, not a.keep_leaders, 0, a.max_rounds)
+        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange)   # warm-up
         ms = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity)
+            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange)
             ms.append(round(1e3 * (time.perf_counter() - t0), 3))
         return res, ms
 
@@ -62,11 +70,36 @@ def main():
     if "large" in a.cases:
         rows, B, _, _ = lr.large_instance()
         cases["large"] = (rows, B, (np.arange(B) % 10).astype(np.uint8), 10, 1)
+    import disk_ref as dr
+    for name, shape in (("small", (12, 3, 1200, 3)), ("mid", (100, 10, 10000, 3))):
+        if name in a.cases.split(","):
+            c = dr.lognormal_case(*shape, 0.7, 7, zeros=0.0)   # (the sizes are drawn per sigma below)
+            cases[name] = (c["rows"], shape[0], c["rack_of"].astype(np.uint8), shape[1], 1)
     lines = []
     for name, (rows, B, rack_of, R, cap) in cases.items():
         for sigma in (float(s) for s in a.sigmas.split(",")):
             size = sizes(len(rows), sigma, 11)
             total = int((size[:, None] * (rows != 0xFFFF)).sum())
+            if a.exchange:
+                plain, pms = timed(rows, B, rack_of, R, size, cap, None)
+                res, xms = timed(rows, B, rack_of, R, size, cap, None, exchange=True)
+                pm, xm = float(np.median(pms)), float(np.median(xms))
+                lb = max(res.lower_bound, 1)
+                line = {"workload": name, "sigma": sigma, "brokers": B, "racks": R, "partitions": len(rows), "max_per_rack": cap, "move_leaders": not a.keep_leaders,
+                        "max_rounds": a.max_rounds, "lower_bound": res.lower_bound, "peak_before": res.peak_before,
+                        "peak_over_bound": [round(plain.peak_after / lb, 7), round(res.peak_after / lb, 7)], "peak_after": [plain.peak_after, res.peak_after],
+                        "peak_of_moves": res.peak_of_moves, "bytes_moved": [plain.bytes_moved, res.bytes_moved], "bytes_total": total,
+                        "rounds": [int(plain.stats[0]), int(res.stats[0])], "move_rounds": int(res.stats[0] - res.stats[8]), "exchange_rounds": res.exchange_rounds,
+                        "exchanges": res.exchanges, "exchange_proposals": res.exchange_proposals, "launches": [int(plain.stats[3]), int(res.stats[3])],
+                        "stopped_by_max_rounds": [int(plain.stats[5]), int(res.stats[5])], "wall_ms_median": [round(pm, 3), round(xm, 3)], "wall_ms": [pms, xms],
+                        "ms_per_move_round": round(pm / max(int(plain.stats[0]), 1), 4),
+                        "ms_per_exchange_round": round((xm - pm) / max(res.exchange_rounds, 1), 4), "changes_nothing": res.exchanges == 0}
+                lines.append(json.dumps(line))
+                print(lines[-1], flush=True)
+                if a.write:
+                    with open(os.path.join(ROOT, "profiles", "disk_x_time.txt"), "a") as f:
+                        f.write(lines[-1] + "\n")
+                continue
             for pct in [None] if a.max_bytes_pct is None else a.max_bytes_pct.split(","):   # None: kao_balance_disk
                 max_bytes = None if pct is None else 2 ** 64 - 1 if pct == "none" else int(total * float(pct) / 100)
                 capacity = None if a.capacity is None else np.where((np.arange(B) % 2 == 0) & (a.capacity == "4:1"), 4, 1).astype(np.int64) * 2 ** 36
@@ -98,7 +131,7 @@ def main():
                     line["wall_ms"] = ms
                 lines.append(json.dumps(line))
                 print(lines[-1], flush=True)
-    if a.write:
+    if a.write and not a.exchange:
         name = "disk_capacity_time.txt" if a.capacity is not None else "disk_time.txt" if a.max_bytes_pct is None else "disk_budget_time.txt"
         with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write("\n".join(lines) + "\n")
