@@ -51,6 +51,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kao_host.h"
@@ -141,6 +142,20 @@ struct DkRow {
     int b[KAO_MAX_RF], rk[KAO_MAX_RF], rr[KAO_MAX_RF];
 };
 
+__device__ __forceinline__ DkRow dk_load_row(const DkNet &n, int p) {
+    const uint16_t *src = n.rows + (size_t)p * n.W;
+    DkRow row;
+#pragma unroll
+    for (int j = 0; j < KAO_MAX_RF; ++j) {
+        const int x = j < n.W ? (int)src[j] : (int)KAO_NONE;
+        const bool held = x != KAO_NONE;
+        row.b[j] = x;
+        row.rk[j] = held ? (int)n.rack[x] : -1;
+        row.rr[j] = held ? n.rank[x] : -1;
+    }
+    return row;
+}
+
 // c is admissible for a replica that leaves rack ra: not in the row; no rack rule, the same rack, or room in rack(c)
 __device__ __forceinline__ bool dk_admissible(const DkRow &row, int c, int rc, int ra, int cap) {
     bool in_row = false;
@@ -173,17 +188,6 @@ __device__ __forceinline__ bool dk_home(const DkHome &h, int c) {   // c < KAO_N
     return in;
 }
 
-// the first admissible broker among the ranks hi, hi - 1, .., lo; -1 when there is none.  Under a budget the broker must be
-// affordable too: `free` (the size fits what is left, or the replica is a fresh copy), or a broker of the input row
-template <bool Budget>
-__device__ __forceinline__ int dk_first(const DkNet &n, const DkRow &row, const DkHome &home, bool free, int hi, int lo, int ra) {
-    for (int q = hi; q >= lo; --q) {
-        const int c = n.order[q];
-        if (dk_admissible(row, c, n.rack[c], ra, n.cap) && (!Budget || free || dk_home(home, c))) return c;
-    }
-    return -1;
-}
-
 // the gain test of a move a -> c.  By bytes: descent_gains.  By utilisation: (S(c) + w + min_gain) * cap(a) < S(a) * cap(c); S(c) + w
 // stays below 2^63, and a sum that min_gain takes past 2^64 does not pass
 template <bool Cap>
@@ -194,12 +198,14 @@ __device__ __forceinline__ bool dk_gains(const DkNet &n, u64 sa, u64 ca, int c, 
     return (u128)left * ca < (u128)sa * n.capacity[c];
 }
 
-// THOROUGH: the first admissible (and affordable) broker among the ranks hi, hi - 1, .., lo that passes the gain test; -1 when none does
-template <bool Budget>
-__device__ __forceinline__ int dk_first_gain(const DkNet &n, const DkRow &row, const DkHome &home, bool free, int hi, int lo, int ra, u64 sa, u64 ca, u64 w) {
+// the first admissible broker among the ranks hi, hi - 1, .., lo; -1 when there is none.  Under a budget the broker must be
+// affordable too: `free` (the size fits what is left, or the replica is a fresh copy), or a broker of the input row.  Gain (THOROUGH):
+// it must pass the gain test by utilisation as well
+template <bool Budget, bool Gain>
+__device__ __forceinline__ int dk_walk(const DkNet &n, const DkRow &row, const DkHome &home, bool free, int hi, int lo, int ra, u64 sa = 0, u64 ca = 0, u64 w = 0) {
     for (int q = hi; q >= lo; --q) {
         const int c = n.order[q];
-        if (dk_admissible(row, c, n.rack[c], ra, n.cap) && (!Budget || free || dk_home(home, c)) && dk_gains<true>(n, sa, ca, c, w)) return c;
+        if (dk_admissible(row, c, n.rack[c], ra, n.cap) && (!Budget || free || dk_home(home, c)) && (!Gain || dk_gains<true>(n, sa, ca, c, w))) return c;
     }
     return -1;
 }
@@ -212,16 +218,7 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
         u64 key = kDkNoKey;
         const u64 w = n.size[p];
         if (w) {
-            const uint16_t *src = n.rows + (size_t)p * n.W;
-            DkRow row;
-#pragma unroll
-            for (int j = 0; j < KAO_MAX_RF; ++j) {
-                const int x = j < n.W ? (int)src[j] : (int)KAO_NONE;
-                const bool held = x != KAO_NONE;
-                row.b[j] = x;
-                row.rk[j] = held ? (int)n.rack[x] : -1;
-                row.rr[j] = held ? n.rank[x] : -1;
-            }
+            const DkRow row = dk_load_row(n, p);
             DkHome home;
             bool fits = true;   // the size fits what is left of the budget: tested first, so the home compares run only when it is nearly spent
             if (Budget) {
@@ -242,11 +239,11 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
                 const u64 ca = Cap ? n.capacity[a] : 0;
                 int c;
                 if (Thorough) {
-                    c = dk_first_gain<Budget>(n, row, home, free, n.B - 1, ra_rank + 1, ra, sa, ca, w);
+                    c = dk_walk<Budget, true>(n, row, home, free, n.B - 1, ra_rank + 1, ra, sa, ca, w);
                 } else {
-                    c = dk_first<Budget>(n, row, home, free, n.B - 1 - ra_rank, ra_rank + 1, ra);
+                    c = dk_walk<Budget, false>(n, row, home, free, n.B - 1 - ra_rank, ra_rank + 1, ra);
                     if (c < 0 || !dk_gains<Cap>(n, sa, ca, c, w)) {
-                        c = dk_first<Budget>(n, row, home, free, n.B - 1, n.B - ra_rank, ra);
+                        c = dk_walk<Budget, false>(n, row, home, free, n.B - 1, n.B - ra_rank, ra);
                         if (c >= 0 && !dk_gains<Cap>(n, sa, ca, c, w)) c = -1;
                     }
                 }
@@ -321,39 +318,6 @@ __global__ __launch_bounds__(kDkGrantThreads) void k_dk_grant(DkNet n, int r) {
     }
 }
 
-template <bool Budget>
-__global__ void k_dk_apply(DkNet n, int r) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    {   // the row of round r + 1 was last read by the apply of round r - 1
-        u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
-        for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kDkNoKey;
-    }
-    bool won = false;
-    u64 cost = 0;   // under a budget: +size, 0 or -size (wrapping)
-    if (p < n.P) {
-        const u64 key = n.key[p];
-        if (key != kDkNoKey) {
-            uint16_t *row = n.rows + (size_t)p * n.W;
-            const int slot = n.slot[p], a = row[slot], c = n.dest[p];
-            const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
-            won = mine[a] == key && mine[c] == key;
-            if (Budget) won = won && n.grant[a] != 0;   // grant[] was settled from the spend before this kernel, which changes it
-            if (won) {   // no other winner touches a or c
-                const u64 w = n.size[p];
-                if (Budget) {
-                    const DkHome home = dk_home_row(n, p);
-                    cost = (dk_home(home, c) ? 0 : w) - (dk_home(home, a) ? 0 : w);
-                }
-                n.load[a] -= w;
-                n.load[c] += w;
-                row[slot] = (uint16_t)c;
-            }
-        }
-    }
-    lane_count_to(won, &n.ctl[D_MOVES]);
-    if (Budget) wave_sum_to(cost, &n.ctl[D_SPENT]);   // the sum of a wavefront wraps as its terms do; it adds nothing when it is 0
-}
-
 // ---- exchange rounds (kao_balance_disk_exchange) -----------------------------------------------------------------
 // Where a round has no move proposal, two replicas of different partitions trade places across a broker pair (include/kao.h has the
 // definition).  x walks the lighter brokers c lightest first; the partners y on c whose size lies in (size[x] - D + min_gain, size[x]),
@@ -362,7 +326,7 @@ __global__ void k_dk_apply(DkNet n, int r) {
 // partitions: a partition has several replicas, so two winners at four distinct brokers could otherwise write one row.
 // A type of its own: the kernels above keep their arguments.  PI (the partitions with size > 0, size descending, then index ascending)
 // is sorted by the host once; bit t & 63 of mask[b * words + (t >> 6)] is set iff the partition at position t of PI has a movable slot on
-// broker b.  k_dkx_index builds the masks from the input rows; k_dkx_apply keeps them current through rounds of BOTH kinds (a move
+// broker b.  k_dkx_index builds the masks from the input rows; k_dk_apply<false, true> keeps them current through rounds of BOTH kinds (a move
 // flips two bits, an exchange four; a winner alone touches the mask rows of its two brokers), so no round rebuilds them.
 struct DkNetX : DkNet {
     int N, words;              // positions of PI; mask words per broker
@@ -459,16 +423,7 @@ __global__ void k_dkx_propose(DkNetX n, int r, const uint32_t *__restrict__ coun
     if (p < n.P) {
         const u64 w = n.size[p];
         if (w) {
-            const uint16_t *src = n.rows + (size_t)p * n.W;
-            DkRow row;
-#pragma unroll
-            for (int j = 0; j < KAO_MAX_RF; ++j) {
-                const int x = j < n.W ? (int)src[j] : (int)KAO_NONE;
-                const bool held = x != KAO_NONE;
-                row.b[j] = x;
-                row.rk[j] = held ? (int)n.rack[x] : -1;
-                row.rr[j] = held ? n.rank[x] : -1;
-            }
+            const DkRow row = dk_load_row(n, p);
             const int top = dkx_first_le<false>(n.ps, (int)n.pos[p], n.N, (long long)w - 1);   // delta > 0 from here on
             int last = -1;
             for (int t = n.first; t < n.W && !prop; ++t) {
@@ -523,50 +478,75 @@ __global__ void k_dkx_propose(DkNetX n, int r, const uint32_t *__restrict__ coun
     lane_count_to(prop, xcount);
 }
 
-// the apply of the exchange call: whichever kind round r is.  It clears the words of round r + 1, keeps the masks current and sets
-// ctl[D_DONE] once a round has had neither kind of proposal.  A winner of an exchange reads only what its proposer stored.
-__global__ void k_dkx_apply(DkNetX n, int r, const uint32_t *__restrict__ count, const uint32_t *__restrict__ xcount) {
+// the move that lane p proposed with `key`, if it won the round (mine = the round's minkey row): the lowest key at both of its
+// brokers and, under a budget, granted.  No other winner touches a or c, and no other lane writes this row: plain stores.  The exchange
+// call keeps its masks current (a move flips two bits).  *cost, under a budget: +size, 0 or -size (wrapping)
+template <bool Budget, bool X>
+__device__ __forceinline__ bool dk_apply_move(const std::conditional_t<X, DkNetX, DkNet> &n, int p, u64 key, const u64 *mine, u64 *cost) {
+    uint16_t *row = n.rows + (size_t)p * n.W;
+    const int slot = n.slot[p], a = row[slot], c = n.dest[p];
+    bool won = mine[a] == key && mine[c] == key;
+    if (Budget) won = won && n.grant[a] != 0;   // grant[] was settled from the spend before this kernel, which changes it
+    if (won) {
+        const u64 w = n.size[p];
+        if (Budget) {
+            const DkHome home = dk_home_row(n, p);
+            *cost = (dk_home(home, c) ? 0 : w) - (dk_home(home, a) ? 0 : w);
+        }
+        n.load[a] -= w;
+        n.load[c] += w;
+        row[slot] = (uint16_t)c;
+        if constexpr (X) {
+            const uint32_t px = n.pos[p];
+            const u64 bx = 1ull << (px & 63);
+            n.mask[(size_t)a * n.words + (px >> 6)] &= ~bx;
+            n.mask[(size_t)c * n.words + (px >> 6)] |= bx;
+        }
+    }
+    return won;
+}
+
+// APPLY of round r.  It clears the minkey words of round r + 1 (last read by the apply of round r - 1) and applies the winners.  In
+// the exchange call (X; count, xcount = the round's proposals of the two kinds) the round is whichever kind it is: an exchange round
+// iff it has no move proposal, and ctl[D_DONE] is set once a round has had neither kind.  A winner of an exchange reads only what its
+// proposer stored (an exchange flips four mask bits; a winner alone touches the mask rows of its two brokers).
+template <bool Budget, bool X>
+__global__ void k_dk_apply(std::conditional_t<X, DkNetX, DkNet> n, int r, const uint32_t *__restrict__ count, const uint32_t *__restrict__ xcount) {
+    static_assert(!(Budget && X), "exchange rounds are by bytes, without a budget");
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     {
         u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
         for (int e = p; e < n.B; e += gridDim.x * blockDim.x) clr[e] = kDkNoKey;
-        if (p < n.P) n.pk[(size_t)((r + 1) & 1) * n.P + p] = kDkNoKey;
+        if constexpr (X) {
+            if (p < n.P) n.pk[(size_t)((r + 1) & 1) * n.P + p] = kDkNoKey;
+        }
     }
-    const bool isx = *count == 0;   // the round's move proposals
-    if (p == 0 && isx && *xcount == 0) n.ctl[D_DONE] = 1;
+    bool isx = false;   // the round is an exchange round
+    if constexpr (X) {
+        isx = *count == 0;
+        if (p == 0 && isx && *xcount == 0) n.ctl[D_DONE] = 1;
+    }
     bool won = false;
+    u64 cost = 0;
     if (p < n.P) {
         const u64 key = n.key[p];
         if (key != kDkNoKey) {
             const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
-            uint16_t *row = n.rows + (size_t)p * n.W;
-            const int slot = n.slot[p], c = n.dest[p];
-            const uint32_t px = n.pos[p];
-            const u64 bx = 1ull << (px & 63);
             if (!isx) {
-                const int a = row[slot];   // a move: no other lane writes this row
-                won = mine[a] == key && mine[c] == key;
-                if (won) {
-                    const u64 w = n.size[p];
-                    n.load[a] -= w;
-                    n.load[c] += w;
-                    row[slot] = (uint16_t)c;
-                    n.mask[(size_t)a * n.words + (px >> 6)] &= ~bx;
-                    n.mask[(size_t)c * n.words + (px >> 6)] |= bx;
-                }
-            } else {
-                const int a = n.xsrc[p];
+                won = dk_apply_move<Budget, X>(n, p, key, mine, &cost);
+            } else if constexpr (X) {
+                const int slot = n.slot[p], a = n.xsrc[p], c = n.dest[p];
                 const uint32_t y = n.xpart[p];
                 const u64 *part = n.pk + (size_t)(r & 1) * n.P;
                 won = mine[a] == key && mine[c] == key && part[p] == key && part[y] == key;
                 if (won) {   // no other winner touches a, c, x or y
                     const u64 d = n.size[p] - n.size[y];
-                    const uint32_t py = n.pos[y];
-                    const u64 by = 1ull << (py & 63);
+                    const uint32_t px = n.pos[p], py = n.pos[y];
+                    const u64 bx = 1ull << (px & 63), by = 1ull << (py & 63);
                     u64 *ma = n.mask + (size_t)a * n.words, *mc = n.mask + (size_t)c * n.words;
                     n.load[a] -= d;
                     n.load[c] += d;
-                    row[slot] = (uint16_t)c;
+                    n.rows[(size_t)p * n.W + slot] = (uint16_t)c;
                     n.rows[(size_t)y * n.W + n.xslot[p]] = (uint16_t)a;
                     ma[px >> 6] &= ~bx;
                     ma[py >> 6] |= by;
@@ -577,7 +557,8 @@ __global__ void k_dkx_apply(DkNetX n, int r, const uint32_t *__restrict__ count,
         }
     }
     lane_count_to(won, &n.ctl[D_MOVES]);
-    lane_count_to(won && isx, &n.ctl[D_XCH]);
+    if (Budget) wave_sum_to(cost, &n.ctl[D_SPENT]);   // the sum of a wavefront wraps as its terms do; it adds nothing when it is 0
+    if constexpr (X) lane_count_to(won && isx, &n.ctl[D_XCH]);
 }
 
 // ---- the result ---------------------------------------------------------------------------------------------------------------------
@@ -638,18 +619,6 @@ int validate_disk(const std::string &fn, int32_t B, int32_t R, const uint8_t *ra
     return KAO_OK;
 }
 
-// one PROPOSE of the round's kind
-template <bool Budget, bool Cap>
-void dk_propose(const DkNet &n, bool thorough, unsigned blocks, hipStream_t st, int r, uint32_t *count) {
-    if constexpr (Cap) {
-        if (thorough) {
-            k_dk_propose<Budget, true, true><<<blocks, kDkThreads, 0, st>>>(n, r, count);
-            return;
-        }
-    }
-    k_dk_propose<Budget, Cap, false><<<blocks, kDkThreads, 0, st>>>(n, r, count);
-}
-
 // a fraction {numerator, denominator}, compared by the two 128-bit products; every part stays below 2^62 (denominators are >= 1)
 struct DkFrac {
     uint64_t num, den;
@@ -674,228 +643,274 @@ bool frac_integral(const DkFrac &peak, const uint64_t *cap, int B, uint64_t tota
     return sum < total;
 }
 
-// the entry points: Budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]; Cap (cap != NULL) is
-// the descent by utilisation: the rank by utilisation, the capacity form of the test, THOROUGH rounds, fractions as outputs, stats[10];
-// X (kao_balance_disk_exchange, by bytes and without a budget) adds PI, the masks and the partition words, makes a round RANK, PROPOSE,
-// the exchange PROPOSE (which returns at once in a round with a move proposal, and after the call has ended) and k_dkx_apply, and
-// fills stats[8..11]
-template <bool Budget, bool Cap, bool X = false>
-int balance_disk(const std::string &fn, int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
-                 const uint64_t *size, const uint64_t *cap, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes,
-                 int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
-                 uint64_t *lower_bound, int32_t *status, int64_t *stats) {
-    const void *outs[] = {n_moved, bytes_moved, peak_before, peak_after, lower_bound, status};
-    int rc = validate_disk(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, outs, 6);
-    if (rc) return rc;
-    uint64_t cap_sum = 0, cap_max = 0;
-    if (Cap) {   // 1 <= cap[b], and a sum below 2^62: with the loads below 2^62 every product of the two fits 128 bits
-        for (int b = 0; b < n_brokers; ++b) {
-            if (cap[b] == 0) return fail(KAO_ERR_INVALID, fn + "cap[" + std::to_string(b) + "] is 0");
-            if (__builtin_add_overflow(cap_sum, cap[b], &cap_sum) || cap_sum >= (uint64_t(1) << 62))
-                return fail(KAO_ERR_INVALID, fn + "cap[" + std::to_string(b) + "]: the capacities sum to 2^62 or more");
-            cap_max = std::max(cap_max, cap[b]);
-        }
-    }
-    static_assert(!X || (!Budget && !Cap), "exchange rounds are by bytes, without a budget");
-    std::vector<uint32_t> h_pi, h_pos;   // X: PI, and the position of a partition in it
-    std::vector<uint64_t> h_ps;
-    if (X) {
-        for (int32_t p = 0; p < n_partitions; ++p)
-            if (size[p]) h_pi.push_back((uint32_t)p);
-        if ((uint64_t)n_brokers * ((h_pi.size() + 63) / 64) > KAO_DISK_EXCHANGE_MAX_WORDS)
-            return fail(KAO_ERR_UNSUPPORTED, fn + "n_brokers * ceil(N / 64) is above 2^27 mask words (N = the partitions with size > 0)");
-        std::sort(h_pi.begin(), h_pi.end(), [&](uint32_t x, uint32_t y) { return size[x] != size[y] ? size[x] > size[y] : x < y; });
-        h_pos.assign((size_t)n_partitions, 0);
-        h_ps.resize(h_pi.size());
-        for (size_t t = 0; t < h_pi.size(); ++t) {
-            h_pos[h_pi[t]] = (uint32_t)t;
-            h_ps[t] = size[h_pi[t]];
-        }
-    }
-    if ((rc = require_init())) return rc;
-    const int B = n_brokers, P = n_partitions, W = width, PW = P * W, N = (int)h_pi.size(), words = (N + 63) / 64;
+// ---- the host side of a call ----------------------------------------------------------------------------------------------------------
+// Which entry point: budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]; cap (by utilisation)
+// the rank by utilisation, the capacity form of the test, THOROUGH rounds, fractions as outputs and stats[10]; exchange
+// (kao_balance_disk_exchange: by bytes, without a budget, as k_dk_apply asserts) PI, the masks and the partition words, the exchange
+// PROPOSE in every round (it returns at once in a round with a move proposal, and after the call has ended) and stats[8..11].
+struct DkKind {
+    bool budget, cap, exchange;
+};
 
-    // one arena: ctl u64[D_N] | count u32[kDkBatch] (2 kDkBatch with X: the exchange proposals behind the moves') | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] |
-    //            capacity u64[B] | rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B]
+struct DkArgs {   // the arguments of the C calls in their order (cap, max_bytes where the call has them); the peaks and the bound are two words by utilisation
+    int32_t B, R; const uint8_t *rack_of; int32_t P, W; uint16_t *rows; const uint64_t *size, *cap;
+    int32_t max_per_rack, move_leaders; uint64_t min_gain, max_bytes; int32_t max_rounds, dry_run;
+    int32_t *n_moved; uint64_t *bytes_moved, *peak_before, *peak_after, *lower_bound; int32_t *status; int64_t *stats;
+};
+
+struct DkCall {   // one call on the host
+    DkKind kind;
+    uint64_t cap_sum = 0, cap_max = 0;   // by utilisation
+    std::vector<uint32_t> pi, pos;       // exchange: PI (the partitions with size > 0, size descending, then index ascending), the position of
+    std::vector<uint64_t> ps;            // a partition in it, the sizes along it
+    CallBufs m;
+    hipStream_t st;
+    DkNetX x;                 // the exchange call's; its DkNet part is every call's
+    uint32_t *d_cnt;          // [2][kDkBatch] the move proposals of a batch's rounds, then (exchange) their exchange proposals
+    u64 *d_fixed, *d_load0;   // [B] the bytes of the slot-0 replicas; the loads of the input
+    unsigned pblocks, bblocks;
+    int64_t launches = 0, rounds = 0, props = 0, thorough_rounds = 0, x_rounds = 0, x_props = 0;   // what the host counts
+    bool more = false, open = false;   // max_rounds rounds have run and there is more to do; the budget stopped the descent
+    const DkNet &n() const { return x; }
+};
+
+// 1 <= cap[b], and a sum below 2^62: with the loads below 2^62 every product of the two fits 128 bits
+int dk_check_capacity(const std::string &fn, int B, const uint64_t *cap, DkCall &c) {
+    for (int b = 0; b < B; ++b) {
+        if (cap[b] == 0) return fail(KAO_ERR_INVALID, fn + "cap[" + std::to_string(b) + "] is 0");
+        if (__builtin_add_overflow(c.cap_sum, cap[b], &c.cap_sum) || c.cap_sum >= (uint64_t(1) << 62))
+            return fail(KAO_ERR_INVALID, fn + "cap[" + std::to_string(b) + "]: the capacities sum to 2^62 or more");
+        c.cap_max = std::max(c.cap_max, cap[b]);
+    }
+    return KAO_OK;
+}
+
+// the exchange call's order: a host sort, once (the sizes never change)
+int dkx_build_order(const std::string &fn, int B, int P, const uint64_t *size, DkCall &o) {
+    for (int32_t p = 0; p < P; ++p)
+        if (size[p]) o.pi.push_back((uint32_t)p);
+    if ((uint64_t)B * ((o.pi.size() + 63) / 64) > KAO_DISK_EXCHANGE_MAX_WORDS)
+        return fail(KAO_ERR_UNSUPPORTED, fn + "n_brokers * ceil(N / 64) is above 2^27 mask words (N = the partitions with size > 0)");
+    std::sort(o.pi.begin(), o.pi.end(), [&](uint32_t x, uint32_t y) { return size[x] != size[y] ? size[x] > size[y] : x < y; });
+    o.pos.assign((size_t)P, 0);
+    o.ps.resize(o.pi.size());
+    for (size_t t = 0; t < o.pi.size(); ++t) {
+        o.pos[o.pi[t]] = (uint32_t)t;
+        o.ps[t] = size[o.pi[t]];
+    }
+    return KAO_OK;
+}
+
+// carves the arena, uploads the inputs and fills the net; with exchange it builds the masks (k_dkx_index)
+int dk_open(DkCall &c, const DkArgs &in) {
+    const bool X = c.kind.exchange;
+    const int B = in.B, P = in.P, PW = P * in.W, N = (int)c.pi.size(), words = (N + 63) / 64;
+    // one arena: ctl u64[D_N] | count u32[2 kDkBatch] | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] | capacity u64[B] |
+    //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B]
     Carve cv;
-    const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>((X ? 2 : 1) * kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
-                 o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_cap = cv.take<u64>(Cap ? B : 0), o_rank = cv.take<int32_t>(B),
-                 o_order = cv.take<int32_t>(B),
-                 o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW), o_rows0 = cv.take<uint16_t>(PW),
-                 o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B), o_grant = cv.take<uint8_t>(Budget ? B : 0);
-    // X: pk u64[2P] (all ones) | mask u64[B words] (zeroed) | ps u64[N] | pi u32[N] | pos, xpart u32[P] | xsrc u16[P] | xslot u8[P]
+    const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(2 * kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
+                 o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_cap = cv.take<u64>(c.kind.cap ? B : 0), o_rank = cv.take<int32_t>(B),
+                 o_order = cv.take<int32_t>(B), o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW),
+                 o_rows0 = cv.take<uint16_t>(PW), o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B),
+                 o_grant = cv.take<uint8_t>(c.kind.budget ? B : 0);
+    // exchange: pk u64[2P] (all ones) | mask u64[B words] (zeroed) | ps u64[N] | pi u32[N] | pos, xpart u32[P] | xsrc u16[P] | xslot u8[P]
     const size_t o_pk = cv.take<u64>(X ? 2 * (size_t)P : 0), o_mask = cv.take<u64>(X ? (size_t)B * words : 0), o_ps = cv.take<u64>(N), o_pi = cv.take<uint32_t>(N),
                  o_pos = cv.take<uint32_t>(X ? P : 0), o_xpart = cv.take<uint32_t>(X ? P : 0), o_xsrc = cv.take<uint16_t>(X ? P : 0),
                  o_xslot = cv.take<uint8_t>(X ? P : 0);
-    CallBufs m;
-    if ((rc = m.open(cv.end()))) return rc;
-    hipStream_t st = m.stream;
-    uint32_t *d_cnt = m.at<uint32_t>(o_cnt);
-    [[maybe_unused]] uint32_t *d_xcnt = d_cnt + kDkBatch;
-    u64 *d_fixed = m.at<u64>(o_fixed), *d_load0 = m.at<u64>(o_load0);
-    uint16_t *d_rows = m.at<uint16_t>(o_rows), *d_rows0 = m.at<uint16_t>(o_rows0);
-    DkNet n;
-    n.P = P; n.W = W; n.B = B; n.cap = max_per_rack; n.first = move_leaders ? 0 : 1; n.min_gain = min_gain;
-    n.rows = d_rows; n.rows0 = d_rows0; n.size = m.at<u64>(o_size); n.rack = m.at<uint8_t>(o_rack); n.slot = m.at<uint8_t>(o_slot);
-    n.dest = m.at<uint16_t>(o_dest); n.key = m.at<u64>(o_key); n.load = m.at<u64>(o_load); n.rank = m.at<int32_t>(o_rank);
-    n.order = m.at<int32_t>(o_order); n.mk = m.at<u64>(o_mk); n.ctl = m.at<u64>(o_ctl);
-    n.grant = m.at<uint8_t>(o_grant); n.max_bytes = max_bytes;
+    if (int rc = c.m.open(cv.end())) return rc;
+    const CallBufs &m = c.m;
+    hipStream_t st = c.st = m.stream;
+    c.d_cnt = m.at<uint32_t>(o_cnt); c.d_fixed = m.at<u64>(o_fixed); c.d_load0 = m.at<u64>(o_load0);
+    c.pblocks = grid_for(P, kDkThreads); c.bblocks = grid_for(B, kDkThreads);
+    DkNetX &n = c.x;
+    n.P = P; n.W = in.W; n.B = B; n.cap = in.max_per_rack; n.first = in.move_leaders ? 0 : 1; n.min_gain = in.min_gain;
+    n.rows = m.at<uint16_t>(o_rows); n.rows0 = m.at<uint16_t>(o_rows0); n.size = m.at<u64>(o_size); n.rack = m.at<uint8_t>(o_rack);
+    n.slot = m.at<uint8_t>(o_slot); n.dest = m.at<uint16_t>(o_dest); n.key = m.at<u64>(o_key); n.load = m.at<u64>(o_load);
+    n.rank = m.at<int32_t>(o_rank); n.order = m.at<int32_t>(o_order); n.mk = m.at<u64>(o_mk); n.ctl = m.at<u64>(o_ctl);
+    n.grant = m.at<uint8_t>(o_grant); n.max_bytes = in.max_bytes; n.capacity = c.kind.cap ? m.at<u64>(o_cap) : nullptr;
+    n.N = N; n.words = words; n.pi = m.at<uint32_t>(o_pi); n.ps = m.at<u64>(o_ps); n.pos = m.at<uint32_t>(o_pos); n.mask = m.at<u64>(o_mask);
+    n.pk = m.at<u64>(o_pk); n.xsrc = m.at<uint16_t>(o_xsrc); n.xpart = m.at<uint32_t>(o_xpart); n.xslot = m.at<uint8_t>(o_xslot);
 
     HIP_TRY(hipMemsetAsync(m.arena, 0, zeroed, st));
     HIP_TRY(hipMemsetAsync(n.mk, 0xFF, 2 * (size_t)B * sizeof(u64), st));
-    HIP_TRY(hipMemcpyAsync(m.at<uint8_t>(o_rack), rack_of, (size_t)B, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m.at<uint8_t>(o_rack), in.rack_of, (size_t)B, hipMemcpyHostToDevice, st));
     if (P) {
-        HIP_TRY(hipMemcpyAsync(d_rows0, rows, (size_t)PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_rows, d_rows0, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(m.at<u64>(o_size), size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<uint16_t>(o_rows0), in.rows, (size_t)PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(n.rows, n.rows0, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<u64>(o_size), in.size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
-    if (Cap) {
-        n.capacity = m.at<u64>(o_cap);
-        HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), cap, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    } else {
-        n.capacity = nullptr;
+    if (c.kind.cap) HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), in.cap, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (X && P) {
+        HIP_TRY(hipMemsetAsync(n.pk, 0xFF, 2 * (size_t)P * sizeof(u64), st));
+        HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pos), c.pos.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
-    const unsigned pblocks = grid_for(P, kDkThreads), bblocks = grid_for(B, kDkThreads);
-    int64_t launches = 0, rounds = 0, props = 0, thorough_rounds = 0, x_rounds = 0, x_props = 0;
-    [[maybe_unused]] DkNetX nx;
-    if constexpr (X) {
-        static_cast<DkNet &>(nx) = n;
-        nx.N = N; nx.words = words; nx.pi = m.at<uint32_t>(o_pi); nx.ps = m.at<u64>(o_ps); nx.pos = m.at<uint32_t>(o_pos); nx.mask = m.at<u64>(o_mask);
-        nx.pk = m.at<u64>(o_pk); nx.xsrc = m.at<uint16_t>(o_xsrc); nx.xpart = m.at<uint32_t>(o_xpart); nx.xslot = m.at<uint8_t>(o_xslot);
-        if (P) {
-            HIP_TRY(hipMemsetAsync(nx.pk, 0xFF, 2 * (size_t)P * sizeof(u64), st));
-            HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pos), h_pos.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        }
-        if (N) {
-            HIP_TRY(hipMemsetAsync(nx.mask, 0, (size_t)B * words * sizeof(u64), st));
-            HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pi), h_pi.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(m.at<u64>(o_ps), h_ps.data(), (size_t)N * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-            k_dkx_index<<<grid_for(N, kDkThreads), kDkThreads, 0, st>>>(nx);
-            ++launches;
-        }
+    if (X && N) {
+        HIP_TRY(hipMemsetAsync(n.mask, 0, (size_t)B * words * sizeof(u64), st));
+        HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pi), c.pi.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(m.at<u64>(o_ps), c.ps.data(), (size_t)N * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        k_dkx_index<<<grid_for(N, kDkThreads), kDkThreads, 0, st>>>(n);
+        ++c.launches;
     }
-    bool more = false, open = false;   // open: the budget stopped the descent
-    if (P) {
-        k_dk_init<<<pblocks, kDkThreads, 0, st>>>(n, d_fixed);
-        ++launches;
-    }
-    k_dk_peak0<<<bblocks, kDkThreads, 0, st>>>(n, d_fixed, d_load0);
-    ++launches;
-    HIP_TRY(hipGetLastError());
-    const auto rank = [&] { k_dk_rank<Cap><<<bblocks, kDkThreads, 0, st>>>(B, n.load, n.capacity, n.rank, n.order); };
+    return KAO_OK;
+}
 
-    if (P) {
-        uint32_t cnt[(X ? 2 : 1) * kDkBatch];
-        bool thorough = false;   // by utilisation: a FAST round had no proposal
-        for (int r = 0, done = 0; !done;) {
-            if (r >= kDkHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
-            const int batch = thorough ? kDkThoroughBatch : kDkBatch;
-            const int nb = max_rounds > 0 ? std::min(batch, max_rounds - r) : batch;
-            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof cnt, st));
-            if (nb == 0) {   // max_rounds rounds have run, every one with a move: is there more to do?  (THOROUGH sees every move a FAST round sees)
-                rank();
-                dk_propose<Budget, Cap>(n, Cap, pblocks, st, r, d_cnt);
-                launches += 2;
-                if constexpr (X) {
-                    k_dkx_propose<<<pblocks, kDkThreads, 0, st>>>(nx, r, d_cnt, d_xcnt);
-                    ++launches;
-                }
-            }
-            for (int i = 0; i < nb; ++i) {
-                rank();
-                dk_propose<Budget, Cap>(n, thorough, pblocks, st, r + i, d_cnt + i);
-                if (Budget) k_dk_grant<<<1, kDkGrantThreads, 0, st>>>(n, r + i);
-                if constexpr (X) {
-                    k_dkx_propose<<<pblocks, kDkThreads, 0, st>>>(nx, r + i, d_cnt + i, d_xcnt + i);
-                    k_dkx_apply<<<pblocks, kDkThreads, 0, st>>>(nx, r + i, d_cnt + i, d_xcnt + i);
-                } else {
-                    k_dk_apply<Budget><<<pblocks, kDkThreads, 0, st>>>(n, r + i);
-                }
-                launches += Budget || X ? 4 : 3;
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (nb == 0) { more = cnt[0] != 0 || (X && cnt[X ? kDkBatch : 0] != 0); break; }
-            int ran = 0;   // the rounds of the batch before the first one without a proposal; the ones after it changed nothing
-            if constexpr (X) {   // a round without a move proposal is an exchange round
-                for (; ran < nb && (cnt[ran] != 0 || cnt[kDkBatch + ran] != 0); ++ran) {
-                    props += cnt[ran] + cnt[kDkBatch + ran];
-                    x_props += cnt[kDkBatch + ran];
-                    x_rounds += cnt[ran] == 0;
-                }
-            } else {
-                while (ran < nb && cnt[ran] != 0) props += cnt[ran++];
-            }
-            rounds += ran;
-            if (thorough) thorough_rounds += ran;
-            if (ran < nb && Cap && !thorough) {   // the first empty FAST round: THOROUGH from here on.  It and the empty rounds behind it left
-                thorough = true;                  // both minkey rows clear and every key[p] empty, so the count of rounds goes on from `ran`
-                r += ran;
-            } else {
-                done = ran < nb;                  // the first round without a proposal ends the descent
-                r += nb;
-            }
-        }
-        if (Budget && !more) {   // no affordable proposal is left: is there one without the budget?  (no row changes: nothing is applied)
-            uint32_t left = 0;
-            HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof left, st));
-            rank();
-            dk_propose<false, Cap>(n, Cap, pblocks, st, 0, d_cnt);
-            launches += 2;
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&left, d_cnt, sizeof left, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            open = left != 0;
-        }
-        k_dk_finish<<<pblocks, kDkThreads, 0, st>>>(n);
-        ++launches;
+// PROPOSE: by bytes, or FAST / THOROUGH by utilisation; `budget` is the round's (the probe at the end of a budgeted call runs without)
+void dk_propose(const DkCall &c, bool budget, bool thorough, int r, uint32_t *count) {
+    void (*const k)(DkNet, int, uint32_t *) = !c.kind.cap ? (budget ? k_dk_propose<true, false, false> : k_dk_propose<false, false, false>)
+                                              : thorough  ? (budget ? k_dk_propose<true, true, true> : k_dk_propose<false, true, true>)
+                                                          : (budget ? k_dk_propose<true, true, false> : k_dk_propose<false, true, false>);
+    k<<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, count);
+}
+
+// APPLY of round r, whose proposals were counted in column i
+void dk_apply(const DkCall &c, int r, int i) {
+    if (c.kind.exchange) k_dk_apply<false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.x, r, c.d_cnt + i, c.d_cnt + kDkBatch + i);
+    else if (c.kind.budget) k_dk_apply<true, false><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
+    else k_dk_apply<false, false><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
+}
+
+// RANK, PROPOSE and (exchange) the exchange PROPOSE of round r, counted in column i: the head of a round, or all of "is there a proposal?"
+void dk_probe(DkCall &c, bool budget, bool thorough, int r, int i) {
+    const DkNet &n = c.n();
+    (c.kind.cap ? k_dk_rank<true> : k_dk_rank<false>)<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.capacity, n.rank, n.order);
+    dk_propose(c, budget, thorough, r, c.d_cnt + i);
+    c.launches += 2;
+    if (c.kind.exchange) {
+        k_dkx_propose<<<c.pblocks, kDkThreads, 0, c.st>>>(c.x, r, c.d_cnt + i, c.d_cnt + kDkBatch + i);
+        ++c.launches;
     }
-    k_dk_peak1<<<bblocks, kDkThreads, 0, st>>>(n, d_load0);
-    ++launches;
+}
+
+// the rounds, in batches: nb rounds are enqueued, then the host reads their proposal counts.  The rounds of a batch before the first
+// one without a proposal of either kind ran; the ones after it changed nothing.  A budgeted call ends with the probe behind stats[9]
+int dk_rounds(const std::string &fn, DkCall &c, int max_rounds) {
+    uint32_t cnt[2 * kDkBatch] = {};   // the second row stays 0 without exchange
+    bool thorough = false;             // by utilisation: a FAST round had no proposal
+    for (int r = 0, done = 0; !done;) {
+        if (r >= kDkHardRounds) return fail(KAO_ERR_HIP, fn + "the rounds did not finish");
+        const int batch = thorough ? kDkThoroughBatch : kDkBatch;
+        const int nb = max_rounds > 0 ? std::min(batch, max_rounds - r) : batch;
+        HIP_TRY(hipMemsetAsync(c.d_cnt, 0, sizeof cnt, c.st));
+        if (nb == 0) dk_probe(c, c.kind.budget, c.kind.cap, r, 0);   // max_rounds rounds have run, every one with a proposal: is there more to do?  (THOROUGH sees every move a FAST round sees)
+        for (int i = 0; i < nb; ++i) {
+            dk_probe(c, c.kind.budget, thorough, r + i, i);
+            if (c.kind.budget) k_dk_grant<<<1, kDkGrantThreads, 0, c.st>>>(c.n(), r + i);
+            dk_apply(c, r + i, i);
+            c.launches += c.kind.budget ? 2 : 1;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(cnt, c.d_cnt, sizeof cnt, hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipStreamSynchronize(c.st));
+        if (nb == 0) { c.more = cnt[0] != 0 || cnt[kDkBatch] != 0; break; }
+        int ran = 0;
+        for (; ran < nb && (cnt[ran] != 0 || cnt[kDkBatch + ran] != 0); ++ran) {
+            c.props += cnt[ran] + cnt[kDkBatch + ran];
+            c.x_props += cnt[kDkBatch + ran];
+            c.x_rounds += cnt[ran] == 0;   // a round without a move proposal is an exchange round
+        }
+        c.rounds += ran;
+        if (thorough) c.thorough_rounds += ran;
+        if (ran < nb && c.kind.cap && !thorough) {   // the first empty FAST round: THOROUGH from here on.  It and the empty rounds behind it left
+            thorough = true;                         // both minkey rows clear and every key[p] empty, so the count of rounds goes on from `ran`
+            r += ran;
+        } else {
+            done = ran < nb;                         // the first round without a proposal ends the descent
+            r += nb;
+        }
+    }
+    if (c.kind.budget && !c.more) {   // no affordable proposal is left: is there one without the budget?  (Round index 0; nothing is applied)
+        HIP_TRY(hipMemsetAsync(c.d_cnt, 0, sizeof cnt[0], c.st));
+        dk_probe(c, false, c.kind.cap, 0, 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(cnt, c.d_cnt, sizeof cnt[0], hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipStreamSynchronize(c.st));
+        c.open = cnt[0] != 0;
+    }
+    return KAO_OK;
+}
+
+// the peaks, the bound (the highest of three terms, the lowest term on ties) and the status, by bytes; returns the term
+int dk_outputs_bytes(const u64 *ctl, const DkArgs &out) {
+    const uint64_t terms[3] = {(uint64_t)ctl[D_MAXSIZE], ((uint64_t)ctl[D_TOTAL] + (uint64_t)out.B - 1) / (uint64_t)out.B, out.move_leaders ? 0 : (uint64_t)ctl[D_FIXED]};
+    int which = 0;
+    for (int i = 1; i < 3; ++i)
+        if (terms[i] > terms[which]) which = i;
+    *out.peak_before = ctl[D_PEAK0];
+    *out.peak_after = ctl[D_PEAK1];
+    *out.lower_bound = terms[which];
+    *out.status = ctl[D_PEAK1] == terms[which] ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    return which;
+}
+
+// ... by utilisation: fractions, their maxima taken on the host from h = load0, load, fixed; term 3 is the integrality test
+int dk_outputs_fractions(const u64 *ctl, const DkCall &c, const DkArgs &out, const std::vector<uint64_t> *h) {
+    const uint64_t *cap = out.cap;
+    const DkFrac terms[3] = {{(uint64_t)ctl[D_MAXSIZE], c.cap_max}, {(uint64_t)ctl[D_TOTAL], c.cap_sum}, out.move_leaders ? DkFrac{0, 1} : frac_peak(h[2], cap)};
+    int which = 0;
+    for (int i = 1; i < 3; ++i)
+        if (frac_above(terms[i], terms[which])) which = i;
+    const DkFrac before = frac_peak(h[0], cap), after = frac_peak(h[1], cap);
+    out.peak_before[0] = before.num; out.peak_before[1] = before.den;
+    out.peak_after[0] = after.num; out.peak_after[1] = after.den;
+    out.lower_bound[0] = terms[which].num; out.lower_bound[1] = terms[which].den;
+    bool proven = frac_equal(after, terms[which]);
+    if (!proven && frac_integral(after, cap, out.B, (uint64_t)ctl[D_TOTAL])) { proven = true; which = 3; }
+    *out.status = proven ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    return which;
+}
+
+int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
+    if (kind.exchange && (kind.budget || kind.cap)) return fail(KAO_ERR_INVALID, fn + "exchange rounds are by bytes, without a budget");
+    const void *outs[] = {a.n_moved, a.bytes_moved, a.peak_before, a.peak_after, a.lower_bound, a.status};
+    int rc = validate_disk(fn, a.B, a.R, a.rack_of, a.P, a.W, a.rows, a.size, outs, 6);
+    if (rc) return rc;
+    DkCall c;
+    c.kind = kind;
+    if (kind.cap && (rc = dk_check_capacity(fn, a.B, a.cap, c))) return rc;
+    if (kind.exchange && (rc = dkx_build_order(fn, a.B, a.P, a.size, c))) return rc;
+    if ((rc = require_init())) return rc;
+    if ((rc = dk_open(c, a))) return rc;
+    const DkNet &n = c.n();
+    const int B = a.B, P = a.P;
+    hipStream_t st = c.st;
+    if (P) {
+        k_dk_init<<<c.pblocks, kDkThreads, 0, st>>>(n, c.d_fixed);
+        ++c.launches;
+    }
+    k_dk_peak0<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_fixed, c.d_load0);
+    ++c.launches;
+    HIP_TRY(hipGetLastError());
+    if (P) {
+        if ((rc = dk_rounds(fn, c, a.max_rounds))) return rc;
+        k_dk_finish<<<c.pblocks, kDkThreads, 0, st>>>(n);
+        ++c.launches;
+    }
+    k_dk_peak1<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_load0);
+    ++c.launches;
     HIP_TRY(hipGetLastError());
     u64 ctl[D_N];
-    std::vector<uint64_t> h_load0, h_load, h_fixed;   // by utilisation: a maximum over fractions is taken on the host, from one read at the end
+    std::vector<uint64_t> h[3];   // by utilisation: load0, load, fixed.  A maximum over fractions is taken on the host, from one read at the end
+    const u64 *d_h[3] = {c.d_load0, n.load, c.d_fixed};
     HIP_TRY(hipMemcpyAsync(ctl, n.ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    if (Cap) {
-        h_load0.resize(B); h_load.resize(B); h_fixed.resize(B);
-        HIP_TRY(hipMemcpyAsync(h_load0.data(), d_load0, (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_load.data(), n.load, (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_fixed.data(), d_fixed, (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    for (int i = 0; kind.cap && i < 3; ++i) {
+        h[i].resize(B);
+        HIP_TRY(hipMemcpyAsync(h[i].data(), d_h[i], (size_t)B * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
-    if (P && !dry_run) HIP_TRY(hipMemcpyAsync(rows, d_rows, (size_t)PW * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    if (P && !a.dry_run) HIP_TRY(hipMemcpyAsync(a.rows, n.rows, (size_t)P * a.W * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
 
-    *n_moved = (int32_t)ctl[D_NMOVED];
-    *bytes_moved = ctl[D_BYTES];
-    int which = 0;
-    if (Cap) {
-        const DkFrac terms[3] = {{(uint64_t)ctl[D_MAXSIZE], cap_max}, {(uint64_t)ctl[D_TOTAL], cap_sum}, move_leaders ? DkFrac{0, 1} : frac_peak(h_fixed, cap)};
-        for (int i = 1; i < 3; ++i)
-            if (frac_above(terms[i], terms[which])) which = i;   // the lowest term on ties
-        const DkFrac before = frac_peak(h_load0, cap), after = frac_peak(h_load, cap);
-        peak_before[0] = before.num; peak_before[1] = before.den;
-        peak_after[0] = after.num; peak_after[1] = after.den;
-        lower_bound[0] = terms[which].num; lower_bound[1] = terms[which].den;
-        bool proven = frac_equal(after, terms[which]);
-        if (!proven && frac_integral(after, cap, B, (uint64_t)ctl[D_TOTAL])) { proven = true; which = 3; }
-        *status = proven ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
-    } else {
-        const uint64_t terms[3] = {(uint64_t)ctl[D_MAXSIZE], ((uint64_t)ctl[D_TOTAL] + (uint64_t)B - 1) / (uint64_t)B, move_leaders ? 0 : (uint64_t)ctl[D_FIXED]};
-        for (int i = 1; i < 3; ++i)
-            if (terms[i] > terms[which]) which = i;   // the lowest term on ties
-        *peak_before = ctl[D_PEAK0];
-        *peak_after = ctl[D_PEAK1];
-        *lower_bound = terms[which];
-        *status = ctl[D_PEAK1] == terms[which] ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
-    }
-    if (stats) {
-        stats[0] = rounds; stats[1] = (int64_t)ctl[D_MOVES]; stats[2] = props; stats[3] = launches; stats[4] = (int64_t)ctl[D_ROWS];
-        stats[5] = more ? 1 : 0; stats[6] = which; stats[7] = (int64_t)ctl[D_BROKERS];
-        if (Budget) { stats[8] = (int64_t)ctl[D_REFUSED]; stats[9] = open ? 1 : 0; }
-        else if (Cap) stats[8] = stats[9] = 0;
-        if (Cap) stats[10] = thorough_rounds;
-        if (X) { stats[8] = x_rounds; stats[9] = (int64_t)ctl[D_XCH]; stats[10] = x_props; stats[11] = (int64_t)ctl[D_XPEAK]; }
+    *a.n_moved = (int32_t)ctl[D_NMOVED];
+    *a.bytes_moved = ctl[D_BYTES];
+    const int which = kind.cap ? dk_outputs_fractions(ctl, c, a, h) : dk_outputs_bytes(ctl, a);
+    if (int64_t *stats = a.stats) {
+        stats[0] = c.rounds; stats[1] = (int64_t)ctl[D_MOVES]; stats[2] = c.props; stats[3] = c.launches; stats[4] = (int64_t)ctl[D_ROWS];
+        stats[5] = c.more ? 1 : 0; stats[6] = which; stats[7] = (int64_t)ctl[D_BROKERS];
+        if (kind.exchange) {
+            stats[8] = c.x_rounds; stats[9] = (int64_t)ctl[D_XCH]; stats[10] = c.x_props; stats[11] = (int64_t)ctl[D_XPEAK];
+        } else if (kind.budget || kind.cap) {   // by utilisation without a budget: both 0
+            stats[8] = kind.budget ? (int64_t)ctl[D_REFUSED] : 0; stats[9] = c.open ? 1 : 0;
+            if (kind.cap) stats[10] = c.thorough_rounds;
+        }
     }
     return KAO_OK;
 }
@@ -906,16 +921,18 @@ extern "C" int kao_balance_disk(int32_t n_brokers, int32_t n_racks, const uint8_
                                 const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, int32_t max_rounds, int32_t dry_run,
                                 int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound,
                                 int32_t *status, int64_t stats[8]) {
-    return balance_disk<false, false>("kao_balance_disk: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain,
-                               UINT64_MAX, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
+    return balance_disk({false, false, false}, "kao_balance_disk: ",
+                        {n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run,
+                         n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats});
 }
 
 extern "C" int kao_balance_disk_budget(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
                                        const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, uint64_t max_bytes,
                                        int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before,
                                        uint64_t *peak_after, uint64_t *lower_bound, int32_t *status, int64_t stats[10]) {
-    return balance_disk<true, false>("kao_balance_disk_budget: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders,
-                              min_gain, max_bytes, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
+    return balance_disk({true, false, false}, "kao_balance_disk_budget: ",
+                        {n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain, max_bytes, max_rounds, dry_run,
+                         n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats});
 }
 
 extern "C" int kao_balance_disk_capacity(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
@@ -924,18 +941,16 @@ extern "C" int kao_balance_disk_capacity(int32_t n_brokers, int32_t n_racks, con
                                          uint64_t peak_before[2], uint64_t peak_after[2], uint64_t lower_bound[2], int32_t *status, int64_t stats[11]) {
     const std::string fn = "kao_balance_disk_capacity: ";
     if (!cap) return fail(KAO_ERR_INVALID, fn + "null pointer");
-    if (max_bytes == UINT64_MAX)   // no budget: no grant kernel, stats[8] = stats[9] = 0
-        return balance_disk<false, true>(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, cap, max_per_rack, move_leaders, min_gain, max_bytes,
-                                         max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
-    return balance_disk<true, true>(fn, n_brokers, n_racks, rack_of, n_partitions, width, rows, size, cap, max_per_rack, move_leaders, min_gain, max_bytes,
-                                    max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats);
+    return balance_disk({max_bytes != UINT64_MAX, true, false}, fn,   // no budget: no grant kernel, stats[8] = stats[9] = 0
+                        {n_brokers, n_racks, rack_of, n_partitions, width, rows, size, cap, max_per_rack, move_leaders, min_gain, max_bytes, max_rounds, dry_run,
+                         n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats});
 }
 
 extern "C" int kao_balance_disk_exchange(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
                                          const uint64_t *size, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain, int32_t max_rounds,
                                          int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
                                          uint64_t *lower_bound, int32_t *status, int64_t stats[12]) {
-    return balance_disk<false, false, true>("kao_balance_disk_exchange: ", n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack,
-                                            move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run, n_moved, bytes_moved, peak_before, peak_after, lower_bound,
-                                            status, stats);
+    return balance_disk({false, false, true}, "kao_balance_disk_exchange: ",
+                        {n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run,
+                         n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats});
 }

@@ -115,6 +115,13 @@ def capacity_of(broker_ids: Sequence[int], capacities: Dict[int, object], defaul
     return np.array([table.get(int(b), default_capacity) for b in broker_ids], dtype=object)
 
 
+def _checked_max_bytes(exchange: bool, max_bytes, capacity) -> Optional[int]:
+    """max_bytes as the C call takes it (None without one), after the refusal of exchange together with a budget or capacities."""
+    if exchange and (max_bytes is not None or capacity is not None):
+        raise ValueError("exchange=True works by bytes only: not together with max_bytes or capacity")
+    return None if max_bytes is None else _budget(max_bytes)
+
+
 def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0,
                         max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False) -> DiskResult:
     """kao_balance_disk on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); size[p] is the bytes of one replica of
@@ -122,50 +129,28 @@ def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_p
     value >= 1 per broker index) it is kao_balance_disk_capacity: the peak of S(b) / capacity[b] is what the moves lower.  With
     exchange=True it is kao_balance_disk_exchange: exchanges go on from the move-stable state (by bytes only: a ValueError together
     with max_bytes or capacity)."""
-    if exchange and (max_bytes is not None or capacity is not None):
-        raise ValueError("exchange=True works by bytes only: not together with max_bytes or capacity")
-    if max_bytes is not None:
-        max_bytes = _budget(max_bytes)
-    if capacity is not None:
-        return _balance_disk_capacity(rows, n_brokers, rack_of, n_racks, size, _capacity_buffer(capacity, n_brokers), max_per_rack, move_leaders, min_gain,
-                                      max_rounds, dry_run, max_bytes)
+    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity)
+    cbuf = None if capacity is None else _capacity_buffer(capacity, n_brokers)
     r, flat, P, W = dense_rows(rows)
     rk = _rack_buffer(rack_of, n_brokers)
     sbuf = weight_buffer(size, P, min_gain)
-    stats = np.zeros(12 if exchange else 8 if max_bytes is None else 10, dtype=np.int64)
-    n, status = C.c_int32(0), C.c_int32(0)
-    moved, before, after, bound = (C.c_uint64(0) for _ in range(4))
-    head = [int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
-            sbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_per_rack), int(bool(move_leaders)), int(min_gain)]
-    tail = [int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), C.byref(before), C.byref(after), C.byref(bound), C.byref(status),
-            stats.ctypes.data_as(C.POINTER(C.c_int64))]
-    if exchange:
-        _check(_ffi.load().kao_balance_disk_exchange(*head, *tail), "kao_balance_disk_exchange")
-    elif max_bytes is None:
-        _check(_ffi.load().kao_balance_disk(*head, *tail), "kao_balance_disk")
-    else:
-        _check(_ffi.load().kao_balance_disk_budget(*head, max_bytes, *tail), "kao_balance_disk_budget")
-    return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before.value), peak_after=int(after.value),
-                      lower_bound=int(bound.value), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes,
-                      **(dict(exchange_rounds=int(stats[8]), exchanges=int(stats[9]), exchange_proposals=int(stats[10]), peak_of_moves=int(stats[11]))
-                         if exchange else {}))
-
-
-def _balance_disk_capacity(rows, n_brokers, rack_of, n_racks, size, cbuf, max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes) -> DiskResult:
-    r, flat, P, W = dense_rows(rows)
-    rk = _rack_buffer(rack_of, n_brokers)
-    sbuf = weight_buffer(size, P, min_gain)
-    stats = np.zeros(11, dtype=np.int64)
+    name, n_stats, extra = (("kao_balance_disk_capacity", 11, [(1 << 64) - 1 if max_bytes is None else max_bytes]) if cbuf is not None   # with or without a budget
+                            else ("kao_balance_disk_exchange", 12, []) if exchange else ("kao_balance_disk", 8, []) if max_bytes is None
+                            else ("kao_balance_disk_budget", 10, [max_bytes]))
+    stats = np.zeros(n_stats, dtype=np.int64)
     n, status, moved = C.c_int32(0), C.c_int32(0), C.c_uint64(0)
-    before, after, bound = ((C.c_uint64 * 2)() for _ in range(3))
-    _check(_ffi.load().kao_balance_disk_capacity(
-        int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
-        sbuf.ctypes.data_as(C.POINTER(C.c_uint64)), cbuf.ctypes.data_as(C.POINTER(C.c_uint64)), int(max_per_rack), int(bool(move_leaders)), int(min_gain),
-        (1 << 64) - 1 if max_bytes is None else max_bytes, int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), before, after, bound,
-        C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))), "kao_balance_disk_capacity")
+    before, after, bound = ((C.c_uint64 * 2)() for _ in range(3))   # {numerator, denominator} by utilisation; the calls by bytes write the first word only
+    head = [int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
+            sbuf.ctypes.data_as(C.POINTER(C.c_uint64))] + ([] if cbuf is None else [cbuf.ctypes.data_as(C.POINTER(C.c_uint64))])
+    tail = [int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), before, after, bound, C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))]
+    _check(getattr(_ffi.load(), name)(*head, int(max_per_rack), int(bool(move_leaders)), int(min_gain), *extra, *tail), name)
+    more = {}
+    if cbuf is not None:
+        more = dict(peak_before_capacity=int(before[1]), peak_after_capacity=int(after[1]), lower_bound_den=int(bound[1]))
+    elif exchange:
+        more = dict(exchange_rounds=int(stats[8]), exchanges=int(stats[9]), exchange_proposals=int(stats[10]), peak_of_moves=int(stats[11]))
     return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before[0]), peak_after=int(after[0]),
-                      lower_bound=int(bound[0]), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes,
-                      peak_before_capacity=int(before[1]), peak_after_capacity=int(after[1]), lower_bound_den=int(bound[1]))
+                      lower_bound=int(bound[0]), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes, **more)
 
 
 def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int] = None) -> np.ndarray:
@@ -197,10 +182,7 @@ def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, d
     `broker_list`, the moves lower the peak utilisation (kao_balance_disk_capacity).  With exchange=True exchanges go on from the
     move-stable state (kao_balance_disk_exchange; a ValueError together with max_bytes or capacity)."""
     from .waves import parse_sizes
-    if exchange and (max_bytes is not None or capacity is not None):
-        raise ValueError("exchange=True works by bytes only: not together with max_bytes or capacity")
-    if max_bytes is not None:
-        max_bytes = _budget(max_bytes)
+    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity)
     fi = parse_current(doc, broker_list, racks)
     if isinstance(capacity, dict):
         capacity = capacity_of(fi.broker_ids, capacity, default_capacity)

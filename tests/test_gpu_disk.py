@@ -13,6 +13,7 @@ import pytest
 
 import disk_ref as dr
 from conftest import ROOT
+from disk_launches import disk_launches
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFF
@@ -269,3 +270,16 @@ def test_cli_end_to_end(kao, tmp_path):
     r = subprocess.run([os.path.join(ROOT, "cli", "kao-waves"), "--current", str(cur_path), "--plan", str(tmp_path / "plain0.json"), "--sizes", str(sizes_path),
                         "--default-size", "70K", "--max-bytes-per-broker", "1M", "--out-prefix", str(tmp_path / "wave")], capture_output=True, cwd=ROOT)
     assert r.returncode == 0 and (tmp_path / "wave1.json").exists(), r.stderr
+
+
+# ---- 9. the ends of a batch of rounds --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed,max_rounds,rounds,stopped", [(25, 0, 128, 0), (1, 0, 127, 0), (11, 0, 129, 0), (25, 31, 31, 1), (25, 32, 32, 1), (25, 33, 33, 1),
+                                                            (25, 64, 64, 1), (25, 128, 128, 0), (25, 129, 128, 0)])
+def test_descent_ends_and_max_rounds_on_batch_boundaries(call, seed, max_rounds, rounds, stopped):
+    """24 brokers in 4 racks, 400 partitions, one replica per rack.  The host enqueues 32 rounds between two reads of the proposal
+    counts: seed 25 takes 128 rounds (the empty round is the first of a fifth batch), seed 1 takes 127 (the last of the fourth), seed 11
+    takes 129.  On seed 25 max_rounds falls before, on and after the end of a batch; 128 ends through the probe that finds nothing
+    left, 129 by the empty round.  stats[3] is the launch schedule of tests/disk_launches.py."""
+    res, ref = _checked(call, dr.lognormal_case(24, 4, 400, 3, 0.7, seed), cap=1, max_rounds=max_rounds)
+    assert (ref["rounds"], int(ref["more"])) == (rounds, stopped)
+    assert res.stats[3] == disk_launches(rounds, max_rounds, bool(stopped))

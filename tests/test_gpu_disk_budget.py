@@ -14,6 +14,7 @@ import pytest
 import disk_budget_ref as br
 import disk_ref as dr
 from conftest import ROOT
+from disk_launches import disk_launches
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFF
@@ -252,3 +253,18 @@ def test_cli_end_to_end(kao, tmp_path):
     r = subprocess.run([os.path.join(ROOT, "cli", "kao-waves"), "--current", str(cur_path), "--plan", str(tmp_path / "cap0.json"), "--sizes", str(sizes_path),
                         "--default-size", "70K", "--max-bytes-per-broker", "1M", "--out-prefix", str(tmp_path / "wave")], capture_output=True, cwd=ROOT)
     assert r.returncode == 0 and (tmp_path / "wave1.json").exists(), r.stderr
+
+
+# ---- 8. the ends of a batch of rounds --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_bytes,max_rounds,rounds,stopped", [(3 * 10 ** 8, 0, 87, 0), (3 * 10 ** 8, 32, 32, 1), (3 * 10 ** 8, 64, 64, 1), (3 * 10 ** 8, 87, 87, 0),
+                                                                 (3 * 10 ** 8, 88, 87, 0), (10 ** 8, 0, 23, 0)])
+def test_budget_ends_and_max_rounds_on_batch_boundaries(call, max_bytes, max_rounds, rounds, stopped):
+    """lognormal_case(24, 4, 400, 3, 0.7, 11), one replica per rack: a budget of 3e8 bytes ends the descent after 87 rounds with 3
+    winners refused, one of 1e8 after 23.  max_rounds on the end of a batch of 32 rounds, on the last round (the probe finds nothing
+    affordable, so the call was not stopped, and the unbudgeted probe follows) and past it.  stats[3] is the launch schedule of
+    tests/disk_launches.py."""
+    res, ref = _checked(call, dr.lognormal_case(24, 4, 400, 3, 0.7, 11), max_bytes, cap=1, max_rounds=max_rounds)
+    assert (ref["rounds"], int(ref["more"])) == (rounds, stopped)
+    if not stopped:
+        assert (ref["refused"], int(ref["budget_bound"])) == (3, 1)
+    assert res.stats[3] == disk_launches(rounds, max_rounds, bool(stopped), budget=True)

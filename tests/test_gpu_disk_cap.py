@@ -16,6 +16,7 @@ import pytest
 import disk_cap_ref as cr
 import disk_ref as dr
 from conftest import ROOT
+from disk_launches import disk_launches
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFF
@@ -320,3 +321,20 @@ def test_cli_end_to_end(kao, tmp_path):
     r = subprocess.run([os.path.join(ROOT, "cli", "kao-waves"), "--current", str(paths["current.json"]), "--plan", str(tmp_path / "cap0.json"), "--sizes",
                         str(paths["sizes.json"]), "--max-bytes-per-broker", "64M", "--out-prefix", str(tmp_path / "wave")], capture_output=True, cwd=ROOT)
     assert r.returncode == 0 and (tmp_path / "wave1.json").exists(), r.stderr
+
+
+# ---- 9. the ends of a batch of rounds --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed,max_bytes,max_rounds,rounds,thorough,stopped", [
+    (50, None, 0, 99, 4, 0), (59, None, 0, 97, 2, 0), (4, None, 0, 130, 0, 0), (50, None, 95, 95, 0, 1), (50, None, 96, 96, 1, 1), (50, None, 97, 97, 2, 1),
+    (50, None, 99, 99, 4, 0), (50, None, 100, 99, 4, 0), (50, 3 * 10 ** 8, 0, 51, 0, 0)])
+def test_thorough_switch_and_max_rounds_on_batch_boundaries(call, seed, max_bytes, max_rounds, rounds, thorough, stopped):
+    """lognormal_case(24, 4, 400, 3, 0.7, seed), one replica per rack, capacities of 1, 2 or 4 MB drawn with the same seed.  Seed 50:
+    the first empty FAST round is round 95, the last of a batch of 32, and the 4 THOROUGH rounds fill one batch of 4 exactly.  Seed
+    59: 2 THOROUGH rounds.  Seed 4: the switch is followed at once by an empty THOROUGH round.  On seed 50 max_rounds falls on the
+    switch, inside the THOROUGH batch, on its end (the probe finds nothing left) and past it; once more under a budget.  No seed in
+    0..119 of this family ends its FAST rounds at an exact multiple of 32.  stats[3] is the launch schedule of tests/disk_launches.py."""
+    c = dr.lognormal_case(24, 4, 400, 3, 0.7, seed)
+    capacity = np.random.default_rng(seed).choice([1, 2, 4], 24) * 10 ** 6
+    res, ref = _checked(call, c, capacity, max_bytes=max_bytes, cap=1, max_rounds=max_rounds)
+    assert (ref["rounds"], ref["thorough"], int(ref["more"])) == (rounds, thorough, stopped)
+    assert res.stats[3] == disk_launches(rounds, max_rounds, bool(stopped), budget=max_bytes is not None, capacity=True, thorough=thorough)

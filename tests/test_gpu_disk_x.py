@@ -13,6 +13,7 @@ import pytest
 import disk_ref as dr
 import disk_x_ref as dx
 from conftest import ROOT
+from disk_launches import disk_launches
 
 pytestmark = pytest.mark.gpu
 NONE = 0xFFFF
@@ -289,3 +290,15 @@ def test_cli_and_python_api_end_to_end(kao, tmp_path):
     r = subprocess.run([os.path.join(ROOT, "cli", "kao-waves"), "--current", str(cur_path), "--plan", str(tmp_path / "plain0.json"), "--sizes", str(sizes_path),
                         "--max-bytes-per-broker", "1M", "--out-prefix", str(tmp_path / "wave")], capture_output=True, cwd=ROOT)
     assert r.returncode == 0 and (tmp_path / "wave1.json").exists(), r.stderr
+
+
+# ---- 8. the ends of a batch of rounds --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_rounds,rounds,x_rounds,stopped", [(0, 437, 303, 0), (31, 31, 0, 1), (32, 32, 0, 1), (33, 33, 0, 1), (160, 160, 26, 1)])
+def test_max_rounds_on_batch_boundaries(call, max_rounds, rounds, x_rounds, stopped):
+    """lognormal_case(24, 4, 400, 3, 0.7, 11), one replica per rack: 437 rounds, 303 of them exchange rounds.  max_rounds before, on
+    and after the end of the first batch of 32 rounds, and 160, which reaches into the exchange phase (the whole descent has 134 move
+    rounds).  stats[8..11] against the restatement, stats[3] against the launch schedule of tests/disk_launches.py."""
+    res, ref = _checked(call, dr.lognormal_case(24, 4, 400, 3, 0.7, 11), cap=1, max_rounds=max_rounds, twice=False)
+    assert (ref["rounds"], ref["x_rounds"], int(ref["more"])) == (rounds, x_rounds, stopped)
+    assert res.stats[8:].tolist() == [ref["x_rounds"], ref["exchanges"], ref["x_proposals"], ref["x_peak"]]
+    assert res.stats[3] == disk_launches(rounds, max_rounds, bool(stopped), exchange=True)
