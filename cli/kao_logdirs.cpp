@@ -155,106 +155,131 @@ void warn_full(const std::vector<int> &ids, const std::vector<std::vector<const 
         }
 }
 
-// --plan / --evacuate: kao_place_logdirs (the mapping is in the head of this file).  Returns when the plan is written.
-void place(const Capacities &caps, const std::string &cur_path, const std::string &dirs_path, const std::string &plan_path, const std::vector<std::pair<int, std::string>> &evacuate,
-           bool have_list, const std::string &brokers_csv, bool rebalance, bool have_default, uint64_t default_size, uint64_t min_gain, int max_rounds,
-           bool dry_run, bool report, int device, const std::string &out_path) {
-    auto rows_of = [](const std::string &path, const char *what) {
-        std::map<Key, std::vector<int>> out;
-        const std::string txt = slurp(path);
-        const JValue doc = JParser(txt).parse();
-        const JValue *parts = doc.get("partitions");
-        for (size_t i = 0; parts && i < parts->arr.size(); ++i) {
-            const JValue &e = parts->arr[i];
-            const JValue *t = e.get("topic"), *p = e.get("partition"), *r = e.get("replicas");
-            if (!t || !p || !r || r->kind != JValue::Arr) throw std::runtime_error("partition entry needs topic/partition/replicas");
-            const Key k{t->str, (int)p->num};
-            if (out.count(k)) throw std::runtime_error(std::string(what) + ": partition " + k.first + "-" + std::to_string(k.second) + " listed twice");
-            std::vector<int> &reps = out[k];
-            for (auto &x : r->arr) reps.push_back((int)x.num);
-        }
-        return out;
-    };
-    const std::map<Key, std::vector<int>> by_key = rows_of(cur_path, "current");
-    std::map<Key, std::vector<int>> plan;
-    if (!plan_path.empty()) plan = rows_of(plan_path, "plan");
-    for (auto &kv : plan) {
+// what main makes of the flags
+struct Options {
+    std::string cur_path, dirs_path, plan_path, out_path, brokers_csv;
+    std::vector<std::pair<int, std::string>> evacuate;
+    bool have_list = false, rebalance = false, have_default = false, exchange = false, dry_run = false, report = false;
+    uint64_t default_size = 0, min_gain = 0;
+    int max_rounds = 0, device = 0;
+    Capacities caps;
+    bool placing() const { return !plan_path.empty() || !evacuate.empty(); }   // kao_place_logdirs, not kao_balance_logdirs
+};
+
+using Rows = std::map<Key, std::vector<int>>;
+
+// the rows of a reassignment document by (topic, partition)
+Rows rows_of(const std::string &path, const char *what) {
+    Rows out;
+    const std::string txt = slurp(path);
+    const JValue doc = JParser(txt).parse();
+    const JValue *parts = doc.get("partitions");
+    for (size_t i = 0; parts && i < parts->arr.size(); ++i) {
+        const JValue &e = parts->arr[i];
+        const JValue *t = e.get("topic"), *p = e.get("partition"), *r = e.get("replicas");
+        if (!t || !p || !r || r->kind != JValue::Arr) throw std::runtime_error("partition entry needs topic/partition/replicas");
+        const Key k{t->str, (int)p->num};
+        if (out.count(k)) throw std::runtime_error(std::string(what) + ": partition " + k.first + "-" + std::to_string(k.second) + " listed twice");
+        std::vector<int> &reps = out[k];
+        for (auto &x : r->arr) reps.push_back((int)x.num);
+    }
+    return out;
+}
+
+// The documents as the arrays of the call (the mapping is in the head of this file).  The balance call is the placement with no
+// plan and no evacuation: every replica a resident, nothing stranded.  Moved, never copied: the pointers go into its own maps.
+struct Slot { const Key *key; const std::vector<int> *row; int j; };
+struct Mapping {
+    std::map<int, std::vector<LogDir>> table;
+    Rows by_key, plan;
+    std::vector<int> ids, skipped;                           // per broker: its id, its dirs left out for their error
+    std::vector<std::vector<const LogDir *>> stay, gone;     // per broker: its usable dirs byte-wise ascending, the evacuated ones apart
+    std::vector<std::set<std::string>> out_of;               // per broker: the names of its evacuated dirs
+    std::vector<int32_t> dir_start{0};
+    std::vector<std::string> flat;                           // global dir index -> name
+    std::vector<int32_t> broker, dir;                        // per replica; dir -1 = homeless
+    std::vector<uint64_t> size;
+    std::vector<Slot> slots;
+    std::vector<uint64_t> base;
+    std::vector<unsigned long long> stranded;                // per broker: bytes of the entries of its evacuated dirs that are not planned
+    Mapping() = default;
+    Mapping(Mapping &&) = default;
+    Mapping(const Mapping &) = delete;
+};
+
+Mapping map_documents(const Options &o) {
+    Mapping m;
+    m.by_key = rows_of(o.cur_path, "current");
+    if (!o.plan_path.empty()) m.plan = rows_of(o.plan_path, "plan");
+    for (auto &kv : m.plan) {
         const std::string what = kv.first.first + "-" + std::to_string(kv.first.second);
-        if (!by_key.count(kv.first)) throw std::runtime_error("plan: partition " + what + " is not in the current assignment");
+        if (!m.by_key.count(kv.first)) throw std::runtime_error("plan: partition " + what + " is not in the current assignment");
         if (std::set<int>(kv.second.begin(), kv.second.end()).size() != kv.second.size()) throw std::runtime_error("plan: partition " + what + " lists a broker twice");
     }
-    const std::map<int, std::vector<LogDir>> table = load_log_dirs(dirs_path);
-    std::vector<int> ids;
-    if (have_list) {
-        for (auto &t : split(brokers_csv, ',')) if (!t.empty()) ids.push_back(std::atoi(t.c_str()));
+    m.table = load_log_dirs(o.dirs_path);
+    if (o.have_list) {
+        for (auto &t : split(o.brokers_csv, ',')) if (!t.empty()) m.ids.push_back(std::atoi(t.c_str()));
     } else {
-        for (auto &kv : table) ids.push_back(kv.first);
+        for (auto &kv : m.table) m.ids.push_back(kv.first);
     }
-    if (ids.empty()) throw std::runtime_error("empty broker list");
+    if (m.ids.empty()) throw std::runtime_error("empty broker list");
     std::map<int, int> dense;
-    for (size_t i = 0; i < ids.size(); ++i) if (!dense.emplace(ids[i], (int)i).second) throw std::runtime_error("duplicate id in broker list");
-    const int B = (int)ids.size();
-    std::vector<std::set<std::string>> out_of((size_t)B);
-    for (auto &ev : evacuate) {
+    for (size_t i = 0; i < m.ids.size(); ++i) if (!dense.emplace(m.ids[i], (int)i).second) throw std::runtime_error("duplicate id in broker list");
+    const size_t B = m.ids.size();
+    m.out_of.resize(B);
+    for (auto &ev : o.evacuate) {
         auto di = dense.find(ev.first);
-        auto it = table.find(ev.first);
+        auto it = m.table.find(ev.first);
         bool ok = false;
-        if (di != dense.end() && it != table.end())
+        if (di != dense.end() && it != m.table.end())
             for (auto &d : it->second) ok |= d.name == ev.second && !d.failed;
         if (!ok) throw std::runtime_error("evacuate: " + std::to_string(ev.first) + ":" + ev.second + " is not a usable log dir of a listed broker");
-        out_of[(size_t)di->second].insert(ev.second);
+        m.out_of[(size_t)di->second].insert(ev.second);
     }
     std::map<Key, uint64_t> psize;   // the largest non-future size of a partition anywhere: the size of an arrival
-    for (auto &kv : table)
+    for (auto &kv : m.table)
         for (auto &d : kv.second)
             for (auto &e : d.entries)
                 if (!e.future) { uint64_t &x = psize[e.key]; x = std::max(x, e.size); }
 
     // the usable dirs of every broker, byte-wise ascending, without the evacuated ones; where each partition sits on it
     struct Held { int dir; uint64_t size; };
-    std::vector<std::vector<const LogDir *>> stay((size_t)B), gone((size_t)B);
-    std::vector<int> skipped((size_t)B, 0);
-    std::vector<int32_t> dir_start(1, 0);
-    std::vector<std::map<Key, Held>> where((size_t)B);
-    std::vector<std::map<Key, uint64_t>> leaving((size_t)B);
-    std::vector<std::string> flat;   // global dir index -> name
-    for (int i = 0; i < B; ++i) {
+    m.stay.resize(B);
+    m.gone.resize(B);
+    m.skipped.assign(B, 0);
+    std::vector<std::map<Key, Held>> where(B);
+    std::vector<std::map<Key, uint64_t>> leaving(B);
+    for (size_t i = 0; i < B; ++i) {
         std::vector<const LogDir *> usable;
-        auto it = table.find(ids[(size_t)i]);
-        if (it != table.end())
+        auto it = m.table.find(m.ids[i]);
+        if (it != m.table.end())
             for (auto &d : it->second) {
-                if (d.failed) ++skipped[(size_t)i];
+                if (d.failed) ++m.skipped[i];
                 else usable.push_back(&d);
             }
         std::sort(usable.begin(), usable.end(), [](const LogDir *x, const LogDir *y) { return x->name < y->name; });
-        for (auto *d : usable) (out_of[(size_t)i].count(d->name) ? gone : stay)[(size_t)i].push_back(d);
-        if (!out_of[(size_t)i].empty() && stay[(size_t)i].empty())
-            throw std::runtime_error("evacuate: broker " + std::to_string(ids[(size_t)i]) + " is left without a usable log dir");
+        for (auto *d : usable) (m.out_of[i].count(d->name) ? m.gone : m.stay)[i].push_back(d);
+        if (!m.out_of[i].empty() && m.stay[i].empty()) throw std::runtime_error("evacuate: broker " + std::to_string(m.ids[i]) + " is left without a usable log dir");
         for (auto *d : usable) {
-            const bool out = out_of[(size_t)i].count(d->name) != 0;
-            const int li = out ? 0 : (int)(std::find(stay[(size_t)i].begin(), stay[(size_t)i].end(), d) - stay[(size_t)i].begin());
+            const bool out = m.out_of[i].count(d->name) != 0;
+            const int li = out ? 0 : (int)(std::find(m.stay[i].begin(), m.stay[i].end(), d) - m.stay[i].begin());
             for (auto &e : d->entries) {
                 if (e.future) continue;
-                if (where[(size_t)i].count(e.key) || leaving[(size_t)i].count(e.key))
-                    throw std::runtime_error("log-dirs: broker " + std::to_string(ids[(size_t)i]) + " holds partition " + e.key.first + "-" + std::to_string(e.key.second) + " twice");
-                if (out) leaving[(size_t)i][e.key] = e.size;
-                else where[(size_t)i][e.key] = Held{dir_start.back() + li, e.size};
+                if (where[i].count(e.key) || leaving[i].count(e.key))
+                    throw std::runtime_error("log-dirs: broker " + std::to_string(m.ids[i]) + " holds partition " + e.key.first + "-" + std::to_string(e.key.second) + " twice");
+                if (out) leaving[i][e.key] = e.size;
+                else where[i][e.key] = Held{m.dir_start.back() + li, e.size};
             }
         }
-        for (auto *d : stay[(size_t)i]) flat.push_back(d->name);
-        dir_start.push_back(dir_start.back() + (int32_t)stay[(size_t)i].size());
+        for (auto *d : m.stay[i]) m.flat.push_back(d->name);
+        m.dir_start.push_back(m.dir_start.back() + (int32_t)m.stay[i].size());
     }
-    const int D = dir_start.back();
 
     // the replicas: residents, and the homeless ones (dir -1) of evacuated dirs and of the plan's arrivals
-    struct Slot { const Key *key; const std::vector<int> *row; int j; };
-    std::vector<int32_t> broker, dir;
-    std::vector<uint64_t> size;
-    std::vector<Slot> slots;
     std::set<std::pair<int, Key>> claimed, rescued, departed;
-    for (auto &kv : by_key) {
-        auto pl = plan.find(kv.first);
-        const std::vector<int> &row = pl == plan.end() ? kv.second : pl->second;
+    for (auto &kv : m.by_key) {
+        auto pl = m.plan.find(kv.first);
+        const std::vector<int> &row = pl == m.plan.end() ? kv.second : pl->second;
         const std::set<int> was(kv.second.begin(), kv.second.end());
         for (int x : was)
             if (std::find(row.begin(), row.end(), x) == row.end() && dense.count(x)) departed.insert({dense[x], kv.first});
@@ -275,110 +300,165 @@ void place(const Capacities &caps, const std::string &cur_path, const std::strin
                 sz = h->second.size;
                 claimed.insert({di->second, kv.first});
             } else {   // an arrival
-                if (stay[i].empty()) continue;
+                if (m.stay[i].empty()) continue;
                 auto ps = psize.find(kv.first);
                 if (ps != psize.end()) sz = ps->second;
-                else if (have_default) sz = default_size;
+                else if (o.have_default) sz = o.default_size;
                 else
                     throw std::runtime_error("log-dirs: no size for partition " + kv.first.first + "-" + std::to_string(kv.first.second) + ", which the plan brings to broker " +
                                              std::to_string(row[j]) + " (give a default size)");
             }
-            broker.push_back(di->second);
-            dir.push_back(d);
-            size.push_back(sz);
-            slots.push_back(Slot{&kv.first, &row, (int)j});
+            m.broker.push_back(di->second);
+            m.dir.push_back(d);
+            m.size.push_back(sz);
+            m.slots.push_back(Slot{&kv.first, &row, (int)j});
         }
     }
-    std::vector<uint64_t> base((size_t)std::max(D, 1), 0);
-    std::vector<unsigned long long> stranded((size_t)B, 0);
-    for (int i = 0; i < B; ++i) {
-        for (size_t li = 0; li < stay[(size_t)i].size(); ++li)
-            for (auto &e : stay[(size_t)i][li]->entries) {
-                if (!e.future && departed.count({i, e.key})) continue;
-                if (e.future || !claimed.count({i, e.key})) base[(size_t)dir_start[(size_t)i] + li] += e.size;
+    m.base.assign((size_t)std::max(m.dir_start.back(), 1), 0);
+    m.stranded.assign(B, 0);
+    for (size_t i = 0; i < B; ++i) {
+        for (size_t li = 0; li < m.stay[i].size(); ++li)
+            for (auto &e : m.stay[i][li]->entries) {
+                if (!e.future && departed.count({(int)i, e.key})) continue;
+                if (e.future || !claimed.count({(int)i, e.key})) m.base[(size_t)m.dir_start[i] + li] += e.size;
             }
-        for (auto *d : gone[(size_t)i])
+        for (auto *d : m.gone[i])
             for (auto &e : d->entries)
-                if (e.future || !rescued.count({i, e.key})) stranded[(size_t)i] += e.size;
+                if (e.future || !rescued.count({(int)i, e.key})) m.stranded[i] += e.size;
     }
-    const int R = (int)dir.size();
-    const std::vector<int32_t> dir0 = dir;
-    if (dir.empty()) { broker.push_back(0); dir.push_back(0); size.push_back(0); }   // the library takes no null pointer
-    const std::vector<uint64_t> cap = caps.on ? dir_capacities(caps, ids, stay) : std::vector<uint64_t>();
+    return m;
+}
 
-    int rc = kao_init(device);
-    if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+// what a call gives back; a call by bytes writes the first word of a peak alone
+struct Called {
     int32_t n_placed = 0, n_moved = 0, status = 0;
     uint64_t bytes_placed = 0, bytes_moved = 0, before[2] = {0, 1}, after[2] = {0, 1};
-    int64_t stats[10] = {0};
-    const size_t W = caps.on ? 12 : 8;
-    std::vector<uint64_t> per((size_t)B * W, 0);
-    if (caps.on) {
-        rc = kao_place_logdirs_capacity(B, dir_start.data(), base.data(), cap.data(), R, broker.data(), dir.data(), size.data(), rebalance ? 1 : 0, min_gain,
-                                        max_rounds, dry_run ? 1 : 0, &n_placed, &bytes_placed, &n_moved, &bytes_moved, before, after, per.data(), &status, stats);
-        if (rc) throw std::runtime_error(std::string("kao_place_logdirs_capacity: ") + kao_strerror(rc) + " " + kao_last_error());
-    } else {
-        rc = kao_place_logdirs(B, dir_start.data(), base.data(), R, broker.data(), dir.data(), size.data(), rebalance ? 1 : 0, min_gain, max_rounds, dry_run ? 1 : 0,
-                               &n_placed, &bytes_placed, &n_moved, &bytes_moved, before, after, per.data(), &status, stats);
-        if (rc) throw std::runtime_error(std::string("kao_place_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
+    int64_t stats[12] = {0};
+    std::vector<uint64_t> per;   // [B, W]
+    size_t W = 0;
+};
+
+// the entry points and the words of a broker's row in per_broker[]
+enum { BALANCE, EXCHANGE, BALANCE_CAPACITY, PLACE, PLACE_CAPACITY };
+struct Entry { const char *name; size_t per; };
+const Entry ENTRIES[] = {{"kao_balance_logdirs", 6}, {"kao_balance_logdirs_exchange", 8}, {"kao_balance_logdirs_capacity", 10}, {"kao_place_logdirs", 8},
+                         {"kao_place_logdirs_capacity", 12}};
+
+// the one call of the library: the five entry points take their arrays in one order, the balance ones without broker[]
+Called call(const Options &o, Mapping &m, const std::vector<uint64_t> &cap) {
+    const int B = (int)m.ids.size(), R = (int)m.dir.size(), dry = o.dry_run ? 1 : 0;
+    if (m.dir.empty()) { m.broker.push_back(0); m.dir.push_back(0); m.size.push_back(0); }   // the library takes no null pointer
+    const int32_t *ds = m.dir_start.data(), *br = m.broker.data();
+    const uint64_t *bs = m.base.data(), *sz = m.size.data();
+    int32_t *dir = m.dir.data();
+    const int entry = o.placing() ? (o.caps.on ? PLACE_CAPACITY : PLACE) : o.caps.on ? BALANCE_CAPACITY : o.exchange ? EXCHANGE : BALANCE;
+    const char *const name = ENTRIES[entry].name;
+    Called c;
+    c.W = ENTRIES[entry].per;
+    c.per.assign((size_t)B * c.W, 0);
+    int rc;
+    switch (entry) {
+    case BALANCE:
+        rc = kao_balance_logdirs(B, ds, bs, R, dir, sz, o.min_gain, o.max_rounds, dry, &c.n_moved, &c.bytes_moved, c.before, c.after, c.per.data(), &c.status, c.stats);
+        break;
+    case EXCHANGE:
+        rc = kao_balance_logdirs_exchange(B, ds, bs, R, dir, sz, o.min_gain, o.max_rounds, dry, &c.n_moved, &c.bytes_moved, c.before, c.after, c.per.data(), &c.status,
+                                          c.stats);
+        break;
+    case BALANCE_CAPACITY:
+        rc = kao_balance_logdirs_capacity(B, ds, bs, cap.data(), R, dir, sz, o.min_gain, o.max_rounds, dry, &c.n_moved, &c.bytes_moved, c.before, c.after, c.per.data(),
+                                          &c.status, c.stats);
+        break;
+    case PLACE:
+        rc = kao_place_logdirs(B, ds, bs, R, br, dir, sz, o.rebalance ? 1 : 0, o.min_gain, o.max_rounds, dry, &c.n_placed, &c.bytes_placed, &c.n_moved, &c.bytes_moved,
+                               c.before, c.after, c.per.data(), &c.status, c.stats);
+        break;
+    default:   // PLACE_CAPACITY
+        rc = kao_place_logdirs_capacity(B, ds, bs, cap.data(), R, br, dir, sz, o.rebalance ? 1 : 0, o.min_gain, o.max_rounds, dry, &c.n_placed, &c.bytes_placed,
+                                        &c.n_moved, &c.bytes_moved, c.before, c.after, c.per.data(), &c.status, c.stats);
     }
-    if (report) {
-        if (caps.on) warn_full(ids, stay, dir_start, base, cap);
-        std::vector<int> residents((size_t)B, 0), homeless((size_t)B, 0);
-        unsigned long long total = 0, all_skipped = 0, all_out = 0, all_stranded = 0;
-        int all_res = 0, all_home = 0;
-        for (int r = 0; r < R; ++r) {
-            ++(dir0[(size_t)r] < 0 ? homeless : residents)[(size_t)broker[(size_t)r]];
-            ++(dir0[(size_t)r] < 0 ? all_home : all_res);
-            total += size[(size_t)r];
-        }
-        for (int d = 0; d < D; ++d) total += base[(size_t)d];
-        for (int i = 0; i < B; ++i) {
-            const uint64_t *q = per.data() + (size_t)i * W;
-            // with capacities {peak_before, cap, peak_after, cap, bound num, den, placed, bytes_placed, moved, bytes_moved, rounds, proof}
-            const uint64_t p[8] = {q[0], caps.on ? q[2] : q[1], caps.on ? q[4] : q[2], caps.on ? q[6] : q[3], caps.on ? q[7] : q[4], caps.on ? q[8] : q[5],
-                                   caps.on ? q[9] : q[6], caps.on ? q[10] : q[7]};
-            all_skipped += (unsigned long long)skipped[(size_t)i];
-            all_out += (unsigned long long)out_of[(size_t)i].size();
-            all_stranded += stranded[(size_t)i];
-            std::fprintf(stderr, "logdirs: broker=%d dirs=%d skipped_dirs=%d evacuated_dirs=%d replicas=%d residents=%d homeless=%d peak_before=%llu peak_after=%llu "
-                                 "lower_bound=%llu placed=%llu bytes_placed=%llu moved=%llu bytes_moved=%llu rounds=%llu stranded_bytes=%llu",
-                         ids[(size_t)i], (int)stay[(size_t)i].size(), skipped[(size_t)i], (int)out_of[(size_t)i].size(), residents[(size_t)i] + homeless[(size_t)i],
-                         residents[(size_t)i], homeless[(size_t)i], (unsigned long long)p[0], (unsigned long long)p[1], (unsigned long long)p[2], (unsigned long long)p[3],
-                         (unsigned long long)p[4], (unsigned long long)p[5], (unsigned long long)p[6], (unsigned long long)p[7], stranded[(size_t)i]);
-            if (caps.on)
-                std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s lower_bound_ppm=%s proof=%llu", ppm(q[0], q[1]).c_str(), ppm(q[2], q[3]).c_str(),
-                             ppm(q[4], q[5]).c_str(), (unsigned long long)q[11]);
-            std::fprintf(stderr, "\n");
-        }
-        std::fprintf(stderr, "logdirs: status=%s brokers=%d dirs=%d skipped_dirs=%llu evacuated_dirs=%llu replicas=%d residents=%d homeless=%d peak_before=%llu "
-                             "peak_after=%llu replicas_placed=%d bytes_placed=%llu replicas_moved=%d bytes_moved=%llu bytes_total=%llu stranded_bytes=%llu "
-                             "brokers_placed=%lld brokers_moved=%lld rounds=%lld moves=%lld proposals=%lld launches=%lld stopped_by_max_rounds=%lld proven=%lld "
-                             "max_rounds_of_a_broker=%lld max_homeless_of_a_broker=%lld",
-                     status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, all_out, R, all_res, all_home,
-                     (unsigned long long)before[0], (unsigned long long)after[0], n_placed, (unsigned long long)bytes_placed, n_moved, (unsigned long long)bytes_moved, total,
-                     all_stranded, (long long)stats[0], (long long)stats[1], (long long)stats[2], (long long)stats[3], (long long)stats[4], (long long)stats[5],
-                     (long long)stats[6], (long long)stats[7], (long long)stats[8], (long long)stats[9]);
-        if (caps.on) std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s", ppm(before[0], before[1]).c_str(), ppm(after[0], after[1]).c_str());
-        std::fprintf(stderr, "\n");
+    if (rc) throw std::runtime_error(std::string(name) + ": " + kao_strerror(rc) + " " + kao_last_error());
+    return c;
+}
+
+// the names of a broker's columns once the capacity words are folded away, and of stats[]
+const char *const BALANCE_COLUMNS[] = {"peak_before", "peak_after", "lower_bound", "moved", "bytes_moved", "rounds"};
+const char *const PLACE_COLUMNS[] = {"peak_before", "peak_after", "lower_bound", "placed", "bytes_placed", "moved", "bytes_moved", "rounds"};
+const char *const STAT_KEYS[] = {"brokers_moved", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven", "max_rounds_of_a_broker",
+                                 "exchange_rounds", "exchanges", "exchange_proposals", "brokers_lowered_by_exchange"};   // the last four with --exchange
+const char *const PLACE_STAT_KEYS[] = {"brokers_placed", "brokers_moved", "rounds", "moves", "proposals", "launches", "stopped_by_max_rounds", "proven",
+                                       "max_rounds_of_a_broker", "max_homeless_of_a_broker"};
+
+template <class T> void field(std::string &line, const char *key, T value) { line += std::string(" ") + key + "=" + std::to_string(value); }
+
+// --report: one line per broker and one for the call, to stderr.  dir0 is dir[] as the mapping made it.
+void report(const Options &o, const Mapping &m, const std::vector<int32_t> &dir0, const std::vector<uint64_t> &cap, const Called &c) {
+    const bool placing = o.placing(), by_cap = o.caps.on;
+    const size_t B = m.ids.size(), n_cols = placing ? 8 : 6;
+    if (by_cap) warn_full(m.ids, m.stay, m.dir_start, m.base, cap);
+    std::vector<int> residents(B, 0), homeless(B, 0);
+    unsigned long long total = 0, all_skipped = 0, all_out = 0, all_stranded = 0;
+    int all_home = 0;
+    for (size_t r = 0; r < dir0.size(); ++r) {
+        ++(dir0[r] < 0 ? homeless : residents)[(size_t)m.broker[r]];
+        all_home += dir0[r] < 0;
+        total += m.size[r];
     }
-    // the partitions of the plan and those with a placed or moved replica, in (topic, partition) order
+    for (int d = 0; d < m.dir_start.back(); ++d) total += m.base[(size_t)d];
+    for (size_t i = 0; i < B; ++i) {
+        const uint64_t *q = c.per.data() + i * c.W;   // with capacities {peak_before, cap, peak_after, cap, bound num, den, <the other columns>, proof}
+        all_skipped += (unsigned long long)m.skipped[i];
+        all_out += m.out_of[i].size();
+        all_stranded += m.stranded[i];
+        std::string line = "logdirs: broker=" + std::to_string(m.ids[i]);
+        field(line, "dirs", m.stay[i].size());
+        field(line, "skipped_dirs", m.skipped[i]);
+        if (placing) field(line, "evacuated_dirs", m.out_of[i].size());
+        field(line, "replicas", residents[i] + homeless[i]);
+        if (placing) { field(line, "residents", residents[i]); field(line, "homeless", homeless[i]); }
+        for (size_t k = 0; k < n_cols; ++k) field(line, (placing ? PLACE_COLUMNS : BALANCE_COLUMNS)[k], !by_cap ? q[k] : k < 3 ? q[2 * k] : q[k + 3]);
+        if (placing) field(line, "stranded_bytes", m.stranded[i]);
+        if (by_cap) line += " peak_before_ppm=" + ppm(q[0], q[1]) + " peak_after_ppm=" + ppm(q[2], q[3]) + " lower_bound_ppm=" + ppm(q[4], q[5]) + " proof=" + std::to_string(q[c.W - 1]);
+        if (o.exchange) { field(line, "exchange_rounds", q[6]); field(line, "exchanges", q[7]); }
+        std::fprintf(stderr, "%s\n", line.c_str());
+    }
+    std::string line = std::string("logdirs: status=") + (c.status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP");
+    field(line, "brokers", B);
+    field(line, "dirs", m.dir_start.back());
+    field(line, "skipped_dirs", all_skipped);
+    if (placing) field(line, "evacuated_dirs", all_out);
+    field(line, "replicas", dir0.size());
+    if (placing) { field(line, "residents", (int)dir0.size() - all_home); field(line, "homeless", all_home); }
+    field(line, "peak_before", c.before[0]);
+    field(line, "peak_after", c.after[0]);
+    if (placing) { field(line, "replicas_placed", c.n_placed); field(line, "bytes_placed", c.bytes_placed); }
+    field(line, "replicas_moved", c.n_moved);
+    field(line, "bytes_moved", c.bytes_moved);
+    field(line, "bytes_total", total);
+    if (placing) field(line, "stranded_bytes", all_stranded);
+    for (size_t k = 0; k < (placing ? 10u : o.exchange ? 12u : 8u); ++k) field(line, (placing ? PLACE_STAT_KEYS : STAT_KEYS)[k], c.stats[k]);
+    if (by_cap) line += " peak_before_ppm=" + ppm(c.before[0], c.before[1]) + " peak_after_ppm=" + ppm(c.after[0], c.after[1]);
+    std::fprintf(stderr, "%s\n", line.c_str());
+}
+
+// the partitions of the plan and those with a placed or moved replica, in (topic, partition) order; none with --dry-run
+void write_plan(const Options &o, const Mapping &m, const std::vector<int32_t> &dir0) {
     std::map<Key, std::vector<std::string>> lists;
-    if (!dry_run) {
-        for (auto &kv : plan) lists[kv.first] = std::vector<std::string>(kv.second.size(), "any");
-        for (int r = 0; r < R; ++r) {
-            if (dir[(size_t)r] == dir0[(size_t)r]) continue;
-            const Slot &sl = slots[(size_t)r];
+    if (!o.dry_run) {
+        for (auto &kv : m.plan) lists[kv.first] = std::vector<std::string>(kv.second.size(), "any");
+        for (size_t r = 0; r < dir0.size(); ++r) {
+            if (m.dir[r] == dir0[r]) continue;
+            const Slot &sl = m.slots[r];
             auto it = lists.find(*sl.key);
             if (it == lists.end()) it = lists.emplace(*sl.key, std::vector<std::string>(sl.row->size(), "any")).first;
-            it->second[(size_t)sl.j] = flat[(size_t)dir[(size_t)r]];
+            it->second[(size_t)sl.j] = m.flat[(size_t)m.dir[r]];
         }
     }
     std::string body;
     int n_out = 0;
     for (auto &kv : lists) {
-        auto pl = plan.find(kv.first);
-        const std::vector<int> &row = pl == plan.end() ? by_key.at(kv.first) : pl->second;
+        auto pl = m.plan.find(kv.first);
+        const std::vector<int> &row = pl == m.plan.end() ? m.by_key.at(kv.first) : pl->second;
         body += (n_out++ ? ",\n" : "\n");
         body += "    {\"topic\":" + quoted(kv.first.first) + ",\"partition\":" + std::to_string(kv.first.second) + ",\"replicas\":[";
         for (size_t k = 0; k < row.size(); ++k) body += (k ? "," : "") + std::to_string(row[k]);
@@ -386,36 +466,43 @@ void place(const Capacities &caps, const std::string &cur_path, const std::strin
         for (size_t k = 0; k < kv.second.size(); ++k) body += (k ? "," : "") + quoted(kv.second[k]);
         body += "]}";
     }
-    std::ofstream f(out_path);
+    std::ofstream f(o.out_path);
     f << "{\"version\":1,\"partitions\":[" << body << "\n]}\n";
     f.close();
-    if (!f) throw std::runtime_error("cannot write " + out_path);
+    if (!f) throw std::runtime_error("cannot write " + o.out_path);
+}
+
+// documents -> arrays -> the call -> report -> plan; every input error comes before the device is touched
+void run(const Options &o) {
+    Mapping m = map_documents(o);
+    const std::vector<uint64_t> cap = o.caps.on ? dir_capacities(o.caps, m.ids, m.stay) : std::vector<uint64_t>();
+    const std::vector<int32_t> dir0 = m.dir;
+    const int rc = kao_init(o.device);
+    if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+    const Called c = call(o, m, cap);
+    if (o.report) report(o, m, dir0, cap, c);
+    write_plan(o, m, dir0);
     kao_shutdown();
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string cur_path, brokers_csv, out_path, dirs_path, plan_path;
-    std::vector<std::pair<int, std::string>> evacuate;
-    int device = 0, max_rounds = 0;
-    bool report = false, dry_run = false, have_list = false, rebalance = false, have_default = false, exchange = false;
-    uint64_t min_gain = 0, default_size = 0;
-    Capacities caps;
+    Options o;
     std::string caps_path;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
-        if (a == "--current") cur_path = need("--current");
-        else if (a == "--log-dirs") dirs_path = need("--log-dirs");
-        else if (a == "--broker-list") { brokers_csv = need("--broker-list"); have_list = true; }
-        else if (a == "--out") out_path = need("--out");
-        else if (a == "--dry-run") dry_run = true;
-        else if (a == "--device") device = std::atoi(need("--device").c_str());
-        else if (a == "--report") report = true;
-        else if (a == "--plan") plan_path = need("--plan");
-        else if (a == "--rebalance") rebalance = true;
-        else if (a == "--exchange") exchange = true;
+        if (a == "--current") o.cur_path = need("--current");
+        else if (a == "--log-dirs") o.dirs_path = need("--log-dirs");
+        else if (a == "--broker-list") { o.brokers_csv = need("--broker-list"); o.have_list = true; }
+        else if (a == "--out") o.out_path = need("--out");
+        else if (a == "--dry-run") o.dry_run = true;
+        else if (a == "--device") o.device = std::atoi(need("--device").c_str());
+        else if (a == "--report") o.report = true;
+        else if (a == "--plan") o.plan_path = need("--plan");
+        else if (a == "--rebalance") o.rebalance = true;
+        else if (a == "--exchange") o.exchange = true;
         else if (a == "--evacuate") {
             const std::string v = need("--evacuate");
             const size_t colon = v.find(':');
@@ -423,212 +510,45 @@ int main(int argc, char **argv) {
             const std::string digits = !b.empty() && b[0] == '-' ? b.substr(1) : b;
             if (colon == std::string::npos || colon + 1 >= v.size() || digits.empty() || b.size() > 10 || digits.find_first_not_of("0123456789") != std::string::npos)
                 usage("--evacuate needs BROKER:DIR");
-            evacuate.emplace_back(std::atoi(b.c_str()), v.substr(colon + 1));
+            o.evacuate.emplace_back(std::atoi(b.c_str()), v.substr(colon + 1));
         } else if (a == "--default-size") {
-            if (!parse_bytes(need("--default-size"), default_size)) usage("--default-size needs a byte count (N, or N with K/M/G/T)");
-            have_default = true;
+            if (!parse_bytes(need("--default-size"), o.default_size)) usage("--default-size needs a byte count (N, or N with K/M/G/T)");
+            o.have_default = true;
         } else if (a == "--utilisation") {
-            caps.utilisation = true;
+            o.caps.utilisation = true;
         } else if (a == "--capacities") {
             caps_path = need("--capacities");
         } else if (a == "--default-capacity") {
-            if (!parse_bytes(need("--default-capacity"), caps.default_cap)) usage("--default-capacity needs a byte count (N, or N with K/M/G/T)");
-            caps.have_default = true;
+            if (!parse_bytes(need("--default-capacity"), o.caps.default_cap)) usage("--default-capacity needs a byte count (N, or N with K/M/G/T)");
+            o.caps.have_default = true;
         } else if (a == "--min-gain") {
-            if (!parse_bytes(need("--min-gain"), min_gain)) usage("--min-gain needs a byte count (N, or N with K/M/G/T)");
+            if (!parse_bytes(need("--min-gain"), o.min_gain)) usage("--min-gain needs a byte count (N, or N with K/M/G/T)");
         } else if (a == "--max-rounds") {
             const std::string v = need("--max-rounds");
             if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage("--max-rounds needs a value >= 0");
-            max_rounds = std::atoi(v.c_str());
+            o.max_rounds = std::atoi(v.c_str());
         } else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown flag " + a).c_str());
     }
-    if (cur_path.empty() || dirs_path.empty() || out_path.empty()) usage("--current, --log-dirs and --out are required");
-    const bool placing = !plan_path.empty() || !evacuate.empty();
-    if ((rebalance || have_default) && !placing) usage("--rebalance and --default-size need --plan or --evacuate");
-    caps.on = caps.utilisation || !caps_path.empty() || caps.have_default;
-    if (exchange && (placing || caps.on))
+    if (o.cur_path.empty() || o.dirs_path.empty() || o.out_path.empty()) usage("--current, --log-dirs and --out are required");
+    if ((o.rebalance || o.have_default) && !o.placing()) usage("--rebalance and --default-size need --plan or --evacuate");
+    o.caps.on = o.caps.utilisation || !caps_path.empty() || o.caps.have_default;
+    if (o.exchange && (o.placing() || o.caps.on))
         usage("--exchange cannot be combined with --utilisation, --capacities, --default-capacity, --plan, --evacuate or --rebalance");
     if (!caps_path.empty()) {
         std::string msg;
         try {
-            read_capacities(caps_path, caps);
+            read_capacities(caps_path, o.caps);
         } catch (const std::exception &e) {
             msg = std::string("--capacities: ") + e.what();
         }
         if (!msg.empty()) usage(msg.c_str());
     }
     try {
-        if (placing) {
-            place(caps, cur_path, dirs_path, plan_path, evacuate, have_list, brokers_csv, rebalance, have_default, default_size, min_gain, max_rounds, dry_run, report, device,
-                  out_path);
-            return 0;
-        }
-        // the rows of --current by (topic, partition)
-        std::map<Key, std::vector<int>> by_key;
-        {
-            const std::string txt = slurp(cur_path);
-            const JValue doc = JParser(txt).parse();
-            const JValue *parts = doc.get("partitions");
-            for (size_t i = 0; parts && i < parts->arr.size(); ++i) {
-                const JValue &e = parts->arr[i];
-                const JValue *t = e.get("topic"), *p = e.get("partition"), *r = e.get("replicas");
-                if (!t || !p || !r || r->kind != JValue::Arr) throw std::runtime_error("partition entry needs topic/partition/replicas");
-                const Key k{t->str, (int)p->num};
-                if (by_key.count(k)) throw std::runtime_error("current: partition " + k.first + "-" + std::to_string(k.second) + " listed twice");
-                std::vector<int> &reps = by_key[k];
-                for (auto &x : r->arr) reps.push_back((int)x.num);
-            }
-        }
-        const std::map<int, std::vector<LogDir>> table = load_log_dirs(dirs_path);
-        std::vector<int> ids;
-        if (have_list) {
-            for (auto &t : split(brokers_csv, ',')) if (!t.empty()) ids.push_back(std::atoi(t.c_str()));
-        } else {
-            for (auto &kv : table) ids.push_back(kv.first);
-        }
-        if (ids.empty()) throw std::runtime_error("empty broker list");
-        std::map<int, int> dense;
-        for (size_t i = 0; i < ids.size(); ++i) if (!dense.emplace(ids[i], (int)i).second) throw std::runtime_error("duplicate id in broker list");
-        const int B = (int)ids.size();
-
-        // the usable dirs of every broker, byte-wise ascending; where each partition sits on it
-        struct Held { int dir; uint64_t size; };
-        std::vector<std::vector<const LogDir *>> usable((size_t)B);
-        std::vector<int> skipped((size_t)B, 0);
-        std::vector<int32_t> dir_start(1, 0);
-        std::vector<std::map<Key, Held>> where((size_t)B);
-        std::vector<std::string> flat;   // global dir index -> name
-        for (int i = 0; i < B; ++i) {
-            auto it = table.find(ids[(size_t)i]);
-            if (it != table.end())
-                for (auto &d : it->second) {
-                    if (d.failed) ++skipped[(size_t)i];
-                    else usable[(size_t)i].push_back(&d);
-                }
-            std::sort(usable[(size_t)i].begin(), usable[(size_t)i].end(), [](const LogDir *x, const LogDir *y) { return x->name < y->name; });
-            for (size_t li = 0; li < usable[(size_t)i].size(); ++li) {
-                flat.push_back(usable[(size_t)i][li]->name);
-                for (auto &e : usable[(size_t)i][li]->entries) {
-                    if (e.future) continue;
-                    if (!where[(size_t)i].emplace(e.key, Held{dir_start.back() + (int)li, e.size}).second)
-                        throw std::runtime_error("log-dirs: broker " + std::to_string(ids[(size_t)i]) + " holds partition " + e.key.first + "-" + std::to_string(e.key.second) + " twice");
-                }
-            }
-            dir_start.push_back(dir_start.back() + (int32_t)usable[(size_t)i].size());
-        }
-        const int D = dir_start.back();
-
-        // the movable replicas; every other entry of a usable dir is base
-        struct Slot { const Key *key; const std::vector<int> *row; int j; };
-        std::vector<int32_t> dir;
-        std::vector<uint64_t> size;
-        std::vector<Slot> slots;
-        std::set<std::pair<int, Key>> claimed;
-        for (auto &kv : by_key)
-            for (size_t j = 0; j < kv.second.size(); ++j) {
-                auto di = dense.find(kv.second[j]);
-                if (di == dense.end()) continue;
-                auto h = where[(size_t)di->second].find(kv.first);
-                if (h == where[(size_t)di->second].end()) continue;
-                dir.push_back(h->second.dir);
-                size.push_back(h->second.size);
-                slots.push_back(Slot{&kv.first, &kv.second, (int)j});
-                claimed.insert({di->second, kv.first});
-            }
-        std::vector<uint64_t> base((size_t)std::max(D, 1), 0);
-        for (int i = 0; i < B; ++i)
-            for (size_t li = 0; li < usable[(size_t)i].size(); ++li)
-                for (auto &e : usable[(size_t)i][li]->entries)
-                    if (e.future || !claimed.count({i, e.key})) base[(size_t)dir_start[(size_t)i] + li] += e.size;
-        const int R = (int)dir.size();
-        const std::vector<int32_t> dir0 = dir;
-        if (dir.empty()) { dir.push_back(0); size.push_back(0); }   // the library takes no null pointer
-        const std::vector<uint64_t> cap = caps.on ? dir_capacities(caps, ids, usable) : std::vector<uint64_t>();
-
-        int rc = kao_init(device);
-        if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
-        int32_t n_moved = 0, status = 0;
-        uint64_t bytes_moved = 0, before[2] = {0, 1}, after[2] = {0, 1};
-        int64_t stats[12] = {0};
-        const size_t W = caps.on ? 10 : exchange ? 8 : 6;
-        std::vector<uint64_t> per((size_t)B * W, 0);
-        if (exchange) {
-            rc = kao_balance_logdirs_exchange(B, dir_start.data(), base.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved,
-                                              &bytes_moved, before, after, per.data(), &status, stats);
-            if (rc) throw std::runtime_error(std::string("kao_balance_logdirs_exchange: ") + kao_strerror(rc) + " " + kao_last_error());
-        } else if (caps.on) {
-            rc = kao_balance_logdirs_capacity(B, dir_start.data(), base.data(), cap.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved,
-                                              &bytes_moved, before, after, per.data(), &status, stats);
-            if (rc) throw std::runtime_error(std::string("kao_balance_logdirs_capacity: ") + kao_strerror(rc) + " " + kao_last_error());
-        } else {
-            rc = kao_balance_logdirs(B, dir_start.data(), base.data(), R, dir.data(), size.data(), min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved,
-                                     before, after, per.data(), &status, stats);
-            if (rc) throw std::runtime_error(std::string("kao_balance_logdirs: ") + kao_strerror(rc) + " " + kao_last_error());
-        }
-        if (report) {
-            if (caps.on) warn_full(ids, usable, dir_start, base, cap);
-            std::vector<int> replicas((size_t)B, 0);
-            for (int r = 0; r < R; ++r) ++replicas[(size_t)(std::upper_bound(dir_start.begin(), dir_start.end(), dir0[(size_t)r]) - dir_start.begin() - 1)];
-            unsigned long long total = 0, all_skipped = 0;
-            for (int r = 0; r < R; ++r) total += size[(size_t)r];
-            for (int d = 0; d < D; ++d) total += base[(size_t)d];
-            for (int i = 0; i < B; ++i) {
-                const uint64_t *q = per.data() + (size_t)i * W;
-                // with capacities {peak_before, cap, peak_after, cap, bound num, den, moved, bytes_moved, rounds, proof}
-                const uint64_t p[6] = {q[0], caps.on ? q[2] : q[1], caps.on ? q[4] : q[2], caps.on ? q[6] : q[3], caps.on ? q[7] : q[4], caps.on ? q[8] : q[5]};
-                all_skipped += (unsigned long long)skipped[(size_t)i];
-                std::fprintf(stderr, "logdirs: broker=%d dirs=%d skipped_dirs=%d replicas=%d peak_before=%llu peak_after=%llu lower_bound=%llu moved=%llu "
-                                     "bytes_moved=%llu rounds=%llu",
-                             ids[(size_t)i], (int)usable[(size_t)i].size(), skipped[(size_t)i], replicas[(size_t)i], (unsigned long long)p[0], (unsigned long long)p[1],
-                             (unsigned long long)p[2], (unsigned long long)p[3], (unsigned long long)p[4], (unsigned long long)p[5]);
-                if (caps.on)
-                    std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s lower_bound_ppm=%s proof=%llu", ppm(q[0], q[1]).c_str(), ppm(q[2], q[3]).c_str(),
-                                 ppm(q[4], q[5]).c_str(), (unsigned long long)q[9]);
-                if (exchange) std::fprintf(stderr, " exchange_rounds=%llu exchanges=%llu", (unsigned long long)q[6], (unsigned long long)q[7]);
-                std::fprintf(stderr, "\n");
-            }
-            std::fprintf(stderr, "logdirs: status=%s brokers=%d dirs=%d skipped_dirs=%llu replicas=%d peak_before=%llu peak_after=%llu replicas_moved=%d "
-                                 "bytes_moved=%llu bytes_total=%llu brokers_moved=%lld rounds=%lld moves=%lld proposals=%lld launches=%lld "
-                                 "stopped_by_max_rounds=%lld proven=%lld max_rounds_of_a_broker=%lld",
-                         status == KAO_STATUS_OPTIMAL_PROVEN ? "OPTIMAL_PROVEN" : "FEASIBLE_BOUND_GAP", B, D, all_skipped, R, (unsigned long long)before[0],
-                         (unsigned long long)after[0], n_moved, (unsigned long long)bytes_moved, total, (long long)stats[0], (long long)stats[1], (long long)stats[2],
-                         (long long)stats[3], (long long)stats[4], (long long)stats[5], (long long)stats[6], (long long)stats[7]);
-            if (exchange)
-                std::fprintf(stderr, " exchange_rounds=%lld exchanges=%lld exchange_proposals=%lld brokers_lowered_by_exchange=%lld", (long long)stats[8],
-                             (long long)stats[9], (long long)stats[10], (long long)stats[11]);
-            if (caps.on) std::fprintf(stderr, " peak_before_ppm=%s peak_after_ppm=%s", ppm(before[0], before[1]).c_str(), ppm(after[0], after[1]).c_str());
-            std::fprintf(stderr, "\n");
-        }
-        // the partitions with a moved replica, in (topic, partition) order: the replicas come out in that order already
-        std::string body;
-        int n_out = 0;
-        for (int r = 0; r < R;) {
-            int e = r;
-            bool moved = false;
-            while (e < R && slots[(size_t)e].key == slots[(size_t)r].key) { moved |= dir[(size_t)e] != dir0[(size_t)e]; ++e; }
-            if (moved) {
-                const std::vector<int> &row = *slots[(size_t)r].row;
-                std::vector<std::string> names(row.size(), "any");
-                for (int q = r; q < e; ++q)
-                    if (dir[(size_t)q] != dir0[(size_t)q]) names[(size_t)slots[(size_t)q].j] = flat[(size_t)dir[(size_t)q]];
-                body += (n_out++ ? ",\n" : "\n");
-                body += "    {\"topic\":" + quoted(slots[(size_t)r].key->first) + ",\"partition\":" + std::to_string(slots[(size_t)r].key->second) + ",\"replicas\":[";
-                for (size_t k = 0; k < row.size(); ++k) body += (k ? "," : "") + std::to_string(row[k]);
-                body += "],\"log_dirs\":[";
-                for (size_t k = 0; k < names.size(); ++k) body += (k ? "," : "") + quoted(names[k]);
-                body += "]}";
-            }
-            r = e;
-        }
-        std::ofstream f(out_path);
-        f << "{\"version\":1,\"partitions\":[" << body << "\n]}\n";
-        f.close();
-        if (!f) throw std::runtime_error("cannot write " + out_path);
-        kao_shutdown();
-        return 0;
+        run(o);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "kao-logdirs: %s\n", e.what());
         return 1;
     }
+    return 0;
 }

@@ -289,54 +289,10 @@ def parse_input(current_doc: dict, log_dirs, broker_list: Optional[Sequence[int]
     current document by (topic, partition), the slots of a row in order; a slot is a movable replica iff its broker is in the list
     and has a non-future entry for the partition in a usable dir, whose size it takes.  Every other entry of a usable dir (future
     replicas, partitions the current document does not hold, brokers outside the partition's row) adds its size to the dir's base.
-    The same partition non-future twice on one broker is a ValueError."""
-    from .waves import _entries
-    table = _table_of(log_dirs)
-    ids = sorted(table) if broker_list is None else [int(b) for b in broker_list]
-    if not ids:
-        raise ValueError("empty broker list")
-    if len(set(ids)) != len(ids):
-        raise ValueError("duplicate id in broker list")
-    by_key = _entries(current_doc, "current")
-    keys = sorted(by_key, key=lambda k: (k[0].encode(), k[1]))
-    names, skipped, dir_start = [], [], [0]
-    where: List[Dict[Tuple[str, int], Tuple[int, int]]] = []   # per broker: partition -> (global dir, size) of its non-future entry
-    for b in ids:
-        dirs = table.get(b, {})
-        usable = sorted((n for n, d in dirs.items() if d.error is None), key=lambda n: n.encode())
-        names.append(usable)
-        skipped.append(len(dirs) - len(usable))
-        at: Dict[Tuple[str, int], Tuple[int, int]] = {}
-        for i, n in enumerate(usable):
-            for topic, part, sz, fut in dirs[n].entries:
-                if fut:
-                    continue
-                if (topic, part) in at:
-                    raise ValueError(f"log-dirs: broker {b} holds partition {topic}-{part} twice")
-                at[(topic, part)] = (dir_start[-1] + i, sz)
-        where.append(at)
-        dir_start.append(dir_start[-1] + len(usable))
-    dense = {b: i for i, b in enumerate(ids)}
-    rdir, rsize, slots, claimed = [], [], [], set()
-    for k, key in enumerate(keys):
-        for j, x in enumerate(by_key[key]):
-            i = dense.get(x)
-            if i is None or key not in where[i]:
-                continue
-            d, sz = where[i][key]
-            rdir.append(d)
-            rsize.append(sz)
-            slots.append((k, j))
-            claimed.add((i, key))
-    base = [0] * dir_start[-1]
-    for i, b in enumerate(ids):
-        for li, n in enumerate(names[i]):
-            for topic, part, sz, fut in table[b][n].entries:
-                if fut or (i, (topic, part)) not in claimed:
-                    base[dir_start[i] + li] += sz
-    return LogDirsInput(broker_ids=ids, dir_names=names, skipped=skipped, dir_start=np.asarray(dir_start, dtype=np.int32),
-                        base=np.asarray(base, dtype=np.uint64).reshape(-1), dir=np.asarray(rdir, dtype=np.int32).reshape(-1),
-                        size=np.asarray(rsize, dtype=np.uint64).reshape(-1), slots=slots, keys=keys, rows=[by_key[k] for k in keys])
+    The same partition non-future twice on one broker is a ValueError.  The mapping is parse_place_input's without a plan and without
+    an evacuation: every replica a resident of its broker, nothing stranded."""
+    pi = parse_place_input(current_doc, log_dirs, None, (), broker_list)
+    return LogDirsInput(**{f: getattr(pi, f) for f in LogDirsInput.__dataclass_fields__})
 
 
 def dir_capacities(broker_ids: Sequence[int], dir_names: Sequence[Sequence[str]], table: Dict[int, Dict[str, LogDir]], capacity: Optional[dict] = None,
@@ -415,6 +371,19 @@ class _PlanDocument:
         return '{"version":1,"partitions":[' + "".join(("\n" if i == 0 else ",\n") + r for i, r in enumerate(rows)) + "\n]}\n"
 
 
+def _plan_entries(inp, new_dir: np.ndarray, planned: Sequence[bool], dry_run: bool) -> List[Tuple[str, int, List[int], List[str]]]:
+    """The entries of a plan on a LogDirsInput or a PlaceInput: the planned partitions and those with a replica whose dir changed, in
+    the order of the keys; the new dir's name in the slot of such a replica and "any" in every other.  None with dry_run."""
+    if dry_run:
+        return []
+    flat = [n for names in inp.dir_names for n in names]
+    lists: Dict[int, List[str]] = {k: ["any"] * len(inp.rows[k]) for k, p in enumerate(planned) if p}
+    for r in np.nonzero(new_dir != inp.dir)[0]:
+        k, j = inp.slots[int(r)]
+        lists.setdefault(k, ["any"] * len(inp.rows[k]))[j] = flat[int(new_dir[r])]
+    return [(inp.keys[k][0], inp.keys[k][1], list(inp.rows[k]), lists[k]) for k in sorted(lists)]
+
+
 @dataclass
 class LogDirsPlan(_PlanDocument):
     result: LogDirsResult
@@ -433,13 +402,8 @@ def plan_input(li: LogDirsInput, min_gain: int = 0, max_rounds: int = 0, dry_run
     kao_balance_logdirs_exchange with exchange); the entries are the partitions with a moved replica (none with dry_run)."""
     res = balance_logdirs_arrays(li.dir_start, li.dir, li.size, li.base, min_gain, max_rounds, dry_run, **({} if capacity is None else {"capacity": capacity}),
                                  **({"exchange": True} if exchange else {}))
-    flat = [n for names in li.dir_names for n in names]
-    lists: Dict[int, List[str]] = {}
-    for r in np.nonzero(res.dir != li.dir)[0]:
-        k, j = li.slots[int(r)]
-        lists.setdefault(k, ["any"] * len(li.rows[k]))[j] = flat[int(res.dir[r])]
-    entries = [(li.keys[k][0], li.keys[k][1], list(li.rows[k]), lists[k]) for k in sorted(lists)]
-    return LogDirsPlan(result=res, input=li, entries=entries, capacity=None if capacity is None else [int(x) for x in capacity], exchange=bool(exchange))
+    return LogDirsPlan(result=res, input=li, entries=_plan_entries(li, res.dir, (), dry_run), capacity=None if capacity is None else [int(x) for x in capacity],
+                       exchange=bool(exchange))
 
 
 def balance_logdirs(current_doc: dict, log_dirs, *, broker_list: Optional[Sequence[int]] = None, min_gain: int = 0, max_rounds: int = 0,
@@ -459,25 +423,32 @@ def balance_logdirs(current_doc: dict, log_dirs, *, broker_list: Optional[Sequen
     return plan_input(li, min_gain, max_rounds, dry_run, cap, exchange)
 
 
+def _report_parts(plan, columns: Sequence[str]):
+    """What the two reports share: the warning lines; per broker the text of its columns, the capacity words folded away ({peak_before,
+    cap, peak_after, cap, bound num, den, <the other columns>, proof} with capacities), and the ppm tail of its line; bytes_total; the
+    ppm tail of the call's line."""
+    res, inp = plan.result, plan.input
+    by_cap = res.peak_after_frac is not None
+    warnings = _capacity_warnings(inp.broker_ids, inp.dir_names, inp.dir_start, inp.base, plan.capacity) if by_cap else []
+    cols, tails = [], []
+    for row in res.per_broker:
+        p = [int(x) for x in row]
+        tails.append(f" peak_before_ppm={_ppm(p[0], p[1])} peak_after_ppm={_ppm(p[2], p[3])} lower_bound_ppm={_ppm(p[4], p[5])} proof={p[-1]}" if by_cap else "")
+        cols.append(" ".join(f"{k}={v}" for k, v in zip(columns, p[0:6:2] + p[6:-1] if by_cap else p)))
+    total = sum(int(x) for x in inp.size) + sum(int(x) for x in inp.base)
+    return warnings, cols, tails, total, f" peak_before_ppm={_ppm(*res.peak_before_frac)} peak_after_ppm={_ppm(*res.peak_after_frac)}" if by_cap else ""
+
+
 def report_lines(plan: LogDirsPlan) -> List[str]:
     """The --report text, line for line as cli/kao-logdirs prints it: one line per broker, one for the call."""
-    res, li, s = plan.result, plan.input, plan.result.stats
+    res, li = plan.result, plan.input
     per_replicas = np.bincount(np.searchsorted(li.dir_start, li.dir, side="right") - 1, minlength=len(li.broker_ids)) if len(li.dir) else [0] * len(li.broker_ids)
-    by_cap = res.peak_after_frac is not None
-    out = _capacity_warnings(li.broker_ids, li.dir_names, li.dir_start, li.base, plan.capacity) if by_cap else []
+    out, cols, tails, total, call_tail = _report_parts(plan, X_PER_BROKER_KEYS if plan.exchange else PER_BROKER_KEYS)
     for i, b in enumerate(li.broker_ids):
-        p = [int(x) for x in res.per_broker[i]]
-        if by_cap:   # {peak_before, cap, peak_after, cap, bound num, den, moved, bytes_moved, rounds, proof}
-            p = [p[0], p[2], p[4], p[6], p[7], p[8], _ppm(p[0], p[1]), _ppm(p[2], p[3]), _ppm(p[4], p[5]), p[9]]
-        out.append(f"logdirs: broker={b} dirs={len(li.dir_names[i])} skipped_dirs={li.skipped[i]} replicas={int(per_replicas[i])} peak_before={p[0]} "
-                   f"peak_after={p[1]} lower_bound={p[2]} moved={p[3]} bytes_moved={p[4]} rounds={p[5]}"
-                   + (f" peak_before_ppm={p[6]} peak_after_ppm={p[7]} lower_bound_ppm={p[8]} proof={p[9]}" if by_cap else "")
-                   + (f" exchange_rounds={p[6]} exchanges={p[7]}" if plan.exchange else ""))
-    total = sum(int(x) for x in li.size) + sum(int(x) for x in li.base)
+        out.append(f"logdirs: broker={b} dirs={len(li.dir_names[i])} skipped_dirs={li.skipped[i]} replicas={int(per_replicas[i])} {cols[i]}{tails[i]}")
     out.append(f"logdirs: status={res.status} brokers={len(li.broker_ids)} dirs={int(li.dir_start[-1])} skipped_dirs={sum(li.skipped)} replicas={len(li.dir)} "
                f"peak_before={res.peak_before} peak_after={res.peak_after} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
-               + " ".join(f"{k}={int(v)}" for k, v in zip(X_STAT_KEYS if plan.exchange else STAT_KEYS, s))
-               + (f" peak_before_ppm={_ppm(*res.peak_before_frac)} peak_after_ppm={_ppm(*res.peak_after_frac)}" if by_cap else ""))
+               + " ".join(f"{k}={int(v)}" for k, v in zip(X_STAT_KEYS if plan.exchange else STAT_KEYS, res.stats)) + call_tail)
     return out
 
 
@@ -634,15 +605,7 @@ def place_input(pi: PlaceInput, rebalance: bool = False, min_gain: int = 0, max_
     other (no entry with dry_run)."""
     res = place_logdirs_arrays(pi.dir_start, pi.broker, pi.dir, pi.size, pi.base, rebalance, min_gain, max_rounds, dry_run,
                                **({} if capacity is None else {"capacity": capacity}))
-    entries = []
-    if not dry_run:
-        flat = [n for names in pi.dir_names for n in names]
-        lists: Dict[int, List[str]] = {k: ["any"] * len(pi.rows[k]) for k in range(len(pi.keys)) if pi.planned[k]}
-        for r in np.nonzero(res.dir != pi.dir)[0]:
-            k, j = pi.slots[int(r)]
-            lists.setdefault(k, ["any"] * len(pi.rows[k]))[j] = flat[int(res.dir[r])]
-        entries = [(pi.keys[k][0], pi.keys[k][1], list(pi.rows[k]), lists[k]) for k in sorted(lists)]
-    return PlaceLogDirsPlan(result=res, input=pi, entries=entries, capacity=None if capacity is None else [int(x) for x in capacity])
+    return PlaceLogDirsPlan(result=res, input=pi, entries=_plan_entries(pi, res.dir, pi.planned, dry_run), capacity=None if capacity is None else [int(x) for x in capacity])
 
 
 def place_logdirs(current_doc: dict, log_dirs, plan_doc: Optional[dict] = None, evacuate: Sequence[Tuple[int, str]] = (),
@@ -664,26 +627,19 @@ def place_logdirs(current_doc: dict, log_dirs, plan_doc: Optional[dict] = None, 
 
 def place_report_lines(plan: PlaceLogDirsPlan) -> List[str]:
     """The --report text of a placement, line for line as cli/kao-logdirs prints it: one line per broker, one for the call."""
-    res, pi, s = plan.result, plan.input, plan.result.stats
+    res, pi = plan.result, plan.input
     B = len(pi.broker_ids)
     homeless = np.bincount(pi.broker[pi.dir < 0], minlength=B) if len(pi.dir) else np.zeros(B, dtype=np.int64)
     residents = np.bincount(pi.broker[pi.dir >= 0], minlength=B) if len(pi.dir) else np.zeros(B, dtype=np.int64)
-    by_cap = res.peak_after_frac is not None
-    out = _capacity_warnings(pi.broker_ids, pi.dir_names, pi.dir_start, pi.base, plan.capacity) if by_cap else []
+    out, cols, tails, total, call_tail = _report_parts(plan, PLACE_PER_BROKER_KEYS)
     for i, b in enumerate(pi.broker_ids):
-        p = [int(x) for x in res.per_broker[i]]
-        if by_cap:   # {peak_before, cap, peak_after, cap, bound num, den, placed, bytes_placed, moved, bytes_moved, rounds, proof}
-            p = [p[0], p[2], p[4], p[6], p[7], p[8], p[9], p[10], _ppm(p[0], p[1]), _ppm(p[2], p[3]), _ppm(p[4], p[5]), p[11]]
         out.append(f"logdirs: broker={b} dirs={len(pi.dir_names[i])} skipped_dirs={pi.skipped[i]} evacuated_dirs={pi.evacuated[i]} "
-                   f"replicas={int(residents[i] + homeless[i])} residents={int(residents[i])} homeless={int(homeless[i])} peak_before={p[0]} peak_after={p[1]} "
-                   f"lower_bound={p[2]} placed={p[3]} bytes_placed={p[4]} moved={p[5]} bytes_moved={p[6]} rounds={p[7]} stranded_bytes={pi.stranded[i]}"
-                   + (f" peak_before_ppm={p[8]} peak_after_ppm={p[9]} lower_bound_ppm={p[10]} proof={p[11]}" if by_cap else ""))
-    total = sum(int(x) for x in pi.size) + sum(int(x) for x in pi.base)
+                   f"replicas={int(residents[i] + homeless[i])} residents={int(residents[i])} homeless={int(homeless[i])} {cols[i]} "
+                   f"stranded_bytes={pi.stranded[i]}{tails[i]}")
     out.append(f"logdirs: status={res.status} brokers={B} dirs={int(pi.dir_start[-1])} skipped_dirs={sum(pi.skipped)} evacuated_dirs={sum(pi.evacuated)} "
                f"replicas={len(pi.dir)} residents={int(residents.sum())} homeless={int(homeless.sum())} peak_before={res.peak_before} peak_after={res.peak_after} "
                f"replicas_placed={res.n_placed} bytes_placed={res.bytes_placed} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
-               f"stranded_bytes={sum(pi.stranded)} " + " ".join(f"{k}={int(v)}" for k, v in zip(PLACE_STAT_KEYS, s))
-               + (f" peak_before_ppm={_ppm(*res.peak_before_frac)} peak_after_ppm={_ppm(*res.peak_after_frac)}" if by_cap else ""))
+               f"stranded_bytes={sum(pi.stranded)} " + " ".join(f"{k}={int(v)}" for k, v in zip(PLACE_STAT_KEYS, res.stats)) + call_tail)
     return out
 
 
@@ -755,13 +711,6 @@ def main(argv=None) -> int:
     except ValueError as e:
         ap.error(str(e))
 
-    def capacities_of(table, inp):   # a usable dir without a capacity is a usage error
-        if not by_capacity:
-            return None
-        try:
-            return dir_capacities(inp.broker_ids, inp.dir_names, table, cap_table, default_capacity, a.utilisation)
-        except ValueError as e:
-            ap.error(str(e))
     try:
         with open(a.current) as f:
             doc = json.load(f)
@@ -769,22 +718,20 @@ def main(argv=None) -> int:
             text = f.read()
         ids = None if a.broker_list is None else [int(b) for b in a.broker_list.split(",") if b]
         from .solver import init
-        if placing:
-            plan_doc = None
-            if a.plan is not None:
-                with open(a.plan) as f:
-                    plan_doc = json.load(f)
-            table = parse_log_dirs(text)
-            pi = parse_place_input(doc, table, plan_doc, evacuate, ids, default_size)   # input errors before the device is touched
-            cap = capacities_of(table, pi)
-            init(a.device)
-            plan = place_input(pi, a.rebalance, min_gain, a.max_rounds, a.dry_run, cap)
-        else:
-            table = parse_log_dirs(text)
-            li = parse_input(doc, table, ids)   # input errors before the device is touched
-            cap = capacities_of(table, li)
-            init(a.device)
-            plan = plan_input(li, min_gain, a.max_rounds, a.dry_run, cap, a.exchange)
+        plan_doc = None
+        if a.plan is not None:
+            with open(a.plan) as f:
+                plan_doc = json.load(f)
+        table = parse_log_dirs(text)
+        inp = parse_place_input(doc, table, plan_doc, evacuate, ids, default_size) if placing else parse_input(doc, table, ids)   # input errors before the device is touched
+        cap = None
+        if by_capacity:
+            try:
+                cap = dir_capacities(inp.broker_ids, inp.dir_names, table, cap_table, default_capacity, a.utilisation)
+            except ValueError as e:   # a usable dir without a capacity is a usage error
+                ap.error(str(e))
+        init(a.device)
+        plan = place_input(inp, a.rebalance, min_gain, a.max_rounds, a.dry_run, cap) if placing else plan_input(inp, min_gain, a.max_rounds, a.dry_run, cap, a.exchange)
         if a.report:
             for line in plan.report_lines():
                 print(line, file=sys.stderr)
