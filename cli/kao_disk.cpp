@@ -54,34 +54,6 @@ namespace {
     std::exit(2);
 }
 
-// --capacities: id:bytes,id:bytes or a JSON file {"<brokerId>": bytes}, a value a number or a string, each N or N with K/M/G/T
-std::map<int, uint64_t> read_capacities(const std::string &arg) {
-    std::map<int, uint64_t> out;
-    auto put = [&](const std::string &id, const std::string &text) {
-        uint64_t v = 0;
-        if (id.empty() || id.find_first_not_of("0123456789") != std::string::npos || !parse_bytes(text, v))
-            throw std::runtime_error("capacity of broker " + id + ": not a byte count: " + text);
-        out[std::atoi(id.c_str())] = v;
-    };
-    if (arg.find(':') != std::string::npos && arg.find('{') == std::string::npos && (arg.size() < 5 || arg.compare(arg.size() - 5, 5, ".json") != 0)) {
-        for (auto &t : split(arg, ',')) {
-            if (t.empty()) continue;
-            auto kv = split(t, ':');
-            if (kv.size() != 2) throw std::runtime_error("bad --capacities entry " + t);
-            put(kv[0], kv[1]);
-        }
-    } else {
-        const std::string txt = slurp(arg);
-        const JValue doc = JParser(txt).parse();
-        if (doc.kind != JValue::Obj) throw std::runtime_error("capacities file must be a JSON object {\"<brokerId>\": bytes}");
-        for (auto &kv : doc.obj) {
-            if (kv.second.kind != JValue::Num && kv.second.kind != JValue::Str) throw std::runtime_error("capacity of broker " + kv.first + ": not a byte count");
-            put(kv.first, kv.second.kind == JValue::Num ? kv.second.raw : kv.second.str);
-        }
-    }
-    return out;
-}
-
 // floor(num * 10^6 / den) in decimal; the product passes 64 bits
 std::string ppm(uint64_t num, uint64_t den) {
     unsigned __int128 v = (unsigned __int128)num * 1000000u / den;
@@ -141,7 +113,7 @@ int main(int argc, char **argv) {
     if (by_capacity) {                // a broker without a capacity is a usage error
         std::string msg;
         try {
-            const std::map<int, uint64_t> table = have_caps ? read_capacities(caps_arg) : std::map<int, uint64_t>();
+            const std::map<int, uint64_t> table = have_caps ? read_broker_capacities(caps_arg) : std::map<int, uint64_t>();
             std::vector<std::string> missing;
             for (auto &t : split(brokers_csv, ',')) {
                 if (t.empty()) continue;

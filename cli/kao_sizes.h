@@ -42,6 +42,38 @@ inline bool parse_bytes(const std::string &text, uint64_t &out) {
     return true;
 }
 
+// --capacities of kao-disk and kao-waves: id:bytes,id:bytes or a JSON file {"<brokerId>": bytes}, a value a number or a string, each N
+// or N with K/M/G/T
+inline std::map<int, uint64_t> read_broker_capacities(const std::string &arg) {
+    std::map<int, uint64_t> out;
+    auto put = [&](const std::string &id, const std::string &text) {
+        uint64_t v = 0;
+        if (id.empty() || id.find_first_not_of("0123456789") != std::string::npos || !parse_bytes(text, v))
+            throw std::runtime_error("capacity of broker " + id + ": not a byte count: " + text);
+        out[std::atoi(id.c_str())] = v;
+    };
+    if (arg.find(':') != std::string::npos && arg.find('{') == std::string::npos && (arg.size() < 5 || arg.compare(arg.size() - 5, 5, ".json") != 0)) {
+        std::istringstream in(arg);
+        std::string t;
+        while (std::getline(in, t, ',')) {
+            t.erase(std::remove_if(t.begin(), t.end(), [](unsigned char c) { return std::isspace(c) != 0; }), t.end());
+            if (t.empty()) continue;
+            const size_t colon = t.find(':');
+            if (colon == std::string::npos || t.find(':', colon + 1) != std::string::npos) throw std::runtime_error("bad --capacities entry " + t);
+            put(t.substr(0, colon), t.substr(colon + 1));
+        }
+    } else {
+        const std::string txt = slurp(arg);
+        const JValue doc = JParser(txt).parse();
+        if (doc.kind != JValue::Obj) throw std::runtime_error("capacities file must be a JSON object {\"<brokerId>\": bytes}");
+        for (auto &kv : doc.obj) {
+            if (kv.second.kind != JValue::Num && kv.second.kind != JValue::Str) throw std::runtime_error("capacity of broker " + kv.first + ": not a byte count");
+            put(kv.first, kv.second.kind == JValue::Num ? kv.second.raw : kv.second.str);
+        }
+    }
+    return out;
+}
+
 inline uint64_t size_value(const JValue *v, const std::string &what) {
     uint64_t x = 0;
     if (!v || v->kind != JValue::Num || v->raw.empty() || v->raw.size() > 16 || v->raw.find_first_not_of("0123456789") != std::string::npos ||

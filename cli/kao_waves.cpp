@@ -9,10 +9,17 @@
 // (kao_plan_waves_sized): an added broker receives size[p], the source sends size[p] once per added broker.  --max-per-broker
 // is then optional (0 = no count cap); --default-size N sizes the moving partitions --sizes does not list.
 //
+// With --headroom (needs --sizes; implied by --capacities FILE|id:bytes,.., --default-capacity N and --max-utilisation PCT) no wave
+// fills a broker beyond capacity * PCT / 100, counting what it holds plus everything arriving in the wave (kao_plan_waves_headroom,
+// DESIGN.md section 4v); both caps are then optional.  A broker's capacity is its --capacities entry, else the sum of its log dirs'
+// totalBytes when --sizes is kafka-log-dirs output that reports one for every dir (Kafka >= 3.3), else --default-capacity.  What a
+// broker holds now is the sizes of its current replicas, or all its entries of the kafka-log-dirs output when that is more.
+// Partitions that fit no wave go to PREFIX-stuck.json; the tool then says "stuck: N partitions, X bytes" and exits with status 3.
+//
 // which writes wave1.json .. waveN.json, each a reassignment document `kafka-reassign-partitions --execute` takes on its own; run
 // them in order, each after the previous one has finished.  A partition of current.json that plan.json leaves out is unchanged;
 // a partition of plan.json that current.json does not list is an error.  All computation happens in libkao.so on the GPU.
-// Exit status: 0 = waves written, 1 = error, 2 = usage.
+// Exit status: 0 = waves written, 1 = error, 2 = usage, 3 = waves written but some partitions are stuck (--headroom).
 #include <algorithm>
 #include <cerrno>
 #include <climits>
@@ -38,7 +45,10 @@ namespace {
         "                 [--seed S] [--device D] [--report]\n"
         "       sized: --sizes <kafka-log-dirs output | sizes.json> --max-bytes-per-broker N[K|M|G|T] [--default-size N]\n"
         "              (--max-per-broker optional; 0 = no count cap)\n"
-        "writes PREFIX1.json .. PREFIXn.json; exit status: 0 = ok, 1 = error, 2 = usage\n");
+        "       headroom: --headroom --sizes FILE [--capacities <caps.json | id:bytes,...>] [--default-capacity N[K|M|G|T]]\n"
+        "              [--max-utilisation PCT] (each of the three implies --headroom; both caps optional; stuck partitions go to\n"
+        "              PREFIX-stuck.json)\n"
+        "writes PREFIX1.json .. PREFIXn.json; exit status: 0 = ok, 1 = error, 2 = usage, 3 = stuck partitions\n");
     std::exit(2);
 }
 
@@ -90,8 +100,10 @@ int main(int argc, char **argv) {
     std::string cur_path, plan_path, prefix, sizes_path;
     int k = 0, device = 0;
     unsigned long long seed = 1;
-    bool report = false, have_k = false, sized = false, have_default = false;
-    uint64_t cap_bytes = 0, default_size = 0;
+    bool report = false, have_k = false, sized = false, have_default = false, headroom = false, have_default_cap = false;
+    uint64_t cap_bytes = 0, default_size = 0, default_cap = 0;
+    std::string caps_arg;
+    int max_util = 100;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
@@ -106,6 +118,17 @@ int main(int argc, char **argv) {
             if (!parse_bytes(need("--default-size"), default_size) || default_size > kMaxSize) usage("--default-size needs a byte count up to 2^53");
             sized = have_default = true;
         }
+        else if (a == "--headroom") headroom = true;
+        else if (a == "--capacities") { caps_arg = need("--capacities"); headroom = true; }
+        else if (a == "--default-capacity") {
+            if (!parse_bytes(need("--default-capacity"), default_cap)) usage("--default-capacity needs a byte count (N, or N with K/M/G/T)");
+            headroom = have_default_cap = true;
+        } else if (a == "--max-utilisation") {
+            const std::string v = need("--max-utilisation");
+            if (v.empty() || v.size() > 3 || v.find_first_not_of("0123456789") != std::string::npos || (max_util = std::atoi(v.c_str())) < 1 || max_util > 100)
+                usage("--max-utilisation needs a percentage 1..100");
+            headroom = true;
+        }
         else if (a == "--out-prefix") prefix = need("--out-prefix");
         else if (a == "--seed") seed = std::strtoull(need("--seed").c_str(), nullptr, 0);
         else if (a == "--device") device = std::atoi(need("--device").c_str());
@@ -114,8 +137,11 @@ int main(int argc, char **argv) {
         else usage(("unknown flag " + a).c_str());
     }
     if (cur_path.empty() || plan_path.empty() || prefix.empty()) usage("--current, --plan and --out-prefix are required");
+    if (headroom && sizes_path.empty()) usage("--headroom needs --sizes");
+    if (headroom && k < 0) usage("--max-per-broker must be >= 0");
+    sized = sized || headroom;
     if (!sized && k < 1) usage("--max-per-broker needs a value >= 1");
-    if (sized && (k < 0 || (k == 0 && cap_bytes == 0)))
+    if (sized && !headroom && (k < 0 || (k == 0 && cap_bytes == 0)))
         usage(have_k ? "--max-per-broker must be >= 0, and a cap must be set (--max-per-broker >= 1 or --max-bytes-per-broker >= 1)"
                      : "give --max-per-broker K >= 1 or --max-bytes-per-broker N >= 1");
     try {
@@ -168,11 +194,55 @@ int main(int argc, char **argv) {
                 throw std::runtime_error(msg + " (give them in --sizes or set --default-size)");
             }
         }
+        std::vector<uint64_t> stored, capacity, effective;   // per dense broker (--headroom)
+        std::vector<int> broker_id((size_t)nb);
+        for (auto &kv : dense) broker_id[(size_t)kv.second] = kv.first;
+        if (headroom) {
+            std::map<int, std::vector<LogDir>> dirs;
+            if (slurp(sizes_path).find("\"brokers\"") != std::string::npos) dirs = load_log_dirs(sizes_path);
+            const std::map<int, uint64_t> table = caps_arg.empty() ? std::map<int, uint64_t>() : read_broker_capacities(caps_arg);
+            stored.assign((size_t)nb, 0);
+            for (size_t i = 0; i < P; ++i)
+                for (size_t j = 0; j < W; ++j)
+                    if (c[i * W + j] != KAO_NONE) stored[c[i * W + j]] += size[i];
+            std::vector<int> missing;
+            for (int b = 0; b < nb; ++b) {
+                uint64_t on_disk = 0, total = 0;
+                bool every = false;
+                auto d = dirs.find(broker_id[(size_t)b]);
+                if (d != dirs.end()) {
+                    every = !d->second.empty();
+                    for (auto &ld : d->second) {
+                        every = every && ld.has_total;
+                        total += ld.total_bytes;
+                        for (auto &e : ld.entries) on_disk += e.size;   // future replicas too: they are bytes on disk
+                    }
+                }
+                stored[(size_t)b] = std::max(stored[(size_t)b], on_disk);
+                auto it = table.find(broker_id[(size_t)b]);
+                if (it != table.end()) capacity.push_back(it->second);
+                else if (every && total > 0) capacity.push_back(total);
+                else if (have_default_cap) capacity.push_back(default_cap);
+                else missing.push_back(broker_id[(size_t)b]);
+            }
+            if (!missing.empty()) {
+                std::string msg = "no capacity for brokers ";
+                for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + std::to_string(missing[i]);
+                if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
+                throw std::runtime_error(msg + " (give them in --capacities, read totalBytes from a kafka-log-dirs --sizes document or set --default-capacity)");
+            }
+            for (uint64_t v : capacity) effective.push_back((uint64_t)((unsigned __int128)v * (unsigned)max_util / 100u));
+        }
         int rc = kao_init(device);
         if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
         std::vector<int32_t> wave(std::max<size_t>(P, 1));
         int32_t n_waves = 0, lb = 0;
-        if (sized) {
+        int64_t hstats[8] = {0, 0, -1, 0, 0, -1, -1, -1};
+        if (headroom) {
+            rc = kao_plan_waves_headroom(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), size.data(), stored.data(), effective.data(), cap_bytes, k, seed,
+                                         wave.data(), &n_waves, &lb, hstats);
+            if (rc) throw std::runtime_error(std::string("kao_plan_waves_headroom: ") + kao_strerror(rc) + " " + kao_last_error());
+        } else if (sized) {
             rc = kao_plan_waves_sized(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), size.data(), cap_bytes, k, seed, wave.data(), &n_waves, &lb);
             if (rc) throw std::runtime_error(std::string("kao_plan_waves_sized: ") + kao_strerror(rc) + " " + kao_last_error());
         } else {
@@ -194,8 +264,24 @@ int main(int argc, char **argv) {
             f << "\n]}\n";
             if (!f) throw std::runtime_error("cannot write " + path);
         }
+        if (hstats[0] > 0) {   // the partitions that fit no wave, as a reassignment document of their own
+            const std::string path = prefix + "-stuck.json";
+            std::ofstream f(path);
+            if (!f) throw std::runtime_error("cannot write " + path);
+            f << "{\"version\":1,\"partitions\":[";
+            bool first = true;
+            for (size_t i = 0; i < P; ++i) {
+                if (wave[i] != -2) continue;
+                f << (first ? "\n" : ",\n") << "    {\"topic\":" << quoted(cur[i].first.first) << ",\"partition\":" << cur[i].first.second << ",\"replicas\":[";
+                first = false;
+                for (size_t j = 0; j < tgt[i]->size(); ++j) f << (j ? "," : "") << (*tgt[i])[j];
+                f << "]}";
+            }
+            f << "\n]}\n";
+            if (!f) throw std::runtime_error("cannot write " + path);
+        }
         if (report) {
-            std::fprintf(stderr, "waves=%d lower_bound=%d optimal=%s partitions_per_wave=", n_waves, lb, n_waves == lb ? "yes" : "no");
+            std::fprintf(stderr, "waves=%d lower_bound=%d optimal=%s partitions_per_wave=", n_waves, lb, n_waves == lb && hstats[0] == 0 ? "yes" : "no");
             for (int w = 0; w < n_waves; ++w) std::fprintf(stderr, "%s%d", w ? "," : "", sizes[(size_t)w]);
             if (sized) {   // bytes: the byte lower bound max_b ceil(sum_p min(t, C) / C) and each wave's busiest broker
                 std::map<std::pair<int, int>, uint64_t> load;
@@ -203,7 +289,7 @@ int main(int argc, char **argv) {
                 for (size_t i = 0; i < P; ++i)
                     for (auto &bn : traffic(&c[i * W], &t[i * W], W)) {
                         const uint64_t tr = bn.second * size[i];   // below 2^62: kao_plan_waves_sized checked the totals
-                        load[{wave[i], bn.first}] += tr;
+                        if (wave[i] >= 0) load[{wave[i], bn.first}] += tr;   // a stuck partition (--headroom) is in no wave
                         if (cap_bytes) clamp[bn.first] += std::min(tr, cap_bytes);
                     }
                 uint64_t blb = 0;
@@ -213,9 +299,40 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, " bytes_lower_bound=%llu max_broker_bytes_per_wave=", (unsigned long long)blb);
                 for (int w = 0; w < n_waves; ++w) std::fprintf(stderr, "%s%llu", w ? "," : "", (unsigned long long)peak[(size_t)w]);
             }
+            if (headroom) {   // the fullest receiving broker of each wave in percent of its capacity: occ follows the waves
+                std::vector<uint64_t> occ = stored;
+                std::fprintf(stderr, " fullest_receiver_pct_per_wave=");
+                for (int w = 0; w < n_waves; ++w) {
+                    std::map<int, uint64_t> arr, dep;
+                    for (size_t i = 0; i < P; ++i) {
+                        if (wave[i] != w || size[i] == 0) continue;
+                        for (size_t j = 0; j < W; ++j) {
+                            const uint16_t tb = t[i * W + j], cb = c[i * W + j];
+                            if (tb != KAO_NONE && std::find(&c[i * W], &c[i * W] + W, tb) == &c[i * W] + W) arr[tb] += size[i];
+                            if (cb != KAO_NONE && std::find(&t[i * W], &t[i * W] + W, cb) == &t[i * W] + W) dep[cb] += size[i];
+                        }
+                    }
+                    unsigned long long ppm = 0;
+                    for (auto &kv : arr) {
+                        const uint64_t cap = capacity[(size_t)kv.first];
+                        const unsigned __int128 v = cap ? (unsigned __int128)(occ[(size_t)kv.first] + kv.second) * 1000000u / cap : 1000000u;
+                        ppm = std::max(ppm, (unsigned long long)v);
+                    }
+                    for (auto &kv : arr) occ[(size_t)kv.first] += kv.second;
+                    for (auto &kv : dep) occ[(size_t)kv.first] -= kv.second;
+                    std::fprintf(stderr, "%s%llu.%02llu", w ? "," : "", ppm / 10000, ppm / 100 % 100);
+                }
+                std::fprintf(stderr, " min_free=%lld min_free_wave=%lld min_free_broker=%d stuck=%lld stuck_bytes=%lld", (long long)hstats[5],
+                             (long long)(hstats[6] >= 0 ? hstats[6] + 1 : 0), hstats[7] >= 0 ? broker_id[(size_t)hstats[7]] : -1, (long long)hstats[0],
+                             (long long)hstats[1]);
+            }
             std::fprintf(stderr, "\n");
         }
         kao_shutdown();
+        if (hstats[0] > 0) {
+            std::fprintf(stderr, "stuck: %lld partitions, %lld bytes\n", (long long)hstats[0], (long long)hstats[1]);
+            return 3;
+        }
         return 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "kao-waves: %s\n", e.what());

@@ -468,6 +468,30 @@ int kao_plan_waves_sized(int32_t n_brokers, int32_t n_partitions, int32_t width,
                          const uint64_t *size /* [n_partitions] bytes */, uint64_t max_bytes_per_broker, int32_t max_per_broker,
                          uint64_t seed, int32_t *wave /* [n_partitions] */, int32_t *n_waves, int32_t *lower_bound);
 
+/* Waves that never overfill a disk.  Everything of kao_plan_waves_sized (classes, participants, t_p(b),
+ * both caps, keys and orders, *lower_bound), plus stored[b] = bytes broker b holds now and capacity[b] = bytes it may hold.  Kafka
+ * keeps the departing copy until the new one is in sync, so within a wave a broker holds its old bytes plus every arrival.  One
+ * priority order is run as a sequence of waves w = 0, 1, ..: occ = stored; the still unplaced moving partitions are visited in key
+ * order, and p joins wave w iff the sized fit test passes at every participant and, at every added broker b,
+ * size[p] == 0 || occ[b] + arr[b] + size[p] <= capacity[b] (arr = bytes arriving in wave w so far).  At the end of the wave
+ * occ[b] += arr[b] - dep[b], dep = size[p] at every broker of current \ target of the wave's partitions: departures free room for
+ * the NEXT wave.  The metadata-only partitions stay in wave 0, count against no cap and leave with it.  The first wave that takes
+ * no partition and frees no byte ends the order; the partitions left over are stuck, wave[p] = -2: in the state reached none of
+ * them fits even alone.  The result is the order with the fewest stuck partitions, then the fewest waves, then the lowest index;
+ * *n_waves counts up to the last wave that holds a partition.  max_per_broker = 0 and max_bytes_per_broker = 0 together are
+ * allowed: headroom alone then shapes the waves.  With capacity[b] = 2^63 everywhere wave[], *n_waves and *lower_bound are those
+ * of kao_plan_waves_sized.  stats (may be NULL): [0] stuck partitions, [1] stuck bytes (sum of n_added(p) * size[p], at most
+ * 2^63 - 1), [2] the winning order (-1: nothing moves), [3] orders run, [4] round launches, [5] the least free bytes seen, capacity - occ - arr over
+ * (wave, broker that receives bytes) of the winning order, at most 2^63 - 1 (-1: none), [6] its wave, [7] its broker (the first
+ * wave, then the lowest broker on ties).  KAO_ERR_INVALID, checked before any device is used: everything kao_plan_waves_sized
+ * rejects except both caps 0, and stored == NULL, capacity == NULL, some stored[b] >= 2^62, or some stored[b] below the sum of
+ * size[p] over the changed partitions p that leave b. */
+int kao_plan_waves_headroom(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
+                            const uint64_t *size /* [n_partitions] bytes */, const uint64_t *stored /* [n_brokers] bytes */,
+                            const uint64_t *capacity /* [n_brokers] bytes */, uint64_t max_bytes_per_broker, int32_t max_per_broker,
+                            uint64_t seed, int32_t *wave /* [n_partitions] */, int32_t *n_waves, int32_t *lower_bound,
+                            int64_t stats[8] /* may be NULL */);
+
 /* ---- Leaders: leader-only rebalancing ---------------------------------------------------------------
  * The fewest preferred-leader changes that put every broker inside the leader band [lead_lo, lead_hi] (as kao_derive_bounds gives
  * it, overrides honoured), moving no data: the README model with every variable of a broker that holds no replica of the

@@ -109,6 +109,9 @@ SIGNATURES = {
                                  _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
     "kao_plan_waves_sized": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint16), _P(C.c_uint64), C.c_uint64,
                                        C.c_int32, C.c_uint64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    "kao_plan_waves_headroom": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint16), _P(C.c_uint64), _P(C.c_uint64),
+                                          _P(C.c_uint64), C.c_uint64, C.c_int32, C.c_uint64, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                          _P(C.c_int64)]),
     "kao_balance_leaders": (C.c_int, [_P(KaoTopic), _P(C.c_uint16), _P(C.c_int32), _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)]),
     "kao_failover_order": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_uint8), C.c_int32, C.c_int32, _P(C.c_uint16), C.c_int32, C.c_int32,
                                      _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),

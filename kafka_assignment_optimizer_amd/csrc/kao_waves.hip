@@ -1,6 +1,7 @@
 // kao_waves.hip -- kao_plan_waves: a reassignment plan split into waves with at most k partition movements per broker per wave;
-// kao_plan_waves_sized: the same with a cap on the bytes each broker moves per wave.  Kernels and the C
-// entry points.
+// kao_plan_waves_sized: the same with a cap on the bytes each broker moves per wave;
+// kao_plan_waves_headroom: waves as a sequence of states in which no broker holds more than its capacity (section 4v, further
+// down).  Kernels and the C entry points.
 //
 // A partition p that changed and adds brokers (add(p) = target \ current) moves data: its participants S(p) are add(p) plus the
 // copy source current[p][0] (new followers fetch from the leader).  The waves are a first fit: partitions in a priority order,
@@ -270,6 +271,225 @@ __global__ void k_wave_scatter(int32_t n_mv, const int32_t *__restrict__ waveo, 
     if (i < n_mv) wave[mv_idx[i]] = waveo[i];
 }
 
+// ---- kao_plan_waves_headroom: waves as a sequence of states, each of which fits every disk ----
+//
+// Per order o, in global memory: occ / arr / dep / byt (u64) and cnt (i32) over the brokers, three rotating minkey rows, waveo[slot]
+// (-1 = undecided or stuck), skipw[slot] = the wave in which the slot last decided "skip" (so nothing is reset between waves), and
+// the words of HeadOrder.  An order works on ONE wave at a time (its loads are the open wave's), and orders sit at different waves
+// within one launch.
+//
+// k_head_round, round r: an undecided slot that did not skip the open wave tests the fit (the sized test at its participants, the
+// headroom test occ + arr + size <= capacity at add(p)) against the loads as they stand.  Every test only turns from true to false
+// within a wave, and the only stores to the loads a slot reads come from slots with a lower key at that broker (the holder of a
+// broker's minimum), which the sequential pass visits earlier: failing now is failing there, so the slot skips the wave at once,
+// without bidding.  A slot that fits and holds the minimum of the previous round's bids at every participant has no undecided
+// fitting slot ahead of it at any of its brokers: the loads it just tested are the sequential ones, and it joins with plain
+// stores (two joiners of one round share no participant).  dep[] at rem(p) is read by the close step only, so it takes an
+// atomicAdd there and rem(p) is not bid at: shorter chains, and 9 rather than 17 brokers per slot.  Every other fitting slot
+// bids its key into the next round's row.
+//
+// k_head_close, after every round, one workgroup per order: when the round had no bidder the open wave is complete.  It records
+// the least free bytes over the brokers with arr > 0, does occ += arr - dep, clears the wave's loads, advances the wave, and
+// marks the order done when the wave was idle (no joiner, dep 0 everywhere).  Fusing the close into the round would need a
+// barrier over the order's workgroups between a round's last store and the next round's first test; a launch boundary is that
+// barrier, and a closing workgroup that has nothing to do exits after two loads.
+struct HeadOrder {
+    int32_t wave;      // the open wave
+    int32_t took;      // a slot joined the open wave
+    int32_t done;      // the first idle wave was seen
+    int32_t n_waves;   // 1 + the last wave that holds a moving partition
+    int32_t bid[3];    // bid[(r + 1) % 3] != 0: round r had a bidder
+    int32_t mf_wave, mf_broker;
+    int32_t stuck;
+    unsigned long long mf;   // least free bytes so far, ~0 = none
+};
+
+__device__ inline uint64_t ld64(const uint64_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+__device__ inline void st64(uint64_t *p, uint64_t v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+__device__ inline int32_t ld32(const int32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+__device__ inline void st32(int32_t *p, int32_t v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+
+// One thread per partition: dep0[b] = bytes that leave b in wave 0 with the metadata-only partitions (changed, nothing added).
+__global__ void k_head_dep0(int32_t P, int32_t W, const uint16_t *__restrict__ cur, const uint16_t *__restrict__ tgt,
+                            const uint64_t *__restrict__ size, unsigned long long *__restrict__ dep0) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    uint16_t c[KAO_MAX_RF], n[KAO_MAX_RF];
+    bool changed = false;
+    for (int i = 0; i < W; ++i) {
+        c[i] = cur[p * W + i];
+        n[i] = tgt[p * W + i];
+        changed |= c[i] != n[i];
+    }
+    if (!changed || size[p] == 0) return;
+    for (int i = 0; i < W; ++i) {   // any added broker: the partition moves data and leaves with its own wave
+        if (n[i] == KAO_NONE) continue;
+        bool held = false;
+        for (int j = 0; j < W; ++j) held |= c[j] == n[i];
+        if (!held) return;
+    }
+    for (int i = 0; i < W; ++i) {
+        if (c[i] == KAO_NONE) continue;
+        bool kept = false;
+        for (int j = 0; j < W; ++j) kept |= n[j] == c[i];
+        if (!kept) atomicAdd(&dep0[c[i]], (unsigned long long)size[p]);
+    }
+}
+
+// grid = (brokers / 256, orders): every order starts from occ = stored and wave 0's departures.
+__global__ void k_head_init(int32_t B, const uint64_t *__restrict__ stored, const unsigned long long *__restrict__ dep0,
+                            uint64_t *__restrict__ occ, uint64_t *__restrict__ dep) {
+    const int32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const size_t e = (size_t)blockIdx.y * B + b;
+    occ[e] = stored[b];
+    dep[e] = dep0[b];
+}
+
+__global__ void k_head_round(int32_t r, int32_t n_ord, int32_t n_mv, int32_t B, int32_t W, int32_t k, uint64_t C, uint64_t seed,
+                             const uint16_t *__restrict__ cur, const uint16_t *__restrict__ tgt, const uint64_t *__restrict__ size,
+                             const uint64_t *__restrict__ capacity, const uint16_t *__restrict__ part,
+                             const uint8_t *__restrict__ npart, const int32_t *__restrict__ mv_idx, const uint32_t *__restrict__ khi,
+                             const uint64_t *__restrict__ traf, unsigned long long *__restrict__ mk, uint64_t *__restrict__ occ,
+                             uint64_t *__restrict__ arr, uint64_t *__restrict__ dep, uint64_t *__restrict__ byt, int32_t *__restrict__ cnt,
+                             int32_t *__restrict__ waveo, int32_t *__restrict__ skipw, HeadOrder *__restrict__ ord) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t o = blockIdx.y;
+    HeadOrder *ho = ord + o;
+    if (ho->done) return;   // uniform over the order's workgroups: written by the close step only
+    const size_t per = (size_t)n_ord * B, ob = (size_t)o * B;
+    {   // clear this order's row of round r + 2 (read by round r - 1, bid into by round r + 1)
+        unsigned long long *clr = mk + (size_t)((r + 2) % 3) * per + ob;
+        for (int32_t e = i; e < B; e += gridDim.x * blockDim.x) clr[e] = ~0ull;
+        if (i == 0) ho->bid[(r + 2) % 3] = 0;
+    }
+    const int32_t w = ho->wave;
+    bool bids = false;
+    const size_t os = (size_t)o * n_mv + (i < n_mv ? i : 0);
+    if (i < n_mv && waveo[os] < 0 && skipw[os] != w) {
+        const int32_t p = mv_idx[i];
+        const int np = npart[i];
+        const int n_added = cur[(size_t)p * W] != KAO_NONE ? np - 1 : np;   // the source, when there is one, is the last participant
+        const uint64_t sz = size[p];
+        const uint16_t *pb = part + (size_t)i * kWavePart;   // re-read per loop rather than kept in a runtime-indexed array
+        const uint64_t *pt = traf + (size_t)i * kWavePart;
+        bool fit = true;
+        for (int j = 0; j < np; ++j) {
+            const size_t e = ob + pb[j];
+            if (k) fit &= ld32(&cnt[e]) < k;
+            if (C) {
+                const uint64_t l = ld64(&byt[e]);
+                fit &= l == 0 || l + pt[j] <= C;                        // loads stay below 2^63: no overflow
+            }
+            if (j < n_added && sz)                                      // occ + arr < 2^63, size < 2^62: no overflow
+                fit &= ld64(&occ[e]) + ld64(&arr[e]) + sz <= capacity[pb[j]];
+        }
+        if (!fit) {
+            skipw[os] = w;
+        } else {
+            const unsigned long long key = wave_key(o, (uint32_t)p, khi[i], wave_salt(seed, o));
+            const unsigned long long *mine = mk + (size_t)(r % 3) * per + ob;
+            bool ready = true;
+            for (int j = 0; j < np; ++j) ready &= mine[pb[j]] == key;
+            if (ready) {
+                for (int j = 0; j < np; ++j) {
+                    const size_t e = ob + pb[j];
+                    if (k) st32(&cnt[e], cnt[e] + 1);
+                    if (C) st64(&byt[e], byt[e] + pt[j]);
+                    if (j < n_added) st64(&arr[e], arr[e] + sz);
+                }
+                if (sz) {
+                    for (int c = 0; c < W; ++c) {   // rem(p) = current \ target
+                        const uint16_t cb = cur[(size_t)p * W + c];
+                        if (cb == KAO_NONE) continue;
+                        bool kept = false;
+                        for (int j = 0; j < W; ++j) kept |= tgt[(size_t)p * W + j] == cb;
+                        if (!kept) atomicAdd(reinterpret_cast<unsigned long long *>(&dep[ob + cb]), (unsigned long long)sz);
+                    }
+                }
+                waveo[os] = w;
+                st32(&ho->took, 1);
+            } else {
+                unsigned long long *next = mk + (size_t)((r + 1) % 3) * per + ob;
+                for (int j = 0; j < np; ++j) atomicMin(&next[pb[j]], key);
+                bids = true;
+            }
+        }
+    }
+    if (__ballot(bids) != 0ull && __lane_id() == 0) st32(&ho->bid[(r + 1) % 3], 1);
+}
+
+// grid = orders, one workgroup each, after round r.  n_done counts the orders that have seen their idle wave.
+__global__ void __launch_bounds__(kWaveThreads) k_head_close(int32_t r, int32_t B, const uint64_t *__restrict__ capacity,
+                                                             uint64_t *__restrict__ occ, uint64_t *__restrict__ arr, uint64_t *__restrict__ dep,
+                                                             uint64_t *__restrict__ byt, int32_t *__restrict__ cnt, HeadOrder *__restrict__ ord,
+                                                             int32_t *__restrict__ n_done) {
+    __shared__ unsigned long long s_free[kWaveThreads];
+    __shared__ int32_t s_b[kWaveThreads];
+    __shared__ int32_t s_dep[kWaveThreads];
+    HeadOrder *ho = ord + blockIdx.x;
+    if (ho->done || ho->bid[(r + 1) % 3]) return;   // uniform over the workgroup
+    const size_t ob = (size_t)blockIdx.x * B;
+    unsigned long long mf = ~0ull;
+    int32_t mb = -1, any_dep = 0;
+    for (int32_t b = threadIdx.x; b < B; b += kWaveThreads) {   // ascending b per thread: the first minimum is the lowest broker
+        const uint64_t a = arr[ob + b], d = dep[ob + b];
+        any_dep |= d != 0;
+        if (a) {
+            const uint64_t fr = capacity[b] - occ[ob + b] - a;   // the fit test held: no wrap
+            if (fr < mf) { mf = fr; mb = b; }
+        }
+        if (a | d) occ[ob + b] += a - d;                          // stored >= every departure (host check): no wrap
+        arr[ob + b] = 0;
+        dep[ob + b] = 0;
+        byt[ob + b] = 0;
+        cnt[ob + b] = 0;
+    }
+    s_free[threadIdx.x] = mf;
+    s_b[threadIdx.x] = mb;
+    s_dep[threadIdx.x] = any_dep;
+    __syncthreads();
+    for (int off = kWaveThreads / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            const unsigned long long f2 = s_free[threadIdx.x + off];
+            const int32_t b2 = s_b[threadIdx.x + off];
+            if (b2 >= 0 && (s_b[threadIdx.x] < 0 || f2 < s_free[threadIdx.x] || (f2 == s_free[threadIdx.x] && b2 < s_b[threadIdx.x]))) {
+                s_free[threadIdx.x] = f2;
+                s_b[threadIdx.x] = b2;
+            }
+            s_dep[threadIdx.x] |= s_dep[threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int32_t w = ho->wave;
+        if (s_b[0] >= 0 && (ho->mf_broker < 0 || s_free[0] < ho->mf)) {   // strictly less: the earliest wave keeps a tie
+            ho->mf = s_free[0];
+            ho->mf_wave = w;
+            ho->mf_broker = s_b[0];
+        }
+        if (ho->took) ho->n_waves = w + 1;
+        if (!ho->took && !s_dep[0]) {
+            ho->done = 1;
+            atomicAdd(n_done, 1);
+        }
+        ho->took = 0;
+        ho->wave = w + 1;
+    }
+}
+
+// grid = (slots / 256, orders): the stuck slots of every order.
+__global__ void k_head_tally(int32_t n_mv, const int32_t *__restrict__ waveo, HeadOrder *__restrict__ ord) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long m = __ballot(i < n_mv && waveo[(size_t)blockIdx.y * n_mv + (i < n_mv ? i : 0)] < 0);
+    if (m != 0ull && __lane_id() == 0) atomicAdd(&ord[blockIdx.y].stuck, __popcll(m));
+}
+
+__global__ void k_head_scatter(int32_t n_mv, const int32_t *__restrict__ waveo, const int32_t *__restrict__ mv_idx, int32_t *__restrict__ wave) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_mv) wave[mv_idx[i]] = waveo[i] < 0 ? -2 : waveo[i];
+}
+
 // device buffers of one call, released on every return path (not CallBufs of kao_host.h: a call allocates up to 1 GiB, which must
 // not be parked in the arena pool)
 struct WaveBufs {
@@ -315,7 +535,7 @@ int validate_waves(const char *fn, int32_t B, int32_t P, int32_t W, const uint16
 
 // T_b, the bytes broker b moves over the whole plan, with overflow-checked arithmetic: every load and every load + t_p(b) of the
 // kernel then stays below 2^63.  KAO_ERR_INVALID when some T_b reaches 2^62.  Rows are valid (validate_waves).
-int validate_traffic(int32_t B, int32_t P, int32_t W, const uint16_t *cur, const uint16_t *tgt, const uint64_t *size) {
+int validate_traffic(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *cur, const uint16_t *tgt, const uint64_t *size) {
     constexpr uint64_t kLimit = uint64_t(1) << 62;
     std::vector<uint64_t> tot((size_t)B, 0);
     for (int64_t p = 0; p < P; ++p) {
@@ -334,7 +554,7 @@ int validate_traffic(int32_t B, int32_t P, int32_t W, const uint16_t *cur, const
         for (int j = 0; j < na && !bad; ++j) bad = __builtin_add_overflow(tot[add[j]], size[p], &tot[add[j]]) || tot[add[j]] >= kLimit;
         if (!bad && c[0] != KAO_NONE) bad = __builtin_add_overflow(tot[c[0]], src, &tot[c[0]]) || tot[c[0]] >= kLimit;
         if (bad)
-            return fail(KAO_ERR_INVALID, "kao_plan_waves_sized: partition " + std::to_string(p) + ": a broker's traffic reaches 2^62 bytes");
+            return fail(KAO_ERR_INVALID, std::string(fn) + ": partition " + std::to_string(p) + ": a broker's traffic reaches 2^62 bytes");
     }
     return KAO_OK;
 }
@@ -439,6 +659,178 @@ int plan_waves(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *
     return KAO_OK;
 }
 
+// stored[b] against the bytes that leave b over the whole plan (rem(p) = current \ target of every changed partition), and the
+// 2^62 limit.  Rows are valid (validate_waves).
+int validate_stored(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *cur, const uint16_t *tgt, const uint64_t *size,
+                    const uint64_t *stored) {
+    constexpr uint64_t kLimit = uint64_t(1) << 62;
+    const std::string f = fn;
+    for (int32_t b = 0; b < B; ++b)
+        if (stored[b] >= kLimit) return fail(KAO_ERR_INVALID, f + ": stored[" + std::to_string(b) + "] reaches 2^62 bytes");
+    std::vector<uint64_t> left(stored, stored + B);
+    for (int64_t p = 0; p < P; ++p) {
+        const uint16_t *c = cur + p * W, *n = tgt + p * W;
+        for (int i = 0; i < W; ++i) {
+            if (c[i] == KAO_NONE) continue;
+            bool kept = false;
+            for (int j = 0; j < W; ++j) kept |= n[j] == c[i];
+            if (kept) continue;
+            if (left[c[i]] < size[p])
+                return fail(KAO_ERR_INVALID, f + ": stored[" + std::to_string(c[i]) + "] is below the bytes of the partitions that leave the broker (partition " +
+                                                 std::to_string(p) + ")");
+            left[c[i]] -= size[p];
+        }
+    }
+    return KAO_OK;
+}
+
+int plan_headroom(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *current, const uint16_t *target, const uint64_t *size,
+                  const uint64_t *stored, const uint64_t *capacity, uint64_t C, int32_t k, uint64_t seed, int32_t *wave, int32_t *n_waves,
+                  int32_t *lower_bound, int64_t *stats) {
+    int rc = require_init();
+    if (rc) return rc;
+    *n_waves = 0;
+    *lower_bound = 0;
+    int64_t st8[8] = {0, 0, -1, 0, 0, -1, -1, -1};
+    if (P == 0) {
+        if (stats) std::copy(st8, st8 + 8, stats);
+        return KAO_OK;
+    }
+    WaveBufs m;
+    HIP_TRY(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
+    hipStream_t st = m.stream;
+    uint16_t *d_cur, *d_tgt, *d_part;
+    uint8_t *d_npart;
+    int32_t *d_wave, *d_mv, *d_deg, *d_ctl;
+    uint32_t *d_khi;
+    uint64_t *d_size, *d_traf, *d_stored, *d_capacity;
+    unsigned long long *d_tot, *d_clamp, *d_dep0;
+    const size_t PW = (size_t)P * W;
+    if ((rc = m.alloc(&d_cur, PW)) || (rc = m.alloc(&d_tgt, PW)) || (rc = m.alloc(&d_part, (size_t)P * kWavePart)) ||
+        (rc = m.alloc(&d_npart, (size_t)P)) || (rc = m.alloc(&d_wave, (size_t)P)) || (rc = m.alloc(&d_mv, (size_t)P)) ||
+        (rc = m.alloc(&d_deg, (size_t)B)) || (rc = m.alloc(&d_khi, (size_t)P)) || (rc = m.alloc(&d_ctl, CTL_N)) ||
+        (rc = m.alloc(&d_size, (size_t)P)) || (rc = m.alloc(&d_traf, (size_t)P * kWavePart)) || (rc = m.alloc(&d_tot, (size_t)B)) ||
+        (rc = m.alloc(&d_clamp, (size_t)B)) || (rc = m.alloc(&d_dep0, (size_t)B)) || (rc = m.alloc(&d_stored, (size_t)B)) ||
+        (rc = m.alloc(&d_capacity, (size_t)B)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_cur, current, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_tgt, target, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_stored, stored, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_capacity, capacity, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_deg, 0, (size_t)B * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(d_ctl, 0, CTL_N * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(d_tot, 0, (size_t)B * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(d_clamp, 0, (size_t)B * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(d_dep0, 0, (size_t)B * sizeof(unsigned long long), st));
+    const unsigned pblocks = (unsigned)(((size_t)P + kWaveThreads - 1) / kWaveThreads);
+    k_wave_classify<true><<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_wave, d_part, d_npart, d_mv, d_deg, d_ctl, d_size, C, d_traf,
+                                                            d_tot, d_clamp);
+    HIP_TRY(hipGetLastError());
+    int32_t ctl[CTL_N];
+    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int32_t n_mv = ctl[CTL_NMV];
+    int32_t best_waves = 0;
+    if (n_mv > 0) {
+        const unsigned mblocks = (unsigned)((n_mv + kWaveThreads - 1) / kWaveThreads);
+        k_wave_bound<true><<<mblocks, kWaveThreads, 0, st>>>(n_mv, k, d_part, d_npart, d_deg, d_khi, d_ctl, C, d_traf, d_tot, d_clamp);
+        HIP_TRY(hipGetLastError());
+        k_head_dep0<<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_size, d_dep0);
+        HIP_TRY(hipGetLastError());
+        // per-order state: occ, arr, dep, byt (8 bytes) and cnt (4) per broker, three minkey rows, waveo and skipw per slot
+        const size_t per_order = (size_t)B * (4 * 8 + 4 + 3 * 8) + (size_t)n_mv * 8;
+        const int n_ord = (int)std::max<size_t>(1, std::min<size_t>(kWaveOrders, kWaveBudget / per_order));
+        const size_t OB = (size_t)n_ord * B, OS = (size_t)n_ord * n_mv;
+        uint64_t *d_occ, *d_arr, *d_dep, *d_byt;
+        int32_t *d_cnt, *d_waveo, *d_skipw, *d_ndone;
+        unsigned long long *d_mk;
+        HeadOrder *d_ord;
+        if ((rc = m.alloc(&d_occ, OB)) || (rc = m.alloc(&d_arr, OB)) || (rc = m.alloc(&d_dep, OB)) || (rc = m.alloc(&d_byt, OB)) ||
+            (rc = m.alloc(&d_cnt, OB)) || (rc = m.alloc(&d_mk, 3 * OB)) || (rc = m.alloc(&d_waveo, OS)) || (rc = m.alloc(&d_skipw, OS)) ||
+            (rc = m.alloc(&d_ord, (size_t)n_ord)) || (rc = m.alloc(&d_ndone, 1)))
+            return rc;
+        HIP_TRY(hipMemsetAsync(d_arr, 0, OB * sizeof(uint64_t), st));
+        HIP_TRY(hipMemsetAsync(d_byt, 0, OB * sizeof(uint64_t), st));
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, OB * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(d_mk, 0xFF, 2 * OB * sizeof(unsigned long long), st));   // rows of rounds 0 and 1
+        HIP_TRY(hipMemsetAsync(d_waveo, 0xFF, OS * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(d_skipw, 0xFF, OS * sizeof(int32_t), st));
+        HIP_TRY(hipMemsetAsync(d_ndone, 0, sizeof(int32_t), st));
+        std::vector<HeadOrder> ord((size_t)n_ord);
+        for (HeadOrder &h : ord) h = HeadOrder{0, 0, 0, 0, {0, 0, 0}, -1, -1, 0, ~0ull};
+        HIP_TRY(hipMemcpyAsync(d_ord, ord.data(), ord.size() * sizeof(HeadOrder), hipMemcpyHostToDevice, st));
+        k_head_init<<<dim3((unsigned)((B + kWaveThreads - 1) / kWaveThreads), (unsigned)n_ord), kWaveThreads, 0, st>>>(B, d_stored, d_dep0, d_occ, d_dep);
+        HIP_TRY(hipGetLastError());
+        const dim3 grid(mblocks, (unsigned)n_ord);
+        // an order has at most n_mv + 2 waves (every wave but the first and the last takes a partition), a wave at most n_mv + 2
+        // rounds (every round but its first and its last decides a slot)
+        const int64_t max_rounds = ((int64_t)n_mv + 2) * ((int64_t)n_mv + 2);
+        int64_t r = 0;
+        int32_t n_done = 0;
+        while (n_done < n_ord) {
+            if (r > max_rounds) return fail(KAO_ERR_HIP, std::string(fn) + ": rounds did not finish");
+            for (int i = 0; i < kWaveBatch; ++i, ++r) {
+                const int32_t r3 = (int32_t)(r % 3);   // the kernels use the round number modulo 3 only
+                k_head_round<<<grid, kWaveThreads, 0, st>>>(r3, n_ord, n_mv, B, W, k, C, seed, d_cur, d_tgt, d_size, d_capacity, d_part, d_npart,
+                                                            d_mv, d_khi, d_traf, d_mk, d_occ, d_arr, d_dep, d_byt, d_cnt, d_waveo, d_skipw, d_ord);
+                k_head_close<<<(unsigned)n_ord, kWaveThreads, 0, st>>>(r3, B, d_capacity, d_occ, d_arr, d_dep, d_byt, d_cnt, d_ord, d_ndone);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&n_done, d_ndone, sizeof n_done, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        k_head_tally<<<grid, kWaveThreads, 0, st>>>(n_mv, d_waveo, d_ord);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ord.data(), d_ord, ord.size() * sizeof(HeadOrder), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        int best = 0;   // fewest stuck, then fewest waves, then the lowest order
+        for (int o = 1; o < n_ord; ++o)
+            if (ord[(size_t)o].stuck < ord[(size_t)best].stuck ||
+                (ord[(size_t)o].stuck == ord[(size_t)best].stuck && ord[(size_t)o].n_waves < ord[(size_t)best].n_waves))
+                best = o;
+        const HeadOrder &h = ord[(size_t)best];
+        best_waves = h.n_waves;
+        st8[0] = h.stuck;
+        st8[2] = best;
+        st8[3] = n_ord;
+        st8[4] = r;
+        if (h.mf_broker >= 0) {
+            st8[5] = (int64_t)std::min<unsigned long long>(h.mf, (unsigned long long)INT64_MAX);
+            st8[6] = h.mf_wave;
+            st8[7] = h.mf_broker;
+        }
+        k_head_scatter<<<mblocks, kWaveThreads, 0, st>>>(n_mv, d_waveo + (size_t)best * n_mv, d_mv, d_wave);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(wave, d_wave, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    auto n_added = [&](int64_t p) {
+        int na = 0;
+        for (int i = 0; i < W; ++i) {
+            const uint16_t b = target[p * W + i];
+            if (b == KAO_NONE) continue;
+            bool held = false;
+            for (int j = 0; j < W; ++j) held |= current[p * W + j] == b;
+            na += !held;
+        }
+        return na;
+    };
+    bool meta = false;   // metadata-only partitions share wave 0
+    for (int64_t p = 0; p < P; ++p) {
+        if (wave[p] == -2) {   // stuck bytes: one copy per added broker, each product below 2^62 (part of a broker's checked traffic)
+            if (__builtin_add_overflow(st8[1], (int64_t)((uint64_t)n_added(p) * size[p]), &st8[1])) st8[1] = INT64_MAX;
+        } else if (wave[p] == 0 && !meta) {
+            meta = n_added(p) == 0;
+        }
+    }
+    *n_waves = std::max<int32_t>(best_waves, meta ? 1 : 0);
+    *lower_bound = n_mv > 0 ? ctl[CTL_LB] : *n_waves;
+    if (stats) std::copy(st8, st8 + 8, stats);
+    return KAO_OK;
+}
+
 }  // namespace
 
 extern "C" int kao_plan_waves(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
@@ -460,7 +852,24 @@ extern "C" int kao_plan_waves_sized(int32_t n_brokers, int32_t n_partitions, int
     if (max_per_broker < 0) return fail(KAO_ERR_INVALID, "kao_plan_waves_sized: max_per_broker must be >= 0");
     if (max_per_broker == 0 && max_bytes_per_broker == 0)
         return fail(KAO_ERR_INVALID, "kao_plan_waves_sized: max_bytes_per_broker and max_per_broker are both 0 (no cap)");
-    if ((rc = validate_traffic(n_brokers, n_partitions, width, current, target, size))) return rc;
+    if ((rc = validate_traffic(fn, n_brokers, n_partitions, width, current, target, size))) return rc;
     return plan_waves<true>(fn, n_brokers, n_partitions, width, current, target, size, max_bytes_per_broker, max_per_broker, seed, wave,
                             n_waves, lower_bound);
+}
+
+extern "C" int kao_plan_waves_headroom(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,
+                                       const uint64_t *size, const uint64_t *stored, const uint64_t *capacity, uint64_t max_bytes_per_broker,
+                                       int32_t max_per_broker, uint64_t seed, int32_t *wave, int32_t *n_waves, int32_t *lower_bound,
+                                       int64_t stats[8]) {
+    const char *fn = "kao_plan_waves_headroom";
+    int rc = validate_waves(fn, n_brokers, n_partitions, width, current, target, wave, n_waves, lower_bound);
+    if (rc) return rc;
+    if (!size) return fail(KAO_ERR_INVALID, "kao_plan_waves_headroom: null size");
+    if (!stored) return fail(KAO_ERR_INVALID, "kao_plan_waves_headroom: null stored");
+    if (!capacity) return fail(KAO_ERR_INVALID, "kao_plan_waves_headroom: null capacity");
+    if (max_per_broker < 0) return fail(KAO_ERR_INVALID, "kao_plan_waves_headroom: max_per_broker must be >= 0");
+    if ((rc = validate_traffic(fn, n_brokers, n_partitions, width, current, target, size))) return rc;
+    if ((rc = validate_stored(fn, n_brokers, n_partitions, width, current, target, size, stored))) return rc;
+    return plan_headroom(fn, n_brokers, n_partitions, width, current, target, size, stored, capacity, max_bytes_per_broker, max_per_broker,
+                         seed, wave, n_waves, lower_bound, stats);
 }
