@@ -483,7 +483,8 @@ int kao_plan_waves_sized(int32_t n_brokers, int32_t n_partitions, int32_t width,
  * of kao_plan_waves_sized.  stats (may be NULL): [0] stuck partitions, [1] stuck bytes (sum of n_added(p) * size[p], at most
  * 2^63 - 1), [2] the winning order (-1: nothing moves), [3] orders run, [4] round launches, [5] the least free bytes seen, capacity - occ - arr over
  * (wave, broker that receives bytes) of the winning order, at most 2^63 - 1 (-1: none), [6] its wave, [7] its broker (the first
- * wave, then the lowest broker on ties).  KAO_ERR_INVALID, checked before any device is used: everything kao_plan_waves_sized
+ * wave, then the lowest broker on ties).  Candidates are compared after the clamp: free values above 2^63 - 1 tie.
+ * KAO_ERR_INVALID, checked before any device is used: everything kao_plan_waves_sized
  * rejects except both caps 0, and stored == NULL, capacity == NULL, some stored[b] >= 2^62, or some stored[b] below the sum of
  * size[p] over the changed partitions p that leave b. */
 int kao_plan_waves_headroom(int32_t n_brokers, int32_t n_partitions, int32_t width, const uint16_t *current, const uint16_t *target,

@@ -436,7 +436,8 @@ __global__ void __launch_bounds__(kWaveThreads) k_head_close(int32_t r, int32_t 
         const uint64_t a = arr[ob + b], d = dep[ob + b];
         any_dep |= d != 0;
         if (a) {
-            const uint64_t fr = capacity[b] - occ[ob + b] - a;   // the fit test held: no wrap
+            // the fit test held: no wrap; clamped as it is reported, before every comparison (here, the reduction, ho->mf)
+            const uint64_t fr = std::min<uint64_t>(capacity[b] - occ[ob + b] - a, (uint64_t)INT64_MAX);
             if (fr < mf) { mf = fr; mb = b; }
         }
         if (a | d) occ[ob + b] += a - d;                          // stored >= every departure (host check): no wrap

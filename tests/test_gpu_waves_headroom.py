@@ -1,6 +1,7 @@
 """kao_plan_waves_headroom on the MI355X: waves as a sequence of states, each of which fits every disk.  Every
 result is bit for bit the sequential reference of tests/waves_headroom_ref.py (wave, n_waves, lower_bound, stats[0..3] and [5..7])
-and passes its independent checker; at capacity 2^63 it is also what kao_plan_waves_sized returns on the device."""
+and passes its independent checker; at capacity 2^63 it is also what kao_plan_waves_sized returns on the device.
+One case per kernel path (wide broker indices, ties, capacities above 2^63, batch edges): tests/test_gpu_waves_headroom_paths.py."""
 import numpy as np
 import pytest
 
