@@ -72,19 +72,6 @@ std::vector<std::pair<Key, std::vector<int>>> entries(const std::string &path, c
     return out;
 }
 
-// participants of one partition and their copies of it: 1 at each added broker, n_added at the source; empty when it moves no data
-std::vector<std::pair<int, uint64_t>> traffic(const uint16_t *c, const uint16_t *t, size_t W) {
-    std::vector<std::pair<int, uint64_t>> out;
-    for (size_t i = 0; i < W; ++i) {
-        if (t[i] == KAO_NONE) continue;
-        bool held = false;
-        for (size_t j = 0; j < W; ++j) held |= c[j] == t[i];
-        if (!held) out.emplace_back(t[i], 1);
-    }
-    if (!out.empty() && c[0] != KAO_NONE) out.emplace_back(c[0], (uint64_t)out.size());
-    return out;
-}
-
 std::string quoted(const std::string &s) {
     std::string o = "\"";
     for (char c : s) {
@@ -94,246 +81,303 @@ std::string quoted(const std::string &s) {
     return o + "\"";
 }
 
-}  // namespace
+// "a, b, c, d, e and N more": the first five of a list that may be long
+std::string name_list(const std::vector<std::string> &items) {
+    std::string out;
+    for (size_t i = 0; i < items.size() && i < 5; ++i) out += (i ? ", " : "") + items[i];
+    if (items.size() > 5) out += " and " + std::to_string(items.size() - 5) + " more";
+    return out;
+}
 
-int main(int argc, char **argv) {
-    std::string cur_path, plan_path, prefix, sizes_path;
-    int k = 0, device = 0;
+// what main makes of the flags
+struct Options {
+    std::string cur_path, plan_path, prefix, sizes_path, caps_arg;
+    int k = 0, device = 0, max_util = 100;
     unsigned long long seed = 1;
     bool report = false, have_k = false, sized = false, have_default = false, headroom = false, have_default_cap = false;
     uint64_t cap_bytes = 0, default_size = 0, default_cap = 0;
-    std::string caps_arg;
-    int max_util = 100;
+};
+
+// The two documents as dense rows over the union broker index: every id of either document, ascending.
+struct Rows {
+    std::vector<Key> keys;                     // the partitions of --current, in document order
+    std::vector<std::vector<int>> replicas;    // per partition: broker ids as the plan lists them, else the current ones (unchanged)
+    std::vector<int> broker_id;                // dense index -> broker id
+    size_t P = 0, W = 1;
+    std::vector<uint16_t> c, t;                // [P, W] current and target, KAO_NONE-padded
+};
+
+Rows map_documents(const Options &o) {
+    Rows r;
+    const auto cur = entries(o.cur_path, "current");
+    const auto plan = entries(o.plan_path, "plan");
+    std::map<Key, size_t> index;
+    for (auto &e : cur) {
+        index[e.first] = r.keys.size();
+        r.keys.push_back(e.first);
+        r.replicas.push_back(e.second);
+    }
+    for (auto &e : plan) {
+        auto it = index.find(e.first);
+        if (it == index.end())
+            throw std::runtime_error("plan names partition " + e.first.first + "-" + std::to_string(e.first.second) + ", which the current assignment does not have");
+        r.replicas[it->second] = e.second;
+    }
+    r.P = cur.size();
+    std::map<int, int> dense;
+    for (size_t i = 0; i < r.P; ++i) {
+        for (int b : cur[i].second) dense[b] = 0;
+        for (int b : r.replicas[i]) dense[b] = 0;
+        r.W = std::max({r.W, cur[i].second.size(), r.replicas[i].size()});
+    }
+    if (r.W > KAO_MAX_RF) throw std::runtime_error("more than " + std::to_string(KAO_MAX_RF) + " replicas in a partition");
+    for (auto &kv : dense) {
+        kv.second = (int)r.broker_id.size();
+        r.broker_id.push_back(kv.first);
+    }
+    r.c.assign(r.P * r.W, KAO_NONE);
+    r.t.assign(r.P * r.W, KAO_NONE);
+    for (size_t i = 0; i < r.P; ++i) {
+        for (size_t j = 0; j < cur[i].second.size(); ++j) r.c[i * r.W + j] = (uint16_t)dense[cur[i].second[j]];
+        for (size_t j = 0; j < r.replicas[i].size(); ++j) r.t[i * r.W + j] = (uint16_t)dense[r.replicas[i][j]];
+    }
+    return r;
+}
+
+// The row test: b is a broker and the row does not hold it.  A partition's added brokers are those of its target row that its
+// current row lacks, its removed ones those of its current row that its target row lacks.
+bool lacks(const uint16_t *row, size_t W, uint16_t b) { return b != KAO_NONE && std::find(row, row + W, b) == row + W; }
+
+// participants of one partition and their copies of it: 1 at each added broker, n_added at the source; empty when it moves no data
+std::vector<std::pair<int, uint64_t>> traffic(const uint16_t *c, const uint16_t *t, size_t W) {
+    std::vector<std::pair<int, uint64_t>> out;
+    for (size_t i = 0; i < W; ++i)
+        if (lacks(c, W, t[i])) out.emplace_back(t[i], 1);
+    if (!out.empty() && c[0] != KAO_NONE) out.emplace_back(c[0], (uint64_t)out.size());
+    return out;
+}
+
+// bytes per partition; every partition that moves data needs one
+std::vector<uint64_t> partition_sizes(const Options &o, const Rows &r) {
+    const std::map<Key, uint64_t> known = o.sizes_path.empty() ? std::map<Key, uint64_t>() : load_sizes(o.sizes_path);
+    std::vector<uint64_t> size(std::max<size_t>(r.P, 1), 0);
+    std::vector<std::string> missing;
+    for (size_t i = 0; i < r.P; ++i) {
+        auto it = known.find(r.keys[i]);
+        if (it != known.end()) size[i] = it->second;
+        else if (!traffic(&r.c[i * r.W], &r.t[i * r.W], r.W).empty()) {
+            if (o.have_default) size[i] = o.default_size;
+            else missing.push_back(r.keys[i].first + "-" + std::to_string(r.keys[i].second));
+        }
+    }
+    if (!missing.empty()) throw std::runtime_error("no size for moving partitions " + name_list(missing) + " (give them in --sizes or set --default-size)");
+    return size;
+}
+
+// --headroom, per dense broker: what it holds now, its capacity, and capacity * PCT / 100, which the call takes
+struct Disks { std::vector<uint64_t> stored, capacity, effective; };
+
+Disks broker_disks(const Options &o, const Rows &r, const std::vector<uint64_t> &size) {
+    Disks d;
+    std::map<int, std::vector<LogDir>> dirs;
+    if (slurp(o.sizes_path).find("\"brokers\"") != std::string::npos) dirs = load_log_dirs(o.sizes_path);
+    const std::map<int, uint64_t> table = o.caps_arg.empty() ? std::map<int, uint64_t>() : read_broker_capacities(o.caps_arg);
+    d.stored.assign(r.broker_id.size(), 0);
+    for (size_t i = 0; i < r.P; ++i)
+        for (size_t j = 0; j < r.W; ++j)
+            if (r.c[i * r.W + j] != KAO_NONE) d.stored[r.c[i * r.W + j]] += size[i];
+    std::vector<std::string> missing;
+    for (size_t b = 0; b < r.broker_id.size(); ++b) {
+        uint64_t on_disk = 0, total = 0;
+        bool every = false;
+        auto bd = dirs.find(r.broker_id[b]);
+        if (bd != dirs.end()) {
+            every = !bd->second.empty();
+            for (auto &ld : bd->second) {
+                every = every && ld.has_total;
+                total += ld.total_bytes;
+                for (auto &e : ld.entries) on_disk += e.size;   // future replicas too: they are bytes on disk
+            }
+        }
+        d.stored[b] = std::max(d.stored[b], on_disk);
+        auto it = table.find(r.broker_id[b]);
+        if (it != table.end()) d.capacity.push_back(it->second);
+        else if (every && total > 0) d.capacity.push_back(total);
+        else if (o.have_default_cap) d.capacity.push_back(o.default_cap);
+        else missing.push_back(std::to_string(r.broker_id[b]));
+    }
+    if (!missing.empty())
+        throw std::runtime_error("no capacity for brokers " + name_list(missing) +
+                                 " (give them in --capacities, read totalBytes from a kafka-log-dirs --sizes document or set --default-capacity)");
+    for (uint64_t v : d.capacity) d.effective.push_back((uint64_t)((unsigned __int128)v * (unsigned)o.max_util / 100u));
+    return d;
+}
+
+// what a call gives back; the plain and the sized call leave stats[] as it is
+struct Called {
+    std::vector<int32_t> wave;
+    int32_t n_waves = 0, lb = 0;
+    int64_t stats[8] = {0, 0, -1, 0, 0, -1, -1, -1};
+};
+
+// the one call of the library
+Called call(const Options &o, const Rows &r, const std::vector<uint64_t> &size, const Disks &d) {
+    Called c;
+    c.wave.resize(std::max<size_t>(r.P, 1));
+    const int32_t B = (int32_t)r.broker_id.size(), P = (int32_t)r.P, W = (int32_t)r.W;
+    const char *const name = o.headroom ? "kao_plan_waves_headroom" : o.sized ? "kao_plan_waves_sized" : "kao_plan_waves";
+    int rc;
+    if (o.headroom)
+        rc = kao_plan_waves_headroom(B, P, W, r.c.data(), r.t.data(), size.data(), d.stored.data(), d.effective.data(), o.cap_bytes, o.k, o.seed, c.wave.data(),
+                                     &c.n_waves, &c.lb, c.stats);
+    else if (o.sized)
+        rc = kao_plan_waves_sized(B, P, W, r.c.data(), r.t.data(), size.data(), o.cap_bytes, o.k, o.seed, c.wave.data(), &c.n_waves, &c.lb);
+    else
+        rc = kao_plan_waves(B, P, W, r.c.data(), r.t.data(), o.k, o.seed, c.wave.data(), &c.n_waves, &c.lb);
+    if (rc) throw std::runtime_error(std::string(name) + ": " + kao_strerror(rc) + " " + kao_last_error());
+    return c;
+}
+
+// the partitions whose wave is `wave_value` as a reassignment document of their own; how many they are
+int write_document(const std::string &path, const Rows &r, const std::vector<int32_t> &wave, int32_t wave_value) {
+    std::ofstream f(path);
+    if (!f) throw std::runtime_error("cannot write " + path);
+    f << "{\"version\":1,\"partitions\":[";
+    int n = 0;
+    for (size_t i = 0; i < r.P; ++i) {
+        if (wave[i] != wave_value) continue;
+        f << (n++ ? ",\n" : "\n") << "    {\"topic\":" << quoted(r.keys[i].first) << ",\"partition\":" << r.keys[i].second << ",\"replicas\":[";
+        for (size_t j = 0; j < r.replicas[i].size(); ++j) f << (j ? "," : "") << r.replicas[i][j];
+        f << "]}";
+    }
+    f << "\n]}\n";
+    if (!f) throw std::runtime_error("cannot write " + path);
+    return n;
+}
+
+// --report, sized: the byte lower bound max_b ceil(sum_p min(t, C) / C) and each wave's busiest broker
+void report_bytes(const Options &o, const Rows &r, const std::vector<uint64_t> &size, const Called &c) {
+    std::map<std::pair<int, int>, uint64_t> load;
+    std::map<int, uint64_t> clamp;
+    for (size_t i = 0; i < r.P; ++i)
+        for (auto &bn : traffic(&r.c[i * r.W], &r.t[i * r.W], r.W)) {
+            const uint64_t tr = bn.second * size[i];   // below 2^62: kao_plan_waves_sized checked the totals
+            if (c.wave[i] >= 0) load[{c.wave[i], bn.first}] += tr;   // a stuck partition (--headroom) is in no wave
+            if (o.cap_bytes) clamp[bn.first] += std::min(tr, o.cap_bytes);
+        }
+    uint64_t blb = 0;
+    for (auto &kv : clamp) blb = std::max(blb, kv.second / o.cap_bytes + (kv.second % o.cap_bytes != 0));
+    std::vector<uint64_t> peak((size_t)c.n_waves, 0);
+    for (auto &kv : load) peak[(size_t)kv.first.first] = std::max(peak[(size_t)kv.first.first], kv.second);
+    std::fprintf(stderr, " bytes_lower_bound=%llu max_broker_bytes_per_wave=", (unsigned long long)blb);
+    for (int w = 0; w < c.n_waves; ++w) std::fprintf(stderr, "%s%llu", w ? "," : "", (unsigned long long)peak[(size_t)w]);
+}
+
+// --report, headroom: the fullest receiving broker of each wave in percent of its capacity (occ follows the waves), then the stats
+void report_utilisation(const Rows &r, const std::vector<uint64_t> &size, const Disks &d, const Called &c) {
+    std::vector<uint64_t> occ = d.stored;
+    std::fprintf(stderr, " fullest_receiver_pct_per_wave=");
+    for (int w = 0; w < c.n_waves; ++w) {
+        std::map<int, uint64_t> arr, dep;
+        for (size_t i = 0; i < r.P; ++i) {
+            if (c.wave[i] != w || size[i] == 0) continue;
+            const uint16_t *cr = &r.c[i * r.W], *tr = &r.t[i * r.W];
+            for (size_t j = 0; j < r.W; ++j) {
+                if (lacks(cr, r.W, tr[j])) arr[tr[j]] += size[i];
+                if (lacks(tr, r.W, cr[j])) dep[cr[j]] += size[i];
+            }
+        }
+        unsigned long long ppm = 0;
+        for (auto &kv : arr) {
+            const uint64_t cap = d.capacity[(size_t)kv.first];
+            const unsigned __int128 v = cap ? (unsigned __int128)(occ[(size_t)kv.first] + kv.second) * 1000000u / cap : 1000000u;
+            ppm = std::max(ppm, (unsigned long long)v);
+        }
+        for (auto &kv : arr) occ[(size_t)kv.first] += kv.second;
+        for (auto &kv : dep) occ[(size_t)kv.first] -= kv.second;
+        std::fprintf(stderr, "%s%llu.%02llu", w ? "," : "", ppm / 10000, ppm / 100 % 100);
+    }
+    std::fprintf(stderr, " min_free=%lld min_free_wave=%lld min_free_broker=%d stuck=%lld stuck_bytes=%lld", (long long)c.stats[5],
+                 (long long)(c.stats[6] >= 0 ? c.stats[6] + 1 : 0), c.stats[7] >= 0 ? r.broker_id[(size_t)c.stats[7]] : -1, (long long)c.stats[0],
+                 (long long)c.stats[1]);
+}
+
+// --report: one line to stderr
+void report(const Options &o, const Rows &r, const std::vector<uint64_t> &size, const Disks &d, const Called &c, const std::vector<int> &per_wave) {
+    std::fprintf(stderr, "waves=%d lower_bound=%d optimal=%s partitions_per_wave=", c.n_waves, c.lb, c.n_waves == c.lb && c.stats[0] == 0 ? "yes" : "no");
+    for (int w = 0; w < c.n_waves; ++w) std::fprintf(stderr, "%s%d", w ? "," : "", per_wave[(size_t)w]);
+    if (o.sized) report_bytes(o, r, size, c);
+    if (o.headroom) report_utilisation(r, size, d, c);
+    std::fprintf(stderr, "\n");
+}
+
+// documents -> rows -> sizes -> disks -> the call -> wave files -> report; every input error comes before the device is touched.
+// The exit status: 3 when partitions are stuck, else 0.
+int run(const Options &o) {
+    const Rows r = map_documents(o);
+    const std::vector<uint64_t> size = o.sized ? partition_sizes(o, r) : std::vector<uint64_t>();
+    const Disks d = o.headroom ? broker_disks(o, r, size) : Disks();
+    const int rc = kao_init(o.device);
+    if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
+    const Called c = call(o, r, size, d);
+    std::vector<int> per_wave;
+    for (int w = 0; w < c.n_waves; ++w) per_wave.push_back(write_document(o.prefix + std::to_string(w + 1) + ".json", r, c.wave, w));
+    if (c.stats[0] > 0) write_document(o.prefix + "-stuck.json", r, c.wave, -2);   // the partitions that fit no wave
+    if (o.report) report(o, r, size, d, c, per_wave);
+    kao_shutdown();
+    if (c.stats[0] > 0) {
+        std::fprintf(stderr, "stuck: %lld partitions, %lld bytes\n", (long long)c.stats[0], (long long)c.stats[1]);
+        return 3;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    Options o;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto need = [&](const char *flag) -> std::string { if (i + 1 >= argc) usage((std::string(flag) + " needs a value").c_str()); return argv[++i]; };
-        if (a == "--current") cur_path = need("--current");
-        else if (a == "--plan") plan_path = need("--plan");
-        else if (a == "--max-per-broker") { k = std::atoi(need("--max-per-broker").c_str()); have_k = true; }
-        else if (a == "--sizes") { sizes_path = need("--sizes"); sized = true; }
+        if (a == "--current") o.cur_path = need("--current");
+        else if (a == "--plan") o.plan_path = need("--plan");
+        else if (a == "--max-per-broker") { o.k = std::atoi(need("--max-per-broker").c_str()); o.have_k = true; }
+        else if (a == "--sizes") { o.sizes_path = need("--sizes"); o.sized = true; }
         else if (a == "--max-bytes-per-broker") {
-            if (!parse_bytes(need("--max-bytes-per-broker"), cap_bytes)) usage("--max-bytes-per-broker needs a byte count (N, or N with K/M/G/T)");
-            sized = true;
+            if (!parse_bytes(need("--max-bytes-per-broker"), o.cap_bytes)) usage("--max-bytes-per-broker needs a byte count (N, or N with K/M/G/T)");
+            o.sized = true;
         } else if (a == "--default-size") {
-            if (!parse_bytes(need("--default-size"), default_size) || default_size > kMaxSize) usage("--default-size needs a byte count up to 2^53");
-            sized = have_default = true;
+            if (!parse_bytes(need("--default-size"), o.default_size) || o.default_size > kMaxSize) usage("--default-size needs a byte count up to 2^53");
+            o.sized = o.have_default = true;
         }
-        else if (a == "--headroom") headroom = true;
-        else if (a == "--capacities") { caps_arg = need("--capacities"); headroom = true; }
+        else if (a == "--headroom") o.headroom = true;
+        else if (a == "--capacities") { o.caps_arg = need("--capacities"); o.headroom = true; }
         else if (a == "--default-capacity") {
-            if (!parse_bytes(need("--default-capacity"), default_cap)) usage("--default-capacity needs a byte count (N, or N with K/M/G/T)");
-            headroom = have_default_cap = true;
+            if (!parse_bytes(need("--default-capacity"), o.default_cap)) usage("--default-capacity needs a byte count (N, or N with K/M/G/T)");
+            o.headroom = o.have_default_cap = true;
         } else if (a == "--max-utilisation") {
             const std::string v = need("--max-utilisation");
-            if (v.empty() || v.size() > 3 || v.find_first_not_of("0123456789") != std::string::npos || (max_util = std::atoi(v.c_str())) < 1 || max_util > 100)
+            if (v.empty() || v.size() > 3 || v.find_first_not_of("0123456789") != std::string::npos || (o.max_util = std::atoi(v.c_str())) < 1 || o.max_util > 100)
                 usage("--max-utilisation needs a percentage 1..100");
-            headroom = true;
+            o.headroom = true;
         }
-        else if (a == "--out-prefix") prefix = need("--out-prefix");
-        else if (a == "--seed") seed = std::strtoull(need("--seed").c_str(), nullptr, 0);
-        else if (a == "--device") device = std::atoi(need("--device").c_str());
-        else if (a == "--report") report = true;
+        else if (a == "--out-prefix") o.prefix = need("--out-prefix");
+        else if (a == "--seed") o.seed = std::strtoull(need("--seed").c_str(), nullptr, 0);
+        else if (a == "--device") o.device = std::atoi(need("--device").c_str());
+        else if (a == "--report") o.report = true;
         else if (a == "-h" || a == "--help") usage(nullptr);
         else usage(("unknown flag " + a).c_str());
     }
-    if (cur_path.empty() || plan_path.empty() || prefix.empty()) usage("--current, --plan and --out-prefix are required");
-    if (headroom && sizes_path.empty()) usage("--headroom needs --sizes");
-    if (headroom && k < 0) usage("--max-per-broker must be >= 0");
-    sized = sized || headroom;
-    if (!sized && k < 1) usage("--max-per-broker needs a value >= 1");
-    if (sized && !headroom && (k < 0 || (k == 0 && cap_bytes == 0)))
-        usage(have_k ? "--max-per-broker must be >= 0, and a cap must be set (--max-per-broker >= 1 or --max-bytes-per-broker >= 1)"
-                     : "give --max-per-broker K >= 1 or --max-bytes-per-broker N >= 1");
+    if (o.cur_path.empty() || o.plan_path.empty() || o.prefix.empty()) usage("--current, --plan and --out-prefix are required");
+    if (o.headroom && o.sizes_path.empty()) usage("--headroom needs --sizes");
+    if (o.headroom && o.k < 0) usage("--max-per-broker must be >= 0");
+    o.sized = o.sized || o.headroom;
+    if (!o.sized && o.k < 1) usage("--max-per-broker needs a value >= 1");
+    if (o.sized && !o.headroom && (o.k < 0 || (o.k == 0 && o.cap_bytes == 0)))
+        usage(o.have_k ? "--max-per-broker must be >= 0, and a cap must be set (--max-per-broker >= 1 or --max-bytes-per-broker >= 1)"
+                       : "give --max-per-broker K >= 1 or --max-bytes-per-broker N >= 1");
     try {
-        const auto cur = entries(cur_path, "current");
-        const auto plan = entries(plan_path, "plan");
-        std::map<Key, size_t> index;
-        for (size_t i = 0; i < cur.size(); ++i) index[cur[i].first] = i;
-        std::vector<const std::vector<int> *> tgt(cur.size());
-        for (size_t i = 0; i < cur.size(); ++i) tgt[i] = &cur[i].second;
-        for (auto &e : plan) {
-            auto it = index.find(e.first);
-            if (it == index.end())
-                throw std::runtime_error("plan names partition " + e.first.first + "-" + std::to_string(e.first.second) + ", which the current assignment does not have");
-            tgt[it->second] = &e.second;
-        }
-        // union broker index: every id of either document, ascending
-        std::map<int, int> dense;
-        size_t width = 1;
-        for (size_t i = 0; i < cur.size(); ++i) {
-            for (int b : cur[i].second) dense[b] = 0;
-            for (int b : *tgt[i]) dense[b] = 0;
-            width = std::max({width, cur[i].second.size(), tgt[i]->size()});
-        }
-        if (width > KAO_MAX_RF) throw std::runtime_error("more than " + std::to_string(KAO_MAX_RF) + " replicas in a partition");
-        int nb = 0;
-        for (auto &kv : dense) kv.second = nb++;
-        const size_t P = cur.size(), W = width;
-        std::vector<uint16_t> c(P * W, KAO_NONE), t(P * W, KAO_NONE);
-        for (size_t i = 0; i < P; ++i) {
-            for (size_t j = 0; j < cur[i].second.size(); ++j) c[i * W + j] = (uint16_t)dense[cur[i].second[j]];
-            for (size_t j = 0; j < tgt[i]->size(); ++j) t[i * W + j] = (uint16_t)dense[(*tgt[i])[j]];
-        }
-        std::vector<uint64_t> size;
-        if (sized) {   // bytes per partition; every partition that moves data needs one
-            const std::map<Key, uint64_t> known = sizes_path.empty() ? std::map<Key, uint64_t>() : load_sizes(sizes_path);
-            size.assign(std::max<size_t>(P, 1), 0);
-            std::vector<std::string> missing;
-            for (size_t i = 0; i < P; ++i) {
-                auto it = known.find(cur[i].first);
-                if (it != known.end()) size[i] = it->second;
-                else if (!traffic(&c[i * W], &t[i * W], W).empty()) {
-                    if (have_default) size[i] = default_size;
-                    else missing.push_back(cur[i].first.first + "-" + std::to_string(cur[i].first.second));
-                }
-            }
-            if (!missing.empty()) {
-                std::string msg = "no size for moving partitions ";
-                for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + missing[i];
-                if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
-                throw std::runtime_error(msg + " (give them in --sizes or set --default-size)");
-            }
-        }
-        std::vector<uint64_t> stored, capacity, effective;   // per dense broker (--headroom)
-        std::vector<int> broker_id((size_t)nb);
-        for (auto &kv : dense) broker_id[(size_t)kv.second] = kv.first;
-        if (headroom) {
-            std::map<int, std::vector<LogDir>> dirs;
-            if (slurp(sizes_path).find("\"brokers\"") != std::string::npos) dirs = load_log_dirs(sizes_path);
-            const std::map<int, uint64_t> table = caps_arg.empty() ? std::map<int, uint64_t>() : read_broker_capacities(caps_arg);
-            stored.assign((size_t)nb, 0);
-            for (size_t i = 0; i < P; ++i)
-                for (size_t j = 0; j < W; ++j)
-                    if (c[i * W + j] != KAO_NONE) stored[c[i * W + j]] += size[i];
-            std::vector<int> missing;
-            for (int b = 0; b < nb; ++b) {
-                uint64_t on_disk = 0, total = 0;
-                bool every = false;
-                auto d = dirs.find(broker_id[(size_t)b]);
-                if (d != dirs.end()) {
-                    every = !d->second.empty();
-                    for (auto &ld : d->second) {
-                        every = every && ld.has_total;
-                        total += ld.total_bytes;
-                        for (auto &e : ld.entries) on_disk += e.size;   // future replicas too: they are bytes on disk
-                    }
-                }
-                stored[(size_t)b] = std::max(stored[(size_t)b], on_disk);
-                auto it = table.find(broker_id[(size_t)b]);
-                if (it != table.end()) capacity.push_back(it->second);
-                else if (every && total > 0) capacity.push_back(total);
-                else if (have_default_cap) capacity.push_back(default_cap);
-                else missing.push_back(broker_id[(size_t)b]);
-            }
-            if (!missing.empty()) {
-                std::string msg = "no capacity for brokers ";
-                for (size_t i = 0; i < missing.size() && i < 5; ++i) msg += (i ? ", " : "") + std::to_string(missing[i]);
-                if (missing.size() > 5) msg += " and " + std::to_string(missing.size() - 5) + " more";
-                throw std::runtime_error(msg + " (give them in --capacities, read totalBytes from a kafka-log-dirs --sizes document or set --default-capacity)");
-            }
-            for (uint64_t v : capacity) effective.push_back((uint64_t)((unsigned __int128)v * (unsigned)max_util / 100u));
-        }
-        int rc = kao_init(device);
-        if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
-        std::vector<int32_t> wave(std::max<size_t>(P, 1));
-        int32_t n_waves = 0, lb = 0;
-        int64_t hstats[8] = {0, 0, -1, 0, 0, -1, -1, -1};
-        if (headroom) {
-            rc = kao_plan_waves_headroom(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), size.data(), stored.data(), effective.data(), cap_bytes, k, seed,
-                                         wave.data(), &n_waves, &lb, hstats);
-            if (rc) throw std::runtime_error(std::string("kao_plan_waves_headroom: ") + kao_strerror(rc) + " " + kao_last_error());
-        } else if (sized) {
-            rc = kao_plan_waves_sized(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), size.data(), cap_bytes, k, seed, wave.data(), &n_waves, &lb);
-            if (rc) throw std::runtime_error(std::string("kao_plan_waves_sized: ") + kao_strerror(rc) + " " + kao_last_error());
-        } else {
-            rc = kao_plan_waves(nb, (int32_t)P, (int32_t)W, c.data(), t.data(), k, seed, wave.data(), &n_waves, &lb);
-            if (rc) throw std::runtime_error(std::string("kao_plan_waves: ") + kao_strerror(rc) + " " + kao_last_error());
-        }
-        std::vector<int> sizes((size_t)n_waves, 0);
-        for (int w = 0; w < n_waves; ++w) {
-            const std::string path = prefix + std::to_string(w + 1) + ".json";
-            std::ofstream f(path);
-            if (!f) throw std::runtime_error("cannot write " + path);
-            f << "{\"version\":1,\"partitions\":[";
-            for (size_t i = 0; i < P; ++i) {
-                if (wave[i] != w) continue;
-                f << (sizes[(size_t)w]++ ? ",\n" : "\n") << "    {\"topic\":" << quoted(cur[i].first.first) << ",\"partition\":" << cur[i].first.second << ",\"replicas\":[";
-                for (size_t j = 0; j < tgt[i]->size(); ++j) f << (j ? "," : "") << (*tgt[i])[j];
-                f << "]}";
-            }
-            f << "\n]}\n";
-            if (!f) throw std::runtime_error("cannot write " + path);
-        }
-        if (hstats[0] > 0) {   // the partitions that fit no wave, as a reassignment document of their own
-            const std::string path = prefix + "-stuck.json";
-            std::ofstream f(path);
-            if (!f) throw std::runtime_error("cannot write " + path);
-            f << "{\"version\":1,\"partitions\":[";
-            bool first = true;
-            for (size_t i = 0; i < P; ++i) {
-                if (wave[i] != -2) continue;
-                f << (first ? "\n" : ",\n") << "    {\"topic\":" << quoted(cur[i].first.first) << ",\"partition\":" << cur[i].first.second << ",\"replicas\":[";
-                first = false;
-                for (size_t j = 0; j < tgt[i]->size(); ++j) f << (j ? "," : "") << (*tgt[i])[j];
-                f << "]}";
-            }
-            f << "\n]}\n";
-            if (!f) throw std::runtime_error("cannot write " + path);
-        }
-        if (report) {
-            std::fprintf(stderr, "waves=%d lower_bound=%d optimal=%s partitions_per_wave=", n_waves, lb, n_waves == lb && hstats[0] == 0 ? "yes" : "no");
-            for (int w = 0; w < n_waves; ++w) std::fprintf(stderr, "%s%d", w ? "," : "", sizes[(size_t)w]);
-            if (sized) {   // bytes: the byte lower bound max_b ceil(sum_p min(t, C) / C) and each wave's busiest broker
-                std::map<std::pair<int, int>, uint64_t> load;
-                std::map<int, uint64_t> clamp;
-                for (size_t i = 0; i < P; ++i)
-                    for (auto &bn : traffic(&c[i * W], &t[i * W], W)) {
-                        const uint64_t tr = bn.second * size[i];   // below 2^62: kao_plan_waves_sized checked the totals
-                        if (wave[i] >= 0) load[{wave[i], bn.first}] += tr;   // a stuck partition (--headroom) is in no wave
-                        if (cap_bytes) clamp[bn.first] += std::min(tr, cap_bytes);
-                    }
-                uint64_t blb = 0;
-                for (auto &kv : clamp) blb = std::max(blb, kv.second / cap_bytes + (kv.second % cap_bytes != 0));
-                std::vector<uint64_t> peak((size_t)n_waves, 0);
-                for (auto &kv : load) peak[(size_t)kv.first.first] = std::max(peak[(size_t)kv.first.first], kv.second);
-                std::fprintf(stderr, " bytes_lower_bound=%llu max_broker_bytes_per_wave=", (unsigned long long)blb);
-                for (int w = 0; w < n_waves; ++w) std::fprintf(stderr, "%s%llu", w ? "," : "", (unsigned long long)peak[(size_t)w]);
-            }
-            if (headroom) {   // the fullest receiving broker of each wave in percent of its capacity: occ follows the waves
-                std::vector<uint64_t> occ = stored;
-                std::fprintf(stderr, " fullest_receiver_pct_per_wave=");
-                for (int w = 0; w < n_waves; ++w) {
-                    std::map<int, uint64_t> arr, dep;
-                    for (size_t i = 0; i < P; ++i) {
-                        if (wave[i] != w || size[i] == 0) continue;
-                        for (size_t j = 0; j < W; ++j) {
-                            const uint16_t tb = t[i * W + j], cb = c[i * W + j];
-                            if (tb != KAO_NONE && std::find(&c[i * W], &c[i * W] + W, tb) == &c[i * W] + W) arr[tb] += size[i];
-                            if (cb != KAO_NONE && std::find(&t[i * W], &t[i * W] + W, cb) == &t[i * W] + W) dep[cb] += size[i];
-                        }
-                    }
-                    unsigned long long ppm = 0;
-                    for (auto &kv : arr) {
-                        const uint64_t cap = capacity[(size_t)kv.first];
-                        const unsigned __int128 v = cap ? (unsigned __int128)(occ[(size_t)kv.first] + kv.second) * 1000000u / cap : 1000000u;
-                        ppm = std::max(ppm, (unsigned long long)v);
-                    }
-                    for (auto &kv : arr) occ[(size_t)kv.first] += kv.second;
-                    for (auto &kv : dep) occ[(size_t)kv.first] -= kv.second;
-                    std::fprintf(stderr, "%s%llu.%02llu", w ? "," : "", ppm / 10000, ppm / 100 % 100);
-                }
-                std::fprintf(stderr, " min_free=%lld min_free_wave=%lld min_free_broker=%d stuck=%lld stuck_bytes=%lld", (long long)hstats[5],
-                             (long long)(hstats[6] >= 0 ? hstats[6] + 1 : 0), hstats[7] >= 0 ? broker_id[(size_t)hstats[7]] : -1, (long long)hstats[0],
-                             (long long)hstats[1]);
-            }
-            std::fprintf(stderr, "\n");
-        }
-        kao_shutdown();
-        if (hstats[0] > 0) {
-            std::fprintf(stderr, "stuck: %lld partitions, %lld bytes\n", (long long)hstats[0], (long long)hstats[1]);
-            return 3;
-        }
-        return 0;
+        return run(o);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "kao-waves: %s\n", e.what());
         return 1;

@@ -22,6 +22,12 @@
 // (k = 0: no count cap); a partition above C thus goes alone.  The key's high word becomes (~code(max_b t_p(b))) << 16 |
 // ~min(maxdeg, 0xFFFF), so order 0 is first fit decreasing by traffic.  The rounds are unchanged: the argument above holds for
 // any fit test that depends on the loads a partition sees.
+//
+// Layout: the row walk (wave_each_added / wave_each_removed) that every kernel and host check of add(p) and rem(p) goes through;
+// the kernels of the plain and sized calls; the kernels of the headroom call; the host checks; then the host flow.  All three
+// calls share their front half (wave_front: buffers, uploads, k_wave_classify, k_wave_bound) and their tail (wave_tail: the one
+// scatter kernel, wave[] read back, the lower bound); each keeps its own round loop between the two, since the loops end on
+// different conditions.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +46,26 @@ constexpr int kWaveThreads = 256;
 constexpr int kWaveBatch = 32;               // rounds enqueued between two checks of the "anything left" flag
 constexpr size_t kWaveBudget = size_t(1) << 30;  // device bytes the per-order state may take; fewer orders when it would not fit
 enum { CTL_NMV = 0, CTL_CHANGED = 1, CTL_LB = 2, CTL_WCAP = 3, CTL_ERR = 4, CTL_N = 8 };
+
+// The row walk: f(broker) for every broker of row `of` that row `other` does not hold, in the slot order of `of`.
+template <class F>
+__host__ __device__ inline void wave_each_missing(const uint16_t *of, const uint16_t *other, int W, F f) {
+    for (int i = 0; i < W; ++i) {
+        const uint16_t b = of[i];
+        if (b == KAO_NONE) continue;
+        bool held = false;
+        for (int j = 0; j < W; ++j) held |= other[j] == b;
+        if (!held) f(b);
+    }
+}
+
+// add(p) = target \ current in target-slot order: the order fixes the participant order and the source's place in part[]
+template <class F>
+__host__ __device__ inline void wave_each_added(const uint16_t *cur, const uint16_t *tgt, int W, F f) { wave_each_missing(tgt, cur, W, f); }
+
+// rem(p) = current \ target in current-slot order
+template <class F>
+__host__ __device__ inline void wave_each_removed(const uint16_t *cur, const uint16_t *tgt, int W, F f) { wave_each_missing(cur, tgt, W, f); }
 
 __host__ __device__ inline uint32_t wave_mix32(uint32_t x) {  // murmur3 finaliser: a bijection of 32-bit words
     x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
@@ -97,12 +123,7 @@ __global__ void k_wave_classify(int32_t P, int32_t W, const uint16_t *__restrict
             changed |= c[i] != n[i];
         }
         if (changed) {
-            for (int i = 0; i < W; ++i) {
-                if (n[i] == KAO_NONE) continue;
-                bool held = false;
-                for (int j = 0; j < W; ++j) held |= c[j] == n[i];
-                if (!held) s[ns++] = n[i];
-            }
+            wave_each_added(c, n, W, [&](uint16_t b) { s[ns++] = b; });
             if (ns > 0 && c[0] != KAO_NONE) s[ns++] = c[0];
         }
         if (!changed) wave[p] = -1;
@@ -266,9 +287,11 @@ __global__ void k_wave_round(int32_t r, int32_t n_ord, int32_t n_mv, int32_t B, 
     wave_max_to(pending ? 1 : 0, &flags[(r + 1) % 3]);
 }
 
+// The winning order's waves by partition, for all three calls: -2 for a slot left without a wave (stuck, headroom only: the other
+// two calls place every slot or fail).
 __global__ void k_wave_scatter(int32_t n_mv, const int32_t *__restrict__ waveo, const int32_t *__restrict__ mv_idx, int32_t *__restrict__ wave) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_mv) wave[mv_idx[i]] = waveo[i];
+    if (i < n_mv) wave[mv_idx[i]] = waveo[i] < 0 ? -2 : waveo[i];
 }
 
 // ---- kao_plan_waves_headroom: waves as a sequence of states, each of which fits every disk ----
@@ -322,18 +345,10 @@ __global__ void k_head_dep0(int32_t P, int32_t W, const uint16_t *__restrict__ c
         changed |= c[i] != n[i];
     }
     if (!changed || size[p] == 0) return;
-    for (int i = 0; i < W; ++i) {   // any added broker: the partition moves data and leaves with its own wave
-        if (n[i] == KAO_NONE) continue;
-        bool held = false;
-        for (int j = 0; j < W; ++j) held |= c[j] == n[i];
-        if (!held) return;
-    }
-    for (int i = 0; i < W; ++i) {
-        if (c[i] == KAO_NONE) continue;
-        bool kept = false;
-        for (int j = 0; j < W; ++j) kept |= n[j] == c[i];
-        if (!kept) atomicAdd(&dep0[c[i]], (unsigned long long)size[p]);
-    }
+    bool adds = false;
+    wave_each_added(c, n, W, [&](uint16_t) { adds = true; });
+    if (adds) return;   // any added broker: the partition moves data and leaves with its own wave
+    wave_each_removed(c, n, W, [&](uint16_t b) { atomicAdd(&dep0[b], (unsigned long long)size[p]); });
 }
 
 // grid = (brokers / 256, orders): every order starts from occ = stored and wave 0's departures.
@@ -399,7 +414,8 @@ __global__ void k_head_round(int32_t r, int32_t n_ord, int32_t n_mv, int32_t B, 
                     if (j < n_added) st64(&arr[e], arr[e] + sz);
                 }
                 if (sz) {
-                    for (int c = 0; c < W; ++c) {   // rem(p) = current \ target
+                    // rem(p) = current \ target, written out: through wave_each_removed the compiler emits other code for this kernel
+                    for (int c = 0; c < W; ++c) {
                         const uint16_t cb = cur[(size_t)p * W + c];
                         if (cb == KAO_NONE) continue;
                         bool kept = false;
@@ -486,11 +502,6 @@ __global__ void k_head_tally(int32_t n_mv, const int32_t *__restrict__ waveo, He
     if (m != 0ull && __lane_id() == 0) atomicAdd(&ord[blockIdx.y].stuck, __popcll(m));
 }
 
-__global__ void k_head_scatter(int32_t n_mv, const int32_t *__restrict__ waveo, const int32_t *__restrict__ mv_idx, int32_t *__restrict__ wave) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_mv) wave[mv_idx[i]] = waveo[i] < 0 ? -2 : waveo[i];
-}
-
 // device buffers of one call, released on every return path (not CallBufs of kao_host.h: a call allocates up to 1 GiB, which must
 // not be parked in the arena pool)
 struct WaveBufs {
@@ -543,12 +554,7 @@ int validate_traffic(const char *fn, int32_t B, int32_t P, int32_t W, const uint
         const uint16_t *c = cur + p * W, *n = tgt + p * W;
         uint16_t add[KAO_MAX_RF];
         int na = 0;
-        for (int i = 0; i < W; ++i) {
-            if (n[i] == KAO_NONE) continue;
-            bool held = false;
-            for (int j = 0; j < W; ++j) held |= c[j] == n[i];
-            if (!held) add[na++] = n[i];
-        }
+        wave_each_added(c, n, W, [&](uint16_t b) { add[na++] = b; });
         if (na == 0) continue;   // unchanged, or changed without moving data
         uint64_t src = 0;
         bool bad = __builtin_mul_overflow(size[p], (uint64_t)na, &src);
@@ -557,106 +563,6 @@ int validate_traffic(const char *fn, int32_t B, int32_t P, int32_t W, const uint
         if (bad)
             return fail(KAO_ERR_INVALID, std::string(fn) + ": partition " + std::to_string(p) + ": a broker's traffic reaches 2^62 bytes");
     }
-    return KAO_OK;
-}
-
-// Both planners after validation.  Sized: size != nullptr, C = max_bytes_per_broker (0 = no byte cap), k = 0 = no count cap.
-template <bool Sized>
-int plan_waves(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *current, const uint16_t *target, const uint64_t *size,
-               uint64_t C, int32_t k, uint64_t seed, int32_t *wave, int32_t *n_waves, int32_t *lower_bound) {
-    int rc = require_init();
-    if (rc) return rc;
-    *n_waves = 0;
-    *lower_bound = 0;
-    if (P == 0) return KAO_OK;
-
-    WaveBufs m;
-    HIP_TRY(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-    hipStream_t st = m.stream;
-    uint16_t *d_cur, *d_tgt, *d_part;
-    uint8_t *d_npart;
-    int32_t *d_wave, *d_mv, *d_deg, *d_ctl;
-    uint32_t *d_khi;
-    uint64_t *d_size = nullptr, *d_traf = nullptr;
-    unsigned long long *d_tot = nullptr, *d_clamp = nullptr;
-    const size_t PW = (size_t)P * W;
-    if ((rc = m.alloc(&d_cur, PW)) || (rc = m.alloc(&d_tgt, PW)) || (rc = m.alloc(&d_part, (size_t)P * kWavePart)) ||
-        (rc = m.alloc(&d_npart, (size_t)P)) || (rc = m.alloc(&d_wave, (size_t)P)) || (rc = m.alloc(&d_mv, (size_t)P)) ||
-        (rc = m.alloc(&d_deg, (size_t)B)) || (rc = m.alloc(&d_khi, (size_t)P)) || (rc = m.alloc(&d_ctl, CTL_N)))
-        return rc;
-    if (Sized && ((rc = m.alloc(&d_size, (size_t)P)) || (rc = m.alloc(&d_traf, (size_t)P * kWavePart)) ||
-                  (rc = m.alloc(&d_tot, (size_t)B)) || (rc = m.alloc(&d_clamp, (size_t)B))))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(d_cur, current, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_tgt, target, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_deg, 0, (size_t)B * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(d_ctl, 0, CTL_N * sizeof(int32_t), st));
-    if (Sized) {
-        HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_tot, 0, (size_t)B * sizeof(unsigned long long), st));
-        HIP_TRY(hipMemsetAsync(d_clamp, 0, (size_t)B * sizeof(unsigned long long), st));
-    }
-    const unsigned pblocks = (unsigned)(((size_t)P + kWaveThreads - 1) / kWaveThreads);
-    k_wave_classify<Sized><<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_wave, d_part, d_npart, d_mv, d_deg, d_ctl, d_size, C,
-                                                             d_traf, d_tot, d_clamp);
-    HIP_TRY(hipGetLastError());
-    int32_t ctl[CTL_N];
-    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int32_t n_mv = ctl[CTL_NMV];
-    int32_t best_waves = ctl[CTL_CHANGED] ? 1 : 0;  // metadata-only partitions share wave 0
-    if (n_mv > 0) {
-        const unsigned mblocks = (unsigned)((n_mv + kWaveThreads - 1) / kWaveThreads);
-        k_wave_bound<Sized><<<mblocks, kWaveThreads, 0, st>>>(n_mv, k, d_part, d_npart, d_deg, d_khi, d_ctl, C, d_traf, d_tot, d_clamp);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const int32_t wcap = ctl[CTL_WCAP];
-        // per-order state: loads[B][wcap] (sized: only with a count cap), bytes[B][wcap] (sized), waveo[n_mv], three minkey rows [B]
-        const bool counts = !Sized || k > 0;
-        const size_t per_order = (size_t)B * wcap * ((counts ? 4 : 0) + (Sized ? 8 : 0)) + (size_t)n_mv * 4 + (size_t)3 * B * 8;
-        const int n_ord = (int)std::max<size_t>(1, std::min<size_t>(kWaveOrders, kWaveBudget / per_order));
-        int32_t *d_loads = nullptr, *d_waveo, *d_nw, *d_flags;
-        uint64_t *d_bytes = nullptr;
-        unsigned long long *d_mk;
-        if ((counts && (rc = m.alloc(&d_loads, (size_t)n_ord * B * wcap))) || (rc = m.alloc(&d_waveo, (size_t)n_ord * n_mv)) ||
-            (rc = m.alloc(&d_mk, (size_t)3 * n_ord * B)) || (rc = m.alloc(&d_nw, (size_t)n_ord)) || (rc = m.alloc(&d_flags, 3)) ||
-            (Sized && (rc = m.alloc(&d_bytes, (size_t)n_ord * B * wcap))))
-            return rc;
-        if (counts) HIP_TRY(hipMemsetAsync(d_loads, 0, (size_t)n_ord * B * wcap * sizeof(int32_t), st));
-        if (Sized) HIP_TRY(hipMemsetAsync(d_bytes, 0, (size_t)n_ord * B * wcap * sizeof(uint64_t), st));
-        HIP_TRY(hipMemsetAsync(d_waveo, 0xFF, (size_t)n_ord * n_mv * sizeof(int32_t), st));
-        HIP_TRY(hipMemsetAsync(d_mk, 0xFF, (size_t)2 * n_ord * B * sizeof(unsigned long long), st));  // rows of rounds 0 and 1
-        HIP_TRY(hipMemsetAsync(d_nw, 0, (size_t)n_ord * sizeof(int32_t), st));
-        HIP_TRY(hipMemsetAsync(d_flags, 0, 3 * sizeof(int32_t), st));
-        const dim3 grid(mblocks, (unsigned)n_ord);
-        k_wave_seed<<<grid, kWaveThreads, 0, st>>>(n_mv, B, seed, d_part, d_npart, d_mv, d_khi, d_mk);
-        HIP_TRY(hipGetLastError());
-        // every round places at least the lowest key of each order: n_mv rounds always suffice
-        int32_t r = 0, left = 1;
-        while (left) {
-            if (r > n_mv) return fail(KAO_ERR_HIP, std::string(fn) + ": rounds did not finish");
-            for (int i = 0; i < kWaveBatch; ++i, ++r)
-                k_wave_round<Sized><<<grid, kWaveThreads, 0, st>>>(r, n_ord, n_mv, B, wcap, k, seed, d_part, d_npart, d_mv, d_khi, d_mk, d_loads,
-                                                                   d_waveo, d_nw, d_flags, d_ctl, C, d_traf, d_bytes);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&left, d_flags + r % 3, sizeof left, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            if (ctl[CTL_ERR]) return fail(KAO_ERR_HIP, std::string(fn) + ": a partition found no wave below the cap");
-        }
-        std::vector<int32_t> nw((size_t)n_ord);
-        HIP_TRY(hipMemcpyAsync(nw.data(), d_nw, nw.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const int best = (int)(std::min_element(nw.begin(), nw.end()) - nw.begin());  // first minimum: the lowest order
-        best_waves = nw[(size_t)best];
-        k_wave_scatter<<<mblocks, kWaveThreads, 0, st>>>(n_mv, d_waveo + (size_t)best * n_mv, d_mv, d_wave);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(wave, d_wave, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_waves = best_waves;
-    *lower_bound = n_mv > 0 ? ctl[CTL_LB] : best_waves;
     return KAO_OK;
 }
 
@@ -671,20 +577,264 @@ int validate_stored(const char *fn, int32_t B, int32_t P, int32_t W, const uint1
     std::vector<uint64_t> left(stored, stored + B);
     for (int64_t p = 0; p < P; ++p) {
         const uint16_t *c = cur + p * W, *n = tgt + p * W;
-        for (int i = 0; i < W; ++i) {
-            if (c[i] == KAO_NONE) continue;
-            bool kept = false;
-            for (int j = 0; j < W; ++j) kept |= n[j] == c[i];
-            if (kept) continue;
-            if (left[c[i]] < size[p])
-                return fail(KAO_ERR_INVALID, f + ": stored[" + std::to_string(c[i]) + "] is below the bytes of the partitions that leave the broker (partition " +
-                                                 std::to_string(p) + ")");
-            left[c[i]] -= size[p];
-        }
+        int short_of = -1;   // the first broker of rem(p) that holds less than leaves it
+        wave_each_removed(c, n, W, [&](uint16_t b) {
+            if (short_of >= 0) return;
+            if (left[b] < size[p]) short_of = b;
+            else left[b] -= size[p];
+        });
+        if (short_of >= 0)
+            return fail(KAO_ERR_INVALID, f + ": stored[" + std::to_string(short_of) + "] is below the bytes of the partitions that leave the broker (partition " +
+                                             std::to_string(p) + ")");
     }
     return KAO_OK;
 }
 
+// The number of priority orders whose state (per_order bytes each) fits the budget.
+int wave_orders(size_t per_order) { return (int)std::max<size_t>(1, std::min<size_t>(kWaveOrders, kWaveBudget / per_order)); }
+
+// What every call holds once its partitions are classified and bounded: the stream and the buffers (released with it), the
+// device pointers the later kernels take, the grids, and the control words as k_wave_bound left them.
+struct WaveFront {
+    WaveBufs m;
+    hipStream_t st = nullptr;
+    uint16_t *cur, *tgt, *part;
+    uint8_t *npart;
+    int32_t *wave, *mv, *deg, *d_ctl;
+    uint32_t *khi;
+    uint64_t *size = nullptr, *traf = nullptr;               // sized calls only
+    unsigned long long *tot = nullptr, *clamp = nullptr;     // sized calls only
+    int32_t n_mv = 0;                                        // moving partitions (slots)
+    unsigned pblocks = 0, mblocks = 0;                       // workgroups over the partitions / over the slots
+    int32_t ctl[CTL_N];
+};
+
+// The front half of every call: buffers, uploads, k_wave_classify and, when a partition moves, k_wave_bound.  Sized: size != nullptr,
+// C = max_bytes_per_broker (0 = no byte cap), k = 0 = no count cap.
+template <bool Sized>
+int wave_front(WaveFront &f, int32_t B, int32_t P, int32_t W, const uint16_t *current, const uint16_t *target, const uint64_t *size, uint64_t C,
+               int32_t k) {
+    WaveBufs &m = f.m;
+    HIP_TRY(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
+    const hipStream_t st = f.st = m.stream;
+    int rc;
+    const size_t PW = (size_t)P * W;
+    if ((rc = m.alloc(&f.cur, PW)) || (rc = m.alloc(&f.tgt, PW)) || (rc = m.alloc(&f.part, (size_t)P * kWavePart)) ||
+        (rc = m.alloc(&f.npart, (size_t)P)) || (rc = m.alloc(&f.wave, (size_t)P)) || (rc = m.alloc(&f.mv, (size_t)P)) ||
+        (rc = m.alloc(&f.deg, (size_t)B)) || (rc = m.alloc(&f.khi, (size_t)P)) || (rc = m.alloc(&f.d_ctl, CTL_N)))
+        return rc;
+    if (Sized && ((rc = m.alloc(&f.size, (size_t)P)) || (rc = m.alloc(&f.traf, (size_t)P * kWavePart)) ||
+                  (rc = m.alloc(&f.tot, (size_t)B)) || (rc = m.alloc(&f.clamp, (size_t)B))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(f.cur, current, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(f.tgt, target, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(f.deg, 0, (size_t)B * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(f.d_ctl, 0, CTL_N * sizeof(int32_t), st));
+    if (Sized) {
+        HIP_TRY(hipMemcpyAsync(f.size, size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(f.tot, 0, (size_t)B * sizeof(unsigned long long), st));
+        HIP_TRY(hipMemsetAsync(f.clamp, 0, (size_t)B * sizeof(unsigned long long), st));
+    }
+    f.pblocks = (unsigned)(((size_t)P + kWaveThreads - 1) / kWaveThreads);
+    k_wave_classify<Sized><<<f.pblocks, kWaveThreads, 0, st>>>(P, W, f.cur, f.tgt, f.wave, f.part, f.npart, f.mv, f.deg, f.d_ctl, f.size, C, f.traf,
+                                                               f.tot, f.clamp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(f.ctl, f.d_ctl, sizeof f.ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    f.n_mv = f.ctl[CTL_NMV];
+    if (f.n_mv == 0) return KAO_OK;
+    f.mblocks = (unsigned)((f.n_mv + kWaveThreads - 1) / kWaveThreads);
+    k_wave_bound<Sized><<<f.mblocks, kWaveThreads, 0, st>>>(f.n_mv, k, f.part, f.npart, f.deg, f.khi, f.d_ctl, C, f.traf, f.tot, f.clamp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(f.ctl, f.d_ctl, sizeof f.ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return KAO_OK;
+}
+
+// The tail of every call: the winning order's waves (waveo, null when nothing moves) into wave[], wave[] read back, the results.
+int wave_tail(WaveFront &f, int32_t P, const int32_t *waveo, int32_t best_waves, int32_t *wave, int32_t *n_waves, int32_t *lower_bound) {
+    if (f.n_mv > 0) {
+        k_wave_scatter<<<f.mblocks, kWaveThreads, 0, f.st>>>(f.n_mv, waveo, f.mv, f.wave);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(wave, f.wave, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, f.st));
+    HIP_TRY(hipStreamSynchronize(f.st));
+    *n_waves = best_waves;
+    *lower_bound = f.n_mv > 0 ? f.ctl[CTL_LB] : best_waves;
+    return KAO_OK;
+}
+
+// The plain and the sized call after validation.
+template <bool Sized>
+int plan_waves(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *current, const uint16_t *target, const uint64_t *size,
+               uint64_t C, int32_t k, uint64_t seed, int32_t *wave, int32_t *n_waves, int32_t *lower_bound) {
+    int rc = require_init();
+    if (rc) return rc;
+    *n_waves = 0;
+    *lower_bound = 0;
+    if (P == 0) return KAO_OK;
+    WaveFront f;
+    if ((rc = wave_front<Sized>(f, B, P, W, current, target, size, C, k))) return rc;
+    if (f.n_mv == 0) return wave_tail(f, P, nullptr, f.ctl[CTL_CHANGED] ? 1 : 0, wave, n_waves, lower_bound);  // metadata-only partitions share wave 0
+    const hipStream_t st = f.st;
+    const int32_t n_mv = f.n_mv, wcap = f.ctl[CTL_WCAP];
+    // per-order state: loads[B][wcap] (sized: only with a count cap), bytes[B][wcap] (sized), waveo[n_mv], three minkey rows [B]
+    const bool counts = !Sized || k > 0;
+    const size_t per_order = (size_t)B * wcap * ((counts ? 4 : 0) + (Sized ? 8 : 0)) + (size_t)n_mv * 4 + (size_t)3 * B * 8;
+    const int n_ord = wave_orders(per_order);
+    int32_t *d_loads = nullptr, *d_waveo, *d_nw, *d_flags;
+    uint64_t *d_bytes = nullptr;
+    unsigned long long *d_mk;
+    if ((counts && (rc = f.m.alloc(&d_loads, (size_t)n_ord * B * wcap))) || (rc = f.m.alloc(&d_waveo, (size_t)n_ord * n_mv)) ||
+        (rc = f.m.alloc(&d_mk, (size_t)3 * n_ord * B)) || (rc = f.m.alloc(&d_nw, (size_t)n_ord)) || (rc = f.m.alloc(&d_flags, 3)) ||
+        (Sized && (rc = f.m.alloc(&d_bytes, (size_t)n_ord * B * wcap))))
+        return rc;
+    if (counts) HIP_TRY(hipMemsetAsync(d_loads, 0, (size_t)n_ord * B * wcap * sizeof(int32_t), st));
+    if (Sized) HIP_TRY(hipMemsetAsync(d_bytes, 0, (size_t)n_ord * B * wcap * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(d_waveo, 0xFF, (size_t)n_ord * n_mv * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(d_mk, 0xFF, (size_t)2 * n_ord * B * sizeof(unsigned long long), st));  // rows of rounds 0 and 1
+    HIP_TRY(hipMemsetAsync(d_nw, 0, (size_t)n_ord * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(d_flags, 0, 3 * sizeof(int32_t), st));
+    const dim3 grid(f.mblocks, (unsigned)n_ord);
+    k_wave_seed<<<grid, kWaveThreads, 0, st>>>(n_mv, B, seed, f.part, f.npart, f.mv, f.khi, d_mk);
+    HIP_TRY(hipGetLastError());
+    // every round places at least the lowest key of each order: n_mv rounds always suffice
+    int32_t r = 0, left = 1;
+    while (left) {
+        if (r > n_mv) return fail(KAO_ERR_HIP, std::string(fn) + ": rounds did not finish");
+        for (int i = 0; i < kWaveBatch; ++i, ++r)
+            k_wave_round<Sized><<<grid, kWaveThreads, 0, st>>>(r, n_ord, n_mv, B, wcap, k, seed, f.part, f.npart, f.mv, f.khi, d_mk, d_loads, d_waveo,
+                                                               d_nw, d_flags, f.d_ctl, C, f.traf, d_bytes);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&left, d_flags + r % 3, sizeof left, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(f.ctl, f.d_ctl, sizeof f.ctl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (f.ctl[CTL_ERR]) return fail(KAO_ERR_HIP, std::string(fn) + ": a partition found no wave below the cap");
+    }
+    std::vector<int32_t> nw((size_t)n_ord);
+    HIP_TRY(hipMemcpyAsync(nw.data(), d_nw, nw.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int best = (int)(std::min_element(nw.begin(), nw.end()) - nw.begin());  // first minimum: the lowest order
+    return wave_tail(f, P, d_waveo + (size_t)best * n_mv, nw[(size_t)best], wave, n_waves, lower_bound);
+}
+
+// The state of the headroom call's orders (the layout is described above k_head_round) and the host's copy of their words.
+struct HeadState {
+    int n_ord = 0;
+    uint64_t *capacity, *occ, *arr, *dep, *byt;
+    int32_t *cnt, *waveo, *skipw, *n_done;
+    unsigned long long *mk;
+    HeadOrder *d_ord;
+    std::vector<HeadOrder> ord;
+};
+
+// Uploads stored and capacity, allocates and clears the per-order state, and starts every order from occ = stored with the
+// departures of the metadata-only partitions (k_head_dep0) waiting in wave 0.
+int head_start(WaveFront &f, HeadState &h, int32_t B, int32_t P, int32_t W, const uint64_t *stored, const uint64_t *capacity) {
+    const hipStream_t st = f.st;
+    WaveBufs &m = f.m;
+    uint64_t *d_stored;
+    unsigned long long *d_dep0;
+    int rc;
+    if ((rc = m.alloc(&d_dep0, (size_t)B)) || (rc = m.alloc(&d_stored, (size_t)B)) || (rc = m.alloc(&h.capacity, (size_t)B))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_stored, stored, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h.capacity, capacity, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_dep0, 0, (size_t)B * sizeof(unsigned long long), st));
+    k_head_dep0<<<f.pblocks, kWaveThreads, 0, st>>>(P, W, f.cur, f.tgt, f.size, d_dep0);
+    HIP_TRY(hipGetLastError());
+    // per-order state: occ, arr, dep, byt (8 bytes) and cnt (4) per broker, three minkey rows, waveo and skipw per slot
+    const size_t per_order = (size_t)B * (4 * 8 + 4 + 3 * 8) + (size_t)f.n_mv * 8;
+    h.n_ord = wave_orders(per_order);
+    const size_t OB = (size_t)h.n_ord * B, OS = (size_t)h.n_ord * f.n_mv;
+    if ((rc = m.alloc(&h.occ, OB)) || (rc = m.alloc(&h.arr, OB)) || (rc = m.alloc(&h.dep, OB)) || (rc = m.alloc(&h.byt, OB)) ||
+        (rc = m.alloc(&h.cnt, OB)) || (rc = m.alloc(&h.mk, 3 * OB)) || (rc = m.alloc(&h.waveo, OS)) || (rc = m.alloc(&h.skipw, OS)) ||
+        (rc = m.alloc(&h.d_ord, (size_t)h.n_ord)) || (rc = m.alloc(&h.n_done, 1)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(h.arr, 0, OB * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(h.byt, 0, OB * sizeof(uint64_t), st));
+    HIP_TRY(hipMemsetAsync(h.cnt, 0, OB * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(h.mk, 0xFF, 2 * OB * sizeof(unsigned long long), st));   // rows of rounds 0 and 1
+    HIP_TRY(hipMemsetAsync(h.waveo, 0xFF, OS * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(h.skipw, 0xFF, OS * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(h.n_done, 0, sizeof(int32_t), st));
+    h.ord.assign((size_t)h.n_ord, HeadOrder{0, 0, 0, 0, {0, 0, 0}, -1, -1, 0, ~0ull});
+    HIP_TRY(hipMemcpyAsync(h.d_ord, h.ord.data(), h.ord.size() * sizeof(HeadOrder), hipMemcpyHostToDevice, st));
+    k_head_init<<<dim3((unsigned)((B + kWaveThreads - 1) / kWaveThreads), (unsigned)h.n_ord), kWaveThreads, 0, st>>>(B, d_stored, d_dep0, h.occ, h.dep);
+    HIP_TRY(hipGetLastError());
+    return KAO_OK;
+}
+
+// Rounds and closes until every order has seen its idle wave, then the tally of the stuck slots; h.ord is read back.  *rounds =
+// the round launches.
+int head_rounds(const char *fn, WaveFront &f, HeadState &h, int32_t B, int32_t W, int32_t k, uint64_t C, uint64_t seed, int64_t *rounds) {
+    const hipStream_t st = f.st;
+    const int32_t n_mv = f.n_mv;
+    const dim3 grid(f.mblocks, (unsigned)h.n_ord);
+    // an order has at most n_mv + 2 waves (every wave but the first and the last takes a partition), a wave at most n_mv + 2
+    // rounds (every round but its first and its last decides a slot)
+    const int64_t max_rounds = ((int64_t)n_mv + 2) * ((int64_t)n_mv + 2);
+    int64_t r = 0;
+    int32_t n_done = 0;
+    while (n_done < h.n_ord) {
+        if (r > max_rounds) return fail(KAO_ERR_HIP, std::string(fn) + ": rounds did not finish");
+        for (int i = 0; i < kWaveBatch; ++i, ++r) {
+            const int32_t r3 = (int32_t)(r % 3);   // the kernels use the round number modulo 3 only
+            k_head_round<<<grid, kWaveThreads, 0, st>>>(r3, h.n_ord, n_mv, B, W, k, C, seed, f.cur, f.tgt, f.size, h.capacity, f.part, f.npart, f.mv,
+                                                        f.khi, f.traf, h.mk, h.occ, h.arr, h.dep, h.byt, h.cnt, h.waveo, h.skipw, h.d_ord);
+            k_head_close<<<(unsigned)h.n_ord, kWaveThreads, 0, st>>>(r3, B, h.capacity, h.occ, h.arr, h.dep, h.byt, h.cnt, h.d_ord, h.n_done);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&n_done, h.n_done, sizeof n_done, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    k_head_tally<<<grid, kWaveThreads, 0, st>>>(n_mv, h.waveo, h.d_ord);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h.ord.data(), h.d_ord, h.ord.size() * sizeof(HeadOrder), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *rounds = r;
+    return KAO_OK;
+}
+
+// The winning order: fewest stuck, then fewest waves, then the lowest order.  Its words go into st8[0] and st8[2..7].
+int head_best(const HeadState &h, int64_t rounds, int64_t *st8) {
+    int best = 0;
+    for (int o = 1; o < h.n_ord; ++o)
+        if (h.ord[(size_t)o].stuck < h.ord[(size_t)best].stuck ||
+            (h.ord[(size_t)o].stuck == h.ord[(size_t)best].stuck && h.ord[(size_t)o].n_waves < h.ord[(size_t)best].n_waves))
+            best = o;
+    const HeadOrder &w = h.ord[(size_t)best];
+    st8[0] = w.stuck;
+    st8[2] = best;
+    st8[3] = h.n_ord;
+    st8[4] = rounds;
+    if (w.mf_broker >= 0) {
+        st8[5] = (int64_t)std::min<unsigned long long>(w.mf, (unsigned long long)INT64_MAX);
+        st8[6] = w.mf_wave;
+        st8[7] = w.mf_broker;
+    }
+    return best;
+}
+
+// The host pass over wave[]: the bytes of the stuck partitions (saturating), and whether wave 0 holds a metadata-only partition.
+bool head_stuck_bytes_and_meta(int32_t P, int32_t W, const uint16_t *current, const uint16_t *target, const uint64_t *size, const int32_t *wave,
+                               int64_t *stuck_bytes) {
+    auto n_added = [&](int64_t p) {
+        int na = 0;
+        wave_each_added(current + p * W, target + p * W, W, [&](uint16_t) { ++na; });
+        return na;
+    };
+    bool meta = false;   // metadata-only partitions share wave 0
+    for (int64_t p = 0; p < P; ++p) {
+        if (wave[p] == -2) {   // stuck bytes: one copy per added broker, each product below 2^62 (part of a broker's checked traffic)
+            if (__builtin_add_overflow(*stuck_bytes, (int64_t)((uint64_t)n_added(p) * size[p]), stuck_bytes)) *stuck_bytes = INT64_MAX;
+        } else if (wave[p] == 0 && !meta) {
+            meta = n_added(p) == 0;
+        }
+    }
+    return meta;
+}
+
+// The headroom call after validation.
 int plan_headroom(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_t *current, const uint16_t *target, const uint64_t *size,
                   const uint64_t *stored, const uint64_t *capacity, uint64_t C, int32_t k, uint64_t seed, int32_t *wave, int32_t *n_waves,
                   int32_t *lower_bound, int64_t *stats) {
@@ -697,137 +847,21 @@ int plan_headroom(const char *fn, int32_t B, int32_t P, int32_t W, const uint16_
         if (stats) std::copy(st8, st8 + 8, stats);
         return KAO_OK;
     }
-    WaveBufs m;
-    HIP_TRY(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-    hipStream_t st = m.stream;
-    uint16_t *d_cur, *d_tgt, *d_part;
-    uint8_t *d_npart;
-    int32_t *d_wave, *d_mv, *d_deg, *d_ctl;
-    uint32_t *d_khi;
-    uint64_t *d_size, *d_traf, *d_stored, *d_capacity;
-    unsigned long long *d_tot, *d_clamp, *d_dep0;
-    const size_t PW = (size_t)P * W;
-    if ((rc = m.alloc(&d_cur, PW)) || (rc = m.alloc(&d_tgt, PW)) || (rc = m.alloc(&d_part, (size_t)P * kWavePart)) ||
-        (rc = m.alloc(&d_npart, (size_t)P)) || (rc = m.alloc(&d_wave, (size_t)P)) || (rc = m.alloc(&d_mv, (size_t)P)) ||
-        (rc = m.alloc(&d_deg, (size_t)B)) || (rc = m.alloc(&d_khi, (size_t)P)) || (rc = m.alloc(&d_ctl, CTL_N)) ||
-        (rc = m.alloc(&d_size, (size_t)P)) || (rc = m.alloc(&d_traf, (size_t)P * kWavePart)) || (rc = m.alloc(&d_tot, (size_t)B)) ||
-        (rc = m.alloc(&d_clamp, (size_t)B)) || (rc = m.alloc(&d_dep0, (size_t)B)) || (rc = m.alloc(&d_stored, (size_t)B)) ||
-        (rc = m.alloc(&d_capacity, (size_t)B)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(d_cur, current, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_tgt, target, PW * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_size, size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_stored, stored, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_capacity, capacity, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_deg, 0, (size_t)B * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(d_ctl, 0, CTL_N * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(d_tot, 0, (size_t)B * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(d_clamp, 0, (size_t)B * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(d_dep0, 0, (size_t)B * sizeof(unsigned long long), st));
-    const unsigned pblocks = (unsigned)(((size_t)P + kWaveThreads - 1) / kWaveThreads);
-    k_wave_classify<true><<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_wave, d_part, d_npart, d_mv, d_deg, d_ctl, d_size, C, d_traf,
-                                                            d_tot, d_clamp);
-    HIP_TRY(hipGetLastError());
-    int32_t ctl[CTL_N];
-    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int32_t n_mv = ctl[CTL_NMV];
+    WaveFront f;
+    if ((rc = wave_front<true>(f, B, P, W, current, target, size, C, k))) return rc;
+    HeadState h;
     int32_t best_waves = 0;
-    if (n_mv > 0) {
-        const unsigned mblocks = (unsigned)((n_mv + kWaveThreads - 1) / kWaveThreads);
-        k_wave_bound<true><<<mblocks, kWaveThreads, 0, st>>>(n_mv, k, d_part, d_npart, d_deg, d_khi, d_ctl, C, d_traf, d_tot, d_clamp);
-        HIP_TRY(hipGetLastError());
-        k_head_dep0<<<pblocks, kWaveThreads, 0, st>>>(P, W, d_cur, d_tgt, d_size, d_dep0);
-        HIP_TRY(hipGetLastError());
-        // per-order state: occ, arr, dep, byt (8 bytes) and cnt (4) per broker, three minkey rows, waveo and skipw per slot
-        const size_t per_order = (size_t)B * (4 * 8 + 4 + 3 * 8) + (size_t)n_mv * 8;
-        const int n_ord = (int)std::max<size_t>(1, std::min<size_t>(kWaveOrders, kWaveBudget / per_order));
-        const size_t OB = (size_t)n_ord * B, OS = (size_t)n_ord * n_mv;
-        uint64_t *d_occ, *d_arr, *d_dep, *d_byt;
-        int32_t *d_cnt, *d_waveo, *d_skipw, *d_ndone;
-        unsigned long long *d_mk;
-        HeadOrder *d_ord;
-        if ((rc = m.alloc(&d_occ, OB)) || (rc = m.alloc(&d_arr, OB)) || (rc = m.alloc(&d_dep, OB)) || (rc = m.alloc(&d_byt, OB)) ||
-            (rc = m.alloc(&d_cnt, OB)) || (rc = m.alloc(&d_mk, 3 * OB)) || (rc = m.alloc(&d_waveo, OS)) || (rc = m.alloc(&d_skipw, OS)) ||
-            (rc = m.alloc(&d_ord, (size_t)n_ord)) || (rc = m.alloc(&d_ndone, 1)))
-            return rc;
-        HIP_TRY(hipMemsetAsync(d_arr, 0, OB * sizeof(uint64_t), st));
-        HIP_TRY(hipMemsetAsync(d_byt, 0, OB * sizeof(uint64_t), st));
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, OB * sizeof(int32_t), st));
-        HIP_TRY(hipMemsetAsync(d_mk, 0xFF, 2 * OB * sizeof(unsigned long long), st));   // rows of rounds 0 and 1
-        HIP_TRY(hipMemsetAsync(d_waveo, 0xFF, OS * sizeof(int32_t), st));
-        HIP_TRY(hipMemsetAsync(d_skipw, 0xFF, OS * sizeof(int32_t), st));
-        HIP_TRY(hipMemsetAsync(d_ndone, 0, sizeof(int32_t), st));
-        std::vector<HeadOrder> ord((size_t)n_ord);
-        for (HeadOrder &h : ord) h = HeadOrder{0, 0, 0, 0, {0, 0, 0}, -1, -1, 0, ~0ull};
-        HIP_TRY(hipMemcpyAsync(d_ord, ord.data(), ord.size() * sizeof(HeadOrder), hipMemcpyHostToDevice, st));
-        k_head_init<<<dim3((unsigned)((B + kWaveThreads - 1) / kWaveThreads), (unsigned)n_ord), kWaveThreads, 0, st>>>(B, d_stored, d_dep0, d_occ, d_dep);
-        HIP_TRY(hipGetLastError());
-        const dim3 grid(mblocks, (unsigned)n_ord);
-        // an order has at most n_mv + 2 waves (every wave but the first and the last takes a partition), a wave at most n_mv + 2
-        // rounds (every round but its first and its last decides a slot)
-        const int64_t max_rounds = ((int64_t)n_mv + 2) * ((int64_t)n_mv + 2);
-        int64_t r = 0;
-        int32_t n_done = 0;
-        while (n_done < n_ord) {
-            if (r > max_rounds) return fail(KAO_ERR_HIP, std::string(fn) + ": rounds did not finish");
-            for (int i = 0; i < kWaveBatch; ++i, ++r) {
-                const int32_t r3 = (int32_t)(r % 3);   // the kernels use the round number modulo 3 only
-                k_head_round<<<grid, kWaveThreads, 0, st>>>(r3, n_ord, n_mv, B, W, k, C, seed, d_cur, d_tgt, d_size, d_capacity, d_part, d_npart,
-                                                            d_mv, d_khi, d_traf, d_mk, d_occ, d_arr, d_dep, d_byt, d_cnt, d_waveo, d_skipw, d_ord);
-                k_head_close<<<(unsigned)n_ord, kWaveThreads, 0, st>>>(r3, B, d_capacity, d_occ, d_arr, d_dep, d_byt, d_cnt, d_ord, d_ndone);
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&n_done, d_ndone, sizeof n_done, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        k_head_tally<<<grid, kWaveThreads, 0, st>>>(n_mv, d_waveo, d_ord);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(ord.data(), d_ord, ord.size() * sizeof(HeadOrder), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        int best = 0;   // fewest stuck, then fewest waves, then the lowest order
-        for (int o = 1; o < n_ord; ++o)
-            if (ord[(size_t)o].stuck < ord[(size_t)best].stuck ||
-                (ord[(size_t)o].stuck == ord[(size_t)best].stuck && ord[(size_t)o].n_waves < ord[(size_t)best].n_waves))
-                best = o;
-        const HeadOrder &h = ord[(size_t)best];
-        best_waves = h.n_waves;
-        st8[0] = h.stuck;
-        st8[2] = best;
-        st8[3] = n_ord;
-        st8[4] = r;
-        if (h.mf_broker >= 0) {
-            st8[5] = (int64_t)std::min<unsigned long long>(h.mf, (unsigned long long)INT64_MAX);
-            st8[6] = h.mf_wave;
-            st8[7] = h.mf_broker;
-        }
-        k_head_scatter<<<mblocks, kWaveThreads, 0, st>>>(n_mv, d_waveo + (size_t)best * n_mv, d_mv, d_wave);
-        HIP_TRY(hipGetLastError());
+    const int32_t *best_waveo = nullptr;
+    if (f.n_mv > 0) {
+        int64_t rounds = 0;
+        if ((rc = head_start(f, h, B, P, W, stored, capacity)) || (rc = head_rounds(fn, f, h, B, W, k, C, seed, &rounds))) return rc;
+        const int best = head_best(h, rounds, st8);
+        best_waves = h.ord[(size_t)best].n_waves;
+        best_waveo = h.waveo + (size_t)best * f.n_mv;
     }
-    HIP_TRY(hipMemcpyAsync(wave, d_wave, (size_t)P * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    auto n_added = [&](int64_t p) {
-        int na = 0;
-        for (int i = 0; i < W; ++i) {
-            const uint16_t b = target[p * W + i];
-            if (b == KAO_NONE) continue;
-            bool held = false;
-            for (int j = 0; j < W; ++j) held |= current[p * W + j] == b;
-            na += !held;
-        }
-        return na;
-    };
-    bool meta = false;   // metadata-only partitions share wave 0
-    for (int64_t p = 0; p < P; ++p) {
-        if (wave[p] == -2) {   // stuck bytes: one copy per added broker, each product below 2^62 (part of a broker's checked traffic)
-            if (__builtin_add_overflow(st8[1], (int64_t)((uint64_t)n_added(p) * size[p]), &st8[1])) st8[1] = INT64_MAX;
-        } else if (wave[p] == 0 && !meta) {
-            meta = n_added(p) == 0;
-        }
-    }
-    *n_waves = std::max<int32_t>(best_waves, meta ? 1 : 0);
-    *lower_bound = n_mv > 0 ? ctl[CTL_LB] : *n_waves;
+    if ((rc = wave_tail(f, P, best_waveo, best_waves, wave, n_waves, lower_bound))) return rc;
+    if (head_stuck_bytes_and_meta(P, W, current, target, size, wave, &st8[1])) *n_waves = std::max<int32_t>(*n_waves, 1);
+    if (f.n_mv == 0) *lower_bound = *n_waves;
     if (stats) std::copy(st8, st8 + 8, stats);
     return KAO_OK;
 }

@@ -98,77 +98,58 @@ def parse_pair(current_doc: dict, plan_doc: dict) -> WaveInput:
     return WaveInput(keys=keys, broker_ids=np.array(ids, dtype=np.int64), current=cur_rows, target=tgt_rows, target_replicas=tgt)
 
 
-def plan_waves_arrays(current: np.ndarray, target: np.ndarray, n_brokers: int, max_per_broker: int, seed: int = 1):
-    """kao_plan_waves on dense rows ([P, width] each, NONE-padded): (wave int32[P], n_waves, lower_bound)."""
+HEADROOM_STAT_KEYS = ("stuck", "stuck_bytes", "winning_order", "orders", "round_launches", "min_free", "min_free_wave",
+                      "min_free_broker")
+
+
+def _call(name: str, current, target, n_brokers: int, caps, seed: int, size=None, per_broker=None, trailing=()):
+    """One library call on dense rows: (wave int32[P], n_waves, lower_bound).  The three calls take the rows, then size[P] and the
+    per-broker arrays (stored, capacity) where they have them, then `caps`, the seed, the outputs and what `trailing` holds."""
     cur = np.ascontiguousarray(current, dtype=np.uint16)
     tgt = np.ascontiguousarray(target, dtype=np.uint16)
     if cur.shape != tgt.shape or cur.ndim != 2:
         raise ValueError("current and target must be [P, width] arrays of one shape")
     P, W = cur.shape
+    u16, u64, i32 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    args = [int(n_brokers), int(P), int(W), cur.ctypes.data_as(u16), tgt.ctypes.data_as(u16)]
+    arrays = []   # kept alive over the call
+    if size is not None:
+        sz = np.ascontiguousarray(size, dtype=np.uint64)
+        if sz.shape != (P,):
+            raise ValueError(f"size must hold one value per partition ({P}), got shape {sz.shape}")
+        arrays.append(sz if P else np.zeros(1, dtype=np.uint64))
+    if per_broker is not None:
+        sto, cap = (np.ascontiguousarray(a, dtype=np.uint64) for a in per_broker)
+        if sto.shape != (int(n_brokers),) or cap.shape != (int(n_brokers),):
+            raise ValueError(f"stored and capacity must hold one value per broker ({n_brokers}), got shapes {sto.shape} and {cap.shape}")
+        arrays += [sto, cap]
     wave = np.zeros(max(P, 1), dtype=np.int32)
     nw, lb = C.c_int32(0), C.c_int32(0)
-    u16, i32 = C.POINTER(C.c_uint16), C.POINTER(C.c_int32)
-    _check(_ffi.load().kao_plan_waves(int(n_brokers), int(P), int(W), cur.ctypes.data_as(u16), tgt.ctypes.data_as(u16),
-                                      int(max_per_broker), int(seed) & 0xFFFFFFFFFFFFFFFF, wave.ctypes.data_as(i32), C.byref(nw),
-                                      C.byref(lb)), "kao_plan_waves")
+    args += [a.ctypes.data_as(u64) for a in arrays] + [int(c) for c in caps]
+    args += [int(seed) & 0xFFFFFFFFFFFFFFFF, wave.ctypes.data_as(i32), C.byref(nw), C.byref(lb), *trailing]
+    _check(getattr(_ffi.load(), name)(*args), name)
     return wave[:P], int(nw.value), int(lb.value)
+
+
+def plan_waves_arrays(current: np.ndarray, target: np.ndarray, n_brokers: int, max_per_broker: int, seed: int = 1):
+    """kao_plan_waves on dense rows ([P, width] each, NONE-padded): (wave int32[P], n_waves, lower_bound)."""
+    return _call("kao_plan_waves", current, target, n_brokers, (max_per_broker,), seed)
 
 
 def plan_waves_sized_arrays(current: np.ndarray, target: np.ndarray, n_brokers: int, size, max_bytes_per_broker: int,
                             max_per_broker: int = 0, seed: int = 1):
     """kao_plan_waves_sized on dense rows: size = bytes per partition ([P]), max_bytes_per_broker = C (0: no byte cap),
     max_per_broker = k (0: no count cap).  (wave int32[P], n_waves, lower_bound)."""
-    cur = np.ascontiguousarray(current, dtype=np.uint16)
-    tgt = np.ascontiguousarray(target, dtype=np.uint16)
-    if cur.shape != tgt.shape or cur.ndim != 2:
-        raise ValueError("current and target must be [P, width] arrays of one shape")
-    P, W = cur.shape
-    sz = np.ascontiguousarray(size, dtype=np.uint64)
-    if sz.shape != (P,):
-        raise ValueError(f"size must hold one value per partition ({P}), got shape {sz.shape}")
-    sz = sz if P else np.zeros(1, dtype=np.uint64)
-    wave = np.zeros(max(P, 1), dtype=np.int32)
-    nw, lb = C.c_int32(0), C.c_int32(0)
-    u16, u64, i32 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
-    _check(_ffi.load().kao_plan_waves_sized(int(n_brokers), int(P), int(W), cur.ctypes.data_as(u16), tgt.ctypes.data_as(u16),
-                                            sz.ctypes.data_as(u64), int(max_bytes_per_broker), int(max_per_broker),
-                                            int(seed) & 0xFFFFFFFFFFFFFFFF, wave.ctypes.data_as(i32), C.byref(nw), C.byref(lb)),
-           "kao_plan_waves_sized")
-    return wave[:P], int(nw.value), int(lb.value)
-
-
-HEADROOM_STAT_KEYS = ("stuck", "stuck_bytes", "winning_order", "orders", "round_launches", "min_free", "min_free_wave",
-                      "min_free_broker")
+    return _call("kao_plan_waves_sized", current, target, n_brokers, (max_bytes_per_broker, max_per_broker), seed, size=size)
 
 
 def plan_waves_headroom_arrays(current: np.ndarray, target: np.ndarray, n_brokers: int, size, stored, capacity,
                                max_bytes_per_broker: int = 0, max_per_broker: int = 0, seed: int = 1, with_stats: bool = True):
     """kao_plan_waves_headroom on dense rows: stored / capacity = bytes each broker holds now / may hold ([n_brokers]); both caps may
     be 0.  (wave int32[P] with -2 = stuck, n_waves, lower_bound, stats int64[8] or None when `with_stats` is false)."""
-    cur = np.ascontiguousarray(current, dtype=np.uint16)
-    tgt = np.ascontiguousarray(target, dtype=np.uint16)
-    if cur.shape != tgt.shape or cur.ndim != 2:
-        raise ValueError("current and target must be [P, width] arrays of one shape")
-    P, W = cur.shape
-    sz = np.ascontiguousarray(size, dtype=np.uint64)
-    if sz.shape != (P,):
-        raise ValueError(f"size must hold one value per partition ({P}), got shape {sz.shape}")
-    sto = np.ascontiguousarray(stored, dtype=np.uint64)
-    cap = np.ascontiguousarray(capacity, dtype=np.uint64)
-    if sto.shape != (int(n_brokers),) or cap.shape != (int(n_brokers),):
-        raise ValueError(f"stored and capacity must hold one value per broker ({n_brokers}), got shapes {sto.shape} and {cap.shape}")
-    sz = sz if P else np.zeros(1, dtype=np.uint64)
-    wave = np.zeros(max(P, 1), dtype=np.int32)
-    stats = np.zeros(8, dtype=np.int64)
-    nw, lb = C.c_int32(0), C.c_int32(0)
-    u16, u64, i32 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
-    _check(_ffi.load().kao_plan_waves_headroom(int(n_brokers), int(P), int(W), cur.ctypes.data_as(u16), tgt.ctypes.data_as(u16),
-                                               sz.ctypes.data_as(u64), sto.ctypes.data_as(u64), cap.ctypes.data_as(u64),
-                                               int(max_bytes_per_broker), int(max_per_broker), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                               wave.ctypes.data_as(i32), C.byref(nw), C.byref(lb),
-                                               stats.ctypes.data_as(C.POINTER(C.c_int64)) if with_stats else None),
-           "kao_plan_waves_headroom")
-    return wave[:P], int(nw.value), int(lb.value), stats if with_stats else None
+    stats = np.zeros(8, dtype=np.int64) if with_stats else None
+    return _call("kao_plan_waves_headroom", current, target, n_brokers, (max_bytes_per_broker, max_per_broker), seed, size=size,
+                 per_broker=(stored, capacity), trailing=(stats.ctypes.data_as(C.POINTER(C.c_int64)) if with_stats else None,)) + (stats,)
 
 
 MAX_SIZE = 1 << 53   # sizes above it are not exact as JSON doubles (the C++ reader): rejected, never rounded
@@ -377,43 +358,72 @@ def plan_waves(current_doc: dict, plan_doc: dict, max_per_broker: int = 0, seed:
     it holds plus everything arriving; both caps are then optional.  Capacities come from capacity_for (the mapping, else the
     totalBytes of a kafka-log-dirs `sizes` document, else `default_capacity`), `stored` ({broker id: bytes} or None) from
     stored_for.  Partitions that fit no wave are in plan.stuck (wave -2) and in no wave document."""
+    return _run(_prepare(current_doc, plan_doc, max_per_broker, seed, sizes, max_bytes_per_broker, default_size, capacity, stored,
+                         max_utilisation, default_capacity, headroom))
+
+
+@dataclass
+class _Prepared:
+    """What plan_waves knows before the library is called: the rows, which call it will be and that call's arrays."""
+    input: WaveInput
+    call: str                                    # "plain", "sized" or "headroom"
+    max_per_broker: int
+    max_bytes_per_broker: int
+    seed: int
+    size: Optional[np.ndarray] = None            # [P] uint64 (sized and headroom)
+    stored: Optional[np.ndarray] = None          # [B] uint64 (headroom)
+    capacity: Optional[np.ndarray] = None        # [B] uint64 as given, what the utilisation is reported against (headroom)
+    effective: Optional[np.ndarray] = None       # [B] uint64 capacity * max_utilisation // 100, what the call takes (headroom)
+
+
+def _prepare(current_doc, plan_doc, max_per_broker, seed, sizes, max_bytes_per_broker, default_size, capacity, stored, max_utilisation,
+             default_capacity, headroom) -> _Prepared:
+    """The host-only first step of plan_waves (its arguments, all of them): every ValueError of the inputs is raised here."""
     wi = parse_pair(current_doc, plan_doc)
     headroom = bool(headroom) or capacity is not None or default_capacity is not None or max_utilisation != 100
     sized = headroom or sizes is not None or default_size is not None or max_bytes_per_broker
-    size = None
-    raw_cap = sto = stats = None
-    if sized:
-        dirs = _log_dirs_table(sizes) if headroom else None
-        if dirs is not None and sizes is dirs:   # a parse_log_dirs table: a partition's size is its largest non-future replica
-            sizes = {}
-            for ld in (ld for d in dirs.values() for ld in d.values()):
-                for t, p, sz, future in ld.entries:
-                    if not future:
-                        sizes[(t, p)] = max(sizes.get((t, p), 0), sz)
-        if sizes is not None and not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
-            sizes = parse_sizes(sizes)
-        size = sizes_for(wi, sizes or {}, default_size)
+    pre = _Prepared(wi, "headroom" if headroom else "sized" if sized else "plain", max_per_broker, max_bytes_per_broker, seed)
+    if not sized:
+        return pre
+    dirs = _log_dirs_table(sizes) if headroom else None
+    if dirs is not None and sizes is dirs:   # a parse_log_dirs table: a partition's size is its largest non-future replica
+        sizes = {}
+        for ld in (ld for d in dirs.values() for ld in d.values()):
+            for t, p, sz, future in ld.entries:
+                if not future:
+                    sizes[(t, p)] = max(sizes.get((t, p), 0), sz)
+    if sizes is not None and not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
+        sizes = parse_sizes(sizes)
+    pre.size = sizes_for(wi, sizes or {}, default_size)
     if headroom:
-        raw_cap, eff_cap = capacity_for(wi, capacity, dirs, default_capacity, max_utilisation)
-        sto = stored_for(wi, size, dirs)
+        pre.capacity, pre.effective = capacity_for(wi, capacity, dirs, default_capacity, max_utilisation)
+        pre.stored = stored_for(wi, pre.size, dirs)
         if stored is not None:
-            sto = np.array([int(stored.get(int(b), sto[j])) for j, b in enumerate(wi.broker_ids)], dtype=np.uint64)
-        wave, nw, lb, stats = plan_waves_headroom_arrays(wi.current, wi.target, len(wi.broker_ids), size, sto, eff_cap,
-                                                         max_bytes_per_broker, max_per_broker, seed)
-    elif sized:
-        wave, nw, lb = plan_waves_sized_arrays(wi.current, wi.target, len(wi.broker_ids), size, max_bytes_per_broker, max_per_broker,
-                                               seed)
+            pre.stored = np.array([int(stored.get(int(b), pre.stored[j])) for j, b in enumerate(wi.broker_ids)], dtype=np.uint64)
+    return pre
+
+
+def _run(pre: _Prepared) -> WavePlan:
+    """The second step of plan_waves: the one library call, and the WavePlan made of its result."""
+    wi, size = pre.input, pre.size
+    rows = (wi.current, wi.target, len(wi.broker_ids))
+    stats = None
+    if pre.call == "headroom":
+        wave, nw, lb, stats = plan_waves_headroom_arrays(*rows, size, pre.stored, pre.effective, pre.max_bytes_per_broker,
+                                                         pre.max_per_broker, pre.seed)
+    elif pre.call == "sized":
+        wave, nw, lb = plan_waves_sized_arrays(*rows, size, pre.max_bytes_per_broker, pre.max_per_broker, pre.seed)
     else:
-        wave, nw, lb = plan_waves_arrays(wi.current, wi.target, len(wi.broker_ids), max_per_broker, seed)
+        wave, nw, lb = plan_waves_arrays(*rows, pre.max_per_broker, pre.seed)
     docs = [{"version": 1, "partitions": []} for _ in range(nw)]
     for i, (t, p) in enumerate(wi.keys):
         if wave[i] >= 0:
             docs[int(wave[i])]["partitions"].append({"topic": t, "partition": p, "replicas": wi.target_replicas[i]})
     res = WavePlan(n_waves=nw, lower_bound=lb, optimal=nw == lb, wave=wave, waves=docs, input=wi)
-    if sized:
+    if size is not None:
         res.size = size
-        res.max_broker_bytes, res.bytes_lower_bound = wave_bytes(wi, size, wave, nw, int(max_bytes_per_broker))
-    if headroom:
+        res.max_broker_bytes, res.bytes_lower_bound = wave_bytes(wi, size, wave, nw, int(pre.max_bytes_per_broker))
+    if pre.call == "headroom":
         res.headroom, res.stats = True, stats
         res.stuck = [(wi.keys[i][0], wi.keys[i][1], wi.target_replicas[i]) for i in np.nonzero(wave == -2)[0]]
         res.stuck_bytes = int(stats[1])
@@ -421,7 +431,7 @@ def plan_waves(current_doc: dict, plan_doc: dict, max_per_broker: int = 0, seed:
         res.optimal = res.optimal and not res.stuck
         res.min_free, res.min_free_wave = int(stats[5]), int(stats[6])
         res.min_free_broker = int(wi.broker_ids[int(stats[7])]) if stats[7] >= 0 else -1
-        res.peak_utilisation_ppm = wave_utilisation(wi, size, wave, nw, sto, raw_cap)
+        res.peak_utilisation_ppm = wave_utilisation(wi, size, wave, nw, pre.stored, pre.capacity)
     return res
 
 
@@ -485,30 +495,19 @@ def main(argv=None) -> int:
             cur = json.load(f)
         with open(a.plan) as f:
             plan = json.load(f)
-        sizes = None
+        sizes, capacity = ({} if sized else None), None   # a byte flag without --sizes is still the sized call
         if a.sizes is not None:
             with open(a.sizes) as f:
-                sizes_text = f.read()
-            sizes = parse_sizes(sizes_text)
-        if sized:   # a missing size is reported before the device is touched
-            sizes_for(parse_pair(cur, plan), sizes or {}, default_size)
-        hkw = {}
-        if headroom:   # and so is a broker without a capacity
+                sizes = f.read()
+        if headroom:
             from .disk import _capacities
-            dirs = _log_dirs_table(sizes_text)
-            hkw = dict(capacity=_capacities(a.capacities) if a.capacities is not None else {}, default_capacity=default_capacity,
-                       max_utilisation=100 if a.max_utilisation is None else a.max_utilisation, headroom=True)
-            capacity_for(parse_pair(cur, plan), hkw["capacity"], dirs, default_capacity, hkw["max_utilisation"])
+            capacity = _capacities(a.capacities) if a.capacities is not None else {}
+        # a missing size, then a broker without a capacity, are reported here, before the device is touched
+        pre = _prepare(cur, plan, a.max_per_broker or 0, a.seed, sizes, cap_bytes, default_size, capacity, None,
+                       100 if a.max_utilisation is None else a.max_utilisation, default_capacity, headroom)
         from .solver import init
         init(a.device)
-        if headroom:
-            res = plan_waves(cur, plan, a.max_per_broker or 0, a.seed, sizes=dirs if dirs is not None else sizes, max_bytes_per_broker=cap_bytes,
-                             default_size=default_size, **hkw)
-        elif sized:
-            res = plan_waves(cur, plan, a.max_per_broker or 0, a.seed, sizes=sizes or {}, max_bytes_per_broker=cap_bytes,
-                             default_size=default_size)
-        else:
-            res = plan_waves(cur, plan, a.max_per_broker, a.seed)
+        res = _run(pre)
         for w, doc in enumerate(res.waves):
             with open(f"{a.out_prefix}{w + 1}.json", "w") as f:
                 f.write(json.dumps(doc) + "\n")
