@@ -1,10 +1,10 @@
 // kao-disk -- disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk, DESIGN.md
 // section 4m; under --max-bytes kao_balance_disk_budget, section 4n; with --capacities kao_balance_disk_capacity, section 4q; with
-// --exchange kao_balance_disk_exchange, section 4u).
+// --exchange kao_balance_disk_exchange, section 4u; with --drain kao_balance_disk_drain, section 4w).
 //
 //   kao-disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt [--default-size N]
 //            [--max-per-rack N] [--keep-leaders] [--min-gain BYTES] [--max-bytes BYTES] [--max-rounds N] [--dry-run] --out plan.json
-//            [--capacities caps.json | id:bytes,...] [--default-capacity BYTES] [--exchange] [--report] [--device D]
+//            [--capacities caps.json | id:bytes,...] [--default-capacity BYTES] [--exchange] [--drain ID[,ID...]] [--report] [--device D]
 //
 // Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
 // output or a sizes document, as kao-waves reads them) and moves replicas to brokers outside their row until no single move closes a
@@ -23,8 +23,14 @@
 // --exchange goes on from the move-stable state with exchanges: two replicas of different partitions trade places across a broker
 // pair.  It works by bytes only, so it is refused together with --max-bytes, --capacities or --default-capacity; the report line then
 // ends in peak_of_moves (the peak the moves alone reach), exchange_rounds, exchanges and exchange_proposals.
+// --drain ID[,ID...] names brokers of --broker-list that are to end empty: their replicas leave whatever the gain (slot 0 and size 0
+// included), nothing moves onto them, and the live brokers are balanced around what arrives.  An id outside the list, a duplicate or
+// every broker is a usage error.  It works by bytes only, so it is refused together with --max-bytes, --capacities, --default-capacity
+// or --exchange.  The report line then ends in draining, drain_bytes_before, drain_bytes_after, drain_moves, last_drain_round,
+// replicas_left and bytes_left, and one line "disk: left <topic>-<partition> broker=<id> reason=<why>" follows per replica left: its row
+// holds every live broker, the rack rule forbids every other one, or (only when --max-rounds stopped the call) max_rounds.
 // All computation happens in libkao.so on the GPU.
-// Exit status: 0 = ok, 1 = error, 2 = usage.
+// Exit status: 0 = ok, 1 = error, 2 = usage, 3 = with --drain, replicas are left on a draining broker (every file is written).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -47,10 +53,14 @@ namespace {
         "usage: kao-disk --current <reassignment.json> --broker-list <id,id,...> --racks <racks.json | id:rack,...>\n"
         "                --sizes <kafka-log-dirs output | sizes.json> [--default-size N] [--max-per-rack N] [--keep-leaders]\n"
         "                [--min-gain N[K|M|G|T]] [--max-bytes N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report]\n"
-        "                [--capacities <caps.json | id:bytes,...>] [--default-capacity N[K|M|G|T]] [--exchange] [--device D]\n"
+        "                [--capacities <caps.json | id:bytes,...>] [--default-capacity N[K|M|G|T]] [--exchange] [--drain ID[,ID...]]\n"
+        "                [--device D]\n"
         "--exchange: exchanges of two replicas across a broker pair go on from the move-stable state (by bytes only: not with\n"
         "            --max-bytes, --capacities or --default-capacity)\n"
-        "writes the partitions whose replicas move; exit status: 0 = ok, 1 = error, 2 = usage\n");
+        "--drain: the named brokers of --broker-list are to end empty (by bytes only: not with --max-bytes, --capacities,\n"
+        "            --default-capacity or --exchange)\n"
+        "writes the partitions whose replicas move; exit status: 0 = ok, 1 = error, 2 = usage, 3 = with --drain, replicas are left\n"
+        "on a draining broker (no admissible live broker takes them; every file is written)\n");
     std::exit(2);
 }
 
@@ -65,9 +75,9 @@ std::string ppm(uint64_t num, uint64_t den) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path, caps_arg;
+    std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path, caps_arg, drain_csv;
     int device = 0, max_per_rack = 0, max_rounds = 0;
-    bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false, have_caps = false, have_default_cap = false, exchange = false;
+    bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false, have_caps = false, have_default_cap = false, exchange = false, have_drain = false;
     uint64_t default_size = 0, min_gain = 0, max_bytes = 0, default_cap = 0;
     auto count_arg = [](const std::string &v, const char *msg) {
         if (v.empty() || v.size() > 9 || v.find_first_not_of("0123456789") != std::string::npos) usage(msg);
@@ -84,6 +94,7 @@ int main(int argc, char **argv) {
         else if (a == "--dry-run") dry_run = true;
         else if (a == "--keep-leaders") keep_leaders = true;
         else if (a == "--exchange") exchange = true;
+        else if (a == "--drain") { drain_csv = need("--drain"); have_drain = true; }
         else if (a == "--device") device = std::atoi(need("--device").c_str());
         else if (a == "--report") report = true;
         else if (a == "--default-size") {
@@ -109,6 +120,25 @@ int main(int argc, char **argv) {
         usage("--current, --broker-list, --racks, --sizes and --out are required");
     const bool by_capacity = have_caps || have_default_cap;
     if (exchange && (have_budget || by_capacity)) usage("--exchange works by bytes only: not together with --max-bytes, --capacities or --default-capacity");
+    if (have_drain && (exchange || have_budget || by_capacity)) usage("--drain works by bytes only: not together with --max-bytes, --capacities, --default-capacity or --exchange");
+    std::vector<uint8_t> drain;       // per broker of --broker-list, in its order: != 0 for a draining one
+    if (have_drain) {                 // an unknown id, a duplicate or every broker is a usage error
+        std::vector<int> ids;
+        for (auto &t : split(brokers_csv, ',')) if (!t.empty()) ids.push_back(std::atoi(t.c_str()));
+        drain.assign(ids.size(), 0);
+        size_t n = 0;
+        for (auto &t : split(drain_csv, ',')) {
+            if (t.empty()) continue;
+            if (t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) usage("--drain needs broker ids, CSV");
+            const auto at = std::find(ids.begin(), ids.end(), std::atoi(t.c_str()));
+            if (at == ids.end()) usage(("--drain: broker " + t + " is not in the broker list").c_str());
+            if (drain[(size_t)(at - ids.begin())]) usage(("--drain: broker " + t + " is named twice").c_str());
+            drain[(size_t)(at - ids.begin())] = 1;
+            ++n;
+        }
+        if (n == 0) usage("--drain needs broker ids, CSV");
+        if (n == ids.size()) usage("--drain: every broker is draining, no live broker is left");
+    }
     std::vector<uint64_t> capacity;   // per broker of --broker-list, in its order
     if (by_capacity) {                // a broker without a capacity is a usage error
         std::string msg;
@@ -158,10 +188,11 @@ int main(int argc, char **argv) {
         if (rc) throw std::runtime_error(std::string("kao_init: ") + kao_strerror(rc) + " " + kao_last_error());
 
         std::vector<uint16_t> rows = cr.rows;
-        int32_t n_moved = 0, status = 0;
-        uint64_t bytes_moved = 0, before = 0, after = 0, bound = 0, before2[2] = {0, 1}, after2[2] = {0, 1}, bound2[2] = {0, 1};
+        int32_t n_moved = 0, status = 0, n_left = 0;
+        uint64_t bytes_left = 0, bytes_moved = 0, before = 0, after = 0, bound = 0, before2[2] = {0, 1}, after2[2] = {0, 1}, bound2[2] = {0, 1};
         int64_t stats[12] = {0};
-        const char *entry = by_capacity ? "kao_balance_disk_capacity: " : have_budget ? "kao_balance_disk_budget: " : exchange ? "kao_balance_disk_exchange: " : "kao_balance_disk: ";
+        const char *entry = by_capacity ? "kao_balance_disk_capacity: " : have_budget ? "kao_balance_disk_budget: " : exchange ? "kao_balance_disk_exchange: "
+                            : have_drain ? "kao_balance_disk_drain: " : "kao_balance_disk: ";
         if (by_capacity) {
             rc = kao_balance_disk_capacity(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), capacity.data(), max_per_rack,
                                            keep_leaders ? 0 : 1, min_gain, have_budget ? max_bytes : UINT64_MAX, max_rounds, dry_run ? 1 : 0, &n_moved,
@@ -173,6 +204,9 @@ int main(int argc, char **argv) {
         else if (exchange)
             rc = kao_balance_disk_exchange(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1,
                                            min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
+        else if (have_drain)
+            rc = kao_balance_disk_drain(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), drain.data(), max_per_rack, keep_leaders ? 0 : 1,
+                                        min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &n_left, &bytes_left, &status, stats);
         else
             rc = kao_balance_disk(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), max_per_rack, keep_leaders ? 0 : 1, min_gain,
                                   max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, &status, stats);
@@ -196,7 +230,35 @@ int main(int argc, char **argv) {
             if (exchange)
                 std::fprintf(stderr, " peak_of_moves=%lld exchange_rounds=%lld exchanges=%lld exchange_proposals=%lld", (long long)stats[11], (long long)stats[8],
                              (long long)stats[9], (long long)stats[10]);
+            if (have_drain) {
+                std::string ids;
+                unsigned long long held = 0;
+                for (int b = 0; b < B; ++b)
+                    if (drain[(size_t)b]) ids += (ids.empty() ? "" : ",") + std::to_string(cl.brokers[(size_t)b]);
+                for (int p = 0; p < P; ++p)
+                    for (int j = 0; j < W && cr.rows[(size_t)p * W + j] != KAO_NONE; ++j) held += drain[cr.rows[(size_t)p * W + j]] ? size[(size_t)p] : 0;
+                std::fprintf(stderr, " draining=%s drain_bytes_before=%llu drain_bytes_after=%llu drain_moves=%lld last_drain_round=%lld replicas_left=%d bytes_left=%llu",
+                             ids.c_str(), held, (unsigned long long)bytes_left, (long long)stats[8], (long long)stats[9], n_left, (unsigned long long)bytes_left);
+            }
             std::fprintf(stderr, "\n");
+            for (int p = 0; have_drain && !dry_run && p < P; ++p) {   // one line per replica left, by row and slot, with the reason
+                const uint16_t *row = rows.data() + (size_t)p * W;
+                int k = 0;
+                while (k < W && row[k] != KAO_NONE) ++k;
+                for (int j = 0; j < k; ++j) {
+                    if (!drain[row[j]]) continue;
+                    bool outside = false, ok = false;
+                    for (int c = 0; c < B; ++c) {
+                        if (drain[(size_t)c] || std::find(row, row + k, (uint16_t)c) != row + k) continue;
+                        outside = true;
+                        int cnt = 0;
+                        for (int i = 0; i < k; ++i) cnt += cl.rack_of[row[i]] == cl.rack_of[(size_t)c];
+                        ok |= max_per_rack <= 0 || cl.rack_of[(size_t)c] == cl.rack_of[row[j]] || cnt < max_per_rack;
+                    }
+                    std::fprintf(stderr, "disk: left %s-%d broker=%d reason=%s\n", cr.keys[(size_t)p].first.c_str(), cr.keys[(size_t)p].second, cl.brokers[row[j]],
+                                 !outside ? "row_holds_every_live_broker" : !ok ? "rack_rule" : "max_rounds");
+                }
+            }
         }
         const std::string text = changed_rows_text(cr, rows, cl.brokers);
         std::ofstream f(out_path);
@@ -204,7 +266,7 @@ int main(int argc, char **argv) {
         f.close();
         if (!f) throw std::runtime_error("cannot write " + out_path);
         kao_shutdown();
-        return 0;
+        return n_left > 0 ? 3 : 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "kao-disk: %s\n", e.what());
         return 1;

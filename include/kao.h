@@ -846,6 +846,42 @@ int kao_balance_disk_exchange(int32_t n_brokers, int32_t n_racks, const uint8_t 
                               uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *status,
                               int64_t stats[12] /* may be NULL */);
 
+/* ---- Disk-usage balance that empties brokers ------------------------------------------------------------------
+ * kao_balance_disk with a set of DRAINING brokers, drain[b] != 0, that are to end without a replica; the others are LIVE.  D = the
+ * number of draining brokers.  By bytes only: no byte budget, no capacities, no exchanges.  Rows, sizes, S(b), rounds on the loads as
+ * they stand at the round's start, the two walks, key, bid, win rule, apply, determinism and dry_run are those of kao_balance_disk.
+ * Six things change.
+ * RANK: draining brokers rank before every live broker; inside each group the order is S descending, then index ascending.  A
+ * draining broker of rank r < D is thus paired with the (r+1)-th lightest live broker by the unchanged walks.
+ * ADMISSIBLE: a destination c must also have drain[c] == 0.  Nothing ever moves onto a draining broker.
+ * MOVABLE: a slot whose broker is draining is always movable: slot 0 even with move_leaders == 0 (the preferred leadership goes with
+ * it; once on a live broker it is fixed again), and the slots of a partition with size[p] == 0 (skipped everywhere else, as ever).
+ * GAIN: a proposal from a draining source needs no gain test: it ignores min_gain and takes c1 if there is one, else c2.  Live
+ * sources are tested as in kao_balance_disk.
+ * KEY, WIN, APPLY: unchanged.  The rank in the key makes drain moves beat live moves wherever they meet, and a draining broker gives
+ * up one replica per round.
+ * END: when a round has no proposal, or after max_rounds rounds.  A round with a drain move lowers the number of replicas on draining
+ * brokers; any other round leaves it and lowers the sum of S^2: the rounds end.  The peak may RISE while the drain runs;
+ * *peak_before / *peak_after stay max_b S(b) over all brokers.
+ * *n_left / *bytes_left = the replicas (and their bytes) still on draining brokers in the final rows.  With stats[5] == 0 each of them
+ * has no admissible live destination: its row holds every live broker, or the rack rule forbids every other one.  They are reported,
+ * they are no error, and the rack rule is never relaxed.
+ * *lower_bound holds for every reachable state with the draining brokers empty: the maximum of (0) max_p size[p], (1)
+ * ceil(sum of k_p * size[p] / (n_brokers - D)), (2) with move_leaders == 0, the largest sum of the slot-0 replicas that start on one
+ * LIVE broker.  *status = KAO_STATUS_OPTIMAL_PROVEN iff *n_left == 0 and *peak_after == *lower_bound, else
+ * KAO_STATUS_FEASIBLE_BOUND_GAP; the return code is KAO_OK either way.
+ * D == 0 gives byte for byte the rows, numbers and stats[0..7] of kao_balance_disk, *n_left == 0 and stats[8] == stats[9] == 0.
+ * stats (may be NULL): [0..7] as for kao_balance_disk, [8] drain moves applied, [9] the number (from 1) of the last round that applied
+ * a drain move, 0 when there was none.  Checks, limits and refusals are those of kao_balance_disk, before any device is used, the rows
+ * untouched on error; and KAO_ERR_INVALID for drain == NULL, n_left == NULL, bytes_left == NULL, or D == n_brokers (no live broker). */
+int kao_balance_disk_drain(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
+                           uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *size /* [n_partitions] */,
+                           const uint8_t *drain /* [n_brokers], != 0: this broker is to end empty */,
+                           int32_t max_per_rack /* <= 0: no rack rule */, int32_t move_leaders, uint64_t min_gain,
+                           int32_t max_rounds /* <= 0: no limit */, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                           uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *n_left, uint64_t *bytes_left,
+                           int32_t *status, int64_t stats[10] /* may be NULL */);
+
 /* ---- Log-dir balance inside each broker ---------------------------------------------------------------------
  * Every planner above treats a broker as one disk; a JBOD broker has several log dirs and dies on the fullest of them.  Broker b
  * owns the dirs dir_start[b] .. dir_start[b+1]-1 of ONE global dir index (CSR; n_dirs = dir_start[n_brokers]; a broker may own no

@@ -46,6 +46,12 @@
 // a, so it ranks behind a: the THOROUGH walk sees every move there is, and a round of it without a proposal ends the descent.  A
 // winner leaves both of its brokers strictly below the old u(a), so the utilisations sorted descending fall lexicographically.
 // Grant, apply and finish work on ranks and bytes and are the ones above.
+//
+// DRAINING (kao_balance_disk_drain, section 4w) D of the brokers are to end empty.  RANK puts them before every live broker (inside
+// each group S descending, then index ascending), so "broker x is draining" is "rank(x) < D" everywhere below and costs no load of
+// its own: a walk never goes below rank D (nothing moves onto a draining broker), a slot whose broker ranks below D is always movable
+// (slot 0 and size 0 included), and its proposal takes c1, else c2, without a gain test.  Key, bid, win and apply are the ones above:
+// the rank in the key puts the drain moves first, and a draining broker gives up one replica a round.  The peak may rise meanwhile.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -65,7 +71,7 @@ constexpr int kDkThoroughBatch = 4;     // ... of THOROUGH rounds: few of them h
 constexpr int kDkHardRounds = 1 << 26;  // no descent gets here; a guard against an endless loop
 constexpr u64 kDkNoKey = ~0ull;
 constexpr int kDkGrantThreads = 1024;   // k_dk_grant: one workgroup, one rank per lane and chunk
-enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_SPENT, D_REFUSED, D_XCH, D_XPEAK, D_XSEEN, D_DONE, D_N = 16 };
+enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_SPENT, D_REFUSED, D_XCH, D_XPEAK, D_XSEEN, D_DONE, D_DRAINED, D_LASTDRAIN, D_NLEFT, D_BLEFT, D_N = 20 };
 
 struct DkNet {   // one call; every pointer is device memory
     int P, W, B, cap, first;   // first = the lowest movable slot: 0 with move_leaders, else 1
@@ -84,10 +90,13 @@ struct DkNet {   // one call; every pointer is device memory
     uint8_t *grant;            // [B] under a budget: the winner that leaves b is applied in this round
     u64 max_bytes;             // the budget; ctl[D_SPENT] = the costs of the moves applied so far
     const u64 *capacity;       // [B] by utilisation only: the bytes of disk a broker has
+    int nd;                    // draining only: D, the number of draining brokers (they hold the ranks 0 .. D-1); 0 in every other call
+    const uint8_t *drain;      // [B] draining only: != 0 for a broker that is to end empty
 };
 
 // ---- once per call ------------------------------------------------------------------------------------------------------------------
-// loads, the largest size, sum k_p size[p], the bytes of the slot-0 replicas per broker
+// loads, the largest size, sum k_p size[p], the bytes of the slot-0 replicas per broker (Drain: per LIVE broker; a draining one's leave)
+template <bool Drain>
 __global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     u64 w = 0, all = 0;
@@ -102,7 +111,7 @@ __global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) {
                 atomicAdd(&n.load[x], w);
                 all += w;
             }
-            atomicAdd(&fixed[row[0]], w);
+            if (!Drain || n.drain[row[0]] == 0) atomicAdd(&fixed[row[0]], w);
         }
     }
     wave_max_to(w, &n.ctl[D_MAXSIZE]);
@@ -131,6 +140,18 @@ __global__ __launch_bounds__(kDkThreads) void k_dk_rank(int B, const u64 *__rest
     const int b = blockIdx.x * kDkThreads + threadIdx.x;
     const u64 mine = b < B ? load[b] : 0, mcap = Cap && b < B ? capacity[b] : 1;
     const int r = rank_ahead<kDkThreads, Cap>(B, b, mine, mcap, load, capacity);
+    if (b < B) {   // ranks are a permutation: r < B
+        rank[b] = r;
+        order[r] = b;
+    }
+}
+
+// ... with draining brokers: they rank before every live one (rank_ahead with a first group)
+__global__ __launch_bounds__(kDkThreads) void k_dk_rank_drain(int B, const u64 *__restrict__ load, const uint8_t *__restrict__ drain, int32_t *__restrict__ rank,
+                                                              int32_t *__restrict__ order) {
+    const int b = blockIdx.x * kDkThreads + threadIdx.x;
+    const u64 mine = b < B ? load[b] | (drain[b] ? 1ull << 63 : 0) : 0;
+    const int r = rank_ahead<kDkThreads, false, true>(B, b, mine, 1, load, nullptr, drain);
     if (b < B) {   // ranks are a permutation: r < B
         rank[b] = r;
         order[r] = b;
@@ -210,14 +231,46 @@ __device__ __forceinline__ int dk_walk(const DkNet &n, const DkRow &row, const D
     return -1;
 }
 
-template <bool Budget, bool Cap = false, bool Thorough = false>
+// Drain: a slot on a broker of rank < n.nd is movable whatever its index and whatever the size, and proposes without a gain test; no walk
+// goes below rank n.nd.  The other slots of a partition with size > 0 are as ever (with n.nd == 0 the proposals are those of <false>)
+template <bool Budget, bool Cap = false, bool Thorough = false, bool Drain = false>
 __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
+    static_assert(!Drain || !(Budget || Cap || Thorough), "draining is by bytes, without a budget");
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     bool prop = false;
     if (p < n.P) {
         u64 key = kDkNoKey;
         const u64 w = n.size[p];
-        if (w) {
+        if constexpr (Drain) {
+            const DkRow row = dk_load_row(n, p);
+            const DkHome home{};
+            const int lowest = w ? n.first : n.W;   // the lowest slot that is movable on a live broker
+            int last = -1;
+            for (int t = 0; t < n.W && !prop; ++t) {
+                int ra_rank = n.B, a = 0, ra = 0, slot = 0;
+#pragma unroll
+                for (int j = 0; j < KAO_MAX_RF; ++j) {
+                    if ((j >= lowest || row.rr[j] < n.nd) && row.rr[j] > last && row.rr[j] < ra_rank) { ra_rank = row.rr[j]; a = row.b[j]; ra = row.rk[j]; slot = j; }
+                }
+                if (ra_rank == n.B) break;   // no movable slot is left
+                last = ra_rank;
+                const bool leaves = ra_rank < n.nd;   // the source is draining
+                int c = dk_walk<false, false>(n, row, home, true, n.B - 1 - ra_rank, max(ra_rank + 1, n.nd), ra);
+                if (c < 0 || (!leaves && !descent_gains(n.load[a], n.load[c], w, n.min_gain))) {
+                    c = dk_walk<false, false>(n, row, home, true, n.B - 1, max(n.B - ra_rank, n.nd), ra);
+                    if (c >= 0 && !leaves && !descent_gains(n.load[a], n.load[c], w, n.min_gain)) c = -1;
+                }
+                if (c >= 0) {
+                    prop = true;
+                    key = (u64)(uint32_t)ra_rank << 48 | (u64)(0xFFFFu - wave_bytes_code(w)) << 32 | (u64)(uint32_t)p;
+                    n.slot[p] = (uint8_t)slot;
+                    n.dest[p] = (uint16_t)c;
+                    u64 *mine = n.mk + (size_t)(r & 1) * n.B;
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&mine[a], key);
+                    descent_bid<__HIP_MEMORY_SCOPE_AGENT>(&mine[c], key);
+                }
+            }
+        } else if (w) {
             const DkRow row = dk_load_row(n, p);
             DkHome home;
             bool fits = true;   // the size fits what is left of the budget: tested first, so the home compares run only when it is nearly spent
@@ -509,10 +562,12 @@ __device__ __forceinline__ bool dk_apply_move(const std::conditional_t<X, DkNetX
 // APPLY of round r.  It clears the minkey words of round r + 1 (last read by the apply of round r - 1) and applies the winners.  In
 // the exchange call (X; count, xcount = the round's proposals of the two kinds) the round is whichever kind it is: an exchange round
 // iff it has no move proposal, and ctl[D_DONE] is set once a round has had neither kind.  A winner of an exchange reads only what its
-// proposer stored (an exchange flips four mask bits; a winner alone touches the mask rows of its two brokers).
-template <bool Budget, bool X>
+// proposer stored (an exchange flips four mask bits; a winner alone touches the mask rows of its two brokers).  Drain: a winner whose
+// key carries a rank below n.nd left a draining broker; they are counted, and the last round (from 1) that had one is kept.
+template <bool Budget, bool X, bool Drain = false>
 __global__ void k_dk_apply(std::conditional_t<X, DkNetX, DkNet> n, int r, const uint32_t *__restrict__ count, const uint32_t *__restrict__ xcount) {
     static_assert(!(Budget && X), "exchange rounds are by bytes, without a budget");
+    static_assert(!Drain || !(Budget || X), "draining is by bytes, without a budget or exchanges");
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     {
         u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
@@ -526,7 +581,7 @@ __global__ void k_dk_apply(std::conditional_t<X, DkNetX, DkNet> n, int r, const 
         isx = *count == 0;
         if (p == 0 && isx && *xcount == 0) n.ctl[D_DONE] = 1;
     }
-    bool won = false;
+    bool won = false, left = false;   // left: the winner took a replica off a draining broker
     u64 cost = 0;
     if (p < n.P) {
         const u64 key = n.key[p];
@@ -534,6 +589,7 @@ __global__ void k_dk_apply(std::conditional_t<X, DkNetX, DkNet> n, int r, const 
             const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
             if (!isx) {
                 won = dk_apply_move<Budget, X>(n, p, key, mine, &cost);
+                if (Drain) left = won && (int)(key >> 48) < n.nd;
             } else if constexpr (X) {
                 const int slot = n.slot[p], a = n.xsrc[p], c = n.dest[p];
                 const uint32_t y = n.xpart[p];
@@ -559,14 +615,20 @@ __global__ void k_dk_apply(std::conditional_t<X, DkNetX, DkNet> n, int r, const 
     lane_count_to(won, &n.ctl[D_MOVES]);
     if (Budget) wave_sum_to(cost, &n.ctl[D_SPENT]);   // the sum of a wavefront wraps as its terms do; it adds nothing when it is 0
     if constexpr (X) lane_count_to(won && isx, &n.ctl[D_XCH]);
+    if constexpr (Drain) {
+        lane_count_to(left, &n.ctl[D_DRAINED]);
+        wave_max_to(left ? (u64)r + 1 : 0, &n.ctl[D_LASTDRAIN]);
+    }
 }
 
 // ---- the result ---------------------------------------------------------------------------------------------------------------------
-// one lane per partition: the brokers of the final row that the input row did not hold, their bytes, the rows that changed
+// one lane per partition: the brokers of the final row that the input row did not hold, their bytes, the rows that changed.  Drain:
+// and the replicas still on draining brokers, with their bytes
+template <bool Drain>
 __global__ void k_dk_finish(DkNet n) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     bool ch = false;
-    u64 fresh = 0, bytes = 0;
+    u64 fresh = 0, bytes = 0, stay = 0;
     if (p < n.P) {
         const uint16_t *now = n.rows + (size_t)p * n.W, *was = n.rows0 + (size_t)p * n.W;
         for (int j = 0; j < n.W; ++j) {
@@ -576,8 +638,13 @@ __global__ void k_dk_finish(DkNet n) {
             bool old = false;
             for (int i = 0; i < n.W; ++i) old |= was[i] == x;
             fresh += old ? 0 : 1;
+            if (Drain) stay += n.drain[x] ? 1 : 0;
         }
         bytes = fresh * n.size[p];
+    }
+    if constexpr (Drain) {
+        wave_sum_to(stay, &n.ctl[D_NLEFT]);
+        wave_sum_to(p < n.P ? stay * n.size[p] : 0, &n.ctl[D_BLEFT]);
     }
     wave_sum_to(fresh, &n.ctl[D_NMOVED]);
     wave_sum_to(bytes, &n.ctl[D_BYTES]);
@@ -647,15 +714,18 @@ bool frac_integral(const DkFrac &peak, const uint64_t *cap, int B, uint64_t tota
 // Which entry point: budget adds k_dk_grant to every round, stats[8], stats[9] and the probe that decides stats[9]; cap (by utilisation)
 // the rank by utilisation, the capacity form of the test, THOROUGH rounds, fractions as outputs and stats[10]; exchange
 // (kao_balance_disk_exchange: by bytes, without a budget, as k_dk_apply asserts) PI, the masks and the partition words, the exchange
-// PROPOSE in every round (it returns at once in a round with a move proposal, and after the call has ended) and stats[8..11].
+// PROPOSE in every round (it returns at once in a round with a move proposal, and after the call has ended) and stats[8..11]; drain
+// (kao_balance_disk_drain: by bytes, without a budget or exchanges) the drain forms of RANK, PROPOSE, APPLY, the init and the finish, the
+// bound over the live brokers, n_left / bytes_left and stats[8..9].  It launches what kao_balance_disk launches, kernel for kernel.
 struct DkKind {
-    bool budget, cap, exchange;
+    bool budget, cap, exchange, drain = false;
 };
 
 struct DkArgs {   // the arguments of the C calls in their order (cap, max_bytes where the call has them); the peaks and the bound are two words by utilisation
     int32_t B, R; const uint8_t *rack_of; int32_t P, W; uint16_t *rows; const uint64_t *size, *cap;
     int32_t max_per_rack, move_leaders; uint64_t min_gain, max_bytes; int32_t max_rounds, dry_run;
     int32_t *n_moved; uint64_t *bytes_moved, *peak_before, *peak_after, *lower_bound; int32_t *status; int64_t *stats;
+    const uint8_t *drain = nullptr; int32_t *n_left = nullptr; uint64_t *bytes_left = nullptr;   // kao_balance_disk_drain only
 };
 
 struct DkCall {   // one call on the host
@@ -663,6 +733,7 @@ struct DkCall {   // one call on the host
     uint64_t cap_sum = 0, cap_max = 0;   // by utilisation
     std::vector<uint32_t> pi, pos;       // exchange: PI (the partitions with size > 0, size descending, then index ascending), the position of
     std::vector<uint64_t> ps;            // a partition in it, the sizes along it
+    int n_drain = 0;                     // draining: D
     CallBufs m;
     hipStream_t st;
     DkNetX x;                 // the exchange call's; its DkNet part is every call's
@@ -706,13 +777,13 @@ int dk_open(DkCall &c, const DkArgs &in) {
     const bool X = c.kind.exchange;
     const int B = in.B, P = in.P, PW = P * in.W, N = (int)c.pi.size(), words = (N + 63) / 64;
     // one arena: ctl u64[D_N] | count u32[2 kDkBatch] | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] | capacity u64[B] |
-    //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B]
+    //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B] | drain u8[B]
     Carve cv;
     const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(2 * kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
                  o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_cap = cv.take<u64>(c.kind.cap ? B : 0), o_rank = cv.take<int32_t>(B),
                  o_order = cv.take<int32_t>(B), o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW),
                  o_rows0 = cv.take<uint16_t>(PW), o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B),
-                 o_grant = cv.take<uint8_t>(c.kind.budget ? B : 0);
+                 o_grant = cv.take<uint8_t>(c.kind.budget ? B : 0), o_drain = cv.take<uint8_t>(c.kind.drain ? B : 0);
     // exchange: pk u64[2P] (all ones) | mask u64[B words] (zeroed) | ps u64[N] | pi u32[N] | pos, xpart u32[P] | xsrc u16[P] | xslot u8[P]
     const size_t o_pk = cv.take<u64>(X ? 2 * (size_t)P : 0), o_mask = cv.take<u64>(X ? (size_t)B * words : 0), o_ps = cv.take<u64>(N), o_pi = cv.take<uint32_t>(N),
                  o_pos = cv.take<uint32_t>(X ? P : 0), o_xpart = cv.take<uint32_t>(X ? P : 0), o_xsrc = cv.take<uint16_t>(X ? P : 0),
@@ -728,6 +799,7 @@ int dk_open(DkCall &c, const DkArgs &in) {
     n.slot = m.at<uint8_t>(o_slot); n.dest = m.at<uint16_t>(o_dest); n.key = m.at<u64>(o_key); n.load = m.at<u64>(o_load);
     n.rank = m.at<int32_t>(o_rank); n.order = m.at<int32_t>(o_order); n.mk = m.at<u64>(o_mk); n.ctl = m.at<u64>(o_ctl);
     n.grant = m.at<uint8_t>(o_grant); n.max_bytes = in.max_bytes; n.capacity = c.kind.cap ? m.at<u64>(o_cap) : nullptr;
+    n.nd = c.n_drain; n.drain = c.kind.drain ? m.at<uint8_t>(o_drain) : nullptr;
     n.N = N; n.words = words; n.pi = m.at<uint32_t>(o_pi); n.ps = m.at<u64>(o_ps); n.pos = m.at<uint32_t>(o_pos); n.mask = m.at<u64>(o_mask);
     n.pk = m.at<u64>(o_pk); n.xsrc = m.at<uint16_t>(o_xsrc); n.xpart = m.at<uint32_t>(o_xpart); n.xslot = m.at<uint8_t>(o_xslot);
 
@@ -740,6 +812,7 @@ int dk_open(DkCall &c, const DkArgs &in) {
         HIP_TRY(hipMemcpyAsync(m.at<u64>(o_size), in.size, (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     }
     if (c.kind.cap) HIP_TRY(hipMemcpyAsync(m.at<u64>(o_cap), in.cap, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (c.kind.drain) HIP_TRY(hipMemcpyAsync(m.at<uint8_t>(o_drain), in.drain, (size_t)B, hipMemcpyHostToDevice, st));
     if (X && P) {
         HIP_TRY(hipMemsetAsync(n.pk, 0xFF, 2 * (size_t)P * sizeof(u64), st));
         HIP_TRY(hipMemcpyAsync(m.at<uint32_t>(o_pos), c.pos.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -756,7 +829,8 @@ int dk_open(DkCall &c, const DkArgs &in) {
 
 // PROPOSE: by bytes, or FAST / THOROUGH by utilisation; `budget` is the round's (the probe at the end of a budgeted call runs without)
 void dk_propose(const DkCall &c, bool budget, bool thorough, int r, uint32_t *count) {
-    void (*const k)(DkNet, int, uint32_t *) = !c.kind.cap ? (budget ? k_dk_propose<true, false, false> : k_dk_propose<false, false, false>)
+    void (*const k)(DkNet, int, uint32_t *) = c.kind.drain ? k_dk_propose<false, false, false, true>
+                                              : !c.kind.cap ? (budget ? k_dk_propose<true, false, false> : k_dk_propose<false, false, false>)
                                               : thorough  ? (budget ? k_dk_propose<true, true, true> : k_dk_propose<false, true, true>)
                                                           : (budget ? k_dk_propose<true, true, false> : k_dk_propose<false, true, false>);
     k<<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, count);
@@ -766,13 +840,15 @@ void dk_propose(const DkCall &c, bool budget, bool thorough, int r, uint32_t *co
 void dk_apply(const DkCall &c, int r, int i) {
     if (c.kind.exchange) k_dk_apply<false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.x, r, c.d_cnt + i, c.d_cnt + kDkBatch + i);
     else if (c.kind.budget) k_dk_apply<true, false><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
+    else if (c.kind.drain) k_dk_apply<false, false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
     else k_dk_apply<false, false><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
 }
 
 // RANK, PROPOSE and (exchange) the exchange PROPOSE of round r, counted in column i: the head of a round, or all of "is there a proposal?"
 void dk_probe(DkCall &c, bool budget, bool thorough, int r, int i) {
     const DkNet &n = c.n();
-    (c.kind.cap ? k_dk_rank<true> : k_dk_rank<false>)<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.capacity, n.rank, n.order);
+    if (c.kind.drain) k_dk_rank_drain<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.drain, n.rank, n.order);
+    else (c.kind.cap ? k_dk_rank<true> : k_dk_rank<false>)<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.capacity, n.rank, n.order);
     dk_propose(c, budget, thorough, r, c.d_cnt + i);
     c.launches += 2;
     if (c.kind.exchange) {
@@ -829,16 +905,17 @@ int dk_rounds(const std::string &fn, DkCall &c, int max_rounds) {
     return KAO_OK;
 }
 
-// the peaks, the bound (the highest of three terms, the lowest term on ties) and the status, by bytes; returns the term
-int dk_outputs_bytes(const u64 *ctl, const DkArgs &out) {
-    const uint64_t terms[3] = {(uint64_t)ctl[D_MAXSIZE], ((uint64_t)ctl[D_TOTAL] + (uint64_t)out.B - 1) / (uint64_t)out.B, out.move_leaders ? 0 : (uint64_t)ctl[D_FIXED]};
+// the peaks, the bound (the highest of three terms, the lowest term on ties) and the status, by bytes; returns the term.  live = the
+// brokers that share the bytes: all of them, or (draining) the ones that stay, and then the peak is proven only with nothing left
+int dk_outputs_bytes(const u64 *ctl, const DkArgs &out, int live) {
+    const uint64_t terms[3] = {(uint64_t)ctl[D_MAXSIZE], ((uint64_t)ctl[D_TOTAL] + (uint64_t)live - 1) / (uint64_t)live, out.move_leaders ? 0 : (uint64_t)ctl[D_FIXED]};
     int which = 0;
     for (int i = 1; i < 3; ++i)
         if (terms[i] > terms[which]) which = i;
     *out.peak_before = ctl[D_PEAK0];
     *out.peak_after = ctl[D_PEAK1];
     *out.lower_bound = terms[which];
-    *out.status = ctl[D_PEAK1] == terms[which] ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
+    *out.status = ctl[D_PEAK1] == terms[which] && ctl[D_NLEFT] == 0 ? KAO_STATUS_OPTIMAL_PROVEN : KAO_STATUS_FEASIBLE_BOUND_GAP;
     return which;
 }
 
@@ -861,11 +938,16 @@ int dk_outputs_fractions(const u64 *ctl, const DkCall &c, const DkArgs &out, con
 
 int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
     if (kind.exchange && (kind.budget || kind.cap)) return fail(KAO_ERR_INVALID, fn + "exchange rounds are by bytes, without a budget");
-    const void *outs[] = {a.n_moved, a.bytes_moved, a.peak_before, a.peak_after, a.lower_bound, a.status};
-    int rc = validate_disk(fn, a.B, a.R, a.rack_of, a.P, a.W, a.rows, a.size, outs, 6);
+    if (kind.drain && (kind.budget || kind.cap || kind.exchange)) return fail(KAO_ERR_INVALID, fn + "draining is by bytes, without a budget or exchanges");
+    const void *outs[] = {a.n_moved, a.bytes_moved, a.peak_before, a.peak_after, a.lower_bound, a.status, a.drain, a.n_left, a.bytes_left};   // the last three: draining only
+    int rc = validate_disk(fn, a.B, a.R, a.rack_of, a.P, a.W, a.rows, a.size, outs, kind.drain ? 9 : 6);
     if (rc) return rc;
     DkCall c;
     c.kind = kind;
+    if (kind.drain) {
+        for (int b = 0; b < a.B; ++b) c.n_drain += a.drain[b] != 0;
+        if (c.n_drain == a.B) return fail(KAO_ERR_INVALID, fn + "every broker is draining: no live broker is left");
+    }
     if (kind.cap && (rc = dk_check_capacity(fn, a.B, a.cap, c))) return rc;
     if (kind.exchange && (rc = dkx_build_order(fn, a.B, a.P, a.size, c))) return rc;
     if ((rc = require_init())) return rc;
@@ -874,7 +956,7 @@ int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
     const int B = a.B, P = a.P;
     hipStream_t st = c.st;
     if (P) {
-        k_dk_init<<<c.pblocks, kDkThreads, 0, st>>>(n, c.d_fixed);
+        (kind.drain ? k_dk_init<true> : k_dk_init<false>)<<<c.pblocks, kDkThreads, 0, st>>>(n, c.d_fixed);
         ++c.launches;
     }
     k_dk_peak0<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_fixed, c.d_load0);
@@ -882,7 +964,7 @@ int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
     HIP_TRY(hipGetLastError());
     if (P) {
         if ((rc = dk_rounds(fn, c, a.max_rounds))) return rc;
-        k_dk_finish<<<c.pblocks, kDkThreads, 0, st>>>(n);
+        (kind.drain ? k_dk_finish<true> : k_dk_finish<false>)<<<c.pblocks, kDkThreads, 0, st>>>(n);
         ++c.launches;
     }
     k_dk_peak1<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_load0);
@@ -901,12 +983,18 @@ int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
 
     *a.n_moved = (int32_t)ctl[D_NMOVED];
     *a.bytes_moved = ctl[D_BYTES];
-    const int which = kind.cap ? dk_outputs_fractions(ctl, c, a, h) : dk_outputs_bytes(ctl, a);
+    const int which = kind.cap ? dk_outputs_fractions(ctl, c, a, h) : dk_outputs_bytes(ctl, a, B - c.n_drain);
+    if (kind.drain) {
+        *a.n_left = (int32_t)ctl[D_NLEFT];
+        *a.bytes_left = ctl[D_BLEFT];
+    }
     if (int64_t *stats = a.stats) {
         stats[0] = c.rounds; stats[1] = (int64_t)ctl[D_MOVES]; stats[2] = c.props; stats[3] = c.launches; stats[4] = (int64_t)ctl[D_ROWS];
         stats[5] = c.more ? 1 : 0; stats[6] = which; stats[7] = (int64_t)ctl[D_BROKERS];
         if (kind.exchange) {
             stats[8] = c.x_rounds; stats[9] = (int64_t)ctl[D_XCH]; stats[10] = c.x_props; stats[11] = (int64_t)ctl[D_XPEAK];
+        } else if (kind.drain) {
+            stats[8] = (int64_t)ctl[D_DRAINED]; stats[9] = (int64_t)ctl[D_LASTDRAIN];
         } else if (kind.budget || kind.cap) {   // by utilisation without a budget: both 0
             stats[8] = kind.budget ? (int64_t)ctl[D_REFUSED] : 0; stats[9] = c.open ? 1 : 0;
             if (kind.cap) stats[10] = c.thorough_rounds;
@@ -953,4 +1041,13 @@ extern "C" int kao_balance_disk_exchange(int32_t n_brokers, int32_t n_racks, con
     return balance_disk({false, false, true}, "kao_balance_disk_exchange: ",
                         {n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run,
                          n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats});
+}
+
+extern "C" int kao_balance_disk_drain(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                                      const uint64_t *size, const uint8_t *drain, int32_t max_per_rack, int32_t move_leaders, uint64_t min_gain,
+                                      int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before, uint64_t *peak_after,
+                                      uint64_t *lower_bound, int32_t *n_left, uint64_t *bytes_left, int32_t *status, int64_t stats[10]) {
+    return balance_disk({false, false, false, true}, "kao_balance_disk_drain: ",
+                        {n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run,
+                         n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats, drain, n_left, bytes_left});
 }

@@ -109,15 +109,19 @@ __device__ __forceinline__ void descent_bid(u64 *word, u64 key) {
 // ---- the all-pairs rank of the descents over all brokers: how many brokers x are AHEAD of b, all pairs tiled through LDS.  By load:
 // load[x] > mine, mine = load[b].  Cap, by utilisation: load[x] * mcap > mine * capacity[x], mcap = capacity[b]; loads and capacities
 // stay below 2^62, so the products fit 128 bits.  Ties: x < b.  Every lane of a workgroup of T calls it (two barriers per tile); a
-// lane with b >= B passes mine = 0, mcap = 1 and drops the result.  Static LDS: 8 T bytes, 16 T with Cap.
-template <int T, bool Cap>
-__device__ __forceinline__ int rank_ahead(int B, int b, u64 mine, u64 mcap, const u64 *__restrict__ load, const u64 *__restrict__ capacity) {
+// lane with b >= B passes mine = 0, mcap = 1 and drops the result.  Static LDS: 8 T bytes, 16 T with Cap.  First (by load only):
+// the brokers with first[x] != 0 rank before all others; bit 63 of a tile entry carries the flag (the loads stay below 2^62), and
+// `mine` comes with it set for such a b.
+template <int T, bool Cap, bool First = false>
+__device__ __forceinline__ int rank_ahead(int B, int b, u64 mine, u64 mcap, const u64 *__restrict__ load, const u64 *__restrict__ capacity,
+                                          const uint8_t *__restrict__ first = nullptr) {
+    static_assert(!(Cap && First), "a first group is ranked by load only");
     __shared__ u64 tile[T], tcap[Cap ? T : 1];   // (tcap is never touched without Cap, and takes no LDS then)
     int r = 0;
     for (int base = 0; base < B; base += T) {
         const int cnt = min(T, B - base);
         if ((int)threadIdx.x < cnt) {
-            tile[threadIdx.x] = load[base + threadIdx.x];
+            tile[threadIdx.x] = load[base + threadIdx.x] | (First && first[base + threadIdx.x] ? 1ull << 63 : 0);
             if (Cap) tcap[threadIdx.x] = capacity[base + threadIdx.x];
         }
         __syncthreads();

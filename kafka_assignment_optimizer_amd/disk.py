@@ -17,6 +17,11 @@ brokers do not have equal disks.  The report line then ends in the three ratios 
 --exchange goes on from the move-stable state with exchanges: two replicas of different partitions trade places across a broker pair
 (kao_balance_disk_exchange, section 4u).  By bytes only: it is refused together with --max-bytes, --capacities and
 --default-capacity.  The report line then ends in the peak the moves alone reach and the exchange counts.
+--drain ID[,ID...] names brokers of --broker-list that are to end empty (kao_balance_disk_drain, section 4w): their replicas leave
+whatever the gain, slot 0 and size 0 included, nothing moves onto them, and the live brokers are balanced around what arrives.  By
+bytes only: refused together with --max-bytes, --capacities, --default-capacity and --exchange.  The report line then ends in the
+draining brokers, their bytes before and after, the drain moves and what is left, and one line follows per replica that has no
+admissible live broker; the exit status is then 3, after every file is written.
 """
 from __future__ import annotations
 
@@ -38,6 +43,7 @@ from .solver import STATUS_NAMES, _check
 STAT_KEYS = ("rounds", "moves", "proposals", "launches", "rows_changed", "stopped_by_max_rounds", "bound_term", "brokers_changed")
 BUDGET_STAT_KEYS = STAT_KEYS + ("refused", "budget_bound")   # kao_balance_disk_budget
 CAPACITY_STAT_KEYS = BUDGET_STAT_KEYS + ("thorough_rounds",)   # kao_balance_disk_capacity
+DRAIN_STAT_KEYS = STAT_KEYS + ("drain_moves", "last_drain_round")   # kao_balance_disk_drain
 EXCHANGE_STAT_KEYS = STAT_KEYS + ("exchange_rounds", "exchanges", "exchange_proposals", "peak_of_moves")   # kao_balance_disk_exchange (section 4u)
 BOUND_TERMS = ("largest_partition", "mean_load", "fixed_leaders", "integrality")
 
@@ -63,6 +69,12 @@ class DiskResult:
     exchanges: Optional[int] = None
     exchange_proposals: Optional[int] = None
     peak_of_moves: Optional[int] = None      # the peak at the start of the first exchange round (what kao_balance_disk ends at), 0 without one
+    # with drain (kao_balance_disk_drain): stats is int64[10] (DRAIN_STAT_KEYS); None otherwise
+    drain: Optional[np.ndarray] = None       # [n_brokers] uint8: != 0 for a draining broker
+    n_left: Optional[int] = None             # replicas still on draining brokers: with stats[5] == 0 none of them has an admissible live broker
+    bytes_left: Optional[int] = None
+    drain_moves: Optional[int] = None        # stats[8]
+    last_drain_round: Optional[int] = None   # stats[9]: the last round (from 1) that applied a drain move
 
 
 @dataclass
@@ -71,6 +83,7 @@ class DiskPlan:
     input: FailoverInput
     size: np.ndarray                                                           # [P] uint64 per row
     entries: List[Tuple[str, int, List[int]]] = field(default_factory=list)    # (topic, partition, replicas as broker ids) of the changed rows
+    left: List[Tuple[str, int, int, str]] = field(default_factory=list)        # with drain: (topic, partition, broker id, reason) per replica left
 
     @property
     def document(self) -> dict:
@@ -115,42 +128,102 @@ def capacity_of(broker_ids: Sequence[int], capacities: Dict[int, object], defaul
     return np.array([table.get(int(b), default_capacity) for b in broker_ids], dtype=object)
 
 
-def _checked_max_bytes(exchange: bool, max_bytes, capacity) -> Optional[int]:
-    """max_bytes as the C call takes it (None without one), after the refusal of exchange together with a budget or capacities."""
+def _drain_buffer(drain, n_brokers: int) -> np.ndarray:
+    """drain as the C call takes it: one flag per broker index, not all of them set; a ValueError otherwise."""
+    flags = np.asarray(drain).reshape(-1)
+    if len(flags) != int(n_brokers):
+        raise ValueError(f"drain must hold one flag per broker ({n_brokers}), got {len(flags)}")
+    out = np.ascontiguousarray(flags != 0, dtype=np.uint8)
+    if len(out) and out.all():
+        raise ValueError("drain: every broker is draining, no live broker is left")
+    return out
+
+
+def drain_flags(broker_ids: Sequence[int], drain_ids: Sequence[int]) -> np.ndarray:
+    """drain[b] over `broker_ids` from the ids of the draining brokers; an unknown id, a duplicate or all brokers draining is a
+    ValueError."""
+    index = {int(b): i for i, b in enumerate(broker_ids)}
+    out = np.zeros(len(index), dtype=np.uint8)
+    for d in drain_ids:
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or int(d) not in index:
+            raise ValueError(f"--drain: broker {d} is not in the broker list")
+        if out[index[int(d)]]:
+            raise ValueError(f"--drain: broker {d} is named twice")
+        out[index[int(d)]] = 1
+    if len(out) and out.all():
+        raise ValueError("--drain: every broker is draining, no live broker is left")
+    return out
+
+
+def _checked_max_bytes(exchange: bool, max_bytes, capacity, drain=None) -> Optional[int]:
+    """max_bytes as the C call takes it (None without one), after the refusal of exchange together with a budget or capacities and of
+    drain together with any of the three."""
     if exchange and (max_bytes is not None or capacity is not None):
         raise ValueError("exchange=True works by bytes only: not together with max_bytes or capacity")
+    if drain is not None and (exchange or max_bytes is not None or capacity is not None):
+        raise ValueError("drain works by bytes only: not together with max_bytes, capacity or exchange")
     return None if max_bytes is None else _budget(max_bytes)
 
 
 def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0,
-                        max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False) -> DiskResult:
+                        max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False,
+                        drain=None) -> DiskResult:
     """kao_balance_disk on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); size[p] is the bytes of one replica of
     row p.  With max_bytes (0..2^64-1) it is kao_balance_disk_budget: the moves copy at most that many bytes.  With capacity (one
     value >= 1 per broker index) it is kao_balance_disk_capacity: the peak of S(b) / capacity[b] is what the moves lower.  With
     exchange=True it is kao_balance_disk_exchange: exchanges go on from the move-stable state (by bytes only: a ValueError together
-    with max_bytes or capacity)."""
-    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity)
+    with max_bytes or capacity).  With drain (one flag per broker index, != 0: this broker is to end empty) it is
+    kao_balance_disk_drain (a ValueError together with any of the other three, or with every flag set)."""
+    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity, drain)
     cbuf = None if capacity is None else _capacity_buffer(capacity, n_brokers)
+    dbuf = None if drain is None else _drain_buffer(drain, n_brokers)
     r, flat, P, W = dense_rows(rows)
     rk = _rack_buffer(rack_of, n_brokers)
     sbuf = weight_buffer(size, P, min_gain)
     name, n_stats, extra = (("kao_balance_disk_capacity", 11, [(1 << 64) - 1 if max_bytes is None else max_bytes]) if cbuf is not None   # with or without a budget
-                            else ("kao_balance_disk_exchange", 12, []) if exchange else ("kao_balance_disk", 8, []) if max_bytes is None
+                            else ("kao_balance_disk_exchange", 12, []) if exchange else ("kao_balance_disk_drain", 10, []) if dbuf is not None
+                            else ("kao_balance_disk", 8, []) if max_bytes is None
                             else ("kao_balance_disk_budget", 10, [max_bytes]))
     stats = np.zeros(n_stats, dtype=np.int64)
-    n, status, moved = C.c_int32(0), C.c_int32(0), C.c_uint64(0)
+    n, status, moved, n_left, bytes_left = C.c_int32(0), C.c_int32(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
     before, after, bound = ((C.c_uint64 * 2)() for _ in range(3))   # {numerator, denominator} by utilisation; the calls by bytes write the first word only
     head = [int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
-            sbuf.ctypes.data_as(C.POINTER(C.c_uint64))] + ([] if cbuf is None else [cbuf.ctypes.data_as(C.POINTER(C.c_uint64))])
-    tail = [int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), before, after, bound, C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))]
+            sbuf.ctypes.data_as(C.POINTER(C.c_uint64))] + ([] if cbuf is None else [cbuf.ctypes.data_as(C.POINTER(C.c_uint64))]) \
+        + ([] if dbuf is None else [dbuf.ctypes.data_as(C.POINTER(C.c_uint8))])
+    tail = [int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), before, after, bound] + ([] if dbuf is None else [C.byref(n_left), C.byref(bytes_left)]) \
+        + [C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))]
     _check(getattr(_ffi.load(), name)(*head, int(max_per_rack), int(bool(move_leaders)), int(min_gain), *extra, *tail), name)
     more = {}
     if cbuf is not None:
         more = dict(peak_before_capacity=int(before[1]), peak_after_capacity=int(after[1]), lower_bound_den=int(bound[1]))
     elif exchange:
         more = dict(exchange_rounds=int(stats[8]), exchanges=int(stats[9]), exchange_proposals=int(stats[10]), peak_of_moves=int(stats[11]))
+    elif dbuf is not None:
+        more = dict(drain=dbuf, n_left=int(n_left.value), bytes_left=int(bytes_left.value), drain_moves=int(stats[8]), last_drain_round=int(stats[9]))
     return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before[0]), peak_after=int(after[0]),
                       lower_bound=int(bound[0]), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes, **more)
+
+
+LEFT_REASONS = ("row_holds_every_live_broker", "rack_rule", "max_rounds")
+
+
+def left_replicas(rows, rack_of, drain, max_per_rack: int = 0) -> List[Tuple[int, int, str]]:
+    """(row, slot, reason) of every replica of `rows` on a draining broker, by row and slot.  The reason: its row holds every live broker;
+    or the rack rule forbids every other one; or a live broker would take it ("max_rounds": only a call stopped by max_rounds leaves
+    such a replica)."""
+    rows = np.asarray(rows)
+    rk = np.asarray(rack_of, dtype=np.int64)
+    live = np.nonzero(np.asarray(drain) == 0)[0]
+    out = []
+    for p, row in enumerate(rows.tolist()):
+        held = [b for b in row if b != NONE]
+        for j, a in enumerate(held):
+            if not drain[a]:
+                continue
+            outside = [c for c in live if c not in held]
+            ok = [c for c in outside if max_per_rack <= 0 or rk[c] == rk[a] or sum(rk[b] == rk[c] for b in held) < max_per_rack]
+            out.append((p, j, LEFT_REASONS[0] if not outside else LEFT_REASONS[1] if not ok else LEFT_REASONS[2]))
+    return out
 
 
 def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int] = None) -> np.ndarray:
@@ -161,41 +234,56 @@ def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int
 
 
 def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0,
-               dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False) -> DiskPlan:
+               dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False, drain=None) -> DiskPlan:
     """kao_balance_disk on a FailoverInput, size[p] per row of it; the entries are the rows that changed (none with dry_run).  With
     max_bytes it is kao_balance_disk_budget; with capacity (per broker index of fi) kao_balance_disk_capacity; with exchange
-    kao_balance_disk_exchange."""
+    kao_balance_disk_exchange; with drain (flags per broker index of fi) kao_balance_disk_drain."""
     res = balance_disk_arrays(fi.rows, len(fi.broker_ids), fi.rack_of, len(fi.rack_names), size, max_per_rack, move_leaders, min_gain, max_rounds,
-                              dry_run, max_bytes, capacity, exchange)
+                              dry_run, max_bytes, capacity, exchange, drain)
     changed = np.nonzero((res.rows != fi.rows).any(axis=1))[0]
     entries = [(fi.keys[p][0], fi.keys[p][1], [int(fi.broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
-    return DiskPlan(result=res, input=fi, size=np.asarray(size, dtype=np.uint64), entries=entries)
+    left = []
+    if drain is not None and not dry_run:   # (with dry_run the rows are the input's: the counts are reported, the replicas are not named)
+        left = [(fi.keys[p][0], fi.keys[p][1], int(fi.broker_ids[res.rows[p][j]]), why) for p, j, why in left_replicas(res.rows, fi.rack_of, res.drain, max_per_rack)]
+    return DiskPlan(result=res, input=fi, size=np.asarray(size, dtype=np.uint64), entries=entries, left=left)
 
 
 def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, default_size: Optional[int] = None, max_per_rack: int = 0,
                  move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None,
-                 capacity=None, default_capacity: Optional[int] = None, exchange: bool = False) -> DiskPlan:
+                 capacity=None, default_capacity: Optional[int] = None, exchange: bool = False, drain: Optional[Sequence[int]] = None) -> DiskPlan:
     """kao_balance_disk on a reassignment document with `broker_list` and `racks` ({broker id: rack name}).  `sizes` is
     {(topic, partition): bytes}, or a kafka-log-dirs / sizes document or text (waves.parse_sizes).  plan.document is the
     reassignment document of the changed rows.  With max_bytes the moves copy at most that many bytes (kao_balance_disk_budget).
     With capacity, a {broker id: bytes} mapping (default_capacity for the brokers it does not name) or an array in the order of
     `broker_list`, the moves lower the peak utilisation (kao_balance_disk_capacity).  With exchange=True exchanges go on from the
-    move-stable state (kao_balance_disk_exchange; a ValueError together with max_bytes or capacity)."""
+    move-stable state (kao_balance_disk_exchange; a ValueError together with max_bytes or capacity).  With drain, the ids of brokers of
+    `broker_list` that are to end empty, it is kao_balance_disk_drain (a ValueError together with any of the other three, for an id
+    outside the list, a duplicate, or every broker)."""
     from .waves import parse_sizes
-    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity)
+    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity, drain)
+    if drain is not None:
+        drain_flags(broker_list, drain)   # the refusals, before anything else is read
     fi = parse_current(doc, broker_list, racks)
+    flags = None if drain is None else drain_flags(fi.broker_ids, drain)   # over the index the rows use
     if isinstance(capacity, dict):
         capacity = capacity_of(fi.broker_ids, capacity, default_capacity)
     if not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
         sizes = parse_sizes(sizes)
-    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes, capacity, exchange)
+    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes, capacity, exchange, flags)
 
 
 def report_lines(plan: DiskPlan) -> List[str]:
     """The --report text, line for line as cli/kao-disk prints it."""
     res, s = plan.result, plan.result.stats
     total = int(sum(int(x) * int((row != NONE).sum()) for x, row in zip(plan.size, plan.input.rows)))
-    return [f"disk: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
+    tail = []
+    if res.drain is not None:   # the draining brokers, their bytes before and after, the drain moves, what is left; then one line per replica left
+        ids = [int(b) for b, d in zip(plan.input.broker_ids, res.drain) if d]
+        before = int(sum(int(x) * int(sum(1 for b in row if b != NONE and res.drain[b])) for x, row in zip(plan.size, plan.input.rows)))
+        tail = [f" draining={','.join(str(b) for b in ids)} drain_bytes_before={before} drain_bytes_after={res.bytes_left} drain_moves={res.drain_moves} "
+                f"last_drain_round={res.last_drain_round} replicas_left={res.n_left} bytes_left={res.bytes_left}"]
+        tail += [f"disk: left {t}-{p} broker={b} reason={why}" for t, p, b, why in plan.left]
+    return _with_tail([f"disk: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
             f"bound_term={BOUND_TERMS[int(s[6])]} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
             f"rows_changed={s[4]} brokers_changed={s[7]} rounds={s[0]} moves={s[1]} launches={s[3]}"
             + ("" if res.max_bytes is None else f" max_bytes={res.max_bytes} bytes_left={res.max_bytes - res.bytes_moved} refused={s[8]} budget_bound={s[9]}")
@@ -203,7 +291,12 @@ def report_lines(plan: DiskPlan) -> List[str]:
                f"peak_after_ppm={res.peak_after * 10 ** 6 // res.peak_after_capacity} lower_bound_ppm={res.lower_bound * 10 ** 6 // res.lower_bound_den} "
                f"thorough_rounds={s[10]}")
             + ("" if res.exchanges is None else f" peak_of_moves={res.peak_of_moves} exchange_rounds={res.exchange_rounds} exchanges={res.exchanges} "
-               f"exchange_proposals={res.exchange_proposals}")]
+               f"exchange_proposals={res.exchange_proposals}")], tail)
+
+
+def _with_tail(lines: List[str], tail: List[str]) -> List[str]:
+    """The report line with the first of `tail` appended to it, the others as lines of their own."""
+    return lines if not tail else [lines[0] + tail[0]] + tail[1:]
 
 
 def _capacities(arg: str) -> dict:
@@ -215,7 +308,8 @@ def _capacities(arg: str) -> dict:
 
 
 def main(argv=None) -> int:
-    """Python twin of cli/kao-disk: same flags, same bytes, same exit status (0 ok, 1 error, 2 usage)."""
+    """Python twin of cli/kao-disk: same flags, same bytes, same exit status (0 ok, 1 error, 2 usage, 3 with --drain: replicas are left
+    on a draining broker, every file is written)."""
     from .leaders import plan_text
     from .waves import MAX_SIZE, parse_bytes, parse_sizes
     ap = argparse.ArgumentParser(prog="kao-disk", description="replica moves that lower the peak bytes per broker")
@@ -233,15 +327,27 @@ def main(argv=None) -> int:
     ap.add_argument("--default-capacity", default=None, help="bytes of disk of the brokers --capacities does not name")
     ap.add_argument("--exchange", action="store_true", help="go on from the move-stable state with exchanges of two replicas across a broker pair "
                     "(not with --max-bytes, --capacities or --default-capacity)")
+    ap.add_argument("--drain", default=None, help="brokers of --broker-list that are to end empty, CSV (not with --max-bytes, --capacities, --default-capacity "
+                    "or --exchange); exit status 3 when a replica has no admissible live broker and stays")
     ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
-    min_gain, default_size, max_bytes, capacity = 0, None, None, None
+    min_gain, default_size, max_bytes, capacity, drain_ids = 0, None, None, None, None
     if a.exchange and (a.max_bytes is not None or a.capacities is not None or a.default_capacity is not None):
         ap.error("--exchange works by bytes only: not together with --max-bytes, --capacities or --default-capacity")
+    if a.drain is not None and (a.exchange or a.max_bytes is not None or a.capacities is not None or a.default_capacity is not None):
+        ap.error("--drain works by bytes only: not together with --max-bytes, --capacities, --default-capacity or --exchange")
     try:
+        if a.drain is not None:   # an unknown id, a duplicate or every broker is a usage error
+            ids = [t.strip() for t in a.drain.split(",") if t.strip()]
+            if not ids or any(not t.isdigit() for t in ids):
+                raise ValueError("--drain needs broker ids, CSV")
+            drain_ids = [int(t) for t in ids]
+            listed = [b.strip() for b in a.broker_list.split(",") if b.strip()]
+            if all(b.lstrip("-").isdigit() for b in listed):   # (a list that does not parse is reported where it always is, below)
+                drain_flags([int(b) for b in listed], drain_ids)
         if a.capacities is not None or a.default_capacity is not None:   # a broker without a capacity is a usage error
             default_capacity = None if a.default_capacity is None else parse_bytes(a.default_capacity)
             try:
@@ -265,9 +371,10 @@ def main(argv=None) -> int:
         fi = parse_current(doc, [int(b) for b in a.broker_list.split(",") if b], _racks(a.racks))   # input errors before the device is touched
         with open(a.sizes) as f:
             size = sizes_of(fi.keys, parse_sizes(f.read()), default_size)
+        drain = None if drain_ids is None else drain_flags(fi.broker_ids, drain_ids)   # over the index the rows use
         from .solver import init
         init(a.device)
-        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes, capacity, a.exchange)
+        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes, capacity, a.exchange, drain)
         if a.report:
             for line in report_lines(plan):
                 print(line, file=sys.stderr)
@@ -276,7 +383,7 @@ def main(argv=None) -> int:
     except Exception as e:  # noqa: BLE001 -- reported, exit status 1
         print(f"kao-disk: {e}", file=sys.stderr)
         return 1
-    return 0
+    return 3 if plan.result.n_left else 0
 
 
 if __name__ == "__main__":

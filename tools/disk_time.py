@@ -18,7 +18,11 @@ of --reps after a warm-up, with dry_run.  The cases `small` (12 brokers x 1,200 
 10,000, 10 racks, max_per_rack 1) of tests/disk_ref.py's log-normal family may be named in --cases beside the two above.  A line
 carries, as plain call -> this call: peak / bound, bytes moved, rounds (move + exchange), launches and wall time, then the exchanges
 and the cost of one exchange round against one move round (the extra wall time over the exchange rounds; the plain call's wall time
-over its rounds).  --write appends the lines to profiles/disk_x_time.txt.  --max-rounds N caps the rounds of both calls."""
+over its rounds).  --write appends the lines to profiles/disk_x_time.txt.  --max-rounds N caps the rounds of both calls.
+--drain N[,N..] times kao_balance_disk and kao_balance_disk_drain in one process on the same rows, the N
+heaviest brokers draining, once per N.  A line carries the draining brokers' largest replica count (stats[9] is at least that), the
+rounds, drain moves (stats[8]), the last round with a drain move (stats[9]), what is left, peak / bound, bytes moved and, as plain call
+-> this call, rounds, launches and wall time.  --write appends the lines to profiles/disk_drain_time.txt."""
 import argparse
 import json
 import os
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--max-bytes-pct", default=None, help="CSV of budgets in percent of the bytes stored, or `none`: times kao_balance_disk_budget")
     ap.add_argument("--capacity", default=None, choices=["4:1", "equal"], help="times kao_balance_disk_capacity with this capacity vector")
     ap.add_argument("--exchange", action="store_true", help="times kao_balance_disk and kao_balance_disk_exchange side by side")
+    ap.add_argument("--drain", default=None, help="CSV of N: times kao_balance_disk and kao_balance_disk_drain side by side, the N heaviest brokers draining")
     ap.add_argument("--max-rounds", type=int, default=0)
     ap.add_argument("--write", action="store_true", help="write the lines to profiles/disk_time.txt (disk_budget_time.txt with --max-bytes-pct) as well")
     a = ap.parse_args()
@@ -52,13 +57,13 @@ def main():
         rng = np.random.default_rng(seed)
         return np.maximum(1, np.round(np.exp(rng.normal(np.log(2.0 ** 20), sigma, P)))).astype(np.int64)
 
-    def timed(rows, B, rack_of, R, size, cap, max_bytes, capacity=None, exchange=False):
+    def timed(rows, B, rack_of, R, size, cap, max_bytes, capacity=None, exchange=False, drain=None):
         args = (rows, B, rack_of, R, size, cap, not a.keep_leaders, 0, a.max_rounds)
-        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange)   # warm-up
+        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange, drain=drain)   # warm-up
         ms = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange)
+            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange, drain=drain)
             ms.append(round(1e3 * (time.perf_counter() - t0), 3))
         return res, ms
 
@@ -80,6 +85,33 @@ def main():
         for sigma in (float(s) for s in a.sigmas.split(",")):
             size = sizes(len(rows), sigma, 11)
             total = int((size[:, None] * (rows != 0xFFFF)).sum())
+            if a.drain is not None:
+                plain, pms = timed(rows, B, rack_of, R, size, cap, None)
+                S = np.zeros(B, dtype=np.int64)
+                held = rows != 0xFFFF
+                np.add.at(S, rows[held], np.broadcast_to(size[:, None], rows.shape)[held])
+                for n in (int(x) for x in a.drain.split(",")):
+                    ids = np.lexsort((np.arange(B), -S))[:n]   # the n heaviest, the lower index on ties
+                    flags = np.zeros(B, dtype=np.uint8)
+                    flags[ids] = 1
+                    res, dms = timed(rows, B, rack_of, R, size, cap, None, drain=flags)
+                    pm, dm = float(np.median(pms)), float(np.median(dms))
+                    lb = max(res.lower_bound, 1)
+                    line = {"workload": name, "sigma": sigma, "brokers": B, "racks": R, "partitions": len(rows), "max_per_rack": cap, "move_leaders": not a.keep_leaders,
+                            "max_rounds": a.max_rounds, "draining": n, "drain_ids": [int(b) for b in ids], "drain_replicas_max": int(max((rows == b).sum() for b in ids)),
+                            "drain_replicas": int(sum((rows == b).sum() for b in ids)), "status": res.status, "rounds": [int(plain.stats[0]), int(res.stats[0])],
+                            "drain_moves": res.drain_moves, "last_drain_round": res.last_drain_round, "replicas_left": res.n_left, "bytes_left": res.bytes_left,
+                            "peak_before": res.peak_before, "peak_after": [plain.peak_after, res.peak_after], "lower_bound": [plain.lower_bound, res.lower_bound],
+                            "peak_over_bound": [round(plain.peak_after / max(plain.lower_bound, 1), 5), round(res.peak_after / lb, 5)],
+                            "replicas_moved": [plain.n_moved, res.n_moved], "bytes_moved": [plain.bytes_moved, res.bytes_moved], "bytes_total": total,
+                            "moves": [int(plain.stats[1]), int(res.stats[1])], "launches": [int(plain.stats[3]), int(res.stats[3])],
+                            "stopped_by_max_rounds": [int(plain.stats[5]), int(res.stats[5])], "wall_ms_median": [round(pm, 3), round(dm, 3)], "wall_ms": [pms, dms]}
+                    lines.append(json.dumps(line))
+                    print(lines[-1], flush=True)
+                    if a.write:
+                        with open(os.path.join(ROOT, "profiles", "disk_drain_time.txt"), "a") as f:
+                            f.write(lines[-1] + "\n")
+                continue
             if a.exchange:
                 plain, pms = timed(rows, B, rack_of, R, size, cap, None)
                 res, xms = timed(rows, B, rack_of, R, size, cap, None, exchange=True)
@@ -131,7 +163,7 @@ def main():
                     line["wall_ms"] = ms
                 lines.append(json.dumps(line))
                 print(lines[-1], flush=True)
-    if a.write and not a.exchange:
+    if a.write and not a.exchange and a.drain is None:
         name = "disk_capacity_time.txt" if a.capacity is not None else "disk_time.txt" if a.max_bytes_pct is None else "disk_budget_time.txt"
         with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write("\n".join(lines) + "\n")
