@@ -1,10 +1,12 @@
 // kao-disk -- disk-usage balance: the replica moves that lower the peak of the bytes a broker stores (kao_balance_disk, DESIGN.md
 // section 4m; under --max-bytes kao_balance_disk_budget, section 4n; with --capacities kao_balance_disk_capacity, section 4q; with
-// --exchange kao_balance_disk_exchange, section 4u; with --drain kao_balance_disk_drain, section 4w).
+// --exchange kao_balance_disk_exchange, section 4u; with --drain kao_balance_disk_drain, section 4w; with --replica-band or
+// --count-slack kao_balance_disk_banded, section 4x).
 //
 //   kao-disk --current current.json --broker-list 0,1,2 --racks racks.json --sizes log-dirs.txt [--default-size N]
 //            [--max-per-rack N] [--keep-leaders] [--min-gain BYTES] [--max-bytes BYTES] [--max-rounds N] [--dry-run] --out plan.json
 //            [--capacities caps.json | id:bytes,...] [--default-capacity BYTES] [--exchange] [--drain ID[,ID...]] [--report] [--device D]
+//            [--replica-band LO:HI | --count-slack K]
 //
 // Every other planner counts a replica as one unit or moves no data; this one reads the partition sizes (`kafka-log-dirs --describe`
 // output or a sizes document, as kao-waves reads them) and moves replicas to brokers outside their row until no single move closes a
@@ -29,6 +31,13 @@
 // or --exchange.  The report line then ends in draining, drain_bytes_before, drain_bytes_after, drain_moves, last_drain_round,
 // replicas_left and bytes_left, and one line "disk: left <topic>-<partition> broker=<id> reason=<why>" follows per replica left: its row
 // holds every live broker, the rack rule forbids every other one, or (only when --max-rounds stopped the call) max_rounds.
+// --replica-band LO:HI keeps the number of replicas per broker inside LO..HI while the bytes are balanced: no move goes onto a broker
+// that holds HI replicas or leaves one that holds LO, so a broker outside the band may move toward it and never away.  --count-slack K
+// is the band floor(R/B) - K : ceil(R/B) + K (LO not below 0) for the R replicas on the B brokers of --broker-list.  With --exchange
+// the exchanges, which keep every count, go on under the band.  By bytes only: refused together with --max-bytes, --capacities,
+// --default-capacity or --drain, and the two flags refuse each other.  The report gains one line "disk: replica_band=LO:HI
+// counts_before=MIN..MAX counts_after=MIN..MAX outside_before=N outside_after=N"; a broker outside the band at the end is a warning on
+// stderr and exit status 0: the band never forced anything.
 // All computation happens in libkao.so on the GPU.
 // Exit status: 0 = ok, 1 = error, 2 = usage, 3 = with --drain, replicas are left on a draining broker (every file is written).
 #include <algorithm>
@@ -54,11 +63,13 @@ namespace {
         "                --sizes <kafka-log-dirs output | sizes.json> [--default-size N] [--max-per-rack N] [--keep-leaders]\n"
         "                [--min-gain N[K|M|G|T]] [--max-bytes N[K|M|G|T]] [--max-rounds N] [--dry-run] --out <file> [--report]\n"
         "                [--capacities <caps.json | id:bytes,...>] [--default-capacity N[K|M|G|T]] [--exchange] [--drain ID[,ID...]]\n"
-        "                [--device D]\n"
+        "                [--replica-band LO:HI | --count-slack K] [--device D]\n"
         "--exchange: exchanges of two replicas across a broker pair go on from the move-stable state (by bytes only: not with\n"
         "            --max-bytes, --capacities or --default-capacity)\n"
         "--drain: the named brokers of --broker-list are to end empty (by bytes only: not with --max-bytes, --capacities,\n"
         "            --default-capacity or --exchange)\n"
+        "--replica-band, --count-slack: the replicas per broker stay inside LO..HI, or within K of the mean (by bytes only: not with\n"
+        "            --max-bytes, --capacities, --default-capacity or --drain; with or without --exchange)\n"
         "writes the partitions whose replicas move; exit status: 0 = ok, 1 = error, 2 = usage, 3 = with --drain, replicas are left\n"
         "on a draining broker (no admissible live broker takes them; every file is written)\n");
     std::exit(2);
@@ -76,7 +87,8 @@ std::string ppm(uint64_t num, uint64_t den) {
 
 int main(int argc, char **argv) {
     std::string cur_path, brokers_csv, racks_arg, out_path, sizes_path, caps_arg, drain_csv;
-    int device = 0, max_per_rack = 0, max_rounds = 0;
+    int device = 0, max_per_rack = 0, max_rounds = 0, band_lo = 0, band_hi = 0, slack = 0;
+    bool have_band = false, have_slack = false;
     bool report = false, dry_run = false, keep_leaders = false, have_default = false, have_budget = false, have_caps = false, have_default_cap = false, exchange = false, have_drain = false;
     uint64_t default_size = 0, min_gain = 0, max_bytes = 0, default_cap = 0;
     auto count_arg = [](const std::string &v, const char *msg) {
@@ -95,6 +107,14 @@ int main(int argc, char **argv) {
         else if (a == "--keep-leaders") keep_leaders = true;
         else if (a == "--exchange") exchange = true;
         else if (a == "--drain") { drain_csv = need("--drain"); have_drain = true; }
+        else if (a == "--replica-band") {
+            const std::string v = need("--replica-band");
+            const size_t at = v.find(':');
+            if (at == std::string::npos) usage("--replica-band needs LO:HI, two counts");
+            band_lo = count_arg(v.substr(0, at), "--replica-band needs LO:HI, two counts");
+            band_hi = count_arg(v.substr(at + 1), "--replica-band needs LO:HI, two counts");
+            have_band = true;
+        } else if (a == "--count-slack") { slack = count_arg(need("--count-slack"), "--count-slack needs a count"); have_slack = true; }
         else if (a == "--device") device = std::atoi(need("--device").c_str());
         else if (a == "--report") report = true;
         else if (a == "--default-size") {
@@ -121,6 +141,11 @@ int main(int argc, char **argv) {
     const bool by_capacity = have_caps || have_default_cap;
     if (exchange && (have_budget || by_capacity)) usage("--exchange works by bytes only: not together with --max-bytes, --capacities or --default-capacity");
     if (have_drain && (exchange || have_budget || by_capacity)) usage("--drain works by bytes only: not together with --max-bytes, --capacities, --default-capacity or --exchange");
+    if (have_band && (have_budget || by_capacity || have_drain)) usage("--replica-band works by bytes only: not together with --max-bytes, --capacities, --default-capacity or --drain");
+    if (have_slack && (have_budget || by_capacity || have_drain)) usage("--count-slack works by bytes only: not together with --max-bytes, --capacities, --default-capacity or --drain");
+    if (have_band && have_slack) usage("--replica-band and --count-slack: give one of the two");
+    if (have_band && band_hi < band_lo) usage("--replica-band: HI is below LO");
+    const bool banded = have_band || have_slack;
     std::vector<uint8_t> drain;       // per broker of --broker-list, in its order: != 0 for a draining one
     if (have_drain) {                 // an unknown id, a duplicate or every broker is a usage error
         std::vector<int> ids;
@@ -190,10 +215,20 @@ int main(int argc, char **argv) {
         std::vector<uint16_t> rows = cr.rows;
         int32_t n_moved = 0, status = 0, n_left = 0;
         uint64_t bytes_left = 0, bytes_moved = 0, before = 0, after = 0, bound = 0, before2[2] = {0, 1}, after2[2] = {0, 1}, bound2[2] = {0, 1};
-        int64_t stats[12] = {0};
-        const char *entry = by_capacity ? "kao_balance_disk_capacity: " : have_budget ? "kao_balance_disk_budget: " : exchange ? "kao_balance_disk_exchange: "
+        int32_t counts[4] = {0, 0, 0, 0};
+        int64_t stats[14] = {0};
+        if (have_slack && B > 0) {   // floor(R / B) - K : ceil(R / B) + K over the replicas of the rows
+            long long R = 0;
+            for (uint16_t b : cr.rows) R += b != KAO_NONE;
+            band_lo = (int)std::max(0ll, R / B - slack);
+            band_hi = (int)std::min((R + B - 1) / B + slack, (long long)INT32_MAX);
+        }
+        const char *entry = banded ? "kao_balance_disk_banded: " : by_capacity ? "kao_balance_disk_capacity: " : have_budget ? "kao_balance_disk_budget: " : exchange ? "kao_balance_disk_exchange: "
                             : have_drain ? "kao_balance_disk_drain: " : "kao_balance_disk: ";
-        if (by_capacity) {
+        if (banded)
+            rc = kao_balance_disk_banded(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), band_lo, band_hi, exchange ? 1 : 0, max_per_rack,
+                                         keep_leaders ? 0 : 1, min_gain, max_rounds, dry_run ? 1 : 0, &n_moved, &bytes_moved, &before, &after, &bound, counts, &status, stats);
+        else if (by_capacity) {
             rc = kao_balance_disk_capacity(B, (int)cl.rack_names.size(), cl.rack_of.data(), P, W, rows.data(), size.data(), capacity.data(), max_per_rack,
                                            keep_leaders ? 0 : 1, min_gain, have_budget ? max_bytes : UINT64_MAX, max_rounds, dry_run ? 1 : 0, &n_moved,
                                            &bytes_moved, before2, after2, bound2, &status, stats);
@@ -241,6 +276,9 @@ int main(int argc, char **argv) {
                              ids.c_str(), held, (unsigned long long)bytes_left, (long long)stats[8], (long long)stats[9], n_left, (unsigned long long)bytes_left);
             }
             std::fprintf(stderr, "\n");
+            if (banded)
+                std::fprintf(stderr, "disk: replica_band=%d:%d counts_before=%d..%d counts_after=%d..%d outside_before=%lld outside_after=%lld\n", band_lo, band_hi, counts[0],
+                             counts[1], counts[2], counts[3], (long long)stats[13], (long long)stats[12]);
             for (int p = 0; have_drain && !dry_run && p < P; ++p) {   // one line per replica left, by row and slot, with the reason
                 const uint16_t *row = rows.data() + (size_t)p * W;
                 int k = 0;
@@ -260,6 +298,8 @@ int main(int argc, char **argv) {
                 }
             }
         }
+        if (banded && stats[12] > 0)   // the band never forced anything: a warning, status 0
+            std::fprintf(stderr, "kao-disk: warning: %lld brokers hold a replica count outside the band %d:%d\n", (long long)stats[12], band_lo, band_hi);
         const std::string text = changed_rows_text(cr, rows, cl.brokers);
         std::ofstream f(out_path);
         f << text;

@@ -882,6 +882,43 @@ int kao_balance_disk_drain(int32_t n_brokers, int32_t n_racks, const uint8_t *ra
                            uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t *n_left, uint64_t *bytes_left,
                            int32_t *status, int64_t stats[10] /* may be NULL */);
 
+/* ---- Disk-usage balance inside a replica-count band -----------------------------------------------------------
+ * kao_balance_disk (exchange == 0) or kao_balance_disk_exchange (exchange != 0) that keeps the number of replicas per broker inside
+ * [count_lo, count_hi].  By bytes only: no byte budget, no capacities, no draining brokers.  Everything of those two calls holds (rows,
+ * sizes, S(b), rank, the two walks, the gain test, key, bid, win rule, dry_run, *n_moved / *bytes_moved, the exchange rounds) except
+ * what follows.
+ * COUNT: n(b) = the number of rows that contain b; partitions of size 0 count too.  Like the loads, the counts are taken as they
+ * stand at the round's start.
+ * ADMISSIBLE: a destination c must also have n(c) < count_hi.
+ * MOVABLE: a slot on a is movable only if also n(a) > count_lo.
+ * This is the rack rule's form: the count of a broker never rises above max(count_hi, its input count) and never falls below
+ * min(count_lo, its input count).  A broker that starts above the band can give and cannot receive; one that starts below can receive
+ * and cannot give.  Nothing is forced: a move still needs its gain, so a band the total replica count cannot satisfy is no error, and
+ * the sum over b of max(0, n(b) - count_hi) + max(0, count_lo - n(b)) never rises.
+ * MOVE rounds: key, bid, win and apply are unchanged; a winner also does n(a) -= 1, n(c) += 1.  Winners share no broker, so a count
+ * changes by at most one per round and the test on the counts of the round's start is never overshot.
+ * EXCHANGE rounds (exchange != 0; taken when a round has no move proposal inside the band) are those of kao_balance_disk_exchange,
+ * untouched: an exchange keeps every count, so the band says nothing about it.
+ * END: as in the two calls (the sum of S^2 falls in every round, the peak never rises).  Without a max_rounds stop the end state has no
+ * admissible move inside the band that passes the gain test; with exchange it is exchange-stable as well.
+ * *lower_bound and *status: the three terms of kao_balance_disk, unchanged.  They hold for every state the call can reach, because the
+ * band only removes moves; the bound knows nothing of the band, so a tight band may leave a gap that no plan inside it can close.
+ * count_range = {min_b n(b), max_b n(b)} of the input, then the same two of the final rows.
+ * stats (may be NULL, else 14 words): [0..7] as for kao_balance_disk; [8..11] as for kao_balance_disk_exchange, and 0 when
+ * exchange == 0; [12] the brokers with n(b) outside [count_lo, count_hi] in the final rows, [13] the same of the input.
+ * IDENTITY: with count_lo <= 0 and count_hi >= n_partitions the call gives byte for byte the rows, numbers and stats[0..7] of
+ * kao_balance_disk (the counts are built inside that call's own launches, so stats[3] is equal too), with exchange != 0 those and
+ * stats[8..11] of kao_balance_disk_exchange; stats[12] == stats[13] == 0.
+ * Checks, limits and refusals are those of kao_balance_disk and, with exchange != 0, KAO_DISK_EXCHANGE_MAX_WORDS; and KAO_ERR_INVALID
+ * for count_lo < 0, count_hi < count_lo or count_range == NULL; all before any device is used, the rows untouched on error. */
+int kao_balance_disk_banded(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width,
+                            uint16_t *rows /* [n_partitions*width] in / out */, const uint64_t *size /* [n_partitions] */,
+                            int32_t count_lo, int32_t count_hi, int32_t exchange /* != 0: exchange rounds as well */,
+                            int32_t max_per_rack /* <= 0: no rack rule */, int32_t move_leaders, uint64_t min_gain,
+                            int32_t max_rounds /* <= 0: no limit */, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved,
+                            uint64_t *peak_before, uint64_t *peak_after, uint64_t *lower_bound, int32_t count_range[4],
+                            int32_t *status, int64_t stats[14] /* may be NULL */);
+
 /* ---- Log-dir balance inside each broker ---------------------------------------------------------------------
  * Every planner above treats a broker as one disk; a JBOD broker has several log dirs and dies on the fullest of them.  Broker b
  * owns the dirs dir_start[b] .. dir_start[b+1]-1 of ONE global dir index (CSR; n_dirs = dir_start[n_brokers]; a broker may own no

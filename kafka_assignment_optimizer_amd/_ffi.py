@@ -142,6 +142,9 @@ SIGNATURES = {
     "kao_balance_disk_drain": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_uint8), C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint64), _P(C.c_uint8), C.c_int32,
                                          C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64),
                                          _P(C.c_uint64), _P(C.c_int32), _P(C.c_uint64), _P(C.c_int32), _P(C.c_int64)]),
+    "kao_balance_disk_banded": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_uint8), C.c_int32, C.c_int32, _P(C.c_uint16), _P(C.c_uint64), C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64),
+                                          _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
     "kao_balance_logdirs": (C.c_int, [C.c_int32, _P(C.c_int32), _P(C.c_uint64), C.c_int32, _P(C.c_int32), _P(C.c_uint64), C.c_uint64, C.c_int32, C.c_int32,
                                       _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_int32), _P(C.c_int64)]),
     "kao_place_logdirs": (C.c_int, [C.c_int32, _P(C.c_int32), _P(C.c_uint64), C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_uint64), C.c_int32, C.c_uint64,

@@ -52,6 +52,12 @@
 // its own: a walk never goes below rank D (nothing moves onto a draining broker), a slot whose broker ranks below D is always movable
 // (slot 0 and size 0 included), and its proposal takes c1, else c2, without a gain test.  Key, bid, win and apply are the ones above:
 // the rank in the key puts the drain moves first, and a draining broker gives up one replica a round.  The peak may rise meanwhile.
+//
+// INSIDE A COUNT BAND (kao_balance_disk_banded, section 4x) n(b) = the rows that contain b (size 0 included), taken like the loads as it
+// stands at the round's start.  A destination must also have n(c) < count_hi and a slot on a is movable only with n(a) > count_lo.
+// Winners share no broker, so a count changes by at most one a round: the test on the round's start is never overshot and the winners
+// update n with plain stores.  RANK writes one 16-bit word per broker, rack | full << 8 | floor << 9, which the walks read IN PLACE of
+// rack[c]: a candidate costs what it cost.  The exchange rounds keep every count and are the ones below, untouched.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,7 +77,9 @@ constexpr int kDkThoroughBatch = 4;     // ... of THOROUGH rounds: few of them h
 constexpr int kDkHardRounds = 1 << 26;  // no descent gets here; a guard against an endless loop
 constexpr u64 kDkNoKey = ~0ull;
 constexpr int kDkGrantThreads = 1024;   // k_dk_grant: one workgroup, one rank per lane and chunk
-enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_SPENT, D_REFUSED, D_XCH, D_XPEAK, D_XSEEN, D_DONE, D_DRAINED, D_LASTDRAIN, D_NLEFT, D_BLEFT, D_N = 20 };
+enum { D_PEAK0 = 0, D_PEAK1, D_MOVES, D_MAXSIZE, D_TOTAL, D_FIXED, D_NMOVED, D_BYTES, D_ROWS, D_BROKERS, D_SPENT, D_REFUSED, D_XCH, D_XPEAK, D_XSEEN, D_DONE, D_DRAINED, D_LASTDRAIN, D_NLEFT, D_BLEFT, D_CMIN0, D_CMAX0, D_CMIN1, D_CMAX1, D_OUT0, D_OUT1, D_N = 26 };
+constexpr int kDkFull = 0x100, kDkFloor = 0x200;   // the band's word of a broker: n(b) >= count_hi, n(b) <= count_lo; the rack below them
+constexpr u64 kDkCountTop = 0x7FFFFFFF;             // a minimum of counts travels as the maximum of kDkCountTop - n (ctl starts at 0)
 
 struct DkNet {   // one call; every pointer is device memory
     int P, W, B, cap, first;   // first = the lowest movable slot: 0 with move_leaders, else 1
@@ -94,16 +102,29 @@ struct DkNet {   // one call; every pointer is device memory
     const uint8_t *drain;      // [B] draining only: != 0 for a broker that is to end empty
 };
 
+// inside a count band: the net of the call (DkNet, or DkNetX with exchanges) and the band's own words behind it, so that the kernels of
+// the other calls keep their arguments
+template <class Base>
+struct DkBandNet : Base {
+    int32_t *cnt;              // [B] n(b), kept current by the winners of the move rounds
+    uint16_t *rf;              // [B] rack | kDkFull | kDkFloor as of the round's start, written by k_dk_rank_band
+    int32_t lo, hi;            // the band
+};
+
 // ---- once per call ------------------------------------------------------------------------------------------------------------------
 // loads, the largest size, sum k_p size[p], the bytes of the slot-0 replicas per broker (Drain: per LIVE broker; a draining one's leave)
-template <bool Drain>
-__global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) {
+// (Band: and the counts, one atomic add per replica, size 0 included)
+template <bool Drain, bool Band, class Net>
+__device__ __forceinline__ void dk_init(const Net n, u64 *fixed) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     u64 w = 0, all = 0;
     if (p < n.P) {
         w = n.size[p];
         n.key[p] = kDkNoKey;
         const uint16_t *row = n.rows0 + (size_t)p * n.W;
+        if constexpr (Band) {
+            for (int j = 0; j < n.W && row[j] != KAO_NONE; ++j) atomicAdd(&n.cnt[row[j]], 1);
+        }
         if (w) {
             for (int j = 0; j < n.W; ++j) {
                 const int x = row[j];
@@ -118,8 +139,20 @@ __global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) {
     wave_sum_to(all, &n.ctl[D_TOTAL]);
 }
 
+template <bool Drain>
+__global__ void k_dk_init(DkNet n, u64 *__restrict__ fixed) { dk_init<Drain, false>(n, fixed); }
+__global__ void k_dk_init_band(DkBandNet<DkNet> n, u64 *__restrict__ fixed) { dk_init<false, true>(n, fixed); }
+
+// inside a band, beside either peak: the lowest and the highest count and the brokers outside the band, into ctl[at .. at + 1] and ctl[out]
+__device__ __forceinline__ void dk_count_range(const DkBandNet<DkNet> &n, int b, int at, int out) {
+    const int c = b < n.B ? n.cnt[b] : 0;
+    wave_max_to(b < n.B ? kDkCountTop - (u64)c : 0, &n.ctl[at]);
+    wave_max_to((u64)c, &n.ctl[at + 1]);
+    lane_count_to(b < n.B && (c < n.lo || c > n.hi), &n.ctl[out]);
+}
+
 // the peak before and the largest fixed load; the loads kept for the finish
-__global__ void k_dk_peak0(DkNet n, const u64 *__restrict__ fixed, u64 *__restrict__ load0) {
+__device__ __forceinline__ void dk_peak0(const DkNet &n, const u64 *fixed, u64 *load0) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     u64 s = 0, f = 0;
     if (b < n.B) {
@@ -129,6 +162,12 @@ __global__ void k_dk_peak0(DkNet n, const u64 *__restrict__ fixed, u64 *__restri
     }
     wave_max_to(s, &n.ctl[D_PEAK0]);
     wave_max_to(f, &n.ctl[D_FIXED]);
+}
+
+__global__ void k_dk_peak0(DkNet n, const u64 *__restrict__ fixed, u64 *__restrict__ load0) { dk_peak0(n, fixed, load0); }
+__global__ void k_dk_peak0_band(DkBandNet<DkNet> n, const u64 *__restrict__ fixed, u64 *__restrict__ load0) {
+    dk_peak0(n, fixed, load0);
+    dk_count_range(n, blockIdx.x * blockDim.x + threadIdx.x, D_CMIN0, D_OUT0);
 }
 
 // ---- a round ------------------------------------------------------------------------------------------------------------------------
@@ -155,6 +194,20 @@ __global__ __launch_bounds__(kDkThreads) void k_dk_rank_drain(int B, const u64 *
     if (b < B) {   // ranks are a permutation: r < B
         rank[b] = r;
         order[r] = b;
+    }
+}
+
+// ... inside a count band: the plain rank, and the band's word of the broker from the count as it stands now, before the round's moves
+__global__ __launch_bounds__(kDkThreads) void k_dk_rank_band(int B, const u64 *__restrict__ load, int32_t *__restrict__ rank, int32_t *__restrict__ order,
+                                                             const int32_t *__restrict__ cnt, const uint8_t *__restrict__ rack, uint16_t *__restrict__ rf, int lo, int hi) {
+    const int b = blockIdx.x * kDkThreads + threadIdx.x;
+    const u64 mine = b < B ? load[b] : 0;
+    const int r = rank_ahead<kDkThreads, false>(B, b, mine, 1, load, nullptr);
+    if (b < B) {   // ranks are a permutation: r < B
+        rank[b] = r;
+        order[r] = b;
+        const int c = cnt[b];
+        rf[b] = (uint16_t)(rack[b] | (c >= hi ? kDkFull : 0) | (c <= lo ? kDkFloor : 0));
     }
 }
 
@@ -221,21 +274,28 @@ __device__ __forceinline__ bool dk_gains(const DkNet &n, u64 sa, u64 ca, int c, 
 
 // the first admissible broker among the ranks hi, hi - 1, .., lo; -1 when there is none.  Under a budget the broker must be
 // affordable too: `free` (the size fits what is left, or the replica is a fresh copy), or a broker of the input row.  Gain (THOROUGH):
-// it must pass the gain test by utilisation as well
-template <bool Budget, bool Gain>
-__device__ __forceinline__ int dk_walk(const DkNet &n, const DkRow &row, const DkHome &home, bool free, int hi, int lo, int ra, u64 sa = 0, u64 ca = 0, u64 w = 0) {
+// it must pass the gain test by utilisation as well.  Band: the broker's band word stands in for its rack, and a full broker is passed over
+template <bool Budget, bool Gain, bool Band = false, class Net = DkNet>
+__device__ __forceinline__ int dk_walk(const Net &n, const DkRow &row, const DkHome &home, bool free, int hi, int lo, int ra, u64 sa = 0, u64 ca = 0, u64 w = 0) {
     for (int q = hi; q >= lo; --q) {
         const int c = n.order[q];
-        if (dk_admissible(row, c, n.rack[c], ra, n.cap) && (!Budget || free || dk_home(home, c)) && (!Gain || dk_gains<true>(n, sa, ca, c, w))) return c;
+        if constexpr (Band) {
+            const int word = n.rf[c];
+            if (!(word & kDkFull) && dk_admissible(row, c, word & 0xFF, ra, n.cap)) return c;
+        } else {
+            if (dk_admissible(row, c, n.rack[c], ra, n.cap) && (!Budget || free || dk_home(home, c)) && (!Gain || dk_gains<true>(n, sa, ca, c, w))) return c;
+        }
     }
     return -1;
 }
 
 // Drain: a slot on a broker of rank < n.nd is movable whatever its index and whatever the size, and proposes without a gain test; no walk
 // goes below rank n.nd.  The other slots of a partition with size > 0 are as ever (with n.nd == 0 the proposals are those of <false>)
-template <bool Budget, bool Cap = false, bool Thorough = false, bool Drain = false>
-__global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
+// Band: a slot on a broker at the band's floor is passed over (one word per slot tried), and the walks pass over the full brokers
+template <bool Budget, bool Cap = false, bool Thorough = false, bool Drain = false, bool Band = false>
+__global__ void k_dk_propose(std::conditional_t<Band, DkBandNet<DkNet>, DkNet> n, int r, uint32_t *__restrict__ count) {
     static_assert(!Drain || !(Budget || Cap || Thorough), "draining is by bytes, without a budget");
+    static_assert(!Band || !(Budget || Cap || Thorough || Drain), "the count band is by bytes, without a budget or draining brokers");
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     bool prop = false;
     if (p < n.P) {
@@ -287,6 +347,9 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
                 }
                 if (ra_rank == n.B) break;   // no movable slot is left
                 last = ra_rank;
+                if constexpr (Band) {
+                    if (n.rf[a] & kDkFloor) continue;   // n(a) <= count_lo: not movable
+                }
                 const u64 sa = n.load[a];
                 const bool free = !Budget || fits || !dk_home(home, a);
                 const u64 ca = Cap ? n.capacity[a] : 0;
@@ -294,9 +357,9 @@ __global__ void k_dk_propose(DkNet n, int r, uint32_t *__restrict__ count) {
                 if (Thorough) {
                     c = dk_walk<Budget, true>(n, row, home, free, n.B - 1, ra_rank + 1, ra, sa, ca, w);
                 } else {
-                    c = dk_walk<Budget, false>(n, row, home, free, n.B - 1 - ra_rank, ra_rank + 1, ra);
+                    c = dk_walk<Budget, false, Band>(n, row, home, free, n.B - 1 - ra_rank, ra_rank + 1, ra);
                     if (c < 0 || !dk_gains<Cap>(n, sa, ca, c, w)) {
-                        c = dk_walk<Budget, false>(n, row, home, free, n.B - 1, n.B - ra_rank, ra);
+                        c = dk_walk<Budget, false, Band>(n, row, home, free, n.B - 1, n.B - ra_rank, ra);
                         if (c >= 0 && !dk_gains<Cap>(n, sa, ca, c, w)) c = -1;
                     }
                 }
@@ -534,8 +597,8 @@ __global__ void k_dkx_propose(DkNetX n, int r, const uint32_t *__restrict__ coun
 // the move that lane p proposed with `key`, if it won the round (mine = the round's minkey row): the lowest key at both of its
 // brokers and, under a budget, granted.  No other winner touches a or c, and no other lane writes this row: plain stores.  The exchange
 // call keeps its masks current (a move flips two bits).  *cost, under a budget: +size, 0 or -size (wrapping)
-template <bool Budget, bool X>
-__device__ __forceinline__ bool dk_apply_move(const std::conditional_t<X, DkNetX, DkNet> &n, int p, u64 key, const u64 *mine, u64 *cost) {
+template <bool Budget, bool X, bool Band = false, class Net>
+__device__ __forceinline__ bool dk_apply_move(const Net &n, int p, u64 key, const u64 *mine, u64 *cost) {
     uint16_t *row = n.rows + (size_t)p * n.W;
     const int slot = n.slot[p], a = row[slot], c = n.dest[p];
     bool won = mine[a] == key && mine[c] == key;
@@ -549,6 +612,10 @@ __device__ __forceinline__ bool dk_apply_move(const std::conditional_t<X, DkNetX
         n.load[a] -= w;
         n.load[c] += w;
         row[slot] = (uint16_t)c;
+        if constexpr (Band) {
+            n.cnt[a] -= 1;
+            n.cnt[c] += 1;
+        }
         if constexpr (X) {
             const uint32_t px = n.pos[p];
             const u64 bx = 1ull << (px & 63);
@@ -563,11 +630,14 @@ __device__ __forceinline__ bool dk_apply_move(const std::conditional_t<X, DkNetX
 // the exchange call (X; count, xcount = the round's proposals of the two kinds) the round is whichever kind it is: an exchange round
 // iff it has no move proposal, and ctl[D_DONE] is set once a round has had neither kind.  A winner of an exchange reads only what its
 // proposer stored (an exchange flips four mask bits; a winner alone touches the mask rows of its two brokers).  Drain: a winner whose
-// key carries a rank below n.nd left a draining broker; they are counted, and the last round (from 1) that had one is kept.
-template <bool Budget, bool X, bool Drain = false>
-__global__ void k_dk_apply(std::conditional_t<X, DkNetX, DkNet> n, int r, const uint32_t *__restrict__ count, const uint32_t *__restrict__ xcount) {
+// key carries a rank below n.nd left a draining broker; they are counted, and the last round (from 1) that had one is kept.  Band: the
+// winner of a move also takes one off n(a) and adds one to n(c); an exchange keeps both.
+template <bool Budget, bool X, bool Drain = false, bool Band = false>
+__global__ void k_dk_apply(std::conditional_t<Band, DkBandNet<std::conditional_t<X, DkNetX, DkNet>>, std::conditional_t<X, DkNetX, DkNet>> n, int r,
+                           const uint32_t *__restrict__ count, const uint32_t *__restrict__ xcount) {
     static_assert(!(Budget && X), "exchange rounds are by bytes, without a budget");
     static_assert(!Drain || !(Budget || X), "draining is by bytes, without a budget or exchanges");
+    static_assert(!Band || !(Budget || Drain), "the count band is by bytes, without a budget or draining brokers");
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     {
         u64 *clr = n.mk + (size_t)((r + 1) & 1) * n.B;
@@ -588,7 +658,7 @@ __global__ void k_dk_apply(std::conditional_t<X, DkNetX, DkNet> n, int r, const 
         if (key != kDkNoKey) {
             const u64 *mine = n.mk + (size_t)(r & 1) * n.B;
             if (!isx) {
-                won = dk_apply_move<Budget, X>(n, p, key, mine, &cost);
+                won = dk_apply_move<Budget, X, Band>(n, p, key, mine, &cost);
                 if (Drain) left = won && (int)(key >> 48) < n.nd;
             } else if constexpr (X) {
                 const int slot = n.slot[p], a = n.xsrc[p], c = n.dest[p];
@@ -652,7 +722,7 @@ __global__ void k_dk_finish(DkNet n) {
 }
 
 // the peak after; the brokers whose load changed
-__global__ void k_dk_peak1(DkNet n, const u64 *__restrict__ load0) {
+__device__ __forceinline__ void dk_peak1(const DkNet &n, const u64 *load0) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     u64 s = 0;
     bool ch = false;
@@ -662,6 +732,12 @@ __global__ void k_dk_peak1(DkNet n, const u64 *__restrict__ load0) {
     }
     wave_max_to(s, &n.ctl[D_PEAK1]);
     lane_count_to(ch, &n.ctl[D_BROKERS]);
+}
+
+__global__ void k_dk_peak1(DkNet n, const u64 *__restrict__ load0) { dk_peak1(n, load0); }
+__global__ void k_dk_peak1_band(DkBandNet<DkNet> n, const u64 *__restrict__ load0) {
+    dk_peak1(n, load0);
+    dk_count_range(n, blockIdx.x * blockDim.x + threadIdx.x, D_CMIN1, D_OUT1);
 }
 
 int validate_disk(const std::string &fn, int32_t B, int32_t R, const uint8_t *rack_of, int32_t P, int32_t W, const uint16_t *rows, const uint64_t *size,
@@ -716,9 +792,11 @@ bool frac_integral(const DkFrac &peak, const uint64_t *cap, int B, uint64_t tota
 // (kao_balance_disk_exchange: by bytes, without a budget, as k_dk_apply asserts) PI, the masks and the partition words, the exchange
 // PROPOSE in every round (it returns at once in a round with a move proposal, and after the call has ended) and stats[8..11]; drain
 // (kao_balance_disk_drain: by bytes, without a budget or exchanges) the drain forms of RANK, PROPOSE, APPLY, the init and the finish, the
-// bound over the live brokers, n_left / bytes_left and stats[8..9].  It launches what kao_balance_disk launches, kernel for kernel.
+// bound over the live brokers, n_left / bytes_left and stats[8..9].  It launches what kao_balance_disk launches, kernel for kernel.  band
+// (kao_balance_disk_banded: by bytes, without a budget or draining, with or without exchange) the band forms of INIT, RANK, PROPOSE, APPLY
+// and the two peaks, the counts, count_range and stats[12..13]; again kernel for kernel what the call without a band launches.
 struct DkKind {
-    bool budget, cap, exchange, drain = false;
+    bool budget, cap, exchange, drain = false, band = false;
 };
 
 struct DkArgs {   // the arguments of the C calls in their order (cap, max_bytes where the call has them); the peaks and the bound are two words by utilisation
@@ -726,6 +804,7 @@ struct DkArgs {   // the arguments of the C calls in their order (cap, max_bytes
     int32_t max_per_rack, move_leaders; uint64_t min_gain, max_bytes; int32_t max_rounds, dry_run;
     int32_t *n_moved; uint64_t *bytes_moved, *peak_before, *peak_after, *lower_bound; int32_t *status; int64_t *stats;
     const uint8_t *drain = nullptr; int32_t *n_left = nullptr; uint64_t *bytes_left = nullptr;   // kao_balance_disk_drain only
+    int32_t count_lo = 0, count_hi = 0, *count_range = nullptr;                                  // kao_balance_disk_banded only
 };
 
 struct DkCall {   // one call on the host
@@ -739,6 +818,15 @@ struct DkCall {   // one call on the host
     DkNetX x;                 // the exchange call's; its DkNet part is every call's
     uint32_t *d_cnt;          // [2][kDkBatch] the move proposals of a batch's rounds, then (exchange) their exchange proposals
     u64 *d_fixed, *d_load0;   // [B] the bytes of the slot-0 replicas; the loads of the input
+    int32_t *d_n = nullptr, lo = 0, hi = 0;   // inside a count band: [B] n(b); the band
+    uint16_t *d_rf = nullptr;                 // ... [B] the band words of the round
+    template <class Base>
+    DkBandNet<Base> banded(const Base &net) const {   // the net a band kernel takes
+        DkBandNet<Base> b;
+        static_cast<Base &>(b) = net;
+        b.cnt = d_n; b.rf = d_rf; b.lo = lo; b.hi = hi;
+        return b;
+    }
     unsigned pblocks, bblocks;
     int64_t launches = 0, rounds = 0, props = 0, thorough_rounds = 0, x_rounds = 0, x_props = 0;   // what the host counts
     bool more = false, open = false;   // max_rounds rounds have run and there is more to do; the budget stopped the descent
@@ -776,11 +864,11 @@ int dkx_build_order(const std::string &fn, int B, int P, const uint64_t *size, D
 int dk_open(DkCall &c, const DkArgs &in) {
     const bool X = c.kind.exchange;
     const int B = in.B, P = in.P, PW = P * in.W, N = (int)c.pi.size(), words = (N + 63) / 64;
-    // one arena: ctl u64[D_N] | count u32[2 kDkBatch] | load, fixed u64[B] (zeroed up to here) | mk u64[2B] (all ones) | load0 u64[B] | capacity u64[B] |
+    // one arena: ctl u64[D_N] | count u32[2 kDkBatch] | load, fixed u64[B] | n i32[B] (band; zeroed up to here) | rf u16[B] (band) | mk u64[2B] (all ones) | load0 u64[B] | capacity u64[B] |
     //            rank, order i32[B] | key, size u64[P] | rows, rows0 u16[PW] | dest u16[P] | slot u8[P] | rack u8[B] | grant u8[B] | drain u8[B]
     Carve cv;
-    const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(2 * kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B), zeroed = cv.end(),
-                 o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_cap = cv.take<u64>(c.kind.cap ? B : 0), o_rank = cv.take<int32_t>(B),
+    const size_t o_ctl = cv.take<u64>(D_N), o_cnt = cv.take<uint32_t>(2 * kDkBatch), o_load = cv.take<u64>(B), o_fixed = cv.take<u64>(B),
+                 o_n = cv.take<int32_t>(c.kind.band ? B : 0), zeroed = cv.end(), o_rf = cv.take<uint16_t>(c.kind.band ? B : 0), o_mk = cv.take<u64>(2 * (size_t)B), o_load0 = cv.take<u64>(B), o_cap = cv.take<u64>(c.kind.cap ? B : 0), o_rank = cv.take<int32_t>(B),
                  o_order = cv.take<int32_t>(B), o_key = cv.take<u64>(P), o_size = cv.take<u64>(P), o_rows = cv.take<uint16_t>(PW),
                  o_rows0 = cv.take<uint16_t>(PW), o_dest = cv.take<uint16_t>(P), o_slot = cv.take<uint8_t>(P), o_rack = cv.take<uint8_t>(B),
                  o_grant = cv.take<uint8_t>(c.kind.budget ? B : 0), o_drain = cv.take<uint8_t>(c.kind.drain ? B : 0);
@@ -792,6 +880,7 @@ int dk_open(DkCall &c, const DkArgs &in) {
     const CallBufs &m = c.m;
     hipStream_t st = c.st = m.stream;
     c.d_cnt = m.at<uint32_t>(o_cnt); c.d_fixed = m.at<u64>(o_fixed); c.d_load0 = m.at<u64>(o_load0);
+    c.d_n = m.at<int32_t>(o_n); c.d_rf = m.at<uint16_t>(o_rf); c.lo = in.count_lo; c.hi = in.count_hi;
     c.pblocks = grid_for(P, kDkThreads); c.bblocks = grid_for(B, kDkThreads);
     DkNetX &n = c.x;
     n.P = P; n.W = in.W; n.B = B; n.cap = in.max_per_rack; n.first = in.move_leaders ? 0 : 1; n.min_gain = in.min_gain;
@@ -829,6 +918,10 @@ int dk_open(DkCall &c, const DkArgs &in) {
 
 // PROPOSE: by bytes, or FAST / THOROUGH by utilisation; `budget` is the round's (the probe at the end of a budgeted call runs without)
 void dk_propose(const DkCall &c, bool budget, bool thorough, int r, uint32_t *count) {
+    if (c.kind.band) {
+        k_dk_propose<false, false, false, false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.banded(c.n()), r, count);
+        return;
+    }
     void (*const k)(DkNet, int, uint32_t *) = c.kind.drain ? k_dk_propose<false, false, false, true>
                                               : !c.kind.cap ? (budget ? k_dk_propose<true, false, false> : k_dk_propose<false, false, false>)
                                               : thorough  ? (budget ? k_dk_propose<true, true, true> : k_dk_propose<false, true, true>)
@@ -838,7 +931,9 @@ void dk_propose(const DkCall &c, bool budget, bool thorough, int r, uint32_t *co
 
 // APPLY of round r, whose proposals were counted in column i
 void dk_apply(const DkCall &c, int r, int i) {
-    if (c.kind.exchange) k_dk_apply<false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.x, r, c.d_cnt + i, c.d_cnt + kDkBatch + i);
+    if (c.kind.band && c.kind.exchange) k_dk_apply<false, true, false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.banded(c.x), r, c.d_cnt + i, c.d_cnt + kDkBatch + i);
+    else if (c.kind.band) k_dk_apply<false, false, false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.banded(c.n()), r, nullptr, nullptr);
+    else if (c.kind.exchange) k_dk_apply<false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.x, r, c.d_cnt + i, c.d_cnt + kDkBatch + i);
     else if (c.kind.budget) k_dk_apply<true, false><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
     else if (c.kind.drain) k_dk_apply<false, false, true><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
     else k_dk_apply<false, false><<<c.pblocks, kDkThreads, 0, c.st>>>(c.n(), r, nullptr, nullptr);
@@ -847,7 +942,8 @@ void dk_apply(const DkCall &c, int r, int i) {
 // RANK, PROPOSE and (exchange) the exchange PROPOSE of round r, counted in column i: the head of a round, or all of "is there a proposal?"
 void dk_probe(DkCall &c, bool budget, bool thorough, int r, int i) {
     const DkNet &n = c.n();
-    if (c.kind.drain) k_dk_rank_drain<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.drain, n.rank, n.order);
+    if (c.kind.band) k_dk_rank_band<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.rank, n.order, c.d_n, n.rack, c.d_rf, c.lo, c.hi);
+    else if (c.kind.drain) k_dk_rank_drain<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.drain, n.rank, n.order);
     else (c.kind.cap ? k_dk_rank<true> : k_dk_rank<false>)<<<c.bblocks, kDkThreads, 0, c.st>>>(n.B, n.load, n.capacity, n.rank, n.order);
     dk_propose(c, budget, thorough, r, c.d_cnt + i);
     c.launches += 2;
@@ -939,9 +1035,15 @@ int dk_outputs_fractions(const u64 *ctl, const DkCall &c, const DkArgs &out, con
 int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
     if (kind.exchange && (kind.budget || kind.cap)) return fail(KAO_ERR_INVALID, fn + "exchange rounds are by bytes, without a budget");
     if (kind.drain && (kind.budget || kind.cap || kind.exchange)) return fail(KAO_ERR_INVALID, fn + "draining is by bytes, without a budget or exchanges");
+    if (kind.band && (kind.budget || kind.cap || kind.drain)) return fail(KAO_ERR_INVALID, fn + "the count band is by bytes, without a budget or draining brokers");
     const void *outs[] = {a.n_moved, a.bytes_moved, a.peak_before, a.peak_after, a.lower_bound, a.status, a.drain, a.n_left, a.bytes_left};   // the last three: draining only
     int rc = validate_disk(fn, a.B, a.R, a.rack_of, a.P, a.W, a.rows, a.size, outs, kind.drain ? 9 : 6);
     if (rc) return rc;
+    if (kind.band) {
+        if (!a.count_range) return fail(KAO_ERR_INVALID, fn + "null pointer");
+        if (a.count_lo < 0) return fail(KAO_ERR_INVALID, fn + "count_lo < 0");
+        if (a.count_hi < a.count_lo) return fail(KAO_ERR_INVALID, fn + "count_hi < count_lo");
+    }
     DkCall c;
     c.kind = kind;
     if (kind.drain) {
@@ -956,10 +1058,12 @@ int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
     const int B = a.B, P = a.P;
     hipStream_t st = c.st;
     if (P) {
-        (kind.drain ? k_dk_init<true> : k_dk_init<false>)<<<c.pblocks, kDkThreads, 0, st>>>(n, c.d_fixed);
+        if (kind.band) k_dk_init_band<<<c.pblocks, kDkThreads, 0, st>>>(c.banded(n), c.d_fixed);
+        else (kind.drain ? k_dk_init<true> : k_dk_init<false>)<<<c.pblocks, kDkThreads, 0, st>>>(n, c.d_fixed);
         ++c.launches;
     }
-    k_dk_peak0<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_fixed, c.d_load0);
+    if (kind.band) k_dk_peak0_band<<<c.bblocks, kDkThreads, 0, st>>>(c.banded(n), c.d_fixed, c.d_load0);
+    else k_dk_peak0<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_fixed, c.d_load0);
     ++c.launches;
     HIP_TRY(hipGetLastError());
     if (P) {
@@ -967,7 +1071,8 @@ int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
         (kind.drain ? k_dk_finish<true> : k_dk_finish<false>)<<<c.pblocks, kDkThreads, 0, st>>>(n);
         ++c.launches;
     }
-    k_dk_peak1<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_load0);
+    if (kind.band) k_dk_peak1_band<<<c.bblocks, kDkThreads, 0, st>>>(c.banded(n), c.d_load0);
+    else k_dk_peak1<<<c.bblocks, kDkThreads, 0, st>>>(n, c.d_load0);
     ++c.launches;
     HIP_TRY(hipGetLastError());
     u64 ctl[D_N];
@@ -988,9 +1093,17 @@ int balance_disk(DkKind kind, const std::string &fn, const DkArgs &a) {
         *a.n_left = (int32_t)ctl[D_NLEFT];
         *a.bytes_left = ctl[D_BLEFT];
     }
+    if (kind.band) {   // {min, max} of n(b) before, then after
+        const u64 range[4] = {kDkCountTop - ctl[D_CMIN0], ctl[D_CMAX0], kDkCountTop - ctl[D_CMIN1], ctl[D_CMAX1]};
+        for (int i = 0; i < 4; ++i) a.count_range[i] = (int32_t)range[i];
+    }
     if (int64_t *stats = a.stats) {
         stats[0] = c.rounds; stats[1] = (int64_t)ctl[D_MOVES]; stats[2] = c.props; stats[3] = c.launches; stats[4] = (int64_t)ctl[D_ROWS];
         stats[5] = c.more ? 1 : 0; stats[6] = which; stats[7] = (int64_t)ctl[D_BROKERS];
+        if (kind.band) {
+            for (int i = 8; i < 12; ++i) stats[i] = 0;
+            stats[12] = (int64_t)ctl[D_OUT1]; stats[13] = (int64_t)ctl[D_OUT0];
+        }
         if (kind.exchange) {
             stats[8] = c.x_rounds; stats[9] = (int64_t)ctl[D_XCH]; stats[10] = c.x_props; stats[11] = (int64_t)ctl[D_XPEAK];
         } else if (kind.drain) {
@@ -1050,4 +1163,14 @@ extern "C" int kao_balance_disk_drain(int32_t n_brokers, int32_t n_racks, const 
     return balance_disk({false, false, false, true}, "kao_balance_disk_drain: ",
                         {n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run,
                          n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats, drain, n_left, bytes_left});
+}
+
+extern "C" int kao_balance_disk_banded(int32_t n_brokers, int32_t n_racks, const uint8_t *rack_of, int32_t n_partitions, int32_t width, uint16_t *rows,
+                                       const uint64_t *size, int32_t count_lo, int32_t count_hi, int32_t exchange, int32_t max_per_rack, int32_t move_leaders,
+                                       uint64_t min_gain, int32_t max_rounds, int32_t dry_run, int32_t *n_moved, uint64_t *bytes_moved, uint64_t *peak_before,
+                                       uint64_t *peak_after, uint64_t *lower_bound, int32_t count_range[4], int32_t *status, int64_t stats[14]) {
+    DkArgs a{n_brokers, n_racks, rack_of, n_partitions, width, rows, size, nullptr, max_per_rack, move_leaders, min_gain, UINT64_MAX, max_rounds, dry_run,
+             n_moved, bytes_moved, peak_before, peak_after, lower_bound, status, stats};
+    a.count_lo = count_lo; a.count_hi = count_hi; a.count_range = count_range;
+    return balance_disk({false, false, exchange != 0, false, true}, "kao_balance_disk_banded: ", a);
 }

@@ -22,6 +22,12 @@ whatever the gain, slot 0 and size 0 included, nothing moves onto them, and the 
 bytes only: refused together with --max-bytes, --capacities, --default-capacity and --exchange.  The report line then ends in the
 draining brokers, their bytes before and after, the drain moves and what is left, and one line follows per replica that has no
 admissible live broker; the exit status is then 3, after every file is written.
+--replica-band LO:HI keeps the number of replicas per broker inside LO..HI while the bytes are balanced (kao_balance_disk_banded,
+section 4x): no move goes onto a broker that holds HI replicas or leaves one that holds LO, so a broker outside the band may move
+toward it and never away; --count-slack K is the band floor(R/B) - K : ceil(R/B) + K for the R replicas on the B brokers of the list.
+With --exchange the exchanges, which keep every count, go on under the band.  By bytes only: refused together with --max-bytes,
+--capacities, --default-capacity and --drain, and the two flags refuse each other.  The report gains one line with the band, the
+count range and the brokers outside the band, before and after; a broker outside the band at the end is a warning, never an error.
 """
 from __future__ import annotations
 
@@ -45,6 +51,7 @@ BUDGET_STAT_KEYS = STAT_KEYS + ("refused", "budget_bound")   # kao_balance_disk_
 CAPACITY_STAT_KEYS = BUDGET_STAT_KEYS + ("thorough_rounds",)   # kao_balance_disk_capacity
 DRAIN_STAT_KEYS = STAT_KEYS + ("drain_moves", "last_drain_round")   # kao_balance_disk_drain
 EXCHANGE_STAT_KEYS = STAT_KEYS + ("exchange_rounds", "exchanges", "exchange_proposals", "peak_of_moves")   # kao_balance_disk_exchange (section 4u)
+BANDED_STAT_KEYS = EXCHANGE_STAT_KEYS + ("outside_band", "outside_band_before")   # kao_balance_disk_banded (section 4x); [8..11] are 0 without exchange
 BOUND_TERMS = ("largest_partition", "mean_load", "fixed_leaders", "integrality")
 
 
@@ -75,6 +82,11 @@ class DiskResult:
     bytes_left: Optional[int] = None
     drain_moves: Optional[int] = None        # stats[8]
     last_drain_round: Optional[int] = None   # stats[9]: the last round (from 1) that applied a drain move
+    # with count_band (kao_balance_disk_banded): stats is int64[14] (BANDED_STAT_KEYS); None otherwise
+    count_band: Optional[Tuple[int, int]] = None           # (lo, hi)
+    count_range: Optional[Tuple[int, int, int, int]] = None   # (min, max) of the replicas per broker before, then after
+    outside_band: Optional[int] = None                     # stats[12]: brokers whose count is outside the band after the call
+    outside_band_before: Optional[int] = None              # stats[13]: ... of the input
 
 
 @dataclass
@@ -155,9 +167,36 @@ def drain_flags(broker_ids: Sequence[int], drain_ids: Sequence[int]) -> np.ndarr
     return out
 
 
-def _checked_max_bytes(exchange: bool, max_bytes, capacity, drain=None) -> Optional[int]:
-    """max_bytes as the C call takes it (None without one), after the refusal of exchange together with a budget or capacities and of
-    drain together with any of the three."""
+def _band(count_band) -> Tuple[int, int]:
+    """count_band as the C call takes it: (lo, hi) integers with 0 <= lo <= hi < 2^31; a ValueError otherwise."""
+    try:
+        lo, hi = count_band
+    except (TypeError, ValueError):
+        raise ValueError("count_band must be a pair (lo, hi)")
+    if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in (lo, hi)):
+        raise ValueError("count_band: lo and hi must be integers")
+    if int(lo) < 0:
+        raise ValueError("count_band: lo must be >= 0")
+    if int(hi) < int(lo):
+        raise ValueError("count_band: hi must be >= lo")
+    return int(lo), min(int(hi), (1 << 31) - 1)
+
+
+def slack_band(n_replicas: int, n_brokers: int, slack: int) -> Tuple[int, int]:
+    """--count-slack K as a band: (max(0, floor(R / B) - K), ceil(R / B) + K) for R replicas on B brokers."""
+    if isinstance(slack, (bool, np.bool_)) or not isinstance(slack, (int, np.integer)) or int(slack) < 0:
+        raise ValueError("count_slack must be an integer >= 0")
+    if int(n_brokers) < 1:
+        raise ValueError("count_slack needs at least one broker")
+    R, B, K = int(n_replicas), int(n_brokers), int(slack)
+    return max(0, R // B - K), -(-R // B) + K
+
+
+def _checked_max_bytes(exchange: bool, max_bytes, capacity, drain=None, count_band=None) -> Optional[int]:
+    """max_bytes as the C call takes it (None without one), after the refusal of exchange together with a budget or capacities, of
+    drain together with any of the three, and of a count band together with a budget, capacities or drain."""
+    if count_band is not None and (max_bytes is not None or capacity is not None or drain is not None):
+        raise ValueError("count_band works by bytes only: not together with max_bytes, capacity or drain")
     if exchange and (max_bytes is not None or capacity is not None):
         raise ValueError("exchange=True works by bytes only: not together with max_bytes or capacity")
     if drain is not None and (exchange or max_bytes is not None or capacity is not None):
@@ -167,38 +206,44 @@ def _checked_max_bytes(exchange: bool, max_bytes, capacity, drain=None) -> Optio
 
 def balance_disk_arrays(rows, n_brokers: int, rack_of, n_racks: int, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0,
                         max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False,
-                        drain=None) -> DiskResult:
+                        drain=None, count_band=None) -> DiskResult:
     """kao_balance_disk on dense rows ([P, width], NONE-padded, slot 0 = preferred leader); size[p] is the bytes of one replica of
     row p.  With max_bytes (0..2^64-1) it is kao_balance_disk_budget: the moves copy at most that many bytes.  With capacity (one
     value >= 1 per broker index) it is kao_balance_disk_capacity: the peak of S(b) / capacity[b] is what the moves lower.  With
     exchange=True it is kao_balance_disk_exchange: exchanges go on from the move-stable state (by bytes only: a ValueError together
     with max_bytes or capacity).  With drain (one flag per broker index, != 0: this broker is to end empty) it is
-    kao_balance_disk_drain (a ValueError together with any of the other three, or with every flag set)."""
-    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity, drain)
+    kao_balance_disk_drain (a ValueError together with any of the other three, or with every flag set).  With count_band=(lo, hi) it
+    is kao_balance_disk_banded, with or without exchange: the replicas per broker stay inside the band (a ValueError together with
+    max_bytes, capacity or drain, for lo < 0 or hi < lo)."""
+    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity, drain, count_band)
+    band = None if count_band is None else _band(count_band)
     cbuf = None if capacity is None else _capacity_buffer(capacity, n_brokers)
     dbuf = None if drain is None else _drain_buffer(drain, n_brokers)
     r, flat, P, W = dense_rows(rows)
     rk = _rack_buffer(rack_of, n_brokers)
     sbuf = weight_buffer(size, P, min_gain)
-    name, n_stats, extra = (("kao_balance_disk_capacity", 11, [(1 << 64) - 1 if max_bytes is None else max_bytes]) if cbuf is not None   # with or without a budget
+    name, n_stats, extra = (("kao_balance_disk_banded", 14, []) if band is not None else ("kao_balance_disk_capacity", 11, [(1 << 64) - 1 if max_bytes is None else max_bytes]) if cbuf is not None   # with or without a budget
                             else ("kao_balance_disk_exchange", 12, []) if exchange else ("kao_balance_disk_drain", 10, []) if dbuf is not None
                             else ("kao_balance_disk", 8, []) if max_bytes is None
                             else ("kao_balance_disk_budget", 10, [max_bytes]))
     stats = np.zeros(n_stats, dtype=np.int64)
     n, status, moved, n_left, bytes_left = C.c_int32(0), C.c_int32(0), C.c_uint64(0), C.c_int32(0), C.c_uint64(0)
+    counts = (C.c_int32 * 4)()
     before, after, bound = ((C.c_uint64 * 2)() for _ in range(3))   # {numerator, denominator} by utilisation; the calls by bytes write the first word only
     head = [int(n_brokers), int(n_racks), rk.ctypes.data_as(C.POINTER(C.c_uint8)), int(P), int(W), flat.ctypes.data_as(C.POINTER(C.c_uint16)),
             sbuf.ctypes.data_as(C.POINTER(C.c_uint64))] + ([] if cbuf is None else [cbuf.ctypes.data_as(C.POINTER(C.c_uint64))]) \
-        + ([] if dbuf is None else [dbuf.ctypes.data_as(C.POINTER(C.c_uint8))])
+        + ([] if dbuf is None else [dbuf.ctypes.data_as(C.POINTER(C.c_uint8))]) + ([] if band is None else [band[0], band[1], int(bool(exchange))])
     tail = [int(max_rounds), int(bool(dry_run)), C.byref(n), C.byref(moved), before, after, bound] + ([] if dbuf is None else [C.byref(n_left), C.byref(bytes_left)]) \
-        + [C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))]
+        + ([] if band is None else [counts]) + [C.byref(status), stats.ctypes.data_as(C.POINTER(C.c_int64))]
     _check(getattr(_ffi.load(), name)(*head, int(max_per_rack), int(bool(move_leaders)), int(min_gain), *extra, *tail), name)
     more = {}
     if cbuf is not None:
         more = dict(peak_before_capacity=int(before[1]), peak_after_capacity=int(after[1]), lower_bound_den=int(bound[1]))
-    elif exchange:
-        more = dict(exchange_rounds=int(stats[8]), exchanges=int(stats[9]), exchange_proposals=int(stats[10]), peak_of_moves=int(stats[11]))
-    elif dbuf is not None:
+    if band is not None:
+        more = dict(count_band=band, count_range=tuple(int(v) for v in counts), outside_band=int(stats[12]), outside_band_before=int(stats[13]))
+    if cbuf is None and exchange:
+        more.update(exchange_rounds=int(stats[8]), exchanges=int(stats[9]), exchange_proposals=int(stats[10]), peak_of_moves=int(stats[11]))
+    if dbuf is not None:
         more = dict(drain=dbuf, n_left=int(n_left.value), bytes_left=int(bytes_left.value), drain_moves=int(stats[8]), last_drain_round=int(stats[9]))
     return DiskResult(rows=r, n_moved=int(n.value), bytes_moved=int(moved.value), peak_before=int(before[0]), peak_after=int(after[0]),
                       lower_bound=int(bound[0]), status=STATUS_NAMES[int(status.value)], stats=stats, max_bytes=max_bytes, **more)
@@ -234,12 +279,13 @@ def sizes_of(keys, sizes: Dict[Tuple[str, int], int], default_size: Optional[int
 
 
 def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0,
-               dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False, drain=None) -> DiskPlan:
+               dry_run: bool = False, max_bytes: Optional[int] = None, capacity=None, exchange: bool = False, drain=None, count_band=None) -> DiskPlan:
     """kao_balance_disk on a FailoverInput, size[p] per row of it; the entries are the rows that changed (none with dry_run).  With
     max_bytes it is kao_balance_disk_budget; with capacity (per broker index of fi) kao_balance_disk_capacity; with exchange
-    kao_balance_disk_exchange; with drain (flags per broker index of fi) kao_balance_disk_drain."""
+    kao_balance_disk_exchange; with drain (flags per broker index of fi) kao_balance_disk_drain; with count_band (lo, hi)
+    kao_balance_disk_banded."""
     res = balance_disk_arrays(fi.rows, len(fi.broker_ids), fi.rack_of, len(fi.rack_names), size, max_per_rack, move_leaders, min_gain, max_rounds,
-                              dry_run, max_bytes, capacity, exchange, drain)
+                              dry_run, max_bytes, capacity, exchange, drain, count_band)
     changed = np.nonzero((res.rows != fi.rows).any(axis=1))[0]
     entries = [(fi.keys[p][0], fi.keys[p][1], [int(fi.broker_ids[b]) for b in res.rows[p] if b != NONE]) for p in changed]
     left = []
@@ -250,7 +296,8 @@ def plan_input(fi: FailoverInput, size, max_per_rack: int = 0, move_leaders: boo
 
 def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, default_size: Optional[int] = None, max_per_rack: int = 0,
                  move_leaders: bool = True, min_gain: int = 0, max_rounds: int = 0, dry_run: bool = False, max_bytes: Optional[int] = None,
-                 capacity=None, default_capacity: Optional[int] = None, exchange: bool = False, drain: Optional[Sequence[int]] = None) -> DiskPlan:
+                 capacity=None, default_capacity: Optional[int] = None, exchange: bool = False, drain: Optional[Sequence[int]] = None,
+                 count_band=None, count_slack: Optional[int] = None) -> DiskPlan:
     """kao_balance_disk on a reassignment document with `broker_list` and `racks` ({broker id: rack name}).  `sizes` is
     {(topic, partition): bytes}, or a kafka-log-dirs / sizes document or text (waves.parse_sizes).  plan.document is the
     reassignment document of the changed rows.  With max_bytes the moves copy at most that many bytes (kao_balance_disk_budget).
@@ -258,9 +305,17 @@ def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, d
     `broker_list`, the moves lower the peak utilisation (kao_balance_disk_capacity).  With exchange=True exchanges go on from the
     move-stable state (kao_balance_disk_exchange; a ValueError together with max_bytes or capacity).  With drain, the ids of brokers of
     `broker_list` that are to end empty, it is kao_balance_disk_drain (a ValueError together with any of the other three, for an id
-    outside the list, a duplicate, or every broker)."""
+    outside the list, a duplicate, or every broker).  With count_band=(lo, hi), or count_slack=K for the band slack_band gives for the
+    replicas of `doc` on `broker_list`, it is kao_balance_disk_banded, with or without exchange (a ValueError for both at once, or
+    together with max_bytes, capacity or drain)."""
     from .waves import parse_sizes
-    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity, drain)
+    if count_band is not None and count_slack is not None:
+        raise ValueError("count_band and count_slack: give one of the two")
+    if count_slack is not None:
+        slack_band(0, 1, count_slack)   # the refusal, before anything else is read
+    max_bytes = _checked_max_bytes(exchange, max_bytes, capacity, drain, count_band if count_slack is None else (0, 0))
+    if count_band is not None:
+        count_band = _band(count_band)
     if drain is not None:
         drain_flags(broker_list, drain)   # the refusals, before anything else is read
     fi = parse_current(doc, broker_list, racks)
@@ -269,7 +324,10 @@ def balance_disk(doc: dict, sizes, *, broker_list: Sequence[int], racks: dict, d
         capacity = capacity_of(fi.broker_ids, capacity, default_capacity)
     if not (isinstance(sizes, dict) and all(isinstance(k, tuple) for k in sizes)):
         sizes = parse_sizes(sizes)
-    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes, capacity, exchange, flags)
+    if count_slack is not None:
+        count_band = slack_band(int((fi.rows != NONE).sum()), len(fi.broker_ids), count_slack)
+    return plan_input(fi, sizes_of(fi.keys, sizes, default_size), max_per_rack, move_leaders, min_gain, max_rounds, dry_run, max_bytes, capacity, exchange, flags,
+                      count_band)
 
 
 def report_lines(plan: DiskPlan) -> List[str]:
@@ -283,6 +341,10 @@ def report_lines(plan: DiskPlan) -> List[str]:
         tail = [f" draining={','.join(str(b) for b in ids)} drain_bytes_before={before} drain_bytes_after={res.bytes_left} drain_moves={res.drain_moves} "
                 f"last_drain_round={res.last_drain_round} replicas_left={res.n_left} bytes_left={res.bytes_left}"]
         tail += [f"disk: left {t}-{p} broker={b} reason={why}" for t, p, b, why in plan.left]
+    if res.count_band is not None:   # one line of its own: the band, the count range and the brokers outside the band, before -> after
+        r = res.count_range
+        tail = ["", f"disk: replica_band={res.count_band[0]}:{res.count_band[1]} counts_before={r[0]}..{r[1]} counts_after={r[2]}..{r[3]} "
+                f"outside_before={res.outside_band_before} outside_after={res.outside_band}"]
     return _with_tail([f"disk: status={res.status} peak_before={res.peak_before} peak_after={res.peak_after} lower_bound={res.lower_bound} "
             f"bound_term={BOUND_TERMS[int(s[6])]} replicas_moved={res.n_moved} bytes_moved={res.bytes_moved} bytes_total={total} "
             f"rows_changed={s[4]} brokers_changed={s[7]} rounds={s[0]} moves={s[1]} launches={s[3]}"
@@ -329,6 +391,9 @@ def main(argv=None) -> int:
                     "(not with --max-bytes, --capacities or --default-capacity)")
     ap.add_argument("--drain", default=None, help="brokers of --broker-list that are to end empty, CSV (not with --max-bytes, --capacities, --default-capacity "
                     "or --exchange); exit status 3 when a replica has no admissible live broker and stays")
+    ap.add_argument("--replica-band", default=None, help="LO:HI: the replicas per broker stay inside LO..HI (not with --max-bytes, --capacities, --default-capacity, "
+                    "--drain or --count-slack)")
+    ap.add_argument("--count-slack", default=None, help="K: the band floor(R/B)-K : ceil(R/B)+K for the R replicas on the B brokers of the list")
     ap.add_argument("--dry-run", action="store_true", help="report only: the plan stays empty")
     ap.add_argument("--out", required=True)
     ap.add_argument("--report", action="store_true")
@@ -339,6 +404,23 @@ def main(argv=None) -> int:
         ap.error("--exchange works by bytes only: not together with --max-bytes, --capacities or --default-capacity")
     if a.drain is not None and (a.exchange or a.max_bytes is not None or a.capacities is not None or a.default_capacity is not None):
         ap.error("--drain works by bytes only: not together with --max-bytes, --capacities, --default-capacity or --exchange")
+    band, slack = None, None
+    for flag, value in (("--replica-band", a.replica_band), ("--count-slack", a.count_slack)):
+        if value is not None and (a.max_bytes is not None or a.capacities is not None or a.default_capacity is not None or a.drain is not None):
+            ap.error(f"{flag} works by bytes only: not together with --max-bytes, --capacities, --default-capacity or --drain")
+    if a.replica_band is not None and a.count_slack is not None:
+        ap.error("--replica-band and --count-slack: give one of the two")
+    if a.replica_band is not None:
+        lo, sep, hi = a.replica_band.partition(":")
+        if not sep or not lo.isdigit() or not hi.isdigit() or len(lo) > 9 or len(hi) > 9:
+            ap.error("--replica-band needs LO:HI, two counts")
+        if int(hi) < int(lo):
+            ap.error("--replica-band: HI is below LO")
+        band = (int(lo), int(hi))
+    if a.count_slack is not None:
+        if not a.count_slack.isdigit() or len(a.count_slack) > 9:
+            ap.error("--count-slack needs a count")
+        slack = int(a.count_slack)
     try:
         if a.drain is not None:   # an unknown id, a duplicate or every broker is a usage error
             ids = [t.strip() for t in a.drain.split(",") if t.strip()]
@@ -374,10 +456,14 @@ def main(argv=None) -> int:
         drain = None if drain_ids is None else drain_flags(fi.broker_ids, drain_ids)   # over the index the rows use
         from .solver import init
         init(a.device)
-        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes, capacity, a.exchange, drain)
+        if slack is not None:
+            band = slack_band(int((fi.rows != NONE).sum()), len(fi.broker_ids), slack)
+        plan = plan_input(fi, size, a.max_per_rack, not a.keep_leaders, min_gain, a.max_rounds, a.dry_run, max_bytes, capacity, a.exchange, drain, band)
         if a.report:
             for line in report_lines(plan):
                 print(line, file=sys.stderr)
+        if plan.result.outside_band:   # the band never forced anything: a warning, status 0
+            print(f"kao-disk: warning: {plan.result.outside_band} brokers hold a replica count outside the band {band[0]}:{band[1]}", file=sys.stderr)
         with open(a.out, "w") as f:
             f.write(plan_text(plan.entries))
     except Exception as e:  # noqa: BLE001 -- reported, exit status 1

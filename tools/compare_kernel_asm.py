@@ -8,7 +8,10 @@ A kernel is the text from its label to the end of its function: the instructions
 Comments, blank lines, .file / .ident lines and the __hip_cuid_* symbol are ignored, and the function number in local labels (.LBB12_3 ->
 .LBB_3) is dropped, so a kernel may move between translation units.  A kernel of an unnamed namespace that several files define (a
 shared header) is compared per file.  Exit status 0 iff both sides hold the same kernel names and every
-kernel compares equal."""
+kernel compares equal.
+
+A template that gains a defaulted parameter renames its old instantiations; --rename REGEX REPLACEMENT (repeatable) rewrites the text of
+the NEW side first, so that they are compared under the names they had."""
 import argparse
 import os
 import re
@@ -18,10 +21,13 @@ LABEL = re.compile(r"^(_Z\w+):")
 LOCAL = re.compile(r"\.L(BB|func_end|func_begin|post_getpc|JTI|CPI|tmp)(\d+)")
 
 
-def kernels(paths):
+def kernels(paths, renames=()):
     found = []
     for path in paths:
-        lines = open(path).read().split("\n")
+        text = open(path).read()
+        for pattern, repl in renames:
+            text = re.sub(pattern, repl, text)
+        lines = text.split("\n")
         names = {m.group(1) for m in (re.match(r"\s*\.amdhsa_kernel\s+(\S+)", l) for l in lines) if m}
         name, body = None, []
         for line in lines:
@@ -52,8 +58,9 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--old", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
+    ap.add_argument("--rename", nargs=2, action="append", default=[], metavar=("REGEX", "REPLACEMENT"), help="rewrite the NEW side's text before comparing")
     a = ap.parse_args()
-    old, new = kernels(a.old), kernels(a.new)
+    old, new = kernels(a.old), kernels(a.new, a.rename)
     bad = 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:

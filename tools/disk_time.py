@@ -22,7 +22,15 @@ over its rounds).  --write appends the lines to profiles/disk_x_time.txt.  --max
 --drain N[,N..] times kao_balance_disk and kao_balance_disk_drain in one process on the same rows, the N
 heaviest brokers draining, once per N.  A line carries the draining brokers' largest replica count (stats[9] is at least that), the
 rounds, drain moves (stats[8]), the last round with a drain move (stats[9]), what is left, peak / bound, bytes moved and, as plain call
--> this call, rounds, launches and wall time.  --write appends the lines to profiles/disk_drain_time.txt."""
+-> this call, rounds, launches and wall time.  --write appends the lines to profiles/disk_drain_time.txt.
+--band LO:HI|slack=K[,...] times kao_balance_disk (kao_balance_disk_exchange with --exchange) and kao_balance_disk_banded (DESIGN.md
+section 4x) in one process on the same rows, once per band.  Its cases are COUNT-BALANCED starts (tests/disk_band_ref.py's
+balanced_case: every broker holds the same number of replicas): `balanced500` (500 brokers x 10,000 partitions, RF 3, no rack rule, 60
+replicas each) and `balanced1000` (1000 x 100,000, RF 3, 10 racks, max_per_rack 1, 300 each).  slack=K is the band of kao-disk
+--count-slack K (slack=0 is the exact band); a band no count reaches, 0:1000000, is the control: its time against the call without a
+band is what the band's own loads and stores cost.  A line carries, as call without a band -> banded call: peak / bound, rounds,
+moves, exchanges, bytes copied, wall time and microseconds per round with their ratio; and the count range before -> after and the
+brokers outside the band.  --write appends the lines to profiles/disk_band_time.txt."""
 import argparse
 import json
 import os
@@ -44,6 +52,7 @@ def main():
     ap.add_argument("--capacity", default=None, choices=["4:1", "equal"], help="times kao_balance_disk_capacity with this capacity vector")
     ap.add_argument("--exchange", action="store_true", help="times kao_balance_disk and kao_balance_disk_exchange side by side")
     ap.add_argument("--drain", default=None, help="CSV of N: times kao_balance_disk and kao_balance_disk_drain side by side, the N heaviest brokers draining")
+    ap.add_argument("--band", default=None, help="CSV of LO:HI or slack=K: times the call without a band and kao_balance_disk_banded side by side on count-balanced starts")
     ap.add_argument("--max-rounds", type=int, default=0)
     ap.add_argument("--write", action="store_true", help="write the lines to profiles/disk_time.txt (disk_budget_time.txt with --max-bytes-pct) as well")
     a = ap.parse_args()
@@ -57,17 +66,25 @@ def main():
         rng = np.random.default_rng(seed)
         return np.maximum(1, np.round(np.exp(rng.normal(np.log(2.0 ** 20), sigma, P)))).astype(np.int64)
 
-    def timed(rows, B, rack_of, R, size, cap, max_bytes, capacity=None, exchange=False, drain=None):
+    def timed(rows, B, rack_of, R, size, cap, max_bytes, capacity=None, exchange=False, drain=None, count_band=None):
         args = (rows, B, rack_of, R, size, cap, not a.keep_leaders, 0, a.max_rounds)
-        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange, drain=drain)   # warm-up
+        res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange, drain=drain, count_band=count_band)   # warm-up
         ms = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange, drain=drain)
+            res = balance_disk_arrays(*args, dry_run=True, max_bytes=max_bytes, capacity=capacity, exchange=exchange, drain=drain, count_band=count_band)
             ms.append(round(1e3 * (time.perf_counter() - t0), 3))
         return res, ms
 
     cases = {}   # name -> rows, B, rack_of, R, max_per_rack
+    if a.band is not None:   # count-balanced starts only
+        import disk_band_ref as db
+        from kafka_assignment_optimizer_amd.disk import slack_band
+        for name, (B, P, R, cap) in (("balanced500", (500, 10000, 1, 0)), ("balanced1000", (1000, 100000, 10, 1))):
+            if a.cases in ("config4,large", "") or name in a.cases.split(","):
+                c = db.balanced_case(B, P, 3, 0.7, 7, R=R)   # (the sizes are drawn per sigma below)
+                cases[name] = (c["rows"], B, c["rack_of"].astype(np.uint8), R, cap)
+        a.cases = ""
     if "config4" in a.cases:
         topics = lr.config4_topics()
         cases["config4"] = (np.concatenate([np.asarray(t.current, dtype=np.int64) for t in topics]), topics[0].n_brokers,
@@ -85,6 +102,31 @@ def main():
         for sigma in (float(s) for s in a.sigmas.split(",")):
             size = sizes(len(rows), sigma, 11)
             total = int((size[:, None] * (rows != 0xFFFF)).sum())
+            if a.band is not None:
+                plain, pms = timed(rows, B, rack_of, R, size, cap, None, exchange=a.exchange)
+                pm = float(np.median(pms))
+                for text in a.band.split(","):
+                    band = slack_band(int((rows != 0xFFFF).sum()), B, int(text[6:])) if text.startswith("slack=") else tuple(int(v) for v in text.split(":"))
+                    res, bms = timed(rows, B, rack_of, R, size, cap, None, exchange=a.exchange, count_band=band)
+                    bm = float(np.median(bms))
+                    lb = max(res.lower_bound, 1)
+                    us = [round(1e3 * pm / max(int(plain.stats[0]), 1), 2), round(1e3 * bm / max(int(res.stats[0]), 1), 2)]
+                    line = {"workload": name, "sigma": sigma, "brokers": B, "racks": R, "partitions": len(rows), "max_per_rack": cap, "move_leaders": not a.keep_leaders,
+                            "max_rounds": a.max_rounds, "exchange": a.exchange, "band": text, "count_band": list(band), "count_range": list(res.count_range),
+                            "outside_band": [res.outside_band_before, res.outside_band], "status": res.status, "lower_bound": res.lower_bound, "peak_before": res.peak_before,
+                            "peak_after": [plain.peak_after, res.peak_after], "peak_over_bound": [round(plain.peak_after / lb, 5), round(res.peak_after / lb, 5)],
+                            "rounds": [int(plain.stats[0]), int(res.stats[0])], "moves": [int(plain.stats[1]), int(res.stats[1])],
+                            "exchanges": [int(plain.stats[9]) if a.exchange else 0, int(res.stats[9])], "replicas_moved": [plain.n_moved, res.n_moved],
+                            "bytes_moved": [plain.bytes_moved, res.bytes_moved], "gib_moved": [round(plain.bytes_moved / 2 ** 30, 2), round(res.bytes_moved / 2 ** 30, 2)],
+                            "bytes_total": total, "launches": [int(plain.stats[3]), int(res.stats[3])], "stopped_by_max_rounds": [int(plain.stats[5]), int(res.stats[5])],
+                            "wall_ms_median": [round(pm, 3), round(bm, 3)], "wall_ms": [pms, bms], "us_per_round": us,
+                            "us_per_round_ratio": round(us[1] / us[0], 3) if us[0] and int(res.stats[0]) else None}
+                    lines.append(json.dumps(line))
+                    print(lines[-1], flush=True)
+                    if a.write:
+                        with open(os.path.join(ROOT, "profiles", "disk_band_time.txt"), "a") as f:
+                            f.write(lines[-1] + "\n")
+                continue
             if a.drain is not None:
                 plain, pms = timed(rows, B, rack_of, R, size, cap, None)
                 S = np.zeros(B, dtype=np.int64)
@@ -163,7 +205,7 @@ def main():
                     line["wall_ms"] = ms
                 lines.append(json.dumps(line))
                 print(lines[-1], flush=True)
-    if a.write and not a.exchange and a.drain is None:
+    if a.write and not a.exchange and a.drain is None and a.band is None:
         name = "disk_capacity_time.txt" if a.capacity is not None else "disk_time.txt" if a.max_bytes_pct is None else "disk_budget_time.txt"
         with open(os.path.join(ROOT, "profiles", name), "w") as f:
             f.write("\n".join(lines) + "\n")
